@@ -7,8 +7,14 @@ weights.  One message update = one executed receive or send.  Inp
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 1024] [--labels 32]
-                    [--order colour_major|row_major] [--no-cpu-baseline]
+                    [--order colour_major|row_major] [--no-cpu-baseline] [--full] [--dump-outputs DIR]
                     [--workload c3|c4|c5] [--partitioner auto|metis|builtin] [--partition-file F]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  Everything
+else the line can carry runs only with --full, after the timed region: the oracle check against tests/golden/, the
+event-timed roofline leg, the primal-rounding pass, the CPU baseline, and on several ranks the dual-bound gap, the
+per-rank probe leg and the scaling model.  --dump-outputs DIR writes what the last timed step left (a fixed sample of the
+duals and the lower bound) as .npy files.
 
 N > 1: one process per GPU (self-launched, or under torch.distributed.run).  Every wait of the start-up is bounded: the rendezvous
 (--rendezvous-timeout), one all_reduce and one all_to_all_single with the real split sizes before the timed region
@@ -30,6 +36,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_STREAM_GBS = 6290.0  # what a copy kernel streams from HBM on this chip (same guide; r01 copy probe agrees)
+DUMP_MAX_ENTRIES = 1 << 21   # --dump-outputs: float64 duals written in full up to this count, else a sample of it (+ its positions)
 
 
 def parse():
@@ -93,7 +100,7 @@ def parse():
                          "the unpartitioned sweep bit for bit, gap 0 (overlap.py); 'lockstep' = the parts run the unpartitioned sweep level "
                          "by level with halo copies in between (lockstep.py; gap 0, one exchange per dependent level that reads across the "
                          "cut; any graph); 'boundary' = every part sweeps its own sub-problem, cut messages reconciled in a boundary step "
-                         "(multi_gpu.py; a dual-bound gap of 0.1 - 2 %, few exchanges).  auto: overlap for colour-major grids, lockstep otherwise "
+                         "(multi_gpu.py; a dual-bound gap of 0.1 - 2 %%, few exchanges).  auto: overlap for colour-major grids, lockstep otherwise "
                          "(the exact schedules; C4 at full size in 8 parts: lock step 2.6 ms per pass and part, boundary steps 4.0)")
     ap.add_argument("--ghost-rows", type=int, default=12, help="overlap schedule: rows of each neighbour a rank holds (even; n passes between exchanges need 2 n + 2)")
     ap.add_argument("--rows-layout", default="auto", choices=["auto", "on", "off"],
@@ -114,6 +121,12 @@ def parse():
                     help="--gpus N without a launcher: print the rank processes that WOULD be started (command, environment) as one "
                          "JSON object and exit; nothing touches a GPU (tests/test_bench_contract.py)")
     ap.add_argument("--launch-timeout", type=float, default=3600.0, help="self-launched ranks: give up after this many seconds (0: never)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (oracle check, roofline leg, rounding pass, CPU baseline; several "
+                         "ranks: dual-bound gap, per-rank probe leg, scaling model) — off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/<name>.npy (float64): the lower bound, and the duals "
+                         "(all of them up to %d entries, else a fixed seeded sample plus the sampled positions; 64 MB at most)" % DUMP_MAX_ENTRIES)
     ap.add_argument("--prewarm-ms", type=float, default=0.0,
                     help="untimed passes (prewarm_ms / 8 of them) before the W warmup steps so that clocks and "
                          "power state have settled; 0 disables")
@@ -586,6 +599,39 @@ def golden_check_c5(torch, dist, args, runner, lb):
             "fixture": "tests/golden/c5_small.npz (oracle/lpmp_oracle.c on the same model, tests/golden/make_c5_small.py)"}
 
 
+def dump_outputs(out_dir, torch, eng, dual, lb, rank, world):
+    """--dump-outputs: what the last timed step left, as a caller of the timed path receives it — the lower bound
+    (lower_bound.npy) and the packed duals (duals.npy, float64).  More than DUMP_MAX_ENTRIES duals: a sample at positions drawn
+    with a fixed seed (duals_index.npy, as float64), the same positions on every run of the same arguments.  Several ranks: the
+    global bound and rank 0's own part.  ``dual``: the engine's dual buffer on the device when the caller holds it (C3 on one
+    GPU), else the duals are downloaded.  Returns what the line says about the files."""
+    import numpy as np
+    eng.synchronize()                                # (rows layout: the packed dual buffer is written out here)
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    host = None
+    if dual is None:
+        host = eng.download_duals()
+    n = int(dual.numel()) if dual is not None else int(host.shape[0])
+    idx = None
+    if n > DUMP_MAX_ENTRIES:
+        idx = np.unique(np.random.default_rng(12345).integers(0, n, DUMP_MAX_ENTRIES, dtype=np.int64))
+    if dual is not None:
+        sel = dual if idx is None else dual[torch.from_numpy(idx).to(dual.device)]
+        d = sel.double().cpu().numpy()
+    else:
+        d = host if idx is None else host[idx]
+    files = {"lower_bound": np.array([lb], np.float64), "duals": np.ascontiguousarray(d, np.float64)}
+    if idx is not None:
+        files["duals_index"] = idx.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in files), "n_duals": n,
+            "duals": "all" if idx is None else f"{idx.shape[0]} positions drawn with a fixed seed (duals_index.npy)",
+            "part": "rank 0's part of the duals, the global lower bound" if world > 1 else None}
+
+
 def hbm_min_bytes_per_pass(runner, args, world, bytes_per_pass, updates_per_pass, L):
     """Least HBM traffic of one pass: SURVEY 8(d) counts a dense table once per receive (8 L^2 per message and pass, two
     reads of every table per anisotropic pass); if every second read were served on-die, HBM would still deliver every
@@ -675,8 +721,19 @@ def rank_commands(args, argv, port):
         env = {"RANK": str(r), "LOCAL_RANK": str(r), "WORLD_SIZE": str(args.gpus), "LOCAL_WORLD_SIZE": str(args.gpus),
                "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "LPMP_BENCH_SELF_LAUNCHED": "1",
                "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")}
-        cmds.append({"argv": [sys.executable, os.path.abspath(__file__)] + [a for a in argv if a != "--dry-run-launch"], "env": env})
+        cmds.append({"argv": [sys.executable, os.path.abspath(__file__)] + [a for a in abs_dump_dir(argv) if a != "--dry-run-launch"], "env": env})
     return cmds
+
+
+def abs_dump_dir(argv):
+    """--dump-outputs DIR names a directory relative to the caller's; the rank processes run in the repository root"""
+    out = list(argv)
+    for i, a in enumerate(out):
+        if a == "--dump-outputs" and i + 1 < len(out):
+            out[i + 1] = os.path.abspath(out[i + 1])
+        elif a.startswith("--dump-outputs="):
+            out[i] = "--dump-outputs=" + os.path.abspath(a.split("=", 1)[1])
+    return out
 
 
 def launch_ranks(args, argv):
@@ -922,30 +979,35 @@ def main():
     # (tests/golden/make_c3_full.py, seed 1); its lower bound and the checksums of its packed duals after the same
     # number of passes are compared with the state the timed passes left in HBM
     oracle_check = None
-    if not dist_on and args.workload == "c3":
+    if args.full and not dist_on and args.workload == "c3":
         eng.synchronize()                            # (rows layout: the packed dual buffer is written out here)
         oracle_check = golden_check(torch, args, dual, lb1)
-    if args.workload == "c5" and args.c5_small:
+    if args.full and args.workload == "c5" and args.c5_small:
         oracle_check = golden_check_c5(torch, dist if dist_on else None, args, runner, lb1)
+    # what the last timed step left, before any later leg runs more passes on the same duals
+    dumped = dump_outputs(args.dump_outputs, torch, eng, dual if not dist_on and args.workload == "c3" else None, lb1, rank, world) \
+        if args.dump_outputs else None
 
     # roofline leg: the same passes again with every launch bracketed by HIP events on the engine's stream
-    eng.reset_kernel_timing()
-    eng.enable_kernel_timing(True)
-    runner.compute_pass(args.steps)
-    torch.cuda.synchronize()
-    kt = eng.kernel_timing()
-    eng.enable_kernel_timing(False)
+    kt = None
+    if args.full:
+        eng.reset_kernel_timing()
+        eng.enable_kernel_timing(True)
+        runner.compute_pass(args.steps)
+        torch.cuda.synchronize()
+        kt = eng.kernel_timing()
+        eng.enable_kernel_timing(False)
 
     # several ranks: the same passes once more with every exchange bracketed by events — where the time of a pass goes, per rank
     rank_stats = model_line = None
-    if dist_on:
+    if dist_on and args.full:
         rank_stats = rank_stats_leg(torch, dist, runner, args.steps)
         model_line = scaling_model(args, world, rank_stats, dt / args.steps * 1e3, shared_device)
 
     # outside the timed region: one pass with primal rounding (what MpRoundingSolver runs every 5th iteration,
     # reference solver.hxx:387-397) and LP::EvaluatePrimal
     rounding = None
-    if not dist_on and args.workload == "c3":
+    if args.full and not dist_on and args.workload == "c3":
         # what a DEFAULT MpRoundingSolver run executes on every 5th iteration (standard_visitor.hxx:37,172-185): the visitor
         # switches to roundingReparametrization = damped_uniform (every message received and sent in EACH direction:
         # 2x the message updates of an anisotropic pass), then forward-and-primal, EvaluatePrimal,
@@ -980,7 +1042,12 @@ def main():
         rounding["ms_pass_and_primal_" + args.mode] = (time.perf_counter() - t0) * 1e3
 
     gap_fn = {"c3": dual_bound_gap, "c4": dual_bound_gap_c4, "c5": dual_bound_gap_c5}[args.workload]
-    gap = gap_fn(torch, dist, args, mode, world, rank) if dist_on else {"dual_bound_gap": 0.0, "gap_config": "1 GPU: the unpartitioned sweep itself"}
+    if not dist_on:
+        gap = {"dual_bound_gap": 0.0, "gap_config": "1 GPU: the unpartitioned sweep itself"}
+    elif args.full:
+        gap = gap_fn(torch, dist, args, mode, world, rank)
+    else:
+        gap = {"dual_bound_gap": None, "gap_config": "not measured (the gap leg runs with --full)"}
     # the other multi-GPU schedules on the same strips, same pass count (outside the timed region): what the choice costs
     schedules = None
     peak_bytes = torch.cuda.max_memory_allocated()
@@ -1093,6 +1160,7 @@ def main():
             "setup_s": setup, "peak_device_memory_GB_rank0": peak_bytes / 1e9,
             "lower_bound_before": lb0, "lower_bound_after": lb1,
             "oracle_check": oracle_check,
+            "full": bool(args.full), "outputs": dumped,
             "dual_bound_gap": gap["dual_bound_gap"], "dual_bound_gap_detail": gap, "schedule": args.schedule if dist_on else None,
             "overlap_exchange": bool(args.overlap_exchange) if dist_on and args.schedule == "lockstep" else None,
             "schedules": schedules,
@@ -1113,7 +1181,7 @@ def main():
             "rounding": rounding,
             "roofline": roof,
         }
-        if not args.no_cpu_baseline and world == 1:      # (the contract: the CPU baseline is timed on rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:      # (the contract: the CPU baseline is timed on rank 0 at N = 1 only)
             out["cpu_baseline"] = cpu_baseline(args, S, M)
     if not dist_on and args.workload == "c3" and args.also_row_major and args.order != "row_major":
         del eng, runner

@@ -71,7 +71,7 @@ def test_running_library_reports_the_hash_of_its_sources():
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "128", "--steps", "3", "--warmup", "1",
-                                   "--cpu-sample-grid", "16"], text=True, cwd=ROOT, timeout=600)
+                                   "--cpu-sample-grid", "16", "--full"], text=True, cwd=ROOT, timeout=600)
     d = json.loads([l for l in out.strip().splitlines() if l.startswith('{"metric"')][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -93,7 +93,7 @@ def test_bench_row_major_order_runs_the_mailbox_chain():
     message vectors over through the mailbox; the line carries the same contract, and the bound of the colour-major default
     at the same pass count is a different one (another sweep order)"""
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "128", "--order", "row_major", "--steps", "3",
-                                   "--warmup", "1", "--no-cpu-baseline"], text=True, cwd=ROOT, timeout=600)
+                                   "--warmup", "1", "--no-cpu-baseline", "--full"], text=True, cwd=ROOT, timeout=600)
     d = json.loads([l for l in out.strip().splitlines() if l.startswith('{"metric"')][-1])
     assert d["config"]["levels_per_direction"] == [255, 255] and "row_major" in d["config"]["workload"]
     assert d["value"] > 0 and d["lower_bound_after"] > d["lower_bound_before"] and d["rounding"]["primal_cost"] >= d["rounding"]["lower_bound"]
@@ -126,7 +126,7 @@ def test_bench_distributed_branch_on_rccl_at_world_size_one(workload, schedule):
     env.pop("LPMP_DIST_BACKEND", None)
     extra = ["--grid", "128"] if workload == "c3" else ["--workload", "c4", "--c4-nodes", "20000", "--c4-edges", "100000"]
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1",
-                                   "--no-cpu-baseline", "--schedule", schedule] + extra, text=True, cwd=ROOT, timeout=900, env=env)
+                                   "--no-cpu-baseline", "--full", "--schedule", schedule] + extra, text=True, cwd=ROOT, timeout=900, env=env)
     # the line the driver parses is the last thing on stdout (RCCL's version banner, buffered by C stdio, must not trail it)
     assert out.strip().splitlines()[-1].startswith('{"metric"'), out[-600:]
     d = json.loads([l for l in out.strip().splitlines() if l.startswith('{"metric"')][-1])
@@ -142,6 +142,85 @@ def test_default_multi_gpu_schedule_is_always_an_exact_one():
     assert bench.auto_schedule(_args(workload="c3", order="row_major")) == "lockstep"
     assert bench.auto_schedule(_args(workload="c3", grid=1023)) == "lockstep"
     assert bench.auto_schedule(_args(workload="c4")) == "lockstep"
+
+
+# ---- a plain run (the headline figure only) and --dump-outputs ---------------------------------------------------------------------
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    # self-launched ranks run in the repository root: a relative DIR is resolved against the caller's directory first
+    cmds = bench.rank_commands(types.SimpleNamespace(gpus=2), ["--gpus", "2", "--dump-outputs", "out", "--full"], 29999)
+    assert all(c["argv"][2:] == ["--gpus", "2", "--dump-outputs", os.path.abspath("out"), "--full"] for c in cmds)
+
+
+class _FakeEngine:
+    def __init__(self, duals):
+        self.duals, self.synced = duals, 0
+
+    def synchronize(self):
+        self.synced += 1
+
+    def download_duals(self):
+        return self.duals.copy()
+
+
+def test_dump_outputs_writes_the_duals_and_the_bound(tmp_path):
+    """duals that fit are written whole; more than DUMP_MAX_ENTRIES: a sample at seeded positions, the same positions every time,
+    whether the duals come from the engine (download) or from the caller's device buffer (a tensor); float64, 64 MB at most"""
+    import numpy as np
+    import torch
+    small = np.arange(1000, dtype=np.float64) * 0.5
+    d = bench.dump_outputs(str(tmp_path / "a"), torch, _FakeEngine(small), None, 3.25, 0, 1)
+    assert d["files"] == ["duals.npy", "lower_bound.npy"] and d["duals"] == "all"
+    assert np.array_equal(np.load(tmp_path / "a" / "duals.npy"), small)
+    assert np.load(tmp_path / "a" / "lower_bound.npy").tolist() == [3.25]
+    n = bench.DUMP_MAX_ENTRIES * 3 + 17
+    big = np.random.default_rng(0).standard_normal(n)
+    eng = _FakeEngine(big)
+    d1 = bench.dump_outputs(str(tmp_path / "b"), torch, eng, None, -1.0, 0, 1)
+    d2 = bench.dump_outputs(str(tmp_path / "c"), torch, _FakeEngine(np.zeros(1)), torch.from_numpy(big), -1.0, 0, 1)
+    assert eng.synced == 1 and d1["n_duals"] == d2["n_duals"] == n
+    for sub in ("b", "c"):
+        assert sorted(os.listdir(tmp_path / sub)) == ["duals.npy", "duals_index.npy", "lower_bound.npy"]
+        idx, vals = np.load(tmp_path / sub / "duals_index.npy"), np.load(tmp_path / sub / "duals.npy")
+        assert idx.dtype == vals.dtype == np.float64 and bench.DUMP_MAX_ENTRIES // 2 < idx.shape[0] <= bench.DUMP_MAX_ENTRIES
+        assert np.array_equal(vals, big[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+        total = sum(os.path.getsize(tmp_path / sub / f) for f in os.listdir(tmp_path / sub))
+        assert total <= 64 * 2**20
+    assert np.array_equal(np.load(tmp_path / "b" / "duals_index.npy"), np.load(tmp_path / "c" / "duals_index.npy"))
+    # several ranks: rank 0 writes (its part, the global bound), the others only synchronise
+    assert bench.dump_outputs(str(tmp_path / "d"), torch, _FakeEngine(small), None, 1.0, 1, 2) is None and not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline keys, no leg beyond the timed steps; --dump-outputs writes what the
+    last timed step left, and two runs of the same command write the same files"""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "128", "--steps", "5", "--warmup", "2",
+                                       "--dump-outputs", str(tmp_path / f"run{k}")], text=True, cwd=ROOT, timeout=600)
+        assert out.strip().splitlines()[-1].startswith('{"metric"'), out[-600:]
+        lines.append(json.loads(out.strip().splitlines()[-1]))
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert d[key] is not None, key
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "msg-updates/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - d["config"]["msg_updates_per_pass"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and d["roofline"] is None and d["rounding"] is None and d["oracle_check"] is None
+    assert d["outputs"]["files"] == ["duals.npy", "duals_index.npy", "lower_bound.npy"]
+    assert d["lower_bound_after"] > d["lower_bound_before"]
+    a, b = tmp_path / "run0", tmp_path / "run1"
+    for f in d["outputs"]["files"]:
+        x, y = np.load(a / f), np.load(b / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y), f
+    assert np.load(a / "lower_bound.npy")[0] == d["lower_bound_after"]
 
 
 def test_golden_fixture_covers_whatever_pass_count_the_driver_runs():
@@ -205,7 +284,7 @@ def test_bench_gpus_2_launches_its_own_ranks(schedule):
     (backend falls back to gloo: RCCL refuses two ranks on one GPU), the line says how many ranks ran and where"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LPMP_DIST_BACKEND")}
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "128", "--steps", "4", "--warmup", "2",
-                                   "--no-cpu-baseline", "--schedule", schedule] + (["--compare-schedules"] if schedule == "overlap" else []),
+                                   "--no-cpu-baseline", "--full", "--schedule", schedule] + (["--compare-schedules"] if schedule == "overlap" else []),
                                   text=True, cwd=ROOT, timeout=1200, env=env)
     assert out.strip().splitlines()[-1].startswith('{"metric"'), out[-600:]
     d = json.loads(out.strip().splitlines()[-1])
@@ -226,7 +305,7 @@ def test_bench_gpus_2_c4_runs_in_lock_step_by_default():
     variable order on every path), the line carries the boundary-step schedule of the same model beside it"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LPMP_DIST_BACKEND")}
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4", "--c4-nodes", "20000", "--c4-edges", "100000",
-                                   "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--compare-schedules"], text=True, cwd=ROOT, timeout=1200, env=env)
+                                   "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--full", "--compare-schedules"], text=True, cwd=ROOT, timeout=1200, env=env)
     d = json.loads(out.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["schedule"] == "lockstep" and d["config"]["variable_order"] == "colour_major"
     assert abs(d["dual_bound_gap"]) <= 1e-12 and d["lower_bound_after"] > d["lower_bound_before"]

@@ -2,7 +2,9 @@
 container `two_dim_variable_array` behind `weight_array` / `receive_array` (reference include/two_dimensional_variable_array.hxx,
 used at include/LP_MP.h:989-992, sized by allocate_omega :1008-1040).  The reference's own test of it must pass as built, and the
 layout the real container reports is what lpmp_plan_get_omega / _mask hand out — a check against reference CODE, not
-against a restatement.  Skipped where neither /root/reference nor a previously built oracle/_ref is present."""
+against a restatement.  Where the reference sources are absent (and with them oracle/_ref), the answers those binaries gave for
+exactly these inputs come from tests/golden/ref_outputs.npz (tests/golden/make_ref_outputs.py); where both exist they must agree."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -16,16 +18,52 @@ from lp_mp_amd import engine as E, model as M, synthetic as S  # noqa: E402
 from oracle import build_ref  # noqa: E402
 
 
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_outputs.npz")
+
+
+class Ref:
+    """the reference programs of oracle/_ref by name: run where they were built, else their recorded output for the same input"""
+
+    def __init__(self, exes, recorded, record=None):
+        self.exes, self.recorded, self.record = exes, recorded, record
+
+    @staticmethod
+    def key(name, text):
+        return name + ":" + hashlib.sha256(text.encode()).hexdigest()
+
+    def __contains__(self, name):
+        return name in self.exes or any(k.startswith(name + ":") for k in self.recorded)
+
+    def run(self, name, text, timeout=120):
+        k = self.key(name, text)
+        if name in self.exes:
+            out = subprocess.check_output([self.exes[name]], input=text, text=True, timeout=timeout)
+            if self.record is not None:
+                self.record[k] = out
+            if k in self.recorded:
+                assert out == self.recorded[k], f"{name}: the built program and tests/golden/ref_outputs.npz disagree"
+            return out
+        assert k in self.recorded, f"{name}: no recorded output for this input (regenerate tests/golden/ref_outputs.npz)"
+        return self.recorded[k]
+
+
+def recorded_outputs():
+    if not os.path.exists(RECORDED):
+        return {}
+    g = np.load(RECORDED)
+    return dict(zip(map(str, g["keys"]), map(str, g["outputs"])))
+
+
 @pytest.fixture(scope="module")
 def ref():
-    exes = build_ref.build()
-    if "ref_two_dim" not in exes:
-        pytest.skip("no reference sources and no oracle/_ref build on this box")
-    return exes
+    r = Ref(build_ref.build(), recorded_outputs())
+    if "ref_two_dim" not in r:
+        pytest.skip("no reference sources, no oracle/_ref build and no recorded outputs")
+    return r
 
 
-def _layout(exe, sizes):
-    out = subprocess.check_output([exe], input=" ".join(map(str, [len(sizes)] + list(sizes))), text=True, timeout=120)
+def _layout(ref, sizes):
+    out = ref.run("ref_two_dim", " ".join(map(str, [len(sizes)] + list(sizes))))
     rows, flat = [], []
     for line in out.splitlines():
         w = line.split()
@@ -40,9 +78,9 @@ def _layout(exe, sizes):
 
 
 def test_the_references_own_container_test_passes_as_built(ref):
-    if "ref_test_two_dimensional_variable_array" not in ref:
+    if "ref_test_two_dimensional_variable_array" not in ref.exes:
         pytest.skip("the reference's test was not built")
-    assert subprocess.run([ref["ref_test_two_dimensional_variable_array"]], timeout=300).returncode == 0
+    assert subprocess.run([ref.exes["ref_test_two_dimensional_variable_array"]], timeout=300).returncode == 0
 
 
 def test_reference_container_is_a_row_major_csr(ref):
@@ -52,7 +90,7 @@ def test_reference_container_is_a_row_major_csr(ref):
         sizes[rng.integers(0, sizes.shape[0])] = 0                      # rows without entries (factors that send nothing)
         if sizes.sum() == 0:
             continue
-        rows, flat = _layout(ref["ref_two_dim"], sizes)
+        rows, flat = _layout(ref, sizes)
         off = np.concatenate([[0], np.cumsum(sizes)])
         first = int(off[np.nonzero(sizes)[0][0]])
         assert [r[0] for r in rows] == list(map(int, sizes))
@@ -74,7 +112,7 @@ def test_plan_weight_and_mask_arrays_have_the_layout_of_the_reference_container(
                 assert off[0] == 0 and data.shape[0] == off[-1]
                 if sizes.sum() == 0:
                     continue
-                rows, flat = _layout(ref["ref_two_dim"], sizes)
+                rows, flat = _layout(ref, sizes)
                 first = int(off[np.nonzero(sizes)[0][0]])
                 assert all(o == off[i] - first for i, (s, o) in enumerate(rows) if s > 0)
                 # storage position k of the reference holds (row, column) = what data[k] holds here
@@ -97,7 +135,7 @@ def test_partitions_are_numbered_as_the_references_union_find_numbers_them(ref):
         p = E.Plan(gm)
         updated = np.zeros(nf, np.int64); updated[p.update_order(M.FORWARD)] = 1
         text = " ".join(map(str, [nf] + list(updated) + [gm.part_pairs.shape[0]] + list(gm.part_pairs.reshape(-1))))
-        out = subprocess.check_output([ref["ref_union_find"]], input=text, text=True, timeout=60).splitlines()
+        out = ref.run("ref_union_find", text, timeout=60).splitlines()
         P = int(out[0].split()[1])
         want = [[] for _ in range(P)]
         for line in out[1:]:
@@ -110,11 +148,11 @@ def test_partitions_are_numbered_as_the_references_union_find_numbers_them(ref):
 
 
 # ---- a13: the scalar two-minimum behind the O(L) Potts message, from the reference's own help_functions.hxx ------------------------
-def _ref_two_smallest(exe, vectors):
+def _ref_two_smallest(ref, vectors):
     def tok(x):
         return "inf" if x == np.inf else "-inf" if x == -np.inf else float(x).hex()
     text = "\n".join(" ".join([str(len(v))] + [tok(x) for x in v]) for v in vectors)
-    out = subprocess.check_output([exe], input=text, text=True, timeout=120).split()
+    out = ref.run("ref_two_smallest", text).split()
     return [(float.fromhex(a) if "inf" not in a else float(a), float.fromhex(b) if "inf" not in b else float(b)) for a, b in zip(out[0::2], out[1::2])]
 
 
@@ -152,7 +190,7 @@ def test_oracle_potts_message_equals_the_references_two_smallest_elements(ref):
     if "ref_two_smallest" not in ref:
         pytest.skip("ref_two_smallest was not built")
     cases = _potts_vectors(np.random.default_rng(21), 60, with_inf=True)
-    twos = _ref_two_smallest(ref["ref_two_smallest"], [c[2] for c in cases])
+    twos = _ref_two_smallest(ref, [c[2] for c in cases])
     for (L, m1, m2, d), two in zip(cases, twos):
         srt = np.sort(m2)
         assert two == (srt[0], srt[1] if L > 1 else np.inf)             # what the reference function returns
@@ -169,7 +207,7 @@ def test_device_two_min_equals_the_references_two_smallest_elements(ref):
     if "ref_two_smallest" not in ref:
         pytest.skip("ref_two_smallest was not built")
     cases = _potts_vectors(np.random.default_rng(22), 50, with_inf=False)
-    twos = _ref_two_smallest(ref["ref_two_smallest"], [c[2] for c in cases])
+    twos = _ref_two_smallest(ref, [c[2] for c in cases])
     eng = E.Engine(0)
     for (L, m1, m2, d), two in zip(cases, twos):
         m, p = _single_pairwise(None, m1, m2, potts=d, L=L)

@@ -229,7 +229,7 @@ def test_single_pass_of_a_rotating_model_gets_its_chain_plan_lazily(monkeypatch)
 def _bench(args, env=None, timeout=1500):
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LPMP_DIST_BACKEND")}
     e.update(env or {})
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py")] + args, text=True, cwd=ROOT, timeout=timeout, env=e)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, text=True, cwd=ROOT, timeout=timeout, env=e)
     assert out.strip().splitlines()[-1].startswith('{"metric"'), out[-800:]
     return json.loads(out.strip().splitlines()[-1])
 
@@ -327,7 +327,7 @@ def test_bench_under_torch_distributed_run_the_drivers_own_command():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LPMP_DIST_BACKEND")}
     out = subprocess.check_output([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                    "--master-port", "29591", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "128", "--steps", "4", "--warmup", "2",
-                                   "--no-cpu-baseline", "--no-compare-schedules"], text=True, cwd=ROOT, timeout=1500, env=env, stderr=subprocess.DEVNULL)
+                                   "--no-cpu-baseline", "--no-compare-schedules", "--full"], text=True, cwd=ROOT, timeout=1500, env=env, stderr=subprocess.DEVNULL)
     lines = [l for l in out.strip().splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1                                               # rank 0 prints the one line
     d = json.loads(lines[0])

@@ -51,7 +51,7 @@ def _backend_takes_device_tensors(tmp_path) -> bool:
 def _bench(args, env=None, timeout=1500):
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LPMP_DIST_BACKEND")}
     e.update(env or {})
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py")] + args, text=True, cwd=ROOT, timeout=timeout, env=e)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, text=True, cwd=ROOT, timeout=timeout, env=e)
     assert out.strip().splitlines()[-1].startswith('{"metric"'), out[-800:]
     return json.loads(out.strip().splitlines()[-1])
 

@@ -8,7 +8,7 @@ for cfg in cfgs:
         env = dict(os.environ, LPMP_ROT_VERBOSE="1")
         if off:
             env["LPMP_NO_BLOCKED_PASSES"] = "1"
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "20", "--warmup", "3"] + cfg.split(),
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "20", "--warmup", "3"] + cfg.split(),
                            env=env, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         notes = sorted(set(l for l in r.stderr.splitlines() if l.startswith("lpmp:")))

@@ -11,8 +11,8 @@ cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py "$@" > "$OUT/bench_plain.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_stats.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_write.log" 2>&1
+python3 bench.py --full "$@" > "$OUT/bench_plain.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_stats.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_write.log" 2>&1
 grep -h '^{"metric"' "$OUT/bench_plain.log" | cut -c1-400
