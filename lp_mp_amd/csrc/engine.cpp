@@ -93,13 +93,16 @@ struct DevSchedule {
     bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
     ChainLaunchDev* launches = nullptr; int32_t *tk_launch = nullptr, *tk_block = nullptr, *dep_off = nullptr, *dep = nullptr, *done = nullptr, *next = nullptr;
     unsigned long long* mailbox = nullptr;   // tagged granules of the message vectors that travel between dependent records (plan.cpp)
+    void release() {
+      for (void* p : {(void*)launches, (void*)tk_launch, (void*)tk_block, (void*)dep_off, (void*)dep, (void*)done, (void*)next, (void*)mailbox}) if (p) (void)hipFree(p);
+      launches = nullptr; tk_launch = tk_block = dep_off = dep = done = next = nullptr; mailbox = nullptr;
+    }
   };
   std::vector<DevChain> chains;
   std::vector<LevelRange> plain;           // launches that do not belong to a chain
   bool chain = false;
   void release_chain() {
-    for (auto& c : chains)
-      for (void* p : {(void*)c.launches, (void*)c.tk_launch, (void*)c.tk_block, (void*)c.dep_off, (void*)c.dep, (void*)c.done, (void*)c.next, (void*)c.mailbox}) if (p) (void)hipFree(p);
+    for (auto& c : chains) c.release();
     chains.clear(); plain.clear(); chain = false;
   }
   void release() {
@@ -136,25 +139,6 @@ constexpr int HIST_END = 1, HIST_MID = 2;   // kernels.hip
 struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0; };
 
 }  // namespace
-
-// Joined passes as ONE persistent launch (chain executor with a skewed ticket order): what the expansion
-// for n passes needs of the two fused schedules.  Templates: H, W, T = the three steps of forward+backward, K = the middle
-// step of backward+forward; n passes = H, W, (K, W)^(n-1), T.
-struct RotationInfo {
-  bool valid = false;
-  int kclass = 0, gpb = 1;
-  struct Tmpl { int sched; LevelRange lr; int32_t nb; int64_t factors, recv, bytes; };   // sched: 0 forward+backward, 1 backward+forward
-  Tmpl t[4];                                                   // H, W, K, T
-  // predecessors of a step's blocks: kind 0 W after [H]; 1 K after [W, H]; 2 W after [K, W]; 3 K after [W, K];
-  // 4 T after [W, K]; 5 T after [W, H].  (delta, block): the block of the step delta steps earlier
-  std::vector<int64_t> off[6]; std::vector<int8_t> delta[6]; std::vector<int32_t> block[6];
-  // every factor's bound at a pass seam is known to a W record (its own, at the end) or a K record (its own after the
-  // receives, or as the pairwise peer of one of its receives): then a joined launch can emit one bound row per pass
-  bool hist_ok = false;
-  // how far AHEAD in a step's block list a steady-state block's predecessors of the step before lie, as a fraction of the
-  // list (a W x H grid in a 2-colour order: one grid row, 1 / H): what the lag of the skewed ticket order has to cover before any slack
-  double reach = 0;
-};
 
 struct lpmp_plan {
   Plan p;
@@ -251,93 +235,6 @@ static void plan_rotation(lpmp_plan* pl, int mode) {
 }
 
 
-// who touches what in one launch: the block (of gpb records) whose record updates factor g or reaches it through an op
-static std::vector<int32_t> launch_touchers(const Schedule& s, const LevelRange& lr, int gpb, int64_t nf) {
-  std::vector<int32_t> t((size_t)nf, -1);
-  for (int64_t i = lr.begin; i < lr.end; ++i) {
-    const UpdRec& r = s.recs[i];
-    const int32_t b = (int32_t)((i - lr.begin) / gpb);
-    t[r.factor] = b;
-    for (int k = 0; k < r.n_recv + r.n_send; ++k) t[s.ops[r.op_begin + k].peer] = b;
-  }
-  return t;
-}
-static void plan_rotation_chain(lpmp_plan* pl, int mode) {
-  RotationInfo& ri = pl->rot[mode];
-  ri = RotationInfo();
-  if (!pl->rotation_ok[mode]) return;
-  const Schedule& fb = pl->pass_cache[mode];
-  const Schedule& bf = pl->bf_cache[mode];
-  auto only_launch = [](const Schedule& s, int level, LevelRange& out) {
-    int n = 0;
-    for (const auto& lr : s.launches) if (lr.level == level) { out = lr; ++n; }
-    return n == 1;
-  };
-  LevelRange h, w, k, t;
-  if (!only_launch(fb, 1, h) || !only_launch(fb, 2, w) || !only_launch(fb, 3, t) || !only_launch(bf, 2, k)) return;
-  const int kc = w.kclass;
-  if (h.kclass != kc || k.kclass != kc || t.kclass != kc || !kc_chain_capable(kc) || kc_width(kc) == 0) return;
-
-  if (h.stride == 0 || w.stride == 0 || k.stride == 0 || t.stride == 0) return;
-  ri.kclass = kc; ri.gpb = kc_block_records(kc);
-  const LevelRange* lrs[4] = {&h, &w, &k, &t};
-  const Schedule* sch[4] = {&fb, &fb, &bf, &fb};
-  std::vector<int32_t> touch[4];
-  for (int i = 0; i < 4; ++i) {
-    const int64_t cnt = lrs[i]->end - lrs[i]->begin;
-    ri.t[i] = {i == 2 ? 1 : 0, *lrs[i], (int32_t)((cnt + ri.gpb - 1) / ri.gpb), cnt, lrs[i]->n_recv, lrs[i]->bytes};
-    touch[i] = launch_touchers(*sch[i], *lrs[i], ri.gpb, pl->p.nf);
-  }
-  // kind -> (X, Y1, Y2)
-  const int X[6] = {1, 2, 1, 2, 3, 3}, Y1[6] = {0, 1, 2, 1, 1, 1}, Y2[6] = {-1, 0, 1, 2, 2, 0};
-  for (int kind = 0; kind < 6; ++kind) {
-    const Schedule& s = *sch[X[kind]];
-    const LevelRange& lr = *lrs[X[kind]];
-    // (blocks are independent: chunks of them on several threads, see plan.hpp parallel_blocks)
-    const int64_t nbk = ri.t[X[kind]].nb;
-    std::vector<std::vector<std::pair<int8_t, int32_t>>> per((size_t)nbk);
-    parallel_blocks(nbk, 4096, [&](int64_t b0, int64_t b1) {
-      for (int64_t b = b0; b < b1; ++b) {
-        auto& dst = per[(size_t)b];
-        for (int64_t i = lr.begin + b * ri.gpb; i < std::min<int64_t>(lr.end, lr.begin + (b + 1) * ri.gpb); ++i) {
-          const UpdRec& r = s.recs[i];
-          auto visit = [&](int32_t g) {
-            if (touch[Y1[kind]][g] >= 0) dst.emplace_back((int8_t)1, touch[Y1[kind]][g]);
-            else if (Y2[kind] >= 0 && touch[Y2[kind]][g] >= 0) dst.emplace_back((int8_t)2, touch[Y2[kind]][g]);
-          };
-          visit(r.factor);
-          for (int q = 0; q < r.n_recv + r.n_send; ++q) visit(s.ops[r.op_begin + q].peer);
-        }
-        std::sort(dst.begin(), dst.end());
-        dst.erase(std::unique(dst.begin(), dst.end()), dst.end());
-      }
-    });
-    ri.off[kind].assign(1, 0);
-    for (auto& v : per) {
-      for (const auto& d : v) { ri.delta[kind].push_back(d.first); ri.block[kind].push_back(d.second); }
-      ri.off[kind].push_back((int64_t)ri.block[kind].size());
-    }
-    if (kind == 2 || kind == 3) {
-      const double nbs = (double)std::max<int64_t>(1, nbk), nbp = (double)std::max<int32_t>(1, ri.t[Y1[kind]].nb);
-      for (int64_t b = 0; b < nbk; ++b)
-        for (const auto& d : per[(size_t)b])
-          if (d.first == 1) ri.reach = std::max(ri.reach, (d.second + 0.5) / nbp - (b + 0.5) / nbs);
-    }
-  }
-  {   // coverage of the per-pass bound rows (kernels.hip HIST_END / HIST_MID)
-    std::vector<uint8_t> cov((size_t)pl->p.nf, 0);
-    for (int64_t i = w.begin; i < w.end; ++i) cov[fb.recs[i].factor] = 1;
-    for (int64_t i = k.begin; i < k.end; ++i) {
-      const UpdRec& r = bf.recs[i];
-      cov[r.factor] = 1;
-      for (int q = 0; q < r.n_recv; ++q) cov[bf.ops[r.op_begin + q].peer] = 1;
-    }
-    ri.hist_ok = true;
-    for (int64_t f = 0; f < pl->p.nf; ++f) if (!cov[f]) { ri.hist_ok = false; break; }
-  }
-  ri.valid = true;
-}
-
 struct lpmp_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -423,24 +320,21 @@ struct lpmp_engine {
   bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
   bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
-  int rot_bands = 0, rot_lag = 3, rot_depth = 4;   // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
-  bool rot_lag_set = false, rot_depth_set = false; // LPMP_ROT_LAG / LPMP_ROT_DEPTH given: used as they are; else from the model (rot_geometry)
+  RotSettings rot_opts;            // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
   // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
   // unset: the engine's own choice (tiles of 1024 blocks where the band order is down to depth 2 or does not fit at all)
   int rot_tiles = 0; bool rot_tiles_set = false;
-  // delayed[sd]: share of a steady-state step's blocks that run later than their own tile's phase, sd steps into a group
-  struct TileSet { bool built = false; int T = 0; std::vector<int32_t> w, k; int32_t n = 0; double radius = 0; double delayed[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
-  TileSet rot_tile_set[LPMP_REPAM_COUNT];
-  void release_rot_chains() {
-    for (auto& m : rot_chain) {
-      for (auto& kv : m) {
-        auto& c = kv.second.dc;
-        for (void* p : {(void*)c.launches, (void*)c.tk_launch, (void*)c.tk_block, (void*)c.dep_off, (void*)c.dep, (void*)c.done, (void*)c.next, (void*)c.mailbox}) if (p) (void)hipFree(p);
-      }
-      m.clear();
+  // the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
+  struct RotOrder { bool have_geo = false; RotGeometry geo; TileSet tiles; };
+  RotOrder rot_order[LPMP_REPAM_COUNT];
+  // drop the joined-pass launches of a mode (or of all modes) and their order
+  void release_rot_chains(int only_mode = -1) {
+    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
+      if (only_mode >= 0 && m != only_mode) continue;
+      for (auto& kv : rot_chain[m]) { kv.second.dc.release(); rot_cache_bytes -= std::min(rot_cache_bytes, kv.second.dev_bytes); }
+      rot_chain[m].clear();
+      rot_order[m] = RotOrder();
     }
-    rot_cache_bytes = 0;
-    for (auto& t : rot_tile_set) t = TileSet();
   }
   bool timing = false;
   ClassTiming ct[KC_COUNT];
@@ -629,6 +523,28 @@ void fill_device(T*& dst, size_t& cap, const V& src, hipStream_t stream) {
   h2d(dst, src.data(), src.size() * sizeof(T), stream);
 }
 
+// a chain's tables on the device: its launches, ticket lists and dependency lists, n_done zeroed completion flags and the ticket
+// counter.  Nothing half-built stays behind: on failure every buffer of dc is freed again.
+void upload_chain(DevSchedule::DevChain& dc, const std::vector<ChainLaunchDev>& lds, const std::vector<int32_t>& tk_launch, const std::vector<int32_t>& tk_block,
+                  const std::vector<int32_t>& dep_off, const std::vector<int32_t>& dep, size_t n_done, hipStream_t stream) {
+  auto up = [&](auto*& dst, const auto& v) {
+    using T = std::remove_reference_t<decltype(*dst)>;
+    HIP_CHECK(hipMalloc((void**)&dst, std::max<size_t>(1, v.size()) * sizeof(T)));
+    if (!v.empty()) h2d(dst, v.data(), v.size() * sizeof(T), stream);
+  };
+  try {
+    up(dc.launches, lds); up(dc.tk_launch, tk_launch); up(dc.tk_block, tk_block); up(dc.dep_off, dep_off); up(dc.dep, dep);
+    dc.tickets = (int32_t)tk_launch.size();
+    n_done = std::max<size_t>(1, n_done);
+    HIP_CHECK(hipMalloc((void**)&dc.done, n_done * sizeof(int32_t)));
+    HIP_CHECK(hipMalloc((void**)&dc.next, sizeof(int32_t)));
+    HIP_CHECK(hipMemsetAsync(dc.done, 0, n_done * sizeof(int32_t), stream));
+  } catch (...) {
+    dc.release();
+    throw;
+  }
+}
+
 // keep: refill d's buffers in place where they are large enough (the scratch schedule of lpmp_compute_pass_custom)
 void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool keep = false, bool adaptive_built = false) {
   if (keep) { if (d.graph) { (void)hipGraphExecDestroy(d.graph); d.graph = nullptr; } if (d.graph_primal) { (void)hipGraphExecDestroy(d.graph_primal); d.graph_primal = nullptr; } }
@@ -640,20 +556,12 @@ void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool
   fill_device(d.packets, d.packets_cap, s.packets, stream);
   d.release_chain();
   if (!s.chains.empty() && !adaptive_built) {
-    auto up = [&](auto*& dst, const auto& v) {
-      using T = std::remove_reference_t<decltype(*dst)>;
-      HIP_CHECK(hipMalloc((void**)&dst, std::max<size_t>(1, v.size()) * sizeof(T)));
-      if (!v.empty()) h2d(dst, v.data(), v.size() * sizeof(T), stream);
-    };
     for (const ChainPlan& c : s.chains) {
-      DevSchedule::DevChain dc;
       std::vector<ChainLaunchDev> lds;
       for (const auto& l : c.launches) lds.push_back({l.stride > 0 ? d.packets + l.pk_begin : nullptr, d.recs + l.rec_begin, d.ops, l.count, l.stride, l.flags});
-      up(dc.launches, lds); up(dc.tk_launch, c.tk_launch); up(dc.tk_block, c.tk_block); up(dc.dep_off, c.dep_off); up(dc.dep, c.dep);
-      dc.tickets = (int32_t)c.tk_launch.size();
-      HIP_CHECK(hipMalloc((void**)&dc.done, std::max<size_t>(1, (size_t)dc.tickets) * sizeof(int32_t)));
-      HIP_CHECK(hipMalloc((void**)&dc.next, sizeof(int32_t)));
-      HIP_CHECK(hipMemsetAsync(dc.done, 0, std::max<size_t>(1, (size_t)dc.tickets) * sizeof(int32_t), stream));
+      d.chains.emplace_back();                 // (owned by d from here on: release_chain frees what a failure leaves)
+      DevSchedule::DevChain& dc = d.chains.back();
+      upload_chain(dc, lds, c.tk_launch, c.tk_block, c.dep_off, c.dep, c.tk_launch.size(), stream);
       dc.kclass = c.kclass; dc.banded = c.banded; dc.level_loop = c.level_loop; dc.n_launches = (int32_t)c.launches.size();
       if (c.mailbox_rows > 0) {
         // a granule is valid when its tag is the epoch of the running launch: zeroed once, epochs start at 1
@@ -665,7 +573,6 @@ void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool
         }
         HIP_CHECK(hipMemsetAsync(dc.mailbox, 0, bytes, stream));
       }
-      d.chains.push_back(dc);
     }
     for (int32_t li : s.plain_launches) d.plain.push_back(s.launches[li]);
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -744,7 +651,7 @@ void ensure_pass_schedule(lpmp_engine* e, int mode) {
   if (e->rotation_ok[mode]) {
     upload_schedule(e->plan->bf_cache[mode], e->sched_bf[mode], e->stream);
     lap_("... uploaded");
-    plan_rotation_chain(e->plan.get(), mode);
+    e->plan->rot[mode] = plan_rotation_chain(e->plan->pass_cache[mode], e->plan->bf_cache[mode], e->plan->p.nf);
     lap_("block relations of the steps");
     e->plan->bf_cache[mode] = Schedule();
   }
@@ -767,13 +674,7 @@ void ensure_pass_chain_plan(lpmp_engine* e, int mode) {
   plan_pass_schedule(e->plan.get(), mode, true);
   check_generic_limits(e->plan->p, e->plan->pass_cache[mode]);
   HIP_CHECK(hipStreamSynchronize(e->stream));
-  for (auto& kv : e->rot_chain[mode]) {
-    auto& c = kv.second.dc;
-    for (void* p : {(void*)c.launches, (void*)c.tk_launch, (void*)c.tk_block, (void*)c.dep_off, (void*)c.dep, (void*)c.done, (void*)c.next, (void*)c.mailbox}) if (p) (void)hipFree(p);
-    e->rot_cache_bytes -= std::min(e->rot_cache_bytes, kv.second.dev_bytes);
-  }
-  e->rot_chain[mode].clear();
-  e->rot_tile_set[mode] = lpmp_engine::TileSet();
+  e->release_rot_chains(mode);
   upload_schedule(e->plan->pass_cache[mode], e->sched_pass[mode], e->stream);
   Schedule& h = e->plan->pass_cache[mode];
   h.recs.clear(); h.recs.shrink_to_fit(); h.ops.clear(); h.ops.shrink_to_fit(); h.packets.clear(); h.packets.shrink_to_fit();
@@ -949,136 +850,35 @@ void check_rows(int64_t n, const int64_t* om_off, const double* om, const int64_
 // parity: the kernel maps ticket t to (template ticket, copy of the period) (kernels.hip, chain_ticket_ref), and the
 // completion flags are a ring of a few groups.  Host work, upload and device memory of an n-pass launch no longer depend on n.
 constexpr int ROT_EXPLICIT_MAX = 7;
-// The window of the skewed order — (bands, lag, depth) — from the model (round 6).  A table is read by two consecutive steps; with
-// bands of a step issued at time b + lag * d (d = the step's place in its group of `depth` steps) the second read comes
-// lag * depth bands after the first, and it finds the table in the 256 MiB Infinity Cache while that window stays below it.
-// The lag has to cover the REACH of the dependencies — how far ahead in the block list a block's predecessors lie: one grid row —
-// plus slack: a ticket whose predecessors were issued fewer tickets ago than there are resident workgroups (256 CUs x 3) is drawn
-// while they are still running, and its workgroup waits.  In ticket order the steps of a group are interleaved, so a slack of
-// S tickets is S / depth blocks of one step.  Measured (profiles/r06_blocked_pass_probe_*.txt, 32 labels, bands of 16 MiB, a
-// block = 156 KB): 1024^2 (row 20 MB) lag 3, depth 4: 5.12 ms per pass (lag 2: 5.24, lag 4: 5.18); 1536^2 (row 30 MB) lag 3 / 4 / 5:
-// 12.17 / 11.94 / 12.85 (11.5 = 2.25 times the 1024^2 time; 14.5 launch by launch); 2048^2 (row 40 MB) 25.3 with lag 3 (slack
-// 260 tickets: no better than one launch per step, 26.0), 21.3 with lag 4 (700 tickets; 20.4 = four times), 22.6 with lag 5
-// (window 336 MB: the reuse goes); 3072^2 (row 60 MB) 65.4 with lag 3 / depth 4 (57.2 launch by launch), 50.3 with lag 6 / depth 2
-// (46 = nine times; depth 3 and 4 with lags 5-6: 50.2-52.1).  So: a slack of 700 tickets behind the reach; depth 4 while
-// (reach + slack) * 4 stays under 275 MiB, else 2 (half of the second reads instead of three quarters, but they hit); the lag
-// stretched to a window of 200 MiB where the reach leaves room; `fits` = false when even depth 2 cannot hold the window (then the
-// tiled order below, or one launch per step).
-struct RotGeometry { int bands = 1, lag = 3, depth = 4; bool fits = true; double reach_bytes = 0; };
-static RotGeometry rot_geometry(const lpmp_engine* e, const RotationInfo& ri) {
-  RotGeometry g;
-  g.lag = std::max(1, e->rot_lag); g.depth = std::max(1, e->rot_depth);
-  if (!ri.valid) return g;
-  g.bands = e->rot_bands > 0 ? e->rot_bands : (int)std::max<int64_t>(1, std::min<int64_t>(ri.t[1].nb, ri.t[1].bytes / ((int64_t)16 << 20)));
-  if (e->rot_bands > 0) return g;                   // bands forced (tests, probes): lag and depth as given or their defaults
-  constexpr double MiB = 1048576.0, SLACK_TICKETS = 700, WINDOW_TARGET = 200 * MiB, WINDOW_MAX = 275 * MiB;
-  const double step_bytes = (double)ri.t[1].bytes, band_bytes = step_bytes / g.bands;
-  const double slack1 = SLACK_TICKETS * step_bytes / (double)std::max<int32_t>(1, ri.t[1].nb);   // the slack as bytes of ONE step's block list, depth 1
-  g.reach_bytes = ri.reach * step_bytes;
-  if (!e->rot_depth_set) g.depth = (g.reach_bytes + slack1 / 4) * 4 <= WINDOW_MAX ? 4 : 2;
-  const double need = g.reach_bytes + slack1 / g.depth;
-  // (rounded up from .3: a band short on slack costs more than a band of window — 1536^2: 3.4 bands -> 4)
-  if (!e->rot_lag_set) g.lag = std::max(2, (int)std::floor(std::max(need, WINDOW_TARGET / g.depth) / band_bytes + 0.7));
-  g.fits = e->rot_depth_set || e->rot_lag_set || need * g.depth <= 1.25 * WINDOW_MAX;
-  return g;
-}
-// Tiled ticket order (round 6; chosen in rotation_chain below, LPMP_ROT_TILES overrides).  The band order walks a step's block list in memory order, so its lag has
-// to cover how far ahead a block's predecessors lie IN THAT LIST — a grid row, a z-slice of a 3-D grid — whatever the distance in
-// the graph is.  Tiles are compact in the GRAPH instead: sets of about T blocks of either alternating step template (W and K; H and
-// T update K's factors), grown breadth-first over the block dependencies.  Inside a group of `depth` steps a block runs in the phase
-// of its own tile or of the latest tile one of its predecessors ran in, whichever is later — the skew of a time-tiled stencil
-// without any geometry: valid by construction, a table is read again by the next step T blocks later, and nothing grows with the
-// width of the grid.
-static int32_t grow_tiles(const RotationInfo& ri, int64_t T, std::vector<int32_t>& tile_w, std::vector<int32_t>& tile_k, double& radius) {
-  const int64_t nw = ri.t[1].nb, nk = ri.t[2].nb, nn = nw + nk;
-  std::vector<int64_t> deg((size_t)nn + 1, 0);
-  auto each_edge = [&](auto f) {      // W block j <-> K block p (kind 2: W after K), K block j <-> W block p (kind 3: K after W)
-    for (int kind = 2; kind <= 3; ++kind) {
-      const int64_t nb = kind == 2 ? nw : nk;
-      for (int64_t j = 0; j < nb; ++j)
-        for (int64_t q = ri.off[kind][j]; q < ri.off[kind][j + 1]; ++q)
-          if (ri.delta[kind][q] == 1) { const int64_t a = kind == 2 ? j : nw + j, b = kind == 2 ? nw + ri.block[kind][q] : ri.block[kind][q]; f(a, b); }
-    }
-  };
-  each_edge([&](int64_t a, int64_t b) { ++deg[a + 1]; ++deg[b + 1]; });
-  for (int64_t i = 0; i < nn; ++i) deg[i + 1] += deg[i];
-  std::vector<int32_t> adj((size_t)deg[nn]);
-  { std::vector<int64_t> cur(deg.begin(), deg.end() - 1); each_edge([&](int64_t a, int64_t b) { adj[cur[a]++] = (int32_t)b; adj[cur[b]++] = (int32_t)a; }); }
-  std::vector<int32_t> tile((size_t)nn, -1), queue, hops;
-  int32_t n_tiles = 0;
-  double radius_sum = 0; int64_t full_tiles = 0;    // hops from the seed to the last block of a tile that reached its size
-  for (int64_t seed0 = 0; seed0 < std::max(nw, nk); ++seed0)
-    for (int64_t seed : {seed0 < nw ? seed0 : (int64_t)-1, seed0 < nk ? nw + seed0 : (int64_t)-1}) {
-      if (seed < 0 || tile[seed] >= 0) continue;
-      queue.assign(1, (int32_t)seed); hops.assign(1, 0);
-      int64_t taken = 0; int32_t last_hops = 0;
-      for (size_t head = 0; head < queue.size() && taken < 2 * T; ++head) {
-        const int32_t v = queue[head];
-        if (tile[v] >= 0) continue;
-        tile[v] = n_tiles; ++taken; last_hops = hops[head];
-        for (int64_t q = deg[v]; q < deg[v + 1]; ++q) if (tile[adj[q]] < 0) { queue.push_back(adj[q]); hops.push_back(hops[head] + 1); }
-      }
-      if (taken >= 2 * T) { radius_sum += last_hops; ++full_tiles; }
-      ++n_tiles;
-    }
-  radius = full_tiles ? radius_sum / (double)full_tiles : 0.0;
-  tile_w.assign(tile.begin(), tile.begin() + nw);
-  tile_k.assign(tile.begin() + nw, tile.end());
-  return n_tiles;
-}
-
-// how much of a tile is left after sd steps: phases of a steady-state group (K, W, K, W, ...) of 8 steps, share of delayed blocks per step
-static void tile_delays(const RotationInfo& ri, const std::vector<int32_t>& tile_w, const std::vector<int32_t>& tile_k, double (&delayed)[8]) {
-  std::vector<int32_t> ph[3];
-  for (int sd = 0; sd < 8; ++sd) {
-    const int kd = sd % 2 == 0 ? 3 : 2;
-    const std::vector<int32_t>& tl = sd % 2 == 0 ? tile_k : tile_w;
-    const int64_t nb = (int64_t)tl.size();
-    std::vector<int32_t>& cur = ph[sd % 3];
-    cur.resize((size_t)nb);
-    int64_t late = 0;
-    for (int64_t j = 0; j < nb; ++j) {
-      int32_t p = tl[j];
-      if (sd > 0)
-        for (int64_t q = ri.off[kd][j]; q < ri.off[kd][j + 1]; ++q) {
-          const int dl = ri.delta[kd][q];
-          if (dl <= sd) p = std::max(p, ph[(sd - dl) % 3][ri.block[kd][q]]);
-        }
-      cur[j] = p;
-      late += p != tl[j];
-    }
-    delayed[sd] = nb ? (double)late / (double)nb : 0.0;
-  }
-}
-
+// (the window (bands, lag, depth) follows the model: order.cpp rot_geometry; the tiled order: order.cpp make_tiles / tiled_order)
 lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
-  RotGeometry geo = rot_geometry(e, e->plan->rot[mode]);
+  const RotationInfo& ri = e->plan->rot[mode];
+  lpmp_engine::RotOrder& ro = e->rot_order[mode];
+  if (!ro.have_geo) { ro.geo = rot_geometry(e->rot_opts, ri); ro.have_geo = true; }
+  const RotGeometry& geo = ro.geo;
+  const int rot_bands = e->rot_opts.bands;
   // Band order or tiled order?  Measured (profiles/r06_tile_sweep.txt, r06_blocked_pass_probe_tiles_*.txt; tiles of 1024 blocks): where
   // the band order runs at depth 4 it is as good or better (1024^2: 5.09 against 5.31 ms per pass, 2048^2: 21.35 / 21.26); where
   // the reach of the dependencies has pushed it to depth 2 or out of the cache, tiles win — 3072^2: 49.5 -> 47.7 ms, 256 x 4096: 5.89
   // -> 5.44, 128 x 8192 (no band order fits: 6.95 launch by launch) -> 5.37, 3-D grids 96^3 x 32 labels: 8.88 -> 7.27, 128^3 x 16
   // labels: 6.23 -> 5.72.  Calls of fewer than 4 passes keep the band order (single passes: 9.0 against 6.8 ms at 1024^2).
-  // Depth: a block whose predecessor ran in a later tile is delayed to that tile's phase — one more shell of every tile per step: the
-  // deepest even depth (up to 8) whose LAST step still runs at least half of its blocks in their own tile's phase (tile_delays: the
-  // flat tiles of a 2-D grid lose about 4 % per step: depth 8; the balls of a 3-D grid 16 %: depth 4 — measured there: depth 2 / 4 /
-  // 6 / 8 = 7.9 / 7.27 / 7.28 / 7.6 ms per pass at 96^3 x 32 labels, 5.92 / 5.72 / - / 7.24 at 128^3 x 16).
-  bool tiled = false;
-  lpmp_engine::TileSet* ts = nullptr;
+  // Depth of the tiled order (TileSet::depth): the flat tiles of a 2-D grid lose about 4 % per step: depth 8; the balls of a 3-D grid
+  // 16 %: depth 4 — measured there: depth 2 / 4 / 6 / 8 = 7.9 / 7.27 / 7.28 / 7.6 ms per pass at 96^3 x 32 labels, 5.92 / 5.72 / - /
+  // 7.24 at 128^3 x 16).
+  JoinedOrder ord{geo.bands, geo.lag, geo.depth, nullptr};
   {
-    const RotationInfo& ri0 = e->plan->rot[mode];
-    const bool worthwhile = ri0.valid && kc_is_dense(ri0.kclass) && !kc_is_var(ri0.kclass) &&
-                            (e->rot_bands > 0 || (e->model_big && ri0.t[1].bytes >= ((int64_t)64 << 20)));
-    const int want = !worthwhile || ri0.t[0].nb != ri0.t[2].nb || ri0.t[3].nb != ri0.t[2].nb ? 0
+    const bool worthwhile = ri.valid && kc_is_dense(ri.kclass) && !kc_is_var(ri.kclass) &&
+                            (rot_bands > 0 || (e->model_big && ri.t[1].bytes >= ((int64_t)64 << 20)));
+    const int want = !worthwhile || ri.t[0].nb != ri.t[2].nb || ri.t[3].nb != ri.t[2].nb ? 0
                    : e->rot_tiles_set ? e->rot_tiles
-                   : (e->rot_bands <= 0 && (geo.depth != 4 || !geo.fits) && n_call >= 4 ? 1024 : 0);
+                   : (rot_bands <= 0 && (geo.depth != 4 || !geo.fits) && n_call >= 4 ? 1024 : 0);
     if (want > 0) {
-      ts = &e->rot_tile_set[mode];
-      if (!ts->built || ts->T != want) { ts->n = grow_tiles(ri0, want, ts->w, ts->k, ts->radius); tile_delays(ri0, ts->w, ts->k, ts->delayed); ts->T = want; ts->built = true; }
-      tiled = true;
-      if (!e->rot_depth_set) { geo.depth = 2; for (int d = 4; d <= 8; d += 2) if (ts->delayed[d - 1] <= 0.5) geo.depth = d; }
+      if (ro.tiles.T != want) ro.tiles = make_tiles(ri, want);
+      ord.tiles = &ro.tiles;
+      if (!e->rot_opts.depth_set) ord.depth = ro.tiles.depth;
     }
   }
-  const int depth = geo.depth;
+  const int depth = ord.depth;
   // template: groups 0, 1 (prologue), 2 (the period) and a tail as long as the call's: r = (2 n + 1) mod depth steps
   const int tail = depth % 2 == 0 ? (2 * n_call + 1) % depth : 0;
   const int n_template = (3 * depth + tail - 1) / 2;
@@ -1087,233 +887,80 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const int key = periodic ? -tail : n_call;
   auto it = e->rot_chain[mode].find(key);
   if (it != e->rot_chain[mode].end()) { it->second.last_use = ++e->rot_clock; return it->second.n_steps > 0 ? &it->second : nullptr; }
-  // bound the cache in bytes: drop the least recently used built chains (of any mode) until the new one fits; the stream is drained first
-  auto evict_for = [&](size_t need) {
-    bool drained = false;
-    while (e->rot_cache_bytes + need > e->rot_cache_limit) {
-      std::map<int, lpmp_engine::RotChain>* vm = nullptr; std::map<int, lpmp_engine::RotChain>::iterator victim;
-      for (auto& m : e->rot_chain)
-        for (auto i2 = m.begin(); i2 != m.end(); ++i2)
-          if (i2->second.n_steps > 0 && (!vm || i2->second.last_use < victim->second.last_use)) { vm = &m; victim = i2; }
-      if (!vm) break;
-      if (!drained) { HIP_CHECK(hipStreamSynchronize(e->stream)); drained = true; }
-      auto& c = victim->second.dc;
-      for (void* p : {(void*)c.launches, (void*)c.tk_launch, (void*)c.tk_block, (void*)c.dep_off, (void*)c.dep, (void*)c.done, (void*)c.next, (void*)c.mailbox}) if (p) (void)hipFree(p);
-      e->rot_cache_bytes -= std::min(e->rot_cache_bytes, victim->second.dev_bytes);
-      vm->erase(victim);
-    }
-  };
   lpmp_engine::RotChain& rc = e->rot_chain[mode][key];           // n_steps == 0: tried, not possible
   rc.last_use = ++e->rot_clock;
-  const RotationInfo& ri = e->plan->rot[mode];
   const bool verbose = std::getenv("LPMP_ROT_VERBOSE") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
-  auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
   auto no = [&](const char* why) -> lpmp_engine::RotChain* { if (verbose) std::fprintf(stderr, "lpmp: %d passes stay one launch per step: %s\n", n_call, why); return nullptr; };
   if (!ri.valid) return no("the pass does not have the H, W, K, T shape of one packed class");
-  const int n_steps = 2 * n + 1;
-  std::vector<int> tmpl(n_steps), kind(n_steps, -1);
-  tmpl[0] = 0;
-  for (int s = 1; s < n_steps - 1; ++s) tmpl[s] = (s & 1) ? 1 : 2;
-  tmpl[n_steps - 1] = 3;
-  for (int s = 1; s < n_steps; ++s) kind[s] = s == n_steps - 1 ? (n == 1 ? 5 : 4) : s == 1 ? 0 : s == 2 ? 1 : (s & 1) ? 2 : 3;
-  std::vector<int64_t> base(n_steps + 1, 0);
-  for (int s = 0; s < n_steps; ++s) base[s + 1] = base[s] + ri.t[tmpl[s]].nb;
-  const int64_t N = base[n_steps];
-  if (N > (int64_t)48 << 20) return no("too many tickets");                   // too many tickets for one launch: the caller splits the passes
   // a model whose tables fit the caches gains nothing from the order and is launch-bound: one launch per step then
   // (nor does one that fits the Infinity Cache as a whole: plain launches already re-read it on-die, and the chain's
   // agent-scope accesses only cost — C2, 512 x 512 8-label Potts: 0.065 ms per pass as launches, 0.10 as a chain)
-  if (e->rot_bands <= 0 && (ri.t[1].bytes < ((int64_t)64 << 20) || !e->model_big)) return no("the model fits the caches");
+  if (rot_bands <= 0 && (ri.t[1].bytes < ((int64_t)64 << 20) || !e->model_big)) return no("the model fits the caches");
   // (the run-time-dims classes read their tables with 8-byte loads of rows that are not line-aligned: as a chain in
   // Infinity-Cache order 1024 x 1024 x 21 labels takes 5.48 ms per pass against 4.38 launch by launch)
-  if (e->rot_bands <= 0 && kc_is_var(ri.kclass)) return no("run-time-dims class");
+  if (rot_bands <= 0 && kc_is_var(ri.kclass)) return no("run-time-dims class");
   // (Potts steps stream message vectors only, at 7.6 TB/s with the non-temporal policy; as a chain their agent-scope
   // vector loads make 2048 x 2048 x 32 labels 6.4 ms per pass against 3.2)
-  if (e->rot_bands <= 0 && !kc_is_dense(ri.kclass)) return no("no pairwise tables to re-read (Potts)");
+  if (rot_bands <= 0 && !kc_is_dense(ri.kclass)) return no("no pairwise tables to re-read (Potts)");
   // bands: about 16 MiB of algorithmic bytes per band of a step.  What a group keeps alive between two reads of a table is
   // lag * depth bands (3 * 4 * 16 MiB = 192 MiB of the 256 MiB Infinity Cache); measured on C3: windows of 200-230 MB are
   // the fastest whatever the split (1024:3:4 5.09, 2048:4:6 5.03, 1536:3:6 5.09 ms per pass), 290 MB and more lose the
   // reuse (1024:3:5 5.67, 1024:3:6 6.37), lag 2 leaves the waiting workgroups less slack (1024:2:4 5.24)
-  // (round 6: lag and depth follow the reach of the dependencies — rot_geometry above; C3 keeps 3 and 4)
-  if (!geo.fits && !tiled) return no("a step's dependencies reach further than the Infinity Cache window can cover");
-  const int bands = geo.bands;
-  static const std::vector<int32_t> no_tiles;
-  const std::vector<int32_t>& tile_w = tiled ? ts->w : no_tiles;
-  const std::vector<int32_t>& tile_k = tiled ? ts->k : no_tiles;
-  const int32_t n_tiles = tiled ? ts->n : 0;
-  if (tiled && verbose) std::fprintf(stderr, "lpmp:   %d tiles of about %d blocks per step, radius %.1f hops, delayed after 1 / 3 / 5 / 7 steps: %.2f / %.2f / %.2f / %.2f\n", n_tiles, ts->T, ts->radius,
-                                     ts->delayed[1], ts->delayed[3], ts->delayed[5], ts->delayed[7]);
-  std::vector<int32_t> new_of((size_t)N), tk_launch((size_t)N), tk_block((size_t)N);
-  std::vector<int64_t> group_begin;                                 // first ticket of every group of `depth` steps
-  auto band_begin = [](int64_t b, int64_t nb, int64_t bands_) { return (b * nb + bands_ - 1) / bands_; };   // first block of band b
-  for (int lag = geo.lag; lag <= std::max(16, 2 * geo.lag); ++lag) {
-    int64_t at = 0;
-    group_begin.clear();
-    if (tiled) {
-      // phase of (step of the group, block) = max(own tile, phases of its predecessors inside the group); tickets by (phase, step, block)
-      std::vector<int32_t> ph[3];
-      std::vector<int64_t> bucket;
-      std::vector<std::vector<int32_t>> key_of((size_t)depth);
-      for (int s0 = 0; s0 < n_steps; s0 += depth) {
-        group_begin.push_back(at);
-        const int d = std::min(depth, n_steps - s0);
-        bucket.assign((size_t)n_tiles * d + 1, 0);
-        for (int sd = 0; sd < d; ++sd) {
-          const int s = s0 + sd;
-          const int64_t nb = ri.t[tmpl[s]].nb;
-          const std::vector<int32_t>& tl = tmpl[s] == 1 ? tile_w : tile_k;
-          std::vector<int32_t>& cur = ph[sd % 3];
-          cur.resize((size_t)nb);
-          key_of[sd].resize((size_t)nb);
-          const int kd = kind[s];
-          for (int64_t j = 0; j < nb; ++j) {
-            int32_t p = tl[j];
-            if (kd >= 0)
-              for (int64_t q = ri.off[kd][j]; q < ri.off[kd][j + 1]; ++q) {
-                const int dl = ri.delta[kd][q];
-                if (dl <= sd) p = std::max(p, ph[(sd - dl) % 3][ri.block[kd][q]]);
-              }
-            cur[j] = p;
-            key_of[sd][j] = p * d + sd;
-            ++bucket[(size_t)key_of[sd][j] + 1];
-          }
-        }
-        for (size_t k = 0; k + 1 < bucket.size(); ++k) bucket[k + 1] += bucket[k];
-        for (int sd = 0; sd < d; ++sd) {
-          const int s = s0 + sd;
-          const int64_t nb = ri.t[tmpl[s]].nb;
-          for (int64_t j = 0; j < nb; ++j) {
-            const int64_t t = at + bucket[key_of[sd][j]]++;
-            new_of[base[s] + j] = (int32_t)t; tk_launch[t] = s; tk_block[t] = (int32_t)j;
-          }
-        }
-        for (int sd = 0; sd < d; ++sd) at += ri.t[tmpl[s0 + sd]].nb;
-      }
-    } else
-    for (int s0 = 0; s0 < n_steps; s0 += depth) {
-      group_begin.push_back(at);
-      const int d = std::min(depth, n_steps - s0);
-      for (int64_t tau = 0; tau < bands + (int64_t)lag * (d - 1); ++tau)
-        for (int sd = 0; sd < d; ++sd) {
-          const int64_t b = tau - (int64_t)lag * sd;
-          if (b < 0 || b >= bands) continue;
-          const int s = s0 + sd;
-          const int64_t nb = ri.t[tmpl[s]].nb;
-          for (int64_t j = band_begin(b, nb, bands); j < band_begin(b + 1, nb, bands); ++j) {
-            new_of[base[s] + j] = (int32_t)at; tk_launch[at] = s; tk_block[at] = (int32_t)j; ++at;
-          }
-        }
-    }
-    group_begin.push_back(at);
-    if (at != N) throw std::runtime_error("rotation chain: ticket count");
-    if (verbose) std::fprintf(stderr, "lpmp:   %d passes, lag %d: order after %.0f ms\n", n, lag, since());
-    // every predecessor must come earlier
-    bool ok = true;
-    for (int s = 1; s < n_steps && ok; ++s) {
-      const int kd = kind[s];
-      const auto& off = ri.off[kd];
-      for (int64_t j = 0; j < ri.t[tmpl[s]].nb && ok; ++j)
-        for (int64_t q = off[j]; q < off[j + 1]; ++q)
-          if (new_of[base[s - ri.delta[kd][q]] + ri.block[kd][q]] >= new_of[base[s] + j]) {
-            if (verbose) std::fprintf(stderr, "lpmp:   lag %d: step %d (kind %d) block %lld of %lld needs block %d of step %d (%lld blocks), %d bands\n", lag, s, kd,
-                                      (long long)j, (long long)ri.t[tmpl[s]].nb, ri.block[kd][q], s - ri.delta[kd][q], (long long)ri.t[tmpl[s - ri.delta[kd][q]]].nb, bands);
-            ok = false; break;
-          }
-    }
-    if (verbose) std::fprintf(stderr, "lpmp:   checked after %.0f ms (%s)\n", since(), ok ? "valid" : "a dependency points forward");
-    if (!ok && tiled) { tiled = false; if (!geo.fits) return no("the tiled order broke a dependency and the band order does not fit"); --lag; continue; }
-    if (!ok) continue;
-    // dependencies in ticket order
-    std::vector<int32_t> dep_off((size_t)N + 1, 0);
-    for (int s = 1; s < n_steps; ++s) {
-      const auto& off = ri.off[kind[s]];
-      for (int64_t j = 0; j < ri.t[tmpl[s]].nb; ++j) dep_off[new_of[base[s] + j] + 1] = (int32_t)(off[j + 1] - off[j]);
-    }
-    for (int64_t i = 0; i < N; ++i) dep_off[i + 1] += dep_off[i];
-    std::vector<int32_t> dep((size_t)dep_off[N]);
-    for (int s = 1; s < n_steps; ++s) {
-      const int kd = kind[s];
-      const auto& off = ri.off[kd];
-      for (int64_t j = 0; j < ri.t[tmpl[s]].nb; ++j) {
-        int32_t* dst = dep.data() + dep_off[new_of[base[s] + j]];
-        for (int64_t q = off[j]; q < off[j + 1]; ++q) *dst++ = new_of[base[s - ri.delta[kd][q]] + ri.block[kd][q]];
-      }
-    }
-    if (verbose) std::fprintf(stderr, "lpmp:   dependency lists after %.0f ms (%zu)\n", since(), dep.size());
-    int32_t ring = 0;
-    if (periodic) {
-      // the template is [group 0][group 1][group 2 = the period][tail]; what the kernel's map relies on, checked here:
-      // groups 1 and 2 are the same tickets in the same order, the period's and the tail's dependencies all lie in the
-      // group before the period or later (they move with the copy), the prologue's before the period
-      if (group_begin.size() != 5) throw std::runtime_error("rotation chain: template groups");
-      const int64_t g1 = group_begin[1], g2 = group_begin[2], g3 = group_begin[3], P = g3 - g2;
-      bool fine = g2 - g1 == P;
-      for (int64_t t = g2; t < g3 && fine; ++t) {
-        fine = tk_launch[t] == tk_launch[t - P] + depth && tk_block[t] == tk_block[t - P];
-        for (int64_t q = dep_off[t]; q < dep_off[t + 1] && fine; ++q) fine = dep[q] >= g1;
-      }
-      for (int64_t t = g3; t < N && fine; ++t) for (int64_t q = dep_off[t]; q < dep_off[t + 1] && fine; ++q) fine = dep[q] >= g2;
-      for (int64_t t = 0; t < g2 && fine; ++t) for (int64_t q = dep_off[t]; q < dep_off[t + 1] && fine; ++q) fine = dep[q] < g2;
-      // (group 2's dependencies into group 1 must be what a later copy's are into the copy before it: same relative offsets
-      // as group 1's own... group 1 reaches into group 0, whose order differs, so that cannot be compared — the step kinds
-      // of groups >= 2 are identical by construction: kind[s] depends on the parity of s only from s = 3 on)
-      if (!fine) throw std::runtime_error("rotation chain: the template is not periodic");
-      rc.per_begin = (int32_t)g2; rc.per_len = (int32_t)P;
-      // flags: a ring of three groups — a dependency reaches at most into the group before, and a ticket may only publish
-      // into a slot whose previous occupant (a ring earlier) has published (kernels.hip, chain_wait)
-      ring = (int32_t)(3 * P);
-      if ((int64_t)48 * (int64_t)(2 * P) / ring + 64 >= (1 << CHAIN_GEN_BITS)) throw std::runtime_error("rotation chain: ring too small for its generation counter");
-    }
-    std::vector<ChainLaunchDev> lds;
-    for (int s = 0; s < n_steps; ++s) {
-      const auto& t = ri.t[tmpl[s]];
-      const DevSchedule& ds = t.sched == 0 ? e->sched_pass[mode] : e->sched_bf[mode];
-      // per-pass bound rows (only written when the launch is given rows: speculative batches): W of pass i (step 2 i + 1)
-      // and K after pass i (step 2 i + 2) write row i, for the passes i = 0 ... n - 2 that have a seam behind them
-      // (periodic template: the tail's last W is the last W of ANY call of this parity)
-      int32_t hist = 0;
-      // (periodic template: every W carries its row — whether it has a seam behind it depends on the call, and the kernel drops
-      // rows >= ChainArgs::hist_rows)
-      if (tmpl[s] == 1 && ((s - 1) / 2 < n - 1 || periodic)) hist = HIST_END | (((s - 1) / 2) << 2);
-      if (tmpl[s] == 2) hist = HIST_MID | (((s - 2) / 2) << 2);
-      lds.push_back({t.lr.stride > 0 ? ds.packets + t.lr.pk_begin : nullptr, ds.recs + t.lr.begin, ds.ops, t.lr.end - t.lr.begin, t.lr.stride, hist});
-      rc.factors += t.factors; rc.recv += t.recv; rc.bytes += t.bytes;
-      if (periodic && s >= 2 * depth && s < 3 * depth) { rc.per_factors += t.factors; rc.per_recv += t.recv; rc.per_bytes += t.bytes; }
-    }
-    // (periodic: the kernel looks a ticket's launch up at its TEMPLATE step — the steps of a later copy of the period are the
-    // same K / W launches, and the tail's the same K, W, T; only the bound row in `pad` moves with the copy, depth / 2 rows
-    // per copy — so this table, too, is the template's whatever the call's pass count)
-    const size_t n_done = periodic ? (size_t)ring : (size_t)N;
-    rc.dev_bytes = lds.size() * sizeof(ChainLaunchDev) + (tk_launch.size() + tk_block.size() + dep_off.size() + dep.size() + n_done + 1) * sizeof(int32_t);
-    evict_for(rc.dev_bytes);
-    auto up = [&](auto*& dst, const auto& v) {
-      using T = std::remove_reference_t<decltype(*dst)>;
-      HIP_CHECK(hipMalloc((void**)&dst, std::max<size_t>(1, v.size()) * sizeof(T)));
-      if (!v.empty()) h2d(dst, v.data(), v.size() * sizeof(T), e->stream);
-    };
-    auto& dc = rc.dc;
-    try {
-      up(dc.launches, lds); up(dc.tk_launch, tk_launch); up(dc.tk_block, tk_block); up(dc.dep_off, dep_off); up(dc.dep, dep);
-      dc.tickets = (int32_t)N; dc.kclass = ri.kclass;
-      HIP_CHECK(hipMalloc((void**)&dc.done, n_done * sizeof(int32_t)));
-      HIP_CHECK(hipMalloc((void**)&dc.next, sizeof(int32_t)));
-      HIP_CHECK(hipMemsetAsync(dc.done, 0, n_done * sizeof(int32_t), e->stream));
-      HIP_CHECK(hipStreamSynchronize(e->stream));
-    } catch (...) {
-      // nothing half-built stays behind: the entry goes (a later call tries again), the bytes were never counted
-      for (void* p : {(void*)dc.launches, (void*)dc.tk_launch, (void*)dc.tk_block, (void*)dc.dep_off, (void*)dc.dep, (void*)dc.done, (void*)dc.next}) if (p) (void)hipFree(p);
-      e->rot_chain[mode].erase(key);
-      throw;
-    }
-    e->rot_cache_bytes += rc.dev_bytes;
-    rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = ring;
-    if (verbose)
-      std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
-                   periodic ? (tiled ? " (periodic template, tiled order)" : " (periodic template)") : tiled ? " (tiled order)" : "", (long long)N, bands, lag, depth, geo.reach_bytes / 1e6, (double)ri.t[1].bytes / bands / 1e6, since());
-    return &rc;
+  // (round 6: lag and depth follow the reach of the dependencies — order.cpp rot_geometry; C3 keeps 3 and 4)
+  if (!geo.fits && !ord.tiles) return no("a step's dependencies reach further than the Infinity Cache window can cover");
+  if (ord.tiles && verbose) std::fprintf(stderr, "lpmp:   %d tiles of about %d blocks per step, radius %.1f hops, delayed after 1 / 3 / 5 / 7 steps: %.2f / %.2f / %.2f / %.2f\n", ro.tiles.n, ro.tiles.T,
+                                         ro.tiles.radius, ro.tiles.delayed[1], ro.tiles.delayed[3], ro.tiles.delayed[5], ro.tiles.delayed[7]);
+  JoinedTables jt;
+  const std::string why = joined_pass_tables(ri, ord, n, periodic, jt, verbose ? stderr : nullptr);
+  if (!why.empty()) return no(why.c_str());
+  if (periodic && (int64_t)48 * (int64_t)(2 * jt.per_len) / jt.ring + 64 >= (1 << CHAIN_GEN_BITS)) throw std::runtime_error("rotation chain: ring too small for its generation counter");
+  const int n_steps = 2 * n + 1;
+  std::vector<ChainLaunchDev> lds;
+  for (int s = 0; s < n_steps; ++s) {
+    const auto& t = ri.t[jt.step_tmpl[s]];
+    const DevSchedule& ds = t.sched == 0 ? e->sched_pass[mode] : e->sched_bf[mode];
+    const int32_t row = jt.step_row[s];
+    const int32_t hist = row < 0 ? 0 : (jt.step_tmpl[s] == 1 ? HIST_END : HIST_MID) | (row << 2);
+    lds.push_back({t.lr.stride > 0 ? ds.packets + t.lr.pk_begin : nullptr, ds.recs + t.lr.begin, ds.ops, t.lr.end - t.lr.begin, t.lr.stride, hist});
+    rc.factors += t.factors; rc.recv += t.recv; rc.bytes += t.bytes;
+    if (periodic && s >= 2 * depth && s < 3 * depth) { rc.per_factors += t.factors; rc.per_recv += t.recv; rc.per_bytes += t.bytes; }
   }
-  return no("no band order keeps the dependencies backwards");
+  // (periodic: the kernel looks a ticket's launch up at its TEMPLATE step — the steps of a later copy of the period are the
+  // same K / W launches, and the tail's the same K, W, T; only the bound row in `pad` moves with the copy, depth / 2 rows
+  // per copy — so this table, too, is the template's whatever the call's pass count)
+  const int64_t N = (int64_t)jt.tk_launch.size();
+  const size_t n_done = periodic ? (size_t)jt.ring : (size_t)N;
+  rc.dev_bytes = lds.size() * sizeof(ChainLaunchDev) + (jt.tk_launch.size() + jt.tk_block.size() + jt.dep_off.size() + jt.dep.size() + n_done + 1) * sizeof(int32_t);
+  // bound the cache in bytes: drop the least recently used built chains (of any mode) until the new one fits; the stream is drained first
+  for (bool drained = false; e->rot_cache_bytes + rc.dev_bytes > e->rot_cache_limit;) {
+    std::map<int, lpmp_engine::RotChain>* vm = nullptr; std::map<int, lpmp_engine::RotChain>::iterator victim;
+    for (auto& m : e->rot_chain)
+      for (auto i2 = m.begin(); i2 != m.end(); ++i2)
+        if (i2->second.n_steps > 0 && (!vm || i2->second.last_use < victim->second.last_use)) { vm = &m; victim = i2; }
+    if (!vm) break;
+    if (!drained) { HIP_CHECK(hipStreamSynchronize(e->stream)); drained = true; }
+    victim->second.dc.release();
+    e->rot_cache_bytes -= std::min(e->rot_cache_bytes, victim->second.dev_bytes);
+    vm->erase(victim);
+  }
+  try {
+    upload_chain(rc.dc, lds, jt.tk_launch, jt.tk_block, jt.dep_off, jt.dep, n_done, e->stream);
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+  } catch (...) {
+    // nothing half-built stays behind: the entry goes (a later call tries again), the bytes were never counted
+    rc.dc.release();
+    e->rot_chain[mode].erase(key);
+    throw;
+  }
+  rc.dc.kclass = ri.kclass;
+  e->rot_cache_bytes += rc.dev_bytes;
+  rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
+  if (verbose)
+    std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
+                 periodic ? (ord.tiles ? " (periodic template, tiled order)" : " (periodic template)") : ord.tiles ? " (tiled order)" : "", (long long)N, ord.bands, jt.lag, depth,
+                 geo.reach_bytes / 1e6, (double)ri.t[1].bytes / ord.bands / 1e6, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  return &rc;
 }
 
 bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullptr) {
@@ -1612,9 +1259,9 @@ int lpmp_create(int device, lpmp_engine** out) {
     e->use_chain = !(nc && nc[0] == '1');
     const char* nb = std::getenv("LPMP_NO_BLOCKED_PASSES");
     e->use_blocked_passes = !(nb && nb[0] == '1');
-    if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_bands = std::atoi(v);
-    if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_lag = std::max(1, std::atoi(v)); e->rot_lag_set = true; }
-    if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_depth = std::max(1, std::atoi(v)); e->rot_depth_set = true; }
+    if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
+    if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }
+    if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_opts.depth = std::max(1, std::atoi(v)); e->rot_opts.depth_set = true; }
     if (const char* v = std::getenv("LPMP_ROT_TILES")) { e->rot_tiles = std::max(0, std::atoi(v)); e->rot_tiles_set = true; }
     if (const char* v = std::getenv("LPMP_CHAIN_CACHE_MB")) e->rot_cache_limit = (size_t)std::max(1, std::atoi(v)) << 20;
     if (const char* v = std::getenv("LPMP_ROWS_LAYOUT")) e->want_rows = std::atoi(v) != 0;                             // as lpmp_set_rows_layout

@@ -909,8 +909,6 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   // and the labeling-list factors are separate components); classes with few launches stay plain launches.
   // (LPMP_CHAIN_MIN: experiments — the smallest number of launches that makes a class a chain)
   const int64_t chain_min = [] { const char* v = std::getenv("LPMP_CHAIN_MIN"); return v ? (int64_t)std::atoll(v) : CHAIN_MIN_LAUNCHES; }();
-  const int bands = [] { const char* v = std::getenv("LPMP_CHAIN_BANDS"); return v ? std::atoi(v) : 0; }();
-  const int lag = [] { const char* v = std::getenv("LPMP_CHAIN_LAG"); return v ? std::atoi(v) : 2; }();
   const bool no_level_loop = std::getenv("LPMP_NO_LEVEL_LOOP") != nullptr;
   const bool no_auto_bands = std::getenv("LPMP_NO_BLOCKED_PASSES") != nullptr;
   // (LPMP_BAND_MIN_BYTES, LPMP_BAND_BYTES: tests force the banded order on small models)
@@ -928,7 +926,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   // persistent launch — the gaps between its kernels are a per cent of their run time (measured: 12.15 ms per pass as a chain,
   // 11.96 ms of kernel time launch by launch) — while its ticket, dependency and mailbox tables are seconds of planning: it
   // stays a replayed graph of plain launches.  (Few big steps are the banded case below; LPMP_CHAIN_HEAVY_BYTES moves the bar.)
-  if (!chain_all && bands <= 1 && out.launches.size() > 8) {
+  if (!chain_all && out.launches.size() > 8) {
     const char* hv = std::getenv("LPMP_CHAIN_HEAVY_BYTES");
     const int64_t heavy = hv ? std::atoll(hv) : ((int64_t)256 << 20);
     int64_t total = 0;
@@ -975,7 +973,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       std::vector<int32_t> src_rec, rec_of_upd, rec_launch;
       std::vector<int8_t> src_k;
       bool any_mbox = false;
-      if (!no_mailbox && bands <= 1 && ok) {
+      if (!no_mailbox && ok) {
         for (int c = 0; c < KC_COUNT; ++c) {
           if (!(c >= KC_DENSE_4 && c <= KC_POTTS_V32)) continue;                   // the packed dense and Potts classes, exact and run-time dims
           // (fewer launches: plain launches, or — a few HBM-sized steps — the banded order below; LPMP_CHAIN_MIN lowers the
@@ -1137,40 +1135,31 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
         // (only receives read tables: a directional sweep of a 2-colour grid has ONE such step and gains nothing)
         int64_t max_bytes = 0; int n_table_steps = 0;
         for (const auto& lr : out.launches) if (lr.kclass == c) { max_bytes = std::max(max_bytes, lr.bytes); if (lr.n_recv > 0 && lr.bytes >= band_min_bytes) ++n_table_steps; }
-        const bool dense_cls = kc_is_dense(c) && !kc_is_var(c);   // (run-time-dims classes: slower as a banded chain, engine.cpp plan_rotation_chain)
+        const bool dense_cls = kc_is_dense(c) && !kc_is_var(c);   // (run-time-dims classes: slower as a banded chain, engine.cpp rotation_chain)
         const bool big_steps = model_big && dense_cls && n_table_steps >= 2 && n_launches_of[c] <= 8 && !no_auto_bands;
-        if (n_launches_of[c] < chain_min && !big_steps && !(bands > 1)) {               // few launches: plain
+        if (n_launches_of[c] < chain_min && !big_steps) {               // few launches: plain
           for (size_t li = 0; li < out.launches.size(); ++li) if (out.launches[li].kclass == c) out.plain_launches.push_back((int32_t)li);
           continue;
         }
         ChainPlan& cp = cps[c];
         auto& ed = edges[c];
         const int64_t n_tickets = (int64_t)cp.tk_launch.size();
-        if (big_steps && !(bands > 1) && n_tickets > 0) {
-          // about 16 MiB of algorithmic bytes per band; the smallest lag from 3 on that keeps every dependency backwards
-          const int64_t nl = (int64_t)cp.launches.size();
+        if (big_steps && n_tickets > 0) {
+          // about 16 MiB of algorithmic bytes per band; the smallest lag from 3 on that keeps every dependency backwards (the
+          // skewed band order of order.cpp, one group over all of the class's launches)
           const int gpb = kc_block_records(c);
+          std::vector<int64_t> nb;
           int64_t max_nb = 1;                               // (a band narrower than a few blocks cannot keep the dependencies)
-          for (const auto& l : cp.launches) max_nb = std::max<int64_t>(max_nb, (l.count + gpb - 1) / gpb);
+          for (const auto& l : cp.launches) { nb.push_back((l.count + gpb - 1) / gpb); max_nb = std::max(max_nb, nb.back()); }
           const int nbands = (int)std::max<int64_t>(2, std::min<int64_t>(max_bytes / band_bytes, max_nb / 4));
-          std::vector<int32_t> order((size_t)n_tickets), new_of((size_t)n_tickets);
-          std::vector<int64_t> key((size_t)n_tickets);
+          TicketOrder o;
           for (int lg = 3; lg <= 16 && !cp.banded; ++lg) {
-            for (int64_t t = 0; t < n_tickets; ++t) {
-              const int64_t l = cp.tk_launch[t];
-              const int64_t nb = (cp.launches[l].count + gpb - 1) / gpb;
-              key[t] = ((int64_t)cp.tk_block[t] * nbands / nb + (int64_t)lg * l) * (nl + 1) + l;
-            }
-            std::iota(order.begin(), order.end(), 0);
-            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
-            for (int64_t i = 0; i < n_tickets; ++i) new_of[order[i]] = (int32_t)i;
+            band_order(nb, nbands, lg, (int)nb.size(), o);
             bool fine = true;
-            for (const auto& e : ed) if (new_of[e.second] >= new_of[e.first]) { fine = false; break; }
+            for (const auto& e : ed) if (o.new_of[e.second] >= o.new_of[e.first]) { fine = false; break; }
             if (!fine) continue;
-            for (auto& e : ed) { e.first = new_of[e.first]; e.second = new_of[e.second]; }
-            std::vector<int32_t> tl((size_t)n_tickets), tb((size_t)n_tickets);
-            for (int64_t i = 0; i < n_tickets; ++i) { tl[i] = cp.tk_launch[order[i]]; tb[i] = cp.tk_block[order[i]]; }
-            cp.tk_launch.swap(tl); cp.tk_block.swap(tb);
+            for (auto& e : ed) { e.first = o.new_of[e.first]; e.second = o.new_of[e.second]; }
+            cp.tk_launch.swap(o.tk_step); cp.tk_block.swap(o.tk_block);
             cp.banded = true;
           }
           if (!cp.banded && n_launches_of[c] < chain_min) {   // no valid order and nothing else to gain: plain launches
@@ -1178,34 +1167,10 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
             continue;
           }
         }
-        // Temporal blocking (LPMP_CHAIN_BANDS=NB, experiments): tickets are not taken level by level but in a skewed
-        // order — band j of the l-th launch at time j + LAG * l — so that what a level reads (pairwise tables) is read
-        // again by the next level while it is still in the Infinity Cache.  Only an order: the dependency flags keep
-        // the result identical; an order that would put a dependency behind its dependent is refused.
-        if (bands > 1 && n_tickets > 0) {
-          std::vector<int64_t> key((size_t)n_tickets);
-          const int64_t nl = (int64_t)cp.launches.size();
-          for (int64_t t = 0; t < n_tickets; ++t) {
-            const int64_t l = cp.tk_launch[t];
-            const int gpb = kc_block_records(c);
-            const int64_t nb = (cp.launches[l].count + gpb - 1) / gpb;
-            key[t] = ((int64_t)cp.tk_block[t] * bands / nb + (int64_t)lag * l) * (nl + 1) + l;
-          }
-          std::vector<int32_t> order((size_t)n_tickets);
-          std::iota(order.begin(), order.end(), 0);
-          std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
-          std::vector<int32_t> new_of((size_t)n_tickets);
-          for (int64_t i = 0; i < n_tickets; ++i) new_of[order[i]] = (int32_t)i;
-          for (auto& e : ed) { e.first = new_of[e.first]; e.second = new_of[e.second]; }
-          std::vector<int32_t> tl((size_t)n_tickets), tb((size_t)n_tickets);
-          for (int64_t i = 0; i < n_tickets; ++i) { tl[i] = cp.tk_launch[order[i]]; tb[i] = cp.tk_block[order[i]]; }
-          cp.tk_launch.swap(tl); cp.tk_block.swap(tb);
-          cp.banded = true;
-        }
         std::sort(ed.begin(), ed.end());
         ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
         cp.dep_off.assign((size_t)n_tickets + 1, 0);
-        for (const auto& e : ed) { if (e.second >= e.first) fail("chain plan: dependency on a later ticket (LPMP_CHAIN_BANDS / LPMP_CHAIN_LAG?)"); cp.dep_off[e.first + 1]++; }
+        for (const auto& e : ed) { if (e.second >= e.first) fail("chain plan: dependency on a later ticket"); cp.dep_off[e.first + 1]++; }
         std::partial_sum(cp.dep_off.begin(), cp.dep_off.end(), cp.dep_off.begin());
         cp.dep.resize(ed.size());
         for (size_t i = 0; i < ed.size(); ++i) cp.dep[i] = ed[i].second;   // sorted by ticket: already in CSR order

@@ -11,6 +11,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <exception>
 #include <memory>
 #include <new>
@@ -301,5 +302,62 @@ struct Plan {
 
 // graph.cpp: an order of all factors with the updated ones colour by colour (rank[f] = position; returns the number of colours)
 int32_t suggest_order(const Plan& p, uint64_t seed, int32_t* rank);
+
+// ---- order.cpp: ticket orders of the Infinity-Cache chain launches ------------------------------------------------------------
+// A skewed order of the blocks of consecutive steps: new_of[base[s] + j] = ticket of block j of step s (base: the steps' blocks in
+// step order), tk_step / tk_block = the inverse; group_begin = first ticket of every group of `depth` steps, and N at the end.
+struct TicketOrder { std::vector<int32_t> tk_step, tk_block, new_of; std::vector<int64_t> group_begin; };
+// Skewed band order: step s (nb[s] blocks) is cut into `bands` bands, block j in band floor(j * bands / nb[s]); inside a group of
+// `depth` steps, band b of the group's d-th step comes at time b + lag * d: tickets sorted by (band + lag * d, d, block)
+void band_order(const std::vector<int64_t>& nb, int bands, int lag, int depth, TicketOrder& o);
+
+// Joined passes as ONE persistent launch (chain executor with a skewed ticket order): what the expansion
+// for n passes needs of the two fused schedules.  Templates: H, W, T = the three steps of forward+backward, K = the middle
+// step of backward+forward; n passes = H, W, (K, W)^(n-1), T.
+struct RotationInfo {
+  bool valid = false;
+  int kclass = 0, gpb = 1;
+  struct Tmpl { int sched; LevelRange lr; int32_t nb; int64_t factors, recv, bytes; };   // sched: 0 forward+backward, 1 backward+forward
+  Tmpl t[4];                                                   // H, W, K, T
+  // predecessors of a step's blocks: kind 0 W after [H]; 1 K after [W, H]; 2 W after [K, W]; 3 K after [W, K];
+  // 4 T after [W, K]; 5 T after [W, H].  (delta, block): the block of the step delta steps earlier
+  std::vector<int64_t> off[6]; std::vector<int8_t> delta[6]; std::vector<int32_t> block[6];
+  // every factor's bound at a pass seam is known to a W record (its own, at the end) or a K record (its own after the
+  // receives, or as the pairwise peer of one of its receives): then a joined launch can emit one bound row per pass
+  bool hist_ok = false;
+  // how far AHEAD in a step's block list a steady-state block's predecessors of the step before lie, as a fraction of the
+  // list (a W x H grid in a 2-colour order: one grid row, 1 / H): what the lag of the skewed ticket order has to cover before any slack
+  double reach = 0;
+};
+// fb, bf: forward+backward and backward+forward of a mode whose passes join (engine.cpp plan_rotation), nf factors; not valid
+// unless H, W, K, T are one packed launch each of one chain-capable class
+RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf);
+
+// the window of the band order: LPMP_ROT_BANDS / _LAG / _DEPTH (bands 0: from the table bytes per step; *_set: given, used as they are)
+struct RotSettings { int bands = 0, lag = 3, depth = 4; bool lag_set = false, depth_set = false; };
+// fits = false: even depth 2 cannot hold the window in the Infinity Cache
+struct RotGeometry { int bands = 1, lag = 3, depth = 4; bool fits = true; double reach_bytes = 0; };
+RotGeometry rot_geometry(const RotSettings& rs, const RotationInfo& ri);
+
+// tiles of about T blocks of the W and K steps (w, k: tile of every block; n tiles); delayed[sd]: share of a steady-state step's
+// blocks that run later than their own tile's phase, sd steps into a group; depth: the group depth that follows from it
+struct TileSet { int T = 0; std::vector<int32_t> w, k; int32_t n = 0; double radius = 0; double delayed[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int depth = 2; };
+TileSet make_tiles(const RotationInfo& ri, int T);
+// tiled order of n joined passes: in a group of `depth` steps a block runs in the phase of its own tile or the latest phase of its
+// predecessors in the group; tickets sorted by (phase, step, block)
+void tiled_order(const RotationInfo& ri, int n, const TileSet& ts, int depth, TicketOrder& o);
+
+// the order of a joined-pass launch: band order (bands, lags from `lag` to max(16, 2 lag), depth) or, with tiles, the tiled order
+struct JoinedOrder { int bands = 1, lag = 3, depth = 4; const TileSet* tiles = nullptr; };
+struct JoinedTables {
+  std::vector<int32_t> tk_launch, tk_block, dep_off, dep;   // ticket -> step, block; dependencies (CSR over tickets)
+  std::vector<int> step_tmpl;                               // per step: its template (0 H, 1 W, 2 K, 3 T)
+  std::vector<int32_t> step_row;                            // per step: the per-pass bound row its launch writes (-1: none)
+  int32_t per_begin = 0, per_len = 0, ring = 0;             // periodic template: the period's tickets, slots of the flag ring
+  int lag = 0;                                              // the lag the band order was built with
+};
+// the tables of n joined passes (periodic: the template of n passes whose group 2 is the period; the depth must be even) — ""
+// or why the passes stay one launch per step; log (or nullptr): progress lines.  ri must be valid.
+std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, int n, bool periodic, JoinedTables& out, FILE* log);
 
 }  // namespace lpmp

@@ -498,3 +498,23 @@ def test_update_levels_without_planning_the_sweep_equal_those_of_the_planned_swe
                 p2.schedule_info(d, mode)
                 assert np.array_equal(alone, p2.update_levels(d, mode)), (mode, d)
                 assert alone.max() <= p2.schedule_info(d, mode)["n_levels"]          # (updates without an active message count no level)
+
+
+def test_ticket_orders_of_the_joined_passes(tmp_path):
+    """tests/cpp/test_ticket_order.cpp against lp_mp_amd/csrc/order.cpp (host only, g++): the skewed band order is a permutation and
+    the (band + lag * step, step, block) sort inside every group; a lag below the reach of the dependencies is refused and the reach
+    itself accepted; the tiled order keeps every dependency for tiles of 1 ... 1024 blocks and depths 2 ... 8; a periodic template
+    expanded to 8 ... 40 passes (both parities) is the explicit launch; a step of zero bytes keeps the default window"""
+    import os
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.fail("g++ not found")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "lp_mp_amd", "csrc")
+    exe = str(tmp_path / "test_ticket_order")
+    subprocess.check_call([gxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", csrc, "-o", exe,
+                           os.path.join(root, "tests", "cpp", "test_ticket_order.cpp"), os.path.join(csrc, "order.cpp"), "-lpthread"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "ticket orders ok" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]

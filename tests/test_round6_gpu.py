@@ -171,7 +171,7 @@ def test_forbidden_label_pairs_through_the_joined_pass_launch():
 @pytest.mark.parametrize("H,W,want", [(16, 4096, "chain"), (5, 16384, "sweep")])
 def test_wide_grids_joined_launch_geometry_against_the_oracle(H, W, want, capfd, monkeypatch):
     """HBM-sized colour-major grids whose ROWS are long (80 MB and 320 MB of a step's algorithmic bytes per grid row of one colour; the
-    headline grid: 20 MB): the engine chooses lag and depth of the skewed ticket order from that reach (engine.cpp rot_geometry) —
+    headline grid: 20 MB): the engine chooses lag and depth of the skewed ticket order from that reach (order.cpp rot_geometry) —
     depth 2 and a lag that covers one row plus slack for the 4096-wide grid, no band order at all when even that window cannot sit in
     the Infinity Cache (16384 wide); calls of 4 and more passes take the tiled order there — and the duals equal the oracle's bit for
     bit every way"""
