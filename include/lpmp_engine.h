@@ -48,8 +48,7 @@ enum lpmp_mem { LPMP_MEM_HOST = 0, LPMP_MEM_DEVICE = 1 };
 
 const char* lpmp_last_error(void);
 const char* lpmp_version(void);
-/* 0 for the product library.  1 / 2: an experimental build of tools/build_variant.sh (2: with LPMP_ABLATE_* switches that
-   remove work from the kernels and compute wrong results) — never what lp_mp_amd/build.py produces. */
+/* Always 0: there is one build of the library.  Kept for ABI compatibility. */
 int lpmp_experiment_build(void);
 
 /* ---- host-only analysis (no GPU needed) -------------------------------------------------------

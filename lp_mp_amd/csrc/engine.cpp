@@ -53,6 +53,7 @@ static thread_local std::string g_error;
 const char* lpmp_last_error(void) { return g_error.c_str(); }
 extern "C" int lpmp_set_last_error(const char* msg) { g_error = msg ? msg : ""; return 0; }   // for the other translation units of the library
 const char* lpmp_version(void) { return "lp_mp_amd 0.1 (gfx950)"; }
+int lpmp_experiment_build(void) { return 0; }   // kept for the ABI: the library has no experimental build
 
 namespace {
 
@@ -285,7 +286,6 @@ struct lpmp_engine {
   int mode = -1;
   int rtype = 0;   // enum lpmp_reparametrization_type
   bool use_graph = true;
-  bool use_packed = true;
   bool use_chain = true;          // deep single-class schedules as one persistent launch (LPMP_NO_CHAIN=1: graph replay)
   int32_t* d_chain_abort = nullptr; bool chain_ran = false;
   // joined passes as one persistent launch: expansions of RotationInfo, by mode and pass count
@@ -692,11 +692,14 @@ void issue_launches(lpmp_engine* e, const DevSchedule& s, bool timed, hipStream_
     const bool pw_rounds = e->primal_pass && e->d_pw_unary && kc_is_pw(lr.kclass);
     if (pw_rounds)
       launch_sweep(KC_GENERIC, s.recs, s.ops, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->d_pw_unary, lr.begin, lr.end - lr.begin, flags, stream);
-    else if (!(e->use_packed && lr.stride != 0 &&
+    else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
-                              e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream)))
+                              e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
+      // the packed classes have no op-by-op kernel: plan.cpp gives every launch of one packets or indirect records
+      if (kc_is_packed(lr.kclass)) throw DeviceError("sweep: launch of packed class " + std::to_string(lr.kclass) + " without packets");
       launch_sweep(lr.kclass, s.recs, s.ops, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->d_pw_unary, lr.begin, lr.end - lr.begin,
                    flags | (lr.kclass == KC_DENSE_BIG ? sweep_bigdim_flags(lr.max_dim) : 0), stream);   // (LDS of the streaming class: by the launch's label counts)
+    }
     if (timed) {
       HIP_CHECK(hipEventRecord(b, stream));
       e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes});
@@ -1253,8 +1256,6 @@ int lpmp_create(int device, lpmp_engine** out) {
     e->use_rotation = !(nr && nr[0] == '1');
     const char* nt = std::getenv("LPMP_NO_LB_TRACKING");
     e->use_lb_tracking = !(nt && nt[0] == '1');
-    const char* np = std::getenv("LPMP_NO_PACKED");
-    e->use_packed = !(np && np[0] == '1');
     const char* nc = std::getenv("LPMP_NO_CHAIN");
     e->use_chain = !(nc && nc[0] == '1');
     const char* nb = std::getenv("LPMP_NO_BLOCKED_PASSES");

@@ -20,28 +20,6 @@
 
 #include "plan.hpp"
 
-// The LPMP_ABLATE_* switches below REMOVE work from the kernel bodies (loads, reductions, bound tracking) to price it
-// (tools/build_variant.sh, EXPERIMENTS.md): such a build computes WRONG duals.  They are only accepted together with
-// LPMP_EXPERIMENT_BUILD, which tools/build_variant.sh sets and lp_mp_amd/build.py never does; the product library
-// additionally exports lpmp_experiment_build() == 0 (tests/test_product_isolation.py).
-#if (defined(LPMP_ABLATE_TABLE) || defined(LPMP_ABLATE_RECV_VEC) || defined(LPMP_ABLATE_SEND_VEC) || defined(LPMP_ABLATE_REDUCE) || \
-     defined(LPMP_ABLATE_LB_TRACK)) && !defined(LPMP_EXPERIMENT_BUILD)
-#error "LPMP_ABLATE_* builds compute wrong results: they need -DLPMP_EXPERIMENT_BUILD (tools/build_variant.sh) and must never be the product library"
-#endif
-#if defined(LPMP_ABLATE_TABLE) || defined(LPMP_ABLATE_RECV_VEC) || defined(LPMP_ABLATE_SEND_VEC) || defined(LPMP_ABLATE_REDUCE) || defined(LPMP_ABLATE_LB_TRACK)
-#define LPMP_ANY_ABLATION 1
-#else
-#define LPMP_ANY_ABLATION 0
-#endif
-extern "C" int lpmp_experiment_build(void) {
-#ifdef LPMP_EXPERIMENT_BUILD
-  return 1 + LPMP_ANY_ABLATION;     // 1: an experimental build (tuning knobs only), 2: with ablations (wrong results)
-#else
-  static_assert(LPMP_ANY_ABLATION == 0, "ablations in a product build");
-  return 0;
-#endif
-}
-
 namespace lpmp {
 
 #define LPMP_INF (__builtin_inf())
@@ -269,47 +247,14 @@ __device__ __forceinline__ void mailbox_put(unsigned long long* q, double v, int
   __hip_atomic_store(q, tag | (unsigned)__double2loint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(q + 1, tag | (unsigned)__double2hiint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// experiments (tools/build_variant.sh): polls of one granule pair in flight, spaced LPMP_MBOX_GAP sleeps apart
-#ifndef LPMP_MBOX_PIPE
-#define LPMP_MBOX_PIPE 1
-#endif
-#ifndef LPMP_MBOX_GAP
-#define LPMP_MBOX_GAP 5
-#endif
-#ifndef LPMP_MBOX_SLEEP
-#define LPMP_MBOX_SLEEP 1
-#endif
 __device__ __forceinline__ double mailbox_take(const ChainArgs& ca, const unsigned long long* q, bool& bad) {
   const unsigned tag = (unsigned)ca.epoch;
-#if LPMP_MBOX_PIPE > 1
-  // a poll is a round trip to the far side of the fabric; with several under way, a fraction of a trip apart, the granule is
-  // seen that much sooner after it lands (the loads of a wave return in order)
-  unsigned long long a[LPMP_MBOX_PIPE], b[LPMP_MBOX_PIPE];
-#pragma unroll
-  for (int i = 0; i < LPMP_MBOX_PIPE; ++i) {
-    a[i] = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    b[i] = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (i + 1 < LPMP_MBOX_PIPE) __builtin_amdgcn_s_sleep(LPMP_MBOX_GAP);
-  }
-  long long t0 = 0;
-  for (int spins = 0;;) {
-    if ((unsigned)(a[0] >> 32) == tag && (unsigned)(b[0] >> 32) == tag) return __hiloint2double((int)(unsigned)b[0], (int)(unsigned)a[0]);
-#pragma unroll
-    for (int i = 0; i + 1 < LPMP_MBOX_PIPE; ++i) { a[i] = a[i + 1]; b[i] = b[i + 1]; }
-    a[LPMP_MBOX_PIPE - 1] = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    b[LPMP_MBOX_PIPE - 1] = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
   long long t0 = 0;
   for (int spins = 0;;) {
     const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((unsigned)(a >> 32) == tag && (unsigned)(b >> 32) == tag) return __hiloint2double((int)(unsigned)b, (int)(unsigned)a);
-#if LPMP_MBOX_SLEEP == 1
     chain_poll_pause(spins);
-#else
-    __builtin_amdgcn_s_sleep(LPMP_MBOX_SLEEP);
-#endif
-#endif
     bool own;
     if (chain_wait_expired(ca, ++spins, t0, own)) {
       chain_abort(ca, own, -1, -2, (int)(__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32), t0);   // a mailbox granule
@@ -769,6 +714,11 @@ sweep_generic_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops
 // side 0 (own label = row a):    q[a] = min_b T[a][b] + m2[b]  -> reduce over the L/2 lanes of a row
 // side 1 (own label = column b): q[b] = min_a T[a][b] + m1[a]  -> local over steps, reduce over the RPL row-lanes
 // Vectors (theta, m1, m2, delta) live one element per lane (lane g < L) and are transposed through LDS.
+// Packed for latency:
+//   * the factor's record and all its ops arrive as ONE coalesced packet (no rec -> ops dependent hop);
+//   * the tables of up to KMAX receives and the target vectors of up to 4 sends are requested before
+//     anything is reduced, so a factor's HBM round trips overlap instead of chaining
+//     (what bounds the row-major order, where a level holds only <= min(H,W) factors).
 // -------------------------------------------------------------------------------------------------
 template <int L> struct DenseCfg;
 template <> struct DenseCfg<32> { static constexpr int G = 64; };
@@ -778,132 +728,6 @@ template <> struct DenseCfg<4>  { static constexpr int G = 4; };
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
-template <int L>
-__global__ void __launch_bounds__(256)
-sweep_dense_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
-                   const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
-                   int64_t first, int64_t count, int flags) {
-  constexpr int G = DenseCfg<L>::G;
-  constexpr int CL = L / 2;            // lanes per table row
-  constexpr int RPL = 2 * G / L;       // rows per load step
-  constexpr int NL = L / RPL;          // load steps
-  constexpr int GPB = 256 / G;         // groups (factors) per block
-  static_assert(G >= L / 2 && (2 * G) % L == 0 && L % RPL == 0, "bad dense config");
-  // LDS: per group  mo[L] (other-side vector) + q[L] (min result), one group-private slab
-  __shared__ double lds_mo[GPB][L];
-  __shared__ double lds_q[GPB][L];
-  const int grp = threadIdx.x / G, g = threadIdx.x % G;
-  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
-  const bool live = idx < count;
-  const int c2 = g % CL, rl = g / CL;
-  UpdRec rec;
-  if (live) rec = recs[first + idx]; else { rec.n_recv = 0; rec.n_send = 0; rec.dual_off = 0; rec.op_begin = 0; }
-  double* own_g = dual + rec.dual_off;
-  const bool vl = live && g < L;        // this lane holds vector element g
-  double theta = vl ? own_g[g] : 0.0;
-  // every lane of a wave must run the same number of iterations (cross-lane ops inside)
-  int n_recv = rec.n_recv;
-  int max_recv = n_recv;
-  if (G < 64) {
-#pragma unroll
-    for (int m = 32; m >= G; m >>= 1) max_recv = max(max_recv, __shfl_xor(max_recv, m, 64));
-  }
-  for (int k = 0; k < max_recv; ++k) {
-    const bool act = k < n_recv;
-    Op op;
-    if (act) op = ops[rec.op_begin + k]; else { op.peer_dual = rec.dual_off; op.peer_const = 0; op.info = 0; }
-    const int side = (op.info >> 5) & 1;
-    const double* T = cdata + op.peer_const;
-    double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-    const double* mo = dual + op.peer_dual + (side == 0 ? L : 0);
-    double2_t t[NL];
-    if (act) {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) t[i] = *reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) t[i] = double2_t{0.0, 0.0};
-    }
-    const double ms_v = (act && g < L) ? ms[g] : 0.0;
-    const double mo_v = (act && g < L) ? mo[g] : 0.0;
-    if (g < L) lds_mo[grp][g] = mo_v;
-    wave_sync();
-    if (side == 0) {
-      // lane needs m2[2*c2], m2[2*c2+1]
-      const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_mo[grp][2 * c2]);
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        double v = fmin(t[i].x + mv.x, t[i].y + mv.y);
-        v = row_allreduce_min<CL>(v);
-        if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
-      }
-    } else {
-      double vx = LPMP_INF, vy = LPMP_INF;
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        const double m1v = lds_mo[grp][i * RPL + rl];
-        vx = fmin(vx, t[i].x + m1v);
-        vy = fmin(vy, t[i].y + m1v);
-      }
-#pragma unroll
-      for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
-      if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
-    }
-    wave_sync();
-    double pb = LPMP_INF;                            // peer's bound after this receive
-    if (act && g < L) {
-      const double qv = lds_q[grp][g];
-      const double delta = ms_v + qv;                // omega = 1: delta = min-marginal
-      theta += delta;                                // RepamLeft(+delta)
-      const double mn = ms_v - delta;
-      ms[g] = mn;                                    // RepamRight(-delta)
-      pb = mn + qv;
-    }
-    pb = vec_min<G, L>(pb);
-    if (act && g == 0) lb[op.peer] = pb;
-    wave_sync();
-  }
-  if (flags & SWEEP_PRIMAL) {
-    const int lab = group_argmin<G, L>(theta, vl, g);
-    if (live && g == 0 && (rec.kind_flags & UPD_PRIMAL)) store_label(primal, rec.factor, L, lab);
-  }
-  // sends: delta = omega * theta_snapshot; peer += delta; theta -= delta
-  if (vl) {
-    const double snap = theta;
-    for (int k = 0; k < rec.n_send; ++k) {
-      const Op op = ops[rec.op_begin + rec.n_recv + k];
-      const int side = (op.info >> 5) & 1;
-      double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-      const double delta = op.omega * snap;
-      ms[g] += delta;
-      theta -= delta;
-      if (g == 0) lb[op.peer] = LPMP_NAN;
-    }
-    if (flags & SWEEP_RESIDUAL) {   // second round from the live factor with the running weight sum
-      double residual = 0.0;
-      for (int k = 0; k < rec.n_send; ++k) {
-        const Op op = ops[rec.op_begin + rec.n_recv + k];
-        const int side = (op.info >> 5) & 1;
-        double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-        residual += op.omega;
-        const double delta = residual * theta;
-        ms[g] += delta;
-        theta -= delta;
-      }
-    }
-    own_g[g] = theta;
-  }
-  { const double ob = vec_min<G, L>(vl ? theta : LPMP_INF); if (live && g == 0) lb[rec.factor] = ob; }
-}
-
-
-// -------------------------------------------------------------------------------------------------
-// Dense fast path, packed form (v2).  Same arithmetic as sweep_dense_kernel, restructured for latency:
-//   * the factor's record and all its ops arrive as ONE coalesced packet (no rec -> ops dependent hop);
-//   * the tables of up to KMAX receives and the target vectors of up to 4 sends are requested before
-//     anything is reduced, so a factor's HBM round trips overlap instead of chaining
-//     (what bounds the row-major order, where a level holds only <= min(H,W) factors).
-// -------------------------------------------------------------------------------------------------
 template <int G, class T> __device__ __forceinline__ T uni(T v) {
   if constexpr (G == 64 && sizeof(T) == 4) return (T)__builtin_amdgcn_readfirstlane((int)v);
   else return v;
@@ -1007,11 +831,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
         if constexpr (CHAIN) sm[k] = ld_dual<A>(s_ms[k] + g);
         else {
           const Op& o = lop[n_recv + k];
-#ifdef LPMP_ABLATE_SEND_VEC
-          sm[k] = (double)o.peer_dual * 1e-300;
-#else
           sm[k] = ld_dual<A>(dual + uni64<G>(o.peer_dual) + (((uni<G>(o.info) >> 5) & 1) ? (VAR ? uni<G>(o.pd0) : L) : 0) + g);
-#endif
         }
       }
     }
@@ -1080,11 +900,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
         } else {
           roff[j] = side[j] == 0 ? 0 : L;
 #pragma unroll
-#ifdef LPMP_ABLATE_TABLE      // timing experiments only (tools/build_variant.sh): results are wrong
-          for (int i = 0; i < NL; ++i) t[j][i] = double2_t{(double)(uintptr_t)T * 1e-300, 0.0};
-#else
           for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<NT>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
-#endif
         }
       } else {
 #pragma unroll
@@ -1103,12 +919,8 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           if (g < Lr) msv[j] = ld_dual<A>(dual + pdual[j] + roff[j] + g);
           if (!(MBOX && box[j]) && g < (side[j] == 0 ? dC[j] : dR[j])) mov[j] = ld_dual<A>(dual + pdual[j] + (side[j] == 0 ? dR[j] : 0) + g);
         } else if (g < L) {
-#ifdef LPMP_ABLATE_RECV_VEC
-          msv[j] = (double)pdual[j] * 1e-300; mov[j] = 0.0;
-#else
           msv[j] = ld_dual<A>(dual + pdual[j] + (side[j] == 0 ? 0 : L) + g);
           if (!(MBOX && box[j])) mov[j] = ld_dual<A>(dual + pdual[j] + (side[j] == 0 ? L : 0) + g);
-#endif
         }
       }
     }
@@ -1140,9 +952,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
           double v = fmin(t[j][i].x + mv.x, t[j][i].y + mv.y);
-#ifndef LPMP_ABLATE_REDUCE
           v = row_allreduce_min<CL>(v);
-#endif
           if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
         }
       } else {
@@ -1153,10 +963,8 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           vx = fmin(vx, t[j][i].x + m1v);
           vy = fmin(vy, t[j][i].y + m1v);
         }
-#ifndef LPMP_ABLATE_REDUCE
 #pragma unroll
         for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
-#endif
         if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
       }
       wave_sync();
@@ -1175,13 +983,8 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
             stored = true;
           }
         }
-#ifndef LPMP_ABLATE_RECV_VEC
         if (!stored) st_dual<A>(dual + pdual[j] + roff[j] + g, mn);
-#else
-        if (!stored && mn == 1.2345e-280) st_dual<A>(dual + pdual[j] + roff[j] + g, mn);
-#endif
       }
-#ifndef LPMP_ABLATE_LB_TRACK
       {
         const bool track = !(FW && defer[j]);     // a deferred receive is followed by a send that dirties the peer
         const bool hist = CHAIN && hmode == HIST_MID;   // ... but its bound at the seam between two passes is this one
@@ -1197,7 +1000,6 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           }
         }
       }
-#endif
       wave_sync();
     }
   };
@@ -1216,7 +1018,6 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     const int lab = group_argmin<G, L>(theta, vl, g);
     if (live && g == 0 && (uni<G>(hdr->kind_flags) & UPD_PRIMAL)) store_label(primal, uni<G>(hdr->factor), Lr, lab);
   }
-#ifndef LPMP_ABLATE_LB_TRACK
   // Bound of a pairwise peer after a SEND that follows this record's receive through the same vector (plan.cpp marks the pair:
   // Op::pad of the send = index of that receive + 1).  The receive left m_s = -q (q[a] = min_b T[a][b] + m_o[b], up to the
   // rounding of m_s - (m_s + q)), nothing else of the peer moved since, and the send adds omega * theta_snap: the peer's
@@ -1236,11 +1037,6 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     }
   }
   const bool send_bounds = !MBOX && !(flags & SWEEP_RESIDUAL);   // (the residual rule adds to the sent vectors once more)
-#define LPMP_SNAP_MIN (lds_q[grp][0])
-#else
-  const bool send_bounds = false;
-#define LPMP_SNAP_MIN 0.0
-#endif
   if (vl && !aborted) {
     const double snap = theta;
     if constexpr (CHAIN) {
@@ -1263,11 +1059,9 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           if constexpr (MBOX) { if (s_box[k] && !(flags & SWEEP_RESIDUAL)) mailbox_put(s_box[k] + 2 * g, cur + delta, ca->epoch); }
           st_dual<A>(s_ms[k] + g, cur + delta);
           theta -= delta;
-#ifndef LPMP_ABLATE_LB_TRACK
           // a vector that goes to the mailbox has a reader later in this launch, which sets the peer's tracked bound itself
           // — and is not ordered after THIS store, so it is left out
-          if (g == 0 && !(MBOX && s_box[k])) st_lb<A>(lb + s_peer[k], fw > 0 && send_bounds ? s_om[k] * LPMP_SNAP_MIN : LPMP_NAN);
-#endif
+          if (g == 0 && !(MBOX && s_box[k])) st_lb<A>(lb + s_peer[k], fw > 0 && send_bounds ? s_om[k] * lds_q[grp][0] : LPMP_NAN);
         }
       }
       if constexpr (MBOX) chain_stamp(*ca, ticket, 6);   // first sends issued (the mailbox has them)
@@ -1282,14 +1076,9 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           if (fw > 0) cur = fw == 1 ? mnew[0] : fw == 2 ? mnew[NFW > 1 ? 1 : 0] : fw == 3 ? mnew[NFW > 2 ? 2 : 0] : mnew[NFW > 3 ? 3 : 0];
           else cur = preload_ok ? sm[k] : ld_dual<A>(ms + g);
           const double delta = o.omega * snap;
-#ifdef LPMP_ABLATE_SEND_VEC
-          if (cur + delta == 1.2345e-280)
-#endif
           st_dual<A>(ms + g, cur + delta);
           theta -= delta;
-#ifndef LPMP_ABLATE_LB_TRACK
-          if (g == 0) st_lb<A>(lb + uni<G>(o.peer), fw > 0 && send_bounds ? o.omega * LPMP_SNAP_MIN : LPMP_NAN);
-#endif
+          if (g == 0) st_lb<A>(lb + uni<G>(o.peer), fw > 0 && send_bounds ? o.omega * lds_q[grp][0] : LPMP_NAN);
         }
       }
     }
@@ -1308,20 +1097,13 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
           const Op& o = lop[n_recv + k0 + q];
           msk[q] = dual + o.peer_dual + (((o.info >> 5) & 1) ? (VAR ? o.pd0 : L) : 0);
           om[q] = o.omega; pr[q] = o.peer;
-#ifdef LPMP_ABLATE_SEND_VEC
-          cur[q] = (double)o.peer_dual * 1e-300;
-#else
           cur[q] = ld_dual<A>(msk[q] + g);
-#endif
         }
       }
 #pragma unroll
       for (int q = 0; q < SC; ++q) {
         if (k0 + q < n_send) {
           const double delta = om[q] * snap;
-#ifdef LPMP_ABLATE_SEND_VEC
-          if (cur[q] + delta == 1.2345e-280)
-#endif
           st_dual<A>(msk[q] + g, cur[q] + delta);
           theta -= delta;
           if (g == 0) st_lb<A>(lb + pr[q], LPMP_NAN);
@@ -1343,7 +1125,6 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     }
     st_dual<A>(own_g + g, theta);
   }
-#ifndef LPMP_ABLATE_LB_TRACK
   if constexpr (MBOX) {
     // (a peer this record also SENDS to ends up stale: the send's mark must be the last word, so its bound is not stored)
 #pragma unroll
@@ -1364,20 +1145,10 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
       if constexpr (CHAIN) { if (hmode == HIST_END) st_lb<A>(lbh + uni<G>(hdr->factor), ob); }
     }
   }
-#endif
 }
 
-// experiments (tools/build_variant.sh): receives in flight per lane group of the 16-label class, minimum waves per SIMD
-#ifndef LPMP_KMAX16
-#define LPMP_KMAX16 2
-#endif
-#ifdef LPMP_PK_WPE
-#define LPMP_PK_BOUNDS __launch_bounds__(256, LPMP_PK_WPE)
-#else
-#define LPMP_PK_BOUNDS __launch_bounds__(256)
-#endif
 template <int L, int KMAX, bool VAR, bool NT>
-__global__ void LPMP_PK_BOUNDS
+__global__ void __launch_bounds__(256)
 sweep_dense_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
                       double* __restrict__ dual, const double* __restrict__ cdata, double* __restrict__ lb,
                       int32_t* __restrict__ primal, int64_t count, int stride, int flags) {
@@ -1409,9 +1180,6 @@ __device__ __forceinline__ void chain_loop(const ChainArgs& ca, const ChainLaunc
   }
 }
 // MBOX: a chain whose launches all carry CHAIN_LAUNCH_MAILBOX (plan.cpp marks every launch of such a chain)
-#ifndef LPMP_MBOX_WPE
-#define LPMP_MBOX_WPE 1
-#endif
 // The same loop for mailbox chains, where a level is a couple of microseconds and what a workgroup needs before it can
 // even request its records — ticket number (an atomic on the far side of the fabric), then the ticket's launch, block and
 // dependency count (three arrays streamed from HBM once per launch: a miss each) — was 3.5 us of round trips in a row per
@@ -1451,7 +1219,7 @@ __device__ __forceinline__ void chain_loop_ahead(const ChainArgs& ca, const Chai
 // (the exact 32-label body needs 167-171 VGPRs depending on small things: three waves per SIMD are asked for, so that it stays
 // at the 170 that allows them — the joined passes of the headline grid lose 8 % at two)
 template <int L, int KMAX, bool VAR, bool NT, bool MBOX>
-__global__ void __launch_bounds__(256, MBOX ? LPMP_MBOX_WPE : (L == 32 && !VAR ? 3 : 1))
+__global__ void __launch_bounds__(256, !MBOX && L == 32 && !VAR ? 3 : 1)
 chain_dense_pk_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual,
                       const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal, int flags) {
   if constexpr (MBOX) {
@@ -1573,17 +1341,12 @@ __device__ __forceinline__ void label_ops_body(const ChainLaunch& ln, int64_t fi
       for (int r = 0; r < SMALL_MAXD; ++r) if (r < o.pd0 && tv[r] < nl) st_dual<A>(peer + r, R[r] + +1.0 * D[q][j][tv[r]]);
     }
   } else {
-  // the host marks the records none of whose sends goes to a peer one of its receives rewrites (UPD_PRELOAD_OK, plan.cpp);
-  // where every record of this wave's eight is one, lane j requests the costs of ITS send's peer together with those of its receive's
-  // peer — one round trip instead of two — and the stores of the receives need not be drained before the sends
-  bool pre = false;
-  if constexpr (STAGED) pre = __all(!live || (rec.kind_flags & UPD_PRELOAD_OK) != 0) != 0;
+  static_assert(!STAGED, "the staged form of the general case is label_ops_body_staged");
   Op o2; int tv2[SMALL_MAXD]; double R2[SMALL_MAXD];
   {   // round 1: the receives, lane j = receive j
     const bool recv = live && j < n_recv;
     Op o; int tv[SMALL_MAXD]; double R[SMALL_MAXD];
     load_op(recv, j, o, tv, R);
-    if (pre) load_op(live && j < n_send, n_recv + j, o2, tv2, R2);
     if (recv) {
       const int nl = o.pd1;
       double* peer = dual + o.peer_dual;
@@ -1601,15 +1364,14 @@ __device__ __forceinline__ void label_ops_body(const ChainLaunch& ln, int64_t fi
       for (int r = 0; r < SMALL_MAXD; ++r) if (r < o.pd0 && tv[r] < nl) st_dual<A>(peer + r, R[r] + -1.0 * D[q][j][tv[r]]);
     }
   }
-  if constexpr (STAGED) { if (first == 0) level_stamp(pre ? 1 : 2); }      // (tools/level_trace.py: receives issued; slot 1 when the sends' peers came along)
-  if (!pre) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a send of this record may go to the peer a receive has just rewritten
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a send of this record may go to the peer a receive has just rewritten
   wave_sync();
   for (int k = 0; k < n_recv; ++k) if (j < on) theta += +1.0 * D[q][k][j];   // own(i) += +1.0 * dl(i), receive by receive
   if (live && j < on) S[q][j] = theta;                                        // the state every send starts from
   wave_sync();
   {   // round 2: the sends, lane j = send j
     const bool send = live && j < n_send;
-    if (!pre) load_op(send, n_recv + j, o2, tv2, R2);
+    load_op(send, n_recv + j, o2, tv2, R2);
     if (send) {
       const int nl = o2.pd1;
       double* peer = dual + o2.peer_dual;
@@ -1827,11 +1589,7 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
         else ln = launches[l];
         if (sl.count >= 0) {                         // records, ops and match tables from LDS
           if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED_DEV) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true, true>(ln, first, dual, tabs, lb, D[wave], S[wave], &sl); }
-#ifdef LPMP_LL_OLD_BODY
-          else { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, false, true>(ln, first, dual, tabs, lb, D[wave], S[wave], &sl); }
-#else
           else { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body_staged<ACC_WG>(sl, first, dual, lb, D[wave], S[wave], RS[wave]); }
-#endif
         } else if ((ln.pad & CHAIN_LAUNCH_LABEL_OPS_DEV) && plain_rule) {
           if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED_DEV) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true>(ln, first, dual, tabs, lb, D[wave], S[wave]); }
           else { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, false>(ln, first, dual, tabs, lb, D[wave], S[wave]); }
@@ -1861,97 +1619,9 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
 // Potts fast path: L lanes per unary factor; peers are pairwise_potts_factor(L, diff).
 // min_b (diff*[a!=b] + m_o[b]) = min(m_o[a], diff + min_{b != a} m_o[b]), with min_{b != a} from the two
 // smallest entries of m_o (reference vector::two_min, vector.hxx:348-443).
-// -------------------------------------------------------------------------------------------------
-template <int L>
-__global__ void __launch_bounds__(256)
-sweep_potts_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
-                   const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
-                   int64_t first, int64_t count, int flags) {
-  constexpr int GPB = 256 / L;
-  const int grp = threadIdx.x / L, g = threadIdx.x % L;
-  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
-  const bool live = idx < count;
-  UpdRec rec;
-  if (live) rec = recs[first + idx]; else { rec.n_recv = 0; rec.n_send = 0; rec.dual_off = 0; rec.op_begin = 0; }
-  double* own_g = dual + rec.dual_off;
-  double theta = live ? own_g[g] : 0.0;
-  int n_recv = rec.n_recv, max_recv = rec.n_recv;
-#pragma unroll
-  for (int m = 32; m >= L; m >>= 1) max_recv = max(max_recv, __shfl_xor(max_recv, m, 64));
-  for (int k = 0; k < max_recv; ++k) {
-    const bool act = k < n_recv;
-    Op op;
-    if (act) op = ops[rec.op_begin + k]; else { op.peer_dual = rec.dual_off; op.peer_const = 0; op.info = 0; }
-    const int side = (op.info >> 5) & 1;
-    double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-    const double* mo = dual + op.peer_dual + (side == 0 ? L : 0);
-    const double diff = act ? cdata[op.peer_const] : 0.0;
-    const double ms_v = act ? ms[g] : 0.0;
-    const double mo_v = act ? mo[g] : 0.0;
-    // two smallest of mo over the group (multiset semantics)
-    double a1 = mo_v, a2 = LPMP_INF;
-#pragma unroll
-    for (int m = L / 2; m >= 1; m >>= 1) {
-      const double b1 = shfl_xor_f64(a1, m), b2 = shfl_xor_f64(a2, m);
-      const double n1 = fmin(a1, b1);
-      const double n2 = fmin(fmax(a1, b1), fmin(a2, b2));
-      a1 = n1; a2 = n2;
-    }
-    // exactly one lane may take the role of "the" minimum: the lowest lane holding a1
-    const unsigned long long holders = __ballot(mo_v == a1);
-    const int grp_shift = (threadIdx.x & 63) - g;
-    const unsigned long long gmask = (L == 64 ? ~0ull : ((1ull << L) - 1ull)) << grp_shift;
-    const int first_holder = __ffsll((long long)(holders & gmask)) - 1;
-    const double min_except = ((int)(threadIdx.x & 63) == first_holder) ? a2 : a1;
-    double pb = LPMP_INF;
-    if (act) {
-      const double q = fmin(0.0 + mo_v, diff + min_except);
-      const double delta = ms_v + q;
-      theta += delta;
-      const double mn = ms_v - delta;
-      ms[g] = mn;
-      pb = mn + q;
-    }
-    pb = vec_min<L, L>(pb);
-    if (act && g == 0) lb[op.peer] = pb;
-  }
-  if (flags & SWEEP_PRIMAL) {
-    const int lab = group_argmin<L, L>(theta, live, g);
-    if (live && g == 0 && (rec.kind_flags & UPD_PRIMAL)) store_label(primal, rec.factor, L, lab);
-  }
-  if (live) {
-    const double snap = theta;
-    for (int k = 0; k < rec.n_send; ++k) {
-      const Op op = ops[rec.op_begin + rec.n_recv + k];
-      const int side = (op.info >> 5) & 1;
-      double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-      const double delta = op.omega * snap;
-      ms[g] += delta;
-      theta -= delta;
-      if (g == 0) lb[op.peer] = LPMP_NAN;
-    }
-    if (flags & SWEEP_RESIDUAL) {   // second round from the live factor with the running weight sum
-      double residual = 0.0;
-      for (int k = 0; k < rec.n_send; ++k) {
-        const Op op = ops[rec.op_begin + rec.n_recv + k];
-        const int side = (op.info >> 5) & 1;
-        double* ms = dual + op.peer_dual + (side == 0 ? 0 : L);
-        residual += op.omega;
-        const double delta = residual * theta;
-        ms[g] += delta;
-        theta -= delta;
-      }
-    }
-    own_g[g] = theta;
-  }
-  { const double ob = vec_min<L, L>(live ? theta : LPMP_INF); if (live && g == 0) lb[rec.factor] = ob; }
-}
-
-
-// -------------------------------------------------------------------------------------------------
-// Potts fast path, packed form: as sweep_potts_kernel, with the factor's record + ops in one packet and the
-// vectors / coupling of up to 4 receives and 4 sends requested before anything is reduced (a 512 x 512 grid is
-// launch-latency bound: what counts is the length of one factor's dependent chain).
+// Packed like the dense path: the factor's record + ops in one packet, the vectors / coupling of up to 4 receives
+// and 4 sends requested before anything is reduced (a 512 x 512 grid is launch-latency bound: what counts is the
+// length of one factor's dependent chain).
 // -------------------------------------------------------------------------------------------------
 template <int L>
 __device__ __forceinline__ void two_min_merge(double& a1, double& a2) {   // two smallest over the L-lane group (multiset)
@@ -2597,7 +2267,7 @@ lb_collect_stale_kernel(const double* __restrict__ lb, int64_t n, int32_t* __res
     if (lb[i] != lb[i]) list[atomicAdd(counter, 1ull)] = (int32_t)i;
 }
 
-// dense L x L pairwise bound with the streaming layout of sweep_dense_kernel (G lanes per factor)
+// dense L x L pairwise bound with the table layout of the dense fast path (G lanes per factor, DenseCfg)
 template <int L>
 __global__ void __launch_bounds__(256)
 dense_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
@@ -2712,14 +2382,6 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
   if (count <= 0) return;
   auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
   switch (kclass) {
-    case KC_DENSE_32: hipLaunchKernelGGL(sweep_dense_kernel<32>, blocks(256 / DenseCfg<32>::G), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_DENSE_16: hipLaunchKernelGGL(sweep_dense_kernel<16>, blocks(256 / DenseCfg<16>::G), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_DENSE_8: hipLaunchKernelGGL(sweep_dense_kernel<8>, blocks(256 / DenseCfg<8>::G), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_DENSE_4: hipLaunchKernelGGL(sweep_dense_kernel<4>, blocks(256 / DenseCfg<4>::G), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_POTTS_32: hipLaunchKernelGGL(sweep_potts_kernel<32>, blocks(256 / 32), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_POTTS_16: hipLaunchKernelGGL(sweep_potts_kernel<16>, blocks(256 / 16), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_POTTS_8: hipLaunchKernelGGL(sweep_potts_kernel<8>, blocks(256 / 8), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
-    case KC_POTTS_4: hipLaunchKernelGGL(sweep_potts_kernel<4>, blocks(256 / 4), dim3(256), 0, s, recs, ops, dual, cdata, lb, primal, first, count, flags); break;
     case KC_DENSE_BIG:
       if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
       else hipLaunchKernelGGL(sweep_dense_big_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
@@ -2732,7 +2394,6 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
 bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
                          double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s) {
   if (count <= 0) return true;
-  if (stride > 1 + PK_MAX_OPS) return false;
   auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
   const bool nt = (flags & SWEEP_NT) != 0;
   if (kc_is_pw(kclass)) {
@@ -2752,7 +2413,7 @@ bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, cons
   switch (kclass) {
     // receives in flight per lane group: 2 at 16 / 32 labels (1 and 4 measured slower on C3), 4 below
     case KC_DENSE_32: PK_LAUNCH(32, 2); return true;
-    case KC_DENSE_16: PK_LAUNCH(16, LPMP_KMAX16); return true;
+    case KC_DENSE_16: PK_LAUNCH(16, 2); return true;
     case KC_DENSE_8: PK_LAUNCH(8, 4); return true;
     case KC_DENSE_4: PK_LAUNCH(4, 4); return true;
 #define PPK_LAUNCH1(LL, NTT) hipLaunchKernelGGL((sweep_potts_pk_kernel<LL, false, NTT>), blocks(256 / LL), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags)
@@ -2819,10 +2480,7 @@ bool launch_chain(int kclass, int flags, const void* chain_args, const void* lau
   switch (kclass) {
     case KC_GENERIC: { auto k = chain_generic_kernel<64>; hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, GenCtx<64>::THREADS)), dim3(GenCtx<64>::THREADS), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; }
     case KC_SMALL: { auto k = chain_generic_kernel<1>; hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, GenCtx<1>::THREADS)), dim3(GenCtx<1>::THREADS), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; }
-#ifndef LPMP_MBOX_KMAX32           // experiments: receives in flight per record of the 32-label mailbox chain
-#define LPMP_MBOX_KMAX32 2
-#endif
-    case KC_DENSE_32: if (ca.mailbox) CHAIN_LAUNCH2(32, LPMP_MBOX_KMAX32, false, false, true); else CHAIN_LAUNCH(32, 2); return true;
+    case KC_DENSE_32: CHAIN_LAUNCH(32, 2); return true;
     case KC_DENSE_16: CHAIN_LAUNCH(16, 2); return true;
     case KC_DENSE_8: CHAIN_LAUNCH(8, 4); return true;
     case KC_DENSE_4: CHAIN_LAUNCH(4, 4); return true;

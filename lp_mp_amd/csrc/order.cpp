@@ -37,9 +37,7 @@ RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t
   LevelRange h, w, k, t;
   if (!only_launch(fb, 1, h) || !only_launch(fb, 2, w) || !only_launch(fb, 3, t) || !only_launch(bf, 2, k)) return ri;
   const int kc = w.kclass;
-  if (h.kclass != kc || k.kclass != kc || t.kclass != kc || !kc_chain_capable(kc) || kc_width(kc) == 0) return ri;
-
-  if (h.stride == 0 || w.stride == 0 || k.stride == 0 || t.stride == 0) return ri;
+  if (h.kclass != kc || k.kclass != kc || t.kclass != kc || !kc_is_packed(kc)) return ri;
   ri.kclass = kc; ri.gpb = kc_block_records(kc);
   const LevelRange* lrs[4] = {&h, &w, &k, &t};
   const Schedule* sch[4] = {&fb, &fb, &bf, &fb};

@@ -657,7 +657,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     const bool pow = d0 == 4 || d0 == 8 || d0 == 16 || d0 == 32;
     // more ops than the LDS slab of a lane group holds (a hub of a random graph: C4 has a few 30-neighbour variables among
     // 2 M): such a RECORD goes to the op-by-op streaming kernel — left in its class it took its whole launch off the packed
-    // kernels (21 of C4's 44 launches per pass ran on sweep_dense_kernel<16>: 5.5 of 12.6 ms, profiles/r03_c4a_*)
+    // kernels (21 of C4's 44 launches per pass ran on the unpacked 16-label kernel of the time: 5.5 of 12.6 ms, profiles/r03_c4a_*)
     if (pow && (all_dense[u] || all_potts[u]) && n_recv_of[u] + n_send_of[u] > (all_dense[u] ? pk_dense_cap(d0) : pk_indirect_cap(d0)) && up_any[u]) return KC_DENSE_BIG;
     if (pow && all_dense[u]) return d0 == 4 ? KC_DENSE_4 : d0 == 8 ? KC_DENSE_8 : d0 == 16 ? KC_DENSE_16 : KC_DENSE_32;
     if (pow && all_potts[u]) return d0 == 4 ? KC_POTTS_4 : d0 == 8 ? KC_POTTS_8 : d0 == 16 ? KC_POTTS_16 : KC_POTTS_32;
@@ -802,18 +802,12 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       continue;
     }
     if (lr.kclass == KC_SMALL) {
-      // lane-per-factor records: no send goes to a peer one of the record's receives rewrites -> the level loop's staged
-      // labeling body may request the send peers' costs together with the receive peers' (kernels.hip, label_ops_body)
       for (int64_t i = lr.begin; i < lr.end; ++i) {
-        UpdRec& r = out.recs[i];
-        const Op* o = out.ops.data() + r.op_begin;
-        bool ok = true;
-        for (int a = 0; a < r.n_recv && ok; ++a)
-          for (int b = r.n_recv; b < r.n_recv + r.n_send; ++b) if (o[a].peer_dual == o[b].peer_dual) { ok = false; break; }
-        if (ok) r.kind_flags |= UPD_PRELOAD_OK;
+        const UpdRec& r = out.recs[i];
         // a send into the peer ONE receive of the record has just rewritten (labeling lists: the middle variables of a
-        // triplet): the staged body hands the rewritten costs over in LDS — receive: pad = 1 (no store), send: pad = index
-        // of that receive + 1.  Only a hint: the op-by-op bodies store and reload.
+        // triplet): the level loop's staged body (kernels.hip, label_ops_body_staged) hands the rewritten costs over in
+        // LDS — receive: pad = 1 (no store), send: pad = index of that receive + 1.  Only a hint: the op-by-op bodies
+        // store and reload.
         Op* ow = out.ops.data() + r.op_begin;
         for (int b = r.n_recv; b < r.n_recv + r.n_send; ++b) {
           int hit = -1, n_hit = 0, n_same = 0;
@@ -824,7 +818,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       }
       continue;
     }
-    if (lr.kclass == KC_GENERIC || lr.kclass >= KC_DENSE_BIG) continue;   // packed dense and Potts classes
+    if (!kc_is_packed(lr.kclass)) continue;
     auto same_vec = [](const Op* o, int a, int b) { return o[a].peer_dual == o[b].peer_dual && ((o[a].info >> 5) & 1) == ((o[b].info >> 5) & 1); };
     if (kc_is_var(lr.kclass)) {
       // the padded classes only exist in packed / indirect form: what those cannot run goes to the streaming kernel
@@ -843,9 +837,9 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     }
     // flags of the records (independent of each other: chunks of the launch on several threads), then the packet stride
     const int64_t n_lr = lr.end - lr.begin;
-    std::vector<int> kmax_of(PLAN_MAX_THREADS, 0); std::vector<uint8_t> dup_of(PLAN_MAX_THREADS, 0);
+    std::vector<int> kmax_of(PLAN_MAX_THREADS, 0);
     parallel_chunks(n_lr, 32768, [&](int64_t c0, int64_t c1, int thread) {
-      int kmax_l = 0; bool dup_l = false;
+      int kmax_l = 0;
       for (int64_t i = lr.begin + c0; i < lr.begin + c1; ++i) {
         UpdRec& r = out.recs[i];
         Op* o = out.ops.data() + r.op_begin;
@@ -856,11 +850,6 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
           for (int b = r.n_recv; b < r.n_recv + r.n_send; ++b)
             if (same(a, b)) { preload_ok = false; break; }
         if (preload_ok) r.kind_flags |= UPD_PRELOAD_OK;
-        // two receives, or two sends, into one vector (duplicate messages between the same two factors)
-        for (int a = 0; a < r.n_recv && !dup_l; ++a)
-          for (int a2 = a + 1; a2 < r.n_recv; ++a2) if (same(a, a2)) { dup_l = true; break; }
-        for (int b = r.n_recv; b < r.n_recv + r.n_send && !dup_l; ++b)
-          for (int b2 = b + 1; b2 < r.n_recv + r.n_send; ++b2) if (same(b, b2)) { dup_l = true; break; }
         // register forwarding: send b targets the vector receive a (one of the first 4) has just rewritten ->
         // the receive keeps its result in a register (pad = 1: no store) and the send reads it from there
         // (pad = a + 1); at most one send per receive, and only if no other receive/send touches that vector
@@ -871,13 +860,13 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
           if (n_hit == 1 && n_send_same == 1 && hit < 4) { o[hit].pad = 1; o[b].pad = hit + 1; }
         }
       }
-      kmax_of[(size_t)thread] = kmax_l; dup_of[(size_t)thread] = dup_l;
+      kmax_of[(size_t)thread] = kmax_l;
     });
-    int kmax = 0; bool dup_recv = false;
-    for (int t = 0; t < PLAN_MAX_THREADS; ++t) { kmax = std::max(kmax, kmax_of[(size_t)t]); dup_recv = dup_recv || dup_of[(size_t)t]; }
-    if (dup_recv) continue;                  // only the op-by-op kernels are safe for that: stride stays 0
-    if (kmax > PK_MAX_OPS) {                 // too many ops for a packet: indirect mode if they fit the LDS slab
-      if (kmax <= pk_class_cap(lr.kclass)) lr.stride = -1;
+    const int kmax = *std::max_element(kmax_of.begin(), kmax_of.end());
+    // (records with duplicate messages or more ops than the LDS slab holds never get here: cls_of gives them an op-by-op class)
+    if (kmax > pk_class_cap(lr.kclass)) fail("internal: a record of a packed class has more ops than its LDS slab holds");
+    if (kmax > PK_MAX_OPS) {                 // too many ops for a packet: indirect mode
+      lr.stride = -1;
       continue;
     }
     lr.stride = 1 + kmax;
@@ -938,7 +927,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     bool ok = true;
     for (const auto& lr : out.launches) {
       n_launches_of[lr.kclass]++;
-      ok = ok && kc_chain_capable(lr.kclass) && (kc_width(lr.kclass) == 0 || lr.stride != 0);
+      ok = ok && kc_chain_capable(lr.kclass);
       // lane-per-factor and generic records: every dual access of a chain kernel is a device-scope access that goes past
       // the L2, and these bodies issue them one dependent access at a time — measured slower than replaying a hipGraph
       // of plain launches (C5: 202 ms against 188 ms per pass).  The kernels stay available: LPMP_CHAIN_ALL=1

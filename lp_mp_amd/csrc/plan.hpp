@@ -98,6 +98,8 @@ constexpr int kc_width(int kclass) {
 }
 constexpr bool kc_is_dense(int kclass) { return (kclass >= KC_DENSE_4 && kclass <= KC_DENSE_32) || (kclass >= KC_DENSE_V4 && kclass <= KC_DENSE_V32); }
 constexpr bool kc_is_var(int kclass) { return kclass >= KC_DENSE_V4 && kclass <= KC_POTTS_V32; }
+// the unary classes of the packed kernels: every launch of one has packets or indirect records (LevelRange::stride != 0)
+constexpr bool kc_is_packed(int kclass) { return kclass >= KC_DENSE_4 && kclass <= KC_POTTS_V32; }
 
 struct LevelRange {            // one kernel launch: a range of UpdRec indices of one level and class
   int32_t kclass; int64_t begin, end;
@@ -105,7 +107,7 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   int64_t n_recv = 0, n_send = 0, bytes = 0;   // active receives / sends / algorithmic bytes of the range
   // packed form (fast classes with few ops per factor): factor i of the range has its UpdRec in slot
   // pk_begin + i*stride of Schedule::packets and its ops in the following slots -> one coalesced load, no
-  // dependent rec -> ops hop.  stride 0: not packed.
+  // dependent rec -> ops hop.  stride < 0: indirect mode (below).  stride 0: an op-by-op class (generic, streaming, lane per factor).
   int32_t stride = 0; int64_t pk_begin = 0;
   int32_t max_dim = 0;                          // largest label count of any vector or table side the launch's records touch
 };
@@ -118,10 +120,7 @@ constexpr int pk_indirect_cap(int labels) { return labels >= 16 ? 32 : labels >=
 // occupancy the dense kernel's registers allow anyway — so the hubs of a random graph of mean degree 10 stay on the packed
 // kernel (as launches of their own on the streaming kernel they cost C4 1.5 of 13.4 ms per pass, profiles/r03_c4b_*).
 // The Potts kernels (more waves per SIMD) keep the smaller slab.
-#ifndef LPMP_PK_DENSE_CAP16          // experiments (tools/build_variant.sh)
-#define LPMP_PK_DENSE_CAP16 64
-#endif
-constexpr int pk_dense_cap(int labels) { return labels == 16 ? LPMP_PK_DENSE_CAP16 : pk_indirect_cap(labels); }
+constexpr int pk_dense_cap(int labels) { return labels == 16 ? 64 : pk_indirect_cap(labels); }
 constexpr int pk_class_cap(int kclass) { return kc_is_dense(kclass) ? pk_dense_cap(kc_width(kclass)) : pk_indirect_cap(kc_width(kclass)); }
 constexpr int32_t UPD_PRELOAD_OK = 1 << 16;   // UpdRec::kind_flags: no send targets a vector a receive writes
 constexpr int32_t UPD_PRIMAL = 1 << 17;       // UpdRec::kind_flags: the factor type has COMPUTE_PRIMAL_SOLUTION
@@ -150,10 +149,7 @@ constexpr int32_t CHAIN_LAUNCH_LABEL_PAIRED = 2;  // ... and in every record sen
 constexpr int32_t CHAIN_LAUNCH_MAILBOX = 1 << 30;
 // the sends of a record that may go to the mailbox = the sends (and forwarded receives) the mailbox form of the dense body
 // holds in registers (kernels.hip: KS, NFW)
-#ifndef LPMP_MBOX_KS
-#define LPMP_MBOX_KS 4
-#endif
-constexpr int MAILBOX_SENDS = LPMP_MBOX_KS;
+constexpr int MAILBOX_SENDS = 4;
 constexpr int32_t CHAIN_LAUNCH_LABEL_OPS = 1;   // level loop: every record a vector factor whose ops are labeling messages with it on the left, <= 8 receives and <= 8 sends, no two of a kind on one peer
 struct ChainPlan {
   bool valid = false;
@@ -179,7 +175,7 @@ constexpr int kc_block_records(int kclass) {
   const bool dense = (kclass >= KC_DENSE_4 && kclass <= KC_DENSE_32) || (kclass >= KC_DENSE_V4 && kclass <= KC_DENSE_V32);
   return dense ? (w == 32 ? 4 : 256 / w) : 256 / w;   // dense: G = 64 lanes at 32 labels, else one lane per label
 }
-constexpr bool kc_chain_capable(int kclass) { return (kclass >= KC_DENSE_4 && kclass <= KC_POTTS_V32) || kclass == KC_GENERIC || kclass == KC_SMALL; }
+constexpr bool kc_chain_capable(int kclass) { return kc_is_packed(kclass) || kclass == KC_GENERIC || kclass == KC_SMALL; }
 constexpr int64_t CHAIN_MIN_LAUNCHES = 9;   // shorter schedules run as plain launches
 
 // vectors of op records are hundreds of megabytes at the headline size and every element is written right after the

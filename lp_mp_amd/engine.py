@@ -19,8 +19,8 @@ N_KCLASS = 23
 KCLASS_NAMES = ["generic", "dense4", "dense8", "dense16", "dense32", "potts4", "potts8", "potts16", "potts32",
                 "dense_v4", "dense_v8", "dense_v16", "dense_v32", "potts_v4", "potts_v8", "potts_v16", "potts_v32",
                 "dense_big", "small", "pairwise4", "pairwise8", "pairwise16", "pairwise32"]
-# kernel symbols as rocprofv3 prints them: dense classes run the packed kernel (KMAX 2 at L >= 16, 4 below) whenever a
-# launch's factors have at most 8 active messages, else sweep_dense_kernel<L>; the _v classes (any label count up to
+# kernel symbols as rocprofv3 prints them: dense classes run the packed kernel (KMAX 2 at L >= 16, 4 below; packets for up
+# to 8 active messages per factor, indirect records above); the _v classes (any label count up to
 # the padded width, rectangular tables) are the same kernels with run-time dims; the exact dense kernels come in a
 # plain and a non-temporal-access form (last template argument), chosen by the size of the model: the names below
 # are prefixes
@@ -59,7 +59,7 @@ EXPORTS = [
 
 
 def library_path() -> str:
-    # LPMP_ENGINE_SO: load an experimental build of the same sources (kernel ablations); never a CPU path
+    # LPMP_ENGINE_SO: load another build of the library (an older revision, for an A/B); never a CPU path
     return os.environ.get("LPMP_ENGINE_SO", _build.SO)
 
 

@@ -351,6 +351,47 @@ def test_a_hub_with_more_messages_than_a_packet_slab_holds_gets_a_class_of_its_o
         assert set(E.Plan(m8).schedule_classes(M.FORWARD, M.REPAM_UNIFORM)) == {exact}
 
 
+def _duplicate_message_model(L):
+    """a chain of unaries u0 .. u5 over dense pairwise factors in which u0 .. u4 send their message to the right neighbour's
+    factor TWICE (two messages of one type between the same two factors: both rewrite one vector)"""
+    mt = [M.MsgType(0, 1, M.SCHED_LEFT, 0, 0, M.M_UNARY_PAIRWISE, 0), M.MsgType(0, 1, M.SCHED_LEFT, 0, 0, M.M_UNARY_PAIRWISE, 1)]
+    rng = np.random.default_rng(L)
+    b = M.ModelBuilder(2, mt)
+    u = b.add_vector_factors(0, rng.uniform(0, 1, (6, L)))
+    for k in range(5):
+        p = b.add_dense_pairwise(1, rng.uniform(0, 1, (1, L, L)))[0]
+        b.add_messages(0, u[k], p); b.add_messages(1, u[k + 1], p)
+        b.add_messages(0, u[k], p)                      # duplicate
+        b.add_relations(u[k], p); b.add_relations(p, u[k + 1])
+    return b.finish()
+
+
+def test_packed_classes_only_hold_records_the_packed_kernels_run():
+    """the packed dense / Potts kernels have no op-by-op fallback: plan.cpp refuses to plan a launch of their classes it
+    cannot pack, and the class rule (cls_of) must already have moved every record with duplicate messages or more ops than
+    the LDS slab holds to an op-by-op class.  Every mode and direction of such models plans, with this split:"""
+    # u5 has no duplicate: packed; u0 .. u4 one lane each while their duals fit SMALL_MAXD, else the streaming kernel
+    split = {4: {"dense4": 1, "small": 5}, 8: {"dense8": 1, "small": 5}, 16: {"dense16": 1, "dense_big": 5},
+             32: {"dense32": 1, "dense_big": 5}, 5: {"dense_v8": 1, "small": 5}}
+    for L, want in split.items():
+        p = E.Plan(_duplicate_message_model(L))
+        for d in (M.FORWARD, M.BACKWARD):
+            for mode in MODES:
+                assert p.schedule_classes(d, mode) == want, (L, d, mode)
+    for pairwise in ("dense", "potts"):
+        for L in (4, 8, 16, 32):
+            for n_spokes in (40, 70):
+                p = E.Plan(_hub_model(L, n_spokes, pairwise, seed=n_spokes))
+                exact = "%s%d" % (pairwise, L)
+                for d in (M.FORWARD, M.BACKWARD):
+                    for mode in MODES:
+                        # the hub alone on the streaming kernel, unless its messages fit the slab: 40 receives or sends
+                        # of the dense 16-label class (64 ops) outside the uniform modes, where each is received AND sent
+                        fits = pairwise == "dense" and L == 16 and n_spokes == 40 and mode not in (M.REPAM_UNIFORM, M.REPAM_DAMPED_UNIFORM)
+                        want = {exact: n_spokes + 1} if fits else {exact: n_spokes, "dense_big": 1}
+                        assert p.schedule_classes(d, mode) == want, (pairwise, L, n_spokes, d, mode)
+
+
 def test_chain_plans_default_to_the_packed_classes(monkeypatch):
     """deep schedules of the packed dense / Potts classes become chain launches (tickets + flags); many tiny levels of the
     lane-per-factor class become the level loop (one workgroup, no tickets); the ticket form of that class only on
