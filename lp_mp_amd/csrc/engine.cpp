@@ -93,7 +93,7 @@ struct DevSchedule {
     bool banded = false;                     // Infinity-Cache ticket order: plain table loads, not the streaming policy
     bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
     ChainLaunchDev* launches = nullptr; int32_t *tk_launch = nullptr, *tk_block = nullptr, *dep_off = nullptr, *dep = nullptr, *done = nullptr, *next = nullptr;
-    unsigned long long* mailbox = nullptr;   // tagged granules of the message vectors that travel between dependent records (plan.cpp)
+    unsigned long long* mailbox = nullptr;   // tagged granules of the message vectors that travel between dependent records (chain_plan.cpp)
     void release() {
       for (void* p : {(void*)launches, (void*)tk_launch, (void*)tk_block, (void*)dep_off, (void*)dep, (void*)done, (void*)next, (void*)mailbox}) if (p) (void)hipFree(p);
       launches = nullptr; tk_launch = tk_block = dep_off = dep = done = next = nullptr; mailbox = nullptr;
@@ -773,7 +773,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
     if (!e->d_chain_abort) { HIP_CHECK(hipMalloc((void**)&e->d_chain_abort, CHAIN_ABORT_WORDS * sizeof(int32_t))); HIP_CHECK(hipMemsetAsync(e->d_chain_abort, 0, CHAIN_ABORT_WORDS * sizeof(int32_t), e->stream)); }
     // UpdateFactorPrimal always sends 'shared' (issue_launches)
     const int rule = e->primal_pass ? SWEEP_PRIMAL : e->rtype == LPMP_RTYPE_RESIDUAL ? SWEEP_RESIDUAL : e->rtype == LPMP_RTYPE_ADAPTIVE ? SWEEP_ADAPTIVE : 0;
-    // classes are independent of each other (plan.cpp): the plain launches first, then one persistent launch per class
+    // classes are independent of each other (chain_plan.cpp): the plain launches first, then one persistent launch per class
     if (!s.plain.empty()) {
       DevSchedule tmp;                       // a view: issue_launches only reads recs / ops / packets / launches
       tmp.recs = s.recs; tmp.ops = s.ops; tmp.packets = s.packets; tmp.launches = s.plain;

@@ -104,7 +104,7 @@ struct ChainArgs {
   // joined passes (engine.cpp rotation_chain) with per-pass lower bounds: row r = the tracked bounds of all factors as they
   // are at the END OF PASS r + 1 of the call; a launch writes into the row its ChainLaunch::hist names (nullptr: no rows)
   double* lb_hist; int64_t hist_stride;
-  // launches with CHAIN_LAUNCH_MAILBOX (plan.cpp): rows of L granule pairs, see mailbox_put / mailbox_take
+  // launches with CHAIN_LAUNCH_MAILBOX (chain_plan.cpp): rows of L granule pairs, see mailbox_put / mailbox_take
   unsigned long long* mailbox;
   // bound of every wait in ticks of s_memrealtime (100 MHz; engine.cpp: 20 s, LPMP_CHAIN_TIMEOUT_S).  Time, not a number of
   // polls: a device shared by several processes (N ranks of a smoke run on one GPU) serves a poll an order of magnitude
@@ -236,12 +236,12 @@ __device__ __forceinline__ void chain_publish(const ChainArgs& ca, int ticket) {
 }
 
 
-// Mailbox of a dense chain (plan.cpp decides which vectors travel this way): the value a send has just computed, as two
+// Mailbox of a dense chain (chain_plan.cpp decides which vectors travel this way): the value a send has just computed, as two
 // self-validating 8-byte granules {half of the double, epoch of the running launch}.  An aligned 8-byte access is atomic,
 // so a granule whose tag is this launch's epoch IS the producer's value — no ordering with any other store is needed, and
 // the consumer has the value after ONE trip instead of two (completion flag seen, then the vector fetched).  What the
 // consumer may conclude from a granule is only this value: the producer's other stores are not yet visible, which is why
-// plan.cpp keeps a flag dependency wherever anything else of the producer is read or overwritten.
+// chain_plan.cpp keeps a flag dependency wherever anything else of the producer is read or overwritten.
 __device__ __forceinline__ void mailbox_put(unsigned long long* q, double v, int epoch) {
   const unsigned long long tag = (unsigned long long)(unsigned)epoch << 32;
   __hip_atomic_store(q, tag | (unsigned)__double2loint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1179,7 +1179,7 @@ __device__ __forceinline__ void chain_loop(const ChainArgs& ca, const ChainLaunc
     __syncthreads();                               // s_ticket[(it + 1) & 1] is written, the LDS of the body is free again
   }
 }
-// MBOX: a chain whose launches all carry CHAIN_LAUNCH_MAILBOX (plan.cpp marks every launch of such a chain)
+// MBOX: a chain whose launches all carry CHAIN_LAUNCH_MAILBOX (chain_plan.cpp marks every launch of such a chain)
 // The same loop for mailbox chains, where a level is a couple of microseconds and what a workgroup needs before it can
 // even request its records — ticket number (an atomic on the far side of the fabric), then the ticket's launch, block and
 // dependency count (three arrays streamed from HBM once per launch: a miss each) — was 3.5 us of round trips in a row per
@@ -1249,7 +1249,7 @@ chain_generic_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, dou
 }
 
 // Level loop: a deep schedule of TINY levels of a generic class as one launch of ONE workgroup that walks the launches in
-// order with a workgroup barrier in between (plan.cpp decides; C5 with local triples: 11 887 levels of a dozen one-lane
+// order with a workgroup barrier in between (chain_plan.cpp decides; C5 with local triples: 11 887 levels of a dozen one-lane
 // updates).  No launch per level, no flags through memory; what a level hands to the next stays in this compute unit's L2
 // (stores drained before the barrier, dual loads that bypass the L1: ACC_WG).
 //   G = 64 (wave per factor): the plain body.
@@ -1260,7 +1260,7 @@ constexpr int LEVEL_LOOP_AHEAD = 8;
 constexpr int LL_WAVES = 2;                        // computing waves of level_loop_kernel<1> (+ one that runs ahead)
 constexpr int CHAIN_LAUNCH_LABEL_OPS_DEV = 1, CHAIN_LAUNCH_LABEL_PAIRED_DEV = 2;   // ChainLaunch::pad (plan.hpp CHAIN_LAUNCH_LABEL_*)
 
-// Labeling-list records with one LANE PER OP (plan.cpp marks the launches: vector factors whose ops are all labeling
+// Labeling-list records with one LANE PER OP (chain_plan.cpp marks the launches: vector factors whose ops are all labeling
 // messages with the factor on the left, at most 8 receives with distinct peers and 8 sends with distinct peers, message
 // length = the factor's size).
 // One record per lane runs as many op rounds as its longest receive and send lists (generic_body<1>; measured
@@ -1639,7 +1639,7 @@ __device__ __forceinline__ void two_min_merge(double& a1, double& a2) {   // two
 
 // VAR: L is the padded width, the label count (<= L) is read at run time; lanes beyond it carry +inf
 // A: access policy of the duals; CHAIN: called from the chain executor (see dense_pk_body)
-// MBOX: the mailbox form of the chain body (see dense_pk_body and plan.cpp): message vectors between dependent records as
+// MBOX: the mailbox form of the chain body (see dense_pk_body and chain_plan.cpp): message vectors between dependent records as
 // tagged granules
 template <int L, bool VAR, int A, bool CHAIN, bool MBOX = false>
 __device__ __forceinline__ void potts_pk_body(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,

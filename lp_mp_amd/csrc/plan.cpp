@@ -394,48 +394,85 @@ void Plan::ensure_weights(int mode) {
 // from the state after the receives" is exactly what running u1 then u2 computes, and the factor's dual
 // makes one round trip instead of two (2-colour grids: the receive level of the forward sweep and the
 // send level of the backward sweep are the same factors).
-void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& out, bool chains, std::vector<int32_t>* levels_only) const {
-  out = Schedule();
-  const bool timed_ = std::getenv("LPMP_PLAN_TIMES") != nullptr;
-  auto t_last_ = std::chrono::steady_clock::now();
-  auto lap_ = [&](const char* what) { if (!timed_) return; const auto now = std::chrono::steady_clock::now(); std::fprintf(stderr, "lpmp: make_schedule %-8s %.0f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last_).count()); t_last_ = now; };
+//
+// make_schedule runs the stages below in order; the chain plans of the result come from chain_plan.cpp.
+namespace {
+
+// two ops of one record into the same message vector: the same peer, and the same side of it
+inline bool same_vector(const Op& a, const Op& b) { return a.peer_dual == b.peer_dual && ((a.info >> 5) & 1) == ((b.info >> 5) & 1); }
+
+// The per-update arrays the stages share (u = position in the sequence of the segments).  Hundreds of MB at the headline size:
+// every stage works on them in place.
+struct Updates {
+  int64_t N = 0;
+  std::vector<int32_t> uf, owner, level;       // factor; the update whose record holds u's ops (u itself unless folded); level
+  std::vector<const double*> uom;              // omega row (the effective send weights when some message op batches)
+  std::vector<const uint8_t*> umk;             // receive-mask row
+  std::vector<double> eff_store;               // (the rows of those effective send weights)
+  std::vector<int32_t> n_recv_of, n_send_of;   // active ops accumulated on the owner record
+  std::vector<int32_t> nr_of_u, ns_of_u;       // active receives / sends of every single update (its own, not the owner's sum)
+  int32_t max_level = 0;
+  std::vector<int64_t> op_start;               // [N + 1]: op range of every owner record
+  // class flags of the owner records (only ever cleared):
+  std::vector<uint8_t> all_dense, all_potts;   // exact classes: every peer L x L, L the own label count
+  std::vector<uint8_t> var_dense, var_potts;   // padded classes: runtime dims
+  std::vector<uint8_t> up_any;                 // streaming class: dense and Potts peers mixed
+  std::vector<uint8_t> small_ok;               // lane-per-factor class: every size <= SMALL_MAXD
+  std::vector<uint8_t> pw_right;               // updated dense pairwise factor, every op unary-pairwise with the factor on the right
+  std::vector<int32_t> max_dim;                // largest peer table dim of the record
+  std::vector<int64_t> rec_bytes;              // algorithmic bytes of the record
+  std::vector<int32_t> kclass;                 // kernel class of the record
+  std::vector<int32_t> rec_upd;                // [records]: the update each record stands for
+};
+
+// a COMPUTE_PRIMAL factor is updated even without any active message (FactorUpdated, reference
+// factors_messages.hxx:3125-3130): the primal passes round its label
+bool is_rec(const Plan& p, const Updates& U, int64_t u) {
+  return U.owner[u] == u && (U.n_recv_of[u] + U.n_send_of[u] > 0 || p.ftype_primal[p.f_type[U.uf[u]]]);
+}
+
+// the rows of the segments, checked, with the effective send weights of batch-capable message ops
+void gather_rows(const Plan& p, const std::vector<Plan::Segment>& segs, Updates& U) {
   int64_t N = 0;
   for (const auto& sg : segs) N += sg.n;
-  struct Upd { int32_t f; int32_t owner; int64_t om, mk; };   // om / mk: absolute pointers are per segment
-  std::vector<int32_t> uf(N), owner(N), level(N, 0);
-  std::vector<const double*> uom(N);
-  std::vector<const uint8_t*> umk(N);
-  std::vector<int32_t> n_recv_of(N, 0), n_send_of(N, 0);       // active ops accumulated on the owner record
+  U.N = N;
+  U.uf = std::vector<int32_t>(N); U.owner = std::vector<int32_t>(N); U.level = std::vector<int32_t>(N, 0);
+  U.uom = std::vector<const double*>(N);
+  U.umk = std::vector<const uint8_t*>(N);
+  U.n_recv_of = std::vector<int32_t>(N, 0); U.n_send_of = std::vector<int32_t>(N, 0);
   {
     int64_t u = 0;
     for (const auto& sg : segs)
       for (int64_t i = 0; i < sg.n; ++i, ++u) {
         const int32_t f = sg.factors[i];
-        if (f < 0 || f >= nf) fail("factor index out of range");
-        if (sg.om_off[i + 1] - sg.om_off[i] != row_sends(f) || sg.mk_off[i + 1] - sg.mk_off[i] != row_receives(f))
+        if (f < 0 || f >= p.nf) fail("factor index out of range");
+        if (sg.om_off[i + 1] - sg.om_off[i] != p.row_sends(f) || sg.mk_off[i + 1] - sg.mk_off[i] != p.row_receives(f))
           fail("row " + std::to_string(i) + ": omega / receive mask length does not match the factor's messages");
-        uf[u] = f; uom[u] = sg.om + sg.om_off[i]; umk[u] = sg.mk + sg.mk_off[i];
+        U.uf[u] = f; U.uom[u] = sg.om + sg.om_off[i]; U.umk[u] = sg.mk + sg.mk_off[i];
       }
   }
   if (N > std::numeric_limits<int32_t>::max()) fail("too many updates for one schedule");
   // batch-capable message ops: the weights the individual sends end up with (CallSendMessages' batch rule)
-  std::vector<double> eff_store;
-  if (any_batch) {
+  if (p.any_batch) {
     size_t total = 0;
-    for (int64_t u = 0; u < N; ++u) total += (size_t)row_sends(uf[u]);
-    eff_store.resize(total + 1);
+    for (int64_t u = 0; u < N; ++u) total += (size_t)p.row_sends(U.uf[u]);
+    U.eff_store.resize(total + 1);
     size_t at = 0;
     for (int64_t u = 0; u < N; ++u) {
-      const int64_t ns = row_sends(uf[u]);
-      for (int64_t k = 0; k < ns; ++k) if (uom[u][k] < 0) fail("negative send weight");
-      effective_send_weights(uf[u], uom[u], eff_store.data() + at);
-      uom[u] = eff_store.data() + at;
+      const int64_t ns = p.row_sends(U.uf[u]);
+      for (int64_t k = 0; k < ns; ++k) if (U.uom[u][k] < 0) fail("negative send weight");
+      p.effective_send_weights(U.uf[u], U.uom[u], U.eff_store.data() + at);
+      U.uom[u] = U.eff_store.data() + at;
       at += (size_t)ns;
     }
   }
-  lap_("rows");
-  std::vector<int32_t> last_level(nf, 0), last_toucher(nf, -1), last_update_of(nf, -1);
-  std::vector<int32_t> nr_of_u(N, 0), ns_of_u(N, 0);            // active receives / sends of every single update (its own, not the owner's sum)
+}
+
+// what every update touches, and the level recurrence (with the folding of `fuse`): owner, level, the op counts
+void level_recurrence(const Plan& p, bool fuse, Updates& U) {
+  const int64_t N = U.N;
+  std::vector<int32_t> last_level(p.nf, 0), last_toucher(p.nf, -1), last_update_of(p.nf, -1);
+  U.nr_of_u = std::vector<int32_t>(N, 0); U.ns_of_u = std::vector<int32_t>(N, 0);
   int32_t max_level = 0;
   // what every update touches (its own factor first, then the peers of its active messages) — independent per update, so the
   // walk over the message lists and the weight / mask rows runs on the planner's threads; the recurrence over the levels below
@@ -443,45 +480,49 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   std::vector<int64_t> t_off((size_t)N + 1, 0);
   parallel_chunks(N, 65536, [&](int64_t u_begin, int64_t u_end, int) {
     for (int64_t u = u_begin; u < u_end; ++u) {
-      const int32_t f = uf[u];
+      const int32_t f = U.uf[u];
       int32_t nr = 0, ns = 0; int64_t nt = 1;
       int64_t ks = 0, kr = 0;
-      const bool all = ftype_primal[f_type[f]] && f_kind[f] != LPMP_F_VECTOR;
-      for (int64_t j = fm_off[f]; j < fm_off[f + 1]; ++j) {
-        const MsgEntry& e = fm[j];
+      const bool all = p.ftype_primal[p.f_type[f]] && p.f_kind[f] != LPMP_F_VECTOR;
+      for (int64_t j = p.fm_off[f]; j < p.fm_off[f + 1]; ++j) {
+        const MsgEntry& e = p.fm[j];
         bool active = false;
-        if (e.receives && umk[u][kr++]) { active = true; ++nr; }
-        if (e.sends) { const double w = uom[u][ks++]; if (w < 0) fail("negative send weight"); if (w != 0.0) { active = true; ++ns; } }
+        if (e.receives && U.umk[u][kr++]) { active = true; ++nr; }
+        if (e.sends) { const double w = U.uom[u][ks++]; if (w < 0) fail("negative send weight"); if (w != 0.0) { active = true; ++ns; } }
         if (active || all) ++nt;
       }
-      nr_of_u[u] = nr; ns_of_u[u] = ns; t_off[(size_t)u + 1] = nt;
+      U.nr_of_u[u] = nr; U.ns_of_u[u] = ns; t_off[(size_t)u + 1] = nt;
     }
   });
   for (int64_t u = 0; u < N; ++u) t_off[(size_t)u + 1] += t_off[(size_t)u];
   std::vector<int32_t, default_init_allocator<int32_t>> t_data((size_t)t_off[(size_t)N]);
   parallel_chunks(N, 65536, [&](int64_t u_begin, int64_t u_end, int) {
     for (int64_t u = u_begin; u < u_end; ++u) {
-      const int32_t f = uf[u];
+      const int32_t f = U.uf[u];
       int32_t* out_t = t_data.data() + t_off[(size_t)u];
       *out_t++ = f;
       int64_t ks = 0, kr = 0;
       // a pairwise factor that rounds itself reads and writes the labels of ALL its unaries in a primal pass
       // (engine.cpp, ensure_primal), whether or not the message is active in this sweep
-      const bool all = ftype_primal[f_type[f]] && f_kind[f] != LPMP_F_VECTOR;
-      for (int64_t j = fm_off[f]; j < fm_off[f + 1]; ++j) {
-        const MsgEntry& e = fm[j];
+      const bool all = p.ftype_primal[p.f_type[f]] && p.f_kind[f] != LPMP_F_VECTOR;
+      for (int64_t j = p.fm_off[f]; j < p.fm_off[f + 1]; ++j) {
+        const MsgEntry& e = p.fm[j];
         bool active = false;
-        if (e.receives && umk[u][kr++]) active = true;
-        if (e.sends && uom[u][ks++] != 0.0) active = true;
+        if (e.receives && U.umk[u][kr++]) active = true;
+        if (e.sends && U.uom[u][ks++] != 0.0) active = true;
         if (active || all) *out_t++ = e.adjacent;
       }
     }
   });
   struct Touched { const int32_t* b; const int32_t* e; const int32_t* begin() const { return b; } const int32_t* end() const { return e; } };
+  std::vector<int32_t>& owner = U.owner;
+  std::vector<int32_t>& level = U.level;
+  std::vector<int32_t>& n_recv_of = U.n_recv_of;
+  std::vector<int32_t>& n_send_of = U.n_send_of;
   for (int64_t u = 0; u < N; ++u) {
-    const int32_t f = uf[u];
+    const int32_t f = U.uf[u];
     const Touched touched{t_data.data() + t_off[(size_t)u], t_data.data() + t_off[(size_t)u + 1]};
-    const int32_t nr = nr_of_u[u], ns = ns_of_u[u];
+    const int32_t nr = U.nr_of_u[u], ns = U.ns_of_u[u];
     int32_t lv = 0;
     for (int32_t g : touched) lv = std::max(lv, last_level[g]);
     const int32_t prev = last_update_of[f];
@@ -502,41 +543,43 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       max_level = std::max(max_level, level[u]);
       // an update without active ops touches nothing and is dropped, unless its factor type computes a primal:
       // that record stays (it rounds the label in primal passes) and reads / writes its own duals
-      if (nr + ns > 0 || ftype_primal[f_type[f]]) {
+      if (nr + ns > 0 || p.ftype_primal[p.f_type[f]]) {
         for (int32_t g : touched) { last_level[g] = level[u]; last_toucher[g] = (int32_t)u; }
         last_update_of[f] = (int32_t)u;
       }
     }
   }
-  lap_("levels");
-  out.n_levels = max_level;
-  if (levels_only) {
-    levels_only->resize((size_t)N);
-    for (int64_t u = 0; u < N; ++u) {
-      const int32_t o = owner[u];
-      (*levels_only)[(size_t)u] = (n_recv_of[o] + n_send_of[o] > 0 || ftype_primal[f_type[uf[o]]]) ? level[o] : 0;
-    }
-    return;
-  }
+  U.max_level = max_level;
+}
 
-  // records of the owners, ops = all receives of the members (sequence order), then all sends
-  std::vector<int64_t> op_start(N + 1, 0);
-  for (int64_t u = 0; u < N; ++u) op_start[u + 1] = op_start[u] + (owner[u] == u ? n_recv_of[u] + n_send_of[u] : 0);
+// records of the owners, ops = all receives of the members (sequence order), then all sends; the per-owner class flags and
+// algorithmic bytes.  Returns the algorithmic bytes of the schedule.
+int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
+  const int64_t N = U.N;
+  const std::vector<int32_t>& owner = U.owner;
+  const std::vector<int32_t>& n_recv_of = U.n_recv_of;
+  U.op_start = std::vector<int64_t>(N + 1, 0);
+  std::vector<int64_t>& op_start = U.op_start;
+  for (int64_t u = 0; u < N; ++u) op_start[u + 1] = op_start[u] + (owner[u] == u ? n_recv_of[u] + U.n_send_of[u] : 0);
   if (op_start[N] > std::numeric_limits<int32_t>::max()) fail("too many active message operations for one schedule");
-  OpVec ops((size_t)op_start[N]);                   // (every slot is written below: the counts are the same walk over the rows)
+  ops = OpVec((size_t)op_start[N]);                 // (every slot is written below: the counts are the same walk over the rows)
   // where every update writes inside its owner's op range: receives of the members in sequence order, then the sends
   std::vector<int32_t> r_at(N, 0), s_at(N, 0);
   {
     std::vector<int32_t> cur_r(N, 0), cur_s(N, 0);
-    for (int64_t u = 0; u < N; ++u) { const int32_t o = owner[u]; r_at[u] = cur_r[o]; cur_r[o] += nr_of_u[u]; s_at[u] = cur_s[o]; cur_s[o] += ns_of_u[u]; }
+    for (int64_t u = 0; u < N; ++u) { const int32_t o = owner[u]; r_at[u] = cur_r[o]; cur_r[o] += U.nr_of_u[u]; s_at[u] = cur_s[o]; cur_s[o] += U.ns_of_u[u]; }
   }
-  std::vector<int64_t> rec_bytes(N, 0);
-  std::vector<uint8_t> all_dense(N, 1), all_potts(N, 1);     // exact classes: every peer L x L, L the own label count
-  std::vector<uint8_t> var_dense(N, 1), var_potts(N, 1);     // padded classes: runtime dims
-  std::vector<uint8_t> up_any(N, 1);                         // streaming class: dense and Potts peers mixed
-  std::vector<uint8_t> small_ok(N, 1);                       // lane-per-factor class: every size <= SMALL_MAXD
-  std::vector<uint8_t> pw_right(N, 1);                       // updated dense pairwise factor, every op unary-pairwise with the factor on the right
-  std::vector<int32_t> max_dim(N, 0);                        // largest peer table dim of the record
+  U.rec_bytes = std::vector<int64_t>(N, 0);
+  U.all_dense = std::vector<uint8_t>(N, 1); U.all_potts = std::vector<uint8_t>(N, 1);
+  U.var_dense = std::vector<uint8_t>(N, 1); U.var_potts = std::vector<uint8_t>(N, 1);
+  U.up_any = std::vector<uint8_t>(N, 1);
+  U.small_ok = std::vector<uint8_t>(N, 1);
+  U.pw_right = std::vector<uint8_t>(N, 1);
+  U.max_dim = std::vector<int32_t>(N, 0);
+  std::vector<uint8_t>& all_dense = U.all_dense; std::vector<uint8_t>& all_potts = U.all_potts;
+  std::vector<uint8_t>& var_dense = U.var_dense; std::vector<uint8_t>& var_potts = U.var_potts;
+  std::vector<uint8_t>& up_any = U.up_any; std::vector<uint8_t>& small_ok = U.small_ok; std::vector<uint8_t>& pw_right = U.pw_right;
+  std::vector<int32_t>& max_dim = U.max_dim;
   std::vector<int64_t> alg_bytes_of_thread(PLAN_MAX_THREADS, 0);
   // (several updates may share an owner record — folded sweeps — and land on different threads: the per-owner flags only
   // ever go from 1 to 0, sums and maxima are atomic)
@@ -545,45 +588,46 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   parallel_chunks(N, 65536, [&](int64_t u_begin, int64_t u_end, int thread) {
   int64_t alg_local = 0;
   for (int64_t u = u_begin; u < u_end; ++u) {
-    const int32_t f = uf[u];
+    const int32_t f = U.uf[u];
     const int32_t o = owner[u];
-    const int32_t own_d0 = f_dim0[f];
-    if (f_doff[f + 1] - f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);   // also for a record without any op (COMPUTE_PRIMAL types)
+    const int32_t own_d0 = p.f_dim0[f];
+    if (p.f_doff[f + 1] - p.f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);   // also for a record without any op (COMPUTE_PRIMAL types)
     Op* base = ops.data() + op_start[o];
     auto fill = [&](const MsgEntry& e, double w) {
-      const auto& mt = mtypes[m_type[e.msg]];
+      const auto& mt = p.mtypes[p.m_type[e.msg]];
       const int32_t peer = e.adjacent;
       Op op{};
-      op.peer_dual = doff(peer);
+      op.peer_dual = p.doff(peer);
       op.omega = w;
       op.peer = peer;
-      op.len = f_dim0[m_left[e.msg]];
-      op.pd0 = f_dim0[peer]; op.pd1 = f_dim1[peer];
-      const int32_t right = m_right[e.msg];
+      op.len = p.f_dim0[p.m_left[e.msg]];
+      op.pd0 = p.f_dim0[peer]; op.pd1 = p.f_dim1[peer];
+      const int32_t right = p.m_right[e.msg];
       int side = 0, imp = 0;
       if (mt.kind == LPMP_M_UNARY_PAIRWISE) {
         side = mt.param;
-        op.peer_const = e.role == 0 ? coff(peer) : -1;
-        if (!(f_kind[f] == LPMP_F_VECTOR && e.role == 0 && f_kind[peer] == LPMP_F_PAIRWISE_DENSE && f_dim0[peer] == own_d0 && f_dim1[peer] == own_d0 && (coff(peer) % 2) == 0)) clear_flag(all_dense[o]);
-        if (!(f_kind[f] == LPMP_F_VECTOR && e.role == 0 && f_kind[peer] == LPMP_F_PAIRWISE_POTTS && f_dim0[peer] == own_d0)) clear_flag(all_potts[o]);
-        if (!(f_kind[f] == LPMP_F_VECTOR && e.role == 0 && f_kind[peer] == LPMP_F_PAIRWISE_DENSE && (side == 0 ? f_dim0[peer] : f_dim1[peer]) == own_d0)) clear_flag(var_dense[o]);
-        if (!(f_kind[f] == LPMP_F_VECTOR && e.role == 0 && f_kind[peer] == LPMP_F_PAIRWISE_POTTS && f_dim0[peer] == own_d0 && f_dim1[peer] == own_d0)) clear_flag(var_potts[o]);
-        atomic_max(max_dim[o], std::max(f_dim0[peer], f_dim1[peer]));
-        if (!(f_kind[f] == LPMP_F_VECTOR && e.role == 0 && (f_kind[peer] == LPMP_F_PAIRWISE_DENSE || f_kind[peer] == LPMP_F_PAIRWISE_POTTS) &&
-              (side == 0 ? f_dim0[peer] : f_dim1[peer]) == own_d0)) clear_flag(up_any[o]);
+        op.peer_const = e.role == 0 ? p.coff(peer) : -1;
+        const bool unary_left = p.f_kind[f] == LPMP_F_VECTOR && e.role == 0;
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[peer] == own_d0 && p.f_dim1[peer] == own_d0 && (p.coff(peer) % 2) == 0)) clear_flag(all_dense[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS && p.f_dim0[peer] == own_d0)) clear_flag(all_potts[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(var_dense[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS && p.f_dim0[peer] == own_d0 && p.f_dim1[peer] == own_d0)) clear_flag(var_potts[o]);
+        atomic_max(max_dim[o], std::max(p.f_dim0[peer], p.f_dim1[peer]));
+        if (!(unary_left && (p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE || p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS) &&
+              (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(up_any[o]);
       } else {
         clear_flag(all_dense[o]); clear_flag(all_potts[o]); clear_flag(var_dense[o]); clear_flag(var_potts[o]); clear_flag(up_any[o]);
         if (mt.kind == LPMP_M_LABELING) {
-          op.peer_const = tab_off[mt.param];
-          op.pd1 = tab_nleft[mt.param];
-          imp = (f_flags[right] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 : 0;
+          op.peer_const = p.tab_off[mt.param];
+          op.pd1 = p.tab_nleft[mt.param];
+          imp = (p.f_flags[right] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 : 0;
         }
       }
-      op.info = mt.kind | (e.role << 4) | (side << 5) | (imp << 6) | ((f_flags[peer] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 << 7 : 0) | (f_kind[peer] << 8) |
+      op.info = mt.kind | (e.role << 4) | (side << 5) | (imp << 6) | ((p.f_flags[peer] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 << 7 : 0) | (p.f_kind[peer] << 8) |
                 ((mt.flags & LPMP_MF_IMPROVEMENT) ? OP_HAS_IMPROVEMENT : 0);
-      if (std::max(op.len, std::max(op.pd0, op.pd1)) > SMALL_MAXD || f_doff[f + 1] - f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);
-      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && f_kind[f] != LPMP_F_VECTOR && f_kind[peer] == LPMP_F_VECTOR &&
-            f_dim1[f] > 0 && op.len == (side == 0 ? f_dim0[f] : f_dim1[f]))) clear_flag(pw_right[o]);
+      if (std::max(op.len, std::max(op.pd0, op.pd1)) > SMALL_MAXD || p.f_doff[f + 1] - p.f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);
+      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[peer] == LPMP_F_VECTOR &&
+            p.f_dim1[f] > 0 && op.len == (side == 0 ? p.f_dim0[f] : p.f_dim1[f]))) clear_flag(pw_right[o]);
       return op;
     };
     // algorithmic bytes, counted per update as the reference executes it: own dual read + written
@@ -600,28 +644,34 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     };
     int64_t ks = 0, kr = 0, bytes = 0, n_act = 0;
     int32_t at_r = r_at[u], at_s = n_recv_of[o] + s_at[u];
-    for (int64_t j = fm_off[f]; j < fm_off[f + 1]; ++j) {
-      const MsgEntry& e = fm[j];
-      if (e.receives && umk[u][kr++]) { Op op = fill(e, 1.0); bytes += op_bytes(op, true); base[at_r++] = op; ++n_act; }
+    for (int64_t j = p.fm_off[f]; j < p.fm_off[f + 1]; ++j) {
+      const MsgEntry& e = p.fm[j];
+      if (e.receives && U.umk[u][kr++]) { Op op = fill(e, 1.0); bytes += op_bytes(op, true); base[at_r++] = op; ++n_act; }
     }
-    for (int64_t j = fm_off[f]; j < fm_off[f + 1]; ++j) {
-      const MsgEntry& e = fm[j];
-      if (e.sends) { const double w = uom[u][ks++]; if (w != 0.0) { Op op = fill(e, w); bytes += op_bytes(op, false); base[at_s++] = op; ++n_act; } }
+    for (int64_t j = p.fm_off[f]; j < p.fm_off[f + 1]; ++j) {
+      const MsgEntry& e = p.fm[j];
+      if (e.sends) { const double w = U.uom[u][ks++]; if (w != 0.0) { Op op = fill(e, w); bytes += op_bytes(op, false); base[at_s++] = op; ++n_act; } }
     }
-    if (n_act > 0) bytes += 16 * (f_doff[f + 1] - f_doff[f]);
+    if (n_act > 0) bytes += 16 * (p.f_doff[f + 1] - p.f_doff[f]);
     // an updated dense pairwise factor reads its own table once to compute the min-marginals it sends
-    if (ks > 0 && f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+    if (ks > 0 && p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
       bool sends_any = false;
-      for (int64_t j = 0; j < ks; ++j) if (uom[u][j] != 0.0) { sends_any = true; break; }
-      if (sends_any) bytes += 8 * (int64_t)f_dim0[f] * f_dim1[f];
+      for (int64_t j = 0; j < ks; ++j) if (U.uom[u][j] != 0.0) { sends_any = true; break; }
+      if (sends_any) bytes += 8 * (int64_t)p.f_dim0[f] * p.f_dim1[f];
     }
-    __atomic_fetch_add(&rec_bytes[o], bytes, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&U.rec_bytes[o], bytes, __ATOMIC_RELAXED);
     alg_local += bytes;
   }
   alg_bytes_of_thread[(size_t)thread] = alg_local;
   });
-  for (int64_t b : alg_bytes_of_thread) out.alg_bytes += b;
-  lap_("ops");
+  int64_t alg_bytes = 0;
+  for (int64_t b : alg_bytes_of_thread) alg_bytes += b;
+  return alg_bytes;
+}
+
+// the kernel class of every record
+void classify(const Plan& p, Updates& U, const OpVec& ops) {
+  const int64_t N = U.N;
   // Records with two receives, or two sends, into ONE vector (duplicate messages between the same two factors) need an
   // op-by-op kernel: the packed kernels request a record's vectors before reducing.  They get a class of their own
   // (the streaming / generic / lane-per-factor kernels work op by op), so that one such record does not take its whole
@@ -629,28 +679,32 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   // messages go to different vectors.)
   std::vector<uint8_t> dup_vec(N, 0);
   for (int64_t u = 0; u < N; ++u) {
-    if (owner[u] != u) continue;
-    const Op* o = ops.data() + op_start[u];
-    const int nr = n_recv_of[u], ns = n_send_of[u];
-    auto same = [&](int a, int b) { return o[a].peer_dual == o[b].peer_dual && ((o[a].info >> 5) & 1) == ((o[b].info >> 5) & 1); };
-    for (int a = 0; a < nr && !dup_vec[u]; ++a) for (int b = a + 1; b < nr; ++b) if (same(a, b)) { dup_vec[u] = 1; break; }
-    for (int a = nr; a < nr + ns && !dup_vec[u]; ++a) for (int b = a + 1; b < nr + ns; ++b) if (same(a, b)) { dup_vec[u] = 1; break; }
+    if (U.owner[u] != u) continue;
+    const Op* o = ops.data() + U.op_start[u];
+    const int nr = U.n_recv_of[u], ns = U.n_send_of[u];
+    for (int a = 0; a < nr && !dup_vec[u]; ++a) for (int b = a + 1; b < nr; ++b) if (same_vector(o[a], o[b])) { dup_vec[u] = 1; break; }
+    for (int a = nr; a < nr + ns && !dup_vec[u]; ++a) for (int b = a + 1; b < nr + ns; ++b) if (same_vector(o[a], o[b])) { dup_vec[u] = 1; break; }
   }
-  lap_("dup");
-  // bucket the owner records by (level, class); updates without any active op are dropped
-  std::vector<int32_t> kclass(N, KC_GENERIC);
+  const std::vector<int32_t>& uf = U.uf;
+  const std::vector<int32_t>& n_recv_of = U.n_recv_of;
+  const std::vector<int32_t>& n_send_of = U.n_send_of;
+  const std::vector<uint8_t>& small_ok = U.small_ok;
+  const std::vector<uint8_t>& up_any = U.up_any;
+  const std::vector<uint8_t>& all_dense = U.all_dense;
+  const std::vector<uint8_t>& all_potts = U.all_potts;
+  const std::vector<int32_t>& max_dim = U.max_dim;
   auto cls_of = [&](int64_t u) -> int32_t {
-    const int d0 = f_dim0[uf[u]];
-    if (force_generic) return small_ok[u] && n_send_of[u] <= SMALL_MAXD ? KC_SMALL : KC_GENERIC;
-    if (dup_vec[u] && f_kind[uf[u]] == LPMP_F_VECTOR) {
+    const int d0 = p.f_dim0[uf[u]];
+    if (p.force_generic) return small_ok[u] && n_send_of[u] <= SMALL_MAXD ? KC_SMALL : KC_GENERIC;
+    if (dup_vec[u] && p.f_kind[uf[u]] == LPMP_F_VECTOR) {
       if (small_ok[u]) return KC_SMALL;
       const int wd = std::max(d0, max_dim[u]);
       return up_any[u] && wd >= 1 && wd <= BIG_MAX_LABELS ? KC_DENSE_BIG : KC_GENERIC;
     }
-    if (f_kind[uf[u]] != LPMP_F_VECTOR) {                  // updated pairwise factors
+    if (p.f_kind[uf[u]] != LPMP_F_VECTOR) {                // updated pairwise factors
       if (small_ok[u]) return KC_SMALL;
-      const int w = std::max(f_dim0[uf[u]], f_dim1[uf[u]]);
-      if (pw_right[u] && w <= 32 && n_recv_of[u] + n_send_of[u] <= PW_MAX_OPS)
+      const int w = std::max(p.f_dim0[uf[u]], p.f_dim1[uf[u]]);
+      if (U.pw_right[u] && w <= 32 && n_recv_of[u] + n_send_of[u] <= PW_MAX_OPS)
         return KC_PW_4 + (w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3);
       return KC_GENERIC;
     }
@@ -665,21 +719,27 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     if (w < 1) return small_ok[u] ? KC_SMALL : KC_GENERIC;      // no unary-pairwise peer at all
     if (w > 32) return up_any[u] && w <= BIG_MAX_LABELS ? KC_DENSE_BIG : KC_GENERIC;
     const int slot = w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3;
-    if (var_dense[u]) return KC_DENSE_V4 + slot;
-    if (var_potts[u]) return KC_POTTS_V4 + slot;
+    if (U.var_dense[u]) return KC_DENSE_V4 + slot;
+    if (U.var_potts[u]) return KC_POTTS_V4 + slot;
     if (up_any[u]) return KC_DENSE_V4 + slot;               // unaries with both dense and Potts edges: Potts tables made up in registers
     return small_ok[u] ? KC_SMALL : KC_GENERIC;
   };
-  // a COMPUTE_PRIMAL factor is updated even without any active message (FactorUpdated, reference
-  // factors_messages.hxx:3125-3130): the primal passes round its label
-  auto is_rec = [&](int64_t u) { return owner[u] == u && (n_recv_of[u] + n_send_of[u] > 0 || ftype_primal[f_type[uf[u]]]); };
+  U.kclass = std::vector<int32_t>(N, KC_GENERIC);
+  for (int64_t u = 0; u < N; ++u) if (is_rec(p, U, u)) U.kclass[u] = cls_of(u);
+}
+
+// bucket the owner records by (level, class) into out.recs and out.launches; updates without any active op are dropped
+void bucket(const Plan& p, Updates& U, Schedule& out) {
+  const int64_t N = U.N;
+  const int32_t max_level = U.max_level;
+  const std::vector<int32_t>& level = U.level;
+  const std::vector<int32_t>& kclass = U.kclass;
   // compact keys: only the (level, class) pairs that occur (deep schedules have millions of levels)
   static_assert(KC_COUNT <= 32, "class mask");
   std::vector<uint32_t> level_mask(max_level + 1, 0);
   for (int64_t u = 0; u < N; ++u) {
-    if (!is_rec(u)) continue;
-    if (n_recv_of[u] > 32767 || n_send_of[u] > 32767) fail("factor has too many messages");
-    kclass[u] = cls_of(u);
+    if (!is_rec(p, U, u)) continue;
+    if (U.n_recv_of[u] > 32767 || U.n_send_of[u] > 32767) fail("factor has too many messages");
     level_mask[level[u] - 1] |= 1u << kclass[u];
   }
   std::vector<int64_t> level_base(max_level + 1, 0);
@@ -692,31 +752,31 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   std::vector<int64_t> key_count(n_keys + 1, 0), key_recv(n_keys, 0), key_send(n_keys, 0), key_bytes(n_keys, 0);
   std::vector<int32_t> key_level(n_keys, 0), key_class(n_keys, 0), key_maxdim(n_keys, 0);
   for (int64_t u = 0; u < N; ++u) {
-    if (!is_rec(u)) continue;
+    if (!is_rec(p, U, u)) continue;
     const int64_t k = key(u);
     ++key_count[k + 1];
     key_level[k] = level[u]; key_class[k] = kclass[u];
-    key_recv[k] += n_recv_of[u]; key_send[k] += n_send_of[u]; key_bytes[k] += rec_bytes[u];
-    key_maxdim[k] = std::max(key_maxdim[k], std::max(std::max(f_dim0[uf[u]], f_dim1[uf[u]]), max_dim[u]));
-    out.n_recv += n_recv_of[u]; out.n_send += n_send_of[u];
+    key_recv[k] += U.n_recv_of[u]; key_send[k] += U.n_send_of[u]; key_bytes[k] += U.rec_bytes[u];
+    key_maxdim[k] = std::max(key_maxdim[k], std::max(std::max(p.f_dim0[U.uf[u]], p.f_dim1[U.uf[u]]), U.max_dim[u]));
+    out.n_recv += U.n_recv_of[u]; out.n_send += U.n_send_of[u];
   }
   std::partial_sum(key_count.begin(), key_count.end(), key_count.begin());
   out.recs.resize(key_count[n_keys]);
-  std::vector<int32_t> rec_upd(key_count[n_keys]);   // update (position in the sequence) each record stands for
+  U.rec_upd = std::vector<int32_t>(key_count[n_keys]);
   {
     std::vector<int64_t> cur(key_count.begin(), key_count.end() - 1);
     for (int64_t u = 0; u < N; ++u) {
-      if (!is_rec(u)) continue;
-      const int32_t f = uf[u];
+      if (!is_rec(p, U, u)) continue;
+      const int32_t f = U.uf[u];
       UpdRec r{};
-      r.dual_off = doff(f);
-      r.const_off = f_kind[f] == LPMP_F_VECTOR ? -1 : coff(f);
-      r.d0 = f_dim0[f]; r.d1 = f_dim1[f];
-      r.op_begin = (int32_t)op_start[u];
-      r.n_recv = (int16_t)n_recv_of[u]; r.n_send = (int16_t)n_send_of[u];
+      r.dual_off = p.doff(f);
+      r.const_off = p.f_kind[f] == LPMP_F_VECTOR ? -1 : p.coff(f);
+      r.d0 = p.f_dim0[f]; r.d1 = p.f_dim1[f];
+      r.op_begin = (int32_t)U.op_start[u];
+      r.n_recv = (int16_t)U.n_recv_of[u]; r.n_send = (int16_t)U.n_send_of[u];
       r.factor = f;
-      r.kind_flags = f_kind[f] | (f_flags[f] << 4) | (ftype_primal[f_type[f]] ? UPD_PRIMAL : 0);
-      rec_upd[cur[key(u)]] = (int32_t)u;
+      r.kind_flags = p.f_kind[f] | (p.f_flags[f] << 4) | (p.ftype_primal[p.f_type[f]] ? UPD_PRIMAL : 0);
+      U.rec_upd[cur[key(u)]] = (int32_t)u;
       out.recs[cur[key(u)]++] = r;
     }
   }
@@ -728,13 +788,24 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     lr.max_dim = key_maxdim[k];
     out.launches.push_back(lr);
   }
-  // Inside a launch the order of the records is free (they are independent).  They were placed in SEQUENCE order; what the
-  // kernels and the Infinity-Cache ticket orders want is MEMORY order — duals and tables lie in factor insertion order — so that
-  // blocks that are near in the list touch tables that are near in HBM, in every step alike.  The two agree for a sweep in
-  // insertion order; a backward sweep whose order is the exact reverse of the forward one (a chain of relations through all
-  // factors: lpmp_plan_suggest_order's answer) lists every level backwards, and a band order across its steps would need block 0
-  // of one step to wait for the last block of the step before (measured: 6.75 instead of 5.25 ms per pass on the headline grid).
-  // Records of a launch that are not ascending in the factor index are put in that order (reversed when exactly descending).
+}
+
+// the records of the launch that starts at `begin` in the order perm lists them (indices into out.recs), rec_upd alike
+void permute_launch(Schedule& out, std::vector<int32_t>& rec_upd, int64_t begin, const std::vector<int64_t>& perm) {
+  std::vector<UpdRec> tr(perm.size()); std::vector<int32_t> tu(perm.size());
+  for (size_t i = 0; i < perm.size(); ++i) { tr[i] = out.recs[perm[i]]; tu[i] = rec_upd[perm[i]]; }
+  std::copy(tr.begin(), tr.end(), out.recs.begin() + begin);
+  std::copy(tu.begin(), tu.end(), rec_upd.begin() + begin);
+}
+
+// Inside a launch the order of the records is free (they are independent).  They were placed in SEQUENCE order; what the
+// kernels and the Infinity-Cache ticket orders want is MEMORY order — duals and tables lie in factor insertion order — so that
+// blocks that are near in the list touch tables that are near in HBM, in every step alike.  The two agree for a sweep in
+// insertion order; a backward sweep whose order is the exact reverse of the forward one (a chain of relations through all
+// factors: lpmp_plan_suggest_order's answer) lists every level backwards, and a band order across its steps would need block 0
+// of one step to wait for the last block of the step before (measured: 6.75 instead of 5.25 ms per pass on the headline grid).
+// Records of a launch that are not ascending in the factor index are put in that order (reversed when exactly descending).
+void memory_order(Schedule& out, std::vector<int32_t>& rec_upd) {
   for (const auto& lr : out.launches) {
     const int64_t nrec = lr.end - lr.begin;
     if (nrec < 2) continue;
@@ -752,18 +823,16 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
     std::vector<int64_t> perm((size_t)nrec);
     std::iota(perm.begin(), perm.end(), lr.begin);
     std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return out.recs[x].factor < out.recs[y].factor; });
-    std::vector<UpdRec> tr(perm.size()); std::vector<int32_t> tu(perm.size());
-    for (size_t i = 0; i < perm.size(); ++i) { tr[i] = out.recs[perm[i]]; tu[i] = rec_upd[perm[i]]; }
-    std::copy(tr.begin(), tr.end(), out.recs.begin() + lr.begin);
-    std::copy(tu.begin(), tu.end(), rec_upd.begin() + lr.begin);
+    permute_launch(out, rec_upd, lr.begin, perm);
   }
-  lap_("records");
-  out.ops = std::move(ops);
-  // inside a launch the order of the records is free (they are independent): sub-wave kernels run several
-  // factors per wavefront, so neighbours in the list should have similar amounts of work.  Sorted inside windows of
-  // 1024 records only: the order of the sequence carries the model's locality (rows of a grid), and the Infinity-Cache
-  // ticket orders (make_schedule below, engine.cpp rotation_chain) need blocks that are near in the list to be near in
-  // the model — sorted globally, the border rows of a grid ended up in the last blocks and no band order was valid
+}
+
+// inside a launch the order of the records is free (they are independent): sub-wave kernels run several
+// factors per wavefront, so neighbours in the list should have similar amounts of work.  Sorted inside windows of
+// 1024 records only: the order of the sequence carries the model's locality (rows of a grid), and the Infinity-Cache
+// ticket orders (chain_plan.cpp, engine.cpp rotation_chain) need blocks that are near in the list to be near in
+// the model — sorted globally, the border rows of a grid ended up in the last blocks and no band order was valid
+void work_sort(Schedule& out, std::vector<int32_t>& rec_upd) {
   constexpr int64_t SORT_WINDOW = 1024;
   for (const auto& lr : out.launches)
     if (lr.kclass != KC_GENERIC && lr.kclass != KC_DENSE_32 && lr.kclass != KC_DENSE_V32 && lr.kclass != KC_DENSE_BIG && lr.kclass != KC_PW_32) {   // incl. KC_SMALL
@@ -783,15 +852,15 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
         if (wx != wy) return wx < wy;
         return a.n_recv != b.n_recv ? a.n_recv > b.n_recv : a.n_send > b.n_send;
       });
-      std::vector<UpdRec> tr(perm.size()); std::vector<int32_t> tu(perm.size());
-      for (size_t i = 0; i < perm.size(); ++i) { tr[i] = out.recs[perm[i]]; tu[i] = rec_upd[perm[i]]; }
-      std::copy(tr.begin(), tr.end(), out.recs.begin() + lr.begin);
-      std::copy(tu.begin(), tu.end(), rec_upd.begin() + lr.begin);
+      permute_launch(out, rec_upd, lr.begin, perm);
     }
-  lap_("sorted");
-  // flags of the fast-class records, kept in recs / ops themselves (packets are plain copies)
+}
+
+// flags of the fast-class records, kept in recs / ops themselves (packets are plain copies), and the packet stride of every
+// launch.  Returns the packet slots of all packed launches.
+int64_t packet_flags(Schedule& out) {
   static_assert(sizeof(UpdRec) == sizeof(Op), "a packet slot holds either record");
-  int64_t pk_total = 0;                      // packet slots of all packed launches (the array is allocated once, below)
+  int64_t pk_total = 0;                      // (the array is allocated once, by fill_packets)
   for (auto& lr : out.launches) {
     if (kc_is_pw(lr.kclass)) {               // updated pairwise factors: plain packets (no preload / forwarding flags)
       int kmax = 0;
@@ -819,20 +888,12 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       continue;
     }
     if (!kc_is_packed(lr.kclass)) continue;
-    auto same_vec = [](const Op* o, int a, int b) { return o[a].peer_dual == o[b].peer_dual && ((o[a].info >> 5) & 1) == ((o[b].info >> 5) & 1); };
     if (kc_is_var(lr.kclass)) {
-      // the padded classes only exist in packed / indirect form: what those cannot run goes to the streaming kernel
+      // the padded classes only exist in packed / indirect form: a launch with a record of more ops than the slab holds goes to
+      // the streaming kernel, which works op by op.  (Records with duplicate vectors are not among them: cls_of already gave
+      // them an op-by-op class.)
       bool ok = true;
-      for (int64_t i = lr.begin; i < lr.end && ok; ++i) {
-        const UpdRec& r = out.recs[i];
-        const Op* o = out.ops.data() + r.op_begin;
-        if (r.n_recv + r.n_send > pk_class_cap(lr.kclass)) ok = false;
-        for (int a = 0; a < r.n_recv && ok; ++a)
-          for (int a2 = a + 1; a2 < r.n_recv; ++a2) if (same_vec(o, a, a2)) { ok = false; break; }
-        for (int b = r.n_recv; b < r.n_recv + r.n_send && ok; ++b)
-          for (int b2 = b + 1; b2 < r.n_recv + r.n_send; ++b2) if (same_vec(o, b, b2)) { ok = false; break; }
-      }
-      // (the streaming dense kernel works op by op, so duplicates and any op count are fine for it)
+      for (int64_t i = lr.begin; i < lr.end && ok; ++i) if (out.recs[i].n_recv + out.recs[i].n_send > pk_class_cap(lr.kclass)) ok = false;
       if (!ok) { lr.kclass = KC_DENSE_BIG; continue; }
     }
     // flags of the records (independent of each other: chunks of the launch on several threads), then the packet stride
@@ -844,19 +905,18 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
         UpdRec& r = out.recs[i];
         Op* o = out.ops.data() + r.op_begin;
         kmax_l = std::max<int>(kmax_l, r.n_recv + r.n_send);
-        auto same = [&](int a, int b) { return o[a].peer_dual == o[b].peer_dual && ((o[a].info >> 5) & 1) == ((o[b].info >> 5) & 1); };
         bool preload_ok = true;   // a send may be requested early unless a receive of this update writes the same vector
         for (int a = 0; a < r.n_recv && preload_ok; ++a)
           for (int b = r.n_recv; b < r.n_recv + r.n_send; ++b)
-            if (same(a, b)) { preload_ok = false; break; }
+            if (same_vector(o[a], o[b])) { preload_ok = false; break; }
         if (preload_ok) r.kind_flags |= UPD_PRELOAD_OK;
         // register forwarding: send b targets the vector receive a (one of the first 4) has just rewritten ->
         // the receive keeps its result in a register (pad = 1: no store) and the send reads it from there
         // (pad = a + 1); at most one send per receive, and only if no other receive/send touches that vector
         for (int b = r.n_recv; b < r.n_recv + r.n_send && b - r.n_recv < 4; ++b) {
           int hit = -1, n_hit = 0, n_send_same = 0;
-          for (int a = 0; a < r.n_recv; ++a) if (same(a, b)) { hit = a; ++n_hit; }
-          for (int b2 = r.n_recv; b2 < r.n_recv + r.n_send; ++b2) if (same(b2, b)) ++n_send_same;
+          for (int a = 0; a < r.n_recv; ++a) if (same_vector(o[a], o[b])) { hit = a; ++n_hit; }
+          for (int b2 = r.n_recv; b2 < r.n_recv + r.n_send; ++b2) if (same_vector(o[b2], o[b])) ++n_send_same;
           if (n_hit == 1 && n_send_same == 1 && hit < 4) { o[hit].pad = 1; o[b].pad = hit + 1; }
         }
       }
@@ -870,11 +930,14 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       continue;
     }
     lr.stride = 1 + kmax;
-    lr.pk_begin = pk_total;                  // (filled below, when the size of the whole array is known)
+    lr.pk_begin = pk_total;                  // (filled by fill_packets, when the size of the whole array is known)
     pk_total += n_lr * lr.stride;
   }
-  lap_("pk-flags");
-  // packets: ONE allocation, never zero-filled (every slot is written: the record, its ops, zeros behind them)
+  return pk_total;
+}
+
+// packets: ONE allocation, never zero-filled (every slot is written: the record, its ops, zeros behind them)
+void fill_packets(Schedule& out, int64_t pk_total) {
   out.packets.resize((size_t)pk_total);
   for (const auto& lr : out.launches) {
     if (lr.stride <= 0) continue;
@@ -889,316 +952,46 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
       }
     });
   }
+}
+
+}  // namespace
+
+void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& out, bool chains, std::vector<int32_t>* levels_only) const {
+  out = Schedule();
+  const bool timed_ = std::getenv("LPMP_PLAN_TIMES") != nullptr;
+  auto t_last_ = std::chrono::steady_clock::now();
+  auto lap_ = [&](const char* what) { if (!timed_) return; const auto now = std::chrono::steady_clock::now(); std::fprintf(stderr, "lpmp: make_schedule %-8s %.0f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last_).count()); t_last_ = now; };
+  Updates U;
+  gather_rows(*this, segs, U);
+  lap_("rows");
+  level_recurrence(*this, fuse, U);
+  lap_("levels");
+  out.n_levels = U.max_level;
+  if (levels_only) {
+    levels_only->resize((size_t)U.N);
+    for (int64_t u = 0; u < U.N; ++u) {
+      const int32_t o = U.owner[u];
+      (*levels_only)[(size_t)u] = (U.n_recv_of[o] + U.n_send_of[o] > 0 || ftype_primal[f_type[U.uf[o]]]) ? U.level[o] : 0;
+    }
+    return;
+  }
+  OpVec ops;
+  out.alg_bytes = build_ops(*this, U, ops);
+  lap_("ops");
+  classify(*this, U, ops);
+  lap_("dup");
+  bucket(*this, U, out);
+  memory_order(out, U.rec_upd);
+  lap_("records");
+  out.ops = std::move(ops);
+  work_sort(out, U.rec_upd);
+  lap_("sorted");
+  const int64_t pk_total = packet_flags(out);
+  lap_("pk-flags");
+  fill_packets(out, pk_total);
   lap_("packets");
-  if (!chains && max_level == 3) return;
-  // ---- chain plans: a deep schedule becomes persistent launches (kernels.hip, chain executor), one per kernel class.
-  // Dependencies: update u must see the results of the last earlier update that touched u's factor or a factor u
-  // touches — the same relation the levels were computed from.  Classes are separate launches and cannot wait for each
-  // other, so a schedule qualifies only if no dependency runs between records of different classes (C5: the Potts grid
-  // and the labeling-list factors are separate components); classes with few launches stay plain launches.
-  // (LPMP_CHAIN_MIN: experiments — the smallest number of launches that makes a class a chain)
-  const int64_t chain_min = [] { const char* v = std::getenv("LPMP_CHAIN_MIN"); return v ? (int64_t)std::atoll(v) : CHAIN_MIN_LAUNCHES; }();
-  const bool no_level_loop = std::getenv("LPMP_NO_LEVEL_LOOP") != nullptr;
-  const bool no_auto_bands = std::getenv("LPMP_NO_BLOCKED_PASSES") != nullptr;
-  // (LPMP_BAND_MIN_BYTES, LPMP_BAND_BYTES: tests force the banded order on small models)
-  const char* bmin_env = std::getenv("LPMP_BAND_MIN_BYTES");
-  const int64_t band_min_bytes = bmin_env ? std::atoll(bmin_env) : ((int64_t)64 << 20);
-  // a model that fits the 256 MiB Infinity Cache as a whole is re-read on-die by plain launches already
-  const bool model_big = bmin_env != nullptr || (f_coff[nf] + f_doff[nf]) * (int64_t)sizeof(double) > ((int64_t)1 << 30);
-  const char* bb_env = std::getenv("LPMP_BAND_BYTES");
-  const int64_t band_bytes = bb_env ? std::max<int64_t>(1, std::atoll(bb_env)) : ((int64_t)16 << 20);
-  const char* chain_all_env = std::getenv("LPMP_CHAIN_ALL");
-  const bool chain_all = chain_all_env && std::atoi(chain_all_env) != 0;
-  bool any_big = false;
-  for (const auto& lr : out.launches) any_big = any_big || (model_big && kc_is_dense(lr.kclass) && !kc_is_var(lr.kclass) && lr.n_recv > 0 && lr.bytes >= band_min_bytes);
-  // A long schedule of HEAVY launches (C4 at full size: 66 levels of ~0.8 GB each, 150 - 300 us per launch) gains nothing from a
-  // persistent launch — the gaps between its kernels are a per cent of their run time (measured: 12.15 ms per pass as a chain,
-  // 11.96 ms of kernel time launch by launch) — while its ticket, dependency and mailbox tables are seconds of planning: it
-  // stays a replayed graph of plain launches.  (Few big steps are the banded case below; LPMP_CHAIN_HEAVY_BYTES moves the bar.)
-  if (!chain_all && out.launches.size() > 8) {
-    const char* hv = std::getenv("LPMP_CHAIN_HEAVY_BYTES");
-    const int64_t heavy = hv ? std::atoll(hv) : ((int64_t)256 << 20);
-    int64_t total = 0;
-    for (const auto& lr : out.launches) total += lr.bytes;
-    if (heavy > 0 && total / (int64_t)out.launches.size() >= heavy) return;
-  }
-  if (((int64_t)out.launches.size() >= chain_min || (any_big && out.launches.size() >= 2 && !no_auto_bands)) && !out.launches.empty()) {
-    std::vector<int64_t> n_launches_of(KC_COUNT, 0);
-    bool ok = true;
-    for (const auto& lr : out.launches) {
-      n_launches_of[lr.kclass]++;
-      ok = ok && kc_chain_capable(lr.kclass);
-      // lane-per-factor and generic records: every dual access of a chain kernel is a device-scope access that goes past
-      // the L2, and these bodies issue them one dependent access at a time — measured slower than replaying a hipGraph
-      // of plain launches (C5: 202 ms against 188 ms per pass).  The kernels stay available: LPMP_CHAIN_ALL=1
-      // Those classes get the level loop instead when their levels are tiny (below).
-    }
-    if (ok) {
-      // tickets per class
-      std::vector<ChainPlan> cps(KC_COUNT);
-      std::vector<int32_t> ticket_of_update(N, -1), class_of_update(N, -1);
-      std::vector<int32_t> t0(KC_COUNT, 0);
-      for (size_t li = 0; li < out.launches.size(); ++li) {
-        const auto& lr = out.launches[li];
-        ChainPlan& cp = cps[lr.kclass];
-        cp.kclass = lr.kclass;
-        const int gpb = kc_block_records(lr.kclass);
-        const int32_t nb = (int32_t)((lr.end - lr.begin + gpb - 1) / gpb);
-        cp.launches.push_back({lr.begin, lr.end - lr.begin, lr.pk_begin, lr.stride, t0[lr.kclass]});
-        for (int32_t b = 0; b < nb; ++b) { cp.tk_launch.push_back((int32_t)cp.launches.size() - 1); cp.tk_block.push_back(b); }
-        for (int64_t i = lr.begin; i < lr.end; ++i) { ticket_of_update[rec_upd[i]] = t0[lr.kclass] + (int32_t)((i - lr.begin) / gpb); class_of_update[rec_upd[i]] = lr.kclass; }
-        t0[lr.kclass] += nb;
-        if ((int64_t)t0[lr.kclass] + nb > std::numeric_limits<int32_t>::max() / 2) ok = false;
-      }
-      // ---- mailbox (kernels.hip, dense_pk_body): in a deep chain of a dense class the vector a send writes is what the
-      // neighbour's receive one level later waits for.  Through the completion flag that hand-over costs two trips (flag seen,
-      // then the vector fetched); a send therefore ALSO writes its vector as tagged granules into a mailbox row, the receive
-      // polls that row instead of the dual array, and the dependency between the two tickets needs no flag.
-      // src_rec / src_k: per receive op, the record and send index that LAST wrote the vector the receive reads (the other
-      // side of the pairwise factor) — by vector, not by factor: a record that synchronised on a granule has not seen the
-      // producer's ticket complete, so no one may read that producer's vector from the dual array on its word.
-      const bool no_mailbox = std::getenv("LPMP_NO_MAILBOX") != nullptr;
-      std::vector<char> mbox_class(KC_COUNT, 0);
-      std::vector<int32_t> src_rec, rec_of_upd, rec_launch;
-      std::vector<int8_t> src_k;
-      bool any_mbox = false;
-      if (!no_mailbox && ok) {
-        for (int c = 0; c < KC_COUNT; ++c) {
-          if (!(c >= KC_DENSE_4 && c <= KC_POTTS_V32)) continue;                   // the packed dense and Potts classes, exact and run-time dims
-          // (fewer launches: plain launches, or — a few HBM-sized steps — the banded order below; LPMP_CHAIN_MIN lowers the
-          // bar for the randomised tests, which then run the mailbox on every small chain)
-          bool el = n_launches_of[c] >= chain_min && !(model_big && n_launches_of[c] <= 8 && !no_auto_bands);
-          for (const auto& lr : out.launches) if (lr.kclass == c && lr.stride <= 0) el = false;
-          mbox_class[c] = el; any_mbox = any_mbox || el;
-        }
-      }
-      if (any_mbox) {
-        src_rec.assign(out.ops.size(), -1); src_k.assign(out.ops.size(), -1);
-        rec_of_upd.assign(N, -1); rec_launch.assign(out.recs.size(), -1);
-        std::vector<int32_t> lw_rec((size_t)2 * nf, -1);      // last writer of (factor, side): record ...
-        std::vector<int8_t> lw_k((size_t)2 * nf, -1);         // ... and its send index (-1: written by a receive)
-        for (size_t li = 0; li < out.launches.size(); ++li) {
-          const auto& lr = out.launches[li];
-          for (int64_t i = lr.begin; i < lr.end; ++i) { rec_of_upd[rec_upd[i]] = (int32_t)i; rec_launch[i] = (int32_t)li; }
-          if (!mbox_class[lr.kclass]) continue;
-          if (MAILBOX_SENDS < 4)                    // the mailbox body forwards fewer results in registers: take the other hints back
-            for (int64_t i = lr.begin; i < lr.end; ++i) {
-              const UpdRec& r = out.recs[i];
-              Op* o = out.ops.data() + r.op_begin;
-              Op* pk = out.packets.data() + lr.pk_begin + (i - lr.begin) * lr.stride + 1;
-              for (int b = r.n_recv; b < r.n_recv + r.n_send; ++b) {
-                const int hit = o[b].pad - 1;
-                if (hit >= 0 && (hit >= MAILBOX_SENDS || b - r.n_recv >= MAILBOX_SENDS)) {
-                  o[hit].pad = 0; o[b].pad = 0; pk[hit].pad = 0; pk[b].pad = 0;
-                  out.recs[i].kind_flags &= ~UPD_PRELOAD_OK;      // (it was clear already: the send targets what a receive writes)
-                  Op* hdr = pk - 1; UpdRec rr; std::memcpy(&rr, hdr, sizeof(rr)); rr.kind_flags &= ~UPD_PRELOAD_OK; std::memcpy(hdr, &rr, sizeof(rr));
-                }
-              }
-            }
-          for (int64_t i = lr.begin; i < lr.end; ++i) {
-            const UpdRec& r = out.recs[i];
-            const Op* o = out.ops.data() + r.op_begin;
-            for (int j = 0; j < r.n_recv; ++j) {
-              const int64_t v = (int64_t)2 * o[j].peer + (1 - ((o[j].info >> 5) & 1));
-              const int32_t w = lw_rec[v];
-              if (w >= 0 && lw_k[v] >= 0 && lw_k[v] < MAILBOX_SENDS && out.launches[rec_launch[w]].kclass == lr.kclass) { src_rec[r.op_begin + j] = w; src_k[r.op_begin + j] = lw_k[v]; }
-            }
-            for (int j = 0; j < r.n_recv + r.n_send; ++j) {
-              const int64_t v = (int64_t)2 * o[j].peer + ((o[j].info >> 5) & 1);
-              lw_rec[v] = (int32_t)i; lw_k[v] = j < r.n_recv ? (int8_t)-1 : (int8_t)std::min(j - r.n_recv, 127);
-              // a send after a receive of the same record through the same factor whose result was NOT handed over in a
-              // register: that receive stored the factor's tracked bound, and the reader's own store of that bound is not
-              // ordered after it by a granule -> flag
-              if (j >= r.n_recv && o[j].pad == 0)
-                for (int a = 0; a < r.n_recv; ++a) if (o[a].peer == o[j].peer) lw_k[v] = -1;
-            }
-          }
-        }
-      }
-      if (any_mbox && mailbox_budget_bytes >= 0) {
-        // rows of a class <= its receives with a mailbox source (every row is polled by at least one of them): a class whose
-        // mailbox would not fit the budget keeps its completion flags — decided HERE, before any dependency is dropped
-        std::vector<int64_t> rows_upper(KC_COUNT, 0);
-        for (size_t li = 0; li < out.launches.size(); ++li) {
-          const auto& lr = out.launches[li];
-          if (!mbox_class[lr.kclass]) continue;
-          for (int64_t i = lr.begin; i < lr.end; ++i) {
-            const UpdRec& r = out.recs[i];
-            for (int j = 0; j < r.n_recv; ++j) if (src_rec[r.op_begin + j] >= 0) ++rows_upper[lr.kclass];
-          }
-        }
-        int64_t left = mailbox_budget_bytes;
-        for (int c = 0; c < KC_COUNT; ++c) {
-          if (!mbox_class[c]) continue;
-          const int64_t bytes = rows_upper[c] * (int64_t)kc_width(c) * 16;
-          if (bytes > left) mbox_class[c] = 0; else left -= bytes;
-        }
-      }
-      // replay the sequence: who touched each factor last
-      std::vector<int32_t> toucher(nf, -1);
-      std::vector<std::vector<std::pair<int32_t, int32_t>>> edges(KC_COUNT);     // per class: (ticket, predecessor ticket)
-      for (int64_t u = 0; u < N && ok; ++u) {
-        const int32_t o = owner[u];
-        const int32_t tk = ticket_of_update[o];
-        if (tk < 0) continue;                             // dropped update (no active message)
-        const int32_t f = uf[u];
-        auto visit = [&](int32_t g, bool via_message = false) {
-          const int32_t w = toucher[g];
-          if (w >= 0 && w != o) {
-            if (class_of_update[w] != class_of_update[o]) ok = false;      // a dependency between classes
-            else if (ticket_of_update[w] != tk) {
-              // covered by the mailbox: o receives through g exactly the vector w's send wrote (and w's own reads of g
-              // precede that send in w's program order, so what o writes into g cannot overtake them)
-              bool covered = false;
-              if (via_message && mbox_class[class_of_update[o]]) {
-                const UpdRec& r = out.recs[rec_of_upd[o]];
-                for (int j = 0; j < r.n_recv; ++j)
-                  if (out.ops[r.op_begin + j].peer == g && src_rec[r.op_begin + j] == rec_of_upd[w]) covered = true;
-              }
-              if (!covered) edges[class_of_update[o]].emplace_back(tk, ticket_of_update[w]);
-            }
-          }
-          toucher[g] = o;
-        };
-        visit(f);
-        int64_t ks = 0, kr = 0;
-        for (int64_t j = fm_off[f]; j < fm_off[f + 1]; ++j) {
-          const MsgEntry& e = fm[j];
-          bool active = false;
-          if (e.receives && umk[u][kr++]) active = true;
-          if (e.sends && uom[u][ks++] != 0.0) active = true;
-          if (active) visit(e.adjacent, true);
-        }
-      }
-      for (int c = 0; c < KC_COUNT && ok; ++c) {
-        if (n_launches_of[c] == 0) continue;
-        // A few HBM-sized launches of a dense class (the colour steps of a big grid: forward or backward sweep alone,
-        // a fused pass in a weight mode that does not rotate, the per-pass schedule of a multi-GPU part) are worth a
-        // chain as well: not for the launch gaps but for the ORDER — consecutive steps read the same pairwise tables,
-        // and band j of step l issued at time j + lag * l finds them in the 256 MiB Infinity Cache.
-        if (kc_width(c) == 0 && !chain_all) {
-          // Many TINY levels of the lane-per-factor / generic class (C5 with local triples: 11 887 levels of a dozen
-          // one-lane updates): one workgroup walks the levels with a workgroup barrier in between — no launch per level,
-          // no flags through memory, and the duals it hands from level to level stay in its L2.  Wide levels stay plain.
-          int64_t recs_c = 0;
-          for (const auto& lr : out.launches) if (lr.kclass == c) recs_c += lr.end - lr.begin;
-          if (n_launches_of[c] >= chain_min && recs_c <= (int64_t)kc_block_records(c) * n_launches_of[c] && !no_level_loop) {
-            ChainPlan& lp = cps[c];
-            lp.level_loop = true; lp.valid = true;
-            int dbg_left = 5;
-            if (c == KC_SMALL)
-              for (auto& cl : lp.launches) {           // launches the op-parallel labeling body can run (kernels.hip, label_ops_body)
-                bool fine = true, paired = true;
-                for (int64_t i = cl.rec_begin; i < cl.rec_begin + cl.count && fine; ++i) {
-                  const UpdRec& r = out.recs[i];
-                  const Op* o = out.ops.data() + r.op_begin;
-                  const int n = r.n_recv + r.n_send;
-                  fine = r.n_recv <= 8 && r.n_send <= 8 && (r.kind_flags & 15) == LPMP_F_VECTOR && r.d0 <= SMALL_MAXD;
-                  for (int a = 0; a < n && fine; ++a) {
-                    if ((o[a].info & 15) != OP_LABELING || ((o[a].info >> 4) & 1) != 0 || o[a].pd0 > SMALL_MAXD || o[a].len != r.d0 || o[a].pd1 != r.d0) fine = false;   // message length = label count of the table = the factor's size
-                    // the receives run side by side, and so do the sends: no two of a kind on one peer
-                    for (int b = a + 1; b < n && fine; ++b) if (o[a].peer_dual == o[b].peer_dual && (a < r.n_recv) == (b < r.n_recv)) fine = false;
-                  }
-                  if (r.n_recv != r.n_send) paired = false;
-                  for (int a = 0; a < r.n_recv && paired && fine; ++a)
-                    if (o[a].peer_dual != o[r.n_recv + a].peer_dual || o[a].peer_const != o[r.n_recv + a].peer_const || o[a].pd0 != o[r.n_recv + a].pd0) paired = false;
-                }
-                if (fine) cl.flags |= CHAIN_LAUNCH_LABEL_OPS | (paired ? CHAIN_LAUNCH_LABEL_PAIRED : 0);
-                else if (std::getenv("LPMP_ROT_VERBOSE") && dbg_left-- > 0) {
-                  const UpdRec& r = out.recs[cl.rec_begin]; const Op* o = out.ops.data() + r.op_begin;
-                  std::fprintf(stderr, "lpmp:   not eligible: first record kind %d d0 %d ops %d+%d; op0 code %d role %d pd0 %d pd1 %d len %d\n", r.kind_flags & 15, r.d0, r.n_recv, r.n_send,
-                               (r.n_recv + r.n_send) ? (o[0].info & 15) : -1, (r.n_recv + r.n_send) ? ((o[0].info >> 4) & 1) : -1, (r.n_recv + r.n_send) ? o[0].pd0 : -1, (r.n_recv + r.n_send) ? o[0].pd1 : -1, (r.n_recv + r.n_send) ? o[0].len : -1);
-                }
-              }
-            if (std::getenv("LPMP_ROT_VERBOSE")) {
-              int64_t nf_ = 0, np_ = 0; for (const auto& cl : lp.launches) { nf_ += (cl.flags & CHAIN_LAUNCH_LABEL_OPS) != 0; np_ += (cl.flags & CHAIN_LAUNCH_LABEL_PAIRED) != 0; }
-              std::fprintf(stderr, "lpmp: level loop over %zu launches of class %d, %lld of them with one lane per op (%lld paired)\n", lp.launches.size(), c, (long long)nf_, (long long)np_);
-            }
-            lp.tk_launch.clear(); lp.tk_block.clear(); lp.dep_off.assign(1, 0); lp.dep.clear();
-            out.chains.push_back(std::move(lp));
-          } else {
-            for (size_t li = 0; li < out.launches.size(); ++li) if (out.launches[li].kclass == c) out.plain_launches.push_back((int32_t)li);
-          }
-          continue;
-        }
-        // (only receives read tables: a directional sweep of a 2-colour grid has ONE such step and gains nothing)
-        int64_t max_bytes = 0; int n_table_steps = 0;
-        for (const auto& lr : out.launches) if (lr.kclass == c) { max_bytes = std::max(max_bytes, lr.bytes); if (lr.n_recv > 0 && lr.bytes >= band_min_bytes) ++n_table_steps; }
-        const bool dense_cls = kc_is_dense(c) && !kc_is_var(c);   // (run-time-dims classes: slower as a banded chain, engine.cpp rotation_chain)
-        const bool big_steps = model_big && dense_cls && n_table_steps >= 2 && n_launches_of[c] <= 8 && !no_auto_bands;
-        if (n_launches_of[c] < chain_min && !big_steps) {               // few launches: plain
-          for (size_t li = 0; li < out.launches.size(); ++li) if (out.launches[li].kclass == c) out.plain_launches.push_back((int32_t)li);
-          continue;
-        }
-        ChainPlan& cp = cps[c];
-        auto& ed = edges[c];
-        const int64_t n_tickets = (int64_t)cp.tk_launch.size();
-        if (big_steps && n_tickets > 0) {
-          // about 16 MiB of algorithmic bytes per band; the smallest lag from 3 on that keeps every dependency backwards (the
-          // skewed band order of order.cpp, one group over all of the class's launches)
-          const int gpb = kc_block_records(c);
-          std::vector<int64_t> nb;
-          int64_t max_nb = 1;                               // (a band narrower than a few blocks cannot keep the dependencies)
-          for (const auto& l : cp.launches) { nb.push_back((l.count + gpb - 1) / gpb); max_nb = std::max(max_nb, nb.back()); }
-          const int nbands = (int)std::max<int64_t>(2, std::min<int64_t>(max_bytes / band_bytes, max_nb / 4));
-          TicketOrder o;
-          for (int lg = 3; lg <= 16 && !cp.banded; ++lg) {
-            band_order(nb, nbands, lg, (int)nb.size(), o);
-            bool fine = true;
-            for (const auto& e : ed) if (o.new_of[e.second] >= o.new_of[e.first]) { fine = false; break; }
-            if (!fine) continue;
-            for (auto& e : ed) { e.first = o.new_of[e.first]; e.second = o.new_of[e.second]; }
-            cp.tk_launch.swap(o.tk_step); cp.tk_block.swap(o.tk_block);
-            cp.banded = true;
-          }
-          if (!cp.banded && n_launches_of[c] < chain_min) {   // no valid order and nothing else to gain: plain launches
-            for (size_t li = 0; li < out.launches.size(); ++li) if (out.launches[li].kclass == c) out.plain_launches.push_back((int32_t)li);
-            continue;
-          }
-        }
-        std::sort(ed.begin(), ed.end());
-        ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
-        cp.dep_off.assign((size_t)n_tickets + 1, 0);
-        for (const auto& e : ed) { if (e.second >= e.first) fail("chain plan: dependency on a later ticket"); cp.dep_off[e.first + 1]++; }
-        std::partial_sum(cp.dep_off.begin(), cp.dep_off.end(), cp.dep_off.begin());
-        cp.dep.resize(ed.size());
-        for (size_t i = 0; i < ed.size(); ++i) cp.dep[i] = ed[i].second;   // sorted by ticket: already in CSR order
-        cp.valid = true;
-        if (mbox_class[c]) {
-          if (cp.banded) fail("chain plan: mailbox in a banded order");
-          // rows for the sends some receive polls; the packet copies of both ops carry the row (plan.hpp, OP_MAILBOX)
-          std::vector<int64_t> row_of_op;                     // per op of out.ops (sends): mailbox row, assigned on first use
-          row_of_op.assign(out.ops.size(), -1);
-          auto slot_of = [&](int64_t i) { const auto& lr = out.launches[rec_launch[i]]; return out.packets.data() + lr.pk_begin + (i - lr.begin) * lr.stride; };
-          int64_t rows = 0;
-          for (const auto& cl : cp.launches)
-            for (int64_t i = cl.rec_begin; i < cl.rec_begin + cl.count; ++i) {
-              const UpdRec& r = out.recs[i];
-              for (int j = 0; j < r.n_recv; ++j) {
-                const int32_t w = src_rec[r.op_begin + j];
-                if (w < 0) continue;
-                const UpdRec& rw = out.recs[w];
-                const int64_t sop = (int64_t)rw.op_begin + rw.n_recv + src_k[r.op_begin + j];
-                if (row_of_op[sop] < 0) {
-                  row_of_op[sop] = rows++;
-                  Op& ps = slot_of(w)[1 + rw.n_recv + src_k[r.op_begin + j]];
-                  ps.peer_const = row_of_op[sop]; ps.info |= OP_MAILBOX;
-                }
-                Op& pr = slot_of(i)[1 + j];
-                std::memcpy(&pr.omega, &row_of_op[sop], sizeof(double)); pr.info |= OP_MAILBOX;
-                ++cp.mailbox_receives;
-              }
-            }
-          if (rows > 0) {
-            cp.mailbox_rows = rows; cp.mailbox_width = kc_width(c);
-            for (auto& cl : cp.launches) cl.flags |= CHAIN_LAUNCH_MAILBOX;
-          }
-        }
-        out.chains.push_back(std::move(cp));
-      }
-      if (!ok) { out.chains.clear(); out.plain_launches.clear(); }
-    }
-  }
+  if (!chains && U.max_level == 3) return;
+  plan_chains(*this, UpdateView{U.N, U.uf.data(), U.owner.data(), U.uom.data(), U.umk.data()}, U.rec_upd, chain_settings_from_env(), out);
 }
 
 

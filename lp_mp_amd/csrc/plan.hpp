@@ -41,7 +41,7 @@ struct Csr {
 // Device-side records (plain structs shared with kernels.hip) -----------------------------------
 enum OpCode : int32_t { OP_UP = 0, OP_LABELING = 1, OP_MINNORM = 2 };
 constexpr int32_t OP_HAS_IMPROVEMENT = 1 << 12;   // Op::info: the message op defines send_message_to_*_improvement
-// Op::info, only in the PACKET copy of an op of a chain launch with CHAIN_LAUNCH_MAILBOX (plan.cpp, chain plans): the
+// Op::info, only in the PACKET copy of an op of a chain launch with CHAIN_LAUNCH_MAILBOX (chain_plan.cpp): the
 // message vector travels through the chain's mailbox.  A send: peer_const = mailbox row the new vector is also written to;
 // a receive: the bits of omega = mailbox row (int64) the OTHER side's vector is polled from instead of the dual array.
 constexpr int32_t OP_MAILBOX = 1 << 13;
@@ -172,8 +172,7 @@ constexpr int kc_block_records(int kclass) {
   if (kclass == KC_SMALL) return SMALL_BLOCK_RECORDS;
   const int w = kc_width(kclass);
   if (w == 0) return 0;
-  const bool dense = (kclass >= KC_DENSE_4 && kclass <= KC_DENSE_32) || (kclass >= KC_DENSE_V4 && kclass <= KC_DENSE_V32);
-  return dense ? (w == 32 ? 4 : 256 / w) : 256 / w;   // dense: G = 64 lanes at 32 labels, else one lane per label
+  return kc_is_dense(kclass) ? (w == 32 ? 4 : 256 / w) : 256 / w;   // dense: G = 64 lanes at 32 labels, else one lane per label
 }
 constexpr bool kc_chain_capable(int kclass) { return kc_is_packed(kclass) || kclass == KC_GENERIC || kclass == KC_SMALL; }
 constexpr int64_t CHAIN_MIN_LAUNCHES = 9;   // shorter schedules run as plain launches
@@ -328,6 +327,28 @@ struct RotationInfo {
 // fb, bf: forward+backward and backward+forward of a mode whose passes join (engine.cpp plan_rotation), nf factors; not valid
 // unless H, W, K, T are one packed launch each of one chain-capable class
 RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf);
+
+// ---- chain_plan.cpp: the chain plans of a deep schedule, from its records, launches and packets ------------------------------
+// the knobs of chain planning (chain_settings_from_env: read on every make_schedule that reaches chain planning)
+struct ChainSettings {
+  int64_t chain_min = CHAIN_MIN_LAUNCHES;       // LPMP_CHAIN_MIN: the smallest number of launches that makes a class a chain
+  bool chain_all = false;                       // LPMP_CHAIN_ALL != 0: tickets for the generic / lane-per-factor classes too, no heavy-launch exit
+  bool no_level_loop = false;                   // LPMP_NO_LEVEL_LOOP set
+  bool no_blocked_passes = false;               // LPMP_NO_BLOCKED_PASSES set: no banded order
+  int64_t band_min_bytes = (int64_t)64 << 20;   // LPMP_BAND_MIN_BYTES: bytes of a step with table reads that count for the banded order
+  bool band_min_set = false;                    // ... set: every model counts as bigger than the Infinity Cache
+  int64_t band_bytes = (int64_t)16 << 20;       // LPMP_BAND_BYTES (>= 1): algorithmic bytes per band
+  int64_t heavy_bytes = (int64_t)256 << 20;     // LPMP_CHAIN_HEAVY_BYTES: mean bytes per launch from which a long schedule stays plain (<= 0: never)
+  bool no_mailbox = false;                      // LPMP_NO_MAILBOX set: every hand-over through a completion flag
+  bool verbose = false;                         // LPMP_ROT_VERBOSE set: level-loop diagnostics on stderr
+};
+ChainSettings chain_settings_from_env();
+// the update sequence of a schedule as make_schedule saw it: per update its factor, the update whose record holds its ops (itself
+// unless it was folded into an earlier one), its omega and receive-mask rows
+struct UpdateView { int64_t n; const int32_t* factor; const int32_t* owner; const double* const* om; const uint8_t* const* mk; };
+// rec_upd: the update each record of `out` stands for.  Fills out.chains and out.plain_launches, and marks the mailbox ops of
+// out.packets (OP_MAILBOX); throws std::runtime_error on an inconsistent plan
+void plan_chains(const Plan& p, const UpdateView& seq, const std::vector<int32_t>& rec_upd, const ChainSettings& cs, Schedule& out);
 
 // the window of the band order: LPMP_ROT_BANDS / _LAG / _DEPTH (bands 0: from the table bytes per step; *_set: given, used as they are)
 struct RotSettings { int bands = 0, lag = 3, depth = 4; bool lag_set = false, depth_set = false; };

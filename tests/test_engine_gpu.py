@@ -462,7 +462,7 @@ def test_chain_executor_deep_schedules(pairwise, L, H, W, monkeypatch):
 def test_few_big_launches_run_as_a_banded_chain(pairwise, L, H, W, band_bytes, monkeypatch):
     """the colour steps of an HBM-sized dense grid — a directional sweep, a fused pass in a mode that does not rotate, a
     fused custom schedule like the per-pass schedule of a multi-GPU part — run as one chain launch in Infinity-Cache
-    order (plan.cpp make_schedule).  Forced onto small models here (LPMP_BAND_MIN_BYTES / LPMP_BAND_BYTES); bit for bit
+    order (chain_plan.cpp plan_chains).  Forced onto small models here (LPMP_BAND_MIN_BYTES / LPMP_BAND_BYTES); bit for bit
     against the oracle"""
     from lp_mp_amd.multi_gpu import _cat_rows
     monkeypatch.setenv("LPMP_BAND_MIN_BYTES", "1000"); monkeypatch.setenv("LPMP_BAND_BYTES", str(band_bytes))

@@ -1,4 +1,4 @@
-"""Mailbox of the dense chain executor (plan.cpp: which message vectors travel as tagged granules and which dependencies
+"""Mailbox of the dense chain executor (chain_plan.cpp: which message vectors travel as tagged granules and which dependencies
 that covers; kernels.hip: mailbox_put / mailbox_take) against the oracle, bit for bit — with the mailbox, with every
 hand-over through completion flags (LPMP_NO_MAILBOX=1), and against each other."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Host logic of the product (lp_mp_amd/csrc/plan.cpp, reached through the C ABI) against the oracle:
+"""Host logic of the product (lp_mp_amd/csrc/plan.cpp and chain_plan.cpp, reached through the C ABI) against the oracle:
 orderings, per-factor message lists, weights and receive masks for every mode.  No GPU needed."""
 import ctypes as C
 
@@ -395,7 +395,7 @@ def test_packed_classes_only_hold_records_the_packed_kernels_run():
 def test_chain_plans_default_to_the_packed_classes(monkeypatch):
     """deep schedules of the packed dense / Potts classes become chain launches (tickets + flags); many tiny levels of the
     lane-per-factor class become the level loop (one workgroup, no tickets); the ticket form of that class only on
-    request (LPMP_CHAIN_ALL=1: measured slower than graph replay, plan.cpp make_schedule)"""
+    request (LPMP_CHAIN_ALL=1: measured slower than graph replay, chain_plan.cpp plan_chains)"""
     assert E.Plan(S.grid_model(40, 30, 8, order="row_major")).chain_info(M.FORWARD, M.REPAM_ANISOTROPIC)["n_chains"] == 1
     m = S.c5_model(24, 24, 8, 400, 300, 100, seed=5, window=16)
     ci = E.Plan(m).chain_info(M.BACKWARD, M.REPAM_ANISOTROPIC)
@@ -409,7 +409,7 @@ def test_chain_plans_default_to_the_packed_classes(monkeypatch):
 
 
 def test_mailbox_covers_the_hand_overs_of_a_deep_dense_chain(monkeypatch):
-    """plan.cpp: in a deep chain of an exact dense class a receive polls the mailbox row its neighbour's send writes, and the
+    """chain_plan.cpp: in a deep chain of an exact dense class a receive polls the mailbox row its neighbour's send writes, and the
     dependency between the two tickets is dropped; what a granule cannot vouch for keeps its flag (the own factor's previous
     update in the fused pass); short schedules and LPMP_NO_MAILBOX=1 keep every flag"""
     monkeypatch.delenv("LPMP_NO_MAILBOX", raising=False)
@@ -559,3 +559,19 @@ def test_ticket_orders_of_the_joined_passes(tmp_path):
                            os.path.join(root, "tests", "cpp", "test_ticket_order.cpp"), os.path.join(csrc, "order.cpp"), "-lpthread"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "ticket orders ok" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+
+
+def test_planner_is_plain_cpp17_without_hip(tmp_path):
+    """plan.hpp's claim: the planner (plan.cpp, chain_plan.cpp, order.cpp) is pure C++17 without HIP — it links into a shared
+    library with g++ alone, no undefined symbol left and no warning"""
+    import os
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.fail("g++ not found")
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lp_mp_amd", "csrc")
+    out = subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-Wl,--no-undefined",
+                          "-o", str(tmp_path / "libplanner.so")] + [os.path.join(csrc, f) for f in ("plan.cpp", "chain_plan.cpp", "order.cpp")]
+                         + ["-lpthread"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
