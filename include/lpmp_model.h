@@ -45,7 +45,16 @@ enum lpmp_factor_kind {
   LPMP_F_PAIRWISE_DENSE = 1,
   /* const scalar diff; dual = m1[dim0], m2[dim0]; cost(a,b) = diff*[a!=b] + m1[a] + m2[b]
    * (test/potts_factor.cpp:8-72). dim1 == dim0. */
-  LPMP_F_PAIRWISE_POTTS = 2
+  LPMP_F_PAIRWISE_POTTS = 2,
+  /* const scalar scale; dual = m1[dim0], m2[dim1] (the layout of PAIRWISE_DENSE);
+   * cost(a,b) = scale * V[a][b] + m1[a] + m2[b] with V = shared table f_table[f] of the model-level pool below
+   * (dim0 x dim1 must be the table's dims).  The product is ONE IEEE double multiply wherever the cost is needed, so
+   * the factor is bit for bit a PAIRWISE_DENSE factor whose table is scale * V computed on the host.  +inf entries of V
+   * are hard constraints; scale is finite, and positive where the table holds infinities.  NaN entries are refused.  A scale
+   * of 0 (or NaN) on a table with infinities is outside the contract and NOT detected (the scale may live in device memory):
+   * the NaN products it makes are dropped by the minima of the shared kernel classes but propagate on the generic kernels
+   * and in a dense expansion. */
+  LPMP_F_PAIRWISE_SHARED = 3
 };
 
 enum lpmp_factor_flags {
@@ -143,7 +152,7 @@ typedef struct lpmp_model {
   const int32_t* f_dim0;            /* [n_factors] */
   const int32_t* f_dim1;            /* [n_factors] (PAIRWISE_DENSE only; else ignored) */
   /* packed by factor in insertion order; per-factor sizes follow from kind/dims:
-   *   const: DENSE dim0*dim1, POTTS 1, VECTOR 0;  dual: VECTOR dim0, DENSE dim0+dim1, POTTS 2*dim0 */
+   *   const: DENSE dim0*dim1, POTTS 1, SHARED 1, VECTOR 0;  dual: VECTOR dim0, DENSE / SHARED dim0+dim1, POTTS 2*dim0 */
   const double* const_data;
   const double* dual_data;
 
@@ -165,14 +174,25 @@ typedef struct lpmp_model {
    * --reparametrizationType partition / overlapping_partition (LP_MP.h:1717-1822) --- */
   int64_t n_part_pairs;
   const int32_t* part_pairs;        /* [n_part_pairs][2] */
+
+  /* --- shared pairwise tables (LPMP_F_PAIRWISE_SHARED): table t is sh_dim0[t] x sh_dim1[t], row-major at
+   * sh_data[sh_off[t]]; sh_off[t+1] - sh_off[t] = sh_dim0[t] * sh_dim1[t].  sh_data is HOST memory whatever the
+   * memory kind of const_data.  f_table[f] = table of factor f (read for SHARED factors only; may be NULL when the model
+   * has none).  A caller that zero-initialises the struct and has no SHARED factor need not touch these fields. --- */
+  int32_t n_shared_tables;
+  const int64_t* sh_off;            /* [n_shared_tables+1] */
+  const int32_t* sh_dim0;           /* [n_shared_tables] */
+  const int32_t* sh_dim1;           /* [n_shared_tables] */
+  const double* sh_data;
+  const int32_t* f_table;           /* [n_factors] */
 } lpmp_model;
 
 /* sizes implied by kind/dims */
 static inline int64_t lpmp_factor_const_size(int kind, int dim0, int dim1) {
-  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 1 : 0);
+  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : ((kind == LPMP_F_PAIRWISE_POTTS || kind == LPMP_F_PAIRWISE_SHARED) ? 1 : 0);
 }
 static inline int64_t lpmp_factor_dual_size(int kind, int dim0, int dim1) {
-  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
+  return (kind == LPMP_F_PAIRWISE_DENSE || kind == LPMP_F_PAIRWISE_SHARED) ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
 }
 
 #ifdef __cplusplus

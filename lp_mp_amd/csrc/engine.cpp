@@ -41,6 +41,10 @@ bool launch_dense_lb(int L, const void* recs, const double* dual, const double* 
 void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s);
 void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 void launch_rows_copy(const void* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s);
+bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
+                         double* lb, int32_t* primal, int64_t count, int flags, const void* desc, const int32_t* tabs, int n_tabs, hipStream_t s);
+void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStream_t s);
+struct ShTableDescHost { int64_t off; int32_t d0, d1; };   // kernels.hip: ShTableDesc
 struct RowRecHost { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
 int generic_max_dual();
 int generic_max_adaptive_sends();
@@ -267,6 +271,9 @@ struct lpmp_engine {
   // newer message vectors than the packed array; rows_stale: the packed array was (or may have been) written by the caller
   bool want_rows = false, rows = false, packed_stale = false, rows_stale = false;
   double* d_rows = nullptr; RowRecHost* d_rowrecs = nullptr; int64_t n_rowrecs = 0;
+  // shared pairwise tables: [two words {scale, table offset} per SHARED factor | the pool], an allocation of the engine's own
+  // that the SHARED factors' device const offsets point into (Plan::dev_coff), and the pool's tables as the shared classes' kernel sees them
+  double* d_shared = nullptr; ShTableDescHost* d_sh_desc = nullptr;
   int nt_flag = 0;                // SWEEP_NT when tables + duals are far larger than L2 + Infinity Cache
   bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
   struct LbRun { int cls; int64_t first, count; };
@@ -371,6 +378,8 @@ struct lpmp_engine {
     if (d_tabs) { (void)hipFree(d_tabs); d_tabs = nullptr; }
     if (d_rows) { (void)hipFree(d_rows); d_rows = nullptr; }
     if (d_rowrecs) { (void)hipFree(d_rowrecs); d_rowrecs = nullptr; }
+    if (d_shared) { (void)hipFree(d_shared); d_shared = nullptr; }
+    if (d_sh_desc) { (void)hipFree(d_sh_desc); d_sh_desc = nullptr; }
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
     if (d_lbrecs) { (void)hipFree(d_lbrecs); d_lbrecs = nullptr; }
     if (d_lb) { (void)hipFree(d_lb); d_lb = nullptr; }
@@ -692,6 +701,11 @@ void issue_launches(lpmp_engine* e, const DevSchedule& s, bool timed, hipStream_
     const bool pw_rounds = e->primal_pass && e->d_pw_unary && kc_is_pw(lr.kclass);
     if (pw_rounds)
       launch_sweep(KC_GENERIC, s.recs, s.ops, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->d_pw_unary, lr.begin, lr.end - lr.begin, flags, stream);
+    else if (kc_is_shared(lr.kclass)) {
+      if (!launch_sweep_shared(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual, e->d_const,
+                               e->d_lb, e->d_primal, lr.end - lr.begin, flags, e->d_sh_desc, lr.sh_tab, lr.n_sh, stream))
+        throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
+    }
     else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
                               e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
@@ -1370,6 +1384,34 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
           }
         e->rows = true; e->packed_stale = false; e->rows_stale = false;
       }
+    }
+    if (!p.f_table.empty()) {
+      // SHARED pairwise factors: the host format is one double (the scale) per factor and a model-level pool of tables; on the
+      // device a factor's constants are two words {scale, offset of its table relative to the const base pointer} in an
+      // allocation of the engine's own, followed by the pool (always copied from the host: sh_data is host memory also when the
+      // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
+      std::vector<int64_t> sf;
+      for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED) sf.push_back(f);
+      const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared];
+      HIP_CHECK(hipMalloc((void**)&e->d_shared, (size_t)(2 * n_sf + n_pool) * sizeof(double)));
+      if ((((uintptr_t)e->d_shared - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
+      const int64_t base = (int64_t)(((intptr_t)e->d_shared - (intptr_t)e->d_const) / 8);
+      std::vector<int64_t> cells((size_t)(2 * n_sf));
+      if (pl->p.dev_coff.empty()) pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
+      for (int64_t k = 0; k < n_sf; ++k) {
+        const int64_t f = sf[(size_t)k];
+        cells[(size_t)(2 * k)] = p.f_coff[f];
+        cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + p.sh_off[(size_t)p.f_table[f]];
+        pl->p.dev_coff[f] = base + 2 * k;
+      }
+      h2d(e->d_shared, cells.data(), cells.size() * sizeof(int64_t), e->stream);
+      h2d(e->d_shared + 2 * n_sf, p.sh_data.data(), (size_t)n_pool * sizeof(double), e->stream);
+      launch_shared_cells(e->d_shared, n_sf, e->d_const, e->stream);
+      HIP_CHECK(hipGetLastError());
+      std::vector<ShTableDescHost> desc((size_t)p.n_shared);
+      for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + p.sh_off[(size_t)t], p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
+      HIP_CHECK(hipMalloc((void**)&e->d_sh_desc, desc.size() * sizeof(ShTableDescHost)));
+      h2d(e->d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDescHost), e->stream);
     }
     if (!p.tab_data.empty()) {
       HIP_CHECK(hipMalloc((void**)&e->d_tabs, p.tab_data.size() * sizeof(int32_t)));

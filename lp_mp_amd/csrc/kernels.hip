@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include <type_traits>
 
 #include "plan.hpp"
@@ -371,9 +372,16 @@ template <> struct GenCtx<1> {
   __device__ __forceinline__ static void sync() {}
 };
 
-// pairwise cost T(a,b) of a pairwise factor (dense table or Potts scalar)
+// Device placement of a SHARED pairwise factor's constants (engine.cpp, lpmp_upload_model): two 8-byte words
+// {scale, offset of its table relative to the const base pointer as an int64}; the table is row-major d0 x d1.
+__device__ __forceinline__ int64_t shared_table_off(const double* __restrict__ cdata, int64_t coff) {
+  return __double_as_longlong(cdata[coff + 1]);
+}
+// pairwise cost T(a,b) of a pairwise factor (dense table, Potts scalar, or scale * shared table: ONE multiply, so that the
+// factor is bit for bit a dense factor whose table is scale * V)
 __device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int64_t coff, int kind, int d1, int a, int b) {
   if (kind == LPMP_F_PAIRWISE_DENSE) return cdata[coff + (int64_t)a * d1 + b];
+  if (kind == LPMP_F_PAIRWISE_SHARED) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (int64_t)a * d1 + b];
   return a == b ? 0.0 : cdata[coff];
 }
 
@@ -772,12 +780,22 @@ __device__ __forceinline__ void load_packet(double2_t* slab, const Op* __restric
 // <= L, the own side's equal to the label count) are read at run time, lanes beyond them carry +inf / 0
 // NT: streaming policy of the table loads.  A: access policy of the duals.  CHAIN: called from the chain executor with a
 // ticket: everything constant is requested first, then the ticket's predecessors are awaited, then the duals are read.
-template <int L, int KMAX, bool VAR, bool NT, int A, bool CHAIN, bool MBOX = false>
+// SHARED (the shared classes, VAR form only): every peer is a SHARED pairwise factor; its table is not fetched but read from
+// the LDS slots the workgroup staged and multiplied by the peer's scale, piece by piece, where the dense form uses the registers
+// it loaded.  sh_lds: per table TWO slots of L x L doubles, row stride L — V and its transpose — with NaN beyond the table's
+// dims (fmin drops a NaN operand, whatever the sign of the scale; a lane whose whole row or column is padding holds a label
+// the factor does not have and is never read); sh_toff[q] = offset of table q relative to cdata, n_sh tables.  A receive on
+// side 0 (own label = row of V) reduces the TRANSPOSE with the column form of side 1: the lane accumulates its two columns over
+// the steps and the row-lanes meet in two shuffles, instead of a DPP row reduction per step — min is exact, so q is the same
+// number either way; at 32 labels that is 110 instead of 270 FP64 instructions per receive, and the pass is bound by them.
+template <int L, int KMAX, bool VAR, bool NT, int A, bool CHAIN, bool MBOX = false, bool SHARED = false>
 __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
                                               double* __restrict__ dual, const double* __restrict__ cdata, double* __restrict__ lb,
                                               int32_t* __restrict__ primal, int64_t count, int stride, int flags, int64_t block,
                                               const ChainArgs* ca, int ticket, double* __restrict__ lbh = nullptr, int hmode = 0,
-                                              unsigned long long* __restrict__ mbox = nullptr, int n_deps = -1) {
+                                              unsigned long long* __restrict__ mbox = nullptr, int n_deps = -1,
+                                              const double* sh_lds = nullptr, const int64_t* sh_toff = nullptr, int n_sh = 0) {
+  static_assert(!SHARED || (VAR && !CHAIN && !MBOX), "the shared classes: run-time dims, plain launches");
   static_assert(!CHAIN || A == ACC_COH, "chain bodies hand results over through relaxed agent-scope flags: every dual access must be an agent-scope (sc1) access");
   static_assert(MAILBOX_SENDS >= 1 && MAILBOX_SENDS <= 4, "plan.hpp: the sends whose fields are held in registers (KS)");
   static_assert(!MBOX || CHAIN, "the mailbox belongs to the chain executor");   // (an instantiation of its own: the joined passes of the headline grid lost 8 % with the mailbox fields in their registers)
@@ -785,7 +803,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
   constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
   constexpr int KS = MBOX ? MAILBOX_SENDS : 4;   // sends whose target vectors are prefetched / forwarded
   constexpr int NFW = MBOX ? MAILBOX_SENDS : 4;  // receives whose result can be forwarded in registers (plan.cpp: hints of mailbox chains stay below)
-  constexpr int PIECES = 3 * (1 + pk_dense_cap(L));      // 16-B pieces of the largest packet / op list
+  constexpr int PIECES = 3 * (1 + (SHARED ? pk_indirect_cap(L) : pk_dense_cap(L)));      // 16-B pieces of the largest packet / op list
   __shared__ double2_t lds_pk[GPB][PIECES];
   __shared__ double lds_mo[GPB][L];
   __shared__ double lds_q[GPB][L];
@@ -856,7 +874,9 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
   auto chunk = [&](const int c, auto fw_tag, auto first_tag) {
     constexpr bool FW = decltype(fw_tag)::value;
     constexpr bool FIRST = decltype(first_tag)::value;
-    double2_t t[KMAX][NL];
+    // the tables in registers — NOT under SHARED, where t is never written: every read of a table piece goes through tab() below
+    [[maybe_unused]] double2_t t[KMAX][NL];
+    [[maybe_unused]] const double* tsl[KMAX]; [[maybe_unused]] double tsc[KMAX];   // SHARED: the peer's table slot in LDS, its scale
     double msv[KMAX], mov[KMAX];
     int64_t pdual[KMAX];
     int side[KMAX], defer[KMAX], roff[KMAX];     // roff: offset of the own-side message vector in the peer's dual
@@ -866,6 +886,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     for (int j = 0; j < KMAX; ++j) {             // request everything constant first
       const bool act = c + j < n_recv;
       pdual[j] = 0; side[j] = 0; defer[j] = 0; roff[j] = 0; msv[j] = 0.0; mov[j] = 0.0; dR[j] = L; dC[j] = L; box[j] = nullptr;
+      if constexpr (SHARED) { tsl[j] = sh_lds; tsc[j] = 0.0; }
       if (act) {
         const Op& o = lop[c + j];
         pdual[j] = uni64<G>(o.peer_dual);
@@ -875,6 +896,19 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
         side[j] = (uni<G>(o.info) >> 5) & 1;
         defer[j] = FW ? uni<G>(o.pad) : 0;
         const double* T = cdata + uni64<G>(o.peer_const);
+        if constexpr (SHARED) {
+          const int R = uni<G>(o.pd0), C = uni<G>(o.pd1);
+          dR[j] = R; dC[j] = C;
+          roff[j] = side[j] == 0 ? 0 : R;
+          const int64_t toff = uni64<G>(__double_as_longlong(T[1]));
+          int slot = -1;
+          for (int q = 0; q < n_sh; ++q) if (sh_toff[q] == toff) slot = q;
+          // (a table the launch did not stage would be a planning error: a NaN scale turns every dual this receive writes
+          // into NaN instead of computing with another table)
+          tsc[j] = slot >= 0 ? T[0] : LPMP_NAN;
+          if (slot < 0) slot = 0;
+          tsl[j] = sh_lds + (2 * slot + (side[j] == 0 ? 1 : 0)) * (L * L);   // side 0: the transpose
+        } else
         if constexpr (VAR) {
           const int R = uni<G>(o.pd0), C = uni<G>(o.pd1);
           dR[j] = R; dC[j] = C;
@@ -902,11 +936,19 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
 #pragma unroll
           for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<NT>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
         }
-      } else {
+      } else if constexpr (!SHARED) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
       }
     }
+    // piece i of receive j's table as the lane holds it: registers, or (SHARED) one 16-byte LDS read of the staged table times
+    // the peer's scale — consecutive lanes read consecutive 16-byte pieces (i * 2G + 2g doubles into the slot: conflict free)
+    auto tab = [&](const int j, const int i) -> double2_t {
+      if constexpr (SHARED) {
+        const double2_t v = *reinterpret_cast<const double2_t*>(tsl[j] + i * 2 * G + 2 * g);
+        return double2_t{tsc[j] * v.x, tsc[j] * v.y};
+      } else return t[j][i];
+    };
     if constexpr (CHAIN && FIRST) {              // the tables are in flight while the predecessors finish
       if (MBOX && n_deps == 0) chain_stamp(*ca, ticket, 1);   // (chain_loop_ahead knows: nothing to wait for, no barrier)
       else aborted = !chain_wait(*ca, ticket);
@@ -947,11 +989,12 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
       const bool act = c + j < n_recv;
       if (g < L) lds_mo[grp][g] = mov[j];
       wave_sync();
-      if (side[j] == 0) {
+      if (!SHARED && side[j] == 0) {
         const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_mo[grp][2 * c2]);
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
-          double v = fmin(t[j][i].x + mv.x, t[j][i].y + mv.y);
+          const double2_t tv = tab(j, i);
+          double v = fmin(tv.x + mv.x, tv.y + mv.y);
           v = row_allreduce_min<CL>(v);
           if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
         }
@@ -960,8 +1003,9 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
           const double m1v = lds_mo[grp][i * RPL + rl];
-          vx = fmin(vx, t[j][i].x + m1v);
-          vy = fmin(vy, t[j][i].y + m1v);
+          const double2_t tv = tab(j, i);
+          vx = fmin(vx, tv.x + m1v);
+          vy = fmin(vy, tv.y + m1v);
         }
 #pragma unroll
         for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
@@ -1154,6 +1198,45 @@ sweep_dense_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__
                       int32_t* __restrict__ primal, int64_t count, int stride, int flags) {
   dense_pk_body<L, KMAX, VAR, NT, NT ? ACC_NT : ACC_PLAIN, false>(packets, recs, ops, dual, cdata, lb, primal, count, stride, flags,
                                                                    (int64_t)blockIdx.x, nullptr, 0);
+}
+
+// Shared classes: unaries whose pairwise peers are all SHARED factors (cost = scale * V[a][b], V one of a handful of tables
+// of the model).  A workgroup stages the launch's distinct tables in LDS ONCE (per table V and its transpose: L x L doubles each,
+// row stride L, NaN beyond the table's dims) and then walks blocks of records in a grid-stride loop, so that the staging
+// amortises; a receive reads its pieces of V from LDS — no table byte comes from global memory per receive.  The body is the
+// dense packed body (packets / indirect records, lane mapping, send-target prefetch, tracked bounds, primal and residual rules)
+// with ONE deviation: the dense form reduces a side-0 receive with a DPP row minimum per step; here both sides take the column
+// form (side 0 on the staged transpose).  min is exact and order-free, so q — and with it every dual — is the same number bit for
+// bit (tests/test_shared_tables_gpu.py compares with the oracle on the expansion by np.array_equal).
+// LDS: the slabs of a lane group are private to its wave, so consecutive blocks of one wave need no workgroup barrier.
+struct ShTableDesc { int64_t off; int32_t d0, d1; };                 // a table of the pool: offset relative to the const base pointer, dims
+struct ShTabList { int32_t n; int32_t t[SHARED_MAX_TABLES]; };      // the tables of one launch (indices into the pool)
+template <int L, bool NT>
+__global__ void __launch_bounds__(256)
+sweep_shared_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
+                       double* __restrict__ dual, const double* __restrict__ cdata, double* __restrict__ lb,
+                       int32_t* __restrict__ primal, int64_t count, int stride, int flags,
+                       const ShTableDesc* __restrict__ desc, ShTabList list) {
+  extern __shared__ __attribute__((aligned(16))) double sh_tables[];   // 2 * max(1, list.n) slots of L x L doubles: V, its transpose
+  __shared__ int64_t sh_toff[SHARED_MAX_TABLES];
+  const int n_sh = list.n < SHARED_MAX_TABLES ? list.n : SHARED_MAX_TABLES;
+  for (int q = 0; q < n_sh; ++q) {
+    const ShTableDesc d = desc[list.t[q]];
+    if (threadIdx.x == 0) sh_toff[q] = d.off;
+    const double* V = cdata + d.off;
+    for (int x = threadIdx.x; x < L * L; x += 256) {
+      const int r = x / L, c = x % L;
+      const double v = (r < d.d0 && c < d.d1) ? V[r * d.d1 + c] : LPMP_NAN;
+      sh_tables[(2 * q) * (L * L) + x] = v;
+      sh_tables[(2 * q + 1) * (L * L) + c * L + r] = v;
+    }
+  }
+  __syncthreads();
+  constexpr int GPB = 256 / DenseCfg<L>::G;
+  const int64_t n_blocks = (count + GPB - 1) / GPB;
+  for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x)
+    dense_pk_body<L, 4, true, false, NT ? ACC_NT : ACC_PLAIN, false, false, true>(
+        packets, recs, ops, dual, cdata, lb, primal, count, stride, flags, b, nullptr, 0, nullptr, 0, nullptr, -1, sh_tables, sh_toff, n_sh);
 }
 
 // The chain executor's launch: workgroups take tickets until none is left (kernel classes of one BODY per launch).
@@ -2214,6 +2297,15 @@ factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual
         v = wave_min(v);
         best = fmin(best, d[a] + v);
       }
+    } else if (kind == LPMP_F_PAIRWISE_SHARED) {
+      const double scale = cdata[r.const_off];
+      const double* V = cdata + shared_table_off(cdata, r.const_off);
+      for (int a = 0; a < d0; ++a) {
+        double v = LPMP_INF;
+        for (int b = lane; b < d1; b += 64) v = fmin(v, scale * V[(int64_t)a * d1 + b] + d[d0 + b]);
+        v = wave_min(v);
+        best = fmin(best, d[a] + v);
+      }
     } else {
       const double diff = cdata[r.const_off];
       for (int a = 0; a < d0; ++a) {
@@ -2443,6 +2535,49 @@ bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, cons
 #undef PK_LAUNCH1
 }
 
+// shared classes: a persistent grid (what is resident at once, at most one workgroup per block of records); dynamic LDS = the
+// launch's table slots.  tabs = n_tabs indices into the pool described by desc (device array, engine.cpp).
+template <int L, bool NT>
+static void launch_shared_one(const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata, double* lb,
+                              int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const ShTabList& list, hipStream_t s) {
+  auto k = sweep_shared_pk_kernel<L, NT>;
+  const size_t lds = (size_t)2 * (list.n > 0 ? list.n : 1) * L * L * sizeof(double);
+  // compute units of the device and resident workgroups per CU by table count: asked once, cached per device ordinal (engines on
+  // several host threads share the caches: relaxed atomics, every thread would store the same value)
+  static std::atomic<int> n_cu_of[64];
+  static std::atomic<int> per_cu_of[64][SHARED_MAX_TABLES + 1];
+  int dev = 0; (void)hipGetDevice(&dev);
+  const int di = dev >= 0 && dev < 64 ? dev : 0, ti = list.n > 0 && list.n <= SHARED_MAX_TABLES ? list.n : 0;
+  int n_cu = n_cu_of[di].load(std::memory_order_relaxed);
+  if (n_cu == 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; n_cu = v; n_cu_of[di].store(v, std::memory_order_relaxed); }
+  int per_cu = per_cu_of[di][ti].load(std::memory_order_relaxed);
+  if (per_cu == 0) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, lds) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    per_cu_of[di][ti].store(per_cu, std::memory_order_relaxed);
+  }
+  constexpr int GPB = 256 / DenseCfg<L>::G;
+  const int64_t n_blocks = (count + GPB - 1) / GPB, cap = (int64_t)n_cu * per_cu;
+  hipLaunchKernelGGL(k, dim3((unsigned)(n_blocks < cap ? n_blocks : cap)), dim3(256), lds, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags, desc, list);
+}
+bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
+                         double* lb, int32_t* primal, int64_t count, int flags, const void* desc, const int32_t* tabs, int n_tabs, hipStream_t s) {
+  if (count <= 0) return true;
+  if (!kc_is_shared(kclass) || stride == 0 || n_tabs < 0 || n_tabs > SHARED_MAX_TABLES || !desc) return false;
+  ShTabList list; list.n = n_tabs;
+  for (int q = 0; q < SHARED_MAX_TABLES; ++q) list.t[q] = q < n_tabs ? tabs[q] : 0;
+  const ShTableDesc* d = static_cast<const ShTableDesc*>(desc);
+  const bool nt = (flags & SWEEP_NT) != 0;
+#define SH_LAUNCH(LL) do { if (nt) launch_shared_one<LL, true>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, d, list, s); \
+                           else launch_shared_one<LL, false>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, d, list, s); } while (0)
+  switch (kclass) {
+    case KC_SHARED_32: SH_LAUNCH(32); return true;
+    case KC_SHARED_16: SH_LAUNCH(16); return true;
+    case KC_SHARED_8: SH_LAUNCH(8); return true;
+    default: SH_LAUNCH(4); return true;
+  }
+#undef SH_LAUNCH
+}
+
 // chain executor: one persistent launch for a deep single-class schedule; grid = what is resident at once (more
 // workgroups would only queue behind the running ones).  Returns false for a class without a chain kernel.
 template <class K>
@@ -2572,6 +2707,19 @@ rows_copy_kernel(const RowRec* __restrict__ recs, int64_t n, const double* __res
   if (what == 2) { for (int x = lane; x < nm; x += 64) dual[r.dual_off + x] = row[nt + x]; }
   else { for (int x = lane; x < nm; x += 64) row[nt + x] = dual[r.dual_off + x]; }
 }
+// Device placement of the SHARED factors' constants (engine.cpp): cell k arrives as {packed const offset of the factor (int64),
+// table offset relative to the const base (int64)} and becomes {scale read from the packed constants, table offset}
+__global__ void __launch_bounds__(256)
+shared_cells_kernel(double* __restrict__ cells, int64_t n, const double* __restrict__ cdata) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int64_t coff = __double_as_longlong(cells[2 * k]);
+  cells[2 * k] = cdata[coff];
+}
+void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(shared_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cells, n, cdata);
+}
+
 void launch_rows_copy(const void* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, (const RowRec*)recs, n, cdata, dual, rows, what);

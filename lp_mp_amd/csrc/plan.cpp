@@ -133,9 +133,39 @@ void Plan::build(const lpmp_model& m) {
   f_dim0.assign(m.f_dim0, m.f_dim0 + nf);
   if (m.f_dim1) f_dim1.assign(m.f_dim1, m.f_dim1 + nf); else f_dim1.assign(nf, 0);
   f_coff.assign(nf + 1, 0); f_doff.assign(nf + 1, 0);
+  // the pool of shared pairwise tables
+  n_shared = m.n_shared_tables;
+  if (n_shared < 0) fail("negative shared table count");
+  sh_off.clear(); sh_dim0.clear(); sh_dim1.clear(); sh_data.clear(); f_table.clear();
+  if (n_shared > 0) {
+    if (!m.sh_off || !m.sh_dim0 || !m.sh_dim1 || !m.sh_data) fail("shared tables missing");
+    sh_off.assign(m.sh_off, m.sh_off + n_shared + 1);
+    sh_dim0.assign(m.sh_dim0, m.sh_dim0 + n_shared);
+    sh_dim1.assign(m.sh_dim1, m.sh_dim1 + n_shared);
+    if (sh_off[0] != 0) fail("shared tables: sh_off must start at 0");
+    for (int t = 0; t < n_shared; ++t)
+      if (sh_dim0[t] <= 0 || sh_dim1[t] <= 0 || sh_off[t + 1] - sh_off[t] != (int64_t)sh_dim0[t] * sh_dim1[t])
+        fail("shared table " + std::to_string(t) + ": bad dimensions / offsets");
+    sh_data.assign(m.sh_data, m.sh_data + sh_off[n_shared]);
+    // the shared classes pad their LDS tables with NaN and rely on fmin dropping it: a NaN entry of the caller's would vanish there
+    // and propagate on the generic kernels — refused here, where the pool is on the host
+    for (int t = 0; t < n_shared; ++t)
+      for (int64_t i = sh_off[t]; i < sh_off[t + 1]; ++i)
+        if (sh_data[(size_t)i] != sh_data[(size_t)i]) fail("shared table " + std::to_string(t) + ": NaN entry");
+  }
   max_dual = 1;
   for (int64_t f = 0; f < nf; ++f) {
-    if (f_kind[f] > LPMP_F_PAIRWISE_POTTS) fail("factor " + std::to_string(f) + ": unknown kind");
+    if (f_kind[f] > LPMP_F_PAIRWISE_SHARED) fail("factor " + std::to_string(f) + ": unknown kind");
+    if (f_kind[f] == LPMP_F_PAIRWISE_SHARED) {
+      if (f_table.empty()) f_table.assign(nf, -1);
+      if (!m.f_table) fail("factor " + std::to_string(f) + ": shared pairwise factor, but the model has no f_table");
+      const int32_t t = m.f_table[f];
+      if (t < 0 || t >= n_shared) fail("factor " + std::to_string(f) + ": shared table index " + std::to_string(t) + " out of range");
+      if (f_dim0[f] != sh_dim0[t] || f_dim1[f] != sh_dim1[t])
+        fail("factor " + std::to_string(f) + ": dims " + std::to_string(f_dim0[f]) + " x " + std::to_string(f_dim1[f]) + " do not match shared table " +
+             std::to_string(t) + " (" + std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]) + ")");
+      f_table[f] = t;
+    }
     if (f_type[f] < 0 || f_type[f] >= n_ftypes) fail("factor " + std::to_string(f) + ": type out of range");
     if (f_dim0[f] <= 0 || (f_kind[f] == LPMP_F_PAIRWISE_DENSE && f_dim1[f] <= 0)) fail("factor " + std::to_string(f) + ": bad dimension");
     if (f_kind[f] == LPMP_F_PAIRWISE_POTTS) f_dim1[f] = f_dim0[f];
@@ -419,10 +449,12 @@ struct Updates {
   std::vector<uint8_t> up_any;                 // streaming class: dense and Potts peers mixed
   std::vector<uint8_t> small_ok;               // lane-per-factor class: every size <= SMALL_MAXD
   std::vector<uint8_t> pw_right;               // updated dense pairwise factor, every op unary-pairwise with the factor on the right
+  std::vector<uint8_t> sh_all;                 // shared classes: every op unary-pairwise to a SHARED peer of dims <= 32, the factor on the left
   std::vector<int32_t> max_dim;                // largest peer table dim of the record
   std::vector<int64_t> rec_bytes;              // algorithmic bytes of the record
   std::vector<int32_t> kclass;                 // kernel class of the record
   std::vector<int32_t> rec_upd;                // [records]: the update each record stands for
+  std::vector<int32_t> sh_group;               // shared classes: the table-set group of the record inside its level and class (classify)
 };
 
 // a COMPUTE_PRIMAL factor is updated even without any active message (FactorUpdated, reference
@@ -575,10 +607,12 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
   U.up_any = std::vector<uint8_t>(N, 1);
   U.small_ok = std::vector<uint8_t>(N, 1);
   U.pw_right = std::vector<uint8_t>(N, 1);
+  U.sh_all = std::vector<uint8_t>(N, 1);
   U.max_dim = std::vector<int32_t>(N, 0);
   std::vector<uint8_t>& all_dense = U.all_dense; std::vector<uint8_t>& all_potts = U.all_potts;
   std::vector<uint8_t>& var_dense = U.var_dense; std::vector<uint8_t>& var_potts = U.var_potts;
   std::vector<uint8_t>& up_any = U.up_any; std::vector<uint8_t>& small_ok = U.small_ok; std::vector<uint8_t>& pw_right = U.pw_right;
+  std::vector<uint8_t>& sh_all = U.sh_all;
   std::vector<int32_t>& max_dim = U.max_dim;
   std::vector<int64_t> alg_bytes_of_thread(PLAN_MAX_THREADS, 0);
   // (several updates may share an owner record — folded sweeps — and land on different threads: the per-owner flags only
@@ -615,7 +649,10 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
         atomic_max(max_dim[o], std::max(p.f_dim0[peer], p.f_dim1[peer]));
         if (!(unary_left && (p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE || p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS) &&
               (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(up_any[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_SHARED && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
+              p.f_dim0[peer] <= 32 && p.f_dim1[peer] <= 32)) clear_flag(sh_all[o]);
       } else {
+        clear_flag(sh_all[o]);
         clear_flag(all_dense[o]); clear_flag(all_potts[o]); clear_flag(var_dense[o]); clear_flag(var_potts[o]); clear_flag(up_any[o]);
         if (mt.kind == LPMP_M_LABELING) {
           op.peer_const = p.tab_off[mt.param];
@@ -626,7 +663,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       op.info = mt.kind | (e.role << 4) | (side << 5) | (imp << 6) | ((p.f_flags[peer] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 << 7 : 0) | (p.f_kind[peer] << 8) |
                 ((mt.flags & LPMP_MF_IMPROVEMENT) ? OP_HAS_IMPROVEMENT : 0);
       if (std::max(op.len, std::max(op.pd0, op.pd1)) > SMALL_MAXD || p.f_doff[f + 1] - p.f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);
-      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[peer] == LPMP_F_VECTOR &&
+      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[f] != LPMP_F_PAIRWISE_SHARED && p.f_kind[peer] == LPMP_F_VECTOR &&
             p.f_dim1[f] > 0 && op.len == (side == 0 ? p.f_dim0[f] : p.f_dim1[f]))) clear_flag(pw_right[o]);
       return op;
     };
@@ -637,7 +674,8 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       const int code = op.info & 15, pk = (op.info >> 8) & 15;
       if (code == LPMP_M_UNARY_PAIRWISE) {
         const int64_t L = op.len;
-        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)op.pd0 * op.pd1 : (pk == LPMP_F_PAIRWISE_POTTS ? 8 : 0));
+        // (a SHARED peer: its scale; the table is on-chip)
+        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED) ? 8 : 0));
         return 16 * L;
       }
       return 16 * (int64_t)op.pd0;
@@ -654,10 +692,10 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
     }
     if (n_act > 0) bytes += 16 * (p.f_doff[f + 1] - p.f_doff[f]);
     // an updated dense pairwise factor reads its own table once to compute the min-marginals it sends
-    if (ks > 0 && p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+    if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED)) {   // (SHARED: its scale)
       bool sends_any = false;
       for (int64_t j = 0; j < ks; ++j) if (U.uom[u][j] != 0.0) { sends_any = true; break; }
-      if (sends_any) bytes += 8 * (int64_t)p.f_dim0[f] * p.f_dim1[f];
+      if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)p.f_dim0[f] * p.f_dim1[f] : 8;
     }
     __atomic_fetch_add(&U.rec_bytes[o], bytes, __ATOMIC_RELAXED);
     alg_local += bytes;
@@ -708,6 +746,14 @@ void classify(const Plan& p, Updates& U, const OpVec& ops) {
         return KC_PW_4 + (w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3);
       return KC_GENERIC;
     }
+    // unaries between SHARED pairwise factors only: the shared class of the padded width (more ops than its slab holds, or
+    // more than 32 labels: the generic kernels, which know the kind)
+    if (U.sh_all[u] && n_recv_of[u] + n_send_of[u] > 0) {
+      const int w = std::max(d0, max_dim[u]);
+      if (w <= 32 && n_recv_of[u] + n_send_of[u] <= pk_indirect_cap(w <= 4 ? 4 : w <= 8 ? 8 : w <= 16 ? 16 : 32))
+        return KC_SHARED_4 + (w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3);
+      return small_ok[u] ? KC_SMALL : KC_GENERIC;
+    }
     const bool pow = d0 == 4 || d0 == 8 || d0 == 16 || d0 == 32;
     // more ops than the LDS slab of a lane group holds (a hub of a random graph: C4 has a few 30-neighbour variables among
     // 2 M): such a RECORD goes to the op-by-op streaming kernel — left in its class it took its whole launch off the packed
@@ -726,10 +772,43 @@ void classify(const Plan& p, Updates& U, const OpVec& ops) {
   };
   U.kclass = std::vector<int32_t>(N, KC_GENERIC);
   for (int64_t u = 0; u < N; ++u) if (is_rec(p, U, u)) U.kclass[u] = cls_of(u);
+  // A launch of a shared class stages its distinct tables in LDS: at most SHARED_MAX_TABLES.  The shared records of one level
+  // and width are therefore split by TABLE SET into up to SHARED_MAX_GROUPS launches: taken in sequence order, a record joins
+  // the first group whose tables together with its own stay within the budget, or opens a group; beyond the last group it runs
+  // on the generic class (models with hundreds of tables mixed in every level).  bucket() makes one launch per group.
+  U.sh_group = std::vector<int32_t>();
+  if (p.n_shared > 0) {
+    U.sh_group.assign((size_t)N, 0);
+    struct TabSet { int n = 0; int32_t t[SHARED_MAX_TABLES]; };
+    std::vector<std::vector<TabSet>> sets;          // per (level, width slot), levels that hold a shared record only: its groups
+    std::vector<int64_t> set_of((size_t)(U.max_level + 1) * 4, -1);
+    for (int64_t u = 0; u < N; ++u) {
+      if (!is_rec(p, U, u) || !kc_is_shared(U.kclass[u])) continue;
+      int64_t& si = set_of[(size_t)(U.level[u] - 1) * 4 + (U.kclass[u] - KC_SHARED_4)];
+      if (si < 0) { si = (int64_t)sets.size(); sets.emplace_back(); }
+      std::vector<TabSet>& groups = sets[(size_t)si];
+      const Op* o = ops.data() + U.op_start[u];
+      int placed = -1;
+      for (size_t gi = 0; gi <= groups.size() && placed < 0; ++gi) {
+        if (gi == groups.size()) { if (gi == (size_t)SHARED_MAX_GROUPS) break; groups.emplace_back(); }
+        TabSet trial = groups[gi];
+        bool fits = true;
+        for (int k = 0; k < n_recv_of[u] && fits; ++k) {        // (only receives read a table)
+          const int32_t t = p.f_table[(size_t)o[k].peer];
+          bool have = false;
+          for (int q = 0; q < trial.n; ++q) have = have || trial.t[q] == t;
+          if (have) continue;
+          if (trial.n == SHARED_MAX_TABLES) fits = false; else trial.t[trial.n++] = t;
+        }
+        if (fits) { groups[gi] = trial; placed = (int)gi; }
+      }
+      if (placed >= 0) U.sh_group[(size_t)u] = placed; else U.kclass[u] = KC_GENERIC;
+    }
+  }
 }
 
 // bucket the owner records by (level, class) into out.recs and out.launches; updates without any active op are dropped
-void bucket(const Plan& p, Updates& U, Schedule& out) {
+void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
   const int64_t N = U.N;
   const int32_t max_level = U.max_level;
   const std::vector<int32_t>& level = U.level;
@@ -786,7 +865,42 @@ void bucket(const Plan& p, Updates& U, Schedule& out) {
     lr.level = key_level[k];
     lr.n_recv = key_recv[k]; lr.n_send = key_send[k]; lr.bytes = key_bytes[k];
     lr.max_dim = key_maxdim[k];
-    out.launches.push_back(lr);
+    if (!kc_is_shared(lr.kclass)) { out.launches.push_back(lr); continue; }
+    // a shared class: one launch per table-set group of the records (classify), each with the list of its distinct tables
+    const int64_t n_lr = lr.end - lr.begin;
+    bool one_group = true;
+    for (int64_t i = lr.begin; i < lr.end && one_group; ++i) one_group = U.sh_group[(size_t)U.rec_upd[(size_t)i]] == U.sh_group[(size_t)U.rec_upd[(size_t)lr.begin]];
+    if (!one_group) {                               // records group by group, sequence order inside a group
+      std::vector<int64_t> perm((size_t)n_lr);
+      std::iota(perm.begin(), perm.end(), lr.begin);
+      std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return U.sh_group[(size_t)U.rec_upd[(size_t)x]] < U.sh_group[(size_t)U.rec_upd[(size_t)y]]; });
+      std::vector<UpdRec> tr((size_t)n_lr); std::vector<int32_t> tu((size_t)n_lr);
+      for (int64_t i = 0; i < n_lr; ++i) { tr[(size_t)i] = out.recs[(size_t)perm[(size_t)i]]; tu[(size_t)i] = U.rec_upd[(size_t)perm[(size_t)i]]; }
+      std::copy(tr.begin(), tr.end(), out.recs.begin() + lr.begin);
+      std::copy(tu.begin(), tu.end(), U.rec_upd.begin() + lr.begin);
+    }
+    for (int64_t b0 = lr.begin; b0 < lr.end;) {
+      const int32_t grp = U.sh_group[(size_t)U.rec_upd[(size_t)b0]];
+      LevelRange sub = lr;
+      sub.begin = b0; sub.n_recv = sub.n_send = sub.bytes = 0; sub.n_sh = 0;
+      int64_t i = b0;
+      for (; i < lr.end && U.sh_group[(size_t)U.rec_upd[(size_t)i]] == grp; ++i) {
+        const UpdRec& r = out.recs[(size_t)i];
+        sub.n_recv += r.n_recv; sub.n_send += r.n_send; sub.bytes += U.rec_bytes[(size_t)U.rec_upd[(size_t)i]];
+        const Op* o = ops.data() + r.op_begin;
+        for (int q = 0; q < r.n_recv; ++q) {
+          const int32_t t = p.f_table[(size_t)o[q].peer];
+          bool have = false;
+          for (int j = 0; j < sub.n_sh; ++j) have = have || sub.sh_tab[j] == t;
+          if (have) continue;
+          if (sub.n_sh == SHARED_MAX_TABLES) fail("internal: a launch of a shared class references more tables than its LDS budget holds");
+          sub.sh_tab[sub.n_sh++] = t;
+        }
+      }
+      sub.end = i;
+      out.launches.push_back(sub);
+      b0 = i;
+    }
   }
 }
 
@@ -835,7 +949,7 @@ void memory_order(Schedule& out, std::vector<int32_t>& rec_upd) {
 void work_sort(Schedule& out, std::vector<int32_t>& rec_upd) {
   constexpr int64_t SORT_WINDOW = 1024;
   for (const auto& lr : out.launches)
-    if (lr.kclass != KC_GENERIC && lr.kclass != KC_DENSE_32 && lr.kclass != KC_DENSE_V32 && lr.kclass != KC_DENSE_BIG && lr.kclass != KC_PW_32) {   // incl. KC_SMALL
+    if (lr.kclass != KC_GENERIC && lr.kclass != KC_DENSE_32 && lr.kclass != KC_DENSE_V32 && lr.kclass != KC_DENSE_BIG && lr.kclass != KC_PW_32 && lr.kclass != KC_SHARED_32) {   // incl. KC_SMALL
       std::vector<int64_t> perm(lr.end - lr.begin);
       std::iota(perm.begin(), perm.end(), lr.begin);
       // (a launch with many different amounts of work per record — a random graph, degrees 2 ... 25 — has no locality
@@ -887,7 +1001,7 @@ int64_t packet_flags(Schedule& out) {
       }
       continue;
     }
-    if (!kc_is_packed(lr.kclass)) continue;
+    if (!kc_is_packed(lr.kclass) && !kc_is_shared(lr.kclass)) continue;   // (shared classes: packets / indirect records as the packed classes)
     if (kc_is_var(lr.kclass)) {
       // the padded classes only exist in packed / indirect form: a launch with a record of more ops than the slab holds goes to
       // the streaming kernel, which works op by op.  (Records with duplicate vectors are not among them: cls_of already gave
@@ -980,7 +1094,7 @@ void Plan::make_schedule(const std::vector<Segment>& segs, bool fuse, Schedule& 
   lap_("ops");
   classify(*this, U, ops);
   lap_("dup");
-  bucket(*this, U, out);
+  bucket(*this, U, ops, out);
   memory_order(out, U.rec_upd);
   lap_("records");
   out.ops = std::move(ops);

@@ -85,15 +85,26 @@ enum KClass : int32_t {
   // UPDATED dense pairwise factors (`right` / `full` schedules: the factor pulls its unaries in and sends both
   // min-marginals back), dims <= the padded width, at most PW_MAX_OPS ops: packet form, one read of the table
   KC_PW_4, KC_PW_8, KC_PW_16, KC_PW_32,
+  // unaries whose active messages all go to SHARED pairwise factors (LPMP_F_PAIRWISE_SHARED): run-time label counts and
+  // rectangular tables up to the padded width; the launch's distinct tables are staged in LDS once per workgroup
+  KC_SHARED_4, KC_SHARED_8, KC_SHARED_16, KC_SHARED_32,
   KC_COUNT
 };
 constexpr int BIG_MAX_LABELS = 512;
 constexpr int SMALL_MAXD = 8;
 constexpr int PW_MAX_OPS = 6;
 constexpr bool kc_is_pw(int kclass) { return kclass >= KC_PW_4 && kclass <= KC_PW_32; }
+constexpr bool kc_is_shared(int kclass) { return kclass >= KC_SHARED_4 && kclass <= KC_SHARED_32; }
+// tables one launch of a shared class may reference (the kernel's LDS budget: per table two slots of width x width doubles —
+// the table and its transpose —, 64 KiB at 32 labels beside 8 KiB of slabs: two workgroups per CU in the worst case); a record
+// that would take its launch beyond it goes to another launch of the class (plan.cpp, classify: split by table set)
+constexpr int SHARED_MAX_TABLES = 4;
+// launches the shared records of one level and width may be split into by table set; what no group takes runs on the generic class
+constexpr int SHARED_MAX_GROUPS = 32;
 // lanes-per-vector width of a packed fast class (0: generic / streaming class)
 constexpr int kc_width(int kclass) {
   if (kclass >= KC_PW_4 && kclass <= KC_PW_32) return 4 << (kclass - KC_PW_4);
+  if (kclass >= KC_SHARED_4 && kclass <= KC_SHARED_32) return 4 << (kclass - KC_SHARED_4);
   return (kclass == KC_GENERIC || kclass >= KC_DENSE_BIG) ? 0 : 4 << ((kclass - 1) % 4);
 }
 constexpr bool kc_is_dense(int kclass) { return (kclass >= KC_DENSE_4 && kclass <= KC_DENSE_32) || (kclass >= KC_DENSE_V4 && kclass <= KC_DENSE_V32); }
@@ -110,6 +121,8 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   // dependent rec -> ops hop.  stride < 0: indirect mode (below).  stride 0: an op-by-op class (generic, streaming, lane per factor).
   int32_t stride = 0; int64_t pk_begin = 0;
   int32_t max_dim = 0;                          // largest label count of any vector or table side the launch's records touch
+  // shared classes: the distinct shared tables (indices into the model's pool) the launch's records reference
+  int32_t n_sh = 0; int32_t sh_tab[SHARED_MAX_TABLES] = {};
 };
 constexpr int PK_MAX_OPS = 8;                 // packets hold at most this many ops per factor
 // launches whose factors have more ops than that (but at most this many: the LDS slab of a lane group) run the
@@ -121,7 +134,7 @@ constexpr int pk_indirect_cap(int labels) { return labels >= 16 ? 32 : labels >=
 // kernel (as launches of their own on the streaming kernel they cost C4 1.5 of 13.4 ms per pass, profiles/r03_c4b_*).
 // The Potts kernels (more waves per SIMD) keep the smaller slab.
 constexpr int pk_dense_cap(int labels) { return labels == 16 ? 64 : pk_indirect_cap(labels); }
-constexpr int pk_class_cap(int kclass) { return kc_is_dense(kclass) ? pk_dense_cap(kc_width(kclass)) : pk_indirect_cap(kc_width(kclass)); }
+constexpr int pk_class_cap(int kclass) { return kc_is_dense(kclass) ? pk_dense_cap(kc_width(kclass)) : pk_indirect_cap(kc_width(kclass)); }   // (shared classes: the smaller slab)
 constexpr int32_t UPD_PRELOAD_OK = 1 << 16;   // UpdRec::kind_flags: no send targets a vector a receive writes
 constexpr int32_t UPD_PRIMAL = 1 << 17;       // UpdRec::kind_flags: the factor type has COMPUTE_PRIMAL_SOLUTION
 
@@ -172,7 +185,7 @@ constexpr int kc_block_records(int kclass) {
   if (kclass == KC_SMALL) return SMALL_BLOCK_RECORDS;
   const int w = kc_width(kclass);
   if (w == 0) return 0;
-  return kc_is_dense(kclass) ? (w == 32 ? 4 : 256 / w) : 256 / w;   // dense: G = 64 lanes at 32 labels, else one lane per label
+  return (kc_is_dense(kclass) || kc_is_shared(kclass)) ? (w == 32 ? 4 : 256 / w) : 256 / w;   // dense / shared: G = 64 lanes at 32 labels, else one lane per label
 }
 constexpr bool kc_chain_capable(int kclass) { return kc_is_packed(kclass) || kclass == KC_GENERIC || kclass == KC_SMALL; }
 constexpr int64_t CHAIN_MIN_LAUNCHES = 9;   // shorter schedules run as plain launches
@@ -234,6 +247,11 @@ struct Plan {
   std::vector<int32_t> f_type, f_dim0, f_dim1;
   std::vector<uint8_t> f_kind, f_flags;
   std::vector<int64_t> f_coff, f_doff;   // [nf+1]
+  // shared pairwise tables (LPMP_F_PAIRWISE_SHARED): the pool, copied (a handful of small tables), and every factor's table
+  // (-1: not a SHARED factor)
+  int32_t n_shared = 0;
+  std::vector<int64_t> sh_off; std::vector<int32_t> sh_dim0, sh_dim1; std::vector<double> sh_data;
+  std::vector<int32_t> f_table;
   std::vector<int32_t> m_type, m_left, m_right;
   double constant = 0;
   // derived

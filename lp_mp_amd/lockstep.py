@@ -193,6 +193,8 @@ def lockstep_mrf(n_vars: int, L: int, edge_i, edge_j, part, world: int, mode: in
     """Lock-step parts of the MRF synthetic.mrf_model(n_vars, L, edge_i, edge_j, ...) for the partition ``part[v]``.
     Returns (schedule, parts); ``only``: just that rank's part.  Costs as in multi_gpu.partition_mrf (host arrays, or
     ``stream_seed``: generated in HBM from the counter stream, fill descriptors in the part)."""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     from . import engine as E
     edge_i = np.asarray(edge_i, np.int64); edge_j = np.asarray(edge_j, np.int64); part = np.asarray(part, np.int64)
     n_edges = edge_i.shape[0]
@@ -297,6 +299,7 @@ def lockstep_model(gm: M.FlatModel, part, world: int, mode: int, only: Optional[
     A part holds its variables, every higher factor touching one of them with ALL its messages, and never-updated ghosts of the
     remote variables behind those; factors and messages keep the global relative order (message lists of a local variable are
     the global ones).  A higher factor counts in the bound where its lowest-numbered variable lives."""
+    M.refuse_shared(gm, "the multi-GPU hosts")
     from . import engine as E
     part = np.asarray(part, np.int64)
     nf, nm = gm.n_factors, gm.n_messages
@@ -641,6 +644,8 @@ def strips_lockstep_part(H: int, W: int, L: int, pairwise: str, order: str, rank
     with a neighbour on both sides looks the same in any world — the part and the schedule come from a 3-strip PROXY
     (first, interior, last strip) and only the positions in the cost stream and the peer ranks are shifted
     (tests/test_lockstep.py compares with the parts of the true global structure)."""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     from . import multi_gpu as MG
     n_loc, e_int = MG.strip_sizes(H, W)
     # (only where the level structure is the same in every strip: 2-colour orders.  A row-major order chains its levels

@@ -74,6 +74,28 @@ class pairwise_potts_factor:
         self.dim, self.diff = int(dim), float(diff_cost)
 
 
+class shared_pairwise_factor:
+    """scale * V[x1][x2] with V a table of the LP's pool (LP.add_shared_table): the engine's F_PAIRWISE_SHARED kind — one double
+    per factor, the table read from on-chip memory by the sweep.  Usable in a FactorContainer wherever PairwiseSimplexFactor is
+    (the same UnaryPairwiseMessage ops): ``lp.add_factor(P, table_id, scale)``."""
+    kind = M.F_PAIRWISE_SHARED
+
+    def __init__(self, table_id: int, scale: float = 1.0):
+        self.table_id, self.scale = int(table_id), float(scale)
+        self.table = None                   # bound by LP.add_factor
+
+    @property
+    def dim1(self) -> int:
+        return int(self.table.shape[0])
+
+    @property
+    def dim2(self) -> int:
+        return int(self.table.shape[1])
+
+    def cost(self, x1, x2):
+        return np.float64(self.scale) * self.table[x1, x2]
+
+
 def labeling_factor(labelings: Sequence[Sequence[int]], implicit_origin: bool):
     """labeling_factor<labelings<...>, IMPLICIT_ORIGIN> (reference include/factors/labeling_list_factor.hxx:220)."""
     labs = [tuple(l) for l in labelings]
@@ -183,6 +205,7 @@ class LP:
         self._partition_graph = []
         self._inner = int(innerIteration)
         self._tables = {}
+        self._shared_tables: List[np.ndarray] = []
         self._constant = 0.0
         self._repam = LPReparametrizationMode.Undefined
         self._engine: Optional[Engine] = None
@@ -191,8 +214,21 @@ class LP:
         self._duals_host: Optional[np.ndarray] = None
 
     # -- problem construction (reference LP_MP.h:239-285, :698-702) ---------------------------------------
+    def add_shared_table(self, table) -> int:
+        """a pairwise table [d0, d1] for shared_pairwise_factor ops; returns its id"""
+        table = np.array(table, np.float64)
+        if table.ndim != 2:
+            raise RuntimeError("add_shared_table: a [d0, d1] table is expected")
+        self._shared_tables.append(table)
+        self._dirty = True
+        return len(self._shared_tables) - 1
+
     def add_factor(self, container: FactorContainer, *args) -> int:
         op = args[0] if len(args) == 1 and isinstance(args[0], container.factor_type) else container.factor_type(*args)
+        if getattr(op, "kind", None) == M.F_PAIRWISE_SHARED:
+            if not 0 <= op.table_id < len(self._shared_tables):
+                raise RuntimeError("shared_pairwise_factor: table id out of range (LP.add_shared_table first)")
+            op.table = self._shared_tables[op.table_id]
         self._pull_duals()
         self._factors.append((container, op))
         self._dirty = True
@@ -280,8 +316,12 @@ class LP:
         b = M.ModelBuilder(len(fmc.FactorList), mtypes, [int(f.compute_primal) for f in fmc.FactorList])
         for key, _ in sorted(self._tables.items(), key=lambda kv: kv[1]):
             b.add_labeling_table(*key)
+        for t in self._shared_tables:
+            b.add_shared_table(t)
         for c, op in self._factors:
-            if op.kind == M.F_VECTOR:
+            if op.kind == M.F_PAIRWISE_SHARED:
+                b.add_shared_pairwise(c.factor_no, [op.table_id], [op.scale])
+            elif op.kind == M.F_VECTOR:
                 b.add_vector_factors(c.factor_no, op.cost[None, :], implicit_origin=op.implicit_origin)
             elif op.kind == M.F_PAIRWISE_DENSE:
                 b.add_dense_pairwise(c.factor_no, op.table[None])

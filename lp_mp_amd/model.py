@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 # enum lpmp_factor_kind
-F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS = 0, 1, 2
+F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS, F_PAIRWISE_SHARED = 0, 1, 2, 3
 FF_IMPLICIT_ORIGIN = 1
 # enum lpmp_msg_kind
 M_UNARY_PAIRWISE, M_LABELING, M_MINNORM = 0, 1, 2
@@ -51,6 +51,8 @@ class c_model(C.Structure):
         ("n_rel_fwd", C.c_int64), ("rel_fwd", C.c_void_p), ("n_rel_bwd", C.c_int64), ("rel_bwd", C.c_void_p),
         ("constant", C.c_double),
         ("n_part_pairs", C.c_int64), ("part_pairs", C.c_void_p),
+        ("n_shared_tables", C.c_int32), ("sh_off", C.c_void_p), ("sh_dim0", C.c_void_p), ("sh_dim1", C.c_void_p),
+        ("sh_data", C.c_void_p), ("f_table", C.c_void_p),
     ]
 
 
@@ -93,6 +95,13 @@ class FlatModel:
     rel_bwd: np.ndarray
     constant: float = 0.0
     part_pairs: Optional[np.ndarray] = None   # [n,2] int32: put_in_same_partition(f1, f2) calls in call order
+    # shared pairwise tables (F_PAIRWISE_SHARED: cost = scale * V[a][b], the factor's one const double is the scale):
+    # table t is sh_dim0[t] x sh_dim1[t], row-major at sh_data[sh_off[t]]; f_table[f] = table of factor f (-1: none)
+    sh_off: Optional[np.ndarray] = None       # [n_tables + 1] int64
+    sh_dim0: Optional[np.ndarray] = None      # [n_tables] int32
+    sh_dim1: Optional[np.ndarray] = None
+    sh_data: Optional[np.ndarray] = None      # float64, host memory always
+    f_table: Optional[np.ndarray] = None      # [n_factors] int32, None when no factor is SHARED
     _keep: list = field(default_factory=list, repr=False)
 
     def __getstate__(self):          # the ctypes views of c_struct() are per process and rebuilt on demand
@@ -111,18 +120,65 @@ class FlatModel:
     def const_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 1, 0))
+        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where((self.f_kind == F_PAIRWISE_POTTS) | (self.f_kind == F_PAIRWISE_SHARED), 1, 0))
 
     def dual_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
+        return np.where((self.f_kind == F_PAIRWISE_DENSE) | (self.f_kind == F_PAIRWISE_SHARED), d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
 
     def dual_offsets(self) -> np.ndarray:
         return np.concatenate([[0], np.cumsum(self.dual_sizes())]).astype(np.int64)
 
     def const_offsets(self) -> np.ndarray:
         return np.concatenate([[0], np.cumsum(self.const_sizes())]).astype(np.int64)
+
+    @property
+    def n_shared_tables(self) -> int:
+        return 0 if self.sh_dim0 is None else int(self.sh_dim0.shape[0])
+
+    @property
+    def has_shared(self) -> bool:
+        return bool(np.any(self.f_kind == F_PAIRWISE_SHARED))
+
+    def shared_table(self, t: int) -> np.ndarray:
+        """table t of the pool as a [d0, d1] view"""
+        d0, d1 = int(self.sh_dim0[t]), int(self.sh_dim1[t])
+        return self.sh_data[int(self.sh_off[t]): int(self.sh_off[t]) + d0 * d1].reshape(d0, d1)
+
+    def expand_shared(self) -> "FlatModel":
+        """the same model with every SHARED factor replaced by a DENSE factor whose table is ``np.float64(scale) * V`` —
+        same factor order, messages, relations and duals (the dual layouts of the two kinds are equal), no pool.  Plain numpy;
+        a model without SHARED factors is returned with its arrays shared."""
+        import dataclasses
+        if not self.has_shared:
+            return dataclasses.replace(self, sh_off=None, sh_dim0=None, sh_dim1=None, sh_data=None, f_table=None, _keep=[])
+        if self.const_data is None:
+            raise ValueError("expand_shared: the model has no host constants")
+        old_off = self.const_offsets()
+        kind = self.f_kind.copy()
+        shared = np.nonzero(kind == F_PAIRWISE_SHARED)[0]
+        kind[shared] = F_PAIRWISE_DENSE
+        new = dataclasses.replace(self, f_kind=kind, sh_off=None, sh_dim0=None, sh_dim1=None, sh_data=None, f_table=None, _keep=[])
+        new_off = new.const_offsets()
+        const = np.empty(int(new_off[-1]), np.float64)
+        is_shared = self.f_kind == F_PAIRWISE_SHARED
+        # runs of factors that are not SHARED keep their constants as they are
+        f = 0
+        nf = self.n_factors
+        while f < nf:
+            g = f
+            if is_shared[f]:
+                V = self.shared_table(int(self.f_table[f]))
+                const[new_off[f]: new_off[f + 1]] = (np.float64(self.const_data[old_off[f]]) * V).reshape(-1)
+                f += 1
+            else:
+                while g < nf and not is_shared[g]:
+                    g += 1
+                const[new_off[f]: new_off[g]] = self.const_data[old_off[f]: old_off[g]]
+                f = g
+        new.const_data = const
+        return new
 
     def with_factor_order(self, rank: np.ndarray) -> "FlatModel":
         """the same factors, messages and costs with the factor relations REPLACED by a chain through all factors in the order
@@ -142,6 +198,8 @@ class FlatModel:
         (lp_mp_amd/include/lpmp_lockstep.hxx, model_file; tools/mgpu_rccl_driver.cpp --model-file)"""
         if self.dual_data is None:
             raise ValueError("dump: the model has no host duals")
+        if self.has_shared:
+            raise ValueError("dump: the model file format has no shared pairwise tables (expand_shared() gives a model it can hold)")
         const = np.zeros(0) if self.const_data is None else np.ascontiguousarray(self.const_data, np.float64)
         mt = np.array([[t.left_ftype, t.right_ftype, t.schedule, t.n_left, t.n_right, t.kind, t.param, t.flags] for t in self.mtypes], np.int32).reshape(-1, 8)
         head = np.array([0x4C504D504D4F444C, self.n_ftypes, len(self.mtypes), self.tab_nleft.shape[0], self.tab_data.shape[0], self.n_factors,
@@ -181,7 +239,26 @@ class FlatModel:
             m.n_part_pairs, m.part_pairs = int(self.part_pairs.shape[0]), _ptr(self.part_pairs)
         else:
             m.n_part_pairs, m.part_pairs = 0, None
+        if self.n_shared_tables:
+            self.sh_off = np.ascontiguousarray(self.sh_off, np.int64)
+            self.sh_dim0 = np.ascontiguousarray(self.sh_dim0, np.int32)
+            self.sh_dim1 = np.ascontiguousarray(self.sh_dim1, np.int32)
+            self.sh_data = np.ascontiguousarray(self.sh_data, np.float64)
+            m.n_shared_tables = self.n_shared_tables
+            m.sh_off, m.sh_dim0, m.sh_dim1, m.sh_data = _ptr(self.sh_off), _ptr(self.sh_dim0), _ptr(self.sh_dim1), _ptr(self.sh_data)
+        else:
+            m.n_shared_tables, m.sh_off, m.sh_dim0, m.sh_dim1, m.sh_data = 0, None, None, None, None
+        if self.f_table is not None:
+            self.f_table = np.ascontiguousarray(self.f_table, np.int32)
+        m.f_table = _ptr(self.f_table)
         return m
+
+
+def refuse_shared(model: "FlatModel", who: str):
+    """hosts that do not know the F_PAIRWISE_SHARED kind say so instead of misreading the model"""
+    if model.has_shared:
+        raise ValueError(who + " do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED): expand_shared() gives the "
+                         "same model with one private dense table per factor")
 
 
 class ModelBuilder:
@@ -194,6 +271,8 @@ class ModelBuilder:
             else np.asarray(ftype_computes_primal, np.uint8)
         self._tables: List[np.ndarray] = []
         self._tab_nleft: List[int] = []
+        self._shared: List[np.ndarray] = []     # shared pairwise tables, [d0, d1] each
+        self._f_table = []                       # (first factor id, table ids) of every add_shared_pairwise call
         self._f = []      # (type, kind, flags, dim0, dim1) array chunks
         self._const = []
         self._dual = []
@@ -260,6 +339,35 @@ class ModelBuilder:
         n = diffs.shape[0]
         return self._add_factors(n, ftype, F_PAIRWISE_POTTS, 0, n_labels, n_labels, diffs, None if self.skip_dual else np.zeros((n, 2 * n_labels)))
 
+    def add_shared_table(self, table) -> int:
+        """a pairwise table V [d0, d1] that any number of factors may use (add_shared_pairwise); returns its id"""
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError("add_shared_table: a [d0, d1] table is expected")
+        self._shared.append(table.copy())
+        return len(self._shared) - 1
+
+    def add_shared_pairwise(self, ftype: int, table_ids, scales) -> np.ndarray:
+        """pairwise factors cost(a, b) = scales[i] * V[table_ids[i]][a][b]: every factor holds one double.  All tables of one
+        call must have the same dims (factors of other dims: another call).  ``scales`` is finite, and positive where the
+        table holds +inf entries."""
+        table_ids = np.atleast_1d(np.asarray(table_ids, np.int32))
+        scales = np.atleast_1d(np.asarray(scales, np.float64))
+        if scales.shape[0] == 1 and table_ids.shape[0] > 1:
+            scales = np.full(table_ids.shape[0], scales[0])
+        if table_ids.shape != scales.shape or table_ids.shape[0] == 0:
+            raise ValueError("add_shared_pairwise: one table id and one scale per factor")
+        if table_ids.min() < 0 or table_ids.max() >= len(self._shared):
+            raise ValueError("add_shared_pairwise: table id out of range")
+        dims = {self._shared[t].shape for t in np.unique(table_ids)}
+        if len(dims) != 1:
+            raise ValueError("add_shared_pairwise: the tables of one call must have the same dims")
+        d0, d1 = dims.pop()
+        n = table_ids.shape[0]
+        ids = self._add_factors(n, ftype, F_PAIRWISE_SHARED, 0, d0, d1, scales, None if self.skip_dual else np.zeros((n, d0 + d1)))
+        self._f_table.append((int(ids[0]), table_ids.copy()))
+        return ids
+
     # -- messages / relations ------------------------------------------------------------------------
     def add_messages(self, mtype: int, left, right) -> np.ndarray:
         left = np.atleast_1d(np.asarray(left, np.int32))
@@ -307,7 +415,19 @@ class ModelBuilder:
                 return np.ascontiguousarray(chunks[0])
             return np.ascontiguousarray(np.concatenate(chunks)) if chunks else np.zeros(shape, dtype)
         tab_off = np.concatenate([[0], np.cumsum([len(t) for t in self._tables])]).astype(np.int64)
+        shared = {}
+        if self._shared:
+            shared = dict(sh_off=np.concatenate([[0], np.cumsum([t.size for t in self._shared])]).astype(np.int64),
+                          sh_dim0=np.asarray([t.shape[0] for t in self._shared], np.int32),
+                          sh_dim1=np.asarray([t.shape[1] for t in self._shared], np.int32),
+                          sh_data=np.ascontiguousarray(np.concatenate([t.reshape(-1) for t in self._shared])))
+        if self._f_table:
+            f_table = np.full(self._nf, -1, np.int32)
+            for first, t in self._f_table:
+                f_table[first: first + t.shape[0]] = t
+            shared["f_table"] = f_table
         return FlatModel(
+            **shared,
             n_ftypes=self.n_ftypes, ftype_computes_primal=self.ftype_computes_primal, mtypes=self.mtypes,
             tab_off=tab_off, tab_data=cat(self._tables, np.int32), tab_nleft=np.asarray(self._tab_nleft, np.int32),
             f_type=cat([c[0] for c in self._f], np.int32), f_kind=cat([c[1] for c in self._f], np.uint8),

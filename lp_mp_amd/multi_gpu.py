@@ -180,6 +180,7 @@ def partition_model(gm: M.FlatModel, part: np.ndarray, world: int) -> List[Local
     variable on the owner's side.  Local factor order: variables, ghosts, higher factors; messages keep the global
     insertion order; a relation survives when both ends are local (a remote variable is represented by its ghost in
     relations with the ghost's own higher factor)."""
+    M.refuse_shared(gm, "the multi-GPU hosts")
     from . import engine as E
     part = np.asarray(part, np.int64)
     nf, nm = gm.n_factors, gm.n_messages
@@ -494,6 +495,7 @@ def graph_partition_model(gm: M.FlatModel, world: int, method: str = "auto", ret
     """``part`` for partition_model: the variables of a factor graph (left factors of its messages) split by
     graph_partition on the graph that links the variables of every higher factor in a chain; entries of higher
     factors are unused (0).  ``method`` / ``return_method`` as graph_partition."""
+    M.refuse_shared(gm, "the multi-GPU hosts")
     ml, mr = gm.m_left.astype(np.int64), gm.m_right.astype(np.int64)
     order = np.lexsort((ml, mr))                              # messages grouped by higher factor
     a, b, same = ml[order][:-1], ml[order][1:], mr[order][:-1] == mr[order][1:]
@@ -531,6 +533,8 @@ def strip_global_edges(H: int, W: int, world: int, order: str):
 
 def strip_costs(H, W, L, world, pairwise, seed):
     """Host arrays of the global cost streams (tests only; sizes grow with world)."""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     n_loc, e_int = strip_sizes(H, W)
     n_vars = world * n_loc
     n_edges = world * e_int + (world - 1) * W
@@ -544,6 +548,8 @@ def strip_local_part(H: int, W: int, L: int, pairwise: str, order: str, rank: in
                      device_const: bool = False) -> LocalPart:
     """The same LocalPart that partition_mrf gives for the strip partition of the global grid, built
     from closed-form index arithmetic on this rank's strip only."""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     n_loc, e_int = strip_sizes(H, W)
     n_vars = world * n_loc
     var = S.grid_variable_order(H, W, order).reshape(-1)

@@ -93,6 +93,8 @@ def strip_window_part(H: int, W: int, L: int, pairwise: str, rank: int, world: i
     """rank's window of the (world * H) x W grid of synthetic.grid_model(world * H, W, L, pairwise, "colour_major", seed).
     ``costs``: host arrays of the GLOBAL model (tests: {"unaries": [n, L], "tables": [E, L, L] or "potts": [E]}); else the
     costs are generated in HBM from the counter stream (fill descriptors, multi_gpu.fill_device_costs)."""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     if g % 2 or g < 4:
         raise ValueError("overlap: the ghost depth must be even (the window keeps the global colouring) and at least 4 (one pass between exchanges needs 4 rows)")
     if H % 2:
@@ -268,6 +270,8 @@ def run_overlapped(sweeps: List[OverlapSweep], n_passes: int):
 def grid_pass_counts(GH: int, W: int, L: int, pairwise: str = "dense") -> Tuple[int, int]:
     """message updates and algorithmic bytes of one anisotropic pass over the GH x W grid: every message is
     received once and sent once"""
+    if pairwise == "shared":
+        raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
     E = GH * (W - 1) + (GH - 1) * W
     n = GH * W
     per_msg = (8 * L * L if pairwise == "dense" else 8) + 40 * L

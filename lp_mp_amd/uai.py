@@ -35,19 +35,22 @@ def parse_uai(text: str) -> Tuple[List[int], List[Tuple[Tuple[int, ...], np.ndar
     return card, tables
 
 
-def FMC_SRMP():
+def FMC_SRMP(share_tables: bool = False):
     U = LPM.FactorContainer(LPM.UnarySimplexFactor, 0, True)     # COMPUTE_PRIMAL_SOLUTION on the unaries: rounding
-    P = LPM.FactorContainer(LPM.PairwiseSimplexFactor, 1)
+    P = LPM.FactorContainer(LPM.shared_pairwise_factor if share_tables else LPM.PairwiseSimplexFactor, 1)
     ML = LPM.MessageContainer(LPM.UnaryPairwiseMessage(0), 0, 1, M.SCHED_LEFT, M.variableMessageNumber, 1, 0)
     MR = LPM.MessageContainer(LPM.UnaryPairwiseMessage(1), 0, 1, M.SCHED_LEFT, M.variableMessageNumber, 1, 1)
     return LPM.FMC("FMC_SRMP", [U, P], [ML, MR]), U, P, ML, MR
 
 
-def build_lp_from_uai(text: str, device: int = 0, order: str = "index") -> LPM.LP:
+def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_tables: bool = False) -> LPM.LP:
     """``order``: "index" — relations u_i -> p_ij -> u_j for i < j in the file's variable numbering, what LP_MP-MRF's
     constructor does (a row-major grid then has H+W-1 dependent steps per sweep); "colour_major" — the same relations
     along a colour-major ranking of the variables (ordering.colour_major_order: 2 steps per sweep on a bipartite
-    graph).  Both are valid block-coordinate-ascent orders; they give different dual trajectories."""
+    graph).  Both are valid block-coordinate-ascent orders; they give different dual trajectories.
+    ``share_tables``: pairwise functions whose tables (oriented along the relation) are bytewise equal and of the same shape
+    become ONE shared table with scale 1.0 (shared_pairwise_factor) instead of a private dense table each — same costs,
+    same duals."""
     card, tables = parse_uai(text)
     if order not in ("index", "colour_major"):
         raise ValueError(order)
@@ -57,8 +60,9 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index") -> LPM.L
         pairs = np.array([sc for sc, _ in tables if len(sc) == 2], np.int64).reshape(-1, 2)
         if pairs.shape[0]:
             rank = colour_major_order(len(card), pairs[:, 0], pairs[:, 1])
-    fmc, U, P, ML, MR = FMC_SRMP()
+    fmc, U, P, ML, MR = FMC_SRMP(share_tables)
     lp = LPM.LP(fmc, device)
+    pool = {}
     unary = [np.zeros(c) for c in card]
     for sc, t in tables:
         if len(sc) == 1:
@@ -72,7 +76,14 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index") -> LPM.L
         i, j = sc
         if rank[i] > rank[j]:
             i, j, t = j, i, t.T
-        p = lp.add_factor(P, card[i], card[j], np.ascontiguousarray(t))
+        t = np.ascontiguousarray(t, np.float64)
+        if share_tables:
+            key = (t.shape, t.tobytes())
+            if key not in pool:
+                pool[key] = lp.add_shared_table(t)
+            p = lp.add_factor(P, pool[key], 1.0)
+        else:
+            p = lp.add_factor(P, card[i], card[j], t)
         lp.add_message(ML, u[i], p)
         lp.add_message(MR, u[j], p)
         lp.AddFactorRelation(u[i], p)
@@ -80,11 +91,11 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index") -> LPM.L
     return lp
 
 
-def solve_uai(text: str, device: int = 0, **visitor_options):
+def solve_uai(text: str, device: int = 0, share_tables: bool = False, **visitor_options):
     """MAP estimation for a model in UAI format with the message-passing rounding solver — the reference's
     ``MpRoundingSolver<Solver<LP<FMC_SRMP>, StandardVisitor>>`` + ``UaiMrfInput::ParseString`` (test/graphical_model.cpp:
     47-56).  Returns (lower bound, primal cost, labeling of the variables)."""
-    lp = build_lp_from_uai(text, device)
+    lp = build_lp_from_uai(text, device, share_tables=share_tables)
     s = LPM.MpRoundingSolver(lp, LPM.StandardVisitor(**visitor_options))
     s.Solve()
     n = len(parse_uai(text)[0])
