@@ -417,6 +417,9 @@ void Plan::ensure_weights(int mode) {
 // commute exactly when they touch disjoint factors, so update u gets
 //   level(u) = 1 + max(level of the latest earlier update that touched u or one of the factors u touches)
 // and all updates of one level run concurrently with a result identical to the sequential sweep.
+// (tests/test_schedule_hazards_host.py states the claim: test_footprints_are_sufficient_for_the_oracle pins what an update
+// reads and writes against the oracle, test_every_planned_schedule_is_hazard_free demands that every conflicting pair of
+// every planned schedule is ordered by what the executor enforces.)
 //
 // Several sweeps can be scheduled as ONE sequence (forward then backward of a pass).  With `fuse`, an
 // update u2 that directly follows an update u1 of the SAME factor — nothing else touched anything u2

@@ -3,7 +3,8 @@
 # on this pool): the library built from the same sources with the sanitizer on the host compile (kernels unchanged), selected with
 # LPMP_ENGINE_SO, the runtime preloaded into python.  ASan + UBSan over the host-logic test files (incl. the gloo worker processes),
 # TSan with 8 planning threads over the same files without the torch.distributed workers (torch's own ProcessGroupGloo reports races
-# on its condition variables under TSan), plus the C4-shaped graph through the C++ colouring / partition refinement / planner.
+# on its condition variables under TSan), plus the C4-shaped graph through the C++ colouring / partition refinement / planner, and the
+# planner as the schedule probe links it over the corpus of tests/test_schedule_hazards_host.py.
 cd "$(dirname "$0")/.." || exit 1
 OUT=${1:-profiles/r05_sanitizers_host.txt}
 mkdir -p build/exp
@@ -18,7 +19,12 @@ echo "## AddressSanitizer + UndefinedBehaviorSanitizer"
 LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0 LPMP_ENGINE_SO=$PWD/build/exp/liblpmp_engine_asan.so \
   timeout 3000 python -m pytest $FILES -q -m "not gpu" -p no:cacheprovider > build/exp/asan_pytest.log 2>&1
 grep -v "Gloo\|^$" build/exp/asan_pytest.log | tail -4
-echo "AddressSanitizer reports: $(grep -c 'ERROR: AddressSanitizer' build/exp/asan_pytest.log)   UBSan reports: $(grep -c 'runtime error:' build/exp/asan_pytest.log)"
+# the planner alone, as tests/cpp/schedule_probe.cpp links it (clang: the same runtime as the preloaded one), over the hazard checker's corpus
+LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0 LPMP_PROBE_CXX=/opt/rocm/lib/llvm/bin/clang++ \
+  LPMP_PROBE_CXXFLAGS="-fsanitize=address,undefined -fno-omit-frame-pointer -g" \
+  timeout 3000 python -m pytest tests/test_schedule_hazards_host.py -q -m "not gpu" -p no:cacheprovider -k "chain_setting or seeded or builders or deep or shared-table" > build/exp/asan_probe.log 2>&1
+tail -2 build/exp/asan_probe.log
+echo "AddressSanitizer reports: $(cat build/exp/asan_pytest.log build/exp/asan_probe.log | grep -c 'ERROR: AddressSanitizer')   UBSan reports: $(cat build/exp/asan_pytest.log build/exp/asan_probe.log | grep -c 'runtime error:')"
 LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0 LPMP_ENGINE_SO=$PWD/build/exp/liblpmp_engine_asan.so python - <<'PY' 2>&1 | tail -5
 import numpy as np
 from lp_mp_amd import engine as E, synthetic as S, multi_gpu as MG, model as M
