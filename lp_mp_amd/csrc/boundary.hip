@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lpmp_engine.h"
+#include "engine_internal.h"
 
 namespace lpmp {
 
@@ -102,13 +102,6 @@ struct lpmp_halo {
 };
 
 extern "C" {
-void* lpmp_engine_stream(lpmp_engine* e);      // engine.cpp
-int lpmp_set_last_error(const char* msg);      // engine.cpp
-int lpmp_boundary_enter(lpmp_engine* e);       // engine.cpp: the engine's device current, speculative passes settled, no aborted chain run behind
-void* lpmp_engine_dual_base(lpmp_engine* e);   // engine.cpp: the dual base pointer the device offsets are relative to
-int64_t lpmp_engine_device_dual_offset(lpmp_engine* e, int64_t packed_off);   // engine.cpp: a packed dual offset as a device offset (rows layout)
-int lpmp_boundary_leave(lpmp_engine* e);       // engine.cpp: duals were written through device offsets
-int lpmp_engine_dual_range_ok(lpmp_engine* e, int64_t packed_off, int64_t len);   // engine.cpp: a run of doubles inside one factor's dual
 
 #define B_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { lpmp_set_last_error((std::string(#x) + ": " + hipGetErrorString(e_)).c_str()); return LPMP_ERR_DEVICE; } } while (0)
 

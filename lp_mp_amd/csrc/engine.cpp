@@ -17,45 +17,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lpmp_engine.h"
-#include "plan.hpp"
-
-namespace lpmp {
-void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, const int32_t* tabs,
-                  double* lb, int32_t* primal, const int32_t* pw_unary, int64_t first, int64_t count, int flags, hipStream_t s);
-bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
-                         double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s);
-bool launch_chain(int kclass, int flags, const void* chain_args, const void* launches, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s);
-bool launch_level_loop(int kclass, int flags, const void* launches, int n_launches, double* dual, const double* cdata,
-                       const int32_t* tabs, double* lb, hipStream_t s);
-void debug_set_level_trace(long long* p);
-void launch_primal_init(const PrimalInit* list, int64_t n, int32_t* primal, hipStream_t s);
-void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal, hipStream_t s);
-void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
-void launch_primal_cost(const void* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s);
-void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);
-void launch_factor_lb_list(const void* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s);
-void launch_factor_lb(const void* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s);
-bool launch_dense_lb(int L, const void* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s);
-void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s);
-void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hipStream_t s);
-void launch_rows_copy(const void* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s);
-bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
-                         double* lb, int32_t* primal, int64_t count, int flags, const void* desc, const int32_t* tabs, int n_tabs, hipStream_t s);
-void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStream_t s);
-struct ShTableDescHost { int64_t off; int32_t d0, d1; };   // kernels.hip: ShTableDesc
-struct RowRecHost { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
-int generic_max_dual();
-int generic_max_adaptive_sends();
-struct LbRecHost { int64_t dual_off; int64_t const_off; int32_t d0, d1; int32_t kind_flags; int32_t pad; };
-}  // namespace lpmp
+#include "engine_internal.h"
+#include "kernels.hpp"
 
 using namespace lpmp;
 
 static thread_local std::string g_error;
 const char* lpmp_last_error(void) { return g_error.c_str(); }
-extern "C" int lpmp_set_last_error(const char* msg) { g_error = msg ? msg : ""; return 0; }   // for the other translation units of the library
+int lpmp_set_last_error(const char* msg) { g_error = msg ? msg : ""; return 0; }   // for the other translation units of the library (engine_internal.h)
 const char* lpmp_version(void) { return "lp_mp_amd 0.1 (gfx950)"; }
 int lpmp_experiment_build(void) { return 0; }   // kept for the ABI: the library has no experimental build
 
@@ -77,69 +46,77 @@ int guarded(F&& f) {
   catch (const std::exception& e) { g_error = e.what(); return LPMP_ERR_INVALID; }
 }
 
-// one launch as the chain kernels see it (layout shared with kernels.hip: ChainLaunch)
-struct ChainLaunchDev { const Op* packets; const UpdRec* recs; const Op* ops; int64_t count; int32_t stride, pad; };
-static_assert(sizeof(ChainLaunchDev) == 40, "ChainLaunch layout");
+// A device allocation that frees itself: move-only, empty or `capacity()` elements.  The only place of this file that calls
+// hipMalloc / hipFree.  Freeing (reset, destructor, move assignment) never throws; hipFree waits for the device.
+template <class T>
+class DevBuf {
+  T* p_ = nullptr; size_t cap_ = 0;
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; } return *this; }
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  size_t capacity() const { return cap_; }
+  void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+  // a fresh allocation of n elements (what the buffer held is freed first); try_alloc reports a failure instead of throwing
+  bool try_alloc(size_t n) {
+    reset();
+    if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return false; }
+    cap_ = n;
+    return true;
+  }
+  void alloc(size_t n) { reset(); HIP_CHECK(hipMalloc((void**)&p_, n * sizeof(T))); cap_ = n; }
+  // a buffer that is refilled in place: a new allocation only when n exceeds the capacity, then with a quarter to spare
+  void grow(size_t n) { if (n > cap_) alloc(n + n / 4 + 16); }
+};
+struct GraphExec {   // an instantiated graph, destroyed with its owner
+  hipGraphExec_t g = nullptr;
+  GraphExec() = default;
+  GraphExec(const GraphExec&) = delete;
+  GraphExec& operator=(const GraphExec&) = delete;
+  ~GraphExec() { reset(); }
+  void reset() { if (g) { (void)hipGraphExecDestroy(g); g = nullptr; } }
+};
+
+// chain executor (deep schedules): the device copy of a ChainPlan, or of the ticket lists of n joined passes
+struct DevChain {
+  int32_t kclass = 0, tickets = 0, epoch = 0;
+  bool banded = false;                     // Infinity-Cache ticket order: plain table loads, not the streaming policy
+  bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
+  DevBuf<ChainLaunch> launches; DevBuf<int32_t> tk_launch, tk_block, dep_off, dep, done, next;
+  DevBuf<unsigned long long> mailbox;      // tagged granules of the message vectors that travel between dependent records (chain_plan.cpp)
+};
+// what issue_launches reads of a schedule: its device arrays and a list of its launches
+struct LaunchView { const UpdRec* recs; const Op* ops; const Op* packets; const std::vector<LevelRange>& launches; };
 
 struct DevSchedule {
-  UpdRec* recs = nullptr;
-  Op* ops = nullptr;
-  Op* packets = nullptr;
+  DevBuf<UpdRec> recs; DevBuf<Op> ops, packets;   // (a scratch schedule is refilled in place: DevBuf::grow)
   std::vector<LevelRange> launches;
   int64_t n_levels = 0, n_recv = 0, n_send = 0, alg_bytes = 0;
-  hipGraphExec_t graph = nullptr;
-  hipGraphExec_t graph_primal = nullptr;   // the same launches with the SWEEP_PRIMAL flag
+  GraphExec graph, graph_primal;           // graph_primal: the same launches with the SWEEP_PRIMAL flag
   bool adaptive_built = false;             // built with every update on the generic kernels (adaptive send rule)
-  size_t recs_cap = 0, ops_cap = 0, packets_cap = 0;   // allocated elements (a scratch schedule is refilled in place)
-  // chain executor (deep schedules): device copies of the ChainPlans, one per kernel class; the other launches stay plain
-  struct DevChain {
-    int32_t kclass = 0, tickets = 0, epoch = 0;
-    bool banded = false;                     // Infinity-Cache ticket order: plain table loads, not the streaming policy
-    bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
-    ChainLaunchDev* launches = nullptr; int32_t *tk_launch = nullptr, *tk_block = nullptr, *dep_off = nullptr, *dep = nullptr, *done = nullptr, *next = nullptr;
-    unsigned long long* mailbox = nullptr;   // tagged granules of the message vectors that travel between dependent records (chain_plan.cpp)
-    void release() {
-      for (void* p : {(void*)launches, (void*)tk_launch, (void*)tk_block, (void*)dep_off, (void*)dep, (void*)done, (void*)next, (void*)mailbox}) if (p) (void)hipFree(p);
-      launches = nullptr; tk_launch = tk_block = dep_off = dep = done = next = nullptr; mailbox = nullptr;
-    }
-  };
-  std::vector<DevChain> chains;
+  std::vector<DevChain> chains;            // one per kernel class; the other launches stay plain
   std::vector<LevelRange> plain;           // launches that do not belong to a chain
   bool chain = false;
-  void release_chain() {
-    for (auto& c : chains) c.release();
-    chains.clear(); plain.clear(); chain = false;
-  }
+  LaunchView view() const { return {recs, ops, packets, launches}; }
+  LaunchView plain_view() const { return {recs, ops, packets, plain}; }
+  void release_chain() { chains.clear(); plain.clear(); chain = false; }
   void release() {
-    if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; }
-    if (graph_primal) { (void)hipGraphExecDestroy(graph_primal); graph_primal = nullptr; }
-    if (recs) { (void)hipFree(recs); recs = nullptr; }
-    if (ops) { (void)hipFree(ops); ops = nullptr; }
-    if (packets) { (void)hipFree(packets); packets = nullptr; }
+    graph.reset(); graph_primal.reset();
+    recs.reset(); ops.reset(); packets.reset();
     release_chain();
-    recs_cap = ops_cap = packets_cap = 0;
     launches.clear();
   }
 };
 
-// device-side description of a chain plan (layouts shared with kernels.hip: ChainArgs, ChainLaunch)
-struct ChainArgsHost {
-  const int32_t* dep_off; const int32_t* dep; int32_t* done; int32_t* next; int32_t* abort_flag; const int32_t* tk_launch;
-  const int32_t* tk_block; int32_t n_tickets; int32_t epoch; long long* trace;
-  double* lb_hist; int64_t hist_stride;     // per-pass bound rows of a joined-pass launch (kernels.hip, ChainArgs)
-  unsigned long long* mailbox;              // or nullptr
-  long long timeout_ticks;                  // bound of every wait, ticks of the 100 MHz s_memrealtime clock
-  int32_t per_begin, per_len, per_count, per_launch_shift, per_row_shift;   // periodic ticket lists (kernels.hip, ChainArgs)
-  int32_t hist_rows;                        // rows of lb_hist the launch may write
-  int32_t ring;                             // slots of done[] when it is a ring (0: one flag per ticket)
-};
-constexpr int CHAIN_GEN_BITS = 8;           // kernels.hip
-constexpr int CHAIN_ABORT_WORDS = 16;       // abort word + what the first wait that gave up was waiting for (kernels.hip, chain_abort)
 static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 s)
   static const long long v = [] { const char* e = std::getenv("LPMP_CHAIN_TIMEOUT_S"); const double s = e ? std::atof(e) : 20.0; return (long long)(std::max(0.001, s) * 1e8); }();
   return v;
 }
-constexpr int HIST_END = 1, HIST_MID = 2;   // kernels.hip
 
 struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0; };
 
@@ -246,22 +223,23 @@ struct lpmp_engine {
   bool own_stream = false;
   hipStream_t capture_stream = nullptr;   // graphs are captured here (the caller's stream may be the legacy default stream, which cannot capture) and replayed on `stream`
   std::unique_ptr<lpmp_plan> plan;
-  double* d_dual = nullptr; bool own_dual = false;
-  double* d_const = nullptr; bool own_const = false;
-  int32_t* d_tabs = nullptr;
-  LbRecHost* d_lbrecs = nullptr;
-  double* d_lb = nullptr; double* d_part = nullptr; double* h_part = nullptr;
+  // the base pointers the kernels use, and beside each the engine's own allocation: empty when the caller's memory is borrowed (LPMP_MEM_DEVICE)
+  double* d_dual = nullptr; DevBuf<double> dual_buf; bool own_dual() const { return dual_buf.get() != nullptr; }
+  double* d_const = nullptr; DevBuf<double> const_buf;
+  DevBuf<int32_t> d_tabs;
+  DevBuf<LbRec> d_lbrecs;
+  DevBuf<double> d_lb, d_part; double* h_part = nullptr;
   // tracked per-factor lower bounds (kernels.hip): d_lb[f] is valid or NaN; lb_all_stale: recompute everything
-  int32_t* d_stale = nullptr; unsigned long long* d_stale_n = nullptr; unsigned long long* h_stale_n = nullptr;
+  DevBuf<int32_t> d_stale; DevBuf<unsigned long long> d_stale_n; unsigned long long* h_stale_n = nullptr;
   bool lb_all_stale = true;
   bool use_lb_tracking = true;
   int64_t last_lb_recomputed = -1;   // factor bounds the last evaluation had to recompute (-1: none evaluated yet)
   // primal rounding: the factors' primal_ members, the lazily initialised set, the message links
-  int32_t* d_primal = nullptr;
-  PrimalInit* d_pinit = nullptr; int64_t n_pinit = 0;
-  PrimalLink* d_plinks = nullptr; int64_t n_plinks = 0, n_pprop = 0;   // all messages; the first n_pprop propagate labels
-  int32_t* d_pw_unary = nullptr;  // [2 nf] the unary on each side of a pairwise factor; only with pairwise types that round themselves
-  double* d_pcost = nullptr; int* d_pbad = nullptr; int* h_pbad = nullptr;
+  DevBuf<int32_t> d_primal;
+  DevBuf<PrimalInit> d_pinit; int64_t n_pinit = 0;
+  DevBuf<PrimalLink> d_plinks; int64_t n_plinks = 0, n_pprop = 0;   // all messages; the first n_pprop propagate labels
+  DevBuf<int32_t> d_pw_unary;     // [2 nf] the unary on each side of a pairwise factor; only with pairwise types that round themselves
+  DevBuf<double> d_pcost; DevBuf<int> d_pbad; int* h_pbad = nullptr;
   char* pinned = nullptr;         // this engine's block of device-written host words (from the pool)
   uint64_t primal_t = 0;          // primal_access_ of every factor a primal pass touches (they move together)
   bool have_primal = false;
@@ -270,10 +248,10 @@ struct lpmp_engine {
   // dual array keeps the vector factors and is the format of every call that hands duals over.  packed_stale: the rows hold
   // newer message vectors than the packed array; rows_stale: the packed array was (or may have been) written by the caller
   bool want_rows = false, rows = false, packed_stale = false, rows_stale = false;
-  double* d_rows = nullptr; RowRecHost* d_rowrecs = nullptr; int64_t n_rowrecs = 0;
+  DevBuf<double> d_rows; DevBuf<RowRec> d_rowrecs; int64_t n_rowrecs = 0;
   // shared pairwise tables: [two words {scale, table offset} per SHARED factor | the pool], an allocation of the engine's own
   // that the SHARED factors' device const offsets point into (Plan::dev_coff), and the pool's tables as the shared classes' kernel sees them
-  double* d_shared = nullptr; ShTableDescHost* d_sh_desc = nullptr;
+  DevBuf<double> d_shared; DevBuf<ShTableDesc> d_sh_desc;
   int nt_flag = 0;                // SWEEP_NT when tables + duals are far larger than L2 + Infinity Cache
   bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
   struct LbRun { int cls; int64_t first, count; };
@@ -294,10 +272,10 @@ struct lpmp_engine {
   int rtype = 0;   // enum lpmp_reparametrization_type
   bool use_graph = true;
   bool use_chain = true;          // deep single-class schedules as one persistent launch (LPMP_NO_CHAIN=1: graph replay)
-  int32_t* d_chain_abort = nullptr; bool chain_ran = false;
+  DevBuf<int32_t> d_chain_abort; bool chain_ran = false;
   // joined passes as one persistent launch: expansions of RotationInfo, by mode and pass count
   struct RotChain {
-    DevSchedule::DevChain dc; int n_steps = 0; int64_t factors = 0, recv = 0, bytes = 0; uint64_t last_use = 0; size_t dev_bytes = 0;
+    DevChain dc; int n_steps = 0; int64_t factors = 0, recv = 0, bytes = 0; uint64_t last_use = 0; size_t dev_bytes = 0;
     // periodic form (rotation_chain): dc holds the TEMPLATE of n_tmpl passes whose tickets [per_begin, per_begin + per_len) are
     // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
     bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
@@ -314,14 +292,14 @@ struct lpmp_engine {
     int n = 0, pos = 0, mode = -1;     // the open batch: n passes were launched as one chain, the caller has asked for pos of them
     int run_len = 0, learned = 0, last_batch = 0;   // plain single passes since the last other call; length of the previous such run
     bool lb_ready = false; std::vector<double> lb;   // bounds after passes 1 ... n - 1 of the batch
-    double* d_snap = nullptr; size_t snap_cap = 0;   // duals (+ tracked bounds) at the start of the batch
-    double* d_hist = nullptr; size_t hist_cap = 0;   // (n - 1) rows of per-factor bounds
-    double* d_hpart = nullptr; size_t hpart_cap = 0; // partial sums of those rows
+    DevBuf<double> d_snap;             // duals (+ tracked bounds) at the start of the batch
+    DevBuf<double> d_hist;             // (n - 1) rows of per-factor bounds
+    DevBuf<double> d_hpart;            // partial sums of those rows
     bool snap_lb_stale = false;
     int64_t batches = 0, passes_launched = 0, passes_used = 0, rollbacks = 0, alloc_failures = 0;
     void release() {
-      for (double** p : {&d_snap, &d_hist, &d_hpart}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-      snap_cap = hist_cap = hpart_cap = 0; n = pos = 0; mode = -1; run_len = learned = last_batch = 0; lb_ready = false;
+      d_snap.reset(); d_hist.reset(); d_hpart.reset();
+      n = pos = 0; mode = -1; run_len = learned = last_batch = 0; lb_ready = false;
     }
   } spec;
   bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
@@ -338,7 +316,7 @@ struct lpmp_engine {
   void release_rot_chains(int only_mode = -1) {
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
       if (only_mode >= 0 && m != only_mode) continue;
-      for (auto& kv : rot_chain[m]) { kv.second.dc.release(); rot_cache_bytes -= std::min(rot_cache_bytes, kv.second.dev_bytes); }
+      for (auto& kv : rot_chain[m]) rot_cache_bytes -= std::min(rot_cache_bytes, kv.second.dev_bytes);
       rot_chain[m].clear();
       rot_order[m] = RotOrder();
     }
@@ -350,12 +328,7 @@ struct lpmp_engine {
   std::vector<hipEvent_t> event_pool;
 
   void release_primal() {
-    if (d_primal) { (void)hipFree(d_primal); d_primal = nullptr; }
-    if (d_pinit) { (void)hipFree(d_pinit); d_pinit = nullptr; }
-    if (d_plinks) { (void)hipFree(d_plinks); d_plinks = nullptr; }
-    if (d_pw_unary) { (void)hipFree(d_pw_unary); d_pw_unary = nullptr; }
-    if (d_pcost) { (void)hipFree(d_pcost); d_pcost = nullptr; }
-    if (d_pbad) { (void)hipFree(d_pbad); d_pbad = nullptr; }
+    d_primal.reset(); d_pinit.reset(); d_plinks.reset(); d_pw_unary.reset(); d_pcost.reset(); d_pbad.reset();
     h_pbad = nullptr;
     have_primal = false; primal_t = 0; n_pinit = n_plinks = n_pprop = 0;
   }
@@ -369,25 +342,16 @@ struct lpmp_engine {
   void release_model() {
     release_schedules();
     deep_note_given = false;
-    for (auto& c : custom) if (c) c->release();
     custom.clear();
     scratch.release();
-    if (own_dual && d_dual) (void)hipFree(d_dual);
-    if (own_const && d_const) (void)hipFree(d_const);
-    d_dual = nullptr; d_const = nullptr; own_dual = own_const = false;
-    if (d_tabs) { (void)hipFree(d_tabs); d_tabs = nullptr; }
-    if (d_rows) { (void)hipFree(d_rows); d_rows = nullptr; }
-    if (d_rowrecs) { (void)hipFree(d_rowrecs); d_rowrecs = nullptr; }
-    if (d_shared) { (void)hipFree(d_shared); d_shared = nullptr; }
-    if (d_sh_desc) { (void)hipFree(d_sh_desc); d_sh_desc = nullptr; }
+    dual_buf.reset(); const_buf.reset();
+    d_dual = nullptr; d_const = nullptr;
+    d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
-    if (d_lbrecs) { (void)hipFree(d_lbrecs); d_lbrecs = nullptr; }
-    if (d_lb) { (void)hipFree(d_lb); d_lb = nullptr; }
-    if (d_part) { (void)hipFree(d_part); d_part = nullptr; }
+    d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
     release_primal();
-    if (d_stale) { (void)hipFree(d_stale); d_stale = nullptr; }
-    if (d_stale_n) { (void)hipFree(d_stale_n); d_stale_n = nullptr; }
+    d_stale.reset(); d_stale_n.reset();
     h_stale_n = nullptr;
     lb_all_stale = true;
     lb_runs.clear();
@@ -522,64 +486,52 @@ void d2h(void* dst, const void* src, size_t bytes, hipStream_t stream) {
 }
 
 template <class T, class V>
-void fill_device(T*& dst, size_t& cap, const V& src, hipStream_t stream) {
-  if (src.size() > cap) {
-    if (dst) { HIP_CHECK(hipFree(dst)); dst = nullptr; cap = 0; }
-    const size_t n = src.size() + src.size() / 4 + 16;
-    HIP_CHECK(hipMalloc((void**)&dst, n * sizeof(T)));
-    cap = n;
-  }
+void fill_device(DevBuf<T>& dst, const V& src, hipStream_t stream) {
+  dst.grow(src.size());
   h2d(dst, src.data(), src.size() * sizeof(T), stream);
 }
 
 // a chain's tables on the device: its launches, ticket lists and dependency lists, n_done zeroed completion flags and the ticket
-// counter.  Nothing half-built stays behind: on failure every buffer of dc is freed again.
-void upload_chain(DevSchedule::DevChain& dc, const std::vector<ChainLaunchDev>& lds, const std::vector<int32_t>& tk_launch, const std::vector<int32_t>& tk_block,
-                  const std::vector<int32_t>& dep_off, const std::vector<int32_t>& dep, size_t n_done, hipStream_t stream) {
-  auto up = [&](auto*& dst, const auto& v) {
-    using T = std::remove_reference_t<decltype(*dst)>;
-    HIP_CHECK(hipMalloc((void**)&dst, std::max<size_t>(1, v.size()) * sizeof(T)));
-    if (!v.empty()) h2d(dst, v.data(), v.size() * sizeof(T), stream);
+// counter.  Nothing half-built stays behind: on failure the buffers go with the local.
+DevChain upload_chain(const std::vector<ChainLaunch>& lds, const std::vector<int32_t>& tk_launch, const std::vector<int32_t>& tk_block,
+                      const std::vector<int32_t>& dep_off, const std::vector<int32_t>& dep, size_t n_done, hipStream_t stream) {
+  DevChain dc;
+  auto up = [&](auto& dst, const auto& v) {
+    dst.alloc(std::max<size_t>(1, v.size()));
+    if (!v.empty()) h2d(dst, v.data(), v.size() * sizeof(v[0]), stream);
   };
-  try {
-    up(dc.launches, lds); up(dc.tk_launch, tk_launch); up(dc.tk_block, tk_block); up(dc.dep_off, dep_off); up(dc.dep, dep);
-    dc.tickets = (int32_t)tk_launch.size();
-    n_done = std::max<size_t>(1, n_done);
-    HIP_CHECK(hipMalloc((void**)&dc.done, n_done * sizeof(int32_t)));
-    HIP_CHECK(hipMalloc((void**)&dc.next, sizeof(int32_t)));
-    HIP_CHECK(hipMemsetAsync(dc.done, 0, n_done * sizeof(int32_t), stream));
-  } catch (...) {
-    dc.release();
-    throw;
-  }
+  up(dc.launches, lds); up(dc.tk_launch, tk_launch); up(dc.tk_block, tk_block); up(dc.dep_off, dep_off); up(dc.dep, dep);
+  dc.tickets = (int32_t)tk_launch.size();
+  n_done = std::max<size_t>(1, n_done);
+  dc.done.alloc(n_done);
+  dc.next.alloc(1);
+  HIP_CHECK(hipMemsetAsync(dc.done, 0, n_done * sizeof(int32_t), stream));
+  return dc;
 }
 
 // keep: refill d's buffers in place where they are large enough (the scratch schedule of lpmp_compute_pass_custom)
 void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool keep = false, bool adaptive_built = false) {
-  if (keep) { if (d.graph) { (void)hipGraphExecDestroy(d.graph); d.graph = nullptr; } if (d.graph_primal) { (void)hipGraphExecDestroy(d.graph_primal); d.graph_primal = nullptr; } }
+  if (keep) { d.graph.reset(); d.graph_primal.reset(); }
   else d.release();
   d.launches = s.launches; d.n_levels = s.n_levels; d.n_recv = s.n_recv; d.n_send = s.n_send; d.alg_bytes = s.alg_bytes;
   d.adaptive_built = adaptive_built;
-  fill_device(d.recs, d.recs_cap, s.recs, stream);
-  fill_device(d.ops, d.ops_cap, s.ops, stream);
-  fill_device(d.packets, d.packets_cap, s.packets, stream);
+  fill_device(d.recs, s.recs, stream);
+  fill_device(d.ops, s.ops, stream);
+  fill_device(d.packets, s.packets, stream);
   d.release_chain();
   if (!s.chains.empty() && !adaptive_built) {
     for (const ChainPlan& c : s.chains) {
-      std::vector<ChainLaunchDev> lds;
+      std::vector<ChainLaunch> lds;
       for (const auto& l : c.launches) lds.push_back({l.stride > 0 ? d.packets + l.pk_begin : nullptr, d.recs + l.rec_begin, d.ops, l.count, l.stride, l.flags});
-      d.chains.emplace_back();                 // (owned by d from here on: release_chain frees what a failure leaves)
-      DevSchedule::DevChain& dc = d.chains.back();
-      upload_chain(dc, lds, c.tk_launch, c.tk_block, c.dep_off, c.dep, c.tk_launch.size(), stream);
+      d.chains.push_back(upload_chain(lds, c.tk_launch, c.tk_block, c.dep_off, c.dep, c.tk_launch.size(), stream));
+      DevChain& dc = d.chains.back();
       dc.kclass = c.kclass; dc.banded = c.banded; dc.level_loop = c.level_loop; dc.n_launches = (int32_t)c.launches.size();
       if (c.mailbox_rows > 0) {
         // a granule is valid when its tag is the epoch of the running launch: zeroed once, epochs start at 1
         const size_t bytes = (size_t)c.mailbox_rows * c.mailbox_width * 16;
-        if (hipMalloc((void**)&dc.mailbox, bytes) != hipSuccess) {
-          (void)hipGetLastError();
+        if (!dc.mailbox.try_alloc(bytes / sizeof(unsigned long long)))
           throw DeviceError("no device memory for the mailbox of a deep schedule (" + std::to_string(bytes >> 20) +
                             " MiB: 16 bytes per label and mailbox send); LPMP_NO_MAILBOX=1 plans the same schedule with completion flags only");
-        }
         HIP_CHECK(hipMemsetAsync(dc.mailbox, 0, bytes, stream));
       }
     }
@@ -590,13 +542,13 @@ void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool
 }
 
 void check_generic_limits(const Plan& p, const Schedule& s) {
-  const int lim = generic_max_dual();
+  const int lim = GEN_MAXD;
   for (const auto& lr : s.launches) {
     if (lr.kclass != KC_GENERIC) continue;
     for (int64_t i = lr.begin; i < lr.end; ++i) {
       const UpdRec& r = s.recs[i];
       const int own = (r.kind_flags & 15) == LPMP_F_VECTOR ? r.d0 : r.d0 + r.d1;
-      if (p.force_generic && r.n_send > generic_max_adaptive_sends())
+      if (p.force_generic && r.n_send > GEN_ADAPTIVE_SENDS)
         throw UnsupportedError("adaptive sends: factor " + std::to_string(r.factor) + " has more active sends than the device kernel keeps improvements for");
       if (own > lim) throw UnsupportedError("factor " + std::to_string(r.factor) + ": dual size " + std::to_string(own) + " exceeds the device limit " + std::to_string(lim));
       for (int k = 0; k < r.n_recv + r.n_send; ++k)
@@ -689,7 +641,7 @@ void ensure_pass_chain_plan(lpmp_engine* e, int mode) {
   h.recs.clear(); h.recs.shrink_to_fit(); h.ops.clear(); h.ops.shrink_to_fit(); h.packets.clear(); h.packets.shrink_to_fit();
 }
 
-void issue_launches(lpmp_engine* e, const DevSchedule& s, bool timed, hipStream_t stream, int only_level = 0) {
+void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t stream, int only_level = 0) {
   for (const auto& lr : s.launches) {
     if (only_level > 0 && lr.level != only_level) continue;
     hipEvent_t a = nullptr, b = nullptr;
@@ -726,7 +678,7 @@ void issue_launches(lpmp_engine* e, const DevSchedule& s, bool timed, hipStream_
 // (ticket in hand, predecessors seen, body done, published; 100 MHz) are written to the file together with the ticket
 // -> launch map and the dependency lists: tools/chain_trace.py turns them into the latency budget of DESIGN.md 6
 struct ChainTrace {
-  long long* d = nullptr; int32_t n = 0;
+  DevBuf<long long> d; int32_t n = 0;
   // ("%p" in the path: this process's id — several ranks on one box)
   static const char* path() {
     static const std::string p = [] {
@@ -741,7 +693,7 @@ struct ChainTrace {
   long long* begin(int32_t n_tickets, hipStream_t s) {
     if (!path()) return nullptr;
     n = n_tickets;
-    HIP_CHECK(hipMalloc((void**)&d, (size_t)8 * n * sizeof(long long)));
+    d.alloc((size_t)8 * n);
     HIP_CHECK(hipMemsetAsync(d, 0, (size_t)8 * n * sizeof(long long), s));
     return d;
   }
@@ -758,7 +710,7 @@ struct ChainTrace {
     HIP_CHECK(hipMemcpy(off.data(), c.dep_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<int32_t> dep((size_t)off[n]);
     if (!dep.empty()) HIP_CHECK(hipMemcpy(dep.data(), c.dep, dep.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d); d = nullptr;
+    d.reset();
     if (FILE* f = std::fopen(out.c_str(), "wb")) {
       const int64_t hdr[2] = {n, off[n]};
       std::fwrite(hdr, sizeof(hdr), 1, f);
@@ -771,11 +723,27 @@ struct ChainTrace {
   }
 };
 
+// the abort words of the chain executor: allocated and zeroed the first time a chain runs
+void ensure_chain_abort(lpmp_engine* e) {
+  if (e->d_chain_abort) return;
+  e->d_chain_abort.alloc(CHAIN_ABORT_WORDS);
+  HIP_CHECK(hipMemsetAsync(e->d_chain_abort, 0, CHAIN_ABORT_WORDS * sizeof(int32_t), e->stream));
+}
+// the arguments every chain launch has: the chain's arrays, the abort words, the next epoch, the bound of a wait, the trace
+// (everything else zero: no bound rows, no mailbox, plain ticket lists)
+ChainArgs chain_args(lpmp_engine* e, DevChain& c, int32_t n_tickets, long long* trace) {
+  ChainArgs ca{};
+  ca.dep_off = c.dep_off; ca.dep = c.dep; ca.done = c.done; ca.next = c.next; ca.abort_flag = e->d_chain_abort;
+  ca.tk_launch = c.tk_launch; ca.tk_block = c.tk_block; ca.n_tickets = n_tickets; ca.epoch = ++c.epoch;
+  ca.trace = trace; ca.timeout_ticks = chain_timeout_ticks();
+  return ca;
+}
+
 // one sweep over a device schedule; long launch chains (row-major grids: one launch per anti-diagonal)
 // are captured once into a hipGraph and replayed
 void run_schedule(lpmp_engine* e, DevSchedule& s) {
   if (s.launches.empty()) return;
-  if (e->timing) { issue_launches(e, s, true, e->stream); if (e->pending.size() > 4096) e->drain_timing(); return; }
+  if (e->timing) { issue_launches(e, s.view(), true, e->stream); if (e->pending.size() > 4096) e->drain_timing(); return; }
   // (a primal pass rounds inside the packed kernels' chain form too; the generic chain kernels carry no labels, and
   // pairwise factors that round themselves need the generic kernels: those passes stay launch by launch)
   bool chain_ok = s.chain && e->use_chain;
@@ -784,38 +752,34 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
     for (const auto& c : s.chains) if (kc_width(c.kclass) == 0) chain_ok = false;
   }
   if (chain_ok) {
-    if (!e->d_chain_abort) { HIP_CHECK(hipMalloc((void**)&e->d_chain_abort, CHAIN_ABORT_WORDS * sizeof(int32_t))); HIP_CHECK(hipMemsetAsync(e->d_chain_abort, 0, CHAIN_ABORT_WORDS * sizeof(int32_t), e->stream)); }
+    ensure_chain_abort(e);
     // UpdateFactorPrimal always sends 'shared' (issue_launches)
     const int rule = e->primal_pass ? SWEEP_PRIMAL : e->rtype == LPMP_RTYPE_RESIDUAL ? SWEEP_RESIDUAL : e->rtype == LPMP_RTYPE_ADAPTIVE ? SWEEP_ADAPTIVE : 0;
     // classes are independent of each other (chain_plan.cpp): the plain launches first, then one persistent launch per class
-    if (!s.plain.empty()) {
-      DevSchedule tmp;                       // a view: issue_launches only reads recs / ops / packets / launches
-      tmp.recs = s.recs; tmp.ops = s.ops; tmp.packets = s.packets; tmp.launches = s.plain;
-      try { issue_launches(e, tmp, false, e->stream); } catch (...) { tmp.recs = nullptr; tmp.ops = nullptr; tmp.packets = nullptr; throw; }
-      tmp.recs = nullptr; tmp.ops = nullptr; tmp.packets = nullptr;
-    }
+    if (!s.plain.empty()) issue_launches(e, s.plain_view(), false, e->stream);
     for (auto& c : s.chains) {
       if (c.level_loop) {
-        // LPMP_LEVEL_TRACE=<file> (debugging): time stamps of the first 4000 levels, written after a synchronisation
+        // LPMP_LEVEL_TRACE=<file> (debugging): time stamps of the first LEVEL_TRACE_MAX levels, written after a synchronisation
         static const char* lt_path = std::getenv("LPMP_LEVEL_TRACE");
-        long long* d_lt = nullptr;
-        const size_t lt_n = 8 + 8 * 4000;
-        if (lt_path) { HIP_CHECK(hipMalloc((void**)&d_lt, lt_n * sizeof(long long))); HIP_CHECK(hipMemset(d_lt, 0, lt_n * sizeof(long long))); debug_set_level_trace(d_lt); }
+        DevBuf<long long> d_lt;
+        const size_t lt_n = 8 + 8 * LEVEL_TRACE_MAX;
+        if (lt_path) { d_lt.alloc(lt_n); HIP_CHECK(hipMemset(d_lt, 0, lt_n * sizeof(long long))); debug_set_level_trace(d_lt); }
         if (!launch_level_loop(c.kclass, rule, c.launches, c.n_launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->stream))
           throw DeviceError("level loop: no kernel for class " + std::to_string(c.kclass));
         if (lt_path) {
           HIP_CHECK(hipStreamSynchronize(e->stream));
           std::vector<long long> h(lt_n);
           HIP_CHECK(hipMemcpy(h.data(), d_lt, lt_n * sizeof(long long), hipMemcpyDeviceToHost));
-          debug_set_level_trace(nullptr); (void)hipFree(d_lt);
+          debug_set_level_trace(nullptr);
           if (FILE* f = std::fopen(lt_path, "wb")) { std::fwrite(h.data(), sizeof(long long), h.size(), f); std::fclose(f); }
         }
         continue;
       }
       HIP_CHECK(hipMemsetAsync(c.next, 0, sizeof(int32_t), e->stream));
       ChainTrace tr;
-      const ChainArgsHost ca{c.dep_off, c.dep, c.done, c.next, e->d_chain_abort, c.tk_launch, c.tk_block, c.tickets, ++c.epoch, tr.begin(c.tickets, e->stream), nullptr, 0, c.mailbox, chain_timeout_ticks(), 0, 0, 0, 0, 0, 0, 0};
-      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->nt_flag), &ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->stream))
+      ChainArgs ca = chain_args(e, c, c.tickets, tr.begin(c.tickets, e->stream));
+      ca.mailbox = c.mailbox;
+      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->nt_flag), ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->stream))
         throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
       tr.end(c, e->stream, e->d_chain_abort);
     }
@@ -826,12 +790,12 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
   // (graphs of up to ~20 k kernel nodes were exercised — C5; beyond 200 k the nodes are issued one by
   // one instead of instantiating a graph of that size)
   if (e->use_graph && s.launches.size() > 8 && s.launches.size() <= 200000) {
-    hipGraphExec_t& exec = e->primal_pass ? s.graph_primal : s.graph;
+    hipGraphExec_t& exec = e->primal_pass ? s.graph_primal.g : s.graph.g;
     if (!exec) {
       hipGraph_t g = nullptr;
       if (!e->capture_stream) e->capture_stream = stream_pool().take(e->device);
       HIP_CHECK(hipStreamBeginCapture(e->capture_stream, hipStreamCaptureModeThreadLocal));
-      try { issue_launches(e, s, false, e->capture_stream); }
+      try { issue_launches(e, s.view(), false, e->capture_stream); }
       catch (...) { (void)hipStreamEndCapture(e->capture_stream, &g); if (g) (void)hipGraphDestroy(g); throw; }
       HIP_CHECK(hipStreamEndCapture(e->capture_stream, &g));
       HIP_CHECK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
@@ -840,7 +804,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
     HIP_CHECK(hipGraphLaunch(exec, e->stream));
     return;
   }
-  issue_launches(e, s, false, e->stream);
+  issue_launches(e, s.view(), false, e->stream);
 }
 
 // weight / receive-mask rows of an iterator-range pass as they come over the C ABI: offsets start at 0 and do not
@@ -933,7 +897,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   if (!why.empty()) return no(why.c_str());
   if (periodic && (int64_t)48 * (int64_t)(2 * jt.per_len) / jt.ring + 64 >= (1 << CHAIN_GEN_BITS)) throw std::runtime_error("rotation chain: ring too small for its generation counter");
   const int n_steps = 2 * n + 1;
-  std::vector<ChainLaunchDev> lds;
+  std::vector<ChainLaunch> lds;
   for (int s = 0; s < n_steps; ++s) {
     const auto& t = ri.t[jt.step_tmpl[s]];
     const DevSchedule& ds = t.sched == 0 ? e->sched_pass[mode] : e->sched_bf[mode];
@@ -948,7 +912,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   // per copy — so this table, too, is the template's whatever the call's pass count)
   const int64_t N = (int64_t)jt.tk_launch.size();
   const size_t n_done = periodic ? (size_t)jt.ring : (size_t)N;
-  rc.dev_bytes = lds.size() * sizeof(ChainLaunchDev) + (jt.tk_launch.size() + jt.tk_block.size() + jt.dep_off.size() + jt.dep.size() + n_done + 1) * sizeof(int32_t);
+  rc.dev_bytes = lds.size() * sizeof(ChainLaunch) + (jt.tk_launch.size() + jt.tk_block.size() + jt.dep_off.size() + jt.dep.size() + n_done + 1) * sizeof(int32_t);
   // bound the cache in bytes: drop the least recently used built chains (of any mode) until the new one fits; the stream is drained first
   for (bool drained = false; e->rot_cache_bytes + rc.dev_bytes > e->rot_cache_limit;) {
     std::map<int, lpmp_engine::RotChain>* vm = nullptr; std::map<int, lpmp_engine::RotChain>::iterator victim;
@@ -957,16 +921,14 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
         if (i2->second.n_steps > 0 && (!vm || i2->second.last_use < victim->second.last_use)) { vm = &m; victim = i2; }
     if (!vm) break;
     if (!drained) { HIP_CHECK(hipStreamSynchronize(e->stream)); drained = true; }
-    victim->second.dc.release();
     e->rot_cache_bytes -= std::min(e->rot_cache_bytes, victim->second.dev_bytes);
     vm->erase(victim);
   }
   try {
-    upload_chain(rc.dc, lds, jt.tk_launch, jt.tk_block, jt.dep_off, jt.dep, n_done, e->stream);
+    rc.dc = upload_chain(lds, jt.tk_launch, jt.tk_block, jt.dep_off, jt.dep, n_done, e->stream);
     HIP_CHECK(hipStreamSynchronize(e->stream));
   } catch (...) {
     // nothing half-built stays behind: the entry goes (a later call tries again), the bytes were never counted
-    rc.dc.release();
     e->rot_chain[mode].erase(key);
     throw;
   }
@@ -984,7 +946,7 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   if (!e->use_chain || !e->use_blocked_passes || e->primal_pass || e->rtype != LPMP_RTYPE_SHARED) return false;
   lpmp_engine::RotChain* rc = rotation_chain(e, mode, n);
   if (!rc) return false;
-  if (!e->d_chain_abort) { HIP_CHECK(hipMalloc((void**)&e->d_chain_abort, CHAIN_ABORT_WORDS * sizeof(int32_t))); HIP_CHECK(hipMemsetAsync(e->d_chain_abort, 0, CHAIN_ABORT_WORDS * sizeof(int32_t), e->stream)); }
+  ensure_chain_abort(e);
   auto& c = rc->dc;
   HIP_CHECK(hipMemsetAsync(c.next, 0, sizeof(int32_t), e->stream));
   // periodic template: the period runs once in the template and `extra` more times in this call
@@ -996,14 +958,13 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   }
   ChainTrace tr;
   const int32_t n_tickets = c.tickets + extra * rc->per_len;
-  const ChainArgsHost ca{c.dep_off, c.dep, c.done, c.next, e->d_chain_abort, c.tk_launch, c.tk_block, n_tickets, ++c.epoch, rc->periodic ? nullptr : tr.begin(c.tickets, e->stream),
-                         lb_hist, lb_hist ? e->plan->p.nf : 0, nullptr, chain_timeout_ticks(),
-                         rc->periodic ? rc->per_begin : 0, rc->periodic ? rc->per_len : 0, rc->periodic ? 1 + extra : 0, 0,
-                         rc->periodic ? rc->depth / 2 : 0, lb_hist ? n - 1 : 0, rc->periodic ? rc->ring : 0};
+  ChainArgs ca = chain_args(e, c, n_tickets, rc->periodic ? nullptr : tr.begin(c.tickets, e->stream));
+  if (lb_hist) { ca.lb_hist = lb_hist; ca.hist_stride = e->plan->p.nf; ca.hist_rows = n - 1; }
+  if (rc->periodic) { ca.per_begin = rc->per_begin; ca.per_len = rc->per_len; ca.per_count = 1 + extra; ca.per_row_shift = rc->depth / 2; ca.ring = rc->ring; }
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
-  if (!launch_chain(c.kclass, 0, &ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, 0, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1290,12 +1251,12 @@ void lpmp_destroy(lpmp_engine* e) {
   (void)hipSetDevice(e->device);
   // a BORROWED dual buffer (LPMP_MEM_DEVICE) outlives the engine: an open batch of passes that ran ahead of the caller must
   // not stay in it
-  if (e->plan && !e->own_dual && e->spec.n > 0) { try { settle(e); } catch (const std::exception& ex) { std::fprintf(stderr, "lpmp_destroy: could not roll back passes that ran ahead: %s\n", ex.what()); } }
+  if (e->plan && !e->own_dual() && e->spec.n > 0) { try { settle(e); } catch (const std::exception& ex) { std::fprintf(stderr, "lpmp_destroy: could not roll back passes that ran ahead: %s\n", ex.what()); } }
   (void)hipStreamSynchronize(e->stream);
   for (auto& p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
   e->release_model();
-  if (e->d_chain_abort) { (void)hipFree(e->d_chain_abort); e->d_chain_abort = nullptr; }
+  e->d_chain_abort.reset();
   if (e->own_stream && e->stream) stream_pool().give(e->device, e->stream);
   if (e->capture_stream) { (void)hipStreamSynchronize(e->capture_stream); stream_pool().give(e->device, e->capture_stream); }
   if (!guarded_ok(e->pinned, PINNED_WORDS_BYTES)) {   // a damaged block is reported and never reused
@@ -1311,9 +1272,9 @@ int lpmp_set_stream(lpmp_engine* e, void* s) {
     settle(e);
     HIP_CHECK(hipStreamSynchronize(e->stream));
     for (int d = 0; d < 2; ++d) for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-      if (e->sched[d][m].graph) { (void)hipGraphExecDestroy(e->sched[d][m].graph); e->sched[d][m].graph = nullptr; }
+      e->sched[d][m].graph.reset();
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-      if (e->sched_pass[m].graph) { (void)hipGraphExecDestroy(e->sched_pass[m].graph); e->sched_pass[m].graph = nullptr; }
+      e->sched_pass[m].graph.reset();
     if (e->own_stream && e->stream) stream_pool().give(e->device, e->stream);
     e->stream = (hipStream_t)s; e->own_stream = false;
   });
@@ -1324,7 +1285,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
   return guarded([&] {
     if (!e || !m) throw std::runtime_error("null argument");
     HIP_CHECK(hipSetDevice(e->device));
-    if (e->plan && !e->own_dual && e->spec.n > 0) settle(e);   // the caller keeps the old model's (borrowed) dual buffer: leave it at the caller's pass
+    if (e->plan && !e->own_dual() && e->spec.n > 0) settle(e);   // the caller keeps the old model's (borrowed) dual buffer: leave it at the caller's pass
     HIP_CHECK(hipStreamSynchronize(e->stream));
     { const int d = e->spec.max_depth; e->release_model(); e->spec.max_depth = d; }   // (an open speculative batch in an engine-owned buffer dies with the old model)
     auto pl = std::make_unique<lpmp_plan>();
@@ -1343,21 +1304,21 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       e->d_const = const_cast<double*>(m->const_data);
       if (((uintptr_t)e->d_const & 15) != 0) throw std::runtime_error("device const buffer must be 16-byte aligned");
     } else if (n_const > 0) {
-      HIP_CHECK(hipMalloc((void**)&e->d_const, (size_t)n_const * sizeof(double)));
-      e->own_const = true;
+      e->const_buf.alloc((size_t)n_const);
+      e->d_const = e->const_buf;
       h2d(e->d_const, m->const_data, (size_t)n_const * sizeof(double), e->stream);
     }
     if (dual_mem == LPMP_MEM_DEVICE) {
       e->d_dual = const_cast<double*>(m->dual_data);
     } else {
-      HIP_CHECK(hipMalloc((void**)&e->d_dual, (size_t)n_dual * sizeof(double)));
-      e->own_dual = true;
+      e->dual_buf.alloc((size_t)n_dual);
+      e->d_dual = e->dual_buf;
       h2d(e->d_dual, m->dual_data, (size_t)n_dual * sizeof(double), e->stream);
     }
     if (e->want_rows && e->d_const) {
       // rows layout: every dense pairwise factor becomes one row [table | m1 | m2] of a private buffer; its device offsets
       // (relative to the const / dual base pointers, which the kernels add them to) point there from now on
-      std::vector<RowRecHost> rr;
+      std::vector<RowRec> rr;
       int64_t at = 0;
       for (int64_t f = 0; f < p.nf; ++f)
         if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
@@ -1365,15 +1326,15 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
           at += ((int64_t)p.f_dim0[f] * p.f_dim1[f] + p.f_dim0[f] + p.f_dim1[f] + 1) / 2 * 2;      // rows start 16-byte aligned
         }
       if (!rr.empty()) {
-        HIP_CHECK(hipMalloc((void**)&e->d_rows, (size_t)at * sizeof(double)));
-        if ((((uintptr_t)e->d_rows - (uintptr_t)e->d_const) % 16) != 0 || (((uintptr_t)e->d_rows - (uintptr_t)e->d_dual) % 8) != 0)
+        e->d_rows.alloc((size_t)at);
+        if ((((uintptr_t)e->d_rows.get() - (uintptr_t)e->d_const) % 16) != 0 || (((uintptr_t)e->d_rows.get() - (uintptr_t)e->d_dual) % 8) != 0)
           throw std::runtime_error("rows layout: buffers are not aligned to each other");
-        HIP_CHECK(hipMalloc((void**)&e->d_rowrecs, rr.size() * sizeof(RowRecHost)));
-        h2d(e->d_rowrecs, rr.data(), rr.size() * sizeof(RowRecHost), e->stream);
+        e->d_rowrecs.alloc(rr.size());
+        h2d(e->d_rowrecs, rr.data(), rr.size() * sizeof(RowRec), e->stream);
         e->n_rowrecs = (int64_t)rr.size();
         launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 0, e->stream);
         HIP_CHECK(hipGetLastError());
-        const int64_t c_shift = (int64_t)(((intptr_t)e->d_rows - (intptr_t)e->d_const) / 8), d_shift = (int64_t)(((intptr_t)e->d_rows - (intptr_t)e->d_dual) / 8);
+        const int64_t c_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_const) / 8), d_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_dual) / 8);
         pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end()); pl->p.dev_doff.assign(p.f_doff.begin(), p.f_doff.end());
         size_t k = 0;
         for (int64_t f = 0; f < p.nf; ++f)
@@ -1393,9 +1354,9 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       std::vector<int64_t> sf;
       for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED) sf.push_back(f);
       const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared];
-      HIP_CHECK(hipMalloc((void**)&e->d_shared, (size_t)(2 * n_sf + n_pool) * sizeof(double)));
-      if ((((uintptr_t)e->d_shared - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
-      const int64_t base = (int64_t)(((intptr_t)e->d_shared - (intptr_t)e->d_const) / 8);
+      e->d_shared.alloc((size_t)(2 * n_sf + n_pool));
+      if ((((uintptr_t)e->d_shared.get() - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
+      const int64_t base = (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8);
       std::vector<int64_t> cells((size_t)(2 * n_sf));
       if (pl->p.dev_coff.empty()) pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
       for (int64_t k = 0; k < n_sf; ++k) {
@@ -1408,17 +1369,17 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       h2d(e->d_shared + 2 * n_sf, p.sh_data.data(), (size_t)n_pool * sizeof(double), e->stream);
       launch_shared_cells(e->d_shared, n_sf, e->d_const, e->stream);
       HIP_CHECK(hipGetLastError());
-      std::vector<ShTableDescHost> desc((size_t)p.n_shared);
+      std::vector<ShTableDesc> desc((size_t)p.n_shared);
       for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + p.sh_off[(size_t)t], p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
-      HIP_CHECK(hipMalloc((void**)&e->d_sh_desc, desc.size() * sizeof(ShTableDescHost)));
-      h2d(e->d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDescHost), e->stream);
+      e->d_sh_desc.alloc(desc.size());
+      h2d(e->d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDesc), e->stream);
     }
     if (!p.tab_data.empty()) {
-      HIP_CHECK(hipMalloc((void**)&e->d_tabs, p.tab_data.size() * sizeof(int32_t)));
+      e->d_tabs.alloc(p.tab_data.size());
       h2d(e->d_tabs, p.tab_data.data(), p.tab_data.size() * sizeof(int32_t), e->stream);
     }
     // lower-bound records, in factor order, and runs of factors the streaming dense kernel can take
-    std::vector<LbRecHost> lb(p.nf);
+    std::vector<LbRec> lb(p.nf);
     auto lb_class = [&](int64_t f) {
       if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[f] == p.f_dim1[f] && (p.coff(f) % 2) == 0 &&
           (p.f_dim0[f] == 8 || p.f_dim0[f] == 16 || p.f_dim0[f] == 32)) return p.f_dim0[f];
@@ -1429,14 +1390,14 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       const int c = lb_class(f);
       if (e->lb_runs.empty() || e->lb_runs.back().cls != c) e->lb_runs.push_back({c, f, 1}); else e->lb_runs.back().count++;
     }
-    HIP_CHECK(hipMalloc((void**)&e->d_lbrecs, (size_t)p.nf * sizeof(LbRecHost)));
-    h2d(e->d_lbrecs, lb.data(), (size_t)p.nf * sizeof(LbRecHost), e->stream);
-    HIP_CHECK(hipMalloc((void**)&e->d_lb, (size_t)p.nf * sizeof(double)));
-    HIP_CHECK(hipMalloc((void**)&e->d_part, 1024 * sizeof(double)));
+    e->d_lbrecs.alloc((size_t)p.nf);
+    h2d(e->d_lbrecs, lb.data(), (size_t)p.nf * sizeof(LbRec), e->stream);
+    e->d_lb.alloc((size_t)p.nf);
+    e->d_part.alloc(1024);
     if (!e->pinned) e->pinned = pinned_pool().take();
     e->h_part = (double*)e->pinned;                            // [0, 1024) doubles: partial sums
-    HIP_CHECK(hipMalloc((void**)&e->d_stale, (size_t)p.nf * sizeof(int32_t)));
-    HIP_CHECK(hipMalloc((void**)&e->d_stale_n, sizeof(unsigned long long)));
+    e->d_stale.alloc((size_t)p.nf);
+    e->d_stale_n.alloc(1);
     e->h_stale_n = (unsigned long long*)(e->pinned + 8 * 1024);   // one counter
     HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));   // all NaN: nothing tracked yet
     HIP_CHECK(hipStreamSynchronize(e->stream));
@@ -1499,11 +1460,11 @@ int lpmp_set_reparametrization_type(lpmp_engine* e, int rtype) {
     if (rtype != e->rtype) {   // captured graphs bake the kernel flag in
       HIP_CHECK(hipStreamSynchronize(e->stream));
       for (int d = 0; d < 2; ++d) for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-        if (e->sched[d][m].graph) { (void)hipGraphExecDestroy(e->sched[d][m].graph); e->sched[d][m].graph = nullptr; }
+        e->sched[d][m].graph.reset();
       for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-        if (e->sched_pass[m].graph) { (void)hipGraphExecDestroy(e->sched_pass[m].graph); e->sched_pass[m].graph = nullptr; }
-      for (int k = 0; k < 2; ++k) if (e->sched_part[k].graph) { (void)hipGraphExecDestroy(e->sched_part[k].graph); e->sched_part[k].graph = nullptr; }
-      for (auto& c : e->custom) if (c && c->graph) { (void)hipGraphExecDestroy(c->graph); c->graph = nullptr; }
+        e->sched_pass[m].graph.reset();
+      for (int k = 0; k < 2; ++k) e->sched_part[k].graph.reset();
+      for (auto& c : e->custom) if (c) c->graph.reset();
     }
     const int mode = e->mode;
     apply_rtype(e, rtype);
@@ -1560,8 +1521,7 @@ static void compute_plain_passes(lpmp_engine* e, int n) {   // ComputeForwardPas
       n -= done;
     }
     if (n >= 2 && e->rotation_ok[e->mode] && e->use_rotation) {
-      const DevSchedule& fb = e->sched_pass[e->mode];
-      const DevSchedule& bf = e->sched_bf[e->mode];
+      const LaunchView fb = e->sched_pass[e->mode].view(), bf = e->sched_bf[e->mode].view();
       const bool timed = e->timing;
       issue_launches(e, fb, timed, e->stream, 1);
       issue_launches(e, fb, timed, e->stream, 2);
@@ -1596,7 +1556,7 @@ int lpmp_prepare_passes(lpmp_engine* e, int n) {
 // persistent launch in Infinity-Cache order (rotation_chain: 5.1 against 6.6 ms per pass on C3).  With speculation on,
 // lpmp_compute_pass(e, 1) launches a BATCH of n passes ahead of the caller — after a snapshot of the duals — and the
 // launch itself leaves the tracked bounds of all factors as they are at the end of every pass (one row per pass,
-// kernels.hip HIST_END / HIST_MID).  The following n - 1 calls of lpmp_compute_pass(e, 1) only advance a cursor, and
+// kernels.hpp HIST_END / HIST_MID).  The following n - 1 calls of lpmp_compute_pass(e, 1) only advance a cursor, and
 // lpmp_lower_bound returns the bound of the pass the caller is at (the sum of that row, in the order lpmp_lower_bound sums).
 // ANY other call settles first: if the caller stopped inside the batch the duals go back to the snapshot and exactly the
 // passes it asked for are run again (bit-identical: n joined passes equal n single ones).  So the speculation
@@ -1643,16 +1603,13 @@ static bool spec_start_batch(lpmp_engine* e, int depth) {
   const size_t nd = (size_t)e->plan->p.f_doff[e->plan->p.nf], nf = (size_t)e->plan->p.nf;
   // (an allocation that fails switches speculation OFF for this engine — the plain pass needs none of these buffers — instead
   // of making every lpmp_compute_pass(e, 1) fail on a model that solves fine without: snapshot = all duals + tracked bounds)
-  auto grow = [&](double*& p, size_t& cap, size_t want) -> bool {
-    if (want <= cap) return true;
+  auto grow = [&](DevBuf<double>& b, size_t want) -> bool {
+    if (want <= b.capacity()) return true;
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (p) { HIP_CHECK(hipFree(p)); p = nullptr; cap = 0; }
-    if (hipMalloc((void**)&p, want * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = want;
-    return true;
+    return b.try_alloc(want);
   };
-  if (!grow(sp.d_snap, sp.snap_cap, nd + nf) || !grow(sp.d_hist, sp.hist_cap, (size_t)(std::min(sp.max_depth, 32) - 1) * nf) ||
-      !grow(sp.d_hpart, sp.hpart_cap, (size_t)(std::min(sp.max_depth, 32) - 1) * 1024)) {
+  if (!grow(sp.d_snap, nd + nf) || !grow(sp.d_hist, (size_t)(std::min(sp.max_depth, 32) - 1) * nf) ||
+      !grow(sp.d_hpart, (size_t)(std::min(sp.max_depth, 32) - 1) * 1024)) {
     sp.release();
     sp.max_depth = 0;
     ++sp.alloc_failures;
@@ -1796,7 +1753,7 @@ static void ensure_primal(lpmp_engine* e) {
     for (int64_t m = 0; m < p.nm; ++m) if (touched[p.m_right[m]]) touched[p.m_left[m]] = 2;
     std::vector<int32_t> h(2 * (size_t)p.nf);
     for (size_t i = 0; i < h.size(); ++i) h[i] = writer[i];
-    HIP_CHECK(hipMalloc((void**)&e->d_pw_unary, std::max<size_t>(1, h.size()) * sizeof(int32_t)));
+    e->d_pw_unary.alloc(std::max<size_t>(1, h.size()));
     if (!h.empty()) h2d(e->d_pw_unary, h.data(), h.size() * sizeof(int32_t), e->stream);
   }
   for (int64_t f = 0; f < p.nf; ++f) if (p.updated[f]) touched[f] = 1;
@@ -1807,12 +1764,12 @@ static void ensure_primal(lpmp_engine* e) {
   prop.insert(prop.end(), rest.begin(), rest.end());
   e->n_plinks = (int64_t)prop.size();
   e->n_pinit = (int64_t)init.size();
-  HIP_CHECK(hipMalloc((void**)&e->d_primal, std::max<size_t>(1, 2 * (size_t)p.nf) * sizeof(int32_t)));
-  HIP_CHECK(hipMalloc((void**)&e->d_pcost, std::max<size_t>(1, (size_t)p.nf) * sizeof(double)));
-  HIP_CHECK(hipMalloc((void**)&e->d_pbad, sizeof(int)));
+  e->d_primal.alloc(std::max<size_t>(1, 2 * (size_t)p.nf));
+  e->d_pcost.alloc(std::max<size_t>(1, (size_t)p.nf));
+  e->d_pbad.alloc(1);
   e->h_pbad = (int*)(e->pinned + 8 * 1024 + 64);               // one flag (the block exists: a model is uploaded)
   if (!prop.empty()) {
-    HIP_CHECK(hipMalloc((void**)&e->d_plinks, prop.size() * sizeof(PrimalLink)));
+    e->d_plinks.alloc(prop.size());
     h2d(e->d_plinks, prop.data(), prop.size() * sizeof(PrimalLink), e->stream);
   }
   // every factor starts unset (init_primal), then only the touched ones are ever re-initialised
@@ -1822,7 +1779,7 @@ static void ensure_primal(lpmp_engine* e) {
     h2d(e->d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
   }
   if (!init.empty()) {
-    HIP_CHECK(hipMalloc((void**)&e->d_pinit, init.size() * sizeof(PrimalInit)));
+    e->d_pinit.alloc(init.size());
     h2d(e->d_pinit, init.data(), init.size() * sizeof(PrimalInit), e->stream);
   }
   e->primal_t = 0;
@@ -1962,7 +1919,7 @@ int lpmp_schedule_create_fused(lpmp_engine* e, int64_t n, const int32_t* factors
                              fuse != 0 && e->use_fused, s);
     check_generic_limits(e->plan->p, s);
     auto d = std::make_unique<DevSchedule>();
-    try { upload_schedule(s, *d, e->stream, false, e->plan->p.force_generic); } catch (...) { d->release(); throw; }
+    upload_schedule(s, *d, e->stream, false, e->plan->p.force_generic);
     e->custom.push_back(std::move(d));
     *id_out = (int)e->custom.size() - 1;
   });
@@ -1996,9 +1953,8 @@ int lpmp_schedule_info(lpmp_engine* e, int id, int64_t* n_levels, int64_t* n_lau
 }
 int lpmp_schedule_destroy(lpmp_engine* e, int id) {
   return guarded([&] {
-    DevSchedule& d = custom_schedule(e, id);
+    (void)custom_schedule(e, id);
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    d.release();
     e->custom[id].reset();
   });
 }
@@ -2088,7 +2044,7 @@ int lpmp_synchronize(lpmp_engine* e) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);                                  // after this call the (possibly borrowed) dual buffer holds the caller's state
     rows_flush(e);
-    if (e->rows && !e->own_dual) e->rows_stale = true;   // ... and the caller may write it: the rows are refreshed before the next pass
+    if (e->rows && !e->own_dual()) e->rows_stale = true;   // ... and the caller may write it: the rows are refreshed before the next pass
     HIP_CHECK(hipStreamSynchronize(e->stream));
     if (e->timing) e->drain_timing();
     check_chain(e);

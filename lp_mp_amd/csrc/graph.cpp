@@ -17,10 +17,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lpmp_engine.h"
+#include "engine_internal.h"
 #include "plan.hpp"
-
-extern "C" int lpmp_set_last_error(const char* msg);   // engine.cpp
 
 namespace lpmp {
 

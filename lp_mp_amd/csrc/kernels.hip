@@ -19,14 +19,12 @@
 #include <atomic>
 #include <type_traits>
 
-#include "plan.hpp"
+#include "kernels.hpp"
 
 namespace lpmp {
 
 #define LPMP_INF (__builtin_inf())
-constexpr int GEN_MAXD = 512;       // generic kernel: max dual size / message length held in LDS per wave
-constexpr int GEN_WAVES = 4;
-constexpr int GEN_ADAPTIVE_SENDS = 64;   // adaptive send rule: sends per updated factor whose improvements a wave keeps
+constexpr int GEN_WAVES = 4;         // (GEN_MAXD, GEN_ADAPTIVE_SENDS: kernels.hpp)
 
 // Tracked lower bounds.  lb[f] holds FactorContainer::LowerBound of factor f, or NaN when it has to be
 // recomputed.  A sweep kernel knows the bound of every factor it touches for free:
@@ -91,44 +89,9 @@ template <int A> __device__ __forceinline__ void st_lb(double* p, double v) {
 // for exactly as long, neither slower polls nor a read-modify-write publish changed it.  One process per device (what the
 // engine is built for) never has this; drivers that put several ranks on one device for smoke runs switch the
 // persistent launches off (bench.py; LPMP_NO_CHAIN=1 LPMP_NO_BLOCKED_PASSES=1).
-struct ChainArgs {
-  const int32_t* dep_off;    // [n_tickets + 1]
-  const int32_t* dep;        // predecessor tickets
-  int32_t* done;             // [n_tickets]: epoch of the run that completed the ticket
-  int32_t* next;             // ticket counter (zeroed before the launch)
-  int32_t* abort_flag;
-  const int32_t* tk_launch;  // [n_tickets]: launch (level x class range) the ticket belongs to
-  const int32_t* tk_block;   // [n_tickets]: block of records inside that launch
-  int32_t n_tickets;
-  int32_t epoch;
-  long long* trace;          // debugging (LPMP_CHAIN_TRACE): 8 slots of time stamps per ticket, 100 MHz; nullptr otherwise
-  // joined passes (engine.cpp rotation_chain) with per-pass lower bounds: row r = the tracked bounds of all factors as they
-  // are at the END OF PASS r + 1 of the call; a launch writes into the row its ChainLaunch::hist names (nullptr: no rows)
-  double* lb_hist; int64_t hist_stride;
-  // launches with CHAIN_LAUNCH_MAILBOX (chain_plan.cpp): rows of L granule pairs, see mailbox_put / mailbox_take
-  unsigned long long* mailbox;
-  // bound of every wait in ticks of s_memrealtime (100 MHz; engine.cpp: 20 s, LPMP_CHAIN_TIMEOUT_S).  Time, not a number of
-  // polls: a device shared by several processes (N ranks of a smoke run on one GPU) serves a poll an order of magnitude
-  // slower, and a count of polls that means seconds on an idle device was reached there by waits that were merely slow
-  long long timeout_ticks;
-  // PERIODIC ticket lists (the joined passes of lpmp_compute_pass(n), engine.cpp rotation_chain): the arrays above describe
-  // a TEMPLATE — prologue tickets [0, per_begin), ONE period of per_len tickets, epilogue — and the launch executes the
-  // period per_count times: ticket t of the launch is template ticket t - q * per_len of copy q = min((t - per_begin) /
-  // per_len, per_count - 1) (0 in the prologue); its launch is the template's + q * per_launch_shift (every copy is a group
-  // of as many steps later), its dependencies the template's + q * per_len, its bound row the template's + q * per_row_shift.
-  // per_len == 0: plain lists.  Host work and device memory of an n-pass launch are then independent of n.
-  int32_t per_begin, per_len, per_count, per_launch_shift, per_row_shift;
-  // rows of lb_hist the launch may write (an n-pass call has n - 1 seams): a W step of a periodic template carries a row
-  // even when, in a call that ends right behind it, it is the LAST step before T and has no seam behind it
-  int32_t hist_rows;
-  // ring > 0: done[] has `ring` slots, ticket t publishes {epoch, t / ring} into slot t % ring AFTER ticket t - ring has
-  // published there (one more dependency of t), and a waiter accepts any generation >= the one it needs
-  int32_t ring;
-};
-constexpr int CHAIN_GEN_BITS = 8;            // low bits of a ring slot: generation t / ring (< 256); the rest: the epoch
-// debugging (LPMP_LEVEL_TRACE, engine.cpp): time stamps of the first levels of a level-loop launch, 8 slots per level
+// (ChainArgs, ChainLaunch and HIST_*: kernels.hpp)
+// debugging (LPMP_LEVEL_TRACE, engine.cpp): time stamps of the first LEVEL_TRACE_MAX levels of a level-loop launch, 8 slots per level
 __device__ long long* g_level_trace = nullptr;
-constexpr int LEVEL_TRACE_MAX = 4000;
 __device__ __forceinline__ void level_stamp(int slot) {
   long long* p = g_level_trace;
   if (p && threadIdx.x == 0) { const long long l = p[0]; if (l < LEVEL_TRACE_MAX) p[8 + 8 * l + slot] = (long long)__builtin_amdgcn_s_memrealtime(); }
@@ -140,17 +103,6 @@ __device__ __forceinline__ void level_stamp_of(int slot, int tid) {   // the sam
 __device__ __forceinline__ void chain_stamp(const ChainArgs& ca, int ticket, int k) {
   if (ca.trace && threadIdx.x == 0) ca.trace[8 * (int64_t)ticket + k] = (long long)__builtin_amdgcn_s_memrealtime();
 }
-// one launch (a level x class range of records) as the chain kernels see it: absolute device pointers, so that tickets of
-// one persistent launch may come from several schedules (the joined passes of lpmp_compute_pass(n), engine.cpp)
-// pad: flags of the level loop (CHAIN_LAUNCH_LABEL_*), or for the joined passes of the dense chain kernel HIST_* | row << 2
-struct ChainLaunch { const Op* packets; const UpdRec* recs; const Op* ops; int64_t count; int32_t stride, pad; };
-// Which tracked bounds of a launch also go to a row of ChainArgs::lb_hist.  n joined passes are H, W, (K, W)^(n-1), T
-// (DESIGN.md 4): the state "after pass i" is never in memory as a whole — K_i holds the last receives of pass i AND the
-// first sends of pass i + 1 — but every factor's bound at that moment is known to exactly one record:
-//   HIST_END  (a W step)  the updated factor's bound at the end of the record (it is not touched again in this pass)
-//   HIST_MID  (a K step)  the updated factor's bound after its receives, before its sends, and the bound of every
-//                         pairwise factor it receives from, right after that receive
-constexpr int HIST_END = 1, HIST_MID = 2;
 // a wait gives up when it has lasted ChainArgs::timeout_ticks (the clock is first read after 1024 polls: short waits never
 // read it) or when another wait of the launch has given up
 __device__ __forceinline__ bool chain_wait_expired(const ChainArgs& ca, int spins, long long& t0, bool& own) {
@@ -1209,8 +1161,7 @@ sweep_dense_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__
 // form (side 0 on the staged transpose).  min is exact and order-free, so q — and with it every dual — is the same number bit for
 // bit (tests/test_shared_tables_gpu.py compares with the oracle on the expansion by np.array_equal).
 // LDS: the slabs of a lane group are private to its wave, so consecutive blocks of one wave need no workgroup barrier.
-struct ShTableDesc { int64_t off; int32_t d0, d1; };                 // a table of the pool: offset relative to the const base pointer, dims
-struct ShTabList { int32_t n; int32_t t[SHARED_MAX_TABLES]; };      // the tables of one launch (indices into the pool)
+struct ShTabList { int32_t n; int32_t t[SHARED_MAX_TABLES]; };      // the tables of one launch (indices into the pool of ShTableDesc)
 template <int L, bool NT>
 __global__ void __launch_bounds__(256)
 sweep_shared_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
@@ -1341,7 +1292,6 @@ chain_generic_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, dou
 //   labeling-list records run with one lane per op (label_ops_body), the others on the generic body (one wave).
 constexpr int LEVEL_LOOP_AHEAD = 8;
 constexpr int LL_WAVES = 2;                        // computing waves of level_loop_kernel<1> (+ one that runs ahead)
-constexpr int CHAIN_LAUNCH_LABEL_OPS_DEV = 1, CHAIN_LAUNCH_LABEL_PAIRED_DEV = 2;   // ChainLaunch::pad (plan.hpp CHAIN_LAUNCH_LABEL_*)
 
 // Labeling-list records with one LANE PER OP (chain_plan.cpp marks the launches: vector factors whose ops are all labeling
 // messages with the factor on the left, at most 8 receives with distinct peers and 8 sends with distinct peers, message
@@ -1573,7 +1523,7 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
       ChainLaunch next; next.packets = nullptr; next.recs = nullptr; next.ops = nullptr; next.count = 0; next.stride = 0; next.pad = 0;
       if (ar + 1 < n_launches) next = launches[ar + 1];
       // --- issue: records of level ar
-      const bool r_ok = have_lnr && ar < n_launches && plain_rule && (lnr.pad & CHAIN_LAUNCH_LABEL_OPS_DEV) && lnr.count <= LL_STAGE_RECS;
+      const bool r_ok = have_lnr && ar < n_launches && plain_rule && (lnr.pad & CHAIN_LAUNCH_LABEL_OPS) && lnr.count <= LL_STAGE_RECS;
       double2_t rr[3] = {double2_t{0.0, 0.0}, double2_t{0.0, 0.0}, double2_t{0.0, 0.0}};
       if (r_ok && lane < lnr.count) { const double2_t* src = reinterpret_cast<const double2_t*>(lnr.recs + lane); rr[0] = src[0]; rr[1] = src[1]; rr[2] = src[2]; }
       // --- issue: ops of level ao (its records are in LDS since the last iteration)
@@ -1650,7 +1600,7 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
         const int la = l + LEVEL_LOOP_AHEAD;         // ... and, further ahead, the touch of everything a level that will NOT be staged reads
         ChainLaunch ln; ln.count = 0; ln.pad = 0;
         if (la < n_launches) ln = launches[la];
-        if (la < n_launches && !(plain_rule && (ln.pad & CHAIN_LAUNCH_LABEL_OPS_DEV) && ln.count <= LL_STAGE_RECS)) {
+        if (la < n_launches && !(plain_rule && (ln.pad & CHAIN_LAUNCH_LABEL_OPS) && ln.count <= LL_STAGE_RECS)) {
           for (int64_t i = lane; i < ln.count; i += 64) {
             const UpdRec r = ln.recs[i];
             double acc = __hip_atomic_load(dual + r.dual_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1671,10 +1621,10 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
         if (sl.count >= 0) { ln.packets = nullptr; ln.recs = nullptr; ln.ops = nullptr; ln.count = sl.count; ln.stride = 0; ln.pad = sl.pad[0]; }
         else ln = launches[l];
         if (sl.count >= 0) {                         // records, ops and match tables from LDS
-          if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED_DEV) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true, true>(ln, first, dual, tabs, lb, D[wave], S[wave], &sl); }
+          if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true, true>(ln, first, dual, tabs, lb, D[wave], S[wave], &sl); }
           else { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body_staged<ACC_WG>(sl, first, dual, lb, D[wave], S[wave], RS[wave]); }
-        } else if ((ln.pad & CHAIN_LAUNCH_LABEL_OPS_DEV) && plain_rule) {
-          if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED_DEV) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true>(ln, first, dual, tabs, lb, D[wave], S[wave]); }
+        } else if ((ln.pad & CHAIN_LAUNCH_LABEL_OPS) && plain_rule) {
+          if (ln.pad & CHAIN_LAUNCH_LABEL_PAIRED) { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, true>(ln, first, dual, tabs, lb, D[wave], S[wave]); }
           else { for (int64_t first = 8 * wave; first < ln.count; first += 8 * LL_WAVES) label_ops_body<ACC_WG, false>(ln, first, dual, tabs, lb, D[wave], S[wave]); }
         } else if (wave == 0) {
           const int64_t nblk = (ln.count + C::FPB - 1) / C::FPB;
@@ -2267,8 +2217,6 @@ sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ du
 // -------------------------------------------------------------------------------------------------
 // Lower bound (reference LP::LowerBound, LP_MP.h:1507-1518): per-factor bound, then a fixed-order sum.
 // -------------------------------------------------------------------------------------------------
-struct LbRec { int64_t dual_off; int64_t const_off; int32_t d0, d1; int32_t kind_flags; int32_t pad; };
-
 // one wave per factor, any kind
 __global__ void __launch_bounds__(256)
 factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
@@ -2468,7 +2416,7 @@ __global__ void synth_fill_kernel(double* __restrict__ out, int64_t n, uint64_t 
   }
 }
 
-// ---- launch wrappers (called from engine.cpp) -----------------------------------------------------
+// ---- launch wrappers (declared in kernels.hpp, called from engine.cpp) -----------------------------------------------------
 void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, const int32_t* tabs,
                   double* lb, int32_t* primal, const int32_t* pw_unary, int64_t first, int64_t count, int flags, hipStream_t s) {
   if (count <= 0) return;
@@ -2483,56 +2431,73 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
   }
 }
 
+// The ONE table kernel class -> template arguments of the packed kernels: f(family, integral_constant<int, L>, bool_constant<VAR>)
+// for a class that has a label width L (VAR: its run-time-dims form), and f's answer; false for every other class.  A wrapper
+// instantiates a kernel only in the `if constexpr` branch of the families it serves, so the kernels that exist are exactly
+// the ones its branches name.
+enum Family { FAM_DENSE, FAM_POTTS, FAM_PW, FAM_SHARED };
+template <Family F, bool VAR, class Fn>
+static bool with_width(int width, Fn&& f) {
+  using Fam = std::integral_constant<Family, F>;
+  switch (width) {
+    case 32: return f(Fam{}, std::integral_constant<int, 32>{}, std::bool_constant<VAR>{});
+    case 16: return f(Fam{}, std::integral_constant<int, 16>{}, std::bool_constant<VAR>{});
+    case 8: return f(Fam{}, std::integral_constant<int, 8>{}, std::bool_constant<VAR>{});
+    case 4: return f(Fam{}, std::integral_constant<int, 4>{}, std::bool_constant<VAR>{});
+    default: return false;
+  }
+}
+template <class Fn>
+static bool with_class(int kclass, Fn&& f) {
+  const int w = kc_width(kclass);
+  if (kclass >= KC_DENSE_4 && kclass <= KC_DENSE_32) return with_width<FAM_DENSE, false>(w, f);
+  if (kclass >= KC_POTTS_4 && kclass <= KC_POTTS_32) return with_width<FAM_POTTS, false>(w, f);
+  if (kclass >= KC_DENSE_V4 && kclass <= KC_DENSE_V32) return with_width<FAM_DENSE, true>(w, f);
+  if (kclass >= KC_POTTS_V4 && kclass <= KC_POTTS_V32) return with_width<FAM_POTTS, true>(w, f);
+  if (kc_is_pw(kclass)) return with_width<FAM_PW, false>(w, f);
+  if (kc_is_shared(kclass)) return with_width<FAM_SHARED, true>(w, f);   // (dims from the table descriptors)
+  return false;
+}
+// receives in flight per lane group of the dense kernels: 2 at 16 / 32 labels (1 and 4 measured slower on C3), 4 below
+constexpr int recv_in_flight(int L) { return L >= 16 ? 2 : 4; }
+
+// compute units of the CURRENT device (a process may hold engines on several devices): asked once, cached per device ordinal
+// (engines on several host threads share the cache: relaxed atomics, every thread would store the same value).  di: the cache slot.
+static int device_cu_count(int& di) {
+  static std::atomic<int> n_cu_of[64];
+  int dev = 0; (void)hipGetDevice(&dev);
+  di = dev >= 0 && dev < 64 ? dev : 0;
+  int n_cu = n_cu_of[di].load(std::memory_order_relaxed);
+  if (n_cu == 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; n_cu = v; n_cu_of[di].store(v, std::memory_order_relaxed); }
+  return n_cu;
+}
+
+// Returns false when the class has no packed kernel for the request: an unknown class, and on the pairwise classes the
+// residual rule or a launch without packets (stride <= 0).
 bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
                          double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s) {
   if (count <= 0) return true;
   auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
   const bool nt = (flags & SWEEP_NT) != 0;
-  if (kc_is_pw(kclass)) {
-    // (the residual rule recomputes the min-marginals after every send: the op-by-op generic kernel does that)
-    if ((flags & SWEEP_RESIDUAL) || stride <= 0) return false;
-#define PWK_LAUNCH(LL) hipLaunchKernelGGL((sweep_pairwise_pk_kernel<LL>), blocks(256 / DenseCfg<LL>::G), dim3(256), 0, s, packets, dual, cdata, lb, count, stride)
-    switch (kclass) {
-      case KC_PW_32: PWK_LAUNCH(32); return true;
-      case KC_PW_16: PWK_LAUNCH(16); return true;
-      case KC_PW_8: PWK_LAUNCH(8); return true;
-      default: PWK_LAUNCH(4); return true;
-    }
-#undef PWK_LAUNCH
-  }
-#define PK_LAUNCH1(LL, KK, NTT) hipLaunchKernelGGL((sweep_dense_pk_kernel<LL, KK, false, NTT>), blocks(256 / DenseCfg<LL>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags)
-#define PK_LAUNCH(LL, KK) do { if (nt) PK_LAUNCH1(LL, KK, true); else PK_LAUNCH1(LL, KK, false); } while (0)
-  switch (kclass) {
-    // receives in flight per lane group: 2 at 16 / 32 labels (1 and 4 measured slower on C3), 4 below
-    case KC_DENSE_32: PK_LAUNCH(32, 2); return true;
-    case KC_DENSE_16: PK_LAUNCH(16, 2); return true;
-    case KC_DENSE_8: PK_LAUNCH(8, 4); return true;
-    case KC_DENSE_4: PK_LAUNCH(4, 4); return true;
-#define PPK_LAUNCH1(LL, NTT) hipLaunchKernelGGL((sweep_potts_pk_kernel<LL, false, NTT>), blocks(256 / LL), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags)
-#define PPK_LAUNCH(LL) do { if (nt) PPK_LAUNCH1(LL, true); else PPK_LAUNCH1(LL, false); } while (0)
-    case KC_POTTS_32: PPK_LAUNCH(32); return true;
-    case KC_POTTS_16: PPK_LAUNCH(16); return true;
-    case KC_POTTS_8: PPK_LAUNCH(8); return true;
-    case KC_POTTS_4: PPK_LAUNCH(4); return true;
-#undef PPK_LAUNCH
-#undef PPK_LAUNCH1
-// (run-time dims: rows are not line-aligned, consecutive 8-B loads share lines — non-temporal loads cost 9 % there)
-#define VPK_LAUNCH(LL, KK) hipLaunchKernelGGL((sweep_dense_pk_kernel<LL, KK, true, false>), blocks(256 / DenseCfg<LL>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags)
-    case KC_DENSE_V32: VPK_LAUNCH(32, 2); return true;
-    case KC_DENSE_V16: VPK_LAUNCH(16, 2); return true;
-    case KC_DENSE_V8: VPK_LAUNCH(8, 4); return true;
-    case KC_DENSE_V4: VPK_LAUNCH(4, 4); return true;
-#undef VPK_LAUNCH
-#define VPPK_LAUNCH(LL) hipLaunchKernelGGL((sweep_potts_pk_kernel<LL, true, false>), blocks(256 / LL), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags)
-    case KC_POTTS_V32: VPPK_LAUNCH(32); return true;
-    case KC_POTTS_V16: VPPK_LAUNCH(16); return true;
-    case KC_POTTS_V8: VPPK_LAUNCH(8); return true;
-    case KC_POTTS_V4: VPPK_LAUNCH(4); return true;
-#undef VPPK_LAUNCH
-    default: return false;
-  }
-#undef PK_LAUNCH
-#undef PK_LAUNCH1
+  return with_class(kclass, [&](auto fam, auto width, auto var) {
+    constexpr Family F = decltype(fam)::value; constexpr int L = decltype(width)::value; constexpr bool VAR = decltype(var)::value;
+    if constexpr (F == FAM_PW) {
+      // (the residual rule recomputes the min-marginals after every send: the op-by-op generic kernel does that)
+      if ((flags & SWEEP_RESIDUAL) || stride <= 0) return false;
+      hipLaunchKernelGGL((sweep_pairwise_pk_kernel<L>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, dual, cdata, lb, count, stride);
+      return true;
+    } else if constexpr (F == FAM_DENSE) {
+      constexpr int K = recv_in_flight(L);
+      // (run-time dims: rows are not line-aligned, consecutive 8-B loads share lines — non-temporal loads cost 9 % there)
+      if constexpr (!VAR) if (nt) { hipLaunchKernelGGL((sweep_dense_pk_kernel<L, K, false, true>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags); return true; }
+      hipLaunchKernelGGL((sweep_dense_pk_kernel<L, K, VAR, false>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags);
+      return true;
+    } else if constexpr (F == FAM_POTTS) {
+      if constexpr (!VAR) if (nt) { hipLaunchKernelGGL((sweep_potts_pk_kernel<L, false, true>), blocks(256 / L), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags); return true; }
+      hipLaunchKernelGGL((sweep_potts_pk_kernel<L, VAR, false>), blocks(256 / L), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags);
+      return true;
+    } else return false;   // (the shared classes: launch_sweep_shared)
+  });
 }
 
 // shared classes: a persistent grid (what is resident at once, at most one workgroup per block of records); dynamic LDS = the
@@ -2542,14 +2507,10 @@ static void launch_shared_one(const Op* packets, const UpdRec* recs, const Op* o
                               int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const ShTabList& list, hipStream_t s) {
   auto k = sweep_shared_pk_kernel<L, NT>;
   const size_t lds = (size_t)2 * (list.n > 0 ? list.n : 1) * L * L * sizeof(double);
-  // compute units of the device and resident workgroups per CU by table count: asked once, cached per device ordinal (engines on
-  // several host threads share the caches: relaxed atomics, every thread would store the same value)
-  static std::atomic<int> n_cu_of[64];
+  // resident workgroups per CU by table count: asked once, cached like the CU count
   static std::atomic<int> per_cu_of[64][SHARED_MAX_TABLES + 1];
-  int dev = 0; (void)hipGetDevice(&dev);
-  const int di = dev >= 0 && dev < 64 ? dev : 0, ti = list.n > 0 && list.n <= SHARED_MAX_TABLES ? list.n : 0;
-  int n_cu = n_cu_of[di].load(std::memory_order_relaxed);
-  if (n_cu == 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; n_cu = v; n_cu_of[di].store(v, std::memory_order_relaxed); }
+  int di = 0;
+  const int n_cu = device_cu_count(di), ti = list.n > 0 && list.n <= SHARED_MAX_TABLES ? list.n : 0;
   int per_cu = per_cu_of[di][ti].load(std::memory_order_relaxed);
   if (per_cu == 0) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, lds) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
@@ -2559,109 +2520,83 @@ static void launch_shared_one(const Op* packets, const UpdRec* recs, const Op* o
   const int64_t n_blocks = (count + GPB - 1) / GPB, cap = (int64_t)n_cu * per_cu;
   hipLaunchKernelGGL(k, dim3((unsigned)(n_blocks < cap ? n_blocks : cap)), dim3(256), lds, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags, desc, list);
 }
+// Returns false for a class that is not a shared one, a launch without packets or indirect records (stride == 0), a table count out of
+// range or no descriptors.
 bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
-                         double* lb, int32_t* primal, int64_t count, int flags, const void* desc, const int32_t* tabs, int n_tabs, hipStream_t s) {
+                         double* lb, int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const int32_t* tabs, int n_tabs, hipStream_t s) {
   if (count <= 0) return true;
   if (!kc_is_shared(kclass) || stride == 0 || n_tabs < 0 || n_tabs > SHARED_MAX_TABLES || !desc) return false;
   ShTabList list; list.n = n_tabs;
   for (int q = 0; q < SHARED_MAX_TABLES; ++q) list.t[q] = q < n_tabs ? tabs[q] : 0;
-  const ShTableDesc* d = static_cast<const ShTableDesc*>(desc);
   const bool nt = (flags & SWEEP_NT) != 0;
-#define SH_LAUNCH(LL) do { if (nt) launch_shared_one<LL, true>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, d, list, s); \
-                           else launch_shared_one<LL, false>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, d, list, s); } while (0)
-  switch (kclass) {
-    case KC_SHARED_32: SH_LAUNCH(32); return true;
-    case KC_SHARED_16: SH_LAUNCH(16); return true;
-    case KC_SHARED_8: SH_LAUNCH(8); return true;
-    default: SH_LAUNCH(4); return true;
-  }
-#undef SH_LAUNCH
+  return with_class(kclass, [&](auto fam, auto width, auto) {
+    if constexpr (decltype(fam)::value == FAM_SHARED) {
+      constexpr int L = decltype(width)::value;
+      if (nt) launch_shared_one<L, true>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, desc, list, s);
+      else launch_shared_one<L, false>(packets, recs, ops, stride, dual, cdata, lb, primal, count, flags, desc, list, s);
+      return true;
+    } else return false;
+  });
 }
 
 // chain executor: one persistent launch for a deep single-class schedule; grid = what is resident at once (more
 // workgroups would only queue behind the running ones).  Returns false for a class without a chain kernel.
 template <class K>
 static unsigned chain_grid(K kernel, int n_tickets, int threads = 256) {
-  // compute units of the CURRENT device (a process may hold engines on several devices): cached per ordinal
-  static int n_cu_of[64] = {0};
-  int dev = 0; (void)hipGetDevice(&dev);
-  int& n_cu = n_cu_of[dev >= 0 && dev < 64 ? dev : 0];
-  if (n_cu == 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; n_cu = v; }
+  int di = 0;
+  const int n_cu = device_cu_count(di);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
   const long cap = (long)n_cu * per_cu;
   return (unsigned)(n_tickets < cap ? n_tickets : cap);
 }
 void debug_set_level_trace(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_level_trace), &p, sizeof(p)); }
-bool launch_level_loop(int kclass, int flags, const void* launches, int n_launches, double* dual, const double* cdata,
+bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launches, double* dual, const double* cdata,
                        const int32_t* tabs, double* lb, hipStream_t s) {
-  const ChainLaunch* ln = static_cast<const ChainLaunch*>(launches);
   if (kclass == KC_SMALL) hipLaunchKernelGGL(level_loop_kernel<1>, dim3(1), dim3(64 * (LL_WAVES + 1)), 0, s, ln, n_launches, dual, cdata, tabs, lb, flags);
   else if (kclass == KC_GENERIC) hipLaunchKernelGGL(level_loop_kernel<64>, dim3(1), dim3(GenCtx<64>::THREADS), 0, s, ln, n_launches, dual, cdata, tabs, lb, flags);
   else return false;
   return true;
 }
-bool launch_chain(int kclass, int flags, const void* chain_args, const void* launches, double* dual, const double* cdata,
+bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
                   const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s) {
-  const ChainArgs ca = *static_cast<const ChainArgs*>(chain_args);
-  const ChainLaunch* ln = static_cast<const ChainLaunch*>(launches);
-  const bool nt = (flags & SWEEP_NT) != 0;
-#define CHAIN_LAUNCH2(LL, KK, VV, NTT, MM) do { auto k = chain_dense_pk_kernel<LL, KK, VV, NTT, MM>; \
-    hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); } while (0)
-#define CHAIN_LAUNCH1(LL, KK, VV, NTT) CHAIN_LAUNCH2(LL, KK, VV, NTT, false)
-  // (a mailbox chain is a deep schedule: latency-bound, no streaming variant)
-#define CHAIN_LAUNCH(LL, KK) do { if (ca.mailbox) CHAIN_LAUNCH2(LL, KK, false, false, true); else if (nt) CHAIN_LAUNCH1(LL, KK, false, true); else CHAIN_LAUNCH1(LL, KK, false, false); } while (0)
-#define CHAIN_LAUNCH_V(LL, KK) do { if (ca.mailbox) CHAIN_LAUNCH2(LL, KK, true, false, true); else CHAIN_LAUNCH1(LL, KK, true, false); } while (0)
-  switch (kclass) {
-    case KC_GENERIC: { auto k = chain_generic_kernel<64>; hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, GenCtx<64>::THREADS)), dim3(GenCtx<64>::THREADS), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; }
-    case KC_SMALL: { auto k = chain_generic_kernel<1>; hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, GenCtx<1>::THREADS)), dim3(GenCtx<1>::THREADS), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; }
-    case KC_DENSE_32: CHAIN_LAUNCH(32, 2); return true;
-    case KC_DENSE_16: CHAIN_LAUNCH(16, 2); return true;
-    case KC_DENSE_8: CHAIN_LAUNCH(8, 4); return true;
-    case KC_DENSE_4: CHAIN_LAUNCH(4, 4); return true;
-    case KC_DENSE_V32: CHAIN_LAUNCH_V(32, 2); return true;
-    case KC_DENSE_V16: CHAIN_LAUNCH_V(16, 2); return true;
-    case KC_DENSE_V8: CHAIN_LAUNCH_V(8, 4); return true;
-    case KC_DENSE_V4: CHAIN_LAUNCH_V(4, 4); return true;
-#define CHAIN_POTTS2(LL, VV, MM) do { auto k = chain_potts_pk_kernel<LL, VV, MM>; \
-    hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); } while (0)
-#define CHAIN_POTTS(LL, VV) CHAIN_POTTS2(LL, VV, false)
-#define CHAIN_POTTS_X(LL) do { if (ca.mailbox) CHAIN_POTTS2(LL, false, true); else CHAIN_POTTS2(LL, false, false); } while (0)
-#define CHAIN_POTTS_XV(LL) do { if (ca.mailbox) CHAIN_POTTS2(LL, true, true); else CHAIN_POTTS2(LL, true, false); } while (0)
-    case KC_POTTS_32: CHAIN_POTTS_X(32); return true;
-    case KC_POTTS_16: CHAIN_POTTS_X(16); return true;
-    case KC_POTTS_8: CHAIN_POTTS_X(8); return true;
-    case KC_POTTS_4: CHAIN_POTTS_X(4); return true;
-    case KC_POTTS_V32: CHAIN_POTTS_XV(32); return true;
-    case KC_POTTS_V16: CHAIN_POTTS_XV(16); return true;
-    case KC_POTTS_V8: CHAIN_POTTS_XV(8); return true;
-    case KC_POTTS_V4: CHAIN_POTTS_XV(4); return true;
-#undef CHAIN_POTTS_X
-#undef CHAIN_POTTS_XV
-#undef CHAIN_POTTS
-#undef CHAIN_POTTS2
-    default: return false;
-  }
-#undef CHAIN_LAUNCH
-#undef CHAIN_LAUNCH_V
-#undef CHAIN_LAUNCH1
-#undef CHAIN_LAUNCH2
+  const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr;
+  auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
+  auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
+  if (kclass == KC_GENERIC) return generic(chain_generic_kernel<64>, GenCtx<64>::THREADS);
+  if (kclass == KC_SMALL) return generic(chain_generic_kernel<1>, GenCtx<1>::THREADS);
+  return with_class(kclass, [&](auto fam, auto width, auto var) {
+    constexpr Family F = decltype(fam)::value; constexpr int L = decltype(width)::value; constexpr bool VAR = decltype(var)::value;
+    // the mailbox form is an instantiation of its own (the joined passes of the headline grid lost 8 % with the mailbox fields in
+    // their registers: dense_pk_body), and a mailbox chain is a deep schedule: latency-bound, no streaming variant; the
+    // run-time-dims forms have none either (launch_sweep_packed)
+    if constexpr (F == FAM_DENSE) {
+      constexpr int K = recv_in_flight(L);
+      if (mailbox) return packed(chain_dense_pk_kernel<L, K, VAR, false, true>);
+      if constexpr (!VAR) if (nt) return packed(chain_dense_pk_kernel<L, K, false, true, false>);
+      return packed(chain_dense_pk_kernel<L, K, VAR, false, false>);
+    } else if constexpr (F == FAM_POTTS) {
+      return mailbox ? packed(chain_potts_pk_kernel<L, VAR, true>) : packed(chain_potts_pk_kernel<L, VAR, false>);
+    } else return false;   // (pairwise and shared classes have no chain form: kc_chain_capable)
+  });
 }
 
-void launch_factor_lb(const void* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s) {
+void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(factor_lb_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, out, count);
+  hipLaunchKernelGGL(factor_lb_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, count);
 }
 
-bool launch_dense_lb(int L, const void* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s) {
+// the streaming bound of square dense factors of 8 / 16 / 32 labels; false for every other L
+bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s) {
   if (count <= 0) return true;
-  auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
-  switch (L) {
-    case 32: hipLaunchKernelGGL(dense_lb_kernel<32>, blocks(256 / DenseCfg<32>::G), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, out, first, count); return true;
-    case 16: hipLaunchKernelGGL(dense_lb_kernel<16>, blocks(256 / DenseCfg<16>::G), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, out, first, count); return true;
-    case 8: hipLaunchKernelGGL(dense_lb_kernel<8>, blocks(256 / DenseCfg<8>::G), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, out, first, count); return true;
-    default: return false;
-  }
+  return with_width<FAM_DENSE, false>(L, [&](auto, auto width, auto) {
+    constexpr int W = decltype(width)::value;
+    if constexpr (W >= 8) {
+      constexpr int per_block = 256 / DenseCfg<W>::G;
+      hipLaunchKernelGGL(dense_lb_kernel<W>, dim3((unsigned)((count + per_block - 1) / per_block)), dim3(256), 0, s, recs, dual, cdata, out, first, count);
+      return true;
+    } else return false;
+  });
 }
 
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s) {
@@ -2669,9 +2604,9 @@ void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigne
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(lb_collect_stale_kernel, dim3((unsigned)blocks), dim3(256), 0, s, lb, n, list, counter);
 }
-void launch_factor_lb_list(const void* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s) {
+void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(factor_lb_list_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, out, list, count);
+  hipLaunchKernelGGL(factor_lb_list_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, list, count);
 }
 
 static dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -2684,8 +2619,8 @@ void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(primal_check_kernel, blocks256(n), dim3(256), 0, s, links, n, primal, bad);
 }
-void launch_primal_cost(const void* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s) {
-  if (count > 0) hipLaunchKernelGGL(primal_cost_kernel, blocks256(count), dim3(256), 0, s, (const LbRec*)recs, dual, cdata, primal, out, count);
+void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s) {
+  if (count > 0) hipLaunchKernelGGL(primal_cost_kernel, blocks256(count), dim3(256), 0, s, recs, dual, cdata, primal, out, count);
 }
 
 // ---- rows layout (engine.cpp): a dense pairwise factor's table and its two message vectors in ONE contiguous row ----------
@@ -2694,7 +2629,6 @@ void launch_primal_cost(const void* recs, const double* dual, const double* cdat
 // arrays stay the boundary's format (serialize_dual order); these copies move between the two.
 //   what 0: build a row (table from the packed constants, vectors from the packed duals)
 //   what 1: packed duals -> rows (vectors only)      what 2: rows -> packed duals (vectors only)
-struct RowRec { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
 __global__ void __launch_bounds__(256)
 rows_copy_kernel(const RowRec* __restrict__ recs, int64_t n, const double* __restrict__ cdata, double* __restrict__ dual, double* __restrict__ rows, int what) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2720,9 +2654,9 @@ void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStrea
   if (n > 0) hipLaunchKernelGGL(shared_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cells, n, cdata);
 }
 
-void launch_rows_copy(const void* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s) {
+void launch_rows_copy(const RowRec* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, (const RowRec*)recs, n, cdata, dual, rows, what);
+  hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, cdata, dual, rows, what);
 }
 
 void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s) {
@@ -2735,8 +2669,5 @@ void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hi
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, out, n, seed, first);
 }
-
-int generic_max_dual() { return GEN_MAXD; }
-int generic_max_adaptive_sends() { return GEN_ADAPTIVE_SENDS; }
 
 }  // namespace lpmp

@@ -1,0 +1,102 @@
+// kernels.hpp — the interface between engine.cpp (host) and kernels.hip (device code and its launch wrappers): the one
+// definition of every struct, constant and prototype that crosses the launch boundary.  Included by those two files only;
+// the planner (plan.hpp and its sources) stays free of HIP.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "plan.hpp"
+
+namespace lpmp {
+
+// ---- limits of the generic kernels (engine.cpp checks every schedule against them) -----------------------------------
+constexpr int GEN_MAXD = 512;            // generic kernel: max dual size / message length held in LDS per wave
+constexpr int GEN_ADAPTIVE_SENDS = 64;   // adaptive send rule: sends per updated factor whose improvements a wave keeps
+
+// ---- chain executor (kernels.hip: dependent levels inside one persistent launch) -------------------------------------
+struct ChainArgs {
+  const int32_t* dep_off;    // [n_tickets + 1]
+  const int32_t* dep;        // predecessor tickets
+  int32_t* done;             // [n_tickets]: epoch of the run that completed the ticket
+  int32_t* next;             // ticket counter (zeroed before the launch)
+  int32_t* abort_flag;
+  const int32_t* tk_launch;  // [n_tickets]: launch (level x class range) the ticket belongs to
+  const int32_t* tk_block;   // [n_tickets]: block of records inside that launch
+  int32_t n_tickets;
+  int32_t epoch;
+  long long* trace;          // debugging (LPMP_CHAIN_TRACE): 8 slots of time stamps per ticket, 100 MHz; nullptr otherwise
+  // joined passes (engine.cpp rotation_chain) with per-pass lower bounds: row r = the tracked bounds of all factors as they
+  // are at the END OF PASS r + 1 of the call; a launch writes into the row its ChainLaunch::hist names (nullptr: no rows)
+  double* lb_hist; int64_t hist_stride;
+  // launches with CHAIN_LAUNCH_MAILBOX (chain_plan.cpp): rows of L granule pairs, see mailbox_put / mailbox_take
+  unsigned long long* mailbox;
+  // bound of every wait in ticks of s_memrealtime (100 MHz; engine.cpp: 20 s, LPMP_CHAIN_TIMEOUT_S).  Time, not a number of
+  // polls: a device shared by several processes (N ranks of a smoke run on one GPU) serves a poll an order of magnitude
+  // slower, and a count of polls that means seconds on an idle device was reached there by waits that were merely slow
+  long long timeout_ticks;
+  // PERIODIC ticket lists (the joined passes of lpmp_compute_pass(n), engine.cpp rotation_chain): the arrays above describe
+  // a TEMPLATE — prologue tickets [0, per_begin), ONE period of per_len tickets, epilogue — and the launch executes the
+  // period per_count times: ticket t of the launch is template ticket t - q * per_len of copy q = min((t - per_begin) /
+  // per_len, per_count - 1) (0 in the prologue); its launch is the template's + q * per_launch_shift (every copy is a group
+  // of as many steps later), its dependencies the template's + q * per_len, its bound row the template's + q * per_row_shift.
+  // per_len == 0: plain lists.  Host work and device memory of an n-pass launch are then independent of n.
+  int32_t per_begin, per_len, per_count, per_launch_shift, per_row_shift;
+  // rows of lb_hist the launch may write (an n-pass call has n - 1 seams): a W step of a periodic template carries a row
+  // even when, in a call that ends right behind it, it is the LAST step before T and has no seam behind it
+  int32_t hist_rows;
+  // ring > 0: done[] has `ring` slots, ticket t publishes {epoch, t / ring} into slot t % ring AFTER ticket t - ring has
+  // published there (one more dependency of t), and a waiter accepts any generation >= the one it needs
+  int32_t ring;
+};
+constexpr int CHAIN_GEN_BITS = 8;            // low bits of a ring slot: generation t / ring (< 256); the rest: the epoch
+constexpr int CHAIN_ABORT_WORDS = 16;        // abort word + what the first wait that gave up was waiting for (kernels.hip, chain_abort)
+// debugging (LPMP_LEVEL_TRACE, engine.cpp): time stamps of the first LEVEL_TRACE_MAX levels of a level-loop launch, 8 slots per level
+constexpr int LEVEL_TRACE_MAX = 4000;
+// one launch (a level x class range of records) as the chain kernels see it: absolute device pointers, so that tickets of
+// one persistent launch may come from several schedules (the joined passes of lpmp_compute_pass(n), engine.cpp)
+// pad: flags of the level loop (CHAIN_LAUNCH_LABEL_*), or for the joined passes of the dense chain kernel HIST_* | row << 2
+struct ChainLaunch { const Op* packets; const UpdRec* recs; const Op* ops; int64_t count; int32_t stride, pad; };
+static_assert(sizeof(ChainLaunch) == 40, "ChainLaunch layout");
+// Which tracked bounds of a launch also go to a row of ChainArgs::lb_hist.  n joined passes are H, W, (K, W)^(n-1), T
+// (DESIGN.md 4): the state "after pass i" is never in memory as a whole — K_i holds the last receives of pass i AND the
+// first sends of pass i + 1 — but every factor's bound at that moment is known to exactly one record:
+//   HIST_END  (a W step)  the updated factor's bound at the end of the record (it is not touched again in this pass)
+//   HIST_MID  (a K step)  the updated factor's bound after its receives, before its sends, and the bound of every
+//                         pairwise factor it receives from, right after that receive
+constexpr int HIST_END = 1, HIST_MID = 2;
+
+// ---- records of the other kernels --------------------------------------------------------------------------------------
+// shared classes: a table of the pool — offset relative to the const base pointer, dims
+struct ShTableDesc { int64_t off; int32_t d0, d1; };
+// lower bound / primal cost of one factor (reference LP::LowerBound, LP_MP.h:1507-1518), in factor order
+struct LbRec { int64_t dual_off; int64_t const_off; int32_t d0, d1; int32_t kind_flags; int32_t pad; };
+// rows layout: one dense pairwise factor's place in the packed arrays and in the rows (kernels.hip, rows_copy_kernel)
+struct RowRec { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
+
+// ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
+// The bool ones return false when there is no kernel for the request (each says when, at its definition).
+void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, const int32_t* tabs,
+                  double* lb, int32_t* primal, const int32_t* pw_unary, int64_t first, int64_t count, int flags, hipStream_t s);
+bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
+                         double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s);
+bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
+                         double* lb, int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const int32_t* tabs, int n_tabs, hipStream_t s);
+bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s);
+bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n_launches, double* dual, const double* cdata,
+                       const int32_t* tabs, double* lb, hipStream_t s);
+void debug_set_level_trace(long long* p);
+void launch_primal_init(const PrimalInit* list, int64_t n, int32_t* primal, hipStream_t s);
+void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal, hipStream_t s);
+void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
+void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s);
+void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);
+void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s);
+void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s);
+bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s);
+void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s);
+void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hipStream_t s);
+void launch_rows_copy(const RowRec* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s);
+void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStream_t s);
+
+}  // namespace lpmp

@@ -83,7 +83,7 @@ RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t
           if (d.first == 1) ri.reach = std::max(ri.reach, (d.second + 0.5) / nbp - (b + 0.5) / nbs);
     }
   }
-  {   // coverage of the per-pass bound rows (kernels.hip HIST_END / HIST_MID)
+  {   // coverage of the per-pass bound rows (kernels.hpp HIST_END / HIST_MID)
     std::vector<uint8_t> cov((size_t)nf, 0);
     for (int64_t i = w.begin; i < w.end; ++i) cov[fb.recs[i].factor] = 1;
     for (int64_t i = k.begin; i < k.end; ++i) {
@@ -385,7 +385,7 @@ std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, i
     // per-pass bound rows (only written when the launch is given rows: speculative batches): W of pass i (step 2 i + 1)
     // and K after pass i (step 2 i + 2) write row i, for the passes i = 0 ... n - 2 that have a seam behind them
     // (periodic template: every W carries its row — whether it has a seam behind it depends on the call, and the kernel drops
-    // rows >= ChainArgs::hist_rows)
+    // rows >= ChainArgs::hist_rows, kernels.hpp)
     out.step_tmpl = tmpl;
     out.step_row.assign((size_t)n_steps, -1);
     for (int s = 0; s < n_steps; ++s) {

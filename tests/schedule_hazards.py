@@ -28,7 +28,7 @@ so primal slots have no bounded footprint here.  What is taken from the oracle's
 ensure_primal's stated rule is: a record of a COMPUTE_PRIMAL type exists even without an active message and reads its own dual
 (maximize_potential_and_compute_primal), and a PAIRWISE factor that rounds itself touches (reads and writes) all its unaries,
 active or not (`Footprint.primal`).  These are checked in one direction only: the planner must order at least these accesses.
-The last rule holds in primal passes only, and engine.cpp run_schedule (:782-785) never runs a primal pass in the chain form when
+The last rule holds in primal passes only, and engine.cpp run_schedule (:750-753) never runs a primal pass in the chain form when
 the model has such factors (d_pw_unary set) or a chain of an op-by-op class: the plain form is checked with it, the chain form
 without it.  chain_plan.cpp `replay` accordingly never visits those accesses; nothing has to be added there.
 
