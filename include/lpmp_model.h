@@ -54,7 +54,15 @@ enum lpmp_factor_kind {
    * of 0 (or NaN) on a table with infinities is outside the contract and NOT detected (the scale may live in device memory):
    * the NaN products it makes are dropped by the minima of the shared kernel classes but propagate on the generic kernels
    * and in a dense expansion. */
-  LPMP_F_PAIRWISE_SHARED = 3
+  LPMP_F_PAIRWISE_SHARED = 3,
+  /* const scalar scale; dual = m1[dim0], m2[dim1] (the layout of PAIRWISE_DENSE);
+   * cost(a,b) = scale * D[a - b + dim1 - 1] + m1[a] + m2[b] with D = entry f_table[f] of the same pool, a VECTOR there:
+   * sh_dim0 == 1 and sh_dim1 == dim0 + dim1 - 1 (truncated linear / quadratic and every other potential of the label
+   * difference; dim0 != dim1 and an asymmetric D are allowed).  The contract is that of SHARED: the product is ONE IEEE
+   * double multiply wherever the cost is needed, so the factor is bit for bit a PAIRWISE_DENSE factor whose table is
+   * scale * D[a - b + dim1 - 1] computed on the host; +inf entries are hard constraints, NaN entries are refused, a scale
+   * of 0 (or NaN) on a vector with infinities is outside the contract. */
+  LPMP_F_PAIRWISE_DIFF = 4
 };
 
 enum lpmp_factor_flags {
@@ -152,7 +160,7 @@ typedef struct lpmp_model {
   const int32_t* f_dim0;            /* [n_factors] */
   const int32_t* f_dim1;            /* [n_factors] (PAIRWISE_DENSE only; else ignored) */
   /* packed by factor in insertion order; per-factor sizes follow from kind/dims:
-   *   const: DENSE dim0*dim1, POTTS 1, SHARED 1, VECTOR 0;  dual: VECTOR dim0, DENSE / SHARED dim0+dim1, POTTS 2*dim0 */
+   *   const: DENSE dim0*dim1, POTTS 1, SHARED 1, DIFF 1, VECTOR 0;  dual: VECTOR dim0, DENSE / SHARED / DIFF dim0+dim1, POTTS 2*dim0 */
   const double* const_data;
   const double* dual_data;
 
@@ -177,8 +185,9 @@ typedef struct lpmp_model {
 
   /* --- shared pairwise tables (LPMP_F_PAIRWISE_SHARED): table t is sh_dim0[t] x sh_dim1[t], row-major at
    * sh_data[sh_off[t]]; sh_off[t+1] - sh_off[t] = sh_dim0[t] * sh_dim1[t].  sh_data is HOST memory whatever the
-   * memory kind of const_data.  f_table[f] = table of factor f (read for SHARED factors only; may be NULL when the model
-   * has none).  A caller that zero-initialises the struct and has no SHARED factor need not touch these fields. --- */
+   * memory kind of const_data.  f_table[f] = table of factor f (read for SHARED and DIFF factors only; may be NULL when the
+   * model has none).  A DIFF factor's entry is a 1 x (dim0 + dim1 - 1) table: the vector D of LPMP_F_PAIRWISE_DIFF.  A caller that
+   * zero-initialises the struct and has no SHARED or DIFF factor need not touch these fields. --- */
   int32_t n_shared_tables;
   const int64_t* sh_off;            /* [n_shared_tables+1] */
   const int32_t* sh_dim0;           /* [n_shared_tables] */
@@ -189,10 +198,10 @@ typedef struct lpmp_model {
 
 /* sizes implied by kind/dims */
 static inline int64_t lpmp_factor_const_size(int kind, int dim0, int dim1) {
-  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : ((kind == LPMP_F_PAIRWISE_POTTS || kind == LPMP_F_PAIRWISE_SHARED) ? 1 : 0);
+  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : ((kind == LPMP_F_PAIRWISE_POTTS || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF) ? 1 : 0);
 }
 static inline int64_t lpmp_factor_dual_size(int kind, int dim0, int dim1) {
-  return (kind == LPMP_F_PAIRWISE_DENSE || kind == LPMP_F_PAIRWISE_SHARED) ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
+  return (kind == LPMP_F_PAIRWISE_DENSE || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF) ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
 }
 
 #ifdef __cplusplus

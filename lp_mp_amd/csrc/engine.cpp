@@ -658,6 +658,8 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
                                e->d_lb, e->d_primal, lr.end - lr.begin, flags, e->d_sh_desc, lr.sh_tab, lr.n_sh, stream))
         throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
     }
+    else if (lr.kclass == KC_DIFF)     // (LDS by the launch's label counts, as the streaming class)
+      launch_sweep_diff(s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
     else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
                               e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
@@ -1352,7 +1354,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       // allocation of the engine's own, followed by the pool (always copied from the host: sh_data is host memory also when the
       // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
       std::vector<int64_t> sf;
-      for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED) sf.push_back(f);
+      for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
       const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared];
       e->d_shared.alloc((size_t)(2 * n_sf + n_pool));
       if ((((uintptr_t)e->d_shared.get() - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");

@@ -329,11 +329,13 @@ template <> struct GenCtx<1> {
 __device__ __forceinline__ int64_t shared_table_off(const double* __restrict__ cdata, int64_t coff) {
   return __double_as_longlong(cdata[coff + 1]);
 }
-// pairwise cost T(a,b) of a pairwise factor (dense table, Potts scalar, or scale * shared table: ONE multiply, so that the
-// factor is bit for bit a dense factor whose table is scale * V)
+// (a DIFF factor has the same two words: its table is the vector D of d0 + d1 - 1 entries, cost(a, b) = scale * D[a - b + d1 - 1])
+// pairwise cost T(a,b) of a pairwise factor (dense table, Potts scalar, or scale * shared table / difference vector: ONE multiply,
+// so that the factor is bit for bit a dense factor whose table is scale * V)
 __device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int64_t coff, int kind, int d1, int a, int b) {
   if (kind == LPMP_F_PAIRWISE_DENSE) return cdata[coff + (int64_t)a * d1 + b];
   if (kind == LPMP_F_PAIRWISE_SHARED) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (int64_t)a * d1 + b];
+  if (kind == LPMP_F_PAIRWISE_DIFF) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (a - b + d1 - 1)];
   return a == b ? 0.0 : cdata[coff];
 }
 
@@ -1903,8 +1905,9 @@ static_assert(BIG_WAVES == BIG_BLOCK_RECORDS, "plan.hpp: records per workgroup o
 // LDS of one wave: theta, m_o, q — `ldim` doubles each, ldim = the launch's largest label count rounded up to 64 (round 6: was
 // BIG_MAX_LABELS for every launch, 48 KiB per workgroup, which alone held the kernel at 3 waves per SIMD whatever its registers)
 struct BigLds { double* theta; double* mo; double* q; };
-__device__ __forceinline__ int big_ldim(int flags) { const int k = (flags & SWEEP_BIGDIM_MASK) >> SWEEP_BIGDIM_SHIFT; return k ? 64 * k : BIG_MAX_LABELS; }
-static size_t big_lds_bytes(int flags) { const int k = (flags & SWEEP_BIGDIM_MASK) >> SWEEP_BIGDIM_SHIFT; return (size_t)BIG_WAVES * 3 * (k ? 64 * k : BIG_MAX_LABELS) * sizeof(double); }
+// (the one decoding of sweep_bigdim_flags, for the kernels and for the LDS sizes of their launches)
+__host__ __device__ __forceinline__ int big_ldim(int flags) { const int k = (flags & SWEEP_BIGDIM_MASK) >> SWEEP_BIGDIM_SHIFT; return k ? 64 * k : BIG_MAX_LABELS; }
+static size_t big_lds_bytes(int flags) { return (size_t)BIG_WAVES * 3 * big_ldim(flags) * sizeof(double); }
 // record and op fields are the same in all lanes of the wave: as scalars, so that row addresses are scalar-base + lane offset
 // (one VGPR of offsets for the 16 loads of a block instead of 16 64-bit addresses) and the loop bounds are uniform
 __device__ __forceinline__ double uni_f64(double v) { return __longlong_as_double(uni64<64>(__double_as_longlong(v))); }
@@ -2106,6 +2109,160 @@ sweep_dense_big_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ o
   dense_big_body<NT, ACC_PLAIN>(recs, ops, dual, cdata, lb, primal, first, count, flags, (int64_t)blockIdx.x);
 }
 // -------------------------------------------------------------------------------------------------
+// Class KC_DIFF: unaries whose pairwise peers are all DIFF factors (cost(a, b) = scale * D[a - b + d1 - 1], D a vector of
+// d0 + d1 - 1 doubles of the shared pool), 2 ... BIG_MAX_LABELS labels.  One wave per unary and op by op: dense_big_body with the
+// table stream replaced.  A receive writes sD[k] = scale * D[k] into LDS — the ONE multiply of the contract, once per entry —
+// and takes q[x] = min_y (sD[x - y + d1 - 1] + m_o[y]) (own side 0; side 1: sD[y - x + d1 - 1]) from there: consecutive lanes read
+// consecutive doubles of sD, m_o[y] is a broadcast, a lane keeps up to four own labels 64 apart so that one m_o[y] serves them
+// all.  min and + are exact, so the result is the dense body's on the expanded table bit for bit.  No table is read from memory:
+// D is 2 ... 8 KB and stays in L2.  (No non-temporal variant: there is no stream it would apply to; SWEEP_NT is ignored.)
+// LDS of one wave: theta, m_o, q (ldim doubles each), then sD (2 * ldim), ldim as in the streaming class.
+// -------------------------------------------------------------------------------------------------
+// q[x] for the own labels x = x0 + lane + 64 i, i < NI.  p0 = the lane's window of sD at y = 0.  Lanes beyond Lr run along
+// (uniform loop) and store nothing; their reads stay inside the wave's own LDS: side 0 reaches sD[ldim - 1 + C - 1] at most,
+// side 1 reaches back ldim - C doubles before sD at most, into the q / m_o slabs.
+template <int NI, bool SIDE1>
+__device__ __forceinline__ void diff_minplus(const double* __restrict__ sD, const double* __restrict__ mo, double* __restrict__ q,
+                                             int x0, int Lr, int Lo, int C, int lane) {
+  const int x = x0 + lane;
+  const double* p0 = sD + (SIDE1 ? C - 1 - x : x + C - 1);
+  double v[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) v[i] = LPMP_INF;
+#pragma unroll 4
+  for (int y = 0; y < Lo; ++y) {
+    const double m = mo[y];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) v[i] = fmin(v[i], (SIDE1 ? p0[y - 64 * i] : p0[64 * i - y]) + m);
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) if (x + 64 * i < Lr) q[x + 64 * i] = v[i];
+}
+template <bool SIDE1>
+__device__ __forceinline__ void diff_minplus_all(const double* __restrict__ sD, const double* __restrict__ mo, double* __restrict__ q,
+                                                 int Lr, int Lo, int C, int lane) {
+  for (int x0 = 0; x0 < Lr; x0 += 256) {
+    const int n = (Lr - x0 + 63) >> 6;
+    if (n >= 4) diff_minplus<4, SIDE1>(sD, mo, q, x0, Lr, Lo, C, lane);
+    else if (n == 3) diff_minplus<3, SIDE1>(sD, mo, q, x0, Lr, Lo, C, lane);
+    else if (n == 2) diff_minplus<2, SIDE1>(sD, mo, q, x0, Lr, Lo, C, lane);
+    else diff_minplus<1, SIDE1>(sD, mo, q, x0, Lr, Lo, C, lane);
+  }
+}
+constexpr int DIFF_WAVES_PER_SIMD = 6;
+// waves (= records) per workgroup: BIG_WAVES while their LDS stays within 64 KiB, two above.  ldim is a multiple of 64, so the
+// last size with four waves is 384 labels (60 KiB; 448 would be 70 KiB): launches of more than 384 labels run two waves, 40 KiB at 512
+static int diff_waves(int flags) { return (size_t)BIG_WAVES * 5 * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
+static size_t diff_lds_bytes(int flags) { return (size_t)diff_waves(flags) * 5 * big_ldim(flags) * sizeof(double); }
+
+__global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_WAVES_PER_SIMD)
+sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
+                  const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
+                  int64_t first, int64_t count, int flags) {
+  constexpr int A = ACC_PLAIN;
+  extern __shared__ double big_lds_pool[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  if (idx >= count) return;
+  const int ldim = big_ldim(flags);
+  double* const slab = big_lds_pool + (size_t)wave * 5 * ldim;
+  BigLds S{slab, slab + ldim, slab + 2 * ldim};
+  double* const sD = slab + 3 * ldim;
+  UpdRec rec = recs[first + idx];
+  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
+  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
+  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
+  auto uni_op = [](Op o) {
+    o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
+    o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
+    return o;
+  };
+  const int Lr = rec.d0;
+  double* own_g = dual + rec.dual_off;
+  for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
+  Op nxt{};
+  double nscale = 0.0; int64_t noff = 0;               // the next receive's two constant words {scale, offset of D}
+  if (rec.n_recv > 0) {
+    nxt = ops[rec.op_begin];
+    const int64_t pc = uni64<64>(nxt.peer_const);
+    nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+  }
+  for (int k = 0; k < rec.n_recv; ++k) {
+    const Op op = uni_op(nxt);
+    const double scale = uni_f64(nscale);
+    const double* D = cdata + uni64<64>(noff);
+    if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's reduction starts
+    const int side = (op.info >> 5) & 1;
+    const int R = op.pd0, C = op.pd1;
+    double* ms = dual + op.peer_dual + (side == 0 ? 0 : R);
+    const double* mo = dual + op.peer_dual + (side == 0 ? R : 0);
+    const int Lo = side == 0 ? C : R;
+    double ms_pre[2];                                  // the own side m_s is requested together with m_o and D
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(ms + lane + 64 * j) : 0.0;
+    for (int i = lane; i < Lo; i += 64) S.mo[i] = ld_dual<A>(mo + i);
+    for (int i = lane; i < R + C - 1; i += 64) sD[i] = scale * D[i];
+    wave_sync();
+    if (side == 0) diff_minplus_all<false>(sD, S.mo, S.q, Lr, Lo, C, lane);
+    else diff_minplus_all<true>(sD, S.mo, S.q, Lr, Lo, C, lane);
+    if (k + 1 < rec.n_recv) {                          // (the next op has arrived long ago: its constants travel during the update below)
+      const int64_t pc = uni64<64>(nxt.peer_const);
+      nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+    }
+    wave_sync();
+    double pb = LPMP_INF;                              // peer's bound after this receive
+    for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
+      const double msv = j == 0 ? ms_pre[0] : j == 1 ? ms_pre[1] : ld_dual<A>(ms + i), qv = S.q[i];
+      const double delta = msv + qv;                   // omega = 1: delta = min-marginal
+      S.theta[i] += delta;
+      const double mn = msv - delta;
+      st_dual<A>(ms + i, mn);
+      pb = fmin(pb, mn + qv);
+    }
+    pb = wave_min(pb);
+    if (lane == 0) st_lb<A>(lb + op.peer, pb);
+    wave_sync();
+  }
+  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
+    double bv = LPMP_INF; int bi = 0x7fffffff;
+    for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
+    const double mn = wave_min(bv);
+    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
+    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
+  }
+  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
+  for (int i = lane; i < Lr; i += 64) S.q[i] = S.theta[i];
+  for (int k = 0; k < rec.n_send; ++k) {
+    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+    for (int i = lane; i < Lr; i += 64) {
+      const double delta = op.omega * S.q[i];
+      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+      S.theta[i] -= delta;
+    }
+    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
+  }
+  if (flags & SWEEP_RESIDUAL) {
+    double residual = 0.0;
+    for (int k = 0; k < rec.n_send; ++k) {
+      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+      residual += op.omega;
+      for (int i = lane; i < Lr; i += 64) {
+        const double delta = residual * S.theta[i];
+        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+        S.theta[i] -= delta;
+      }
+    }
+  }
+  double ob = LPMP_INF;
+  for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
+  ob = wave_min(ob);
+  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+}
+// -------------------------------------------------------------------------------------------------
 // Updated pairwise factors (dense or Potts), packed form (classes KC_PW_4..32; `right` / `full` schedules, e.g. MPLP-style
 // FMCs): the factor is on the right of all its (unary-pairwise) messages.  A receive pulls the whole unary in
 // (delta = 1 * theta_u), the sends push omega * min-marginal back.  Same lane layout as sweep_dense_pk_kernel with
@@ -2251,6 +2408,15 @@ factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual
       for (int a = 0; a < d0; ++a) {
         double v = LPMP_INF;
         for (int b = lane; b < d1; b += 64) v = fmin(v, scale * V[(int64_t)a * d1 + b] + d[d0 + b]);
+        v = wave_min(v);
+        best = fmin(best, d[a] + v);
+      }
+    } else if (kind == LPMP_F_PAIRWISE_DIFF) {
+      const double scale = cdata[r.const_off];
+      const double* D = cdata + shared_table_off(cdata, r.const_off) + (d1 - 1);
+      for (int a = 0; a < d0; ++a) {
+        double v = LPMP_INF;
+        for (int b = lane; b < d1; b += 64) v = fmin(v, scale * D[a - b] + d[d0 + b]);
         v = wave_min(v);
         best = fmin(best, d[a] + v);
       }
@@ -2429,6 +2595,15 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
     case KC_SMALL: hipLaunchKernelGGL(sweep_generic_kernel<1>, blocks(GenCtx<1>::FPB), dim3(GenCtx<1>::THREADS), 0, s, recs, ops, dual, cdata, tabs, lb, primal, pw_unary, first, count, flags); break;
     default: hipLaunchKernelGGL(sweep_generic_kernel<64>, blocks(GEN_WAVES), dim3(64 * GEN_WAVES), 0, s, recs, ops, dual, cdata, tabs, lb, primal, pw_unary, first, count, flags); break;
   }
+}
+
+// class KC_DIFF: one wave per record, dynamic LDS by the launch's label counts (flags: sweep_bigdim_flags)
+void launch_sweep_diff(const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
+                       int flags, hipStream_t s) {
+  if (count <= 0) return;
+  const int waves = diff_waves(flags);
+  hipLaunchKernelGGL(sweep_diff_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), diff_lds_bytes(flags), s,
+                     recs, ops, dual, cdata, lb, primal, first, count, flags);
 }
 
 // The ONE table kernel class -> template arguments of the packed kernels: f(family, integral_constant<int, L>, bool_constant<VAR>)

@@ -155,7 +155,7 @@ void Plan::build(const lpmp_model& m) {
   }
   max_dual = 1;
   for (int64_t f = 0; f < nf; ++f) {
-    if (f_kind[f] > LPMP_F_PAIRWISE_SHARED) fail("factor " + std::to_string(f) + ": unknown kind");
+    if (f_kind[f] > LPMP_F_PAIRWISE_DIFF) fail("factor " + std::to_string(f) + ": unknown kind");
     if (f_kind[f] == LPMP_F_PAIRWISE_SHARED) {
       if (f_table.empty()) f_table.assign(nf, -1);
       if (!m.f_table) fail("factor " + std::to_string(f) + ": shared pairwise factor, but the model has no f_table");
@@ -164,6 +164,17 @@ void Plan::build(const lpmp_model& m) {
       if (f_dim0[f] != sh_dim0[t] || f_dim1[f] != sh_dim1[t])
         fail("factor " + std::to_string(f) + ": dims " + std::to_string(f_dim0[f]) + " x " + std::to_string(f_dim1[f]) + " do not match shared table " +
              std::to_string(t) + " (" + std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]) + ")");
+      f_table[f] = t;
+    }
+    if (f_kind[f] == LPMP_F_PAIRWISE_DIFF) {            // D = a 1 x (dim0 + dim1 - 1) entry of the same pool
+      if (f_table.empty()) f_table.assign(nf, -1);
+      if (!m.f_table) fail("factor " + std::to_string(f) + ": difference-indexed pairwise factor, but the model has no f_table");
+      const int32_t t = m.f_table[f];
+      if (t < 0 || t >= n_shared) fail("factor " + std::to_string(f) + ": shared table index " + std::to_string(t) + " out of range");
+      if (f_dim1[f] <= 0) fail("factor " + std::to_string(f) + ": bad dimension");
+      if (sh_dim0[t] != 1 || (int64_t)sh_dim1[t] != (int64_t)f_dim0[f] + f_dim1[f] - 1)
+        fail("factor " + std::to_string(f) + ": dims " + std::to_string(f_dim0[f]) + " x " + std::to_string(f_dim1[f]) + " need a difference vector of 1 x " +
+             std::to_string((int64_t)f_dim0[f] + f_dim1[f] - 1) + ", shared table " + std::to_string(t) + " is " + std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]));
       f_table[f] = t;
     }
     if (f_type[f] < 0 || f_type[f] >= n_ftypes) fail("factor " + std::to_string(f) + ": type out of range");
@@ -457,6 +468,7 @@ struct Updates {
   std::vector<int64_t> rec_bytes;              // algorithmic bytes of the record
   std::vector<int32_t> kclass;                 // kernel class of the record
   std::vector<int32_t> rec_upd;                // [records]: the update each record stands for
+  std::vector<uint8_t> df_all;                 // class diff: every op unary-pairwise to a DIFF peer of dims <= BIG_MAX_LABELS, the factor on the left
   std::vector<int32_t> sh_group;               // shared classes: the table-set group of the record inside its level and class (classify)
 };
 
@@ -611,11 +623,12 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
   U.small_ok = std::vector<uint8_t>(N, 1);
   U.pw_right = std::vector<uint8_t>(N, 1);
   U.sh_all = std::vector<uint8_t>(N, 1);
+  U.df_all = std::vector<uint8_t>(N, 1);
   U.max_dim = std::vector<int32_t>(N, 0);
   std::vector<uint8_t>& all_dense = U.all_dense; std::vector<uint8_t>& all_potts = U.all_potts;
   std::vector<uint8_t>& var_dense = U.var_dense; std::vector<uint8_t>& var_potts = U.var_potts;
   std::vector<uint8_t>& up_any = U.up_any; std::vector<uint8_t>& small_ok = U.small_ok; std::vector<uint8_t>& pw_right = U.pw_right;
-  std::vector<uint8_t>& sh_all = U.sh_all;
+  std::vector<uint8_t>& sh_all = U.sh_all; std::vector<uint8_t>& df_all = U.df_all;
   std::vector<int32_t>& max_dim = U.max_dim;
   std::vector<int64_t> alg_bytes_of_thread(PLAN_MAX_THREADS, 0);
   // (several updates may share an owner record — folded sweeps — and land on different threads: the per-owner flags only
@@ -654,8 +667,10 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
               (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(up_any[o]);
         if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_SHARED && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
               p.f_dim0[peer] <= 32 && p.f_dim1[peer] <= 32)) clear_flag(sh_all[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DIFF && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
+              p.f_dim0[peer] <= BIG_MAX_LABELS && p.f_dim1[peer] <= BIG_MAX_LABELS)) clear_flag(df_all[o]);
       } else {
-        clear_flag(sh_all[o]);
+        clear_flag(sh_all[o]); clear_flag(df_all[o]);
         clear_flag(all_dense[o]); clear_flag(all_potts[o]); clear_flag(var_dense[o]); clear_flag(var_potts[o]); clear_flag(up_any[o]);
         if (mt.kind == LPMP_M_LABELING) {
           op.peer_const = p.tab_off[mt.param];
@@ -666,7 +681,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       op.info = mt.kind | (e.role << 4) | (side << 5) | (imp << 6) | ((p.f_flags[peer] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 << 7 : 0) | (p.f_kind[peer] << 8) |
                 ((mt.flags & LPMP_MF_IMPROVEMENT) ? OP_HAS_IMPROVEMENT : 0);
       if (std::max(op.len, std::max(op.pd0, op.pd1)) > SMALL_MAXD || p.f_doff[f + 1] - p.f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);
-      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[f] != LPMP_F_PAIRWISE_SHARED && p.f_kind[peer] == LPMP_F_VECTOR &&
+      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[f] != LPMP_F_PAIRWISE_SHARED && p.f_kind[f] != LPMP_F_PAIRWISE_DIFF && p.f_kind[peer] == LPMP_F_VECTOR &&
             p.f_dim1[f] > 0 && op.len == (side == 0 ? p.f_dim0[f] : p.f_dim1[f]))) clear_flag(pw_right[o]);
       return op;
     };
@@ -677,8 +692,8 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       const int code = op.info & 15, pk = (op.info >> 8) & 15;
       if (code == LPMP_M_UNARY_PAIRWISE) {
         const int64_t L = op.len;
-        // (a SHARED peer: its scale; the table is on-chip)
-        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED) ? 8 : 0));
+        // (a SHARED or DIFF peer: its scale; the table is on-chip)
+        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED || pk == LPMP_F_PAIRWISE_DIFF) ? 8 : 0));
         return 16 * L;
       }
       return 16 * (int64_t)op.pd0;
@@ -695,7 +710,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
     }
     if (n_act > 0) bytes += 16 * (p.f_doff[f + 1] - p.f_doff[f]);
     // an updated dense pairwise factor reads its own table once to compute the min-marginals it sends
-    if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED)) {   // (SHARED: its scale)
+    if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF)) {   // (SHARED, DIFF: its scale)
       bool sends_any = false;
       for (int64_t j = 0; j < ks; ++j) if (U.uom[u][j] != 0.0) { sends_any = true; break; }
       if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)p.f_dim0[f] * p.f_dim1[f] : 8;
@@ -757,6 +772,9 @@ void classify(const Plan& p, Updates& U, const OpVec& ops) {
         return KC_SHARED_4 + (w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3);
       return small_ok[u] ? KC_SMALL : KC_GENERIC;
     }
+    // unaries between DIFF pairwise factors only (any label count up to BIG_MAX_LABELS, any number of ops: the kernel works op by
+    // op; duplicate vectors were taken above and run on the generic kernels, which know the kind)
+    if (U.df_all[u] && n_recv_of[u] + n_send_of[u] > 0) return KC_DIFF;
     const bool pow = d0 == 4 || d0 == 8 || d0 == 16 || d0 == 32;
     // more ops than the LDS slab of a lane group holds (a hub of a random graph: C4 has a few 30-neighbour variables among
     // 2 M): such a RECORD goes to the op-by-op streaming kernel — left in its class it took its whole launch off the packed
@@ -952,7 +970,7 @@ void memory_order(Schedule& out, std::vector<int32_t>& rec_upd) {
 void work_sort(Schedule& out, std::vector<int32_t>& rec_upd) {
   constexpr int64_t SORT_WINDOW = 1024;
   for (const auto& lr : out.launches)
-    if (lr.kclass != KC_GENERIC && lr.kclass != KC_DENSE_32 && lr.kclass != KC_DENSE_V32 && lr.kclass != KC_DENSE_BIG && lr.kclass != KC_PW_32 && lr.kclass != KC_SHARED_32) {   // incl. KC_SMALL
+    if (lr.kclass != KC_GENERIC && lr.kclass != KC_DENSE_32 && lr.kclass != KC_DENSE_V32 && lr.kclass != KC_DENSE_BIG && lr.kclass != KC_PW_32 && lr.kclass != KC_SHARED_32 && lr.kclass != KC_DIFF) {   // incl. KC_SMALL
       std::vector<int64_t> perm(lr.end - lr.begin);
       std::iota(perm.begin(), perm.end(), lr.begin);
       // (a launch with many different amounts of work per record — a random graph, degrees 2 ... 25 — has no locality

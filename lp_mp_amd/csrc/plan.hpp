@@ -88,6 +88,9 @@ enum KClass : int32_t {
   // unaries whose active messages all go to SHARED pairwise factors (LPMP_F_PAIRWISE_SHARED): run-time label counts and
   // rectangular tables up to the padded width; the launch's distinct tables are staged in LDS once per workgroup
   KC_SHARED_4, KC_SHARED_8, KC_SHARED_16, KC_SHARED_32,
+  // unaries whose active messages all go to DIFF pairwise factors (LPMP_F_PAIRWISE_DIFF), 2 ... BIG_MAX_LABELS labels, any
+  // number of ops: one wave per unary, op by op; a receive builds scale * D in LDS and reads no table from memory
+  KC_DIFF,
   KC_COUNT
 };
 constexpr int BIG_MAX_LABELS = 512;
@@ -248,7 +251,7 @@ struct Plan {
   std::vector<uint8_t> f_kind, f_flags;
   std::vector<int64_t> f_coff, f_doff;   // [nf+1]
   // shared pairwise tables (LPMP_F_PAIRWISE_SHARED): the pool, copied (a handful of small tables), and every factor's table
-  // (-1: not a SHARED factor)
+  // (-1: neither a SHARED nor a DIFF factor; a DIFF factor's entry is its 1 x (dim0 + dim1 - 1) vector)
   int32_t n_shared = 0;
   std::vector<int64_t> sh_off; std::vector<int32_t> sh_dim0, sh_dim1; std::vector<double> sh_data;
   std::vector<int32_t> f_table;

@@ -15,11 +15,11 @@ from . import build as _build
 from .model import FlatModel
 
 _LIB = None
-N_KCLASS = 27
+N_KCLASS = 28
 KCLASS_NAMES = ["generic", "dense4", "dense8", "dense16", "dense32", "potts4", "potts8", "potts16", "potts32",
                 "dense_v4", "dense_v8", "dense_v16", "dense_v32", "potts_v4", "potts_v8", "potts_v16", "potts_v32",
                 "dense_big", "small", "pairwise4", "pairwise8", "pairwise16", "pairwise32",
-                "shared4", "shared8", "shared16", "shared32"]
+                "shared4", "shared8", "shared16", "shared32", "diff"]
 # kernel symbols as rocprofv3 prints them: dense classes run the packed kernel (KMAX 2 at L >= 16, 4 below; packets for up
 # to 8 active messages per factor, indirect records above); the _v classes (any label count up to
 # the padded width, rectangular tables) are the same kernels with run-time dims; the exact dense kernels come in a
@@ -35,7 +35,8 @@ KERNEL_NAMES = ["sweep_generic_kernel<64>", "sweep_dense_pk_kernel<4, 4, false",
                 "sweep_potts_pk_kernel<16, true, false>", "sweep_potts_pk_kernel<32, true, false>", "sweep_dense_big_kernel", "sweep_generic_kernel<1>",
                 "sweep_pairwise_pk_kernel<4>", "sweep_pairwise_pk_kernel<8>", "sweep_pairwise_pk_kernel<16>",
                 "sweep_pairwise_pk_kernel<32>",
-                "sweep_shared_pk_kernel<4", "sweep_shared_pk_kernel<8", "sweep_shared_pk_kernel<16", "sweep_shared_pk_kernel<32"]
+                "sweep_shared_pk_kernel<4", "sweep_shared_pk_kernel<8", "sweep_shared_pk_kernel<16", "sweep_shared_pk_kernel<32",
+                "sweep_diff_kernel"]
 MEM_HOST, MEM_DEVICE = 0, 1
 
 EXPORTS = [

@@ -186,6 +186,7 @@ struct lockstep_plan {
     if ((int64_t)part.size() != nf) throw std::runtime_error("lockstep: a part for every factor (used for the variables)");
     for (int64_t f = 0; f < nf; ++f)
       if (gm.f_kind[f] == LPMP_F_PAIRWISE_SHARED) throw std::runtime_error("lockstep: models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED) are not supported by the multi-GPU hosts");
+      else if (gm.f_kind[f] == LPMP_F_PAIRWISE_DIFF) throw std::runtime_error("lockstep: models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF) are not supported by the multi-GPU hosts");
     for (int t = 0; t < gm.n_mtypes; ++t)
       if (gm.mtypes[t].schedule != LPMP_SCHED_LEFT || (gm.mtypes[t].kind != LPMP_M_UNARY_PAIRWISE && gm.mtypes[t].kind != LPMP_M_LABELING))
         throw std::runtime_error("lockstep: only `left`-schedule unary-pairwise / labeling messages");
@@ -401,6 +402,7 @@ class lockstep_part {
     const int64_t nf = gm.n_factors, nm = gm.n_messages;
     for (int64_t f = 0; f < nf; ++f)
       if (gm.f_kind[f] == LPMP_F_PAIRWISE_SHARED) throw std::runtime_error("lockstep: models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED) are not supported by the multi-GPU hosts");
+      else if (gm.f_kind[f] == LPMP_F_PAIRWISE_DIFF) throw std::runtime_error("lockstep: models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF) are not supported by the multi-GPU hosts");
     std::vector<uint8_t> is_right((size_t)nf, 0), keep((size_t)nf, 0), in_r((size_t)nf, 0);
     for (int64_t m_ = 0; m_ < nm; ++m_) is_right[(size_t)gm.m_right[m_]] = 1;
     auto local = [&](int64_t f) { return !is_right[(size_t)f] && part_of[(size_t)f] == k; };

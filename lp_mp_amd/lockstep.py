@@ -195,6 +195,8 @@ def lockstep_mrf(n_vars: int, L: int, edge_i, edge_j, part, world: int, mode: in
     ``stream_seed``: generated in HBM from the counter stream, fill descriptors in the part)."""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     from . import engine as E
     edge_i = np.asarray(edge_i, np.int64); edge_j = np.asarray(edge_j, np.int64); part = np.asarray(part, np.int64)
     n_edges = edge_i.shape[0]
@@ -646,6 +648,8 @@ def strips_lockstep_part(H: int, W: int, L: int, pairwise: str, order: str, rank
     (tests/test_lockstep.py compares with the parts of the true global structure)."""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     from . import multi_gpu as MG
     n_loc, e_int = MG.strip_sizes(H, W)
     # (only where the level structure is the same in every strip: 2-colour orders.  A row-major order chains its levels

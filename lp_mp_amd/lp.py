@@ -96,6 +96,21 @@ class shared_pairwise_factor:
         return np.float64(self.scale) * self.table[x1, x2]
 
 
+class diff_pairwise_factor:
+    """scale * D[x1 - x2 + dim2 - 1] with D a vector of the LP's pool (LP.add_diff_table): the engine's F_PAIRWISE_DIFF kind — one
+    double per factor, no table in memory.  ``lp.add_factor(P, table_id, dim1, dim2, scale)`` in a container of its own; an
+    instance may also be handed to a container of PairwiseSimplexFactor or shared_pairwise_factor (the same
+    UnaryPairwiseMessage ops, the same dual layout): ``lp.add_factor(P, diff_pairwise_factor(...))``."""
+    kind = M.F_PAIRWISE_DIFF
+
+    def __init__(self, table_id: int, dim1: int, dim2: int, scale: float = 1.0):
+        self.table_id, self.dim1, self.dim2, self.scale = int(table_id), int(dim1), int(dim2), float(scale)
+        self.vec = None                     # bound by LP.add_factor
+
+    def cost(self, x1, x2):
+        return np.float64(self.scale) * self.vec[np.asarray(x1) - np.asarray(x2) + self.dim2 - 1]
+
+
 def labeling_factor(labelings: Sequence[Sequence[int]], implicit_origin: bool):
     """labeling_factor<labelings<...>, IMPLICIT_ORIGIN> (reference include/factors/labeling_list_factor.hxx:220)."""
     labs = [tuple(l) for l in labelings]
@@ -223,12 +238,34 @@ class LP:
         self._dirty = True
         return len(self._shared_tables) - 1
 
+    def add_diff_table(self, D) -> int:
+        """a difference vector (d0 + d1 - 1 entries) for diff_pairwise_factor ops; returns its id in the pool it shares with
+        add_shared_table"""
+        D = np.array(D, np.float64)
+        if D.ndim != 1 or D.shape[0] < 1:
+            raise RuntimeError("add_diff_table: a vector is expected")
+        self._shared_tables.append(D.reshape(1, -1))
+        self._dirty = True
+        return len(self._shared_tables) - 1
+
     def add_factor(self, container: FactorContainer, *args) -> int:
-        op = args[0] if len(args) == 1 and isinstance(args[0], container.factor_type) else container.factor_type(*args)
+        """a factor of the container: the arguments of ``container.factor_type``, or one ready instance of it.  ONE exception to
+        "an instance of the container's type": a ready ``diff_pairwise_factor`` is also taken by a container whose factor type
+        is another tabled pairwise kind (PairwiseSimplexFactor, shared_pairwise_factor) — the three have one dual layout and
+        take the same messages, and the UAI reader (``diff_tables=True``) puts Toeplitz tables into the file's one pairwise
+        container this way.  Nothing else crosses types."""
+        tabled =(M.F_PAIRWISE_DENSE, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DIFF)     # interchangeable in a container: dual = m1[dim1], m2[dim2]
+        ready = len(args) == 1 and (isinstance(args[0], container.factor_type) or
+                                    (isinstance(args[0], diff_pairwise_factor) and getattr(container.factor_type, "kind", None) in tabled))
+        op = args[0] if ready else container.factor_type(*args)
         if getattr(op, "kind", None) == M.F_PAIRWISE_SHARED:
             if not 0 <= op.table_id < len(self._shared_tables):
                 raise RuntimeError("shared_pairwise_factor: table id out of range (LP.add_shared_table first)")
             op.table = self._shared_tables[op.table_id]
+        if getattr(op, "kind", None) == M.F_PAIRWISE_DIFF:
+            if not 0 <= op.table_id < len(self._shared_tables) or self._shared_tables[op.table_id].shape != (1, op.dim1 + op.dim2 - 1):
+                raise RuntimeError("diff_pairwise_factor: no difference vector of dim1 + dim2 - 1 entries under this id (LP.add_diff_table first)")
+            op.vec = self._shared_tables[op.table_id][0]
         self._pull_duals()
         self._factors.append((container, op))
         self._dirty = True
@@ -321,6 +358,8 @@ class LP:
         for c, op in self._factors:
             if op.kind == M.F_PAIRWISE_SHARED:
                 b.add_shared_pairwise(c.factor_no, [op.table_id], [op.scale])
+            elif op.kind == M.F_PAIRWISE_DIFF:
+                b.add_diff_pairwise(c.factor_no, op.dim1, op.dim2, [op.table_id], [op.scale])
             elif op.kind == M.F_VECTOR:
                 b.add_vector_factors(c.factor_no, op.cost[None, :], implicit_origin=op.implicit_origin)
             elif op.kind == M.F_PAIRWISE_DENSE:

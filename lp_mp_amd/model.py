@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 # enum lpmp_factor_kind
-F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS, F_PAIRWISE_SHARED = 0, 1, 2, 3
+F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS, F_PAIRWISE_SHARED, F_PAIRWISE_DIFF = 0, 1, 2, 3, 4
 FF_IMPLICIT_ORIGIN = 1
 # enum lpmp_msg_kind
 M_UNARY_PAIRWISE, M_LABELING, M_MINNORM = 0, 1, 2
@@ -96,12 +96,13 @@ class FlatModel:
     constant: float = 0.0
     part_pairs: Optional[np.ndarray] = None   # [n,2] int32: put_in_same_partition(f1, f2) calls in call order
     # shared pairwise tables (F_PAIRWISE_SHARED: cost = scale * V[a][b], the factor's one const double is the scale):
-    # table t is sh_dim0[t] x sh_dim1[t], row-major at sh_data[sh_off[t]]; f_table[f] = table of factor f (-1: none)
+    # table t is sh_dim0[t] x sh_dim1[t], row-major at sh_data[sh_off[t]]; f_table[f] = table of factor f (-1: none).
+    # F_PAIRWISE_DIFF: cost = scale * D[a - b + d1 - 1], D = entry f_table[f] of the same pool, a [1, d0 + d1 - 1] table
     sh_off: Optional[np.ndarray] = None       # [n_tables + 1] int64
     sh_dim0: Optional[np.ndarray] = None      # [n_tables] int32
     sh_dim1: Optional[np.ndarray] = None
     sh_data: Optional[np.ndarray] = None      # float64, host memory always
-    f_table: Optional[np.ndarray] = None      # [n_factors] int32, None when no factor is SHARED
+    f_table: Optional[np.ndarray] = None      # [n_factors] int32, None when no factor is SHARED or DIFF
     _keep: list = field(default_factory=list, repr=False)
 
     def __getstate__(self):          # the ctypes views of c_struct() are per process and rebuilt on demand
@@ -120,12 +121,12 @@ class FlatModel:
     def const_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where((self.f_kind == F_PAIRWISE_POTTS) | (self.f_kind == F_PAIRWISE_SHARED), 1, 0))
+        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where((self.f_kind == F_PAIRWISE_POTTS) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF), 1, 0))
 
     def dual_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where((self.f_kind == F_PAIRWISE_DENSE) | (self.f_kind == F_PAIRWISE_SHARED), d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
+        return np.where((self.f_kind == F_PAIRWISE_DENSE) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF), d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
 
     def dual_offsets(self) -> np.ndarray:
         return np.concatenate([[0], np.cumsum(self.dual_sizes())]).astype(np.int64)
@@ -146,39 +147,63 @@ class FlatModel:
         d0, d1 = int(self.sh_dim0[t]), int(self.sh_dim1[t])
         return self.sh_data[int(self.sh_off[t]): int(self.sh_off[t]) + d0 * d1].reshape(d0, d1)
 
-    def expand_shared(self) -> "FlatModel":
-        """the same model with every SHARED factor replaced by a DENSE factor whose table is ``np.float64(scale) * V`` —
-        same factor order, messages, relations and duals (the dual layouts of the two kinds are equal), no pool.  Plain numpy;
-        a model without SHARED factors is returned with its arrays shared."""
+    @property
+    def has_diff(self) -> bool:
+        return bool(np.any(self.f_kind == F_PAIRWISE_DIFF))
+
+    def _expand(self, which: int, name: str) -> "FlatModel":
+        """the factors of kind ``which`` (SHARED or DIFF) replaced by DENSE factors; the pool goes with the last factor
+        that uses it.  While factors of the other pooled kind remain, the pool stays WHOLE: the entries that only the expanded
+        factors used are kept (``n_shared_tables`` still counts them, an upload still carries them), so that the table ids of
+        the remaining factors do not move."""
         import dataclasses
-        if not self.has_shared:
-            return dataclasses.replace(self, sh_off=None, sh_dim0=None, sh_dim1=None, sh_data=None, f_table=None, _keep=[])
+        other = F_PAIRWISE_DIFF if which == F_PAIRWISE_SHARED else F_PAIRWISE_SHARED
+        keep_pool = bool(np.any(self.f_kind == other))
+        is_exp = self.f_kind == which
+        if keep_pool:
+            pool = dict(f_table=np.where(is_exp, np.int32(-1), self.f_table).astype(np.int32), _keep=[])
+        else:
+            pool = dict(sh_off=None, sh_dim0=None, sh_dim1=None, sh_data=None, f_table=None, _keep=[])
+        if not is_exp.any():
+            return dataclasses.replace(self, **pool)
         if self.const_data is None:
-            raise ValueError("expand_shared: the model has no host constants")
+            raise ValueError(name + ": the model has no host constants")
         old_off = self.const_offsets()
         kind = self.f_kind.copy()
-        shared = np.nonzero(kind == F_PAIRWISE_SHARED)[0]
-        kind[shared] = F_PAIRWISE_DENSE
-        new = dataclasses.replace(self, f_kind=kind, sh_off=None, sh_dim0=None, sh_dim1=None, sh_data=None, f_table=None, _keep=[])
+        kind[is_exp] = F_PAIRWISE_DENSE
+        new = dataclasses.replace(self, f_kind=kind, **pool)
         new_off = new.const_offsets()
         const = np.empty(int(new_off[-1]), np.float64)
-        is_shared = self.f_kind == F_PAIRWISE_SHARED
-        # runs of factors that are not SHARED keep their constants as they are
+        # runs of factors that stay keep their constants as they are
         f = 0
         nf = self.n_factors
         while f < nf:
             g = f
-            if is_shared[f]:
+            if is_exp[f]:
                 V = self.shared_table(int(self.f_table[f]))
+                if which == F_PAIRWISE_DIFF:
+                    d0, d1 = int(self.f_dim0[f]), int(self.f_dim1[f])
+                    V = V.reshape(-1)[np.arange(d0)[:, None] - np.arange(d1)[None, :] + (d1 - 1)]
                 const[new_off[f]: new_off[f + 1]] = (np.float64(self.const_data[old_off[f]]) * V).reshape(-1)
                 f += 1
             else:
-                while g < nf and not is_shared[g]:
+                while g < nf and not is_exp[g]:
                     g += 1
                 const[new_off[f]: new_off[g]] = self.const_data[old_off[f]: old_off[g]]
                 f = g
         new.const_data = const
         return new
+
+    def expand_shared(self) -> "FlatModel":
+        """the same model with every SHARED factor replaced by a DENSE factor whose table is ``np.float64(scale) * V`` —
+        same factor order, messages, relations and duals (the dual layouts of the two kinds are equal), no pool (it stays while
+        DIFF factors use it).  Plain numpy; a model without SHARED factors is returned with its arrays shared."""
+        return self._expand(F_PAIRWISE_SHARED, "expand_shared")
+
+    def expand_diff(self) -> "FlatModel":
+        """the same model with every DIFF factor replaced by a DENSE factor whose table is
+        ``np.float64(scale) * D[a - b + d1 - 1]`` — the yardstick of the kind, as expand_shared() is for SHARED factors"""
+        return self._expand(F_PAIRWISE_DIFF, "expand_diff")
 
     def with_factor_order(self, rank: np.ndarray) -> "FlatModel":
         """the same factors, messages and costs with the factor relations REPLACED by a chain through all factors in the order
@@ -200,6 +225,8 @@ class FlatModel:
             raise ValueError("dump: the model has no host duals")
         if self.has_shared:
             raise ValueError("dump: the model file format has no shared pairwise tables (expand_shared() gives a model it can hold)")
+        if self.has_diff:
+            raise ValueError("dump: the model file format has no difference-indexed pairwise factors (expand_diff() gives a model it can hold)")
         const = np.zeros(0) if self.const_data is None else np.ascontiguousarray(self.const_data, np.float64)
         mt = np.array([[t.left_ftype, t.right_ftype, t.schedule, t.n_left, t.n_right, t.kind, t.param, t.flags] for t in self.mtypes], np.int32).reshape(-1, 8)
         head = np.array([0x4C504D504D4F444C, self.n_ftypes, len(self.mtypes), self.tab_nleft.shape[0], self.tab_data.shape[0], self.n_factors,
@@ -259,6 +286,22 @@ def refuse_shared(model: "FlatModel", who: str):
     if model.has_shared:
         raise ValueError(who + " do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED): expand_shared() gives the "
                          "same model with one private dense table per factor")
+    if model.has_diff:
+        raise ValueError(who + " do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF): expand_diff() gives "
+                         "the same model with one private dense table per factor")
+
+
+def truncated_linear(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray:
+    """the difference vector D[k] = min(slope * |k - (d1 - 1)|, trunc) of a d0 x d1 DIFF factor: cost(a, b) = min(slope * |a - b|, trunc)
+    (one multiply per entry: these host values are the values)"""
+    k = np.abs(np.arange(d0 + d1 - 1, dtype=np.float64) - (d1 - 1))
+    return np.minimum(np.float64(slope) * k, np.float64(trunc))
+
+
+def truncated_quadratic(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray:
+    """D[k] = min(slope * (k - (d1 - 1))^2, trunc): the square is exact in double, then one multiply"""
+    k = np.arange(d0 + d1 - 1, dtype=np.float64) - (d1 - 1)
+    return np.minimum(np.float64(slope) * (k * k), np.float64(trunc))
 
 
 class ModelBuilder:
@@ -365,6 +408,34 @@ class ModelBuilder:
         d0, d1 = dims.pop()
         n = table_ids.shape[0]
         ids = self._add_factors(n, ftype, F_PAIRWISE_SHARED, 0, d0, d1, scales, None if self.skip_dual else np.zeros((n, d0 + d1)))
+        self._f_table.append((int(ids[0]), table_ids.copy()))
+        return ids
+
+    def add_diff_table(self, vec) -> int:
+        """a difference vector D of d0 + d1 - 1 entries (add_diff_pairwise: cost(a, b) = scale * D[a - b + d1 - 1]), stored as a
+        [1, n] entry of the shared pool; returns its id"""
+        vec = np.ascontiguousarray(vec, np.float64)
+        if vec.ndim != 1 or vec.shape[0] < 1:
+            raise ValueError("add_diff_table: a vector is expected")
+        self._shared.append(vec.reshape(1, -1).copy())
+        return len(self._shared) - 1
+
+    def add_diff_pairwise(self, ftype: int, d0: int, d1: int, table_ids, scales) -> np.ndarray:
+        """d0 x d1 pairwise factors cost(a, b) = scales[i] * D[table_ids[i]][a - b + d1 - 1]: every factor holds one double.
+        ``scales`` is finite, and positive where the vector holds +inf entries."""
+        table_ids = np.atleast_1d(np.asarray(table_ids, np.int32))
+        scales = np.atleast_1d(np.asarray(scales, np.float64))
+        if scales.shape[0] == 1 and table_ids.shape[0] > 1:
+            scales = np.full(table_ids.shape[0], scales[0])
+        if table_ids.shape != scales.shape or table_ids.shape[0] == 0:
+            raise ValueError("add_diff_pairwise: one table id and one scale per factor")
+        if table_ids.min() < 0 or table_ids.max() >= len(self._shared):
+            raise ValueError("add_diff_pairwise: table id out of range")
+        d0, d1 = int(d0), int(d1)
+        if d0 < 1 or d1 < 1 or any(self._shared[t].shape != (1, d0 + d1 - 1) for t in np.unique(table_ids)):
+            raise ValueError("add_diff_pairwise: a %d x %d factor needs difference vectors of %d entries" % (d0, d1, d0 + d1 - 1))
+        n = table_ids.shape[0]
+        ids = self._add_factors(n, ftype, F_PAIRWISE_DIFF, 0, d0, d1, scales, None if self.skip_dual else np.zeros((n, d0 + d1)))
         self._f_table.append((int(ids[0]), table_ids.copy()))
         return ids
 

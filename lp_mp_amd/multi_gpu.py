@@ -535,6 +535,8 @@ def strip_costs(H, W, L, world, pairwise, seed):
     """Host arrays of the global cost streams (tests only; sizes grow with world)."""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     n_loc, e_int = strip_sizes(H, W)
     n_vars = world * n_loc
     n_edges = world * e_int + (world - 1) * W
@@ -550,6 +552,8 @@ def strip_local_part(H: int, W: int, L: int, pairwise: str, order: str, rank: in
     from closed-form index arithmetic on this rank's strip only."""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     n_loc, e_int = strip_sizes(H, W)
     n_vars = world * n_loc
     var = S.grid_variable_order(H, W, order).reshape(-1)

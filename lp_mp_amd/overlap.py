@@ -95,6 +95,8 @@ def strip_window_part(H: int, W: int, L: int, pairwise: str, rank: int, world: i
     costs are generated in HBM from the counter stream (fill descriptors, multi_gpu.fill_device_costs)."""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     if g % 2 or g < 4:
         raise ValueError("overlap: the ghost depth must be even (the window keeps the global colouring) and at least 4 (one pass between exchanges needs 4 rows)")
     if H % 2:
@@ -272,6 +274,8 @@ def grid_pass_counts(GH: int, W: int, L: int, pairwise: str = "dense") -> Tuple[
     received once and sent once"""
     if pairwise == "shared":
         raise ValueError("the multi-GPU hosts do not take models with shared pairwise tables (LPMP_F_PAIRWISE_SHARED)")
+    if pairwise == "diff":
+        raise ValueError("the multi-GPU hosts do not take models with difference-indexed pairwise factors (LPMP_F_PAIRWISE_DIFF)")
     E = GH * (W - 1) + (GH - 1) * W
     n = GH * W
     per_msg = (8 * L * L if pairwise == "dense" else 8) + 40 * L

@@ -136,14 +136,15 @@ def grid_edges(H: int, W: int) -> Tuple[np.ndarray, np.ndarray]:
 def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unaries: np.ndarray,
               tables: Optional[np.ndarray] = None, potts: Optional[np.ndarray] = None,
               device_const: bool = False, compute_primal: bool = False, device_dual: bool = False,
-              shared: Optional[tuple] = None) -> M.FlatModel:
+              shared: Optional[tuple] = None, diff: Optional[tuple] = None) -> M.FlatModel:
     """MRF over variables 0..n_vars-1 (already in variable order) with edges (i<j required).
     ``compute_primal``: the unary FactorContainer's COMPUTE_PRIMAL_SOLUTION flag (as in LP_MP-MRF's FMC_SRMP);
     needed for the ...AndPrimal passes.
     ``tables`` [E,L,L] (T[e,a,b]: a = label of i) or ``potts`` [E] diffs. With ``device_const`` the dense
     tables are not materialised on the host (they are generated in HBM; see Engine.upload); with ``device_dual`` neither are the
     duals (``unaries`` is ignored: the caller fills the device buffer it hands to Engine.upload).
-    ``shared`` = (tables [T,L,L], table id per edge [E], scale per edge [E]): shared pairwise factors, cost = scale * V[a][b]."""
+    ``shared`` = (tables [T,L,L], table id per edge [E], scale per edge [E]): shared pairwise factors, cost = scale * V[a][b].
+    ``diff`` = (vectors [T,2L-1], vector id per edge [E], scale per edge [E]): difference-indexed factors, cost = scale * D[a - b + L - 1]."""
     edge_i = np.asarray(edge_i, np.int64)
     edge_j = np.asarray(edge_j, np.int64)
     assert np.all(edge_i < edge_j)
@@ -157,6 +158,11 @@ def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unari
         sh_tables, sh_ids, sh_scales = shared
         first = [b.add_shared_table(t) for t in np.asarray(sh_tables, np.float64)][0]
         p = b.add_shared_pairwise(1, first + np.asarray(sh_ids, np.int32), sh_scales)
+    elif diff is not None:
+        assert not device_const and potts is None and tables is None
+        df_vecs, df_ids, df_scales = diff
+        first = [b.add_diff_table(t) for t in np.asarray(df_vecs, np.float64)][0]
+        p = b.add_diff_pairwise(1, L, L, first + np.asarray(df_ids, np.int32), df_scales)
     elif potts is not None:
         assert not device_const
         p = b.add_potts_pairwise(1, L, potts)
@@ -181,11 +187,14 @@ def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unari
 def grid_model(H: int, W: int, L: int, pairwise: str = "dense", order: str = "row_major", seed: int = 1,
                unaries: Optional[np.ndarray] = None, tables: Optional[np.ndarray] = None,
                potts: Optional[np.ndarray] = None, device_const: bool = False, compute_primal: bool = False,
-               n_tables: int = 2, shared_tables: Optional[np.ndarray] = None, scales: Optional[np.ndarray] = None) -> M.FlatModel:
+               n_tables: int = 2, shared_tables: Optional[np.ndarray] = None, scales: Optional[np.ndarray] = None,
+               diff_tables: Optional[np.ndarray] = None) -> M.FlatModel:
     """H x W grid MRF.  Random costs are U(0,1) from the counter-based generator: unaries first
     (variable order), then the pairwise data edge by edge (edge order of grid_edges).
     ``pairwise="shared"``: ``n_tables`` shared L x L tables (the generator's next n_tables L^2 values, or ``shared_tables``
-    [n_tables, L, L]); edge e of grid_edges uses table e mod n_tables with scale 0.5 + 1.5 u (the values after the tables), or ``scales`` [E]."""
+    [n_tables, L, L]); edge e of grid_edges uses table e mod n_tables with scale 0.5 + 1.5 u (the values after the tables), or ``scales`` [E].
+    ``pairwise="diff"``: ``n_tables`` difference vectors of 2L - 1 entries (the generator's next n_tables (2L - 1) values, or
+    ``diff_tables`` [n_tables, 2L - 1]); edge e uses vector e mod n_tables, scales as for "shared"."""
     var = grid_variable_order(H, W, order).reshape(-1)
     a, bb = grid_edges(H, W)
     va, vb = var[a], var[bb]
@@ -204,7 +213,20 @@ def grid_model(H: int, W: int, L: int, pairwise: str = "dense", order: str = "ro
         return mrf_model(n, L, i, j, unaries, potts=potts, compute_primal=compute_primal)
     if pairwise == "shared":
         return mrf_model(n, L, i, j, unaries, compute_primal=compute_primal, shared=_shared_costs(E, L, n * L, seed, n_tables, shared_tables, scales))
+    if pairwise == "diff":
+        return mrf_model(n, L, i, j, unaries, compute_primal=compute_primal, diff=_diff_costs(E, L, n * L, seed, n_tables, diff_tables, scales))
     raise ValueError(pairwise)
+
+
+def _diff_costs(E: int, L: int, first: int, seed: int, n_tables: int, vecs=None, scales=None):
+    """(vectors [T,2L-1], vector of every edge [E], scale of every edge [E]) of the ``pairwise="diff"`` generators"""
+    if vecs is None:
+        vecs = u01(n_tables * (2 * L - 1), seed, first).reshape(n_tables, 2 * L - 1)
+    vecs = np.asarray(vecs, np.float64)
+    T = vecs.shape[0]
+    if scales is None:
+        scales = 0.5 + 1.5 * u01(E, seed, first + T * (2 * L - 1))
+    return vecs, (np.arange(E) % T).astype(np.int32), np.asarray(scales, np.float64)
 
 
 def _shared_costs(E: int, L: int, first: int, seed: int, n_tables: int, tables=None, scales=None):
@@ -227,7 +249,7 @@ def chain_model(n: int, L: int, diff: float = 1.0, seed: int = 1) -> M.FlatModel
 def random_graph_model(n: int, m: int, L: int, seed: int = 1, pairwise: str = "dense", compute_primal: bool = False,
                        n_tables: int = 2) -> M.FlatModel:
     """C4-style G(n, m): m distinct uniform random edges without self loops, variable order = index.
-    ``pairwise="shared"``: as grid_model (edge e uses table e mod n_tables)."""
+    ``pairwise="shared"`` / ``"diff"``: as grid_model (edge e uses table / vector e mod n_tables)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     got = np.zeros((0, 2), np.int64)
     while got.shape[0] < m:
@@ -243,6 +265,8 @@ def random_graph_model(n: int, m: int, L: int, seed: int = 1, pairwise: str = "d
         return mrf_model(n, L, e[:, 0], e[:, 1], un, tables=u01(m * L * L, seed, n * L), compute_primal=compute_primal)
     if pairwise == "shared":
         return mrf_model(n, L, e[:, 0], e[:, 1], un, compute_primal=compute_primal, shared=_shared_costs(m, L, n * L, seed, n_tables))
+    if pairwise == "diff":
+        return mrf_model(n, L, e[:, 0], e[:, 1], un, compute_primal=compute_primal, diff=_diff_costs(m, L, n * L, seed, n_tables))
     return mrf_model(n, L, e[:, 0], e[:, 1], un, potts=u01(m, seed, n * L), compute_primal=compute_primal)
 
 

@@ -37,20 +37,31 @@ def parse_uai(text: str) -> Tuple[List[int], List[Tuple[Tuple[int, ...], np.ndar
 
 def FMC_SRMP(share_tables: bool = False):
     U = LPM.FactorContainer(LPM.UnarySimplexFactor, 0, True)     # COMPUTE_PRIMAL_SOLUTION on the unaries: rounding
-    P = LPM.FactorContainer(LPM.shared_pairwise_factor if share_tables else LPM.PairwiseSimplexFactor, 1)
+    P = LPM.FactorContainer(LPM.shared_pairwise_factor if share_tables else LPM.PairwiseSimplexFactor, 1)   # (also takes diff_pairwise_factor instances)
     ML = LPM.MessageContainer(LPM.UnaryPairwiseMessage(0), 0, 1, M.SCHED_LEFT, M.variableMessageNumber, 1, 0)
     MR = LPM.MessageContainer(LPM.UnaryPairwiseMessage(1), 0, 1, M.SCHED_LEFT, M.variableMessageNumber, 1, 1)
     return LPM.FMC("FMC_SRMP", [U, P], [ML, MR]), U, P, ML, MR
 
 
-def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_tables: bool = False) -> LPM.LP:
+def _difference_vector(t: np.ndarray):
+    """D with t[a][b] == D[a - b + d1 - 1] bytewise on every diagonal, or None"""
+    d0, d1 = t.shape
+    D = np.concatenate([t[0, ::-1], t[1:, 0]])
+    idx = np.arange(d0)[:, None] - np.arange(d1)[None, :] + (d1 - 1)
+    return D if np.array_equal(D[idx].view(np.uint64), t.view(np.uint64)) else None
+
+
+def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_tables: bool = False, diff_tables: bool = False) -> LPM.LP:
     """``order``: "index" — relations u_i -> p_ij -> u_j for i < j in the file's variable numbering, what LP_MP-MRF's
     constructor does (a row-major grid then has H+W-1 dependent steps per sweep); "colour_major" — the same relations
     along a colour-major ranking of the variables (ordering.colour_major_order: 2 steps per sweep on a bipartite
     graph).  Both are valid block-coordinate-ascent orders; they give different dual trajectories.
     ``share_tables``: pairwise functions whose tables (oriented along the relation) are bytewise equal and of the same shape
     become ONE shared table with scale 1.0 (shared_pairwise_factor) instead of a private dense table each — same costs,
-    same duals."""
+    same duals.
+    ``diff_tables``: a pairwise function whose entries depend only on a - b (bytewise equal along every diagonal) becomes a
+    diff_pairwise_factor with scale 1.0 on a pooled difference vector (bytewise equal vectors are one entry); the others stay as
+    they would be without the option."""
     card, tables = parse_uai(text)
     if order not in ("index", "colour_major"):
         raise ValueError(order)
@@ -63,6 +74,7 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_ta
     fmc, U, P, ML, MR = FMC_SRMP(share_tables)
     lp = LPM.LP(fmc, device)
     pool = {}
+    diff_pool = {}
     unary = [np.zeros(c) for c in card]
     for sc, t in tables:
         if len(sc) == 1:
@@ -77,7 +89,13 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_ta
         if rank[i] > rank[j]:
             i, j, t = j, i, t.T
         t = np.ascontiguousarray(t, np.float64)
-        if share_tables:
+        D = _difference_vector(t) if diff_tables else None
+        if D is not None:
+            key = D.tobytes()
+            if key not in diff_pool:
+                diff_pool[key] = lp.add_diff_table(D)
+            p = lp.add_factor(P, LPM.diff_pairwise_factor(diff_pool[key], card[i], card[j], 1.0))
+        elif share_tables:
             key = (t.shape, t.tobytes())
             if key not in pool:
                 pool[key] = lp.add_shared_table(t)
@@ -91,11 +109,11 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_ta
     return lp
 
 
-def solve_uai(text: str, device: int = 0, share_tables: bool = False, **visitor_options):
+def solve_uai(text: str, device: int = 0, share_tables: bool = False, diff_tables: bool = False, **visitor_options):
     """MAP estimation for a model in UAI format with the message-passing rounding solver — the reference's
     ``MpRoundingSolver<Solver<LP<FMC_SRMP>, StandardVisitor>>`` + ``UaiMrfInput::ParseString`` (test/graphical_model.cpp:
     47-56).  Returns (lower bound, primal cost, labeling of the variables)."""
-    lp = build_lp_from_uai(text, device, share_tables=share_tables)
+    lp = build_lp_from_uai(text, device, share_tables=share_tables, diff_tables=diff_tables)
     s = LPM.MpRoundingSolver(lp, LPM.StandardVisitor(**visitor_options))
     s.Solve()
     n = len(parse_uai(text)[0])
