@@ -284,6 +284,28 @@ void* lpmp_device_duals(lpmp_engine* e);   /* device pointer of the packed duals
 int lpmp_set_rows_layout(lpmp_engine* e, int on);
 int lpmp_rows_layout(const lpmp_engine* e);   /* 1 if the uploaded model uses it */
 
+/* Table precision (engine-private): from the NEXT lpmp_upload_model on, every entry of a DENSE pairwise table
+ * (LPMP_F_PAIRWISE_DENSE) is stored as a float on the device and widened to double where a kernel loads it.  All arithmetic stays
+ * double and in the same order, so the result is bit for bit what the engine computes on the model whose tables are the widened
+ * floats — exact for the cost volumes and learned potentials that are float32 where they are produced.  Halves the bytes of the
+ * tables in device memory and per pass.  Potts scalars, SHARED / DIFF scales, the shared pool and all duals stay doubles.
+ *   LPMP_TABLES_F64        doubles, the default
+ *   LPMP_TABLES_F32        strict: the upload returns LPMP_ERR_UNSUPPORTED when an entry x has (double)(float)x != x
+ *   LPMP_TABLES_F32_ROUND  entries are rounded to nearest even
+ * Both f32 modes refuse (LPMP_ERR_UNSUPPORTED) a finite entry that overflows float and a nonzero one of magnitude below FLT_MIN;
+ * the message names the lowest factor index that holds such an entry.  +-inf pass through (hard constraints); NaN is outside the
+ * contract as it is for doubles.  From host memory (LPMP_MEM_HOST) the tables pass through a staging buffer of at most 256 MiB
+ * and are never resident as doubles; from a caller's device buffer they are narrowed out of it, and afterwards the engine reads
+ * only the other factors' constants from that buffer.  Cannot be combined with the rows layout (LPMP_ERR_UNSUPPORTED at the
+ * upload).  The lpmp_boundary_* / lpmp_halo_* kernels touch duals only and work unchanged. */
+enum lpmp_table_precision_mode { LPMP_TABLES_F64 = 0, LPMP_TABLES_F32 = 1, LPMP_TABLES_F32_ROUND = 2 };
+int lpmp_set_table_precision(lpmp_engine* e, int precision);
+int lpmp_table_precision(const lpmp_engine* e);   /* what the uploaded model uses */
+/* the same for a stand-alone plan: only the byte accounting of the schedules planned from now on changes (4 instead of 8 bytes per
+ * dense table entry: algorithmic bytes, band and tile sizes of the Infinity-Cache order, the heavy-launch rule); kernel classes,
+ * levels and records are those of the f64 plan */
+int lpmp_plan_set_table_precision(lpmp_plan* p, int precision);
+
 /* Persistent launches (the chain executor and the joined passes in Infinity-Cache order) assume that resident
  * workgroups keep running, i.e. that the device is this process's own.  When several processes time-share one device its scheduler
  * switches queues, ticket holders freeze while their waiters poll, and a run may end in LPMP_ERR_DEVICE ("a dependency wait timed

@@ -253,6 +253,11 @@ struct lpmp_engine {
   // that the SHARED factors' device const offsets point into (Plan::dev_coff), and the pool's tables as the shared classes' kernel sees them
   DevBuf<double> d_shared; DevBuf<ShTableDesc> d_sh_desc;
   int nt_flag = 0;                // SWEEP_NT when tables + duals are far larger than L2 + Infinity Cache
+  // table precision (lpmp_set_table_precision): want_tab applies to the next upload, tab_prec is the uploaded model's; with an f32
+  // mode the dense tables live as floats in d_tab32 (every table 16-byte aligned), the DENSE factors' device const offsets point
+  // there (Plan::dev_coff, still in 8-byte units relative to d_const) and every launch carries tab_flag = SWEEP_TAB32
+  int want_tab = LPMP_TABLES_F64, tab_prec = LPMP_TABLES_F64, tab_flag = 0;
+  DevBuf<float> d_tab32;
   bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
   struct LbRun { int cls; int64_t first, count; };
   std::vector<LbRun> lb_runs;
@@ -347,6 +352,7 @@ struct lpmp_engine {
     dual_buf.reset(); const_buf.reset();
     d_dual = nullptr; d_const = nullptr;
     d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
+    d_tab32.reset(); tab_prec = LPMP_TABLES_F64; tab_flag = 0;
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
     d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
@@ -648,7 +654,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
     if (timed) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, stream)); }
     // UpdateFactorPrimal always sends 'shared' (reference factors_messages.hxx:2357-2359), whatever the send rule
     const int rule = e->rtype == LPMP_RTYPE_RESIDUAL ? SWEEP_RESIDUAL : e->rtype == LPMP_RTYPE_ADAPTIVE ? SWEEP_ADAPTIVE : 0;
-    const int flags = (e->primal_pass ? SWEEP_PRIMAL : rule) | e->nt_flag;
+    const int flags = (e->primal_pass ? SWEEP_PRIMAL : rule) | e->nt_flag | e->tab_flag;
     // primal pass over pairwise factors that round themselves: those records take the generic kernels (ensure_primal)
     const bool pw_rounds = e->primal_pass && e->d_pw_unary && kc_is_pw(lr.kclass);
     if (pw_rounds)
@@ -766,7 +772,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
         DevBuf<long long> d_lt;
         const size_t lt_n = 8 + 8 * LEVEL_TRACE_MAX;
         if (lt_path) { d_lt.alloc(lt_n); HIP_CHECK(hipMemset(d_lt, 0, lt_n * sizeof(long long))); debug_set_level_trace(d_lt); }
-        if (!launch_level_loop(c.kclass, rule, c.launches, c.n_launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->stream))
+        if (!launch_level_loop(c.kclass, rule | e->tab_flag, c.launches, c.n_launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->stream))
           throw DeviceError("level loop: no kernel for class " + std::to_string(c.kclass));
         if (lt_path) {
           HIP_CHECK(hipStreamSynchronize(e->stream));
@@ -781,7 +787,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
       ChainTrace tr;
       ChainArgs ca = chain_args(e, c, c.tickets, tr.begin(c.tickets, e->stream));
       ca.mailbox = c.mailbox;
-      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->nt_flag), ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->stream))
+      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->nt_flag) | e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->stream))
         throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
       tr.end(c, e->stream, e->d_chain_abort);
     }
@@ -966,7 +972,7 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
-  if (!launch_chain(c.kclass, 0, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1282,6 +1288,85 @@ int lpmp_set_stream(lpmp_engine* e, void* s) {
   });
 }
 
+// Table precision f32 (lpmp_set_table_precision): every DENSE table of the packed constants becomes floats in e->d_tab32, each
+// table 16-byte aligned, and p.dev_coff[f] of a DENSE factor its place there (8-byte units relative to e->d_const).
+//   on_device: `consts` is the caller's device buffer — it stays e->d_const, the tables are narrowed out of it, and afterwards
+//     the engine reads only the cells of the other factors from it.
+//   otherwise `consts` is host memory: the tables pass through a staging buffer of at most 256 MiB, chunk by chunk, and are never
+//     resident as doubles as a whole; the cells of the other factors (Potts, SHARED and DIFF scalars) are gathered into a compact
+//     buffer of doubles that becomes e->d_const, and dev_coff of those factors points into it.
+// Throws UnsupportedError naming the lowest DENSE factor that holds an entry the mode refuses (kernels.hip, narrow_tables_kernel).
+static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on_device) {
+  const int strict = e->want_tab == LPMP_TABLES_F32 ? 1 : 0;
+  std::vector<NarrowRec> recs;
+  std::vector<double> small;
+  p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
+  int64_t at = 0;                                  // floats
+  for (int64_t f = 0; f < p.nf; ++f) {
+    const int64_t n = p.f_coff[f + 1] - p.f_coff[f];
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+      recs.push_back({p.f_coff[f], at, n, (int32_t)f, 0});
+      at += (n + 3) / 4 * 4;
+    } else if (!on_device) {
+      p.dev_coff[f] = (int64_t)small.size();
+      small.insert(small.end(), consts + p.f_coff[f], consts + p.f_coff[f + 1]);
+    }
+  }
+  if (!on_device) {
+    e->const_buf.alloc(std::max<size_t>(2, small.size()));
+    e->d_const = e->const_buf;
+    if (!small.empty()) h2d(e->d_const, small.data(), small.size() * sizeof(double), e->stream);
+  }
+  if (recs.empty()) return;
+  e->d_tab32.alloc((size_t)at);
+  if ((((uintptr_t)e->d_tab32.get() - (uintptr_t)e->d_const) % 16) != 0) throw std::runtime_error("table precision: buffers are not aligned to each other");
+  const int64_t shift = (int64_t)(((intptr_t)e->d_tab32.get() - (intptr_t)e->d_const) / 8);
+  for (const NarrowRec& r : recs) p.dev_coff[r.factor] = shift + r.dst_off / 2;
+  DevBuf<int> d_bad; d_bad.alloc(1);
+  const int none = INT32_MAX;
+  h2d(d_bad, &none, sizeof(int), e->stream);
+  DevBuf<NarrowRec> d_recs;
+  if (on_device) {
+    d_recs.alloc(recs.size());
+    h2d(d_recs, recs.data(), recs.size() * sizeof(NarrowRec), e->stream);
+    launch_narrow_tables(d_recs, (int64_t)recs.size(), e->d_const, e->d_tab32, strict, d_bad, e->stream);
+    HIP_CHECK(hipGetLastError());
+  } else {
+    // chunks of whole tables, at most STAGE doubles of the packed array each (a table has at most BIG_MAX_LABELS^2 entries: 2 MiB)
+    const int64_t STAGE = ((int64_t)256 << 20) / (int64_t)sizeof(double);
+    int64_t span = 0, cnt = 0;
+    for (size_t a = 0; a < recs.size();) {        // the largest chunk: sizes the two device buffers once
+      size_t b = a; const int64_t c0 = recs[a].src_off;
+      while (b < recs.size() && recs[b].src_off + recs[b].n - c0 <= STAGE) ++b;
+      if (b == a) throw std::runtime_error("table precision: a table larger than the staging buffer");
+      span = std::max(span, recs[b - 1].src_off + recs[b - 1].n - c0); cnt = std::max(cnt, (int64_t)(b - a));
+      a = b;
+    }
+    DevBuf<double> stage; stage.alloc((size_t)span);
+    d_recs.alloc((size_t)cnt);
+    std::vector<NarrowRec> part;
+    for (size_t a = 0; a < recs.size();) {
+      size_t b = a; const int64_t c0 = recs[a].src_off;
+      while (b < recs.size() && recs[b].src_off + recs[b].n - c0 <= STAGE) ++b;
+      part.assign(recs.begin() + (std::ptrdiff_t)a, recs.begin() + (std::ptrdiff_t)b);
+      for (NarrowRec& r : part) r.src_off -= c0;
+      h2d(stage, consts + c0, (size_t)(recs[b - 1].src_off + recs[b - 1].n - c0) * sizeof(double), e->stream);
+      h2d(d_recs, part.data(), part.size() * sizeof(NarrowRec), e->stream);
+      launch_narrow_tables(d_recs, (int64_t)part.size(), stage, e->d_tab32, strict, d_bad, e->stream);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(e->stream));   // `part` and the staging buffer are reused by the next chunk
+      a = b;
+    }
+  }
+  int bad = none;
+  d2h(&bad, d_bad, sizeof(int), e->stream);
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (bad != none)
+    throw UnsupportedError("table precision " + std::string(strict ? "f32" : "f32_round") + ": the table of factor " + std::to_string(bad) +
+                           (strict ? " holds an entry that is not exactly a float (or a finite one beyond float's range or below FLT_MIN)"
+                                   : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN"));
+}
+
 static void check_rtype(const lpmp_engine* e, int rtype);
 int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int dual_mem) {
   return guarded([&] {
@@ -1302,9 +1387,15 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       e->nt_flag = (env ? atoi(env) != 0 : big) ? SWEEP_NT : 0;
       e->model_big = big;
     }
+    const bool f32 = e->want_tab != LPMP_TABLES_F64;
+    if (f32 && e->want_rows) throw UnsupportedError("table precision f32 and the rows layout cannot be combined (the rows hold the tables as doubles)");
+    if (f32) pl->p.tables_f32 = true;   // before the first schedule: the byte accounting of every plan of this model
     if (const_mem == LPMP_MEM_DEVICE) {
       e->d_const = const_cast<double*>(m->const_data);
       if (((uintptr_t)e->d_const & 15) != 0) throw std::runtime_error("device const buffer must be 16-byte aligned");
+      if (f32) try { narrow_tables(e, pl->p, m->const_data, true); } catch (...) { e->release_model(); throw; }
+    } else if (f32) {
+      try { narrow_tables(e, pl->p, m->const_data, false); } catch (...) { e->release_model(); throw; }
     } else if (n_const > 0) {
       e->const_buf.alloc((size_t)n_const);
       e->d_const = e->const_buf;
@@ -1363,7 +1454,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       if (pl->p.dev_coff.empty()) pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
       for (int64_t k = 0; k < n_sf; ++k) {
         const int64_t f = sf[(size_t)k];
-        cells[(size_t)(2 * k)] = p.f_coff[f];
+        cells[(size_t)(2 * k)] = pl->p.dev_coff[f];   // (the packed offset, or the factor's cell of the compact constants: table precision)
         cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + p.sh_off[(size_t)p.f_table[f]];
         pl->p.dev_coff[f] = base + 2 * k;
       }
@@ -1404,6 +1495,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
     HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));   // all NaN: nothing tracked yet
     HIP_CHECK(hipStreamSynchronize(e->stream));
     e->lb_all_stale = true;
+    if (f32) { e->tab_prec = e->want_tab; e->tab_flag = SWEEP_TAB32; }
     e->plan = std::move(pl);
     e->plan->p.force_generic = e->rtype == LPMP_RTYPE_ADAPTIVE;
     {   // mailbox budget of every schedule planned for this model: half of what the device has left now (LPMP_MAILBOX_MB overrides)
@@ -1846,7 +1938,7 @@ int lpmp_evaluate_primal(lpmp_engine* e, double* cost) {
     if (!primal_consistent(e)) { *cost = std::numeric_limits<double>::infinity(); return; }
     const int64_t nf = e->plan->p.nf;
     rows_refresh(e);
-    launch_primal_cost(e->d_lbrecs, e->d_dual, e->d_const, e->d_primal, e->d_pcost, nf, e->stream);
+    launch_primal_cost(e->d_lbrecs, e->d_dual, e->d_const, e->d_primal, e->d_pcost, nf, e->tab_flag, e->stream);
     int64_t nb = std::min<int64_t>(1024, (nf + 255) / 256);
     const int64_t per = (nf + nb - 1) / nb;
     nb = (nf + per - 1) / per;
@@ -1994,7 +2086,7 @@ static void compute_factor_lbs(lpmp_engine* e) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
     const int64_t n_stale = (int64_t)*e->h_stale_n;
     if (n_stale <= nf / 8) {
-      launch_factor_lb_list(e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, e->d_stale, n_stale, e->stream);
+      launch_factor_lb_list(e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, e->d_stale, n_stale, e->tab_flag, e->stream);
       HIP_CHECK(hipGetLastError());
       e->last_lb_recomputed = n_stale;
       return;
@@ -2002,8 +2094,8 @@ static void compute_factor_lbs(lpmp_engine* e) {
   }
   e->last_lb_recomputed = e->plan->p.nf;
   for (const auto& r : e->lb_runs) {
-    if (r.cls == 0 || !launch_dense_lb(r.cls, e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, r.first, r.count, e->stream))
-      launch_factor_lb(e->d_lbrecs + r.first, e->d_dual, e->d_const, e->d_lb + r.first, r.count, e->stream);
+    if (r.cls == 0 || !launch_dense_lb(r.cls, e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, r.first, r.count, e->tab_flag, e->stream))
+      launch_factor_lb(e->d_lbrecs + r.first, e->d_dual, e->d_const, e->d_lb + r.first, r.count, e->tab_flag, e->stream);
   }
   HIP_CHECK(hipGetLastError());
   e->lb_all_stale = false;
@@ -2168,6 +2260,22 @@ int lpmp_set_rows_layout(lpmp_engine* e, int on) {
   return guarded([&] { if (!e) throw std::runtime_error("null engine"); e->want_rows = on != 0; });
 }
 int lpmp_rows_layout(const lpmp_engine* e) { return e && e->rows ? 1 : 0; }
+int lpmp_set_table_precision(lpmp_engine* e, int precision) {
+  return guarded([&] {
+    if (!e) throw std::runtime_error("null argument");
+    if (precision != LPMP_TABLES_F64 && precision != LPMP_TABLES_F32 && precision != LPMP_TABLES_F32_ROUND) throw std::runtime_error("unknown table precision");
+    e->want_tab = precision;
+  });
+}
+int lpmp_table_precision(const lpmp_engine* e) { return e ? e->tab_prec : LPMP_TABLES_F64; }
+int lpmp_plan_set_table_precision(lpmp_plan* p, int precision) {
+  return guarded([&] {
+    if (!p) throw std::runtime_error("null argument");
+    if (precision != LPMP_TABLES_F64 && precision != LPMP_TABLES_F32 && precision != LPMP_TABLES_F32_ROUND) throw std::runtime_error("unknown table precision");
+    const bool f32 = precision != LPMP_TABLES_F64;
+    if (f32 != p->p.tables_f32) { p->p.tables_f32 = f32; p->drop_caches(); }
+  });
+}
 int64_t lpmp_lower_bound_recomputed(const lpmp_engine* e) { return e ? e->last_lb_recomputed : -1; }
 void* lpmp_engine_stream(lpmp_engine* e) { return e ? (void*)e->stream : nullptr; }
 const lpmp_plan* lpmp_engine_plan(const lpmp_engine* e) { return e ? e->plan.get() : nullptr; }

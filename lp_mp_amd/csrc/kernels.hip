@@ -332,8 +332,11 @@ __device__ __forceinline__ int64_t shared_table_off(const double* __restrict__ c
 // (a DIFF factor has the same two words: its table is the vector D of d0 + d1 - 1 entries, cost(a, b) = scale * D[a - b + d1 - 1])
 // pairwise cost T(a,b) of a pairwise factor (dense table, Potts scalar, or scale * shared table / difference vector: ONE multiply,
 // so that the factor is bit for bit a dense factor whose table is scale * V)
-__device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int64_t coff, int kind, int d1, int a, int b) {
-  if (kind == LPMP_F_PAIRWISE_DENSE) return cdata[coff + (int64_t)a * d1 + b];
+// t32 (wave-uniform, SWEEP_TAB32): DENSE tables are stored as floats (engine.cpp, table precision) and widened here — every
+// other constant stays a double
+__device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int64_t coff, int kind, int d1, int a, int b, int t32) {
+  if (kind == LPMP_F_PAIRWISE_DENSE)
+    return t32 ? (double)reinterpret_cast<const float*>(cdata + coff)[(int64_t)a * d1 + b] : cdata[coff + (int64_t)a * d1 + b];
   if (kind == LPMP_F_PAIRWISE_SHARED) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (int64_t)a * d1 + b];
   if (kind == LPMP_F_PAIRWISE_DIFF) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (a - b + d1 - 1)];
   return a == b ? 0.0 : cdata[coff];
@@ -343,18 +346,18 @@ __device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int6
 // read through m (global: live peer, or LDS: own snapshot / live own state)
 template <class C, class Src>
 __device__ __forceinline__ void pw_min_marginal(const C& c, const double* __restrict__ cdata, int64_t coff, int kind, int d0, int d1,
-                                                Src m, int side, double omega) {
+                                                Src m, int side, double omega, int t32) {
   if (side == 0) {
     for (int a = 0; a < d0; ++a) {
       double v = LPMP_INF;
-      for (int b = c.first(); b < d1; b += C::STRIDE) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b) + m(d0 + b));
+      for (int b = c.first(); b < d1; b += C::STRIDE) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b, t32) + m(d0 + b));
       v = C::gmin(v);
       if (c.leader()) c.dl(a) = omega * (m(a) + v);
     }
   } else {
     for (int b = c.first(); b < d1; b += C::STRIDE) {
       double v = LPMP_INF;
-      for (int a = 0; a < d0; ++a) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b) + m(a));
+      for (int a = 0; a < d0; ++a) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b, t32) + m(a));
       c.dl(b) = omega * (m(d0 + b) + v);
     }
   }
@@ -395,11 +398,11 @@ __device__ __forceinline__ double vec_lb_through(const C& c, int n, Acc d, int i
   return v;
 }
 template <class C, class Acc>
-__device__ __forceinline__ double pw_lb_through(const C& c, const double* __restrict__ cdata, int64_t coff, int kind, int d0, int d1, Acc m) {
+__device__ __forceinline__ double pw_lb_through(const C& c, const double* __restrict__ cdata, int64_t coff, int kind, int d0, int d1, Acc m, int t32) {
   double best = LPMP_INF;
   for (int a = 0; a < d0; ++a) {
     double v = LPMP_INF;
-    for (int b = c.first(); b < d1; b += C::STRIDE) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b) + m(d0 + b));
+    for (int b = c.first(); b < d1; b += C::STRIDE) v = fmin(v, pw_cost(cdata, coff, kind, d1, a, b, t32) + m(d0 + b));
     v = C::gmin(v);
     best = fmin(best, m(a) + v);
   }
@@ -419,6 +422,7 @@ __device__ __forceinline__ void generic_body(const UpdRec* __restrict__ recs, co
   if (idx >= count) return;
   const C c{lds[wave], lane};
   const UpdRec rec = recs[first + idx];
+  const int t32 = flags & SWEEP_TAB32;
   const int okind = rec.kind_flags & 15;
   const int on = okind == LPMP_F_VECTOR ? rec.d0 : rec.d0 + rec.d1;   // own dual size
   double* own_g = dual + rec.dual_off;
@@ -438,8 +442,8 @@ __device__ __forceinline__ void generic_body(const UpdRec* __restrict__ recs, co
     const bool by_right = recv ? (role == 0) : (role == 1);
     if (code == OP_UP) {
       if (by_right) {   // min-marginal of the pairwise (right) factor
-        if (recv) pw_min_marginal(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, from_peer, side, omega);
-        else pw_min_marginal(c, cdata, rec.const_off, okind, rec.d0, rec.d1, from_own, side, omega);
+        if (recv) pw_min_marginal(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, from_peer, side, omega, t32);
+        else pw_min_marginal(c, cdata, rec.const_off, okind, rec.d0, rec.d1, from_own, side, omega, t32);
       } else {          // omega * theta of the unary (left) factor
         for (int i = c.first(); i < len; i += C::STRIDE) c.dl(i) = omega * (recv ? ld_dual<A>(peer + i) : from_own(i));
         C::sync();
@@ -541,8 +545,8 @@ __device__ __forceinline__ void generic_body(const UpdRec* __restrict__ recs, co
       double lb_r, la_r;
       if (code == OP_UP) {
         const int o = side == 0 ? 0 : op.pd0;
-        lb_r = pw_lb_through(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, [&](int j) { return ld_dual<A>(peer + j); });
-        la_r = pw_lb_through(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, [&](int j) { return (j >= o && j < o + len) ? ld_dual<A>(peer + j) + s_right * c.dl(j - o) : ld_dual<A>(peer + j); });
+        lb_r = pw_lb_through(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, [&](int j) { return ld_dual<A>(peer + j); }, t32);
+        la_r = pw_lb_through(c, cdata, op.peer_const, pkind, op.pd0, op.pd1, [&](int j) { return (j >= o && j < o + len) ? ld_dual<A>(peer + j) + s_right * c.dl(j - o) : ld_dual<A>(peer + j); }, t32);
       } else if (code == OP_LABELING) {
         lb_r = vec_lb_through(c, op.pd0, [&](int j) { return ld_dual<A>(peer + j); }, peer_io);
         la_r = vec_lb_through(c, op.pd0, [&](int j) { return tab[j] < nl ? ld_dual<A>(peer + j) + s_right * c.dl(tab[j]) : ld_dual<A>(peer + j); }, peer_io);
@@ -557,8 +561,8 @@ __device__ __forceinline__ void generic_body(const UpdRec* __restrict__ recs, co
       double lb_r, la_r;
       if (code == OP_UP) {
         const int o = side == 0 ? 0 : rec.d0;
-        lb_r = pw_lb_through(c, cdata, rec.const_off, okind, rec.d0, rec.d1, [&](int j) { return c.own(j); });
-        la_r = pw_lb_through(c, cdata, rec.const_off, okind, rec.d0, rec.d1, [&](int j) { return (j >= o && j < o + len) ? c.own(j) + s_right * c.dl(j - o) : c.own(j); });
+        lb_r = pw_lb_through(c, cdata, rec.const_off, okind, rec.d0, rec.d1, [&](int j) { return c.own(j); }, t32);
+        la_r = pw_lb_through(c, cdata, rec.const_off, okind, rec.d0, rec.d1, [&](int j) { return (j >= o && j < o + len) ? c.own(j) + s_right * c.dl(j - o) : c.own(j); }, t32);
       } else if (code == OP_LABELING) {
         lb_r = vec_lb_through(c, on, [&](int j) { return c.own(j); }, own_io);
         la_r = vec_lb_through(c, on, [&](int j) { return tab[j] < nl ? c.own(j) + s_right * c.dl(tab[j]) : c.own(j); }, own_io);
@@ -589,7 +593,7 @@ __device__ __forceinline__ void generic_body(const UpdRec* __restrict__ recs, co
         double bv = LPMP_INF; int bi = 0x7fffffff;
         for (int i = c.first(); i < na * nb; i += C::STRIDE) {
           const int a = a0 + i / nb, b = b0 + i % nb;
-          const double v = pw_cost(cdata, rec.const_off, okind, d1, a, b) + c.own(a) + c.own(d0 + b);
+          const double v = pw_cost(cdata, rec.const_off, okind, d1, a, b, t32) + c.own(a) + c.own(d0 + b);
           if (bi == 0x7fffffff || v < bv) { bv = v; bi = i; }
         }
         const double mn = C::gmin(bv);
@@ -689,6 +693,8 @@ template <> struct DenseCfg<8>  { static constexpr int G = 8; };
 template <> struct DenseCfg<4>  { static constexpr int G = 4; };
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
+typedef float float4_t __attribute__((ext_vector_type(4)));
 
 template <int G, class T> __device__ __forceinline__ T uni(T v) {
   if constexpr (G == 64 && sizeof(T) == 4) return (T)__builtin_amdgcn_readfirstlane((int)v);
@@ -742,7 +748,12 @@ __device__ __forceinline__ void load_packet(double2_t* slab, const Op* __restric
 // side 0 (own label = row of V) reduces the TRANSPOSE with the column form of side 1: the lane accumulates its two columns over
 // the steps and the row-lanes meet in two shuffles, instead of a DPP row reduction per step — min is exact, so q is the same
 // number either way; at 32 labels that is 110 instead of 270 FP64 instructions per receive, and the pass is bound by them.
-template <int L, int KMAX, bool VAR, bool NT, int A, bool CHAIN, bool MBOX = false, bool SHARED = false>
+// TAB32 (SWEEP_TAB32; engine.cpp, table precision): the dense tables are stored as floats and widened where they are added —
+// every dual, every sum and every minimum stays a double, so the result is the f64 body's on the widened tables bit for bit.
+// The exact classes keep the 16-byte load per lane: a lane holds PER = 4 consecutive columns (a float4) of NL rows, side 0
+// takes the minimum over its four columns and then over the CL = L / 4 lanes of a row, side 1 keeps four column accumulators;
+// the run-time-dims classes keep the two-column mapping and load element by element.
+template <int L, int KMAX, bool VAR, bool NT, int A, bool CHAIN, bool MBOX = false, bool SHARED = false, bool TAB32 = false>
 __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
                                               double* __restrict__ dual, const double* __restrict__ cdata, double* __restrict__ lb,
                                               int32_t* __restrict__ primal, int64_t count, int stride, int flags, int64_t block,
@@ -750,11 +761,14 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
                                               unsigned long long* __restrict__ mbox = nullptr, int n_deps = -1,
                                               const double* sh_lds = nullptr, const int64_t* sh_toff = nullptr, int n_sh = 0) {
   static_assert(!SHARED || (VAR && !CHAIN && !MBOX), "the shared classes: run-time dims, plain launches");
+  static_assert(!(SHARED && TAB32), "shared tables stay doubles");
   static_assert(!CHAIN || A == ACC_COH, "chain bodies hand results over through relaxed agent-scope flags: every dual access must be an agent-scope (sc1) access");
   static_assert(MAILBOX_SENDS >= 1 && MAILBOX_SENDS <= 4, "plan.hpp: the sends whose fields are held in registers (KS)");
   static_assert(!MBOX || CHAIN, "the mailbox belongs to the chain executor");   // (an instantiation of its own: the joined passes of the headline grid lost 8 % with the mailbox fields in their registers)
   constexpr int G = DenseCfg<L>::G;
-  constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
+  constexpr int PER = (TAB32 && !VAR) ? 4 : 2;   // table elements per lane and load step
+  constexpr int CL = L / PER, RPL = PER * G / L, NL = L / RPL, GPB = 256 / G;
+  using TabT = std::conditional_t<PER == 4, float4_t, double2_t>;
   constexpr int KS = MBOX ? MAILBOX_SENDS : 4;   // sends whose target vectors are prefetched / forwarded
   constexpr int NFW = MBOX ? MAILBOX_SENDS : 4;  // receives whose result can be forwarded in registers (plan.cpp: hints of mailbox chains stay below)
   constexpr int PIECES = 3 * (1 + (SHARED ? pk_indirect_cap(L) : pk_dense_cap(L)));      // 16-B pieces of the largest packet / op list
@@ -829,7 +843,7 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     constexpr bool FW = decltype(fw_tag)::value;
     constexpr bool FIRST = decltype(first_tag)::value;
     // the tables in registers — NOT under SHARED, where t is never written: every read of a table piece goes through tab() below
-    [[maybe_unused]] double2_t t[KMAX][NL];
+    [[maybe_unused]] TabT t[KMAX][NL];
     [[maybe_unused]] const double* tsl[KMAX]; [[maybe_unused]] double tsc[KMAX];   // SHARED: the peer's table slot in LDS, its scale
     double msv[KMAX], mov[KMAX];
     int64_t pdual[KMAX];
@@ -876,6 +890,14 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
               t[j][i].x = (row < R && 2 * c2 < C) ? (row == 2 * c2 ? 0.0 : diff) : LPMP_INF;
               t[j][i].y = (row < R && 2 * c2 + 1 < C) ? (row == 2 * c2 + 1 ? 0.0 : diff) : LPMP_INF;
             }
+          } else if constexpr (TAB32) {
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+              const int row = i * RPL + rl;
+              const float* Tr = reinterpret_cast<const float*>(T) + (int64_t)row * C + 2 * c2;
+              t[j][i].x = (row < R && 2 * c2 < C) ? (double)ld_stream<NT>(Tr) : LPMP_INF;
+              t[j][i].y = (row < R && 2 * c2 + 1 < C) ? (double)ld_stream<NT>(Tr + 1) : LPMP_INF;
+            }
           } else {
 #pragma unroll
             for (int i = 0; i < NL; ++i) {
@@ -885,11 +907,19 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
               t[j][i].y = (row < R && 2 * c2 + 1 < C) ? ld_stream<NT>(Tr + 1) : LPMP_INF;
             }
           }
+        } else if constexpr (PER == 4) {
+          roff[j] = side[j] == 0 ? 0 : L;
+          // consecutive lanes take consecutive 16-byte pieces: floats [4 (i G + g), + 4) = row i RPL + rl, columns 4 c2 ... 4 c2 + 3
+#pragma unroll
+          for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<NT>(reinterpret_cast<const float4_t*>(T) + (int64_t)i * G + g);
         } else {
           roff[j] = side[j] == 0 ? 0 : L;
 #pragma unroll
           for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<NT>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
         }
+      } else if constexpr (PER == 4) {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) t[j][i] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
       } else if constexpr (!SHARED) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
@@ -897,8 +927,9 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
     }
     // piece i of receive j's table as the lane holds it: registers, or (SHARED) one 16-byte LDS read of the staged table times
     // the peer's scale — consecutive lanes read consecutive 16-byte pieces (i * 2G + 2g doubles into the slot: conflict free)
-    auto tab = [&](const int j, const int i) -> double2_t {
-      if constexpr (SHARED) {
+    [[maybe_unused]] auto tab = [&](const int j, const int i) -> double2_t {
+      if constexpr (PER == 4) return double2_t{0.0, 0.0};   // (the float4 form reads t directly, below)
+      else if constexpr (SHARED) {
         const double2_t v = *reinterpret_cast<const double2_t*>(tsl[j] + i * 2 * G + 2 * g);
         return double2_t{tsc[j] * v.x, tsc[j] * v.y};
       } else return t[j][i];
@@ -943,6 +974,34 @@ __device__ __forceinline__ void dense_pk_body(const Op* __restrict__ packets, co
       const bool act = c + j < n_recv;
       if (g < L) lds_mo[grp][g] = mov[j];
       wave_sync();
+      if constexpr (PER == 4) {
+        if (side[j] == 0) {
+          const double2_t ma = *reinterpret_cast<const double2_t*>(&lds_mo[grp][4 * c2]);
+          const double2_t mb = *reinterpret_cast<const double2_t*>(&lds_mo[grp][4 * c2 + 2]);
+#pragma unroll
+          for (int i = 0; i < NL; ++i) {
+            const float4_t tv = t[j][i];
+            double v = fmin(fmin((double)tv.x + ma.x, (double)tv.y + ma.y), fmin((double)tv.z + mb.x, (double)tv.w + mb.y));
+            if constexpr (CL > 1) v = row_allreduce_min<CL>(v);
+            if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
+          }
+        } else {
+          double v0 = LPMP_INF, v1 = LPMP_INF, v2 = LPMP_INF, v3 = LPMP_INF;
+#pragma unroll
+          for (int i = 0; i < NL; ++i) {
+            const double m1v = lds_mo[grp][i * RPL + rl];
+            const float4_t tv = t[j][i];
+            v0 = fmin(v0, (double)tv.x + m1v); v1 = fmin(v1, (double)tv.y + m1v);
+            v2 = fmin(v2, (double)tv.z + m1v); v3 = fmin(v3, (double)tv.w + m1v);
+          }
+#pragma unroll
+          for (int m = G / 2; m >= CL; m >>= 1) {
+            v0 = fmin(v0, shfl_xor_f64(v0, m)); v1 = fmin(v1, shfl_xor_f64(v1, m));
+            v2 = fmin(v2, shfl_xor_f64(v2, m)); v3 = fmin(v3, shfl_xor_f64(v3, m));
+          }
+          if (rl == 0) { lds_q[grp][4 * c2] = v0; lds_q[grp][4 * c2 + 1] = v1; lds_q[grp][4 * c2 + 2] = v2; lds_q[grp][4 * c2 + 3] = v3; }
+        }
+      } else
       if (!SHARED && side[j] == 0) {
         const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_mo[grp][2 * c2]);
 #pragma unroll
@@ -1154,6 +1213,16 @@ sweep_dense_pk_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__
                                                                    (int64_t)blockIdx.x, nullptr, 0);
 }
 
+// the same launch on float tables (SWEEP_TAB32): a kernel of its own, so that the f64 kernels above keep their code
+template <int L, int KMAX, bool VAR, bool NT>
+__global__ void __launch_bounds__(256)
+sweep_dense_pk_f32_kernel(const Op* __restrict__ packets, const UpdRec* __restrict__ recs, const Op* __restrict__ ops,
+                          double* __restrict__ dual, const double* __restrict__ cdata, double* __restrict__ lb,
+                          int32_t* __restrict__ primal, int64_t count, int stride, int flags) {
+  dense_pk_body<L, KMAX, VAR, NT, NT ? ACC_NT : ACC_PLAIN, false, false, false, true>(packets, recs, ops, dual, cdata, lb, primal, count, stride, flags,
+                                                                                       (int64_t)blockIdx.x, nullptr, 0);
+}
+
 // Shared classes: unaries whose pairwise peers are all SHARED factors (cost = scale * V[a][b], V one of a handful of tables
 // of the model).  A workgroup stages the launch's distinct tables in LDS ONCE (per table V and its transpose: L x L doubles each,
 // row stride L, NaN beyond the table's dims) and then walks blocks of records in a grid-stride loop, so that the staging
@@ -1268,6 +1337,25 @@ chain_dense_pk_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, do
       const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
       dense_pk_body<L, KMAX, VAR, NT, ACC_COH, true>(ln.packets, ln.recs, ln.ops, dual, cdata, lb, primal, ln.count, ln.stride, flags, block, &ca, ticket,
                                                      hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr, hmode);
+    });
+  }
+}
+
+// float tables (SWEEP_TAB32): the exact 32-label body holds its two tables in 32 instead of 64 VGPRs and keeps the three waves
+template <int L, int KMAX, bool VAR, bool NT, bool MBOX>
+__global__ void __launch_bounds__(256, !MBOX && L == 32 && !VAR ? 3 : 1)
+chain_dense_pk_f32_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual,
+                          const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal, int flags) {
+  if constexpr (MBOX) {
+    chain_loop_ahead(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int n_deps) {
+      dense_pk_body<L, KMAX, VAR, NT, ACC_COH, true, true, false, true>(ln.packets, ln.recs, ln.ops, dual, cdata, lb, primal, ln.count, ln.stride, flags, block,
+                                                                        &ca, ticket, nullptr, 0, ca.mailbox, n_deps);
+    });
+  } else {
+    chain_loop(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket) {
+      const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
+      dense_pk_body<L, KMAX, VAR, NT, ACC_COH, true, false, false, true>(ln.packets, ln.recs, ln.ops, dual, cdata, lb, primal, ln.count, ln.stride, flags, block,
+                                                                         &ca, ticket, hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr, hmode);
     });
   }
 }
@@ -1955,7 +2043,13 @@ __device__ __forceinline__ double transpose_min16(double (&v)[16], int lane) {
 // grid with 33 ... 48 labels as one persistent launch in Infinity-Cache order: bit-identical and SLOWER than one launch per step,
 // 12.6 against 9.9 ms per pass at 33 labels, 15.4 against 12.1 at 40, 16.8 against 16.6 at 48, and from about 56 labels on the
 // window cannot sit in the cache at all — EXPERIMENTS.md K; the kernel went, the policy parameter stayed)
-template <bool NT, int A>
+// entry idx of a dense table: a double, or (T32: SWEEP_TAB32) a float that is widened
+template <bool NT, bool T32>
+__device__ __forceinline__ double ld_tab(const double* __restrict__ T, int64_t idx) {
+  if constexpr (T32) return (double)ld_stream<NT>(reinterpret_cast<const float*>(T) + idx);
+  else return ld_stream<NT>(T + idx);
+}
+template <bool NT, int A, bool T32 = false>
 __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
                                                const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
                                                int64_t first, int64_t count, int flags, int64_t block) {
@@ -2025,7 +2119,7 @@ __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, 
           const double m = cb ? S.mo[b] : 0.0;
           double t[16];
 #pragma unroll
-          for (int r = 0; r < 16; ++r) t[r] = (cb && a0 + r < R) ? ld_stream<NT>(T + (int64_t)(a0 + r) * C + b) : LPMP_INF;
+          for (int r = 0; r < 16; ++r) t[r] = (cb && a0 + r < R) ? ld_tab<NT, T32>(T, (int64_t)(a0 + r) * C + b) : LPMP_INF;
 #pragma unroll
           for (int r = 0; r < 16; ++r) v[r] = fmin(v[r], t[r] + m);
         }
@@ -2040,7 +2134,7 @@ __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, 
         for (int a0 = 0; a0 < R; a0 += 16) {
           double t[16];
 #pragma unroll
-          for (int r = 0; r < 16; ++r) t[r] = (cb && a0 + r < R) ? ld_stream<NT>(T + (int64_t)(a0 + r) * C + b) : LPMP_INF;
+          for (int r = 0; r < 16; ++r) t[r] = (cb && a0 + r < R) ? ld_tab<NT, T32>(T, (int64_t)(a0 + r) * C + b) : LPMP_INF;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { const double m = a0 + r < R ? S.mo[a0 + r] : 0.0; v = fmin(v, t[r] + m); }
         }
@@ -2107,6 +2201,14 @@ sweep_dense_big_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ o
                        const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
                        int64_t first, int64_t count, int flags) {
   dense_big_body<NT, ACC_PLAIN>(recs, ops, dual, cdata, lb, primal, first, count, flags, (int64_t)blockIdx.x);
+}
+// float tables (SWEEP_TAB32): one column per lane as above, 4-byte loads
+template <bool NT>
+__global__ void __launch_bounds__(64 * BIG_WAVES, 5)
+sweep_dense_big_f32_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
+                           const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
+                           int64_t first, int64_t count, int flags) {
+  dense_big_body<NT, ACC_PLAIN, true>(recs, ops, dual, cdata, lb, primal, first, count, flags, (int64_t)blockIdx.x);
 }
 // -------------------------------------------------------------------------------------------------
 // Class KC_DIFF: unaries whose pairwise peers are all DIFF factors (cost(a, b) = scale * D[a - b + d1 - 1], D a vector of
@@ -2370,6 +2472,109 @@ sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ du
   if (g < C) own_g[R + g] = m2;
   if (live && g == 0) lb[hdr->factor] = LPMP_NAN;
 }
+// The same kernel for a factor whose own dense table is stored as floats (SWEEP_TAB32).  A copy, not a shared body: the f64
+// kernel above keeps its code to the instruction (tools/compare_kernel_asm.py), and the two differ in the three lines of the load.
+template <int L>
+__global__ void __launch_bounds__(256)
+sweep_pairwise_pk_f32_kernel(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
+                             double* __restrict__ lb, int64_t count, int stride) {
+  constexpr int G = DenseCfg<L>::G;
+  constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
+  constexpr int PIECES = 3 * (1 + PW_MAX_OPS);
+  __shared__ double2_t lds_pk[GPB][PIECES];
+  __shared__ double lds_m1[GPB][L];
+  __shared__ double lds_m2[GPB][L];
+  __shared__ double lds_q0[GPB][L];
+  __shared__ double lds_q1[GPB][L];
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
+  const bool live = idx < count;
+  const int c2 = g % CL, rl = g / CL;
+  load_packet<G>(lds_pk[grp], packets, nullptr, nullptr, idx, stride, live, g);
+  const UpdRec* hdr = reinterpret_cast<const UpdRec*>(&lds_pk[grp][0]);
+  const Op* lop = reinterpret_cast<const Op*>(&lds_pk[grp][3]);
+  const int n_recv = live ? (int)hdr->n_recv : 0;
+  const int n_send = live ? (int)hdr->n_send : 0;
+  const int R = live ? hdr->d0 : 0, C = live ? hdr->d1 : 0;
+  double* own_g = dual + (live ? hdr->dual_off : 0);
+  const double* T = cdata + (live ? hdr->const_off : 0);
+  double2_t t[NL];
+  if (live && (hdr->kind_flags & 15) == LPMP_F_PAIRWISE_POTTS) {   // diff * [a != b] (reference test/potts_factor.cpp:34-36)
+    const double diff = T[0];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int row = i * RPL + rl;
+      t[i].x = (row < R && 2 * c2 < C) ? (row == 2 * c2 ? 0.0 : diff) : LPMP_INF;
+      t[i].y = (row < R && 2 * c2 + 1 < C) ? (row == 2 * c2 + 1 ? 0.0 : diff) : LPMP_INF;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int row = i * RPL + rl;
+      const float* Tr = reinterpret_cast<const float*>(T) + (int64_t)row * C + 2 * c2;   // floats, widened
+      t[i].x = (row < R && 2 * c2 < C) ? (double)Tr[0] : LPMP_INF;
+      t[i].y = (row < R && 2 * c2 + 1 < C) ? (double)Tr[1] : LPMP_INF;
+    }
+  }
+  double m1 = g < R ? own_g[g] : 0.0;            // message vector of side 0, element g
+  double m2 = g < C ? own_g[R + g] : 0.0;        // message vector of side 1, element g
+  // receives: delta = 1 * theta_u; the unary gives it up, the factor's vector of that side takes it
+#pragma unroll
+  for (int k = 0; k < PW_MAX_OPS; ++k) {
+    if (k < n_recv) {
+      const Op& o = lop[k];
+      const int side = (o.info >> 5) & 1;
+      if (g < o.len) {
+        double* th = dual + o.peer_dual + g;
+        const double v = *th;
+        const double dl = 1.0 * v;
+        *th = v + -1.0 * dl;
+        if (side == 0) m1 += +1.0 * dl; else m2 += +1.0 * dl;
+      }
+      if (g == 0) lb[o.peer] = LPMP_NAN;
+    }
+  }
+  // both min-marginal parts of the state after the receives: q0[a] = min_b T[a][b] + m2[b], q1[b] = min_a T[a][b] + m1[a]
+  const double m1s = m1, m2s = m2;
+  if (g < L) { lds_m1[grp][g] = m1s; lds_m2[grp][g] = m2s; }
+  wave_sync();
+  {
+    const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_m2[grp][2 * c2]);
+    double vx = LPMP_INF, vy = LPMP_INF;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      double v = fmin(t[i].x + mv.x, t[i].y + mv.y);
+      v = row_allreduce_min<CL>(v);
+      if (c2 == 0) lds_q0[grp][i * RPL + rl] = v;
+      const double m1v = lds_m1[grp][i * RPL + rl];
+      vx = fmin(vx, t[i].x + m1v);
+      vy = fmin(vy, t[i].y + m1v);
+    }
+#pragma unroll
+    for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
+    if (rl == 0) { lds_q1[grp][2 * c2] = vx; lds_q1[grp][2 * c2 + 1] = vy; }
+  }
+  wave_sync();
+  const double q0 = g < L ? lds_q0[grp][g] : 0.0, q1 = g < L ? lds_q1[grp][g] : 0.0;
+  // sends: delta = omega * min-marginal of the snapshot
+#pragma unroll
+  for (int k = 0; k < PW_MAX_OPS; ++k) {
+    if (k < n_send) {
+      const Op& o = lop[n_recv + k];
+      const int side = (o.info >> 5) & 1;
+      if (g < o.len) {
+        const double dl = o.omega * (side == 0 ? m1s + q0 : m2s + q1);
+        double* th = dual + o.peer_dual + g;
+        *th += +1.0 * dl;
+        if (side == 0) m1 += -1.0 * dl; else m2 += -1.0 * dl;
+      }
+      if (g == 0) lb[o.peer] = LPMP_NAN;
+    }
+  }
+  if (g < R) own_g[g] = m1;
+  if (g < C) own_g[R + g] = m2;
+  if (live && g == 0) lb[hdr->factor] = LPMP_NAN;
+}
 
 // -------------------------------------------------------------------------------------------------
 // Lower bound (reference LP::LowerBound, LP_MP.h:1507-1518): per-factor bound, then a fixed-order sum.
@@ -2377,7 +2582,7 @@ sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ du
 // one wave per factor, any kind
 __global__ void __launch_bounds__(256)
 factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
-                 double* __restrict__ out, int64_t count) {
+                 double* __restrict__ out, int64_t count, int tab32) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t f = (int64_t)blockIdx.x * 4 + wave;
   if (f >= count) return;
@@ -2396,9 +2601,10 @@ factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual
     double best = LPMP_INF;
     if (kind == LPMP_F_PAIRWISE_DENSE) {
       const double* T = cdata + r.const_off;
+      const float* T32 = reinterpret_cast<const float*>(T);
       for (int a = 0; a < d0; ++a) {
         double v = LPMP_INF;
-        for (int b = lane; b < d1; b += 64) v = fmin(v, T[(int64_t)a * d1 + b] + d[d0 + b]);
+        for (int b = lane; b < d1; b += 64) v = fmin(v, (tab32 ? (double)T32[(int64_t)a * d1 + b] : T[(int64_t)a * d1 + b]) + d[d0 + b]);
         v = wave_min(v);
         best = fmin(best, d[a] + v);
       }
@@ -2437,7 +2643,7 @@ factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual
 // the same for an explicit list of factors (the ones whose tracked bound is stale)
 __global__ void __launch_bounds__(256)
 factor_lb_list_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
-                      double* __restrict__ out, const int32_t* __restrict__ list, int64_t count) {
+                      double* __restrict__ out, const int32_t* __restrict__ list, int64_t count, int tab32) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + wave;
   if (i >= count) return;
@@ -2456,7 +2662,7 @@ factor_lb_list_kernel(const LbRec* __restrict__ recs, const double* __restrict__
     double best = LPMP_INF;
     for (int a = 0; a < d0; ++a) {
       double v = LPMP_INF;
-      for (int b = lane; b < d1; b += 64) v = fmin(v, pw_cost(cdata, r.const_off, kind, d1, a, b) + d[d0 + b]);
+      for (int b = lane; b < d1; b += 64) v = fmin(v, pw_cost(cdata, r.const_off, kind, d1, a, b, tab32) + d[d0 + b]);
       v = wave_min(v);
       best = fmin(best, d[a] + v);
     }
@@ -2477,7 +2683,7 @@ lb_collect_stale_kernel(const double* __restrict__ lb, int64_t n, int32_t* __res
 template <int L>
 __global__ void __launch_bounds__(256)
 dense_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
-                double* __restrict__ out, int64_t first, int64_t count) {
+                double* __restrict__ out, int64_t first, int64_t count, int tab32) {
   constexpr int G = DenseCfg<L>::G;
   constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
   __shared__ double lds_m[GPB][2 * L];
@@ -2491,7 +2697,11 @@ dense_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual,
   const double* d = dual + r.dual_off;
   double2_t t[NL];
 #pragma unroll
-  for (int i = 0; i < NL; ++i) t[i] = live ? *reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g) : double2_t{0.0, 0.0};
+  for (int i = 0; i < NL; ++i) {
+    if (!live) t[i] = double2_t{0.0, 0.0};
+    else if (tab32) { const float2_t f = *reinterpret_cast<const float2_t*>(reinterpret_cast<const float*>(T) + (int64_t)i * 2 * G + 2 * g); t[i] = double2_t{(double)f.x, (double)f.y}; }
+    else t[i] = *reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g);
+  }
   for (int i = g; i < 2 * L; i += G) lds_m[grp][i] = live ? d[i] : 0.0;
   wave_sync();
   const double2_t m2 = *reinterpret_cast<const double2_t*>(&lds_m[grp][L + 2 * c2]);
@@ -2539,7 +2749,7 @@ primal_check_kernel(const PrimalLink* __restrict__ links, int64_t n, const int32
 // FactorContainer::EvaluatePrimal per factor: reparametrised cost at the factor's primal, +inf when a side is unset
 __global__ void __launch_bounds__(256)
 primal_cost_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
-                   const int32_t* __restrict__ primal, double* __restrict__ out, int64_t count) {
+                   const int32_t* __restrict__ primal, double* __restrict__ out, int64_t count, int tab32) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= count) return;
   const LbRec r = recs[f];
@@ -2549,8 +2759,33 @@ primal_cost_kernel(const LbRec* __restrict__ recs, const double* __restrict__ du
   double c;
   if (kind == LPMP_F_VECTOR) c = a < r.d0 ? d[a] : LPMP_INF;
   else if (a >= r.d0 || b >= r.d1) c = LPMP_INF;
-  else c = pw_cost(cdata, r.const_off, kind, r.d1, a, b) + d[a] + d[r.d0 + b];
+  else c = pw_cost(cdata, r.const_off, kind, r.d1, a, b, tab32) + d[a] + d[r.d0 + b];
   out[f] = c;
+}
+
+// Table precision (engine.cpp): table k of the chunk — n doubles at src[src_off] — becomes n floats at dst[dst_off]; one wave
+// per table.  An entry the mode refuses (strict: not exactly a float; both modes: a finite value that overflows float, a
+// nonzero one below FLT_MIN) puts its factor into *bad, which keeps the lowest such index.  +-inf pass through.
+__global__ void __launch_bounds__(256)
+narrow_tables_kernel(const NarrowRec* __restrict__ recs, int64_t n, const double* __restrict__ src, float* __restrict__ dst, int strict,
+                     int* __restrict__ bad) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const NarrowRec r = recs[k];
+  bool refuse = false;
+  for (int64_t i = lane; i < r.n; i += 64) {
+    const double x = src[r.src_off + i];
+    const float f = (float)x;                     // round to nearest even
+    const double ax = fabs(x);
+    if (ax < LPMP_INF) {                          // finite (NaN: outside the contract, passes)
+      if (fabsf(f) == __builtin_inff()) refuse = true;
+      else if (x != 0.0 && ax < 1.17549435082228750797e-38) refuse = true;
+      else if (strict && (double)f != x) refuse = true;
+    }
+    dst[r.dst_off + i] = f;
+  }
+  if (refuse) atomicMin(bad, r.factor);
 }
 
 // deterministic two-stage sum: block b sums a fixed contiguous slice in a fixed tree order
@@ -2589,6 +2824,10 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
   auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
   switch (kclass) {
     case KC_DENSE_BIG:
+      if (flags & SWEEP_TAB32) {
+        if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_f32_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+        else hipLaunchKernelGGL(sweep_dense_big_f32_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+      } else
       if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
       else hipLaunchKernelGGL(sweep_dense_big_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
       break;
@@ -2653,16 +2892,22 @@ bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, cons
                          double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s) {
   if (count <= 0) return true;
   auto blocks = [&](int per_block) { return dim3((unsigned)((count + per_block - 1) / per_block)); };
-  const bool nt = (flags & SWEEP_NT) != 0;
+  const bool nt = (flags & SWEEP_NT) != 0, t32 = (flags & SWEEP_TAB32) != 0;
   return with_class(kclass, [&](auto fam, auto width, auto var) {
     constexpr Family F = decltype(fam)::value; constexpr int L = decltype(width)::value; constexpr bool VAR = decltype(var)::value;
     if constexpr (F == FAM_PW) {
       // (the residual rule recomputes the min-marginals after every send: the op-by-op generic kernel does that)
       if ((flags & SWEEP_RESIDUAL) || stride <= 0) return false;
-      hipLaunchKernelGGL((sweep_pairwise_pk_kernel<L>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, dual, cdata, lb, count, stride);
+      if (t32) hipLaunchKernelGGL((sweep_pairwise_pk_f32_kernel<L>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, dual, cdata, lb, count, stride);
+      else hipLaunchKernelGGL((sweep_pairwise_pk_kernel<L>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, dual, cdata, lb, count, stride);
       return true;
     } else if constexpr (F == FAM_DENSE) {
       constexpr int K = recv_in_flight(L);
+      if (t32) {   // float tables: the same choice among the f32 kernels
+        if constexpr (!VAR) if (nt) { hipLaunchKernelGGL((sweep_dense_pk_f32_kernel<L, K, false, true>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags); return true; }
+        hipLaunchKernelGGL((sweep_dense_pk_f32_kernel<L, K, VAR, false>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags);
+        return true;
+      }
       // (run-time dims: rows are not line-aligned, consecutive 8-B loads share lines — non-temporal loads cost 9 % there)
       if constexpr (!VAR) if (nt) { hipLaunchKernelGGL((sweep_dense_pk_kernel<L, K, false, true>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags); return true; }
       hipLaunchKernelGGL((sweep_dense_pk_kernel<L, K, VAR, false>), blocks(256 / DenseCfg<L>::G), dim3(256), 0, s, packets, recs, ops, dual, cdata, lb, primal, count, stride, flags);
@@ -2735,7 +2980,7 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
                   const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s) {
-  const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr;
+  const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
   if (kclass == KC_GENERIC) return generic(chain_generic_kernel<64>, GenCtx<64>::THREADS);
@@ -2747,6 +2992,11 @@ bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch*
     // run-time-dims forms have none either (launch_sweep_packed)
     if constexpr (F == FAM_DENSE) {
       constexpr int K = recv_in_flight(L);
+      if (t32) {
+        if (mailbox) return packed(chain_dense_pk_f32_kernel<L, K, VAR, false, true>);
+        if constexpr (!VAR) if (nt) return packed(chain_dense_pk_f32_kernel<L, K, false, true, false>);
+        return packed(chain_dense_pk_f32_kernel<L, K, VAR, false, false>);
+      }
       if (mailbox) return packed(chain_dense_pk_kernel<L, K, VAR, false, true>);
       if constexpr (!VAR) if (nt) return packed(chain_dense_pk_kernel<L, K, false, true, false>);
       return packed(chain_dense_pk_kernel<L, K, VAR, false, false>);
@@ -2756,19 +3006,19 @@ bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch*
   });
 }
 
-void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s) {
+void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, int tab32, hipStream_t s) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(factor_lb_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, count);
+  hipLaunchKernelGGL(factor_lb_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, count, tab32);
 }
 
 // the streaming bound of square dense factors of 8 / 16 / 32 labels; false for every other L
-bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s) {
+bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, int tab32, hipStream_t s) {
   if (count <= 0) return true;
   return with_width<FAM_DENSE, false>(L, [&](auto, auto width, auto) {
     constexpr int W = decltype(width)::value;
     if constexpr (W >= 8) {
       constexpr int per_block = 256 / DenseCfg<W>::G;
-      hipLaunchKernelGGL(dense_lb_kernel<W>, dim3((unsigned)((count + per_block - 1) / per_block)), dim3(256), 0, s, recs, dual, cdata, out, first, count);
+      hipLaunchKernelGGL(dense_lb_kernel<W>, dim3((unsigned)((count + per_block - 1) / per_block)), dim3(256), 0, s, recs, dual, cdata, out, first, count, tab32);
       return true;
     } else return false;
   });
@@ -2779,9 +3029,9 @@ void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigne
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(lb_collect_stale_kernel, dim3((unsigned)blocks), dim3(256), 0, s, lb, n, list, counter);
 }
-void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s) {
+void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, int tab32, hipStream_t s) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(factor_lb_list_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, list, count);
+  hipLaunchKernelGGL(factor_lb_list_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, recs, dual, cdata, out, list, count, tab32);
 }
 
 static dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -2794,8 +3044,8 @@ void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(primal_check_kernel, blocks256(n), dim3(256), 0, s, links, n, primal, bad);
 }
-void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s) {
-  if (count > 0) hipLaunchKernelGGL(primal_cost_kernel, blocks256(count), dim3(256), 0, s, recs, dual, cdata, primal, out, count);
+void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s) {
+  if (count > 0) hipLaunchKernelGGL(primal_cost_kernel, blocks256(count), dim3(256), 0, s, recs, dual, cdata, primal, out, count, tab32);
 }
 
 // ---- rows layout (engine.cpp): a dense pairwise factor's table and its two message vectors in ONE contiguous row ----------
@@ -2832,6 +3082,10 @@ void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStrea
 void launch_rows_copy(const RowRec* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, cdata, dual, rows, what);
+}
+
+void launch_narrow_tables(const NarrowRec* recs, int64_t n, const double* src, float* dst, int strict, int* bad, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(narrow_tables_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, src, dst, strict, bad);
 }
 
 void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s) {

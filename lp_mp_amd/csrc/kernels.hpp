@@ -72,6 +72,8 @@ struct ShTableDesc { int64_t off; int32_t d0, d1; };
 struct LbRec { int64_t dual_off; int64_t const_off; int32_t d0, d1; int32_t kind_flags; int32_t pad; };
 // rows layout: one dense pairwise factor's place in the packed arrays and in the rows (kernels.hip, rows_copy_kernel)
 struct RowRec { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
+// table precision: one dense table's place in the chunk of doubles being narrowed and in the float buffer (narrow_tables_kernel)
+struct NarrowRec { int64_t src_off, dst_off, n; int32_t factor, pad; };
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
 // The bool ones return false when there is no kernel for the request (each says when, at its definition).
@@ -91,14 +93,18 @@ void debug_set_level_trace(long long* p);
 void launch_primal_init(const PrimalInit* list, int64_t n, int32_t* primal, hipStream_t s);
 void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal, hipStream_t s);
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
-void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, hipStream_t s);
+void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s);
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);
-void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, hipStream_t s);
-void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, hipStream_t s);
-bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, hipStream_t s);
+// tab32 (here and in launch_primal_cost): nonzero when the DENSE tables are stored as floats (the sweep kernels: SWEEP_TAB32)
+void launch_factor_lb_list(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list, int64_t count, int tab32, hipStream_t s);
+void launch_factor_lb(const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t count, int tab32, hipStream_t s);
+bool launch_dense_lb(int L, const LbRec* recs, const double* dual, const double* cdata, double* out, int64_t first, int64_t count, int tab32, hipStream_t s);
 void launch_sum_stage(const double* in, double* out, int64_t n, int64_t per_block, int64_t n_blocks, hipStream_t s);
 void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 void launch_rows_copy(const RowRec* recs, int64_t n, const double* cdata, double* dual, double* rows, int what, hipStream_t s);
 void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStream_t s);
+// table precision: n tables of src (doubles) become floats in dst; strict: refuse entries that are not exactly floats; *bad keeps the
+// lowest factor index with a refused entry (the caller sets it to INT32_MAX first)
+void launch_narrow_tables(const NarrowRec* recs, int64_t n, const double* src, float* dst, int strict, int* bad, hipStream_t s);
 
 }  // namespace lpmp

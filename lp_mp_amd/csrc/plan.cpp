@@ -658,7 +658,8 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
         side = mt.param;
         op.peer_const = e.role == 0 ? p.coff(peer) : -1;
         const bool unary_left = p.f_kind[f] == LPMP_F_VECTOR && e.role == 0;
-        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[peer] == own_d0 && p.f_dim1[peer] == own_d0 && (p.coff(peer) % 2) == 0)) clear_flag(all_dense[o]);
+        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[peer] == own_d0 && p.f_dim1[peer] == own_d0 && (p.coff(peer) % 2) == 0 &&
+              (!p.tables_f32 || (p.f_coff[peer] % 2) == 0))) clear_flag(all_dense[o]);   // (float tables all start 16-byte aligned: the class stays the f64 model's)
         if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS && p.f_dim0[peer] == own_d0)) clear_flag(all_potts[o]);
         if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DENSE && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(var_dense[o]);
         if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_POTTS && p.f_dim0[peer] == own_d0 && p.f_dim1[peer] == own_d0)) clear_flag(var_potts[o]);
@@ -688,12 +689,13 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
     // algorithmic bytes, counted per update as the reference executes it: own dual read + written
     // once, per receive the peer's table and both message vectors read and one written, per send one peer
     // vector read and written
+    const int64_t tab_entry_bytes = p.tables_f32 ? 4 : 8;   // a dense table entry as the device stores it
     auto op_bytes = [&](const Op& op, bool recv) -> int64_t {
       const int code = op.info & 15, pk = (op.info >> 8) & 15;
       if (code == LPMP_M_UNARY_PAIRWISE) {
         const int64_t L = op.len;
         // (a SHARED or DIFF peer: its scale; the table is on-chip)
-        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED || pk == LPMP_F_PAIRWISE_DIFF) ? 8 : 0));
+        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED || pk == LPMP_F_PAIRWISE_DIFF) ? 8 : 0));
         return 16 * L;
       }
       return 16 * (int64_t)op.pd0;
@@ -713,7 +715,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
     if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF)) {   // (SHARED, DIFF: its scale)
       bool sends_any = false;
       for (int64_t j = 0; j < ks; ++j) if (U.uom[u][j] != 0.0) { sends_any = true; break; }
-      if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? 8 * (int64_t)p.f_dim0[f] * p.f_dim1[f] : 8;
+      if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)p.f_dim0[f] * p.f_dim1[f] : 8;
     }
     __atomic_fetch_add(&U.rec_bytes[o], bytes, __ATOMIC_RELAXED);
     alg_local += bytes;

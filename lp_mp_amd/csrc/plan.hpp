@@ -145,6 +145,8 @@ constexpr int32_t UPD_PRIMAL = 1 << 17;       // UpdRec::kind_flags: the factor 
 constexpr int SWEEP_RESIDUAL = 1;   // --reparametrizationType residual
 constexpr int SWEEP_NT = 4;         // host-side selector: the model is far larger than the caches -> non-temporal variants
 constexpr int SWEEP_ADAPTIVE = 8;   // --reparametrizationType adaptive (generic kernels only)
+constexpr int SWEEP_TAB32 = 16;     // the DENSE pairwise tables are stored as floats (lpmp_set_table_precision): the f32 kernels, and the
+                                    // table reads of the generic kernels
 // bits 8-11: streaming dense class — LDS per wave sized for ceil(max label count of the launch / 64) * 64 labels (0: BIG_MAX_LABELS)
 constexpr int SWEEP_BIGDIM_SHIFT = 8, SWEEP_BIGDIM_MASK = 15 << SWEEP_BIGDIM_SHIFT;
 constexpr int sweep_bigdim_flags(int max_dim) { return max_dim <= 0 ? 0 : (((max_dim + 63) / 64) << SWEEP_BIGDIM_SHIFT) & SWEEP_BIGDIM_MASK; }
@@ -280,6 +282,9 @@ struct Plan {
   // from the free memory of its device, and a class whose mailbox would not fit is planned with completion flags only
   // (-1: no limit)
   int64_t mailbox_budget_bytes = -1;
+  // dense pairwise tables are stored as floats on the device (lpmp_set_table_precision / lpmp_plan_set_table_precision): 4 instead
+  // of 8 bytes per entry in the byte accounting of every schedule made from now on — classes, levels and records are the same
+  bool tables_f32 = false;
   // Engine-private placement of factors on the device (engine.cpp, rows layout): where a factor's constants start relative
   // to the const base pointer and its duals relative to the dual base pointer, in doubles — possibly in ANOTHER allocation
   // (the kernels only ever form base + offset).  Empty: the packed offsets f_coff / f_doff.  Sizes always come from f_*.

@@ -38,6 +38,19 @@ KERNEL_NAMES = ["sweep_generic_kernel<64>", "sweep_dense_pk_kernel<4, 4, false",
                 "sweep_shared_pk_kernel<4", "sweep_shared_pk_kernel<8", "sweep_shared_pk_kernel<16", "sweep_shared_pk_kernel<32",
                 "sweep_diff_kernel"]
 MEM_HOST, MEM_DEVICE = 0, 1
+# lpmp_set_table_precision (include/lpmp_engine.h): how the entries of DENSE pairwise tables are stored on the device
+TABLES_F64, TABLES_F32, TABLES_F32_ROUND = 0, 1, 2
+TABLE_PRECISIONS = {"f64": TABLES_F64, "f32": TABLES_F32, "f32_round": TABLES_F32_ROUND}
+# classes whose kernels read dense tables have an f32 kernel of their own (name: ..._f32_kernel, same template arguments)
+_F32_KERNEL_CLASSES = set(range(1, 5)) | set(range(9, 13)) | {17} | set(range(19, 23))
+
+
+def _table_precision_code(p) -> int:
+    if isinstance(p, str):
+        if p not in TABLE_PRECISIONS:
+            raise ValueError(f"table_precision: one of {sorted(TABLE_PRECISIONS)}, not {p!r}")
+        return TABLE_PRECISIONS[p]
+    return int(p)
 
 EXPORTS = [
     "lpmp_last_error", "lpmp_version", "lpmp_experiment_build", "lpmp_set_rows_layout", "lpmp_rows_layout", "lpmp_lower_bound_recomputed", "lpmp_plan_create", "lpmp_plan_destroy", "lpmp_plan_n_factors",
@@ -58,6 +71,7 @@ EXPORTS = [
     "lpmp_set_speculation", "lpmp_speculation_stats", "lpmp_chain_cache_bytes",
     "lpmp_set_persistent_launches", "lpmp_persistent_launches", "lpmp_device_identity",
     "lpmp_plan_suggest_order", "lpmp_graph_colour_major_order", "lpmp_graph_refine_partition",
+    "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
 ]
 
 
@@ -155,6 +169,10 @@ def lib():
         if hasattr(L, "lpmp_set_rows_layout"):
             L.lpmp_set_rows_layout.argtypes = [C.c_void_p, C.c_int]
             L.lpmp_rows_layout.argtypes = [C.c_void_p]
+        if hasattr(L, "lpmp_set_table_precision"):   # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_set_table_precision.argtypes = [C.c_void_p, C.c_int]
+            L.lpmp_table_precision.argtypes = [C.c_void_p]
+            L.lpmp_plan_set_table_precision.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "lpmp_set_persistent_launches"):
             L.lpmp_set_persistent_launches.argtypes = [C.c_void_p, C.c_int]
             L.lpmp_persistent_launches.argtypes = [C.c_void_p]
@@ -201,7 +219,9 @@ def _chk(rc: int):
 class Plan:
     """Host-only analysis of a model: orderings, weights, level schedule (no GPU needed)."""
 
-    def __init__(self, model: Optional[FlatModel] = None, _handle=None, _owner=None):
+    def __init__(self, model: Optional[FlatModel] = None, _handle=None, _owner=None, table_precision=None):
+        """``table_precision``: "f64" (default) / "f32" / "f32_round" — the byte accounting of a device that stores the dense
+        tables as floats (lpmp_plan_set_table_precision); classes, levels and records do not depend on it"""
         self.L = lib()
         self._owner = _owner
         if _handle is not None:
@@ -213,6 +233,8 @@ class Plan:
             _chk(self.L.lpmp_plan_create(C.addressof(cs), C.addressof(h)))
             self.h = h.value
             self._own = True
+            if table_precision is not None:
+                _chk(self.L.lpmp_plan_set_table_precision(self.h, _table_precision_code(table_precision)))
 
     def __del__(self):
         if getattr(self, "_own", False) and getattr(self, "h", None):
@@ -399,11 +421,16 @@ class Engine:
     def set_stream(self, stream_ptr: int):
         _chk(self.L.lpmp_set_stream(self.h, C.c_void_p(stream_ptr)))
 
-    def upload(self, model: FlatModel, const_dev: Optional[int] = None, dual_dev: Optional[int] = None, keep=None, rows_layout: Optional[bool] = None):
+    def upload(self, model: FlatModel, const_dev: Optional[int] = None, dual_dev: Optional[int] = None, keep=None, rows_layout: Optional[bool] = None,
+               table_precision=None):
         """``rows_layout``: dense pairwise factors as [table | m1 | m2] rows of an engine-private buffer (lpmp_set_rows_layout);
-        None: whatever LPMP_ROWS_LAYOUT says (default off)"""
+        None: whatever LPMP_ROWS_LAYOUT says (default off).
+        ``table_precision``: "f64" / "f32" (strict: every dense table entry must be exactly a float) / "f32_round" — dense tables as
+        floats on the device, widened in the load, all arithmetic in double (lpmp_set_table_precision); None: as set before (f64)"""
         if rows_layout is not None:
             _chk(self.L.lpmp_set_rows_layout(self.h, 1 if rows_layout else 0))
+        if table_precision is not None:
+            _chk(self.L.lpmp_set_table_precision(self.h, _table_precision_code(table_precision)))
         cs = model.c_struct()
         if const_dev is not None:
             cs.const_data = const_dev
@@ -421,6 +448,11 @@ class Engine:
     @property
     def rows_layout(self) -> bool:
         return bool(self.L.lpmp_rows_layout(self.h))
+
+    def table_precision(self) -> str:
+        """"f64" / "f32" / "f32_round": how the uploaded model's dense tables are stored (lpmp_table_precision)"""
+        code = int(self.L.lpmp_table_precision(self.h))
+        return next(k for k, v in TABLE_PRECISIONS.items() if v == code)
 
     @property
     def plan(self) -> Plan:
@@ -625,9 +657,12 @@ class Engine:
         chain = np.zeros(N_KCLASS, np.int64)
         _chk(self.L.lpmp_get_chain_launches(self.h, N_KCLASS, chain.ctypes.data))
         out = {}
+        f32 = hasattr(self.L, "lpmp_table_precision") and int(self.L.lpmp_table_precision(self.h)) != TABLES_F64
         for c in range(N_KCLASS):
             if arrs[0][c] > 0:
                 name = KERNEL_NAMES[c]
+                if f32 and c in _F32_KERNEL_CLASSES:     # float tables: the kernels of their own the launch wrappers select
+                    name = name.replace("_kernel", "_f32_kernel")
                 if chain[c] > 0:             # joined passes as persistent launches: plain table loads, agent-scope dual accesses
                     name = name.replace("sweep_", "chain_")
                     if not name.endswith(">") and "dense" in name:
@@ -639,7 +674,7 @@ class Engine:
                     continue
                 if not name.endswith(">") and "<" in name:       # exact dense kernels: plain / non-temporal form
                     name += ", true>" if self.L.lpmp_streaming_access(self.h) == 1 else ", false>"
-                elif name == "sweep_dense_big_kernel":
+                elif name in ("sweep_dense_big_kernel", "sweep_dense_big_f32_kernel"):
                     name += "<true>" if self.L.lpmp_streaming_access(self.h) == 1 else "<false>"
                 out[KCLASS_NAMES[c]] = dict(kernel=name, ms=float(ms[c]), launches=int(arrs[0][c]),
                                             factors=int(arrs[1][c]), receives=int(arrs[2][c]), bytes=int(arrs[3][c]))

@@ -227,6 +227,14 @@ class LP:
         self._dirty = True
         self._begun = False
         self._duals_host: Optional[np.ndarray] = None
+        self._table_precision = None
+
+    def set_table_precision(self, precision):
+        """"f64" / "f32" (strict) / "f32_round": dense pairwise tables as floats on the device, widened in the load, all arithmetic
+        in double (Engine.upload, table_precision).  To be called before the first pass: afterwards the model is on the device."""
+        if self._engine is not None and not self._dirty:
+            raise RuntimeError("set_table_precision: the model is on the device already (call it before the first pass)")
+        self._table_precision = precision
 
     # -- problem construction (reference LP_MP.h:239-285, :698-702) ---------------------------------------
     def add_shared_table(self, table) -> int:
@@ -393,7 +401,7 @@ class LP:
             self._engine.set_speculation(self._speculation)
         if self._dirty:
             self._model = self.flat_model()
-            self._engine.upload(self._model)
+            self._engine.upload(self._model, table_precision=self._table_precision)
             self._dirty = False
         self._engine.set_inner_iterations(self._inner)
         self._engine.set_reparametrization_type(self._rtype)

@@ -205,6 +205,21 @@ class FlatModel:
         ``np.float64(scale) * D[a - b + d1 - 1]`` — the yardstick of the kind, as expand_shared() is for SHARED factors"""
         return self._expand(F_PAIRWISE_DIFF, "expand_diff")
 
+    def with_f32_tables(self) -> "FlatModel":
+        """the same model with every entry of a DENSE pairwise table rounded to float32 (nearest even) and widened again —
+        the model an engine with ``table_precision="f32_round"`` computes on, bit for bit, and the yardstick of both f32 modes.
+        Potts scalars, SHARED / DIFF scales, the shared pool and the duals are untouched (shared with ``self``); a model whose
+        tables are float-valued already comes back with equal values."""
+        import dataclasses
+        if self.const_data is None:
+            raise ValueError("with_f32_tables: the model has no host constants")
+        off = self.const_offsets()
+        dense = np.repeat(self.f_kind == F_PAIRWISE_DENSE, np.diff(off))
+        const = np.array(self.const_data, np.float64, copy=True)
+        with np.errstate(over="ignore"):
+            const[dense] = const[dense].astype(np.float32).astype(np.float64)
+        return dataclasses.replace(self, const_data=const, _keep=[])
+
     def with_factor_order(self, rank: np.ndarray) -> "FlatModel":
         """the same factors, messages and costs with the factor relations REPLACED by a chain through all factors in the order
         ``rank[f]`` (position of factor f, e.g. Plan.suggest_order): AddFactorRelation(by_rank[i], by_rank[i + 1]) for consecutive

@@ -109,11 +109,14 @@ def build_lp_from_uai(text: str, device: int = 0, order: str = "index", share_ta
     return lp
 
 
-def solve_uai(text: str, device: int = 0, share_tables: bool = False, diff_tables: bool = False, **visitor_options):
+def solve_uai(text: str, device: int = 0, share_tables: bool = False, diff_tables: bool = False, table_precision=None, **visitor_options):
     """MAP estimation for a model in UAI format with the message-passing rounding solver — the reference's
     ``MpRoundingSolver<Solver<LP<FMC_SRMP>, StandardVisitor>>`` + ``UaiMrfInput::ParseString`` (test/graphical_model.cpp:
-    47-56).  Returns (lower bound, primal cost, labeling of the variables)."""
+    47-56).  Returns (lower bound, primal cost, labeling of the variables).
+    ``table_precision``: "f32" / "f32_round" store the dense tables as floats on the device (LP.set_table_precision)."""
     lp = build_lp_from_uai(text, device, share_tables=share_tables, diff_tables=diff_tables)
+    if table_precision is not None:
+        lp.set_table_precision(table_precision)
     s = LPM.MpRoundingSolver(lp, LPM.StandardVisitor(**visitor_options))
     s.Solve()
     n = len(parse_uai(text)[0])
