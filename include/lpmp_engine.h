@@ -82,6 +82,17 @@ int lpmp_plan_schedule_info(lpmp_plan* p, int direction, int mode, int64_t* n_le
 #define LPMP_KCLASS_COUNT 28
 int lpmp_plan_schedule_classes(lpmp_plan* p, int direction, int mode, int64_t* factors /*[LPMP_KCLASS_COUNT]*/);
 
+/* Banded DIFF vectors (class diff).  The band [lo, hi] of pool entry `table` as a difference vector D of n entries:
+ * every entry below lo equals D[0] and every entry above hi equals D[n - 1], compared by the bits of the doubles; lo = n and
+ * hi = n - 1 for a constant vector.  banded: 1 when hi - lo + 1 <= n / 4 (such vectors are reduced in O(labels * width) per
+ * receive with the same result to the bit), 0 when not, -1 (and lo 0, hi -1) when no DIFF factor references the entry. */
+int lpmp_plan_n_shared_tables(const lpmp_plan* p);
+int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t* hi, int* banded);
+/* launches of class diff in that sweep, how many of them run the banded kernel (every receive of every record of the launch
+ * references a banded vector; none when LPMP_NO_DIFF_BAND was set as the plan was made), and the receives of both */
+int lpmp_plan_diff_band_info(lpmp_plan* p, int direction, int mode, int64_t* diff_launches, int64_t* band_launches,
+                             int64_t* diff_receives, int64_t* band_receives);
+
 /* the same summary for an iterator-range pass (LP_MP.h:981-1005) given as factor list + weight rows + receive-mask
  * rows, without a device: what lpmp_schedule_create[_fused] would build.  Arguments as lpmp_compute_pass_custom. */
 int lpmp_plan_custom_schedule_info(lpmp_plan* p, int64_t n, const int32_t* factors, const int64_t* omega_off,
@@ -329,6 +340,8 @@ int lpmp_get_kernel_timing(lpmp_engine* e, int n_classes, double* ms /*[n]*/, in
 int lpmp_reset_kernel_timing(lpmp_engine* e);
 /* of the launches reported per class: how many were persistent launches of the chain executor */
 int lpmp_get_chain_launches(lpmp_engine* e, int n_classes, int64_t* chain_launches /*[n]*/);
+/* of the launches reported for class diff: how many ran the banded kernel (sweep_diff_band_kernel) */
+int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches);
 
 /* ---- boundary step of the partitioned (multi-GPU) sweep, DESIGN.md 7 -------------------------------------------------
  * One process per GPU owns one part of the factor graph (lp_mp_amd/multi_gpu.py builds the parts; a C++ host can do

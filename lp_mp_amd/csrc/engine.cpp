@@ -118,7 +118,7 @@ static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 
   return v;
 }
 
-struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0; };
+struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0; };
 
 }  // namespace
 
@@ -328,7 +328,7 @@ struct lpmp_engine {
   }
   bool timing = false;
   ClassTiming ct[KC_COUNT];
-  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; };
+  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false; };   // band: sweep_diff_band_kernel
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
 
@@ -374,7 +374,7 @@ struct lpmp_engine {
       HIP_CHECK(hipEventSynchronize(p.b));
       float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
       ClassTiming& c = ct[p.cls];
-      c.ms += ms; c.launches++; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
+      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
       event_pool.push_back(p.a); event_pool.push_back(p.b);
     }
     pending.clear();
@@ -665,7 +665,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
         throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
     }
     else if (lr.kclass == KC_DIFF)     // (LDS by the launch's label counts, as the streaming class)
-      launch_sweep_diff(s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
+      launch_sweep_diff(lr.diff_band, s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
     else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
                               e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
@@ -676,7 +676,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
     }
     if (timed) {
       HIP_CHECK(hipEventRecord(b, stream));
-      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes});
+      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes, lr.kclass == KC_DIFF && lr.diff_band});
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -1107,6 +1107,31 @@ int lpmp_plan_schedule_classes(lpmp_plan* p, int d, int mode, int64_t* factors) 
   });
 }
 
+int lpmp_plan_n_shared_tables(const lpmp_plan* p) { return p ? p->p.n_shared : 0; }
+int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t* hi, int* banded) {
+  return guarded([&] {
+    if (!p || table < 0 || table >= p->p.n_shared) throw std::runtime_error("bad argument");
+    const bool diff = p->p.sh_banded[(size_t)table] >= 0;
+    if (lo) *lo = diff ? p->p.sh_lo[(size_t)table] : 0;
+    if (hi) *hi = diff ? p->p.sh_hi[(size_t)table] : -1;
+    if (banded) *banded = p->p.sh_banded[(size_t)table];
+  });
+}
+int lpmp_plan_diff_band_info(lpmp_plan* p, int d, int mode, int64_t* diff_launches, int64_t* band_launches, int64_t* diff_receives,
+                             int64_t* band_receives) {
+  return guarded([&] {
+    if (!p || d < 0 || d > 1 || mode < 0 || mode >= LPMP_REPAM_COUNT) throw std::runtime_error("bad argument");
+    plan_schedule(p, d, mode);
+    int64_t v[4] = {0, 0, 0, 0};
+    for (const auto& lr : p->sched_cache[d][mode].launches)
+      if (lr.kclass == KC_DIFF) { ++v[0]; v[2] += lr.n_recv; if (lr.diff_band) { ++v[1]; v[3] += lr.n_recv; } }
+    if (diff_launches) *diff_launches = v[0];
+    if (band_launches) *band_launches = v[1];
+    if (diff_receives) *diff_receives = v[2];
+    if (band_receives) *band_receives = v[3];
+  });
+}
+
 int lpmp_plan_custom_schedule_info(lpmp_plan* p, int64_t n, const int32_t* factors, const int64_t* om_off, const double* om,
                                    const int64_t* mk_off, const uint8_t* mk, int fuse, int64_t* n_levels, int64_t* n_launches,
                                    int64_t* n_recv, int64_t* n_send, int64_t* alg_bytes) {
@@ -1446,7 +1471,11 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
       std::vector<int64_t> sf;
       for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
-      const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared];
+      // Every pool entry of this copy has one 8-byte band word {int32 lo, int32 hi} in front of it: sweep_diff_band_kernel learns
+      // the band of a DIFF vector from the word before the offset in the factor's cell (entries no DIFF factor references: an
+      // empty band, never read).  Entry t starts at pool_at(t).
+      const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
+      auto pool_at = [&](int32_t t) { return p.sh_off[(size_t)t] + t + 1; };
       e->d_shared.alloc((size_t)(2 * n_sf + n_pool));
       if ((((uintptr_t)e->d_shared.get() - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
       const int64_t base = (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8);
@@ -1455,15 +1484,24 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       for (int64_t k = 0; k < n_sf; ++k) {
         const int64_t f = sf[(size_t)k];
         cells[(size_t)(2 * k)] = pl->p.dev_coff[f];   // (the packed offset, or the factor's cell of the compact constants: table precision)
-        cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + p.sh_off[(size_t)p.f_table[f]];
+        cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + pool_at(p.f_table[f]);
         pl->p.dev_coff[f] = base + 2 * k;
       }
       h2d(e->d_shared, cells.data(), cells.size() * sizeof(int64_t), e->stream);
-      h2d(e->d_shared + 2 * n_sf, p.sh_data.data(), (size_t)n_pool * sizeof(double), e->stream);
+      {
+        std::vector<double> pool((size_t)n_pool);
+        for (int32_t t = 0; t < p.n_shared; ++t) {
+          const int32_t word[2] = {p.sh_lo[(size_t)t], p.sh_hi[(size_t)t]};
+          static_assert(sizeof word == sizeof(double), "band word");
+          std::memcpy(&pool[(size_t)(pool_at(t) - 1)], word, sizeof word);
+          std::copy(p.sh_data.begin() + p.sh_off[(size_t)t], p.sh_data.begin() + p.sh_off[(size_t)t + 1], pool.begin() + pool_at(t));
+        }
+        h2d(e->d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), e->stream);
+      }
       launch_shared_cells(e->d_shared, n_sf, e->d_const, e->stream);
       HIP_CHECK(hipGetLastError());
       std::vector<ShTableDesc> desc((size_t)p.n_shared);
-      for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + p.sh_off[(size_t)t], p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
+      for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + pool_at(t), p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
       e->d_sh_desc.alloc(desc.size());
       h2d(e->d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDesc), e->stream);
     }
@@ -2311,6 +2349,15 @@ int lpmp_get_chain_launches(lpmp_engine* e, int n, int64_t* chain_launches) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
     e->drain_timing();
     for (int c = 0; c < n && c < KC_COUNT; ++c) chain_launches[c] = e->ct[c].chain_launches;
+  });
+}
+// of the launches lpmp_get_kernel_timing reports for class diff: how many ran sweep_diff_band_kernel
+int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches) {
+  return guarded([&] {
+    if (!e || !band_launches) throw std::runtime_error("null argument");
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->drain_timing();
+    *band_launches = e->ct[KC_DIFF].band_launches;
   });
 }
 int lpmp_reset_kernel_timing(lpmp_engine* e) {

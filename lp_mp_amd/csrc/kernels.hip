@@ -2251,11 +2251,104 @@ __device__ __forceinline__ void diff_minplus_all(const double* __restrict__ sD, 
     else diff_minplus<1, SIDE1>(sD, mo, q, x0, Lr, Lo, C, lane);
   }
 }
+// ---- banded form (sweep_diff_band_kernel): D has constant tails, D[k] = D[0] to the bit for k < lo and D[k] = D[n - 1] for k > hi
+// (plan.cpp, diff_band; every receive of the launch has a band of at most n / DIFF_BAND_DIV entries).  fl(c + m) is non-decreasing
+// in m, so the minimum over the y of a tail is c + (the minimum of m_o over them), bit for bit, and those y are a prefix or a
+// suffix of m_o: q[x] = min(window terms, c + pre[...], c + suf[...]) with pre / suf the prefix / suffix minima of m_o.
+__device__ __forceinline__ double shfl_up_f64(double v, int d) {
+  return __hiloint2double(__shfl_up(__double2hiint(v), d, 64), __shfl_up(__double2loint(v), d, 64));
+}
+__device__ __forceinline__ double shfl_down_f64(double v, int d) {
+  return __hiloint2double(__shfl_down(__double2hiint(v), d, 64), __shfl_down(__double2loint(v), d, 64));
+}
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+  return __hiloint2double(__shfl(__double2hiint(v), src, 64), __shfl(__double2loint(v), src, 64));
+}
+// pre[i] = min(mo[0 .. i]), suf[i] = min(mo[i .. Lo - 1]): a wave scan per 64 labels, the chunks joined by a carry
+__device__ __forceinline__ void diff_band_scans(const double* __restrict__ mo, double* __restrict__ pre, double* __restrict__ suf, int Lo, int lane) {
+  double carry = LPMP_INF;
+  for (int c0 = 0; c0 < Lo; c0 += 64) {
+    const int i = c0 + lane;
+    double v = i < Lo ? mo[i] : LPMP_INF;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const double t = shfl_up_f64(v, d); if (lane >= d) v = fmin(v, t); }
+    v = fmin(v, carry);
+    if (i < Lo) pre[i] = v;
+    carry = shfl_f64(v, 63);
+  }
+  carry = LPMP_INF;
+  for (int c0 = ((Lo - 1) >> 6) << 6; c0 >= 0; c0 -= 64) {
+    const int i = c0 + lane;
+    double v = i < Lo ? mo[i] : LPMP_INF;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const double t = shfl_down_f64(v, d); if (lane + d < 64) v = fmin(v, t); }
+    v = fmin(v, carry);
+    if (i < Lo) suf[i] = v;
+    carry = shfl_f64(v, 0);
+  }
+}
+// q[x] for the own labels x = x0 + lane + 64 i, i < NI.  sB[k - lo] = scale * D[k] for k in [lo, hi], cL / cR = scale * D[0] /
+// scale * D[n - 1].  The order of the fmin is fixed: the window entries k = lo ... hi ascending (entry k meets y = x + C - 1 - k on
+// side 0, y = k + x - C + 1 on side 1; a y outside [0, Lo) is no term), then the prefix tail, then the suffix tail.  sB[k - lo]
+// is a broadcast, consecutive lanes read consecutive doubles of m_o; indices are clamped before they are used, a lane beyond Lr
+// runs along and stores nothing.
+template <int NI, bool SIDE1>
+__device__ __forceinline__ void diff_band_minplus(const double* __restrict__ sB, const double* __restrict__ mo, const double* __restrict__ pre,
+                                                  const double* __restrict__ suf, double* __restrict__ q, int x0, int Lr, int Lo, int C,
+                                                  int lo, int hi, double cL, double cR, int lane) {
+  const int x = x0 + lane;
+  double v[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) v[i] = LPMP_INF;
+#pragma unroll 2
+  for (int k = lo; k <= hi; ++k) {
+    const double s = sB[k - lo];
+    const int y0 = SIDE1 ? k + x - C + 1 : x + C - 1 - k;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int y = y0 + 64 * i;
+      const bool in = (unsigned)y < (unsigned)Lo;
+      const double t = s + mo[in ? y : 0];
+      v[i] = in ? fmin(v[i], t) : v[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int xi = x + 64 * i;
+    const int jp = SIDE1 ? lo + xi - C : xi + C - 2 - hi;       // the tail's y are [0, jp] ...
+    const int js = SIDE1 ? hi + xi - C + 2 : xi + C - lo;       // ... and [js, Lo)
+    const double tp = (SIDE1 ? cL : cR) + pre[min(max(jp, 0), Lo - 1)];
+    const double ts = (SIDE1 ? cR : cL) + suf[min(max(js, 0), Lo - 1)];
+    if (jp >= 0) v[i] = fmin(v[i], tp);
+    if (js <= Lo - 1) v[i] = fmin(v[i], ts);
+    if (xi < Lr) q[xi] = v[i];
+  }
+}
+template <bool SIDE1>
+__device__ __forceinline__ void diff_band_minplus_all(const double* __restrict__ sB, const double* __restrict__ mo, const double* __restrict__ pre,
+                                                      const double* __restrict__ suf, double* __restrict__ q, int Lr, int Lo, int C,
+                                                      int lo, int hi, double cL, double cR, int lane) {
+  for (int x0 = 0; x0 < Lr; x0 += 256) {
+    const int n = (Lr - x0 + 63) >> 6;
+    if (n >= 4) diff_band_minplus<4, SIDE1>(sB, mo, pre, suf, q, x0, Lr, Lo, C, lo, hi, cL, cR, lane);
+    else if (n == 3) diff_band_minplus<3, SIDE1>(sB, mo, pre, suf, q, x0, Lr, Lo, C, lo, hi, cL, cR, lane);
+    else if (n == 2) diff_band_minplus<2, SIDE1>(sB, mo, pre, suf, q, x0, Lr, Lo, C, lo, hi, cL, cR, lane);
+    else diff_band_minplus<1, SIDE1>(sB, mo, pre, suf, q, x0, Lr, Lo, C, lo, hi, cL, cR, lane);
+  }
+}
 constexpr int DIFF_WAVES_PER_SIMD = 6;
 // waves (= records) per workgroup: BIG_WAVES while their LDS stays within 64 KiB, two above.  ldim is a multiple of 64, so the
 // last size with four waves is 384 labels (60 KiB; 448 would be 70 KiB): launches of more than 384 labels run two waves, 40 KiB at 512
 static int diff_waves(int flags) { return (size_t)BIG_WAVES * 5 * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
 static size_t diff_lds_bytes(int flags) { return (size_t)diff_waves(flags) * 5 * big_ldim(flags) * sizeof(double); }
+// banded form: LDS of one wave = theta, m_o, q, pre, suf and the band of sD (at most n / DIFF_BAND_DIV < ldim / 2 entries), ldim
+// doubles each: four waves up to 320 labels (60 KiB), two above (48 KiB at 512)
+constexpr int DIFF_BAND_SLABS = 6;
+static_assert(DIFF_BAND_DIV >= 2, "the band of sD must fit one slab of ldim doubles: (2 ldim - 1) / DIFF_BAND_DIV <= ldim");
+static int diff_band_waves(int flags) { return (size_t)BIG_WAVES * DIFF_BAND_SLABS * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
+static size_t diff_band_lds_bytes(int flags) { return (size_t)diff_band_waves(flags) * DIFF_BAND_SLABS * big_ldim(flags) * sizeof(double); }
+// the band word {lo, hi} the engine keeps in front of every pool entry of its own copy (engine.cpp, lpmp_upload_model)
+__device__ __forceinline__ int2 diff_band_word(const double* __restrict__ cdata, int64_t off) { return *reinterpret_cast<const int2*>(cdata + off - 1); }
 
 __global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_WAVES_PER_SIMD)
 sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
@@ -2311,6 +2404,123 @@ sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, d
       const int64_t pc = uni64<64>(nxt.peer_const);
       nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
     }
+    wave_sync();
+    double pb = LPMP_INF;                              // peer's bound after this receive
+    for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
+      const double msv = j == 0 ? ms_pre[0] : j == 1 ? ms_pre[1] : ld_dual<A>(ms + i), qv = S.q[i];
+      const double delta = msv + qv;                   // omega = 1: delta = min-marginal
+      S.theta[i] += delta;
+      const double mn = msv - delta;
+      st_dual<A>(ms + i, mn);
+      pb = fmin(pb, mn + qv);
+    }
+    pb = wave_min(pb);
+    if (lane == 0) st_lb<A>(lb + op.peer, pb);
+    wave_sync();
+  }
+  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
+    double bv = LPMP_INF; int bi = 0x7fffffff;
+    for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
+    const double mn = wave_min(bv);
+    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
+    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
+  }
+  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
+  for (int i = lane; i < Lr; i += 64) S.q[i] = S.theta[i];
+  for (int k = 0; k < rec.n_send; ++k) {
+    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+    for (int i = lane; i < Lr; i += 64) {
+      const double delta = op.omega * S.q[i];
+      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+      S.theta[i] -= delta;
+    }
+    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
+  }
+  if (flags & SWEEP_RESIDUAL) {
+    double residual = 0.0;
+    for (int k = 0; k < rec.n_send; ++k) {
+      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+      residual += op.omega;
+      for (int i = lane; i < Lr; i += 64) {
+        const double delta = residual * S.theta[i];
+        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+        S.theta[i] -= delta;
+      }
+    }
+  }
+  double ob = LPMP_INF;
+  for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
+  ob = wave_min(ob);
+  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+}
+// The banded kernel: sweep_diff_kernel with the reduction of a receive replaced, nothing else (its own copy of the body: the full
+// kernel keeps its code to the instruction, tools/compare_kernel_asm.py).  LDS of one wave: theta, m_o, q, pre, suf, the band of sD.
+__global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_WAVES_PER_SIMD)
+sweep_diff_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
+                       const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
+                       int64_t first, int64_t count, int flags) {
+  constexpr int A = ACC_PLAIN;
+  extern __shared__ double big_lds_pool[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  if (idx >= count) return;
+  const int ldim = big_ldim(flags);
+  double* const slab = big_lds_pool + (size_t)wave * DIFF_BAND_SLABS * ldim;
+  BigLds S{slab, slab + ldim, slab + 2 * ldim};
+  double* const pre = slab + 3 * ldim; double* const suf = slab + 4 * ldim; double* const sB = slab + 5 * ldim;
+  UpdRec rec = recs[first + idx];
+  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
+  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
+  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
+  auto uni_op = [](Op o) {
+    o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
+    o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
+    return o;
+  };
+  const int Lr = rec.d0;
+  double* own_g = dual + rec.dual_off;
+  for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
+  Op nxt{};
+  double nscale = 0.0; int64_t noff = 0;               // the next receive's two constant words {scale, offset of D}
+  int2 nband = make_int2(0, -1);                       // ... and the band word of its D
+  if (rec.n_recv > 0) {
+    nxt = ops[rec.op_begin];
+    const int64_t pc = uni64<64>(nxt.peer_const);
+    nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+    nband = diff_band_word(cdata, uni64<64>(noff));
+  }
+  for (int k = 0; k < rec.n_recv; ++k) {
+    const Op op = uni_op(nxt);
+    const double scale = uni_f64(nscale);
+    const double* D = cdata + uni64<64>(noff);
+    const int lo = uni<64>(nband.x), hi = uni<64>(nband.y);
+    if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's reduction starts
+    const int side = (op.info >> 5) & 1;
+    const int R = op.pd0, C = op.pd1;
+    double* ms = dual + op.peer_dual + (side == 0 ? 0 : R);
+    const double* mo = dual + op.peer_dual + (side == 0 ? R : 0);
+    const int Lo = side == 0 ? C : R;
+    double ms_pre[2];                                  // the own side m_s is requested together with m_o and D
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(ms + lane + 64 * j) : 0.0;
+    for (int i = lane; i < Lo; i += 64) S.mo[i] = ld_dual<A>(mo + i);
+    // the ONE multiply per entry, for the band only; the two tail constants are the products of the end entries
+    for (int i = lo + lane; i <= hi; i += 64) sB[i - lo] = scale * D[i];
+    const double cL = scale * D[0], cR = scale * D[R + C - 2];
+    wave_sync();
+    if (k + 1 < rec.n_recv) {                          // the next op has arrived with m_o: its constants travel during the reduction ...
+      const int64_t pc = uni64<64>(nxt.peer_const);
+      nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+    }
+    diff_band_scans(S.mo, pre, suf, Lo, lane);
+    wave_sync();
+    if (side == 0) diff_band_minplus_all<false>(sB, S.mo, pre, suf, S.q, Lr, Lo, C, lo, hi, cL, cR, lane);
+    else diff_band_minplus_all<true>(sB, S.mo, pre, suf, S.q, Lr, Lo, C, lo, hi, cL, cR, lane);
+    if (k + 1 < rec.n_recv) nband = diff_band_word(cdata, uni64<64>(noff));   // ... and the band word of its D during the update below
     wave_sync();
     double pb = LPMP_INF;                              // peer's bound after this receive
     for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
@@ -2837,9 +3047,15 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
 }
 
 // class KC_DIFF: one wave per record, dynamic LDS by the launch's label counts (flags: sweep_bigdim_flags)
-void launch_sweep_diff(const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
+void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s) {
   if (count <= 0) return;
+  if (band) {                                          // every receive of the launch has a banded D (LevelRange::diff_band)
+    const int waves = diff_band_waves(flags);
+    hipLaunchKernelGGL(sweep_diff_band_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), diff_band_lds_bytes(flags), s,
+                       recs, ops, dual, cdata, lb, primal, first, count, flags);
+    return;
+  }
   const int waves = diff_waves(flags);
   hipLaunchKernelGGL(sweep_diff_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), diff_lds_bytes(flags), s,
                      recs, ops, dual, cdata, lb, primal, first, count, flags);

@@ -83,7 +83,8 @@ bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, cons
                          double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s);
 bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
                          double* lb, int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const int32_t* tabs, int n_tabs, hipStream_t s);
-void launch_sweep_diff(const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
+// band: the launch's LevelRange::diff_band (sweep_diff_band_kernel; cdata then holds a band word in front of every D)
+void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s);
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
                   const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s);

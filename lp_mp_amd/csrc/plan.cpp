@@ -100,6 +100,14 @@ std::vector<int32_t> reference_topological_order(int64_t nf, const int32_t* rel,
 
 }  // namespace
 
+void diff_band(const double* D, int64_t n, int32_t* lo, int32_t* hi) {
+  auto bits = [&](int64_t k) { uint64_t b; std::memcpy(&b, D + k, sizeof b); return b; };
+  int64_t l = 0, h = n - 1;
+  while (l < n && bits(l) == bits(0)) ++l;
+  while (h >= l && bits(h) == bits(n - 1)) --h;
+  *lo = (int32_t)l; *hi = (int32_t)h;
+}
+
 void Plan::build(const lpmp_model& m) {
   const bool timed_ = std::getenv("LPMP_PLAN_TIMES") != nullptr;
   auto t_last_ = std::chrono::steady_clock::now();
@@ -153,6 +161,8 @@ void Plan::build(const lpmp_model& m) {
       for (int64_t i = sh_off[t]; i < sh_off[t + 1]; ++i)
         if (sh_data[(size_t)i] != sh_data[(size_t)i]) fail("shared table " + std::to_string(t) + ": NaN entry");
   }
+  sh_lo.assign((size_t)n_shared, 0); sh_hi.assign((size_t)n_shared, -1); sh_banded.assign((size_t)n_shared, -1);
+  no_diff_band = std::getenv("LPMP_NO_DIFF_BAND") != nullptr;
   max_dual = 1;
   for (int64_t f = 0; f < nf; ++f) {
     if (f_kind[f] > LPMP_F_PAIRWISE_DIFF) fail("factor " + std::to_string(f) + ": unknown kind");
@@ -176,6 +186,10 @@ void Plan::build(const lpmp_model& m) {
         fail("factor " + std::to_string(f) + ": dims " + std::to_string(f_dim0[f]) + " x " + std::to_string(f_dim1[f]) + " need a difference vector of 1 x " +
              std::to_string((int64_t)f_dim0[f] + f_dim1[f] - 1) + ", shared table " + std::to_string(t) + " is " + std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]));
       f_table[f] = t;
+      if (sh_banded[(size_t)t] < 0) {
+        diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
+        sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
+      }
     }
     if (f_type[f] < 0 || f_type[f] >= n_ftypes) fail("factor " + std::to_string(f) + ": type out of range");
     if (f_dim0[f] <= 0 || (f_kind[f] == LPMP_F_PAIRWISE_DENSE && f_dim1[f] <= 0)) fail("factor " + std::to_string(f) + ": bad dimension");
@@ -888,6 +902,19 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
     lr.level = key_level[k];
     lr.n_recv = key_recv[k]; lr.n_send = key_send[k]; lr.bytes = key_bytes[k];
     lr.max_dim = key_maxdim[k];
+    if (lr.kclass == KC_DIFF && !p.no_diff_band) {
+      // the banded kernel: only if every receive of the launch has a banded vector.  A launch without any receive (the first
+      // step of a sweep: sends only, the two kernels do the same there) goes by the vectors of its sends, so that a model is
+      // on one kernel throughout.
+      bool all = true;
+      for (int64_t i = lr.begin; i < lr.end && all; ++i) {
+        const UpdRec& r = out.recs[(size_t)i];
+        const Op* o = ops.data() + r.op_begin;
+        const int n_ops = lr.n_recv > 0 ? r.n_recv : r.n_send;
+        for (int q = 0; q < n_ops && all; ++q) all = p.sh_banded[(size_t)p.f_table[(size_t)o[q].peer]] == 1;
+      }
+      lr.diff_band = all;
+    }
     if (!kc_is_shared(lr.kclass)) { out.launches.push_back(lr); continue; }
     // a shared class: one launch per table-set group of the records (classify), each with the list of its distinct tables
     const int64_t n_lr = lr.end - lr.begin;

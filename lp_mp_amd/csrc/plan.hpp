@@ -94,6 +94,11 @@ enum KClass : int32_t {
   KC_COUNT
 };
 constexpr int BIG_MAX_LABELS = 512;
+// A DIFF vector D of n entries is BANDED when all entries outside an index range [lo, hi] equal, to the bit, D[0] (below lo) or
+// D[n - 1] (above hi) and the range has at most n / DIFF_BAND_DIV entries (a truncated potential).  A KC_DIFF launch
+// whose receives all reference banded vectors runs sweep_diff_band_kernel: the window and two tail terms instead of all pairs.
+constexpr int DIFF_BAND_DIV = 4;
+constexpr bool diff_band_rule(int64_t lo, int64_t hi, int64_t n) { return (hi - lo + 1) * DIFF_BAND_DIV <= n; }
 constexpr int SMALL_MAXD = 8;
 constexpr int PW_MAX_OPS = 6;
 constexpr bool kc_is_pw(int kclass) { return kclass >= KC_PW_4 && kclass <= KC_PW_32; }
@@ -126,6 +131,8 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   int32_t max_dim = 0;                          // largest label count of any vector or table side the launch's records touch
   // shared classes: the distinct shared tables (indices into the model's pool) the launch's records reference
   int32_t n_sh = 0; int32_t sh_tab[SHARED_MAX_TABLES] = {};
+  // class diff: every receive of every record references a banded vector (cleared by LPMP_NO_DIFF_BAND): the banded kernel
+  bool diff_band = false;
 };
 constexpr int PK_MAX_OPS = 8;                 // packets hold at most this many ops per factor
 // launches whose factors have more ops than that (but at most this many: the LDS slab of a lane group) run the
@@ -257,6 +264,10 @@ struct Plan {
   int32_t n_shared = 0;
   std::vector<int64_t> sh_off; std::vector<int32_t> sh_dim0, sh_dim1; std::vector<double> sh_data;
   std::vector<int32_t> f_table;
+  // per pool entry a DIFF factor references: the band [sh_lo, sh_hi] of its vector (diff_band below) and whether the rule holds
+  // (sh_banded: 0 / 1; -1: no DIFF factor references the entry)
+  std::vector<int32_t> sh_lo, sh_hi; std::vector<int8_t> sh_banded;
+  bool no_diff_band = false;     // LPMP_NO_DIFF_BAND set when the plan was built: no launch gets LevelRange::diff_band
   std::vector<int32_t> m_type, m_left, m_right;
   double constant = 0;
   // derived
@@ -320,6 +331,12 @@ struct Plan {
   // why the adaptive send rule cannot run this model ("" if it can)
   std::string adaptive_obstacle() const;
 };
+
+// The band of a difference vector D of n entries, by the BITS of the doubles (-0.0 and +0.0 differ): lo = the first index whose
+// entry is not D[0] (n if there is none), hi = the last index >= lo whose entry is not D[n - 1] (lo - 1 if there is none).  Every
+// entry below lo is D[0], every entry above hi is D[n - 1], and hi - lo + 1 >= 0 is the width.  model.diff_band (Python) is the
+// same statement.
+void diff_band(const double* D, int64_t n, int32_t* lo, int32_t* hi);
 
 // graph.cpp: an order of all factors with the updated ones colour by colour (rank[f] = position; returns the number of colours)
 int32_t suggest_order(const Plan& p, uint64_t seed, int32_t* rank);

@@ -72,6 +72,7 @@ EXPORTS = [
     "lpmp_set_persistent_launches", "lpmp_persistent_launches", "lpmp_device_identity",
     "lpmp_plan_suggest_order", "lpmp_graph_colour_major_order", "lpmp_graph_refine_partition",
     "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
+    "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches",
 ]
 
 
@@ -177,6 +178,11 @@ def lib():
             L.lpmp_set_persistent_launches.argtypes = [C.c_void_p, C.c_int]
             L.lpmp_persistent_launches.argtypes = [C.c_void_p]
             L.lpmp_device_identity.argtypes = [C.c_int, C.c_char_p, C.c_int64]
+        if hasattr(L, "lpmp_plan_get_diff_band"):    # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_plan_n_shared_tables.argtypes = [C.c_void_p]
+            L.lpmp_plan_get_diff_band.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+            L.lpmp_plan_diff_band_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+            L.lpmp_get_diff_band_launches.argtypes = [C.c_void_p, C.c_void_p]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -317,6 +323,29 @@ def _schedule_classes(self, d: int, mode: int) -> dict:
 
 
 Plan.schedule_classes = _schedule_classes
+
+
+def _diff_bands(self) -> dict:
+    """{pool entry: (lo, hi, banded)} for every entry a DIFF factor references: the band of the vector as ``model.diff_band``
+    states it, and whether its width is within the rule of the banded kernel"""
+    out = {}
+    for t in range(self.L.lpmp_plan_n_shared_tables(self.h)):
+        lo, hi, banded = C.c_int32(), C.c_int32(), C.c_int()
+        _chk(self.L.lpmp_plan_get_diff_band(self.h, t, C.addressof(lo), C.addressof(hi), C.addressof(banded)))
+        if banded.value >= 0:
+            out[t] = (lo.value, hi.value, bool(banded.value))
+    return out
+
+
+def _diff_band_info(self, d: int, mode: int) -> dict:
+    """launches / receives of class diff in the sweep, and how many of them run the banded kernel"""
+    v = [C.c_int64() for _ in range(4)]
+    _chk(self.L.lpmp_plan_diff_band_info(self.h, d, mode, *[C.addressof(x) for x in v]))
+    return dict(zip(("diff_launches", "band_launches", "diff_receives", "band_receives"), [x.value for x in v]))
+
+
+Plan.diff_bands = _diff_bands
+Plan.diff_band_info = _diff_band_info
 
 
 def _pass_info(self, mode: int) -> dict:
@@ -678,6 +707,13 @@ class Engine:
                     name += "<true>" if self.L.lpmp_streaming_access(self.h) == 1 else "<false>"
                 out[KCLASS_NAMES[c]] = dict(kernel=name, ms=float(ms[c]), launches=int(arrs[0][c]),
                                             factors=int(arrs[1][c]), receives=int(arrs[2][c]), bytes=int(arrs[3][c]))
+                if name == "sweep_diff_kernel" and hasattr(self.L, "lpmp_get_diff_band_launches"):
+                    # launches whose vectors are all banded run the banded kernel; the name is its only when all timed ones did
+                    nb = C.c_int64()
+                    _chk(self.L.lpmp_get_diff_band_launches(self.h, C.addressof(nb)))
+                    out[KCLASS_NAMES[c]]["band_launches"] = nb.value
+                    if nb.value == arrs[0][c]:
+                        out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_band_kernel"
         return out
 
 

@@ -319,6 +319,28 @@ def truncated_quadratic(d0: int, d1: int, slope: float, trunc: float) -> np.ndar
     return np.minimum(np.float64(slope) * (k * k), np.float64(trunc))
 
 
+DIFF_BAND_DIV = 4      # plan.hpp: a band of at most n / DIFF_BAND_DIV entries runs the banded kernel
+
+
+def diff_band(D) -> tuple:
+    """the band (lo, hi) of a difference vector, as the planner detects it (plan.cpp, diff_band): every entry below lo has the
+    BITS of D[0], every entry above hi the bits of D[n - 1] (-0.0 and +0.0 differ).  lo = the first index whose entry is not D[0]
+    (n if none), hi = the last index >= lo whose entry is not D[n - 1] (lo - 1 if none); hi - lo + 1 >= 0 is the width"""
+    b = np.ascontiguousarray(D, np.float64).reshape(-1).view(np.uint64)
+    n = b.shape[0]
+    left = np.flatnonzero(b != b[0])
+    lo = int(left[0]) if left.size else n
+    right = np.flatnonzero(b[lo:] != b[n - 1])
+    hi = lo + int(right[-1]) if right.size else lo - 1
+    return lo, hi
+
+
+def diff_band_is_banded(D) -> bool:
+    """the rule of the banded kernel: the band has at most n / DIFF_BAND_DIV entries"""
+    lo, hi = diff_band(D)
+    return (hi - lo + 1) * DIFF_BAND_DIV <= np.asarray(D).size
+
+
 class ModelBuilder:
     """Collects factors / messages / relations in insertion order (bulk or one at a time)."""
 

@@ -3,12 +3,15 @@
 dense expansion on the same engine build.  GPU only: there is no CPU path, a missing device is an error.
 
     python tools/diff_table_probe.py --grid 512 --labels 128 --tables 2 --potential linear --warmup 5 --steps 20 --expansion --repeat 5
+    python tools/diff_table_probe.py --grid 512 --labels 128 --trunc-labels 2 --warmup 5 --steps 20 --repeat 5
     python tools/diff_table_probe.py --capacity-check --grid 1024 --labels 128
 
 Comparison mode: --repeat repetitions ALTERNATE the DIFF model and the expansion (two engines held side by side, warm-up and
 timed passes in every repetition); the expansion's tables, 8 L^2 bytes per edge, are built in device memory from the same
 vectors and scales with one multiply per entry (what expand_diff() does on the host), and after the last repetition the duals
 of the two engines are compared.  --shared also times the same potentials as SHARED factors (<= 32 labels).
+--trunc-labels K truncates the potentials after K label steps instead of LABELS / 4 (the band of the vectors, and which launches
+run the banded kernel, are printed: bands, diff_band_info); duals_sha256 lets two libraries (LPMP_ENGINE_SO) be compared bit for bit.
 Capacity-check mode: a DIFF grid that has no dense counterpart that fits; 5 + 20 single passes, the bound after every pass
 must be finite and non-decreasing, and the tracked bound must agree with a recomputation of every factor to 1e-9 relative.
 Prints one JSON line."""
@@ -16,6 +19,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import hashlib
 import json
 import os
 import sys
@@ -26,12 +30,14 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def vectors(potential: str, L: int, T: int, seed: int):
+def vectors(potential: str, L: int, T: int, seed: int, trunc_labels: int = 0):
+    """``trunc_labels`` K: the potential is truncated after K label steps (constant from |a - b| = K on; 0: after L / 4)"""
     from lp_mp_amd import model as M, synthetic as S
+    K = trunc_labels if trunc_labels > 0 else L // 4
     if potential == "linear":
-        return np.stack([M.truncated_linear(L, L, 0.02 * (t + 1), 0.02 * (t + 1) * (L // 4)) for t in range(T)])
+        return np.stack([M.truncated_linear(L, L, 0.02 * (t + 1), 0.02 * (t + 1) * K) for t in range(T)])
     if potential == "quadratic":
-        return np.stack([M.truncated_quadratic(L, L, 0.002 * (t + 1), 0.002 * (t + 1) * (L // 4) ** 2) for t in range(T)])
+        return np.stack([M.truncated_quadratic(L, L, 0.002 * (t + 1), 0.002 * (t + 1) * K ** 2) for t in range(T)])
     return S.u01(T * (2 * L - 1), seed + 1000).reshape(T, 2 * L - 1)
 
 
@@ -82,13 +88,17 @@ def comparison(a, out) -> int:
     from lp_mp_amd import build as B, model as M, synthetic as S
     from lp_mp_amd.engine import Engine
     mode = M.REPAM_NAMES[a.mode]
-    vec = vectors(a.potential, a.labels, a.tables, a.seed)
+    vec = vectors(a.potential, a.labels, a.tables, a.seed, a.trunc_labels)
     m = S.grid_model(a.grid, a.grid, a.labels, pairwise="diff", order=a.order, seed=a.seed, diff_tables=vec)
-    out.update(dual_bytes=int(m.dual_data.nbytes), library_source_hash=B.source_hash())
+    from lp_mp_amd import engine as EG
+    out.update(dual_bytes=int(m.dual_data.nbytes), library_source_hash=B.source_hash(), library=EG.library_path(),
+               bands=[list(M.diff_band(v)) + [bool(M.diff_band_is_banded(v))] for v in vec])
     e = Engine(0)
     e.upload(m)
     e.set_reparametrization(mode)
     e.prepare_passes(a.steps)
+    if hasattr(e.L, "lpmp_plan_diff_band_info"):     # (absent in an older library loaded through LPMP_ENGINE_SO for an A/B)
+        out["diff_band_info"] = [e.plan.diff_band_info(d, mode) for d in (0, 1)]
     info = e.plan.pass_schedule_info(mode)
     out["diff"] = dict(classes_forward=e.plan.schedule_classes(0, mode), classes_backward=e.plan.schedule_classes(1, mode),
                        algorithmic_bytes_per_pass=int(info["algorithmic_bytes"]), n_launches_per_pass=int(info["n_launches"]), ms_per_pass=[])
@@ -107,6 +117,7 @@ def comparison(a, out) -> int:
         if x_eng is not None:
             out["expansion"]["ms_per_pass"].append(timed(x_eng, a.warmup, a.steps))
     out["diff"]["lower_bound"] = e.lower_bound()
+    out["diff"]["duals_sha256"] = hashlib.sha256(e.download_duals().tobytes()).hexdigest()   # (two libraries: equal digests = equal bits)
     if x_eng is not None:
         out["expansion"]["lower_bound"] = x_eng.lower_bound()
         out["duals_equal"] = bool(np.array_equal(e.download_duals(), x_eng.download_duals()))
@@ -133,7 +144,7 @@ def capacity(a, out) -> int:
     from lp_mp_amd import build as B, model as M, synthetic as S
     from lp_mp_amd.engine import Engine
     mode = M.REPAM_NAMES[a.mode]
-    m = S.grid_model(a.grid, a.grid, a.labels, pairwise="diff", order=a.order, seed=a.seed, diff_tables=vectors(a.potential, a.labels, a.tables, a.seed))
+    m = S.grid_model(a.grid, a.grid, a.labels, pairwise="diff", order=a.order, seed=a.seed, diff_tables=vectors(a.potential, a.labels, a.tables, a.seed, a.trunc_labels))
     edges = int((m.f_kind == M.F_PAIRWISE_DIFF).sum())
     out.update(dual_bytes=int(m.dual_data.nbytes), dense_counterpart_bytes=edges * 8 * a.labels * a.labels, library_source_hash=B.source_hash())
     e = Engine(0)
@@ -169,6 +180,7 @@ def main() -> int:
     ap.add_argument("--labels", type=int, default=128)
     ap.add_argument("--tables", type=int, default=2)
     ap.add_argument("--potential", default="linear", choices=["linear", "quadratic", "random"])
+    ap.add_argument("--trunc-labels", type=int, default=0, help="truncate the potential after K label steps instead of LABELS / 4")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeat", type=int, default=1, help="repetitions, alternating DIFF and expansion")
@@ -184,7 +196,7 @@ def main() -> int:
         print("diff_table_probe: no GPU", file=sys.stderr)
         return 2
     out = dict(mode_of_run="capacity-check" if a.capacity_check else "comparison", grid=a.grid, labels=a.labels, tables=a.tables,
-               potential=a.potential, order=a.order, mode=a.mode, warmup=a.warmup, steps=a.steps, repeat=a.repeat, device=torch.cuda.get_device_name(0))
+               potential=a.potential, trunc_labels=a.trunc_labels, order=a.order, mode=a.mode, warmup=a.warmup, steps=a.steps, repeat=a.repeat, device=torch.cuda.get_device_name(0))
     rc = capacity(a, out) if a.capacity_check else comparison(a, out)
     print(json.dumps(out))
     return rc
