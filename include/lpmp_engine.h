@@ -283,6 +283,49 @@ int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);
 int lpmp_upload_duals(lpmp_engine* e, const double* host_in);
+/* ---- new costs on the plan that is already there ---------------------------------------------------------------------------
+ * Everything the engine builds before its first pass — order, weights, level schedules, kernel classes, packets, chain plans, the
+ * ticket templates of joined passes, mailboxes — is a function of the STRUCTURE of the model; none of it reads a cost.  These calls
+ * give a planned model other numbers and plan nothing: lpmp_engine_plan returns the same pointer, every cached schedule, every
+ * lpmp_schedule_create id, every lpmp_boundary / lpmp_halo object, the reparametrization mode and type, the speculation depth, the
+ * rows-layout and table-precision modes stay and stay valid, and lpmp_schedules_built does not change.
+ *
+ * lpmp_upload_costs: same structure, other numbers.  const_data / dual_data are packed exactly as lpmp_model.const_data / dual_data
+ * of the uploaded model; NULL = leave that half as it is; *_mem says where the array lives.  LPMP_ERR_STATE before the first
+ * lpmp_upload_model and when both pointers are NULL.  The data is copied into wherever the engine keeps that half (its own buffer,
+ * or the caller's borrowed one); a LPMP_MEM_DEVICE pointer that IS the buffer the engine already reads is not copied ("I rewrote my
+ * buffer in place"), only the derived copies are refreshed.
+ *   constants given: every engine-private copy is derived again, by the code of the upload — the {scale, offset} cells of SHARED /
+ *     DIFF factors (cell offsets and pool untouched), the float tables under LPMP_TABLES_F32 / _F32_ROUND (same refusals, naming the
+ *     lowest factor), the table part of the rows.  An LPMP_ERR_UNSUPPORTED from the narrowing leaves the constants unspecified: from
+ *     then on every call that would read them (passes, bounds, primal cost) returns LPMP_ERR_STATE until a later lpmp_upload_costs
+ *     with constants succeeds, or lpmp_upload_model.  The dual half of the refused call HAS been applied, and a borrowed constant
+ *     buffer holds the refused constants (the tables are narrowed out of it).
+ *   duals given (cold start): an open batch of passes that ran ahead is dropped without replay.
+ *   duals NOT given (warm start): passes that ran ahead are settled first — the duals are those of the pass the caller is at.  The
+ *     one exception to "plans nothing": settling replays the passes the caller had asked for, and the joined launch of THAT pass count
+ *     is built (and counted by lpmp_schedules_built) if the engine has not run it before — a function of the structure, cached.
+ * In every case all tracked per-factor bounds become stale and the primal labels go back to unset (lpmp_evaluate_primal is +inf
+ * until a rounding pass has run on the new costs); the kernel-timing accumulators are left alone.
+ * The shared pool (lpmp_model.sh_data) is STRUCTURE — the bands of DIFF vectors and the LDS table sets depend on it — and is not
+ * replaced: changing it, like dims, messages, relations or partitions, remains a job for lpmp_upload_model. */
+int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, const double* dual_data, int dual_mem);
+/* theta of the listed VECTOR factors := row i of src (accumulate = 0) or += row i of src (accumulate != 0; one IEEE add per entry).
+ * Row i starts at src + i * src_stride and has f_dim0[factors[i]] entries; src_stride may exceed the longest listed vector (one
+ * [n, Lmax] cost volume).  factors is a host array; src is host or device (src_mem).  Settles first; addresses the packed dual array
+ * (vector factors live only there, also under the rows layout); marks the bounds of the listed factors stale.  LPMP_ERR_INVALID,
+ * naming the offender, with the duals untouched: an index out of range, a non-VECTOR factor, a factor listed twice, src_stride
+ * smaller than the longest listed vector. */
+int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, int src_mem,
+                     int accumulate);
+/* both message vectors of every pairwise factor (DENSE, POTTS, SHARED, DIFF) := +0.0.  Settles first; writes the rows under the rows
+ * layout and the packed array otherwise; marks all bounds stale.  Asynchronous on the engine's stream like a pass (it reads nothing
+ * of the caller's); lpmp_upload_costs and lpmp_set_vectors return after their copies have completed.  A cold start from device data is lpmp_set_vectors(all unaries,
+ * replace) + this call; a warm start after a change of unaries is lpmp_set_vectors(changed ones, differences, accumulate). */
+int lpmp_zero_pairwise_duals(lpmp_engine* e);
+/* schedules, chain plans and joined-pass templates planned and uploaded for the current model since lpmp_upload_model */
+int64_t lpmp_schedules_built(const lpmp_engine* e);
+
 void* lpmp_device_duals(lpmp_engine* e);   /* device pointer of the packed duals (for zero-copy exchange); with the rows layout
                                               the dense pairwise factors' vectors are written out to it first, and the rows are
                                               refreshed from it before the next pass (the caller is assumed to write it) */

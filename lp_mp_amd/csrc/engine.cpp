@@ -259,6 +259,14 @@ struct lpmp_engine {
   int want_tab = LPMP_TABLES_F64, tab_prec = LPMP_TABLES_F64, tab_flag = 0;
   DevBuf<float> d_tab32;
   bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
+  // new costs on the planned model (lpmp_upload_costs, lpmp_set_vectors, lpmp_zero_pairwise_duals): everything below is a function
+  // of the structure, kept so that the engine-private copies of the constants can be derived again without planning anything
+  int64_t schedules_built = 0;    // schedules, chain plans and joined-pass templates planned and uploaded for this model
+  bool const_bad = false;         // a refused lpmp_upload_costs left the constants unspecified: nothing may read them
+  bool tab_compact = false;       // f32 tables from host memory: const_buf holds only the cells of the non-DENSE factors
+  std::vector<int64_t> sh_cells;  // the SHARED / DIFF cells as launch_shared_cells receives them: {const offset, table offset}
+  DevBuf<SetVecRec> d_setrecs; DevBuf<double> d_setsrc;   // records and (host sources) rows of lpmp_set_vectors, refilled in place
+  DevBuf<ZeroRec> d_zero; int64_t n_zero = -1;            // pieces of the pairwise message vectors; -1: not built yet
   struct LbRun { int cls; int64_t first, count; };
   std::vector<LbRun> lb_runs;
   DevSchedule sched[2][LPMP_REPAM_COUNT];
@@ -353,6 +361,8 @@ struct lpmp_engine {
     d_dual = nullptr; d_const = nullptr;
     d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
     d_tab32.reset(); tab_prec = LPMP_TABLES_F64; tab_flag = 0;
+    schedules_built = 0; const_bad = false; tab_compact = false; sh_cells.clear();
+    d_setrecs.reset(); d_setsrc.reset(); d_zero.reset(); n_zero = -1;
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
     d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
@@ -547,6 +557,12 @@ void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool
   }
 }
 
+// ... for an engine's model: counted (lpmp_schedules_built)
+void upload_schedule(lpmp_engine* e, const Schedule& s, DevSchedule& d, bool keep = false, bool adaptive_built = false) {
+  upload_schedule(s, d, e->stream, keep, adaptive_built);
+  ++e->schedules_built;
+}
+
 void check_generic_limits(const Plan& p, const Schedule& s) {
   const int lim = GEN_MAXD;
   for (const auto& lr : s.launches) {
@@ -580,7 +596,7 @@ void ensure_device_schedules(lpmp_engine* e, int mode) {
     plan_schedule(e->plan.get(), d, mode);
     deep_schedule_note(e, e->plan->sched_cache[d][mode].n_levels, d == 0 ? "the forward sweep" : "the backward sweep");
     check_generic_limits(e->plan->p, e->plan->sched_cache[d][mode]);
-    upload_schedule(e->plan->sched_cache[d][mode], e->sched[d][mode], e->stream);
+    upload_schedule(e, e->plan->sched_cache[d][mode], e->sched[d][mode]);
   }
   e->have_sched[mode] = true;
 }
@@ -602,7 +618,7 @@ void ensure_pass_schedule(lpmp_engine* e, int mode) {
     lap_("forward+backward planned again, with its chain plan");
   }
   check_generic_limits(e->plan->p, e->plan->pass_cache[mode]);
-  upload_schedule(e->plan->pass_cache[mode], e->sched_pass[mode], e->stream);
+  upload_schedule(e, e->plan->pass_cache[mode], e->sched_pass[mode]);
   lap_("... uploaded");
   // LPMP_LAUNCH_LOG=<file> (profiling aid): one line per launch of the fused pass in execution order — level, class, records,
   // receives, sends, algorithmic bytes, packet stride — to lay beside the durations of a kernel trace (tools/launch_rates.py)
@@ -616,7 +632,7 @@ void ensure_pass_schedule(lpmp_engine* e, int mode) {
   }
   e->rotation_ok[mode] = e->plan->rotation_ok[mode];
   if (e->rotation_ok[mode]) {
-    upload_schedule(e->plan->bf_cache[mode], e->sched_bf[mode], e->stream);
+    upload_schedule(e, e->plan->bf_cache[mode], e->sched_bf[mode]);
     lap_("... uploaded");
     e->plan->rot[mode] = plan_rotation_chain(e->plan->pass_cache[mode], e->plan->bf_cache[mode], e->plan->p.nf);
     lap_("block relations of the steps");
@@ -642,7 +658,7 @@ void ensure_pass_chain_plan(lpmp_engine* e, int mode) {
   check_generic_limits(e->plan->p, e->plan->pass_cache[mode]);
   HIP_CHECK(hipStreamSynchronize(e->stream));
   e->release_rot_chains(mode);
-  upload_schedule(e->plan->pass_cache[mode], e->sched_pass[mode], e->stream);
+  upload_schedule(e, e->plan->pass_cache[mode], e->sched_pass[mode]);
   Schedule& h = e->plan->pass_cache[mode];
   h.recs.clear(); h.recs.shrink_to_fit(); h.ops.clear(); h.ops.shrink_to_fit(); h.packets.clear(); h.packets.shrink_to_fit();
 }
@@ -942,6 +958,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   }
   rc.dc.kclass = ri.kclass;
   e->rot_cache_bytes += rc.dev_bytes;
+  ++e->schedules_built;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
@@ -1003,7 +1020,12 @@ static void rows_refresh(lpmp_engine* e) {   // packed duals -> rows, before any
 static void rows_flush(lpmp_engine* e) {     // rows -> packed duals, before the packed array is handed to anybody
   if (e->rows && e->packed_stale) { launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 2, e->stream); HIP_CHECK(hipGetLastError()); e->packed_stale = false; }
 }
-static void begin_compute(lpmp_engine* e) { rows_refresh(e); if (e->rows) e->packed_stale = true; }
+// the constants are unspecified after a refused lpmp_upload_costs: whatever would read them says so — passes, bounds, the primal
+// cost.  The lpmp_boundary_* / lpmp_halo_* kernels (boundary.hip) touch duals only and are not checked.
+static void require_consts(const lpmp_engine* e) {
+  if (e->const_bad) throw StateError("the constants are unspecified since lpmp_upload_costs refused them: upload costs the table precision accepts, or the model");
+}
+static void begin_compute(lpmp_engine* e) { require_consts(e); rows_refresh(e); if (e->rows) e->packed_stale = true; }
 
 extern "C" {
 
@@ -1321,32 +1343,45 @@ int lpmp_set_stream(lpmp_engine* e, void* s) {
 //     resident as doubles as a whole; the cells of the other factors (Potts, SHARED and DIFF scalars) are gathered into a compact
 //     buffer of doubles that becomes e->d_const, and dev_coff of those factors points into it.
 // Throws UnsupportedError naming the lowest DENSE factor that holds an entry the mode refuses (kernels.hip, narrow_tables_kernel).
-static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on_device) {
-  const int strict = e->want_tab == LPMP_TABLES_F32 ? 1 : 0;
+// fresh (the upload): the buffers are allocated and dev_coff is laid out.  Not fresh (lpmp_upload_costs): the same narrowing into the
+// buffers and offsets of the upload — the mode is the uploaded model's, `consts` is e->d_const itself (a borrowed buffer, already
+// holding the new constants) or, for an engine whose compact buffer came from host memory, host or device memory of the caller's.
+static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on_device, bool fresh = true) {
+  const int prec = fresh ? e->want_tab : e->tab_prec;
+  const int strict = prec == LPMP_TABLES_F32 ? 1 : 0;
+  const bool compact = fresh ? !on_device : e->tab_compact;
   std::vector<NarrowRec> recs;
   std::vector<double> small;
-  p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
-  int64_t at = 0;                                  // floats
+  struct Run { int64_t src, dst, n; };
+  std::vector<Run> runs;                           // compact cells out of a device buffer: runs of consecutive non-DENSE factors
+  if (fresh) p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
+  int64_t at = 0, small_at = 0;                    // floats; doubles of the compact buffer
   for (int64_t f = 0; f < p.nf; ++f) {
     const int64_t n = p.f_coff[f + 1] - p.f_coff[f];
     if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
       recs.push_back({p.f_coff[f], at, n, (int32_t)f, 0});
       at += (n + 3) / 4 * 4;
-    } else if (!on_device) {
-      p.dev_coff[f] = (int64_t)small.size();
-      small.insert(small.end(), consts + p.f_coff[f], consts + p.f_coff[f + 1]);
+    } else if (compact) {
+      if (fresh) p.dev_coff[f] = small_at;
+      if (!on_device) small.insert(small.end(), consts + p.f_coff[f], consts + p.f_coff[f + 1]);
+      else if (n > 0) { if (!runs.empty() && runs.back().src + runs.back().n == p.f_coff[f]) runs.back().n += n; else runs.push_back({p.f_coff[f], small_at, n}); }
+      small_at += n;
     }
   }
-  if (!on_device) {
-    e->const_buf.alloc(std::max<size_t>(2, small.size()));
-    e->d_const = e->const_buf;
+  if (compact) {
+    if (fresh) { e->const_buf.alloc(std::max<size_t>(2, (size_t)small_at)); e->d_const = e->const_buf; }
+    else if ((size_t)small_at > e->const_buf.capacity()) throw std::runtime_error("table precision: the compact constants do not fit their buffer");
     if (!small.empty()) h2d(e->d_const, small.data(), small.size() * sizeof(double), e->stream);
+    for (const Run& r : runs) HIP_CHECK(hipMemcpyAsync(e->const_buf + r.dst, consts + r.src, (size_t)r.n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   }
   if (recs.empty()) return;
+  if (!fresh) { if ((size_t)at > e->d_tab32.capacity()) throw std::runtime_error("table precision: the tables do not fit their buffer"); }
+  else {
   e->d_tab32.alloc((size_t)at);
   if ((((uintptr_t)e->d_tab32.get() - (uintptr_t)e->d_const) % 16) != 0) throw std::runtime_error("table precision: buffers are not aligned to each other");
   const int64_t shift = (int64_t)(((intptr_t)e->d_tab32.get() - (intptr_t)e->d_const) / 8);
   for (const NarrowRec& r : recs) p.dev_coff[r.factor] = shift + r.dst_off / 2;
+  }
   DevBuf<int> d_bad; d_bad.alloc(1);
   const int none = INT32_MAX;
   h2d(d_bad, &none, sizeof(int), e->stream);
@@ -1354,7 +1389,7 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
   if (on_device) {
     d_recs.alloc(recs.size());
     h2d(d_recs, recs.data(), recs.size() * sizeof(NarrowRec), e->stream);
-    launch_narrow_tables(d_recs, (int64_t)recs.size(), e->d_const, e->d_tab32, strict, d_bad, e->stream);
+    launch_narrow_tables(d_recs, (int64_t)recs.size(), consts, e->d_tab32, strict, d_bad, e->stream);
     HIP_CHECK(hipGetLastError());
   } else {
     // chunks of whole tables, at most STAGE doubles of the packed array each (a table has at most BIG_MAX_LABELS^2 entries: 2 MiB)
@@ -1392,6 +1427,22 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
                                    : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN"));
 }
 
+// The engine-private copies of the constants that are COSTS, not structure: lpmp_upload_model derives them once, lpmp_upload_costs
+// again, with these functions (and narrow_tables above).
+// SHARED / DIFF factors: the cells {const offset of the factor's scale, table offset} go to the device as the upload laid them out
+// and shared_cells_kernel replaces every first word by the scale it finds in the constants; the pool behind the cells is not touched
+static void gather_shared_cells(lpmp_engine* e) {
+  if (e->sh_cells.empty()) return;
+  h2d(e->d_shared, e->sh_cells.data(), e->sh_cells.size() * sizeof(int64_t), e->stream);
+  launch_shared_cells(e->d_shared, (int64_t)e->sh_cells.size() / 2, e->d_const, e->stream);
+  HIP_CHECK(hipGetLastError());
+}
+// rows layout: every row [table | m1 | m2] from the packed constants and the packed duals
+static void build_rows(lpmp_engine* e) {
+  launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 0, e->stream);
+  HIP_CHECK(hipGetLastError());
+}
+
 static void check_rtype(const lpmp_engine* e, int rtype);
 int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int dual_mem) {
   return guarded([&] {
@@ -1420,6 +1471,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       if (((uintptr_t)e->d_const & 15) != 0) throw std::runtime_error("device const buffer must be 16-byte aligned");
       if (f32) try { narrow_tables(e, pl->p, m->const_data, true); } catch (...) { e->release_model(); throw; }
     } else if (f32) {
+      e->tab_compact = true;
       try { narrow_tables(e, pl->p, m->const_data, false); } catch (...) { e->release_model(); throw; }
     } else if (n_const > 0) {
       e->const_buf.alloc((size_t)n_const);
@@ -1450,8 +1502,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
         e->d_rowrecs.alloc(rr.size());
         h2d(e->d_rowrecs, rr.data(), rr.size() * sizeof(RowRec), e->stream);
         e->n_rowrecs = (int64_t)rr.size();
-        launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 0, e->stream);
-        HIP_CHECK(hipGetLastError());
+        build_rows(e);
         const int64_t c_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_const) / 8), d_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_dual) / 8);
         pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end()); pl->p.dev_doff.assign(p.f_doff.begin(), p.f_doff.end());
         size_t k = 0;
@@ -1487,7 +1538,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
         cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + pool_at(p.f_table[f]);
         pl->p.dev_coff[f] = base + 2 * k;
       }
-      h2d(e->d_shared, cells.data(), cells.size() * sizeof(int64_t), e->stream);
+      e->sh_cells = std::move(cells);
       {
         std::vector<double> pool((size_t)n_pool);
         for (int32_t t = 0; t < p.n_shared; ++t) {
@@ -1498,8 +1549,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
         }
         h2d(e->d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), e->stream);
       }
-      launch_shared_cells(e->d_shared, n_sf, e->d_const, e->stream);
-      HIP_CHECK(hipGetLastError());
+      gather_shared_cells(e);
       std::vector<ShTableDesc> desc((size_t)p.n_shared);
       for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + pool_at(t), p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
       e->d_sh_desc.alloc(desc.size());
@@ -1628,7 +1678,7 @@ static void ensure_partition_schedule(lpmp_engine* e, int rtype) {
   Schedule s;
   e->plan->p.make_schedule(segs, e->use_fused, s);
   check_generic_limits(e->plan->p, s);
-  upload_schedule(s, e->sched_part[k], e->stream);
+  upload_schedule(e, s, e->sched_part[k]);
   e->have_part[k] = true;
 }
 
@@ -1844,6 +1894,14 @@ int lpmp_compute_pass(lpmp_engine* e, int n) {   // LP::ComputePass, LP_MP.h:869
 // pairwise factors afterwards.  The copy can wait because a pairwise factor's primal_[side] has a single writer and
 // nothing reads it before EvaluatePrimal: with a `left` schedule the recursion of propagate_primal_through_messages
 // stops at the pairwise factor (its other side is unset or already equal).
+// init_primal of every factor: an unset entry holds the dimension (what PrimalInit records say for the touched ones)
+static void upload_unset_primal(lpmp_engine* e) {
+  const Plan& p = e->plan->p;
+  if (p.nf <= 0) return;
+  std::vector<int32_t> h(2 * (size_t)p.nf);
+  for (int64_t f = 0; f < p.nf; ++f) { h[2 * f] = p.f_dim0[f]; h[2 * f + 1] = p.f_kind[f] == LPMP_F_VECTOR ? 0 : p.f_dim1[f]; }
+  h2d(e->d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
+}
 static void ensure_primal(lpmp_engine* e) {
   if (e->have_primal) return;
   e->release_primal();   // a previous attempt may have stopped half way
@@ -1890,8 +1948,8 @@ static void ensure_primal(lpmp_engine* e) {
   }
   for (int64_t f = 0; f < p.nf; ++f) if (p.updated[f]) touched[f] = 1;
   auto unset = [&](int64_t f) { return PrimalInit{(int32_t)f, p.f_dim0[f], p.f_kind[f] == LPMP_F_VECTOR ? 0 : p.f_dim1[f], 0}; };
-  std::vector<PrimalInit> init, all((size_t)p.nf);
-  for (int64_t f = 0; f < p.nf; ++f) { all[f] = unset(f); if (touched[f]) init.push_back(unset(f)); }
+  std::vector<PrimalInit> init;
+  for (int64_t f = 0; f < p.nf; ++f) if (touched[f]) init.push_back(unset(f));
   e->n_pprop = (int64_t)prop.size();
   prop.insert(prop.end(), rest.begin(), rest.end());
   e->n_plinks = (int64_t)prop.size();
@@ -1905,11 +1963,7 @@ static void ensure_primal(lpmp_engine* e) {
     h2d(e->d_plinks, prop.data(), prop.size() * sizeof(PrimalLink), e->stream);
   }
   // every factor starts unset (init_primal), then only the touched ones are ever re-initialised
-  if (p.nf > 0) {
-    std::vector<int32_t> h(2 * (size_t)p.nf);
-    for (int64_t f = 0; f < p.nf; ++f) { h[2 * f] = all[f].a; h[2 * f + 1] = all[f].b; }
-    h2d(e->d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
-  }
+  upload_unset_primal(e);
   if (!init.empty()) {
     e->d_pinit.alloc(init.size());
     h2d(e->d_pinit, init.data(), init.size() * sizeof(PrimalInit), e->stream);
@@ -1972,6 +2026,7 @@ int lpmp_evaluate_primal(lpmp_engine* e, double* cost) {
     if (!cost) throw std::runtime_error("null argument");
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
+    require_consts(e);
     ensure_primal(e);
     if (!primal_consistent(e)) { *cost = std::numeric_limits<double>::infinity(); return; }
     const int64_t nf = e->plan->p.nf;
@@ -2024,7 +2079,7 @@ int lpmp_compute_pass_custom(lpmp_engine* e, int64_t n, const int32_t* factors, 
     check_generic_limits(e->plan->p, s);
     // the schedule lives in a scratch buffer of the engine that is refilled in place: no allocation per call
     DevSchedule& d = e->scratch;
-    upload_schedule(s, d, e->stream, true, e->plan->p.force_generic);
+    upload_schedule(e, s, d, true, e->plan->p.force_generic);
     const bool g = e->use_graph; e->use_graph = false;
     try { run_schedule(e, d); } catch (...) { e->use_graph = g; throw; }
     e->use_graph = g;
@@ -2051,7 +2106,7 @@ int lpmp_schedule_create_fused(lpmp_engine* e, int64_t n, const int32_t* factors
                              fuse != 0 && e->use_fused, s);
     check_generic_limits(e->plan->p, s);
     auto d = std::make_unique<DevSchedule>();
-    upload_schedule(s, *d, e->stream, false, e->plan->p.force_generic);
+    upload_schedule(e, s, *d, false, e->plan->p.force_generic);
     e->custom.push_back(std::move(d));
     *id_out = (int)e->custom.size() - 1;
   });
@@ -2113,6 +2168,7 @@ static void check_chain(lpmp_engine* e) {
 }
 
 static void compute_factor_lbs(lpmp_engine* e) {
+  require_consts(e);
   check_chain(e);
   rows_refresh(e);
   if (e->use_lb_tracking && !e->lb_all_stale) {
@@ -2232,6 +2288,133 @@ int lpmp_invalidate_lower_bounds(lpmp_engine* e) {
   // the caller did not touch survives)
   return guarded([&] { require_model(e); settle(e); if (e->rows) { rows_flush(e); e->rows_stale = true; } e->lb_all_stale = true; });
 }
+// ---- new costs on the plan that is already there (include/lpmp_engine.h) --------------------------------------------------------
+// all tracked bounds stale, primal labels unset: what every change of costs leaves behind
+static void costs_changed(lpmp_engine* e) {
+  HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)e->plan->p.nf * sizeof(double), e->stream));   // all NaN, as after the upload
+  e->lb_all_stale = true;
+  if (e->have_primal) { upload_unset_primal(e); e->primal_t = 0; }
+}
+int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, const double* dual_data, int dual_mem) {
+  return guarded([&] {
+    if (!e || !e->plan) throw StateError("lpmp_upload_costs: no model uploaded (the structure comes from lpmp_upload_model)");
+    if (!const_data && !dual_data) throw StateError("lpmp_upload_costs: neither constants nor duals given");
+    HIP_CHECK(hipSetDevice(e->device));
+    Plan& p = e->plan->p;
+    const int64_t n_const = p.f_coff[p.nf], n_dual = p.f_doff[p.nf];
+    if (dual_data) {   // cold start: an open batch of passes that ran ahead is dropped, its snapshot is dead
+      e->spec.n = 0; e->spec.pos = 0; e->spec.lb_ready = false;
+      spec_interrupt(e);
+    } else settle(e);  // warm start: the duals are those of the pass the caller is at
+    check_chain(e);
+    if (dual_data) {
+      if (dual_mem != LPMP_MEM_DEVICE) h2d(e->d_dual, dual_data, (size_t)n_dual * sizeof(double), e->stream);
+      else if (dual_data != e->d_dual) HIP_CHECK(hipMemcpyAsync(e->d_dual, dual_data, (size_t)n_dual * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (e->rows) { e->rows_stale = true; e->packed_stale = false; }
+    }
+    if (const_data && n_const > 0) {
+      const bool dev = const_mem == LPMP_MEM_DEVICE;
+      if (!e->tab_compact) {   // the packed constants as a whole: the engine's own buffer, or the caller's borrowed one
+        if (!dev) h2d(e->d_const, const_data, (size_t)n_const * sizeof(double), e->stream);
+        else if (const_data != e->d_const) HIP_CHECK(hipMemcpyAsync(e->d_const, const_data, (size_t)n_const * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      }
+      if (e->tab_prec != LPMP_TABLES_F64) {
+        e->const_bad = true;   // until the narrowing has accepted every table
+        try { if (e->tab_compact) narrow_tables(e, p, const_data, dev, false); else narrow_tables(e, p, e->d_const, true, false); }
+        catch (...) { e->lb_all_stale = true; throw; }
+      }
+      e->const_bad = false;
+      gather_shared_cells(e);
+      if (e->rows) {
+        // the rows take their tables from the constants and their vectors from the packed duals: the packed array first gets what
+        // the rows hold that it does not (warm start), then every row is built as at the upload
+        if (e->rows_stale && e->packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
+        rows_flush(e);
+        build_rows(e);
+        e->rows_stale = false;
+      }
+    }
+    costs_changed(e);
+    HIP_CHECK(hipStreamSynchronize(e->stream));   // the caller's arrays are the caller's again
+  });
+}
+
+int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, int src_mem, int accumulate) {
+  return guarded([&] {
+    require_model(e);
+    if (n < 0 || (n > 0 && (!factors || !src))) throw std::runtime_error("lpmp_set_vectors: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    const Plan& p = e->plan->p;
+    std::vector<uint8_t> seen((size_t)p.nf, 0);
+    std::vector<SetVecRec> recs((size_t)n);
+    const bool dev = src_mem == LPMP_MEM_DEVICE;
+    int32_t longest = 0, longest_f = -1;
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t f = factors[i];
+      if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_set_vectors: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+      if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error("lpmp_set_vectors: factor " + std::to_string(f) + " is not a VECTOR factor");
+      if (seen[(size_t)f]) throw std::runtime_error("lpmp_set_vectors: factor " + std::to_string(f) + " is listed twice (the result would depend on the order of two waves)");
+      seen[(size_t)f] = 1;
+      const int32_t len = p.f_dim0[f];
+      if (len > longest) { longest = len; longest_f = f; }
+      // (vector factors live in the packed array under every layout; a host source is packed row after row: stride 1, row = offset)
+      recs[(size_t)i] = {p.f_doff[f], dev ? i : total, len, f};
+      total += len;
+    }
+    if (n > 0 && src_stride < longest)
+      throw std::runtime_error("lpmp_set_vectors: src_stride " + std::to_string(src_stride) + " is smaller than the " + std::to_string(longest) + " entries of factor " + std::to_string(longest_f));
+    settle(e);
+    check_chain(e);
+    if (n == 0) return;
+    e->d_setrecs.grow((size_t)n);
+    h2d(e->d_setrecs, recs.data(), (size_t)n * sizeof(SetVecRec), e->stream);
+    const double* d_src = src;
+    if (!dev) {
+      std::vector<double> rows((size_t)total);
+      for (int64_t i = 0; i < n; ++i) std::copy(src + i * src_stride, src + i * src_stride + recs[(size_t)i].len, rows.begin() + recs[(size_t)i].src_row);
+      e->d_setsrc.grow((size_t)total);
+      h2d(e->d_setsrc, rows.data(), (size_t)total * sizeof(double), e->stream);
+      d_src = e->d_setsrc;
+    }
+    launch_set_vectors(e->d_setrecs, n, d_src, dev ? src_stride : 1, e->d_dual, e->d_lb, accumulate != 0, e->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
+  });
+}
+
+int lpmp_zero_pairwise_duals(lpmp_engine* e) {
+  return guarded([&] {
+    require_model(e);
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);
+    check_chain(e);
+    const Plan& p = e->plan->p;
+    if (e->n_zero < 0) {   // once per model: the pairwise factors' vectors where the kernels address them, contiguous runs merged, cut into pieces
+      std::vector<ZeroRec> runs, recs;
+      for (int64_t f = 0; f < p.nf; ++f) {
+        if (p.f_kind[f] == LPMP_F_VECTOR) continue;
+        const int64_t off = p.doff(f), len = (int64_t)p.f_dim0[f] + p.f_dim1[f];
+        if (!runs.empty() && runs.back().dual_off + runs.back().len == off) runs.back().len += len; else runs.push_back({off, len});
+      }
+      for (const ZeroRec& r : runs)
+        for (int64_t a = 0; a < r.len; a += ZERO_RUN_MAX) recs.push_back({r.dual_off + a, std::min(ZERO_RUN_MAX, r.len - a)});
+      if (!recs.empty()) { e->d_zero.alloc(recs.size()); h2d(e->d_zero, recs.data(), recs.size() * sizeof(ZeroRec), e->stream); }
+      e->n_zero = (int64_t)recs.size();
+    }
+    // (dense pairwise vectors live in the rows under the rows layout: what the caller put into the packed array goes there first, and
+    // from here on the rows are the newer copy — as for a pass)
+    rows_refresh(e);
+    if (e->rows) e->packed_stale = true;
+    launch_zero_pairwise(e->d_zero, e->n_zero, e->d_dual, e->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));
+    e->lb_all_stale = true;
+  });
+}
+
+int64_t lpmp_schedules_built(const lpmp_engine* e) { return e && e->plan ? e->schedules_built : 0; }
+
 // The packed dual array (serialize_dual order) on the device.  With the rows layout the dense pairwise factors' vectors are
 // written out to it first (stream-ordered on the engine's stream), and the caller is assumed to write it: the rows are
 // refreshed from it before the next pass — callers that only read may say so by not calling this between passes.

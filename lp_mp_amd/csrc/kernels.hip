@@ -3315,4 +3315,40 @@ void launch_synth_fill(double* out, int64_t n, uint64_t seed, uint64_t first, hi
   hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, out, n, seed, first);
 }
 
+// ---- new costs on a planned model (engine.cpp, lpmp_set_vectors / lpmp_zero_pairwise_duals) -----------------------------
+// Both are streams: no LDS, no atomics, plain 8-byte loads and stores; consecutive lanes touch consecutive doubles.
+// theta of listed vector factor k := (accumulate: +=, one IEEE add per entry) row src_row of src; one wave per record, lanes
+// stride over the entries.  The factor's tracked bound becomes NaN: the next lower bound recomputes exactly these.
+__global__ void __launch_bounds__(256)
+set_vectors_kernel(const SetVecRec* __restrict__ recs, int64_t n, const double* __restrict__ src, int64_t src_stride, double* __restrict__ dual,
+                   double* __restrict__ lb, int accumulate) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const SetVecRec r = recs[k];
+  const double* row = src + r.src_row * src_stride;
+  double* th = dual + r.dual_off;
+  if (accumulate) { for (int x = lane; x < r.len; x += 64) th[x] = th[x] + row[x]; }
+  else { for (int x = lane; x < r.len; x += 64) th[x] = row[x]; }
+  if (lane == 0) lb[r.factor] = __longlong_as_double(-1LL);   // all bits set: the NaN the stale marks of the sweep kernels are
+}
+// the message vectors of the pairwise factors := +0.0: runs of (device dual offset, length), merged by the host where they are
+// contiguous and cut into pieces of at most ZERO_RUN_MAX doubles; one wave per piece, as set_vectors_kernel — where nothing merges
+// (rows layout, pairwise factors between vectors) a piece is one factor's d0 + d1 doubles and no lane of a wider block would idle
+__global__ void __launch_bounds__(256)
+zero_pairwise_kernel(const ZeroRec* __restrict__ recs, int64_t n, double* __restrict__ dual) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const ZeroRec r = recs[k];
+  double* d = dual + r.dual_off;
+  for (int64_t x = lane; x < r.len; x += 64) d[x] = 0.0;
+}
+void launch_set_vectors(const SetVecRec* recs, int64_t n, const double* src, int64_t src_stride, double* dual, double* lb, int accumulate, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(set_vectors_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, src, src_stride, dual, lb, accumulate);
+}
+void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(zero_pairwise_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, dual);
+}
+
 }  // namespace lpmp

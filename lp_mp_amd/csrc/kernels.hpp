@@ -74,6 +74,11 @@ struct LbRec { int64_t dual_off; int64_t const_off; int32_t d0, d1; int32_t kind
 struct RowRec { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
 // table precision: one dense table's place in the chunk of doubles being narrowed and in the float buffer (narrow_tables_kernel)
 struct NarrowRec { int64_t src_off, dst_off, n; int32_t factor, pad; };
+// new costs on a planned model: one listed vector factor of lpmp_set_vectors (its place in the packed duals, its row of the source)
+struct SetVecRec { int64_t dual_off, src_row; int32_t len, factor; };
+// ... and one piece of the pairwise message vectors lpmp_zero_pairwise_duals clears (device dual offset, at most ZERO_RUN_MAX doubles)
+struct ZeroRec { int64_t dual_off, len; };
+constexpr int64_t ZERO_RUN_MAX = 8192;
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
 // The bool ones return false when there is no kernel for the request (each says when, at its definition).
@@ -107,5 +112,9 @@ void launch_shared_cells(double* cells, int64_t n, const double* cdata, hipStrea
 // table precision: n tables of src (doubles) become floats in dst; strict: refuse entries that are not exactly floats; *bad keeps the
 // lowest factor index with a refused entry (the caller sets it to INT32_MAX first)
 void launch_narrow_tables(const NarrowRec* recs, int64_t n, const double* src, float* dst, int strict, int* bad, hipStream_t s);
+// new costs on a planned model: theta of the listed vector factors := / += rows of src (and their tracked bounds become NaN);
+// the listed runs of the dual array := +0.0
+void launch_set_vectors(const SetVecRec* recs, int64_t n, const double* src, int64_t src_stride, double* dual, double* lb, int accumulate, hipStream_t s);
+void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStream_t s);
 
 }  // namespace lpmp

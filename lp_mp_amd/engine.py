@@ -73,6 +73,7 @@ EXPORTS = [
     "lpmp_plan_suggest_order", "lpmp_graph_colour_major_order", "lpmp_graph_refine_partition",
     "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
     "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches",
+    "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
 ]
 
 
@@ -183,6 +184,12 @@ def lib():
             L.lpmp_plan_get_diff_band.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
             L.lpmp_plan_diff_band_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
             L.lpmp_get_diff_band_launches.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "lpmp_upload_costs"):          # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_upload_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            L.lpmp_set_vectors.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+            L.lpmp_zero_pairwise_duals.argtypes = [C.c_void_p]
+            L.lpmp_schedules_built.restype = C.c_int64
+            L.lpmp_schedules_built.argtypes = [C.c_void_p]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -469,6 +476,71 @@ class Engine:
         self.model = model
         _chk(self.L.lpmp_upload_model(self.h, C.addressof(cs), MEM_DEVICE if const_dev is not None else MEM_HOST,
                                       MEM_DEVICE if dual_dev is not None else MEM_HOST))
+
+    # ---- new costs on the plan that is already there (include/lpmp_engine.h): nothing is planned, every schedule stays ----
+    def upload_costs(self, const=None, duals=None, const_dev: Optional[int] = None, dual_dev: Optional[int] = None):
+        """Same structure, other numbers (lpmp_upload_costs).  ``const`` / ``duals``: numpy arrays packed as ``FlatModel.const_data`` /
+        ``dual_data``; ``const_dev`` / ``dual_dev``: raw device pointers instead, as in ``upload`` (a pointer that is the buffer the
+        engine already borrows is not copied: "rewritten in place").  A half that is not given stays as it is: constants alone are
+        a warm start (the messages are kept).  ``self.model`` becomes a copy with the host arrays given; halves that came as device
+        pointers keep the arrays of the upload there (the structure is what ``self.model`` is read for)."""
+        import dataclasses
+        n_const, n_dual = int(self.model.const_sizes().sum()), int(self.L.lpmp_dual_size(self.h))
+        cp, cm, dp, dm = None, MEM_HOST, None, MEM_HOST
+        if const_dev is not None:
+            cp, cm = C.c_void_p(const_dev), MEM_DEVICE
+        elif const is not None:
+            const = np.ascontiguousarray(const, np.float64)
+            if const.shape != (n_const,):
+                raise ValueError(f"upload_costs: {n_const} constants expected, got an array of shape {const.shape}")
+            if n_const == 0:
+                const = np.zeros(1)                  # (a model without constants: a valid pointer that is never read, alive across the call)
+            cp = C.c_void_p(const.ctypes.data)
+        if dual_dev is not None:
+            dp, dm = C.c_void_p(dual_dev), MEM_DEVICE
+        elif duals is not None:
+            duals = np.ascontiguousarray(duals, np.float64)
+            if duals.shape != (n_dual,):
+                raise ValueError(f"upload_costs: {n_dual} duals expected, got an array of shape {duals.shape}")
+            dp = C.c_void_p(duals.ctypes.data)
+        _chk(self.L.lpmp_upload_costs(self.h, cp, cm, dp, dm))
+        new = {}
+        if const_dev is None and const is not None and n_const:
+            new["const_data"] = const
+        if dual_dev is None and duals is not None:
+            new["dual_data"] = duals
+        if new:
+            self.model = dataclasses.replace(self.model, _keep=[], **new)
+
+    def set_vectors(self, factors, src=None, accumulate: bool = False, src_dev: Optional[int] = None, src_stride: Optional[int] = None):
+        """theta of the listed VECTOR factors := (``accumulate``: +=) row i of ``src`` (lpmp_set_vectors).  ``src``: a 2-D numpy array
+        [n, >= longest vector], or a 1-D one with ``src_stride``; ``src_dev``: a raw device pointer with ``src_stride`` instead."""
+        factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
+        n = int(factors.shape[0])
+        if src_dev is not None:
+            if src_stride is None:
+                raise ValueError("set_vectors: src_dev needs src_stride")
+            ptr, mem = C.c_void_p(src_dev), MEM_DEVICE
+        else:
+            src = np.ascontiguousarray(src, np.float64)
+            if src.ndim == 2:
+                if src.shape[0] < n:
+                    raise ValueError("set_vectors: fewer rows than factors")
+                src_stride = src.shape[1] if src_stride is None else src_stride
+            elif src_stride is None:
+                raise ValueError("set_vectors: a flat source needs src_stride")
+            if n > 0 and src.size < (n - 1) * int(src_stride) + 1:
+                raise ValueError("set_vectors: source shorter than the rows it is said to hold")
+            ptr, mem = C.c_void_p(src.ctypes.data), MEM_HOST
+        _chk(self.L.lpmp_set_vectors(self.h, n, factors.ctypes.data, ptr, int(src_stride), mem, 1 if accumulate else 0))
+
+    def zero_pairwise_duals(self):
+        """both message vectors of every pairwise factor := +0.0 (lpmp_zero_pairwise_duals)"""
+        _chk(self.L.lpmp_zero_pairwise_duals(self.h))
+
+    def schedules_built(self) -> int:
+        """schedules, chain plans and joined-pass templates planned and uploaded for the current model since ``upload``"""
+        return int(self.L.lpmp_schedules_built(self.h))
 
     def lower_bound_recomputed(self) -> int:
         """per-factor bounds the last lower_bound() had to recompute (the rest were tracked by the sweep kernels)"""

@@ -474,6 +474,49 @@ class LP_gpu {
     return s;
   }
 
+  // Not in the reference: hand the costs the factor ops hold NOW to the structure that is already on the device
+  // (lpmp_upload_costs: nothing is planned again, every schedule stays).  Write the new numbers into the ops
+  // (GetFactor()->cost(a, b) = ..., (*GetFactor())[i] = ..., diff_cost() = ...) — not a structural change, no set_flags_dirty —
+  // and call this.  After a structural change it is the ordinary upload.
+  //   cold (default): constants := the ops' tables / scalars, vectors := what the vector ops hold, every message vector := 0.
+  //   warm: constants only; the messages on the device are kept, and every vector factor whose op differs from what this mirror
+  //         last exchanged with the device (the upload, or the last pull_duals) receives the difference, one add per entry —
+  //         an op that still holds its old cost and is overwritten with the new one gets new - old.
+  void upload_costs(const bool warm = false) {
+    if (!engine_ || dirty_) { ready(); return; }
+    ready();
+    Flat fl;
+    for (INDEX i = 0; i < f_.size(); ++i) (this->*flatteners_[i])(f_[i].get(), fl);
+    if (fl.dual.size() != exchanged_.size()) throw std::runtime_error("upload_costs: the factors changed their sizes (a structural change)");
+    const REAL* c = fl.cdata.empty() ? nullptr : fl.cdata.data();
+    if (!warm) {
+      check(lpmp_upload_costs(engine_, c, LPMP_MEM_HOST, fl.dual.data(), LPMP_MEM_HOST));
+      check(lpmp_zero_pairwise_duals(engine_));
+      exchanged_ = fl.dual;
+    } else {
+      if (c) check(lpmp_upload_costs(engine_, c, LPMP_MEM_HOST, nullptr, LPMP_MEM_HOST));
+      std::vector<int32_t> changed;
+      std::vector<std::size_t> at;
+      std::size_t off = 0, longest = 0;
+      for (INDEX i = 0; i < f_.size(); ++i) {
+        const std::size_t n = (std::size_t)lpmp_factor_dual_size(fl.kind[i], fl.d0[i], fl.d1[i]);
+        if (fl.kind[i] == LPMP_F_VECTOR && !std::equal(fl.dual.begin() + (std::ptrdiff_t)off, fl.dual.begin() + (std::ptrdiff_t)(off + n), exchanged_.begin() + (std::ptrdiff_t)off)) {
+          changed.push_back((int32_t)i); at.push_back(off); longest = std::max(longest, n);
+        }
+        off += n;
+      }
+      std::vector<REAL> rows(changed.size() * longest, 0.0);
+      for (std::size_t k = 0; k < changed.size(); ++k) {
+        const std::size_t n = (std::size_t)fl.d0[(std::size_t)changed[k]];
+        for (std::size_t x = 0; x < n; ++x) { rows[k * longest + x] = fl.dual[at[k] + x] - exchanged_[at[k] + x]; exchanged_[at[k] + x] = fl.dual[at[k] + x]; }
+      }
+      if (!changed.empty()) check(lpmp_set_vectors(engine_, (int64_t)changed.size(), changed.data(), rows.data(), (int64_t)longest, LPMP_MEM_HOST, 1));
+    }
+    duals_on_device_ = true;
+  }
+  // schedules, chain plans and joined-pass templates built for the model on the device (lpmp_schedules_built): unchanged by upload_costs
+  int64_t schedules_built() const { return engine_ ? lpmp_schedules_built(engine_) : 0; }
+
   std::vector<FactorTypeAdapter*> forward_update_ordering() { return update_ordering(0); }
   std::vector<FactorTypeAdapter*> backward_update_ordering() { return update_ordering(1); }
 
@@ -484,6 +527,7 @@ class LP_gpu {
     check(lpmp_download_duals(engine_, d.data()));
     const REAL* p = d.data();
     for (INDEX i = 0; i < f_.size(); ++i) p = (this->*unflatteners_[i])(f_[i].get(), p);
+    exchanged_ = std::move(d);
     duals_on_device_ = false;
   }
 
@@ -582,6 +626,7 @@ class LP_gpu {
     check(lpmp_set_reparametrization_type(engine_, rtype_));
     dirty_ = false;
     duals_on_device_ = false;
+    exchanged_ = std::move(fl.dual);
   }
   void ready_mode() { ready(); check(lpmp_set_reparametrization(engine_, mode_index())); }
 
@@ -601,6 +646,7 @@ class LP_gpu {
   bool dirty_ = true, duals_on_device_ = false;
   int rtype_ = LPMP_RTYPE_SHARED, inner_ = 5;
   std::vector<int32_t> part_;
+  std::vector<REAL> exchanged_;   // the packed duals as last exchanged with the device (ready, pull_duals, upload_costs): upload_costs(warm) sends differences to it
   LPReparametrizationMode repamMode_ = LPReparametrizationMode::Undefined;
   REAL constant_ = 0;
   std::vector<std::unique_ptr<FactorTypeAdapter>> f_;

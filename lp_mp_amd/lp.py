@@ -384,10 +384,70 @@ class LP:
             a = np.asarray(self._partition_graph, np.int32); b.put_in_same_partition(a[:, 0], a[:, 1])
         b.constant = self._constant
         m = b.finish()
+        self._flat_costs = m.dual_data               # the costs alone, in dual layout: what upload_costs(warm) takes differences to
         if self._duals_host is not None:     # duals of factors that existed before a structural change
+            m.dual_data = m.dual_data.copy()
             n = min(self._duals_host.shape[0], m.dual_data.shape[0])
             m.dual_data[:n] = self._duals_host[:n]
         return m
+
+    # -- new costs on the structure that is on the device (Engine.upload_costs: nothing is planned again) -----------------
+    def set_factor_cost(self, i: int, *cost):
+        """replace the cost of factor ``i``: the arguments of the factor's own constructor (or one ready instance of its type), as
+        ``add_factor`` takes them.  NOT a structural call — the LP stays clean and ``upload_costs()`` hands the new numbers to the
+        planned model.  Raises when the kind, a dimension or the pool entry of the factor would change."""
+        c, old = self._factors[i]
+        new = cost[0] if len(cost) == 1 and isinstance(cost[0], type(old)) else type(old)(*cost)
+        if new.kind != old.kind:
+            raise RuntimeError("set_factor_cost: the kind of factor %d would change" % i)
+        if old.kind == M.F_VECTOR:
+            same = new.cost.shape == old.cost.shape and new.implicit_origin == old.implicit_origin
+        elif old.kind == M.F_PAIRWISE_DENSE:
+            same = (new.dim1, new.dim2) == (old.dim1, old.dim2)
+        elif old.kind == M.F_PAIRWISE_POTTS:
+            same = new.dim == old.dim
+        elif old.kind == M.F_PAIRWISE_SHARED:
+            same = new.table_id == old.table_id          # (the pool is structure: another table is another model)
+            new.table = old.table
+        else:
+            same = (new.table_id, new.dim1, new.dim2) == (old.table_id, old.dim1, old.dim2)
+            new.vec = old.vec
+        if not same:
+            raise RuntimeError("set_factor_cost: the shape of factor %d would change (a structural change: add the factor to a new LP)" % i)
+        self._factors[i] = (c, new)
+
+    def upload_costs(self, warm: bool = False):
+        """hand the factors' current costs (``set_factor_cost``) to the device.  No structural call since the last upload: the
+        planned model gets new numbers (Engine.upload_costs), every schedule stays.  Cold (default): constants, and duals = the
+        costs — a fresh problem.  ``warm``: constants only, the messages are kept, and every unary whose cost changed receives
+        new - old (Engine.set_vectors, accumulate): the reparametrised problem of the new costs.  After a structural call this is
+        the ordinary upload."""
+        if self._engine is None or self._dirty:
+            self._ready()
+            return
+        e = self._ready()
+        kept, self._duals_host = self._duals_host, None      # (flat_model lays pulled duals over the costs: not wanted here)
+        try:
+            new = self.flat_model()
+        finally:
+            self._duals_host = kept
+        if warm:
+            if new.const_data.shape[0] > 0:
+                e.upload_costs(const=new.const_data)
+            off = new.dual_offsets()
+            delta = new.dual_data - self._cost_dual    # new - old COSTS (the device holds reparametrised duals; so may _model)
+            vec = np.flatnonzero(new.f_kind == M.F_VECTOR)
+            changed = [int(f) for f in vec if np.any(delta[off[f]:off[f + 1]] != 0.0)]
+            if changed:
+                src = np.zeros((len(changed), int(max(off[f + 1] - off[f] for f in changed))))
+                for k, f in enumerate(changed):
+                    src[k, :off[f + 1] - off[f]] = delta[off[f]:off[f + 1]]
+                e.set_vectors(changed, src, accumulate=True)
+        else:
+            e.upload_costs(const=new.const_data if new.const_data.shape[0] > 0 else None, duals=new.dual_data)
+        self._model = new
+        self._cost_dual = new.dual_data
+        e.model = new
 
     def _pull_duals(self):
         if self._engine is not None and not self._dirty:
@@ -401,6 +461,7 @@ class LP:
             self._engine.set_speculation(self._speculation)
         if self._dirty:
             self._model = self.flat_model()
+            self._cost_dual = self._flat_costs       # (not _model.dual_data: after a structural call that holds pulled duals)
             self._engine.upload(self._model, table_precision=self._table_precision)
             self._dirty = False
         self._engine.set_inner_iterations(self._inner)
