@@ -87,6 +87,13 @@ const Op* packet_op(const Probe& p, int64_t i, int k) {
   return p.s.packets.data() + lr.pk_begin + (i - lr.begin) * lr.stride + 1 + k;
 }
 
+// the packet header of record i (nullptr: its launch has no packets)
+const UpdRec* packet_rec(const Probe& p, int64_t i) {
+  const Op* first = packet_op(p, i, 0);
+  return first ? reinterpret_cast<const UpdRec*>(first - 1) : nullptr;
+}
+constexpr int64_t NO_PACKET = INT64_MIN;
+
 template <class F>
 int64_t emit(int64_t n, int64_t* out, F&& f) { if (out) for (int64_t i = 0; i < n; ++i) out[i] = f(i); return n; }
 
@@ -162,6 +169,13 @@ int64_t probe_get(void* h, const char* name, int chain, int64_t* out) {
   if (n == "rec_n_send") return emit(NR, out, [&](int64_t i) { return (int64_t)s.recs[(size_t)i].n_send; });
   if (n == "rec_op_begin") return emit(NR, out, [&](int64_t i) { return (int64_t)s.recs[(size_t)i].op_begin; });
   if (n == "rec_kind_flags") return emit(NR, out, [&](int64_t i) { return (int64_t)s.recs[(size_t)i].kind_flags; });
+  // where the record's factor lies in the dual / const arrays, in elements (read-only: tests/test_far_offsets_host.py)
+  if (n == "rec_dual_off") return emit(NR, out, [&](int64_t i) { return s.recs[(size_t)i].dual_off; });
+  if (n == "rec_const_off") return emit(NR, out, [&](int64_t i) { return s.recs[(size_t)i].const_off; });
+  // ... and the same words of the record's packet header (NO_PACKET: its launch has no packets)
+  if (n == "pk_rec_dual_off") return emit(NR, out, [&](int64_t i) { const UpdRec* h = packet_rec(p, i); return h ? h->dual_off : NO_PACKET; });
+  if (n == "pk_rec_const_off") return emit(NR, out, [&](int64_t i) { const UpdRec* h = packet_rec(p, i); return h ? h->const_off : NO_PACKET; });
+  if (n == "no_packet") return emit(1, out, [&](int64_t) { return NO_PACKET; });
   // per op (of Schedule::ops)
   if (n == "op_peer") return emit(NO, out, [&](int64_t i) { return (int64_t)s.ops[(size_t)i].peer; });
   if (n == "op_side") return emit(NO, out, [&](int64_t i) { return (int64_t)((s.ops[(size_t)i].info >> 5) & 1); });
@@ -169,6 +183,21 @@ int64_t probe_get(void* h, const char* name, int chain, int64_t* out) {
   if (n == "op_code") return emit(NO, out, [&](int64_t i) { return (int64_t)(s.ops[(size_t)i].info & 15); });
   if (n == "op_pad") return emit(NO, out, [&](int64_t i) { return (int64_t)s.ops[(size_t)i].pad; });
   if (n == "op_omega_bits") return emit(NO, out, [&](int64_t i) { int64_t b; std::memcpy(&b, &s.ops[(size_t)i].omega, 8); return b; });
+  if (n == "op_peer_dual") return emit(NO, out, [&](int64_t i) { return s.ops[(size_t)i].peer_dual; });
+  if (n == "op_peer_const") return emit(NO, out, [&](int64_t i) { return s.ops[(size_t)i].peer_const; });
+  // the packet copies of the same two words (a mailbox send's peer_const is its row: op_mailbox_row); NO_PACKET where there is none
+  if (n == "pk_op_peer_dual" || n == "pk_op_peer_const") {
+    const bool dual = n == "pk_op_peer_dual";
+    if (out) {
+      for (int64_t i = 0; i < NO; ++i) out[i] = NO_PACKET;
+      for (int64_t r = 0; r < NR; ++r) {
+        const UpdRec& rec = s.recs[(size_t)r];
+        for (int k = 0; k < rec.n_recv + rec.n_send; ++k)
+          if (const Op* po = packet_op(p, r, k)) out[rec.op_begin + k] = dual ? po->peer_dual : po->peer_const;
+      }
+    }
+    return NO;
+  }
   // the packet copies: OP_MAILBOX and the row (send: peer_const, receive: the bits of omega); -1 where there is no packet or no bit
   if (n == "op_mailbox_row") {
     if (out) {

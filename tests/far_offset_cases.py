@@ -1,0 +1,206 @@
+"""Far offsets: a small live model behind tens of thousands of isolated padding factors, so that every constant and dual offset
+the planner hands the kernels lies past 2^31 (placement P31) or 2^32 (P32) elements.  Helpers of tests/test_far_offsets_host.py
+and tests/test_far_offsets_gpu.py.
+
+The padding factors have no message: they are never updated, appear in no record, and contribute 0.0 to every bound (their
+constants and duals are zero).  The far model has no host costs: they live in two caller-owned device tensors, zero in front and
+the small model's packed arrays at the tail.  The oracle only ever sees the small model."""
+import dataclasses
+import functools
+
+import numpy as np
+
+from lp_mp_amd import model as M
+from lp_mp_amd import synthetic as S
+
+PAD_LABELS = 65536
+N_PAD = {"P31": 32768, "P32": 65536}
+TAIL = 1 << 22                 # doubles behind the padding: room for the largest live model of the tests (40 x 36 x 32: 2.9 M constants)
+GIB = 1 << 30
+
+
+def pad_sizes(n_pad, kind):
+    """(const elements, dual elements) of the padding = the first live const / dual offset"""
+    if kind == "dense":
+        return n_pad * PAD_LABELS, n_pad * (PAD_LABELS + 1)
+    if kind == "vector":
+        return 0, n_pad * PAD_LABELS
+    raise ValueError(kind)
+
+
+def _pad_type(m, kind):
+    """a factor type for the padding: one whose factors do not round a primal (those get a record without any message);
+    kind dense: the type of m's pairwise factors where there is one"""
+    cp = np.asarray(m.ftype_computes_primal)
+    want = (m.f_kind != M.F_VECTOR) if kind == "dense" else (m.f_kind == M.F_VECTOR)
+    for t in list(dict.fromkeys(int(t) for t in m.f_type[want])) + list(range(m.n_ftypes)):
+        if not cp[t]:
+            return t
+    raise ValueError("pad_front: every factor type rounds a primal")
+
+
+def pad_front(m, n_pad, kind="dense"):
+    """``m`` with n_pad isolated factors in front: DENSE 1 x 65536 factors of the pairwise type (65 536 constants and 65 537 duals
+    each) or VECTOR factors of 65 536 labels (duals only).  No host costs: upload with ``const_dev=`` / ``dual_dev=``."""
+    n_pad = int(n_pad)
+    pad_sizes(n_pad, kind)
+    t = _pad_type(m, kind)
+    front = lambda a, v: np.ascontiguousarray(np.concatenate([np.full(n_pad, v, a.dtype), a]))
+    shift = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.int32) + np.int32(n_pad))
+    dense = kind == "dense"
+    return dataclasses.replace(
+        m, _keep=[], const_data=None, dual_data=None,
+        f_type=front(m.f_type, t), f_kind=front(m.f_kind, M.F_PAIRWISE_DENSE if dense else M.F_VECTOR), f_flags=front(m.f_flags, 0),
+        f_dim0=front(m.f_dim0, 1 if dense else PAD_LABELS), f_dim1=front(m.f_dim1, PAD_LABELS if dense else 0),
+        f_table=None if m.f_table is None else front(np.asarray(m.f_table, np.int32), -1),
+        m_left=shift(m.m_left), m_right=shift(m.m_right), rel_fwd=shift(m.rel_fwd), rel_bwd=shift(m.rel_bwd),
+        part_pairs=shift(m.part_pairs) if m.part_pairs is not None and len(m.part_pairs) else m.part_pairs)
+
+
+class FarBuffers:
+    """the two borrowed device tensors of one placement: ``torch.zeros(pad + TAIL)`` each, allocated once; ``load`` writes a small
+    model's packed arrays behind the padding, ``reset`` zeroes what the last test used of the tails"""
+
+    def __init__(self, placement, kind="dense"):
+        import torch
+        self.torch = torch
+        self.placement, self.kind, self.n_pad = placement, kind, N_PAD[placement]
+        self.pad_c, self.pad_d = pad_sizes(self.n_pad, kind)
+        self.const = torch.zeros(self.pad_c + TAIL, dtype=torch.float64, device="cuda")
+        self.dual = torch.zeros(self.pad_d + TAIL, dtype=torch.float64, device="cuda")
+        self.n_c = self.n_d = 0
+        torch.cuda.synchronize()
+
+    @staticmethod
+    def bytes_needed(placement, kind="dense"):
+        c, d = pad_sizes(N_PAD[placement], kind)
+        return 8 * (c + d + 2 * TAIL)
+
+    def load(self, m, const=None, dual=None):
+        """the tails := m.const_data / m.dual_data (or the arrays given); returns (const pointer, dual pointer)"""
+        torch = self.torch
+        const = m.const_data if const is None else const
+        dual = m.dual_data if dual is None else dual
+        assert const.shape[0] <= TAIL and dual.shape[0] <= TAIL
+        self.reset()
+        self.n_c, self.n_d = int(const.shape[0]), int(dual.shape[0])
+        self.write_const(const)
+        self.dual[self.pad_d: self.pad_d + self.n_d].copy_(torch.from_numpy(np.ascontiguousarray(dual, np.float64)))
+        torch.cuda.synchronize()
+        return self.const.data_ptr(), self.dual.data_ptr()
+
+    def write_const(self, const):
+        """the const tail rewritten in place (same length)"""
+        n = int(const.shape[0])
+        assert n == self.n_c
+        if n:
+            self.const[self.pad_c: self.pad_c + n].copy_(self.torch.from_numpy(np.ascontiguousarray(const, np.float64)))
+        self.torch.cuda.synchronize()
+
+    def reset(self):
+        if self.n_c:
+            self.const[self.pad_c: self.pad_c + self.n_c].zero_()
+        if self.n_d:
+            self.dual[self.pad_d: self.pad_d + self.n_d].zero_()
+        self.n_c = self.n_d = 0
+        self.torch.cuda.synchronize()
+
+    def dual_tail(self):
+        self.torch.cuda.synchronize()
+        return self.dual[self.pad_d: self.pad_d + self.n_d].cpu().numpy()
+
+    def const_tail(self):
+        self.torch.cuda.synchronize()
+        return self.const[self.pad_c: self.pad_c + self.n_c].cpu().numpy()
+
+    def _nonzero_bits(self, t, n):
+        """words of the first n doubles that are not +0.0 (by their bits: a -0.0 counts)"""
+        return int(self.torch.count_nonzero(t[:n].view(self.torch.int64)).item()) if n else 0
+
+    def dual_padding_nonzero(self):
+        self.torch.cuda.synchronize()
+        return self._nonzero_bits(self.dual, self.pad_d) + self._nonzero_bits(self.dual[self.pad_d + self.n_d:], TAIL - self.n_d)
+
+    def const_padding_nonzero(self):
+        self.torch.cuda.synchronize()
+        return self._nonzero_bits(self.const, self.pad_c) + self._nonzero_bits(self.const[self.pad_c + self.n_c:], TAIL - self.n_c)
+
+
+# ---- the live models: the smallest that still reach each kernel family ------------------------------------------------------
+def _grid(L, pairwise="dense", shape=(6, 5), order="colour_major", **kw):
+    return S.grid_model(shape[0], shape[1], L, pairwise=pairwise, order=order, seed=100 + L, **kw)
+
+
+def _mixed():
+    import diff_tables_cases as DT
+    return DT.mixed_graph(np.random.default_rng(311), n=30)
+
+
+def _diff40():
+    import diff_tables_cases as DT
+    return DT.label_grid(40, "colour_major")
+
+
+def _band130():
+    import diff_band_cases as DB
+    return DB.label_grid(130, "colour_major", 2)
+
+
+def _scheduled(sched):
+    import f32_tables_cases as FC
+    return FC.scheduled_grid(6, 5, 8, sched, 8 + sched)
+
+
+def _level_loop():
+    import diff_tables_cases as DT
+    return DT.updated_pairwise_grid(M.SCHED_RIGHT, 40)     # row-major, updated DIFF factors: many tiny generic levels
+
+
+def _c5():
+    import recost_cases as RC
+    return RC.c5_small()
+
+
+# name -> (builder, the kernel classes the forward sweep must consist of under ANISOTROPIC; None: only "something generic")
+LIVE = {
+    "dense32": (lambda: _grid(32), {"dense32"}),
+    "dense8": (lambda: _grid(8), {"dense8"}),
+    "dense4": (lambda: _grid(4), {"dense4"}),
+    "dense_v21": (lambda: _grid(21), {"dense_v32"}),
+    "dense_v5": (lambda: _grid(5), {"dense_v8"}),
+    "potts16": (lambda: _grid(16, "potts"), {"potts16"}),
+    "potts_v5": (lambda: _grid(5, "potts"), {"potts_v8"}),
+    "big48": (lambda: _grid(48, shape=(4, 4)), {"dense_big"}),
+    "big130": (lambda: _grid(130, shape=(4, 4)), {"dense_big"}),
+    "shared32": (lambda: _grid(32, "shared", n_tables=2), {"shared32"}),
+    "shared8": (lambda: _grid(8, "shared", n_tables=2), {"shared8"}),
+    "diff40": (_diff40, {"diff"}),
+    "diff_band130": (_band130, {"diff"}),
+    "pairwise8_right": (lambda: _scheduled(M.SCHED_RIGHT), None),
+    "pairwise8_full": (lambda: _scheduled(M.SCHED_FULL), None),
+    "mixed_graph": (_mixed, None),
+    "c5_small": (_c5, None),
+    "level_loop40": (_level_loop, None),
+    "joined_dense32": (lambda: _grid(32, shape=(40, 36)), {"dense32"}),
+    "joined_potts8": (lambda: _grid(8, "potts", shape=(64, 48)), {"potts8"}),
+    "deep_dense16": (lambda: S.grid_model(40, 30, 16, order="row_major", seed=5), {"dense16"}),
+    "deep_potts8": (lambda: S.grid_model(60, 50, 8, pairwise="potts", order="row_major", seed=6), {"potts8"}),
+    "halo16": (lambda: _grid(16), {"dense16"}),
+    "halo40": (lambda: _grid(40), {"dense_big"}),
+    "primal_dense8": (lambda: _grid(8, compute_primal=True), {"dense8"}),
+    "primal_potts8": (lambda: _grid(8, "potts", compute_primal=True), {"potts8"}),
+    "recost13": (lambda: _grid(13, shape=(7, 6)), {"dense_v16"}),
+}
+# the first three families of the issue's table: placement P32 as well
+P32_MODELS = ("dense32", "dense8", "dense4", "dense_v21", "dense_v5", "potts16", "potts_v5", "big48", "big130")
+
+
+@functools.lru_cache(maxsize=None)
+def live(name):
+    """built once per process and never modified"""
+    return LIVE[name][0]()
+
+
+def oracle_model(m):
+    """what the unchanged CPU oracle runs: DIFF and SHARED factors expanded to private tables"""
+    return m.expand_diff().expand_shared()

@@ -368,11 +368,16 @@ def chain_settings_fields():
     return names
 
 
-_REC = ("rec_launch", "rec_level", "rec_class", "rec_factor", "rec_n_recv", "rec_n_send", "rec_op_begin", "rec_kind_flags")
-_OP = ("op_peer", "op_side", "op_role", "op_code", "op_pad", "op_omega_bits", "op_mailbox_row")
+_REC = ("rec_launch", "rec_level", "rec_class", "rec_factor", "rec_n_recv", "rec_n_send", "rec_op_begin", "rec_kind_flags",
+        "rec_dual_off", "rec_const_off", "pk_rec_dual_off", "pk_rec_const_off")
+_OP = ("op_peer", "op_side", "op_role", "op_code", "op_pad", "op_omega_bits", "op_mailbox_row",
+       "op_peer_dual", "op_peer_const", "pk_op_peer_dual", "pk_op_peer_const")
 _LAUNCH = ("launch_class", "launch_begin", "launch_end", "launch_level", "launch_stride", "launch_n_recv", "launch_bytes", "launch_n_sh", "plain_launches", "n_levels")
 _CHAIN = ("chain_class", "chain_block_records", "chain_level_loop", "chain_banded", "chain_valid", "chain_mailbox_rows", "chain_mailbox_width", "mailbox_sends")
 _PER_CHAIN = ("cl_rec_begin", "cl_count", "cl_ticket0", "cl_flags", "tk_launch", "tk_block", "dep_off", "dep")
+# read-only words of the records, the ops and their packet copies: where a factor lies in the dual / const arrays, in elements
+# (Python ints via .tolist(); pk_*: NO_PACKET where the launch has no packets) — tests/test_far_offsets_host.py
+NO_PACKET = -(1 << 63)
 _SEQ = ("seg_n", "seq_factor", "seq_om_off", "seq_mk_off", "seq_mk", "seq_om_bits")
 
 
