@@ -92,6 +92,12 @@ int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t*
  * references a banded vector; none when LPMP_NO_DIFF_BAND was set as the plan was made), and the receives of both */
 int lpmp_plan_diff_band_info(lpmp_plan* p, int direction, int mode, int64_t* diff_launches, int64_t* band_launches,
                              int64_t* diff_receives, int64_t* band_receives);
+/* host only: new VALUES for the pool of a plan, packed as lpmp_model.sh_data (same n_shared_tables, sh_off, dims).  A NaN entry is
+ * refused (LPMP_ERR_INVALID naming the table, the plan untouched), as are a NULL pointer and a plan without a pool.  The band of
+ * every entry a DIFF factor references is detected again (LPMP_NO_DIFF_BAND stays what it was when the plan was made), and in every
+ * schedule the plan has cached each launch of class diff gets its kernel choice again by the rule above: nothing else of a schedule
+ * moves and none is built.  lpmp_plan_get_diff_band / lpmp_plan_diff_band_info report the new state. */
+int lpmp_plan_set_shared_pool(lpmp_plan* p, const double* sh_data);
 
 /* the same summary for an iterator-range pass (LP_MP.h:981-1005) given as factor list + weight rows + receive-mask
  * rows, without a device: what lpmp_schedule_create[_fused] would build.  Arguments as lpmp_compute_pass_custom. */
@@ -307,8 +313,9 @@ int lpmp_upload_duals(lpmp_engine* e, const double* host_in);
  *     is built (and counted by lpmp_schedules_built) if the engine has not run it before — a function of the structure, cached.
  * In every case all tracked per-factor bounds become stale and the primal labels go back to unset (lpmp_evaluate_primal is +inf
  * until a rounding pass has run on the new costs); the kernel-timing accumulators are left alone.
- * The shared pool (lpmp_model.sh_data) is STRUCTURE — the bands of DIFF vectors and the LDS table sets depend on it — and is not
- * replaced: changing it, like dims, messages, relations or partitions, remains a job for lpmp_upload_model. */
+ * The shared pool (lpmp_model.sh_data) is not part of the packed constants and is not touched here: lpmp_upload_shared_pool below
+ * replaces its values.  Its entries, their dims, the entry a factor references, like dims, messages, relations or partitions,
+ * remain a job for lpmp_upload_model. */
 int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, const double* dual_data, int dual_mem);
 /* theta of the listed VECTOR factors := row i of src (accumulate = 0) or += row i of src (accumulate != 0; one IEEE add per entry).
  * Row i starts at src + i * src_stride and has f_dim0[factors[i]] entries; src_stride may exceed the longest listed vector (one
@@ -318,6 +325,32 @@ int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, c
  * smaller than the longest listed vector. */
 int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, int src_mem,
                      int accumulate);
+/* New VALUES for the shared pool of the planned model: sh_data is packed as lpmp_model.sh_data of the uploaded model (same
+ * n_shared_tables, sh_off, dims), host or device memory (sh_mem); a device source is copied to the host first, where the NaN refusal
+ * and the band detection read it.  LPMP_ERR_STATE before the first lpmp_upload_model; LPMP_ERR_INVALID for a NULL pointer, a model
+ * without a pool, or a NaN entry (naming the table; +inf is allowed, as at the upload) — with nothing changed.  Only two things in
+ * a plan read a pool value: that refusal, and the band of every entry a DIFF factor references.  So the call settles passes that
+ * ran ahead, runs lpmp_plan_set_shared_pool on the engine's plan, rewrites the pool block of its device copy (band words and values;
+ * the {scale, offset} cells do not move) and drops the captured graphs of every schedule with a launch of class diff — a graph holds
+ * the kernel choice; it is captured again on the schedule's next run.  The duals are not touched (any duals are a valid
+ * reparametrisation of the new costs); all tracked bounds become stale and the primal labels unset, as after lpmp_upload_costs.
+ * Plans nothing: the plan handle, lpmp_schedules_built, every lpmp_schedule_create id and boundary / halo object stay.  Returns after
+ * its copies have completed. */
+int lpmp_upload_shared_pool(lpmp_engine* e, const double* sh_data, int sh_mem);
+/* constants of the listed PAIRWISE factors := row i of src.  Row i starts at src + i * src_stride and has
+ * as many entries as the factor has constants (lpmp_model.h: DENSE dim0 * dim1, row-major; POTTS, SHARED, DIFF: 1); factors is a host array,
+ * src host or device memory (src_mem).  Settles first.  The row goes to every place the sweep kernels read that factor's constants
+ * from: the Potts scalar; the first word of a SHARED / DIFF cell AND the scalar of the constants the cell is gathered from (a later
+ * lpmp_upload_costs without new constants keeps it); a dense table in the constant buffer — the engine's own or the caller's borrowed
+ * one — and, under the rows layout, the table part of the factor's row (not its messages); under LPMP_TABLES_F32 / _F32_ROUND the
+ * narrowed floats in the float table and nothing as doubles (a borrowed buffer is not written for tables).  The bounds of the listed
+ * factors become stale and the primal labels unset.  n == 0 is a no-op after the checks.
+ * LPMP_ERR_INVALID, naming the offender, with nothing written: an index out of range, a VECTOR factor, a factor listed twice,
+ * src_stride smaller than the longest listed row.  LPMP_ERR_UNSUPPORTED, naming the lowest factor, when a float mode refuses an entry
+ * of a listed table (the refusals of the upload) — checked by a read-only launch over the listed rows BEFORE anything is written:
+ * the old costs are whole and passes continue on them (stronger than lpmp_upload_costs, which cannot afford that pass over every
+ * table).  Scales are not validated, as at the upload. */
+int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, int src_mem);
 /* both message vectors of every pairwise factor (DENSE, POTTS, SHARED, DIFF) := +0.0.  Settles first; writes the rows under the rows
  * layout and the packed array otherwise; marks all bounds stale.  Asynchronous on the engine's stream like a pass (it reads nothing
  * of the caller's); lpmp_upload_costs and lpmp_set_vectors return after their copies have completed.  A cold start from device data is lpmp_set_vectors(all unaries,

@@ -96,6 +96,7 @@ struct LaunchView { const UpdRec* recs; const Op* ops; const Op* packets; const 
 struct DevSchedule {
   DevBuf<UpdRec> recs; DevBuf<Op> ops, packets;   // (a scratch schedule is refilled in place: DevBuf::grow)
   std::vector<LevelRange> launches;
+  std::vector<int32_t> diff_tab_off, diff_tab;   // Schedule::diff_tab_off / diff_tab: what new pool values ask again (refresh_diff_band)
   int64_t n_levels = 0, n_recv = 0, n_send = 0, alg_bytes = 0;
   GraphExec graph, graph_primal;           // graph_primal: the same launches with the SWEEP_PRIMAL flag
   bool adaptive_built = false;             // built with every update on the generic kernels (adaptive send rule)
@@ -109,7 +110,14 @@ struct DevSchedule {
     graph.reset(); graph_primal.reset();
     recs.reset(); ops.reset(); packets.reset();
     release_chain();
-    launches.clear();
+    launches.clear(); diff_tab_off.clear(); diff_tab.clear();
+  }
+  // new pool values: diff_band of the KC_DIFF launches again; a graph captured with the other kernel choice is never replayed
+  void refresh_diff_band(const Plan& p) {
+    const bool a = p.refresh_diff_band(launches, diff_tab_off, diff_tab), b = p.refresh_diff_band(plain, diff_tab_off, diff_tab);
+    bool diff = false;
+    for (const auto& lr : launches) diff = diff || lr.kclass == KC_DIFF;
+    if (a || b || diff) { graph.reset(); graph_primal.reset(); }
   }
 };
 
@@ -129,6 +137,15 @@ struct lpmp_plan {
   Schedule pass_cache[LPMP_REPAM_COUNT]; bool have_pass[LPMP_REPAM_COUNT] = {false};   // forward+backward as one fused sequence
   Schedule bf_cache[LPMP_REPAM_COUNT]; bool have_bf[LPMP_REPAM_COUNT] = {false};       // backward+forward (the seam between two passes)
   bool rotation_ok[LPMP_REPAM_COUNT] = {false};
+  // new VALUES for the pool (Plan::set_shared_pool): of the cached schedules only diff_band of their KC_DIFF launches moves
+  void set_shared_pool(const double* values) {
+    p.set_shared_pool(values);
+    auto again = [&](Schedule& s) { p.refresh_diff_band(s.launches, s.diff_tab_off, s.diff_tab); };
+    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
+      for (int d = 0; d < 2; ++d) again(sched_cache[d][m]);
+      again(pass_cache[m]); again(bf_cache[m]);
+    }
+  }
   void drop_caches() {   // the kernel classes of every schedule change with Plan::force_generic
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
       for (int d = 0; d < 2; ++d) { sched_cache[d][m] = Schedule(); have_sched[d][m] = false; }
@@ -266,6 +283,7 @@ struct lpmp_engine {
   bool tab_compact = false;       // f32 tables from host memory: const_buf holds only the cells of the non-DENSE factors
   std::vector<int64_t> sh_cells;  // the SHARED / DIFF cells as launch_shared_cells receives them: {const offset, table offset}
   DevBuf<SetVecRec> d_setrecs; DevBuf<double> d_setsrc;   // records and (host sources) rows of lpmp_set_vectors, refilled in place
+  DevBuf<SetConstRec> d_setcrecs;                         // records of lpmp_set_constants (its host rows share d_setsrc)
   DevBuf<ZeroRec> d_zero; int64_t n_zero = -1;            // pieces of the pairwise message vectors; -1: not built yet
   struct LbRun { int cls; int64_t first, count; };
   std::vector<LbRun> lb_runs;
@@ -340,6 +358,14 @@ struct lpmp_engine {
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
 
+  // every device schedule of the engine (built-in, partition, prepared iterator-range passes, the scratch one)
+  template <class F>
+  void for_each_schedule(F&& f) {
+    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) { for (int d = 0; d < 2; ++d) f(sched[d][m]); f(sched_pass[m]); f(sched_bf[m]); }
+    for (int k = 0; k < 2; ++k) f(sched_part[k]);
+    for (auto& c : custom) if (c) f(*c);
+    f(scratch);
+  }
   void release_primal() {
     d_primal.reset(); d_pinit.reset(); d_plinks.reset(); d_pw_unary.reset(); d_pcost.reset(); d_pbad.reset();
     h_pbad = nullptr;
@@ -362,7 +388,7 @@ struct lpmp_engine {
     d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
     d_tab32.reset(); tab_prec = LPMP_TABLES_F64; tab_flag = 0;
     schedules_built = 0; const_bad = false; tab_compact = false; sh_cells.clear();
-    d_setrecs.reset(); d_setsrc.reset(); d_zero.reset(); n_zero = -1;
+    d_setrecs.reset(); d_setsrc.reset(); d_setcrecs.reset(); d_zero.reset(); n_zero = -1;
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
     d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
@@ -529,7 +555,7 @@ DevChain upload_chain(const std::vector<ChainLaunch>& lds, const std::vector<int
 void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool keep = false, bool adaptive_built = false) {
   if (keep) { d.graph.reset(); d.graph_primal.reset(); }
   else d.release();
-  d.launches = s.launches; d.n_levels = s.n_levels; d.n_recv = s.n_recv; d.n_send = s.n_send; d.alg_bytes = s.alg_bytes;
+  d.launches = s.launches; d.diff_tab_off = s.diff_tab_off; d.diff_tab = s.diff_tab; d.n_levels = s.n_levels; d.n_recv = s.n_recv; d.n_send = s.n_send; d.alg_bytes = s.alg_bytes;
   d.adaptive_built = adaptive_built;
   fill_device(d.recs, s.recs, stream);
   fill_device(d.ops, s.ops, stream);
@@ -1139,6 +1165,12 @@ int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t*
     if (banded) *banded = p->p.sh_banded[(size_t)table];
   });
 }
+int lpmp_plan_set_shared_pool(lpmp_plan* p, const double* sh_data) {
+  return guarded([&] {
+    if (!p || !sh_data) throw std::runtime_error("lpmp_plan_set_shared_pool: null argument");
+    p->set_shared_pool(sh_data);
+  });
+}
 int lpmp_plan_diff_band_info(lpmp_plan* p, int d, int mode, int64_t* diff_launches, int64_t* band_launches, int64_t* diff_receives,
                              int64_t* band_receives) {
   return guarded([&] {
@@ -1437,6 +1469,22 @@ static void gather_shared_cells(lpmp_engine* e) {
   launch_shared_cells(e->d_shared, (int64_t)e->sh_cells.size() / 2, e->d_const, e->stream);
   HIP_CHECK(hipGetLastError());
 }
+// ... the pool block of d_shared, behind the cells of n_sf factors: every entry t of the plan's pool with one 8-byte band word
+// {int32 lo, int32 hi} in front of it — sweep_diff_band_kernel learns the band of a DIFF vector from the word before the offset in
+// the factor's cell (entries no DIFF factor references: an empty band, never read).  Entry t starts at shared_pool_at(p, t).
+static int64_t shared_pool_at(const Plan& p, int32_t t) { return p.sh_off[(size_t)t] + t + 1; }
+static void write_shared_pool(lpmp_engine* e, const Plan& p, int64_t n_sf) {
+  const int64_t n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
+  if ((size_t)(2 * n_sf + n_pool) > e->d_shared.capacity()) throw std::runtime_error("shared tables: the pool does not fit its buffer");
+  std::vector<double> pool((size_t)n_pool);
+  for (int32_t t = 0; t < p.n_shared; ++t) {
+    const int32_t word[2] = {p.sh_lo[(size_t)t], p.sh_hi[(size_t)t]};
+    static_assert(sizeof word == sizeof(double), "band word");
+    std::memcpy(&pool[(size_t)(shared_pool_at(p, t) - 1)], word, sizeof word);
+    std::copy(p.sh_data.begin() + p.sh_off[(size_t)t], p.sh_data.begin() + p.sh_off[(size_t)t + 1], pool.begin() + shared_pool_at(p, t));
+  }
+  h2d(e->d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), e->stream);
+}
 // rows layout: every row [table | m1 | m2] from the packed constants and the packed duals
 static void build_rows(lpmp_engine* e) {
   launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 0, e->stream);
@@ -1522,11 +1570,9 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
       std::vector<int64_t> sf;
       for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
-      // Every pool entry of this copy has one 8-byte band word {int32 lo, int32 hi} in front of it: sweep_diff_band_kernel learns
-      // the band of a DIFF vector from the word before the offset in the factor's cell (entries no DIFF factor references: an
-      // empty band, never read).  Entry t starts at pool_at(t).
+      // (the pool behind the cells: write_shared_pool)
       const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
-      auto pool_at = [&](int32_t t) { return p.sh_off[(size_t)t] + t + 1; };
+      auto pool_at = [&](int32_t t) { return shared_pool_at(p, t); };
       e->d_shared.alloc((size_t)(2 * n_sf + n_pool));
       if ((((uintptr_t)e->d_shared.get() - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
       const int64_t base = (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8);
@@ -1539,16 +1585,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
         pl->p.dev_coff[f] = base + 2 * k;
       }
       e->sh_cells = std::move(cells);
-      {
-        std::vector<double> pool((size_t)n_pool);
-        for (int32_t t = 0; t < p.n_shared; ++t) {
-          const int32_t word[2] = {p.sh_lo[(size_t)t], p.sh_hi[(size_t)t]};
-          static_assert(sizeof word == sizeof(double), "band word");
-          std::memcpy(&pool[(size_t)(pool_at(t) - 1)], word, sizeof word);
-          std::copy(p.sh_data.begin() + p.sh_off[(size_t)t], p.sh_data.begin() + p.sh_off[(size_t)t + 1], pool.begin() + pool_at(t));
-        }
-        h2d(e->d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), e->stream);
-      }
+      write_shared_pool(e, p, n_sf);
       gather_shared_cells(e);
       std::vector<ShTableDesc> desc((size_t)p.n_shared);
       for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + pool_at(t), p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
@@ -2379,6 +2416,105 @@ int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const do
     }
     launch_set_vectors(e->d_setrecs, n, d_src, dev ? src_stride : 1, e->d_dual, e->d_lb, accumulate != 0, e->stream);
     HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
+  });
+}
+
+int lpmp_upload_shared_pool(lpmp_engine* e, const double* sh_data, int sh_mem) {
+  return guarded([&] {
+    if (!e || !e->plan) throw StateError("lpmp_upload_shared_pool: no model uploaded (the structure comes from lpmp_upload_model)");
+    if (!sh_data) throw std::runtime_error("lpmp_upload_shared_pool: null argument");
+    Plan& p = e->plan->p;
+    if (p.n_shared <= 0 || !e->d_shared) throw std::runtime_error("lpmp_upload_shared_pool: the model has no pool of shared tables");
+    HIP_CHECK(hipSetDevice(e->device));
+    // the band detection and the NaN refusal read the values on the host: a device source (KBs to a few MB) is copied there first
+    std::vector<double> host;
+    if (sh_mem == LPMP_MEM_DEVICE) {
+      host.resize((size_t)p.sh_off[(size_t)p.n_shared]);
+      d2h(host.data(), sh_data, host.size() * sizeof(double), e->stream);
+      sh_data = host.data();
+    }
+    settle(e);          // the duals are those of the pass the caller is at (as the warm start of lpmp_upload_costs)
+    check_chain(e);
+    e->plan->set_shared_pool(sh_data);          // (a NaN entry: thrown before anything has changed)
+    HIP_CHECK(hipStreamSynchronize(e->stream));   // no launch in flight reads the pool while it is rewritten
+    write_shared_pool(e, p, (int64_t)e->sh_cells.size() / 2);
+    e->for_each_schedule([&](DevSchedule& d) { d.refresh_diff_band(p); });
+    costs_changed(e);
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, int src_mem) {
+  return guarded([&] {
+    require_model(e);
+    if (n < 0 || (n > 0 && (!factors || !src))) throw std::runtime_error("lpmp_set_constants: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    const Plan& p = e->plan->p;
+    std::vector<uint8_t> seen((size_t)p.nf, 0);
+    std::vector<SetConstRec> recs((size_t)n);
+    const bool dev = src_mem == LPMP_MEM_DEVICE, f32 = e->tab_prec != LPMP_TABLES_F64;
+    const int64_t sh_base = e->d_shared ? (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8) : 0;
+    int64_t longest = 0, total = 0;
+    int32_t longest_f = -1;
+    bool any_f32 = false;
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t f = factors[i];
+      if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_set_constants: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+      if (p.f_kind[f] == LPMP_F_VECTOR) throw std::runtime_error("lpmp_set_constants: factor " + std::to_string(f) + " is a VECTOR factor (its costs are duals: lpmp_set_vectors)");
+      if (seen[(size_t)f]) throw std::runtime_error("lpmp_set_constants: factor " + std::to_string(f) + " is listed twice (the result would depend on the order of two waves)");
+      seen[(size_t)f] = 1;
+      const int64_t len = p.f_coff[f + 1] - p.f_coff[f];
+      if (len > longest) { longest = len; longest_f = f; }
+      // (a host source is packed row after row: stride 1, row = offset)
+      SetConstRec r{p.coff(f), 0, dev ? i : total, (int32_t)len, f, 0, 0};
+      if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+        if (f32) { r.f32 = 1; any_f32 = true; }                       // the float table only: nothing is written as doubles
+        else if (e->rows) { r.dst = p.f_coff[f]; r.dst2 = p.coff(f); r.two = 1; }   // the packed table, and the table part of the factor's row
+      } else if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) {
+        // the first word of the factor's cell, and the scalar lpmp_upload_costs would gather the cell from again
+        const int64_t k = (r.dst - sh_base) / 2;
+        if (k < 0 || 2 * k + 1 >= (int64_t)e->sh_cells.size() || sh_base + 2 * k != r.dst) throw std::runtime_error("lpmp_set_constants: internal: factor " + std::to_string(f) + " has no cell");
+        r.dst2 = e->sh_cells[(size_t)(2 * k)]; r.two = 1;
+      }
+      recs[(size_t)i] = r;
+      total += len;
+    }
+    if (n > 0 && src_stride < longest)
+      throw std::runtime_error("lpmp_set_constants: src_stride " + std::to_string(src_stride) + " is smaller than the " + std::to_string(longest) + " entries of factor " + std::to_string(longest_f));
+    settle(e);
+    check_chain(e);
+    if (n == 0) return;
+    e->d_setcrecs.grow((size_t)n);
+    h2d(e->d_setcrecs, recs.data(), (size_t)n * sizeof(SetConstRec), e->stream);
+    const double* d_src = src;
+    if (!dev) {
+      std::vector<double> rows((size_t)total);
+      for (int64_t i = 0; i < n; ++i) std::copy(src + i * src_stride, src + i * src_stride + recs[(size_t)i].len, rows.begin() + recs[(size_t)i].src_row);
+      e->d_setsrc.grow((size_t)total);
+      h2d(e->d_setsrc, rows.data(), (size_t)total * sizeof(double), e->stream);
+      d_src = e->d_setsrc;
+    }
+    const int64_t stride = dev ? src_stride : 1;
+    if (any_f32) {
+      // a listed set is small: every row of a float table is checked BEFORE anything is written, so a refusal leaves the old costs
+      // whole (stronger than lpmp_upload_costs, which cannot afford a pass over all tables)
+      const int strict = e->tab_prec == LPMP_TABLES_F32 ? 1 : 0;
+      DevBuf<int> d_bad; d_bad.alloc(1);
+      int bad = INT32_MAX;
+      h2d(d_bad, &bad, sizeof(int), e->stream);
+      launch_set_constants_check(e->d_setcrecs, n, d_src, stride, strict, d_bad, e->stream);
+      HIP_CHECK(hipGetLastError());
+      d2h(&bad, d_bad, sizeof(int), e->stream);
+      HIP_CHECK(hipStreamSynchronize(e->stream));
+      if (bad != INT32_MAX)
+        throw UnsupportedError("lpmp_set_constants: table precision " + std::string(strict ? "f32" : "f32_round") + ": the row of factor " + std::to_string(bad) +
+                               (strict ? " holds an entry that is not exactly a float (or a finite one beyond float's range or below FLT_MIN)"
+                                       : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN") + "; nothing was written");
+    }
+    launch_set_constants(e->d_setcrecs, n, d_src, stride, e->d_const, e->d_lb, e->stream);
+    HIP_CHECK(hipGetLastError());
+    if (e->have_primal) { upload_unset_primal(e); e->primal_t = 0; }   // as after lpmp_upload_costs: the labels belong to the old costs
     HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
   });
 }

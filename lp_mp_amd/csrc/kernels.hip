@@ -3344,6 +3344,57 @@ zero_pairwise_kernel(const ZeroRec* __restrict__ recs, int64_t n, double* __rest
   double* d = dual + r.dual_off;
   for (int64_t x = lane; x < r.len; x += 64) d[x] = 0.0;
 }
+// constants of listed pairwise factor k := row src_row of src (engine.cpp, lpmp_set_constants): one wave per record, lanes stride over
+// the entries, 64-bit offsets (a table may start past 2^32 doubles).  A record names every place the sweep kernels read the
+// factor's constants from — the Potts scalar; the first word of a SHARED / DIFF cell and the scalar the cell was gathered from; a
+// dense table in the packed constants and in the factor's row of the rows layout; or the float table, narrowed here as
+// narrow_tables_kernel narrows (round to nearest even).  The check kernel applies that kernel's refusals to the rows of the float
+// tables and writes nothing else: the host launches it first and stops before any store when a row is refused.
+__device__ __forceinline__ bool narrow_refuses(double x, int strict) {
+  const float f = (float)x;
+  const double ax = fabs(x);
+  if (!(ax < LPMP_INF)) return false;              // +-inf pass through (NaN: outside the contract, passes)
+  if (fabsf(f) == __builtin_inff()) return true;
+  if (x != 0.0 && ax < 1.17549435082228750797e-38) return true;
+  return strict && (double)f != x;
+}
+__global__ void __launch_bounds__(256)
+set_constants_check_kernel(const SetConstRec* __restrict__ recs, int64_t n, const double* __restrict__ src, int64_t src_stride, int strict,
+                           int* __restrict__ bad) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const SetConstRec r = recs[k];
+  if (!r.f32) return;
+  const double* row = src + r.src_row * src_stride;
+  bool refuse = false;
+  for (int x = lane; x < r.len; x += 64) refuse = refuse || narrow_refuses(row[x], strict);
+  if (refuse) atomicMin(bad, r.factor);
+}
+__global__ void __launch_bounds__(256)
+set_constants_kernel(const SetConstRec* __restrict__ recs, int64_t n, const double* __restrict__ src, int64_t src_stride, double* __restrict__ cdata,
+                     double* __restrict__ lb) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const SetConstRec r = recs[k];
+  const double* row = src + r.src_row * src_stride;
+  if (r.f32) {
+    float* t = reinterpret_cast<float*>(cdata + r.dst);
+    for (int x = lane; x < r.len; x += 64) t[x] = (float)row[x];
+  } else {
+    double* a = cdata + r.dst;
+    for (int x = lane; x < r.len; x += 64) a[x] = row[x];
+    if (r.two) { double* b = cdata + r.dst2; for (int x = lane; x < r.len; x += 64) b[x] = row[x]; }
+  }
+  if (lane == 0) lb[r.factor] = __longlong_as_double(-1LL);   // stale, as set_vectors_kernel marks it
+}
+void launch_set_constants_check(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, int strict, int* bad, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(set_constants_check_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, src, src_stride, strict, bad);
+}
+void launch_set_constants(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, double* cdata, double* lb, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(set_constants_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, src, src_stride, cdata, lb);
+}
 void launch_set_vectors(const SetVecRec* recs, int64_t n, const double* src, int64_t src_stride, double* dual, double* lb, int accumulate, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(set_vectors_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, src, src_stride, dual, lb, accumulate);
 }

@@ -76,6 +76,11 @@ struct RowRec { int64_t dual_off, const_off, row_off; int32_t d0, d1; };
 struct NarrowRec { int64_t src_off, dst_off, n; int32_t factor, pad; };
 // new costs on a planned model: one listed vector factor of lpmp_set_vectors (its place in the packed duals, its row of the source)
 struct SetVecRec { int64_t dual_off, src_row; int32_t len, factor; };
+// ... one listed pairwise factor of lpmp_set_constants: its row of the source and every place the sweep kernels read its constants
+// from, in 8-byte units relative to the const base pointer (the engine's other allocations are addressed that way, too, so an
+// offset may be negative): dst, and with `two` set dst2 for a second copy of doubles.  f32: the factor is a DENSE one whose table
+// is stored as floats, starting at dst
+struct SetConstRec { int64_t dst, dst2, src_row; int32_t len, factor, f32, two; };
 // ... and one piece of the pairwise message vectors lpmp_zero_pairwise_duals clears (device dual offset, at most ZERO_RUN_MAX doubles)
 struct ZeroRec { int64_t dual_off, len; };
 constexpr int64_t ZERO_RUN_MAX = 8192;
@@ -116,5 +121,10 @@ void launch_narrow_tables(const NarrowRec* recs, int64_t n, const double* src, f
 // the listed runs of the dual array := +0.0
 void launch_set_vectors(const SetVecRec* recs, int64_t n, const double* src, int64_t src_stride, double* dual, double* lb, int accumulate, hipStream_t s);
 void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStream_t s);
+// constants of the listed pairwise factors := rows of src, written to every place of the record (float tables narrowed), their
+// tracked bounds NaN.  The check launch writes nothing but *bad: the lowest factor index whose float table would refuse an entry of
+// its row, by the rule of launch_narrow_tables (the caller sets it to INT32_MAX first)
+void launch_set_constants_check(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, int strict, int* bad, hipStream_t s);
+void launch_set_constants(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, double* cdata, double* lb, hipStream_t s);
 
 }  // namespace lpmp

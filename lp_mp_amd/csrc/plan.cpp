@@ -108,6 +108,38 @@ void diff_band(const double* D, int64_t n, int32_t* lo, int32_t* hi) {
   *lo = (int32_t)l; *hi = (int32_t)h;
 }
 
+bool Plan::diff_launch_banded(const int32_t* tabs, int64_t n) const {
+  if (no_diff_band) return false;
+  for (int64_t j = 0; j < n; ++j) if (sh_banded[(size_t)tabs[j]] != 1) return false;
+  return true;
+}
+
+bool Plan::refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs) const {
+  bool changed = false;
+  for (LevelRange& lr : launches) {
+    if (lr.kclass != KC_DIFF || lr.diff_row < 0 || (size_t)lr.diff_row + 1 >= tabs_off.size()) continue;
+    const int32_t t0 = tabs_off[(size_t)lr.diff_row], t1 = tabs_off[(size_t)lr.diff_row + 1];
+    const bool band = diff_launch_banded(tabs.data() + t0, t1 - t0);
+    changed = changed || band != lr.diff_band;
+    lr.diff_band = band;
+  }
+  return changed;
+}
+
+void Plan::set_shared_pool(const double* values) {
+  if (!values) fail("shared pool: null argument");
+  if (n_shared <= 0) fail("shared pool: the model has no pool of shared tables");
+  for (int t = 0; t < n_shared; ++t)       // (refused for the reason build() gives, before anything is changed)
+    for (int64_t i = sh_off[(size_t)t]; i < sh_off[(size_t)t + 1]; ++i)
+      if (values[i] != values[i]) fail("shared table " + std::to_string(t) + ": NaN entry");
+  sh_data.assign(values, values + sh_off[(size_t)n_shared]);
+  for (int t = 0; t < n_shared; ++t) {
+    if (sh_banded[(size_t)t] < 0) continue;                 // no DIFF factor references the entry
+    diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
+    sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
+  }
+}
+
 void Plan::build(const lpmp_model& m) {
   const bool timed_ = std::getenv("LPMP_PLAN_TIMES") != nullptr;
   auto t_last_ = std::chrono::steady_clock::now();
@@ -896,24 +928,33 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
       out.recs[cur[key(u)]++] = r;
     }
   }
+  out.diff_tab_off.assign(1, 0); out.diff_tab.clear();
+  std::vector<uint8_t> diff_seen((size_t)p.n_shared, 0);
   for (int64_t k = 0; k < n_keys; ++k) {
     LevelRange lr;
     lr.kclass = key_class[k]; lr.begin = key_count[k]; lr.end = key_count[k + 1];
     lr.level = key_level[k];
     lr.n_recv = key_recv[k]; lr.n_send = key_send[k]; lr.bytes = key_bytes[k];
     lr.max_dim = key_maxdim[k];
-    if (lr.kclass == KC_DIFF && !p.no_diff_band) {
+    if (lr.kclass == KC_DIFF) {
       // the banded kernel: only if every receive of the launch has a banded vector.  A launch without any receive (the first
       // step of a sweep: sends only, the two kernels do the same there) goes by the vectors of its sends, so that a model is
-      // on one kernel throughout.
-      bool all = true;
-      for (int64_t i = lr.begin; i < lr.end && all; ++i) {
+      // on one kernel throughout.  The pool entries asked are kept: new pool values ask them again (Plan::refresh_diff_band).
+      for (int64_t i = lr.begin; i < lr.end; ++i) {
         const UpdRec& r = out.recs[(size_t)i];
         const Op* o = ops.data() + r.op_begin;
         const int n_ops = lr.n_recv > 0 ? r.n_recv : r.n_send;
-        for (int q = 0; q < n_ops && all; ++q) all = p.sh_banded[(size_t)p.f_table[(size_t)o[q].peer]] == 1;
+        for (int q = 0; q < n_ops; ++q) {
+          const int32_t t = p.f_table[(size_t)o[q].peer];
+          if (!diff_seen[(size_t)t]) { diff_seen[(size_t)t] = 1; out.diff_tab.push_back(t); }
+        }
       }
-      lr.diff_band = all;
+      const int32_t t0 = out.diff_tab_off.back();
+      for (size_t j = (size_t)t0; j < out.diff_tab.size(); ++j) diff_seen[(size_t)out.diff_tab[j]] = 0;
+      std::sort(out.diff_tab.begin() + t0, out.diff_tab.end());
+      lr.diff_row = (int32_t)out.diff_tab_off.size() - 1;
+      out.diff_tab_off.push_back((int32_t)out.diff_tab.size());
+      lr.diff_band = p.diff_launch_banded(out.diff_tab.data() + t0, (int64_t)out.diff_tab.size() - t0);
     }
     if (!kc_is_shared(lr.kclass)) { out.launches.push_back(lr); continue; }
     // a shared class: one launch per table-set group of the records (classify), each with the list of its distinct tables

@@ -133,6 +133,8 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   int32_t n_sh = 0; int32_t sh_tab[SHARED_MAX_TABLES] = {};
   // class diff: every receive of every record references a banded vector (cleared by LPMP_NO_DIFF_BAND): the banded kernel
   bool diff_band = false;
+  // class diff: the launch's row of Schedule::diff_tab_off — the pool entries diff_band was decided from (-1: another class)
+  int32_t diff_row = -1;
 };
 constexpr int PK_MAX_OPS = 8;                 // packets hold at most this many ops per factor
 // launches whose factors have more ops than that (but at most this many: the LDS slab of a lane group) run the
@@ -246,6 +248,10 @@ struct Schedule {             // executable form of one (factor list, omega, mas
   // sequences), the launches of the remaining classes stay plain launches (indices into `launches`)
   std::vector<ChainPlan> chains;
   std::vector<int32_t> plain_launches;
+  // per KC_DIFF launch (LevelRange::diff_row, CSR): the distinct pool entries that decide its kernel — those of its receives, of its
+  // sends where it has no receive.  All a schedule keeps of the pool's VALUES is diff_band of those launches, and with this list
+  // Plan::refresh_diff_band sets it again from new values without the records and ops (which the engine does not keep on the host)
+  std::vector<int32_t> diff_tab_off, diff_tab;
 };
 
 struct Plan {
@@ -305,6 +311,14 @@ struct Plan {
 
   // throws std::runtime_error on invalid input (the reference throws too, LP_MP.h:458)
   void build(const lpmp_model& m);
+  // New VALUES for the pool (same entries, offsets and dims; packed as lpmp_model.sh_data).  A NaN entry is refused with nothing
+  // changed.  Of the plan, only sh_data and the band of every entry a DIFF factor references (sh_lo / sh_hi / sh_banded) read a
+  // pool value; of a schedule, only diff_band of its KC_DIFF launches: refresh_diff_band sets those again, for the launches of a
+  // schedule or of any copy of them (tabs_off / tabs: the schedule's diff_tab_off / diff_tab).  Returns whether a launch changed.
+  void set_shared_pool(const double* values);
+  // the banded kernel for a KC_DIFF launch: only if every one of these pool entries (Schedule::diff_tab) holds a banded vector
+  bool diff_launch_banded(const int32_t* tabs, int64_t n) const;
+  bool refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs) const;
   void ensure_weights(int mode);
   void anisotropic_weights(const int32_t* list, int64_t n, Csr<double>& om, Csr<uint8_t>& mk) const;
   // one sweep: a factor list with one omega row and one receive-mask row per listed factor

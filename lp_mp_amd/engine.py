@@ -74,6 +74,7 @@ EXPORTS = [
     "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
     "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches",
     "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
+    "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
 ]
 
 
@@ -190,6 +191,10 @@ def lib():
             L.lpmp_zero_pairwise_duals.argtypes = [C.c_void_p]
             L.lpmp_schedules_built.restype = C.c_int64
             L.lpmp_schedules_built.argtypes = [C.c_void_p]
+        if hasattr(L, "lpmp_set_constants"):         # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_plan_set_shared_pool.argtypes = [C.c_void_p, C.c_void_p]
+            L.lpmp_upload_shared_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.lpmp_set_constants.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -351,6 +356,19 @@ def _diff_band_info(self, d: int, mode: int) -> dict:
     return dict(zip(("diff_launches", "band_launches", "diff_receives", "band_receives"), [x.value for x in v]))
 
 
+def _set_shared_pool(self, sh_data):
+    """new VALUES for the pool of this plan (lpmp_plan_set_shared_pool): ``sh_data`` packed as ``FlatModel.sh_data``.  The bands of
+    the DIFF vectors and the kernel choice of every cached launch of class diff follow; nothing else of a schedule moves.  None is
+    passed through as a null pointer (refused).  For a stand-alone plan: the plan of an engine (``Engine.plan``) is swapped together
+    with the device copy of the pool by ``Engine.upload_shared_pool``."""
+    if sh_data is None:
+        _chk(self.L.lpmp_plan_set_shared_pool(self.h, None))
+        return
+    sh = np.ascontiguousarray(sh_data, np.float64).reshape(-1)
+    _chk(self.L.lpmp_plan_set_shared_pool(self.h, C.c_void_p(sh.ctypes.data)))
+
+
+Plan.set_shared_pool = _set_shared_pool
 Plan.diff_bands = _diff_bands
 Plan.diff_band_info = _diff_band_info
 
@@ -533,6 +551,50 @@ class Engine:
                 raise ValueError("set_vectors: source shorter than the rows it is said to hold")
             ptr, mem = C.c_void_p(src.ctypes.data), MEM_HOST
         _chk(self.L.lpmp_set_vectors(self.h, n, factors.ctypes.data, ptr, int(src_stride), mem, 1 if accumulate else 0))
+
+    def upload_shared_pool(self, sh_data=None, sh_dev: Optional[int] = None):
+        """New VALUES for the shared pool of the planned model (lpmp_upload_shared_pool): ``sh_data`` packed as ``FlatModel.sh_data``
+        (same entries and dims), or ``sh_dev``: a raw device pointer to such an array.  Plans nothing; the duals stay.  With a host
+        array ``self.model`` becomes ``self.model.with_pool(sh_data)``."""
+        if sh_dev is not None:
+            _chk(self.L.lpmp_upload_shared_pool(self.h, C.c_void_p(sh_dev), MEM_DEVICE))
+            return
+        if sh_data is None:
+            _chk(self.L.lpmp_upload_shared_pool(self.h, None, MEM_HOST))
+            return
+        sh = np.ascontiguousarray(sh_data, np.float64).reshape(-1)
+        have = getattr(getattr(self, "model", None), "sh_data", None)
+        if have is not None and sh.shape != np.shape(have):
+            raise ValueError(f"upload_shared_pool: a pool of {np.shape(have)[0]} entries expected, got {sh.shape[0]}")
+        _chk(self.L.lpmp_upload_shared_pool(self.h, C.c_void_p(sh.ctypes.data), MEM_HOST))
+        if have is not None:
+            import dataclasses
+            self.model = dataclasses.replace(self.model, sh_data=np.array(sh, copy=True), _keep=[])
+
+    def set_constants(self, factors, src=None, src_dev: Optional[int] = None, src_stride: Optional[int] = None):
+        """constants of the listed PAIRWISE factors := row i of ``src`` (lpmp_set_constants): a dense table row-major, or the one
+        scalar of a Potts / SHARED / DIFF factor.  ``src``: a 2-D numpy array [n, >= longest row], or a 1-D one with ``src_stride``;
+        ``src_dev``: a raw device pointer with ``src_stride`` instead."""
+        factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
+        n = int(factors.shape[0])
+        if src_dev is not None:
+            if src_stride is None:
+                raise ValueError("set_constants: src_dev needs src_stride")
+            ptr, mem = C.c_void_p(src_dev), MEM_DEVICE
+        else:
+            src = np.ascontiguousarray(src, np.float64)
+            if src.ndim == 2:
+                if src.shape[0] < n:
+                    raise ValueError("set_constants: fewer rows than factors")
+                src_stride = src.shape[1] if src_stride is None else src_stride
+            elif src_stride is None:
+                raise ValueError("set_constants: a flat source needs src_stride")
+            if n > 0 and src.size < (n - 1) * int(src_stride) + 1:
+                raise ValueError("set_constants: source shorter than the rows it is said to hold")
+            if src.size == 0:
+                src = np.zeros(1)                    # (n == 0: a valid pointer that is never read)
+            ptr, mem = C.c_void_p(src.ctypes.data), MEM_HOST
+        _chk(self.L.lpmp_set_constants(self.h, n, factors.ctypes.data, ptr, int(src_stride), mem))
 
     def zero_pairwise_duals(self):
         """both message vectors of every pairwise factor := +0.0 (lpmp_zero_pairwise_duals)"""

@@ -228,6 +228,7 @@ class LP:
         self._begun = False
         self._duals_host: Optional[np.ndarray] = None
         self._table_precision = None
+        self._pool_changed = False           # set_shared_table / set_diff_table since the last upload
 
     def set_table_precision(self, precision):
         """"f64" / "f32" (strict) / "f32_round": dense pairwise tables as floats on the device, widened in the load, all arithmetic
@@ -255,6 +256,32 @@ class LP:
         self._shared_tables.append(D.reshape(1, -1))
         self._dirty = True
         return len(self._shared_tables) - 1
+
+    def _set_pool_entry(self, who: str, t: int, values: np.ndarray):
+        if not 0 <= int(t) < len(self._shared_tables):
+            raise RuntimeError("%s: table id out of range" % who)
+        have = self._shared_tables[int(t)]
+        if values.shape != have.shape:
+            raise RuntimeError("%s: entry %d is %s, not %s (a structural change: another pool is another model)" % (who, t, have.shape, values.shape))
+        if np.any(np.isnan(values)):
+            raise RuntimeError("%s: NaN entry" % who)
+        have[...] = values                   # in place: every factor object bound to the entry sees the new values
+        self._pool_changed = True
+
+    def set_shared_table(self, t: int, V):
+        """new values for pool entry ``t`` (add_shared_table), same shape.  NOT a structural call: ``upload_costs()`` hands the pool
+        to the planned model (Engine.upload_shared_pool).  Every shared_pairwise_factor on the entry sees the new table."""
+        V = np.array(V, np.float64)
+        if V.ndim != 2:
+            raise RuntimeError("set_shared_table: a [d0, d1] table is expected")
+        self._set_pool_entry("set_shared_table", t, V)
+
+    def set_diff_table(self, t: int, D):
+        """new values for the difference vector ``t`` (add_diff_table), same length; as ``set_shared_table``"""
+        D = np.array(D, np.float64)
+        if D.ndim != 1:
+            raise RuntimeError("set_diff_table: a vector is expected")
+        self._set_pool_entry("set_diff_table", t, D.reshape(1, -1))
 
     def add_factor(self, container: FactorContainer, *args) -> int:
         """a factor of the container: the arguments of ``container.factor_type``, or one ready instance of it.  ONE exception to
@@ -420,8 +447,9 @@ class LP:
         """hand the factors' current costs (``set_factor_cost``) to the device.  No structural call since the last upload: the
         planned model gets new numbers (Engine.upload_costs), every schedule stays.  Cold (default): constants, and duals = the
         costs — a fresh problem.  ``warm``: constants only, the messages are kept, and every unary whose cost changed receives
-        new - old (Engine.set_vectors, accumulate): the reparametrised problem of the new costs.  After a structural call this is
-        the ordinary upload."""
+        new - old (Engine.set_vectors, accumulate): the reparametrised problem of the new costs; of the pairwise factors only those
+        whose constants differ from the uploaded ones are sent (Engine.set_constants).  A pool changed by ``set_shared_table`` /
+        ``set_diff_table`` goes first (Engine.upload_shared_pool).  After a structural call this is the ordinary upload."""
         if self._engine is None or self._dirty:
             self._ready()
             return
@@ -431,9 +459,22 @@ class LP:
             new = self.flat_model()
         finally:
             self._duals_host = kept
+        if self._pool_changed:
+            e.upload_shared_pool(new.sh_data)
+            self._pool_changed = False
         if warm:
-            if new.const_data.shape[0] > 0:
+            listed = getattr(e, "set_constants", None)     # (an engine object without listed constants takes the whole array)
+            if new.const_data.shape[0] > 0 and listed is None:
                 e.upload_costs(const=new.const_data)
+            elif new.const_data.shape[0] > 0:
+                coff = new.const_offsets()
+                diff = new.const_data != self._model.const_data
+                pw = [int(f) for f in np.flatnonzero(new.f_kind != M.F_VECTOR) if np.any(diff[coff[f]:coff[f + 1]])]
+                if pw:
+                    rows = np.zeros((len(pw), int(max(coff[f + 1] - coff[f] for f in pw))))
+                    for k, f in enumerate(pw):
+                        rows[k, :coff[f + 1] - coff[f]] = new.const_data[coff[f]:coff[f + 1]]
+                    listed(pw, rows)
             off = new.dual_offsets()
             delta = new.dual_data - self._cost_dual    # new - old COSTS (the device holds reparametrised duals; so may _model)
             vec = np.flatnonzero(new.f_kind == M.F_VECTOR)
@@ -464,6 +505,7 @@ class LP:
             self._cost_dual = self._flat_costs       # (not _model.dual_data: after a structural call that holds pulled duals)
             self._engine.upload(self._model, table_precision=self._table_precision)
             self._dirty = False
+            self._pool_changed = False
         self._engine.set_inner_iterations(self._inner)
         self._engine.set_reparametrization_type(self._rtype)
         return self._engine

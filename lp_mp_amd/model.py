@@ -220,6 +220,20 @@ class FlatModel:
             const[dense] = const[dense].astype(np.float32).astype(np.float64)
         return dataclasses.replace(self, const_data=const, _keep=[])
 
+    def with_pool(self, sh_data) -> "FlatModel":
+        """the same structure with other VALUES in the shared pool (``sh_data`` packed as ``self.sh_data``: same entries, same
+        dims) — what ``Engine.upload_shared_pool`` / ``Plan.set_shared_pool`` turn a planned model into.  Another length and a NaN
+        entry are refused; every other array is shared with ``self``."""
+        import dataclasses
+        if self.sh_data is None:
+            raise ValueError("with_pool: the model has no shared pool")
+        sh = np.array(sh_data, np.float64, copy=True).reshape(-1)
+        if sh.shape != np.shape(self.sh_data):
+            raise ValueError(f"with_pool: a pool of {np.shape(self.sh_data)[0]} entries expected, got {sh.shape[0]}")
+        if np.any(np.isnan(sh)):
+            raise ValueError("with_pool: NaN entry")
+        return dataclasses.replace(self, sh_data=sh, _keep=[])
+
     def with_factor_order(self, rank: np.ndarray) -> "FlatModel":
         """the same factors, messages and costs with the factor relations REPLACED by a chain through all factors in the order
         ``rank[f]`` (position of factor f, e.g. Plan.suggest_order): AddFactorRelation(by_rank[i], by_rank[i + 1]) for consecutive
