@@ -128,6 +128,12 @@ int lpmp_plan_mailbox_info(lpmp_plan* p, int direction, int mode, int64_t* n_row
  * orders: n passes = H, W, (K, W) x (n-1), T) — decided by an op-by-op comparison of the fused
  * schedules; 0 when consecutive passes run one after the other; negative lpmp_status on error */
 int lpmp_plan_pass_rotates(lpmp_plan* p, int mode);
+/* 1 when the STRUCTURE of this mode's joined passes allows the peer-minima form (the W records publish per edge
+ * what the record at the other end would compute from the table, K / T read no table): exact 32-label dense class, every W
+ * record sends over exactly the <= 4 edges it receives from, every receive of K / T served by exactly one W record.  The
+ * engine further needs f64 tables in the packed layout and LPMP_NO_PEER_MINIMA unset.  why (n bytes; may be null): "" or the
+ * first obstacle.  0 otherwise; negative lpmp_status on error */
+int lpmp_plan_peer_minima(lpmp_plan* p, int mode, char* why, int n);
 
 /* ---- variable orders and partitions (host only; csrc/graph.cpp) ---------------------------------------------------------------
  * The sweep is Gauss-Seidel over the factor ORDER, which is the caller's input (AddFactorRelation, include/LP_MP.h:698-702; the
@@ -418,6 +424,9 @@ int lpmp_reset_kernel_timing(lpmp_engine* e);
 int lpmp_get_chain_launches(lpmp_engine* e, int n_classes, int64_t* chain_launches /*[n]*/);
 /* of the launches reported for class diff: how many ran the banded kernel (sweep_diff_band_kernel) */
 int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches);
+/* joined-pass launches in the peer-minima form since the last lpmp_reset_kernel_timing; counted with timing off,
+ * too (passes that run ahead of the caller are never timed): with timing on since the reset, a part of dense32's chain launches */
+int lpmp_get_peer_minima_launches(lpmp_engine* e, int64_t* launches);
 
 /* ---- boundary step of the partitioned (multi-GPU) sweep, DESIGN.md 7 -------------------------------------------------
  * One process per GPU owns one part of the factor graph (lp_mp_amd/multi_gpu.py builds the parts; a C++ host can do

@@ -126,7 +126,7 @@ static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 
   return v;
 }
 
-struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0; };
+struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, peer_minima_launches = 0; };
 
 }  // namespace
 
@@ -310,6 +310,7 @@ struct lpmp_engine {
     // periodic form (rotation_chain): dc holds the TEMPLATE of n_tmpl passes whose tickets [per_begin, per_begin + per_len) are
     // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
     bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
+    bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
     int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
   };
   // the ticket lists of a pass count are device memory (C3, 32 passes: ~350 MB): the cache of built chains is bounded in
@@ -334,6 +335,11 @@ struct lpmp_engine {
     }
   } spec;
   bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
+  // peer minima (kernels.hip, dense_pq_*_body): 32 doubles per factor, written by the W steps of a joined launch and read by its K / T
+  // steps — never across calls (every call starts with H and W), so no upload invalidates it.  Allocated with the first eligible
+  // joined launch, freed with the model; not part of the chain cache.  LPMP_NO_PEER_MINIMA=1: every launch in the old form
+  bool use_peer_minima = true;
+  DevBuf<double> d_peerq;
   bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
   RotSettings rot_opts;            // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
@@ -387,6 +393,7 @@ struct lpmp_engine {
     d_dual = nullptr; d_const = nullptr;
     d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
     d_tab32.reset(); tab_prec = LPMP_TABLES_F64; tab_flag = 0;
+    d_peerq.reset();
     schedules_built = 0; const_bad = false; tab_compact = false; sh_cells.clear();
     d_setrecs.reset(); d_setsrc.reset(); d_setcrecs.reset(); d_zero.reset(); n_zero = -1;
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
@@ -947,12 +954,21 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   if (!why.empty()) return no(why.c_str());
   if (periodic && (int64_t)48 * (int64_t)(2 * jt.per_len) / jt.ring + 64 >= (1 << CHAIN_GEN_BITS)) throw std::runtime_error("rotation chain: ring too small for its generation counter");
   const int n_steps = 2 * n + 1;
+  // peer minima: the structure allows it (order.cpp), the tables are doubles in the packed layout, and the buffer can be had
+  const char* pq_why = !e->use_peer_minima ? "switched off (LPMP_NO_PEER_MINIMA)" : !ri.peer_minima ? ri.peer_minima_why.c_str()
+                     : e->tab_flag != 0 ? "float tables" : e->rows ? "rows layout" : nullptr;
+  if (!pq_why && !e->d_peerq.get()) {
+    if (!e->d_peerq.try_alloc((size_t)e->plan->p.nf * 32)) pq_why = "no device memory for the published minima";
+  }
+  const bool pq = pq_why == nullptr;
+  if (verbose) std::fprintf(stderr, "lpmp:   peer minima: %s\n", pq ? "W publishes, K / T read no table" : pq_why);
   std::vector<ChainLaunch> lds;
   for (int s = 0; s < n_steps; ++s) {
     const auto& t = ri.t[jt.step_tmpl[s]];
     const DevSchedule& ds = t.sched == 0 ? e->sched_pass[mode] : e->sched_bf[mode];
     const int32_t row = jt.step_row[s];
-    const int32_t hist = row < 0 ? 0 : (jt.step_tmpl[s] == 1 ? HIST_END : HIST_MID) | (row << 2);
+    int32_t hist = row < 0 ? 0 : (jt.step_tmpl[s] == 1 ? HIST_END : HIST_MID) | (row << 2);
+    if (pq) hist |= jt.step_tmpl[s] == 1 ? CHAIN_LAUNCH_PQ_PUBLISH : CHAIN_LAUNCH_PQ_CONSUME;
     lds.push_back({t.lr.stride > 0 ? ds.packets + t.lr.pk_begin : nullptr, ds.recs + t.lr.begin, ds.ops, t.lr.end - t.lr.begin, t.lr.stride, hist});
     rc.factors += t.factors; rc.recv += t.recv; rc.bytes += t.bytes;
     if (periodic && s >= 2 * depth && s < 3 * depth) { rc.per_factors += t.factors; rc.per_recv += t.recv; rc.per_bytes += t.bytes; }
@@ -985,6 +1001,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   rc.dc.kclass = ri.kclass;
   e->rot_cache_bytes += rc.dev_bytes;
   ++e->schedules_built;
+  rc.peer_minima = pq;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
@@ -1015,13 +1032,15 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
-  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (rc->peer_minima && !e->d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
+  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream, rc->peer_minima ? e->d_peerq.get() : nullptr)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
     e->pending.push_back({a, b, c.kclass, rc->factors + extra * rc->per_factors, rc->recv + extra * rc->per_recv, rc->bytes + extra * rc->per_bytes});
     e->ct[c.kclass].chain_launches++;
   }
+  if (rc->peer_minima) e->ct[c.kclass].peer_minima_launches++;   // (counted with timing off, too: passes that run ahead are never timed)
   HIP_CHECK(hipGetLastError());
   e->chain_ran = true;
   return true;
@@ -1298,6 +1317,29 @@ int lpmp_plan_pass_rotates(lpmp_plan* p, int mode) {
   return rc == LPMP_OK ? r : rc;
 }
 
+// may the joined passes of a mode take the peer-minima form, as far as the STRUCTURE decides (RotationInfo::peer_minima; the engine
+// adds: f64 tables, packed layout, LPMP_NO_PEER_MINIMA unset)?  1 / 0, or an error code; why (n bytes, may be null): "" or the obstacle
+int lpmp_plan_peer_minima(lpmp_plan* p, int mode, char* why, int n) {
+  int r = 0;
+  const int rc = guarded([&] {
+    if (!p || mode < 0 || mode >= LPMP_REPAM_COUNT) throw std::runtime_error("bad argument");
+    std::string reason;
+    if (p->rot[mode].valid) { r = p->rot[mode].peer_minima ? 1 : 0; reason = p->rot[mode].peer_minima_why; }
+    else {
+      if (!p->have_bf[mode]) { plan_pass_schedule(p, mode); if (p->pass_cache[mode].recs.empty() && !p->pass_cache[mode].launches.empty()) throw StateError("pass schedule already handed to the device"); plan_rotation(p, mode); }
+      if (!p->rotation_ok[mode]) reason = "the passes of this mode do not join";
+      else if (p->pass_cache[mode].recs.empty() || p->bf_cache[mode].recs.empty()) throw StateError("pass schedule already handed to the device");
+      else {
+        const RotationInfo ri = plan_rotation_chain(p->pass_cache[mode], p->bf_cache[mode], p->p.nf);
+        r = ri.valid && ri.peer_minima ? 1 : 0;
+        reason = ri.valid ? ri.peer_minima_why : "the pass does not have the H, W, K, T shape of one packed class";
+      }
+    }
+    if (why && n > 0) { std::snprintf(why, (size_t)n, "%s", reason.c_str()); }
+  });
+  return rc == LPMP_OK ? r : rc;
+}
+
 // ---- engine ---------------------------------------------------------------------------------------
 int lpmp_create(int device, lpmp_engine** out) {
   return guarded([&] {
@@ -1322,6 +1364,8 @@ int lpmp_create(int device, lpmp_engine** out) {
     e->use_chain = !(nc && nc[0] == '1');
     const char* nb = std::getenv("LPMP_NO_BLOCKED_PASSES");
     e->use_blocked_passes = !(nb && nb[0] == '1');
+    const char* np = std::getenv("LPMP_NO_PEER_MINIMA");
+    e->use_peer_minima = !(np && np[0] == '1');
     if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
     if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }
     if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_opts.depth = std::max(1, std::atoi(v)); e->rot_opts.depth_set = true; }
@@ -2668,6 +2712,16 @@ int lpmp_get_chain_launches(lpmp_engine* e, int n, int64_t* chain_launches) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
     e->drain_timing();
     for (int c = 0; c < n && c < KC_COUNT; ++c) chain_launches[c] = e->ct[c].chain_launches;
+  });
+}
+// joined-pass launches in the peer-minima form (W publishes, K / T read no table) since the last lpmp_reset_kernel_timing; counted
+// whether or not timing is on — with timing on from the reset, it is a part of the class's chain launches
+int lpmp_get_peer_minima_launches(lpmp_engine* e, int64_t* launches) {
+  return guarded([&] {
+    if (!e || !launches) throw std::runtime_error("null argument");
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->drain_timing();
+    *launches = e->ct[KC_DENSE_32].peer_minima_launches;
   });
 }
 // of the launches lpmp_get_kernel_timing reports for class diff: how many ran sweep_diff_band_kernel

@@ -1360,6 +1360,322 @@ chain_dense_pk_f32_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches
   }
 }
 
+// ---- peer minima (joined passes of the exact 32-label f64 class) -----------------------------------------------
+// In n joined passes H, W, (K, W)^(n-1), T every table is needed twice per pass: by the W record at one end of the edge and by
+// the K / T record at the other.  The W record that has just SENT m' over an edge still holds the edge's table, and
+// q'[a] = min_b (T[a][b] + m'[b]) is all the neighbour's next receive over that edge computes from the table.  In a launch whose
+// steps carry roles (plan.hpp, CHAIN_LAUNCH_PQ_*; order.cpp decides per mode) the W records PUBLISH q' — 32 doubles in
+// peerq[factor * 32 ...] — and the H / K / T records CONSUME it: they request no table and no m_o.  min is exact and every
+// T[a][b] + m'[b] is one rounding whatever the lane layout, so q' is bit for bit what the consumer computes today.
+// Bodies of their own, so that the shared dense body (and every kernel made from it) keeps its code.
+// KM: tables a publishing record holds at once.  2 (shipped): 165 VGPRs, three waves per SIMD; the tables of the last two receives
+// are still in registers when theta is final, those of the first two are requested again behind the sends (a second read, mostly
+// on-die).  4: every table stays in registers from its receive to its publish, 227 VGPRs, two waves per SIMD — measured slower
+// than the old form on the headline grid (1.54 against 1.61-1.65 G message updates per second; KM = 2: 1.78-1.79; EXPERIMENTS.md N).
+constexpr int PQ_KM = 2;
+constexpr int PQ_OPS = PEER_MINIMA_MAX_OPS;                        // receives and sends of a record of such a launch (order.cpp checks)
+
+// one record's packet and the fields both bodies read from it
+struct PqRec {
+  const UpdRec* hdr; const Op* lop;
+  int n_recv, n_send; bool live, vl, preload_ok; double* own_g;
+  double* s_ms[PQ_OPS]; double s_om[PQ_OPS]; int s_fw[PQ_OPS], s_peer[PQ_OPS];
+  int64_t pdual[PQ_OPS]; int side[PQ_OPS], defer[PQ_OPS], rpeer[PQ_OPS];
+};
+template <int L>
+__device__ __forceinline__ void pq_load_rec(PqRec& r, double2_t* slab, const Op* __restrict__ packets, double* __restrict__ dual, int64_t idx, int64_t count,
+                                            int stride, int g) {
+  constexpr int G = 64;
+  r.live = idx < count;
+  load_packet<G>(slab, packets, nullptr, nullptr, idx, stride, r.live, g);
+  r.hdr = reinterpret_cast<const UpdRec*>(&slab[0]);
+  r.lop = reinterpret_cast<const Op*>(&slab[3]);
+  r.n_recv = r.live ? min(uni<G>((int)r.hdr->n_recv), PQ_OPS) : 0;
+  r.n_send = r.live ? min(uni<G>((int)r.hdr->n_send), PQ_OPS) : 0;
+  r.preload_ok = r.live && (uni<G>(r.hdr->kind_flags) & UPD_PRELOAD_OK) != 0;
+  r.own_g = dual + (r.live ? uni64<G>(r.hdr->dual_off) : 0);
+  r.vl = r.live && g < L;
+#pragma unroll
+  for (int k = 0; k < PQ_OPS; ++k) {
+    r.s_ms[k] = dual; r.s_om[k] = 0.0; r.s_fw[k] = 0; r.s_peer[k] = 0;
+    if (k < r.n_send) {
+      const Op& o = r.lop[r.n_recv + k];
+      r.s_ms[k] = dual + uni64<G>(o.peer_dual) + (((uni<G>(o.info) >> 5) & 1) ? L : 0);
+      r.s_om[k] = o.omega; r.s_fw[k] = uni<G>(o.pad); r.s_peer[k] = uni<G>(o.peer);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) {
+    r.pdual[j] = 0; r.side[j] = 0; r.defer[j] = 0; r.rpeer[j] = 0;
+    if (j < r.n_recv) {
+      const Op& o = r.lop[j];
+      r.pdual[j] = uni64<G>(o.peer_dual); r.side[j] = (uni<G>(o.info) >> 5) & 1; r.defer[j] = uni<G>(o.pad); r.rpeer[j] = uni<G>(o.peer);
+    }
+  }
+}
+
+// H, K, T: a receive is msv (its own side's vector) and the published q — no table, no m_o; from delta = msv + qv on, and in
+// the sends, statement for statement what dense_pk_body does in a chain
+template <int L>
+__device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ packets, double* __restrict__ dual, double* __restrict__ lb,
+                                                      const double* __restrict__ peerq, int64_t count, int stride, int64_t block,
+                                                      const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
+  constexpr int G = 64, GPB = 256 / G, A = ACC_COH;
+  __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  PqRec r;
+  pq_load_rec<L>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
+  const bool aborted = !chain_wait(*ca, ticket);
+  double theta = r.vl ? ld_dual<A>(r.own_g + g) : 0.0;
+  double sm[PQ_OPS], msv[PQ_OPS], qv[PQ_OPS], mnew[PQ_OPS];
+#pragma unroll
+  for (int k = 0; k < PQ_OPS; ++k) { sm[k] = 0.0; if (r.preload_ok && k < r.n_send && g < L) sm[k] = ld_dual<A>(r.s_ms[k] + g); }
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) {
+    msv[j] = 0.0; qv[j] = 0.0; mnew[j] = 0.0;
+    if (j < r.n_recv && g < L) {
+      msv[j] = ld_dual<A>(dual + r.pdual[j] + (r.side[j] == 0 ? 0 : L) + g);
+      // the slot was written by the W record that wrote the m' this record waits for anyway (see dense_pq_publish_body)
+      qv[j] = ld_dual<A>(peerq + (int64_t)r.rpeer[j] * L + g);
+    }
+  }
+  // every dual this record reads is awaited before its first store (see dense_pk_body)
+  asm volatile("" :: "v"(theta));
+#pragma unroll
+  for (int k = 0; k < PQ_OPS; ++k) { asm volatile("" :: "v"(sm[k])); asm volatile("" :: "v"(msv[k])); asm volatile("" :: "v"(qv[k])); }
+  chain_stamp(*ca, ticket, 4);
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) {
+    if (j >= r.n_recv) break;
+    double pb = LPMP_INF;
+    if (g < L) {
+      const double delta = msv[j] + qv[j];
+      theta += delta;
+      const double mn = msv[j] - delta;
+      pb = mn + qv[j];
+      if (r.defer[j]) mnew[j] = mn;
+      else st_dual<A>(dual + r.pdual[j] + (r.side[j] == 0 ? 0 : L) + g, mn);
+    }
+    const bool track = !r.defer[j], hist = hmode == HIST_MID;
+    if (track || hist) {
+      pb = vec_min<G, L>(pb);
+      if (g == 0) {
+        if (track) st_lb<A>(lb + r.rpeer[j], pb);
+        if (hist) st_lb<A>(lbh + r.rpeer[j], pb);
+      }
+    }
+  }
+  chain_stamp(*ca, ticket, 5);
+  const double snap_min_v = vec_min<G, L>(r.vl ? theta : LPMP_INF);
+  if (hmode == HIST_MID) { if (r.live && g == 0) st_lb<A>(lbh + uni<G>(r.hdr->factor), snap_min_v); }
+  if (r.vl && !aborted) {
+    const double snap = theta;
+    if (!r.preload_ok) {
+#pragma unroll
+      for (int k = 0; k < PQ_OPS; ++k) if (k < r.n_send && r.s_fw[k] == 0) sm[k] = ld_dual<A>(r.s_ms[k] + g);
+#pragma unroll
+      for (int k = 0; k < PQ_OPS; ++k) asm volatile("" :: "v"(sm[k]));
+    }
+#pragma unroll
+    for (int k = 0; k < PQ_OPS; ++k) {
+      if (k < r.n_send) {
+        const int fw = r.s_fw[k];
+        const double cur = fw > 0 ? (fw == 1 ? mnew[0] : fw == 2 ? mnew[1] : fw == 3 ? mnew[2] : mnew[3]) : sm[k];
+        const double delta = r.s_om[k] * snap;
+        st_dual<A>(r.s_ms[k] + g, cur + delta);
+        theta -= delta;
+        if (g == 0) st_lb<A>(lb + r.s_peer[k], fw > 0 ? r.s_om[k] * snap_min_v : LPMP_NAN);
+      }
+    }
+    st_dual<A>(r.own_g + g, theta);
+  }
+  const double ob = vec_min<G, L>(r.vl ? theta : LPMP_INF);
+  if (r.live && g == 0) {
+    st_lb<A>(lb + uni<G>(r.hdr->factor), ob);
+    if (hmode == HIST_END) st_lb<A>(lbh + uni<G>(r.hdr->factor), ob);
+  }
+}
+
+// W: the receives and sends of dense_pk_body in a chain (every receive is deferred into its send: order.cpp), then the publish
+template <int L, int KM>
+__device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
+                                                      double* __restrict__ lb, double* __restrict__ peerq, int64_t count, int stride, int64_t block,
+                                                      const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
+  static_assert(L == 32 && (KM == 2 || KM == 4), "the exact 32-label class");
+  constexpr int G = 64, GPB = 256 / G, A = ACC_COH;
+  constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL;
+  __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
+  __shared__ double lds_mo[GPB][L];
+  __shared__ double lds_q[GPB][L];
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int c2 = g % CL, rl = g / CL;
+  PqRec r;
+  pq_load_rec<L>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
+  double2_t t[KM][NL];
+  auto load_tabs = [&](const int c) {
+#pragma unroll
+    for (int j = 0; j < KM; ++j) {
+      if (c + j < r.n_recv) {
+        const double* T = cdata + uni64<G>(r.lop[c + j].peer_const);
+#pragma unroll
+        for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<false>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
+      } else {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
+      }
+    }
+  };
+  // lds_q[a] = min over the other side of T + lds_mo, for the side whose labels a are: 0 the table's rows, 1 its columns
+  // (the two reductions of dense_pk_body)
+  auto reduce = [&](const int j, const int side) {
+    if (side == 0) {
+      const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_mo[grp][2 * c2]);
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double2_t tv = t[j][i];
+        double v = fmin(tv.x + mv.x, tv.y + mv.y);
+        v = row_allreduce_min<CL>(v);
+        if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
+      }
+    } else {
+      double vx = LPMP_INF, vy = LPMP_INF;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double m1v = lds_mo[grp][i * RPL + rl];
+        const double2_t tv = t[j][i];
+        vx = fmin(vx, tv.x + m1v);
+        vy = fmin(vy, tv.y + m1v);
+      }
+#pragma unroll
+      for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
+      if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
+    }
+  };
+  load_tabs(0);                                  // constants first, then the predecessors, then the duals
+  const bool aborted = !chain_wait(*ca, ticket);
+  double theta = r.vl ? ld_dual<A>(r.own_g + g) : 0.0;
+  double msv[PQ_OPS], mov[PQ_OPS], mnew[PQ_OPS];
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) {
+    msv[j] = 0.0; mov[j] = 0.0; mnew[j] = 0.0;
+    if (j < r.n_recv && g < L) {
+      msv[j] = ld_dual<A>(dual + r.pdual[j] + (r.side[j] == 0 ? 0 : L) + g);
+      mov[j] = ld_dual<A>(dual + r.pdual[j] + (r.side[j] == 0 ? L : 0) + g);
+    }
+  }
+  asm volatile("" :: "v"(theta));
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) { asm volatile("" :: "v"(msv[j])); asm volatile("" :: "v"(mov[j])); }
+  chain_stamp(*ca, ticket, 4);
+#pragma unroll
+  for (int c = 0; c < PQ_OPS; c += KM) {
+    if (c >= r.n_recv) break;
+    if (c > 0) load_tabs(c);
+#pragma unroll
+    for (int j = 0; j < KM; ++j) {
+      if (c + j >= r.n_recv) break;
+      if (g < L) lds_mo[grp][g] = mov[c + j];
+      wave_sync();
+      reduce(j, r.side[c + j]);
+      wave_sync();
+      if (g < L) {
+        const double qv = lds_q[grp][g];
+        const double delta = msv[c + j] + qv;
+        theta += delta;
+        mnew[c + j] = msv[c + j] - delta;        // stored by the send that forwards it
+      }
+      wave_sync();
+    }
+  }
+  chain_stamp(*ca, ticket, 5);
+  const double snap_min_v = vec_min<G, L>(r.vl ? theta : LPMP_INF);
+  double mpr[PQ_OPS];                            // the vector sent over the edge of receive j
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) mpr[j] = 0.0;
+  if (r.vl && !aborted) {
+    const double snap = theta;
+#pragma unroll
+    for (int k = 0; k < PQ_OPS; ++k) {
+      if (k < r.n_send) {
+        const int fw = r.s_fw[k];
+        const double cur = fw == 1 ? mnew[0] : fw == 2 ? mnew[1] : fw == 3 ? mnew[2] : mnew[3];
+        const double delta = r.s_om[k] * snap;
+        const double v = cur + delta;
+        st_dual<A>(r.s_ms[k] + g, v);
+        theta -= delta;
+#pragma unroll
+        for (int j = 0; j < PQ_OPS; ++j) if (fw == j + 1) mpr[j] = v;
+        if (g == 0) st_lb<A>(lb + r.s_peer[k], r.s_om[k] * snap_min_v);
+      }
+    }
+    st_dual<A>(r.own_g + g, theta);
+  }
+  // Publish: for every edge q' from the vector just stored and the table still (KM = 4) or again (KM = 2) in registers: the
+  // reduction of the OTHER side, i.e. what the neighbour's receive would compute.  No new flag or wait: the slot's reader
+  // is the record that already waits for this ticket because it reads the m' stored above, these are agent-scope stores
+  // issued before chain_publish like that one, and the next W record that overwrites the slot already depends on that
+  // reader (order.cpp plan_rotation_chain, kinds 2 / 3: both touch the pairwise factor).
+  auto publish = [&](const int c) {
+#pragma unroll
+    for (int j = 0; j < KM; ++j) {
+      if (c + j >= r.n_recv) break;
+      const int q = c + j;
+      if (g < L) lds_mo[grp][g] = q == 0 ? mpr[0] : q == 1 ? mpr[1] : q == 2 ? mpr[2] : mpr[3];
+      wave_sync();
+      reduce(j, 1 - r.side[q]);
+      wave_sync();
+      if (g < L && !aborted) st_dual<A>(peerq + (int64_t)r.rpeer[q] * L + g, lds_q[grp][g]);
+      wave_sync();
+    }
+  };
+  if constexpr (KM == 4) publish(0);
+  else {
+    if (r.n_recv > KM) { publish(KM); load_tabs(0); }
+    publish(0);
+  }
+  const double ob = vec_min<G, L>(r.vl ? theta : LPMP_INF);
+  if (r.live && g == 0) {
+    st_lb<A>(lb + uni<G>(r.hdr->factor), ob);
+    if (hmode == HIST_END) st_lb<A>(lbh + uni<G>(r.hdr->factor), ob);
+  }
+}
+
+// chain_loop for launches whose steps carry a role in ChainLaunch::pad above the bound row
+template <class Body>
+__device__ __forceinline__ void chain_loop_roles(const ChainArgs& ca, const ChainLaunch* __restrict__ launches, Body body) {
+  __shared__ int s_ticket[2];
+  if (threadIdx.x == 0) s_ticket[0] = atomicAdd(ca.next, 1);
+  __syncthreads();
+  for (int it = 0;; ++it) {
+    const int ticket = s_ticket[it & 1];
+    if (ticket >= ca.n_tickets) break;
+    if (threadIdx.x == 0) s_ticket[(it + 1) & 1] = atomicAdd(ca.next, 1);
+    chain_stamp(ca, ticket, 0);
+    const TicketRef tr = chain_ticket_ref(ca, ticket);
+    ChainLaunch ln = launches[ca.tk_launch[tr.idx] + tr.copy * ca.per_launch_shift];
+    const int role = ln.pad & CHAIN_LAUNCH_PQ_MASK;
+    ln.pad &= ~CHAIN_LAUNCH_PQ_MASK;
+    if (ln.pad & 3) {
+      ln.pad += (tr.copy * ca.per_row_shift) << 2;
+      if ((ln.pad >> 2) >= ca.hist_rows) ln.pad = 0;
+    }
+    body(ln, (int64_t)ca.tk_block[tr.idx], ticket, role);
+    chain_publish(ca, ticket);
+    __syncthreads();
+  }
+}
+template <int L, int KM>
+__global__ void __launch_bounds__(256, KM == 2 ? 3 : 2)
+chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
+                      double* __restrict__ lb, double* __restrict__ peerq) {
+  chain_loop_roles(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int role) {
+    const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
+    double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
+    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish_body<L, KM>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    else dense_pq_consume_body<L>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+  });
+}
+
 // the generic kernels inside the chain executor (chains of tiny factors: multicut / C5 labeling lists): nothing
 // constant worth requesting ahead, so the wait comes first
 static_assert(GEN_WAVES == GENERIC_BLOCK_RECORDS && 64 * SMALL_WAVES == SMALL_BLOCK_RECORDS, "plan.hpp: records per workgroup of the generic kernels");
@@ -3195,8 +3511,14 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
+  if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
+    if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
+    auto k = chain_dense_pq_kernel<32, PQ_KM>;
+    hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq);
+    return true;
+  }
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
   if (kclass == KC_GENERIC) return generic(chain_generic_kernel<64>, GenCtx<64>::THREADS);

@@ -96,8 +96,9 @@ bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, cons
 // band: the launch's LevelRange::diff_band (sweep_diff_band_kernel; cdata then holds a band word in front of every D)
 void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s);
+// peerq != nullptr: the launches carry CHAIN_LAUNCH_PQ_* roles (joined passes with peer minima; KC_DENSE_32 on f64 tables only)
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s);
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr);
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n_launches, double* dual, const double* cdata,
                        const int32_t* tabs, double* lb, hipStream_t s);
 void debug_set_level_trace(long long* p);

@@ -25,6 +25,52 @@ std::vector<int32_t> launch_touchers(const Schedule& s, const LevelRange& lr, in
   return t;
 }
 
+// Peer minima (kernels.hip, dense_pq_*_body): may the W records publish, per edge, what the record at the other end computes
+// from the table?  "" or the first obstacle.  The W step: every record receives and then sends over the same <= 4 edges, each
+// send forwarding a distinct receive (Op::pad of the send = index of the receive + 1, and the receive is marked deferred).  The
+// H, K, T steps: at most 4 receives and 4 sends, H receives nothing (no slot is written before it), and every receive of K and T
+// reads a pairwise factor that exactly one W record receives-and-sends.
+std::string peer_minima_obstacle(const Schedule& fb, const Schedule& bf, const LevelRange& h, const LevelRange& w, const LevelRange& k,
+                                 const LevelRange& t, int64_t nf) {
+  if (w.kclass != KC_DENSE_32) return "not the exact 32-label dense class";
+  for (const LevelRange* lr : {&h, &w, &k, &t}) if (lr->stride <= 0 || lr->stride > 1 + PK_MAX_OPS) return "a step is not in packet form";
+  std::vector<uint8_t> pub((size_t)nf, 0);
+  for (int64_t i = w.begin; i < w.end; ++i) {
+    const UpdRec& r = fb.recs[i];
+    if (r.n_recv != r.n_send || r.n_recv > PEER_MINIMA_MAX_OPS) return "a W record does not send over exactly the <= 4 edges it receives from";
+    uint32_t seen = 0;
+    for (int q = 0; q < r.n_send; ++q) {
+      const Op& o = fb.ops[r.op_begin + r.n_recv + q];
+      if (o.pad < 1 || o.pad > r.n_recv || ((seen >> o.pad) & 1u)) return "a W send does not forward a receive of its own";
+      seen |= 1u << o.pad;
+      if (fb.ops[r.op_begin + o.pad - 1].peer != o.peer) return "a W send forwards a receive of another factor";
+    }
+    for (int q = 0; q < r.n_recv; ++q) {
+      const Op& o = fb.ops[r.op_begin + q];
+      if (o.pad == 0) return "a W receive is stored before its send";
+      if (o.peer < 0 || o.peer >= nf || pub[o.peer]) return "two W records reach one pairwise factor";
+      pub[o.peer] = 1;
+    }
+  }
+  for (int64_t i = h.begin; i < h.end; ++i) {
+    const UpdRec& r = fb.recs[i];
+    if (r.n_recv != 0 || r.n_send > PEER_MINIMA_MAX_OPS) return "an H record receives, or sends over more than 4 edges";
+  }
+  for (int which = 0; which < 2; ++which) {
+    const Schedule& s = which == 0 ? bf : fb;
+    const LevelRange& lr = which == 0 ? k : t;
+    for (int64_t i = lr.begin; i < lr.end; ++i) {
+      const UpdRec& r = s.recs[i];
+      if (r.n_recv > PEER_MINIMA_MAX_OPS || r.n_send > PEER_MINIMA_MAX_OPS) return "a K / T record has more than 4 receives or sends";
+      for (int q = 0; q < r.n_recv; ++q) {
+        const int32_t f = s.ops[r.op_begin + q].peer;
+        if (f < 0 || f >= nf || !pub[f]) return "a K / T receive reads a pairwise factor no W record receives-and-sends";
+      }
+    }
+  }
+  return "";
+}
+
 }  // namespace
 
 RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf) {
@@ -94,6 +140,8 @@ RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t
     ri.hist_ok = true;
     for (int64_t f = 0; f < nf; ++f) if (!cov[f]) { ri.hist_ok = false; break; }
   }
+  ri.peer_minima_why = peer_minima_obstacle(fb, bf, h, w, k, t, nf);
+  ri.peer_minima = ri.peer_minima_why.empty();
   ri.valid = true;
   return ri;
 }

@@ -174,6 +174,11 @@ constexpr int32_t CHAIN_LAUNCH_LABEL_PAIRED = 2;  // ... and in every record sen
 // dense chain launches: message vectors between dependent records travel as tagged granules (kernels.hip, mailbox); the
 // dependencies they cover are not in dep[] any more.  Bit 30: the low bits of ChainLaunch::pad belong to the joined passes.
 constexpr int32_t CHAIN_LAUNCH_MAILBOX = 1 << 30;
+// joined passes with peer minima (kernels.hip, dense_pq_*_body): the role of a step, in ChainLaunch::pad above the bound row —
+// a W step publishes per edge what the neighbour's next receive computes from the table, the other steps consume it
+constexpr int32_t CHAIN_LAUNCH_PQ_PUBLISH = 1 << 28, CHAIN_LAUNCH_PQ_CONSUME = 1 << 29;
+constexpr int32_t CHAIN_LAUNCH_PQ_MASK = CHAIN_LAUNCH_PQ_PUBLISH | CHAIN_LAUNCH_PQ_CONSUME;
+constexpr int PEER_MINIMA_MAX_OPS = 4;          // receives / sends per record the peer-minima bodies hold in registers
 // the sends of a record that may go to the mailbox = the sends (and forwarded receives) the mailbox form of the dense body
 // holds in registers (kernels.hip: KS, NFW)
 constexpr int MAILBOX_SENDS = 4;
@@ -380,6 +385,11 @@ struct RotationInfo {
   // how far AHEAD in a step's block list a steady-state block's predecessors of the step before lie, as a fraction of the
   // list (a W x H grid in a 2-colour order: one grid row, 1 / H): what the lag of the skewed ticket order has to cover before any slack
   double reach = 0;
+  // peer minima: the STRUCTURE allows the W records to publish, per edge, the minima the K / T record at the other
+  // end would compute from the table, so that K / T read no table (the engine adds: f64 tables, packed layout, switch not off);
+  // peer_minima_why: "" or the first obstacle (LPMP_ROT_VERBOSE prints it)
+  bool peer_minima = false;
+  std::string peer_minima_why = "not a joined pass";
 };
 // fb, bf: forward+backward and backward+forward of a mode whose passes join (engine.cpp plan_rotation), nf factors; not valid
 // unless H, W, K, T are one packed launch each of one chain-capable class

@@ -75,6 +75,7 @@ EXPORTS = [
     "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches",
     "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
     "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
+    "lpmp_plan_peer_minima", "lpmp_get_peer_minima_launches",
 ]
 
 
@@ -185,6 +186,9 @@ def lib():
             L.lpmp_plan_get_diff_band.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
             L.lpmp_plan_diff_band_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
             L.lpmp_get_diff_band_launches.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "lpmp_plan_peer_minima"):      # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_plan_peer_minima.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+            L.lpmp_get_peer_minima_launches.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "lpmp_upload_costs"):          # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
             L.lpmp_upload_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
             L.lpmp_set_vectors.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
@@ -380,6 +384,19 @@ def _pass_info(self, mode: int) -> dict:
 
 
 Plan.pass_schedule_info = _pass_info
+
+
+def _peer_minima(self, mode: int):
+    """(eligible, why): does the STRUCTURE of this mode's joined passes allow the peer-minima form (lpmp_plan_peer_minima)?
+    why: "" or the first obstacle.  The engine further needs f64 tables in the packed layout."""
+    buf = C.create_string_buffer(256)
+    r = self.L.lpmp_plan_peer_minima(self.h, mode, buf, 256)
+    if r < 0:
+        _chk(r)
+    return bool(r), buf.value.decode()
+
+
+Plan.peer_minima = _peer_minima
 
 
 def _pass_rotates(self, mode: int) -> bool:
@@ -644,6 +661,12 @@ class Engine:
         _chk(self.L.lpmp_speculation_stats(self.h, *[C.addressof(x) for x in v]))
         return dict(zip(("batches", "passes_launched", "passes_used", "rollbacks"), [x.value for x in v]))
 
+    def peer_minima_launches(self) -> int:
+        """joined-pass launches in the peer-minima form since the last reset_kernel_timing (lpmp_get_peer_minima_launches)"""
+        nq = C.c_int64()
+        _chk(self.L.lpmp_get_peer_minima_launches(self.h, C.addressof(nq)))
+        return nq.value
+
     def chain_cache_bytes(self) -> int:
         return self.L.lpmp_chain_cache_bytes(self.h)
 
@@ -834,6 +857,11 @@ class Engine:
                         name += ">"
                     out[KCLASS_NAMES[c]] = dict(kernel=name, ms=float(ms[c]), launches=int(arrs[0][c]), chain_launches=int(chain[c]),
                                                 factors=int(arrs[1][c]), receives=int(arrs[2][c]), bytes=int(arrs[3][c]))
+                    if KCLASS_NAMES[c] == "dense32" and hasattr(self.L, "lpmp_get_peer_minima_launches"):
+                        # joined passes in the peer-minima form; the kernel string stays the class's
+                        nq = C.c_int64()
+                        _chk(self.L.lpmp_get_peer_minima_launches(self.h, C.addressof(nq)))
+                        out[KCLASS_NAMES[c]]["peer_minima_launches"] = nq.value
                     continue
                 if not name.endswith(">") and "<" in name:       # exact dense kernels: plain / non-temporal form
                     name += ", true>" if self.L.lpmp_streaming_access(self.h) == 1 else ", false>"
