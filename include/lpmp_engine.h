@@ -291,6 +291,47 @@ int lpmp_evaluate_primal(lpmp_engine* e, double* cost);                         
 int lpmp_download_primal(lpmp_engine* e, int32_t* host_out);
 int lpmp_upload_primal(lpmp_engine* e, const int32_t* host_in);
 
+/* ---- labels from the duals: conditional rounding -------------------------------------------------------------------
+ * The extraction of TRW-S / SRMP: walk the unaries in the sweep order and give each the minimiser of its reparametrised cost
+ * CONDITIONED on the labels its already-visited neighbours got.  Reads the duals, writes only the primal array that
+ * lpmp_download_primal / lpmp_evaluate_primal / lpmp_check_primal_consistency read.  No counterpart in the reference.
+ *
+ * Supported models: every message is LPMP_M_UNARY_PAIRWISE, and every pairwise factor (DENSE in any table precision, POTTS,
+ * SHARED, DIFF) has exactly one such message on each side, from two DIFFERENT unaries.  Anything else — a message of another
+ * kind, a side without a unary or with two, one unary on both sides — is LPMP_ERR_UNSUPPORTED naming the lowest offending factor.
+ * Decoded unaries: every VECTOR factor.  Decode order pi: lpmp_plan_get_order(plan, direction) restricted to them.
+ *
+ * Per unary u with d0 labels:
+ *   c[x] = theta_u[x]                                            (the current dual)
+ *   for every message k of u, in ascending MESSAGE INDEX, whose pairwise factor p has its other unary v LABELLED:
+ *       s = side of u in p;  t[x] = cost_p(x, x_v) if s == 0 else cost_p(x_v, x)
+ *       c[x] = c[x] + (t[x] + m_s[x])                            (m_s: p's dual vector of side s; the inner sum first)
+ *   x_u = the smallest x with c[x] == min_x c[x]
+ * cost_p is the pairwise cost of lpmp_model.h (DENSE: the table entry, floats widened; POTTS: a == b ? 0.0 : diff; SHARED / DIFF:
+ * ONE multiply scale * entry).  All arithmetic is IEEE double in this order, no contraction.  +inf entries are allowed (all +inf:
+ * label 0); NaN is outside the contract.
+ *   initial sweep        "labelled" = earlier in pi
+ *   refine_sweeps >= 0   further sweeps over pi in which EVERY neighbour counts: those earlier in pi with this sweep's label, the
+ *                        others with the previous sweep's.  With all neighbours theta_u + sum m_s is the original unary, so a
+ *                        refinement sweep is ICM on the original energy: the primal cost never rises over these sweeps.
+ * Afterwards both slots of every pairwise factor take the labels of its unaries.
+ * Direction: decode AGAINST the direction of the last sweep (after lpmp_compute_pass, which ends with a backward sweep: LPMP_FORWARD),
+ * as TRW-S does — on chains that is the exact optimum, the other direction is not.
+ *
+ * Settles passes that ran ahead first; asynchronous on the engine's stream like a pass.  Duals, tracked bounds, weights, schedules
+ * and kernel timing do not move; a later ..._pass_and_primal behaves as after lpmp_upload_primal.  The primal array is allocated on
+ * first use whatever ftype_computes_primal says.  The device tables of a direction are structure: built on the first call (one
+ * launch per level and label-count class: the levels of lpmp_plan_get_decode_levels), counted by lpmp_schedules_built, kept across
+ * lpmp_upload_costs / lpmp_upload_shared_pool / lpmp_set_constants / lpmp_set_vectors, dropped by lpmp_upload_model.
+ * LPMP_ERR_STATE before lpmp_upload_model; LPMP_ERR_INVALID for a direction other than 0 / 1 or refine_sweeps < 0. */
+int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps);
+/* host only: the structure of that decode.  n_unaries decoded unaries, n_levels dependent levels (level(u) = 1 + the highest level of
+ * a neighbour earlier in pi, 1 without one: neighbours never share a level, so a level is one launch), n_links unary-pairwise links;
+ * any pointer may be NULL.  lpmp_plan_get_decode_levels: factor_out[i] = i-th unary of pi, level_out[i] its level (n_unaries each).
+ * LPMP_ERR_UNSUPPORTED with the refusal above. */
+int lpmp_plan_decode_info(lpmp_plan* p, int direction, int64_t* n_unaries, int64_t* n_levels, int64_t* n_links);
+int lpmp_plan_get_decode_levels(lpmp_plan* p, int direction, int32_t* factor_out, int32_t* level_out);
+
 int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);

@@ -137,6 +137,11 @@ struct lpmp_plan {
   Schedule pass_cache[LPMP_REPAM_COUNT]; bool have_pass[LPMP_REPAM_COUNT] = {false};   // forward+backward as one fused sequence
   Schedule bf_cache[LPMP_REPAM_COUNT]; bool have_bf[LPMP_REPAM_COUNT] = {false};       // backward+forward (the seam between two passes)
   bool rotation_ok[LPMP_REPAM_COUNT] = {false};
+  DecodePlan decode_cache[2]; bool have_decode[2] = {false, false};   // conditional rounding (structure only: no weights, no mode)
+  const DecodePlan& decode(int d) {
+    if (!have_decode[d]) { decode_cache[d] = p.decode_plan(d); have_decode[d] = true; }
+    return decode_cache[d];
+  }
   // new VALUES for the pool (Plan::set_shared_pool): of the cached schedules only diff_band of their KC_DIFF launches moves
   void set_shared_pool(const double* values) {
     p.set_shared_pool(values);
@@ -261,6 +266,15 @@ struct lpmp_engine {
   uint64_t primal_t = 0;          // primal_access_ of every factor a primal pass touches (they move together)
   bool have_primal = false;
   bool primal_pass = false;       // the launches being issued belong to an ...AndPrimal pass
+  // conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
+  // their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
+  struct DevDecode {
+    struct Launch { int64_t first, count; int32_t width, level; };
+    bool have = false;
+    DevBuf<DecodeRec> recs; DevBuf<DecodeLink> links;
+    std::vector<Launch> launches;
+    void release() { have = false; recs.reset(); links.reset(); launches.clear(); }
+  } decode[2];
   // rows layout (kernels.hip, rows_copy_kernel): dense pairwise factors live as [table | m1 | m2] rows of d_rows; the packed
   // dual array keeps the vector factors and is the format of every call that hands duals over.  packed_stale: the rows hold
   // newer message vectors than the packed array; rows_stale: the packed array was (or may have been) written by the caller
@@ -400,6 +414,7 @@ struct lpmp_engine {
     d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
     release_primal();
+    for (auto& d : decode) d.release();
     d_stale.reset(); d_stale_n.reset();
     h_stale_n = nullptr;
     lb_all_stale = true;
@@ -1244,6 +1259,30 @@ int lpmp_plan_get_update_levels(lpmp_plan* p, int d, int mode, int32_t* out) {
     for (const auto& lr : s.launches) for (int64_t i = lr.begin; i < lr.end; ++i) level_of[s.recs[i].factor] = lr.level;
     const auto& upd = p->p.upd[d];
     for (size_t i = 0; i < upd.size(); ++i) out[i] = level_of[upd[i]];
+  });
+}
+
+// the decode structure of a direction, or the planner's refusal
+static const DecodePlan& decode_plan_or_refuse(lpmp_plan* p, int d) {
+  const DecodePlan& dp = p->decode(d);
+  if (!dp.why.empty()) throw UnsupportedError(dp.why);
+  return dp;
+}
+int lpmp_plan_decode_info(lpmp_plan* p, int d, int64_t* n_unaries, int64_t* n_levels, int64_t* n_links) {
+  return guarded([&] {
+    if (!p || d < 0 || d > 1) throw std::runtime_error("bad argument");
+    const DecodePlan& dp = decode_plan_or_refuse(p, d);
+    if (n_unaries) *n_unaries = (int64_t)dp.unaries.size();
+    if (n_levels) *n_levels = dp.n_levels;
+    if (n_links) *n_links = (int64_t)dp.edges.size();
+  });
+}
+int lpmp_plan_get_decode_levels(lpmp_plan* p, int d, int32_t* factor_out, int32_t* level_out) {
+  return guarded([&] {
+    if (!p || d < 0 || d > 1 || !factor_out || !level_out) throw std::runtime_error("bad argument");
+    const DecodePlan& dp = decode_plan_or_refuse(p, d);
+    std::copy(dp.unaries.begin(), dp.unaries.end(), factor_out);
+    std::copy(dp.level.begin(), dp.level.end(), level_out);
   });
 }
 
@@ -2142,6 +2181,66 @@ int lpmp_upload_primal(lpmp_engine* e, const int32_t* in) {
     settle(e);
     ensure_primal(e);
     h2d(e->d_primal, in, 2 * (size_t)e->plan->p.nf * sizeof(int32_t), e->stream);
+  });
+}
+
+// ---- conditional rounding from the duals -------------------------------------------------------------------
+// The device tables of a direction: the planner's unaries sorted by (level, class) — class 0: at most DECODE_GROUP_MAX labels, a
+// lane group per unary; class 1: a wave per unary — with the device offsets of the uploaded model (rows layout, float tables and
+// SHARED / DIFF cells are all behind Plan::doff / coff).  A function of the structure, like a schedule, and counted as one.
+static void ensure_decode(lpmp_engine* e, int d) {
+  lpmp_engine::DevDecode& dd = e->decode[d];
+  if (dd.have) return;
+  dd.release();
+  const DecodePlan& dp = decode_plan_or_refuse(e->plan.get(), d);
+  const Plan& p = e->plan->p;
+  const size_t nu = dp.unaries.size();
+  auto bucket = [&](size_t i) { return 2 * (size_t)(dp.level[i] - 1) + (p.f_dim0[dp.unaries[i]] > DECODE_GROUP_MAX ? 1 : 0); };
+  std::vector<int64_t> start(2 * (size_t)dp.n_levels + 1, 0);
+  std::vector<int32_t> width(2 * (size_t)dp.n_levels, 0);
+  for (size_t i = 0; i < nu; ++i) { const size_t b = bucket(i); ++start[b + 1]; width[b] = std::max(width[b], p.f_dim0[dp.unaries[i]]); }
+  for (size_t b = 0; b + 1 < start.size(); ++b) start[b + 1] += start[b];
+  std::vector<int32_t> level_of((size_t)p.nf, 0);
+  for (size_t i = 0; i < nu; ++i) level_of[(size_t)dp.unaries[i]] = dp.level[i];
+  std::vector<DecodeRec> recs(nu);
+  std::vector<DecodeLink> links(dp.edges.size());
+  {
+    std::vector<int64_t> cur(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < nu; ++i) {
+      const int32_t u = dp.unaries[i];
+      recs[(size_t)cur[bucket(i)]++] = {p.doff(u), p.f_dim0[u], (int32_t)dp.edge_off[i], (int32_t)(dp.edge_off[i + 1] - dp.edge_off[i]), u};
+    }
+  }
+  for (size_t k = 0; k < links.size(); ++k) {
+    const DecodeEdge& ed = dp.edges[k];
+    links[k] = {p.doff(ed.p), p.coff(ed.p), p.f_kind[ed.p], p.f_dim0[ed.p], p.f_dim1[ed.p], ed.side, ed.other, level_of[(size_t)ed.other]};
+  }
+  for (size_t b = 0; b + 1 < start.size(); ++b)
+    if (start[b + 1] > start[b]) dd.launches.push_back({start[b], start[b + 1] - start[b], width[b], (int32_t)(b / 2) + 1});
+  if (nu) { dd.recs.alloc(nu); h2d(dd.recs, recs.data(), nu * sizeof(DecodeRec), e->stream); }
+  if (!links.empty()) { dd.links.alloc(links.size()); h2d(dd.links, links.data(), links.size() * sizeof(DecodeLink), e->stream); }
+  dd.have = true;
+  ++e->schedules_built;
+  deep_schedule_note(e, dp.n_levels, "the decode order");
+}
+
+int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
+  return guarded([&] {
+    require_model(e);
+    if (direction < 0 || direction > 1) throw std::runtime_error("lpmp_decode_primal: direction must be LPMP_FORWARD or LPMP_BACKWARD");
+    if (refine_sweeps < 0) throw std::runtime_error("lpmp_decode_primal: negative number of refinement sweeps");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);                 // passes that ran ahead: the duals decoded are those of the pass the caller is at
+    require_consts(e);
+    ensure_decode(e, direction);
+    ensure_primal(e);
+    rows_refresh(e);           // (reads the rows; writes no dual)
+    const lpmp_engine::DevDecode& dd = e->decode[direction];
+    for (int sweep = 0; sweep <= refine_sweeps; ++sweep)
+      for (const auto& l : dd.launches)
+        launch_decode(dd.recs, dd.links, e->d_dual, e->d_const, e->d_primal, l.first, l.count, l.width, l.level, sweep ? DECODE_ALL : 0, e->tab_flag, e->stream);
+    launch_primal_propagate(e->d_plinks, e->n_plinks, e->d_primal, e->stream);   // every message's pairwise slot := its unary's label
+    HIP_CHECK(hipGetLastError());
   });
 }
 

@@ -3264,6 +3264,92 @@ primal_propagate_kernel(const PrimalLink* __restrict__ links, int64_t n, int32_t
   const int32_t x = primal[2 * (int64_t)l.u];
   if (x < l.dim) primal[2 * (int64_t)l.p + l.side] = x;
 }
+// ---- conditional rounding from the duals (lpmp_decode_primal) -------------------------------------------------
+// One level of a decode sweep.  A unary u takes the first minimiser of
+//   c[x] = theta_u[x] + sum over its counted links, in link order, of (cost_p(x, x_v) + m_s[x])      (the inner sum first)
+// where x_v is the label the unary on the other side of pairwise factor p holds and m_s p's message vector of u's side.  Counted:
+// every link (DECODE_ALL, a refinement sweep) or the links whose other unary has a lower level than this launch (the initial
+// sweep: exactly the neighbours that are earlier in the order, plan.hpp).  Nothing but u's label is written, so the unaries of a
+// level — never neighbours — are independent.  G lanes per unary stride over x; a lane holds CH entries of c in registers, and
+// a unary of more than G * CH labels is done chunk by chunk (the links are read again; the running minimum keeps the first).
+// Per link: the other label is one load per group, m_s a coalesced vector load, the table line the contiguous row for side 1 and
+// the column (stride pd1) for side 0; the next link's record, label and m_s are requested before the current line is added.
+template <int G>
+__device__ __forceinline__ double decode_min(double v) {
+#pragma unroll
+  for (int m = G / 2; m >= 1; m >>= 1) v = fmin(v, shfl_xor_f64(v, m));
+  return v;
+}
+template <int G>
+__device__ __forceinline__ int decode_min(int v) {
+#pragma unroll
+  for (int m = G / 2; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
+  return v;
+}
+template <int G, int CH>
+struct DecodeFetch {      // what is requested one link ahead
+  DecodeLink lk; int xv; double ms[CH]; bool use;
+  __device__ __forceinline__ void load(const DecodeLink* __restrict__ links, int k, int n, const double* __restrict__ dual,
+                                       const int32_t* __restrict__ primal, int level, int flags, int base, int g, int d0) {
+    use = false;
+    if (k >= n) return;
+    lk = links[k];
+    use = (flags & DECODE_ALL) || lk.level < level;
+    if (!use) return;
+    const int od = lk.side == 0 ? lk.pd1 : lk.pd0;                 // labels of the other unary
+    xv = min(max(primal[2 * (int64_t)lk.other], 0), od - 1);        // (a counted neighbour always holds a label: the clamp only keeps a stray array in bounds)
+    const double* m = dual + lk.peer_dual + (lk.side ? lk.pd0 : 0);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; ms[j] = x < d0 ? m[x] : 0.0; }
+  }
+};
+template <int G, int CH>
+__global__ void __launch_bounds__(256)
+decode_kernel(const DecodeRec* __restrict__ recs, const DecodeLink* __restrict__ links, const double* __restrict__ dual,
+              const double* __restrict__ cdata, int32_t* __restrict__ primal, int64_t first, int64_t count, int level, int flags, int tab32) {
+  constexpr int GPB = 256 / G, NONE = 0x7fffffff;
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
+  const bool live = idx < count;
+  DecodeRec r;
+  if (live) r = recs[first + idx]; else { r.dual_off = 0; r.d0 = 0; r.link_begin = 0; r.n_links = 0; r.factor = 0; }
+  const int d0 = r.d0, n = r.n_links;
+  const DecodeLink* lks = links + r.link_begin;
+  const double* th = dual + r.dual_off;
+  double best = LPMP_INF; int label = NONE;
+  for (int base = 0; base < d0; base += G * CH) {
+    double c[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; c[j] = x < d0 ? th[x] : LPMP_INF; }
+    DecodeFetch<G, CH> cur, nxt;
+    cur.load(lks, 0, n, dual, primal, level, flags, base, g, d0);
+    for (int k = 0; k < n; ++k) {
+      nxt.load(lks, k + 1, n, dual, primal, level, flags, base, g, d0);
+      if (cur.use) {
+        const DecodeLink& lk = cur.lk;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          const int x = base + j * G + g;
+          if (x < d0) {
+            const double t = lk.side == 0 ? pw_cost(cdata, lk.peer_const, lk.kind, lk.pd1, x, cur.xv, tab32)
+                                          : pw_cost(cdata, lk.peer_const, lk.kind, lk.pd1, cur.xv, x, tab32);
+            c[j] = c[j] + (t + cur.ms[j]);
+          }
+        }
+      }
+      cur = nxt;
+    }
+    // first minimiser of the chunk: per lane in ascending x, then value / index butterflies over the group
+    double bv = LPMP_INF; int bi = NONE;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; if (x < d0 && (bi == NONE || c[j] < bv)) { bv = c[j]; bi = x; } }
+    const double mn = decode_min<G>(bv);
+    const int cand = decode_min<G>((bi != NONE && bv == mn) ? bi : NONE);
+    if (label == NONE || mn < best) { best = mn; label = cand; }
+  }
+  if (live && g == 0 && label != NONE) primal[2 * (int64_t)r.factor] = label;
+}
+
 // LP::CheckPrimalConsistency (reference LP_MP.h:1067-1082): every message's two sides agree
 __global__ void __launch_bounds__(256)
 primal_check_kernel(const PrimalLink* __restrict__ links, int64_t n, const int32_t* __restrict__ primal, int* __restrict__ bad) {
@@ -3578,6 +3664,23 @@ void launch_primal_init(const PrimalInit* list, int64_t n, int32_t* primal, hipS
 }
 void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(primal_propagate_kernel, blocks256(n), dim3(256), 0, s, links, n, primal);
+}
+template <int G, int CH>
+static void launch_decode_as(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
+                             int64_t first, int64_t count, int level, int flags, int tab32, hipStream_t s) {
+  constexpr int GPB = 256 / G;
+  hipLaunchKernelGGL((decode_kernel<G, CH>), dim3((unsigned)((count + GPB - 1) / GPB)), dim3(256), 0, s, recs, links, dual, cdata, primal, first, count,
+                     level, flags, tab32);
+}
+void launch_decode(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
+                   int64_t first, int64_t count, int width, int level, int flags, int tab32, hipStream_t s) {
+  if (count <= 0) return;
+  if (width <= 4) launch_decode_as<4, 1>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
+  else if (width <= 8) launch_decode_as<8, 1>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
+  else if (width <= 16) launch_decode_as<16, 1>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
+  else if (width <= DECODE_GROUP_MAX) launch_decode_as<32, 1>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
+  else if (width <= 64) launch_decode_as<64, 1>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
+  else launch_decode_as<64, DECODE_CHUNK / 64>(recs, links, dual, cdata, primal, first, count, level, flags, tab32, s);
 }
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(primal_check_kernel, blocks256(n), dim3(256), 0, s, links, n, primal, bad);

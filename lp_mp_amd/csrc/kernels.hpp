@@ -84,6 +84,15 @@ struct SetConstRec { int64_t dst, dst2, src_row; int32_t len, factor, f32, two; 
 // ... and one piece of the pairwise message vectors lpmp_zero_pairwise_duals clears (device dual offset, at most ZERO_RUN_MAX doubles)
 struct ZeroRec { int64_t dual_off, len; };
 constexpr int64_t ZERO_RUN_MAX = 8192;
+// conditional rounding from the duals (decode_kernel; plan.hpp, DecodePlan): one decoded unary, and one of its links — the pairwise
+// factor's duals and constants (relative to the two base pointers, as everywhere), its kind and dims, the unary's side in it, the
+// unary on the other side and that unary's level (the launch of level l counts, in the initial sweep, the links with level < l)
+struct DecodeRec { int64_t dual_off; int32_t d0, link_begin, n_links, factor; };
+struct DecodeLink { int64_t peer_dual, peer_const; int32_t kind, pd0, pd1, side, other, level; };
+static_assert(sizeof(DecodeRec) == 24 && sizeof(DecodeLink) == 40, "decode record layout");
+constexpr int DECODE_GROUP_MAX = 32;     // up to this many labels a lane group of 4 / 8 / 16 / 32 lanes takes a unary, above it a wave
+constexpr int DECODE_CHUNK = 4 * 64;     // labels a wave holds in registers at a time (more: chunk by chunk, the links read again)
+constexpr int DECODE_ALL = 1;            // launch flag: every link counts (a refinement sweep); otherwise only those of a lower level
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
 // The bool ones return false when there is no kernel for the request (each says when, at its definition).
@@ -104,6 +113,10 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n
 void debug_set_level_trace(long long* p);
 void launch_primal_init(const PrimalInit* list, int64_t n, int32_t* primal, hipStream_t s);
 void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal, hipStream_t s);
+// one level of a decode sweep: records [first, first + count) of recs, all with at most `width` labels when width <= DECODE_GROUP_MAX
+// (a lane group of the next power of two >= max(width, 4) per unary), any label count otherwise (a wave per unary)
+void launch_decode(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
+                   int64_t first, int64_t count, int width, int level, int flags, int tab32, hipStream_t s);
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
 void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s);
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);

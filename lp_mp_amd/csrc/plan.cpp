@@ -1239,6 +1239,62 @@ std::string Plan::adaptive_obstacle() const {
   return "";
 }
 
+// ---- conditional rounding from the duals (plan.hpp, DecodePlan) ---------------------------------------------------------
+DecodePlan Plan::decode_plan(int direction) const {
+  DecodePlan dp;
+  if (direction < 0 || direction > 1) fail("decode plan: bad direction");
+  // the refusals: the lowest factor that breaks the rule of the supported models, and what it breaks
+  int64_t bad = nf; const char* what = "";
+  auto offend = [&](int64_t f, const char* w) { if (f < bad) { bad = f; what = w; } };
+  std::vector<int32_t> side_unary(2 * (size_t)nf, -1);       // [pairwise factor][side]: the unary of that side
+  std::vector<uint8_t> side_count(2 * (size_t)nf, 0);
+  for (int64_t m = 0; m < nm; ++m) {
+    const int32_t l = m_left[m], r = m_right[m];
+    if (mtypes[m_type[m]].kind != LPMP_M_UNARY_PAIRWISE) { offend(std::min(l, r), "has a message that is not a unary-pairwise one"); continue; }
+    const size_t slot = 2 * (size_t)r + mtypes[m_type[m]].param;
+    if (side_count[slot] < 2) ++side_count[slot];
+    side_unary[slot] = l;
+  }
+  for (int64_t f = 0; f < nf && f < bad; ++f) {
+    if (f_kind[f] == LPMP_F_VECTOR) continue;
+    const size_t s = 2 * (size_t)f;
+    if (side_count[s] == 0 || side_count[s + 1] == 0) offend(f, "is a pairwise factor with a side that has no unary");
+    else if (side_count[s] > 1 || side_count[s + 1] > 1) offend(f, "is a pairwise factor with two unaries on one side");
+    else if (side_unary[s] == side_unary[s + 1]) offend(f, "is a pairwise factor with one unary on both sides");
+  }
+  if (bad < nf) {
+    dp.bad_factor = (int32_t)bad;
+    dp.why = "decode: factor " + std::to_string(bad) + " " + what + " (DESIGN.md 8)";
+    return dp;
+  }
+  // pi, positions, edges in ascending message index
+  std::vector<int32_t> pos((size_t)nf, -1);
+  for (int32_t f : order[direction]) if (f_kind[f] == LPMP_F_VECTOR) { pos[(size_t)f] = (int32_t)dp.unaries.size(); dp.unaries.push_back(f); }
+  const size_t nu = dp.unaries.size();
+  dp.edge_off.assign(nu + 1, 0);
+  for (int64_t m = 0; m < nm; ++m) ++dp.edge_off[(size_t)pos[(size_t)m_left[m]] + 1];
+  std::partial_sum(dp.edge_off.begin(), dp.edge_off.end(), dp.edge_off.begin());
+  dp.edges.resize((size_t)nm);
+  {
+    std::vector<int64_t> cur(dp.edge_off.begin(), dp.edge_off.end() - 1);
+    for (int64_t m = 0; m < nm; ++m) {
+      const int32_t r = m_right[m], side = mtypes[m_type[m]].param;
+      dp.edges[(size_t)cur[(size_t)pos[(size_t)m_left[m]]]++] = {r, side, side_unary[2 * (size_t)r + (1 - side)]};
+    }
+  }
+  dp.level.assign(nu, 1);
+  for (size_t i = 0; i < nu; ++i) {
+    int32_t lv = 1;
+    for (int64_t k = dp.edge_off[i]; k < dp.edge_off[i + 1]; ++k) {
+      const size_t j = (size_t)pos[(size_t)dp.edges[(size_t)k].other];
+      if (j < i) lv = std::max(lv, dp.level[j] + 1);
+    }
+    dp.level[i] = lv;
+    dp.n_levels = std::max(dp.n_levels, lv);
+  }
+  return dp;
+}
+
 // ---- partition sweeps (reference LP_MP.h:1717-1843).  union_find.hxx:5-93: union by size, the first argument's root
 // wins ties, contiguous ids in increasing root index; partitions without updated factors are dropped (:1736-1745).
 // Intra-partition order: the reference sorts by position in forwardOrdering_ with a comparator that is false for every

@@ -259,6 +259,21 @@ struct Schedule {             // executable form of one (factor list, omega, mas
   std::vector<int32_t> diff_tab_off, diff_tab;
 };
 
+// Conditional rounding from the duals (lpmp_decode_primal): the structure of a decode in one direction.  Every vector
+// factor is a decoded unary; pi = Plan::order[direction] restricted to them.  level(u) = 1 + max level(v) over the neighbours v
+// earlier in pi (1 without any): two neighbours never share a level and a neighbour later in pi has a higher one, so the
+// unaries of one level are independent and level by level equals the sequential walk — for the initial sweep (neighbours of a
+// LOWER level count) and for a refinement sweep (all count: lower levels hold this sweep's label, higher ones the previous one's).
+struct DecodeEdge { int32_t p, side, other; };   // pairwise factor, the unary's side in it, the unary on the other side
+struct DecodePlan {
+  std::string why;                       // "" or why the model is refused (names the lowest offending factor); nothing else is filled then
+  int32_t bad_factor = -1;
+  std::vector<int32_t> unaries, level;   // in pi; level is 1-based
+  std::vector<int64_t> edge_off;         // CSR over `unaries`: the edges of a unary in ascending message index
+  std::vector<DecodeEdge> edges;
+  int32_t n_levels = 0;
+};
+
 struct Plan {
   // copied structure (no cost data)
   int32_t n_ftypes = 0, n_mtypes = 0, n_tables = 0;
@@ -349,6 +364,11 @@ struct Plan {
   void effective_send_weights(int32_t f, const double* omega, double* w) const;
   // why the adaptive send rule cannot run this model ("" if it can)
   std::string adaptive_obstacle() const;
+  // Structure of lpmp_decode_primal in `direction` (0 / 1).  Supported: every message is LPMP_M_UNARY_PAIRWISE and every
+  // pairwise factor has exactly one of them on each side, from two different unaries.  Otherwise DecodePlan::why says what the
+  // lowest offending factor is (a factor of a message of another kind; a pairwise factor with a side that has no unary or two,
+  // or with one unary on both sides)
+  DecodePlan decode_plan(int direction) const;
 };
 
 // The band of a difference vector D of n entries, by the BITS of the doubles (-0.0 and +0.0 differ): lo = the first index whose

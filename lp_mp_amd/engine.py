@@ -76,6 +76,7 @@ EXPORTS = [
     "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
     "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
     "lpmp_plan_peer_minima", "lpmp_get_peer_minima_launches",
+    "lpmp_decode_primal", "lpmp_plan_decode_info", "lpmp_plan_get_decode_levels",
 ]
 
 
@@ -199,6 +200,10 @@ def lib():
             L.lpmp_plan_set_shared_pool.argtypes = [C.c_void_p, C.c_void_p]
             L.lpmp_upload_shared_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             L.lpmp_set_constants.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+        if hasattr(L, "lpmp_decode_primal"):         # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_decode_primal.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            L.lpmp_plan_decode_info.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+            L.lpmp_plan_get_decode_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -447,6 +452,26 @@ def _suggest_order(self, seed: int = 0):
 
 
 Plan.suggest_order = _suggest_order
+
+
+def _decode_info(self, d: int) -> dict:
+    """structure of ``Engine.decode_primal`` in direction d (lpmp_plan_decode_info): decoded unaries, dependent levels (one launch
+    step each), unary-pairwise links.  EngineError (LPMP_ERR_UNSUPPORTED, naming the factor) for a model the decode refuses."""
+    v = [C.c_int64() for _ in range(3)]
+    _chk(self.L.lpmp_plan_decode_info(self.h, d, *[C.addressof(x) for x in v]))
+    return dict(zip(("n_unaries", "n_levels", "n_links"), [x.value for x in v]))
+
+
+def _decode_levels(self, d: int):
+    """(factors, levels): the decoded unaries in decode order and the 1-based level of each (lpmp_plan_get_decode_levels)"""
+    n = self.decode_info(d)["n_unaries"]
+    f, lv = np.empty(n, np.int32), np.empty(n, np.int32)
+    _chk(self.L.lpmp_plan_get_decode_levels(self.h, d, f.ctypes.data, lv.ctypes.data))
+    return f, lv
+
+
+Plan.decode_info = _decode_info
+Plan.decode_levels = _decode_levels
 
 
 def graph_colour_major_order(n: int, edge_i, edge_j, seed: int = 0):
@@ -737,6 +762,14 @@ class Engine:
 
     def compute_pass_and_primal(self, iteration: int):
         _chk(self.L.lpmp_compute_pass_and_primal(self.h, int(iteration)))
+
+    def decode_primal(self, direction: int = 0, refine: int = 0):
+        """labels from the current duals by conditional rounding (lpmp_decode_primal): every unary, in the order of
+        ``direction`` (0 forward, 1 backward), takes the first minimiser of its reparametrised cost given the labels of the
+        neighbours already visited; then ``refine`` sweeps in which every neighbour counts (ICM on the original energy).  Reads the
+        duals only; the labels land where ``download_primal`` / ``evaluate_primal`` read them.  Decode against the direction of
+        the last sweep: forward after ``compute_pass``."""
+        _chk(self.L.lpmp_decode_primal(self.h, int(direction), int(refine)))
 
     def check_primal_consistency(self) -> bool:
         out = C.c_int()

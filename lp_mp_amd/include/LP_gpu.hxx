@@ -421,6 +421,8 @@ class LP_gpu {
   void ComputeForwardPassAndPrimal(const INDEX iteration) { ready_mode(); check(lpmp_compute_forward_pass_and_primal(engine_, iteration)); duals_on_device_ = true; }
   void ComputeBackwardPassAndPrimal(const INDEX iteration) { ready_mode(); check(lpmp_compute_backward_pass_and_primal(engine_, iteration)); duals_on_device_ = true; }
   void ComputePassAndPrimal(const INDEX iteration) { ComputeForwardPassAndPrimal(iteration); ComputeBackwardPassAndPrimal(iteration); }
+  // labels from the current duals by conditional rounding (lpmp_decode_primal; no reference counterpart)
+  void DecodePrimal(const int direction = LPMP_FORWARD, const int refine_sweeps = 0) { ready(); check(lpmp_decode_primal(engine_, direction, refine_sweeps)); }
   bool CheckPrimalConsistency() { ready(); int ok = 0; check(lpmp_check_primal_consistency(engine_, &ok)); return ok != 0; }
   REAL EvaluatePrimal() { ready(); REAL c = 0; check(lpmp_evaluate_primal(engine_, &c)); return c; }
   // the factors' primal_ members in factor order: vector factor (label, 0), pairwise factor (x0, x1); unset = dimension

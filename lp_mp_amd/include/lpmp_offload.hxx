@@ -378,6 +378,8 @@ class offloaded : public LP_BASE {
   void ComputeForwardPassAndPrimal(const std::size_t iteration) { ready_mode(); check(lpmp_compute_forward_pass_and_primal(engine_, iteration)); device_ahead_ = true; }
   void ComputeBackwardPassAndPrimal(const std::size_t iteration) { ready_mode(); check(lpmp_compute_backward_pass_and_primal(engine_, iteration)); device_ahead_ = true; }
   void ComputePassAndPrimal(const std::size_t iteration) { ComputeForwardPassAndPrimal(iteration); ComputeBackwardPassAndPrimal(iteration); }
+  // labels from the current duals by conditional rounding (lpmp_decode_primal; no reference counterpart)
+  void DecodePrimal(const int direction = LPMP_FORWARD, const int refine_sweeps = 0) { sync_to_device(); check(lpmp_decode_primal(engine_, direction, refine_sweeps)); }
   double LowerBound() { sync_to_device(); double lb = 0; check(lpmp_lower_bound(engine_, &lb)); return lb; }
   double EvaluatePrimal() { sync_to_device(); double c = 0; check(lpmp_evaluate_primal(engine_, &c)); return c; }
   bool CheckPrimalConsistency() { sync_to_device(); int ok = 0; check(lpmp_check_primal_consistency(engine_, &ok)); return ok != 0; }

@@ -558,6 +558,14 @@ class LP:
     def EvaluatePrimal(self) -> float:
         return self._ready().evaluate_primal()
 
+    def decode_primal(self, direction: int = 0, refine: int = 0) -> float:
+        """labels from the current duals by conditional rounding (Engine.decode_primal; no reference counterpart):
+        reads the duals only, returns EvaluatePrimal(); primal() then returns the labels.  Decode against the direction of the
+        last sweep: forward (0) after ComputePass."""
+        e = self._ready()
+        e.decode_primal(direction, refine)
+        return e.evaluate_primal()
+
     def primal(self) -> np.ndarray:
         """[n_factors, 2] the factors' primal_ members in serialize_primal order: vector factor (label, 0), pairwise
         factor (x0, x1); an unset entry holds the dimension."""
