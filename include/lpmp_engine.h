@@ -332,6 +332,51 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps);
 int lpmp_plan_decode_info(lpmp_plan* p, int direction, int64_t* n_unaries, int64_t* n_levels, int64_t* n_links);
 int lpmp_plan_get_decode_levels(lpmp_plan* p, int direction, int32_t* factor_out, int32_t* level_out);
 
+/* ---- prepared read-outs: labels, unaries and beliefs of listed VECTOR factors into the caller's array ---------------
+ * The output twin of lpmp_set_vectors.  A read-out is a prepared list of VECTOR factors, like an lpmp_schedule_create id or an
+ * lpmp_halo: its record tables are uploaded once, a call plans and uploads nothing.
+ * lpmp_readout_create: `factors` is a host array of n VECTOR factor indices in the caller's order (a factor may be listed twice: reads
+ * are idempotent, both rows get the same content); factors == NULL: every VECTOR factor in ascending index, n is ignored.  n == 0
+ * makes an empty read-out whose calls are no-ops after their checks.  LPMP_ERR_STATE before lpmp_upload_model; LPMP_ERR_INVALID,
+ * naming the offender, for an index out of range or a non-VECTOR factor.  The object is structure: it stays valid across
+ * lpmp_upload_costs, lpmp_set_vectors, lpmp_upload_shared_pool, lpmp_set_constants, lpmp_zero_pairwise_duals, passes and decodes;
+ * after the next lpmp_upload_model every call on it returns LPMP_ERR_STATE (destroying it stays legal); lpmp_destroy does not free
+ * it.  lpmp_schedules_built does not move at create: the link tables behind the beliefs are built on the first lpmp_readout_beliefs
+ * of a read-out and counted once then.
+ *
+ * Common to the three calls: they settle passes that ran ahead first (the state read is that of the pass the caller is at); duals,
+ * tracked bounds, the primal array, weights, schedules, kernel timing and speculation depth do not move; nothing is written but dst.
+ * dst_mem == LPMP_MEM_DEVICE: asynchronous on the engine's stream like a pass, no host synchronisation (so an aborted persistent
+ * launch is reported by the next call that synchronises, as after lpmp_decode_primal, not here).  LPMP_MEM_HOST: through a
+ * buffer of the engine, the call returns after the copy.  Row i starts at dst + i * dst_stride; entries of a row beyond the
+ * factor's dim0 are not written; dst_stride < lpmp_readout_max_labels is LPMP_ERR_INVALID.
+ *   labels   dst[i] = the label slot of factor factors[i] exactly as lpmp_download_primal reports it (an unset entry holds the
+ *            dimension).  The primal array is allocated on first use, as in lpmp_decode_primal.  Every model — on one the rounding
+ *            code refuses (messages other than unary-pairwise) no call can set a label and every entry is the dimension.
+ *   vectors  row i = the current theta of the factor.  Every model, every layout.
+ *   beliefs  per-label min-marginal estimates.  A listed unary u with d0 labels gets
+ *              b[x] = theta_u[x]
+ *              for every message k of u IN THE ORDER OF u's MESSAGE LIST (lpmp_plan_get_msg_lists: the order in which a sweep
+ *              receives), p its pairwise factor and s the side of u in p:
+ *                  q[x] = min_y (cost_p(x, y) + m_o[y]) for s == 0, cost_p(y, x) for s == 1       (m_o: p's vector of the other side)
+ *                  b[x] = b[x] + (m_s[x] + q[x])
+ *            cost_p as in lpmp_decode_primal (ONE multiply for SHARED / DIFF, floats widened under the f32 table modes); all
+ *            arithmetic IEEE double in this order, no contraction.  +inf entries are allowed, NaN is outside the contract, which
+ *            zero a minimum over -0.0 and +0.0 returns is unspecified.  This is bit for bit the theta_u the receive phase of a sweep
+ *            would produce if u received over all its messages and sent nothing.  NOT the ascending-message-index order of the
+ *            decode.  Supported per listed factor: every message of u is LPMP_M_UNARY_PAIRWISE with u as its left factor (the peer
+ *            DENSE in any table precision, POTTS, SHARED or DIFF); a unary without messages gets theta.  Otherwise
+ *            LPMP_ERR_UNSUPPORTED naming the lowest such listed factor (checked at create and stored; labels and vectors stay
+ *            usable).  LPMP_ERR_STATE while the constants are unspecified (a refused lpmp_upload_costs). */
+typedef struct lpmp_readout lpmp_readout;
+int lpmp_readout_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_readout** out);
+void lpmp_readout_destroy(lpmp_readout* r);
+int64_t lpmp_readout_n(const lpmp_readout* r);          /* rows */
+int32_t lpmp_readout_max_labels(const lpmp_readout* r); /* longest listed vector */
+int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_mem);
+int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
+int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
+
 int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);

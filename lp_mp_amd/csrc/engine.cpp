@@ -6,10 +6,12 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <memory>
@@ -265,6 +267,7 @@ struct lpmp_engine {
   char* pinned = nullptr;         // this engine's block of device-written host words (from the pool)
   uint64_t primal_t = 0;          // primal_access_ of every factor a primal pass touches (they move together)
   bool have_primal = false;
+  bool primal_unset_only = false; // d_primal holds only the unset labels of a model the rounding code refuses (lpmp_readout_labels)
   bool primal_pass = false;       // the launches being issued belong to an ...AndPrimal pass
   // conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
   // their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
@@ -299,6 +302,10 @@ struct lpmp_engine {
   DevBuf<SetVecRec> d_setrecs; DevBuf<double> d_setsrc;   // records and (host sources) rows of lpmp_set_vectors, refilled in place
   DevBuf<SetConstRec> d_setcrecs;                         // records of lpmp_set_constants (its host rows share d_setsrc)
   DevBuf<ZeroRec> d_zero; int64_t n_zero = -1;            // pieces of the pairwise message vectors; -1: not built yet
+  // prepared read-outs (lpmp_readout_*): model_gen names the uploaded model (unique over all engines of the process; a read-out
+  // remembers the one it was made for), d_readout is where a call with a HOST destination lets the kernel write before the copy
+  uint64_t model_gen = 0;
+  DevBuf<double> d_readout;
   struct LbRun { int cls; int64_t first, count; };
   std::vector<LbRun> lb_runs;
   DevSchedule sched[2][LPMP_REPAM_COUNT];
@@ -389,7 +396,7 @@ struct lpmp_engine {
   void release_primal() {
     d_primal.reset(); d_pinit.reset(); d_plinks.reset(); d_pw_unary.reset(); d_pcost.reset(); d_pbad.reset();
     h_pbad = nullptr;
-    have_primal = false; primal_t = 0; n_pinit = n_plinks = n_pprop = 0;
+    have_primal = false; primal_unset_only = false; primal_t = 0; n_pinit = n_plinks = n_pprop = 0;
   }
   // the built-in schedules (everything but the caller's prepared iterator-range passes)
   void release_schedules() {
@@ -410,6 +417,7 @@ struct lpmp_engine {
     d_peerq.reset();
     schedules_built = 0; const_bad = false; tab_compact = false; sh_cells.clear();
     d_setrecs.reset(); d_setsrc.reset(); d_setcrecs.reset(); d_zero.reset(); n_zero = -1;
+    model_gen = 0; d_readout.reset();
     rows = packed_stale = rows_stale = false; n_rowrecs = 0;
     d_lbrecs.reset(); d_lb.reset(); d_part.reset();
     h_part = nullptr;
@@ -1705,6 +1713,7 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
     e->lb_all_stale = true;
     if (f32) { e->tab_prec = e->want_tab; e->tab_flag = SWEEP_TAB32; }
     e->plan = std::move(pl);
+    { static std::atomic<uint64_t> gen{0}; e->model_gen = ++gen; }   // (read-outs of an earlier model answer LPMP_ERR_STATE from here on)
     e->plan->p.force_generic = e->rtype == LPMP_RTYPE_ADAPTIVE;
     {   // mailbox budget of every schedule planned for this model: half of what the device has left now (LPMP_MAILBOX_MB overrides)
       size_t free_b = 0, total_b = 0;
@@ -2241,6 +2250,189 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
         launch_decode(dd.recs, dd.links, e->d_dual, e->d_const, e->d_primal, l.first, l.count, l.width, l.level, sweep ? DECODE_ALL : 0, e->tab_flag, e->stream);
     launch_primal_propagate(e->d_plinks, e->n_plinks, e->d_primal, e->stream);   // every message's pairwise slot := its unary's label
     HIP_CHECK(hipGetLastError());
+  });
+}
+
+// ---- prepared read-outs: labels, unaries and beliefs of listed VECTOR factors into the caller's array (include/lpmp_engine.h) -------
+// The output twin of lpmp_set_vectors, prepared like a schedule: the record list is uploaded at create, a call uploads nothing.
+struct lpmp_readout {
+  int device = 0;
+  uint64_t gen = 0;                     // lpmp_engine::model_gen of the model it was made for
+  int64_t n = 0;
+  int32_t max_labels = 0;
+  std::vector<int32_t> factors, d0;     // the list, and every row's label count (a host destination is filled row by row)
+  DevBuf<ReadoutRec> recs;              // in the caller's order: row i = record i
+  int32_t unsupported = -1;             // lowest listed factor with a message the beliefs do not take (-1: none)
+  std::string why;
+  // beliefs: the records again, sorted by label-count class, with their links in message-list order; built on the first call
+  struct Launch { int64_t first, count; int32_t width; };
+  bool have_links = false;
+  DevBuf<ReadoutRec> brecs; DevBuf<DecodeLink> links;
+  std::vector<Launch> launches;
+};
+
+static int readout_class(int32_t d0) { return d0 <= 4 ? 0 : d0 <= 8 ? 1 : d0 <= 16 ? 2 : d0 <= READOUT_GROUP_MAX ? 3 : d0 <= 64 ? 4 : 5; }
+static const int32_t READOUT_CLASS_WIDTH[6] = {4, 8, 16, READOUT_GROUP_MAX, 64, GEN_MAXD};
+
+// the link tables of the beliefs: a function of the structure, like a schedule, and counted as one
+static void ensure_readout_links(lpmp_engine* e, lpmp_readout* r) {
+  if (r->have_links) return;
+  r->brecs.reset(); r->links.reset(); r->launches.clear();
+  const Plan& p = e->plan->p;
+  int64_t start[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = 0; i < r->n; ++i) ++start[readout_class(r->d0[(size_t)i]) + 1];
+  for (int c = 0; c < 6; ++c) start[c + 1] += start[c];
+  std::vector<ReadoutRec> recs((size_t)r->n);
+  std::vector<DecodeLink> links;
+  std::vector<int64_t> begin_of((size_t)p.nf, -1);   // a factor listed twice shares its links
+  int64_t cur[6];
+  for (int c = 0; c < 6; ++c) cur[c] = start[c];
+  for (int64_t i = 0; i < r->n; ++i) {
+    const int32_t u = r->factors[(size_t)i];
+    const int64_t a = p.fm_off[(size_t)u], b = p.fm_off[(size_t)u + 1];
+    if (begin_of[(size_t)u] < 0) {
+      begin_of[(size_t)u] = (int64_t)links.size();
+      for (int64_t k = a; k < b; ++k) {   // the order of the message list: the order in which a sweep receives
+        const int32_t msg = p.fm[(size_t)k].msg, pw = p.m_right[(size_t)msg];
+        links.push_back({p.doff(pw), p.coff(pw), p.f_kind[pw], p.f_dim0[pw], p.f_dim1[pw], p.mtypes[(size_t)p.m_type[(size_t)msg]].param, 0, 0});
+      }
+      if (links.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error("lpmp_readout_beliefs: more than 2^31 links");
+    }
+    recs[(size_t)cur[readout_class(r->d0[(size_t)i])]++] = {p.f_doff[(size_t)u], i, r->d0[(size_t)i], u, (int32_t)begin_of[(size_t)u], (int32_t)(b - a)};
+  }
+  for (int c = 0; c < 6; ++c) if (start[c + 1] > start[c]) r->launches.push_back({start[c], start[c + 1] - start[c], READOUT_CLASS_WIDTH[c]});
+  if (r->n) { r->brecs.alloc((size_t)r->n); h2d(r->brecs, recs.data(), recs.size() * sizeof(ReadoutRec), e->stream); }
+  if (!links.empty()) { r->links.alloc(links.size()); h2d(r->links, links.data(), links.size() * sizeof(DecodeLink), e->stream); }
+  r->have_links = true;
+  ++e->schedules_built;
+}
+
+int lpmp_readout_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_readout** out) {
+  return guarded([&] {
+    if (!e || !e->plan) throw StateError("lpmp_readout_create: no model uploaded (a read-out lists factors of the uploaded model)");
+    if (!out || (factors && n < 0)) throw std::runtime_error("lpmp_readout_create: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    const Plan& p = e->plan->p;
+    auto r = std::make_unique<lpmp_readout>();
+    r->device = e->device; r->gen = e->model_gen;
+    if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) r->factors.push_back((int32_t)f); }
+    else {
+      r->factors.reserve((size_t)n);
+      for (int64_t i = 0; i < n; ++i) {
+        const int32_t f = factors[i];
+        if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_readout_create: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+        if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error("lpmp_readout_create: factor " + std::to_string(f) + " is not a VECTOR factor");
+        r->factors.push_back(f);
+      }
+    }
+    r->n = (int64_t)r->factors.size();
+    std::vector<ReadoutRec> recs((size_t)r->n);
+    r->d0.resize((size_t)r->n);
+    for (int64_t i = 0; i < r->n; ++i) {
+      const int32_t f = r->factors[(size_t)i], len = p.f_dim0[f];
+      r->d0[(size_t)i] = len;
+      r->max_labels = std::max(r->max_labels, len);
+      recs[(size_t)i] = {p.f_doff[f], i, len, f, 0, 0};
+      // beliefs: every message of the factor is a unary-pairwise one with the factor on its left (the unary) and a pairwise factor on its right
+      for (int64_t k = p.fm_off[(size_t)f]; k < p.fm_off[(size_t)f + 1]; ++k) {
+        const MsgEntry& me = p.fm[(size_t)k];
+        const bool ok = p.mtypes[(size_t)p.m_type[(size_t)me.msg]].kind == LPMP_M_UNARY_PAIRWISE && me.role == 0 && p.f_kind[p.m_right[(size_t)me.msg]] != LPMP_F_VECTOR;
+        if (!ok && (r->unsupported < 0 || f < r->unsupported)) r->unsupported = f;
+      }
+    }
+    if (r->unsupported >= 0)
+      r->why = "lpmp_readout_beliefs: factor " + std::to_string(r->unsupported) + " has a message that is not a unary-pairwise message with the factor as its unary (DESIGN.md 8)";
+    if (r->n) { r->recs.alloc((size_t)r->n); h2d(r->recs, recs.data(), recs.size() * sizeof(ReadoutRec), e->stream); }
+    *out = r.release();
+  });
+}
+void lpmp_readout_destroy(lpmp_readout* r) {
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  delete r;
+}
+int64_t lpmp_readout_n(const lpmp_readout* r) { return r ? r->n : 0; }
+int32_t lpmp_readout_max_labels(const lpmp_readout* r) { return r ? r->max_labels : 0; }
+
+// common entry of the three calls: the read-out belongs to the uploaded model, the arguments are usable, passes that ran ahead
+// are settled (the state read is that of the pass the caller is at)
+static void readout_enter(lpmp_engine* e, lpmp_readout* r, const void* dst, int dst_mem, const int64_t* dst_stride, const char* who) {
+  if (!e || !r) throw std::runtime_error(std::string(who) + ": null argument");
+  if (!e->plan || r->gen != e->model_gen) throw StateError(std::string(who) + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
+  if (dst_mem != LPMP_MEM_HOST && dst_mem != LPMP_MEM_DEVICE) throw std::runtime_error(std::string(who) + ": dst_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
+  if (r->n > 0 && !dst) throw std::runtime_error(std::string(who) + ": null destination");
+  if (dst_stride && *dst_stride < r->max_labels)
+    throw std::runtime_error(std::string(who) + ": dst_stride " + std::to_string(*dst_stride) + " is smaller than the " + std::to_string(r->max_labels) + " entries of the longest listed vector");
+  HIP_CHECK(hipSetDevice(e->device));
+  settle(e);
+  // a DEVICE destination never waits for the stream, as lpmp_decode_primal does not: an aborted chain run is reported by the next
+  // call that synchronises anyway.  A HOST destination ends in a synchronising copy and reports it here
+  if (dst_mem == LPMP_MEM_HOST) check_chain(e);
+}
+// rows of doubles: straight into a device destination, or into the engine's buffer (rows max_labels apart) and from there, row by
+// row, into the entries of the host destination that belong to a factor
+static void readout_rows(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem, const std::function<void(double*, int64_t)>& launch) {
+  if (dst_mem == LPMP_MEM_DEVICE) { launch(dst, dst_stride); HIP_CHECK(hipGetLastError()); return; }
+  const size_t total = (size_t)r->n * (size_t)r->max_labels;
+  if (total == 0) return;
+  e->d_readout.grow(total);
+  launch(e->d_readout.get(), (int64_t)r->max_labels);
+  HIP_CHECK(hipGetLastError());
+  // (whole rows, one staging chunk at a time: no second buffer of the size of the read-out on the host)
+  const int64_t L = r->max_labels, per = std::max<int64_t>(1, (int64_t)(STAGE_CHUNK / sizeof(double)) / L);
+  std::vector<double> rows((size_t)(std::min(per, r->n) * L));
+  for (int64_t first = 0; first < r->n; first += per) {
+    const int64_t cnt = std::min(per, r->n - first);
+    d2h(rows.data(), e->d_readout.get() + first * L, (size_t)(cnt * L) * sizeof(double), e->stream);
+    for (int64_t i = 0; i < cnt; ++i)
+      std::copy(rows.begin() + i * L, rows.begin() + i * L + r->d0[(size_t)(first + i)], dst + (first + i) * dst_stride);
+  }
+}
+
+int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_mem) {
+  return guarded([&] {
+    readout_enter(e, r, dst, dst_mem, nullptr, "lpmp_readout_labels");
+    if (r->n == 0) return;
+    if (!e->have_primal && !e->primal_unset_only) {
+      try { ensure_primal(e); }
+      catch (const UnsupportedError&) {
+        // a model the rounding code does not take (messages other than unary-pairwise): no call can set a label, every slot is
+        // unset.  The array is made once and remembered until release_primal (the model goes, or another call tries the rounding tables)
+        e->d_primal.alloc(std::max<size_t>(1, 2 * (size_t)e->plan->p.nf));
+        upload_unset_primal(e);
+        e->primal_unset_only = true;
+      }
+    }
+    if (dst_mem == LPMP_MEM_DEVICE) { launch_readout_labels(r->recs, r->n, e->d_primal, dst, e->stream); HIP_CHECK(hipGetLastError()); return; }
+    e->d_readout.grow(((size_t)r->n + 1) / 2);
+    int32_t* stage = reinterpret_cast<int32_t*>(e->d_readout.get());
+    launch_readout_labels(r->recs, r->n, e->d_primal, stage, e->stream);
+    HIP_CHECK(hipGetLastError());
+    d2h(dst, stage, (size_t)r->n * sizeof(int32_t), e->stream);
+  });
+}
+int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem) {
+  return guarded([&] {
+    readout_enter(e, r, dst, dst_mem, &dst_stride, "lpmp_readout_vectors");
+    if (r->n == 0) return;
+    // (vector factors live in the packed array under every layout: nothing of the rows is read)
+    readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
+      launch_readout_vectors(r->recs, r->n, r->max_labels, e->d_dual, d, stride, e->stream);
+    });
+  });
+}
+int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem) {
+  return guarded([&] {
+    readout_enter(e, r, dst, dst_mem, &dst_stride, "lpmp_readout_beliefs");
+    if (r->unsupported >= 0) throw UnsupportedError(r->why);
+    if (r->n == 0) return;
+    require_consts(e);
+    ensure_readout_links(e, r);
+    rows_refresh(e);           // (reads the rows; writes no dual)
+    readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
+      for (const auto& l : r->launches)
+        launch_readout_beliefs(r->brecs, r->links, e->d_dual, e->d_const, d, stride, l.first, l.count, l.width, e->tab_flag, e->stream);
+    });
   });
 }
 

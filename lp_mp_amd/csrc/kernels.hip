@@ -3827,4 +3827,145 @@ void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStrea
   if (n > 0) hipLaunchKernelGGL(zero_pairwise_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, dual);
 }
 
+// ---- prepared read-outs (engine.cpp, lpmp_readout_*) ----------------------------------------------------------
+// Gathers over a device record list into the caller's array: no LDS, no atomics, plain vector stores, 64-bit offsets.  Nothing but
+// dst is written, and of a row only the entries below the factor's label count.
+// labels: one thread per listed factor; dst[i] = its label slot of the primal array
+__global__ void __launch_bounds__(256)
+readout_labels_kernel(const ReadoutRec* __restrict__ recs, int64_t n, const int32_t* __restrict__ primal, int32_t* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const ReadoutRec r = recs[i];
+  dst[r.row] = primal[2 * (int64_t)r.factor];
+}
+// vectors: G lanes per listed factor stride over its theta; consecutive lanes write consecutive doubles of the row
+template <int G>
+__global__ void __launch_bounds__(256)
+readout_vectors_kernel(const ReadoutRec* __restrict__ recs, int64_t n, const double* __restrict__ dual, double* __restrict__ dst, int64_t dst_stride) {
+  constexpr int GPB = 256 / G;
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int64_t i = (int64_t)blockIdx.x * GPB + grp;
+  if (i >= n) return;
+  const ReadoutRec r = recs[i];
+  const double* th = dual + r.dual_off;
+  double* row = dst + r.row * dst_stride;
+  for (int x = g; x < r.d0; x += G) row[x] = th[x];
+}
+// beliefs: per-label min-marginal estimates of a unary u,
+//   b[x] = theta_u[x];  for every link k of u in the order of its message list:  b[x] = b[x] + (m_s[x] + q[x]),
+//   q[x] = min_y (cost_p(x, y) + m_o[y]) when u is on side 0 of pairwise factor p, cost_p(y, x) on side 1
+// — what the receive phase of a sweep leaves in theta_u when u receives over all its messages and sends nothing.  G lanes per
+// unary, a lane holds CH entries of b (x = base + j * G + g); a unary of more than G * CH labels is done chunk by chunk, the links
+// read again.  Per link the table is read line by line, every line contiguous over the lanes:
+//   side 1 (u indexes the columns): the lanes hold x and walk the rows y; m_o[y] is one load per group and row
+//   side 0 (u indexes the rows):    the lanes hold y (strided when the peer has more labels than the group lanes), one row x per step,
+//                                   a group minimum per row that the lane holding x keeps
+// The next link's record, its m_s and the first stride of its m_o are requested before the current table is reduced.
+template <int G, int CH>
+struct BeliefFetch {
+  DecodeLink lk; double ms[CH]; double mo0; bool have;
+  __device__ __forceinline__ void load(const DecodeLink* __restrict__ links, int k, int n, const double* __restrict__ dual, int base, int g, int d0) {
+    have = k < n;
+    if (!have) return;
+    lk = links[k];
+    const double* m = dual + lk.peer_dual;
+    const double* own = m + (lk.side ? lk.pd0 : 0);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; ms[j] = x < d0 ? own[x] : 0.0; }
+    mo0 = (lk.side == 0 && g < lk.pd1) ? m[lk.pd0 + g] : LPMP_INF;
+  }
+};
+template <int G, int CH>
+__global__ void __launch_bounds__(256)
+readout_beliefs_kernel(const ReadoutRec* __restrict__ recs, const DecodeLink* __restrict__ links, const double* __restrict__ dual,
+                       const double* __restrict__ cdata, double* __restrict__ dst, int64_t dst_stride, int64_t first, int64_t count, int tab32) {
+  constexpr int GPB = 256 / G;
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
+  const bool live = idx < count;
+  ReadoutRec r;
+  if (live) r = recs[first + idx]; else { r.dual_off = 0; r.row = 0; r.d0 = 0; r.factor = 0; r.link_begin = 0; r.n_links = 0; }
+  const int d0 = r.d0, n = r.n_links;
+  const DecodeLink* lks = links + r.link_begin;
+  const double* th = dual + r.dual_off;
+  double* row = dst + r.row * dst_stride;
+  for (int base = 0; base < d0; base += G * CH) {
+    double b[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; b[j] = x < d0 ? th[x] : 0.0; }
+    BeliefFetch<G, CH> cur, nxt;
+    cur.load(lks, 0, n, dual, base, g, d0);
+    for (int k = 0; k < n; ++k) {
+      nxt.load(lks, k + 1, n, dual, base, g, d0);
+      const DecodeLink& lk = cur.lk;
+      const double* m = dual + lk.peer_dual;
+      double q[CH];
+#pragma unroll
+      for (int j = 0; j < CH; ++j) q[j] = LPMP_INF;
+      if (lk.side) {
+        for (int y = 0; y < lk.pd0; ++y) {
+          const double mo = m[y];
+#pragma unroll
+          for (int j = 0; j < CH; ++j) {
+            const int x = base + j * G + g;
+            if (x < d0) q[j] = fmin(q[j], pw_cost(cdata, lk.peer_const, lk.kind, lk.pd1, y, x, tab32) + mo);
+          }
+        }
+      } else {
+        const int od = lk.pd1;
+        const double* mo = m + lk.pd0;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          const int end = min(G, d0 - (base + j * G));        // rows of this stride (the same for every lane of the group)
+          for (int xx = 0; xx < end; ++xx) {
+            const int x = base + j * G + xx;
+            double v = LPMP_INF;
+            if (g < od) v = pw_cost(cdata, lk.peer_const, lk.kind, od, x, g, tab32) + cur.mo0;
+            for (int y = g + G; y < od; y += G) v = fmin(v, pw_cost(cdata, lk.peer_const, lk.kind, od, x, y, tab32) + mo[y]);
+            v = vec_min<G, G>(v);
+            if (g == xx) q[j] = v;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < CH; ++j) b[j] = b[j] + (cur.ms[j] + q[j]);
+      cur = nxt;
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { const int x = base + j * G + g; if (x < d0) row[x] = b[j]; }
+  }
+}
+void launch_readout_labels(const ReadoutRec* recs, int64_t n, const int32_t* primal, int32_t* dst, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(readout_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, primal, dst);
+}
+template <int G>
+static void launch_readout_vectors_as(const ReadoutRec* recs, int64_t n, const double* dual, double* dst, int64_t dst_stride, hipStream_t s) {
+  constexpr int GPB = 256 / G;
+  hipLaunchKernelGGL((readout_vectors_kernel<G>), dim3((unsigned)((n + GPB - 1) / GPB)), dim3(256), 0, s, recs, n, dual, dst, dst_stride);
+}
+void launch_readout_vectors(const ReadoutRec* recs, int64_t n, int width, const double* dual, double* dst, int64_t dst_stride, hipStream_t s) {
+  if (n <= 0) return;
+  if (width <= 8) launch_readout_vectors_as<8>(recs, n, dual, dst, dst_stride, s);
+  else if (width <= 16) launch_readout_vectors_as<16>(recs, n, dual, dst, dst_stride, s);
+  else if (width <= 32) launch_readout_vectors_as<32>(recs, n, dual, dst, dst_stride, s);
+  else launch_readout_vectors_as<64>(recs, n, dual, dst, dst_stride, s);
+}
+template <int G, int CH>
+static void launch_readout_beliefs_as(const ReadoutRec* recs, const DecodeLink* links, const double* dual, const double* cdata, double* dst,
+                                      int64_t dst_stride, int64_t first, int64_t count, int tab32, hipStream_t s) {
+  constexpr int GPB = 256 / G;
+  hipLaunchKernelGGL((readout_beliefs_kernel<G, CH>), dim3((unsigned)((count + GPB - 1) / GPB)), dim3(256), 0, s, recs, links, dual, cdata, dst,
+                     dst_stride, first, count, tab32);
+}
+void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, const double* dual, const double* cdata, double* dst,
+                            int64_t dst_stride, int64_t first, int64_t count, int width, int tab32, hipStream_t s) {
+  if (count <= 0) return;
+  if (width <= 4) launch_readout_beliefs_as<4, 1>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+  else if (width <= 8) launch_readout_beliefs_as<8, 1>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+  else if (width <= 16) launch_readout_beliefs_as<16, 1>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+  else if (width <= READOUT_GROUP_MAX) launch_readout_beliefs_as<32, 1>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+  else if (width <= 64) launch_readout_beliefs_as<64, 1>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+  else launch_readout_beliefs_as<64, READOUT_CHUNK / 64>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
+}
+
 }  // namespace lpmp

@@ -93,6 +93,13 @@ static_assert(sizeof(DecodeRec) == 24 && sizeof(DecodeLink) == 40, "decode recor
 constexpr int DECODE_GROUP_MAX = 32;     // up to this many labels a lane group of 4 / 8 / 16 / 32 lanes takes a unary, above it a wave
 constexpr int DECODE_CHUNK = 4 * 64;     // labels a wave holds in registers at a time (more: chunk by chunk, the links read again)
 constexpr int DECODE_ALL = 1;            // launch flag: every link counts (a refinement sweep); otherwise only those of a lower level
+// prepared read-outs (lpmp_readout_*): one listed vector factor — its place in the packed duals (vector factors live
+// there under every layout), the row of the destination it fills, its label count; for the beliefs its links (DecodeLink records
+// whose `other` / `level` are unused) in the order of its MESSAGE LIST, the order in which a sweep receives
+struct ReadoutRec { int64_t dual_off, row; int32_t d0, factor, link_begin, n_links; };
+static_assert(sizeof(ReadoutRec) == 32, "read-out record layout");
+constexpr int READOUT_GROUP_MAX = DECODE_GROUP_MAX;   // beliefs: a lane group per unary up to this many labels, a wave above (the decode's split)
+constexpr int READOUT_CHUNK = DECODE_CHUNK;           // ... and the labels a wave holds in registers at a time
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
 // The bool ones return false when there is no kernel for the request (each says when, at its definition).
@@ -117,6 +124,13 @@ void launch_primal_propagate(const PrimalLink* links, int64_t n, int32_t* primal
 // (a lane group of the next power of two >= max(width, 4) per unary), any label count otherwise (a wave per unary)
 void launch_decode(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
                    int64_t first, int64_t count, int width, int level, int flags, int tab32, hipStream_t s);
+// prepared read-outs: dst[row] = label slot of the record's factor; row `row` of dst (rows dst_stride doubles apart) = its theta
+// (width: the longest listed vector, which picks the lane group); ... = its belief, for records [first, first + count) that all have
+// at most `width` labels when width <= READOUT_GROUP_MAX.  Entries of a row beyond the factor's label count are not written
+void launch_readout_labels(const ReadoutRec* recs, int64_t n, const int32_t* primal, int32_t* dst, hipStream_t s);
+void launch_readout_vectors(const ReadoutRec* recs, int64_t n, int width, const double* dual, double* dst, int64_t dst_stride, hipStream_t s);
+void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, const double* dual, const double* cdata, double* dst,
+                            int64_t dst_stride, int64_t first, int64_t count, int width, int tab32, hipStream_t s);
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
 void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s);
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);

@@ -77,6 +77,8 @@ EXPORTS = [
     "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
     "lpmp_plan_peer_minima", "lpmp_get_peer_minima_launches",
     "lpmp_decode_primal", "lpmp_plan_decode_info", "lpmp_plan_get_decode_levels",
+    "lpmp_readout_create", "lpmp_readout_destroy", "lpmp_readout_n", "lpmp_readout_max_labels",
+    "lpmp_readout_labels", "lpmp_readout_vectors", "lpmp_readout_beliefs",
 ]
 
 
@@ -204,6 +206,17 @@ def lib():
             L.lpmp_decode_primal.argtypes = [C.c_void_p, C.c_int, C.c_int]
             L.lpmp_plan_decode_info.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
             L.lpmp_plan_get_decode_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lpmp_readout_create"):        # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_readout_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+            L.lpmp_readout_destroy.restype = None
+            L.lpmp_readout_destroy.argtypes = [C.c_void_p]
+            L.lpmp_readout_n.restype = C.c_int64
+            L.lpmp_readout_n.argtypes = [C.c_void_p]
+            L.lpmp_readout_max_labels.restype = C.c_int32
+            L.lpmp_readout_max_labels.argtypes = [C.c_void_p]
+            L.lpmp_readout_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.lpmp_readout_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+            L.lpmp_readout_beliefs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -771,6 +784,11 @@ class Engine:
         the last sweep: forward after ``compute_pass``."""
         _chk(self.L.lpmp_decode_primal(self.h, int(direction), int(refine)))
 
+    def readout(self, factors=None) -> "Readout":
+        """a prepared read-out of the listed VECTOR factors (lpmp_readout_create; None: every VECTOR factor in ascending index):
+        labels, unaries and beliefs into device or host arrays without planning or uploading anything per call"""
+        return Readout(self, factors)
+
     def check_primal_consistency(self) -> bool:
         out = C.c_int()
         _chk(self.L.lpmp_check_primal_consistency(self.h, C.addressof(out)))
@@ -910,6 +928,62 @@ class Engine:
                     if nb.value == arrs[0][c]:
                         out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_band_kernel"
         return out
+
+
+class Readout:
+    """A prepared list of VECTOR factors of the engine's uploaded model (include/lpmp_engine.h, lpmp_readout_*).  Structure: it stays
+    valid across new costs, passes and decodes; after the engine's next ``upload`` every call raises (LPMP_ERR_STATE) and ``close``
+    still works.  ``dst_dev``: a raw device pointer — the call is asynchronous on the engine's stream and returns None."""
+
+    def __init__(self, engine: Engine, factors=None):
+        self.e = engine
+        self.L = engine.L
+        h = C.c_void_p()
+        if factors is None:
+            _chk(self.L.lpmp_readout_create(engine.h, 0, None, C.addressof(h)))
+        else:
+            factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
+            keep = factors if factors.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
+            _chk(self.L.lpmp_readout_create(engine.h, int(factors.shape[0]), keep.ctypes.data, C.addressof(h)))
+        self.h = h.value
+        self.n = int(self.L.lpmp_readout_n(self.h))
+        self.max_labels = int(self.L.lpmp_readout_max_labels(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lpmp_readout_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def labels(self, dst_dev: Optional[int] = None):
+        """[n] int32: the label slot of every listed factor as ``Engine.download_primal`` reports it (unset: the label count)"""
+        if dst_dev is not None:
+            _chk(self.L.lpmp_readout_labels(self.e.h, self.h, C.c_void_p(dst_dev), MEM_DEVICE))
+            return None
+        out = np.zeros(max(self.n, 1), np.int32)
+        _chk(self.L.lpmp_readout_labels(self.e.h, self.h, out.ctypes.data, MEM_HOST))
+        return out[:self.n]
+
+    def _rows(self, fn, dst_dev, stride):
+        stride = self.max_labels if stride is None else int(stride)
+        if dst_dev is not None:
+            _chk(fn(self.e.h, self.h, C.c_void_p(dst_dev), stride, MEM_DEVICE))
+            return None
+        out = np.full(max(self.n * max(stride, 0), 1), np.nan)
+        _chk(fn(self.e.h, self.h, out.ctypes.data, stride, MEM_HOST))
+        return out[:self.n * stride].reshape(self.n, stride)
+
+    def vectors(self, dst_dev: Optional[int] = None, stride: Optional[int] = None):
+        """[n, stride] float64: row i is the current theta of listed factor i; entries beyond its label count are NaN (a device
+        destination keeps what it held there)"""
+        return self._rows(self.L.lpmp_readout_vectors, dst_dev, stride)
+
+    def beliefs(self, dst_dev: Optional[int] = None, stride: Optional[int] = None):
+        """[n, stride] float64: row i is the belief of listed factor i — theta plus what every adjacent pairwise factor would send it,
+        in the order of its message list (include/lpmp_engine.h has the rule); padding as in ``vectors``"""
+        return self._rows(self.L.lpmp_readout_beliefs, dst_dev, stride)
 
 
 def device_identity(device: int = 0) -> str:

@@ -566,6 +566,12 @@ class LP:
         e.decode_primal(direction, refine)
         return e.evaluate_primal()
 
+    def readout(self, factor_handles=None):
+        """a prepared read-out (Engine.readout; no reference counterpart) of the listed vector factors — what
+        ``add_factor`` returned for them, None: all of them — with ``labels()``, ``vectors()`` and ``beliefs()`` into host or device
+        arrays.  It belongs to the uploaded model: a structural change of the LP (the next upload) ends it."""
+        return self._ready().readout(factor_handles)
+
     def primal(self) -> np.ndarray:
         """[n_factors, 2] the factors' primal_ members in serialize_primal order: vector factor (label, 0), pairwise
         factor (x0, x1); an unset entry holds the dimension."""
