@@ -360,6 +360,7 @@ struct lpmp_engine {
   // steps — never across calls (every call starts with H and W), so no upload invalidates it.  Allocated with the first eligible
   // joined launch, freed with the model; not part of the chain cache.  LPMP_NO_PEER_MINIMA=1: every launch in the old form
   bool use_peer_minima = true;
+  int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
   DevBuf<double> d_peerq;
   bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
@@ -1026,6 +1027,11 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   ++e->schedules_built;
   rc.peer_minima = pq;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
+  if (verbose && pq) {
+    int per_cu = 0;
+    const unsigned grid = chain_pq_grid(e->pq_lds, (int)std::min<int64_t>(N, INT32_MAX), &per_cu);
+    std::fprintf(stderr, "lpmp:   peer minima launch (LPMP_PQ_LDS=%d): %d resident workgroups per CU, grid %u\n", e->pq_lds, per_cu, grid);
+  }
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
                  periodic ? (ord.tiles ? " (periodic template, tiled order)" : " (periodic template)") : ord.tiles ? " (tiled order)" : "", (long long)N, ord.bands, jt.lag, depth,
@@ -1056,7 +1062,7 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
   if (rc->peer_minima && !e->d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
-  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream, rc->peer_minima ? e->d_peerq.get() : nullptr)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream, rc->peer_minima ? e->d_peerq.get() : nullptr, e->pq_lds)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1413,6 +1419,7 @@ int lpmp_create(int device, lpmp_engine** out) {
     e->use_blocked_passes = !(nb && nb[0] == '1');
     const char* np = std::getenv("LPMP_NO_PEER_MINIMA");
     e->use_peer_minima = !(np && np[0] == '1');
+    if (const char* v = std::getenv("LPMP_PQ_LDS")) e->pq_lds = v[0] == '0' ? 0 : 1;
     if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
     if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }
     if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_opts.depth = std::max(1, std::atoi(v)); e->rot_opts.depth_set = true; }

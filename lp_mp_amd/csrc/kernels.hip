@@ -1372,6 +1372,11 @@ chain_dense_pk_f32_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches
 // are still in registers when theta is final, those of the first two are requested again behind the sends (a second read, mostly
 // on-die).  4: every table stays in registers from its receive to its publish, 227 VGPRs, two waves per SIMD — measured slower
 // than the old form on the headline grid (1.54 against 1.61-1.65 G message updates per second; KM = 2: 1.78-1.79; EXPERIMENTS.md N).
+// S: tables a publishing record PARKS in LDS between its receive and its publish (KM = 2 only).  0: the form above.  1 (shipped):
+// a record with more than two receives writes table 0 to its wave's own 8 KiB of LDS before the second pair takes the registers and
+// reads it back for the publish; of the first pair only table 1 is requested again, and not even that when the second pair has one
+// member (its slot was never overwritten): 1.25 instead of 1.5 table requests per table and pass, the same registers, three waves
+// per SIMD, 38 KiB of LDS per workgroup (EXPERIMENTS.md O; non-temporal last requests measured there as well: no difference).
 constexpr int PQ_KM = 2;
 constexpr int PQ_OPS = PEER_MINIMA_MAX_OPS;                        // receives and sends of a record of such a launch (order.cpp checks)
 
@@ -1496,12 +1501,19 @@ __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ pac
   }
 }
 
+// a wave's parking area: [NL][64] double2_t in the registers' lane layout (16 B per lane, consecutive lanes consecutive); S = 0: none
+template <int S, int NL>
+__device__ __forceinline__ double2_t* pq_park_area(int grp) {
+  if constexpr (S > 0) { __shared__ double2_t lds_park[256 / 64][NL * 64]; return lds_park[grp]; }
+  else return nullptr;
+}
 // W: the receives and sends of dense_pk_body in a chain (every receive is deferred into its send: order.cpp), then the publish
-template <int L, int KM>
+template <int L, int KM, int S>
 __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
                                                       double* __restrict__ lb, double* __restrict__ peerq, int64_t count, int stride, int64_t block,
                                                       const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
   static_assert(L == 32 && (KM == 2 || KM == 4), "the exact 32-label class");
+  static_assert(S == 0 || (S == 1 && KM == 2), "one parked table beside two in registers");
   constexpr int G = 64, GPB = 256 / G, A = ACC_COH;
   constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL;
   __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
@@ -1512,14 +1524,18 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
   PqRec r;
   pq_load_rec<L>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
   double2_t t[KM][NL];
-  auto load_tabs = [&](const int c) {
+  double2_t* const park = pq_park_area<S, NL>(grp);
+  auto load_tab = [&](const int j, const int q) {   // table q into slot j
+    const double* T = cdata + uni64<G>(r.lop[q].peer_const);
+#pragma unroll
+    for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<false>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
+  };
+  // keep: a slot without a table in this chunk keeps what it holds (S = 1: table 1 stays for the publish)
+  auto load_tabs = [&](const int c, const bool keep) {
 #pragma unroll
     for (int j = 0; j < KM; ++j) {
-      if (c + j < r.n_recv) {
-        const double* T = cdata + uni64<G>(r.lop[c + j].peer_const);
-#pragma unroll
-        for (int i = 0; i < NL; ++i) t[j][i] = ld_stream<false>(reinterpret_cast<const double2_t*>(T + (int64_t)i * 2 * G + 2 * g));
-      } else {
+      if (c + j < r.n_recv) load_tab(j, c + j);
+      else if (!keep) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
       }
@@ -1551,7 +1567,7 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
       if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
     }
   };
-  load_tabs(0);                                  // constants first, then the predecessors, then the duals
+  load_tabs(0, false);                           // constants first, then the predecessors, then the duals
   const bool aborted = !chain_wait(*ca, ticket);
   double theta = r.vl ? ld_dual<A>(r.own_g + g) : 0.0;
   double msv[PQ_OPS], mov[PQ_OPS], mnew[PQ_OPS];
@@ -1570,7 +1586,13 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
 #pragma unroll
   for (int c = 0; c < PQ_OPS; c += KM) {
     if (c >= r.n_recv) break;
-    if (c > 0) load_tabs(c);
+    if (c > 0) {
+      if constexpr (S == 1) {                    // every lane reads back only what it wrote itself: no wave_sync, no barrier
+#pragma unroll
+        for (int i = 0; i < NL; ++i) park[i * G + g] = t[0][i];
+      }
+      load_tabs(c, S == 1);
+    }
 #pragma unroll
     for (int j = 0; j < KM; ++j) {
       if (c + j >= r.n_recv) break;
@@ -1629,8 +1651,16 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
     }
   };
   if constexpr (KM == 4) publish(0);
-  else {
-    if (r.n_recv > KM) { publish(KM); load_tabs(0); }
+  else if constexpr (S == 1) {
+    if (r.n_recv > KM) {
+      publish(KM);
+      if (r.n_recv == 2 * KM) load_tab(1, 1);    // the one table requested twice; with three receives slot 1 still holds it
+#pragma unroll
+      for (int i = 0; i < NL; ++i) t[0][i] = park[i * G + g];
+    }
+    publish(0);
+  } else {
+    if (r.n_recv > KM) { publish(KM); load_tabs(0, false); }
     publish(0);
   }
   const double ob = vec_min<G, L>(r.vl ? theta : LPMP_INF);
@@ -1664,14 +1694,14 @@ __device__ __forceinline__ void chain_loop_roles(const ChainArgs& ca, const Chai
     __syncthreads();
   }
 }
-template <int L, int KM>
+template <int L, int KM, int S = 0>
 __global__ void __launch_bounds__(256, KM == 2 ? 3 : 2)
 chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
                       double* __restrict__ lb, double* __restrict__ peerq) {
   chain_loop_roles(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int role) {
     const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
     double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
-    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish_body<L, KM>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish_body<L, KM, S>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
     else dense_pq_consume_body<L>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
   });
 }
@@ -3580,13 +3610,18 @@ bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, cons
 // chain executor: one persistent launch for a deep single-class schedule; grid = what is resident at once (more
 // workgroups would only queue behind the running ones).  Returns false for a class without a chain kernel.
 template <class K>
-static unsigned chain_grid(K kernel, int n_tickets, int threads = 256) {
+static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_cu_out = nullptr) {
   int di = 0;
   const int n_cu = device_cu_count(di);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+  if (per_cu_out) *per_cu_out = per_cu;
   const long cap = (long)n_cu * per_cu;
   return (unsigned)(n_tickets < cap ? n_tickets : cap);
+}
+// what launch_chain will launch for a peer-minima chain of n_tickets (LPMP_ROT_VERBOSE, engine.cpp)
+unsigned chain_pq_grid(int pq_lds, int n_tickets, int* per_cu) {
+  return pq_lds == 0 ? chain_grid(chain_dense_pq_kernel<32, PQ_KM>, n_tickets, 256, per_cu) : chain_grid(chain_dense_pq_kernel<32, PQ_KM, 1>, n_tickets, 256, per_cu);
 }
 void debug_set_level_trace(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_level_trace), &p, sizeof(p)); }
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launches, double* dual, const double* cdata,
@@ -3597,13 +3632,12 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
     if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
-    auto k = chain_dense_pq_kernel<32, PQ_KM>;
-    hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq);
-    return true;
+    auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
+    return pq_lds == 0 ? go(chain_dense_pq_kernel<32, PQ_KM>) : go(chain_dense_pq_kernel<32, PQ_KM, 1>);
   }
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };

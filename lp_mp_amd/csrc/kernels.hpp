@@ -113,8 +113,11 @@ bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, cons
 void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s);
 // peerq != nullptr: the launches carry CHAIN_LAUNCH_PQ_* roles (joined passes with peer minima; KC_DENSE_32 on f64 tables only)
+// pq_lds: the publishing records' form (LPMP_PQ_LDS): 1 park their first table in LDS, 0 request both of the first pair again
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr);
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr, int pq_lds = 1);
+// grid and resident workgroups per CU of that launch
+unsigned chain_pq_grid(int pq_lds, int n_tickets, int* per_cu);
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n_launches, double* dual, const double* cdata,
                        const int32_t* tabs, double* lb, hipStream_t s);
 void debug_set_level_trace(long long* p);
