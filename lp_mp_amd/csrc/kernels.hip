@@ -2341,7 +2341,11 @@ static_assert(BIG_WAVES == BIG_BLOCK_RECORDS, "plan.hpp: records per workgroup o
 struct BigLds { double* theta; double* mo; double* q; };
 // (the one decoding of sweep_bigdim_flags, for the kernels and for the LDS sizes of their launches)
 __host__ __device__ __forceinline__ int big_ldim(int flags) { const int k = (flags & SWEEP_BIGDIM_MASK) >> SWEEP_BIGDIM_SHIFT; return k ? 64 * k : BIG_MAX_LABELS; }
-static size_t big_lds_bytes(int flags) { return (size_t)BIG_WAVES * 3 * big_ldim(flags) * sizeof(double); }
+// waves (= records) per workgroup and dynamic LDS of a wave-per-unary launch whose waves hold `slabs` slabs of ldim doubles each:
+// BIG_WAVES while the workgroup stays within 64 KiB, two above (the streaming class, three slabs, always runs four: 48 KiB at most)
+static int big_waves(int flags, int slabs) { return (size_t)BIG_WAVES * slabs * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
+static size_t big_lds_bytes(int flags, int slabs) { return (size_t)big_waves(flags, slabs) * slabs * big_ldim(flags) * sizeof(double); }
+static_assert((size_t)BIG_WAVES * 3 * BIG_MAX_LABELS * sizeof(double) <= 65536, "the streaming dense launches assume BIG_WAVES waves per workgroup");
 // record and op fields are the same in all lanes of the wave: as scalars, so that row addresses are scalar-base + lane offset
 // (one VGPR of offsets for the 16 loads of a block instead of 16 64-bit addresses) and the loop bounds are uniform
 __device__ __forceinline__ double uni_f64(double v) { return __longlong_as_double(uni64<64>(__double_as_longlong(v))); }
@@ -2395,6 +2399,116 @@ __device__ __forceinline__ double ld_tab(const double* __restrict__ T, int64_t i
   if constexpr (T32) return (double)ld_stream<NT>(reinterpret_cast<const float*>(T) + idx);
   else return ld_stream<NT>(T + idx);
 }
+// ---- The one text of the wave-per-unary kernels (dense_big_body, sweep_diff_kernel; sweep_diff_band_kernel has a copy, see there): everything of a record
+// that does not depend on how a receive's q is reduced.  A kernel carves its LDS, calls big_begin, runs each receive as
+//   big_recv_begin / stage its constants / wave_sync / fill S.q / wave_sync / big_recv_end
+// and ends in big_finish.  What travels with the next op (nothing, {scale, offset}, plus the band word), what is staged into LDS
+// and the reduction that fills S.q are the kernel's own.  A: access policy of the duals.  The helpers take the LDS slabs as plain
+// pointers and the prefetched values as scalars, not BigLds / BigRecv by reference (EXPERIMENTS.md P: the form that costs a kernel
+// at its register cap the least).
+__device__ __forceinline__ Op uni_op(Op o) {
+  o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
+  o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
+  return o;
+}
+// record i with its fields as scalars; theta = the unary's own duals, into LDS
+template <int A>
+__device__ __forceinline__ UpdRec big_begin(const UpdRec* recs, int64_t i, double* dual, double* theta, int lane) {
+  UpdRec rec = recs[i];
+  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
+  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
+  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
+  const double* own_g = dual + rec.dual_off;
+  for (int i = lane; i < rec.d0; i += 64) theta[i] = ld_dual<A>(own_g + i);
+  return rec;
+}
+// a receive from an R x C factor on `side`: ms = the own side's message vector (Lr entries), Lo = the other side's label count
+struct BigRecv { int side, R, C, Lo; double* ms; double ms_pre[2]; };
+// requests m_s and stages m_o into LDS.  The own side m_s is requested together with m_o (round 6: it used to be loaded after the
+// table had been reduced — one more exposed round trip per receive; one or two values per lane up to 128 labels, later ones are
+// loaded where they are needed)
+template <int A>
+__device__ __forceinline__ BigRecv big_recv_begin(const Op& op, double* dual, double* s_mo, int Lr, int lane) {
+  BigRecv r;
+  r.side = (op.info >> 5) & 1;
+  r.R = op.pd0; r.C = op.pd1;
+  r.ms = dual + op.peer_dual + (r.side == 0 ? 0 : r.R);
+  const double* mo = dual + op.peer_dual + (r.side == 0 ? r.R : 0);
+  r.Lo = r.side == 0 ? r.C : r.R;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) r.ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(r.ms + lane + 64 * j) : 0.0;
+  for (int i = lane; i < r.Lo; i += 64) s_mo[i] = ld_dual<A>(mo + i);
+  return r;
+}
+// the update after q is filled: the min-marginal moves from m_s (ms0, ms1 = BigRecv::ms_pre) into theta; the peer's bound after this receive
+template <int A>
+__device__ __forceinline__ void big_recv_end(double* ms, double ms0, double ms1, int32_t peer, double* theta, const double* q, double* lb, int Lr, int lane) {
+  double pb = LPMP_INF;
+  for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
+    const double msv = j == 0 ? ms0 : j == 1 ? ms1 : ld_dual<A>(ms + i), qv = q[i];
+    const double delta = msv + qv;                   // omega = 1: delta = min-marginal
+    theta[i] += delta;
+    const double mn = msv - delta;
+    st_dual<A>(ms + i, mn);
+    pb = fmin(pb, mn + qv);
+  }
+  pb = wave_min(pb);
+  if (lane == 0) st_lb<A>(lb + peer, pb);
+  wave_sync();
+}
+// after the receives: the primal label and the sends ...
+template <int A>
+__device__ __forceinline__ void big_sends(UpdRec rec, const Op* ops, double* dual, double* lb, int32_t* primal,
+                                          double* theta, double* q, int flags, int lane) {
+  const int Lr = rec.d0;
+  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
+    double bv = LPMP_INF; int bi = 0x7fffffff;
+    for (int i = lane; i < Lr; i += 64) { const double x = theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
+    const double mn = wave_min(bv);
+    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
+    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
+  }
+  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
+  for (int i = lane; i < Lr; i += 64) q[i] = theta[i];
+  for (int k = 0; k < rec.n_send; ++k) {
+    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+    for (int i = lane; i < Lr; i += 64) {
+      const double delta = op.omega * q[i];
+      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+      theta[i] -= delta;
+    }
+    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
+  }
+}
+// ... and with them the residual rule, the store of theta and the unary's own bound
+template <int A>
+__device__ __forceinline__ void big_finish(UpdRec rec, const Op* ops, double* dual, double* lb, int32_t* primal,
+                                           double* theta, double* q, int flags, int lane) {
+  const int Lr = rec.d0;
+  big_sends<A>(rec, ops, dual, lb, primal, theta, q, flags, lane);
+  if (flags & SWEEP_RESIDUAL) {
+    double residual = 0.0;
+    for (int k = 0; k < rec.n_send; ++k) {
+      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+      residual += op.omega;
+      for (int i = lane; i < Lr; i += 64) {
+        const double delta = residual * theta[i];
+        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+        theta[i] -= delta;
+      }
+    }
+  }
+  double* own_g = dual + rec.dual_off;
+  double ob = LPMP_INF;
+  for (int i = lane; i < Lr; i += 64) { const double x = theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
+  ob = wave_min(ob);
+  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+}
+
 template <bool NT, int A, bool T32 = false>
 __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
                                                const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
@@ -2404,37 +2518,18 @@ __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, 
   const int64_t idx = block * BIG_WAVES + wave;
   if (idx >= count) return;
   const int ldim = big_ldim(flags);
-  BigLds S{big_lds_pool + (size_t)wave * 3 * ldim, big_lds_pool + (size_t)wave * 3 * ldim + ldim, big_lds_pool + (size_t)wave * 3 * ldim + 2 * ldim};
-  UpdRec rec = recs[first + idx];
-  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
-  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
-  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
-  auto uni_op = [](Op o) {
-    o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
-    o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
-    return o;
-  };
+  const BigLds S{big_lds_pool + (size_t)wave * 3 * ldim, big_lds_pool + (size_t)wave * 3 * ldim + ldim, big_lds_pool + (size_t)wave * 3 * ldim + 2 * ldim};
+  const UpdRec rec = big_begin<A>(recs, first + idx, dual, S.theta, lane);
   const int Lr = rec.d0;
-  double* own_g = dual + rec.dual_off;
-  for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
   const int my_row = 8 * (lane & 1) + 4 * ((lane >> 1) & 1) + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1);
   Op nxt{};
   if (rec.n_recv > 0) nxt = ops[rec.op_begin];
   for (int k = 0; k < rec.n_recv; ++k) {
     const Op op = uni_op(nxt);
     if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's table stream starts
-    const int side = (op.info >> 5) & 1;
-    const int R = op.pd0, C = op.pd1;
     const double* T = cdata + op.peer_const;
-    double* ms = dual + op.peer_dual + (side == 0 ? 0 : R);
-    const double* mo = dual + op.peer_dual + (side == 0 ? R : 0);
-    const int Lo = side == 0 ? C : R;
-    // the own side m_s is requested together with m_o (round 6: it used to be loaded after the table had been reduced — one more
-    // exposed round trip per receive; one or two values per lane up to 128 labels, later ones are loaded where they are needed)
-    double ms_pre[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(ms + lane + 64 * j) : 0.0;
-    for (int i = lane; i < Lo; i += 64) S.mo[i] = ld_dual<A>(mo + i);
+    const BigRecv r = big_recv_begin<A>(op, dual, S.mo, Lr, lane);
+    const int side = r.side, R = r.R, C = r.C, Lo = r.Lo;
     wave_sync();
     if (((op.info >> 8) & 15) == LPMP_F_PAIRWISE_POTTS) {
       // q[x] = min(m_o[x], diff + min_{y != x} m_o[y]) from the two smallest entries of m_o (multiset) and the
@@ -2488,57 +2583,9 @@ __device__ __forceinline__ void dense_big_body(const UpdRec* __restrict__ recs, 
       }
     }
     wave_sync();
-    double pb = LPMP_INF;                              // peer's bound after this receive
-    for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
-      const double msv = j == 0 ? ms_pre[0] : j == 1 ? ms_pre[1] : ld_dual<A>(ms + i), qv = S.q[i];
-      const double delta = msv + qv;                   // omega = 1: delta = min-marginal
-      S.theta[i] += delta;
-      const double mn = msv - delta;
-      st_dual<A>(ms + i, mn);
-      pb = fmin(pb, mn + qv);
-    }
-    pb = wave_min(pb);
-    if (lane == 0) st_lb<A>(lb + op.peer, pb);
-    wave_sync();
+    big_recv_end<A>(r.ms, r.ms_pre[0], r.ms_pre[1], op.peer, S.theta, S.q, lb, Lr, lane);
   }
-  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
-    double bv = LPMP_INF; int bi = 0x7fffffff;
-    for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
-    const double mn = wave_min(bv);
-    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
-    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
-  }
-  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
-  for (int i = lane; i < Lr; i += 64) S.q[i] = S.theta[i];
-  for (int k = 0; k < rec.n_send; ++k) {
-    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
-    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
-    for (int i = lane; i < Lr; i += 64) {
-      const double delta = op.omega * S.q[i];
-      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
-      S.theta[i] -= delta;
-    }
-    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
-  }
-  if (flags & SWEEP_RESIDUAL) {
-    double residual = 0.0;
-    for (int k = 0; k < rec.n_send; ++k) {
-      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
-      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
-      residual += op.omega;
-      for (int i = lane; i < Lr; i += 64) {
-        const double delta = residual * S.theta[i];
-        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
-        S.theta[i] -= delta;
-      }
-    }
-  }
-  double ob = LPMP_INF;
-  for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
-  ob = wave_min(ob);
-  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+  big_finish<A>(rec, ops, dual, lb, primal, S.theta, S.q, flags, lane);
 }
 // (five waves per SIMD: the body needs 96-101 VGPRs depending on small things, and the kernel is bound by round trips per wave)
 template <bool NT>
@@ -2558,8 +2605,8 @@ sweep_dense_big_f32_kernel(const UpdRec* __restrict__ recs, const Op* __restrict
 }
 // -------------------------------------------------------------------------------------------------
 // Class KC_DIFF: unaries whose pairwise peers are all DIFF factors (cost(a, b) = scale * D[a - b + d1 - 1], D a vector of
-// d0 + d1 - 1 doubles of the shared pool), 2 ... BIG_MAX_LABELS labels.  One wave per unary and op by op: dense_big_body with the
-// table stream replaced.  A receive writes sD[k] = scale * D[k] into LDS — the ONE multiply of the contract, once per entry —
+// d0 + d1 - 1 doubles of the shared pool), 2 ... BIG_MAX_LABELS labels.  One wave per unary and op by op: the shared text of
+// dense_big_body (big_begin ... big_finish) around another reduction.  A receive writes sD[k] = scale * D[k] into LDS — the ONE multiply of the contract, once per entry —
 // and takes q[x] = min_y (sD[x - y + d1 - 1] + m_o[y]) (own side 0; side 1: sD[y - x + d1 - 1]) from there: consecutive lanes read
 // consecutive doubles of sD, m_o[y] is a broadcast, a lane keeps up to four own labels 64 apart so that one m_o[y] serves them
 // all.  min and + are exact, so the result is the dense body's on the expanded table bit for bit.  No table is read from memory:
@@ -2683,16 +2730,12 @@ __device__ __forceinline__ void diff_band_minplus_all(const double* __restrict__
   }
 }
 constexpr int DIFF_WAVES_PER_SIMD = 6;
-// waves (= records) per workgroup: BIG_WAVES while their LDS stays within 64 KiB, two above.  ldim is a multiple of 64, so the
-// last size with four waves is 384 labels (60 KiB; 448 would be 70 KiB): launches of more than 384 labels run two waves, 40 KiB at 512
-static int diff_waves(int flags) { return (size_t)BIG_WAVES * 5 * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
-static size_t diff_lds_bytes(int flags) { return (size_t)diff_waves(flags) * 5 * big_ldim(flags) * sizeof(double); }
-// banded form: LDS of one wave = theta, m_o, q, pre, suf and the band of sD (at most n / DIFF_BAND_DIV < ldim / 2 entries), ldim
-// doubles each: four waves up to 320 labels (60 KiB), two above (48 KiB at 512)
-constexpr int DIFF_BAND_SLABS = 6;
+// LDS of one wave, in slabs of ldim doubles.  DIFF: theta, m_o, q and sD (2 ldim): four waves while that stays within 64 KiB, two
+// above.  ldim is a multiple of 64, so the last size with four waves is 384 labels (60 KiB; 448 would be 70 KiB): launches of more
+// than 384 labels run two waves, 40 KiB at 512.  Banded: theta, m_o, q, pre, suf and the band of sD (at most n / DIFF_BAND_DIV <
+// ldim / 2 entries): four waves up to 320 labels (60 KiB), two above (48 KiB at 512)
+constexpr int DIFF_SLABS = 5, DIFF_BAND_SLABS = 6;
 static_assert(DIFF_BAND_DIV >= 2, "the band of sD must fit one slab of ldim doubles: (2 ldim - 1) / DIFF_BAND_DIV <= ldim");
-static int diff_band_waves(int flags) { return (size_t)BIG_WAVES * DIFF_BAND_SLABS * big_ldim(flags) * sizeof(double) <= 65536 ? BIG_WAVES : 2; }
-static size_t diff_band_lds_bytes(int flags) { return (size_t)diff_band_waves(flags) * DIFF_BAND_SLABS * big_ldim(flags) * sizeof(double); }
 // the band word {lo, hi} the engine keeps in front of every pool entry of its own copy (engine.cpp, lpmp_upload_model)
 __device__ __forceinline__ int2 diff_band_word(const double* __restrict__ cdata, int64_t off) { return *reinterpret_cast<const int2*>(cdata + off - 1); }
 
@@ -2706,21 +2749,11 @@ sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, d
   const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
   if (idx >= count) return;
   const int ldim = big_ldim(flags);
-  double* const slab = big_lds_pool + (size_t)wave * 5 * ldim;
-  BigLds S{slab, slab + ldim, slab + 2 * ldim};
+  double* const slab = big_lds_pool + (size_t)wave * DIFF_SLABS * ldim;
+  const BigLds S{slab, slab + ldim, slab + 2 * ldim};
   double* const sD = slab + 3 * ldim;
-  UpdRec rec = recs[first + idx];
-  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
-  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
-  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
-  auto uni_op = [](Op o) {
-    o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
-    o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
-    return o;
-  };
+  const UpdRec rec = big_begin<A>(recs, first + idx, dual, S.theta, lane);
   const int Lr = rec.d0;
-  double* own_g = dual + rec.dual_off;
-  for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
   Op nxt{};
   double nscale = 0.0; int64_t noff = 0;               // the next receive's two constant words {scale, offset of D}
   if (rec.n_recv > 0) {
@@ -2733,78 +2766,28 @@ sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, d
     const double scale = uni_f64(nscale);
     const double* D = cdata + uni64<64>(noff);
     if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's reduction starts
-    const int side = (op.info >> 5) & 1;
-    const int R = op.pd0, C = op.pd1;
-    double* ms = dual + op.peer_dual + (side == 0 ? 0 : R);
-    const double* mo = dual + op.peer_dual + (side == 0 ? R : 0);
-    const int Lo = side == 0 ? C : R;
-    double ms_pre[2];                                  // the own side m_s is requested together with m_o and D
-#pragma unroll
-    for (int j = 0; j < 2; ++j) ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(ms + lane + 64 * j) : 0.0;
-    for (int i = lane; i < Lo; i += 64) S.mo[i] = ld_dual<A>(mo + i);
-    for (int i = lane; i < R + C - 1; i += 64) sD[i] = scale * D[i];
+    const BigRecv r = big_recv_begin<A>(op, dual, S.mo, Lr, lane);   // (m_s is requested together with m_o and D)
+    for (int i = lane; i < r.R + r.C - 1; i += 64) sD[i] = scale * D[i];
     wave_sync();
-    if (side == 0) diff_minplus_all<false>(sD, S.mo, S.q, Lr, Lo, C, lane);
-    else diff_minplus_all<true>(sD, S.mo, S.q, Lr, Lo, C, lane);
+    if (r.side == 0) diff_minplus_all<false>(sD, S.mo, S.q, Lr, r.Lo, r.C, lane);
+    else diff_minplus_all<true>(sD, S.mo, S.q, Lr, r.Lo, r.C, lane);
     if (k + 1 < rec.n_recv) {                          // (the next op has arrived long ago: its constants travel during the update below)
       const int64_t pc = uni64<64>(nxt.peer_const);
       nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
     }
     wave_sync();
-    double pb = LPMP_INF;                              // peer's bound after this receive
-    for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
-      const double msv = j == 0 ? ms_pre[0] : j == 1 ? ms_pre[1] : ld_dual<A>(ms + i), qv = S.q[i];
-      const double delta = msv + qv;                   // omega = 1: delta = min-marginal
-      S.theta[i] += delta;
-      const double mn = msv - delta;
-      st_dual<A>(ms + i, mn);
-      pb = fmin(pb, mn + qv);
-    }
-    pb = wave_min(pb);
-    if (lane == 0) st_lb<A>(lb + op.peer, pb);
-    wave_sync();
+    big_recv_end<A>(r.ms, r.ms_pre[0], r.ms_pre[1], op.peer, S.theta, S.q, lb, Lr, lane);
   }
-  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
-    double bv = LPMP_INF; int bi = 0x7fffffff;
-    for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
-    const double mn = wave_min(bv);
-    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
-    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
-  }
-  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
-  for (int i = lane; i < Lr; i += 64) S.q[i] = S.theta[i];
-  for (int k = 0; k < rec.n_send; ++k) {
-    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
-    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
-    for (int i = lane; i < Lr; i += 64) {
-      const double delta = op.omega * S.q[i];
-      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
-      S.theta[i] -= delta;
-    }
-    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
-  }
-  if (flags & SWEEP_RESIDUAL) {
-    double residual = 0.0;
-    for (int k = 0; k < rec.n_send; ++k) {
-      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
-      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
-      residual += op.omega;
-      for (int i = lane; i < Lr; i += 64) {
-        const double delta = residual * S.theta[i];
-        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
-        S.theta[i] -= delta;
-      }
-    }
-  }
-  double ob = LPMP_INF;
-  for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
-  ob = wave_min(ob);
-  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+  big_finish<A>(rec, ops, dual, lb, primal, S.theta, S.q, flags, lane);
 }
-// The banded kernel: sweep_diff_kernel with the reduction of a receive replaced, nothing else (its own copy of the body: the full
-// kernel keeps its code to the instruction, tools/compare_kernel_asm.py).  LDS of one wave: theta, m_o, q, pre, suf, the band of sD.
+// The banded kernel: sweep_diff_kernel with the reduction of a receive replaced, nothing else.  LDS of one wave: theta, m_o, q, pre,
+// suf, the band of sD.  It keeps its own text of the whole body (only uni_op is shared).  The kernel uses all 80 VGPRs of its six
+// waves per SIMD: with the shared helpers taking structs by reference, or with big_finish's residual rule or final store in a helper
+// in any form, it spills a register (80 VGPRs + 8 B of scratch); sharing big_begin / big_recv_begin / big_recv_end / big_sends and
+// keeping only those 16 lines compiled to 80 + 0 and gave the parent's bits, but its pass at 512 x 512 x 128 labels was 0.3 %
+// slower than the parent's, outside the parent-against-parent spread in two runs (2.7075 ms against [2.6936, 2.7058]).  A
+// wave-uniform slab base avoids the spill (69 VGPRs) but keeps 16 SGPRs in VGPR lanes and changes the waves per SIMD.
+// EXPERIMENTS.md P has the forms and the figures; a change to the shared text above is made here too.
 __global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_WAVES_PER_SIMD)
 sweep_diff_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
                        const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
@@ -2822,11 +2805,6 @@ sweep_diff_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ o
   rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
   rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
   rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
-  auto uni_op = [](Op o) {
-    o.peer_dual = uni64<64>(o.peer_dual); o.peer_const = uni64<64>(o.peer_const); o.omega = uni_f64(o.omega);
-    o.info = uni<64>(o.info); o.pd0 = uni<64>(o.pd0); o.pd1 = uni<64>(o.pd1); o.peer = uni<64>(o.peer);
-    return o;
-  };
   const int Lr = rec.d0;
   double* own_g = dual + rec.dual_off;
   for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
@@ -2927,10 +2905,10 @@ sweep_diff_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ o
 // run-time dims (d0 x d1 <= L x L): record + ops in one packet, the factor's OWN table requested right away and
 // read ONCE for both sides' min-marginals of the snapshot.
 // -------------------------------------------------------------------------------------------------
-template <int L>
-__global__ void __launch_bounds__(256)
-sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
-                         double* __restrict__ lb, int64_t count, int stride) {
+// T32: the factor's own dense table is stored as floats (SWEEP_TAB32) and widened in the load, nothing else differs
+template <int L, bool T32>
+__device__ __forceinline__ void pairwise_pk_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
+                                                 double* __restrict__ lb, int64_t count, int stride) {
   constexpr int G = DenseCfg<L>::G;
   constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
   constexpr int PIECES = 3 * (1 + PW_MAX_OPS);
@@ -2964,9 +2942,15 @@ sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ du
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int row = i * RPL + rl;
-      const double* Tr = T + (int64_t)row * C + 2 * c2;
-      t[i].x = (row < R && 2 * c2 < C) ? Tr[0] : LPMP_INF;
-      t[i].y = (row < R && 2 * c2 + 1 < C) ? Tr[1] : LPMP_INF;
+      if constexpr (T32) {
+        const float* Tr = reinterpret_cast<const float*>(T) + (int64_t)row * C + 2 * c2;   // floats, widened
+        t[i].x = (row < R && 2 * c2 < C) ? (double)Tr[0] : LPMP_INF;
+        t[i].y = (row < R && 2 * c2 + 1 < C) ? (double)Tr[1] : LPMP_INF;
+      } else {
+        const double* Tr = T + (int64_t)row * C + 2 * c2;
+        t[i].x = (row < R && 2 * c2 < C) ? Tr[0] : LPMP_INF;
+        t[i].y = (row < R && 2 * c2 + 1 < C) ? Tr[1] : LPMP_INF;
+      }
     }
   }
   double m1 = g < R ? own_g[g] : 0.0;            // message vector of side 0, element g
@@ -3028,171 +3012,83 @@ sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ du
   if (g < C) own_g[R + g] = m2;
   if (live && g == 0) lb[hdr->factor] = LPMP_NAN;
 }
-// The same kernel for a factor whose own dense table is stored as floats (SWEEP_TAB32).  A copy, not a shared body: the f64
-// kernel above keeps its code to the instruction (tools/compare_kernel_asm.py), and the two differ in the three lines of the load.
+template <int L>
+__global__ void __launch_bounds__(256)
+sweep_pairwise_pk_kernel(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
+                         double* __restrict__ lb, int64_t count, int stride) {
+  pairwise_pk_body<L, false>(packets, dual, cdata, lb, count, stride);
+}
 template <int L>
 __global__ void __launch_bounds__(256)
 sweep_pairwise_pk_f32_kernel(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
                              double* __restrict__ lb, int64_t count, int stride) {
-  constexpr int G = DenseCfg<L>::G;
-  constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL, GPB = 256 / G;
-  constexpr int PIECES = 3 * (1 + PW_MAX_OPS);
-  __shared__ double2_t lds_pk[GPB][PIECES];
-  __shared__ double lds_m1[GPB][L];
-  __shared__ double lds_m2[GPB][L];
-  __shared__ double lds_q0[GPB][L];
-  __shared__ double lds_q1[GPB][L];
-  const int grp = threadIdx.x / G, g = threadIdx.x % G;
-  const int64_t idx = (int64_t)blockIdx.x * GPB + grp;
-  const bool live = idx < count;
-  const int c2 = g % CL, rl = g / CL;
-  load_packet<G>(lds_pk[grp], packets, nullptr, nullptr, idx, stride, live, g);
-  const UpdRec* hdr = reinterpret_cast<const UpdRec*>(&lds_pk[grp][0]);
-  const Op* lop = reinterpret_cast<const Op*>(&lds_pk[grp][3]);
-  const int n_recv = live ? (int)hdr->n_recv : 0;
-  const int n_send = live ? (int)hdr->n_send : 0;
-  const int R = live ? hdr->d0 : 0, C = live ? hdr->d1 : 0;
-  double* own_g = dual + (live ? hdr->dual_off : 0);
-  const double* T = cdata + (live ? hdr->const_off : 0);
-  double2_t t[NL];
-  if (live && (hdr->kind_flags & 15) == LPMP_F_PAIRWISE_POTTS) {   // diff * [a != b] (reference test/potts_factor.cpp:34-36)
-    const double diff = T[0];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int row = i * RPL + rl;
-      t[i].x = (row < R && 2 * c2 < C) ? (row == 2 * c2 ? 0.0 : diff) : LPMP_INF;
-      t[i].y = (row < R && 2 * c2 + 1 < C) ? (row == 2 * c2 + 1 ? 0.0 : diff) : LPMP_INF;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int row = i * RPL + rl;
-      const float* Tr = reinterpret_cast<const float*>(T) + (int64_t)row * C + 2 * c2;   // floats, widened
-      t[i].x = (row < R && 2 * c2 < C) ? (double)Tr[0] : LPMP_INF;
-      t[i].y = (row < R && 2 * c2 + 1 < C) ? (double)Tr[1] : LPMP_INF;
-    }
-  }
-  double m1 = g < R ? own_g[g] : 0.0;            // message vector of side 0, element g
-  double m2 = g < C ? own_g[R + g] : 0.0;        // message vector of side 1, element g
-  // receives: delta = 1 * theta_u; the unary gives it up, the factor's vector of that side takes it
-#pragma unroll
-  for (int k = 0; k < PW_MAX_OPS; ++k) {
-    if (k < n_recv) {
-      const Op& o = lop[k];
-      const int side = (o.info >> 5) & 1;
-      if (g < o.len) {
-        double* th = dual + o.peer_dual + g;
-        const double v = *th;
-        const double dl = 1.0 * v;
-        *th = v + -1.0 * dl;
-        if (side == 0) m1 += +1.0 * dl; else m2 += +1.0 * dl;
-      }
-      if (g == 0) lb[o.peer] = LPMP_NAN;
-    }
-  }
-  // both min-marginal parts of the state after the receives: q0[a] = min_b T[a][b] + m2[b], q1[b] = min_a T[a][b] + m1[a]
-  const double m1s = m1, m2s = m2;
-  if (g < L) { lds_m1[grp][g] = m1s; lds_m2[grp][g] = m2s; }
-  wave_sync();
-  {
-    const double2_t mv = *reinterpret_cast<const double2_t*>(&lds_m2[grp][2 * c2]);
-    double vx = LPMP_INF, vy = LPMP_INF;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      double v = fmin(t[i].x + mv.x, t[i].y + mv.y);
-      v = row_allreduce_min<CL>(v);
-      if (c2 == 0) lds_q0[grp][i * RPL + rl] = v;
-      const double m1v = lds_m1[grp][i * RPL + rl];
-      vx = fmin(vx, t[i].x + m1v);
-      vy = fmin(vy, t[i].y + m1v);
-    }
-#pragma unroll
-    for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
-    if (rl == 0) { lds_q1[grp][2 * c2] = vx; lds_q1[grp][2 * c2 + 1] = vy; }
-  }
-  wave_sync();
-  const double q0 = g < L ? lds_q0[grp][g] : 0.0, q1 = g < L ? lds_q1[grp][g] : 0.0;
-  // sends: delta = omega * min-marginal of the snapshot
-#pragma unroll
-  for (int k = 0; k < PW_MAX_OPS; ++k) {
-    if (k < n_send) {
-      const Op& o = lop[n_recv + k];
-      const int side = (o.info >> 5) & 1;
-      if (g < o.len) {
-        const double dl = o.omega * (side == 0 ? m1s + q0 : m2s + q1);
-        double* th = dual + o.peer_dual + g;
-        *th += +1.0 * dl;
-        if (side == 0) m1 += -1.0 * dl; else m2 += -1.0 * dl;
-      }
-      if (g == 0) lb[o.peer] = LPMP_NAN;
-    }
-  }
-  if (g < R) own_g[g] = m1;
-  if (g < C) own_g[R + g] = m2;
-  if (live && g == 0) lb[hdr->factor] = LPMP_NAN;
+  pairwise_pk_body<L, true>(packets, dual, cdata, lb, count, stride);
 }
 
 // -------------------------------------------------------------------------------------------------
 // Lower bound (reference LP::LowerBound, LP_MP.h:1507-1518): per-factor bound, then a fixed-order sum.
 // -------------------------------------------------------------------------------------------------
-// one wave per factor, any kind
+// the bound of factor record r, by one wave (any kind); the same value in every lane.  The kind is decided outside the loops; the
+// cost expressions are pw_cost's, one multiply for SHARED / DIFF.
+__device__ __forceinline__ double factor_lb(const LbRec& r, const double* __restrict__ dual, const double* __restrict__ cdata, int tab32, int lane) {
+  const int kind = r.kind_flags & 15, flags = r.kind_flags >> 4;
+  const double* d = dual + r.dual_off;
+  if (kind == LPMP_F_VECTOR) {
+    double v = LPMP_INF;
+    for (int i = lane; i < r.d0; i += 64) v = fmin(v, d[i]);
+    double lb = wave_min(v);
+    if ((flags & LPMP_FF_IMPLICIT_ORIGIN) && 0.0 < lb) lb = 0.0;
+    return lb;
+  }
+  // min_a ( m1[a] + min_b (T[a][b] + m2[b]) ): lanes sweep the table row-major (coalesced)
+  const int d0 = r.d0, d1 = r.d1;
+  double best = LPMP_INF;
+  if (kind == LPMP_F_PAIRWISE_DENSE) {
+    const double* T = cdata + r.const_off;
+    const float* T32 = reinterpret_cast<const float*>(T);
+    for (int a = 0; a < d0; ++a) {
+      double v = LPMP_INF;
+      for (int b = lane; b < d1; b += 64) v = fmin(v, (tab32 ? (double)T32[(int64_t)a * d1 + b] : T[(int64_t)a * d1 + b]) + d[d0 + b]);
+      v = wave_min(v);
+      best = fmin(best, d[a] + v);
+    }
+  } else if (kind == LPMP_F_PAIRWISE_SHARED) {
+    const double scale = cdata[r.const_off];
+    const double* V = cdata + shared_table_off(cdata, r.const_off);
+    for (int a = 0; a < d0; ++a) {
+      double v = LPMP_INF;
+      for (int b = lane; b < d1; b += 64) v = fmin(v, scale * V[(int64_t)a * d1 + b] + d[d0 + b]);
+      v = wave_min(v);
+      best = fmin(best, d[a] + v);
+    }
+  } else if (kind == LPMP_F_PAIRWISE_DIFF) {
+    const double scale = cdata[r.const_off];
+    const double* D = cdata + shared_table_off(cdata, r.const_off) + (d1 - 1);
+    for (int a = 0; a < d0; ++a) {
+      double v = LPMP_INF;
+      for (int b = lane; b < d1; b += 64) v = fmin(v, scale * D[a - b] + d[d0 + b]);
+      v = wave_min(v);
+      best = fmin(best, d[a] + v);
+    }
+  } else {
+    const double diff = cdata[r.const_off];
+    for (int a = 0; a < d0; ++a) {
+      double v = LPMP_INF;
+      for (int b = lane; b < d1; b += 64) v = fmin(v, (a == b ? 0.0 : diff) + d[d0 + b]);
+      v = wave_min(v);
+      best = fmin(best, d[a] + v);
+    }
+  }
+  return best;
+}
+// one wave per factor, every factor
 __global__ void __launch_bounds__(256)
 factor_lb_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
                  double* __restrict__ out, int64_t count, int tab32) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t f = (int64_t)blockIdx.x * 4 + wave;
   if (f >= count) return;
-  const LbRec r = recs[f];
-  const int kind = r.kind_flags & 15, flags = r.kind_flags >> 4;
-  const double* d = dual + r.dual_off;
-  double lb;
-  if (kind == LPMP_F_VECTOR) {
-    double v = LPMP_INF;
-    for (int i = lane; i < r.d0; i += 64) v = fmin(v, d[i]);
-    lb = wave_min(v);
-    if ((flags & LPMP_FF_IMPLICIT_ORIGIN) && 0.0 < lb) lb = 0.0;
-  } else {
-    // min_a ( m1[a] + min_b (T[a][b] + m2[b]) ): lanes sweep the table row-major (coalesced)
-    const int d0 = r.d0, d1 = r.d1;
-    double best = LPMP_INF;
-    if (kind == LPMP_F_PAIRWISE_DENSE) {
-      const double* T = cdata + r.const_off;
-      const float* T32 = reinterpret_cast<const float*>(T);
-      for (int a = 0; a < d0; ++a) {
-        double v = LPMP_INF;
-        for (int b = lane; b < d1; b += 64) v = fmin(v, (tab32 ? (double)T32[(int64_t)a * d1 + b] : T[(int64_t)a * d1 + b]) + d[d0 + b]);
-        v = wave_min(v);
-        best = fmin(best, d[a] + v);
-      }
-    } else if (kind == LPMP_F_PAIRWISE_SHARED) {
-      const double scale = cdata[r.const_off];
-      const double* V = cdata + shared_table_off(cdata, r.const_off);
-      for (int a = 0; a < d0; ++a) {
-        double v = LPMP_INF;
-        for (int b = lane; b < d1; b += 64) v = fmin(v, scale * V[(int64_t)a * d1 + b] + d[d0 + b]);
-        v = wave_min(v);
-        best = fmin(best, d[a] + v);
-      }
-    } else if (kind == LPMP_F_PAIRWISE_DIFF) {
-      const double scale = cdata[r.const_off];
-      const double* D = cdata + shared_table_off(cdata, r.const_off) + (d1 - 1);
-      for (int a = 0; a < d0; ++a) {
-        double v = LPMP_INF;
-        for (int b = lane; b < d1; b += 64) v = fmin(v, scale * D[a - b] + d[d0 + b]);
-        v = wave_min(v);
-        best = fmin(best, d[a] + v);
-      }
-    } else {
-      const double diff = cdata[r.const_off];
-      for (int a = 0; a < d0; ++a) {
-        double v = LPMP_INF;
-        for (int b = lane; b < d1; b += 64) v = fmin(v, (a == b ? 0.0 : diff) + d[d0 + b]);
-        v = wave_min(v);
-        best = fmin(best, d[a] + v);
-      }
-    }
-    lb = best;
-  }
+  const double lb = factor_lb(recs[f], dual, cdata, tab32, lane);
   if (lane == 0) out[f] = lb;
 }
 
@@ -3204,26 +3100,7 @@ factor_lb_list_kernel(const LbRec* __restrict__ recs, const double* __restrict__
   const int64_t i = (int64_t)blockIdx.x * 4 + wave;
   if (i >= count) return;
   const int32_t f = list[i];
-  const LbRec r = recs[f];
-  const int kind = r.kind_flags & 15, flags = r.kind_flags >> 4;
-  const double* d = dual + r.dual_off;
-  double lb;
-  if (kind == LPMP_F_VECTOR) {
-    double v = LPMP_INF;
-    for (int k = lane; k < r.d0; k += 64) v = fmin(v, d[k]);
-    lb = wave_min(v);
-    if ((flags & LPMP_FF_IMPLICIT_ORIGIN) && 0.0 < lb) lb = 0.0;
-  } else {
-    const int d0 = r.d0, d1 = r.d1;
-    double best = LPMP_INF;
-    for (int a = 0; a < d0; ++a) {
-      double v = LPMP_INF;
-      for (int b = lane; b < d1; b += 64) v = fmin(v, pw_cost(cdata, r.const_off, kind, d1, a, b, tab32) + d[d0 + b]);
-      v = wave_min(v);
-      best = fmin(best, d[a] + v);
-    }
-    lb = best;
-  }
+  const double lb = factor_lb(recs[f], dual, cdata, tab32, lane);
   if (lane == 0) out[f] = lb;
 }
 
@@ -3467,11 +3344,11 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
   switch (kclass) {
     case KC_DENSE_BIG:
       if (flags & SWEEP_TAB32) {
-        if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_f32_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
-        else hipLaunchKernelGGL(sweep_dense_big_f32_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+        if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_f32_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags, 3), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+        else hipLaunchKernelGGL(sweep_dense_big_f32_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags, 3), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
       } else
-      if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
-      else hipLaunchKernelGGL(sweep_dense_big_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+      if (flags & SWEEP_NT) hipLaunchKernelGGL(sweep_dense_big_kernel<true>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags, 3), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
+      else hipLaunchKernelGGL(sweep_dense_big_kernel<false>, blocks(BIG_WAVES), dim3(64 * BIG_WAVES), big_lds_bytes(flags, 3), s, recs, ops, dual, cdata, lb, primal, first, count, flags);
       break;
     case KC_SMALL: hipLaunchKernelGGL(sweep_generic_kernel<1>, blocks(GenCtx<1>::FPB), dim3(GenCtx<1>::THREADS), 0, s, recs, ops, dual, cdata, tabs, lb, primal, pw_unary, first, count, flags); break;
     default: hipLaunchKernelGGL(sweep_generic_kernel<64>, blocks(GEN_WAVES), dim3(64 * GEN_WAVES), 0, s, recs, ops, dual, cdata, tabs, lb, primal, pw_unary, first, count, flags); break;
@@ -3483,13 +3360,13 @@ void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dua
                        int flags, hipStream_t s) {
   if (count <= 0) return;
   if (band) {                                          // every receive of the launch has a banded D (LevelRange::diff_band)
-    const int waves = diff_band_waves(flags);
-    hipLaunchKernelGGL(sweep_diff_band_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), diff_band_lds_bytes(flags), s,
+    const int waves = big_waves(flags, DIFF_BAND_SLABS);
+    hipLaunchKernelGGL(sweep_diff_band_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_BAND_SLABS), s,
                        recs, ops, dual, cdata, lb, primal, first, count, flags);
     return;
   }
-  const int waves = diff_waves(flags);
-  hipLaunchKernelGGL(sweep_diff_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), diff_lds_bytes(flags), s,
+  const int waves = big_waves(flags, DIFF_SLABS);
+  hipLaunchKernelGGL(sweep_diff_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_SLABS), s,
                      recs, ops, dual, cdata, lb, primal, first, count, flags);
 }
 

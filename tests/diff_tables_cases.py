@@ -265,6 +265,17 @@ def lower_bound_grid():
     return S.grid_model(9, 8, 70, pairwise="diff", order="colour_major", seed=12)
 
 
+def stale_bound_models():
+    """(name, model, model -> the dense model the oracle gets, table precision): 4 x 4 grids of 5 labels, one per pairwise kind the
+    two bound kernels tell apart"""
+    kw = dict(order="colour_major", seed=11)
+    same = lambda m: m
+    return (("dense", S.grid_model(4, 4, 5, **kw), same, None), ("dense_f32", S.grid_model(4, 4, 5, **kw).with_f32_tables(), same, "f32"),
+            ("shared", S.grid_model(4, 4, 5, pairwise="shared", n_tables=2, **kw), lambda m: m.expand_shared(), None),
+            ("diff", diff_grid(4, 4, 5, order="colour_major", seed=11), expand, None),
+            ("potts", S.grid_model(4, 4, 5, pairwise="potts", **kw), same, None))
+
+
 def uai_model():
     from lp_mp_amd import uai
     return uai.build_lp_from_uai(UAI_TEXT, diff_tables=True).flat_model()

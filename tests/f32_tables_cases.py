@@ -16,13 +16,13 @@ def grid(H, W, L, order="colour_major", seed=None, compute_primal=False):
 
 
 @functools.lru_cache(maxsize=None)
-def rect_chain():
-    """5 variables with (3, 7, 4, 9, 2) labels: tables 3x7, 7x4, 4x9, 9x2 — odd row lengths, rows that are not 16-byte aligned as floats"""
+def rect_chain(dims=(3, 7, 4, 9, 2)):
+    """5 variables with (3, 7, 4, 9, 2) labels: tables 3x7, 7x4, 4x9, 9x2 — odd row lengths, rows that are not 16-byte aligned as floats
+    (or a chain of other label counts: (5, 130, 5, 130) is the streaming class with rectangular tables received on both sides)"""
     b = M.ModelBuilder(2, S.mrf_mtypes())
     rng = np.random.default_rng(5)
-    dims = [3, 7, 4, 9, 2]
     u = [b.add_vector_factors(0, rng.uniform(0, 1, (1, d)))[0] for d in dims]
-    for i in range(4):
+    for i in range(len(dims) - 1):
         p = b.add_dense_pairwise(1, rng.uniform(0, 1, (dims[i], dims[i + 1])))[0]
         b.add_messages(0, u[i], p); b.add_messages(1, u[i + 1], p)
         b.add_relations(u[i], p); b.add_relations(p, u[i + 1])
@@ -51,15 +51,23 @@ def mixed_graph(n=40, n_edges=90, L=8, seed=7):
 
 
 @functools.lru_cache(maxsize=None)
-def scheduled_grid(H, W, L, sched, seed, flags=0, order="colour_major"):
-    """grid MRF whose unary-pairwise messages have the given schedule (right / full: the pairwise factors are updated)"""
+def scheduled_grid(H, W, L, sched, seed, flags=0, order="colour_major", dims=None, potts=False):
+    """grid MRF whose unary-pairwise messages have the given schedule (right / full: the pairwise factors are updated).
+    dims: label counts drawn per variable (rectangular tables); potts: Potts factors with couplings of both signs"""
     mt = [M.MsgType(0, 1, sched, 0, 1, M.M_UNARY_PAIRWISE, 0, flags), M.MsgType(0, 1, sched, 0, 1, M.M_UNARY_PAIRWISE, 1, flags)]
     b = M.ModelBuilder(2, mt)
     var = S.grid_variable_order(H, W, order).reshape(-1)
     a, bb = S.grid_edges(H, W)
     i, j = np.minimum(var[a], var[bb]), np.maximum(var[a], var[bb])
-    u = b.add_vector_factors(0, S.u01(H * W * L, seed).reshape(-1, L))
-    p = b.add_dense_pairwise(1, S.u01(len(a) * L * L, seed + 1).reshape(-1, L, L))
+    if dims is not None:
+        rng = np.random.default_rng(seed)
+        d = rng.choice(dims, size=H * W)
+        u = np.array([b.add_vector_factors(0, rng.uniform(0, 1, (1, int(x))))[0] for x in d])
+        p = np.array([b.add_dense_pairwise(1, rng.uniform(0, 1, (1, int(d[x]), int(d[y]))))[0] for x, y in zip(i, j)])
+    else:
+        u = b.add_vector_factors(0, S.u01(H * W * L, seed).reshape(-1, L))
+        p = (b.add_potts_pairwise(1, L, np.where(S.u01(len(a), seed + 1) < 0.5, -0.5, 0.75)) if potts
+             else b.add_dense_pairwise(1, S.u01(len(a) * L * L, seed + 1).reshape(-1, L, L)))
     b.add_interleaved_messages(np.tile(np.array([0, 1], np.int32), len(a)), np.stack([u[i], u[j]], 1).reshape(-1), np.repeat(p, 2))
     b.add_relations(np.stack([u[i], p], 1).reshape(-1), np.stack([p, u[j]], 1).reshape(-1))
     return b.finish()

@@ -14,6 +14,7 @@ from lp_mp_amd import synthetic as S
 from oracle.binding import Oracle
 
 import diff_tables_cases as C
+import repool_cases as R
 
 pytestmark = pytest.mark.gpu
 
@@ -290,6 +291,30 @@ def test_tracked_lower_bounds_equal_recomputed_ones(eng):
         full = eng.lower_bound()
         assert eng.lower_bound_recomputed() == m.n_factors
         assert abs(tracked - full) <= 1e-9 * max(1.0, abs(full)), (tracked, full)
+    # A few stale bounds, every pairwise kind: lower_bound() recomputes just those from the list (factor_lb_list_kernel),
+    # factor_lower_bounds() and a bound after invalidate_lower_bounds() recompute every factor (factor_lb_kernel and the packed
+    # classes' own).  One device function serves the first two, so the sums are the same double, not merely close.
+    for name, model, dense, prec in C.stale_bound_models():
+        e = E.Engine(0)
+        try:
+            e.upload(model, table_precision=prec); e.set_reparametrization(M.REPAM_ANISOTROPIC)
+            e.compute_pass(1)
+            e.invalidate_lower_bounds(); e.lower_bound()                      # every bound recomputed, none stale
+            fs = np.flatnonzero(model.f_kind != M.F_VECTOR)[[1, 7, 18]].astype(np.int32)
+            rows = R.rows_for(model, fs, 31, float_valued=prec is not None)
+            e.set_constants(fs, rows)                                         # their bounds are stale now
+            lb = e.lower_bound()
+            k = e.lower_bound_recomputed()
+            print(name, "recomputed from the list:", k, "of", model.n_factors)
+            assert len(fs) <= k <= model.n_factors // 8, (name, k)          # (more than an eighth stale: everything is recomputed)
+            flb = e.factor_lower_bounds()
+            e.invalidate_lower_bounds()
+            assert lb == e.lower_bound() and e.lower_bound_recomputed() == model.n_factors, name
+            o = Oracle(dense(R.with_duals(R.with_rows(model, fs, rows), e.download_duals())))
+            assert np.max(np.abs(flb - np.array([o.factor_lower_bound(f) for f in range(model.n_factors)]))) <= FLB_ATOL, name
+            assert abs(lb - o.LowerBound()) <= LB_RTOL * max(1.0, abs(o.LowerBound())), name
+        finally:
+            e.close()
 
 
 # ---- mid size, engine against engine ----------------------------------------------------------------------------------------

@@ -115,22 +115,32 @@ def test_random_graph_half_dense_half_potts(eng):
 
 
 # ---- 3. streaming class -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L", [33, 64, 65, 130])
+@pytest.mark.parametrize("L", [33, 64, 65, 130, pytest.param(("residual", 65), id="65-residual"), pytest.param(("residual", 130), id="130-residual"),
+                               pytest.param(("rect", (5, 130, 5, 130)), id="5x130-rect")])
 def test_streaming_class(nt_eng, L):
-    m = C.grid(4, 3, L, "colour_major")
+    """(the cases with a name: the residual send rule on a 3 x 3 grid, and a chain of 5- and 130-label variables, whose tables are
+    received as rows by one neighbour and as columns by the other — the parts of the wave-per-unary text the plain grids leave out)"""
+    what, L = L if isinstance(L, tuple) else ("grid", L)
+    m = C.rect_chain(L) if what == "rect" else C.grid(3, 3, L, "colour_major") if what == "residual" else C.grid(4, 3, L, "colour_major")
     for mode in (M.REPAM_ANISOTROPIC, M.REPAM_DAMPED_UNIFORM):
-        _check(nt_eng, m, mode, 2, classes={"dense_big"}, kernels={"dense_big": "sweep_dense_big_f32_kernel<"})
+        _check(nt_eng, m, mode, 2, classes={"dense_big"}, kernels={"dense_big": "sweep_dense_big_f32_kernel<"},
+               rtype=M.RTYPE_RESIDUAL if what == "residual" else 0)
 
 
 # ---- 4. updated pairwise factors ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sched", [M.SCHED_RIGHT, M.SCHED_FULL])
-@pytest.mark.parametrize("L", [5, 16, 33])
+@pytest.mark.parametrize("L", [5, 16, 33, pytest.param(("potts", 5), id="5-potts"), pytest.param(("rect", (2, 3, 7, 12, 30)), id="rect")])
 def test_updated_pairwise_factors(eng, sched, L):
-    m = C.scheduled_grid(6, 5, L, sched, seed=L)
+    """(the cases with a name: Potts factors, and tables of unequal dims — the other two branches of the packed kernel's load)"""
+    what, L = L if isinstance(L, tuple) else ("dense", L)
+    m = (C.scheduled_grid(3, 3, 0, sched, seed=3, dims=L) if what == "rect" else C.scheduled_grid(3, 3, L, sched, seed=L, potts=True) if what == "potts"
+         else C.scheduled_grid(6, 5, L, sched, seed=L))
     for mode in MODES:
         _check(eng, m, mode, 2)
     cls = eng.plan.schedule_classes(M.BACKWARD, M.REPAM_UNIFORM)
-    if L <= 32:
+    if what != "dense":
+        assert sum(v for k, v in cls.items() if k.startswith("pairwise")) > 0 and "generic" not in cls
+    elif L <= 32:
         want = "pairwise%d" % (8 if L <= 8 else 16 if L <= 16 else 32)
         assert cls.get(want, 0) > 0 and "generic" not in cls
     else:
@@ -206,7 +216,13 @@ def test_deep_chains(L, mailbox, monkeypatch):
 
 # ---- 8. rounding ------------------------------------------------------------------------------------------------------------
 def test_rounding_labels_and_cost(eng):
-    m = C.grid(6, 5, 8, "colour_major", compute_primal=True).with_f32_tables()
+    # (8 labels: a packed class; 65 and 130: the streaming class, whose label rule is the wave-per-unary kernels' shared one)
+    for m in (C.grid(6, 5, 8, "colour_major", compute_primal=True).with_f32_tables(), C.grid(3, 3, 65, "colour_major", compute_primal=True).with_f32_tables(),
+              C.grid(3, 3, 130, "colour_major", compute_primal=True).with_f32_tables()):
+        _rounding_labels_and_cost(eng, m)
+
+
+def _rounding_labels_and_cost(eng, m):
     for mode in (M.REPAM_ANISOTROPIC, M.REPAM_UNIFORM):
         o = Oracle(m); o.set_reparametrization(mode)
         eng.upload(m, table_precision="f32"); eng.set_reparametrization(mode)
