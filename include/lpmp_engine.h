@@ -178,7 +178,14 @@ int lpmp_set_stream(lpmp_engine* e, void* hip_stream);
  * updated by the wave-per-factor kernels may hold at most 512 doubles of duals and its messages at most 512 entries
  * (unaries with pairwise neighbours: 512 labels; everything else the generic kernel runs: 512 doubles); factors that
  * are only peers (pairwise tables of updated unaries) are bounded by those label counts; at most 32767 active
- * receives and 32767 active sends per updated factor. */
+ * receives and 32767 active sends per updated factor.
+ * What an upload leaves: the weight mode is unset (lpmp_set_reparametrization comes again before a pass: LPMP_ERR_STATE otherwise), the
+ * primal labels are unset, every lpmp_schedule_create id and every read-out of the previous model is dead (ids start again at 0); the
+ * send rule (lpmp_set_reparametrization_type), the speculation depth, the rows-layout and table-precision requests, persistent
+ * launches and the kernel-timing accumulators stay.  The previous model is released BEFORE the new one is planned: when the call
+ * fails, for whatever reason (a malformed model, LPMP_ERR_UNSUPPORTED from the table precision, float tables asked for together with
+ * the rows layout, a send rule the model does not run under), the engine holds NO model afterwards and every call that needs one
+ * returns LPMP_ERR_STATE until an upload succeeds. */
 int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int dual_mem);
 
 /* LP::set_reparametrization, LP_MP.h:330 (+ the lazy get_omega, :412-460).  Builds the weights of that mode and, for models of up
@@ -246,6 +253,10 @@ int lpmp_schedule_create(lpmp_engine* e, int64_t n, const int32_t* factors, cons
  * with fuse != 0 back-to-back updates of one factor are folded into one record (same results) */
 int lpmp_schedule_create_fused(lpmp_engine* e, int64_t n, const int32_t* factors, const int64_t* om_off,
                                const double* om, const int64_t* mk_off, const uint8_t* mk, int fuse, int* id_out);
+/* lpmp_schedule_run / _info / _destroy with an id that was never returned, that was destroyed, or that belongs to a model replaced
+ * since by lpmp_upload_model (before a new schedule takes the number): LPMP_ERR_INVALID ("unknown schedule id"), nothing runs.  A run
+ * settles passes that ran ahead, like every pass; the ids stay valid across lpmp_upload_costs, lpmp_set_vectors,
+ * lpmp_upload_shared_pool, lpmp_set_constants, lpmp_zero_pairwise_duals and lpmp_upload_duals and run on the costs of the moment. */
 int lpmp_schedule_run(lpmp_engine* e, int id);
 int lpmp_schedule_info(lpmp_engine* e, int id, int64_t* n_levels, int64_t* n_launches, int64_t* n_receives,
                        int64_t* n_sends, int64_t* algorithmic_bytes);
@@ -265,6 +276,10 @@ int lpmp_invalidate_lower_bounds(lpmp_engine* e);
  * kernels keep the others current: DESIGN.md 5); the number of factors when it recomputed everything, -1 before the first. */
 int64_t lpmp_lower_bound_recomputed(const lpmp_engine* e);
 int lpmp_synchronize(lpmp_engine* e);
+/* Calls that move no value — no dual, no bound beyond the rounding of a recomputed sum, no label, no schedule: lpmp_set_speculation,
+ * lpmp_set_persistent_launches, lpmp_enable_kernel_timing, lpmp_invalidate_lower_bounds and lpmp_synchronize settle passes that ran
+ * ahead; lpmp_prepare_passes, lpmp_reset_kernel_timing and the getters (lpmp_speculation_stats, lpmp_chain_cache_bytes,
+ * lpmp_get_kernel_timing, ...) do not.  lpmp_lower_bound inside an open batch reads that pass's row and does not settle either. */
 /* diagnostic: 1 when the uploaded model is streamed with non-temporal loads / stores (tables + duals above 1 GiB, i.e.
  * far larger than L2 + Infinity Cache; LPMP_NT=0/1 in the environment overrides), else 0; -1 without a model */
 int lpmp_streaming_access(const lpmp_engine* e);
@@ -380,6 +395,9 @@ int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
 int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);
+/* lpmp_upload_duals settles first, marks all tracked bounds stale and leaves the primal labels as they are (lpmp_evaluate_primal
+ * prices them on the duals of the moment), as do lpmp_set_vectors and lpmp_zero_pairwise_duals: only a change of CONSTANTS
+ * (lpmp_upload_costs, lpmp_upload_shared_pool, lpmp_set_constants) and lpmp_upload_model unset the labels. */
 int lpmp_upload_duals(lpmp_engine* e, const double* host_in);
 /* ---- new costs on the plan that is already there ---------------------------------------------------------------------------
  * Everything the engine builds before its first pass — order, weights, level schedules, kernel classes, packets, chain plans, the

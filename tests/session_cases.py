@@ -1,0 +1,1355 @@
+"""Session tests: random call sequences on ONE engine against the oracle (tests/test_session_host.py, tests/test_session_gpu.py,
+tests/session_replay.py).  The engine keeps much derived state between calls (tracked bounds, the rows layout and its two flags,
+speculative batches, the cache of joined-pass chains, labels and their time stamp, decode tables, read-outs, prepared schedules,
+``const_bad``, the float tables, the pool cells); every call has to leave all of it right for every call that may follow.  A session
+is a list of ``(op, args)`` steps — a pure function of (cell, seed, n) — applied to an engine and to a ``Shadow`` that states
+every call in numpy / on the CPU oracle; everything the caller can observe is compared.
+
+The contract, call by call (op -> paragraph of include/lpmp_engine.h -> statement the shadow uses).  "rebuild" = a new ``Oracle`` on
+``oracle_model(with_duals(model, duals))`` with send rule and weight mode set again; "labels unset" = every slot holds its dimension.
+
+  op                          header paragraph                          statement
+  --------------------------  ----------------------------------------  ------------------------------------------------------------
+  upload                      lpmp_upload_model, lpmp_set_rows_layout,  new model, its duals, no weight mode, labels unset, every
+                              lpmp_set_table_precision                  schedule id and read-out of the old model dead; the send rule
+                                                                        stays.  f32 tables + rows layout: LPMP_ERR_UNSUPPORTED and
+                                                                        NO model afterwards (every call LPMP_ERR_STATE)
+  compute_pass(n)             lpmp_compute_pass                         Oracle.ComputePass(n)
+  forward_ / backward_pass    lpmp_compute_forward_ / _backward_pass    Oracle.ComputeForwardPass / ComputeBackwardPass
+  compute_pass_custom         lpmp_compute_pass_custom                  Oracle.compute_pass_custom(test_fuzz_gpu.random_rows)
+  schedule_create / run       lpmp_schedule_create_fused / _run         the rows are kept; run = Oracle.compute_pass_custom(rows)
+  schedule_destroy            lpmp_schedule_destroy, lpmp_schedule_run  the id is dead: LPMP_ERR_INVALID from then on
+  ..._pass_and_primal(it)     primal rounding inside the sweep          Oracle.Compute...PassAndPrimal(it); labels = Oracle.primal()
+  decode_primal(d, refine)    lpmp_decode_primal                        labels = decode_cases.decode_reference; duals do not move
+  set_reparametrization       lpmp_set_reparametrization                Oracle.set_reparametrization
+  set_reparametrization_type  lpmp_set_reparametrization_type           Oracle.set_reparametrization_type (SHARED / RESIDUAL)
+  knobs                       lpmp_set_speculation ("results never      nothing: set_speculation, set_persistent_launches,
+                              differ"), lpmp_set_persistent_launches    enable_ / reset_kernel_timing, prepare_passes,
+                              ("same results"), lpmp_prepare_passes,    invalidate_lower_bounds, synchronize move no value
+                              lpmp_invalidate_lower_bounds, ...
+  upload_costs(const, duals)  lpmp_upload_costs, "duals given"          recost_cases.recost: model and duals replaced; labels unset
+  upload_costs(const)         lpmp_upload_costs, "duals NOT given"      constants replaced, duals kept, labels unset
+  set_vectors(new - old)      lpmp_zero_pairwise_duals (last sentence)  after every other warm start, as a step of its own:
+                                                                        scatter_rows(all unaries, new - old, accumulate)
+  set_vectors                 lpmp_set_vectors                          recost_cases.scatter_rows; labels stay
+  zero_pairwise_duals         lpmp_zero_pairwise_duals                  recost_cases.zero_pairwise; labels stay
+  set_constants               lpmp_set_constants                        repool_cases.with_rows; labels unset
+  upload_shared_pool          lpmp_upload_shared_pool                   FlatModel.with_pool; duals kept; labels unset
+  upload_duals                lpmp_upload_duals                         the duals given; labels stay
+  lower_bound                 lpmp_lower_bound                          Oracle.LowerBound
+  factor_lower_bounds         lpmp_factor_lower_bounds                  Oracle.factor_lower_bound per factor
+  download_duals              lpmp_download_duals                       Oracle.duals
+  labels                      lpmp_download_primal,                     the label array; consistent = every message's pairwise slot
+                              lpmp_check_primal_consistency,            equals its unary's; cost = decode_cases.energy on the
+                              lpmp_evaluate_primal                      original unaries theta_u + sum m_s (+inf: inconsistent / unset)
+  read-out labels / vectors   lpmp_readout_labels / _vectors            the label column / readout_cases.vectors_np
+  read-out beliefs            lpmp_readout_beliefs                      readout_cases.beliefs_np (floats widened under f32 tables)
+  refused                     the refusal sentence of each call         the documented code, and nothing moves
+
+Nothing an engine returns ever enters the shadow."""
+import collections
+import dataclasses
+import functools
+import zlib
+
+import numpy as np
+
+from lp_mp_amd import engine as E
+from lp_mp_amd import model as M
+from lp_mp_amd import synthetic as S
+from oracle.binding import Oracle
+
+import decode_cases as DC
+import mixed_precision_cases as MP
+import readout_cases as RO
+import recost_cases as RC
+import repool_cases as RP
+from test_fuzz_gpu import random_rows
+
+ERR_INVALID, ERR_UNSUPPORTED, ERR_DEVICE, ERR_STATE = -1, -2, -3, -4
+ANISO = M.REPAM_ANISOTROPIC
+MODES = (M.REPAM_ANISOTROPIC, M.REPAM_ANISOTROPIC2, M.REPAM_UNIFORM, M.REPAM_DAMPED_UNIFORM)
+RT_SHARED, RT_RESIDUAL = 0, 1
+LB_RTOL = 1e-9            # tests/test_fuzz_gpu.py; a tracked and a recomputed sum differ in association (tests/test_bound_sum_gpu.py)
+FLB_ATOL = 1e-12          # tests/test_fuzz_gpu.py, tests/test_recost_gpu.py on costs of this magnitude
+ENERGY_RTOL = 1e-9        # tests/test_decode_gpu.py test_decoded_labels_are_consistent_and_cost_the_original_energy
+PAIR_TOL = 1e-12          # tests/test_speculation_gpu.py lines 115-121: bounds of two engines, rtol = atol
+
+OBSERVING = ("lb", "flb", "dl", "labels", "ro_labels", "ro_vectors", "ro_beliefs")
+COST = ("cold", "warm", "vectors", "zero", "consts", "pool", "duals")
+STATE = ("pass", "dir", "custom", "primal_pass", "decode", "mode", "rtype", "knob") + COST + ("reupload", "refused")
+OP_CLASS = {
+    "compute_pass": "pass", "forward_pass": "dir", "backward_pass": "dir",
+    "compute_pass_custom": "custom", "schedule_create": "custom", "schedule_run": "custom", "schedule_destroy": "custom",
+    "forward_pass_and_primal": "primal_pass", "backward_pass_and_primal": "primal_pass", "compute_pass_and_primal": "primal_pass",
+    "decode_primal": "decode", "set_reparametrization": "mode", "set_reparametrization_type": "rtype",
+    "set_speculation": "knob", "set_persistent_launches": "knob", "enable_kernel_timing": "knob", "reset_kernel_timing": "knob",
+    "prepare_passes": "knob", "invalidate_lower_bounds": "knob", "synchronize": "knob",
+    "upload_costs_cold": "cold", "upload_costs_warm": "warm", "set_vectors": "vectors", "zero_pairwise_duals": "zero",
+    "set_vectors_diff": "vectors", "set_constants": "consts", "upload_shared_pool": "pool", "upload_duals": "duals", "upload": "reupload", "refused": "refused",
+    "lower_bound": "lb", "factor_lower_bounds": "flb", "download_duals": "dl", "labels": "labels",
+    "ro_labels": "ro_labels", "ro_vectors": "ro_vectors", "ro_beliefs": "ro_beliefs",
+}
+CLASS_OPS = {c: tuple(o for o, k in OP_CLASS.items() if k == c) for c in STATE + OBSERVING}
+NEEDS_MODE = {"compute_pass", "forward_pass", "backward_pass", "forward_pass_and_primal", "backward_pass_and_primal",
+              "compute_pass_and_primal", "prepare_passes"}
+
+
+# ---- models ------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def base_model(key):
+    """the models of the cells, built once per process and never modified"""
+    if key == "joined32":          # (compute_primal keeps the peer-minima form: Plan.peer_minima, checked in test_session_host.py)
+        return S.grid_model(40, 36, 32, order="colour_major", compute_primal=True)
+    if key == "mixed4":
+        return MP.m1()
+    if key == "rows":
+        return RC.rows_graph()
+    if key == "deep":
+        return RC.mailbox_grid()
+    if key == "lists":
+        return RC.c5_small()
+    if key == "diff40":
+        return RP.diff_grid(40)
+    if key == "shared32":
+        return RP.shared_grid_small(32)
+    raise KeyError(key)
+
+
+@functools.lru_cache(maxsize=None)
+def props(key):
+    m = base_model(key)
+    mrf = all(t.kind == M.M_UNARY_PAIRWISE for t in m.mtypes)
+    vec_types = np.unique(m.f_type[m.f_kind == M.F_VECTOR])
+    return dict(mrf=mrf, rounds=mrf and bool(np.all(np.asarray(m.ftype_computes_primal)[vec_types] != 0)), pool=m.sh_data is not None,
+                diff=m.has_diff, dense=bool(np.any(m.f_kind == M.F_PAIRWISE_DENSE)), rows_layout=key == "rows")
+
+
+@functools.lru_cache(maxsize=None)
+def _structure_oracle(key):
+    return Oracle(RC.oracle_model(base_model(key)))
+
+
+@functools.lru_cache(maxsize=6)
+def model_with_costs(key, seed, strict):
+    """the cell's model with the costs of ``seed`` (None: as built); ``strict``: constants that are exactly floats"""
+    m = base_model(key)
+    if seed is None:
+        return MP.float_valued(m) if strict else m
+    return RC.recost(m, seed, float_valued=strict)
+
+
+def vectors_of(m):
+    return np.flatnonzero((m.f_kind == M.F_VECTOR) & (m.dual_sizes() == m.f_dim0)).astype(np.int32)
+
+
+def vector_subset(m, seed):
+    """about a third of the vector factors in shuffled order, and one row of new values for each"""
+    rng = np.random.default_rng(seed)
+    v = vectors_of(m)
+    f = rng.permutation(v)[:max(1, len(v) // 3)].astype(np.int32)
+    return f, rng.random((len(f), int(m.f_dim0[f].max())))
+
+
+@functools.lru_cache(maxsize=16)
+def custom_rows(key, seed):
+    return random_rows(np.random.default_rng(seed), None, _structure_oracle(key), base_model(key))
+
+
+def pool_variant(m, variant):
+    """pool values by name: "u<seed>" a u01 stream (repool_cases.pool_of); for a pool that is ONE difference vector the truncated
+    linear ones of repool_cases (banded / unbanded: the launches of class diff change their kernel)"""
+    if variant[1:].isdigit():
+        return RP.pool_of(m, int(variant[1:]))
+    L = (m.sh_data.shape[0] + 1) // 2
+    return RP.tl(L, {"banded": RP.BANDED, "banded2": RP.BANDED_2, "unbanded": RP.UNBANDED}[variant]).reshape(-1).copy()
+
+
+def original_unaries(m, duals):
+    """the packed duals with every pairwise vector zero and every unary theta_u + sum over its messages of m_s (lpmp_decode_primal:
+    "with all neighbours theta_u + sum m_s is the original unary"), added in ascending message index"""
+    doff = m.dual_offsets()
+    out = np.array(duals, np.float64, copy=True)
+    for k in range(m.n_messages):
+        u, p, s = int(m.m_left[k]), int(m.m_right[k]), int(m.mtypes[int(m.m_type[k])].param)
+        d0 = int(m.f_dim0[u])
+        a = int(doff[p]) + (0 if s == 0 else int(m.f_dim0[p]))
+        out[doff[u]:doff[u] + d0] = out[doff[u]:doff[u] + d0] + duals[a:a + d0]
+    out[~RC.vector_mask(m)] = 0.0
+    return out
+
+
+_MEMO = collections.OrderedDict()
+
+
+def _memo(what, m, duals, extra, fn):
+    """a pure numpy statement evaluated once per (costs, duals, arguments): the two sides of a host run ask for the same one"""
+    # (a large constant array is told by its identity — the entry keeps it alive —: the costs of a seed are one array for every shadow)
+    big = m.const_data.size > 200000
+    key = (what, id(m.const_data) if big else zlib.crc32(np.ascontiguousarray(m.const_data).tobytes()),
+           0 if m.sh_data is None else zlib.crc32(m.sh_data.tobytes()), m.n_factors, zlib.crc32(np.ascontiguousarray(duals).tobytes()), extra)
+    if key not in _MEMO:
+        _MEMO[key] = (fn(), m.const_data)          # (the array lives as long as the entry that is keyed by its identity)
+        if len(_MEMO) > 8:
+            _MEMO.popitem(last=False)
+    return _MEMO[key][0]
+
+
+_LISTS = {}
+
+
+def _message_lists(m):
+    key = (m.n_factors, m.n_messages, zlib.crc32(m.m_left.tobytes()), zlib.crc32(m.m_right.tobytes()), zlib.crc32(m.m_type.tobytes()))
+    if key not in _LISTS:
+        _LISTS[key] = RO.message_lists(m)
+    return _LISTS[key]
+
+
+def _beliefs(m, duals, factors):
+    """readout_cases.beliefs_np(m, duals, factors) with the message lists of the structure made once per model (they read no cost)"""
+    lists, doff, coff = _message_lists(m), m.dual_offsets(), m.const_offsets()
+    out = np.full((len(factors), max([int(m.f_dim0[f]) for f in factors], default=0)), np.nan)
+    for i, u in enumerate(factors):
+        out[i, :int(m.f_dim0[u])] = RO.belief_row(m, duals, u, lists[u], doff, coff)
+    return out
+
+
+def unset_labels(m):
+    out = np.zeros((m.n_factors, 2), np.int32)
+    out[:, 0] = m.f_dim0
+    out[:, 1] = np.where(m.f_kind == M.F_VECTOR, 0, m.f_dim1)
+    return out
+
+
+# ---- the shadow ----------------------------------------------------------------------------------------------------------------
+def refuse(code, what):
+    return E.EngineError(code, "shadow: " + what)
+
+
+class ShadowReadout:
+    def __init__(self, sh, factors):
+        self.sh, self.gen = sh, sh.gen
+        m = sh.raw
+        self.factors = [int(f) for f in (RO.unaries(m) if factors is None else factors)]
+        self.n = len(self.factors)
+
+    def _enter(self):
+        if self.sh.raw is None or self.gen != self.sh.gen:
+            raise refuse(ERR_STATE, "the read-out was made for another model")
+
+    def labels(self):
+        self._enter()
+        return self.sh.labels[self.factors, 0].copy()
+
+    def vectors(self):
+        self._enter()
+        return RO.vectors_np(self.sh.raw, self.sh.duals(), self.factors)
+
+    def beliefs(self):
+        self._enter()
+        m = self.sh.raw
+        # supported per listed factor: every message of u is LPMP_M_UNARY_PAIRWISE with u as its left factor
+        up = np.array([t.kind == M.M_UNARY_PAIRWISE for t in m.mtypes])[m.m_type]
+        other = np.zeros(m.n_factors, bool)
+        other[m.m_left[~up]] = True
+        other[m.m_right] = True
+        bad = [u for u in sorted(set(self.factors)) if other[u]]
+        if bad:
+            raise refuse(ERR_UNSUPPORTED, "beliefs: factor %d " % bad[0])
+        m, d = self.sh.eff(), self.sh.duals()
+        return _memo("beliefs", m, d, tuple(self.factors), lambda: _beliefs(m, d, self.factors)).copy()
+
+    def close(self):
+        pass
+
+
+class Shadow:
+    """the engine's method names, stated in numpy and on the CPU oracle (the table at the top of this file)"""
+
+    def __init__(self, device=0):
+        self.raw, self.o, self.gen = None, None, 0
+        self.rtype, self.mode, self.prec = RT_SHARED, None, "f64"
+        self.labels, self.schedules = None, []
+
+    # ---- state ----
+    def eff(self):
+        """the model the engine computes on: under the f32 table modes its dense tables are the widened floats"""
+        return self.raw if self.prec == "f64" else self.raw.with_f32_tables()
+
+    def oracle_model(self, m):
+        return MP.oracle_model(m) if self.prec != "f64" else RC.oracle_model(m)      # (round, then expand: mixed_precision_cases)
+
+    def duals(self):
+        return self.o.duals()
+
+    def _model(self):
+        if self.raw is None:
+            raise refuse(ERR_STATE, "no model uploaded")
+
+    def _rebuild(self, duals):
+        self.o = Oracle(self.oracle_model(RP.with_duals(self.raw, duals)))
+        self.o.set_reparametrization_type(self.rtype)
+        if self.mode is not None:
+            self.o.set_reparametrization(self.mode)
+
+    def _mrf(self):
+        return all(t.kind == M.M_UNARY_PAIRWISE for t in self.raw.mtypes)
+
+    # ---- model and costs ----
+    def upload(self, model, const_dev=None, dual_dev=None, keep=None, rows_layout=None, table_precision=None):
+        prec = "f64" if table_precision is None else table_precision
+        if prec != "f64" and rows_layout:
+            self.raw, self.o, self.labels, self.schedules, self.mode = None, None, None, [], None
+            self.gen += 1
+            raise refuse(ERR_UNSUPPORTED, "table precision f32 and the rows layout cannot be combined")
+        self.raw, self.prec, self.mode = model, prec, None
+        self.gen += 1
+        self.schedules = []
+        self.labels = unset_labels(model)
+        self._rebuild(model.dual_data)
+
+    def upload_costs(self, const=None, duals=None):
+        self._model()
+        if const is None and duals is None:
+            raise refuse(ERR_STATE, "neither constants nor duals given")
+        d = self.duals() if duals is None else np.array(duals, np.float64, copy=True)
+        if const is not None:
+            self.raw = dataclasses.replace(self.raw, const_data=np.ascontiguousarray(const, np.float64), _keep=[])
+        self.labels = unset_labels(self.raw)
+        self._rebuild(d)
+
+    def set_vectors(self, factors, src, accumulate=False):
+        self._model()
+        factors = [int(f) for f in factors]
+        for f in factors:
+            if self.raw.f_kind[f] != M.F_VECTOR:
+                raise refuse(ERR_INVALID, "factor %d is not a VECTOR factor" % f)
+        if len(set(factors)) != len(factors):
+            raise refuse(ERR_INVALID, "listed twice")
+        self._rebuild(RC.scatter_rows(self.raw, self.duals(), factors, src, accumulate))
+
+    def zero_pairwise_duals(self):
+        self._model()
+        self._rebuild(RC.zero_pairwise(self.raw, self.duals()))
+
+    def set_constants(self, factors, src):
+        self._model()
+        factors = [int(f) for f in factors]
+        m = self.raw
+        for f in factors:
+            if m.f_kind[f] == M.F_VECTOR:
+                raise refuse(ERR_INVALID, "factor %d is a VECTOR factor" % f)
+        if len(set(factors)) != len(factors):
+            raise refuse(ERR_INVALID, "listed twice")
+        if self.prec != "f64":
+            sizes = m.const_sizes()
+            for i, f in enumerate(factors):
+                if m.f_kind[f] != M.F_PAIRWISE_DENSE:
+                    continue
+                row = np.asarray(src[i][:int(sizes[f])], np.float64)
+                with np.errstate(over="ignore"):
+                    r32 = row.astype(np.float32).astype(np.float64)
+                fin = np.isfinite(row)
+                bad = (fin & ~np.isfinite(r32)) | ((row != 0) & (np.abs(row) < np.finfo(np.float32).tiny))
+                if self.prec == "f32":
+                    bad |= r32 != row
+                if np.any(bad):
+                    raise refuse(ERR_UNSUPPORTED, "table precision: the row of factor %d" % f)
+        self.raw = RP.with_rows(m, factors, src)
+        self.labels = unset_labels(self.raw)
+        self._rebuild(self.duals())
+
+    def upload_shared_pool(self, sh_data=None):
+        self._model()
+        if sh_data is None or self.raw.sh_data is None:
+            raise refuse(ERR_INVALID, "null argument / no pool")
+        sh = np.asarray(sh_data, np.float64).reshape(-1)
+        if sh.shape != self.raw.sh_data.shape:
+            raise ValueError("upload_shared_pool: a pool of %d entries expected" % self.raw.sh_data.shape[0])
+        if np.any(np.isnan(sh)):
+            raise refuse(ERR_INVALID, "NaN entry")
+        self.raw = self.raw.with_pool(sh)
+        self.labels = unset_labels(self.raw)
+        self._rebuild(self.duals())
+
+    def upload_duals(self, d):
+        self._model()
+        self._rebuild(d)
+
+    # ---- passes ----
+    def set_reparametrization(self, mode):
+        self._model()
+        self.mode = int(mode)
+        self.o.set_reparametrization(self.mode)
+
+    def set_reparametrization_type(self, rtype):
+        self.rtype = int(rtype)
+        if self.o is not None:
+            self.o.set_reparametrization_type(self.rtype)
+
+    def _mode(self):
+        self._model()
+        if self.mode is None:
+            raise refuse(ERR_STATE, "no reparametrization set")
+
+    def compute_pass(self, n=1):
+        self._mode(); self.o.ComputePass(n)
+
+    def forward_pass(self):
+        self._mode(); self.o.ComputeForwardPass()
+
+    def backward_pass(self):
+        self._mode(); self.o.ComputeBackwardPass()
+
+    def compute_pass_custom(self, *rows):
+        self._model(); self.o.compute_pass_custom(*rows)
+
+    def schedule_create(self, factors, om_off, om, mk_off, mk, fuse=False):
+        self._model()
+        self.schedules.append((factors, om_off, om, mk_off, mk))
+        return len(self.schedules) - 1
+
+    def _schedule(self, sid):
+        self._model()
+        if not (0 <= sid < len(self.schedules)) or self.schedules[sid] is None:
+            raise refuse(ERR_INVALID, "unknown schedule id")
+        return self.schedules[sid]
+
+    def schedule_run(self, sid):
+        self.o.compute_pass_custom(*self._schedule(sid))
+
+    def schedule_destroy(self, sid):
+        self._schedule(sid)
+        self.schedules[sid] = None
+
+    def _primal(self, call, it):
+        self._mode()
+        if not self._mrf():
+            raise refuse(ERR_UNSUPPORTED, "primal rounding is built for unary / pairwise models")
+        call(it)
+        self.labels = self.o.primal()
+
+    def forward_pass_and_primal(self, it):
+        self._primal(self.o.ComputeForwardPassAndPrimal, it)
+
+    def backward_pass_and_primal(self, it):
+        self._primal(self.o.ComputeBackwardPassAndPrimal, it)
+
+    def compute_pass_and_primal(self, it):
+        self._primal(self.o.ComputePassAndPrimal, it)
+
+    def decode_primal(self, direction=0, refine=0):
+        self._model()
+        if direction not in (0, 1) or refine < 0:
+            raise refuse(ERR_INVALID, "direction / refine_sweeps")
+        if not self._mrf():
+            raise refuse(ERR_UNSUPPORTED, "decode: a message that is not a unary-pairwise one")
+        m, d = self.eff(), self.duals()
+        self.labels = _memo("decode", m, d, (direction, refine), lambda: DC.decode_reference(m, d, self.o.order(direction), refine)).copy()
+
+    # ---- knobs: no value moves ----
+    def set_speculation(self, k): pass
+    def set_persistent_launches(self, on): pass
+    def enable_kernel_timing(self, on): pass
+    def reset_kernel_timing(self): pass
+    def invalidate_lower_bounds(self): self._model()
+    def synchronize(self): pass
+    def prepare_passes(self, n): self._mode()
+
+    # ---- observations ----
+    def lower_bound(self):
+        self._model()
+        return self.o.LowerBound()
+
+    def factor_lower_bounds(self):
+        self._model()
+        m, d = self.eff(), self.duals()
+        return _memo("flb", m, d, 0, lambda: np.array([self.o.factor_lower_bound(f) for f in range(m.n_factors)])).copy()
+
+    def download_duals(self):
+        self._model()
+        return self.duals()
+
+    def download_primal(self):
+        self._model()
+        return self.labels.copy()
+
+    def upload_primal(self, primal):
+        self._model()
+        self.labels = np.array(primal, np.int32, copy=True)
+
+    def check_primal_consistency(self):
+        m, lab = self.raw, self.labels
+        side = np.array([int(m.mtypes[int(t)].param) for t in m.m_type], np.int64)
+        return bool(np.all(lab[m.m_left, 0] == lab[m.m_right, side]))
+
+    def evaluate_primal(self):
+        m, lab = self.raw, self.labels
+        unset = (lab[:, 0] >= m.f_dim0) | ((m.f_kind != M.F_VECTOR) & (lab[:, 1] >= m.f_dim1))
+        if not self.check_primal_consistency() or np.any(unset):
+            return np.inf
+        e, d = self.eff(), self.duals()
+        return _memo("energy", e, d, zlib.crc32(lab.tobytes()), lambda: DC.energy(RP.with_duals(e, original_unaries(m, d)), lab))
+
+    def readout(self, factors=None):
+        self._model()
+        return ShadowReadout(self, factors)
+
+    def close(self):
+        self.o = None
+
+
+# ---- cells -----------------------------------------------------------------------------------------------------------------------
+PRECISIONS = ("f64", "f32", "f32_round")
+# models: what the cell's uploads move through; n: session length; seeds: committed seeds; prologue: fixed first steps
+CELLS = {
+    "joined32": dict(models=("joined32",), n=116, seeds=(0, 1, 2, 3)),
+    "mixed4": dict(models=("mixed4",), n=64, seeds=(0, 1, 2, 3, 4, 5)),
+    "rows": dict(models=("rows",), n=82, seeds=(0, 1, 2, 3)),
+    "deep": dict(models=("deep",), n=90, seeds=(0, 1, 2, 3)),
+    "lists": dict(models=("lists",), n=72, seeds=(0, 1, 2, 3)),
+    "diffpool": dict(models=("diff40", "shared32"), n=96, seeds=(0, 1, 2, 3), weight={"pool": 3, "consts": 3}),
+}
+HOP_ROUTES = {0: ("shared32", "joined32", "lists", "diff40"), 1: ("mixed4", "deep", "rows", "shared32"), 2: ("lists", "joined32", "diff40", "rows")}
+HOP_SEEDS = tuple(HOP_ROUTES)
+
+
+def variant(cell, seed):
+    """what a session of the cell is run with besides its steps: table precision, borrowed buffers, environment"""
+    v = dict(prec="f64", borrowed=False, env={})
+    if cell == "joined32":
+        v["env"] = {"LPMP_ROT_BANDS": "6"}
+        if seed % 2:
+            # the smallest limit there is; explicit ticket lists for every pass count (not the periodic template of long calls), so
+            # that the chains of a few long calls together exceed it: the prologue of these seeds prepares them
+            v["env"].update({"LPMP_CHAIN_CACHE_MB": "1", "LPMP_ROT_EXPLICIT": "1"})
+    elif cell == "mixed4":
+        v["prec"], v["borrowed"] = PRECISIONS[seed % 3], seed >= 3
+    elif cell == "hop":
+        v["env"] = {"LPMP_ROT_BANDS": "6"}
+        v["prec"] = "f32_round" if seed == 1 else "f64"
+    return v
+
+
+def admissible_ops(key, prec):
+    """op names that may be drawn on this model (the refused ones are kinds of the op "refused")"""
+    p = props(key)
+    ops = {"compute_pass", "forward_pass", "backward_pass", "compute_pass_custom", "schedule_create", "schedule_run", "schedule_destroy",
+           "set_reparametrization", "set_speculation", "set_persistent_launches", "enable_kernel_timing", "reset_kernel_timing",
+           "prepare_passes", "invalidate_lower_bounds", "synchronize", "upload_costs_cold", "upload_costs_warm", "set_vectors",
+           "zero_pairwise_duals", "set_constants", "upload_duals", "upload", "refused", "lower_bound", "factor_lower_bounds",
+           "download_duals", "ro_labels", "ro_vectors"}
+    if p["mrf"]:
+        ops |= {"decode_primal", "set_reparametrization_type", "labels", "ro_beliefs"}
+    if p["rounds"]:
+        ops |= {"forward_pass_and_primal", "backward_pass_and_primal", "compute_pass_and_primal"}
+    if p["pool"]:
+        ops.add("upload_shared_pool")
+    return ops
+
+
+def refusal_kinds(key, prec):
+    """refusals the header documents, by model: (kind, code)"""
+    p = props(key)
+    kinds = ["vectors_twice", "vectors_nonvector", "consts_vector", "consts_twice"]
+    kinds += ["decode_direction"] if p["mrf"] else ["decode_lists", "beliefs_lists"]
+    kinds += ["pool_nan", "pool_size"] if p["pool"] else ["pool_none"]
+    if prec != "f64" and p["dense"]:
+        kinds.append("consts_f32")
+    return kinds
+
+
+def admissible_classes(cell):
+    keys = CELLS[cell]["models"]
+    ops = set.intersection(*[admissible_ops(k, "f64") for k in keys])
+    return [c for c in STATE if any(o in ops for o in CLASS_OPS[c])], [c for c in OBSERVING if any(o in ops for o in CLASS_OPS[c])], ops
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------------------------
+def _euler_pairs(items):
+    """a sequence over ``items`` in which every ordered pair of two different ones occurs as neighbours (an Euler circuit of the
+    complete digraph, Hierholzer)"""
+    out_edges = {a: [b for b in items if b != a] for a in items}
+    stack, circuit = [items[0]], []
+    while stack:
+        v = stack[-1]
+        if out_edges[v]:
+            stack.append(out_edges[v].pop())
+        else:
+            circuit.append(stack.pop())
+    return circuit[::-1]
+
+
+@functools.lru_cache(maxsize=None)
+def _covering_blocks(cell):
+    """per seed of the cell a list of blocks — tuples of (class, op or refusal kind): together they hold every (state-changing,
+    observing) pair as neighbours, every ordered pair of cost-changing classes as neighbours, every op three times and every
+    refusal kind once.  The ops of a class are taken in turn over the whole cell."""
+    st, ob, ops = admissible_classes(cell)
+    blocks = [(s, o) for s in st for o in ob]
+    cost = [c for c in COST if c in st]
+    chain = _euler_pairs(cost)
+    blocks += [tuple(chain[i:i + 7]) for i in range(0, len(chain) - 1, 6)]       # pieces overlap by one class: no pair is lost
+    blocks += [("mode", "pass")] * len(CELLS[cell]["seeds"])                      # other weights for the very next pass
+    kinds = sorted(set().union(*[refusal_kinds(k, "f64") for k in CELLS[cell]["models"]]) | {"destroyed_schedule", "stale_readout"})
+    names = {c: ([o for o in CLASS_OPS[c] if o in ops] if c != "refused" else kinds) for c in st + ob}
+    for c in st + ob:
+        have = sum(b.count(c) for b in blocks)
+        blocks += [(c,)] * max(0, (3 if c != "refused" else 1) * len(names[c]) - have)
+    turn = collections.Counter()
+    named = []
+    for b in blocks:
+        nb = []
+        for c in b:
+            nb.append((c, names[c][turn[c] % len(names[c])]))
+            turn[c] += 1
+        named.append(tuple(nb))
+    # messages that are not zero, zeroed while a prepared schedule exists, and the schedule run on them
+    named.append((("custom", "schedule_create"), ("pass", "compute_pass"), ("zero", "zero_pairwise_duals"), ("custom", "schedule_run"), ("dl", "download_duals")))
+    if cell == "joined32":
+        # every state-changing class right behind single passes with a batch of passes that ran ahead open (_Gen.spec_block)
+        named += [(("spec", c),) for c in st]
+    rng = np.random.default_rng(zlib.crc32(cell.encode()))
+    order = rng.permutation(len(named))
+    seeds = CELLS[cell]["seeds"]
+    return {s: [named[i] for i in order[k::len(seeds)]] for k, s in enumerate(seeds)}
+
+
+def observe_plan(cell, seed, session):
+    """per step: are the duals downloaded and compared after it?  About one state-changing step in four (a knob: one in two), always
+    after a refusal, never after compute_pass(1) — a download settles a speculative batch, and a batch has to live across the call
+    that follows it.  One draw per step index, so a prefix of a session has the prefix of the plan."""
+    u = np.random.default_rng([zlib.crc32(cell.encode()), int(seed), 7]).random(len(session))
+    out = []
+    for (op, a), x in zip(session, u):
+        c = OP_CLASS[op]
+        out.append(c not in OBSERVING and (c == "refused" or (op != "compute_pass" or a[0] != 1) and x < (0.5 if c == "knob" else 0.25)))
+    return out
+
+
+class SpecSim:
+    """what lpmp_set_speculation's paragraph says of batches, as a state machine over the steps: when a batch of passes that ran ahead
+    is open and whether the caller stands inside it (include/lpmp_engine.h; only the joined32 model with its switches opens one).  The
+    generator asks it where a call would meet an open batch; tests/test_session_gpu.py compares its counts with the engine's."""
+
+    def __init__(self):
+        self.max_depth = self.n = self.pos = self.run_len = self.learned = self.last_batch = 0
+        self.timing, self.persistent, self.rtype, self.mode, self.key = False, True, RT_SHARED, None, None
+        self.batches = self.rollbacks = 0
+
+    def usable(self):
+        return (self.key == "joined32" and self.max_depth >= 2 and self.rtype == RT_SHARED and self.persistent and not self.timing
+                and self.mode in (M.REPAM_ANISOTROPIC, M.REPAM_ANISOTROPIC2))
+
+    def inside(self):
+        return self.n > 0 and self.pos < self.n
+
+    def _interrupt(self):
+        if self.run_len > 0:
+            self.learned = self.run_len
+        self.run_len = self.last_batch = 0
+
+    def settle(self):
+        if self.inside():
+            self.rollbacks += 1
+        self.n = self.pos = 0
+        self._interrupt()
+
+    def _release(self):
+        self.n = self.pos = self.run_len = self.learned = self.last_batch = 0
+
+    def step(self, op, a, check=False):
+        """(a batch was open, the caller stood inside it) when the step came"""
+        before = (self.n > 0, self.inside())
+        if op == "upload":
+            self._release()
+            self.key, self.mode = a[0], None
+        elif op == "set_speculation":
+            self.settle()
+            self.max_depth = min(a[0], 32)
+            if self.max_depth < 2:
+                self._release()
+        elif op == "compute_pass" and a[0] == 1 and self.max_depth >= 2:
+            if self.inside():
+                self.pos += 1; self.run_len += 1
+            else:
+                self.n = self.pos = 0
+                depth = (self.learned if self.learned > 0 else 2) if self.run_len == 0 else max(2, 2 * self.last_batch)
+                depth = min(depth, self.max_depth)
+                if self.usable() and depth >= 2:
+                    self.n, self.pos, self.last_batch = depth, 1, depth
+                    self.batches += 1
+                else:
+                    self.last_batch = 0
+                self.run_len += 1
+        elif op in ("lower_bound", "prepare_passes", "reset_kernel_timing"):
+            pass
+        elif op == "set_reparametrization":
+            if a[0] != self.mode:
+                self.settle()
+            self.mode = a[0]
+        elif op == "set_reparametrization_type":
+            if a[0] != self.rtype:
+                self.settle()
+            self.rtype = a[0]
+        elif op == "upload_costs_cold":
+            self.n = self.pos = 0
+            self._interrupt()
+        else:
+            self.settle()
+            if op == "enable_kernel_timing":
+                self.timing = bool(a[0])
+            if op == "set_persistent_launches":
+                self.persistent = bool(a[0])
+        if check:
+            self.settle()
+        return before
+
+
+def spec_trace(cell, seed, session):
+    """SpecSim over a session under its observe plan: per step (open, inside) as the step came, and the machine at the end"""
+    sim, out = SpecSim(), []
+    for (op, a), chk in zip(session, observe_plan(cell, seed, session)):
+        out.append(sim.step(op, a, chk))
+    return out, sim
+
+
+class _Gen:
+    """emits steps one by one; keeps the little state that decides what may come next — a pure function of what it emitted"""
+
+    def __init__(self, cell, seed, prec):
+        self.cell, self.seed, self.prec0 = cell, seed, prec
+        self.rng = np.random.default_rng([zlib.crc32(cell.encode()), seed])
+        self.steps = []
+        self.key, self.prec, self.mode_set = None, prec, False
+        self.live, self.dead, self.n_slots = [], [], 0
+        self.turn = {}
+        self.uploads = 0
+        self.stale = False           # handles of the previous model not yet tried
+        self.tried_f32 = False
+        self.sim = SpecSim()         # follows every step pushed (with the observe plan of the session)
+        self.u = np.random.default_rng([zlib.crc32(cell.encode()), int(seed), 7]).random(4096)
+        self.mode, self.rtype = None, RT_SHARED
+        self.warm_diff = False       # the difference new - old of the last warm start is still to come
+        self.warms = 0
+
+    def _next(self, what, options):
+        i = self.turn.get(what, int(self.rng.integers(0, 1 << 16)))
+        self.turn[what] = i + 1
+        return options[i % len(options)]
+
+    def _seed(self):
+        return int(self.rng.integers(1, 1 << 30))
+
+    def push(self, op, *args):
+        self.steps.append((op, tuple(args)))
+        i = len(self.steps) - 1
+        self.sim.step(op, tuple(args), self._check(i))
+        if op == "set_reparametrization":
+            self.mode, self.mode_set = args[0], True
+        if op == "set_reparametrization_type":
+            self.rtype = args[0]
+
+    def _check(self, i):
+        op, a = self.steps[i]
+        c = OP_CLASS[op]
+        return c not in OBSERVING and (c == "refused" or (op != "compute_pass" or a[0] != 1) and self.u[i] < (0.5 if c == "knob" else 0.25))
+
+    def spec_block(self, c, want=None):
+        """speculation usable, single passes until the caller stands inside a batch, then a call of class ``c`` and a download"""
+        if self.sim.max_depth < 2:
+            self.push("set_speculation", 8)
+        if self.sim.timing:
+            self.push("enable_kernel_timing", False)
+        if not self.sim.persistent:
+            self.push("set_persistent_launches", True)
+        if self.rtype != RT_SHARED:
+            self.push("set_reparametrization_type", RT_SHARED)
+        if not self.mode_set or self.mode not in (M.REPAM_ANISOTROPIC, M.REPAM_ANISOTROPIC2):
+            self.push("set_reparametrization", ANISO)
+        for _ in range(6):
+            self.push("compute_pass", 1)
+            if self.sim.inside():
+                break
+        if c == "pass":
+            self.push("compute_pass", int(self._next("n_spec", (3, 2, 5))))
+        elif c == "mode":
+            self.push("set_reparametrization", int(self._next("mode_spec", (M.REPAM_UNIFORM, M.REPAM_DAMPED_UNIFORM))))
+        elif c == "rtype":
+            self.push("set_reparametrization_type", RT_RESIDUAL)
+        elif c == "custom":
+            self.emit_class(c, self._next("custom_spec", ("compute_pass_custom", "schedule_create")))
+        elif c == "refused":
+            self.emit_class(c, self._next("refused_spec", ("vectors_twice", "consts_vector", "decode_direction", "pool_none", "pool_nan")))
+        else:
+            self.emit_class(c, want)
+        self.push("download_duals")
+
+    def restore_speculation(self):
+        """the random tail keeps passes that run ahead possible most of the time: a switch that rules them out is set back"""
+        if self.key != "joined32":
+            return
+        if self.sim.max_depth < 2:
+            self.push("set_speculation", int(self._next("spec_on", (8, 2, 4))))
+        if self.sim.timing:
+            self.push("enable_kernel_timing", False)
+        if not self.sim.persistent:
+            self.push("set_persistent_launches", True)
+        if self.rtype != RT_SHARED:
+            self.push("set_reparametrization_type", RT_SHARED)
+
+    def upload(self, key, recost=True, prec=None):
+        p = props(key)
+        prec = self.prec0 if prec is None else prec
+        if p["rows_layout"]:
+            prec = "f64"
+        # every third upload of a model with dense tables first asks for float tables under the rows layout: refused, no model left
+        refused_first = p["dense"] and self.uploads % 3 == 1
+        if not p["mrf"] and self.rtype != RT_SHARED:      # the send rule stays across an upload: only SHARED is drawn on such a model
+            self.push("set_reparametrization_type", RT_SHARED)
+        self.push("upload", key, self._seed() if recost and self.uploads else None, prec, self._seed(), refused_first)
+        self.stale = self.uploads > 0
+        self.uploads += 1
+        self.key, self.prec, self.mode_set = key, prec, False
+        self.live, self.dead = [], []
+        self.warm_diff = False
+
+    def need_mode(self):
+        if not self.mode_set:
+            self.push("set_reparametrization", int(self._next("mode", MODES)))
+
+    def emit_class(self, c, want=None):
+        """one step of class ``c`` (``want``: this op / refusal kind where it can be drawn now), after whatever it needs first"""
+        ops = [o for o in CLASS_OPS[c] if o in admissible_ops(self.key, self.prec)]
+        if c == "custom":
+            op = want if want in ops else self._next(c, ops)
+            if op in ("schedule_run", "schedule_destroy") and not self.live:
+                self.push("schedule_create", self.n_slots, self._seed(), bool(self.rng.integers(0, 2)))
+                self.live.append(self.n_slots); self.n_slots += 1
+            if op == "compute_pass_custom":
+                self.push(op, self._seed())
+            elif op == "schedule_create":
+                self.push(op, self.n_slots, self._seed(), bool(self.rng.integers(0, 2)))
+                self.live.append(self.n_slots); self.n_slots += 1
+            elif op == "schedule_run":
+                self.push(op, int(self.live[int(self.rng.integers(0, len(self.live)))]))
+            else:
+                slot = self.live.pop(int(self.rng.integers(0, len(self.live))))
+                self.dead.append(slot)
+                self.push(op, int(slot))
+            return
+        if c == "reupload":
+            keys = CELLS[self.cell]["models"] if self.cell in CELLS else (self.key,)
+            precs = (self.prec0, "f64") if self.prec0 != "f64" else ("f64",)
+            self.upload(self._next("key", keys), prec=self._next("prec", precs))
+            return
+        if c == "refused":
+            kinds = refusal_kinds(self.key, self.prec) + ["destroyed_schedule"] + (["stale_readout"] if self.uploads >= 2 else [])
+            kind = want if want in kinds else self._next(c, kinds)
+            if self.stale and kind != "stale_readout":              # handles of the previous model are tried once after every move
+                self.push("refused", "stale_readout", self._seed())
+            extra = "consts_f32" in kinds and not self.tried_f32 and kind not in ("consts_f32", "stale_readout")      # once per session with float tables
+            self.stale = False
+            self.tried_f32 |= kind == "consts_f32"
+            if kind == "destroyed_schedule" and not self.dead:
+                self.push("schedule_create", self.n_slots, self._seed(), False)
+                self.push("schedule_destroy", self.n_slots)
+                self.dead.append(self.n_slots); self.n_slots += 1
+            self.push("refused", kind, int(self.dead[-1]) if kind == "destroyed_schedule" else self._seed())
+            if extra:
+                self.push("refused", "consts_f32", self._seed())
+                self.tried_f32 = True
+            return
+        op = want if want in ops else self._next(c, ops)
+        if op in NEEDS_MODE:
+            self.need_mode()
+        if op == "compute_pass":
+            self.push(op, int(self._next("n", (1, 2, 3, 5, 1, 1))))
+        elif c == "primal_pass":
+            self.push(op, len(self.steps) + 1)                      # the iteration: time stamps never repeat and never decrease
+        elif op == "decode_primal":
+            self.push(op, int(self.rng.integers(0, 2)), int(self._next("refine", (0, 1, 2))))
+        elif op == "set_reparametrization":
+            self.push(op, int(self._next("mode", MODES)))
+        elif op == "set_reparametrization_type":
+            self.push(op, int(self._next("rtype", (RT_RESIDUAL, RT_SHARED))))
+        elif op == "set_speculation":
+            self.push(op, int(self._next("spec", (8, 2, 0, 8))))
+        elif op in ("set_persistent_launches", "enable_kernel_timing"):
+            self.push(op, bool(self._next(op, (False, True, True))))
+        elif op == "prepare_passes":
+            self.push(op, int(self._next("prep", (2, 3, 5))))
+        elif op in ("upload_costs_cold", "upload_costs_warm", "set_constants"):
+            self.push(op, self._seed())
+            if op == "upload_costs_warm":
+                self.warms += 1
+                self.warm_diff = self.warms % 2 == 1
+            elif op == "upload_costs_cold":
+                self.warm_diff = False
+        elif op == "set_vectors":
+            self.push(op, self._seed(), bool(self._next("acc", (False, True))))
+        elif op == "upload_shared_pool":
+            one_vector = self.key == "diff40"
+            self.push(op, self._next("pool", ("unbanded", "banded", "u7", "banded2", "unbanded", "u9") if one_vector else ("u%d" % self._seed(),)))
+        else:
+            self.push(op)
+
+    def random_class(self):
+        st, ob, _ = admissible_classes(self.cell) if self.cell in CELLS else (None, None, None)
+        if st is None:
+            ops = admissible_ops(self.key, self.prec)
+            st = [c for c in STATE if c != "reupload" and any(o in ops for o in CLASS_OPS[c])]
+            ob = [c for c in OBSERVING if any(o in ops for o in CLASS_OPS[c])]
+        w = CELLS.get(self.cell, {}).get("weight", {})
+        cls = st + ob + ["pass"] * 3
+        p = np.array([w.get(c, 1) for c in cls], np.float64)
+        return cls[int(self.rng.choice(len(cls), p=p / p.sum()))]
+
+
+def _after_block(g, state):
+    if g.warm_diff:                                  # every other warm start is followed, a step or two later, by its new - old
+        g.push("set_vectors_diff")
+        g.warm_diff = False
+    if g.key == "joined32":
+        s = g.sim
+        off = s.max_depth < 2 or s.timing or not s.persistent or g.rtype != RT_SHARED
+        state["off"] = state.get("off", 0) + 1 if off else 0
+        if state["off"] >= 2:
+            g.restore_speculation()
+            state["off"] = 0
+
+
+def _cell_steps(cell, seed, n):
+    g = _Gen(cell, seed, variant(cell, seed)["prec"])
+    g.upload(CELLS[cell]["models"][0], recost=False)
+    if cell in ("joined32", "deep"):
+        g.push("set_reparametrization", ANISO)
+    g.need_mode()
+    if cell == "joined32":
+        # passes that run ahead, and a call that stops inside the second batch (2, then 4): batches > 0, rollbacks > 0, peer minima
+        for op, a in (("set_speculation", (8,)), ("compute_pass", (1,)), ("compute_pass", (1,)), ("compute_pass", (1,)), ("lower_bound", ()),
+                      ("forward_pass", ()), ("compute_pass", (3,)), ("compute_pass", (2,)), ("compute_pass", (5,)), ("download_duals", ())):
+            g.push(op, *a)
+        if "LPMP_CHAIN_CACHE_MB" in variant(cell, seed)["env"]:
+            # chains of long calls until the least recently used ones have to go, then calls whose chains went
+            for k in (31, 30, 29, 28, 27, 26):
+                g.push("prepare_passes", k)
+            g.push("compute_pass", 3); g.push("compute_pass", 2); g.push("lower_bound")
+    if cell == "deep":
+        g.push("forward_pass"); g.push("compute_pass", 1); g.push("download_duals")
+    if cell == "diffpool":
+        # the vector of the upload is banded: a pass on it, a pass after the swap to an unbanded one
+        g.push("compute_pass", 1); g.push("upload_shared_pool", "unbanded"); g.push("forward_pass"); g.push("lower_bound")
+    blocks = list(_covering_blocks(cell)[seed])
+    state = {}
+    while blocks if n is None else len(g.steps) < n:
+        block = blocks.pop(0) if blocks else ((g.random_class(), None),)
+        if block[0][0] == "spec":
+            if g.key == "joined32":
+                g.spec_block(block[0][1])
+        else:
+            for c, want in block:
+                g.emit_class(c, want)
+        _after_block(g, state)
+    return g.steps
+
+
+def _hop_steps(seed, n):
+    g = _Gen("hop", seed, variant("hop", seed)["prec"])
+    state = {}
+    for k, key in enumerate(HOP_ROUTES[seed]):
+        had_slot = bool(g.live or g.dead)
+        g.upload(key, recost=k > 0)
+        if k > 0:
+            g.emit_class("refused", "stale_readout")                  # the read-outs of the previous model
+            if had_slot:
+                g.push("refused", "stale_schedule", 0)
+        g.need_mode()
+        g.push("schedule_create", g.n_slots, g._seed(), False)       # a handle for the next move to try
+        g.live.append(g.n_slots); g.n_slots += 1
+        spec = [g._next("hop_spec", ("cold", "vectors", "consts", "decode", "custom", "warm", "zero", "duals", "knob", "refused"))
+                for _ in range(3)] if key == "joined32" else []
+        for j in range(int(g.rng.integers(15, 21)) - 4 * len(spec)):
+            g.emit_class(g.random_class())
+            _after_block(g, state)
+            if spec and j % 2 == 1:
+                g.spec_block(spec.pop())
+        g.emit_class("dl")
+    return g.steps
+
+
+def steps(cell, seed, n=None):
+    """the session (cell, seed) as a list of (op, args): a pure function of its arguments; the first k steps of a longer session
+    are the session of length k"""
+    if cell == "hop":
+        full = _hop_steps(seed, n)
+        return full if n is None else full[:n]
+    n = CELLS[cell]["n"] if n is None else n
+    return _cell_steps(cell, seed, n)[:n]
+
+
+def covering_length(cell, seed):
+    """steps until the covering list of the session has been emitted (its length must not be cut below this)"""
+    return len(_cell_steps(cell, seed, None))
+
+
+def sessions():
+    """(cell, seed) of every committed session but the hops"""
+    return [(c, s) for c in CELLS for s in CELLS[c]["seeds"]]
+
+
+# ---- the runner ------------------------------------------------------------------------------------------------------------------
+class Mismatch(AssertionError):
+    index = None          # the step the error names
+
+
+class _Side:
+    """one engine (or a shadow in an engine's place) with the handles of the session: schedule ids by slot, read-outs by upload"""
+
+    def __init__(self, target, borrowed=False):
+        self.t, self.borrowed = target, borrowed
+        self.ids, self.readouts, self.old_readouts = {}, None, None
+        self.stale_id = None
+        self.keep = None
+
+    def close(self):
+        for r in (self.readouts or ()) + (self.old_readouts or ()):
+            r.close()
+        self.readouts = self.old_readouts = None
+
+
+class Reach:
+    """what a session on a real engine reached of the state its cell is about (asserted by tests/test_session_gpu.py)"""
+
+    def __init__(self):
+        self.peer_minima = self.chain_launches = self.batches = self.rollbacks = 0
+        self.cache_max = 0
+        self.evictions = 0
+        self.banded = self.full = self.rows = False
+        self.deep_chain_passes = 0           # passes of a deep schedule planned as ONE persistent launch, run with timing off
+        self._timing = False
+        self.precisions = set()
+        self._cache = 0
+
+    def before_reset(self, e):
+        st = e.speculation_stats()
+        self.batches, self.rollbacks = max(self.batches, st["batches"]), max(self.rollbacks, st["rollbacks"])
+        self.peer_minima += e.peer_minima_launches()
+        self.chain_launches += sum(v.get("chain_launches", 0) for v in e.kernel_timing().values())
+
+    def after_step(self, e, op, args, mode):
+        if op == "enable_kernel_timing":
+            self._timing = bool(args[0])
+        if OP_CLASS[op] in ("pass", "dir") and mode is not None and not self._timing and e.persistent_launches:
+            # (with timing on a deep schedule runs launch by launch, and the chain executor keeps no counter of its own: the plan says
+            # how the sweep is run, as tests/test_recost_gpu.py test_deep_schedule_as_a_chain_with_the_mailbox asserts it)
+            ci = e.plan.chain_info(M.FORWARD, mode)
+            self.deep_chain_passes += int(ci["n_chains"] == 1 and ci["mailbox_rows"] > 0)
+        st = e.speculation_stats()
+        self.batches, self.rollbacks = max(self.batches, st["batches"]), max(self.rollbacks, st["rollbacks"])
+        b = e.chain_cache_bytes()
+        if b < self._cache and op != "upload":
+            self.evictions += 1
+        self._cache = b
+        self.cache_max = max(self.cache_max, b)
+        if op == "upload":
+            self.rows |= bool(e.rows_layout)
+            self.precisions.add(e.table_precision())
+        if OP_CLASS[op] in ("pass", "dir") and mode is not None and e.model.has_diff:
+            for d in (0, 1):
+                info = e.plan.diff_band_info(d, mode)
+                self.banded |= info["band_launches"] > 0
+                self.full |= info["diff_launches"] > info["band_launches"]
+
+
+def _upload(side, m, prec, rows_layout):
+    t = side.t
+    if side.borrowed and isinstance(t, E.Engine):
+        import torch
+        c = torch.from_numpy(np.ascontiguousarray(m.const_data)).cuda()
+        d = torch.from_numpy(np.ascontiguousarray(m.dual_data)).cuda()
+        torch.cuda.synchronize()
+        t.upload(m, const_dev=c.data_ptr(), dual_dev=d.data_ptr(), keep=(c, d), rows_layout=rows_layout, table_precision=prec)
+    else:
+        t.upload(m, rows_layout=rows_layout, table_precision=prec)
+
+
+def _expect(code, call):
+    """the call is refused with that code (a ValueError of the Python binding: code "ValueError")"""
+    try:
+        call()
+    except E.EngineError as ex:
+        return ex.code == code, "EngineError %s: %s" % (ex.code, ex)
+    except ValueError as ex:
+        return code == "ValueError", "ValueError: %s" % ex
+    return False, "no error"
+
+
+def _refused(side, sh, kind, arg):
+    """(code, call) of a refusal the header documents; ``sh``: the shadow, read for the structure of the current model only"""
+    t, m = side.t, sh.raw
+    vec, pw = vectors_of(m), np.flatnonzero(m.f_kind != M.F_VECTOR).astype(np.int32)
+    L = int(m.f_dim0[vec].max())
+    if kind == "vectors_twice":
+        return ERR_INVALID, lambda: t.set_vectors([vec[0], vec[-1], vec[0]], np.ones((3, L)))
+    if kind == "vectors_nonvector":
+        return ERR_INVALID, lambda: t.set_vectors([vec[0], pw[0]], np.ones((2, L)))
+    if kind in ("consts_vector", "consts_twice"):
+        f = [pw[0], vec[0]] if kind == "consts_vector" else [pw[0], pw[-1], pw[0]]
+        return ERR_INVALID, lambda: t.set_constants(f, np.ones((3, int(m.const_sizes().max()))))
+    if kind == "consts_f32":
+        dense = np.flatnonzero(m.f_kind == M.F_PAIRWISE_DENSE).astype(np.int32)
+        f = [dense[arg % len(dense)], pw[0]] if pw[0] != dense[arg % len(dense)] else [dense[arg % len(dense)]]
+        rows = RP.rows_for(m, f, arg, float_valued=True)
+        rows[0, 3] = 0.1 if sh.prec == "f32" else 1e300              # not a float / beyond float's range
+        return ERR_UNSUPPORTED, lambda: t.set_constants(f, rows)
+    if kind == "decode_direction":
+        return ERR_INVALID, lambda: t.decode_primal(2, 0)
+    if kind == "decode_lists":
+        return ERR_UNSUPPORTED, lambda: t.decode_primal(arg % 2, 0)
+    if kind == "beliefs_lists":
+        return ERR_UNSUPPORTED, lambda: side.readouts[1].beliefs()
+    if kind == "pool_none":
+        return ERR_INVALID, lambda: t.upload_shared_pool(np.ones(4))
+    if kind == "pool_nan":
+        sh_new = RP.pool_of(m, arg)
+        sh_new[(arg % len(sh_new)) // 2 + len(sh_new) // 2 - 1] = np.nan          # in the second half: a half-written pool would show
+        return ERR_INVALID, lambda: t.upload_shared_pool(sh_new)
+    if kind == "pool_size":
+        return "ValueError", lambda: t.upload_shared_pool(np.ones(m.sh_data.shape[0] + 1))
+    if kind == "destroyed_schedule":
+        return ERR_INVALID, lambda: t.schedule_run(side.ids[arg])
+    if kind == "stale_schedule":
+        return ERR_INVALID, lambda: t.schedule_run(side.stale_id)
+    if kind == "stale_readout":
+        return ERR_STATE, lambda: side.old_readouts[arg % 2].vectors()
+    raise KeyError(kind)
+
+
+def apply(side, sh, step):
+    """applies one step to ``side.t``; returns what an observing step saw (None otherwise).  ``sh``: the shadow of the session — its
+    MODEL is read where a step's arguments are made from the current costs (the same for every side)"""
+    op, a = step
+    t = side.t
+    if op == "upload":
+        key, cost_seed, prec, ro_seed, refused_first = a
+        m = model_with_costs(key, cost_seed, strict=prec == "f32")
+        if refused_first:
+            ok, got = _expect(ERR_UNSUPPORTED, lambda: t.upload(m, rows_layout=True, table_precision="f32_round"))
+            if not ok:
+                raise Mismatch("upload with float tables under the rows layout: expected LPMP_ERR_UNSUPPORTED, got " + got)
+            ok, got = _expect(ERR_STATE, t.lower_bound)
+            if not ok:
+                raise Mismatch("after a refused upload the engine holds no model: expected LPMP_ERR_STATE, got " + got)
+        if side.ids:
+            side.stale_id = sorted(side.ids.values())[0]
+        side.ids = {}
+        _upload(side, m, prec, props(key)["rows_layout"])
+        for r in side.old_readouts or ():
+            r.close()
+        side.old_readouts = side.readouts
+        sub, _ = vector_subset(m, ro_seed)
+        side.readouts = (t.readout(sub), t.readout(None))
+    elif op == "compute_pass_custom":
+        t.compute_pass_custom(*custom_rows(_key_of(sh), a[0]))
+    elif op == "schedule_create":
+        side.ids[a[0]] = t.schedule_create(*custom_rows(_key_of(sh), a[1]), fuse=a[2])
+    elif op in ("schedule_run", "schedule_destroy"):
+        getattr(t, op)(side.ids[a[0]])
+    elif op == "upload_costs_cold":
+        new = _recost(sh, a[0])
+        t.upload_costs(const=new.const_data, duals=new.dual_data)
+    elif op == "upload_costs_warm":
+        t.upload_costs(const=_recost(sh, a[0]).const_data)           # constants only: the messages and the unaries stay
+    elif op == "set_vectors_diff":
+        # the second half of the header's warm start: on the changed unaries the difference new - old, accumulated
+        new, old = sh.warm_new, sh.nominal
+        v = vectors_of(sh.raw)
+        doff, L = sh.raw.dual_offsets(), int(sh.raw.f_dim0[v].max())
+        diff = np.zeros((len(v), L))
+        for i, f in enumerate(v):
+            n = int(sh.raw.f_dim0[f])
+            diff[i, :n] = new[doff[f]:doff[f] + n] - old[doff[f]:doff[f] + n]
+        t.set_vectors(v, diff, accumulate=True)
+    elif op == "set_vectors":
+        f, rows = vector_subset(sh.raw, a[0])
+        t.set_vectors(f, rows, accumulate=a[1])
+    elif op == "set_constants":
+        f = RP.listed_subset(sh.raw, a[0])
+        t.set_constants(f, RP.rows_for(sh.raw, f, a[0], float_valued=sh.prec == "f32"))
+    elif op == "upload_shared_pool":
+        t.upload_shared_pool(pool_variant(sh.raw, a[0]))
+    elif op == "upload_duals":
+        t.upload_duals(sh.pending_duals)
+    elif op == "refused":
+        if (a[0] == "stale_readout" and side.old_readouts is None) or (a[0] == "stale_schedule" and side.stale_id is None):
+            return None                                   # (an engine that took over in the middle of a replay has no older handles)
+        code, call = _refused(side, sh, a[0], a[1])
+        ok, got = _expect(code, call)
+        if not ok:
+            raise Mismatch("refusal %s: expected %s, got %s" % (a[0], code, got))
+    elif op == "labels":
+        return (t.evaluate_primal(), t.check_primal_consistency(), t.download_primal())
+    elif op in ("ro_labels", "ro_vectors", "ro_beliefs"):
+        return tuple(getattr(r, op[3:])() for r in side.readouts)
+    elif op in ("lower_bound", "factor_lower_bounds", "download_duals"):
+        return getattr(t, op)()
+    else:
+        getattr(t, op)(*a)
+    return None
+
+
+def _key_of(sh):
+    return sh.key
+
+
+def _recost(sh, seed):
+    return model_with_costs(sh.key, seed, sh.prec == "f32")
+
+
+def _first_diff(x, y):
+    x, y = np.asarray(x), np.asarray(y)
+    if x.shape != y.shape:
+        return "shapes %s / %s" % (x.shape, y.shape)
+    bad = np.argwhere(~((x == y) | (_nan(x) & _nan(y))))
+    i = tuple(int(k) for k in bad[0])
+    return "first difference at %s: %r / %r (%d entries differ)" % (i, x[i].item(), y[i].item(), len(bad))
+
+
+def _nan(x):
+    return np.isnan(x) if x.dtype.kind == "f" else np.zeros(x.shape, bool)
+
+
+def compare(op, got, want, pair=False):
+    """None, or what differs between an observation and the shadow's (``pair``: between two engines, where a tracked and a recomputed
+    bound may differ in the last bit: tests/test_speculation_gpu.py lines 115-121)"""
+    if op == "lower_bound":
+        tol = PAIR_TOL * (1.0 + abs(want)) if pair else LB_RTOL * max(1.0, abs(want))
+        return None if np.isfinite(got) and abs(got - want) <= tol else "lower bound %r / %r" % (got, want)
+    if op == "factor_lower_bounds":
+        tol = PAIR_TOL * (1.0 + np.abs(want)) if pair else FLB_ATOL
+        return None if got.shape == want.shape and np.all(np.abs(got - want) <= tol) else "factor bounds: " + _first_diff(got, want)
+    if op == "download_duals":
+        return None if np.array_equal(got, want) else "duals: " + _first_diff(got, want)
+    if op == "labels":
+        (c, ok, lab), (cw, okw, labw) = got, want
+        if not np.array_equal(lab, labw):
+            return "labels: " + _first_diff(lab, labw)
+        if ok != okw:
+            return "check_primal_consistency %r / %r" % (ok, okw)
+        if pair or np.isinf(cw) or np.isinf(c):
+            return None if c == cw else "evaluate_primal %r / %r" % (c, cw)
+        # tests/test_decode_gpu.py test_decoded_labels_are_consistent_and_cost_the_original_energy: abs(cost - want) <= 1e-9 * max(1, abs(want))
+        return None if abs(c - cw) <= ENERGY_RTOL * max(1.0, abs(cw)) else "evaluate_primal %r / %r" % (c, cw)
+    # read-outs: tests/test_readout_gpu.py _check_labels_vectors (lines 91-92) and _check_beliefs (line 69): np.array_equal, equal_nan
+    for k, (x, y) in enumerate(zip(got, want)):
+        same = np.array_equal(x, y, equal_nan=True) if np.asarray(x).dtype.kind == "f" else np.array_equal(x, y)
+        if not same:
+            return "%s of read-out %d: %s" % (op, k, _first_diff(x, y))
+    return None
+
+
+def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=False, reach=None, fresh_at=None, fresh=None, log=None, skip=None):
+    """applies every step to every engine of ``engines`` (one, or two for the pair tests) and to ``shadow``, and compares: an observing
+    step at once, the duals after a state-changing step where ``observe`` (``observe_plan(cell, seed, session)``; None: always) says so —
+    about one step in four, since a download settles a speculative batch —, everything after the last step.  The first mismatch raises ``Mismatch``.
+    ``fresh_at`` / ``fresh``: at that step a new engine (made by ``fresh()``) takes over with the shadow's model and duals.
+    ``skip``: {engine number: ops it is not given} — knobs only, for the engine of a pair that keeps a setting."""
+    skip = skip or {}
+    engines = list(engines) if isinstance(engines, (list, tuple)) else [engines]
+    sides = [_Side(e, borrowed) for e in engines]
+    ssh = _Side(shadow)
+    reach = reach if reach is not None else Reach()
+
+    def fail(i, what):
+        lines = ["session %s seed %s, step %d %s%r: %s" % (cell, seed, i, session[i][0], session[i][1], what), "the last steps:"]
+        lines += ["  %3d %s%r" % (k, session[k][0], session[k][1]) for k in range(max(0, i - 7), i + 1)]
+        ex = Mismatch("\n".join(lines))
+        ex.index = i
+        return ex
+
+    def check(i, op):
+        try:
+            want = apply(ssh, shadow, (op, ()))
+            seen = [apply(s, shadow, (op, ())) for s in sides]
+        except E.EngineError as ex:
+            if ex.code == ERR_DEVICE:
+                raise
+            raise fail(i, "%s raised EngineError %s: %s" % (op, ex.code, ex))
+        for got in seen:
+            bad = compare(op, got, want)
+            if bad:
+                raise fail(i, bad + "  (engine / shadow)")
+        if len(seen) == 2:
+            bad = compare(op, seen[0], seen[1], pair=True)
+            if bad:
+                raise fail(i, bad + "  (first / second engine)")
+
+    try:
+        for i, (op, a) in enumerate(session):
+            if log:
+                log(i, op, a)
+            cls = OP_CLASS[op]
+            if fresh_at is not None and i == fresh_at:
+                d = shadow.download_duals()
+                for s in sides:
+                    s.close(); s.t.close()
+                    s.t = fresh()
+                    _upload(s, RP.with_duals(shadow.raw, d), shadow.prec, props(shadow.key)["rows_layout"])
+                    s.t.set_reparametrization_type(shadow.rtype)
+                    if shadow.mode is not None:
+                        s.t.set_reparametrization(shadow.mode)
+                    s.readouts = tuple(s.t.readout(None if r is None else r) for r in shadow.ro_lists)
+                    s.ids = {slot: s.t.schedule_create(*rows) for slot, rows in shadow.slot_rows.items()}
+                    if props(shadow.key)["mrf"]:                    # the labels, too: a later labels / read-out step compares them
+                        s.t.upload_primal(shadow.download_primal())
+                engines[:] = [s.t for s in sides]
+            if cls in OBSERVING:
+                check(i, op)
+                continue
+            if op == "upload":
+                shadow.key, shadow.slot_rows = a[0], {}
+                shadow.ro_lists = (vector_subset(base_model(a[0]), a[3])[0], None)
+            if op == "upload_duals":
+                shadow.pending_duals = shadow.download_duals() * 0.5
+            if op == "schedule_create":
+                shadow.slot_rows[a[0]] = custom_rows(shadow.key, a[1]) + (a[2],)
+            if op == "schedule_destroy":
+                shadow.slot_rows.pop(a[0], None)
+            try:
+                for k, s in enumerate(sides):
+                    if op in skip.get(k, ()):
+                        continue
+                    if op == "reset_kernel_timing" and isinstance(s.t, E.Engine):
+                        reach.before_reset(s.t)
+                    apply(s, shadow, (op, a))
+                apply(ssh, shadow, (op, a))
+            except Mismatch as ex:
+                raise fail(i, str(ex))
+            except E.EngineError as ex:
+                if ex.code == ERR_DEVICE:                           # a device error is no mismatch: the caller stops using the device
+                    raise
+                raise fail(i, "a call the step did not announce as refused raised EngineError %s: %s" % (ex.code, ex))
+            if op in ("upload", "upload_costs_cold"):
+                shadow.nominal = shadow.raw.dual_data if op == "upload" else _recost(shadow, a[0]).dual_data
+            if op == "upload_costs_warm":
+                shadow.warm_new = _recost(shadow, a[0]).dual_data
+            if op == "set_vectors_diff":
+                shadow.nominal = shadow.warm_new
+            for s in sides:
+                if isinstance(s.t, E.Engine):
+                    reach.after_step(s.t, op, a, shadow.mode)
+            if observe is None or observe[i]:
+                check(i, "download_duals")
+            if cls == "refused":                                   # the point of a refusal is the state after it
+                check(i, "factor_lower_bounds")
+        last = len(session) - 1
+        for op in ("download_duals", "lower_bound", "factor_lower_bounds", "ro_labels", "ro_vectors") + (("labels", "ro_beliefs") if props(shadow.key)["mrf"] else ()):
+            check(last, op)
+        for s in sides:
+            if isinstance(s.t, E.Engine):
+                reach.before_reset(s.t)
+    finally:
+        for s in sides + [ssh]:
+            s.close()
+    return reach
