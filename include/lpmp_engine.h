@@ -528,6 +528,8 @@ int lpmp_reset_kernel_timing(lpmp_engine* e);
 int lpmp_get_chain_launches(lpmp_engine* e, int n_classes, int64_t* chain_launches /*[n]*/);
 /* of the launches reported for class diff: how many ran the banded kernel (sweep_diff_band_kernel) */
 int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches);
+/* ... and how many ran the shifted kernel (sweep_diff_shift_kernel: launches with a LPMP_F_PAIRWISE_DIFF_SHIFT factor; never banded) */
+int lpmp_get_diff_shift_launches(lpmp_engine* e, int64_t* shift_launches);
 /* joined-pass launches in the peer-minima form since the last lpmp_reset_kernel_timing; counted with timing off,
  * too (passes that run ahead of the caller are never timed): with timing on since the reset, a part of dense32's chain launches */
 int lpmp_get_peer_minima_launches(lpmp_engine* e, int64_t* launches);

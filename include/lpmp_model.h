@@ -62,7 +62,22 @@ enum lpmp_factor_kind {
    * double multiply wherever the cost is needed, so the factor is bit for bit a PAIRWISE_DENSE factor whose table is
    * scale * D[a - b + dim1 - 1] computed on the host; +inf entries are hard constraints, NaN entries are refused, a scale
    * of 0 (or NaN) on a vector with infinities is outside the contract. */
-  LPMP_F_PAIRWISE_DIFF = 4
+  LPMP_F_PAIRWISE_DIFF = 4,
+  /* const TWO doubles {scale, shift}; dual = m1[dim0], m2[dim1] (the layout of PAIRWISE_DENSE);
+   * cost(a,b) = scale * D[min(max(a - b + s, 0), n - 1)] + m1[a] + m2[b] with D = entry f_table[f] of the same pool, a VECTOR
+   * there of ANY length: sh_dim0 == 1, n = sh_dim1 >= 1, and s = shift as an integer.  The index is clamped, so D continues
+   * with its end values: a truncated potential needs the entries of its band only (2 T + 1 for a truncated linear one), whatever
+   * dim0 and dim1 are, and the window of labels a variable holds (labels c_u ... c_u + dim0 - 1 against c_v ... c_v + dim1 - 1)
+   * is the shift s = c_u - c_v + (index of difference 0 in D).  PAIRWISE_DIFF is the case n = dim0 + dim1 - 1, s = dim1 - 1; one
+   * pool entry may serve DIFF and DIFF_SHIFT factors of any dims.  The contract is DIFF's: ONE IEEE double multiply wherever
+   * the cost is needed, bit for bit a PAIRWISE_DENSE factor whose table is that expression computed on the host; +inf entries are
+   * hard constraints, NaN entries are refused, a scale of 0 (or NaN) on a vector with infinities is outside the contract.
+   * shift is an integer-valued double with |shift| <= 2^30.  Like the scale it is NOT validated by the C ABI (it may live in
+   * device memory; lp_mp_amd.model.ModelBuilder and lp_mp_amd.lp refuse anything else), and no bit pattern of it makes a kernel
+   * read outside D.  The device converts it where it is used: NaN -> 0, then saturated to [-2^30, 2^30], then truncated toward
+   * zero (a C cast); lp_mp_amd.model.diff_shift_int and expand_diff() do the same.  The shift is a cost, not structure: it is
+   * replaced with lpmp_set_constants (a row {scale, shift}) or lpmp_upload_costs without planning anything. */
+  LPMP_F_PAIRWISE_DIFF_SHIFT = 6 /* (5 is not assigned: it stays an unknown kind, LPMP_ERR_INVALID) */
 };
 
 enum lpmp_factor_flags {
@@ -160,7 +175,7 @@ typedef struct lpmp_model {
   const int32_t* f_dim0;            /* [n_factors] */
   const int32_t* f_dim1;            /* [n_factors] (PAIRWISE_DENSE only; else ignored) */
   /* packed by factor in insertion order; per-factor sizes follow from kind/dims:
-   *   const: DENSE dim0*dim1, POTTS 1, SHARED 1, DIFF 1, VECTOR 0;  dual: VECTOR dim0, DENSE / SHARED / DIFF dim0+dim1, POTTS 2*dim0 */
+   *   const: DENSE dim0*dim1, POTTS 1, SHARED 1, DIFF 1, DIFF_SHIFT 2, VECTOR 0;  dual: VECTOR dim0, DENSE / SHARED / DIFF / DIFF_SHIFT dim0+dim1, POTTS 2*dim0 */
   const double* const_data;
   const double* dual_data;
 
@@ -185,8 +200,8 @@ typedef struct lpmp_model {
 
   /* --- shared pairwise tables (LPMP_F_PAIRWISE_SHARED): table t is sh_dim0[t] x sh_dim1[t], row-major at
    * sh_data[sh_off[t]]; sh_off[t+1] - sh_off[t] = sh_dim0[t] * sh_dim1[t].  sh_data is HOST memory whatever the
-   * memory kind of const_data.  f_table[f] = table of factor f (read for SHARED and DIFF factors only; may be NULL when the
-   * model has none).  A DIFF factor's entry is a 1 x (dim0 + dim1 - 1) table: the vector D of LPMP_F_PAIRWISE_DIFF.  A caller that
+   * memory kind of const_data.  f_table[f] = table of factor f (read for SHARED, DIFF and DIFF_SHIFT factors only; may be NULL when the
+   * model has none).  A DIFF factor's entry is a 1 x (dim0 + dim1 - 1) table: the vector D of LPMP_F_PAIRWISE_DIFF; a DIFF_SHIFT factor's a 1 x n table of any n.  A caller that
    * zero-initialises the struct and has no SHARED or DIFF factor need not touch these fields. --- */
   int32_t n_shared_tables;
   const int64_t* sh_off;            /* [n_shared_tables+1] */
@@ -198,10 +213,10 @@ typedef struct lpmp_model {
 
 /* sizes implied by kind/dims */
 static inline int64_t lpmp_factor_const_size(int kind, int dim0, int dim1) {
-  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : ((kind == LPMP_F_PAIRWISE_POTTS || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF) ? 1 : 0);
+  return kind == LPMP_F_PAIRWISE_DENSE ? (int64_t)dim0 * dim1 : (kind == LPMP_F_PAIRWISE_DIFF_SHIFT ? 2 : ((kind == LPMP_F_PAIRWISE_POTTS || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF) ? 1 : 0));
 }
 static inline int64_t lpmp_factor_dual_size(int kind, int dim0, int dim1) {
-  return (kind == LPMP_F_PAIRWISE_DENSE || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF) ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
+  return (kind == LPMP_F_PAIRWISE_DENSE || kind == LPMP_F_PAIRWISE_SHARED || kind == LPMP_F_PAIRWISE_DIFF || kind == LPMP_F_PAIRWISE_DIFF_SHIFT) ? (int64_t)dim0 + dim1 : (kind == LPMP_F_PAIRWISE_POTTS ? 2 * (int64_t)dim0 : dim0);
 }
 
 #ifdef __cplusplus

@@ -128,7 +128,7 @@ static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 
   return v;
 }
 
-struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, peer_minima_launches = 0; };
+struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, shift_launches = 0, peer_minima_launches = 0; };
 
 }  // namespace
 
@@ -298,7 +298,7 @@ struct lpmp_engine {
   int64_t schedules_built = 0;    // schedules, chain plans and joined-pass templates planned and uploaded for this model
   bool const_bad = false;         // a refused lpmp_upload_costs left the constants unspecified: nothing may read them
   bool tab_compact = false;       // f32 tables from host memory: const_buf holds only the cells of the non-DENSE factors
-  std::vector<int64_t> sh_cells;  // the SHARED / DIFF cells as launch_shared_cells receives them: {const offset, table offset}
+  std::vector<int64_t> sh_cells;  // the SHARED / DIFF cells as launch_shared_cells receives them: {const offset, table offset}; a DIFF_SHIFT factor has two in a row, the second {const offset of its shift, length of D}
   DevBuf<SetVecRec> d_setrecs; DevBuf<double> d_setsrc;   // records and (host sources) rows of lpmp_set_vectors, refilled in place
   DevBuf<SetConstRec> d_setcrecs;                         // records of lpmp_set_constants (its host rows share d_setsrc)
   DevBuf<ZeroRec> d_zero; int64_t n_zero = -1;            // pieces of the pairwise message vectors; -1: not built yet
@@ -382,7 +382,7 @@ struct lpmp_engine {
   }
   bool timing = false;
   ClassTiming ct[KC_COUNT];
-  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false; };   // band: sweep_diff_band_kernel
+  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false; };   // band: sweep_diff_band_kernel; shift: sweep_diff_shift_kernel
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
 
@@ -441,7 +441,7 @@ struct lpmp_engine {
       HIP_CHECK(hipEventSynchronize(p.b));
       float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
       ClassTiming& c = ct[p.cls];
-      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
+      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.shift_launches += p.shift ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
       event_pool.push_back(p.a); event_pool.push_back(p.b);
     }
     pending.clear();
@@ -738,7 +738,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
         throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
     }
     else if (lr.kclass == KC_DIFF)     // (LDS by the launch's label counts, as the streaming class)
-      launch_sweep_diff(lr.diff_band, s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
+      launch_sweep_diff(lr.diff_band, lr.diff_shift, s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
     else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
                               e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
@@ -749,7 +749,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
     }
     if (timed) {
       HIP_CHECK(hipEventRecord(b, stream));
-      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes, lr.kclass == KC_DIFF && lr.diff_band});
+      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes, lr.kclass == KC_DIFF && lr.diff_band, lr.kclass == KC_DIFF && lr.diff_shift});
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -1560,14 +1560,17 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
 // The engine-private copies of the constants that are COSTS, not structure: lpmp_upload_model derives them once, lpmp_upload_costs
 // again, with these functions (and narrow_tables above).
 // SHARED / DIFF factors: the cells {const offset of the factor's scale, table offset} go to the device as the upload laid them out
-// and shared_cells_kernel replaces every first word by the scale it finds in the constants; the pool behind the cells is not touched
+// and shared_cells_kernel replaces every first word by the scale it finds in the constants; the pool behind the cells is not touched.
+// A DIFF_SHIFT factor has a second cell right behind the first, {const offset of its shift, n = the length of D}: the same kernel
+// gathers the shift as it gathers a scale, and the factor's four words on the device are {scale, offset of D, shift (the double
+// of the constants: the kernels convert it, kernels.hip diff_shift_int), n}
 static void gather_shared_cells(lpmp_engine* e) {
   if (e->sh_cells.empty()) return;
   h2d(e->d_shared, e->sh_cells.data(), e->sh_cells.size() * sizeof(int64_t), e->stream);
   launch_shared_cells(e->d_shared, (int64_t)e->sh_cells.size() / 2, e->d_const, e->stream);
   HIP_CHECK(hipGetLastError());
 }
-// ... the pool block of d_shared, behind the cells of n_sf factors: every entry t of the plan's pool with one 8-byte band word
+// ... the pool block of d_shared, behind the n_sf cells (two words each): every entry t of the plan's pool with one 8-byte band word
 // {int32 lo, int32 hi} in front of it — sweep_diff_band_kernel learns the band of a DIFF vector from the word before the offset in
 // the factor's cell (entries no DIFF factor references: an empty band, never read).  Entry t starts at shared_pool_at(p, t).
 static int64_t shared_pool_at(const Plan& p, int32_t t) { return p.sh_off[(size_t)t] + t + 1; }
@@ -1666,8 +1669,11 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
       // device a factor's constants are two words {scale, offset of its table relative to the const base pointer} in an
       // allocation of the engine's own, followed by the pool (always copied from the host: sh_data is host memory also when the
       // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
-      std::vector<int64_t> sf;
-      for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
+      std::vector<int64_t> sf;                      // the factor of every cell; a DIFF_SHIFT factor is listed twice (its two cells)
+      for (int64_t f = 0; f < p.nf; ++f) {
+        if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
+        else if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) { sf.push_back(f); sf.push_back(f); }
+      }
       // (the pool behind the cells: write_shared_pool)
       const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
       auto pool_at = [&](int32_t t) { return shared_pool_at(p, t); };
@@ -1680,7 +1686,12 @@ int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int du
         const int64_t f = sf[(size_t)k];
         cells[(size_t)(2 * k)] = pl->p.dev_coff[f];   // (the packed offset, or the factor's cell of the compact constants: table precision)
         cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + pool_at(p.f_table[f]);
+        if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {   // its second cell: the shift, and n from the plan (structure: never from device memory)
+          cells[(size_t)(2 * k + 2)] = pl->p.dev_coff[f] + 1;
+          cells[(size_t)(2 * k + 3)] = p.sh_dim1[(size_t)p.f_table[f]];
+        }
         pl->p.dev_coff[f] = base + 2 * k;
+        if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) ++k;
       }
       e->sh_cells = std::move(cells);
       write_shared_pool(e, p, n_sf);
@@ -2813,11 +2824,13 @@ int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const 
       if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
         if (f32) { r.f32 = 1; any_f32 = true; }                       // the float table only: nothing is written as doubles
         else if (e->rows) { r.dst = p.f_coff[f]; r.dst2 = p.coff(f); r.two = 1; }   // the packed table, and the table part of the factor's row
-      } else if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) {
-        // the first word of the factor's cell, and the scalar lpmp_upload_costs would gather the cell from again
+      } else if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {
+        // the first word of the factor's cell, and the scalar lpmp_upload_costs would gather the cell from again (DIFF_SHIFT, two: the
+        // first words of its two cells — every second word from r.dst on — and the two scalars)
+        const bool shift = p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT;
         const int64_t k = (r.dst - sh_base) / 2;
-        if (k < 0 || 2 * k + 1 >= (int64_t)e->sh_cells.size() || sh_base + 2 * k != r.dst) throw std::runtime_error("lpmp_set_constants: internal: factor " + std::to_string(f) + " has no cell");
-        r.dst2 = e->sh_cells[(size_t)(2 * k)]; r.two = 1;
+        if (k < 0 || 2 * k + (shift ? 3 : 1) >= (int64_t)e->sh_cells.size() || sh_base + 2 * k != r.dst) throw std::runtime_error("lpmp_set_constants: internal: factor " + std::to_string(f) + " has no cell");
+        r.dst2 = e->sh_cells[(size_t)(2 * k)]; r.two = shift ? 2 : 1;
       }
       recs[(size_t)i] = r;
       total += len;
@@ -3029,6 +3042,15 @@ int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
     e->drain_timing();
     *band_launches = e->ct[KC_DIFF].band_launches;
+  });
+}
+// ... and how many ran sweep_diff_shift_kernel
+int lpmp_get_diff_shift_launches(lpmp_engine* e, int64_t* shift_launches) {
+  return guarded([&] {
+    if (!e || !shift_launches) throw std::runtime_error("null argument");
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->drain_timing();
+    *shift_launches = e->ct[KC_DIFF].shift_launches;
   });
 }
 int lpmp_reset_kernel_timing(lpmp_engine* e) {

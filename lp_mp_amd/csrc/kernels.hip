@@ -330,6 +330,16 @@ __device__ __forceinline__ int64_t shared_table_off(const double* __restrict__ c
   return __double_as_longlong(cdata[coff + 1]);
 }
 // (a DIFF factor has the same two words: its table is the vector D of d0 + d1 - 1 entries, cost(a, b) = scale * D[a - b + d1 - 1])
+// A DIFF_SHIFT factor has four words {scale, offset of D, shift, n}: shift is the double of the constants as the caller wrote it
+// (it may never have been on the host), n the length of D as an int64, from the plan.  cost(a, b) = scale * D[clamp(a - b + s, 0, n - 1)]
+// with s = diff_shift_int(shift): NaN -> 0, saturated to [-2^30, 2^30], truncated toward zero (include/lpmp_model.h).  |a - b| < 2^16,
+// so a - b + s cannot overflow, and the clamp keeps every read inside D whatever the bits of shift are.
+__device__ __forceinline__ int diff_shift_int(double shift) {
+  const double x = shift == shift ? shift : 0.0;
+  return (int)fmin(fmax(x, -1073741824.0), 1073741824.0);
+}
+__device__ __forceinline__ int diff_shift_n(const double* __restrict__ cdata, int64_t coff) { return (int)__double_as_longlong(cdata[coff + 3]); }
+__device__ __forceinline__ int diff_shift_index(int k, int s, int n) { return min(max(k + s, 0), n - 1); }
 // pairwise cost T(a,b) of a pairwise factor (dense table, Potts scalar, or scale * shared table / difference vector: ONE multiply,
 // so that the factor is bit for bit a dense factor whose table is scale * V)
 // t32 (wave-uniform, SWEEP_TAB32): DENSE tables are stored as floats (engine.cpp, table precision) and widened here — every
@@ -339,6 +349,8 @@ __device__ __forceinline__ double pw_cost(const double* __restrict__ cdata, int6
     return t32 ? (double)reinterpret_cast<const float*>(cdata + coff)[(int64_t)a * d1 + b] : cdata[coff + (int64_t)a * d1 + b];
   if (kind == LPMP_F_PAIRWISE_SHARED) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (int64_t)a * d1 + b];
   if (kind == LPMP_F_PAIRWISE_DIFF) return cdata[coff] * cdata[shared_table_off(cdata, coff) + (a - b + d1 - 1)];
+  if (kind == LPMP_F_PAIRWISE_DIFF_SHIFT)
+    return cdata[coff] * cdata[shared_table_off(cdata, coff) + diff_shift_index(a - b, diff_shift_int(cdata[coff + 2]), diff_shift_n(cdata, coff))];
   return a == b ? 0.0 : cdata[coff];
 }
 
@@ -2780,6 +2792,64 @@ sweep_diff_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, d
   }
   big_finish<A>(rec, ops, dual, lb, primal, S.theta, S.q, flags, lane);
 }
+// The shifted kernel (launches with a DIFF_SHIFT peer: LevelRange::diff_shift): sweep_diff_kernel with another fill, nothing else —
+// the same shared text (big_begin ... big_finish), the same LDS slabs, the same waves, the same reduction, which reads sD only.
+// What travels with the next op is {scale, offset of D} and the window {s, n} of the fill, sD[i] = scale * D[clamp(i - (C - 1) + s,
+// 0, n - 1)].  A plain DIFF peer of such a launch has no third and fourth word: its window is s = C - 1, n = R + C - 1, by the kind
+// in Op::info, and its fill then reads D[i] as the plain kernel does.  The two kernels keep their own lines between the shared
+// helpers: with both over one body template the plain kernel compiled to other registers.
+struct DiffWin { int s, n; };
+__device__ __forceinline__ DiffWin diff_next_win(const Op& nxt, const double* __restrict__ cdata, int64_t pc) {
+  if (((uni<64>(nxt.info) >> 8) & 15) == LPMP_F_PAIRWISE_DIFF_SHIFT) return {diff_shift_int(cdata[pc + 2]), diff_shift_n(cdata, pc)};
+  const int C = uni<64>(nxt.pd1);
+  return {C - 1, uni<64>(nxt.pd0) + C - 1};
+}
+__global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_WAVES_PER_SIMD)
+sweep_diff_shift_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
+                        const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
+                        int64_t first, int64_t count, int flags) {
+  constexpr int A = ACC_PLAIN;
+  extern __shared__ double big_lds_pool[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  if (idx >= count) return;
+  const int ldim = big_ldim(flags);
+  double* const slab = big_lds_pool + (size_t)wave * DIFF_SLABS * ldim;
+  const BigLds S{slab, slab + ldim, slab + 2 * ldim};
+  double* const sD = slab + 3 * ldim;
+  const UpdRec rec = big_begin<A>(recs, first + idx, dual, S.theta, lane);
+  const int Lr = rec.d0;
+  Op nxt{};
+  double nscale = 0.0; int64_t noff = 0;               // the next receive's constant words {scale, offset of D} ...
+  DiffWin nwin{0, 1};                                  // ... and its window {s, n}
+  if (rec.n_recv > 0) {
+    nxt = ops[rec.op_begin];
+    const int64_t pc = uni64<64>(nxt.peer_const);
+    nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+    nwin = diff_next_win(nxt, cdata, pc);
+  }
+  for (int k = 0; k < rec.n_recv; ++k) {
+    const Op op = uni_op(nxt);
+    const double scale = uni_f64(nscale);
+    const double* D = cdata + uni64<64>(noff);
+    const int ws = uni<64>(nwin.s), wn = uni<64>(nwin.n);
+    if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's reduction starts
+    const BigRecv r = big_recv_begin<A>(op, dual, S.mo, Lr, lane);   // (m_s is requested together with m_o and D)
+    // i < R + C - 1 <= 2 ldim - 1: inside the sD slab; the index of D is clamped to [0, n - 1], n from the plan
+    for (int i = lane; i < r.R + r.C - 1; i += 64) sD[i] = scale * D[diff_shift_index(i - (r.C - 1), ws, wn)];
+    wave_sync();
+    if (r.side == 0) diff_minplus_all<false>(sD, S.mo, S.q, Lr, r.Lo, r.C, lane);
+    else diff_minplus_all<true>(sD, S.mo, S.q, Lr, r.Lo, r.C, lane);
+    if (k + 1 < rec.n_recv) {                          // (the next op has arrived long ago: its constants travel during the update below)
+      const int64_t pc = uni64<64>(nxt.peer_const);
+      nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+      nwin = diff_next_win(nxt, cdata, pc);
+    }
+    wave_sync();
+    big_recv_end<A>(r.ms, r.ms_pre[0], r.ms_pre[1], op.peer, S.theta, S.q, lb, Lr, lane);
+  }
+  big_finish<A>(rec, ops, dual, lb, primal, S.theta, S.q, flags, lane);
+}
 // The banded kernel: sweep_diff_kernel with the reduction of a receive replaced, nothing else.  LDS of one wave: theta, m_o, q, pre,
 // suf, the band of sD.  It keeps its own text of the whole body (only uni_op is shared).  The kernel uses all 80 VGPRs of its six
 // waves per SIMD: with the shared helpers taking structs by reference, or with big_finish's residual rule or final store in a helper
@@ -3029,7 +3099,7 @@ sweep_pairwise_pk_f32_kernel(const Op* __restrict__ packets, double* __restrict_
 // Lower bound (reference LP::LowerBound, LP_MP.h:1507-1518): per-factor bound, then a fixed-order sum.
 // -------------------------------------------------------------------------------------------------
 // the bound of factor record r, by one wave (any kind); the same value in every lane.  The kind is decided outside the loops; the
-// cost expressions are pw_cost's, one multiply for SHARED / DIFF.
+// cost expressions are pw_cost's, one multiply for SHARED / DIFF / DIFF_SHIFT.
 __device__ __forceinline__ double factor_lb(const LbRec& r, const double* __restrict__ dual, const double* __restrict__ cdata, int tab32, int lane) {
   const int kind = r.kind_flags & 15, flags = r.kind_flags >> 4;
   const double* d = dual + r.dual_off;
@@ -3067,6 +3137,16 @@ __device__ __forceinline__ double factor_lb(const LbRec& r, const double* __rest
     for (int a = 0; a < d0; ++a) {
       double v = LPMP_INF;
       for (int b = lane; b < d1; b += 64) v = fmin(v, scale * D[a - b] + d[d0 + b]);
+      v = wave_min(v);
+      best = fmin(best, d[a] + v);
+    }
+  } else if (kind == LPMP_F_PAIRWISE_DIFF_SHIFT) {
+    const double scale = cdata[r.const_off];
+    const double* D = cdata + shared_table_off(cdata, r.const_off);
+    const int s = diff_shift_int(cdata[r.const_off + 2]), n = diff_shift_n(cdata, r.const_off);
+    for (int a = 0; a < d0; ++a) {
+      double v = LPMP_INF;
+      for (int b = lane; b < d1; b += 64) v = fmin(v, scale * D[diff_shift_index(a - b, s, n)] + d[d0 + b]);
       v = wave_min(v);
       best = fmin(best, d[a] + v);
     }
@@ -3356,7 +3436,7 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
 }
 
 // class KC_DIFF: one wave per record, dynamic LDS by the launch's label counts (flags: sweep_bigdim_flags)
-void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
+void launch_sweep_diff(bool band, bool shift, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s) {
   if (count <= 0) return;
   if (band) {                                          // every receive of the launch has a banded D (LevelRange::diff_band)
@@ -3366,6 +3446,11 @@ void launch_sweep_diff(bool band, const UpdRec* recs, const Op* ops, double* dua
     return;
   }
   const int waves = big_waves(flags, DIFF_SLABS);
+  if (shift) {                                         // a record of the launch has a DIFF_SHIFT peer (LevelRange::diff_shift): same LDS, same waves
+    hipLaunchKernelGGL(sweep_diff_shift_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_SLABS), s,
+                       recs, ops, dual, cdata, lb, primal, first, count, flags);
+    return;
+  }
   hipLaunchKernelGGL(sweep_diff_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_SLABS), s,
                      recs, ops, dual, cdata, lb, primal, first, count, flags);
 }
@@ -3682,7 +3767,7 @@ zero_pairwise_kernel(const ZeroRec* __restrict__ recs, int64_t n, double* __rest
 }
 // constants of listed pairwise factor k := row src_row of src (engine.cpp, lpmp_set_constants): one wave per record, lanes stride over
 // the entries, 64-bit offsets (a table may start past 2^32 doubles).  A record names every place the sweep kernels read the
-// factor's constants from — the Potts scalar; the first word of a SHARED / DIFF cell and the scalar the cell was gathered from; a
+// factor's constants from — the Potts scalar; the first word of a SHARED / DIFF cell (of both cells of a DIFF_SHIFT factor) and the scalar the cell was gathered from; a
 // dense table in the packed constants and in the factor's row of the rows layout; or the float table, narrowed here as
 // narrow_tables_kernel narrows (round to nearest even).  The check kernel applies that kernel's refusals to the rows of the float
 // tables and writes nothing else: the host launches it first and stops before any store when a row is refused.
@@ -3720,7 +3805,8 @@ set_constants_kernel(const SetConstRec* __restrict__ recs, int64_t n, const doub
     for (int x = lane; x < r.len; x += 64) t[x] = (float)row[x];
   } else {
     double* a = cdata + r.dst;
-    for (int x = lane; x < r.len; x += 64) a[x] = row[x];
+    const int step = r.two == 2 ? 2 : 1;               // (two == 2, a DIFF_SHIFT factor: the first words of its two cells, and the two scalars)
+    for (int x = lane; x < r.len; x += 64) a[step * x] = row[x];
     if (r.two) { double* b = cdata + r.dst2; for (int x = lane; x < r.len; x += 64) b[x] = row[x]; }
   }
   if (lane == 0) lb[r.factor] = __longlong_as_double(-1LL);   // stale, as set_vectors_kernel marks it

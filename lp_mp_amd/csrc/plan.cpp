@@ -119,7 +119,7 @@ bool Plan::refresh_diff_band(std::vector<LevelRange>& launches, const std::vecto
   for (LevelRange& lr : launches) {
     if (lr.kclass != KC_DIFF || lr.diff_row < 0 || (size_t)lr.diff_row + 1 >= tabs_off.size()) continue;
     const int32_t t0 = tabs_off[(size_t)lr.diff_row], t1 = tabs_off[(size_t)lr.diff_row + 1];
-    const bool band = diff_launch_banded(tabs.data() + t0, t1 - t0);
+    const bool band = !lr.diff_shift && diff_launch_banded(tabs.data() + t0, t1 - t0);
     changed = changed || band != lr.diff_band;
     lr.diff_band = band;
   }
@@ -197,7 +197,7 @@ void Plan::build(const lpmp_model& m) {
   no_diff_band = std::getenv("LPMP_NO_DIFF_BAND") != nullptr;
   max_dual = 1;
   for (int64_t f = 0; f < nf; ++f) {
-    if (f_kind[f] > LPMP_F_PAIRWISE_DIFF) fail("factor " + std::to_string(f) + ": unknown kind");
+    if (f_kind[f] > LPMP_F_PAIRWISE_DIFF && f_kind[f] != LPMP_F_PAIRWISE_DIFF_SHIFT) fail("factor " + std::to_string(f) + ": unknown kind");
     if (f_kind[f] == LPMP_F_PAIRWISE_SHARED) {
       if (f_table.empty()) f_table.assign(nf, -1);
       if (!m.f_table) fail("factor " + std::to_string(f) + ": shared pairwise factor, but the model has no f_table");
@@ -222,6 +222,17 @@ void Plan::build(const lpmp_model& m) {
         diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
         sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
       }
+    }
+    if (f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {      // D = a 1 x n entry of the same pool, any n >= 1; the shift is a cost and is not read
+      if (f_table.empty()) f_table.assign(nf, -1);
+      if (!m.f_table) fail("factor " + std::to_string(f) + ": shifted difference-indexed pairwise factor, but the model has no f_table");
+      const int32_t t = m.f_table[f];
+      if (t < 0 || t >= n_shared) fail("factor " + std::to_string(f) + ": shared table index " + std::to_string(t) + " out of range");
+      if (f_dim1[f] <= 0) fail("factor " + std::to_string(f) + ": bad dimension");
+      if (sh_dim0[t] != 1)
+        fail("factor " + std::to_string(f) + ": a shifted difference-indexed factor needs a vector (1 x n), shared table " + std::to_string(t) + " is " +
+             std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]));
+      f_table[f] = t;                                   // (sh_banded stays as it is: the band serves the banded kernel, which no shifted launch runs)
     }
     if (f_type[f] < 0 || f_type[f] >= n_ftypes) fail("factor " + std::to_string(f) + ": type out of range");
     if (f_dim0[f] <= 0 || (f_kind[f] == LPMP_F_PAIRWISE_DENSE && f_dim1[f] <= 0)) fail("factor " + std::to_string(f) + ": bad dimension");
@@ -714,7 +725,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
               (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0)) clear_flag(up_any[o]);
         if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_SHARED && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
               p.f_dim0[peer] <= 32 && p.f_dim1[peer] <= 32)) clear_flag(sh_all[o]);
-        if (!(unary_left && p.f_kind[peer] == LPMP_F_PAIRWISE_DIFF && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
+        if (!(unary_left && (p.f_kind[peer] == LPMP_F_PAIRWISE_DIFF || p.f_kind[peer] == LPMP_F_PAIRWISE_DIFF_SHIFT) && (side == 0 ? p.f_dim0[peer] : p.f_dim1[peer]) == own_d0 &&
               p.f_dim0[peer] <= BIG_MAX_LABELS && p.f_dim1[peer] <= BIG_MAX_LABELS)) clear_flag(df_all[o]);
       } else {
         clear_flag(sh_all[o]); clear_flag(df_all[o]);
@@ -728,7 +739,7 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       op.info = mt.kind | (e.role << 4) | (side << 5) | (imp << 6) | ((p.f_flags[peer] & LPMP_FF_IMPLICIT_ORIGIN) ? 1 << 7 : 0) | (p.f_kind[peer] << 8) |
                 ((mt.flags & LPMP_MF_IMPROVEMENT) ? OP_HAS_IMPROVEMENT : 0);
       if (std::max(op.len, std::max(op.pd0, op.pd1)) > SMALL_MAXD || p.f_doff[f + 1] - p.f_doff[f] > SMALL_MAXD) clear_flag(small_ok[o]);
-      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[f] != LPMP_F_PAIRWISE_SHARED && p.f_kind[f] != LPMP_F_PAIRWISE_DIFF && p.f_kind[peer] == LPMP_F_VECTOR &&
+      if (!(mt.kind == LPMP_M_UNARY_PAIRWISE && e.role == 1 && p.f_kind[f] != LPMP_F_VECTOR && p.f_kind[f] != LPMP_F_PAIRWISE_SHARED && p.f_kind[f] != LPMP_F_PAIRWISE_DIFF && p.f_kind[f] != LPMP_F_PAIRWISE_DIFF_SHIFT && p.f_kind[peer] == LPMP_F_VECTOR &&
             p.f_dim1[f] > 0 && op.len == (side == 0 ? p.f_dim0[f] : p.f_dim1[f]))) clear_flag(pw_right[o]);
       return op;
     };
@@ -740,8 +751,9 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
       const int code = op.info & 15, pk = (op.info >> 8) & 15;
       if (code == LPMP_M_UNARY_PAIRWISE) {
         const int64_t L = op.len;
-        // (a SHARED or DIFF peer: its scale; the table is on-chip)
-        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)op.pd0 * op.pd1 : ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED || pk == LPMP_F_PAIRWISE_DIFF) ? 8 : 0));
+        // (a SHARED or DIFF peer: its scale; the table is on-chip.  DIFF_SHIFT: scale and shift)
+        if (recv) return 24 * L + (pk == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)op.pd0 * op.pd1 : pk == LPMP_F_PAIRWISE_DIFF_SHIFT ? 16 :
+                                   ((pk == LPMP_F_PAIRWISE_POTTS || pk == LPMP_F_PAIRWISE_SHARED || pk == LPMP_F_PAIRWISE_DIFF) ? 8 : 0));
         return 16 * L;
       }
       return 16 * (int64_t)op.pd0;
@@ -758,10 +770,10 @@ int64_t build_ops(const Plan& p, Updates& U, OpVec& ops) {
     }
     if (n_act > 0) bytes += 16 * (p.f_doff[f + 1] - p.f_doff[f]);
     // an updated dense pairwise factor reads its own table once to compute the min-marginals it sends
-    if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF)) {   // (SHARED, DIFF: its scale)
+    if (ks > 0 && (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE || p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT)) {   // (SHARED, DIFF: its scale; DIFF_SHIFT: and its shift)
       bool sends_any = false;
       for (int64_t j = 0; j < ks; ++j) if (U.uom[u][j] != 0.0) { sends_any = true; break; }
-      if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)p.f_dim0[f] * p.f_dim1[f] : 8;
+      if (sends_any) bytes += p.f_kind[f] == LPMP_F_PAIRWISE_DENSE ? tab_entry_bytes * (int64_t)p.f_dim0[f] * p.f_dim1[f] : p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT ? 16 : 8;
     }
     __atomic_fetch_add(&U.rec_bytes[o], bytes, __ATOMIC_RELAXED);
     alg_local += bytes;
@@ -944,6 +956,8 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
         const UpdRec& r = out.recs[(size_t)i];
         const Op* o = ops.data() + r.op_begin;
         const int n_ops = lr.n_recv > 0 ? r.n_recv : r.n_send;
+        // a DIFF_SHIFT peer anywhere in the launch (receive or send): the shifted kernel, which is never banded
+        for (int q = 0; q < r.n_recv + r.n_send && !lr.diff_shift; ++q) lr.diff_shift = p.f_kind[(size_t)o[q].peer] == LPMP_F_PAIRWISE_DIFF_SHIFT;
         for (int q = 0; q < n_ops; ++q) {
           const int32_t t = p.f_table[(size_t)o[q].peer];
           if (!diff_seen[(size_t)t]) { diff_seen[(size_t)t] = 1; out.diff_tab.push_back(t); }
@@ -954,7 +968,7 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
       std::sort(out.diff_tab.begin() + t0, out.diff_tab.end());
       lr.diff_row = (int32_t)out.diff_tab_off.size() - 1;
       out.diff_tab_off.push_back((int32_t)out.diff_tab.size());
-      lr.diff_band = p.diff_launch_banded(out.diff_tab.data() + t0, (int64_t)out.diff_tab.size() - t0);
+      lr.diff_band = !lr.diff_shift && p.diff_launch_banded(out.diff_tab.data() + t0, (int64_t)out.diff_tab.size() - t0);
     }
     if (!kc_is_shared(lr.kclass)) { out.launches.push_back(lr); continue; }
     // a shared class: one launch per table-set group of the records (classify), each with the list of its distinct tables

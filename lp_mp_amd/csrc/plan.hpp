@@ -88,7 +88,7 @@ enum KClass : int32_t {
   // unaries whose active messages all go to SHARED pairwise factors (LPMP_F_PAIRWISE_SHARED): run-time label counts and
   // rectangular tables up to the padded width; the launch's distinct tables are staged in LDS once per workgroup
   KC_SHARED_4, KC_SHARED_8, KC_SHARED_16, KC_SHARED_32,
-  // unaries whose active messages all go to DIFF pairwise factors (LPMP_F_PAIRWISE_DIFF), 2 ... BIG_MAX_LABELS labels, any
+  // unaries whose active messages all go to DIFF or DIFF_SHIFT pairwise factors (LPMP_F_PAIRWISE_DIFF, ..._DIFF_SHIFT, any mix), 2 ... BIG_MAX_LABELS labels, any
   // number of ops: one wave per unary, op by op; a receive builds scale * D in LDS and reads no table from memory
   KC_DIFF,
   KC_COUNT
@@ -133,6 +133,9 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   int32_t n_sh = 0; int32_t sh_tab[SHARED_MAX_TABLES] = {};
   // class diff: every receive of every record references a banded vector (cleared by LPMP_NO_DIFF_BAND): the banded kernel
   bool diff_band = false;
+  // class diff: a record of the launch has a DIFF_SHIFT peer (LPMP_F_PAIRWISE_DIFF_SHIFT): sweep_diff_shift_kernel, never banded —
+  // structure, so new pool values (Plan::refresh_diff_band) leave it alone
+  bool diff_shift = false;
   // class diff: the launch's row of Schedule::diff_tab_off — the pool entries diff_band was decided from (-1: another class)
   int32_t diff_row = -1;
 };
@@ -286,7 +289,7 @@ struct Plan {
   std::vector<uint8_t> f_kind, f_flags;
   std::vector<int64_t> f_coff, f_doff;   // [nf+1]
   // shared pairwise tables (LPMP_F_PAIRWISE_SHARED): the pool, copied (a handful of small tables), and every factor's table
-  // (-1: neither a SHARED nor a DIFF factor; a DIFF factor's entry is its 1 x (dim0 + dim1 - 1) vector)
+  // (-1: neither a SHARED nor a DIFF / DIFF_SHIFT factor; a DIFF factor's entry is its 1 x (dim0 + dim1 - 1) vector, a DIFF_SHIFT factor's a 1 x n vector)
   int32_t n_shared = 0;
   std::vector<int64_t> sh_off; std::vector<int32_t> sh_dim0, sh_dim1; std::vector<double> sh_data;
   std::vector<int32_t> f_table;

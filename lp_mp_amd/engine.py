@@ -72,7 +72,7 @@ EXPORTS = [
     "lpmp_set_persistent_launches", "lpmp_persistent_launches", "lpmp_device_identity",
     "lpmp_plan_suggest_order", "lpmp_graph_colour_major_order", "lpmp_graph_refine_partition",
     "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
-    "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches",
+    "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches", "lpmp_get_diff_shift_launches",
     "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
     "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
     "lpmp_plan_peer_minima", "lpmp_get_peer_minima_launches",
@@ -189,6 +189,8 @@ def lib():
             L.lpmp_plan_get_diff_band.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
             L.lpmp_plan_diff_band_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
             L.lpmp_get_diff_band_launches.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "lpmp_get_diff_shift_launches"):   # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_get_diff_shift_launches.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "lpmp_plan_peer_minima"):      # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
             L.lpmp_plan_peer_minima.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
             L.lpmp_get_peer_minima_launches.argtypes = [C.c_void_p, C.c_void_p]
@@ -628,7 +630,7 @@ class Engine:
 
     def set_constants(self, factors, src=None, src_dev: Optional[int] = None, src_stride: Optional[int] = None):
         """constants of the listed PAIRWISE factors := row i of ``src`` (lpmp_set_constants): a dense table row-major, or the one
-        scalar of a Potts / SHARED / DIFF factor.  ``src``: a 2-D numpy array [n, >= longest row], or a 1-D one with ``src_stride``;
+        scalar of a Potts / SHARED / DIFF factor, or the two of a DIFF_SHIFT factor {scale, shift}.  ``src``: a 2-D numpy array [n, >= longest row], or a 1-D one with ``src_stride``;
         ``src_dev``: a raw device pointer with ``src_stride`` instead."""
         factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
         n = int(factors.shape[0])
@@ -927,6 +929,13 @@ class Engine:
                     out[KCLASS_NAMES[c]]["band_launches"] = nb.value
                     if nb.value == arrs[0][c]:
                         out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_band_kernel"
+                    if hasattr(self.L, "lpmp_get_diff_shift_launches"):
+                        # launches that touch a DIFF_SHIFT factor run the shifted kernel (never banded); the name as above
+                        ns = C.c_int64()
+                        _chk(self.L.lpmp_get_diff_shift_launches(self.h, C.addressof(ns)))
+                        out[KCLASS_NAMES[c]]["shift_launches"] = ns.value
+                        if ns.value == arrs[0][c]:
+                            out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_shift_kernel"
         return out
 
 

@@ -111,6 +111,26 @@ class diff_pairwise_factor:
         return np.float64(self.scale) * self.vec[np.asarray(x1) - np.asarray(x2) + self.dim2 - 1]
 
 
+class diff_shift_pairwise_factor:
+    """scale * D[clip(x1 - x2 + shift, 0, n - 1)] with D a vector of ANY length n of the LP's pool (LP.add_diff_table): the engine's
+    F_PAIRWISE_DIFF_SHIFT kind — two doubles per factor {scale, shift}, no table in memory.  The clamped index continues D with its
+    end values; ``shift`` is an integer with |shift| <= 2^30 (model.window_shift gives the one of two label windows).
+    ``lp.add_factor(P, dim1, dim2, table_id, scale, shift)`` in a container of its own; a ready instance is interchangeable in a
+    tabled container as a diff_pairwise_factor is.  ``set_factor_cost`` replaces scale and shift (not the vector or the dims)."""
+    kind = M.F_PAIRWISE_DIFF_SHIFT
+
+    def __init__(self, dim1: int, dim2: int, table_id: int, scale: float = 1.0, shift: int = 0):
+        self.table_id, self.dim1, self.dim2, self.scale = int(table_id), int(dim1), int(dim2), float(scale)
+        try:
+            self.shift = int(M.check_diff_shifts(shift, "diff_shift_pairwise_factor")[0])
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        self.vec = None                     # bound by LP.add_factor
+
+    def cost(self, x1, x2):
+        return np.float64(self.scale) * self.vec[np.clip(np.asarray(x1) - np.asarray(x2) + self.shift, 0, self.vec.shape[0] - 1)]
+
+
 def labeling_factor(labelings: Sequence[Sequence[int]], implicit_origin: bool):
     """labeling_factor<labelings<...>, IMPLICIT_ORIGIN> (reference include/factors/labeling_list_factor.hxx:220)."""
     labs = [tuple(l) for l in labelings]
@@ -248,8 +268,8 @@ class LP:
         return len(self._shared_tables) - 1
 
     def add_diff_table(self, D) -> int:
-        """a difference vector (d0 + d1 - 1 entries) for diff_pairwise_factor ops; returns its id in the pool it shares with
-        add_shared_table"""
+        """a difference vector for diff_pairwise_factor ops (d0 + d1 - 1 entries) or diff_shift_pairwise_factor ops (any length);
+        returns its id in the pool it shares with add_shared_table"""
         D = np.array(D, np.float64)
         if D.ndim != 1 or D.shape[0] < 1:
             raise RuntimeError("add_diff_table: a vector is expected")
@@ -285,13 +305,14 @@ class LP:
 
     def add_factor(self, container: FactorContainer, *args) -> int:
         """a factor of the container: the arguments of ``container.factor_type``, or one ready instance of it.  ONE exception to
-        "an instance of the container's type": a ready ``diff_pairwise_factor`` is also taken by a container whose factor type
-        is another tabled pairwise kind (PairwiseSimplexFactor, shared_pairwise_factor) — the three have one dual layout and
+        "an instance of the container's type": a ready ``diff_pairwise_factor`` or ``diff_shift_pairwise_factor`` is also taken by
+        a container whose factor type is another tabled pairwise kind (PairwiseSimplexFactor, shared_pairwise_factor, the other
+        difference-indexed one) — they have one dual layout and
         take the same messages, and the UAI reader (``diff_tables=True``) puts Toeplitz tables into the file's one pairwise
         container this way.  Nothing else crosses types."""
-        tabled =(M.F_PAIRWISE_DENSE, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DIFF)     # interchangeable in a container: dual = m1[dim1], m2[dim2]
+        tabled = (M.F_PAIRWISE_DENSE, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DIFF, M.F_PAIRWISE_DIFF_SHIFT)     # interchangeable in a container: dual = m1[dim1], m2[dim2]
         ready = len(args) == 1 and (isinstance(args[0], container.factor_type) or
-                                    (isinstance(args[0], diff_pairwise_factor) and getattr(container.factor_type, "kind", None) in tabled))
+                                    (isinstance(args[0], (diff_pairwise_factor, diff_shift_pairwise_factor)) and getattr(container.factor_type, "kind", None) in tabled))
         op = args[0] if ready else container.factor_type(*args)
         if getattr(op, "kind", None) == M.F_PAIRWISE_SHARED:
             if not 0 <= op.table_id < len(self._shared_tables):
@@ -300,6 +321,10 @@ class LP:
         if getattr(op, "kind", None) == M.F_PAIRWISE_DIFF:
             if not 0 <= op.table_id < len(self._shared_tables) or self._shared_tables[op.table_id].shape != (1, op.dim1 + op.dim2 - 1):
                 raise RuntimeError("diff_pairwise_factor: no difference vector of dim1 + dim2 - 1 entries under this id (LP.add_diff_table first)")
+            op.vec = self._shared_tables[op.table_id][0]
+        if getattr(op, "kind", None) == M.F_PAIRWISE_DIFF_SHIFT:
+            if not 0 <= op.table_id < len(self._shared_tables) or self._shared_tables[op.table_id].shape[0] != 1:
+                raise RuntimeError("diff_shift_pairwise_factor: no difference vector under this id (LP.add_diff_table first)")
             op.vec = self._shared_tables[op.table_id][0]
         self._pull_duals()
         self._factors.append((container, op))
@@ -395,6 +420,8 @@ class LP:
                 b.add_shared_pairwise(c.factor_no, [op.table_id], [op.scale])
             elif op.kind == M.F_PAIRWISE_DIFF:
                 b.add_diff_pairwise(c.factor_no, op.dim1, op.dim2, [op.table_id], [op.scale])
+            elif op.kind == M.F_PAIRWISE_DIFF_SHIFT:
+                b.add_diff_shift_pairwise(c.factor_no, op.dim1, op.dim2, [op.table_id], [op.scale], [op.shift])
             elif op.kind == M.F_VECTOR:
                 b.add_vector_factors(c.factor_no, op.cost[None, :], implicit_origin=op.implicit_origin)
             elif op.kind == M.F_PAIRWISE_DENSE:

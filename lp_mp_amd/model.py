@@ -15,7 +15,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 # enum lpmp_factor_kind
-F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS, F_PAIRWISE_SHARED, F_PAIRWISE_DIFF = 0, 1, 2, 3, 4
+F_VECTOR, F_PAIRWISE_DENSE, F_PAIRWISE_POTTS, F_PAIRWISE_SHARED, F_PAIRWISE_DIFF, F_PAIRWISE_DIFF_SHIFT = 0, 1, 2, 3, 4, 6      # (5 is not assigned)
+DIFF_SHIFT_MAX = 1 << 30      # |shift| of a DIFF_SHIFT factor (include/lpmp_model.h)
 FF_IMPLICIT_ORIGIN = 1
 # enum lpmp_msg_kind
 M_UNARY_PAIRWISE, M_LABELING, M_MINNORM = 0, 1, 2
@@ -98,11 +99,12 @@ class FlatModel:
     # shared pairwise tables (F_PAIRWISE_SHARED: cost = scale * V[a][b], the factor's one const double is the scale):
     # table t is sh_dim0[t] x sh_dim1[t], row-major at sh_data[sh_off[t]]; f_table[f] = table of factor f (-1: none).
     # F_PAIRWISE_DIFF: cost = scale * D[a - b + d1 - 1], D = entry f_table[f] of the same pool, a [1, d0 + d1 - 1] table
+    # F_PAIRWISE_DIFF_SHIFT: two const doubles {scale, shift}; cost = scale * D[clip(a - b + shift, 0, n - 1)], D a [1, n] entry, any n
     sh_off: Optional[np.ndarray] = None       # [n_tables + 1] int64
     sh_dim0: Optional[np.ndarray] = None      # [n_tables] int32
     sh_dim1: Optional[np.ndarray] = None
     sh_data: Optional[np.ndarray] = None      # float64, host memory always
-    f_table: Optional[np.ndarray] = None      # [n_factors] int32, None when no factor is SHARED or DIFF
+    f_table: Optional[np.ndarray] = None      # [n_factors] int32, None when no factor is SHARED, DIFF or DIFF_SHIFT
     _keep: list = field(default_factory=list, repr=False)
 
     def __getstate__(self):          # the ctypes views of c_struct() are per process and rebuilt on demand
@@ -121,12 +123,13 @@ class FlatModel:
     def const_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where((self.f_kind == F_PAIRWISE_POTTS) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF), 1, 0))
+        return np.where(self.f_kind == F_PAIRWISE_DENSE, d0 * d1, np.where(self.f_kind == F_PAIRWISE_DIFF_SHIFT, 2,
+                        np.where((self.f_kind == F_PAIRWISE_POTTS) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF), 1, 0)))
 
     def dual_sizes(self) -> np.ndarray:
         d0 = self.f_dim0.astype(np.int64)
         d1 = self.f_dim1.astype(np.int64)
-        return np.where((self.f_kind == F_PAIRWISE_DENSE) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF), d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
+        return np.where((self.f_kind == F_PAIRWISE_DENSE) | (self.f_kind == F_PAIRWISE_SHARED) | (self.f_kind == F_PAIRWISE_DIFF) | (self.f_kind == F_PAIRWISE_DIFF_SHIFT), d0 + d1, np.where(self.f_kind == F_PAIRWISE_POTTS, 2 * d0, d0))
 
     def dual_offsets(self) -> np.ndarray:
         return np.concatenate([[0], np.cumsum(self.dual_sizes())]).astype(np.int64)
@@ -149,17 +152,18 @@ class FlatModel:
 
     @property
     def has_diff(self) -> bool:
-        return bool(np.any(self.f_kind == F_PAIRWISE_DIFF))
+        """any difference-indexed factor, plain (DIFF) or shifted (DIFF_SHIFT)"""
+        return bool(np.any((self.f_kind == F_PAIRWISE_DIFF) | (self.f_kind == F_PAIRWISE_DIFF_SHIFT)))
 
     def _expand(self, which: int, name: str) -> "FlatModel":
-        """the factors of kind ``which`` (SHARED or DIFF) replaced by DENSE factors; the pool goes with the last factor
+        """the factors of kind ``which`` (SHARED, or DIFF: both difference-indexed kinds) replaced by DENSE factors; the pool goes with the last factor
         that uses it.  While factors of the other pooled kind remain, the pool stays WHOLE: the entries that only the expanded
         factors used are kept (``n_shared_tables`` still counts them, an upload still carries them), so that the table ids of
         the remaining factors do not move."""
         import dataclasses
-        other = F_PAIRWISE_DIFF if which == F_PAIRWISE_SHARED else F_PAIRWISE_SHARED
-        keep_pool = bool(np.any(self.f_kind == other))
-        is_exp = self.f_kind == which
+        is_diff = (self.f_kind == F_PAIRWISE_DIFF) | (self.f_kind == F_PAIRWISE_DIFF_SHIFT)
+        is_exp = is_diff if which == F_PAIRWISE_DIFF else self.f_kind == F_PAIRWISE_SHARED
+        keep_pool = bool(np.any(((self.f_kind == F_PAIRWISE_SHARED) | is_diff) & ~is_exp))
         if keep_pool:
             pool = dict(f_table=np.where(is_exp, np.int32(-1), self.f_table).astype(np.int32), _keep=[])
         else:
@@ -183,7 +187,11 @@ class FlatModel:
                 V = self.shared_table(int(self.f_table[f]))
                 if which == F_PAIRWISE_DIFF:
                     d0, d1 = int(self.f_dim0[f]), int(self.f_dim1[f])
-                    V = V.reshape(-1)[np.arange(d0)[:, None] - np.arange(d1)[None, :] + (d1 - 1)]
+                    k = np.arange(d0, dtype=np.int64)[:, None] - np.arange(d1, dtype=np.int64)[None, :]
+                    if self.f_kind[f] == F_PAIRWISE_DIFF_SHIFT:     # the clamped index, the shift converted as the device converts it
+                        V = V.reshape(-1)[np.clip(k + diff_shift_int(self.const_data[old_off[f] + 1]), 0, V.size - 1)]
+                    else:
+                        V = V.reshape(-1)[k + (d1 - 1)]
                 const[new_off[f]: new_off[f + 1]] = (np.float64(self.const_data[old_off[f]]) * V).reshape(-1)
                 f += 1
             else:
@@ -201,8 +209,9 @@ class FlatModel:
         return self._expand(F_PAIRWISE_SHARED, "expand_shared")
 
     def expand_diff(self) -> "FlatModel":
-        """the same model with every DIFF factor replaced by a DENSE factor whose table is
-        ``np.float64(scale) * D[a - b + d1 - 1]`` — the yardstick of the kind, as expand_shared() is for SHARED factors"""
+        """the same model with every DIFF and every DIFF_SHIFT factor replaced by a DENSE factor whose table is
+        ``np.float64(scale) * D[a - b + d1 - 1]`` (DIFF_SHIFT: ``D[clip(a - b + diff_shift_int(shift), 0, n - 1)]``) — the yardstick
+        of the two kinds, as expand_shared() is for SHARED factors"""
         return self._expand(F_PAIRWISE_DIFF, "expand_diff")
 
     def with_f32_tables(self) -> "FlatModel":
@@ -325,6 +334,57 @@ def truncated_linear(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray
     (one multiply per entry: these host values are the values)"""
     k = np.abs(np.arange(d0 + d1 - 1, dtype=np.float64) - (d1 - 1))
     return np.minimum(np.float64(slope) * k, np.float64(trunc))
+
+
+def diff_shift_int(shift) -> int:
+    """the shift of a DIFF_SHIFT factor as the device converts the double (kernels.hip, diff_shift_int): NaN -> 0, saturated to
+    [-2^30, 2^30], truncated toward zero.  A valid shift (ModelBuilder refuses anything else) is its own value."""
+    x = float(shift)
+    if x != x:
+        return 0
+    return int(min(max(x, -float(DIFF_SHIFT_MAX)), float(DIFF_SHIFT_MAX)))
+
+
+def check_diff_shifts(shifts, who: str) -> np.ndarray:
+    """``shifts`` as doubles; anything but integer values with |s| <= 2^30 is refused (the C ABI does not look at them)"""
+    s = np.atleast_1d(np.asarray(shifts, np.float64))
+    if not np.all(np.isfinite(s)) or np.any(s != np.trunc(s)) or np.any(np.abs(s) > DIFF_SHIFT_MAX):
+        raise ValueError(who + ": a shift is an integer-valued number with |shift| <= 2^30")
+    return s
+
+
+def truncated_linear_compact(slope: float, trunc: float) -> tuple:
+    """(D, zero_index): min(slope * |k|, trunc) for k = -T ... T with T the first difference at which the truncation holds —
+    2 T + 1 entries whatever the label counts.  For DIFF_SHIFT factors: the clamped index continues D with its end values, which
+    ARE the truncation, so the factor is the full-range potential exactly.  zero_index = T is where difference 0 sits
+    (window_shift).  The entries are those of truncated_linear, to the bit."""
+    slope, trunc = np.float64(slope), np.float64(trunc)
+    if not (slope > 0 and trunc >= 0 and np.isfinite(slope) and np.isfinite(trunc)):
+        raise ValueError("truncated_linear_compact: slope > 0 and trunc >= 0 are expected")
+    T = 0
+    while slope * np.float64(T) < trunc:
+        T += 1
+    k = np.abs(np.arange(-T, T + 1, dtype=np.float64))
+    return np.minimum(slope * k, trunc), T
+
+
+def truncated_quadratic_compact(slope: float, trunc: float) -> tuple:
+    """the quadratic twin: min(slope * k^2, trunc) for k = -T ... T, the entries of truncated_quadratic to the bit"""
+    slope, trunc = np.float64(slope), np.float64(trunc)
+    if not (slope > 0 and trunc >= 0 and np.isfinite(slope) and np.isfinite(trunc)):
+        raise ValueError("truncated_quadratic_compact: slope > 0 and trunc >= 0 are expected")
+    T = 0
+    while slope * (np.float64(T) * np.float64(T)) < trunc:
+        T += 1
+    k = np.arange(-T, T + 1, dtype=np.float64)
+    return np.minimum(slope * (k * k), trunc), T
+
+
+def window_shift(c_left, c_right, zero_index):
+    """the shift of a DIFF_SHIFT factor between a variable that holds the absolute labels c_left, c_left + 1, ... (side 0) and
+    one that holds c_right, ... (side 1), for a vector whose entry ``zero_index`` is difference 0: label pair (a, b) stands for
+    the difference (a + c_left) - (b + c_right), which is entry a - b + shift.  Arrays give one shift per factor."""
+    return np.asarray(c_left, np.int64) - np.asarray(c_right, np.int64) + np.int64(zero_index)
 
 
 def truncated_quadratic(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray:
@@ -463,8 +523,8 @@ class ModelBuilder:
         return ids
 
     def add_diff_table(self, vec) -> int:
-        """a difference vector D of d0 + d1 - 1 entries (add_diff_pairwise: cost(a, b) = scale * D[a - b + d1 - 1]), stored as a
-        [1, n] entry of the shared pool; returns its id"""
+        """a difference vector D, stored as a [1, n] entry of the shared pool; returns its id.  Any length n >= 1: add_diff_pairwise
+        (cost(a, b) = scale * D[a - b + d1 - 1]) takes the vectors of d0 + d1 - 1 entries, add_diff_shift_pairwise any"""
         vec = np.ascontiguousarray(vec, np.float64)
         if vec.ndim != 1 or vec.shape[0] < 1:
             raise ValueError("add_diff_table: a vector is expected")
@@ -487,6 +547,29 @@ class ModelBuilder:
             raise ValueError("add_diff_pairwise: a %d x %d factor needs difference vectors of %d entries" % (d0, d1, d0 + d1 - 1))
         n = table_ids.shape[0]
         ids = self._add_factors(n, ftype, F_PAIRWISE_DIFF, 0, d0, d1, scales, None if self.skip_dual else np.zeros((n, d0 + d1)))
+        self._f_table.append((int(ids[0]), table_ids.copy()))
+        return ids
+
+    def add_diff_shift_pairwise(self, ftype: int, d0: int, d1: int, table_ids, scales, shifts) -> np.ndarray:
+        """d0 x d1 pairwise factors cost(a, b) = scales[i] * D[clip(a - b + shifts[i], 0, n - 1)] with D = vector table_ids[i] of
+        ANY length n: every factor holds two doubles {scale, shift}.  ``scales`` as for add_diff_pairwise; ``shifts`` are integers
+        with |shift| <= 2^30 (window_shift gives the one of two label windows)."""
+        table_ids = np.atleast_1d(np.asarray(table_ids, np.int32))
+        n = table_ids.shape[0]
+        scales = np.atleast_1d(np.asarray(scales, np.float64))
+        shifts = check_diff_shifts(shifts, "add_diff_shift_pairwise")
+        if scales.shape[0] == 1 and n > 1:
+            scales = np.full(n, scales[0])
+        if shifts.shape[0] == 1 and n > 1:
+            shifts = np.full(n, shifts[0])
+        if table_ids.shape != scales.shape or table_ids.shape != shifts.shape or n == 0:
+            raise ValueError("add_diff_shift_pairwise: one table id, one scale and one shift per factor")
+        if table_ids.min() < 0 or table_ids.max() >= len(self._shared):
+            raise ValueError("add_diff_shift_pairwise: table id out of range")
+        d0, d1 = int(d0), int(d1)
+        if d0 < 1 or d1 < 1 or any(self._shared[t].shape[0] != 1 for t in np.unique(table_ids)):
+            raise ValueError("add_diff_shift_pairwise: positive dims and difference VECTORS (add_diff_table) are expected")
+        ids = self._add_factors(n, ftype, F_PAIRWISE_DIFF_SHIFT, 0, d0, d1, np.stack([scales, shifts], 1), None if self.skip_dual else np.zeros((n, d0 + d1)))
         self._f_table.append((int(ids[0]), table_ids.copy()))
         return ids
 

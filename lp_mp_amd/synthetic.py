@@ -136,7 +136,7 @@ def grid_edges(H: int, W: int) -> Tuple[np.ndarray, np.ndarray]:
 def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unaries: np.ndarray,
               tables: Optional[np.ndarray] = None, potts: Optional[np.ndarray] = None,
               device_const: bool = False, compute_primal: bool = False, device_dual: bool = False,
-              shared: Optional[tuple] = None, diff: Optional[tuple] = None) -> M.FlatModel:
+              shared: Optional[tuple] = None, diff: Optional[tuple] = None, diff_shift: Optional[tuple] = None) -> M.FlatModel:
     """MRF over variables 0..n_vars-1 (already in variable order) with edges (i<j required).
     ``compute_primal``: the unary FactorContainer's COMPUTE_PRIMAL_SOLUTION flag (as in LP_MP-MRF's FMC_SRMP);
     needed for the ...AndPrimal passes.
@@ -144,7 +144,9 @@ def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unari
     tables are not materialised on the host (they are generated in HBM; see Engine.upload); with ``device_dual`` neither are the
     duals (``unaries`` is ignored: the caller fills the device buffer it hands to Engine.upload).
     ``shared`` = (tables [T,L,L], table id per edge [E], scale per edge [E]): shared pairwise factors, cost = scale * V[a][b].
-    ``diff`` = (vectors [T,2L-1], vector id per edge [E], scale per edge [E]): difference-indexed factors, cost = scale * D[a - b + L - 1]."""
+    ``diff`` = (vectors [T,2L-1], vector id per edge [E], scale per edge [E]): difference-indexed factors, cost = scale * D[a - b + L - 1].
+    ``diff_shift`` = (vectors: [T,n] or a list of vectors of any lengths, vector id per edge [E], scale per edge [E], shift per edge
+    [E]): shifted difference-indexed factors, cost = scale * D[clip(a - b + shift, 0, n - 1)]."""
     edge_i = np.asarray(edge_i, np.int64)
     edge_j = np.asarray(edge_j, np.int64)
     assert np.all(edge_i < edge_j)
@@ -163,6 +165,11 @@ def mrf_model(n_vars: int, L: int, edge_i: np.ndarray, edge_j: np.ndarray, unari
         df_vecs, df_ids, df_scales = diff
         first = [b.add_diff_table(t) for t in np.asarray(df_vecs, np.float64)][0]
         p = b.add_diff_pairwise(1, L, L, first + np.asarray(df_ids, np.int32), df_scales)
+    elif diff_shift is not None:
+        assert not device_const and potts is None and tables is None
+        ds_vecs, ds_ids, ds_scales, ds_shifts = diff_shift
+        first = [b.add_diff_table(t) for t in ds_vecs][0]
+        p = b.add_diff_shift_pairwise(1, L, L, first + np.asarray(ds_ids, np.int32), ds_scales, ds_shifts)
     elif potts is not None:
         assert not device_const
         p = b.add_potts_pairwise(1, L, potts)
@@ -188,13 +195,15 @@ def grid_model(H: int, W: int, L: int, pairwise: str = "dense", order: str = "ro
                unaries: Optional[np.ndarray] = None, tables: Optional[np.ndarray] = None,
                potts: Optional[np.ndarray] = None, device_const: bool = False, compute_primal: bool = False,
                n_tables: int = 2, shared_tables: Optional[np.ndarray] = None, scales: Optional[np.ndarray] = None,
-               diff_tables: Optional[np.ndarray] = None) -> M.FlatModel:
+               diff_tables: Optional[np.ndarray] = None, shifts: Optional[np.ndarray] = None) -> M.FlatModel:
     """H x W grid MRF.  Random costs are U(0,1) from the counter-based generator: unaries first
     (variable order), then the pairwise data edge by edge (edge order of grid_edges).
     ``pairwise="shared"``: ``n_tables`` shared L x L tables (the generator's next n_tables L^2 values, or ``shared_tables``
     [n_tables, L, L]); edge e of grid_edges uses table e mod n_tables with scale 0.5 + 1.5 u (the values after the tables), or ``scales`` [E].
     ``pairwise="diff"``: ``n_tables`` difference vectors of 2L - 1 entries (the generator's next n_tables (2L - 1) values, or
-    ``diff_tables`` [n_tables, 2L - 1]); edge e uses vector e mod n_tables, scales as for "shared"."""
+    ``diff_tables`` [n_tables, 2L - 1]); edge e uses vector e mod n_tables, scales as for "shared".
+    ``pairwise="diff_shift"``: the vectors and scales of "diff" (``diff_tables``: [n_tables, n] or a list of vectors of any
+    lengths) and a shift per edge, ``shifts`` [E] (default L - 1 everywhere: with the default vectors, the "diff" grid)."""
     var = grid_variable_order(H, W, order).reshape(-1)
     a, bb = grid_edges(H, W)
     va, vb = var[a], var[bb]
@@ -215,6 +224,15 @@ def grid_model(H: int, W: int, L: int, pairwise: str = "dense", order: str = "ro
         return mrf_model(n, L, i, j, unaries, compute_primal=compute_primal, shared=_shared_costs(E, L, n * L, seed, n_tables, shared_tables, scales))
     if pairwise == "diff":
         return mrf_model(n, L, i, j, unaries, compute_primal=compute_primal, diff=_diff_costs(E, L, n * L, seed, n_tables, diff_tables, scales))
+    if pairwise == "diff_shift":
+        if diff_tables is None or isinstance(diff_tables, np.ndarray):
+            vecs, ids, sc = _diff_costs(E, L, n * L, seed, n_tables, diff_tables, scales)
+        else:
+            vecs = [np.asarray(v, np.float64) for v in diff_tables]
+            ids = (np.arange(E) % len(vecs)).astype(np.int32)
+            sc = 0.5 + 1.5 * u01(E, seed, n * L + sum(v.size for v in vecs)) if scales is None else np.asarray(scales, np.float64)
+        sh = np.full(E, L - 1, np.int64) if shifts is None else np.asarray(shifts)
+        return mrf_model(n, L, i, j, unaries, compute_primal=compute_primal, diff_shift=(vecs, ids, sc, sh))
     raise ValueError(pairwise)
 
 
