@@ -75,11 +75,13 @@ class DevBuf {
   // a buffer that is refilled in place: a new allocation only when n exceeds the capacity, then with a quarter to spare
   void grow(size_t n) { if (n > cap_) alloc(n + n / 4 + 16); }
 };
-struct GraphExec {   // an instantiated graph, destroyed with its owner
+struct GraphExec {   // an instantiated graph, destroyed with its owner; move-only
   hipGraphExec_t g = nullptr;
   GraphExec() = default;
   GraphExec(const GraphExec&) = delete;
   GraphExec& operator=(const GraphExec&) = delete;
+  GraphExec(GraphExec&& o) noexcept : g(o.g) { o.g = nullptr; }
+  GraphExec& operator=(GraphExec&& o) noexcept { if (this != &o) { reset(); g = o.g; o.g = nullptr; } return *this; }
   ~GraphExec() { reset(); }
   void reset() { if (g) { (void)hipGraphExecDestroy(g); g = nullptr; } }
 };
@@ -240,57 +242,80 @@ static void plan_rotation(lpmp_plan* pl, int mode) {
   if (!ok) bf = Schedule();
 }
 
+// the uploaded model and its parts: internal to the engine's host code
+namespace lpmp {
+namespace host {
 
-struct lpmp_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipStream_t capture_stream = nullptr;   // graphs are captured here (the caller's stream may be the legacy default stream, which cannot capture) and replayed on `stream`
+// joined passes as one persistent launch: expansions of RotationInfo, by mode and pass count
+struct RotChain {
+  DevChain dc; int n_steps = 0; int64_t factors = 0, recv = 0, bytes = 0; uint64_t last_use = 0; size_t dev_bytes = 0;
+  // periodic form (rotation_chain): dc holds the TEMPLATE of n_tmpl passes whose tickets [per_begin, per_begin + per_len) are
+  // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
+  bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
+  bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
+  int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
+};
+// the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
+struct RotOrder { bool have_geo = false; RotGeometry geo; TileSet tiles; };
+// conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
+// their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
+struct DevDecode {
+  struct Launch { int64_t first, count; int32_t width, level; };
+  bool have = false;
+  DevBuf<DecodeRec> recs; DevBuf<DecodeLink> links;
+  std::vector<Launch> launches;
+  void release() { have = false; recs.reset(); links.reset(); launches.clear(); }
+};
+struct LbRun { int cls; int64_t first, count; };
+// speculative passes: the open batch and what the engine has learnt of the caller on this model; a fresh value
+// is "no batch, nothing learnt, no buffers"
+struct SpecBatch {
+  int n = 0, pos = 0, mode = -1;     // the open batch: n passes were launched as one chain, the caller has asked for pos of them
+  int run_len = 0, learned = 0, last_batch = 0;   // plain single passes since the last other call; length of the previous such run
+  bool lb_ready = false; std::vector<double> lb;   // bounds after passes 1 ... n - 1 of the batch
+  DevBuf<double> d_snap;             // duals (+ tracked bounds) at the start of the batch
+  DevBuf<double> d_hist;             // (n - 1) rows of per-factor bounds
+  DevBuf<double> d_hpart;            // partial sums of those rows
+  bool snap_lb_stale = false;
+};
+
+// Everything that belongs to the uploaded model.  A default-constructed value is "no model" (plan empty); lpmp_upload_model builds
+// one as a local and commits it by move, so a refused upload leaves nothing behind, and a member added here needs no line anywhere
+// else to be dropped with its model.
+struct ModelState {
   std::unique_ptr<lpmp_plan> plan;
   // the base pointers the kernels use, and beside each the engine's own allocation: empty when the caller's memory is borrowed (LPMP_MEM_DEVICE)
   double* d_dual = nullptr; DevBuf<double> dual_buf; bool own_dual() const { return dual_buf.get() != nullptr; }
   double* d_const = nullptr; DevBuf<double> const_buf;
   DevBuf<int32_t> d_tabs;
   DevBuf<LbRec> d_lbrecs;
-  DevBuf<double> d_lb, d_part; double* h_part = nullptr;
+  DevBuf<double> d_lb, d_part;
   // tracked per-factor lower bounds (kernels.hip): d_lb[f] is valid or NaN; lb_all_stale: recompute everything
-  DevBuf<int32_t> d_stale; DevBuf<unsigned long long> d_stale_n; unsigned long long* h_stale_n = nullptr;
+  DevBuf<int32_t> d_stale; DevBuf<unsigned long long> d_stale_n;
   bool lb_all_stale = true;
-  bool use_lb_tracking = true;
-  int64_t last_lb_recomputed = -1;   // factor bounds the last evaluation had to recompute (-1: none evaluated yet)
   // primal rounding: the factors' primal_ members, the lazily initialised set, the message links
   DevBuf<int32_t> d_primal;
   DevBuf<PrimalInit> d_pinit; int64_t n_pinit = 0;
   DevBuf<PrimalLink> d_plinks; int64_t n_plinks = 0, n_pprop = 0;   // all messages; the first n_pprop propagate labels
   DevBuf<int32_t> d_pw_unary;     // [2 nf] the unary on each side of a pairwise factor; only with pairwise types that round themselves
-  DevBuf<double> d_pcost; DevBuf<int> d_pbad; int* h_pbad = nullptr;
-  char* pinned = nullptr;         // this engine's block of device-written host words (from the pool)
+  DevBuf<double> d_pcost; DevBuf<int> d_pbad;
   uint64_t primal_t = 0;          // primal_access_ of every factor a primal pass touches (they move together)
   bool have_primal = false;
   bool primal_unset_only = false; // d_primal holds only the unset labels of a model the rounding code refuses (lpmp_readout_labels)
-  bool primal_pass = false;       // the launches being issued belong to an ...AndPrimal pass
-  // conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
-  // their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
-  struct DevDecode {
-    struct Launch { int64_t first, count; int32_t width, level; };
-    bool have = false;
-    DevBuf<DecodeRec> recs; DevBuf<DecodeLink> links;
-    std::vector<Launch> launches;
-    void release() { have = false; recs.reset(); links.reset(); launches.clear(); }
-  } decode[2];
+  DevDecode decode[2];
   // rows layout (kernels.hip, rows_copy_kernel): dense pairwise factors live as [table | m1 | m2] rows of d_rows; the packed
   // dual array keeps the vector factors and is the format of every call that hands duals over.  packed_stale: the rows hold
   // newer message vectors than the packed array; rows_stale: the packed array was (or may have been) written by the caller
-  bool want_rows = false, rows = false, packed_stale = false, rows_stale = false;
+  bool rows = false, packed_stale = false, rows_stale = false;
   DevBuf<double> d_rows; DevBuf<RowRec> d_rowrecs; int64_t n_rowrecs = 0;
   // shared pairwise tables: [two words {scale, table offset} per SHARED factor | the pool], an allocation of the engine's own
   // that the SHARED factors' device const offsets point into (Plan::dev_coff), and the pool's tables as the shared classes' kernel sees them
   DevBuf<double> d_shared; DevBuf<ShTableDesc> d_sh_desc;
   int nt_flag = 0;                // SWEEP_NT when tables + duals are far larger than L2 + Infinity Cache
-  // table precision (lpmp_set_table_precision): want_tab applies to the next upload, tab_prec is the uploaded model's; with an f32
-  // mode the dense tables live as floats in d_tab32 (every table 16-byte aligned), the DENSE factors' device const offsets point
+  // table precision (lpmp_set_table_precision): the engine's want_tab applies to the next upload, tab_prec is the uploaded model's; with
+  // an f32 mode the dense tables live as floats in d_tab32 (every table 16-byte aligned), the DENSE factors' device const offsets point
   // there (Plan::dev_coff, still in 8-byte units relative to d_const) and every launch carries tab_flag = SWEEP_TAB32
-  int want_tab = LPMP_TABLES_F64, tab_prec = LPMP_TABLES_F64, tab_flag = 0;
+  int tab_prec = LPMP_TABLES_F64, tab_flag = 0;
   DevBuf<float> d_tab32;
   bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
   // new costs on the planned model (lpmp_upload_costs, lpmp_set_vectors, lpmp_zero_pairwise_duals): everything below is a function
@@ -306,71 +331,29 @@ struct lpmp_engine {
   // remembers the one it was made for), d_readout is where a call with a HOST destination lets the kernel write before the copy
   uint64_t model_gen = 0;
   DevBuf<double> d_readout;
-  struct LbRun { int cls; int64_t first, count; };
   std::vector<LbRun> lb_runs;
   DevSchedule sched[2][LPMP_REPAM_COUNT];
   bool have_sched[LPMP_REPAM_COUNT] = {false, false, false, false};
   DevSchedule sched_pass[LPMP_REPAM_COUNT];            // fused forward+backward (ComputePass)
   DevSchedule sched_bf[LPMP_REPAM_COUNT];              // fused backward+forward: its middle step joins two passes
   DevSchedule sched_part[2]; bool have_part[2] = {false, false};   // compute_partition_pass / compute_overlapping_partition_pass as ONE sequence
-  int inner_iterations = 5;                            // --innerIteration (reference LP_MP.h:590)
   bool rotation_ok[LPMP_REPAM_COUNT] = {false, false, false, false};
   bool have_pass[LPMP_REPAM_COUNT] = {false, false, false, false};
-  bool use_fused = true;
-  bool use_rotation = true;
+  bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
   std::vector<std::unique_ptr<DevSchedule>> custom;   // prepared iterator-range passes
   DevSchedule scratch;                                 // the one-off schedule of lpmp_compute_pass_custom
   int mode = -1;
-  int rtype = 0;   // enum lpmp_reparametrization_type
-  bool use_graph = true;
-  bool use_chain = true;          // deep single-class schedules as one persistent launch (LPMP_NO_CHAIN=1: graph replay)
-  DevBuf<int32_t> d_chain_abort; bool chain_ran = false;
-  // joined passes as one persistent launch: expansions of RotationInfo, by mode and pass count
-  struct RotChain {
-    DevChain dc; int n_steps = 0; int64_t factors = 0, recv = 0, bytes = 0; uint64_t last_use = 0; size_t dev_bytes = 0;
-    // periodic form (rotation_chain): dc holds the TEMPLATE of n_tmpl passes whose tickets [per_begin, per_begin + per_len) are
-    // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
-    bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
-    bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
-    int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
-  };
-  // the ticket lists of a pass count are device memory (C3, 32 passes: ~350 MB): the cache of built chains is bounded in
-  // BYTES over all modes (default 2 GiB, LPMP_CHAIN_CACHE_MB; least recently used first), lpmp_chain_cache_bytes reports it
-  uint64_t rot_clock = 0;
-  size_t rot_cache_bytes = 0, rot_cache_limit = (size_t)2 << 30;
+  // the ticket lists of a pass count are device memory (C3, 32 passes: ~350 MB): the cache of built chains is bounded in BYTES
+  // over all modes (the engine's rot_cache_limit; least recently used first), lpmp_chain_cache_bytes reports it
+  size_t rot_cache_bytes = 0;
   std::map<int, RotChain> rot_chain[LPMP_REPAM_COUNT];
-  // ---- speculative passes (lpmp_set_speculation, include/lpmp_engine.h) ----
-  struct Spec {
-    int max_depth = 0;                 // 0: off
-    int n = 0, pos = 0, mode = -1;     // the open batch: n passes were launched as one chain, the caller has asked for pos of them
-    int run_len = 0, learned = 0, last_batch = 0;   // plain single passes since the last other call; length of the previous such run
-    bool lb_ready = false; std::vector<double> lb;   // bounds after passes 1 ... n - 1 of the batch
-    DevBuf<double> d_snap;             // duals (+ tracked bounds) at the start of the batch
-    DevBuf<double> d_hist;             // (n - 1) rows of per-factor bounds
-    DevBuf<double> d_hpart;            // partial sums of those rows
-    bool snap_lb_stale = false;
-    int64_t batches = 0, passes_launched = 0, passes_used = 0, rollbacks = 0, alloc_failures = 0;
-    void release() {
-      d_snap.reset(); d_hist.reset(); d_hpart.reset();
-      n = pos = 0; mode = -1; run_len = learned = last_batch = 0; lb_ready = false;
-    }
-  } spec;
-  bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
+  RotOrder rot_order[LPMP_REPAM_COUNT];
   // peer minima (kernels.hip, dense_pq_*_body): 32 doubles per factor, written by the W steps of a joined launch and read by its K / T
   // steps — never across calls (every call starts with H and W), so no upload invalidates it.  Allocated with the first eligible
-  // joined launch, freed with the model; not part of the chain cache.  LPMP_NO_PEER_MINIMA=1: every launch in the old form
-  bool use_peer_minima = true;
-  int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
+  // joined launch, freed with the model; not part of the chain cache
   DevBuf<double> d_peerq;
-  bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
-  bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
-  RotSettings rot_opts;            // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
-  // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
-  // unset: the engine's own choice (tiles of 1024 blocks where the band order is down to depth 2 or does not fit at all)
-  int rot_tiles = 0; bool rot_tiles_set = false;
-  // the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
-  struct RotOrder { bool have_geo = false; RotGeometry geo; TileSet tiles; };
-  RotOrder rot_order[LPMP_REPAM_COUNT];
+  SpecBatch batch;
+
   // drop the joined-pass launches of a mode (or of all modes) and their order
   void release_rot_chains(int only_mode = -1) {
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
@@ -380,12 +363,6 @@ struct lpmp_engine {
       rot_order[m] = RotOrder();
     }
   }
-  bool timing = false;
-  ClassTiming ct[KC_COUNT];
-  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false; };   // band: sweep_diff_band_kernel; shift: sweep_diff_shift_kernel
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> event_pool;
-
   // every device schedule of the engine (built-in, partition, prepared iterator-range passes, the scratch one)
   template <class F>
   void for_each_schedule(F&& f) {
@@ -396,7 +373,6 @@ struct lpmp_engine {
   }
   void release_primal() {
     d_primal.reset(); d_pinit.reset(); d_plinks.reset(); d_pw_unary.reset(); d_pcost.reset(); d_pbad.reset();
-    h_pbad = nullptr;
     have_primal = false; primal_unset_only = false; primal_t = 0; n_pinit = n_plinks = n_pprop = 0;
   }
   // the built-in schedules (everything but the caller's prepared iterator-range passes)
@@ -406,32 +382,53 @@ struct lpmp_engine {
     for (int k = 0; k < 2; ++k) { sched_part[k].release(); have_part[k] = false; }
     release_rot_chains();
   }
-  void release_model() {
-    release_schedules();
-    deep_note_given = false;
-    custom.clear();
-    scratch.release();
-    dual_buf.reset(); const_buf.reset();
-    d_dual = nullptr; d_const = nullptr;
-    d_tabs.reset(); d_rows.reset(); d_rowrecs.reset(); d_shared.reset(); d_sh_desc.reset();
-    d_tab32.reset(); tab_prec = LPMP_TABLES_F64; tab_flag = 0;
-    d_peerq.reset();
-    schedules_built = 0; const_bad = false; tab_compact = false; sh_cells.clear();
-    d_setrecs.reset(); d_setsrc.reset(); d_setcrecs.reset(); d_zero.reset(); n_zero = -1;
-    model_gen = 0; d_readout.reset();
-    rows = packed_stale = rows_stale = false; n_rowrecs = 0;
-    d_lbrecs.reset(); d_lb.reset(); d_part.reset();
-    h_part = nullptr;
-    release_primal();
-    for (auto& d : decode) d.release();
-    d_stale.reset(); d_stale_n.reset();
-    h_stale_n = nullptr;
-    lb_all_stale = true;
-    lb_runs.clear();
-    plan.reset();
-    mode = -1;
-    spec.release();
-  }
+};
+
+}  // namespace host
+}  // namespace lpmp
+using namespace lpmp::host;
+
+struct lpmp_engine {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  hipStream_t capture_stream = nullptr;   // graphs are captured here (the caller's stream may be the legacy default stream, which cannot capture) and replayed on `stream`
+  ModelState model;
+  void release_model() { model = ModelState(); deep_note_given = false; }
+  // this engine's block of device-written host words (from the pool, taken with the first upload) and the words in it
+  char* pinned = nullptr; double* h_part = nullptr; unsigned long long* h_stale_n = nullptr; int* h_pbad = nullptr;
+  bool use_lb_tracking = true;
+  int64_t last_lb_recomputed = -1;   // factor bounds the last evaluation had to recompute (-1: none evaluated yet)
+  bool primal_pass = false;       // the launches being issued belong to an ...AndPrimal pass
+  bool want_rows = false;         // rows layout for the next upload (lpmp_set_rows_layout)
+  int want_tab = LPMP_TABLES_F64; // table precision for the next upload (lpmp_set_table_precision)
+  int inner_iterations = 5;                            // --innerIteration (reference LP_MP.h:590)
+  bool use_fused = true;
+  bool use_rotation = true;
+  int rtype = 0;   // enum lpmp_reparametrization_type
+  bool use_graph = true;
+  bool use_chain = true;          // deep single-class schedules as one persistent launch (LPMP_NO_CHAIN=1: graph replay)
+  DevBuf<int32_t> d_chain_abort; bool chain_ran = false;
+  uint64_t rot_clock = 0;
+  size_t rot_cache_limit = (size_t)2 << 30;   // bound of ModelState::rot_cache_bytes (default 2 GiB, LPMP_CHAIN_CACHE_MB)
+  // ---- speculative passes (lpmp_set_speculation, include/lpmp_engine.h): the setting and the lifetime counters ----
+  struct Spec {
+    int max_depth = 0;                 // 0: off
+    int64_t batches = 0, passes_launched = 0, passes_used = 0, rollbacks = 0, alloc_failures = 0;
+  } spec;
+  bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
+  bool use_peer_minima = true;        // LPMP_NO_PEER_MINIMA=1: every joined launch in the old form (ModelState::d_peerq)
+  int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
+  bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
+  RotSettings rot_opts;      // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
+  // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
+  // unset: the engine's own choice (tiles of 1024 blocks where the band order is down to depth 2 or does not fit at all)
+  int rot_tiles = 0; bool rot_tiles_set = false;
+  bool timing = false;
+  ClassTiming ct[KC_COUNT];
+  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false; };   // band: sweep_diff_band_kernel; shift: sweep_diff_shift_kernel
+  std::vector<Pending> pending;
+  std::vector<hipEvent_t> event_pool;
   hipEvent_t get_event() {
     if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
     hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); return e;
@@ -617,7 +614,7 @@ void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool
 // ... for an engine's model: counted (lpmp_schedules_built)
 void upload_schedule(lpmp_engine* e, const Schedule& s, DevSchedule& d, bool keep = false, bool adaptive_built = false) {
   upload_schedule(s, d, e->stream, keep, adaptive_built);
-  ++e->schedules_built;
+  ++e->model.schedules_built;
 }
 
 void check_generic_limits(const Plan& p, const Schedule& s) {
@@ -648,57 +645,57 @@ static void deep_schedule_note(lpmp_engine* e, int64_t n_levels, const char* wha
 
 constexpr int64_t LAZY_SCHEDULES_MIN_FACTORS = (int64_t)1 << 20;
 void ensure_device_schedules(lpmp_engine* e, int mode) {
-  if (e->have_sched[mode]) return;
+  if (e->model.have_sched[mode]) return;
   for (int d = 0; d < 2; ++d) {
-    plan_schedule(e->plan.get(), d, mode);
-    deep_schedule_note(e, e->plan->sched_cache[d][mode].n_levels, d == 0 ? "the forward sweep" : "the backward sweep");
-    check_generic_limits(e->plan->p, e->plan->sched_cache[d][mode]);
-    upload_schedule(e, e->plan->sched_cache[d][mode], e->sched[d][mode]);
+    plan_schedule(e->model.plan.get(), d, mode);
+    deep_schedule_note(e, e->model.plan->sched_cache[d][mode].n_levels, d == 0 ? "the forward sweep" : "the backward sweep");
+    check_generic_limits(e->model.plan->p, e->model.plan->sched_cache[d][mode]);
+    upload_schedule(e, e->model.plan->sched_cache[d][mode], e->model.sched[d][mode]);
   }
-  e->have_sched[mode] = true;
+  e->model.have_sched[mode] = true;
 }
 
 void ensure_pass_schedule(lpmp_engine* e, int mode) {
-  if (e->have_pass[mode]) return;
+  if (e->model.have_pass[mode]) return;
   const bool timed_ = std::getenv("LPMP_PLAN_TIMES") != nullptr;
   auto t_last_ = std::chrono::steady_clock::now();
   auto lap_ = [&](const char* what) { if (!timed_) return; const auto now = std::chrono::steady_clock::now(); std::fprintf(stderr, "lpmp: pass schedule %-28s %.0f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last_).count()); t_last_ = now; };
   // (a three-level pass is the shape whose passes join: its own chain plan is only built if the joins do not check out)
-  plan_pass_schedule(e->plan.get(), mode, false);
-  deep_schedule_note(e, e->plan->pass_cache[mode].n_levels / 2, "a directional sweep");
+  plan_pass_schedule(e->model.plan.get(), mode, false);
+  deep_schedule_note(e, e->model.plan->pass_cache[mode].n_levels / 2, "a directional sweep");
   lap_("forward+backward planned");
-  plan_rotation(e->plan.get(), mode);
+  plan_rotation(e->model.plan.get(), mode);
   lap_("backward+forward planned, joins checked");
-  if (!e->plan->rotation_ok[mode] && e->plan->pass_cache[mode].n_levels == 3) {
-    e->plan->have_pass[mode] = false;
-    plan_pass_schedule(e->plan.get(), mode, true);
+  if (!e->model.plan->rotation_ok[mode] && e->model.plan->pass_cache[mode].n_levels == 3) {
+    e->model.plan->have_pass[mode] = false;
+    plan_pass_schedule(e->model.plan.get(), mode, true);
     lap_("forward+backward planned again, with its chain plan");
   }
-  check_generic_limits(e->plan->p, e->plan->pass_cache[mode]);
-  upload_schedule(e, e->plan->pass_cache[mode], e->sched_pass[mode]);
+  check_generic_limits(e->model.plan->p, e->model.plan->pass_cache[mode]);
+  upload_schedule(e, e->model.plan->pass_cache[mode], e->model.sched_pass[mode]);
   lap_("... uploaded");
   // LPMP_LAUNCH_LOG=<file> (profiling aid): one line per launch of the fused pass in execution order — level, class, records,
   // receives, sends, algorithmic bytes, packet stride — to lay beside the durations of a kernel trace (tools/launch_rates.py)
   if (const char* path = std::getenv("LPMP_LAUNCH_LOG")) {
     if (FILE* f = std::fopen(path, "w")) {
       std::fprintf(f, "level,kclass,records,receives,sends,bytes,stride\n");
-      for (const auto& lr : e->plan->pass_cache[mode].launches)
+      for (const auto& lr : e->model.plan->pass_cache[mode].launches)
         std::fprintf(f, "%d,%d,%lld,%lld,%lld,%lld,%d\n", lr.level, lr.kclass, (long long)(lr.end - lr.begin), (long long)lr.n_recv, (long long)lr.n_send, (long long)lr.bytes, lr.stride);
       std::fclose(f);
     }
   }
-  e->rotation_ok[mode] = e->plan->rotation_ok[mode];
-  if (e->rotation_ok[mode]) {
-    upload_schedule(e, e->plan->bf_cache[mode], e->sched_bf[mode]);
+  e->model.rotation_ok[mode] = e->model.plan->rotation_ok[mode];
+  if (e->model.rotation_ok[mode]) {
+    upload_schedule(e, e->model.plan->bf_cache[mode], e->model.sched_bf[mode]);
     lap_("... uploaded");
-    e->plan->rot[mode] = plan_rotation_chain(e->plan->pass_cache[mode], e->plan->bf_cache[mode], e->plan->p.nf);
+    e->model.plan->rot[mode] = plan_rotation_chain(e->model.plan->pass_cache[mode], e->model.plan->bf_cache[mode], e->model.plan->p.nf);
     lap_("block relations of the steps");
-    e->plan->bf_cache[mode] = Schedule();
+    e->model.plan->bf_cache[mode] = Schedule();
   }
   // the host copy is only needed for its summary
-  Schedule& h = e->plan->pass_cache[mode];
+  Schedule& h = e->model.plan->pass_cache[mode];
   h.recs.clear(); h.recs.shrink_to_fit(); h.ops.clear(); h.ops.shrink_to_fit(); h.packets.clear(); h.packets.shrink_to_fit();
-  e->have_pass[mode] = true;
+  e->model.have_pass[mode] = true;
 }
 
 // ensure_pass_schedule plans a three-level pass whose consecutive passes join WITHOUT a chain plan of its own (the joined
@@ -706,17 +703,17 @@ void ensure_pass_schedule(lpmp_engine* e, int mode) {
 // launch is unavailable — gets the plan the first time that happens: on an HBM-sized model the banded Infinity-Cache launch of
 // the single pass.  The joined-launch templates of that mode point into the schedule's device arrays and are dropped (rebuilt on demand).
 void ensure_pass_chain_plan(lpmp_engine* e, int mode) {
-  if (e->pass_chain_tried[mode] || !e->use_chain || !e->use_blocked_passes) return;
-  e->pass_chain_tried[mode] = true;
-  const DevSchedule& d = e->sched_pass[mode];
-  if (!e->have_pass[mode] || !e->rotation_ok[mode] || d.chain || d.n_levels != 3 || !e->model_big) return;
-  e->plan->have_pass[mode] = false;
-  plan_pass_schedule(e->plan.get(), mode, true);
-  check_generic_limits(e->plan->p, e->plan->pass_cache[mode]);
+  if (e->model.pass_chain_tried[mode] || !e->use_chain || !e->use_blocked_passes) return;
+  e->model.pass_chain_tried[mode] = true;
+  const DevSchedule& d = e->model.sched_pass[mode];
+  if (!e->model.have_pass[mode] || !e->model.rotation_ok[mode] || d.chain || d.n_levels != 3 || !e->model.model_big) return;
+  e->model.plan->have_pass[mode] = false;
+  plan_pass_schedule(e->model.plan.get(), mode, true);
+  check_generic_limits(e->model.plan->p, e->model.plan->pass_cache[mode]);
   HIP_CHECK(hipStreamSynchronize(e->stream));
-  e->release_rot_chains(mode);
-  upload_schedule(e, e->plan->pass_cache[mode], e->sched_pass[mode]);
-  Schedule& h = e->plan->pass_cache[mode];
+  e->model.release_rot_chains(mode);
+  upload_schedule(e, e->model.plan->pass_cache[mode], e->model.sched_pass[mode]);
+  Schedule& h = e->model.plan->pass_cache[mode];
   h.recs.clear(); h.recs.shrink_to_fit(); h.ops.clear(); h.ops.shrink_to_fit(); h.packets.clear(); h.packets.shrink_to_fit();
 }
 
@@ -727,24 +724,24 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
     if (timed) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, stream)); }
     // UpdateFactorPrimal always sends 'shared' (reference factors_messages.hxx:2357-2359), whatever the send rule
     const int rule = e->rtype == LPMP_RTYPE_RESIDUAL ? SWEEP_RESIDUAL : e->rtype == LPMP_RTYPE_ADAPTIVE ? SWEEP_ADAPTIVE : 0;
-    const int flags = (e->primal_pass ? SWEEP_PRIMAL : rule) | e->nt_flag | e->tab_flag;
+    const int flags = (e->primal_pass ? SWEEP_PRIMAL : rule) | e->model.nt_flag | e->model.tab_flag;
     // primal pass over pairwise factors that round themselves: those records take the generic kernels (ensure_primal)
-    const bool pw_rounds = e->primal_pass && e->d_pw_unary && kc_is_pw(lr.kclass);
+    const bool pw_rounds = e->primal_pass && e->model.d_pw_unary && kc_is_pw(lr.kclass);
     if (pw_rounds)
-      launch_sweep(KC_GENERIC, s.recs, s.ops, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->d_pw_unary, lr.begin, lr.end - lr.begin, flags, stream);
+      launch_sweep(KC_GENERIC, s.recs, s.ops, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->model.d_primal, e->model.d_pw_unary, lr.begin, lr.end - lr.begin, flags, stream);
     else if (kc_is_shared(lr.kclass)) {
-      if (!launch_sweep_shared(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual, e->d_const,
-                               e->d_lb, e->d_primal, lr.end - lr.begin, flags, e->d_sh_desc, lr.sh_tab, lr.n_sh, stream))
+      if (!launch_sweep_shared(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->model.d_dual, e->model.d_const,
+                               e->model.d_lb, e->model.d_primal, lr.end - lr.begin, flags, e->model.d_sh_desc, lr.sh_tab, lr.n_sh, stream))
         throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
     }
     else if (lr.kclass == KC_DIFF)     // (LDS by the launch's label counts, as the streaming class)
-      launch_sweep_diff(lr.diff_band, lr.diff_shift, s.recs, s.ops, e->d_dual, e->d_const, e->d_lb, e->d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
+      launch_sweep_diff(lr.diff_band, lr.diff_shift, s.recs, s.ops, e->model.d_dual, e->model.d_const, e->model.d_lb, e->model.d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
     else if (!(lr.stride != 0 &&
-          launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->d_dual,
-                              e->d_const, e->d_lb, e->d_primal, lr.end - lr.begin, flags, stream))) {
+          launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->model.d_dual,
+                              e->model.d_const, e->model.d_lb, e->model.d_primal, lr.end - lr.begin, flags, stream))) {
       // the packed classes have no op-by-op kernel: plan.cpp gives every launch of one packets or indirect records
       if (kc_is_packed(lr.kclass)) throw DeviceError("sweep: launch of packed class " + std::to_string(lr.kclass) + " without packets");
-      launch_sweep(lr.kclass, s.recs, s.ops, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->d_pw_unary, lr.begin, lr.end - lr.begin,
+      launch_sweep(lr.kclass, s.recs, s.ops, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->model.d_primal, e->model.d_pw_unary, lr.begin, lr.end - lr.begin,
                    flags | (lr.kclass == KC_DENSE_BIG ? sweep_bigdim_flags(lr.max_dim) : 0), stream);   // (LDS of the streaming class: by the launch's label counts)
     }
     if (timed) {
@@ -829,7 +826,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
   // pairwise factors that round themselves need the generic kernels: those passes stay launch by launch)
   bool chain_ok = s.chain && e->use_chain;
   if (chain_ok && e->primal_pass) {
-    if (e->d_pw_unary) chain_ok = false;
+    if (e->model.d_pw_unary) chain_ok = false;
     for (const auto& c : s.chains) if (kc_width(c.kclass) == 0) chain_ok = false;
   }
   if (chain_ok) {
@@ -845,7 +842,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
         DevBuf<long long> d_lt;
         const size_t lt_n = 8 + 8 * LEVEL_TRACE_MAX;
         if (lt_path) { d_lt.alloc(lt_n); HIP_CHECK(hipMemset(d_lt, 0, lt_n * sizeof(long long))); debug_set_level_trace(d_lt); }
-        if (!launch_level_loop(c.kclass, rule | e->tab_flag, c.launches, c.n_launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->stream))
+        if (!launch_level_loop(c.kclass, rule | e->model.tab_flag, c.launches, c.n_launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->stream))
           throw DeviceError("level loop: no kernel for class " + std::to_string(c.kclass));
         if (lt_path) {
           HIP_CHECK(hipStreamSynchronize(e->stream));
@@ -860,7 +857,7 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
       ChainTrace tr;
       ChainArgs ca = chain_args(e, c, c.tickets, tr.begin(c.tickets, e->stream));
       ca.mailbox = c.mailbox;
-      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->nt_flag) | e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, e->d_primal, e->stream))
+      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->model.nt_flag) | e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->model.d_primal, e->stream))
         throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
       tr.end(c, e->stream, e->d_chain_abort);
     }
@@ -913,9 +910,9 @@ void check_rows(int64_t n, const int64_t* om_off, const double* om, const int64_
 // completion flags are a ring of a few groups.  Host work, upload and device memory of an n-pass launch no longer depend on n.
 constexpr int ROT_EXPLICIT_MAX = 7;
 // (the window (bands, lag, depth) follows the model: order.cpp rot_geometry; the tiled order: order.cpp make_tiles / tiled_order)
-lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
-  const RotationInfo& ri = e->plan->rot[mode];
-  lpmp_engine::RotOrder& ro = e->rot_order[mode];
+RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
+  const RotationInfo& ri = e->model.plan->rot[mode];
+  RotOrder& ro = e->model.rot_order[mode];
   if (!ro.have_geo) { ro.geo = rot_geometry(e->rot_opts, ri); ro.have_geo = true; }
   const RotGeometry& geo = ro.geo;
   const int rot_bands = e->rot_opts.bands;
@@ -930,7 +927,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   JoinedOrder ord{geo.bands, geo.lag, geo.depth, nullptr};
   {
     const bool worthwhile = ri.valid && kc_is_dense(ri.kclass) && !kc_is_var(ri.kclass) &&
-                            (rot_bands > 0 || (e->model_big && ri.t[1].bytes >= ((int64_t)64 << 20)));
+                            (rot_bands > 0 || (e->model.model_big && ri.t[1].bytes >= ((int64_t)64 << 20)));
     const int want = !worthwhile || ri.t[0].nb != ri.t[2].nb || ri.t[3].nb != ri.t[2].nb ? 0
                    : e->rot_tiles_set ? e->rot_tiles
                    : (rot_bands <= 0 && (geo.depth != 4 || !geo.fits) && n_call >= 4 ? 1024 : 0);
@@ -947,18 +944,18 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const bool periodic = depth % 2 == 0 && n_call > ROT_EXPLICIT_MAX && n_call >= n_template && !std::getenv("LPMP_ROT_EXPLICIT");
   const int n = periodic ? n_template : n_call;
   const int key = periodic ? -tail : n_call;
-  auto it = e->rot_chain[mode].find(key);
-  if (it != e->rot_chain[mode].end()) { it->second.last_use = ++e->rot_clock; return it->second.n_steps > 0 ? &it->second : nullptr; }
-  lpmp_engine::RotChain& rc = e->rot_chain[mode][key];           // n_steps == 0: tried, not possible
+  auto it = e->model.rot_chain[mode].find(key);
+  if (it != e->model.rot_chain[mode].end()) { it->second.last_use = ++e->rot_clock; return it->second.n_steps > 0 ? &it->second : nullptr; }
+  RotChain& rc = e->model.rot_chain[mode][key];           // n_steps == 0: tried, not possible
   rc.last_use = ++e->rot_clock;
   const bool verbose = std::getenv("LPMP_ROT_VERBOSE") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
-  auto no = [&](const char* why) -> lpmp_engine::RotChain* { if (verbose) std::fprintf(stderr, "lpmp: %d passes stay one launch per step: %s\n", n_call, why); return nullptr; };
+  auto no = [&](const char* why) -> RotChain* { if (verbose) std::fprintf(stderr, "lpmp: %d passes stay one launch per step: %s\n", n_call, why); return nullptr; };
   if (!ri.valid) return no("the pass does not have the H, W, K, T shape of one packed class");
   // a model whose tables fit the caches gains nothing from the order and is launch-bound: one launch per step then
   // (nor does one that fits the Infinity Cache as a whole: plain launches already re-read it on-die, and the chain's
   // agent-scope accesses only cost — C2, 512 x 512 8-label Potts: 0.065 ms per pass as launches, 0.10 as a chain)
-  if (rot_bands <= 0 && (ri.t[1].bytes < ((int64_t)64 << 20) || !e->model_big)) return no("the model fits the caches");
+  if (rot_bands <= 0 && (ri.t[1].bytes < ((int64_t)64 << 20) || !e->model.model_big)) return no("the model fits the caches");
   // (the run-time-dims classes read their tables with 8-byte loads of rows that are not line-aligned: as a chain in
   // Infinity-Cache order 1024 x 1024 x 21 labels takes 5.48 ms per pass against 4.38 launch by launch)
   if (rot_bands <= 0 && kc_is_var(ri.kclass)) return no("run-time-dims class");
@@ -980,16 +977,16 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const int n_steps = 2 * n + 1;
   // peer minima: the structure allows it (order.cpp), the tables are doubles in the packed layout, and the buffer can be had
   const char* pq_why = !e->use_peer_minima ? "switched off (LPMP_NO_PEER_MINIMA)" : !ri.peer_minima ? ri.peer_minima_why.c_str()
-                     : e->tab_flag != 0 ? "float tables" : e->rows ? "rows layout" : nullptr;
-  if (!pq_why && !e->d_peerq.get()) {
-    if (!e->d_peerq.try_alloc((size_t)e->plan->p.nf * 32)) pq_why = "no device memory for the published minima";
+                     : e->model.tab_flag != 0 ? "float tables" : e->model.rows ? "rows layout" : nullptr;
+  if (!pq_why && !e->model.d_peerq.get()) {
+    if (!e->model.d_peerq.try_alloc((size_t)e->model.plan->p.nf * 32)) pq_why = "no device memory for the published minima";
   }
   const bool pq = pq_why == nullptr;
   if (verbose) std::fprintf(stderr, "lpmp:   peer minima: %s\n", pq ? "W publishes, K / T read no table" : pq_why);
   std::vector<ChainLaunch> lds;
   for (int s = 0; s < n_steps; ++s) {
     const auto& t = ri.t[jt.step_tmpl[s]];
-    const DevSchedule& ds = t.sched == 0 ? e->sched_pass[mode] : e->sched_bf[mode];
+    const DevSchedule& ds = t.sched == 0 ? e->model.sched_pass[mode] : e->model.sched_bf[mode];
     const int32_t row = jt.step_row[s];
     int32_t hist = row < 0 ? 0 : (jt.step_tmpl[s] == 1 ? HIST_END : HIST_MID) | (row << 2);
     if (pq) hist |= jt.step_tmpl[s] == 1 ? CHAIN_LAUNCH_PQ_PUBLISH : CHAIN_LAUNCH_PQ_CONSUME;
@@ -1004,14 +1001,14 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const size_t n_done = periodic ? (size_t)jt.ring : (size_t)N;
   rc.dev_bytes = lds.size() * sizeof(ChainLaunch) + (jt.tk_launch.size() + jt.tk_block.size() + jt.dep_off.size() + jt.dep.size() + n_done + 1) * sizeof(int32_t);
   // bound the cache in bytes: drop the least recently used built chains (of any mode) until the new one fits; the stream is drained first
-  for (bool drained = false; e->rot_cache_bytes + rc.dev_bytes > e->rot_cache_limit;) {
-    std::map<int, lpmp_engine::RotChain>* vm = nullptr; std::map<int, lpmp_engine::RotChain>::iterator victim;
-    for (auto& m : e->rot_chain)
+  for (bool drained = false; e->model.rot_cache_bytes + rc.dev_bytes > e->rot_cache_limit;) {
+    std::map<int, RotChain>* vm = nullptr; std::map<int, RotChain>::iterator victim;
+    for (auto& m : e->model.rot_chain)
       for (auto i2 = m.begin(); i2 != m.end(); ++i2)
         if (i2->second.n_steps > 0 && (!vm || i2->second.last_use < victim->second.last_use)) { vm = &m; victim = i2; }
     if (!vm) break;
     if (!drained) { HIP_CHECK(hipStreamSynchronize(e->stream)); drained = true; }
-    e->rot_cache_bytes -= std::min(e->rot_cache_bytes, victim->second.dev_bytes);
+    e->model.rot_cache_bytes -= std::min(e->model.rot_cache_bytes, victim->second.dev_bytes);
     vm->erase(victim);
   }
   try {
@@ -1019,12 +1016,12 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
   } catch (...) {
     // nothing half-built stays behind: the entry goes (a later call tries again), the bytes were never counted
-    e->rot_chain[mode].erase(key);
+    e->model.rot_chain[mode].erase(key);
     throw;
   }
   rc.dc.kclass = ri.kclass;
-  e->rot_cache_bytes += rc.dev_bytes;
-  ++e->schedules_built;
+  e->model.rot_cache_bytes += rc.dev_bytes;
+  ++e->model.schedules_built;
   rc.peer_minima = pq;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
   if (verbose && pq) {
@@ -1041,7 +1038,7 @@ lpmp_engine::RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
 
 bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullptr) {
   if (!e->use_chain || !e->use_blocked_passes || e->primal_pass || e->rtype != LPMP_RTYPE_SHARED) return false;
-  lpmp_engine::RotChain* rc = rotation_chain(e, mode, n);
+  RotChain* rc = rotation_chain(e, mode, n);
   if (!rc) return false;
   ensure_chain_abort(e);
   auto& c = rc->dc;
@@ -1056,13 +1053,13 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   ChainTrace tr;
   const int32_t n_tickets = c.tickets + extra * rc->per_len;
   ChainArgs ca = chain_args(e, c, n_tickets, rc->periodic ? nullptr : tr.begin(c.tickets, e->stream));
-  if (lb_hist) { ca.lb_hist = lb_hist; ca.hist_stride = e->plan->p.nf; ca.hist_rows = n - 1; }
+  if (lb_hist) { ca.lb_hist = lb_hist; ca.hist_stride = e->model.plan->p.nf; ca.hist_rows = n - 1; }
   if (rc->periodic) { ca.per_begin = rc->per_begin; ca.per_len = rc->per_len; ca.per_count = 1 + extra; ca.per_row_shift = rc->depth / 2; ca.ring = rc->ring; }
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
-  if (rc->peer_minima && !e->d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
-  if (!launch_chain(c.kclass, e->tab_flag, ca, c.launches, e->d_dual, e->d_const, e->d_tabs, e->d_lb, nullptr, e->stream, rc->peer_minima ? e->d_peerq.get() : nullptr, e->pq_lds)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (rc->peer_minima && !e->model.d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
+  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1075,10 +1072,10 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   return true;
 }
 
-void require_model(const lpmp_engine* e) { if (!e || !e->plan) throw StateError("no model uploaded"); }
+void require_model(const lpmp_engine* e) { if (!e || !e->model.plan) throw StateError("no model uploaded"); }
 void require_mode(const lpmp_engine* e) {
   require_model(e);
-  if (e->mode < 0) throw StateError("no reparametrization mode set");   // reference LP_MP.h:414,458
+  if (e->model.mode < 0) throw StateError("no reparametrization mode set");   // reference LP_MP.h:414,458
 }
 
 }  // namespace
@@ -1088,18 +1085,61 @@ static void settle(lpmp_engine* e);          // speculative passes: make the dev
 static void rows_refresh(lpmp_engine* e) {   // packed duals -> rows, before anything computes on the rows
   // (every hand-over first writes the rows out — rows_flush — and only then lets the caller write: both copies newer than the
   // other would mean one of the two gets lost)
-  if (e->rows && e->rows_stale && e->packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
-  if (e->rows && e->rows_stale) { launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 1, e->stream); HIP_CHECK(hipGetLastError()); e->rows_stale = false; }
+  if (e->model.rows && e->model.rows_stale && e->model.packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
+  if (e->model.rows && e->model.rows_stale) { launch_rows_copy(e->model.d_rowrecs, e->model.n_rowrecs, e->model.d_const, e->model.d_dual, e->model.d_rows, 1, e->stream); HIP_CHECK(hipGetLastError()); e->model.rows_stale = false; }
 }
 static void rows_flush(lpmp_engine* e) {     // rows -> packed duals, before the packed array is handed to anybody
-  if (e->rows && e->packed_stale) { launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 2, e->stream); HIP_CHECK(hipGetLastError()); e->packed_stale = false; }
+  if (e->model.rows && e->model.packed_stale) { launch_rows_copy(e->model.d_rowrecs, e->model.n_rowrecs, e->model.d_const, e->model.d_dual, e->model.d_rows, 2, e->stream); HIP_CHECK(hipGetLastError()); e->model.packed_stale = false; }
 }
 // the constants are unspecified after a refused lpmp_upload_costs: whatever would read them says so — passes, bounds, the primal
 // cost.  The lpmp_boundary_* / lpmp_halo_* kernels (boundary.hip) touch duals only and are not checked.
 static void require_consts(const lpmp_engine* e) {
-  if (e->const_bad) throw StateError("the constants are unspecified since lpmp_upload_costs refused them: upload costs the table precision accepts, or the model");
+  if (e->model.const_bad) throw StateError("the constants are unspecified since lpmp_upload_costs refused them: upload costs the table precision accepts, or the model");
 }
-static void begin_compute(lpmp_engine* e) { require_consts(e); rows_refresh(e); if (e->rows) e->packed_stale = true; }
+static void begin_compute(lpmp_engine* e) { require_consts(e); rows_refresh(e); if (e->model.rows) e->model.packed_stale = true; }
+
+static void check_chain(lpmp_engine* e);
+namespace {
+// The listed rows of lpmp_set_vectors / lpmp_set_constants.  Validates the list (range, kind: `vectors` says which kind the call
+// takes and wrong_kind how it refuses the other, no factor twice), lets `fill(i, f, src_row)` make record i, checks the stride
+// against the longest row, settles the engine, uploads the records into d_recs and packs a host source row after row into
+// d_setsrc.  Returns the device source and its stride, {nullptr, 0} for an empty list.
+struct ListedSrc { const double* src; int64_t stride; };
+template <class Rec, class Fill>
+ListedSrc listed_rows(lpmp_engine* e, const std::string& who, int64_t n, const int32_t* factors, const double* src, int64_t src_stride, bool dev,
+                      bool vectors, const char* wrong_kind, DevBuf<Rec>& d_recs, Fill&& fill) {
+  const Plan& p = e->model.plan->p;
+  std::vector<uint8_t> seen((size_t)p.nf, 0);
+  std::vector<Rec> recs((size_t)n);
+  int64_t longest = 0, total = 0;
+  int32_t longest_f = -1;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t f = factors[i];
+    if (f < 0 || f >= p.nf) throw std::runtime_error(who + ": factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+    if ((p.f_kind[f] == LPMP_F_VECTOR) != vectors) throw std::runtime_error(who + ": factor " + std::to_string(f) + wrong_kind);
+    if (seen[(size_t)f]) throw std::runtime_error(who + ": factor " + std::to_string(f) + " is listed twice (the result would depend on the order of two waves)");
+    seen[(size_t)f] = 1;
+    // (a host source is packed row after row: stride 1, row = offset)
+    const Rec r = fill(i, f, dev ? i : total);
+    if (r.len > longest) { longest = r.len; longest_f = f; }
+    recs[(size_t)i] = r;
+    total += r.len;
+  }
+  if (n > 0 && src_stride < longest)
+    throw std::runtime_error(who + ": src_stride " + std::to_string(src_stride) + " is smaller than the " + std::to_string(longest) + " entries of factor " + std::to_string(longest_f));
+  settle(e);
+  check_chain(e);
+  if (n == 0) return {nullptr, 0};
+  d_recs.grow((size_t)n);
+  h2d(d_recs, recs.data(), (size_t)n * sizeof(Rec), e->stream);
+  if (dev) return {src, src_stride};
+  std::vector<double> rows((size_t)total);
+  for (int64_t i = 0; i < n; ++i) std::copy(src + i * src_stride, src + i * src_stride + recs[(size_t)i].len, rows.begin() + recs[(size_t)i].src_row);
+  e->model.d_setsrc.grow((size_t)total);
+  h2d(e->model.d_setsrc, rows.data(), (size_t)total * sizeof(double), e->stream);
+  return {e->model.d_setsrc.get(), 1};
+}
+}  // namespace
 
 extern "C" {
 
@@ -1436,7 +1476,7 @@ void lpmp_destroy(lpmp_engine* e) {
   (void)hipSetDevice(e->device);
   // a BORROWED dual buffer (LPMP_MEM_DEVICE) outlives the engine: an open batch of passes that ran ahead of the caller must
   // not stay in it
-  if (e->plan && !e->own_dual() && e->spec.n > 0) { try { settle(e); } catch (const std::exception& ex) { std::fprintf(stderr, "lpmp_destroy: could not roll back passes that ran ahead: %s\n", ex.what()); } }
+  if (e->model.plan && !e->model.own_dual() && e->model.batch.n > 0) { try { settle(e); } catch (const std::exception& ex) { std::fprintf(stderr, "lpmp_destroy: could not roll back passes that ran ahead: %s\n", ex.what()); } }
   (void)hipStreamSynchronize(e->stream);
   for (auto& p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
@@ -1457,29 +1497,36 @@ int lpmp_set_stream(lpmp_engine* e, void* s) {
     settle(e);
     HIP_CHECK(hipStreamSynchronize(e->stream));
     for (int d = 0; d < 2; ++d) for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-      e->sched[d][m].graph.reset();
+      e->model.sched[d][m].graph.reset();
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-      e->sched_pass[m].graph.reset();
+      e->model.sched_pass[m].graph.reset();
     if (e->own_stream && e->stream) stream_pool().give(e->device, e->stream);
     e->stream = (hipStream_t)s; e->own_stream = false;
   });
 }
 
-// Table precision f32 (lpmp_set_table_precision): every DENSE table of the packed constants becomes floats in e->d_tab32, each
-// table 16-byte aligned, and p.dev_coff[f] of a DENSE factor its place there (8-byte units relative to e->d_const).
-//   on_device: `consts` is the caller's device buffer — it stays e->d_const, the tables are narrowed out of it, and afterwards
+// the one sentence that refuses an entry a float table cannot hold (the upload and lpmp_upload_costs: a table; lpmp_set_constants: a row)
+static std::string f32_refusal(const char* who, bool strict, const char* what, int factor, const char* tail) {
+  return std::string(who) + "table precision " + (strict ? "f32" : "f32_round") + ": the " + what + " of factor " + std::to_string(factor) +
+         (strict ? " holds an entry that is not exactly a float (or a finite one beyond float's range or below FLT_MIN)"
+                 : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN") + tail;
+}
+
+// Table precision f32 (lpmp_set_table_precision): every DENSE table of the packed constants becomes floats in m.d_tab32, each
+// table 16-byte aligned, and p.dev_coff[f] of a DENSE factor its place there (8-byte units relative to m.d_const).
+//   on_device: `consts` is the caller's device buffer — it stays m.d_const, the tables are narrowed out of it, and afterwards
 //     the engine reads only the cells of the other factors from it.
 //   otherwise `consts` is host memory: the tables pass through a staging buffer of at most 256 MiB, chunk by chunk, and are never
 //     resident as doubles as a whole; the cells of the other factors (Potts, SHARED and DIFF scalars) are gathered into a compact
-//     buffer of doubles that becomes e->d_const, and dev_coff of those factors points into it.
+//     buffer of doubles that becomes m.d_const (m.tab_compact), and dev_coff of those factors points into it.
 // Throws UnsupportedError naming the lowest DENSE factor that holds an entry the mode refuses (kernels.hip, narrow_tables_kernel).
-// fresh (the upload): the buffers are allocated and dev_coff is laid out.  Not fresh (lpmp_upload_costs): the same narrowing into the
-// buffers and offsets of the upload — the mode is the uploaded model's, `consts` is e->d_const itself (a borrowed buffer, already
-// holding the new constants) or, for an engine whose compact buffer came from host memory, host or device memory of the caller's.
-static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on_device, bool fresh = true) {
-  const int prec = fresh ? e->want_tab : e->tab_prec;
-  const int strict = prec == LPMP_TABLES_F32 ? 1 : 0;
-  const bool compact = fresh ? !on_device : e->tab_compact;
+// The mode is m.tab_prec.  fresh (the upload): the buffers are allocated and dev_coff is laid out.  Not fresh (lpmp_upload_costs):
+// the same narrowing into the buffers and offsets of the upload — `consts` is m.d_const itself (a borrowed buffer, already holding
+// the new constants) or, for a model whose compact buffer came from host memory, host or device memory of the caller's.
+static void narrow_tables(ModelState& m, hipStream_t stream, const double* consts, bool on_device, bool fresh = true) {
+  Plan& p = m.plan->p;
+  const int strict = m.tab_prec == LPMP_TABLES_F32 ? 1 : 0;
+  const bool compact = m.tab_compact;
   std::vector<NarrowRec> recs;
   std::vector<double> small;
   struct Run { int64_t src, dst, n; };
@@ -1499,27 +1546,27 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
     }
   }
   if (compact) {
-    if (fresh) { e->const_buf.alloc(std::max<size_t>(2, (size_t)small_at)); e->d_const = e->const_buf; }
-    else if ((size_t)small_at > e->const_buf.capacity()) throw std::runtime_error("table precision: the compact constants do not fit their buffer");
-    if (!small.empty()) h2d(e->d_const, small.data(), small.size() * sizeof(double), e->stream);
-    for (const Run& r : runs) HIP_CHECK(hipMemcpyAsync(e->const_buf + r.dst, consts + r.src, (size_t)r.n * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    if (fresh) { m.const_buf.alloc(std::max<size_t>(2, (size_t)small_at)); m.d_const = m.const_buf; }
+    else if ((size_t)small_at > m.const_buf.capacity()) throw std::runtime_error("table precision: the compact constants do not fit their buffer");
+    if (!small.empty()) h2d(m.d_const, small.data(), small.size() * sizeof(double), stream);
+    for (const Run& r : runs) HIP_CHECK(hipMemcpyAsync(m.const_buf + r.dst, consts + r.src, (size_t)r.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
   }
   if (recs.empty()) return;
-  if (!fresh) { if ((size_t)at > e->d_tab32.capacity()) throw std::runtime_error("table precision: the tables do not fit their buffer"); }
+  if (!fresh) { if ((size_t)at > m.d_tab32.capacity()) throw std::runtime_error("table precision: the tables do not fit their buffer"); }
   else {
-  e->d_tab32.alloc((size_t)at);
-  if ((((uintptr_t)e->d_tab32.get() - (uintptr_t)e->d_const) % 16) != 0) throw std::runtime_error("table precision: buffers are not aligned to each other");
-  const int64_t shift = (int64_t)(((intptr_t)e->d_tab32.get() - (intptr_t)e->d_const) / 8);
+  m.d_tab32.alloc((size_t)at);
+  if ((((uintptr_t)m.d_tab32.get() - (uintptr_t)m.d_const) % 16) != 0) throw std::runtime_error("table precision: buffers are not aligned to each other");
+  const int64_t shift = (int64_t)(((intptr_t)m.d_tab32.get() - (intptr_t)m.d_const) / 8);
   for (const NarrowRec& r : recs) p.dev_coff[r.factor] = shift + r.dst_off / 2;
   }
   DevBuf<int> d_bad; d_bad.alloc(1);
   const int none = INT32_MAX;
-  h2d(d_bad, &none, sizeof(int), e->stream);
+  h2d(d_bad, &none, sizeof(int), stream);
   DevBuf<NarrowRec> d_recs;
   if (on_device) {
     d_recs.alloc(recs.size());
-    h2d(d_recs, recs.data(), recs.size() * sizeof(NarrowRec), e->stream);
-    launch_narrow_tables(d_recs, (int64_t)recs.size(), consts, e->d_tab32, strict, d_bad, e->stream);
+    h2d(d_recs, recs.data(), recs.size() * sizeof(NarrowRec), stream);
+    launch_narrow_tables(d_recs, (int64_t)recs.size(), consts, m.d_tab32, strict, d_bad, stream);
     HIP_CHECK(hipGetLastError());
   } else {
     // chunks of whole tables, at most STAGE doubles of the packed array each (a table has at most BIG_MAX_LABELS^2 entries: 2 MiB)
@@ -1540,21 +1587,18 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
       while (b < recs.size() && recs[b].src_off + recs[b].n - c0 <= STAGE) ++b;
       part.assign(recs.begin() + (std::ptrdiff_t)a, recs.begin() + (std::ptrdiff_t)b);
       for (NarrowRec& r : part) r.src_off -= c0;
-      h2d(stage, consts + c0, (size_t)(recs[b - 1].src_off + recs[b - 1].n - c0) * sizeof(double), e->stream);
-      h2d(d_recs, part.data(), part.size() * sizeof(NarrowRec), e->stream);
-      launch_narrow_tables(d_recs, (int64_t)part.size(), stage, e->d_tab32, strict, d_bad, e->stream);
+      h2d(stage, consts + c0, (size_t)(recs[b - 1].src_off + recs[b - 1].n - c0) * sizeof(double), stream);
+      h2d(d_recs, part.data(), part.size() * sizeof(NarrowRec), stream);
+      launch_narrow_tables(d_recs, (int64_t)part.size(), stage, m.d_tab32, strict, d_bad, stream);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipStreamSynchronize(e->stream));   // `part` and the staging buffer are reused by the next chunk
+      HIP_CHECK(hipStreamSynchronize(stream));   // `part` and the staging buffer are reused by the next chunk
       a = b;
     }
   }
   int bad = none;
-  d2h(&bad, d_bad, sizeof(int), e->stream);
-  HIP_CHECK(hipStreamSynchronize(e->stream));
-  if (bad != none)
-    throw UnsupportedError("table precision " + std::string(strict ? "f32" : "f32_round") + ": the table of factor " + std::to_string(bad) +
-                           (strict ? " holds an entry that is not exactly a float (or a finite one beyond float's range or below FLT_MIN)"
-                                   : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN"));
+  d2h(&bad, d_bad, sizeof(int), stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (bad != none) throw UnsupportedError(f32_refusal("", strict != 0, "table", bad, ""));
 }
 
 // The engine-private copies of the constants that are COSTS, not structure: lpmp_upload_model derives them once, lpmp_upload_costs
@@ -1564,19 +1608,20 @@ static void narrow_tables(lpmp_engine* e, Plan& p, const double* consts, bool on
 // A DIFF_SHIFT factor has a second cell right behind the first, {const offset of its shift, n = the length of D}: the same kernel
 // gathers the shift as it gathers a scale, and the factor's four words on the device are {scale, offset of D, shift (the double
 // of the constants: the kernels convert it, kernels.hip diff_shift_int), n}
-static void gather_shared_cells(lpmp_engine* e) {
-  if (e->sh_cells.empty()) return;
-  h2d(e->d_shared, e->sh_cells.data(), e->sh_cells.size() * sizeof(int64_t), e->stream);
-  launch_shared_cells(e->d_shared, (int64_t)e->sh_cells.size() / 2, e->d_const, e->stream);
+static void gather_shared_cells(ModelState& m, hipStream_t stream) {
+  if (m.sh_cells.empty()) return;
+  h2d(m.d_shared, m.sh_cells.data(), m.sh_cells.size() * sizeof(int64_t), stream);
+  launch_shared_cells(m.d_shared, (int64_t)m.sh_cells.size() / 2, m.d_const, stream);
   HIP_CHECK(hipGetLastError());
 }
 // ... the pool block of d_shared, behind the n_sf cells (two words each): every entry t of the plan's pool with one 8-byte band word
 // {int32 lo, int32 hi} in front of it — sweep_diff_band_kernel learns the band of a DIFF vector from the word before the offset in
 // the factor's cell (entries no DIFF factor references: an empty band, never read).  Entry t starts at shared_pool_at(p, t).
 static int64_t shared_pool_at(const Plan& p, int32_t t) { return p.sh_off[(size_t)t] + t + 1; }
-static void write_shared_pool(lpmp_engine* e, const Plan& p, int64_t n_sf) {
+static void write_shared_pool(ModelState& m, hipStream_t stream, int64_t n_sf) {
+  const Plan& p = m.plan->p;
   const int64_t n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
-  if ((size_t)(2 * n_sf + n_pool) > e->d_shared.capacity()) throw std::runtime_error("shared tables: the pool does not fit its buffer");
+  if ((size_t)(2 * n_sf + n_pool) > m.d_shared.capacity()) throw std::runtime_error("shared tables: the pool does not fit its buffer");
   std::vector<double> pool((size_t)n_pool);
   for (int32_t t = 0; t < p.n_shared; ++t) {
     const int32_t word[2] = {p.sh_lo[(size_t)t], p.sh_hi[(size_t)t]};
@@ -1584,162 +1629,184 @@ static void write_shared_pool(lpmp_engine* e, const Plan& p, int64_t n_sf) {
     std::memcpy(&pool[(size_t)(shared_pool_at(p, t) - 1)], word, sizeof word);
     std::copy(p.sh_data.begin() + p.sh_off[(size_t)t], p.sh_data.begin() + p.sh_off[(size_t)t + 1], pool.begin() + shared_pool_at(p, t));
   }
-  h2d(e->d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), e->stream);
+  h2d(m.d_shared + 2 * n_sf, pool.data(), (size_t)n_pool * sizeof(double), stream);
 }
 // rows layout: every row [table | m1 | m2] from the packed constants and the packed duals
-static void build_rows(lpmp_engine* e) {
-  launch_rows_copy(e->d_rowrecs, e->n_rowrecs, e->d_const, e->d_dual, e->d_rows, 0, e->stream);
+static void build_rows(ModelState& m, hipStream_t stream) {
+  launch_rows_copy(m.d_rowrecs, m.n_rowrecs, m.d_const, m.d_dual, m.d_rows, 0, stream);
   HIP_CHECK(hipGetLastError());
 }
 
-static void check_rtype(const lpmp_engine* e, int rtype);
+// what keeps a model from running under a send rule (also checked at upload: the rule may be set first,
+// as the reference parses --reparametrizationType in LP::Begin)
+static void check_rtype(const ModelState& m, int rtype) {
+  if (!m.plan) return;
+  const Plan& p = m.plan->p;
+  if (rtype == LPMP_RTYPE_RESIDUAL && p.any_batch)
+    throw UnsupportedError("residual sends with batch-capable message ops are not built (send_messages_residual's batch branch, factors_messages.hxx:2980-2991)");
+  if (rtype == LPMP_RTYPE_ADAPTIVE) { const std::string why = p.adaptive_obstacle(); if (!why.empty()) throw UnsupportedError(why); }
+}
+
+// ---- the layout steps of lpmp_upload_model: each fills the model it is given, from its plan and base pointers ----
+// rows layout: every dense pairwise factor becomes one row [table | m1 | m2] of a private buffer; its device offsets
+// (relative to the const / dual base pointers, which the kernels add them to) point there from now on
+static void layout_rows(ModelState& m, hipStream_t stream) {
+  Plan& p = m.plan->p;
+  std::vector<RowRec> rr;
+  int64_t at = 0;
+  for (int64_t f = 0; f < p.nf; ++f)
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+      rr.push_back({p.f_doff[f], p.f_coff[f], at, p.f_dim0[f], p.f_dim1[f]});
+      at += ((int64_t)p.f_dim0[f] * p.f_dim1[f] + p.f_dim0[f] + p.f_dim1[f] + 1) / 2 * 2;      // rows start 16-byte aligned
+    }
+  if (rr.empty()) return;
+  m.d_rows.alloc((size_t)at);
+  if ((((uintptr_t)m.d_rows.get() - (uintptr_t)m.d_const) % 16) != 0 || (((uintptr_t)m.d_rows.get() - (uintptr_t)m.d_dual) % 8) != 0)
+    throw std::runtime_error("rows layout: buffers are not aligned to each other");
+  m.d_rowrecs.alloc(rr.size());
+  h2d(m.d_rowrecs, rr.data(), rr.size() * sizeof(RowRec), stream);
+  m.n_rowrecs = (int64_t)rr.size();
+  build_rows(m, stream);
+  const int64_t c_shift = (int64_t)(((intptr_t)m.d_rows.get() - (intptr_t)m.d_const) / 8), d_shift = (int64_t)(((intptr_t)m.d_rows.get() - (intptr_t)m.d_dual) / 8);
+  p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end()); p.dev_doff.assign(p.f_doff.begin(), p.f_doff.end());
+  size_t k = 0;
+  for (int64_t f = 0; f < p.nf; ++f)
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
+      p.dev_coff[f] = c_shift + rr[k].row_off;
+      p.dev_doff[f] = d_shift + rr[k].row_off + (int64_t)p.f_dim0[f] * p.f_dim1[f];
+      ++k;
+    }
+  m.rows = true; m.packed_stale = false; m.rows_stale = false;
+}
+// SHARED pairwise factors: the host format is one double (the scale) per factor and a model-level pool of tables; on the
+// device a factor's constants are two words {scale, offset of its table relative to the const base pointer} in an
+// allocation of the engine's own, followed by the pool (always copied from the host: sh_data is host memory also when the
+// packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
+static void layout_shared_cells(ModelState& m, hipStream_t stream) {
+  Plan& p = m.plan->p;
+  std::vector<int64_t> sf;                      // the factor of every cell; a DIFF_SHIFT factor is listed twice (its two cells)
+  for (int64_t f = 0; f < p.nf; ++f) {
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
+    else if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) { sf.push_back(f); sf.push_back(f); }
+  }
+  // (the pool behind the cells: write_shared_pool)
+  const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
+  m.d_shared.alloc((size_t)(2 * n_sf + n_pool));
+  if ((((uintptr_t)m.d_shared.get() - (uintptr_t)m.d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
+  const int64_t base = (int64_t)(((intptr_t)m.d_shared.get() - (intptr_t)m.d_const) / 8);
+  std::vector<int64_t> cells((size_t)(2 * n_sf));
+  if (p.dev_coff.empty()) p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
+  for (int64_t k = 0; k < n_sf; ++k) {
+    const int64_t f = sf[(size_t)k];
+    cells[(size_t)(2 * k)] = p.dev_coff[f];   // (the packed offset, or the factor's cell of the compact constants: table precision)
+    cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + shared_pool_at(p, p.f_table[f]);
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {   // its second cell: the shift, and n from the plan (structure: never from device memory)
+      cells[(size_t)(2 * k + 2)] = p.dev_coff[f] + 1;
+      cells[(size_t)(2 * k + 3)] = p.sh_dim1[(size_t)p.f_table[f]];
+    }
+    p.dev_coff[f] = base + 2 * k;
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) ++k;
+  }
+  m.sh_cells = std::move(cells);
+  write_shared_pool(m, stream, n_sf);
+  gather_shared_cells(m, stream);
+  std::vector<ShTableDesc> desc((size_t)p.n_shared);
+  for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + shared_pool_at(p, t), p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
+  m.d_sh_desc.alloc(desc.size());
+  h2d(m.d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDesc), stream);
+}
+// lower-bound records, in factor order, and runs of factors the streaming dense kernel can take; the tracked bounds start all NaN
+static void layout_bound_records(ModelState& m, hipStream_t stream) {
+  const Plan& p = m.plan->p;
+  std::vector<LbRec> lb(p.nf);
+  auto lb_class = [&](int64_t f) {
+    if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[f] == p.f_dim1[f] && (p.coff(f) % 2) == 0 &&
+        (p.f_dim0[f] == 8 || p.f_dim0[f] == 16 || p.f_dim0[f] == 32)) return p.f_dim0[f];
+    return 0;
+  };
+  for (int64_t f = 0; f < p.nf; ++f) {
+    lb[f] = {p.doff(f), p.f_kind[f] == LPMP_F_VECTOR ? -1 : p.coff(f), p.f_dim0[f], p.f_dim1[f], p.f_kind[f] | (p.f_flags[f] << 4), 0};
+    const int c = lb_class(f);
+    if (m.lb_runs.empty() || m.lb_runs.back().cls != c) m.lb_runs.push_back({c, f, 1}); else m.lb_runs.back().count++;
+  }
+  m.d_lbrecs.alloc((size_t)p.nf);
+  h2d(m.d_lbrecs, lb.data(), (size_t)p.nf * sizeof(LbRec), stream);
+  m.d_lb.alloc((size_t)p.nf);
+  m.d_part.alloc(1024);
+  m.d_stale.alloc((size_t)p.nf);
+  m.d_stale_n.alloc(1);
+  HIP_CHECK(hipMemsetAsync(m.d_lb, 0xFF, (size_t)p.nf * sizeof(double), stream));   // all NaN: nothing tracked yet
+  m.lb_all_stale = true;
+}
+
+// The model is built as a local value and committed by move at the very end: whatever throws on the way, the engine holds no
+// model afterwards (the old one is dropped first: two models need not fit in device memory together).
 int lpmp_upload_model(lpmp_engine* e, const lpmp_model* m, int const_mem, int dual_mem) {
   return guarded([&] {
     if (!e || !m) throw std::runtime_error("null argument");
     HIP_CHECK(hipSetDevice(e->device));
-    if (e->plan && !e->own_dual() && e->spec.n > 0) settle(e);   // the caller keeps the old model's (borrowed) dual buffer: leave it at the caller's pass
+    if (e->model.plan && !e->model.own_dual() && e->model.batch.n > 0) settle(e);   // the caller keeps the old model's (borrowed) dual buffer: leave it at the caller's pass
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    { const int d = e->spec.max_depth; e->release_model(); e->spec.max_depth = d; }   // (an open speculative batch in an engine-owned buffer dies with the old model)
-    auto pl = std::make_unique<lpmp_plan>();
-    pl->p.build(*m);
-    const Plan& p = pl->p;
+    e->release_model();   // (an open speculative batch in an engine-owned buffer dies with the old model)
+    ModelState next;
+    next.plan = std::make_unique<lpmp_plan>();
+    Plan& p = next.plan->p;
+    p.build(*m);
     const int64_t n_const = p.f_coff[p.nf], n_dual = p.f_doff[p.nf];
     if ((n_const > 0 && !m->const_data) || !m->dual_data) throw std::runtime_error("cost arrays missing");
     // streamed-once access policy (kernels.hip, ld_stream): only when the state cannot live in the 256 MiB Infinity Cache
     {
       const char* env = getenv("LPMP_NT");
       const bool big = (n_const + n_dual) * (int64_t)sizeof(double) > (int64_t)1 << 30;
-      e->nt_flag = (env ? atoi(env) != 0 : big) ? SWEEP_NT : 0;
-      e->model_big = big;
+      next.nt_flag = (env ? atoi(env) != 0 : big) ? SWEEP_NT : 0;
+      next.model_big = big;
     }
     const bool f32 = e->want_tab != LPMP_TABLES_F64;
     if (f32 && e->want_rows) throw UnsupportedError("table precision f32 and the rows layout cannot be combined (the rows hold the tables as doubles)");
-    if (f32) pl->p.tables_f32 = true;   // before the first schedule: the byte accounting of every plan of this model
+    if (f32) { p.tables_f32 = true; next.tab_prec = e->want_tab; next.tab_flag = SWEEP_TAB32; }   // before the first schedule: the byte accounting of every plan of this model
     if (const_mem == LPMP_MEM_DEVICE) {
-      e->d_const = const_cast<double*>(m->const_data);
-      if (((uintptr_t)e->d_const & 15) != 0) throw std::runtime_error("device const buffer must be 16-byte aligned");
-      if (f32) try { narrow_tables(e, pl->p, m->const_data, true); } catch (...) { e->release_model(); throw; }
+      next.d_const = const_cast<double*>(m->const_data);
+      if (((uintptr_t)next.d_const & 15) != 0) throw std::runtime_error("device const buffer must be 16-byte aligned");
+      if (f32) narrow_tables(next, e->stream, m->const_data, true);
     } else if (f32) {
-      e->tab_compact = true;
-      try { narrow_tables(e, pl->p, m->const_data, false); } catch (...) { e->release_model(); throw; }
+      next.tab_compact = true;
+      narrow_tables(next, e->stream, m->const_data, false);
     } else if (n_const > 0) {
-      e->const_buf.alloc((size_t)n_const);
-      e->d_const = e->const_buf;
-      h2d(e->d_const, m->const_data, (size_t)n_const * sizeof(double), e->stream);
+      next.const_buf.alloc((size_t)n_const);
+      next.d_const = next.const_buf;
+      h2d(next.d_const, m->const_data, (size_t)n_const * sizeof(double), e->stream);
     }
     if (dual_mem == LPMP_MEM_DEVICE) {
-      e->d_dual = const_cast<double*>(m->dual_data);
+      next.d_dual = const_cast<double*>(m->dual_data);
     } else {
-      e->dual_buf.alloc((size_t)n_dual);
-      e->d_dual = e->dual_buf;
-      h2d(e->d_dual, m->dual_data, (size_t)n_dual * sizeof(double), e->stream);
+      next.dual_buf.alloc((size_t)n_dual);
+      next.d_dual = next.dual_buf;
+      h2d(next.d_dual, m->dual_data, (size_t)n_dual * sizeof(double), e->stream);
     }
-    if (e->want_rows && e->d_const) {
-      // rows layout: every dense pairwise factor becomes one row [table | m1 | m2] of a private buffer; its device offsets
-      // (relative to the const / dual base pointers, which the kernels add them to) point there from now on
-      std::vector<RowRec> rr;
-      int64_t at = 0;
-      for (int64_t f = 0; f < p.nf; ++f)
-        if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
-          rr.push_back({p.f_doff[f], p.f_coff[f], at, p.f_dim0[f], p.f_dim1[f]});
-          at += ((int64_t)p.f_dim0[f] * p.f_dim1[f] + p.f_dim0[f] + p.f_dim1[f] + 1) / 2 * 2;      // rows start 16-byte aligned
-        }
-      if (!rr.empty()) {
-        e->d_rows.alloc((size_t)at);
-        if ((((uintptr_t)e->d_rows.get() - (uintptr_t)e->d_const) % 16) != 0 || (((uintptr_t)e->d_rows.get() - (uintptr_t)e->d_dual) % 8) != 0)
-          throw std::runtime_error("rows layout: buffers are not aligned to each other");
-        e->d_rowrecs.alloc(rr.size());
-        h2d(e->d_rowrecs, rr.data(), rr.size() * sizeof(RowRec), e->stream);
-        e->n_rowrecs = (int64_t)rr.size();
-        build_rows(e);
-        const int64_t c_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_const) / 8), d_shift = (int64_t)(((intptr_t)e->d_rows.get() - (intptr_t)e->d_dual) / 8);
-        pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end()); pl->p.dev_doff.assign(p.f_doff.begin(), p.f_doff.end());
-        size_t k = 0;
-        for (int64_t f = 0; f < p.nf; ++f)
-          if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
-            pl->p.dev_coff[f] = c_shift + rr[k].row_off;
-            pl->p.dev_doff[f] = d_shift + rr[k].row_off + (int64_t)p.f_dim0[f] * p.f_dim1[f];
-            ++k;
-          }
-        e->rows = true; e->packed_stale = false; e->rows_stale = false;
-      }
-    }
-    if (!p.f_table.empty()) {
-      // SHARED pairwise factors: the host format is one double (the scale) per factor and a model-level pool of tables; on the
-      // device a factor's constants are two words {scale, offset of its table relative to the const base pointer} in an
-      // allocation of the engine's own, followed by the pool (always copied from the host: sh_data is host memory also when the
-      // packed constants are a device buffer of the caller's, which is why the scales are gathered by a kernel)
-      std::vector<int64_t> sf;                      // the factor of every cell; a DIFF_SHIFT factor is listed twice (its two cells)
-      for (int64_t f = 0; f < p.nf; ++f) {
-        if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF) sf.push_back(f);   // (DIFF: the same two words, its vector D is a pool entry)
-        else if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) { sf.push_back(f); sf.push_back(f); }
-      }
-      // (the pool behind the cells: write_shared_pool)
-      const int64_t n_sf = (int64_t)sf.size(), n_pool = p.sh_off[(size_t)p.n_shared] + p.n_shared;
-      auto pool_at = [&](int32_t t) { return shared_pool_at(p, t); };
-      e->d_shared.alloc((size_t)(2 * n_sf + n_pool));
-      if ((((uintptr_t)e->d_shared.get() - (uintptr_t)e->d_const) % 8) != 0) throw std::runtime_error("shared tables: buffers are not aligned to each other");
-      const int64_t base = (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8);
-      std::vector<int64_t> cells((size_t)(2 * n_sf));
-      if (pl->p.dev_coff.empty()) pl->p.dev_coff.assign(p.f_coff.begin(), p.f_coff.end());
-      for (int64_t k = 0; k < n_sf; ++k) {
-        const int64_t f = sf[(size_t)k];
-        cells[(size_t)(2 * k)] = pl->p.dev_coff[f];   // (the packed offset, or the factor's cell of the compact constants: table precision)
-        cells[(size_t)(2 * k + 1)] = base + 2 * n_sf + pool_at(p.f_table[f]);
-        if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {   // its second cell: the shift, and n from the plan (structure: never from device memory)
-          cells[(size_t)(2 * k + 2)] = pl->p.dev_coff[f] + 1;
-          cells[(size_t)(2 * k + 3)] = p.sh_dim1[(size_t)p.f_table[f]];
-        }
-        pl->p.dev_coff[f] = base + 2 * k;
-        if (p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) ++k;
-      }
-      e->sh_cells = std::move(cells);
-      write_shared_pool(e, p, n_sf);
-      gather_shared_cells(e);
-      std::vector<ShTableDesc> desc((size_t)p.n_shared);
-      for (int t = 0; t < p.n_shared; ++t) desc[(size_t)t] = {base + 2 * n_sf + pool_at(t), p.sh_dim0[(size_t)t], p.sh_dim1[(size_t)t]};
-      e->d_sh_desc.alloc(desc.size());
-      h2d(e->d_sh_desc, desc.data(), desc.size() * sizeof(ShTableDesc), e->stream);
-    }
+    if (e->want_rows && next.d_const) layout_rows(next, e->stream);
+    if (!p.f_table.empty()) layout_shared_cells(next, e->stream);
     if (!p.tab_data.empty()) {
-      e->d_tabs.alloc(p.tab_data.size());
-      h2d(e->d_tabs, p.tab_data.data(), p.tab_data.size() * sizeof(int32_t), e->stream);
+      next.d_tabs.alloc(p.tab_data.size());
+      h2d(next.d_tabs, p.tab_data.data(), p.tab_data.size() * sizeof(int32_t), e->stream);
     }
-    // lower-bound records, in factor order, and runs of factors the streaming dense kernel can take
-    std::vector<LbRec> lb(p.nf);
-    auto lb_class = [&](int64_t f) {
-      if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE && p.f_dim0[f] == p.f_dim1[f] && (p.coff(f) % 2) == 0 &&
-          (p.f_dim0[f] == 8 || p.f_dim0[f] == 16 || p.f_dim0[f] == 32)) return p.f_dim0[f];
-      return 0;
-    };
-    for (int64_t f = 0; f < p.nf; ++f) {
-      lb[f] = {p.doff(f), p.f_kind[f] == LPMP_F_VECTOR ? -1 : p.coff(f), p.f_dim0[f], p.f_dim1[f], p.f_kind[f] | (p.f_flags[f] << 4), 0};
-      const int c = lb_class(f);
-      if (e->lb_runs.empty() || e->lb_runs.back().cls != c) e->lb_runs.push_back({c, f, 1}); else e->lb_runs.back().count++;
+    layout_bound_records(next, e->stream);
+    if (!e->pinned) {
+      e->pinned = pinned_pool().take();
+      e->h_part = (double*)e->pinned;                               // [0, 1024) doubles: partial sums
+      e->h_stale_n = (unsigned long long*)(e->pinned + 8 * 1024);   // one counter
+      e->h_pbad = (int*)(e->pinned + 8 * 1024 + 64);                // one flag
     }
-    e->d_lbrecs.alloc((size_t)p.nf);
-    h2d(e->d_lbrecs, lb.data(), (size_t)p.nf * sizeof(LbRec), e->stream);
-    e->d_lb.alloc((size_t)p.nf);
-    e->d_part.alloc(1024);
-    if (!e->pinned) e->pinned = pinned_pool().take();
-    e->h_part = (double*)e->pinned;                            // [0, 1024) doubles: partial sums
-    e->d_stale.alloc((size_t)p.nf);
-    e->d_stale_n.alloc(1);
-    e->h_stale_n = (unsigned long long*)(e->pinned + 8 * 1024);   // one counter
-    HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));   // all NaN: nothing tracked yet
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    e->lb_all_stale = true;
-    if (f32) { e->tab_prec = e->want_tab; e->tab_flag = SWEEP_TAB32; }
-    e->plan = std::move(pl);
-    { static std::atomic<uint64_t> gen{0}; e->model_gen = ++gen; }   // (read-outs of an earlier model answer LPMP_ERR_STATE from here on)
-    e->plan->p.force_generic = e->rtype == LPMP_RTYPE_ADAPTIVE;
+    { static std::atomic<uint64_t> gen{0}; next.model_gen = ++gen; }   // (read-outs of an earlier model answer LPMP_ERR_STATE from here on)
+    p.force_generic = e->rtype == LPMP_RTYPE_ADAPTIVE;
     {   // mailbox budget of every schedule planned for this model: half of what the device has left now (LPMP_MAILBOX_MB overrides)
       size_t free_b = 0, total_b = 0;
-      if (const char* v = std::getenv("LPMP_MAILBOX_MB")) e->plan->p.mailbox_budget_bytes = (int64_t)std::atoll(v) << 20;
-      else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) e->plan->p.mailbox_budget_bytes = (int64_t)(free_b / 2);
+      if (const char* v = std::getenv("LPMP_MAILBOX_MB")) p.mailbox_budget_bytes = (int64_t)std::atoll(v) << 20;
+      else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) p.mailbox_budget_bytes = (int64_t)(free_b / 2);
       else (void)hipGetLastError();
     }
-    try { check_rtype(e, e->rtype); } catch (...) { e->release_model(); throw; }
+    check_rtype(next, e->rtype);
+    e->model = std::move(next);
   });
 }
 
@@ -1749,33 +1816,24 @@ int lpmp_set_reparametrization(lpmp_engine* e, int mode) {
     if (mode == LPMP_REPAM_MIXED) throw UnsupportedError("mixed reparametrization is assert(false) in the reference (LP_MP.h:1455)");
     if (mode < 0 || mode >= LPMP_REPAM_COUNT) throw std::runtime_error("unknown reparametrization mode");
     HIP_CHECK(hipSetDevice(e->device));
-    if (mode != e->mode) settle(e);          // (Solver::PreIterate sets the same mode before every pass, solver.hxx:268-271)
+    if (mode != e->model.mode) settle(e);          // (Solver::PreIterate sets the same mode before every pass, solver.hxx:268-271)
     // The directional schedules (ComputeForwardPass / ComputeBackwardPass, the ...AndPrimal sweeps) are built here for models of
     // ordinary size — a model the device kernels cannot run is refused at this call — and on first use for models of millions of
     // factors: LP::ComputePass runs the fused pass schedule and the partitioned drivers their own iterator-range schedules, and
     // two directional schedules nobody runs were 2.6 s of the 10 s before the first pass of the 2 M / 10 M graph
-    if (e->plan->p.nf <= LAZY_SCHEDULES_MIN_FACTORS) ensure_device_schedules(e, mode);
-    else e->plan->p.ensure_weights(mode);
-    e->mode = mode;
+    if (e->model.plan->p.nf <= LAZY_SCHEDULES_MIN_FACTORS) ensure_device_schedules(e, mode);
+    else e->model.plan->p.ensure_weights(mode);
+    e->model.mode = mode;
   });
 }
 
-// what keeps the uploaded model from running under a send rule (also checked at upload: the rule may be set first,
-// as the reference parses --reparametrizationType in LP::Begin)
-static void check_rtype(const lpmp_engine* e, int rtype) {
-  if (!e->plan) return;
-  const Plan& p = e->plan->p;
-  if (rtype == LPMP_RTYPE_RESIDUAL && p.any_batch)
-    throw UnsupportedError("residual sends with batch-capable message ops are not built (send_messages_residual's batch branch, factors_messages.hxx:2980-2991)");
-  if (rtype == LPMP_RTYPE_ADAPTIVE) { const std::string why = p.adaptive_obstacle(); if (!why.empty()) throw UnsupportedError(why); }
-}
 static void apply_rtype(lpmp_engine* e, int rtype) {
   const bool generic = rtype == LPMP_RTYPE_ADAPTIVE;
-  if (e->plan && e->plan->p.force_generic != generic) {   // other kernel classes: every built-in schedule is rebuilt
-    e->release_schedules();
-    e->plan->drop_caches();
-    e->plan->p.force_generic = generic;
-    e->mode = -1;
+  if (e->model.plan && e->model.plan->p.force_generic != generic) {   // other kernel classes: every built-in schedule is rebuilt
+    e->model.release_schedules();
+    e->model.plan->drop_caches();
+    e->model.plan->p.force_generic = generic;
+    e->model.mode = -1;
   }
   e->rtype = rtype;
 }
@@ -1784,20 +1842,20 @@ int lpmp_set_reparametrization_type(lpmp_engine* e, int rtype) {
   return guarded([&] {
     if (!e) throw std::runtime_error("null engine");
     if (rtype < LPMP_RTYPE_SHARED || rtype > LPMP_RTYPE_ADAPTIVE) throw std::runtime_error("unknown reparametrization type");
-    check_rtype(e, rtype);
+    check_rtype(e->model, rtype);
     if (rtype != e->rtype) settle(e);
     if (rtype != e->rtype) {   // captured graphs bake the kernel flag in
       HIP_CHECK(hipStreamSynchronize(e->stream));
       for (int d = 0; d < 2; ++d) for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-        e->sched[d][m].graph.reset();
+        e->model.sched[d][m].graph.reset();
       for (int m = 0; m < LPMP_REPAM_COUNT; ++m)
-        e->sched_pass[m].graph.reset();
-      for (int k = 0; k < 2; ++k) e->sched_part[k].graph.reset();
-      for (auto& c : e->custom) if (c) c->graph.reset();
+        e->model.sched_pass[m].graph.reset();
+      for (int k = 0; k < 2; ++k) e->model.sched_part[k].graph.reset();
+      for (auto& c : e->model.custom) if (c) c->graph.reset();
     }
-    const int mode = e->mode;
+    const int mode = e->model.mode;
     apply_rtype(e, rtype);
-    if (e->mode < 0 && mode >= 0) { ensure_device_schedules(e, mode); e->mode = mode; }   // the mode survives the rebuild
+    if (e->model.mode < 0 && mode >= 0) { ensure_device_schedules(e, mode); e->model.mode = mode; }   // the mode survives the rebuild
   });
 }
 
@@ -1808,7 +1866,7 @@ int lpmp_set_inner_iterations(lpmp_engine* e, int n) {
     if (n != e->inner_iterations) {
       settle(e);
       HIP_CHECK(hipStreamSynchronize(e->stream));
-      for (int k = 0; k < 2; ++k) { e->sched_part[k].release(); e->have_part[k] = false; }
+      for (int k = 0; k < 2; ++k) { e->model.sched_part[k].release(); e->model.have_part[k] = false; }
     }
     e->inner_iterations = n;
   });
@@ -1819,38 +1877,38 @@ int lpmp_set_inner_iterations(lpmp_engine* e, int n) {
 // level-scheduled as ONE schedule: inner iterations of partitions that touch no common factor run side by side.
 static void ensure_partition_schedule(lpmp_engine* e, int rtype) {
   const int k = rtype - LPMP_RTYPE_PARTITION;
-  if (e->have_part[k]) return;
+  if (e->model.have_part[k]) return;
   std::vector<Plan::Segment> segs;
-  e->plan->p.partition_pass_segments(rtype, e->inner_iterations, segs);
+  e->model.plan->p.partition_pass_segments(rtype, e->inner_iterations, segs);
   Schedule s;
-  e->plan->p.make_schedule(segs, e->use_fused, s);
-  check_generic_limits(e->plan->p, s);
-  upload_schedule(e, s, e->sched_part[k]);
-  e->have_part[k] = true;
+  e->model.plan->p.make_schedule(segs, e->use_fused, s);
+  check_generic_limits(e->model.plan->p, s);
+  upload_schedule(e, s, e->model.sched_part[k]);
+  e->model.have_part[k] = true;
 }
 
 int lpmp_compute_forward_pass(lpmp_engine* e) {
-  return guarded([&] { require_mode(e); HIP_CHECK(hipSetDevice(e->device)); settle(e); ensure_device_schedules(e, e->mode); begin_compute(e); run_schedule(e, e->sched[0][e->mode]); });
+  return guarded([&] { require_mode(e); HIP_CHECK(hipSetDevice(e->device)); settle(e); ensure_device_schedules(e, e->model.mode); begin_compute(e); run_schedule(e, e->model.sched[0][e->model.mode]); });
 }
 int lpmp_compute_backward_pass(lpmp_engine* e) {
-  return guarded([&] { require_mode(e); HIP_CHECK(hipSetDevice(e->device)); settle(e); ensure_device_schedules(e, e->mode); begin_compute(e); run_schedule(e, e->sched[1][e->mode]); });
+  return guarded([&] { require_mode(e); HIP_CHECK(hipSetDevice(e->device)); settle(e); ensure_device_schedules(e, e->model.mode); begin_compute(e); run_schedule(e, e->model.sched[1][e->model.mode]); });
 }
 static void compute_plain_passes(lpmp_engine* e, int n) {   // ComputeForwardPass(); ComputeBackwardPass(); n times
   if (e->use_fused) {
-    ensure_pass_schedule(e, e->mode);
-    if (e->rotation_ok[e->mode] && e->use_rotation) {
+    ensure_pass_schedule(e, e->model.mode);
+    if (e->model.rotation_ok[e->model.mode] && e->use_rotation) {
       // passes in slices of at most 32: each slice one persistent launch (memory of the ticket arrays stays bounded)
       int done = 0;
       while (done < n) {
         const int m = std::min(n - done, 32);
-        if (!run_rotation_chain(e, e->mode, m)) break;
+        if (!run_rotation_chain(e, e->model.mode, m)) break;
         done += m;
       }
       if (done == n) return;
       n -= done;
     }
-    if (n >= 2 && e->rotation_ok[e->mode] && e->use_rotation) {
-      const LaunchView fb = e->sched_pass[e->mode].view(), bf = e->sched_bf[e->mode].view();
+    if (n >= 2 && e->model.rotation_ok[e->model.mode] && e->use_rotation) {
+      const LaunchView fb = e->model.sched_pass[e->model.mode].view(), bf = e->model.sched_bf[e->model.mode].view();
       const bool timed = e->timing;
       issue_launches(e, fb, timed, e->stream, 1);
       issue_launches(e, fb, timed, e->stream, 2);
@@ -1858,12 +1916,12 @@ static void compute_plain_passes(lpmp_engine* e, int n) {   // ComputeForwardPas
       issue_launches(e, fb, timed, e->stream, 3);
       if (timed && e->pending.size() > 4096) e->drain_timing();
     } else {
-      ensure_pass_chain_plan(e, e->mode);
-      for (int i = 0; i < n; ++i) run_schedule(e, e->sched_pass[e->mode]);
+      ensure_pass_chain_plan(e, e->model.mode);
+      for (int i = 0; i < n; ++i) run_schedule(e, e->model.sched_pass[e->model.mode]);
     }
   } else {
-    ensure_device_schedules(e, e->mode);
-    for (int i = 0; i < n; ++i) { run_schedule(e, e->sched[0][e->mode]); run_schedule(e, e->sched[1][e->mode]); }
+    ensure_device_schedules(e, e->model.mode);
+    for (int i = 0; i < n; ++i) { run_schedule(e, e->model.sched[0][e->model.mode]); run_schedule(e, e->model.sched[1][e->model.mode]); }
   }
 }
 // build whatever lpmp_compute_pass(e, n) needs that depends on n (the ticket order of n joined passes), outside of a
@@ -1874,9 +1932,9 @@ int lpmp_prepare_passes(lpmp_engine* e, int n) {
     if (n < 1) throw std::runtime_error("bad argument");
     HIP_CHECK(hipSetDevice(e->device));
     if (e->rtype != LPMP_RTYPE_SHARED || !e->use_fused) return;
-    ensure_pass_schedule(e, e->mode);
-    if (!(e->rotation_ok[e->mode] && e->use_rotation && e->use_chain && e->use_blocked_passes)) return;
-    for (int done = 0; done < n;) { const int m = std::min(n - done, 32); (void)rotation_chain(e, e->mode, m); done += m; }
+    ensure_pass_schedule(e, e->model.mode);
+    if (!(e->model.rotation_ok[e->model.mode] && e->use_rotation && e->use_chain && e->use_blocked_passes)) return;
+    for (int done = 0; done < n;) { const int m = std::min(n - done, 32); (void)rotation_chain(e, e->model.mode, m); done += m; }
   });
 }
 // ---- speculative passes ---------------------------------------------------------------------------------------------
@@ -1892,27 +1950,27 @@ int lpmp_prepare_passes(lpmp_engine* e, int n) {
 // is invisible except in time; how far ahead is learnt from the caller: batches double while single passes keep coming
 // and restart at the length of the previous run (MpRoundingSolver: four plain passes between two rounding iterations).
 static void spec_interrupt(lpmp_engine* e) {
-  auto& sp = e->spec;
+  auto& sp = e->model.batch;
   if (sp.run_len > 0) sp.learned = sp.run_len;
   sp.run_len = 0; sp.last_batch = 0;
 }
 static void settle(lpmp_engine* e) {
   if (!e) return;
-  auto& sp = e->spec;
+  auto& sp = e->model.batch;
   if (sp.n > 0) {
     const int n = sp.n, pos = sp.pos;
     sp.n = 0; sp.pos = 0; sp.lb_ready = false;
-    if (pos < n && e->plan) {   // the caller stopped inside the batch: back to its start, then exactly the passes it asked for
+    if (pos < n && e->model.plan) {   // the caller stopped inside the batch: back to its start, then exactly the passes it asked for
       HIP_CHECK(hipSetDevice(e->device));
-      const size_t nd = (size_t)e->plan->p.f_doff[e->plan->p.nf], nf = (size_t)e->plan->p.nf;
-      HIP_CHECK(hipMemcpyAsync(e->d_dual, sp.d_snap, nd * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      HIP_CHECK(hipMemcpyAsync(e->d_lb, sp.d_snap + nd, nf * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      e->lb_all_stale = sp.snap_lb_stale;
-      ++sp.rollbacks;
-      const int mode = e->mode;
-      e->mode = sp.mode;          // (set_reparametrization settles before it changes the mode)
-      try { compute_plain_passes(e, pos); } catch (...) { e->mode = mode; throw; }
-      e->mode = mode;
+      const size_t nd = (size_t)e->model.plan->p.f_doff[e->model.plan->p.nf], nf = (size_t)e->model.plan->p.nf;
+      HIP_CHECK(hipMemcpyAsync(e->model.d_dual, sp.d_snap, nd * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      HIP_CHECK(hipMemcpyAsync(e->model.d_lb, sp.d_snap + nd, nf * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      e->model.lb_all_stale = sp.snap_lb_stale;
+      ++e->spec.rollbacks;
+      const int mode = e->model.mode;
+      e->model.mode = sp.mode;          // (set_reparametrization settles before it changes the mode)
+      try { compute_plain_passes(e, pos); } catch (...) { e->model.mode = mode; throw; }
+      e->model.mode = mode;
     }
   }
   spec_interrupt(e);
@@ -1923,13 +1981,13 @@ static void lb_sum_blocks(int64_t nf, int64_t& nb, int64_t& per) {   // the part
   nb = (nf + per - 1) / per;
 }
 static bool spec_start_batch(lpmp_engine* e, int depth) {
-  auto& sp = e->spec;
-  ensure_pass_schedule(e, e->mode);
+  auto& sp = e->model.batch;
+  ensure_pass_schedule(e, e->model.mode);
   // (the bound rows are written by the dense chain body only: kernels.hip, dense_pk_body)
-  if (!(e->rotation_ok[e->mode] && e->plan->rot[e->mode].valid && e->plan->rot[e->mode].hist_ok && kc_is_dense(e->plan->rot[e->mode].kclass))) return false;
+  if (!(e->model.rotation_ok[e->model.mode] && e->model.plan->rot[e->model.mode].valid && e->model.plan->rot[e->model.mode].hist_ok && kc_is_dense(e->model.plan->rot[e->model.mode].kclass))) return false;
   depth = std::min(depth, 32);
-  if (!rotation_chain(e, e->mode, depth)) return false;
-  const size_t nd = (size_t)e->plan->p.f_doff[e->plan->p.nf], nf = (size_t)e->plan->p.nf;
+  if (!rotation_chain(e, e->model.mode, depth)) return false;
+  const size_t nd = (size_t)e->model.plan->p.f_doff[e->model.plan->p.nf], nf = (size_t)e->model.plan->p.nf;
   // (an allocation that fails switches speculation OFF for this engine — the plain pass needs none of these buffers — instead
   // of making every lpmp_compute_pass(e, 1) fail on a model that solves fine without: snapshot = all duals + tracked bounds)
   auto grow = [&](DevBuf<double>& b, size_t want) -> bool {
@@ -1937,39 +1995,38 @@ static bool spec_start_batch(lpmp_engine* e, int depth) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
     return b.try_alloc(want);
   };
-  if (!grow(sp.d_snap, nd + nf) || !grow(sp.d_hist, (size_t)(std::min(sp.max_depth, 32) - 1) * nf) ||
-      !grow(sp.d_hpart, (size_t)(std::min(sp.max_depth, 32) - 1) * 1024)) {
-    sp.release();
-    sp.max_depth = 0;
-    ++sp.alloc_failures;
+  if (!grow(sp.d_snap, nd + nf) || !grow(sp.d_hist, (size_t)(std::min(e->spec.max_depth, 32) - 1) * nf) ||
+      !grow(sp.d_hpart, (size_t)(std::min(e->spec.max_depth, 32) - 1) * 1024)) {
+    sp = SpecBatch();
+    e->spec.max_depth = 0;
+    ++e->spec.alloc_failures;
     return false;
   }
-  HIP_CHECK(hipMemcpyAsync(sp.d_snap, e->d_dual, nd * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  HIP_CHECK(hipMemcpyAsync(sp.d_snap + nd, e->d_lb, nf * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-  sp.snap_lb_stale = e->lb_all_stale;
-  if (!run_rotation_chain(e, e->mode, depth, sp.d_hist)) return false;
+  HIP_CHECK(hipMemcpyAsync(sp.d_snap, e->model.d_dual, nd * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  HIP_CHECK(hipMemcpyAsync(sp.d_snap + nd, e->model.d_lb, nf * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  sp.snap_lb_stale = e->model.lb_all_stale;
+  if (!run_rotation_chain(e, e->model.mode, depth, sp.d_hist)) return false;
   // the device is `depth` passes ahead from here on: the batch is open BEFORE anything else can fail, so that settle() rolls back
-  sp.n = depth; sp.pos = 0; sp.mode = e->mode; sp.lb_ready = false; sp.last_batch = depth;
-  ++sp.batches; sp.passes_launched += depth;
+  sp.n = depth; sp.pos = 0; sp.mode = e->model.mode; sp.lb_ready = false; sp.last_batch = depth;
+  ++e->spec.batches; e->spec.passes_launched += depth;
   int64_t nb, per; lb_sum_blocks((int64_t)nf, nb, per);
   for (int i = 0; i < depth - 1; ++i) launch_sum_stage(sp.d_hist + (size_t)i * nf, sp.d_hpart + (size_t)i * 1024, (int64_t)nf, per, nb, e->stream);
   HIP_CHECK(hipGetLastError());
   return true;
 }
-static void check_chain(lpmp_engine* e);
 // the bound of the pass the caller is at, while that pass lies inside an open batch
 static bool spec_lower_bound(lpmp_engine* e, double* out) {
-  auto& sp = e->spec;
+  auto& sp = e->model.batch;
   if (!(sp.n > 0 && sp.pos < sp.n)) return false;
   if (!sp.lb_ready) {
     check_chain(e);
-    const int64_t nf = e->plan->p.nf;
+    const int64_t nf = e->model.plan->p.nf;
     int64_t nb, per; lb_sum_blocks(nf, nb, per);
     std::vector<double> h((size_t)(sp.n - 1) * 1024);
     d2h(h.data(), sp.d_hpart, h.size() * sizeof(double), e->stream);
     sp.lb.assign((size_t)sp.n - 1, 0.0);
     for (int i = 0; i < sp.n - 1; ++i) {
-      double lb = e->plan->p.constant;
+      double lb = e->model.plan->p.constant;
       for (int64_t j = 0; j < nb; ++j) lb += h[(size_t)i * 1024 + j];
       sp.lb[i] = lb;
     }
@@ -1980,7 +2037,7 @@ static bool spec_lower_bound(lpmp_engine* e, double* out) {
 }
 static bool spec_usable(const lpmp_engine* e) {
   return e->spec.max_depth >= 2 && e->rtype == LPMP_RTYPE_SHARED && e->use_fused && e->use_rotation && e->use_chain &&
-         e->use_blocked_passes && e->use_lb_tracking && !e->timing && !e->rows;
+         e->use_blocked_passes && e->use_lb_tracking && !e->timing && !e->model.rows;
 }
 
 int lpmp_set_speculation(lpmp_engine* e, int max_passes_ahead) {
@@ -1989,7 +2046,7 @@ int lpmp_set_speculation(lpmp_engine* e, int max_passes_ahead) {
     if (max_passes_ahead < 0) throw std::runtime_error("bad argument");
     settle(e);
     e->spec.max_depth = std::min(max_passes_ahead, 32);
-    if (e->spec.max_depth < 2) { HIP_CHECK(hipStreamSynchronize(e->stream)); const int d = e->spec.max_depth; e->spec.release(); e->spec.max_depth = d; }
+    if (e->spec.max_depth < 2) { HIP_CHECK(hipStreamSynchronize(e->stream)); e->model.batch = SpecBatch(); }
   });
 }
 int lpmp_speculation_stats(lpmp_engine* e, int64_t* batches, int64_t* passes_launched, int64_t* passes_used, int64_t* rollbacks) {
@@ -2001,7 +2058,7 @@ int lpmp_speculation_stats(lpmp_engine* e, int64_t* batches, int64_t* passes_lau
     if (rollbacks) *rollbacks = e->spec.rollbacks;
   });
 }
-int64_t lpmp_chain_cache_bytes(const lpmp_engine* e) { return e ? (int64_t)e->rot_cache_bytes : 0; }
+int64_t lpmp_chain_cache_bytes(const lpmp_engine* e) { return e ? (int64_t)e->model.rot_cache_bytes : 0; }
 
 int lpmp_compute_pass(lpmp_engine* e, int n) {   // LP::ComputePass, LP_MP.h:869-887
   return guarded([&] {
@@ -2009,25 +2066,25 @@ int lpmp_compute_pass(lpmp_engine* e, int n) {   // LP::ComputePass, LP_MP.h:869
     HIP_CHECK(hipSetDevice(e->device));
     begin_compute(e);
     if (n == 1 && e->spec.max_depth >= 2) {
-      auto& sp = e->spec;
+      auto& sp = e->model.batch;
       if (sp.n > 0) {
-        if (sp.pos < sp.n) { ++sp.pos; ++sp.run_len; ++sp.passes_used; return; }   // already on its way
+        if (sp.pos < sp.n) { ++sp.pos; ++sp.run_len; ++e->spec.passes_used; return; }   // already on its way
         sp.n = 0; sp.pos = 0; sp.lb_ready = false;                                  // used up: the device state is the caller's
       }
       if (spec_usable(e)) {
         int depth = sp.run_len == 0 ? (sp.learned > 0 ? sp.learned : 2) : std::max(2, 2 * sp.last_batch);
-        depth = std::min(depth, sp.max_depth);
-        if (depth >= 2 && spec_start_batch(e, depth)) { sp.pos = 1; ++sp.run_len; ++sp.passes_used; return; }
+        depth = std::min(depth, e->spec.max_depth);
+        if (depth >= 2 && spec_start_batch(e, depth)) { sp.pos = 1; ++sp.run_len; ++e->spec.passes_used; return; }
       }
       ++sp.run_len; sp.last_batch = 0;
       if (e->rtype == LPMP_RTYPE_SHARED) { compute_plain_passes(e, 1); return; }
     } else settle(e);
     if (e->rtype == LPMP_RTYPE_PARTITION) {
       ensure_partition_schedule(e, e->rtype);
-      for (int i = 0; i < n; ++i) run_schedule(e, e->sched_part[0]);
+      for (int i = 0; i < n; ++i) run_schedule(e, e->model.sched_part[0]);
     } else if (e->rtype == LPMP_RTYPE_OVERLAPPING_PARTITION) {
       ensure_partition_schedule(e, e->rtype);
-      for (int i = 0; i < n; ++i) { run_schedule(e, e->sched_part[1]); compute_plain_passes(e, 1); }
+      for (int i = 0; i < n; ++i) { run_schedule(e, e->model.sched_part[1]); compute_plain_passes(e, 1); }
     } else {
       compute_plain_passes(e, n);
     }
@@ -2043,16 +2100,16 @@ int lpmp_compute_pass(lpmp_engine* e, int n) {   // LP::ComputePass, LP_MP.h:869
 // stops at the pairwise factor (its other side is unset or already equal).
 // init_primal of every factor: an unset entry holds the dimension (what PrimalInit records say for the touched ones)
 static void upload_unset_primal(lpmp_engine* e) {
-  const Plan& p = e->plan->p;
+  const Plan& p = e->model.plan->p;
   if (p.nf <= 0) return;
   std::vector<int32_t> h(2 * (size_t)p.nf);
   for (int64_t f = 0; f < p.nf; ++f) { h[2 * f] = p.f_dim0[f]; h[2 * f + 1] = p.f_kind[f] == LPMP_F_VECTOR ? 0 : p.f_dim1[f]; }
-  h2d(e->d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
+  h2d(e->model.d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
 }
 static void ensure_primal(lpmp_engine* e) {
-  if (e->have_primal) return;
-  e->release_primal();   // a previous attempt may have stopped half way
-  const Plan& p = e->plan->p;
+  if (e->model.have_primal) return;
+  e->model.release_primal();   // a previous attempt may have stopped half way
+  const Plan& p = e->model.plan->p;
   for (const auto& mt : p.mtypes)
     if (mt.kind != LPMP_M_UNARY_PAIRWISE)
       throw UnsupportedError("primal rounding is built for unary / pairwise models (DESIGN.md 8)");
@@ -2090,33 +2147,32 @@ static void ensure_primal(lpmp_engine* e) {
     for (int64_t m = 0; m < p.nm; ++m) if (touched[p.m_right[m]]) touched[p.m_left[m]] = 2;
     std::vector<int32_t> h(2 * (size_t)p.nf);
     for (size_t i = 0; i < h.size(); ++i) h[i] = writer[i];
-    e->d_pw_unary.alloc(std::max<size_t>(1, h.size()));
-    if (!h.empty()) h2d(e->d_pw_unary, h.data(), h.size() * sizeof(int32_t), e->stream);
+    e->model.d_pw_unary.alloc(std::max<size_t>(1, h.size()));
+    if (!h.empty()) h2d(e->model.d_pw_unary, h.data(), h.size() * sizeof(int32_t), e->stream);
   }
   for (int64_t f = 0; f < p.nf; ++f) if (p.updated[f]) touched[f] = 1;
   auto unset = [&](int64_t f) { return PrimalInit{(int32_t)f, p.f_dim0[f], p.f_kind[f] == LPMP_F_VECTOR ? 0 : p.f_dim1[f], 0}; };
   std::vector<PrimalInit> init;
   for (int64_t f = 0; f < p.nf; ++f) if (touched[f]) init.push_back(unset(f));
-  e->n_pprop = (int64_t)prop.size();
+  e->model.n_pprop = (int64_t)prop.size();
   prop.insert(prop.end(), rest.begin(), rest.end());
-  e->n_plinks = (int64_t)prop.size();
-  e->n_pinit = (int64_t)init.size();
-  e->d_primal.alloc(std::max<size_t>(1, 2 * (size_t)p.nf));
-  e->d_pcost.alloc(std::max<size_t>(1, (size_t)p.nf));
-  e->d_pbad.alloc(1);
-  e->h_pbad = (int*)(e->pinned + 8 * 1024 + 64);               // one flag (the block exists: a model is uploaded)
+  e->model.n_plinks = (int64_t)prop.size();
+  e->model.n_pinit = (int64_t)init.size();
+  e->model.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)p.nf));
+  e->model.d_pcost.alloc(std::max<size_t>(1, (size_t)p.nf));
+  e->model.d_pbad.alloc(1);
   if (!prop.empty()) {
-    e->d_plinks.alloc(prop.size());
-    h2d(e->d_plinks, prop.data(), prop.size() * sizeof(PrimalLink), e->stream);
+    e->model.d_plinks.alloc(prop.size());
+    h2d(e->model.d_plinks, prop.data(), prop.size() * sizeof(PrimalLink), e->stream);
   }
   // every factor starts unset (init_primal), then only the touched ones are ever re-initialised
   upload_unset_primal(e);
   if (!init.empty()) {
-    e->d_pinit.alloc(init.size());
-    h2d(e->d_pinit, init.data(), init.size() * sizeof(PrimalInit), e->stream);
+    e->model.d_pinit.alloc(init.size());
+    h2d(e->model.d_pinit, init.data(), init.size() * sizeof(PrimalInit), e->stream);
   }
-  e->primal_t = 0;
-  e->have_primal = true;
+  e->model.primal_t = 0;
+  e->model.have_primal = true;
 }
 
 static void run_primal_sweep(lpmp_engine* e, int d, uint64_t t) {
@@ -2127,16 +2183,16 @@ static void run_primal_sweep(lpmp_engine* e, int d, uint64_t t) {
   ensure_primal(e);
   // the reference asserts primal_access_ <= timestamp (factors_messages.hxx:3304); in a release build a smaller
   // stamp lowers primal_access_ of the rounded factors only and later passes depend on the update order
-  if (t < e->primal_t) throw std::runtime_error("primal pass: time stamps (2*iteration+1 / +2) must not decrease");
-  if (t > e->primal_t) {   // conditionally_init_primal: primal_access_ < timestamp
-    launch_primal_init(e->d_pinit, e->n_pinit, e->d_primal, e->stream);
-    e->primal_t = t;
+  if (t < e->model.primal_t) throw std::runtime_error("primal pass: time stamps (2*iteration+1 / +2) must not decrease");
+  if (t > e->model.primal_t) {   // conditionally_init_primal: primal_access_ < timestamp
+    launch_primal_init(e->model.d_pinit, e->model.n_pinit, e->model.d_primal, e->stream);
+    e->model.primal_t = t;
   }
-  ensure_device_schedules(e, e->mode);
+  ensure_device_schedules(e, e->model.mode);
   e->primal_pass = true;
-  try { run_schedule(e, e->sched[d][e->mode]); } catch (...) { e->primal_pass = false; throw; }
+  try { run_schedule(e, e->model.sched[d][e->model.mode]); } catch (...) { e->primal_pass = false; throw; }
   e->primal_pass = false;
-  launch_primal_propagate(e->d_plinks, e->n_pprop, e->d_primal, e->stream);
+  launch_primal_propagate(e->model.d_plinks, e->model.n_pprop, e->model.d_primal, e->stream);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2151,9 +2207,9 @@ int lpmp_compute_pass_and_primal(lpmp_engine* e, uint64_t iteration) {
 }
 
 static bool primal_consistent(lpmp_engine* e) {
-  HIP_CHECK(hipMemsetAsync(e->d_pbad, 0, sizeof(int), e->stream));
-  launch_primal_check(e->d_plinks, e->n_plinks, e->d_primal, e->d_pbad, e->stream);
-  HIP_CHECK(hipMemcpyAsync(e->h_pbad, e->d_pbad, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_CHECK(hipMemsetAsync(e->model.d_pbad, 0, sizeof(int), e->stream));
+  launch_primal_check(e->model.d_plinks, e->model.n_plinks, e->model.d_primal, e->model.d_pbad, e->stream);
+  HIP_CHECK(hipMemcpyAsync(e->h_pbad, e->model.d_pbad, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipStreamSynchronize(e->stream));
   return *e->h_pbad == 0;
 }
@@ -2176,16 +2232,16 @@ int lpmp_evaluate_primal(lpmp_engine* e, double* cost) {
     require_consts(e);
     ensure_primal(e);
     if (!primal_consistent(e)) { *cost = std::numeric_limits<double>::infinity(); return; }
-    const int64_t nf = e->plan->p.nf;
+    const int64_t nf = e->model.plan->p.nf;
     rows_refresh(e);
-    launch_primal_cost(e->d_lbrecs, e->d_dual, e->d_const, e->d_primal, e->d_pcost, nf, e->tab_flag, e->stream);
+    launch_primal_cost(e->model.d_lbrecs, e->model.d_dual, e->model.d_const, e->model.d_primal, e->model.d_pcost, nf, e->model.tab_flag, e->stream);
     int64_t nb = std::min<int64_t>(1024, (nf + 255) / 256);
     const int64_t per = (nf + nb - 1) / nb;
     nb = (nf + per - 1) / per;
-    launch_sum_stage(e->d_pcost, e->d_part, nf, per, nb, e->stream);
-    HIP_CHECK(hipMemcpyAsync(e->h_part, e->d_part, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    launch_sum_stage(e->model.d_pcost, e->model.d_part, nf, per, nb, e->stream);
+    HIP_CHECK(hipMemcpyAsync(e->h_part, e->model.d_part, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    double c = e->plan->p.constant;
+    double c = e->model.plan->p.constant;
     for (int64_t i = 0; i < nb; ++i) c += e->h_part[i];
     *cost = c;
   });
@@ -2197,7 +2253,7 @@ int lpmp_download_primal(lpmp_engine* e, int32_t* out) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
     ensure_primal(e);
-    d2h(out, e->d_primal, 2 * (size_t)e->plan->p.nf * sizeof(int32_t), e->stream);
+    d2h(out, e->model.d_primal, 2 * (size_t)e->model.plan->p.nf * sizeof(int32_t), e->stream);
   });
 }
 int lpmp_upload_primal(lpmp_engine* e, const int32_t* in) {
@@ -2207,7 +2263,7 @@ int lpmp_upload_primal(lpmp_engine* e, const int32_t* in) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
     ensure_primal(e);
-    h2d(e->d_primal, in, 2 * (size_t)e->plan->p.nf * sizeof(int32_t), e->stream);
+    h2d(e->model.d_primal, in, 2 * (size_t)e->model.plan->p.nf * sizeof(int32_t), e->stream);
   });
 }
 
@@ -2216,11 +2272,11 @@ int lpmp_upload_primal(lpmp_engine* e, const int32_t* in) {
 // lane group per unary; class 1: a wave per unary — with the device offsets of the uploaded model (rows layout, float tables and
 // SHARED / DIFF cells are all behind Plan::doff / coff).  A function of the structure, like a schedule, and counted as one.
 static void ensure_decode(lpmp_engine* e, int d) {
-  lpmp_engine::DevDecode& dd = e->decode[d];
+  DevDecode& dd = e->model.decode[d];
   if (dd.have) return;
   dd.release();
-  const DecodePlan& dp = decode_plan_or_refuse(e->plan.get(), d);
-  const Plan& p = e->plan->p;
+  const DecodePlan& dp = decode_plan_or_refuse(e->model.plan.get(), d);
+  const Plan& p = e->model.plan->p;
   const size_t nu = dp.unaries.size();
   auto bucket = [&](size_t i) { return 2 * (size_t)(dp.level[i] - 1) + (p.f_dim0[dp.unaries[i]] > DECODE_GROUP_MAX ? 1 : 0); };
   std::vector<int64_t> start(2 * (size_t)dp.n_levels + 1, 0);
@@ -2247,7 +2303,7 @@ static void ensure_decode(lpmp_engine* e, int d) {
   if (nu) { dd.recs.alloc(nu); h2d(dd.recs, recs.data(), nu * sizeof(DecodeRec), e->stream); }
   if (!links.empty()) { dd.links.alloc(links.size()); h2d(dd.links, links.data(), links.size() * sizeof(DecodeLink), e->stream); }
   dd.have = true;
-  ++e->schedules_built;
+  ++e->model.schedules_built;
   deep_schedule_note(e, dp.n_levels, "the decode order");
 }
 
@@ -2262,11 +2318,11 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
     ensure_decode(e, direction);
     ensure_primal(e);
     rows_refresh(e);           // (reads the rows; writes no dual)
-    const lpmp_engine::DevDecode& dd = e->decode[direction];
+    const DevDecode& dd = e->model.decode[direction];
     for (int sweep = 0; sweep <= refine_sweeps; ++sweep)
       for (const auto& l : dd.launches)
-        launch_decode(dd.recs, dd.links, e->d_dual, e->d_const, e->d_primal, l.first, l.count, l.width, l.level, sweep ? DECODE_ALL : 0, e->tab_flag, e->stream);
-    launch_primal_propagate(e->d_plinks, e->n_plinks, e->d_primal, e->stream);   // every message's pairwise slot := its unary's label
+        launch_decode(dd.recs, dd.links, e->model.d_dual, e->model.d_const, e->model.d_primal, l.first, l.count, l.width, l.level, sweep ? DECODE_ALL : 0, e->model.tab_flag, e->stream);
+    launch_primal_propagate(e->model.d_plinks, e->model.n_plinks, e->model.d_primal, e->stream);   // every message's pairwise slot := its unary's label
     HIP_CHECK(hipGetLastError());
   });
 }
@@ -2275,7 +2331,7 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
 // The output twin of lpmp_set_vectors, prepared like a schedule: the record list is uploaded at create, a call uploads nothing.
 struct lpmp_readout {
   int device = 0;
-  uint64_t gen = 0;                     // lpmp_engine::model_gen of the model it was made for
+  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
   int64_t n = 0;
   int32_t max_labels = 0;
   std::vector<int32_t> factors, d0;     // the list, and every row's label count (a host destination is filled row by row)
@@ -2296,7 +2352,7 @@ static const int32_t READOUT_CLASS_WIDTH[6] = {4, 8, 16, READOUT_GROUP_MAX, 64, 
 static void ensure_readout_links(lpmp_engine* e, lpmp_readout* r) {
   if (r->have_links) return;
   r->brecs.reset(); r->links.reset(); r->launches.clear();
-  const Plan& p = e->plan->p;
+  const Plan& p = e->model.plan->p;
   int64_t start[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int64_t i = 0; i < r->n; ++i) ++start[readout_class(r->d0[(size_t)i]) + 1];
   for (int c = 0; c < 6; ++c) start[c + 1] += start[c];
@@ -2322,17 +2378,17 @@ static void ensure_readout_links(lpmp_engine* e, lpmp_readout* r) {
   if (r->n) { r->brecs.alloc((size_t)r->n); h2d(r->brecs, recs.data(), recs.size() * sizeof(ReadoutRec), e->stream); }
   if (!links.empty()) { r->links.alloc(links.size()); h2d(r->links, links.data(), links.size() * sizeof(DecodeLink), e->stream); }
   r->have_links = true;
-  ++e->schedules_built;
+  ++e->model.schedules_built;
 }
 
 int lpmp_readout_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_readout** out) {
   return guarded([&] {
-    if (!e || !e->plan) throw StateError("lpmp_readout_create: no model uploaded (a read-out lists factors of the uploaded model)");
+    if (!e || !e->model.plan) throw StateError("lpmp_readout_create: no model uploaded (a read-out lists factors of the uploaded model)");
     if (!out || (factors && n < 0)) throw std::runtime_error("lpmp_readout_create: bad argument");
     HIP_CHECK(hipSetDevice(e->device));
-    const Plan& p = e->plan->p;
+    const Plan& p = e->model.plan->p;
     auto r = std::make_unique<lpmp_readout>();
-    r->device = e->device; r->gen = e->model_gen;
+    r->device = e->device; r->gen = e->model.model_gen;
     if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) r->factors.push_back((int32_t)f); }
     else {
       r->factors.reserve((size_t)n);
@@ -2376,7 +2432,7 @@ int32_t lpmp_readout_max_labels(const lpmp_readout* r) { return r ? r->max_label
 // are settled (the state read is that of the pass the caller is at)
 static void readout_enter(lpmp_engine* e, lpmp_readout* r, const void* dst, int dst_mem, const int64_t* dst_stride, const char* who) {
   if (!e || !r) throw std::runtime_error(std::string(who) + ": null argument");
-  if (!e->plan || r->gen != e->model_gen) throw StateError(std::string(who) + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
+  if (!e->model.plan || r->gen != e->model.model_gen) throw StateError(std::string(who) + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
   if (dst_mem != LPMP_MEM_HOST && dst_mem != LPMP_MEM_DEVICE) throw std::runtime_error(std::string(who) + ": dst_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
   if (r->n > 0 && !dst) throw std::runtime_error(std::string(who) + ": null destination");
   if (dst_stride && *dst_stride < r->max_labels)
@@ -2393,15 +2449,15 @@ static void readout_rows(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
   if (dst_mem == LPMP_MEM_DEVICE) { launch(dst, dst_stride); HIP_CHECK(hipGetLastError()); return; }
   const size_t total = (size_t)r->n * (size_t)r->max_labels;
   if (total == 0) return;
-  e->d_readout.grow(total);
-  launch(e->d_readout.get(), (int64_t)r->max_labels);
+  e->model.d_readout.grow(total);
+  launch(e->model.d_readout.get(), (int64_t)r->max_labels);
   HIP_CHECK(hipGetLastError());
   // (whole rows, one staging chunk at a time: no second buffer of the size of the read-out on the host)
   const int64_t L = r->max_labels, per = std::max<int64_t>(1, (int64_t)(STAGE_CHUNK / sizeof(double)) / L);
   std::vector<double> rows((size_t)(std::min(per, r->n) * L));
   for (int64_t first = 0; first < r->n; first += per) {
     const int64_t cnt = std::min(per, r->n - first);
-    d2h(rows.data(), e->d_readout.get() + first * L, (size_t)(cnt * L) * sizeof(double), e->stream);
+    d2h(rows.data(), e->model.d_readout.get() + first * L, (size_t)(cnt * L) * sizeof(double), e->stream);
     for (int64_t i = 0; i < cnt; ++i)
       std::copy(rows.begin() + i * L, rows.begin() + i * L + r->d0[(size_t)(first + i)], dst + (first + i) * dst_stride);
   }
@@ -2411,20 +2467,20 @@ int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_m
   return guarded([&] {
     readout_enter(e, r, dst, dst_mem, nullptr, "lpmp_readout_labels");
     if (r->n == 0) return;
-    if (!e->have_primal && !e->primal_unset_only) {
+    if (!e->model.have_primal && !e->model.primal_unset_only) {
       try { ensure_primal(e); }
       catch (const UnsupportedError&) {
         // a model the rounding code does not take (messages other than unary-pairwise): no call can set a label, every slot is
         // unset.  The array is made once and remembered until release_primal (the model goes, or another call tries the rounding tables)
-        e->d_primal.alloc(std::max<size_t>(1, 2 * (size_t)e->plan->p.nf));
+        e->model.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)e->model.plan->p.nf));
         upload_unset_primal(e);
-        e->primal_unset_only = true;
+        e->model.primal_unset_only = true;
       }
     }
-    if (dst_mem == LPMP_MEM_DEVICE) { launch_readout_labels(r->recs, r->n, e->d_primal, dst, e->stream); HIP_CHECK(hipGetLastError()); return; }
-    e->d_readout.grow(((size_t)r->n + 1) / 2);
-    int32_t* stage = reinterpret_cast<int32_t*>(e->d_readout.get());
-    launch_readout_labels(r->recs, r->n, e->d_primal, stage, e->stream);
+    if (dst_mem == LPMP_MEM_DEVICE) { launch_readout_labels(r->recs, r->n, e->model.d_primal, dst, e->stream); HIP_CHECK(hipGetLastError()); return; }
+    e->model.d_readout.grow(((size_t)r->n + 1) / 2);
+    int32_t* stage = reinterpret_cast<int32_t*>(e->model.d_readout.get());
+    launch_readout_labels(r->recs, r->n, e->model.d_primal, stage, e->stream);
     HIP_CHECK(hipGetLastError());
     d2h(dst, stage, (size_t)r->n * sizeof(int32_t), e->stream);
   });
@@ -2435,7 +2491,7 @@ int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
     if (r->n == 0) return;
     // (vector factors live in the packed array under every layout: nothing of the rows is read)
     readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
-      launch_readout_vectors(r->recs, r->n, r->max_labels, e->d_dual, d, stride, e->stream);
+      launch_readout_vectors(r->recs, r->n, r->max_labels, e->model.d_dual, d, stride, e->stream);
     });
   });
 }
@@ -2449,7 +2505,7 @@ int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
     rows_refresh(e);           // (reads the rows; writes no dual)
     readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
       for (const auto& l : r->launches)
-        launch_readout_beliefs(r->brecs, r->links, e->d_dual, e->d_const, d, stride, l.first, l.count, l.width, e->tab_flag, e->stream);
+        launch_readout_beliefs(r->brecs, r->links, e->model.d_dual, e->model.d_const, d, stride, l.first, l.count, l.width, e->model.tab_flag, e->stream);
     });
   });
 }
@@ -2465,11 +2521,11 @@ int lpmp_compute_pass_custom(lpmp_engine* e, int64_t n, const int32_t* factors, 
     begin_compute(e);
     Schedule s;
     static const double dz = 0; static const uint8_t uz = 0;
-    e->plan->p.make_schedule(factors, n, om_off, om ? om : &dz, mk_off, mk ? mk : &uz, s);
-    check_generic_limits(e->plan->p, s);
+    e->model.plan->p.make_schedule(factors, n, om_off, om ? om : &dz, mk_off, mk ? mk : &uz, s);
+    check_generic_limits(e->model.plan->p, s);
     // the schedule lives in a scratch buffer of the engine that is refilled in place: no allocation per call
-    DevSchedule& d = e->scratch;
-    upload_schedule(e, s, d, true, e->plan->p.force_generic);
+    DevSchedule& d = e->model.scratch;
+    upload_schedule(e, s, d, true, e->model.plan->p.force_generic);
     const bool g = e->use_graph; e->use_graph = false;
     try { run_schedule(e, d); } catch (...) { e->use_graph = g; throw; }
     e->use_graph = g;
@@ -2491,20 +2547,20 @@ int lpmp_schedule_create_fused(lpmp_engine* e, int64_t n, const int32_t* factors
     Schedule s;
     static const double dz = 0; static const uint8_t uz = 0;
     static const int64_t zero_off[1] = {0};
-    e->plan->p.make_schedule(std::vector<Plan::Segment>{Plan::Segment{factors, n, n > 0 ? om_off : zero_off, om ? om : &dz,
+    e->model.plan->p.make_schedule(std::vector<Plan::Segment>{Plan::Segment{factors, n, n > 0 ? om_off : zero_off, om ? om : &dz,
                                                                       n > 0 ? mk_off : zero_off, mk ? mk : &uz}},
                              fuse != 0 && e->use_fused, s);
-    check_generic_limits(e->plan->p, s);
+    check_generic_limits(e->model.plan->p, s);
     auto d = std::make_unique<DevSchedule>();
-    upload_schedule(e, s, *d, false, e->plan->p.force_generic);
-    e->custom.push_back(std::move(d));
-    *id_out = (int)e->custom.size() - 1;
+    upload_schedule(e, s, *d, false, e->model.plan->p.force_generic);
+    e->model.custom.push_back(std::move(d));
+    *id_out = (int)e->model.custom.size() - 1;
   });
 }
 static DevSchedule& custom_schedule(lpmp_engine* e, int id) {
   require_model(e);
-  if (id < 0 || id >= (int)e->custom.size() || !e->custom[id]) throw std::runtime_error("unknown schedule id");
-  return *e->custom[id];
+  if (id < 0 || id >= (int)e->model.custom.size() || !e->model.custom[id]) throw std::runtime_error("unknown schedule id");
+  return *e->model.custom[id];
 }
 int lpmp_schedule_run(lpmp_engine* e, int id) {
   return guarded([&] {
@@ -2532,7 +2588,7 @@ int lpmp_schedule_destroy(lpmp_engine* e, int id) {
   return guarded([&] {
     (void)custom_schedule(e, id);
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    e->custom[id].reset();
+    e->model.custom[id].reset();
   });
 }
 
@@ -2561,28 +2617,28 @@ static void compute_factor_lbs(lpmp_engine* e) {
   require_consts(e);
   check_chain(e);
   rows_refresh(e);
-  if (e->use_lb_tracking && !e->lb_all_stale) {
+  if (e->use_lb_tracking && !e->model.lb_all_stale) {
     // the sweep kernels kept d_lb current except for the entries they marked NaN: recompute only those
-    const int64_t nf = e->plan->p.nf;
-    HIP_CHECK(hipMemsetAsync(e->d_stale_n, 0, sizeof(unsigned long long), e->stream));
-    launch_lb_collect_stale(e->d_lb, nf, e->d_stale, e->d_stale_n, e->stream);
-    HIP_CHECK(hipMemcpyAsync(e->h_stale_n, e->d_stale_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    const int64_t nf = e->model.plan->p.nf;
+    HIP_CHECK(hipMemsetAsync(e->model.d_stale_n, 0, sizeof(unsigned long long), e->stream));
+    launch_lb_collect_stale(e->model.d_lb, nf, e->model.d_stale, e->model.d_stale_n, e->stream);
+    HIP_CHECK(hipMemcpyAsync(e->h_stale_n, e->model.d_stale_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     HIP_CHECK(hipStreamSynchronize(e->stream));
     const int64_t n_stale = (int64_t)*e->h_stale_n;
     if (n_stale <= nf / 8) {
-      launch_factor_lb_list(e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, e->d_stale, n_stale, e->tab_flag, e->stream);
+      launch_factor_lb_list(e->model.d_lbrecs, e->model.d_dual, e->model.d_const, e->model.d_lb, e->model.d_stale, n_stale, e->model.tab_flag, e->stream);
       HIP_CHECK(hipGetLastError());
       e->last_lb_recomputed = n_stale;
       return;
     }
   }
-  e->last_lb_recomputed = e->plan->p.nf;
-  for (const auto& r : e->lb_runs) {
-    if (r.cls == 0 || !launch_dense_lb(r.cls, e->d_lbrecs, e->d_dual, e->d_const, e->d_lb, r.first, r.count, e->tab_flag, e->stream))
-      launch_factor_lb(e->d_lbrecs + r.first, e->d_dual, e->d_const, e->d_lb + r.first, r.count, e->tab_flag, e->stream);
+  e->last_lb_recomputed = e->model.plan->p.nf;
+  for (const auto& r : e->model.lb_runs) {
+    if (r.cls == 0 || !launch_dense_lb(r.cls, e->model.d_lbrecs, e->model.d_dual, e->model.d_const, e->model.d_lb, r.first, r.count, e->model.tab_flag, e->stream))
+      launch_factor_lb(e->model.d_lbrecs + r.first, e->model.d_dual, e->model.d_const, e->model.d_lb + r.first, r.count, e->model.tab_flag, e->stream);
   }
   HIP_CHECK(hipGetLastError());
-  e->lb_all_stale = false;
+  e->model.lb_all_stale = false;
 }
 
 int lpmp_lower_bound(lpmp_engine* e, double* out) {
@@ -2592,14 +2648,14 @@ int lpmp_lower_bound(lpmp_engine* e, double* out) {
     HIP_CHECK(hipSetDevice(e->device));
     if (spec_lower_bound(e, out)) return;      // the caller is inside a batch of passes that ran ahead: that pass's own row
     compute_factor_lbs(e);
-    const int64_t nf = e->plan->p.nf;
+    const int64_t nf = e->model.plan->p.nf;
     int64_t nb = std::min<int64_t>(1024, (nf + 255) / 256);
     const int64_t per = (nf + nb - 1) / nb;
     nb = (nf + per - 1) / per;
-    launch_sum_stage(e->d_lb, e->d_part, nf, per, nb, e->stream);
-    HIP_CHECK(hipMemcpyAsync(e->h_part, e->d_part, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    launch_sum_stage(e->model.d_lb, e->model.d_part, nf, per, nb, e->stream);
+    HIP_CHECK(hipMemcpyAsync(e->h_part, e->model.d_part, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    double lb = e->plan->p.constant;
+    double lb = e->model.plan->p.constant;
     for (int64_t i = 0; i < nb; ++i) lb += e->h_part[i];
     *out = lb;
   });
@@ -2612,7 +2668,7 @@ int lpmp_factor_lower_bounds(lpmp_engine* e, double* out) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
     compute_factor_lbs(e);
-    d2h(out, e->d_lb, (size_t)e->plan->p.nf * sizeof(double), e->stream);
+    d2h(out, e->model.d_lb, (size_t)e->model.plan->p.nf * sizeof(double), e->stream);
   });
 }
 
@@ -2622,7 +2678,7 @@ int lpmp_synchronize(lpmp_engine* e) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);                                  // after this call the (possibly borrowed) dual buffer holds the caller's state
     rows_flush(e);
-    if (e->rows && !e->own_dual()) e->rows_stale = true;   // ... and the caller may write it: the rows are refreshed before the next pass
+    if (e->model.rows && !e->model.own_dual()) e->model.rows_stale = true;   // ... and the caller may write it: the rows are refreshed before the next pass
     HIP_CHECK(hipStreamSynchronize(e->stream));
     if (e->timing) e->drain_timing();
     check_chain(e);
@@ -2646,9 +2702,9 @@ int lpmp_boundary_enter(lpmp_engine* e) {
   });
 }
 
-int lpmp_streaming_access(const lpmp_engine* e) { return e && e->plan ? (e->nt_flag ? 1 : 0) : -1; }
+int lpmp_streaming_access(const lpmp_engine* e) { return e && e->model.plan ? (e->model.nt_flag ? 1 : 0) : -1; }
 
-int64_t lpmp_dual_size(const lpmp_engine* e) { return e && e->plan ? e->plan->p.f_doff[e->plan->p.nf] : 0; }
+int64_t lpmp_dual_size(const lpmp_engine* e) { return e && e->model.plan ? e->model.plan->p.f_doff[e->model.plan->p.nf] : 0; }
 
 int lpmp_download_duals(lpmp_engine* e, double* out) {
   return guarded([&] {
@@ -2658,7 +2714,7 @@ int lpmp_download_duals(lpmp_engine* e, double* out) {
     settle(e);
     check_chain(e);
     rows_flush(e);
-    d2h(out, e->d_dual, (size_t)lpmp_dual_size(e) * sizeof(double), e->stream);
+    d2h(out, e->model.d_dual, (size_t)lpmp_dual_size(e) * sizeof(double), e->stream);
   });
 }
 int lpmp_upload_duals(lpmp_engine* e, const double* in) {
@@ -2667,61 +2723,61 @@ int lpmp_upload_duals(lpmp_engine* e, const double* in) {
     if (!in) throw std::runtime_error("null argument");
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
-    h2d(e->d_dual, in, (size_t)lpmp_dual_size(e) * sizeof(double), e->stream);
-    if (e->rows) { e->rows_stale = true; e->packed_stale = false; }
-    e->lb_all_stale = true;
+    h2d(e->model.d_dual, in, (size_t)lpmp_dual_size(e) * sizeof(double), e->stream);
+    if (e->model.rows) { e->model.rows_stale = true; e->model.packed_stale = false; }
+    e->model.lb_all_stale = true;
   });
 }
 int lpmp_invalidate_lower_bounds(lpmp_engine* e) {
   // (the caller says it wrote the packed dual array behind the engine's back: with the rows layout, what it wrote there for
   // a dense pairwise factor replaces the row's vectors — after what the rows hold has been written out, so that everything
   // the caller did not touch survives)
-  return guarded([&] { require_model(e); settle(e); if (e->rows) { rows_flush(e); e->rows_stale = true; } e->lb_all_stale = true; });
+  return guarded([&] { require_model(e); settle(e); if (e->model.rows) { rows_flush(e); e->model.rows_stale = true; } e->model.lb_all_stale = true; });
 }
 // ---- new costs on the plan that is already there (include/lpmp_engine.h) --------------------------------------------------------
 // all tracked bounds stale, primal labels unset: what every change of costs leaves behind
 static void costs_changed(lpmp_engine* e) {
-  HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)e->plan->p.nf * sizeof(double), e->stream));   // all NaN, as after the upload
-  e->lb_all_stale = true;
-  if (e->have_primal) { upload_unset_primal(e); e->primal_t = 0; }
+  HIP_CHECK(hipMemsetAsync(e->model.d_lb, 0xFF, (size_t)e->model.plan->p.nf * sizeof(double), e->stream));   // all NaN, as after the upload
+  e->model.lb_all_stale = true;
+  if (e->model.have_primal) { upload_unset_primal(e); e->model.primal_t = 0; }
 }
 int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, const double* dual_data, int dual_mem) {
   return guarded([&] {
-    if (!e || !e->plan) throw StateError("lpmp_upload_costs: no model uploaded (the structure comes from lpmp_upload_model)");
+    if (!e || !e->model.plan) throw StateError("lpmp_upload_costs: no model uploaded (the structure comes from lpmp_upload_model)");
     if (!const_data && !dual_data) throw StateError("lpmp_upload_costs: neither constants nor duals given");
     HIP_CHECK(hipSetDevice(e->device));
-    Plan& p = e->plan->p;
+    Plan& p = e->model.plan->p;
     const int64_t n_const = p.f_coff[p.nf], n_dual = p.f_doff[p.nf];
     if (dual_data) {   // cold start: an open batch of passes that ran ahead is dropped, its snapshot is dead
-      e->spec.n = 0; e->spec.pos = 0; e->spec.lb_ready = false;
+      e->model.batch.n = 0; e->model.batch.pos = 0; e->model.batch.lb_ready = false;
       spec_interrupt(e);
     } else settle(e);  // warm start: the duals are those of the pass the caller is at
     check_chain(e);
     if (dual_data) {
-      if (dual_mem != LPMP_MEM_DEVICE) h2d(e->d_dual, dual_data, (size_t)n_dual * sizeof(double), e->stream);
-      else if (dual_data != e->d_dual) HIP_CHECK(hipMemcpyAsync(e->d_dual, dual_data, (size_t)n_dual * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      if (e->rows) { e->rows_stale = true; e->packed_stale = false; }
+      if (dual_mem != LPMP_MEM_DEVICE) h2d(e->model.d_dual, dual_data, (size_t)n_dual * sizeof(double), e->stream);
+      else if (dual_data != e->model.d_dual) HIP_CHECK(hipMemcpyAsync(e->model.d_dual, dual_data, (size_t)n_dual * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (e->model.rows) { e->model.rows_stale = true; e->model.packed_stale = false; }
     }
     if (const_data && n_const > 0) {
       const bool dev = const_mem == LPMP_MEM_DEVICE;
-      if (!e->tab_compact) {   // the packed constants as a whole: the engine's own buffer, or the caller's borrowed one
-        if (!dev) h2d(e->d_const, const_data, (size_t)n_const * sizeof(double), e->stream);
-        else if (const_data != e->d_const) HIP_CHECK(hipMemcpyAsync(e->d_const, const_data, (size_t)n_const * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      if (!e->model.tab_compact) {   // the packed constants as a whole: the engine's own buffer, or the caller's borrowed one
+        if (!dev) h2d(e->model.d_const, const_data, (size_t)n_const * sizeof(double), e->stream);
+        else if (const_data != e->model.d_const) HIP_CHECK(hipMemcpyAsync(e->model.d_const, const_data, (size_t)n_const * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
       }
-      if (e->tab_prec != LPMP_TABLES_F64) {
-        e->const_bad = true;   // until the narrowing has accepted every table
-        try { if (e->tab_compact) narrow_tables(e, p, const_data, dev, false); else narrow_tables(e, p, e->d_const, true, false); }
-        catch (...) { e->lb_all_stale = true; throw; }
+      if (e->model.tab_prec != LPMP_TABLES_F64) {
+        e->model.const_bad = true;   // until the narrowing has accepted every table
+        try { if (e->model.tab_compact) narrow_tables(e->model, e->stream, const_data, dev, false); else narrow_tables(e->model, e->stream, e->model.d_const, true, false); }
+        catch (...) { e->model.lb_all_stale = true; throw; }
       }
-      e->const_bad = false;
-      gather_shared_cells(e);
-      if (e->rows) {
+      e->model.const_bad = false;
+      gather_shared_cells(e->model, e->stream);
+      if (e->model.rows) {
         // the rows take their tables from the constants and their vectors from the packed duals: the packed array first gets what
         // the rows hold that it does not (warm start), then every row is built as at the upload
-        if (e->rows_stale && e->packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
+        if (e->model.rows_stale && e->model.packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
         rows_flush(e);
-        build_rows(e);
-        e->rows_stale = false;
+        build_rows(e->model, e->stream);
+        e->model.rows_stale = false;
       }
     }
     costs_changed(e);
@@ -2734,40 +2790,12 @@ int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const do
     require_model(e);
     if (n < 0 || (n > 0 && (!factors || !src))) throw std::runtime_error("lpmp_set_vectors: bad argument");
     HIP_CHECK(hipSetDevice(e->device));
-    const Plan& p = e->plan->p;
-    std::vector<uint8_t> seen((size_t)p.nf, 0);
-    std::vector<SetVecRec> recs((size_t)n);
-    const bool dev = src_mem == LPMP_MEM_DEVICE;
-    int32_t longest = 0, longest_f = -1;
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t f = factors[i];
-      if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_set_vectors: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
-      if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error("lpmp_set_vectors: factor " + std::to_string(f) + " is not a VECTOR factor");
-      if (seen[(size_t)f]) throw std::runtime_error("lpmp_set_vectors: factor " + std::to_string(f) + " is listed twice (the result would depend on the order of two waves)");
-      seen[(size_t)f] = 1;
-      const int32_t len = p.f_dim0[f];
-      if (len > longest) { longest = len; longest_f = f; }
-      // (vector factors live in the packed array under every layout; a host source is packed row after row: stride 1, row = offset)
-      recs[(size_t)i] = {p.f_doff[f], dev ? i : total, len, f};
-      total += len;
-    }
-    if (n > 0 && src_stride < longest)
-      throw std::runtime_error("lpmp_set_vectors: src_stride " + std::to_string(src_stride) + " is smaller than the " + std::to_string(longest) + " entries of factor " + std::to_string(longest_f));
-    settle(e);
-    check_chain(e);
+    const Plan& p = e->model.plan->p;
+    // (vector factors live in the packed array under every layout)
+    const ListedSrc s = listed_rows(e, "lpmp_set_vectors", n, factors, src, src_stride, src_mem == LPMP_MEM_DEVICE, true, " is not a VECTOR factor", e->model.d_setrecs,
+                                    [&](int64_t, int32_t f, int64_t src_row) { return SetVecRec{p.f_doff[f], src_row, p.f_dim0[f], f}; });
     if (n == 0) return;
-    e->d_setrecs.grow((size_t)n);
-    h2d(e->d_setrecs, recs.data(), (size_t)n * sizeof(SetVecRec), e->stream);
-    const double* d_src = src;
-    if (!dev) {
-      std::vector<double> rows((size_t)total);
-      for (int64_t i = 0; i < n; ++i) std::copy(src + i * src_stride, src + i * src_stride + recs[(size_t)i].len, rows.begin() + recs[(size_t)i].src_row);
-      e->d_setsrc.grow((size_t)total);
-      h2d(e->d_setsrc, rows.data(), (size_t)total * sizeof(double), e->stream);
-      d_src = e->d_setsrc;
-    }
-    launch_set_vectors(e->d_setrecs, n, d_src, dev ? src_stride : 1, e->d_dual, e->d_lb, accumulate != 0, e->stream);
+    launch_set_vectors(e->model.d_setrecs, n, s.src, s.stride, e->model.d_dual, e->model.d_lb, accumulate != 0, e->stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
   });
@@ -2775,10 +2803,10 @@ int lpmp_set_vectors(lpmp_engine* e, int64_t n, const int32_t* factors, const do
 
 int lpmp_upload_shared_pool(lpmp_engine* e, const double* sh_data, int sh_mem) {
   return guarded([&] {
-    if (!e || !e->plan) throw StateError("lpmp_upload_shared_pool: no model uploaded (the structure comes from lpmp_upload_model)");
+    if (!e || !e->model.plan) throw StateError("lpmp_upload_shared_pool: no model uploaded (the structure comes from lpmp_upload_model)");
     if (!sh_data) throw std::runtime_error("lpmp_upload_shared_pool: null argument");
-    Plan& p = e->plan->p;
-    if (p.n_shared <= 0 || !e->d_shared) throw std::runtime_error("lpmp_upload_shared_pool: the model has no pool of shared tables");
+    Plan& p = e->model.plan->p;
+    if (p.n_shared <= 0 || !e->model.d_shared) throw std::runtime_error("lpmp_upload_shared_pool: the model has no pool of shared tables");
     HIP_CHECK(hipSetDevice(e->device));
     // the band detection and the NaN refusal read the values on the host: a device source (KBs to a few MB) is copied there first
     std::vector<double> host;
@@ -2789,10 +2817,10 @@ int lpmp_upload_shared_pool(lpmp_engine* e, const double* sh_data, int sh_mem) {
     }
     settle(e);          // the duals are those of the pass the caller is at (as the warm start of lpmp_upload_costs)
     check_chain(e);
-    e->plan->set_shared_pool(sh_data);          // (a NaN entry: thrown before anything has changed)
+    e->model.plan->set_shared_pool(sh_data);          // (a NaN entry: thrown before anything has changed)
     HIP_CHECK(hipStreamSynchronize(e->stream));   // no launch in flight reads the pool while it is rewritten
-    write_shared_pool(e, p, (int64_t)e->sh_cells.size() / 2);
-    e->for_each_schedule([&](DevSchedule& d) { d.refresh_diff_band(p); });
+    write_shared_pool(e->model, e->stream, (int64_t)e->model.sh_cells.size() / 2);
+    e->model.for_each_schedule([&](DevSchedule& d) { d.refresh_diff_band(p); });
     costs_changed(e);
     HIP_CHECK(hipStreamSynchronize(e->stream));
   });
@@ -2803,73 +2831,44 @@ int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const 
     require_model(e);
     if (n < 0 || (n > 0 && (!factors || !src))) throw std::runtime_error("lpmp_set_constants: bad argument");
     HIP_CHECK(hipSetDevice(e->device));
-    const Plan& p = e->plan->p;
-    std::vector<uint8_t> seen((size_t)p.nf, 0);
-    std::vector<SetConstRec> recs((size_t)n);
-    const bool dev = src_mem == LPMP_MEM_DEVICE, f32 = e->tab_prec != LPMP_TABLES_F64;
-    const int64_t sh_base = e->d_shared ? (int64_t)(((intptr_t)e->d_shared.get() - (intptr_t)e->d_const) / 8) : 0;
-    int64_t longest = 0, total = 0;
-    int32_t longest_f = -1;
+    ModelState& m = e->model;
+    const Plan& p = m.plan->p;
+    const bool f32 = m.tab_prec != LPMP_TABLES_F64;
+    const int64_t sh_base = m.d_shared ? (int64_t)(((intptr_t)m.d_shared.get() - (intptr_t)m.d_const) / 8) : 0;
     bool any_f32 = false;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t f = factors[i];
-      if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_set_constants: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
-      if (p.f_kind[f] == LPMP_F_VECTOR) throw std::runtime_error("lpmp_set_constants: factor " + std::to_string(f) + " is a VECTOR factor (its costs are duals: lpmp_set_vectors)");
-      if (seen[(size_t)f]) throw std::runtime_error("lpmp_set_constants: factor " + std::to_string(f) + " is listed twice (the result would depend on the order of two waves)");
-      seen[(size_t)f] = 1;
-      const int64_t len = p.f_coff[f + 1] - p.f_coff[f];
-      if (len > longest) { longest = len; longest_f = f; }
-      // (a host source is packed row after row: stride 1, row = offset)
-      SetConstRec r{p.coff(f), 0, dev ? i : total, (int32_t)len, f, 0, 0};
+    const ListedSrc s = listed_rows(e, "lpmp_set_constants", n, factors, src, src_stride, src_mem == LPMP_MEM_DEVICE, false,
+                                    " is a VECTOR factor (its costs are duals: lpmp_set_vectors)", m.d_setcrecs, [&](int64_t, int32_t f, int64_t src_row) {
+      SetConstRec r{p.coff(f), 0, src_row, (int32_t)(p.f_coff[f + 1] - p.f_coff[f]), f, 0, 0};
       if (p.f_kind[f] == LPMP_F_PAIRWISE_DENSE) {
         if (f32) { r.f32 = 1; any_f32 = true; }                       // the float table only: nothing is written as doubles
-        else if (e->rows) { r.dst = p.f_coff[f]; r.dst2 = p.coff(f); r.two = 1; }   // the packed table, and the table part of the factor's row
+        else if (m.rows) { r.dst = p.f_coff[f]; r.dst2 = p.coff(f); r.two = 1; }   // the packed table, and the table part of the factor's row
       } else if (p.f_kind[f] == LPMP_F_PAIRWISE_SHARED || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF || p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT) {
         // the first word of the factor's cell, and the scalar lpmp_upload_costs would gather the cell from again (DIFF_SHIFT, two: the
         // first words of its two cells — every second word from r.dst on — and the two scalars)
         const bool shift = p.f_kind[f] == LPMP_F_PAIRWISE_DIFF_SHIFT;
         const int64_t k = (r.dst - sh_base) / 2;
-        if (k < 0 || 2 * k + (shift ? 3 : 1) >= (int64_t)e->sh_cells.size() || sh_base + 2 * k != r.dst) throw std::runtime_error("lpmp_set_constants: internal: factor " + std::to_string(f) + " has no cell");
-        r.dst2 = e->sh_cells[(size_t)(2 * k)]; r.two = shift ? 2 : 1;
+        if (k < 0 || 2 * k + (shift ? 3 : 1) >= (int64_t)m.sh_cells.size() || sh_base + 2 * k != r.dst) throw std::runtime_error("lpmp_set_constants: internal: factor " + std::to_string(f) + " has no cell");
+        r.dst2 = m.sh_cells[(size_t)(2 * k)]; r.two = shift ? 2 : 1;
       }
-      recs[(size_t)i] = r;
-      total += len;
-    }
-    if (n > 0 && src_stride < longest)
-      throw std::runtime_error("lpmp_set_constants: src_stride " + std::to_string(src_stride) + " is smaller than the " + std::to_string(longest) + " entries of factor " + std::to_string(longest_f));
-    settle(e);
-    check_chain(e);
+      return r;
+    });
     if (n == 0) return;
-    e->d_setcrecs.grow((size_t)n);
-    h2d(e->d_setcrecs, recs.data(), (size_t)n * sizeof(SetConstRec), e->stream);
-    const double* d_src = src;
-    if (!dev) {
-      std::vector<double> rows((size_t)total);
-      for (int64_t i = 0; i < n; ++i) std::copy(src + i * src_stride, src + i * src_stride + recs[(size_t)i].len, rows.begin() + recs[(size_t)i].src_row);
-      e->d_setsrc.grow((size_t)total);
-      h2d(e->d_setsrc, rows.data(), (size_t)total * sizeof(double), e->stream);
-      d_src = e->d_setsrc;
-    }
-    const int64_t stride = dev ? src_stride : 1;
     if (any_f32) {
       // a listed set is small: every row of a float table is checked BEFORE anything is written, so a refusal leaves the old costs
       // whole (stronger than lpmp_upload_costs, which cannot afford a pass over all tables)
-      const int strict = e->tab_prec == LPMP_TABLES_F32 ? 1 : 0;
+      const int strict = m.tab_prec == LPMP_TABLES_F32 ? 1 : 0;
       DevBuf<int> d_bad; d_bad.alloc(1);
       int bad = INT32_MAX;
       h2d(d_bad, &bad, sizeof(int), e->stream);
-      launch_set_constants_check(e->d_setcrecs, n, d_src, stride, strict, d_bad, e->stream);
+      launch_set_constants_check(m.d_setcrecs, n, s.src, s.stride, strict, d_bad, e->stream);
       HIP_CHECK(hipGetLastError());
       d2h(&bad, d_bad, sizeof(int), e->stream);
       HIP_CHECK(hipStreamSynchronize(e->stream));
-      if (bad != INT32_MAX)
-        throw UnsupportedError("lpmp_set_constants: table precision " + std::string(strict ? "f32" : "f32_round") + ": the row of factor " + std::to_string(bad) +
-                               (strict ? " holds an entry that is not exactly a float (or a finite one beyond float's range or below FLT_MIN)"
-                                       : " holds a finite entry beyond float's range or a nonzero one below FLT_MIN") + "; nothing was written");
+      if (bad != INT32_MAX) throw UnsupportedError(f32_refusal("lpmp_set_constants: ", strict != 0, "row", bad, "; nothing was written"));
     }
-    launch_set_constants(e->d_setcrecs, n, d_src, stride, e->d_const, e->d_lb, e->stream);
+    launch_set_constants(m.d_setcrecs, n, s.src, s.stride, m.d_const, m.d_lb, e->stream);
     HIP_CHECK(hipGetLastError());
-    if (e->have_primal) { upload_unset_primal(e); e->primal_t = 0; }   // as after lpmp_upload_costs: the labels belong to the old costs
+    if (m.have_primal) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_upload_costs: the labels belong to the old costs
     HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
   });
 }
@@ -2880,8 +2879,8 @@ int lpmp_zero_pairwise_duals(lpmp_engine* e) {
     HIP_CHECK(hipSetDevice(e->device));
     settle(e);
     check_chain(e);
-    const Plan& p = e->plan->p;
-    if (e->n_zero < 0) {   // once per model: the pairwise factors' vectors where the kernels address them, contiguous runs merged, cut into pieces
+    const Plan& p = e->model.plan->p;
+    if (e->model.n_zero < 0) {   // once per model: the pairwise factors' vectors where the kernels address them, contiguous runs merged, cut into pieces
       std::vector<ZeroRec> runs, recs;
       for (int64_t f = 0; f < p.nf; ++f) {
         if (p.f_kind[f] == LPMP_F_VECTOR) continue;
@@ -2890,35 +2889,35 @@ int lpmp_zero_pairwise_duals(lpmp_engine* e) {
       }
       for (const ZeroRec& r : runs)
         for (int64_t a = 0; a < r.len; a += ZERO_RUN_MAX) recs.push_back({r.dual_off + a, std::min(ZERO_RUN_MAX, r.len - a)});
-      if (!recs.empty()) { e->d_zero.alloc(recs.size()); h2d(e->d_zero, recs.data(), recs.size() * sizeof(ZeroRec), e->stream); }
-      e->n_zero = (int64_t)recs.size();
+      if (!recs.empty()) { e->model.d_zero.alloc(recs.size()); h2d(e->model.d_zero, recs.data(), recs.size() * sizeof(ZeroRec), e->stream); }
+      e->model.n_zero = (int64_t)recs.size();
     }
     // (dense pairwise vectors live in the rows under the rows layout: what the caller put into the packed array goes there first, and
     // from here on the rows are the newer copy — as for a pass)
     rows_refresh(e);
-    if (e->rows) e->packed_stale = true;
-    launch_zero_pairwise(e->d_zero, e->n_zero, e->d_dual, e->stream);
+    if (e->model.rows) e->model.packed_stale = true;
+    launch_zero_pairwise(e->model.d_zero, e->model.n_zero, e->model.d_dual, e->stream);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemsetAsync(e->d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));
-    e->lb_all_stale = true;
+    HIP_CHECK(hipMemsetAsync(e->model.d_lb, 0xFF, (size_t)p.nf * sizeof(double), e->stream));
+    e->model.lb_all_stale = true;
   });
 }
 
-int64_t lpmp_schedules_built(const lpmp_engine* e) { return e && e->plan ? e->schedules_built : 0; }
+int64_t lpmp_schedules_built(const lpmp_engine* e) { return e && e->model.plan ? e->model.schedules_built : 0; }
 
 // The packed dual array (serialize_dual order) on the device.  With the rows layout the dense pairwise factors' vectors are
 // written out to it first (stream-ordered on the engine's stream), and the caller is assumed to write it: the rows are
 // refreshed from it before the next pass — callers that only read may say so by not calling this between passes.
 void* lpmp_device_duals(lpmp_engine* e) {
   if (!e) return nullptr;
-  if (e->rows) { try { (void)hipSetDevice(e->device); rows_flush(e); e->rows_stale = true; } catch (const std::exception& ex) { g_error = ex.what(); return nullptr; } }
-  return e->d_dual;
+  if (e->model.rows) { try { (void)hipSetDevice(e->device); rows_flush(e); e->model.rows_stale = true; } catch (const std::exception& ex) { g_error = ex.what(); return nullptr; } }
+  return e->model.d_dual;
 }
 // internal (boundary.hip): the base pointer itself, and where a packed dual offset lives on the device
-void* lpmp_engine_dual_base(lpmp_engine* e) { return e ? e->d_dual : nullptr; }
+void* lpmp_engine_dual_base(lpmp_engine* e) { return e ? e->model.d_dual : nullptr; }
 int64_t lpmp_engine_device_dual_offset(lpmp_engine* e, int64_t packed_off) {
-  if (!e || !e->plan || e->plan->p.dev_doff.empty()) return packed_off;
-  const Plan& p = e->plan->p;
+  if (!e || !e->model.plan || e->model.plan->p.dev_doff.empty()) return packed_off;
+  const Plan& p = e->model.plan->p;
   const int64_t f = (int64_t)(std::upper_bound(p.f_doff.begin(), p.f_doff.end(), packed_off) - p.f_doff.begin()) - 1;
   if (f < 0 || f >= p.nf) return packed_off;
   return p.dev_doff[f] + (packed_off - p.f_doff[f]);
@@ -2926,15 +2925,15 @@ int64_t lpmp_engine_device_dual_offset(lpmp_engine* e, int64_t packed_off) {
 // internal (boundary.hip): is [packed_off, packed_off + len) a run of doubles inside ONE factor's dual?  (what the device
 // offset mapping above and the kernels that follow it assume)
 int lpmp_engine_dual_range_ok(lpmp_engine* e, int64_t packed_off, int64_t len) {
-  if (!e || !e->plan || len < 0 || packed_off < 0) return 0;
-  const Plan& p = e->plan->p;
+  if (!e || !e->model.plan || len < 0 || packed_off < 0) return 0;
+  const Plan& p = e->model.plan->p;
   if (packed_off + len > p.f_doff[p.nf]) return 0;
   if (len == 0) return 1;
   const int64_t f = (int64_t)(std::upper_bound(p.f_doff.begin(), p.f_doff.end(), packed_off) - p.f_doff.begin()) - 1;
   return f >= 0 && f < p.nf && packed_off + len <= p.f_doff[f + 1] ? 1 : 0;
 }
 int lpmp_boundary_leave(lpmp_engine* e) {      // a boundary kernel wrote duals through device offsets: only the tracked bounds are stale
-  return guarded([&] { require_model(e); e->lb_all_stale = true; if (e->rows) e->packed_stale = true; });
+  return guarded([&] { require_model(e); e->model.lb_all_stale = true; if (e->model.rows) e->model.packed_stale = true; });
 }
 // Persistent launches (chain executor, joined passes in Infinity-Cache order) assume that resident workgroups keep running, i.e.
 // that the device is this process's own (kernels.hip): a host that knows it shares the device switches them off per engine.
@@ -2942,7 +2941,7 @@ int lpmp_boundary_leave(lpmp_engine* e) {      // a boundary kernel wrote duals 
 int lpmp_set_persistent_launches(lpmp_engine* e, int on) {
   return guarded([&] {
     if (!e) throw std::runtime_error("null engine");
-    if (e->plan) { HIP_CHECK(hipSetDevice(e->device)); settle(e); }
+    if (e->model.plan) { HIP_CHECK(hipSetDevice(e->device)); settle(e); }
     const char* nc = std::getenv("LPMP_NO_CHAIN"); const char* nb = std::getenv("LPMP_NO_BLOCKED_PASSES");
     e->use_chain = on != 0 && !(nc && nc[0] == '1');
     e->use_blocked_passes = on != 0 && !(nb && nb[0] == '1');
@@ -2971,7 +2970,7 @@ int lpmp_device_identity(int device, char* out, int64_t cap) {
 int lpmp_set_rows_layout(lpmp_engine* e, int on) {
   return guarded([&] { if (!e) throw std::runtime_error("null engine"); e->want_rows = on != 0; });
 }
-int lpmp_rows_layout(const lpmp_engine* e) { return e && e->rows ? 1 : 0; }
+int lpmp_rows_layout(const lpmp_engine* e) { return e && e->model.rows ? 1 : 0; }
 int lpmp_set_table_precision(lpmp_engine* e, int precision) {
   return guarded([&] {
     if (!e) throw std::runtime_error("null argument");
@@ -2979,7 +2978,7 @@ int lpmp_set_table_precision(lpmp_engine* e, int precision) {
     e->want_tab = precision;
   });
 }
-int lpmp_table_precision(const lpmp_engine* e) { return e ? e->tab_prec : LPMP_TABLES_F64; }
+int lpmp_table_precision(const lpmp_engine* e) { return e ? e->model.tab_prec : LPMP_TABLES_F64; }
 int lpmp_plan_set_table_precision(lpmp_plan* p, int precision) {
   return guarded([&] {
     if (!p) throw std::runtime_error("null argument");
@@ -2990,8 +2989,8 @@ int lpmp_plan_set_table_precision(lpmp_plan* p, int precision) {
 }
 int64_t lpmp_lower_bound_recomputed(const lpmp_engine* e) { return e ? e->last_lb_recomputed : -1; }
 void* lpmp_engine_stream(lpmp_engine* e) { return e ? (void*)e->stream : nullptr; }
-const lpmp_plan* lpmp_engine_plan(const lpmp_engine* e) { return e ? e->plan.get() : nullptr; }
-lpmp_plan* lpmp_engine_plan_mut(lpmp_engine* e) { return e ? e->plan.get() : nullptr; }
+const lpmp_plan* lpmp_engine_plan(const lpmp_engine* e) { return e ? e->model.plan.get() : nullptr; }
+lpmp_plan* lpmp_engine_plan_mut(lpmp_engine* e) { return e ? e->model.plan.get() : nullptr; }
 
 int lpmp_enable_kernel_timing(lpmp_engine* e, int on) {
   return guarded([&] {
