@@ -253,6 +253,7 @@ struct RotChain {
   // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
   bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
   bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
+  bool pq_wide = false;           // ... and the H / K / T blocks hold PQ_WIDE_RECORDS records (ModelState::rot_wide): the wide consume form
   int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
 };
 // the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
@@ -347,7 +348,12 @@ struct ModelState {
   // over all modes (the engine's rot_cache_limit; least recently used first), lpmp_chain_cache_bytes reports it
   size_t rot_cache_bytes = 0;
   std::map<int, RotChain> rot_chain[LPMP_REPAM_COUNT];
-  RotOrder rot_order[LPMP_REPAM_COUNT];
+  // (per form as well as per mode: the window and a TileSet are sized by block counts — [1]: the wide consume form, rot_wide)
+  RotOrder rot_order[LPMP_REPAM_COUNT][2];
+  // the block relations of a mode's joined passes with consume blocks (H, K, T) of PQ_WIDE_RECORDS records, beside the plan's own
+  // (lpmp_plan::rot, every block the class's four): what a peer-minima launch in the wide consume form is planned from.  Built
+  // with the plan's, while the host schedules still exist, and only where such a launch can come; not valid otherwise
+  RotationInfo rot_wide[LPMP_REPAM_COUNT];
   // peer minima (kernels.hip, dense_pq_*_body): 32 doubles per factor, written by the W steps of a joined launch and read by its K / T
   // steps — never across calls (every call starts with H and W), so no upload invalidates it.  Allocated with the first eligible
   // joined launch, freed with the model; not part of the chain cache
@@ -360,7 +366,7 @@ struct ModelState {
       if (only_mode >= 0 && m != only_mode) continue;
       for (auto& kv : rot_chain[m]) rot_cache_bytes -= std::min(rot_cache_bytes, kv.second.dev_bytes);
       rot_chain[m].clear();
-      rot_order[m] = RotOrder();
+      rot_order[m][0] = rot_order[m][1] = RotOrder();
     }
   }
   // every device schedule of the engine (built-in, partition, prepared iterator-range passes, the scratch one)
@@ -419,6 +425,7 @@ struct lpmp_engine {
   bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
   bool use_peer_minima = true;        // LPMP_NO_PEER_MINIMA=1: every joined launch in the old form (ModelState::d_peerq)
   int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
+  bool pq_wide = true;            // LPMP_PQ_WIDE=0: the consuming records one per wave, four per ticket, on the plan's own block relations
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
   RotSettings rot_opts;      // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
   // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
@@ -690,6 +697,14 @@ void ensure_pass_schedule(lpmp_engine* e, int mode) {
     lap_("... uploaded");
     e->model.plan->rot[mode] = plan_rotation_chain(e->model.plan->pass_cache[mode], e->model.plan->bf_cache[mode], e->model.plan->p.nf);
     lap_("block relations of the steps");
+    // the same with wide consume blocks, where a peer-minima launch can come (rotation_chain decides as here, mode by mode)
+    e->model.rot_wide[mode] = RotationInfo();
+    const RotationInfo& r0 = e->model.plan->rot[mode];
+    if (e->pq_wide && e->use_peer_minima && r0.valid && r0.peer_minima && e->model.tab_flag == 0 && !e->model.rows &&
+        (e->rot_opts.bands > 0 || (e->model.model_big && r0.t[1].bytes >= ((int64_t)64 << 20)))) {
+      e->model.rot_wide[mode] = plan_rotation_chain(e->model.plan->pass_cache[mode], e->model.plan->bf_cache[mode], e->model.plan->p.nf, PQ_WIDE_RECORDS);
+      lap_("... with wide consume blocks");
+    }
     e->model.plan->bf_cache[mode] = Schedule();
   }
   // the host copy is only needed for its summary
@@ -911,8 +926,15 @@ void check_rows(int64_t n, const int64_t* om_off, const double* om, const int64_
 constexpr int ROT_EXPLICIT_MAX = 7;
 // (the window (bands, lag, depth) follows the model: order.cpp rot_geometry; the tiled order: order.cpp make_tiles / tiled_order)
 RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
-  const RotationInfo& ri = e->model.plan->rot[mode];
-  RotOrder& ro = e->model.rot_order[mode];
+  // The peer-minima form is decided first, because the wide consume form has block relations of its own and everything below is
+  // sized by block counts: the structure allows it (order.cpp), the tables are doubles in the packed layout (and, further down, the
+  // buffer can be had).  Every other launch is planned from the plan's own relations, as ever.
+  const RotationInfo& ri_own = e->model.plan->rot[mode];
+  const char* pq_why = !e->use_peer_minima ? "switched off (LPMP_NO_PEER_MINIMA)" : !ri_own.peer_minima ? ri_own.peer_minima_why.c_str()
+                     : e->model.tab_flag != 0 ? "float tables" : e->model.rows ? "rows layout" : nullptr;
+  const bool wide = !pq_why && e->pq_wide && e->model.rot_wide[mode].valid;
+  const RotationInfo& ri = wide ? e->model.rot_wide[mode] : ri_own;
+  RotOrder& ro = e->model.rot_order[mode][wide ? 1 : 0];
   if (!ro.have_geo) { ro.geo = rot_geometry(e->rot_opts, ri); ro.have_geo = true; }
   const RotGeometry& geo = ro.geo;
   const int rot_bands = e->rot_opts.bands;
@@ -970,17 +992,19 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   if (!geo.fits && !ord.tiles) return no("a step's dependencies reach further than the Infinity Cache window can cover");
   if (ord.tiles && verbose) std::fprintf(stderr, "lpmp:   %d tiles of about %d blocks per step, radius %.1f hops, delayed after 1 / 3 / 5 / 7 steps: %.2f / %.2f / %.2f / %.2f\n", ro.tiles.n, ro.tiles.T,
                                          ro.tiles.radius, ro.tiles.delayed[1], ro.tiles.delayed[3], ro.tiles.delayed[5], ro.tiles.delayed[7]);
+  if (!pq_why && !e->model.d_peerq.get() && !e->model.d_peerq.try_alloc((size_t)e->model.plan->p.nf * 32)) {
+    if (wide) {   // the old form then, planned from its own relations: this entry goes, the wide relations with it
+      e->model.rot_chain[mode].erase(key);
+      e->model.rot_wide[mode] = RotationInfo();
+      return rotation_chain(e, mode, n_call);
+    }
+    pq_why = "no device memory for the published minima";
+  }
   JoinedTables jt;
   const std::string why = joined_pass_tables(ri, ord, n, periodic, jt, verbose ? stderr : nullptr);
   if (!why.empty()) return no(why.c_str());
   if (periodic && (int64_t)48 * (int64_t)(2 * jt.per_len) / jt.ring + 64 >= (1 << CHAIN_GEN_BITS)) throw std::runtime_error("rotation chain: ring too small for its generation counter");
   const int n_steps = 2 * n + 1;
-  // peer minima: the structure allows it (order.cpp), the tables are doubles in the packed layout, and the buffer can be had
-  const char* pq_why = !e->use_peer_minima ? "switched off (LPMP_NO_PEER_MINIMA)" : !ri.peer_minima ? ri.peer_minima_why.c_str()
-                     : e->model.tab_flag != 0 ? "float tables" : e->model.rows ? "rows layout" : nullptr;
-  if (!pq_why && !e->model.d_peerq.get()) {
-    if (!e->model.d_peerq.try_alloc((size_t)e->model.plan->p.nf * 32)) pq_why = "no device memory for the published minima";
-  }
   const bool pq = pq_why == nullptr;
   if (verbose) std::fprintf(stderr, "lpmp:   peer minima: %s\n", pq ? "W publishes, K / T read no table" : pq_why);
   std::vector<ChainLaunch> lds;
@@ -1022,12 +1046,13 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   rc.dc.kclass = ri.kclass;
   e->model.rot_cache_bytes += rc.dev_bytes;
   ++e->model.schedules_built;
-  rc.peer_minima = pq;
+  rc.peer_minima = pq; rc.pq_wide = pq && wide;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
   if (verbose && pq) {
     int per_cu = 0;
-    const unsigned grid = chain_pq_grid(e->pq_lds, (int)std::min<int64_t>(N, INT32_MAX), &per_cu);
-    std::fprintf(stderr, "lpmp:   peer minima launch (LPMP_PQ_LDS=%d): %d resident workgroups per CU, grid %u\n", e->pq_lds, per_cu, grid);
+    const unsigned grid = chain_pq_grid(e->pq_lds, rc.pq_wide, (int)std::min<int64_t>(N, INT32_MAX), &per_cu);
+    std::fprintf(stderr, "lpmp:   peer minima launch (LPMP_PQ_LDS=%d, LPMP_PQ_WIDE=%d: %d records per consume ticket, %lld tickets): %d resident workgroups per CU, grid %u\n",
+                 e->pq_lds, rc.pq_wide ? 1 : 0, ri.consume_gpb, (long long)N, per_cu, grid);
   }
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
@@ -1059,7 +1084,7 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
   if (rc->peer_minima && !e->model.d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
-  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds, rc->pq_wide)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1460,6 +1485,7 @@ int lpmp_create(int device, lpmp_engine** out) {
     const char* np = std::getenv("LPMP_NO_PEER_MINIMA");
     e->use_peer_minima = !(np && np[0] == '1');
     if (const char* v = std::getenv("LPMP_PQ_LDS")) e->pq_lds = v[0] == '0' ? 0 : 1;
+    if (const char* v = std::getenv("LPMP_PQ_WIDE")) e->pq_wide = v[0] != '0';
     if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
     if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }
     if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_opts.depth = std::max(1, std::atoi(v)); e->rot_opts.depth_set = true; }

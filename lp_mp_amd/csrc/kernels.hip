@@ -1399,10 +1399,11 @@ struct PqRec {
   double* s_ms[PQ_OPS]; double s_om[PQ_OPS]; int s_fw[PQ_OPS], s_peer[PQ_OPS];
   int64_t pdual[PQ_OPS]; int side[PQ_OPS], defer[PQ_OPS], rpeer[PQ_OPS];
 };
-template <int L>
+// G: lanes per record.  64: a wave per record, the fields are wave-uniform scalars.  32 (consume records only, PQ_CG): two records
+// per wave, every field a per-lane value read from the half-wave's own slab
+template <int L, int G = 64>
 __device__ __forceinline__ void pq_load_rec(PqRec& r, double2_t* slab, const Op* __restrict__ packets, double* __restrict__ dual, int64_t idx, int64_t count,
                                             int stride, int g) {
-  constexpr int G = 64;
   r.live = idx < count;
   load_packet<G>(slab, packets, nullptr, nullptr, idx, stride, r.live, g);
   r.hdr = reinterpret_cast<const UpdRec*>(&slab[0]);
@@ -1433,15 +1434,25 @@ __device__ __forceinline__ void pq_load_rec(PqRec& r, double2_t* slab, const Op*
 
 // H, K, T: a receive is msv (its own side's vector) and the published q — no table, no m_o; from delta = msv + qv on, and in
 // the sends, statement for statement what dense_pk_body does in a chain
-template <int L>
+// G = 64: a wave per record, four records per ticket, half of the lanes idle.  G = 32 (PQ_WIDE_RECORDS = 8 records per ticket,
+// order.cpp plans the K / T / H blocks to match): a wave carries two records, which differ in live, n_recv, n_send, defer and
+// preload_ok — so nothing that moves data across lanes (vec_min: DPP, shuffles) sits in a branch only one half takes: the
+// reductions run for all four receives on every lane (+inf where there is none) and only the loads and stores are guarded.
+// Per lane the arithmetic and the order of its statements are those of the 64-lane form.
+template <int L, int G>
 __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ packets, double* __restrict__ dual, double* __restrict__ lb,
                                                       const double* __restrict__ peerq, int64_t count, int stride, int64_t block,
                                                       const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
-  constexpr int G = 64, GPB = 256 / G, A = ACC_COH;
+  static_assert(G == 64 || (G == 32 && L == 32), "a wave or half a wave per record");
+  constexpr int GPB = 256 / G, A = ACC_COH;
   __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
-  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  unsigned tid = threadIdx.x;
+  // (the 32-lane form's lane constants — group, lane, slab address — are made here, per ticket: hoisted out of the ticket loop they
+  // would be live through the publishing body, which has no register to spare: 168 VGPRs and 12-16 bytes of scratch instead of 165 and 0)
+  if constexpr (G == 32) asm volatile("" : "+v"(tid));
+  const int grp = tid / G, g = tid % G;
   PqRec r;
-  pq_load_rec<L>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
+  pq_load_rec<L, G>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
   const bool aborted = !chain_wait(*ca, ticket);
   double theta = r.vl ? ld_dual<A>(r.own_g + g) : 0.0;
   double sm[PQ_OPS], msv[PQ_OPS], qv[PQ_OPS], mnew[PQ_OPS];
@@ -1463,9 +1474,10 @@ __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ pac
   chain_stamp(*ca, ticket, 4);
 #pragma unroll
   for (int j = 0; j < PQ_OPS; ++j) {
-    if (j >= r.n_recv) break;
+    if constexpr (G == 64) { if (j >= r.n_recv) break; }
+    const bool recv = G == 64 || j < r.n_recv;
     double pb = LPMP_INF;
-    if (g < L) {
+    if (recv && g < L) {
       const double delta = msv[j] + qv[j];
       theta += delta;
       const double mn = msv[j] - delta;
@@ -1474,9 +1486,17 @@ __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ pac
       else st_dual<A>(dual + r.pdual[j] + (r.side[j] == 0 ? 0 : L) + g, mn);
     }
     const bool track = !r.defer[j], hist = hmode == HIST_MID;
-    if (track || hist) {
+    if constexpr (G == 64) {
+      if (track || hist) {
+        pb = vec_min<G, L>(pb);
+        if (g == 0) {
+          if (track) st_lb<A>(lb + r.rpeer[j], pb);
+          if (hist) st_lb<A>(lbh + r.rpeer[j], pb);
+        }
+      }
+    } else {
       pb = vec_min<G, L>(pb);
-      if (g == 0) {
+      if (recv && g == 0) {
         if (track) st_lb<A>(lb + r.rpeer[j], pb);
         if (hist) st_lb<A>(lbh + r.rpeer[j], pb);
       }
@@ -1706,7 +1726,9 @@ __device__ __forceinline__ void chain_loop_roles(const ChainArgs& ca, const Chai
     __syncthreads();
   }
 }
-template <int L, int KM, int S = 0>
+// CG: lanes per CONSUME record (dense_pq_consume_body): 64, or 32 for PQ_WIDE_RECORDS records per consume ticket
+static_assert(PQ_WIDE_RECORDS == 256 / 32, "plan.hpp: records per consume ticket of the wide form");
+template <int L, int KM, int S = 0, int CG = 64>
 __global__ void __launch_bounds__(256, KM == 2 ? 3 : 2)
 chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
                       double* __restrict__ lb, double* __restrict__ peerq) {
@@ -1714,7 +1736,7 @@ chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, do
     const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
     double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
     if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish_body<L, KM, S>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
-    else dense_pq_consume_body<L>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
   });
 }
 
@@ -3582,8 +3604,13 @@ static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_
   return (unsigned)(n_tickets < cap ? n_tickets : cap);
 }
 // what launch_chain will launch for a peer-minima chain of n_tickets (LPMP_ROT_VERBOSE, engine.cpp)
-unsigned chain_pq_grid(int pq_lds, int n_tickets, int* per_cu) {
-  return pq_lds == 0 ? chain_grid(chain_dense_pq_kernel<32, PQ_KM>, n_tickets, 256, per_cu) : chain_grid(chain_dense_pq_kernel<32, PQ_KM, 1>, n_tickets, 256, per_cu);
+template <class F>
+static auto with_pq_kernel(int pq_lds, bool wide, F f) {
+  if (wide) return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM, 0, 32>) : f(chain_dense_pq_kernel<32, PQ_KM, 1, 32>);
+  return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM>) : f(chain_dense_pq_kernel<32, PQ_KM, 1>);
+}
+unsigned chain_pq_grid(int pq_lds, bool pq_wide, int n_tickets, int* per_cu) {
+  return with_pq_kernel(pq_lds, pq_wide, [&](auto k) { return chain_grid(k, n_tickets, 256, per_cu); });
 }
 void debug_set_level_trace(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_level_trace), &p, sizeof(p)); }
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launches, double* dual, const double* cdata,
@@ -3594,12 +3621,12 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
     if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
     auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
-    return pq_lds == 0 ? go(chain_dense_pq_kernel<32, PQ_KM>) : go(chain_dense_pq_kernel<32, PQ_KM, 1>);
+    return with_pq_kernel(pq_lds, pq_wide, go);
   }
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };

@@ -73,7 +73,7 @@ std::string peer_minima_obstacle(const Schedule& fb, const Schedule& bf, const L
 
 }  // namespace
 
-RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf) {
+RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf, int consume_gpb) {
   RotationInfo ri;
   auto only_launch = [](const Schedule& s, int level, LevelRange& out) {
     int n = 0;
@@ -85,13 +85,15 @@ RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t
   const int kc = w.kclass;
   if (h.kclass != kc || k.kclass != kc || t.kclass != kc || !kc_is_packed(kc)) return ri;
   ri.kclass = kc; ri.gpb = kc_block_records(kc);
+  ri.consume_gpb = consume_gpb > 0 ? consume_gpb : ri.gpb;
+  const int tg[4] = {ri.consume_gpb, ri.gpb, ri.consume_gpb, ri.consume_gpb};   // records per block of H, W, K, T
   const LevelRange* lrs[4] = {&h, &w, &k, &t};
   const Schedule* sch[4] = {&fb, &fb, &bf, &fb};
   std::vector<int32_t> touch[4];
   for (int i = 0; i < 4; ++i) {
     const int64_t cnt = lrs[i]->end - lrs[i]->begin;
-    ri.t[i] = {i == 2 ? 1 : 0, *lrs[i], (int32_t)((cnt + ri.gpb - 1) / ri.gpb), cnt, lrs[i]->n_recv, lrs[i]->bytes};
-    touch[i] = launch_touchers(*sch[i], *lrs[i], ri.gpb, nf);
+    ri.t[i] = {i == 2 ? 1 : 0, *lrs[i], (int32_t)((cnt + tg[i] - 1) / tg[i]), cnt, lrs[i]->n_recv, lrs[i]->bytes};
+    touch[i] = launch_touchers(*sch[i], *lrs[i], tg[i], nf);
   }
   // kind -> (X, Y1, Y2)
   const int X[6] = {1, 2, 1, 2, 3, 3}, Y1[6] = {0, 1, 2, 1, 1, 1}, Y2[6] = {-1, 0, 1, 2, 2, 0};
@@ -99,12 +101,12 @@ RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t
     const Schedule& s = *sch[X[kind]];
     const LevelRange& lr = *lrs[X[kind]];
     // (blocks are independent: chunks of them on several threads, see plan.hpp parallel_blocks)
-    const int64_t nbk = ri.t[X[kind]].nb;
+    const int64_t nbk = ri.t[X[kind]].nb, gx = tg[X[kind]];
     std::vector<std::vector<std::pair<int8_t, int32_t>>> per((size_t)nbk);
     parallel_blocks(nbk, 4096, [&](int64_t b0, int64_t b1) {
       for (int64_t b = b0; b < b1; ++b) {
         auto& dst = per[(size_t)b];
-        for (int64_t i = lr.begin + b * ri.gpb; i < std::min<int64_t>(lr.end, lr.begin + (b + 1) * ri.gpb); ++i) {
+        for (int64_t i = lr.begin + b * gx; i < std::min<int64_t>(lr.end, lr.begin + (b + 1) * gx); ++i) {
           const UpdRec& r = s.recs[i];
           auto visit = [&](int32_t g) {
             if (touch[Y1[kind]][g] >= 0) dst.emplace_back((int8_t)1, touch[Y1[kind]][g]);

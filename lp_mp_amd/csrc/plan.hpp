@@ -396,7 +396,8 @@ void band_order(const std::vector<int64_t>& nb, int bands, int lag, int depth, T
 // step of backward+forward; n passes = H, W, (K, W)^(n-1), T.
 struct RotationInfo {
   bool valid = false;
-  int kclass = 0, gpb = 1;
+  int kclass = 0, gpb = 1;       // gpb: records per block of the W template (the class's own)
+  int consume_gpb = 1;           // ... of the H, K and T templates (one common count: the tiled order needs equal block counts there)
   struct Tmpl { int sched; LevelRange lr; int32_t nb; int64_t factors, recv, bytes; };   // sched: 0 forward+backward, 1 backward+forward
   Tmpl t[4];                                                   // H, W, K, T
   // predecessors of a step's blocks: kind 0 W after [H]; 1 K after [W, H]; 2 W after [K, W]; 3 K after [W, K];
@@ -416,7 +417,10 @@ struct RotationInfo {
 };
 // fb, bf: forward+backward and backward+forward of a mode whose passes join (engine.cpp plan_rotation), nf factors; not valid
 // unless H, W, K, T are one packed launch each of one chain-capable class
-RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf);
+// consume_gpb: records per block of the H, K, T templates (0: the class's own, as W) — the wide consume form of the peer-minima
+// kernel takes PQ_WIDE_RECORDS; dependencies, reach and block counts follow every template's own block size
+constexpr int PQ_WIDE_RECORDS = 8;
+RotationInfo plan_rotation_chain(const Schedule& fb, const Schedule& bf, int64_t nf, int consume_gpb = 0);
 
 // ---- chain_plan.cpp: the chain plans of a deep schedule, from its records, launches and packets ------------------------------
 // the knobs of chain planning (chain_settings_from_env: read on every make_schedule that reaches chain planning)

@@ -3,6 +3,9 @@
     python tools/chain_trace.py run [grid] [labels] [order]   on the GPU box: one traced pass of a grid, then the analysis
                                                                (order c5: C5 with local triples instead of a grid)
     python tools/chain_trace.py show FILE                      analysis of a dump
+    python tools/chain_trace.py joined GRID PASSES [FILE]      on the GPU box: one traced joined launch of PASSES (<= 7) passes of a
+                                                               32-label colour-major grid (the third call of that size), then `roles`
+    python tools/chain_trace.py roles FILE                     a joined launch by step role: where the workgroup-slot time goes
 
 Per ticket: t0 ticket in hand, t1 predecessors seen (wait over), t2 body done (stores issued), t3 published.
   startup  = t1 - t0 when the ticket did not have to wait (its predecessors were published before t0 + startup): the
@@ -120,9 +123,68 @@ def show(path):
               f"publish {us(parts[2]) / hops:.2f}, startup not hidden {us(parts[3]) / hops:.2f} us")
 
 
+def roles(path):
+    """A joined launch H, W, (K, W)^(n-1), T holds a workgroup slot from t0 (ticket in hand) to t3 (published) per ticket, and the
+    launch lasts about sum(t3 - t0) / resident workgroups: per role the tickets, the quantiles of t3 - t0 and of its parts, and
+    the share of that sum"""
+    st, tl, off, dep = load(path)
+    n = st.shape[0]
+    n_steps = int(tl.max()) + 1
+    if n_steps < 3 or n_steps % 2 == 0:
+        print(f"{n_steps} steps: not a joined launch"); return
+    t0, t1, t2, t3, t4, t5 = (st.T[k].astype(np.float64) * 0.01 for k in range(6))
+    role = np.where(tl == 0, 0, np.where(tl == n_steps - 1, 3, np.where(tl % 2 == 1, 1, 2)))
+    hold = t3 - t0
+    total = float(hold.sum())
+    span = float(t3.max() - t0.min())
+    print(f"{n} tickets in {n_steps} steps ({(n_steps - 1) // 2} passes), {span:.1f} us from the first ticket to the last publish; "
+          f"sum of t3 - t0 = {total:.1f} us = {total / span:.1f} slots busy on average")
+    parts = (("hold     t3 - t0", hold), ("wait     t1 - t0", t1 - t0), ("duals    t4 - t1", t4 - t1), ("receives t5 - t4", t5 - t4),
+             ("sends    t2 - t5", t2 - t5), ("publish  t3 - t2", t3 - t2))
+    consume = 0.0
+    for r, name in enumerate("HWKT"):
+        sel = role == r
+        if not sel.any():
+            continue
+        share = float(hold[sel].sum()) / total
+        consume += share if r != 1 else 0.0
+        print(f"  {name}: {int(sel.sum())} tickets, share of the slot time {share:.3f}")
+        for what, a in parts:
+            print("     %s: median %.2f, p10 %.2f, p90 %.2f us" % ((what,) + tuple(np.percentile(a[sel], [50, 10, 90]))))
+    print(f"  consume share c (H + K + T) = {consume:.3f}")
+
+
+def run_joined(g, passes, path):
+    code = f"""
+import sys
+sys.path.insert(0, {ROOT!r})
+import torch
+from lp_mp_amd import engine as E, model as M, synthetic as S
+import bench as B
+torch.cuda.set_device(0)
+sp = torch.cuda.current_stream().cuda_stream
+m, const, dual = B.build_device_grid(torch, {g}, {g}, 32, "dense", "colour_major", 1, E, S, sp)
+e = E.Engine(0); e.set_stream(sp)
+e.upload(m, const_dev=const.data_ptr(), dual_dev=dual.data_ptr(), keep=(const, dual))
+e.set_reparametrization(M.REPAM_ANISOTROPIC)
+for _ in range(3):
+    e.compute_pass({passes})
+e.synchronize()
+"""
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LPMP_CHAIN_TRACE=path), capture_output=True, text=True)
+    if r.returncode != 0:
+        print(r.stderr[-2000:]); sys.exit(1)
+    sys.stderr.write(r.stderr[-4000:])
+    roles(path)
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "show":
         show(sys.argv[2])
+    elif sys.argv[1] == "roles":
+        roles(sys.argv[2])
+    elif sys.argv[1] == "joined":
+        run_joined(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4] if len(sys.argv) > 4 else "/tmp/chain_trace.bin")
     else:
         g = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
         L = int(sys.argv[3]) if len(sys.argv) > 3 else 32
