@@ -7,9 +7,17 @@
 // ticket is an ancestor of the later one in the dependency graph (then every linear extension, however adversarial, keeps them in
 // order).  Band order, tiled order and the periodic template expanded as the kernel expands it; several pass counts.
 // Prints "peer minima ok" and exits 0, or names the first failed check and exits 1.
+// With arguments, `peer_minima_probe GRAPH bands:lag:depth ...`, the eligibility rule and the hazard proof run on the bipartite
+// graph of the file GRAPH instead of the grids ("n0 n1", then an edge "a b" per line, a < n0 of colour 0 and b < n1 of colour 1, in
+// the order the model's builder adds them: tests/peer_minima_cases.py), in the given windows.  The tiled order needs equal block
+// counts of H, K and T (engine.cpp offers it only then); where they differ it is skipped, and the output says so.
+// make_steps emits a record's ops in edge order and the records in vertex order.  plan.cpp lists a factor's messages type by type,
+// so on a graph whose records sit on either side of their tables its receives come side 0 first; the slots' writer and reader
+// blocks, and with them every check here, depend on which factors a record receives over, not on the order of its ops.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <functional>
 #include <string>
 #include <vector>
@@ -35,6 +43,16 @@ static Graph stars(int arms, int leaves) {
   Graph g; g.n = arms * (leaves + 1); g.side.assign((size_t)g.n, 0);
   for (int a = 0; a < arms; ++a) { const int c = a * (leaves + 1); g.side[c] = 1; for (int i = 1; i <= leaves; ++i) g.edges.emplace_back(c + i, c); }
   return g;
+}
+
+static bool read_graph(const char* path, Graph& g) {
+  std::ifstream in(path);
+  long long n0 = 0, n1 = 0, a = 0, b = 0;
+  if (!(in >> n0 >> n1) || n0 < 0 || n1 < 0 || n0 + n1 > (1 << 24)) return false;
+  g.n = (int)(n0 + n1); g.side.assign((size_t)g.n, 0);
+  for (long long v = n0; v < n0 + n1; ++v) g.side[(size_t)v] = 1;
+  while (in >> a >> b) { if (a < 0 || a >= n0 || b < 0 || b >= n1) return false; g.edges.emplace_back((int)a, (int)(n0 + b)); }
+  return in.eof();
 }
 
 // forward+backward (levels H, W, T) and backward+forward (level K) of that graph: unary v = factor v, edge e = factor n + e
@@ -138,10 +156,56 @@ static void check_slots(const Steps& s, const RotationInfo& ri, const Launch& l,
   }
 }
 
+struct Window { int bands, lag, depth; };
+// every window, band order and tiled order, 1 to 32 passes, explicit tables and the periodic template
+static void check_windows(const Steps& s, const RotationInfo& ri, const std::vector<Window>& windows, const char* name) {
+  const bool tiles_ok = ri.t[0].nb == ri.t[2].nb && ri.t[3].nb == ri.t[2].nb;
+  if (!tiles_ok) std::printf("%s: H, K, T have %d, %d, %d blocks: the tiled order is not offered, skipped\n", name, ri.t[0].nb, ri.t[2].nb, ri.t[3].nb);
+  const TileSet ts = tiles_ok ? make_tiles(ri, 3) : TileSet();
+  for (const Window& wnd : windows) for (int tiled = 0; tiled < (tiles_ok ? 2 : 1); ++tiled) {
+    const JoinedOrder ord{wnd.bands, wnd.lag, tiled ? std::max(2, wnd.depth & ~1) : wnd.depth, tiled ? &ts : nullptr};
+    for (int n : {1, 2, 3, 5, 7, 9, 12, 20, 32}) {
+      JoinedTables jt;
+      std::string why = joined_pass_tables(ri, ord, n, false, jt, nullptr);
+      CHECK(why.empty(), "%s, %d passes: %s", name, n, why.c_str());
+      if (why.empty()) check_slots(s, ri, expand(jt, ord.depth, 0), n, tiled ? "tiled order" : "band order");
+      // the periodic template of this pass count's parity, expanded to n passes
+      const int depth = ord.depth, tail = (2 * n + 1) % depth, n_tmpl = (3 * depth + tail - 1) / 2;
+      if (depth % 2 || n < n_tmpl || n <= 7) continue;
+      JoinedTables tp;
+      why = joined_pass_tables(ri, ord, n_tmpl, true, tp, nullptr);
+      CHECK(why.empty(), "%s, template of %d passes: %s", name, n_tmpl, why.c_str());
+      const int extra = (n - n_tmpl) / (depth / 2);
+      if (why.empty() && n_tmpl + extra * (depth / 2) == n) check_slots(s, ri, expand(tp, depth, extra), n, tiled ? "periodic, tiled order" : "periodic, band order");
+    }
+  }
+}
+
+// the eligibility rule and the hazard proof on a graph read from a file, in the caller's windows
+static int graph_mode(int argc, char** argv) {
+  Graph g;
+  if (!read_graph(argv[1], g)) { std::printf("%s: not a graph file\n", argv[1]); return 2; }
+  std::vector<Window> windows;
+  for (int i = 2; i < argc; ++i) {
+    Window w{};
+    if (std::sscanf(argv[i], "%d:%d:%d", &w.bands, &w.lag, &w.depth) != 3 || w.bands < 1 || w.lag < 1 || w.depth < 1) { std::printf("%s: not bands:lag:depth\n", argv[i]); return 2; }
+    windows.push_back(w);
+  }
+  if (windows.empty()) { std::printf("no window given\n"); return 2; }
+  const Steps s = make_steps(g);
+  const RotationInfo ri = plan_rotation_chain(s.fb, s.bf, s.nf);
+  CHECK(ri.valid && ri.peer_minima && ri.peer_minima_why.empty(), "%s: '%s'", argv[1], ri.peer_minima_why.c_str());
+  if (ri.valid) check_windows(s, ri, windows, argv[1]);
+  if (failures) { std::printf("%d checks failed\n", failures); return 1; }
+  std::printf("peer minima ok (%lld ordered pairs)\n", (long long)pairs_checked);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   // ---- eligibility
   const std::pair<int, int> grids[] = {{2, 2}, {1, 7}, {3, 3}, {13, 11}, {14, 10}, {40, 36}};
-  if (argc > 1 && std::string(argv[1]) == "why") {   // the obstacle strings, for the record
+  if (argc > 1 && std::string(argv[1]) != "why") return graph_mode(argc, argv);
+  if (argc > 1) {   // the obstacle strings, for the record
     for (int leaves : {4, 5}) { const Steps s = make_steps(stars(3, leaves)); std::printf("stars of %d: '%s'\n", leaves, plan_rotation_chain(s.fb, s.bf, s.nf).peer_minima_why.c_str()); }
     return 0;
   }
@@ -167,29 +231,12 @@ int main(int argc, char** argv) {
     CHECK(!plan_rotation_chain(s.fb, s.bf, s.nf).peer_minima, "a W receive that is stored, not forwarded");
   }
   // ---- hazards of the slots
-  const int windows[][3] = {{8, 2, 4}, {5, 1, 2}, {16, 2, 3}, {3, 4, 7}};
+  const std::vector<Window> windows = {{8, 2, 4}, {5, 1, 2}, {16, 2, 3}, {3, 4, 7}};
   for (const auto& hw : grids) {
     const Steps s = make_steps(grid(hw.first, hw.second));
     const RotationInfo ri = plan_rotation_chain(s.fb, s.bf, s.nf);
     if (!ri.valid) continue;
-    const TileSet ts = make_tiles(ri, 3);
-    for (const auto& wnd : windows) for (int tiled = 0; tiled < 2; ++tiled) {
-      const JoinedOrder ord{wnd[0], wnd[1], tiled ? std::max(2, wnd[2] & ~1) : wnd[2], tiled ? &ts : nullptr};
-      for (int n : {1, 2, 3, 5, 7, 9, 12, 20, 32}) {
-        JoinedTables jt;
-        std::string why = joined_pass_tables(ri, ord, n, false, jt, nullptr);
-        CHECK(why.empty(), "%d x %d, %d passes: %s", hw.first, hw.second, n, why.c_str());
-        if (why.empty()) check_slots(s, ri, expand(jt, ord.depth, 0), n, tiled ? "tiled order" : "band order");
-        // the periodic template of this pass count's parity, expanded to n passes
-        const int depth = ord.depth, tail = (2 * n + 1) % depth, n_tmpl = (3 * depth + tail - 1) / 2;
-        if (depth % 2 || n < n_tmpl || n <= 7) continue;
-        JoinedTables tp;
-        why = joined_pass_tables(ri, ord, n_tmpl, true, tp, nullptr);
-        CHECK(why.empty(), "%d x %d, template of %d passes: %s", hw.first, hw.second, n_tmpl, why.c_str());
-        const int extra = (n - n_tmpl) / (depth / 2);
-        if (why.empty() && n_tmpl + extra * (depth / 2) == n) check_slots(s, ri, expand(tp, depth, extra), n, tiled ? "periodic, tiled order" : "periodic, band order");
-      }
-    }
+    check_windows(s, ri, windows, (std::to_string(hw.first) + " x " + std::to_string(hw.second)).c_str());
   }
   if (failures) { std::printf("%d checks failed\n", failures); return 1; }
   std::printf("peer minima ok (%lld ordered pairs)\n", (long long)pairs_checked);
