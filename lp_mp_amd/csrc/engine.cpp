@@ -44,6 +44,7 @@ int guarded(F&& f) {
   catch (const DeviceError& e) { g_error = e.what(); return LPMP_ERR_DEVICE; }
   catch (const StateError& e) { g_error = e.what(); return LPMP_ERR_STATE; }
   catch (const UnsupportedError& e) { g_error = e.what(); return LPMP_ERR_UNSUPPORTED; }
+  catch (const lpmp::UnsupportedModel& e) { g_error = e.what(); return LPMP_ERR_UNSUPPORTED; }   // (the planner's size limits)
   catch (const std::bad_alloc&) { g_error = "out of host memory"; return LPMP_ERR_INVALID; }
   catch (const std::exception& e) { g_error = e.what(); return LPMP_ERR_INVALID; }
 }

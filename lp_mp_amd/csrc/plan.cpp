@@ -899,7 +899,8 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
   std::vector<uint32_t> level_mask(max_level + 1, 0);
   for (int64_t u = 0; u < N; ++u) {
     if (!is_rec(p, U, u)) continue;
-    if (U.n_recv_of[u] > 32767 || U.n_send_of[u] > 32767) fail("factor has too many messages");
+    if (U.n_recv_of[u] > 32767 || U.n_send_of[u] > 32767)     // (UpdRec::n_recv / n_send are int16_t)
+      throw UnsupportedModel("factor " + std::to_string(U.uf[u]) + " has more than 32767 active receives or sends in one update");
     level_mask[level[u] - 1] |= 1u << kclass[u];
   }
   std::vector<int64_t> level_base(max_level + 1, 0);

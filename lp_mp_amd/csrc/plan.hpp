@@ -15,6 +15,7 @@
 #include <exception>
 #include <memory>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <utility>
@@ -23,6 +24,11 @@
 #include "../../include/lpmp_model.h"
 
 namespace lpmp {
+
+// a model that is valid in the reference but beyond a size limit of the device kernels (include/lpmp_engine.h,
+// lpmp_upload_model): the C ABI answers LPMP_ERR_UNSUPPORTED; every other std::runtime_error of the planner is a malformed
+// model or argument (LPMP_ERR_INVALID)
+struct UnsupportedModel : std::runtime_error { using std::runtime_error::runtime_error; };
 
 struct MsgEntry {          // one element of FactorContainer::get_messages()
   int32_t msg;

@@ -369,7 +369,8 @@ def _duplicate_message_model(L):
 def test_packed_classes_only_hold_records_the_packed_kernels_run():
     """the packed dense / Potts kernels have no op-by-op fallback: plan.cpp refuses to plan a launch of their classes it
     cannot pack, and the class rule (cls_of) must already have moved every record with duplicate messages or more ops than
-    the LDS slab holds to an op-by-op class.  Every mode and direction of such models plans, with this split:"""
+    the LDS slab holds to an op-by-op class.  Every mode and direction of such models plans, with this split (the exact boundaries
+    of every class — cap - 1, cap, cap + 1 ops — are in the census of tests/op_cap_cases.py, tests/test_op_caps_host.py):"""
     # u5 has no duplicate: packed; u0 .. u4 one lane each while their duals fit SMALL_MAXD, else the streaming kernel
     split = {4: {"dense4": 1, "small": 5}, 8: {"dense8": 1, "small": 5}, 16: {"dense16": 1, "dense_big": 5},
              32: {"dense32": 1, "dense_big": 5}, 5: {"dense_v8": 1, "small": 5}}
