@@ -123,6 +123,19 @@ int lpmp_plan_chain_info(lpmp_plan* p, int direction, int mode, int64_t* n_chain
  * granules polled by the receiving record instead of a completion flag followed by a fetch): rows = sends
  * that also write a mailbox row, receives = receives that poll one.  0 / 0: every hand-over goes through flags. */
 int lpmp_plan_mailbox_info(lpmp_plan* p, int direction, int mode, int64_t* n_rows, int64_t* n_receives);
+/* ... and, where a chain of that sweep is a LEVEL LOOP (many tiny levels of the generic or the lane-per-factor class walked by
+ * one workgroup), which body its launches take.  Read-only; every pointer may be null.
+ *   n_launches             launches of all level loops of the sweep (0: none)
+ *   n_lane_launches        those of the lane-per-factor class; the rest run one wave per factor
+ *   n_label_ops            lane-per-factor launches whose records run with one lane per OP (labeling-list records with the
+ *                          factor on the left, at most 8 receives and 8 sends, no two of a kind on one peer); the other
+ *                          lane-per-factor launches run one lane per factor inside the loop
+ *   n_label_paired         ... of these, launches in which every record receives and then sends each of its messages
+ *   n_label_staged         ... of n_label_ops, launches of at most 16 records: records, ops and match tables are staged in LDS
+ *                          (with the shared send rule and without rounding; otherwise every launch reads them from memory)
+ *   n_label_paired_staged  launches counted in both */
+int lpmp_plan_level_loop_info(lpmp_plan* p, int direction, int mode, int64_t* n_launches, int64_t* n_lane_launches,
+                              int64_t* n_label_ops, int64_t* n_label_paired, int64_t* n_label_staged, int64_t* n_label_paired_staged);
 
 /* 1 when lpmp_compute_pass(n >= 2) joins the tail of a pass with the head of the next one for this mode (2-colour
  * orders: n passes = H, W, (K, W) x (n-1), T) — decided by an op-by-op comparison of the fused

@@ -213,6 +213,11 @@ void label_ops_flags(const Schedule& out, ChainPlan& lp, bool verbose) {
         if ((o[a].info & 15) != OP_LABELING || ((o[a].info >> 4) & 1) != 0 || o[a].pd0 > SMALL_MAXD || o[a].len != r.d0 || o[a].pd1 != r.d0) fine = false;
         // the receives run side by side, and so do the sends: no two of a kind on one peer
         for (int b = a + 1; b < n && fine; ++b) if (o[a].peer_dual == o[b].peer_dual && (a < r.n_recv) == (b < r.n_recv)) fine = false;
+        // a send into the peer of a receive needs that receive's result: the staged body takes it from LDS where plan.cpp marked
+        // the pair (packet_flags: Op::pad, same match table) and otherwise requests the peer's costs together with the receive's,
+        // before the receive has rewritten them — one peer through two tables (an iterator-range pass that receives through one
+        // and sends through the other) stays on the op-by-op body
+        for (int b = r.n_recv; b < n && fine && a < r.n_recv; ++b) if (o[a].peer_dual == o[b].peer_dual && o[b].pad != a + 1) fine = false;
       }
       if (r.n_recv != r.n_send) paired = false;
       for (int a = 0; a < r.n_recv && paired && fine; ++a)

@@ -1413,6 +1413,35 @@ int lpmp_plan_mailbox_info(lpmp_plan* p, int d, int mode, int64_t* n_rows, int64
   });
 }
 
+// which body every launch of a level loop takes (kernels.hip, level_loop_kernel): read from the flags chain_plan.cpp set, nothing planned
+// beyond what lpmp_plan_chain_info plans
+int lpmp_plan_level_loop_info(lpmp_plan* p, int d, int mode, int64_t* n_launches, int64_t* n_lane_launches, int64_t* n_label_ops,
+                              int64_t* n_label_paired, int64_t* n_label_staged, int64_t* n_label_paired_staged) {
+  return guarded([&] {
+    if (!p || mode < 0 || mode >= LPMP_REPAM_COUNT || d < -1 || d > 1) throw std::runtime_error("bad argument");
+    const Schedule* s;
+    if (d < 0) { plan_pass_schedule(p, mode); s = &p->pass_cache[mode]; } else { plan_schedule(p, d, mode); s = &p->sched_cache[d][mode]; }
+    int64_t n = 0, lane = 0, ops = 0, paired = 0, staged = 0, paired_staged = 0;
+    for (const auto& c : s->chains) {
+      if (!c.level_loop) continue;
+      n += (int64_t)c.launches.size();
+      if (c.kclass != KC_SMALL) continue;
+      lane += (int64_t)c.launches.size();
+      for (const auto& cl : c.launches) {
+        if (!(cl.flags & CHAIN_LAUNCH_LABEL_OPS)) continue;
+        const bool pr = (cl.flags & CHAIN_LAUNCH_LABEL_PAIRED) != 0, st = cl.count <= LL_STAGE_RECS;
+        ++ops; paired += pr; staged += st; paired_staged += pr && st;
+      }
+    }
+    if (n_launches) *n_launches = n;
+    if (n_lane_launches) *n_lane_launches = lane;
+    if (n_label_ops) *n_label_ops = ops;
+    if (n_label_paired) *n_label_paired = paired;
+    if (n_label_staged) *n_label_staged = staged;
+    if (n_label_paired_staged) *n_label_paired_staged = paired_staged;
+  });
+}
+
 int lpmp_plan_get_partitions(lpmp_plan* p, int64_t* n_partitions, int64_t* off, int32_t* factors) {
   return guarded([&] {
     if (!p || !n_partitions) throw std::runtime_error("bad argument");

@@ -1776,7 +1776,11 @@ constexpr int LL_WAVES = 2;                        // computing waves of level_l
 // the match tables of their labeling messages — everything CONSTANT a level needs.  Read from the L2 they are a chain of
 // three dependent round trips (launch -> record -> op -> table) in front of the one that matters (the peers' costs); of the
 // ~5 round trips a level of C5's local triples took (5.4 us, 64 ms per pass) they were more than half.
-constexpr int LL_STAGE_RECS = 16, LL_STAGE_OPS = 16, LL_RING = 4;
+constexpr int LL_RING = 4;                         // (LL_STAGE_RECS, LL_STAGE_OPS: plan.hpp)
+static_assert(LL_STAGE_OPS == 8 + 8 && 4 * 64 == LL_STAGE_RECS * LL_STAGE_OPS, "one op slot per lane of the staging wave in four rounds");
+// doubles of the peer an op touches: pd1 is a second dimension only for a pairwise peer (OP_UP); for a labeling message it is the
+// table's n_left and the peer a vector of pd0 entries
+__device__ __forceinline__ int peer_dual_size(const Op& o) { return (o.info & 15) == OP_UP ? o.pd0 + o.pd1 : o.pd0; }
 struct alignas(16) StagedLevel {
   UpdRec recs[LL_STAGE_RECS];
   Op ops[LL_STAGE_RECS][LL_STAGE_OPS];
@@ -2026,7 +2030,7 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
           for (int x = 0; x < SMALL_MAXD; ++x) tv[t][x] = x < o.pd0 ? tab[x] : o.pd1;
           const double* pd = dual + o.peer_dual;
           acc += __hip_atomic_load(pd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          acc += __hip_atomic_load(pd + max(o.pd0 + o.pd1 - 1, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          acc += __hip_atomic_load(pd + max(peer_dual_size(o) - 1, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           if (k == 0) acc += __hip_atomic_load(dual + st.recs[r].dual_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
@@ -2079,7 +2083,7 @@ level_loop_kernel(const ChainLaunch* __restrict__ launches, int n_launches, doub
               const Op o = ln.ops[r.op_begin + k];
               const double* pd = dual + o.peer_dual;
               acc += __hip_atomic_load(pd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              acc += __hip_atomic_load(pd + max(o.pd0 + o.pd1 - 1, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // a peer of this class spans at most two lines
+              acc += __hip_atomic_load(pd + max(peer_dual_size(o) - 1, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // a peer of this class spans at most two lines
               if ((o.info & 15) == OP_LABELING) acc += (double)tabs[o.peer_const];
             }
             asm volatile("" :: "v"(acc));

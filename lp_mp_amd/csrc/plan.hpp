@@ -192,6 +192,9 @@ constexpr int PEER_MINIMA_MAX_OPS = 4;          // receives / sends per record t
 // holds in registers (kernels.hip: KS, NFW)
 constexpr int MAILBOX_SENDS = 4;
 constexpr int32_t CHAIN_LAUNCH_LABEL_OPS = 1;   // level loop: every record a vector factor whose ops are labeling messages with it on the left, <= 8 receives and <= 8 sends, no two of a kind on one peer
+// level loop: a CHAIN_LAUNCH_LABEL_OPS launch of at most LL_STAGE_RECS records is staged in LDS by the wave that runs ahead
+// (kernels.hip, StagedLevel: LL_STAGE_OPS op slots per record = 8 receives + 8 sends); a larger one reads its records from memory
+constexpr int LL_STAGE_RECS = 16, LL_STAGE_OPS = 16;
 struct ChainPlan {
   bool valid = false;
   int32_t kclass = 0;                       // the one kernel class of the schedule

@@ -172,6 +172,23 @@ def test_labeling_message_values():
     assert o2.duals()[0] == 0.0
 
 
+def test_labeling_message_values_with_three_left_labelings():
+    """labeling_message<{01, 10, 11}, {001 ... 111}, 0, 1> computed by hand (labeling_list_factor.hxx:411-443): the right labelings
+    001 010 011 100 101 110 111 with costs 5 1 4 2 8 7 3 show 00 01 01 10 10 11 11 at the indices, so 001 is not taken (cost 5) and
+    the minima per left labeling are 1, 2, 3; tests/test_labeling_shapes_host.py holds the other tables and a full update"""
+    left, right = [(0, 1), (1, 0), (1, 1)], [(0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1)]
+    for origin, want in ((False, [-4.0, -3.0, -2.0]), (True, [1.0, 2.0, 3.0])):
+        b = M.ModelBuilder(2, [M.MsgType(0, 1, M.SCHED_LEFT, 0, 1, M.M_LABELING, 0)])
+        assert b.add_labeling_table(left, right, (0, 1)) == 0 and b._tables[0].tolist() == [3, 0, 0, 1, 1, 2, 2]
+        l = b.add_vector_factors(0, [[10.0, 20.0, 30.0]])
+        r = b.add_vector_factors(1, [[5.0, 1.0, 4.0, 2.0, 8.0, 7.0, 3.0]], implicit_origin=origin)
+        b.add_messages(0, l[0], r[0])
+        o = Oracle(b.finish())
+        assert o.message_value(0, True, 1.0).tolist() == want
+        assert o.message_value(0, True, 0.5).tolist() == [0.5 * v for v in want]
+        assert o.message_value(0, False, 0.5).tolist() == [5.0, 10.0, 15.0]
+
+
 # ---- reference runs recorded in SURVEY.md 8(c), 8(a5) --------------------------------------------
 def _survey_grid(H, W, L, costs):
     n = H * W

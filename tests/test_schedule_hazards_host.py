@@ -637,7 +637,17 @@ def _partition_grid():
     return b.finish()
 
 
+def _fam_labeling_shapes():
+    """labeling-list models whose left factor has several labelings (tests/labeling_cases.py): one case per family, shape and
+    message schedule (the implicit-origin flags do not bear on a schedule)"""
+    import labeling_cases as LC
+    for c in LC.CASES.values():
+        if c.io == c.fam.io:
+            yield c.name, LC.build(c), dict(modes=(M.REPAM_ANISOTROPIC, M.REPAM_UNIFORM), all_forms=c.shape != "chain" or c.sched != "left", sublists=1)
+
+
 FAMILIES = {
+    "labeling shapes": _fam_labeling_shapes,
     "builders of test_plan_host": _fam_builders,
     "dense grids": _fam_grids("dense"),
     "potts grids": _fam_grids("potts"),
