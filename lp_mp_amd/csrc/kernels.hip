@@ -1389,6 +1389,12 @@ chain_dense_pk_f32_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches
 // reads it back for the publish; of the first pair only table 1 is requested again, and not even that when the second pair has one
 // member (its slot was never overwritten): 1.25 instead of 1.5 table requests per table and pass, the same registers, three waves
 // per SIMD, 38 KiB of LDS per workgroup (EXPERIMENTS.md O; non-temporal last requests measured there as well: no difference).
+// KM = 3 (shipped, LPMP_PQ_HOLD=3; a body of its own, dense_pq_publish3_body): three tables in registers and table 0 parked, so
+// that every table is requested ONCE per table and pass.  It fits in 150 VGPRs without scratch because the record's fields stay in
+// the packet in LDS and its vectors m_o / m_new / m' in LDS rows; 42 KiB of LDS per workgroup, three waves per SIMD.  Measured
+// 3.78 against 4.17 ms per pass on the headline grid, 22.3 against 26.5 GB per pass on the fabric side (EXPERIMENTS.md R).
+// LPMP_PQ_HOLD=2 selects <KM = 2, S = 1>, LPMP_PQ_LDS=0 <KM = 2, S = 0> whatever LPMP_PQ_HOLD says; both kept instruction for
+// instruction.  PQ_KM names the two-table forms.
 constexpr int PQ_KM = 2;
 constexpr int PQ_OPS = PEER_MINIMA_MAX_OPS;                        // receives and sends of a record of such a launch (order.cpp checks)
 
@@ -1702,6 +1708,163 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
   }
 }
 
+// W, KM = 3 (LPMP_PQ_HOLD=3): THREE tables in registers and one parked, so that no table is requested twice.  A record with four
+// receives requests tables 0, 1, 2 before the wait; after receive 0 it parks table 0 in its wave's LDS area and requests table 3
+// into that slot, behind receives 1 and 2; after the sends it publishes edge 3 from that slot, reads table 0 back and publishes
+// 1, 2, 0 (the publishes write distinct peerq slots: their order is free).  With <= 3 receives nothing is parked.  96 VGPRs of
+// tables leave 72 for everything else at three waves per SIMD, so what the shipped form keeps in registers for the whole record
+// lives elsewhere: the record's fields stay in the packet in LDS and are made uniform where they are used (pq_load_rec holds them
+// in > 40 SGPRs, and the kernel is at the SGPR cap), and the vectors m_o, then m_new, then m' of receive j share row j of lds_mv —
+// the reductions read the row directly, the send picks its row by the run-time forward index instead of a select chain that keeps
+// four vectors live.  Per lane the floating-point statements and their order are those of dense_pq_publish_body.
+template <int L>
+__device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
+                                                       double* __restrict__ lb, double* __restrict__ peerq, int64_t count, int stride, int64_t block,
+                                                       const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
+  static_assert(L == 32, "the exact 32-label class");
+  constexpr int G = 64, GPB = 256 / G, A = ACC_COH, KM = 3;
+  constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL;
+  __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
+  __shared__ double lds_mv[GPB][PQ_OPS][L];
+  __shared__ double lds_q[GPB][L];
+  const int grp = threadIdx.x / G, g = threadIdx.x % G;
+  const int c2 = g % CL, rl = g / CL;
+  const int64_t idx = block * GPB + grp;
+  const bool live = idx < count;
+  load_packet<G>(lds_pk[grp], packets, nullptr, nullptr, idx, stride, live, g);
+  const UpdRec* const hdr = reinterpret_cast<const UpdRec*>(&lds_pk[grp][0]);
+  const Op* const lop = reinterpret_cast<const Op*>(&lds_pk[grp][3]);
+  const int n_recv = live ? min(uni<G>((int)hdr->n_recv), PQ_OPS) : 0;
+  const int n_send = live ? min(uni<G>((int)hdr->n_send), PQ_OPS) : 0;
+  const bool vl = live && g < L;
+  auto side_of = [&](const int j) { return (uni<G>(lop[j].info) >> 5) & 1; };
+  double2_t t[KM][NL];
+  double2_t* const park = pq_park_area<1, NL>(grp);
+  auto load_tab = [&](const int s, const int q) {   // table q into slot s
+    const double2_t* T = reinterpret_cast<const double2_t*>(cdata + uni64<G>(lop[q].peer_const)) + g;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) t[s][i] = ld_stream<false>(T + i * G);
+  };
+  // lds_q[a] = min over the other side of T + mo, as in dense_pq_publish_body; mo is a row of lds_mv
+  auto reduce = [&](const int s, const int side, const double* mo) {
+    if (side == 0) {
+      const double2_t mv = *reinterpret_cast<const double2_t*>(&mo[2 * c2]);
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double2_t tv = t[s][i];
+        double v = fmin(tv.x + mv.x, tv.y + mv.y);
+        v = row_allreduce_min<CL>(v);
+        if (c2 == 0) lds_q[grp][i * RPL + rl] = v;
+      }
+    } else {
+      double vx = LPMP_INF, vy = LPMP_INF;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double m1v = mo[i * RPL + rl];
+        const double2_t tv = t[s][i];
+        vx = fmin(vx, tv.x + m1v);
+        vy = fmin(vy, tv.y + m1v);
+      }
+#pragma unroll
+      for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
+      if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < KM; ++j) {                   // constants first, then the predecessors, then the duals
+    if (j < n_recv) load_tab(j, j);
+    else {
+#pragma unroll
+      for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
+    }
+  }
+  const bool aborted = !chain_wait(*ca, ticket);
+  double* const own_g = dual + (live ? uni64<G>(hdr->dual_off) : 0);
+  double theta = vl ? ld_dual<A>(own_g + g) : 0.0;
+  double msv[PQ_OPS], mov[PQ_OPS];
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) {
+    msv[j] = 0.0; mov[j] = 0.0;
+    if (j < n_recv && g < L) {
+      const double* pd = dual + uni64<G>(lop[j].peer_dual);
+      const int sd = side_of(j);
+      msv[j] = ld_dual<A>(pd + (sd == 0 ? 0 : L) + g);
+      mov[j] = ld_dual<A>(pd + (sd == 0 ? L : 0) + g);
+    }
+  }
+  asm volatile("" :: "v"(theta));
+#pragma unroll
+  for (int j = 0; j < PQ_OPS; ++j) { asm volatile("" :: "v"(msv[j])); asm volatile("" :: "v"(mov[j])); }
+  chain_stamp(*ca, ticket, 4);
+  if (g < L) {
+#pragma unroll
+    for (int j = 0; j < PQ_OPS; ++j) lds_mv[grp][j][g] = mov[j];
+  }
+  wave_sync();
+  auto receive = [&](const int j, const int s) {   // row j: m_o in, m_new out (stored by the send that forwards it)
+    reduce(s, side_of(j), lds_mv[grp][j]);
+    wave_sync();
+    if (g < L) {
+      const double qv = lds_q[grp][g];
+      const double delta = msv[j] + qv;
+      theta += delta;
+      lds_mv[grp][j][g] = msv[j] - delta;
+    }
+    wave_sync();
+  };
+  if (n_recv > 0) receive(0, 0);
+  if (n_recv > KM) {                               // every lane reads back only what it wrote itself: no wave_sync, no barrier
+#pragma unroll
+    for (int i = 0; i < NL; ++i) park[i * G + g] = t[0][i];
+    load_tab(0, KM);
+  }
+  if (n_recv > 1) receive(1, 1);
+  if (n_recv > 2) receive(2, 2);
+  if (n_recv > KM) receive(KM, 0);
+  chain_stamp(*ca, ticket, 5);
+  const double snap_min_v = vec_min<G, L>(vl ? theta : LPMP_INF);
+  if (vl && !aborted) {
+    const double snap = theta;
+#pragma unroll
+    for (int k = 0; k < PQ_OPS; ++k) {
+      if (k < n_send) {
+        const Op& o = lop[n_recv + k];
+        const int fw = uni<G>(o.pad);
+        double* const row = lds_mv[grp][fw >= 1 && fw < PQ_OPS ? fw - 1 : PQ_OPS - 1];
+        const double om = o.omega;
+        const double delta = om * snap;
+        const double v = row[g] + delta;
+        st_dual<A>(dual + uni64<G>(o.peer_dual) + (((uni<G>(o.info) >> 5) & 1) ? L : 0) + g, v);
+        theta -= delta;
+        row[g] = v;                                // m': what the publish of that edge reduces
+        if (g == 0) st_lb<A>(lb + uni<G>(o.peer), om * snap_min_v);
+      }
+    }
+    st_dual<A>(own_g + g, theta);
+  }
+  wave_sync();
+  // Publish (see dense_pq_publish_body): the reduction of the OTHER side from the vector just stored
+  auto publish = [&](const int q, const int s) {
+    reduce(s, 1 - side_of(q), lds_mv[grp][q]);
+    wave_sync();
+    if (g < L && !aborted) st_dual<A>(peerq + (int64_t)uni<G>(lop[q].peer) * L + g, lds_q[grp][g]);
+    wave_sync();
+  };
+  if (n_recv > KM) {
+    publish(KM, 0);
+#pragma unroll
+    for (int i = 0; i < NL; ++i) t[0][i] = park[i * G + g];
+  }
+  if (n_recv > 1) publish(1, 1);
+  if (n_recv > 2) publish(2, 2);
+  if (n_recv > 0) publish(0, 0);
+  const double ob = vec_min<G, L>(vl ? theta : LPMP_INF);
+  if (live && g == 0) {
+    st_lb<A>(lb + uni<G>(hdr->factor), ob);
+    if (hmode == HIST_END) st_lb<A>(lbh + uni<G>(hdr->factor), ob);
+  }
+}
+
 // chain_loop for launches whose steps carry a role in ChainLaunch::pad above the bound row
 template <class Body>
 __device__ __forceinline__ void chain_loop_roles(const ChainArgs& ca, const ChainLaunch* __restrict__ launches, Body body) {
@@ -1729,14 +1892,16 @@ __device__ __forceinline__ void chain_loop_roles(const ChainArgs& ca, const Chai
 // CG: lanes per CONSUME record (dense_pq_consume_body): 64, or 32 for PQ_WIDE_RECORDS records per consume ticket
 static_assert(PQ_WIDE_RECORDS == 256 / 32, "plan.hpp: records per consume ticket of the wide form");
 template <int L, int KM, int S = 0, int CG = 64>
-__global__ void __launch_bounds__(256, KM == 2 ? 3 : 2)
+__global__ void __launch_bounds__(256, KM == 4 ? 2 : 3)
 chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
                       double* __restrict__ lb, double* __restrict__ peerq) {
   chain_loop_roles(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int role) {
     const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
     double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
-    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish_body<L, KM, S>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
-    else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    if (role == CHAIN_LAUNCH_PQ_PUBLISH) {
+      if constexpr (KM == 3) dense_pq_publish3_body<L>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+      else dense_pq_publish_body<L, KM, S>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    } else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
   });
 }
 
@@ -3609,12 +3774,19 @@ static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_
 }
 // what launch_chain will launch for a peer-minima chain of n_tickets (LPMP_ROT_VERBOSE, engine.cpp)
 template <class F>
-static auto with_pq_kernel(int pq_lds, bool wide, F f) {
+static auto with_pq_kernel(int pq_lds, int pq_hold, bool wide, F f) {
+  if (pq_lds != 0 && pq_hold == 3) return wide ? f(chain_dense_pq_kernel<32, 3, 1, 32>) : f(chain_dense_pq_kernel<32, 3, 1>);
   if (wide) return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM, 0, 32>) : f(chain_dense_pq_kernel<32, PQ_KM, 1, 32>);
   return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM>) : f(chain_dense_pq_kernel<32, PQ_KM, 1>);
 }
-unsigned chain_pq_grid(int pq_lds, bool pq_wide, int n_tickets, int* per_cu) {
-  return with_pq_kernel(pq_lds, pq_wide, [&](auto k) { return chain_grid(k, n_tickets, 256, per_cu); });
+unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, int n_tickets, int* per_cu, int* num_regs, int* scratch_bytes) {
+  return with_pq_kernel(pq_lds, pq_hold, pq_wide, [&](auto k) {
+    hipFuncAttributes fa{};
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k)) != hipSuccess) { (void)hipGetLastError(); fa.numRegs = -1; fa.localSizeBytes = (size_t)-1; }
+    if (num_regs) *num_regs = fa.numRegs;
+    if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
+    return chain_grid(k, n_tickets, 256, per_cu);
+  });
 }
 void debug_set_level_trace(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_level_trace), &p, sizeof(p)); }
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launches, double* dual, const double* cdata,
@@ -3625,12 +3797,12 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide, int pq_hold) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
     if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
     auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
-    return with_pq_kernel(pq_lds, pq_wide, go);
+    return with_pq_kernel(pq_lds, pq_hold, pq_wide, go);
   }
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
