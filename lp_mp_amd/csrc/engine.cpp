@@ -426,6 +426,7 @@ struct lpmp_engine {
   bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
   bool use_peer_minima = true;        // LPMP_NO_PEER_MINIMA=1: every joined launch in the old form (ModelState::d_peerq)
   int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
+  bool pq_scatter = true;         // LPMP_PQ_SCATTER: the three-table form publishes a table's row minima with a reduce-scatter (0: eight row all-reduces)
   int pq_hold = 3;                // LPMP_PQ_HOLD: tables such a record holds in registers, 3 or 2 (pq_lds 0: always 2, none parked)
   bool pq_wide = true;            // LPMP_PQ_WIDE=0: the consuming records one per wave, four per ticket, on the plan's own block relations
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
@@ -1053,10 +1054,11 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   if (verbose && pq) {
     int per_cu = 0;
     int num_regs = 0, scratch = 0;
-    const unsigned grid = chain_pq_grid(e->pq_lds, e->pq_hold, rc.pq_wide, (int)std::min<int64_t>(N, INT32_MAX), &per_cu, &num_regs, &scratch);
+    const bool three = e->pq_lds != 0 && e->pq_hold == 3;
+    const unsigned grid = chain_pq_grid(e->pq_lds, e->pq_hold, rc.pq_wide, e->pq_scatter, (int)std::min<int64_t>(N, INT32_MAX), &per_cu, &num_regs, &scratch);
     std::fprintf(stderr, "lpmp:   peer minima launch (LPMP_PQ_LDS=%d, LPMP_PQ_WIDE=%d: %d records per consume ticket, %lld tickets): %d resident workgroups per CU, grid %u; "
-                 "%d tables in registers, %d registers, %d bytes of scratch\n",
-                 e->pq_lds, rc.pq_wide ? 1 : 0, ri.consume_gpb, (long long)N, per_cu, grid, e->pq_lds != 0 && e->pq_hold == 3 ? 3 : 2, num_regs, scratch);
+                 "%d tables in registers, %d registers, %d bytes of scratch; publish: %s\n",
+                 e->pq_lds, rc.pq_wide ? 1 : 0, ri.consume_gpb, (long long)N, per_cu, grid, three ? 3 : 2, num_regs, scratch, three && e->pq_scatter ? "reduce-scatter" : "all-reduce");
   }
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
@@ -1088,7 +1090,7 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
   if (rc->peer_minima && !e->model.d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
-  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds, rc->pq_wide, e->pq_hold)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds, rc->pq_wide, e->pq_hold, e->pq_scatter)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1519,6 +1521,7 @@ int lpmp_create(int device, lpmp_engine** out) {
     e->use_peer_minima = !(np && np[0] == '1');
     if (const char* v = std::getenv("LPMP_PQ_LDS")) e->pq_lds = v[0] == '0' ? 0 : 1;
     if (const char* v = std::getenv("LPMP_PQ_HOLD")) e->pq_hold = v[0] == '2' ? 2 : 3;
+    if (const char* v = std::getenv("LPMP_PQ_SCATTER")) e->pq_scatter = v[0] != '0';
     if (const char* v = std::getenv("LPMP_PQ_WIDE")) e->pq_wide = v[0] != '0';
     if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
     if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }

@@ -254,6 +254,29 @@ __device__ __forceinline__ double row_allreduce_min(double v) {
   if constexpr (CL >= 16) v = fmin(v, dpp_mov_f64<0x140>(v)); // row_mirror: other half of the 16
   return v;
 }
+// fmin as ONE v_min_f64.  In front of an fmin whose operand arrived through a DPP move or a shuffle the compiler puts a
+// canonicalising v_max_f64 x, x (it cannot see where the bits come from); that changes a signalling NaN only, and the callers hold
+// none: sums and minima of table entries and duals.  (A DPP move that reads the result still gets its wait states: the hazard
+// check counts any instruction that defines the register, an asm statement included — seen in the assembly.)
+__device__ __forceinline__ double fmin_raw(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// One halving exchange of a min reduce-scatter inside a 16-lane row.  CTRL pairs every lane of the banks (groups of 4 lanes) in
+// LO_BANKS with a lane of the other banks.  The LO lanes keep `lo` and take their partner's `lo`, the others keep `hi` and take
+// their partner's `hi`: two DPP moves per half under complementary bank masks — a lane whose bank is masked out keeps `old`, its own
+// value of the operand it keeps — so both halves end with min(kept, received) without a select.
+template <int CTRL, int LO_BANKS>
+__device__ __forceinline__ double dpp_halve_min(double lo, double hi) {
+  constexpr int HI_BANKS = 0xF & ~LO_BANKS;
+  const int l0 = __double2loint(lo), l1 = __double2hiint(lo), h0 = __double2loint(hi), h1 = __double2hiint(hi);
+  const int a0 = __builtin_amdgcn_update_dpp(h0, l0, CTRL, 0xF, LO_BANKS, false);   // LO lanes: received, others: kept
+  const int a1 = __builtin_amdgcn_update_dpp(h1, l1, CTRL, 0xF, LO_BANKS, false);
+  const int b0 = __builtin_amdgcn_update_dpp(l0, h0, CTRL, 0xF, HI_BANKS, false);   // LO lanes: kept, others: received
+  const int b1 = __builtin_amdgcn_update_dpp(l1, h1, CTRL, 0xF, HI_BANKS, false);
+  return fmin_raw(__hiloint2double(a1, a0), __hiloint2double(b1, b0));
+}
 template <int G, int L>
 __device__ __forceinline__ double vec_min(double v) {   // min over the first L lanes of a G-lane group (others pass +inf)
   constexpr int W = L < G ? L : G;
@@ -1395,6 +1418,12 @@ chain_dense_pk_f32_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches
 // 3.78 against 4.17 ms per pass on the headline grid, 22.3 against 26.5 GB per pass on the fabric side (EXPERIMENTS.md R).
 // LPMP_PQ_HOLD=2 selects <KM = 2, S = 1>, LPMP_PQ_LDS=0 <KM = 2, S = 0> whatever LPMP_PQ_HOLD says; both kept instruction for
 // instruction.  PQ_KM names the two-table forms.
+// SC (shipped, KM = 3 only; dense_pq_publish3_body<L, true> in chain_dense_pq_scatter_kernel): a publish on the column side of a
+// table — every publish of the headline grid — reduces the rows with a reduce-scatter inside the 16-lane row instead of one DPP
+// all-reduce per row: 8 cross-lane steps instead of 32, 78 instead of 152 VALU instructions per table and no canonicalising
+// v_max_f64 (fmin_raw), 32 lanes store one minimum each.  The parent's launch was 0.42 VALU-busy; 3.50 against 3.78 ms per pass,
+// the same 22.3 GB (EXPERIMENTS.md S).  The side-0 RECEIVE keeps the all-reduce (mixed-side models only; its table stays live).
+// LPMP_PQ_SCATTER=0 launches chain_dense_pq_kernel<32, 3, 1, *>, kept instruction for instruction.
 constexpr int PQ_KM = 2;
 constexpr int PQ_OPS = PEER_MINIMA_MAX_OPS;                        // receives and sends of a record of such a launch (order.cpp checks)
 
@@ -1717,7 +1746,7 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
 // in > 40 SGPRs, and the kernel is at the SGPR cap), and the vectors m_o, then m_new, then m' of receive j share row j of lds_mv —
 // the reductions read the row directly, the send picks its row by the run-time forward index instead of a select chain that keeps
 // four vectors live.  Per lane the floating-point statements and their order are those of dense_pq_publish_body.
-template <int L>
+template <int L, bool SC = false>
 __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
                                                        double* __restrict__ lb, double* __restrict__ peerq, int64_t count, int stride, int64_t block,
                                                        const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
@@ -1769,6 +1798,30 @@ __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ pa
       for (int m = G / 2; m >= CL; m >>= 1) { vx = fmin(vx, shfl_xor_f64(vx, m)); vy = fmin(vy, shfl_xor_f64(vy, m)); }
       if (rl == 0) { lds_q[grp][2 * c2] = vx; lds_q[grp][2 * c2 + 1] = vy; }
     }
+  };
+  // SC: the side-0 reduction of a PUBLISH as a reduce-scatter.  All eight row partials of the lane first; then three halving
+  // exchanges inside the 16-lane row — a lane keeps the rows i whose bit 2, 1, 0 is bit 3, 2, 1 of its c2, so 4, 2 and 1 values
+  // move — and one pairing step (lane ^ 1): 8 cross-lane steps where the all-reduce above runs 32, and lane c2 ends with the
+  // minimum of row i = c2 >> 1 alone.  The even lanes store it: 32 lanes one entry each.  The slot is dead afterwards, so the
+  // partials take its registers.  min is exact and every sum is the one above: the same bits.
+  auto scatter = [&](const int s, const double* mo) {
+    static_assert(!SC || (NL == 8 && CL == 16), "three halvings of eight rows over a 16-lane row");
+    const double2_t mv = *reinterpret_cast<const double2_t*>(&mo[2 * c2]);
+    double v[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const double2_t tv = t[s][i];
+      v[i] = fmin(tv.x + mv.x, tv.y + mv.y);
+    }
+    double w[4], x[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = dpp_halve_min<0x140, 0x3>(v[k], v[4 + k]);   // row_mirror: lanes 0-7 keep rows 0-3
+#pragma unroll
+    for (int k = 0; k < 2; ++k) x[k] = dpp_halve_min<0x141, 0x5>(w[k], w[2 + k]);   // row_half_mirror: banks 0 and 2 keep the lower two
+    const bool up = (c2 & 2) != 0;                                                  // lane ^ 2 stays inside a bank: a select
+    double y = fmin_raw(up ? x[1] : x[0], dpp_mov_f64<0x4E>(up ? x[0] : x[1]));
+    y = fmin_raw(y, dpp_mov_f64<0xB1>(y));                                           // lane ^ 1: the pair that holds the row's two halves
+    if ((c2 & 1) == 0) lds_q[grp][(c2 >> 1) * RPL + rl] = y;
   };
 #pragma unroll
   for (int j = 0; j < KM; ++j) {                   // constants first, then the predecessors, then the duals
@@ -1845,7 +1898,10 @@ __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ pa
   wave_sync();
   // Publish (see dense_pq_publish_body): the reduction of the OTHER side from the vector just stored
   auto publish = [&](const int q, const int s) {
-    reduce(s, 1 - side_of(q), lds_mv[grp][q]);
+    if constexpr (SC) {
+      if (side_of(q) == 1) scatter(s, lds_mv[grp][q]);
+      else reduce(s, 1, lds_mv[grp][q]);
+    } else reduce(s, 1 - side_of(q), lds_mv[grp][q]);
     wave_sync();
     if (g < L && !aborted) st_dual<A>(peerq + (int64_t)uni<G>(lop[q].peer) * L + g, lds_q[grp][g]);
     wave_sync();
@@ -1902,6 +1958,20 @@ chain_dense_pq_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, do
       if constexpr (KM == 3) dense_pq_publish3_body<L>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
       else dense_pq_publish_body<L, KM, S>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
     } else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+  });
+}
+
+// the three-table form with the publish's row reduction as a reduce-scatter (dense_pq_publish3_body<L, true>): a kernel of its
+// own, so that chain_dense_pq_kernel<32, 3, 1, *> keeps its symbols and its code (LPMP_PQ_SCATTER=0 launches those)
+template <int L, int CG>
+__global__ void __launch_bounds__(256, 3)
+chain_dense_pq_scatter_kernel(ChainArgs ca, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
+                              double* __restrict__ lb, double* __restrict__ peerq) {
+  chain_loop_roles(ca, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int role) {
+    const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
+    double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
+    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish3_body<L, true>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+    else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
   });
 }
 
@@ -3774,13 +3844,14 @@ static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_
 }
 // what launch_chain will launch for a peer-minima chain of n_tickets (LPMP_ROT_VERBOSE, engine.cpp)
 template <class F>
-static auto with_pq_kernel(int pq_lds, int pq_hold, bool wide, F f) {
+static auto with_pq_kernel(int pq_lds, int pq_hold, bool wide, bool scatter, F f) {
+  if (pq_lds != 0 && pq_hold == 3 && scatter) return wide ? f(chain_dense_pq_scatter_kernel<32, 32>) : f(chain_dense_pq_scatter_kernel<32, 64>);
   if (pq_lds != 0 && pq_hold == 3) return wide ? f(chain_dense_pq_kernel<32, 3, 1, 32>) : f(chain_dense_pq_kernel<32, 3, 1>);
   if (wide) return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM, 0, 32>) : f(chain_dense_pq_kernel<32, PQ_KM, 1, 32>);
   return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM>) : f(chain_dense_pq_kernel<32, PQ_KM, 1>);
 }
-unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, int n_tickets, int* per_cu, int* num_regs, int* scratch_bytes) {
-  return with_pq_kernel(pq_lds, pq_hold, pq_wide, [&](auto k) {
+unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs, int* scratch_bytes) {
+  return with_pq_kernel(pq_lds, pq_hold, pq_wide, pq_scatter, [&](auto k) {
     hipFuncAttributes fa{};
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k)) != hipSuccess) { (void)hipGetLastError(); fa.numRegs = -1; fa.localSizeBytes = (size_t)-1; }
     if (num_regs) *num_regs = fa.numRegs;
@@ -3797,12 +3868,12 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide, int pq_hold) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide, int pq_hold, bool pq_scatter) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
     if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
     auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
-    return with_pq_kernel(pq_lds, pq_hold, pq_wide, go);
+    return with_pq_kernel(pq_lds, pq_hold, pq_wide, pq_scatter, go);
   }
   auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
   auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };

@@ -117,13 +117,15 @@ void launch_sweep_diff(bool band, bool shift, const UpdRec* recs, const Op* ops,
 // pq_lds: the publishing records' form (LPMP_PQ_LDS): 1 park their first table in LDS, 0 request both of the first pair again
 // pq_hold: tables a publishing record holds in registers (LPMP_PQ_HOLD) when pq_lds is 1: 3 = three and one parked, no table
 // requested twice; 2 = two and one parked, table 1 of a record with four receives requested again.  pq_lds 0 ignores it
+// pq_scatter: the three-table form's publish on the column side of a table (LPMP_PQ_SCATTER): true = a reduce-scatter inside the
+// 16-lane row (chain_dense_pq_scatter_kernel), false = eight row all-reduces (chain_dense_pq_kernel<32, 3, 1, *>); the two-table forms ignore it
 // pq_wide: the consuming records' form (LPMP_PQ_WIDE): true = two records per wave, PQ_WIDE_RECORDS per ticket — the launches'
 // H / K / T blocks must have been planned with that many records (order.cpp plan_rotation_chain, consume_gpb)
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr, int pq_lds = 1, bool pq_wide = false, int pq_hold = 2);
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr, int pq_lds = 1, bool pq_wide = false, int pq_hold = 2, bool pq_scatter = false);
 // grid and resident workgroups per CU of that launch; num_regs / scratch_bytes: what hipFuncGetAttributes reports for its kernel
 // (numRegs, localSizeBytes; -1 when the query fails)
-unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, int n_tickets, int* per_cu, int* num_regs = nullptr, int* scratch_bytes = nullptr);
+unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs = nullptr, int* scratch_bytes = nullptr);
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n_launches, double* dual, const double* cdata,
                        const int32_t* tabs, double* lb, hipStream_t s);
 void debug_set_level_trace(long long* p);
