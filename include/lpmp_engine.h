@@ -269,7 +269,8 @@ int lpmp_schedule_create_fused(lpmp_engine* e, int64_t n, const int32_t* factors
 /* lpmp_schedule_run / _info / _destroy with an id that was never returned, that was destroyed, or that belongs to a model replaced
  * since by lpmp_upload_model (before a new schedule takes the number): LPMP_ERR_INVALID ("unknown schedule id"), nothing runs.  A run
  * settles passes that ran ahead, like every pass; the ids stay valid across lpmp_upload_costs, lpmp_set_vectors,
- * lpmp_upload_shared_pool, lpmp_set_constants, lpmp_zero_pairwise_duals and lpmp_upload_duals and run on the costs of the moment. */
+ * lpmp_upload_shared_pool, lpmp_set_constants, lpmp_move_windows, lpmp_zero_pairwise_duals and lpmp_upload_duals and run on the costs
+ * of the moment. */
 int lpmp_schedule_run(lpmp_engine* e, int id);
 int lpmp_schedule_info(lpmp_engine* e, int id, int64_t* n_levels, int64_t* n_launches, int64_t* n_receives,
                        int64_t* n_sends, int64_t* algorithmic_bytes);
@@ -479,6 +480,58 @@ int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const 
  * of the caller's); lpmp_upload_costs and lpmp_set_vectors return after their copies have completed.  A cold start from device data is lpmp_set_vectors(all unaries,
  * replace) + this call; a warm start after a change of unaries is lpmp_set_vectors(changed ones, differences, accumulate). */
 int lpmp_zero_pairwise_duals(lpmp_engine* e);
+/* ---- moving label windows: duals and shifts carried along on the device ------------------------------------------------
+ * A DIFF_SHIFT model gives variable u a WINDOW of labels c_u ... c_u + d_u - 1; the shift of an edge is c_u - c_v + zero.  When the
+ * windows move (coarse to fine, frame to frame) theta_u[x] and the message vectors m_s[x] of the adjacent pairwise factors are indexed
+ * by the window-relative label x, which now names another absolute label: kept where they are (lpmp_set_constants + a warm start) they
+ * are a valid reparametrisation that belongs to the wrong labels.  This call moves them along their label axis and updates the shifts.
+ *
+ * A window set is a prepared list of n distinct VECTOR factors u_0 ... u_{n-1} of the uploaded model, like an lpmp_readout: its record
+ * and link tables are uploaded at create (counted ONCE by lpmp_schedules_built), a move plans and builds nothing.  factors == NULL:
+ * every VECTOR factor in ascending index.  It carries the model it was made for and its device; lpmp_destroy does not free it; after
+ * the next lpmp_upload_model every move on it is LPMP_ERR_STATE and destroying it stays legal.
+ * Supported per listed factor, checked at create: every message of u is LPMP_M_UNARY_PAIRWISE with u as its left factor and a
+ * DIFF_SHIFT factor on the right.  LPMP_ERR_UNSUPPORTED naming the lowest offending listed factor: a peer of any other kind (DENSE,
+ * POTTS, SHARED, plain DIFF) or a message of another kind; two messages of one unary into one vector; a DIFF_SHIFT factor with two
+ * different unaries on one side; more than 512 labels.  LPMP_ERR_INVALID naming the entry: an index out of range, a non-VECTOR factor,
+ * a factor listed twice.  Unlisted parts of the model may be anything.
+ *
+ * lpmp_move_windows: delta[i] (int32, host or device: delta_mem) is the move of listed factor i, |delta[i]| <= 2^20.  delta(f) = delta[i]
+ * for a listed factor, 0 for every other; g_u(x) = min(max(x + delta(u), 0), d_u - 1): new label x is old label x + delta, labels that
+ * enter the window copy the nearest old end value.
+ *   unaries   theta_u'[x] = theta_u[g_u(x)] for every listed u
+ *   messages  m_{p,s}'[x] = m_{p,s}[g_u(x)] for every message of a listed u (pairwise factor p, side s); the vector of the other side
+ *             is touched only if that unary is listed, too
+ *   shifts    every DIFF_SHIFT factor p next to a listed unary, l / r the unary on side 0 / 1 (a side without a unary: delta 0):
+ *             delta(l) != delta(r): shift' = (double) clamp(int(shift) + delta(l) - delta(r), -2^30, 2^30), the conversion of
+ *             lpmp_model.h; the scale stays.  The value goes to every place lpmp_set_constants writes the shift of a DIFF_SHIFT row to.
+ *             delta(l) == delta(r): the factor's constants are not written
+ *   costs     cost_old and cost_new (both or neither; one alone is LPMP_ERR_INVALID): the ORIGINAL unary costs of the listed factors
+ *             in the old and in the new window, [n, cost_stride] doubles, host or device (cost_mem), cost_stride >= the longest listed
+ *             vector.  Then theta_u'[x] = theta_u[g] + (cost_new_i[x] - cost_old_i[g]), g = g_u(x): the inner difference first; where
+ *             the two entries compare equal (==, two +inf included) the term is skipped and theta is carried bit for bit.  Any other
+ *             non-finite entry is outside the contract (lpmp_set_vectors afterwards).
+ * theta_u[x] + sum_p m_{p,s}[x] is the original unary and every term moves by the same g_u; cost(a, b) = scale * D[clip(a - b + s)] is
+ * the same function of the ABSOLUTE labels exactly when s' = s + delta(l) - delta(r): every labelling whose absolute labels lie in
+ * both the old and the new windows keeps its reparametrised energy term by term, bit for bit.  All delta 0 and no costs: no byte of
+ * duals or constants changes.
+ * Settles passes that ran ahead first.  Plans nothing: lpmp_schedules_built does not move, every lpmp_schedule_create id, read-out,
+ * boundary / halo object, the mode and the send rule stay valid.  The tracked bounds of the listed unaries and of every adjacent
+ * pairwise factor become stale; the primal labels become unset, as after lpmp_set_constants.  With device inputs the call is
+ * asynchronous on the engine's stream like a pass; with a host input it returns after its copies.  A host delta out of range is
+ * LPMP_ERR_INVALID, naming the entry, with nothing written; a device delta is saturated to +-2^20 where it is read.  LPMP_ERR_STATE
+ * before an upload, on a set made for a model that has been replaced since, and while the constants are unspecified. */
+typedef struct lpmp_window_set lpmp_window_set;
+int lpmp_window_set_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_window_set** out);
+void lpmp_window_set_destroy(lpmp_window_set* ws);
+int64_t lpmp_window_set_n(const lpmp_window_set* ws);            /* listed factors */
+int32_t lpmp_window_set_max_labels(const lpmp_window_set* ws);   /* longest listed vector */
+int64_t lpmp_window_set_n_pairwise(const lpmp_window_set* ws);   /* DIFF_SHIFT factors whose shift a move may write */
+int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old,
+                      const double* cost_new, int64_t cost_stride, int cost_mem);
+/* host only: the same support check on a plan.  n_links: unary-pairwise links of the listed factors, n_pairwise as above (either may be
+ * NULL); why (why_n bytes; may be NULL): "" or the refusal, which lpmp_last_error reports as well */
+int lpmp_plan_window_info(lpmp_plan* p, int64_t n, const int32_t* factors, int64_t* n_links, int64_t* n_pairwise, char* why, int why_n);
 /* schedules, chain plans and joined-pass templates planned and uploaded for the current model since lpmp_upload_model */
 int64_t lpmp_schedules_built(const lpmp_engine* e);
 

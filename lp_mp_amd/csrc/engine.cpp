@@ -2573,6 +2573,198 @@ int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
   });
 }
 
+// ---- moving label windows: duals and shifts carried along on the device (include/lpmp_engine.h) ---------------------------------
+// What a window set is made of, from the structure alone (lpmp_plan_window_info asks a stand-alone plan): the listed unaries, the
+// links of each in message-list order, and the DIFF_SHIFT factors next to them with the row of the unary on either side.
+namespace {
+struct WindowLink { int32_t p, side; };
+struct WindowPair { int32_t p, left_row, right_row; };
+struct WindowPlan {
+  std::vector<int32_t> factors;
+  std::vector<int64_t> link_off;        // CSR over `factors`
+  std::vector<WindowLink> links;
+  std::vector<WindowPair> pairs;        // in the order the listed unaries meet them
+  int32_t max_labels = 0;
+};
+// LPMP_ERR_INVALID (std::runtime_error) naming the entry: out of range, not a VECTOR factor, listed twice.  LPMP_ERR_UNSUPPORTED
+// naming the lowest listed factor the move does not take.  factors == nullptr: every VECTOR factor
+void window_plan(const Plan& p, int64_t n, const int32_t* factors, const std::string& who, WindowPlan& w) {
+  std::vector<int32_t> row_of((size_t)p.nf, -1);
+  if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) { row_of[(size_t)f] = (int32_t)w.factors.size(); w.factors.push_back((int32_t)f); } }
+  else {
+    if (n > (int64_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error(who + ": more than 2^31 factors listed");
+    w.factors.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t f = factors[i];
+      if (f < 0 || f >= p.nf) throw std::runtime_error(who + ": factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+      if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is not a VECTOR factor");
+      if (row_of[(size_t)f] >= 0) throw std::runtime_error(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is listed twice");
+      row_of[(size_t)f] = (int32_t)i;
+      w.factors.push_back(f);
+    }
+  }
+  int32_t bad = -1; std::string why;
+  auto refuse = [&](int32_t u, const std::string& what) { if (bad < 0 || u < bad) { bad = u; why = what; } };
+  // the unary on each side of a DIFF_SHIFT factor, from ALL its unary-pairwise messages (-1: none, -2: two different ones)
+  auto side_unaries = [&](int32_t pw, int32_t out[2]) {
+    out[0] = out[1] = -1;
+    for (int64_t k = p.fm_off[(size_t)pw]; k < p.fm_off[(size_t)pw + 1]; ++k) {
+      const MsgEntry& me = p.fm[(size_t)k];
+      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
+      if (me.role != 1 || mt.kind != LPMP_M_UNARY_PAIRWISE || (mt.param != 0 && mt.param != 1)) continue;
+      const int32_t u = p.m_left[(size_t)me.msg];
+      int32_t& slot = out[mt.param];
+      slot = slot == -1 || slot == u ? u : -2;
+    }
+  };
+  std::vector<int32_t> pair_of((size_t)p.nf, -1);
+  w.link_off.assign(1, 0);
+  for (size_t i = 0; i < w.factors.size(); ++i) {
+    const int32_t u = w.factors[i], d = p.f_dim0[u];
+    w.max_labels = std::max(w.max_labels, d);
+    if (d > MOVE_MAX_LABELS) refuse(u, "has " + std::to_string(d) + " labels (a wave holds a vector of at most " + std::to_string(MOVE_MAX_LABELS) + ")");
+    const size_t first = w.links.size();
+    for (int64_t k = p.fm_off[(size_t)u]; k < p.fm_off[(size_t)u + 1]; ++k) {
+      const MsgEntry& me = p.fm[(size_t)k];
+      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
+      const int32_t pw = me.role == 0 ? p.m_right[(size_t)me.msg] : -1;
+      if (mt.kind != LPMP_M_UNARY_PAIRWISE || pw < 0 || p.f_kind[pw] != LPMP_F_PAIRWISE_DIFF_SHIFT || (mt.param != 0 && mt.param != 1)) {
+        refuse(u, "has a message that is not a unary-pairwise message with the factor as its unary and a DIFF_SHIFT factor on the right");
+        continue;
+      }
+      const int32_t side = mt.param;
+      if ((side ? p.f_dim1[pw] : p.f_dim0[pw]) != d) { refuse(u, "and side " + std::to_string(side) + " of factor " + std::to_string(pw) + " differ in their label counts"); continue; }
+      bool twice = false;
+      for (size_t q = first; q < w.links.size(); ++q) twice = twice || (w.links[q].p == pw && w.links[q].side == side);
+      if (twice) { refuse(u, "has two messages into one vector of factor " + std::to_string(pw)); continue; }
+      w.links.push_back({pw, side});
+      if (pair_of[(size_t)pw] < 0) {
+        int32_t su[2];
+        side_unaries(pw, su);
+        if (su[0] == -2 || su[1] == -2) { refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side"); pair_of[(size_t)pw] = -2; continue; }
+        pair_of[(size_t)pw] = (int32_t)w.pairs.size();
+        w.pairs.push_back({pw, su[0] >= 0 ? row_of[(size_t)su[0]] : -1, su[1] >= 0 ? row_of[(size_t)su[1]] : -1});
+      } else if (pair_of[(size_t)pw] == -2) refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side");
+    }
+    w.link_off.push_back((int64_t)w.links.size());
+  }
+  if (w.links.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error(who + ": more than 2^31 links");
+  if (bad >= 0) throw UnsupportedError(who + ": factor " + std::to_string(bad) + " " + why + " (DESIGN.md 4, moving label windows)");
+}
+}  // namespace
+
+int lpmp_plan_window_info(lpmp_plan* p, int64_t n, const int32_t* factors, int64_t* n_links, int64_t* n_pairwise, char* why, int why_n) {
+  if (why && why_n > 0) why[0] = 0;
+  const int rc = guarded([&] {
+    if (!p || (factors && n < 0)) throw std::runtime_error("lpmp_plan_window_info: bad argument");
+    WindowPlan w;
+    window_plan(p->p, n, factors, "lpmp_plan_window_info", w);
+    if (n_links) *n_links = (int64_t)w.links.size();
+    if (n_pairwise) *n_pairwise = (int64_t)w.pairs.size();
+  });
+  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
+  return rc;
+}
+
+// A prepared list of unaries whose windows move together, modelled on lpmp_readout: records and links are uploaded at create, a
+// move plans and uploads nothing but its inputs
+struct lpmp_window_set {
+  int device = 0;
+  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
+  int64_t n = 0, n_pairwise = 0;
+  int32_t max_labels = 0;
+  DevBuf<MoveRec> recs; DevBuf<MoveLink> links; DevBuf<MoveShiftRec> pairs;
+  DevBuf<int32_t> d_delta;              // a host delta, and host costs, pass through buffers of the set
+  DevBuf<double> d_cost[2];
+};
+
+int lpmp_window_set_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_window_set** out) {
+  return guarded([&] {
+    if (!e || !e->model.plan) throw StateError("lpmp_window_set_create: no model uploaded (a window set lists factors of the uploaded model)");
+    if (!out || (factors && n < 0)) throw std::runtime_error("lpmp_window_set_create: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    ModelState& m = e->model;
+    const Plan& p = m.plan->p;
+    WindowPlan w;
+    window_plan(p, n, factors, "lpmp_window_set_create", w);
+    auto ws = std::make_unique<lpmp_window_set>();
+    ws->device = e->device; ws->gen = m.model_gen;
+    ws->n = (int64_t)w.factors.size(); ws->n_pairwise = (int64_t)w.pairs.size(); ws->max_labels = w.max_labels;
+    std::vector<MoveRec> recs((size_t)ws->n);
+    for (int64_t i = 0; i < ws->n; ++i) {
+      const int32_t u = w.factors[(size_t)i];
+      // (vector factors live in the packed array under every layout)
+      recs[(size_t)i] = {p.f_doff[(size_t)u], p.f_dim0[u], u, (int32_t)w.link_off[(size_t)i], (int32_t)(w.link_off[(size_t)i + 1] - w.link_off[(size_t)i]), (int32_t)i, 0};
+    }
+    std::vector<MoveLink> links(w.links.size());
+    for (size_t k = 0; k < links.size(); ++k) links[k] = {p.doff(w.links[k].p) + (w.links[k].side ? p.f_dim0[w.links[k].p] : 0)};
+    // the places of a shift: those lpmp_set_constants writes for the second entry of a DIFF_SHIFT row
+    const int64_t sh_base = m.d_shared ? (int64_t)(((intptr_t)m.d_shared.get() - (intptr_t)m.d_const) / 8) : 0;
+    std::vector<MoveShiftRec> pairs(w.pairs.size());
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      const int32_t f = w.pairs[k].p;
+      const int64_t cell = p.coff(f), c = (cell - sh_base) / 2;
+      if (c < 0 || 2 * c + 3 >= (int64_t)m.sh_cells.size() || sh_base + 2 * c != cell) throw std::runtime_error("lpmp_window_set_create: internal: factor " + std::to_string(f) + " has no cell");
+      pairs[k] = {cell + 2, m.sh_cells[(size_t)(2 * c + 2)], w.pairs[k].left_row, w.pairs[k].right_row, f, 0};
+    }
+    if (!recs.empty()) { ws->recs.alloc(recs.size()); h2d(ws->recs, recs.data(), recs.size() * sizeof(MoveRec), e->stream); }
+    if (!links.empty()) { ws->links.alloc(links.size()); h2d(ws->links, links.data(), links.size() * sizeof(MoveLink), e->stream); }
+    if (!pairs.empty()) { ws->pairs.alloc(pairs.size()); h2d(ws->pairs, pairs.data(), pairs.size() * sizeof(MoveShiftRec), e->stream); }
+    ++m.schedules_built;   // the link tables: structure, like a schedule, counted once
+    *out = ws.release();
+  });
+}
+void lpmp_window_set_destroy(lpmp_window_set* ws) {
+  if (!ws) return;
+  (void)hipSetDevice(ws->device);
+  delete ws;
+}
+int64_t lpmp_window_set_n(const lpmp_window_set* ws) { return ws ? ws->n : 0; }
+int32_t lpmp_window_set_max_labels(const lpmp_window_set* ws) { return ws ? ws->max_labels : 0; }
+int64_t lpmp_window_set_n_pairwise(const lpmp_window_set* ws) { return ws ? ws->n_pairwise : 0; }
+
+int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
+                      int64_t cost_stride, int cost_mem) {
+  return guarded([&] {
+    const std::string who = "lpmp_move_windows";
+    if (!e || !ws) throw std::runtime_error(who + ": null argument");
+    if (!e->model.plan || ws->gen != e->model.model_gen) throw StateError(who + ": the window set was made for another model (lpmp_upload_model since lpmp_window_set_create)");
+    require_consts(e);
+    const bool costs = cost_old || cost_new;
+    if (delta_mem != LPMP_MEM_HOST && delta_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": delta_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
+    if (costs && cost_mem != LPMP_MEM_HOST && cost_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": cost_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
+    if (!cost_old != !cost_new) throw std::runtime_error(who + ": cost_old and cost_new come together (the unary costs in the old and in the new window), or not at all");
+    if (ws->n > 0 && !delta) throw std::runtime_error(who + ": null delta");
+    if (costs && cost_stride < ws->max_labels)
+      throw std::runtime_error(who + ": cost_stride " + std::to_string(cost_stride) + " is smaller than the " + std::to_string(ws->max_labels) + " entries of the longest listed vector");
+    const bool host_delta = delta_mem == LPMP_MEM_HOST, host_costs = costs && cost_mem == LPMP_MEM_HOST;
+    if (host_delta)
+      for (int64_t i = 0; i < ws->n; ++i)
+        if (delta[i] < -MOVE_DELTA_MAX || delta[i] > MOVE_DELTA_MAX)
+          throw std::runtime_error(who + ": delta " + std::to_string(delta[i]) + " (entry " + std::to_string(i) + ") is beyond +-2^20; nothing was written");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);                 // passes that ran ahead: the duals moved are those of the pass the caller is at
+    // (device inputs never wait for the stream, as a read-out into device memory does not; host inputs end in a synchronisation)
+    if (host_delta || host_costs) check_chain(e);
+    if (ws->n == 0) return;
+    ModelState& m = e->model;
+    const int32_t* d_delta = delta;
+    if (host_delta) { ws->d_delta.grow((size_t)ws->n); h2d(ws->d_delta, delta, (size_t)ws->n * sizeof(int32_t), e->stream); d_delta = ws->d_delta.get(); }
+    const double* d_cost[2] = {cost_old, cost_new};
+    if (host_costs) {
+      const size_t total = (size_t)(ws->n - 1) * (size_t)cost_stride + (size_t)ws->max_labels;   // (the last row need not be a whole stride)
+      for (int k = 0; k < 2; ++k) { ws->d_cost[k].grow(total); h2d(ws->d_cost[k], d_cost[k], total * sizeof(double), e->stream); d_cost[k] = ws->d_cost[k].get(); }
+    }
+    // (the message vectors of DIFF_SHIFT factors and all vector factors live in the packed array under every layout, and both
+    // kernels are plain launches on the engine's stream: never part of a captured graph or a persistent launch)
+    launch_move_shifts(ws->pairs, ws->n_pairwise, d_delta, m.d_const, m.d_lb, e->stream);
+    launch_move_windows(ws->recs, ws->links, ws->n, d_delta, m.d_dual, m.d_lb, d_cost[0], d_cost[1], cost_stride, e->stream);
+    HIP_CHECK(hipGetLastError());
+    if (m.have_primal) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
+    if (host_delta || host_costs) HIP_CHECK(hipStreamSynchronize(e->stream));   // the caller's arrays are the caller's again
+  });
+}
+
 int lpmp_compute_pass_custom(lpmp_engine* e, int64_t n, const int32_t* factors, const int64_t* om_off, const double* om,
                              const int64_t* mk_off, const uint8_t* mk) {
   return guarded([&] {

@@ -4239,4 +4239,83 @@ void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, con
   else launch_readout_beliefs_as<64, READOUT_CHUNK / 64>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
 }
 
+// ---- moving label windows (engine.cpp, lpmp_move_windows) ---------------------------------------------------------
+// The window of a listed unary moves by delta labels: new label x is old label x + delta, labels that enter the window copy the
+// nearest old end value — v'[x] = v[g(x)], g(x) = clamp(x + delta, 0, d0 - 1) — for theta and for the unary's message vector in every
+// adjacent pairwise factor.  One wave per listed unary; a vector of up to MOVE_MAX_LABELS labels is held in registers, lane l the
+// labels l, l + 64, ...  The gather is IN PLACE: with delta < 0 label x reads an entry that label x + delta — another lane, or the
+// same lane's earlier register — overwrites, so every load of a vector has returned (the explicit wait) before its first store is
+// issued.  No LDS, no atomics, plain 8-byte loads and stores, 64-bit offsets.  A device delta is saturated where it is read.
+__device__ __forceinline__ int move_delta(const int32_t* __restrict__ delta, int row) {
+  return row < 0 ? 0 : min(max(delta[row], -MOVE_DELTA_MAX), MOVE_DELTA_MAX);
+}
+__global__ void __launch_bounds__(256)
+move_windows_kernel(const MoveRec* __restrict__ recs, const MoveLink* __restrict__ links, int64_t n, const int32_t* __restrict__ delta,
+                    double* dual, double* __restrict__ lb, const double* __restrict__ cost_old, const double* __restrict__ cost_new,
+                    int64_t cost_stride) {
+  constexpr int PER = MOVE_MAX_LABELS / 64;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const MoveRec r = recs[k];
+  const int d = r.d0, dl = move_delta(delta, r.row);
+  int g[PER];
+#pragma unroll
+  for (int j = 0; j < PER; ++j) g[j] = min(max(lane + 64 * j + dl, 0), d - 1);
+  double v[PER];
+  {
+    double* th = dual + r.dual_off;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (lane + 64 * j < d) v[j] = th[g[j]];
+    if (cost_old) {   // (wave-uniform) the new unary costs: the inner difference first, skipped where the two entries compare equal
+      const double* co = cost_old + (int64_t)r.row * cost_stride;
+      const double* cn = cost_new + (int64_t)r.row * cost_stride;
+#pragma unroll
+      for (int j = 0; j < PER; ++j)
+        if (lane + 64 * j < d) {
+          const double a = cn[lane + 64 * j], b = co[g[j]];
+          if (!(a == b)) v[j] = v[j] + (a - b);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every load of the vector has returned: no store overtakes one
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (lane + 64 * j < d) th[lane + 64 * j] = v[j];
+  }
+  for (int i = 0; i < r.n_links; ++i) {
+    double* m = dual + links[r.link_begin + i].vec_off;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (lane + 64 * j < d) v[j] = m[g[j]];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (lane + 64 * j < d) m[lane + 64 * j] = v[j];
+  }
+  if (lane == 0) lb[r.factor] = __longlong_as_double(-1LL);   // stale, as set_vectors_kernel marks it
+}
+// the shifts of the DIFF_SHIFT factors next to the listed unaries: cost(a, b) = scale * D[clip(a - b + s)] stays the same function of
+// the ABSOLUTE labels exactly when s' = s + delta_left - delta_right.  One thread per factor; the constants are written (both
+// places, as set_constants_kernel writes a DIFF_SHIFT row) only when the two deltas differ, the bound is stale either way — the
+// factor's message vectors have moved
+__global__ void __launch_bounds__(256)
+move_shifts_kernel(const MoveShiftRec* __restrict__ recs, int64_t n, const int32_t* __restrict__ delta, double* __restrict__ cdata,
+                   double* __restrict__ lb) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const MoveShiftRec r = recs[i];
+  const int dl = move_delta(delta, r.left_row), dr = move_delta(delta, r.right_row);
+  if (dl != dr) {
+    const int s = diff_shift_int(cdata[r.cell]) + dl - dr;      // |s| <= 2^30 + 2^21
+    const double v = (double)min(max(s, -(1 << 30)), 1 << 30);
+    cdata[r.cell] = v;
+    cdata[r.packed] = v;
+  }
+  lb[r.factor] = __longlong_as_double(-1LL);
+}
+void launch_move_windows(const MoveRec* recs, const MoveLink* links, int64_t n, const int32_t* delta, double* dual, double* lb,
+                         const double* cost_old, const double* cost_new, int64_t cost_stride, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(move_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, links, n, delta, dual, lb, cost_old, cost_new, cost_stride);
+}
+void launch_move_shifts(const MoveShiftRec* recs, int64_t n, const int32_t* delta, double* cdata, double* lb, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(move_shifts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, delta, cdata, lb);
+}
+
 }  // namespace lpmp

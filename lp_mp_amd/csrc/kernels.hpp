@@ -100,6 +100,18 @@ struct ReadoutRec { int64_t dual_off, row; int32_t d0, factor, link_begin, n_lin
 static_assert(sizeof(ReadoutRec) == 32, "read-out record layout");
 constexpr int READOUT_GROUP_MAX = DECODE_GROUP_MAX;   // beliefs: a lane group per unary up to this many labels, a wave above (the decode's split)
 constexpr int READOUT_CHUNK = DECODE_CHUNK;           // ... and the labels a wave holds in registers at a time
+// moving label windows (lpmp_move_windows): one listed unary — its place in the packed duals, its label count (at most
+// MOVE_MAX_LABELS: a wave holds a whole vector in registers), its row of delta / cost_old / cost_new, and its links in message-list
+// order: the message vector of its side in the pairwise factor (device dual offset) ...
+struct MoveRec { int64_t dual_off; int32_t d0, factor, link_begin, n_links, row, pad; };
+struct MoveLink { int64_t vec_off; };
+// ... and one DIFF_SHIFT factor adjacent to a listed unary: where the sweep kernels read its shift (the third word of its cell) and
+// the scalar of the constants the cell is gathered from, both in 8-byte units relative to the const base pointer as in SetConstRec,
+// and the rows of the unaries on its two sides (-1: no unary there, or one that is not listed: delta 0)
+struct MoveShiftRec { int64_t cell, packed; int32_t left_row, right_row, factor, pad; };
+static_assert(sizeof(MoveRec) == 32 && sizeof(MoveShiftRec) == 32, "window record layout");
+constexpr int MOVE_MAX_LABELS = GEN_MAXD;
+constexpr int MOVE_DELTA_MAX = 1 << 20;               // |delta| of a move: a host value beyond it is refused, a device value saturated
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------
 // The bool ones return false when there is no kernel for the request (each says when, at its definition).
@@ -165,5 +177,12 @@ void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStrea
 // its row, by the rule of launch_narrow_tables (the caller sets it to INT32_MAX first)
 void launch_set_constants_check(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, int strict, int* bad, hipStream_t s);
 void launch_set_constants(const SetConstRec* recs, int64_t n, const double* src, int64_t src_stride, double* cdata, double* lb, hipStream_t s);
+// moving label windows: theta and every linked message vector of record k := the same vector gathered through
+// g(x) = clamp(x + delta[row], 0, d0 - 1), in place; cost_old / cost_new (both or neither; rows cost_stride doubles apart) add
+// cost_new[row][x] - cost_old[row][g(x)] to theta where the two differ.  The shifts: shift := clamp(int(shift) + delta[left_row]
+// - delta[right_row], -2^30, 2^30) at both places of record i when the two deltas differ.  The tracked bounds of all of them: NaN
+void launch_move_windows(const MoveRec* recs, const MoveLink* links, int64_t n, const int32_t* delta, double* dual, double* lb,
+                         const double* cost_old, const double* cost_new, int64_t cost_stride, hipStream_t s);
+void launch_move_shifts(const MoveShiftRec* recs, int64_t n, const int32_t* delta, double* cdata, double* lb, hipStream_t s);
 
 }  // namespace lpmp

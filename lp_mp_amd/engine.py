@@ -79,6 +79,8 @@ EXPORTS = [
     "lpmp_decode_primal", "lpmp_plan_decode_info", "lpmp_plan_get_decode_levels",
     "lpmp_readout_create", "lpmp_readout_destroy", "lpmp_readout_n", "lpmp_readout_max_labels",
     "lpmp_readout_labels", "lpmp_readout_vectors", "lpmp_readout_beliefs",
+    "lpmp_window_set_create", "lpmp_window_set_destroy", "lpmp_window_set_n", "lpmp_window_set_max_labels", "lpmp_window_set_n_pairwise",
+    "lpmp_move_windows", "lpmp_plan_window_info",
 ]
 
 
@@ -220,6 +222,17 @@ def lib():
             L.lpmp_readout_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
             L.lpmp_readout_vectors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
             L.lpmp_readout_beliefs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+        if hasattr(L, "lpmp_move_windows"):          # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_window_set_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+            L.lpmp_window_set_destroy.restype = None
+            L.lpmp_window_set_destroy.argtypes = [C.c_void_p]
+            for n in ("lpmp_window_set_n", "lpmp_window_set_n_pairwise"):
+                getattr(L, n).restype = C.c_int64
+                getattr(L, n).argtypes = [C.c_void_p]
+            L.lpmp_window_set_max_labels.restype = C.c_int32
+            L.lpmp_window_set_max_labels.argtypes = [C.c_void_p]
+            L.lpmp_move_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+            L.lpmp_plan_window_info.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -501,6 +514,26 @@ def _decode_levels(self, d: int):
 
 Plan.decode_info = _decode_info
 Plan.decode_levels = _decode_levels
+
+
+def _window_info(self, factors=None) -> dict:
+    """structure of ``Engine.window_set(factors)`` (lpmp_plan_window_info; None: every VECTOR factor): ``n_links`` unary-pairwise
+    links of the listed factors, ``n_pairwise`` DIFF_SHIFT factors whose shift a move may write.  EngineError: LPMP_ERR_INVALID
+    naming the entry (out of range, not a VECTOR factor, listed twice), LPMP_ERR_UNSUPPORTED naming the lowest listed factor the
+    move does not take."""
+    v = [C.c_int64() for _ in range(2)]
+    buf = C.create_string_buffer(512)
+    if factors is None:
+        n, ptr = 0, None
+    else:
+        factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
+        keep = factors if factors.shape[0] else np.zeros(1, np.int32)
+        n, ptr = int(factors.shape[0]), keep.ctypes.data
+    _chk(self.L.lpmp_plan_window_info(self.h, n, ptr, C.addressof(v[0]), C.addressof(v[1]), buf, 512))
+    return dict(n_links=v[0].value, n_pairwise=v[1].value)
+
+
+Plan.window_info = _window_info
 
 
 def graph_colour_major_order(n: int, edge_i, edge_j, seed: int = 0):
@@ -805,6 +838,11 @@ class Engine:
         labels, unaries and beliefs into device or host arrays without planning or uploading anything per call"""
         return Readout(self, factors)
 
+    def window_set(self, factors=None) -> "WindowSet":
+        """a prepared set of VECTOR factors whose label windows move together (lpmp_window_set_create; None: every VECTOR factor):
+        ``WindowSet.move`` carries their unaries, their messages and the shifts of the adjacent DIFF_SHIFT factors along"""
+        return WindowSet(self, factors)
+
     def check_primal_consistency(self) -> bool:
         out = C.c_int()
         _chk(self.L.lpmp_check_primal_consistency(self.h, C.addressof(out)))
@@ -1007,6 +1045,80 @@ class Readout:
         """[n, stride] float64: row i is the belief of listed factor i — theta plus what every adjacent pairwise factor would send it,
         in the order of its message list (include/lpmp_engine.h has the rule); padding as in ``vectors``"""
         return self._rows(self.L.lpmp_readout_beliefs, dst_dev, stride)
+
+
+class WindowSet:
+    """A prepared list of distinct VECTOR factors of the engine's uploaded model whose label windows move together
+    (include/lpmp_engine.h, lpmp_window_set_* / lpmp_move_windows).  Structure, like a ``Readout``: it stays valid across new costs,
+    passes and moves; after the engine's next ``upload`` every move raises (LPMP_ERR_STATE) and ``close`` still works."""
+
+    def __init__(self, engine: Engine, factors=None):
+        self.e = engine
+        self.L = engine.L
+        h = C.c_void_p()
+        if factors is None:
+            _chk(self.L.lpmp_window_set_create(engine.h, 0, None, C.addressof(h)))
+        else:
+            factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
+            keep = factors if factors.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
+            _chk(self.L.lpmp_window_set_create(engine.h, int(factors.shape[0]), keep.ctypes.data, C.addressof(h)))
+        self.h = h.value
+        self.n = int(self.L.lpmp_window_set_n(self.h))
+        self.n_pairwise = int(self.L.lpmp_window_set_n_pairwise(self.h))
+        self.max_labels = int(self.L.lpmp_window_set_max_labels(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lpmp_window_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def move(self, delta=None, delta_dev: Optional[int] = None, cost_old=None, cost_new=None, cost_dev=None, stride: Optional[int] = None):
+        """move the window of listed factor i by ``delta[i]`` labels (lpmp_move_windows): ``delta`` an integer array of ``n`` entries
+        with |delta| <= 2^20, or ``delta_dev`` a raw device pointer to int32 values.  ``cost_old`` / ``cost_new``: the original unary
+        costs in the old and in the new window as [n, >= max_labels] arrays (both or neither), or ``cost_dev=(old_ptr, new_ptr)`` raw
+        device pointers with ``stride``; a pointer of the pair may be None to hand the library one array alone (refused).  With
+        device inputs only the call is asynchronous on the engine's stream.  ``Engine.model`` keeps the constants of the upload
+        (``model.move_windows`` gives the moved model; ``LP.move_windows`` keeps the mirror's books)."""
+        if delta_dev is not None:
+            dp, dm = C.c_void_p(delta_dev), MEM_DEVICE
+        else:
+            d = np.asarray([] if delta is None else delta).reshape(-1)
+            if d.shape[0] != self.n:
+                raise ValueError(f"move: {self.n} deltas expected, got {d.shape[0]}")
+            if self.n and not np.issubdtype(d.dtype, np.integer):
+                raise ValueError("move: integer deltas are expected")
+            if self.n and (d.min() < -(1 << 31) or d.max() >= (1 << 31)):
+                raise ValueError("move: a delta does not fit an int32")
+            d = np.ascontiguousarray(d, np.int32) if self.n else np.zeros(1, np.int32)
+            dp, dm = C.c_void_p(d.ctypes.data), MEM_HOST
+        co = cn = None
+        cm, cs = MEM_HOST, 0
+        if cost_dev is not None:
+            if stride is None:
+                raise ValueError("move: cost_dev needs stride")
+            co, cn = [None if p is None else C.c_void_p(p) for p in cost_dev]
+            cm, cs = MEM_DEVICE, int(stride)
+        elif cost_old is not None or cost_new is not None:
+            arrs = []
+            for a in (cost_old, cost_new):
+                if a is None:
+                    arrs.append(None)
+                    continue
+                a = np.ascontiguousarray(a, np.float64)
+                if a.ndim != 2 or a.shape[0] < self.n:
+                    raise ValueError("move: costs are [n, >= max_labels] arrays")
+                arrs.append(a)
+            have = [a for a in arrs if a is not None]
+            if len(have) == 2 and have[0].shape != have[1].shape:
+                raise ValueError("move: cost_old and cost_new differ in shape")
+            cs = int(have[0].shape[1]) if stride is None else int(stride)
+            if cs > have[0].shape[1]:
+                raise ValueError("move: stride beyond the rows of the cost arrays")
+            co, cn = [None if a is None else C.c_void_p(a.ctypes.data) for a in arrs]
+        _chk(self.L.lpmp_move_windows(self.e.h, self.h, dp, dm, co, cn, cs, cm))
 
 
 def device_identity(device: int = 0) -> str:

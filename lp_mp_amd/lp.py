@@ -249,6 +249,7 @@ class LP:
         self._duals_host: Optional[np.ndarray] = None
         self._table_precision = None
         self._pool_changed = False           # set_shared_table / set_diff_table since the last upload
+        self._window_sets = {}               # move_windows: the prepared set of a handle list, for the model that is uploaded
 
     def set_table_precision(self, precision):
         """"f64" / "f32" (strict) / "f32_round": dense pairwise tables as floats on the device, widened in the load, all arithmetic
@@ -517,6 +518,60 @@ class LP:
         self._cost_dual = new.dual_data
         e.model = new
 
+    def move_windows(self, handles, delta, new_costs=None):
+        """move the label windows of the unaries ``handles`` (add_factor's return values, each once) by ``delta[i]`` labels ON THE
+        DEVICE (Engine.window_set / WindowSet.move): new label x of unary i is its old label x + delta[i], theta and the messages of
+        the adjacent ``diff_shift_pairwise_factor``s are carried along their label axis, and the shift of every such factor becomes
+        shift + delta_left - delta_right — the warm start that belongs to the new windows.  ``new_costs[i]``: the unary's cost in
+        its new window (same length); None: labels that stay keep their cost and labels that enter the window copy the nearest end.
+        The stored ops follow (``shift`` of the adjacent factors, the unaries' ``cost``), so a following ``upload_costs(warm=True)``
+        finds nothing to send.  NOT a structural call: every schedule stays.  Every message of a listed unary must lead to a
+        diff_shift_pairwise_factor (Engine.window_set raises otherwise, naming the factor)."""
+        import dataclasses
+        e = self._ready()
+        handles = [int(h) for h in handles]
+        delta = np.asarray(delta).reshape(-1)
+        if delta.shape[0] != len(handles) or (len(handles) and not np.issubdtype(delta.dtype, np.integer)):
+            raise RuntimeError("move_windows: one integer delta per handle")
+        if new_costs is not None and len(new_costs) != len(handles):
+            raise RuntimeError("move_windows: one cost vector per handle")
+        key = tuple(handles)
+        if key not in self._window_sets:                  # (prepared once per list and upload: _ready drops them with the model)
+            self._window_sets[key] = (e.window_set(handles), M.window_links(self._model, handles)[2])
+        ws, pairs = self._window_sets[key]
+        old, new = [], []
+        for i, h in enumerate(handles):
+            c = self._factors[h][1].cost
+            g = np.clip(np.arange(c.shape[0]) + int(delta[i]), 0, c.shape[0] - 1)
+            n = c[g] if new_costs is None else np.asarray(new_costs[i], np.float64).reshape(-1)
+            if n.shape != c.shape:
+                raise RuntimeError("move_windows: the cost of factor %d would change its length (a structural change)" % h)
+            old.append(c); new.append(np.array(n, copy=True))
+        if new_costs is None:
+            ws.move(delta)
+        else:
+            L = max(ws.max_labels, 1)
+            co, cn = np.zeros((len(handles), L)), np.zeros((len(handles), L))
+            for i in range(len(handles)):
+                co[i, :old[i].shape[0]] = old[i]; cn[i, :new[i].shape[0]] = new[i]
+            ws.move(delta, cost_old=co, cost_new=cn)
+        # the host's books: ops, the uploaded constants and the costs the next warm upload takes differences to
+        const = np.array(self._model.const_data, np.float64, copy=True)
+        coff, doff = self._model.const_offsets(), self._model.dual_offsets()
+        for p, lrow, rrow in pairs:
+            d = (int(delta[lrow]) if lrow >= 0 else 0) - (int(delta[rrow]) if rrow >= 0 else 0)
+            if d:
+                op = self._factors[p][1]
+                op.shift = int(min(max(op.shift + d, -M.DIFF_SHIFT_MAX), M.DIFF_SHIFT_MAX))
+                const[coff[p] + 1] = np.float64(op.shift)
+        cost_dual = np.array(self._cost_dual, np.float64, copy=True)
+        for i, h in enumerate(handles):
+            self._factors[h][1].cost = new[i]
+            cost_dual[doff[h]:doff[h + 1]] = new[i]
+        self._model = dataclasses.replace(self._model, const_data=const, _keep=[])
+        self._cost_dual = cost_dual
+        e.model = self._model
+
     def _pull_duals(self):
         if self._engine is not None and not self._dirty:
             self._duals_host = self._engine.download_duals()
@@ -532,6 +587,7 @@ class LP:
             self._cost_dual = self._flat_costs       # (not _model.dual_data: after a structural call that holds pulled duals)
             self._engine.upload(self._model, table_precision=self._table_precision)
             self._dirty = False
+            self._window_sets = {}
             self._pool_changed = False
         self._engine.set_inner_iterations(self._inner)
         self._engine.set_reparametrization_type(self._rtype)

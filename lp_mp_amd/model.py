@@ -387,6 +387,140 @@ def window_shift(c_left, c_right, zero_index):
     return np.asarray(c_left, np.int64) - np.asarray(c_right, np.int64) + np.int64(zero_index)
 
 
+MOVE_DELTA_MAX = 1 << 20      # |delta| of a window move (include/lpmp_engine.h, lpmp_move_windows)
+MOVE_MAX_LABELS = 512         # a listed unary's label count
+
+
+class WindowsUnsupported(ValueError):
+    """``window_links`` / ``move_windows``: a listed factor the move does not take (lpmp_window_set_create: LPMP_ERR_UNSUPPORTED)"""
+
+    def __init__(self, factor: int, msg: str):
+        super().__init__(msg)
+        self.factor = factor
+
+
+def window_links(model: "FlatModel", factors=None):
+    """(factors, links, pairs) of a window set, by the rules of lpmp_window_set_create: ``factors`` as an int array (None: every
+    VECTOR factor), ``links[i]`` = [(pairwise factor, side)] of listed factor i, ``pairs`` = [(DIFF_SHIFT factor, row of the listed
+    unary on side 0 or -1, ... on side 1)] in the order the listed unaries meet them.  ValueError for an index out of range, a
+    non-VECTOR factor or a factor listed twice; WindowsUnsupported naming the lowest listed factor the move does not take."""
+    nf = model.n_factors
+    if factors is None:
+        factors = np.flatnonzero(model.f_kind == F_VECTOR)
+    factors = np.asarray(factors, np.int64).reshape(-1)
+    row_of = {}
+    for i, f in enumerate(factors):
+        f = int(f)
+        if f < 0 or f >= nf:
+            raise ValueError(f"window set: factor index {f} (entry {i}) is out of range")
+        if model.f_kind[f] != F_VECTOR:
+            raise ValueError(f"window set: factor {f} (entry {i}) is not a VECTOR factor")
+        if f in row_of:
+            raise ValueError(f"window set: factor {f} (entry {i}) is listed twice")
+        row_of[f] = i
+    of_factor = {}                       # factor -> [(message, role)] in message order
+    for k in range(model.n_messages):
+        of_factor.setdefault(int(model.m_left[k]), []).append((k, 0))
+        of_factor.setdefault(int(model.m_right[k]), []).append((k, 1))
+    bad = {}
+
+    def refuse(u, what):
+        bad.setdefault(u, f"window set: factor {u} {what}")
+
+    def side_unaries(p):
+        out = [-1, -1]
+        for k, role in of_factor.get(p, []):
+            t = model.mtypes[int(model.m_type[k])]
+            if role != 1 or t.kind != M_UNARY_PAIRWISE or t.param not in (0, 1):
+                continue
+            u = int(model.m_left[k])
+            out[t.param] = u if out[t.param] in (-1, u) else -2
+        return out
+    links, pairs, pair_of = [], [], {}
+    for f in factors:
+        u = int(f)
+        d = int(model.f_dim0[u])
+        mine = []
+        if d > MOVE_MAX_LABELS:
+            refuse(u, f"has {d} labels (at most {MOVE_MAX_LABELS})")
+        for k, role in of_factor.get(u, []):
+            t = model.mtypes[int(model.m_type[k])]
+            p = int(model.m_right[k])
+            if role != 0 or t.kind != M_UNARY_PAIRWISE or model.f_kind[p] != F_PAIRWISE_DIFF_SHIFT or t.param not in (0, 1):
+                refuse(u, "has a message that is not a unary-pairwise message with the factor as its unary and a DIFF_SHIFT factor on the right")
+                continue
+            if int(model.f_dim1[p] if t.param else model.f_dim0[p]) != d:
+                refuse(u, f"and side {t.param} of factor {p} differ in their label counts")
+                continue
+            if (p, t.param) in mine:
+                refuse(u, f"has two messages into one vector of factor {p}")
+                continue
+            mine.append((p, t.param))
+            if p not in pair_of:
+                su = side_unaries(p)
+                pair_of[p] = -2 if -2 in su else len(pairs)
+                if pair_of[p] >= 0:
+                    pairs.append((p, row_of.get(su[0], -1), row_of.get(su[1], -1)))
+            if pair_of[p] == -2:
+                refuse(u, f"is next to DIFF_SHIFT factor {p}, which has two different unaries on one side")
+        links.append(mine)
+    if bad:
+        u = min(bad)
+        raise WindowsUnsupported(u, bad[u])
+    return factors, links, pairs
+
+
+def move_windows(model: "FlatModel", duals, factors, delta, cost_old=None, cost_new=None):
+    """The numpy statement of lpmp_move_windows (include/lpmp_engine.h has the rule): the windows of the listed VECTOR ``factors``
+    (None: all of them) move by ``delta[i]`` labels.  Returns ``(model', duals')``: a model with a new const array holding the new
+    shifts (every other array shared with ``model``), and the moved packed duals —
+    theta_u'[x] = theta_u[g(x)] and m_{p,s}'[x] = m_{p,s}[g(x)] with g(x) = clip(x + delta_u, 0, d_u - 1) for every listed u and each
+    of its messages; shift' = clip(diff_shift_int(shift) + delta_l - delta_r, -2^30, 2^30) for every adjacent DIFF_SHIFT factor whose
+    two deltas differ; with ``cost_old`` / ``cost_new`` ([n, >= longest vector], both or neither) theta_u'[x] = theta_u[g] +
+    (cost_new[i][x] - cost_old[i][g]) wherever the two cost entries do not compare equal.  The yardstick of the device call."""
+    import dataclasses
+    factors, links, pairs = window_links(model, factors)
+    n = factors.shape[0]
+    delta = np.asarray(delta).reshape(-1)
+    if delta.shape[0] != n or (n and not np.issubdtype(delta.dtype, np.integer)):
+        raise ValueError("move_windows: one integer delta per listed factor")
+    delta = delta.astype(np.int64)
+    if np.any(np.abs(delta) > MOVE_DELTA_MAX):
+        raise ValueError("move_windows: |delta| <= 2^20")
+    if (cost_old is None) != (cost_new is None):
+        raise ValueError("move_windows: cost_old and cost_new come together, or not at all")
+    if model.const_data is None:
+        raise ValueError("move_windows: the model has no host constants")
+    doff, coff = model.dual_offsets(), model.const_offsets()
+    out = np.array(duals, np.float64, copy=True)
+    src = np.asarray(duals, np.float64)
+    if src.shape != (int(doff[-1]),):
+        raise ValueError("move_windows: duals packed as FlatModel.dual_data are expected")
+    const = np.array(model.const_data, np.float64, copy=True)
+    if cost_old is not None:
+        cost_old, cost_new = np.asarray(cost_old, np.float64), np.asarray(cost_new, np.float64)
+    for i, u in enumerate(factors):
+        u = int(u)
+        d = int(model.f_dim0[u])
+        g = np.clip(np.arange(d, dtype=np.int64) + delta[i], 0, d - 1)
+        th = src[doff[u]: doff[u] + d][g]
+        if cost_old is not None:
+            cn, co = cost_new[i, :d], cost_old[i, :d][g]
+            with np.errstate(invalid="ignore"):
+                th = np.where(cn == co, th, th + (cn - co))
+        out[doff[u]: doff[u] + d] = th
+        for p, side in links[i]:
+            at = int(doff[p]) + (int(model.f_dim0[p]) if side else 0)
+            out[at: at + d] = src[at: at + d][g]
+    for p, lrow, rrow in pairs:
+        dl = int(delta[lrow]) if lrow >= 0 else 0
+        dr = int(delta[rrow]) if rrow >= 0 else 0
+        if dl != dr:
+            s = diff_shift_int(const[coff[p] + 1]) + dl - dr
+            const[coff[p] + 1] = np.float64(min(max(s, -DIFF_SHIFT_MAX), DIFF_SHIFT_MAX))
+    return dataclasses.replace(model, const_data=const, _keep=[]), out
+
+
 def truncated_quadratic(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray:
     """D[k] = min(slope * (k - (d1 - 1))^2, trunc): the square is exact in double, then one multiply"""
     k = np.arange(d0 + d1 - 1, dtype=np.float64) - (d1 - 1)
