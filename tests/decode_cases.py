@@ -35,7 +35,7 @@ def structure(m):
 
 def cost_line(m, coff, p, side, x_other):
     """cost_p(x, x_other) over x when the unary is on side 0, cost_p(x_other, x) when on side 1: the pairwise cost of
-    include/lpmp_model.h (DENSE: the table entry; POTTS: a == b ? 0.0 : diff; SHARED / DIFF: ONE multiply scale * entry)"""
+    include/lpmp_model.h (DENSE: the table entry; POTTS: a == b ? 0.0 : diff; SHARED / DIFF / DIFF_SHIFT: ONE multiply scale * entry)"""
     kind, d0, d1 = int(m.f_kind[p]), int(m.f_dim0[p]), int(m.f_dim1[p])
     c = int(coff[p])
     if kind == M.F_PAIRWISE_DENSE:
@@ -50,6 +50,11 @@ def cost_line(m, coff, p, side, x_other):
     if kind == M.F_PAIRWISE_SHARED:
         V = m.shared_table(t)
         return scale * (V[:, x_other] if side == 0 else V[x_other, :])
+    if kind == M.F_PAIRWISE_DIFF_SHIFT:      # scale * D[clip(a - b + shift, 0, n - 1)], the shift converted as the device converts it
+        n, s = int(m.sh_dim1[t]), M.diff_shift_int(m.const_data[c + 1])
+        D = m.sh_data[int(m.sh_off[t]): int(m.sh_off[t]) + n]
+        k = np.arange(d0) - x_other + s if side == 0 else x_other - np.arange(d1) + s
+        return scale * D[np.clip(k, 0, n - 1)]
     assert kind == M.F_PAIRWISE_DIFF
     D = m.sh_data[int(m.sh_off[t]): int(m.sh_off[t]) + d0 + d1 - 1]
     if side == 0:

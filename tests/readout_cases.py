@@ -18,7 +18,7 @@ INF = float("inf")
 # ---- the rule ------------------------------------------------------------------------------------------------------------------
 def cost_table(m, coff, p):
     """cost_p as a [d0, d1] array: the pairwise cost of include/lpmp_model.h (DENSE: the table; POTTS: a == b ? 0.0 : diff;
-    SHARED / DIFF: ONE multiply scale * entry)"""
+    SHARED / DIFF / DIFF_SHIFT: ONE multiply scale * entry)"""
     kind, d0, d1 = int(m.f_kind[p]), int(m.f_dim0[p]), int(m.f_dim1[p])
     c = int(coff[p])
     if kind == M.F_PAIRWISE_DENSE:
@@ -29,6 +29,10 @@ def cost_table(m, coff, p):
     t = int(m.f_table[p])
     if kind == M.F_PAIRWISE_SHARED:
         return scale * m.shared_table(t)
+    if kind == M.F_PAIRWISE_DIFF_SHIFT:      # scale * D[clip(a - b + shift, 0, n - 1)], the shift converted as the device converts it
+        n, s = int(m.sh_dim1[t]), M.diff_shift_int(m.const_data[c + 1])
+        D = m.sh_data[int(m.sh_off[t]): int(m.sh_off[t]) + n]
+        return scale * D[np.clip(np.arange(d0)[:, None] - np.arange(d1)[None, :] + s, 0, n - 1)]
     assert kind == M.F_PAIRWISE_DIFF
     D = m.sh_data[int(m.sh_off[t]): int(m.sh_off[t]) + d0 + d1 - 1]
     return scale * D[np.arange(d0)[:, None] - np.arange(d1)[None, :] + (d1 - 1)]

@@ -27,6 +27,29 @@ def recost(m, seed, float_valued=False):
     return dataclasses.replace(m, const_data=const, dual_data=dual, _keep=[])
 
 
+def shifts_for(m, factors, seed):
+    """one integer shift per listed DIFF_SHIFT factor, uniform in [-(n + L), n + L] (n: length of the factor's vector D, L: its larger
+    label count), as doubles; every sixteenth entry — counted from ``seed`` — is a named case: shift 0, every index clamped to 0,
+    every index clamped to n - 1"""
+    factors = np.asarray(factors, np.int64)
+    n = np.asarray(m.sh_dim1, np.int64)[np.asarray(m.f_table)[factors]]
+    L = np.maximum(m.f_dim0[factors], m.f_dim1[factors]).astype(np.int64)
+    s = np.random.default_rng([int(seed), 6]).integers(-(n + L), n + L + 1)
+    k = (int(seed) + np.arange(len(factors))) % 16
+    s = np.where(k == 0, 0, np.where(k == 1, -(n + L), np.where(k == 2, n + L, s)))
+    return s.astype(np.float64)
+
+
+def recost_shift(m, seed, float_valued=False):
+    """``recost`` for a model that may hold DIFF_SHIFT factors: their rows are {scale = 0.25 + u, shift = shifts_for} (a shift 0.25 + u
+    is shift 0 on the device for every factor).  A model without the kind: ``recost``, to the bit."""
+    new = recost(m, seed, float_valued)
+    fs = np.flatnonzero(m.f_kind == M.F_PAIRWISE_DIFF_SHIFT)
+    if len(fs):
+        new.const_data[m.const_offsets()[fs] + 1] = shifts_for(m, fs, seed)
+    return new
+
+
 def scatter_rows(m, duals, factors, rows, accumulate=False):
     """the numpy statement of Engine.set_vectors: row i of ``rows`` into (onto) the vector of factors[i] in a copy of the packed duals"""
     off = m.dual_offsets()

@@ -60,6 +60,24 @@ def rows_for(m, factors, seed, float_valued=False, stride=None):
     return rows
 
 
+SHIFT_KINDS = (M.F_PAIRWISE_DENSE, M.F_PAIRWISE_POTTS, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DIFF, M.F_PAIRWISE_DIFF_SHIFT)
+
+
+def listed_subset_shift(m, seed, share=3):
+    """``listed_subset`` that lists DIFF_SHIFT factors as well; a model without the kind: ``listed_subset``, to the entry"""
+    return listed_subset(m, seed, kinds=SHIFT_KINDS, share=share)
+
+
+def rows_for_shift(m, factors, seed, float_valued=False, stride=None):
+    """``rows_for`` whose row of a DIFF_SHIFT factor is {scale = 0.25 + u, shift = recost_cases.shifts_for}; every other row, and
+    every row of a model without the kind, is that of ``rows_for``, to the bit"""
+    rows = rows_for(m, factors, seed, float_valued, stride)
+    at = np.flatnonzero(m.f_kind[np.asarray(factors, np.int64)] == M.F_PAIRWISE_DIFF_SHIFT)
+    if len(at):
+        rows[at, 1] = C.shifts_for(m, np.asarray(factors)[at], seed)
+    return rows
+
+
 def with_rows(m, factors, rows):
     """the numpy statement of Engine.set_constants: the model whose packed constants have those rows replaced"""
     off = m.const_offsets()

@@ -36,6 +36,19 @@ The contract, call by call (op -> paragraph of include/lpmp_engine.h -> statemen
   set_constants               lpmp_set_constants                        repool_cases.with_rows; labels unset
   upload_shared_pool          lpmp_upload_shared_pool                   FlatModel.with_pool; duals kept; labels unset
   upload_duals                lpmp_upload_duals                         the duals given; labels stay
+  window_set_create / destroy lpmp_window_set_create / _destroy         the list is kept by slot (None: every unary); create counts
+                              ("counted ONCE by lpmp_schedules_built")  once in schedules_built; after an upload a move on it is
+                                                                        LPMP_ERR_STATE and destroying it stays legal
+  move_windows(form)          lpmp_move_windows ("moving label          lp_mp_amd.model.move_windows on the model and the duals: duals
+                              windows"): delta / costs from the host    gathered, shifts of the adjacent DIFF_SHIFT factors replaced,
+                              or from device memory, one delta for      labels unset, schedules_built unmoved; every schedule id and
+                              all, all 0                                read-out stays.  The costs: the session's unaries (``nominal``)
+                                                                        in the old window, move_windows_cases.cost_pair in the new
+  (DIFF_SHIFT models)         lpmp_model.h, LPMP_F_PAIRWISE_DIFF_SHIFT  passes and bounds on ``expand_diff()``; decode, energy and
+                                                                        beliefs on scale * D[clip(a - b + int(shift), 0, n - 1)]
+                                                                        (decode_cases.cost_line, readout_cases.cost_table); new costs
+                                                                        and listed rows give {scale, integer shift}
+                                                                        (recost_cases.recost_shift, repool_cases.rows_for_shift)
   lower_bound                 lpmp_lower_bound                          Oracle.LowerBound
   factor_lower_bounds         lpmp_factor_lower_bounds                  Oracle.factor_lower_bound per factor
   download_duals              lpmp_download_duals                       Oracle.duals
@@ -60,7 +73,9 @@ from lp_mp_amd import synthetic as S
 from oracle.binding import Oracle
 
 import decode_cases as DC
+import diff_shift_cases as DS
 import mixed_precision_cases as MP
+import move_windows_cases as MW
 import readout_cases as RO
 import recost_cases as RC
 import repool_cases as RP
@@ -76,7 +91,7 @@ ENERGY_RTOL = 1e-9        # tests/test_decode_gpu.py test_decoded_labels_are_con
 PAIR_TOL = 1e-12          # tests/test_speculation_gpu.py lines 115-121: bounds of two engines, rtol = atol
 
 OBSERVING = ("lb", "flb", "dl", "labels", "ro_labels", "ro_vectors", "ro_beliefs")
-COST = ("cold", "warm", "vectors", "zero", "consts", "pool", "duals")
+COST = ("cold", "warm", "vectors", "zero", "consts", "pool", "duals", "move")
 STATE = ("pass", "dir", "custom", "primal_pass", "decode", "mode", "rtype", "knob") + COST + ("reupload", "refused")
 OP_CLASS = {
     "compute_pass": "pass", "forward_pass": "dir", "backward_pass": "dir",
@@ -89,6 +104,7 @@ OP_CLASS = {
     "set_vectors_diff": "vectors", "set_constants": "consts", "upload_shared_pool": "pool", "upload_duals": "duals", "upload": "reupload", "refused": "refused",
     "lower_bound": "lb", "factor_lower_bounds": "flb", "download_duals": "dl", "labels": "labels",
     "ro_labels": "ro_labels", "ro_vectors": "ro_vectors", "ro_beliefs": "ro_beliefs",
+    "window_set_create": "move", "window_set_destroy": "move", "move_windows": "move",
 }
 CLASS_OPS = {c: tuple(o for o, k in OP_CLASS.items() if k == c) for c in STATE + OBSERVING}
 NEEDS_MODE = {"compute_pass", "forward_pass", "backward_pass", "forward_pass_and_primal", "backward_pass_and_primal",
@@ -113,6 +129,9 @@ def base_model(key):
         return RP.diff_grid(40)
     if key == "shared32":
         return RP.shared_grid_small(32)
+    if key in ("shift24", "shift72"):      # one register per lane and the <= 32 read-out groups | two registers, the > 64 sweep class
+        L = int(key[5:])
+        return DS.shift_grid(7, 6, L, order="colour_major", compute_primal=True, lengths=(5, L, 2 * L - 1))
     raise KeyError(key)
 
 
@@ -121,8 +140,11 @@ def props(key):
     m = base_model(key)
     mrf = all(t.kind == M.M_UNARY_PAIRWISE for t in m.mtypes)
     vec_types = np.unique(m.f_type[m.f_kind == M.F_VECTOR])
+    pw = m.f_kind[m.f_kind != M.F_VECTOR]
+    # shift: some factor is DIFF_SHIFT; windows: every pairwise factor is (every unary may be listed in a window set)
     return dict(mrf=mrf, rounds=mrf and bool(np.all(np.asarray(m.ftype_computes_primal)[vec_types] != 0)), pool=m.sh_data is not None,
-                diff=m.has_diff, dense=bool(np.any(m.f_kind == M.F_PAIRWISE_DENSE)), rows_layout=key == "rows")
+                diff=m.has_diff, dense=bool(np.any(m.f_kind == M.F_PAIRWISE_DENSE)), rows_layout=key == "rows",
+                shift=bool(np.any(pw == M.F_PAIRWISE_DIFF_SHIFT)), windows=mrf and len(pw) > 0 and bool(np.all(pw == M.F_PAIRWISE_DIFF_SHIFT)))
 
 
 @functools.lru_cache(maxsize=None)
@@ -136,7 +158,7 @@ def model_with_costs(key, seed, strict):
     m = base_model(key)
     if seed is None:
         return MP.float_valued(m) if strict else m
-    return RC.recost(m, seed, float_valued=strict)
+    return RC.recost_shift(m, seed, float_valued=strict)
 
 
 def vectors_of(m):
@@ -149,6 +171,62 @@ def vector_subset(m, seed):
     v = vectors_of(m)
     f = rng.permutation(v)[:max(1, len(v) // 3)].astype(np.int32)
     return f, rng.random((len(f), int(m.f_dim0[f].max())))
+
+
+MOVE_FORMS = ("host", "device", "host_costs", "device_costs", "equal", "zero")
+
+
+def window_list(m, seed):
+    """the list of a window set: None (every unary) or the shuffled third of them a read-out lists"""
+    return None if seed is None else vector_subset(m, seed)[0]
+
+
+def window_deltas(dims, seed, form):
+    """one delta per listed unary of ``dims[i]`` labels: about half 0, the rest from +-1, +-2, +-(d - 1), +-d, +-(d + 7); from 65 labels
+    on both signs of a move with 64 <= |delta| < d are forced into two entries (move_windows_cases.has_hazard).  ``equal``: one of the named
+    values, never 0, for every entry; ``zero``: all 0.  No other form gives all 0."""
+    dims = np.asarray(dims, np.int64)
+    if form == "zero":
+        return np.zeros(len(dims), np.int64)
+    rng = np.random.default_rng([int(seed), 11])
+    named = np.stack([dims * 0 + 1, dims * 0 + 2, dims - 1, dims, dims + 7])
+    named = np.concatenate([named, -named])
+    if form == "equal":
+        return np.full(len(dims), named[int(rng.integers(0, 10)), int(np.argmax(dims))], np.int64)
+    out = np.where(rng.random(len(dims)) < 0.5, 0, named[rng.integers(0, 10, len(dims)), np.arange(len(dims))]).astype(np.int64)
+    big = np.flatnonzero(dims > 64)
+    if len(big) >= 2:
+        out[big[-1]] = int(rng.integers(64, dims[big[-1]]))
+        out[big[-2]] = -int(rng.integers(64, dims[big[-2]]))
+    if not out.any():
+        out[0] = 1
+    return out
+
+
+def move_args(m, nominal, lst, seed, form, inf):
+    """(listed factors, delta, cost_old, cost_new, stride) of a move_windows step on model ``m``: the costs (forms ..._costs) are
+    ``nominal`` (packed like the duals: the unary costs the session gave last) in the old window and move_windows_cases.cost_pair's
+    new ones; the device form has a stride above the longest vector"""
+    f = np.asarray(RO.unaries(m) if lst is None else lst, np.int32)
+    delta = window_deltas(m.f_dim0[f], seed, form)
+    if not form.endswith("_costs"):
+        return f, delta, None, None, None
+    stride = int(m.f_dim0[f].max()) + (5 if form == "device_costs" else 0)
+    co, cn = MW.cost_pair(RP.with_duals(m, nominal), f, delta, seed, stride=stride, inf=inf)
+    return f, delta, co, cn, stride
+
+
+def moved_nominal(m, packed, f, delta, cost_new=None):
+    """the unary costs a session keeps (``nominal``, the pending ``warm_new``) after a move: gathered by g like the duals; with costs the
+    listed rows are cost_new (an entry that is +inf in cost_new was carried: it keeps the gathered value)"""
+    out = np.array(packed, np.float64, copy=True)
+    doff = m.dual_offsets()
+    for i, u in enumerate(f):
+        d = int(m.f_dim0[u])
+        g = np.clip(np.arange(d) + int(delta[i]), 0, d - 1)
+        row = np.asarray(packed[doff[u]:doff[u] + d])[g]
+        out[doff[u]:doff[u] + d] = row if cost_new is None else np.where(np.isinf(cost_new[i, :d]), row, cost_new[i, :d])
+    return out
 
 
 @functools.lru_cache(maxsize=16)
@@ -258,6 +336,38 @@ class ShadowReadout:
             raise refuse(ERR_UNSUPPORTED, "beliefs: factor %d " % bad[0])
         m, d = self.sh.eff(), self.sh.duals()
         return _memo("beliefs", m, d, tuple(self.factors), lambda: _beliefs(m, d, self.factors)).copy()
+
+    def close(self):
+        pass
+
+
+class ShadowWindowSet:
+    """Engine.window_set stated on the shadow: the list is checked at create, a move is lp_mp_amd.model.move_windows"""
+
+    def __init__(self, sh, factors):
+        self.sh, self.gen = sh, sh.gen
+        try:
+            self.factors, _, _ = M.window_links(sh.raw, factors)
+        except M.WindowsUnsupported as ex:
+            raise refuse(ERR_UNSUPPORTED, str(ex))
+        except ValueError as ex:
+            raise refuse(ERR_INVALID, str(ex))
+        self.n = len(self.factors)
+        self.max_labels = int(sh.raw.f_dim0[self.factors].max()) if self.n else 0
+
+    def move(self, delta=None, cost_old=None, cost_new=None, stride=None):
+        if not self.sh._window_set_alive(self):
+            raise refuse(ERR_STATE, "the window set was made for another model")
+        delta = np.asarray([] if delta is None else delta).reshape(-1)
+        if delta.shape[0] != self.n:
+            raise ValueError("move: %d deltas expected" % self.n)
+        if (cost_old is None) != (cost_new is None):
+            raise refuse(ERR_INVALID, "cost_old and cost_new come together")
+        if cost_old is not None and (np.shape(cost_old)[1] if stride is None else stride) < self.max_labels:
+            raise refuse(ERR_INVALID, "cost_stride is smaller than the longest listed vector")
+        if np.any(np.abs(delta.astype(np.int64)) > M.MOVE_DELTA_MAX):
+            raise refuse(ERR_INVALID, "a delta beyond +-2^20")
+        self.sh._move(self, delta.astype(np.int64), cost_old, cost_new)
 
     def close(self):
         pass
@@ -374,6 +484,18 @@ class Shadow:
 
     def upload_duals(self, d):
         self._model()
+        self._rebuild(d)
+
+    def window_set(self, factors=None):
+        self._model()
+        return ShadowWindowSet(self, factors)
+
+    def _window_set_alive(self, ws):
+        return self.raw is not None and ws.gen == self.gen
+
+    def _move(self, ws, delta, cost_old, cost_new):
+        self.raw, d = M.move_windows(self.raw, self.duals(), ws.factors, delta, cost_old, cost_new)
+        self.labels = unset_labels(self.raw)
         self._rebuild(d)
 
     # ---- passes ----
@@ -509,8 +631,11 @@ CELLS = {
     "deep": dict(models=("deep",), n=90, seeds=(0, 1, 2, 3)),
     "lists": dict(models=("lists",), n=72, seeds=(0, 1, 2, 3)),
     "diffpool": dict(models=("diff40", "shared32"), n=96, seeds=(0, 1, 2, 3), weight={"pool": 3, "consts": 3}),
+    "windows": dict(models=("shift24", "shift72"), n=144, seeds=(0, 1, 2, 3), weight={"move": 3, "consts": 3}),
 }
-HOP_ROUTES = {0: ("shared32", "joined32", "lists", "diff40"), 1: ("mixed4", "deep", "rows", "shared32"), 2: ("lists", "joined32", "diff40", "rows")}
+# (route 3: a window set goes stale on a hop into a model of another kind, and the engine comes back to a DIFF_SHIFT model)
+HOP_ROUTES = {0: ("shared32", "joined32", "lists", "diff40"), 1: ("mixed4", "deep", "rows", "shared32"), 2: ("lists", "joined32", "diff40", "rows"),
+              3: ("shift24", "deep", "diff40", "shift72")}
 HOP_SEEDS = tuple(HOP_ROUTES)
 
 
@@ -525,6 +650,8 @@ def variant(cell, seed):
             v["env"].update({"LPMP_CHAIN_CACHE_MB": "1", "LPMP_ROT_EXPLICIT": "1"})
     elif cell == "mixed4":
         v["prec"], v["borrowed"] = PRECISIONS[seed % 3], seed >= 3
+    elif cell == "windows":
+        v["borrowed"] = seed == 3          # the packed constants a move writes its shifts to are the caller's buffer
     elif cell == "hop":
         v["env"] = {"LPMP_ROT_BANDS": "6"}
         v["prec"] = "f32_round" if seed == 1 else "f64"
@@ -545,6 +672,8 @@ def admissible_ops(key, prec):
         ops |= {"forward_pass_and_primal", "backward_pass_and_primal", "compute_pass_and_primal"}
     if p["pool"]:
         ops.add("upload_shared_pool")
+    if p["windows"]:
+        ops |= {"window_set_create", "window_set_destroy", "move_windows"}
     return ops
 
 
@@ -556,6 +685,8 @@ def refusal_kinds(key, prec):
     kinds += ["pool_nan", "pool_size"] if p["pool"] else ["pool_none"]
     if prec != "f64" and p["dense"]:
         kinds.append("consts_f32")
+    if p["windows"]:
+        kinds += ["move_delta_range", "move_one_cost", "move_stride", "window_set_twice", "window_set_pairwise"]
     return kinds
 
 
@@ -591,8 +722,17 @@ def _covering_blocks(cell):
     chain = _euler_pairs(cost)
     blocks += [tuple(chain[i:i + 7]) for i in range(0, len(chain) - 1, 6)]       # pieces overlap by one class: no pair is lost
     blocks += [("mode", "pass")] * len(CELLS[cell]["seeds"])                      # other weights for the very next pass
-    kinds = sorted(set().union(*[refusal_kinds(k, "f64") for k in CELLS[cell]["models"]]) | {"destroyed_schedule", "stale_readout"})
+    kinds = sorted(set().union(*[refusal_kinds(k, "f64") for k in CELLS[cell]["models"]]) | {"destroyed_schedule", "stale_readout"}
+                   | ({"stale_window_set"} if "move" in st else set()))
     names = {c: ([o for o in CLASS_OPS[c] if o in ops] if c != "refused" else kinds) for c in st + ob}
+    if "move" in st:
+        # class move stands for the move itself wherever a pair or the chain names it; the handles get blocks of their own below
+        names["move"] = ["move_windows"]
+        # "every call after a move is right": each class that changes no cost right behind a move and right before one (the chain
+        # above holds the cost-changing ones), with an observation behind the pair
+        for s in st:
+            if s not in COST and s not in ("reupload", "refused"):
+                blocks += [("move", s, "dl"), (s, "move", "lb")]
     for c in st + ob:
         have = sum(b.count(c) for b in blocks)
         blocks += [(c,)] * max(0, (3 if c != "refused" else 1) * len(names[c]) - have)
@@ -609,6 +749,16 @@ def _covering_blocks(cell):
     if cell == "joined32":
         # every state-changing class right behind single passes with a batch of passes that ran ahead open (_Gen.spec_block)
         named += [(("spec", c),) for c in st]
+    if "move" in st:
+        mv = ("move", "move_windows")
+        named += [(("move", "window_set_create"),), (("move", "window_set_destroy"),)] * 3
+        # what a move keeps alive or marks stale, used right behind it: a prepared schedule, the labels (unset, decoded anew, rounded
+        # anew), the tracked bounds under a directional sweep and next to lpmp_invalidate_lower_bounds
+        named += [(("custom", "schedule_create"), ("pass", "compute_pass"), mv, ("custom", "schedule_run"), ("dl", "download_duals")),
+                  (("decode", "decode_primal"), mv, ("labels", "labels"), ("decode", "decode_primal"), ("labels", "labels")),
+                  (mv, ("primal_pass", "compute_pass_and_primal"), ("labels", "labels"), mv, ("ro_labels", "ro_labels")),
+                  (("lb", "lower_bound"), mv, ("dir", "forward_pass"), ("lb", "lower_bound"), mv, ("dir", "backward_pass"), ("flb", "factor_lower_bounds")),
+                  (("knob", "invalidate_lower_bounds"), mv, ("lb", "lower_bound"), mv, ("knob", "invalidate_lower_bounds"), ("lb", "lower_bound"))]
     rng = np.random.default_rng(zlib.crc32(cell.encode()))
     order = rng.permutation(len(named))
     seeds = CELLS[cell]["seeds"]
@@ -617,13 +767,13 @@ def _covering_blocks(cell):
 
 def observe_plan(cell, seed, session):
     """per step: are the duals downloaded and compared after it?  About one state-changing step in four (a knob: one in two), always
-    after a refusal, never after compute_pass(1) — a download settles a speculative batch, and a batch has to live across the call
+    after a refusal and after a move_windows (all delta 0: no byte changes), never after compute_pass(1) — a download settles a speculative batch, and a batch has to live across the call
     that follows it.  One draw per step index, so a prefix of a session has the prefix of the plan."""
     u = np.random.default_rng([zlib.crc32(cell.encode()), int(seed), 7]).random(len(session))
     out = []
     for (op, a), x in zip(session, u):
         c = OP_CLASS[op]
-        out.append(c not in OBSERVING and (c == "refused" or (op != "compute_pass" or a[0] != 1) and x < (0.5 if c == "knob" else 0.25)))
+        out.append(c not in OBSERVING and (c == "refused" or op == "move_windows" or (op != "compute_pass" or a[0] != 1) and x < (0.5 if c == "knob" else 0.25)))
     return out
 
 
@@ -732,6 +882,20 @@ class _Gen:
         self.mode, self.rtype = None, RT_SHARED
         self.warm_diff = False       # the difference new - old of the last warm start is still to come
         self.warms = 0
+        self.wlive, self.w_slots, self.w_old = {}, 0, 0      # live window sets {slot: lists every unary}; sets of the previous model not yet tried
+
+    def window_set_create(self, every):
+        self.push("window_set_create", self.w_slots, None if every else self._seed())
+        self.wlive[self.w_slots] = every
+        self.w_slots += 1
+        return self.w_slots - 1
+
+    def move_windows(self, form):
+        slots = sorted(s for s, every in self.wlive.items() if every or form != "equal")
+        if not slots:
+            slots = [self.window_set_create(True)]
+        inf = form.endswith("_costs") and bool(self._next("inf", (True, False, False)))
+        self.push("move_windows", int(slots[int(self.rng.integers(0, len(slots)))]), self._seed(), form, inf)
 
     def _next(self, what, options):
         i = self.turn.get(what, int(self.rng.integers(0, 1 << 16)))
@@ -753,7 +917,7 @@ class _Gen:
     def _check(self, i):
         op, a = self.steps[i]
         c = OP_CLASS[op]
-        return c not in OBSERVING and (c == "refused" or (op != "compute_pass" or a[0] != 1) and self.u[i] < (0.5 if c == "knob" else 0.25))
+        return c not in OBSERVING and (c == "refused" or op == "move_windows" or (op != "compute_pass" or a[0] != 1) and self.u[i] < (0.5 if c == "knob" else 0.25))
 
     def spec_block(self, c, want=None):
         """speculation usable, single passes until the caller stands inside a batch, then a call of class ``c`` and a download"""
@@ -813,6 +977,7 @@ class _Gen:
         self.key, self.prec, self.mode_set = key, prec, False
         self.live, self.dead = [], []
         self.warm_diff = False
+        self.w_old, self.wlive = len(self.wlive), {}
 
     def need_mode(self):
         if not self.mode_set:
@@ -841,11 +1006,36 @@ class _Gen:
         if c == "reupload":
             keys = CELLS[self.cell]["models"] if self.cell in CELLS else (self.key,)
             precs = (self.prec0, "f64") if self.prec0 != "f64" else ("f64",)
-            self.upload(self._next("key", keys), prec=self._next("prec", precs))
+            # (the windows cell goes to its other model every time: both are reached with two uploads)
+            key = [k for k in keys if k != self.key][0] if self.cell == "windows" else self._next("key", keys)
+            self.upload(key, prec=self._next("prec", precs))
+            return
+        if c == "move":
+            op = want if want in ops else self._next(c, ("move_windows", "move_windows", "window_set_create", "move_windows", "move_windows",
+                                                         "window_set_destroy", "move_windows"))
+            if op == "window_set_create":
+                self.window_set_create(bool(self._next("w_every", (False, True, False))))
+            elif op == "window_set_destroy":
+                if len(self.wlive) < 2:                                # (one set stays: a move never waits for one)
+                    self.window_set_create(False)
+                slot = sorted(self.wlive)[int(self.rng.integers(0, len(self.wlive)))]
+                del self.wlive[slot]
+                self.push(op, int(slot))
+            else:
+                self.move_windows(self._next("form", ("host", "device_costs", "equal", "device", "host_costs", "host", "zero", "device", "host_costs", "device_costs")))
             return
         if c == "refused":
             kinds = refusal_kinds(self.key, self.prec) + ["destroyed_schedule"] + (["stale_readout"] if self.uploads >= 2 else [])
+            kinds += ["stale_window_set"] if self.w_old else []
             kind = want if want in kinds else self._next(c, kinds)
+            if self.w_old and kind != "stale_window_set":          # a set of the previous model is tried once after every upload
+                self.push("refused", "stale_window_set", 0)
+                self.w_old -= 1
+            if kind == "stale_window_set":
+                self.w_old -= 1
+            if kind.startswith("move_"):
+                self.push("refused", kind, int(sorted(self.wlive)[int(self.rng.integers(0, len(self.wlive)))]))
+                return
             if self.stale and kind != "stale_readout":              # handles of the previous model are tried once after every move
                 self.push("refused", "stale_readout", self._seed())
             extra = "consts_f32" in kinds and not self.tried_f32 and kind not in ("consts_f32", "stale_readout")      # once per session with float tables
@@ -907,7 +1097,13 @@ class _Gen:
 
 
 def _after_block(g, state):
-    if g.warm_diff:                                  # every other warm start is followed, a step or two later, by its new - old
+    if g.key is not None and props(g.key)["windows"] and not g.wlive:
+        # a set of every unary behind the block of an upload — a move never waits for one —, and one move of the new model's windows
+        # between two passes before anything else happens to it
+        g.window_set_create(True)
+        g.need_mode()
+        g.push("compute_pass", 1); g.move_windows(g._next("first_form", ("host", "device_costs", "device", "host_costs"))); g.push("compute_pass", 1)
+    if g.warm_diff:                                 # every other warm start is followed, a step or two later, by its new - old
         g.push("set_vectors_diff")
         g.warm_diff = False
     if g.key == "joined32":
@@ -921,7 +1117,8 @@ def _after_block(g, state):
 
 def _cell_steps(cell, seed, n):
     g = _Gen(cell, seed, variant(cell, seed)["prec"])
-    g.upload(CELLS[cell]["models"][0], recost=False)
+    # (the windows cell starts on its 24-label model with even seeds and on its 72-label model with odd ones)
+    g.upload(CELLS[cell]["models"][seed % 2 if cell == "windows" else 0], recost=False)
     if cell in ("joined32", "deep"):
         g.push("set_reparametrization", ANISO)
     g.need_mode()
@@ -940,6 +1137,11 @@ def _cell_steps(cell, seed, n):
     if cell == "diffpool":
         # the vector of the upload is banded: a pass on it, a pass after the swap to an unbanded one
         g.push("compute_pass", 1); g.push("upload_shared_pool", "unbanded"); g.push("forward_pass"); g.push("lower_bound")
+    if cell == "windows":
+        # timed launches of the shifted kernel (the count Reach reads), and a move between two passes before anything else happened
+        g.push("enable_kernel_timing", True)
+        _after_block(g, {})
+        g.push("lower_bound")
     blocks = list(_covering_blocks(cell)[seed])
     state = {}
     while blocks if n is None else len(g.steps) < n:
@@ -965,6 +1167,8 @@ def _hop_steps(seed, n):
             if had_slot:
                 g.push("refused", "stale_schedule", 0)
         g.need_mode()
+        if props(key)["windows"]:                                    # the set of the upload moves once at least before the next hop
+            _after_block(g, state)
         g.push("schedule_create", g.n_slots, g._seed(), False)       # a handle for the next move to try
         g.live.append(g.n_slots); g.n_slots += 1
         spec = [g._next("hop_spec", ("cold", "vectors", "consts", "decode", "custom", "warm", "zero", "duals", "knob", "refused"))
@@ -1011,11 +1215,15 @@ class _Side:
         self.ids, self.readouts, self.old_readouts = {}, None, None
         self.stale_id = None
         self.keep = None
+        self.wsets, self.old_wsets = {}, []          # window sets by slot; those of the model before, not yet tried
 
     def close(self):
         for r in (self.readouts or ()) + (self.old_readouts or ()):
             r.close()
         self.readouts = self.old_readouts = None
+        for w in list(self.wsets.values()) + self.old_wsets:
+            w.close()
+        self.wsets, self.old_wsets = {}, []
 
 
 class Reach:
@@ -1030,12 +1238,18 @@ class Reach:
         self._timing = False
         self.precisions = set()
         self._cache = 0
+        self.moves = self.window_sets = 0     # move_windows / window_set_create steps done (run() checks schedules_built around each)
+        self.shift_launches = 0               # timed launches of sweep_diff_shift_kernel
+        self.models = set()                   # keys uploaded
+        self.lb_rel_max = 0.0                 # largest |lower_bound - oracle's| / max(1, |oracle's|) seen (the limit is LB_RTOL)
 
     def before_reset(self, e):
         st = e.speculation_stats()
         self.batches, self.rollbacks = max(self.batches, st["batches"]), max(self.rollbacks, st["rollbacks"])
         self.peer_minima += e.peer_minima_launches()
-        self.chain_launches += sum(v.get("chain_launches", 0) for v in e.kernel_timing().values())
+        timing = e.kernel_timing()
+        self.chain_launches += sum(v.get("chain_launches", 0) for v in timing.values())
+        self.shift_launches += sum(v.get("shift_launches", 0) for v in timing.values())
 
     def after_step(self, e, op, args, mode):
         if op == "enable_kernel_timing":
@@ -1053,6 +1267,7 @@ class Reach:
         self._cache = b
         self.cache_max = max(self.cache_max, b)
         if op == "upload":
+            self.models.add(args[0])
             self.rows |= bool(e.rows_layout)
             self.precisions.add(e.table_precision())
         if OP_CLASS[op] in ("pass", "dir") and mode is not None and e.model.has_diff:
@@ -1070,8 +1285,10 @@ def _upload(side, m, prec, rows_layout):
         d = torch.from_numpy(np.ascontiguousarray(m.dual_data)).cuda()
         torch.cuda.synchronize()
         t.upload(m, const_dev=c.data_ptr(), dual_dev=d.data_ptr(), keep=(c, d), rows_layout=rows_layout, table_precision=prec)
+        side.keep = (c, d)
     else:
         t.upload(m, rows_layout=rows_layout, table_precision=prec)
+        side.keep = None
 
 
 def _expect(code, call):
@@ -1123,6 +1340,23 @@ def _refused(side, sh, kind, arg):
         return ERR_INVALID, lambda: t.schedule_run(side.stale_id)
     if kind == "stale_readout":
         return ERR_STATE, lambda: side.old_readouts[arg % 2].vectors()
+    if kind == "stale_window_set":
+        ws = side.old_wsets[0]
+        return ERR_STATE, lambda: ws.move(np.ones(ws.n, np.int32))
+    if kind == "window_set_twice":
+        return ERR_INVALID, lambda: t.window_set([vec[0], vec[-1], vec[0]])
+    if kind == "window_set_pairwise":
+        return ERR_INVALID, lambda: t.window_set([vec[0], pw[0]])
+    if kind.startswith("move_"):
+        ws = side.wsets[arg]
+        one, co = np.ones(ws.n, np.int32), np.ones((ws.n, ws.max_labels))
+        if kind == "move_delta_range":
+            one[-1] = M.MOVE_DELTA_MAX + 1
+            return ERR_INVALID, lambda: ws.move(one)
+        if kind == "move_one_cost":
+            return ERR_INVALID, lambda: ws.move(one, cost_old=co) if arg % 2 else ws.move(one, cost_new=co)
+        if kind == "move_stride":
+            return ERR_INVALID, lambda: ws.move(one, cost_old=co, cost_new=co + 1.0, stride=ws.max_labels - 1)
     raise KeyError(kind)
 
 
@@ -1150,6 +1384,28 @@ def apply(side, sh, step):
         side.old_readouts = side.readouts
         sub, _ = vector_subset(m, ro_seed)
         side.readouts = (t.readout(sub), t.readout(None))
+        for w in side.old_wsets:
+            w.close()
+        side.old_wsets, side.wsets = [side.wsets[k] for k in sorted(side.wsets)], {}
+    elif op == "window_set_create":
+        side.wsets[a[0]] = t.window_set(window_list(sh.raw, a[1]))
+    elif op == "window_set_destroy":
+        side.wsets.pop(a[0]).close()
+    elif op == "move_windows":
+        ws = side.wsets[a[0]]
+        _, delta, co, cn, stride = move_args(sh.raw, sh.nominal, sh.window_lists[a[0]], a[1], a[2], a[3])
+        if a[2].startswith("device") and isinstance(t, E.Engine):
+            import torch
+            td = torch.from_numpy(delta.astype(np.int32)).cuda()
+            tc = None if co is None else (torch.from_numpy(co).cuda(), torch.from_numpy(cn).cuda())
+            torch.cuda.synchronize()
+            if tc is None:
+                ws.move(delta_dev=td.data_ptr())
+            else:
+                ws.move(delta_dev=td.data_ptr(), cost_dev=(tc[0].data_ptr(), tc[1].data_ptr()), stride=stride)
+            t.synchronize()                           # (the call is asynchronous: the arrays live until it has run)
+        else:
+            ws.move(delta, cost_old=co, cost_new=cn)
     elif op == "compute_pass_custom":
         t.compute_pass_custom(*custom_rows(_key_of(sh), a[0]))
     elif op == "schedule_create":
@@ -1175,8 +1431,8 @@ def apply(side, sh, step):
         f, rows = vector_subset(sh.raw, a[0])
         t.set_vectors(f, rows, accumulate=a[1])
     elif op == "set_constants":
-        f = RP.listed_subset(sh.raw, a[0])
-        t.set_constants(f, RP.rows_for(sh.raw, f, a[0], float_valued=sh.prec == "f32"))
+        f = RP.listed_subset_shift(sh.raw, a[0])            # (DIFF_SHIFT factors listed, too: rows {scale, integer shift})
+        t.set_constants(f, RP.rows_for_shift(sh.raw, f, a[0], float_valued=sh.prec == "f32"))
     elif op == "upload_shared_pool":
         t.upload_shared_pool(pool_variant(sh.raw, a[0]))
     elif op == "upload_duals":
@@ -1184,10 +1440,14 @@ def apply(side, sh, step):
     elif op == "refused":
         if (a[0] == "stale_readout" and side.old_readouts is None) or (a[0] == "stale_schedule" and side.stale_id is None):
             return None                                   # (an engine that took over in the middle of a replay has no older handles)
+        if a[0] == "stale_window_set" and not side.old_wsets:
+            return None
         code, call = _refused(side, sh, a[0], a[1])
         ok, got = _expect(code, call)
         if not ok:
             raise Mismatch("refusal %s: expected %s, got %s" % (a[0], code, got))
+        if a[0] == "stale_window_set":
+            side.old_wsets.pop(0).close()                 # destroying it stays legal
     elif op == "labels":
         return (t.evaluate_primal(), t.check_primal_consistency(), t.download_primal())
     elif op in ("ro_labels", "ro_vectors", "ro_beliefs"):
@@ -1277,6 +1537,8 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                 raise
             raise fail(i, "%s raised EngineError %s: %s" % (op, ex.code, ex))
         for got in seen:
+            if op == "lower_bound" and np.isfinite(got):      # (what the tracked sum differs by from the oracle's: printed with the reach)
+                reach.lb_rel_max = max(reach.lb_rel_max, abs(got - want) / max(1.0, abs(want)))
             bad = compare(op, got, want)
             if bad:
                 raise fail(i, bad + "  (engine / shadow)")
@@ -1301,6 +1563,7 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                         s.t.set_reparametrization(shadow.mode)
                     s.readouts = tuple(s.t.readout(None if r is None else r) for r in shadow.ro_lists)
                     s.ids = {slot: s.t.schedule_create(*rows) for slot, rows in shadow.slot_rows.items()}
+                    s.wsets = {slot: s.t.window_set(lst) for slot, lst in shadow.window_lists.items()}
                     if props(shadow.key)["mrf"]:                    # the labels, too: a later labels / read-out step compares them
                         s.t.upload_primal(shadow.download_primal())
                 engines[:] = [s.t for s in sides]
@@ -1308,8 +1571,14 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                 check(i, op)
                 continue
             if op == "upload":
-                shadow.key, shadow.slot_rows = a[0], {}
+                shadow.key, shadow.slot_rows, shadow.window_lists, shadow.warm_new = a[0], {}, {}, None
                 shadow.ro_lists = (vector_subset(base_model(a[0]), a[3])[0], None)
+            if op == "window_set_create":
+                shadow.window_lists[a[0]] = window_list(shadow.raw, a[1])
+            if op == "window_set_destroy":
+                shadow.window_lists.pop(a[0], None)
+            if op == "move_windows":                               # what the shadow keeps of the costs follows the move (below)
+                mf, md, _, mcn, _ = move_args(shadow.raw, shadow.nominal, shadow.window_lists[a[0]], a[1], a[2], a[3])
             if op == "upload_duals":
                 shadow.pending_duals = shadow.download_duals() * 0.5
             if op == "schedule_create":
@@ -1322,7 +1591,14 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                         continue
                     if op == "reset_kernel_timing" and isinstance(s.t, E.Engine):
                         reach.before_reset(s.t)
+                    built = s.t.schedules_built() if op in ("move_windows", "window_set_create") and isinstance(s.t, E.Engine) else None
                     apply(s, shadow, (op, a))
+                    if built is not None:
+                        # lpmp_window_set_create: "counted ONCE by lpmp_schedules_built"; lpmp_move_windows: "plans nothing"
+                        reach.moves += op == "move_windows"
+                        reach.window_sets += op == "window_set_create"
+                        if s.t.schedules_built() != built + (op == "window_set_create"):
+                            raise Mismatch("schedules_built went from %d to %d" % (built, s.t.schedules_built()))
                 apply(ssh, shadow, (op, a))
             except Mismatch as ex:
                 raise fail(i, str(ex))
@@ -1336,6 +1612,16 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                 shadow.warm_new = _recost(shadow, a[0]).dual_data
             if op == "set_vectors_diff":
                 shadow.nominal = shadow.warm_new
+            if op == "move_windows":
+                for s in sides:                                     # a borrowed constants buffer: the packed shifts, bit for bit
+                    if s.keep is not None:
+                        s.t.synchronize()
+                        got = s.keep[0].cpu().numpy()
+                        if got.tobytes() != np.ascontiguousarray(shadow.raw.const_data, np.float64).tobytes():
+                            raise fail(i, "packed constants in the caller's buffer: " + _first_diff(got, shadow.raw.const_data))
+                shadow.nominal = moved_nominal(shadow.raw, shadow.nominal, mf, md, mcn)
+                if getattr(shadow, "warm_new", None) is not None:
+                    shadow.warm_new = moved_nominal(shadow.raw, shadow.warm_new, mf, md)
             for s in sides:
                 if isinstance(s.t, E.Engine):
                     reach.after_step(s.t, op, a, shadow.mode)

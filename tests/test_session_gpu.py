@@ -21,7 +21,11 @@ def _run(cell, seed, monkeypatch, pair=False):
     engines, skip = [], {}
     reach = SC.Reach()
     try:
-        if pair:                      # the first engine: no passes ahead of the caller, the publishing records without LDS
+        if pair and cell == "windows":    # the first engine: plain launches throughout, the second one follows the session (chain launches)
+            engines.append(E.Engine(0))
+            engines[0].set_persistent_launches(False)
+            skip = {0: {"set_persistent_launches"}}
+        elif pair:                    # the first engine: no passes ahead of the caller, the publishing records without LDS
             monkeypatch.setenv("LPMP_PQ_LDS", "0")
             engines.append(E.Engine(0))
             monkeypatch.delenv("LPMP_PQ_LDS")
@@ -49,6 +53,8 @@ def _run(cell, seed, monkeypatch, pair=False):
 
 @pytest.mark.parametrize("cell,seed", SC.sessions())
 def test_session(cell, seed, monkeypatch):
+    """(the windows cell, 113 factors: with duals bit-identical the bounds differed from the oracle's by at most 6.1e-15 relative over
+    its four sessions, Reach.lb_rel_max — the suite's LB_RTOL = 1e-9 holds for DIFF_SHIFT models, no constant of its own)"""
     reach, v = _run(cell, seed, monkeypatch)
     print(cell, seed, vars(reach))
     if cell == "joined32":
@@ -63,6 +69,10 @@ def test_session(cell, seed, monkeypatch):
         assert reach.deep_chain_passes > 0, vars(reach)
     elif cell == "diffpool":
         assert reach.banded and reach.full, vars(reach)
+    elif cell == "windows":
+        # windows moved, timed launches of the shifted kernel, both label counts (SC.run checked schedules_built around every
+        # window_set_create — one more — and every move_windows — unmoved)
+        assert reach.moves > 0 and reach.window_sets > 0 and reach.shift_launches > 0 and reach.models == {"shift24", "shift72"}, vars(reach)
 
 
 @pytest.mark.parametrize("seed", SC.HOP_SEEDS)
@@ -71,10 +81,13 @@ def test_one_engine_moves_through_four_models(seed, monkeypatch):
     print("hop", seed, vars(reach))
 
 
-@pytest.mark.parametrize("cell,seed", [("joined32", 0), ("mixed4", 2)])
+@pytest.mark.parametrize("cell,seed", [("joined32", 0), ("mixed4", 2), ("windows", 1)])
 def test_two_engines_run_the_same_session(cell, seed, monkeypatch):
-    """one engine without passes ahead and with LPMP_PQ_LDS=0, one with the defaults: both equal the shadow, and each other bit for bit
-    (bounds as tests/test_speculation_gpu.py lines 115-121 allow)"""
+    """one engine without passes ahead and with LPMP_PQ_LDS=0, one with the defaults (windows: one engine with plain launches
+    throughout, one that follows the session's set_persistent_launches): both equal the shadow, and each other bit for bit (bounds
+    as tests/test_speculation_gpu.py lines 115-121 allow)"""
     reach, _ = _run(cell, seed, monkeypatch, pair=True)
     if cell == "joined32":
         assert reach.peer_minima > 0 and reach.batches > 0, vars(reach)
+    if cell == "windows":
+        assert reach.moves > 0 and reach.models == {"shift24", "shift72"}, vars(reach)

@@ -4,6 +4,7 @@ the defects it is for — engines with one seeded defect each make a session fai
 after it.  A green run of tests/test_session_gpu.py means what these tests make it mean."""
 import collections
 import dataclasses
+import zlib
 
 import numpy as np
 import pytest
@@ -38,6 +39,27 @@ def test_steps_are_a_pure_function_and_prefixes_replay(cell, seed):
         assert op in SC.OP_CLASS and all(isinstance(x, (int, str, bool, type(None))) for x in args), (op, args)
 
 
+# crc32 of repr(steps(cell, seed)) of every session that was committed before the windows cell and hop route 3 came (computed on the
+# commit before them): a new op, class or cell must leave the sessions that exist as they are
+STEP_DIGESTS = {
+    "joined32": {0: 0x701a6554, 1: 0xb27b3ebc, 2: 0xd577a5f8, 3: 0x66ba7427},
+    "mixed4": {0: 0x7da306fd, 1: 0x8c2d485a, 2: 0xc3af258a, 3: 0x85e85698, 4: 0x26e2e77c, 5: 0x845003a3},
+    "rows": {0: 0x2de26086, 1: 0xe247779e, 2: 0x4abdeaa7, 3: 0xc6d6db41},
+    "deep": {0: 0x2dc5e04f, 1: 0xc366597f, 2: 0x1115e9cd, 3: 0x01f3443e},
+    "lists": {0: 0x3a7d8a6f, 1: 0x399a6905, 2: 0x32a27a3a, 3: 0x04451d75},
+    "diffpool": {0: 0x010f493c, 1: 0xe5fda1cb, 2: 0xa274ea55, 3: 0x7f75df4f},
+    "hop": {0: 0x904bf48f, 1: 0xe05d07c5, 2: 0x03a8f414},
+}
+
+
+def test_the_sessions_from_before_the_windows_cell_are_unchanged():
+    for cell, seeds in STEP_DIGESTS.items():
+        assert set(seeds) <= set(SC.HOP_SEEDS if cell == "hop" else SC.CELLS[cell]["seeds"]), cell
+        for seed, want in seeds.items():
+            assert zlib.crc32(repr(SC.steps(cell, seed)).encode()) == want, (cell, seed)
+    assert {c for c, _ in ALL} - set(STEP_DIGESTS) == {"windows"} and set(SC.HOP_SEEDS) - set(STEP_DIGESTS["hop"]) == {3}
+
+
 # ---- coverage: a condition on the generator ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cell", list(SC.CELLS))
 def test_committed_sessions_cover_ops_pairs_and_cost_pairs(cell):
@@ -67,6 +89,7 @@ def test_committed_sessions_cover_ops_pairs_and_cost_pairs(cell):
     for key in SC.CELLS[cell]["models"]:
         precs = {SC.variant(cell, s)["prec"] for s in seeds}
         want = set().union(*[SC.refusal_kinds(key, p) for p in precs]) | {"destroyed_schedule", "stale_readout"}
+        want |= {"stale_window_set"} if SC.props(key)["windows"] else set()
         assert want <= set(kinds), want - set(kinds)
 
 
@@ -124,7 +147,148 @@ def test_cells_reach_the_state_they_are_about():
             rtype = a[0] if op == "set_reparametrization_type" else rtype
             assert not (op == "upload" and not SC.props(a[0])["mrf"] and rtype != 0), (seed, i)
         for i in ups[1:]:
-            assert s[i + 1] == ("refused", ("stale_readout", s[i + 1][1][1])) and s[i + 2][:1] == ("refused",) and s[i + 2][1][0] == "stale_schedule"
+            # (the window set that comes with a DIFF_SHIFT model and the try of the one before stand first)
+            r = [x for x in s[i + 1:i + 6] if x[0] != "window_set_create" and x[:1] + x[1][:1] != ("refused", "stale_window_set")]
+            assert r[0] == ("refused", ("stale_readout", r[0][1][1])) and r[1][:1] == ("refused",) and r[1][1][0] == "stale_schedule"
+            assert (("refused", ("stale_window_set", 0)) in s[i + 1:i + 4]) == SC.props(s[[u for u in ups if u < i][-1]][1][0])["windows"]
+
+
+# ---- the windows cell: what its committed steps hold ---------------------------------------------------------------------------
+def _moves(cell, seed):
+    """(step index, model key, form, label counts of the listed unaries, their deltas, inf) of every move_windows step"""
+    key, lists, out = None, {}, []
+    for i, (op, a) in enumerate(SC.steps(cell, seed)):
+        if op == "upload":
+            key, lists = a[0], {}
+        elif op == "window_set_create":
+            lists[a[0]] = SC.window_list(SC.base_model(key), a[1])
+        elif op == "move_windows":
+            m = SC.base_model(key)
+            f = np.asarray(SC.RO.unaries(m) if lists[a[0]] is None else lists[a[0]])
+            out.append((i, key, a[2], m.f_dim0[f], SC.window_deltas(m.f_dim0[f], a[1], a[2]), a[3]))
+    return out
+
+
+def test_window_deltas_and_costs_are_what_the_cell_says():
+    for d in (24, 72):
+        dims = np.full(42, d)
+        named = {0, 1, 2, d - 1, d, d + 7}
+        seen, zeros = set(), 0
+        for seed in range(40):
+            x = SC.window_deltas(dims, seed, "host")
+            assert set(np.abs(x).tolist()) <= named | (set(range(64, d)) if d > 64 else set()) and x.any()
+            assert SC.MW.has_hazard(dims, x) == (d > 64)
+            seen |= set(x.tolist())
+            zeros += int(np.sum(x == 0))
+            e = SC.window_deltas(dims, seed, "equal")
+            assert len(set(e.tolist())) == 1 and abs(int(e[0])) in named - {0}
+            assert not SC.window_deltas(dims, seed, "zero").any()
+        assert {s * v for s in (1, -1) for v in named} <= seen and 0.4 < zeros / (40 * 42) < 0.6
+    # the costs: the session's unaries in the old window; every second row keeps the labels that stay bit for bit
+    m = SC.base_model("shift24")
+    nominal = m.dual_data + 1.0
+    f, delta, co, cn, stride = SC.move_args(m, nominal, None, 4, "device_costs", True)
+    off = m.dual_offsets()
+    assert stride > 24 and co.shape == cn.shape == (42, stride) and np.isinf(co).any() and np.array_equal(np.isinf(co).sum(1), np.isinf(cn).sum(1))
+    for i, u in enumerate(f):
+        fin = np.isfinite(co[i, :24])
+        assert np.array_equal(co[i, :24][fin], nominal[off[u]:off[u] + 24][fin])
+    new = SC.moved_nominal(m, nominal, f, delta, cn)
+    assert np.all(np.isfinite(new)) and np.array_equal(new[off[f[1]]:off[f[1]] + 24], cn[1, :24])
+    assert SC.move_args(m, nominal, None, 4, "host", False)[2:] == (None, None, None)
+
+
+def test_windows_sessions_hold_what_the_cell_is_about():
+    seeds = SC.CELLS["windows"]["seeds"]
+    assert all(SC.props(k)["windows"] and SC.props(k)["shift"] and SC.props(k)["rounds"] and SC.props(k)["pool"] for k in ("shift24", "shift72"))
+    assert not any(SC.props(k)["windows"] or SC.props(k)["shift"] for c in STEP_DIGESTS if c != "hop" for k in SC.CELLS[c]["models"])
+    forms, infs, next_to = collections.Counter(), 0, collections.Counter()
+    run_after, decode_after = 0, 0
+    cost_ops = ("set_constants", "upload_costs_warm", "upload_costs_cold", "upload_duals", "zero_pairwise_duals", "upload_shared_pool")
+    for seed in seeds:
+        s, mv = SC.steps("windows", seed), _moves("windows", seed)
+        assert {a[0] for op, a in s if op == "upload"} == {"shift24", "shift72"}, seed
+        forms.update(x[2] for x in mv)
+        infs += sum(1 for x in mv if x[5] and x[2].endswith("_costs"))
+        # a move with both signs in 64 ... 71 on the 72-label model: the in-place hazard of move_windows_cases.deltas
+        assert any(k == "shift72" and SC.MW.has_hazard(dims, delta) for _, k, _, dims, delta, _ in mv), seed
+        # a cap, not a measurement: the cell cannot pass by not moving
+        still = [x for x in mv if x[2] == "zero" or not x[4].any()]
+        assert 6 * len(still) <= len(mv), (seed, len(still), len(mv))
+        for i in range(len(s) - 1):
+            if s[i][0] == "move_windows" and s[i + 1][0] in cost_ops:
+                next_to[("move", s[i + 1][0])] += 1
+            if s[i + 1][0] == "move_windows" and s[i][0] in cost_ops:
+                next_to[(s[i][0], "move")] += 1
+        # a prepared schedule made before a move runs after it; a decode and the labels follow a move with no cost change between
+        made, moved = {}, []
+        for i, (op, a) in enumerate(s):
+            if op == "upload":
+                made, moved = {}, []
+            elif op == "schedule_create":
+                made[a[0]] = i
+            elif op == "move_windows":
+                moved.append(i)
+            elif op == "schedule_run":
+                run_after += any(made[a[0]] < k for k in moved)
+        plan = SC.observe_plan("windows", seed, s)
+        assert all(plan[i] for i in moved_all(s))          # the duals are compared behind every move
+        for i in moved_all(s):
+            quiet = next((j for j in range(i + 1, len(s)) if _cls(s[j]) in SC.COST + ("reupload",)), len(s))
+            ops = [s[j][0] for j in range(i + 1, quiet)]
+            decode_after += "decode_primal" in ops and "labels" in ops[ops.index("decode_primal"):]
+    print("forms", dict(forms), "| inf", infs, "| next to", dict(next_to), "| schedule_run after a move", run_after, "| decode and labels after a move", decode_after)
+    assert set(forms) == set(SC.MOVE_FORMS) and infs >= 1
+    assert not [x for x in cost_ops if next_to[("move", x)] < 1 or next_to[(x, "move")] < 1], dict(next_to)
+    assert run_after >= 1 and decode_after >= 1
+    # the rows of the committed set_constants steps and the costs of the committed uploads hold shift 0 and shifts that clamp every index
+    shifts = []
+    for seed in seeds:
+        key = None
+        for op, a in SC.steps("windows", seed):
+            key = a[0] if op == "upload" else key
+            m = SC.base_model(key)
+            n_L = np.asarray(m.sh_dim1)[m.f_table] + np.maximum(m.f_dim0, m.f_dim1)
+            if op == "set_constants":
+                f = RP.listed_subset_shift(m, a[0])
+                assert np.all(m.f_kind[f] == M.F_PAIRWISE_DIFF_SHIFT)
+                shifts += list(zip(RP.rows_for_shift(m, f, a[0])[:, 1], n_L[f]))
+            elif op in ("upload_costs_cold", "upload_costs_warm") or (op == "upload" and a[1] is not None):
+                c = SC.model_with_costs(key, a[0] if op != "upload" else a[1], False).const_data.reshape(-1, 2)[:, 1]
+                shifts += list(zip(c, n_L[m.f_kind == M.F_PAIRWISE_DIFF_SHIFT]))
+    assert all(x == np.trunc(x) and abs(x) <= nl for x, nl in shifts)
+    assert any(x == 0 for x, _ in shifts) and any(x == -nl for x, nl in shifts) and any(x == nl for x, nl in shifts)
+    assert len({x for x, _ in shifts}) > 100
+
+
+def moved_all(s):
+    return [i for i, (op, _) in enumerate(s) if op == "move_windows"]
+
+
+def test_numpy_statements_know_diff_shift():
+    """decode, energy and beliefs of a DIFF_SHIFT model stated on the kind equal those on expand_diff() bit for bit (the oracle runs on
+    the expansion); the shift-aware helpers give integer shifts there and leave every other model as it was"""
+    m = SC.model_with_costs("shift24", 5, False)
+    shifts = m.const_data.reshape(-1, 2)[:, 1]
+    assert np.all(shifts == np.trunc(shifts)) and len(set(shifts.tolist())) > 30 and 0.0 in shifts
+    assert all(M.diff_shift_int(x) in (0, 1) for x in RC.recost(SC.base_model("shift24"), 5).const_data.reshape(-1, 2)[:, 1])   # (0.25 + u: the hole)
+    o = Oracle(RC.oracle_model(m))
+    o.set_reparametrization(SC.ANISO)
+    o.ComputePass(2)
+    d, x = o.duals(), m.expand_diff()
+    assert x.n_factors == m.n_factors and np.array_equal(x.dual_offsets(), m.dual_offsets()) and not x.has_diff
+    for direction in (0, 1):
+        lab = SC.DC.decode_reference(m, d, o.order(direction), 1)
+        assert np.array_equal(lab, SC.DC.decode_reference(x, d, o.order(direction), 1))
+        e = SC.DC.energy(RP.with_duals(m, SC.original_unaries(m, d)), lab)
+        assert np.isfinite(e) and e == SC.DC.energy(RP.with_duals(x, SC.original_unaries(x, d)), lab)
+    u = SC.RO.unaries(m)[::5]
+    assert np.array_equal(SC.RO.beliefs_np(m, d, u), SC.RO.beliefs_np(x, d, u))
+    for key in ("diff40", "shared32", "mixed4", "lists"):
+        b = SC.base_model(key)
+        assert np.array_equal(RC.recost_shift(b, 3).const_data, RC.recost(b, 3).const_data)
+        f = RP.listed_subset(b, 9)
+        assert np.array_equal(RP.listed_subset_shift(b, 9), f) and np.array_equal(RP.rows_for_shift(b, f, 9), RP.rows_for(b, f, 9))
 
 
 @pytest.mark.parametrize("key", ["joined32", "mixed4", "deep"])
@@ -148,7 +312,7 @@ def straight_replay(session):
     """the duals at the end of a session from ONE walk through the plain oracle and the per-feature numpy statements, without the
     Shadow class: what moves duals or costs, in the order of the steps"""
     raw = o = mode = key = prec = nominal = warm_new = None
-    rtype, slots = 0, {}
+    rtype, slots, lists = 0, {}, {}
 
     def rebuild(duals):
         m = RP.with_duals(raw, duals)
@@ -160,9 +324,9 @@ def straight_replay(session):
 
     for i, (op, a) in enumerate(session):
         if op == "upload":
-            key, prec, mode, slots = a[0], a[2], None, {}
+            key, prec, mode, slots, lists = a[0], a[2], None, {}, {}
             raw = SC.model_with_costs(key, a[1], prec == "f32")
-            nominal = raw.dual_data
+            nominal, warm_new = raw.dual_data, None
             o = rebuild(raw.dual_data)
         elif op == "set_reparametrization":
             mode = a[0]; o.set_reparametrization(mode)
@@ -201,9 +365,17 @@ def straight_replay(session):
         elif op == "zero_pairwise_duals":
             o = rebuild(RC.zero_pairwise(raw, o.duals()))
         elif op == "set_constants":
-            f = RP.listed_subset(raw, a[0])
-            raw = RP.with_rows(raw, f, RP.rows_for(raw, f, a[0], float_valued=prec == "f32"))
+            f = RP.listed_subset_shift(raw, a[0])
+            raw = RP.with_rows(raw, f, RP.rows_for_shift(raw, f, a[0], float_valued=prec == "f32"))
             o = rebuild(o.duals())
+        elif op == "window_set_create":
+            lists[a[0]] = SC.window_list(raw, a[1])
+        elif op == "move_windows":
+            f, delta, co, cn, _ = SC.move_args(raw, nominal, lists[a[0]], a[1], a[2], a[3])
+            raw, d = M.move_windows(raw, o.duals(), f, delta, co, cn)
+            nominal = SC.moved_nominal(raw, nominal, f, delta, cn)
+            warm_new = None if warm_new is None else SC.moved_nominal(raw, warm_new, f, delta)
+            o = rebuild(d)
         elif op == "upload_shared_pool":
             raw = raw.with_pool(SC.pool_variant(raw, a[0]))
             o = rebuild(o.duals())
@@ -342,6 +514,135 @@ class ReadoutAnswersFromTheUpload(SC.Shadow):
         return _StaleReadout(self, factors)
 
 
+# ---- defects of a move (the windows cell) ----
+class MoveLeavesTheShifts(SC.Shadow):
+    """duals moved, constants kept"""
+
+    def _move(self, ws, delta, cost_old, cost_new):
+        raw = self.raw
+        super()._move(ws, delta, cost_old, cost_new)
+        d, self.raw = self.duals(), raw
+        self._rebuild(d)
+
+
+class MoveSkipsTheMessages(SC.Shadow):
+    """theta and shifts moved, message vectors kept"""
+
+    def _move(self, ws, delta, cost_old, cost_new):
+        before = self.duals()
+        super()._move(ws, delta, cost_old, cost_new)
+        d, pw = self.duals(), ~RC.vector_mask(self.raw)
+        d[pw] = before[pw]
+        self._rebuild(d)
+
+
+class BoundCachedAcrossAMove(SC.Shadow):
+    """the next lower_bound after a move answers with the sum from before it (the bounds were not marked stale)"""
+    _lb = None
+
+    def _move(self, ws, delta, cost_old, cost_new):
+        lb = SC.Shadow.lower_bound(self)
+        super()._move(ws, delta, cost_old, cost_new)
+        self._lb = lb
+
+    def lower_bound(self):
+        self._model()
+        lb, self._lb = self._lb, None
+        return lb if lb is not None else super().lower_bound()
+
+
+class LabelsSurviveAMove(SC.Shadow):
+    def _move(self, ws, delta, cost_old, cost_new):
+        lab = self.labels
+        super()._move(ws, delta, cost_old, cost_new)
+        self.labels = lab
+
+
+class MoveWritesOnlyOnePlace(SC.Shadow):
+    """the new shifts reach the packed constants and not the cells the kernels read: modelled as "the next call that gives duals and
+    no constants runs on the shifts from before the move" (a call that gives constants writes both places again)"""
+    _old = None
+
+    def _move(self, ws, delta, cost_old, cost_new):
+        old = self.raw.const_data if self._old is None else self._old
+        super()._move(ws, delta, cost_old, cost_new)
+        self._old = old
+
+    def _drop(self):
+        if self._old is not None:
+            self.raw, self._old = dataclasses.replace(self.raw, const_data=self._old, _keep=[]), None
+
+    def upload_duals(self, d):
+        self._drop(); super().upload_duals(d)
+
+    def zero_pairwise_duals(self):
+        self._drop(); super().zero_pairwise_duals()
+
+    def upload_costs(self, const=None, duals=None):
+        self._old = None if const is not None else self._old
+        self._drop(); super().upload_costs(const, duals)
+
+    def set_constants(self, factors, src):
+        self._old = None; super().set_constants(factors, src)
+
+    def upload(self, model, **kw):
+        self._old = None; super().upload(model, **kw)
+
+
+class StaleSetStillMoves(SC.Shadow):
+    def _window_set_alive(self, ws):
+        return self.raw is not None
+
+
+_PASSES = ("compute_pass", "forward_pass", "backward_pass", "compute_pass_custom", "schedule_run", "forward_pass_and_primal",
+           "backward_pass_and_primal", "compute_pass_and_primal")
+_COSTS_SEEN = ("lower_bound", "factor_lower_bounds", "ro_beliefs", "refused") + _PASSES
+# defect of a move -> (ops whose call is defective, ops that show it whenever the call before bit, ops that may show it, forms of a
+# move that cannot bite)
+MOVE_DEFECTS = {
+    MoveLeavesTheShifts: (("move_windows",), _COSTS_SEEN, ("labels", "decode_primal"), ("zero", "equal")),
+    MoveSkipsTheMessages: (("move_windows",), (), (), ("zero",)),
+    BoundCachedAcrossAMove: (("move_windows",), ("lower_bound",), (), ("zero",)),
+    LabelsSurviveAMove: (("move_windows",), (), ("labels", "ro_labels"), ()),
+    MoveWritesOnlyOnePlace: (("upload_duals", "zero_pairwise_duals"), _COSTS_SEEN, ("labels", "decode_primal"), ("zero", "equal")),
+    StaleSetStillMoves: (("refused",), (), (), ()),
+}
+
+
+@pytest.mark.parametrize("defect", list(MOVE_DEFECTS), ids=lambda d: d.__name__)
+def test_a_seeded_defect_of_a_move_fails_the_windows_session_where_it_is(defect):
+    """the first committed session of the windows cell fails: at the defective call, or at the first observation behind a defective
+    call that bit (a move of a form that changes what the defect leaves out) which can show it"""
+    at, shows, may, idle = MOVE_DEFECTS[defect]
+    seed = SC.CELLS["windows"]["seeds"][0]
+    session = SC.steps("windows", seed)
+    with pytest.raises(SC.Mismatch) as ei:
+        SC.run(defect(), SC.Shadow(), session, observe=None, cell="windows", seed=seed)
+    i, msg = ei.value.index, str(ei.value)
+    print(defect.__name__, "noticed at step", i, session[i])
+    assert ("session windows seed %d, step %d %s" % (seed, i, session[i][0])) in msg and "the last steps:" in msg
+    if defect is StaleSetStillMoves:
+        assert session[i][0] == "refused" and session[i][1][0] == "stale_window_set" and "expected -4, got no error" in msg
+        assert i == next(k for k, x in enumerate(session) if x[:1] + x[1][:1] == ("refused", "stale_window_set"))
+        return
+    if defect is MoveSkipsTheMessages:
+        # the very first move that moves anything while a message is not zero (every step's duals are compared: observe=None)
+        assert session[i][0] == "move_windows" and "duals: first difference" in msg
+        first = next(k for k, (op, a) in enumerate(session) if op == "move_windows" and a[2] != "zero")
+        assert i == first and any(op in _PASSES for op, _ in session[:i])
+        return
+    bit = [k for k in range(i) if session[k][0] == "move_windows" and session[k][1][2] not in idle]
+    assert bit and session[i][0] in at + shows + may, (i, session[i])
+    if defect is LabelsSurviveAMove:                     # (labels that were unset when the windows moved show nothing)
+        return
+    if defect is MoveWritesOnlyOnePlace:
+        drops = [k for k in range(bit[0], i + 1) if session[k][0] in at]
+        assert drops and not [k for k in range(drops[0] + 1, i) if session[k][0] in shows], (drops, i)
+        return
+    # nothing that shows it whenever it bit stands between the first move that bit and the step that noticed
+    assert not [k for k in range(bit[0] + 1, i) if session[k][0] in shows], (bit[0], i)
+
+
 # defect -> (ops whose call is defective, ops that may be the first to show it)
 DEFECTS = {
     BoundCachedAcrossSetVectors: (("set_vectors", "set_vectors_diff"), ("lower_bound",)),
@@ -415,11 +716,11 @@ def test_a_seeded_defect_fails_the_session_where_it_is(defect, cell):
         assert not [k for k in range(before[-1] + 1, i) if session[k][0] in shows], (before[-1], i)
 
 
-@pytest.mark.parametrize("cell", ["diffpool", "mixed4", "deep", "hop"])
+@pytest.mark.parametrize("cell", ["diffpool", "mixed4", "deep", "hop", "windows"])
 def test_replay_with_a_fresh_engine_in_the_middle(cell):
     """tests/session_replay.py --fresh-at K: a new engine takes over with the shadow's model, duals, mode, read-outs, schedules and
     labels — K right behind a step that sets labels which a later step still observes (no cost change in between unsets them)"""
-    unsets = ("upload", "upload_costs_cold", "upload_costs_warm", "set_constants", "upload_shared_pool")
+    unsets = ("upload", "upload_costs_cold", "upload_costs_warm", "set_constants", "upload_shared_pool", "move_windows")
     k = None
     for seed in (SC.HOP_SEEDS if cell == "hop" else SC.CELLS[cell]["seeds"]):
         s = SC.steps(cell, seed)
