@@ -161,6 +161,32 @@ def _c5():
     return RC.c5_small()
 
 
+def _diff_shift(L):
+    import diff_shift_cases as DS
+    return DS.label_grid(L, "colour_major")
+
+
+def _diff_shift_mixed():
+    import diff_shift_cases as DS
+    return DS.mixed_graph(np.random.default_rng(311))       # DIFF_SHIFT beside DIFF, SHARED, DENSE and POTTS peers
+
+
+def _pq_mixed_sides():
+    import peer_minima_cases as PQ
+    return PQ.case(PQ_MIXED_SIDES).model()
+
+
+def _labeling(name):
+    import labeling_cases as LC
+    return LC.case(name)
+
+
+PQ_MIXED_SIDES = "random-flip 13x11"        # publishing and consuming records on both sides of their tables
+# labeling lists whose left factor has several labelings: a case of the lane-per-factor class whose level loop takes the
+# "paired staged" and the "staged" body, and one of the wave-per-factor class with nine left labelings
+LABELING_NL = {"labeling_nl_small": "pair_trip7 chain full io11", "labeling_nl_generic": "gen9x20 chain full io01"}
+
+
 # name -> (builder, the kernel classes the forward sweep must consist of under ANISOTROPIC; None: only "something generic")
 LIVE = {
     "dense32": (lambda: _grid(32), {"dense32"}),
@@ -190,7 +216,16 @@ LIVE = {
     "primal_dense8": (lambda: _grid(8, compute_primal=True), {"dense8"}),
     "primal_potts8": (lambda: _grid(8, "potts", compute_primal=True), {"potts8"}),
     "recost13": (lambda: _grid(13, shape=(7, 6)), {"dense_v16"}),
+    "diff_shift40": (lambda: _diff_shift(40), {"diff"}),
+    "diff_shift130": (lambda: _diff_shift(130), {"diff"}),          # more than 64 labels: several registers per lane in a move
+    "diff_shift_mixed": (_diff_shift_mixed, None),
+    "pq_mixed_sides": (_pq_mixed_sides, {"dense32"}),
+    # (`full` schedules: both sweeps update factors.  Their classes, "small" and "generic" alone, are pinned in
+    # tests/test_far_offsets_host.py: these classes have no packets, which a class set named here would make the probe test ask for)
+    "labeling_nl_small": (lambda: _labeling(LABELING_NL["labeling_nl_small"]), None),
+    "labeling_nl_generic": (lambda: _labeling(LABELING_NL["labeling_nl_generic"]), None),
 }
+DIFF_SHIFT_MODELS = ("diff_shift40", "diff_shift130", "diff_shift_mixed")
 # the first three families of the issue's table: placement P32 as well
 P32_MODELS = ("dense32", "dense8", "dense4", "dense_v21", "dense_v5", "potts16", "potts_v5", "big48", "big130")
 

@@ -4,6 +4,12 @@ front of a small live model; the costs live in two borrowed device tensors of ab
 tails.  The far engine never moves its duals through the host: after ``synchronize()`` the tail of the borrowed dual tensor is
 compared with the oracle's duals of the SMALL model, bit for bit, and both padding regions must still be all +0.0.
 
+Besides the sweep families the module runs the calls large models make around them: shifted difference-indexed factors, joined
+passes in every form (which one ran is read from the engine's counter), listed constants and the pool swap, prepared read-outs,
+the decode (behind VECTOR padding: far duals, near constants — the only padding its planner accepts), moving label windows with
+their write into the borrowed const buffer, and labeling lists whose left factor has several labelings.  What these calls compute
+is compared with the numpy statements and the oracle of their own near tests, on the SMALL model.
+
 Tolerances are those of tests/test_diff_tables_gpu.py.  The kernel class is asserted before anything runs.  Whether the planner
 hands out the right offsets is tests/test_far_offsets_host.py; this module is about the kernels' index arithmetic."""
 import dataclasses
@@ -93,7 +99,9 @@ class Far:
         assert bufs.pad_d >= 2**31 and (bufs.kind == "vector" or bufs.pad_c >= 2**31)
         cp, dp = bufs.load(m, const, dual)
         assert bufs.dual_padding_nonzero() == 0
-        self.o = Oracle(oracle_of(m)); self.o.set_reparametrization(mode)
+        self.o = None                        # (oracle_of=None: the caller compares with a trajectory computed once)
+        if oracle_of is not None:
+            self.o = Oracle(oracle_of(m)); self.o.set_reparametrization(mode)
         self.e = E.Engine(0)
         try:
             self.e.upload(self.far, const_dev=cp, dual_dev=dp, keep=(bufs.const, bufs.dual), **upload_kw)
@@ -281,13 +289,18 @@ def test_generic_level_loop(p31, monkeypatch):
 # ---- chain executor ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["joined_dense32", "joined_potts8"])
 def test_joined_passes_as_one_blocked_chain_launch(p31, name, monkeypatch):
+    """the engine's default form: peer minima for the dense grid (every chain launch, by the counter), the blocked chain of the packed
+    Potts class, which has no other form, for the Potts grid.  The forms behind the switches: test_joined_passes_in_every_form"""
+    _pq_env(monkeypatch, {})
     monkeypatch.setenv("LPMP_ROT_BANDS", "8"); monkeypatch.setenv("LPMP_ROT_LAG", "2"); monkeypatch.setenv("LPMP_ROT_DEPTH", "4")
     with Far(p31, F.live(name), ANISO) as x:
         x.classes(F.LIVE[name][1])
         assert x.e.plan.pass_rotates(ANISO)
+        assert x.e.plan.peer_minima(ANISO)[0] == (name == "joined_dense32")
         for n in (1, 5, 2):
             kt = x.timed_passes(n, "joined passes")
             assert all(v["kernel"].startswith("chain_") and v["chain_launches"] == 1 for v in kt.values()), kt
+            assert x.e.peer_minima_launches() == (1 if name == "joined_dense32" else 0), (n, kt)
             x.duals(n)
             x.bound(n)
         x.factor_bounds()
@@ -331,7 +344,7 @@ def test_float_tables_from_the_borrowed_buffer(p31, name, kernel):
             assert any(v["kernel"].startswith(kernel) for v in kt.values()), kt
 
 
-# ---- rows layout ------------------------------------------------------------------------------------------------------------
+# ---- behind vector padding (far duals, near constants): the rows layout and the decode -----------------------------------------
 class TestRowsLayout:
     def test_rows_layout_behind_vector_padding(self, p31_vector):
         m = F.live("dense8")
@@ -340,6 +353,44 @@ class TestRowsLayout:
                 assert x.e.rows_layout
                 x.classes({"dense8"})
                 x.standard("rows layout")       # duals(): after synchronize() the packed tail holds the oracle's duals
+
+    @pytest.mark.parametrize("name", ["dense8", "dense_v21", "big130", "shared32", "diff_shift40"])
+    def test_decode_behind_vector_padding(self, p31_vector, name):
+        """Far duals, near constants: the decode planner refuses isolated pairwise factors ("a side that has no unary"), so vector
+        padding is the only padding a far decode can run behind (tests/test_far_offsets_host.py pins both).  Every padding unary
+        is decoded, too: 65 536 all-zero labels, walked chunk by chunk by the wave-per-unary kernel, first minimiser 0"""
+        import decode_cases as DC
+        import readout_cases as R
+        m = F.live(name)
+        us = np.asarray(R.unaries(m), np.int32)
+        small = E.Plan(m)
+        with Far(p31_vector, m, ANISO) as x:
+            e, n_pad = x.e, x.n_pad
+            x.classes(F.LIVE[name][1])
+            info = e.plan.decode_info(0)
+            assert info["n_unaries"] == len(us) + n_pad and info["n_levels"] == small.decode_info(0)["n_levels"]
+            e.compute_pass(2); x.o.ComputePass(2)
+            d = x.duals()
+            r = e.readout(us + n_pad)
+            for direction in (0, 1):
+                order = small.order(direction)
+                for refine in (0, 1):
+                    what = (name, direction, refine)
+                    e.decode_primal(direction, refine)
+                    got = e.download_primal()
+                    want = DC.decode_reference(m, d, order, refine)
+                    assert np.array_equal(got[n_pad:], want), (what, np.argwhere(got[n_pad:] != want)[:8].tolist())
+                    assert not got[:n_pad].any(), what                          # every padding unary: label 0
+                    assert e.check_primal_consistency()
+                    cost, energy = e.evaluate_primal(), DC.energy(m, want)
+                    assert abs(cost - energy) <= 1e-9 * max(1.0, abs(energy)), (what, cost, energy)
+                    assert np.array_equal(r.labels(), want[us, 0]), what
+                    e.synchronize()
+                    assert np.array_equal(p31_vector.dual_tail(), d), what      # the decode reads only
+            r.close()
+            x.padding_untouched()
+        L = int(m.f_dim0[us].max())
+        _note("decode", "decode_kernel<64, 4> (the padding unaries)", "decode_kernel<%s> (%d labels)" % ("64, 4" if L > 64 else "64, 1" if L > 32 else "%d, 1" % max(4, 1 << (L - 1).bit_length()), L))
 
 
 def send_only_updates(o, mode):
@@ -535,6 +586,455 @@ def test_halo_and_boundary_kernels(p31, name):
     _mem["kernels"].setdefault("boundary / halo", ["halo_copy_kernel<16> (16 labels) and <64> (40 labels), boundary_pack / reply / fold kernels (not timed by kernel_timing)"])
 
 
+# ---- the kernels that came after the first far-offset tests -----------------------------------------------------------------
+# Each family is a function over the buffers of a placement: the P31 tests below and the methods of TestP32 call the same one.
+UNSUPPORTED = -2
+SENTINEL = np.array([0x7FF8DEAD0000BEEF], np.uint64).view(np.float64)[0]      # a NaN with a payload (tests/test_readout_gpu.py)
+SENTINEL_I32 = np.int32(-0x5EADBEF)
+
+
+def _note(family, *kernels):
+    """kernels that kernel_timing does not name, for the closing printout"""
+    have = _mem["kernels"].setdefault(family, [])
+    have += [k for k in kernels if k not in have]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _timed(x, call, family):
+    x.e.enable_kernel_timing(True); x.e.reset_kernel_timing()
+    call()
+    kt = x.e.kernel_timing()
+    x.e.enable_kernel_timing(False)
+    _note(family, *sorted(v["kernel"] for v in kt.values()))
+    return kt
+
+
+def _restart_oracle(x, m, duals):
+    """the oracle again, on model ``m`` (same structure) with the packed ``duals``: after a call that changed constants or moved duals"""
+    x.m = m
+    x.o = Oracle(dataclasses.replace(F.oracle_model(m), dual_data=np.array(duals, np.float64, copy=True), _keep=[]))
+    x.o.set_reparametrization(x.mode)
+
+
+# ---- shifted difference-indexed factors -------------------------------------------------------------------------------------
+def _diff_shift_sweep(bufs, name, family):
+    m = F.live(name)
+    only = F.LIVE[name][1]
+    for mode in MODES:
+        with Far(bufs, m, mode) as x:
+            x.classes(only, None if only else {"generic"})
+            kt = _timed(x, lambda: (x.e.forward_pass(), x.o.ComputeForwardPass()), family)
+            if only:
+                assert set(kt) == {"diff"} and kt["diff"]["kernel"] == "sweep_diff_shift_kernel", kt
+                assert kt["diff"]["band_launches"] == 0 and kt["diff"]["shift_launches"] == kt["diff"]["launches"] > 0, kt
+            else:      # DIFF_SHIFT beside DIFF, SHARED, DENSE and POTTS peers of one record: the wave-per-factor kernel reads all of them
+                assert kt["generic"]["kernel"] == "sweep_generic_kernel<64>", kt
+            x.duals("forward")
+            kt = x.standard(family)
+            if only:
+                assert kt["diff"]["kernel"] == "sweep_diff_shift_kernel" and kt["diff"]["shift_launches"] > 0, kt
+
+
+@pytest.mark.parametrize("name", F.DIFF_SHIFT_MODELS)
+def test_diff_shift_sweep(p31, name):
+    if name == "diff_shift_mixed":
+        assert M.F_PAIRWISE_DIFF_SHIFT in set(F.live(name).f_kind.tolist())
+    _diff_shift_sweep(p31, name, "diff shift")
+
+
+# ---- joined passes in every form --------------------------------------------------------------------------------------------
+PQ_KEYS = ("LPMP_PQ_WIDE", "LPMP_PQ_LDS", "LPMP_PQ_HOLD", "LPMP_PQ_SCATTER", "LPMP_NO_PEER_MINIMA")
+# name -> (environment of the engine, whether its joined passes run in the peer-minima form)
+PQ_ENGINES = {"default": ({}, True), "wide0": ({"LPMP_PQ_WIDE": "0"}, True), "lds0": ({"LPMP_PQ_LDS": "0"}, True), "hold2": ({"LPMP_PQ_HOLD": "2"}, True),
+              "scatter0": ({"LPMP_PQ_SCATTER": "0"}, True), "no_peer_minima": ({"LPMP_NO_PEER_MINIMA": "1"}, False)}
+PQ_PASSES = (1, 2, 9, 33)                    # explicit lists, the periodic template, a slice of 32 + 1
+JOINED_WINDOW = (8, 2, 4)                    # bands : lag : depth, as tests/test_peer_minima_shapes_gpu.py runs both models
+JOINED_KERNEL = "chain_dense_pk_kernel<32, 2, false, false>"          # the class's name in the timing, whichever form ran
+_TRAJECTORY = {}
+
+
+def _pq_env(monkeypatch, env):
+    """the switches are read when an engine is created"""
+    for k in PQ_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _joined_trajectory(name):
+    """the oracle on the small model over PQ_PASSES, computed once and left unchanged: (duals, bound) after every call, the factors'
+    bounds at the end (the form of a launch changes nothing in what it computes)"""
+    if name not in _TRAJECTORY:
+        m = F.live(name)
+        o = Oracle(m); o.set_reparametrization(ANISO)
+        steps = []
+        for n in PQ_PASSES:
+            o.ComputePass(n)
+            d = o.duals().copy(); d.setflags(write=False)
+            steps.append((d, o.LowerBound()))
+        flb = np.array([o.factor_lower_bound(f) for f in range(m.n_factors)]); flb.setflags(write=False)
+        _TRAJECTORY[name] = (steps, flb)
+    return _TRAJECTORY[name]
+
+
+def _joined_passes(bufs, name, engine, monkeypatch):
+    env, pq = PQ_ENGINES[engine]
+    _pq_env(monkeypatch, env)
+    for k, v in zip(("LPMP_ROT_BANDS", "LPMP_ROT_LAG", "LPMP_ROT_DEPTH"), JOINED_WINDOW):
+        monkeypatch.setenv(k, str(v))
+    steps, flb = _joined_trajectory(name)
+    with Far(bufs, F.live(name), ANISO, oracle_of=None) as x:
+        x.classes({"dense32"})
+        assert x.e.plan.pass_rotates(ANISO) and x.e.plan.peer_minima(ANISO) == (True, "")
+        for n, (duals, bound) in zip(PQ_PASSES, steps):
+            kt = _timed(x, lambda: x.e.compute_pass(n), "joined passes, " + engine)
+            (v,) = kt.values()
+            assert v["kernel"] == JOINED_KERNEL and v["chain_launches"] == (n + 31) // 32, (engine, n, kt)
+            assert v["peer_minima_launches"] == (v["chain_launches"] if pq else 0), (engine, n, kt)
+            _note("joined passes, " + engine, "peer-minima launches: %s" % ("all" if pq else "none"))
+            x.e.synchronize()
+            d = bufs.dual_tail()
+            assert np.array_equal(d, duals), (engine, n, float(np.max(np.abs(d - duals))))
+            lb = x.e.lower_bound()
+            assert np.isfinite(lb) and abs(lb - bound) <= LB_RTOL * max(1.0, abs(bound)), (engine, n, lb, bound)
+        got = x.e.factor_lower_bounds()
+        assert np.all(got[:x.n_pad] == 0.0) and np.max(np.abs(got[x.n_pad:] - flb)) <= FLB_ATOL, engine
+        x.padding_untouched()
+
+
+@pytest.mark.parametrize("engine", list(PQ_ENGINES))
+@pytest.mark.parametrize("name", ["joined_dense32", "pq_mixed_sides"])
+def test_joined_passes_in_every_form(p31, name, engine, monkeypatch):
+    """peer minima as it is by default, with each of its four switches turned, and the joined form it replaced (what float tables, the
+    rows layout and LPMP_NO_PEER_MINIMA run): which form ran is read from the engine's counter"""
+    _joined_passes(p31, name, engine, monkeypatch)
+
+
+# ---- listed constants and the pool ------------------------------------------------------------------------------------------
+def test_set_constants_from_host_and_device_rows(p31):
+    import torch
+    import repool_cases as RP
+    m = F.live("diff_shift_mixed")
+    fs = RP.listed_subset_shift(m, 3, share=2)
+    assert {M.F_PAIRWISE_DIFF_SHIFT, M.F_PAIRWISE_DIFF, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DENSE, M.F_PAIRWISE_POTTS} == set(m.f_kind[fs].tolist())
+    rows = RP.rows_for_shift(m, fs, 21)
+    stride = rows.shape[1] + 5                                      # a device source with a stride above the longest row
+    rows_dev = RP.rows_for_shift(m, fs, 22, stride=stride)
+    with Far(p31, m, ANISO) as x:
+        e = x.e
+        for n in (1, 2):                                            # the schedules of both calls are built here
+            e.compute_pass(n); x.o.ComputePass(n)
+        d = x.duals("passes on the first constants")
+        built, handle = e.schedules_built(), e.plan.h
+        for source, r in (("host", rows), ("device", rows_dev)):
+            if source == "device":
+                t = torch.from_numpy(np.ascontiguousarray(r)).cuda(); torch.cuda.synchronize()
+                e.set_constants(fs + x.n_pad, src_dev=t.data_ptr(), src_stride=stride)
+            else:
+                e.set_constants(fs + x.n_pad, r)
+            new = RP.with_rows(x.m, fs, r)
+            assert not np.array_equal(new.const_data, x.m.const_data)
+            e.synchronize()
+            assert np.array_equal(p31.const_tail(), new.const_data), source        # the borrowed buffer holds the new rows
+            assert np.array_equal(p31.dual_tail(), d), source
+            _restart_oracle(x, new, d)
+            x.bound(source)
+            e.compute_pass(2); x.o.ComputePass(2)
+            d = x.duals(source)
+            x.bound(source)
+            x.factor_bounds(source)
+            assert e.plan.h == handle and e.schedules_built() == built, source
+        x.padding_untouched(const_tail=False)
+        assert np.array_equal(p31.const_tail(), x.m.const_data)
+    _note("set_constants", "set_constants_kernel (cells and packed scalars of SHARED / DIFF / DIFF_SHIFT factors, dense tables, Potts scalars)")
+
+
+def test_set_constants_on_float_tables(p31):
+    """f32_round: the rows are narrowed into the float tables (the check kernel runs first), the borrowed doubles stay; strict f32: a
+    row that is not float-valued is refused and nothing is written"""
+    import repool_cases as RP
+    m = F.live("recost13")
+    fs = RP.listed_subset(m, 5)
+    rows = RP.rows_for(m, fs, 31)
+    assert np.any(rows.astype(np.float32).astype(np.float64) != rows)
+    with Far(p31, m, ANISO, oracle_of=lambda s: s.with_f32_tables(), table_precision="f32_round") as x:
+        e = x.e
+        assert e.table_precision() == "f32_round"
+        x.classes(F.LIVE["recost13"][1])
+        e.compute_pass(2); x.o.ComputePass(2)
+        d = x.duals()
+        built = e.schedules_built()
+        e.set_constants(fs + x.n_pad, rows)
+        _restart_oracle(x, RP.with_rows(m, fs, rows).with_f32_tables(), d)
+        x.bound("rounded rows")
+        e.compute_pass(2); x.o.ComputePass(2)
+        x.duals("rounded rows"); x.bound("after two passes"); x.factor_bounds()
+        assert e.schedules_built() == built
+        x.m = m
+        x.padding_untouched()                                       # the doubles of the borrowed buffer are never written
+    A = m.with_f32_tables()
+    with Far(p31, A, ANISO, table_precision="f32") as x:
+        e = x.e
+        assert e.table_precision() == "f32"
+        e.compute_pass(2); x.o.ComputePass(2)
+        d = x.duals()
+        with pytest.raises(E.EngineError) as ei:
+            e.set_constants(fs + x.n_pad, rows)
+        assert ei.value.code == UNSUPPORTED and "nothing was written" in str(ei.value), str(ei.value)
+        e.compute_pass(1); x.o.ComputePass(1)
+        x.duals("after the refusal"); x.bound("after the refusal")
+        exact = RP.rows_for(m, fs, 31, float_valued=True)
+        d = x.duals()
+        e.set_constants(fs + x.n_pad, exact)
+        _restart_oracle(x, RP.with_rows(A, fs, exact), d)
+        e.compute_pass(2); x.o.ComputePass(2)
+        x.duals("float-valued rows"); x.bound("float-valued rows"); x.factor_bounds()
+        x.m = A
+        x.padding_untouched()
+    _note("set_constants", "set_constants_check_kernel and the float-table branch of set_constants_kernel")
+
+
+def test_pool_swap(p31):
+    import torch
+    import repool_cases as RP
+    m = F.live("diff40")
+    with Far(p31, m, ANISO) as x:
+        e = x.e
+        x.classes({"diff"})
+        e.compute_pass(2); x.o.ComputePass(2)
+        d = x.duals()
+        built = e.schedules_built()
+        for source, seed in (("host", 41), ("device", 42)):
+            sh = RP.pool_of(m, seed)
+            if source == "device":
+                t = torch.from_numpy(sh).cuda(); torch.cuda.synchronize()
+                e.upload_shared_pool(sh_dev=t.data_ptr())
+            else:
+                e.upload_shared_pool(sh)
+            _restart_oracle(x, m.with_pool(sh), d)
+            x.bound(source)
+            e.compute_pass(2); x.o.ComputePass(2)
+            d = x.duals(source)
+            x.bound(source); x.factor_bounds(source)
+            assert e.schedules_built() == built
+        x.padding_untouched()
+    _note("set_constants", "upload_shared_pool (the pool and its cells lie in an allocation of the engine, addressed relative to the far const base)")
+
+
+# ---- prepared read-outs -----------------------------------------------------------------------------------------------------
+# name -> (upload keywords, the model of the statement)
+READOUT_MODELS = {name: ({}, lambda m: m) for name in ("dense8", "dense_v21", "big48", "potts16", "shared32", "diff40", "diff_shift40")}
+READOUT_MODELS["dense32"] = ({"table_precision": "f32_round"}, lambda m: m.with_f32_tables())       # tab32: the tables read as floats
+
+
+def _device_rows(x, call, n, stride):
+    """``call(dst_dev, stride)`` into a torch tensor of n + 1 rows filled with the sentinel; the array afterwards"""
+    import torch
+    t = torch.from_numpy(np.full((n + 1) * stride, SENTINEL)).cuda()
+    torch.cuda.synchronize()
+    assert call(t.data_ptr(), stride) is None
+    x.e.synchronize()
+    return t.cpu().numpy().reshape(n + 1, stride)
+
+
+def _check_rows(got_dev, want, what):
+    """written entries equal; the padding of every row and the row behind the last are still the sentinel, bit for bit"""
+    n = want.shape[0]
+    written = ~np.isnan(want)
+    assert np.array_equal(got_dev[:n][written], want[written]), what
+    assert np.all(_bits(got_dev[:n][~written]) == _bits(SENTINEL)), what
+    assert np.all(_bits(got_dev[n]) == _bits(SENTINEL)), what
+
+
+def _check_labels(x, r, want, what):
+    import torch
+    assert np.array_equal(r.labels(), want), what
+    t = torch.from_numpy(np.full(r.n + 1, SENTINEL_I32, np.int32)).cuda()
+    torch.cuda.synchronize()
+    assert r.labels(t.data_ptr()) is None
+    x.e.synchronize()
+    got = t.cpu().numpy()
+    assert np.array_equal(got[:r.n], want) and got[r.n] == SENTINEL_I32, what
+
+
+def _readouts(bufs, name, family):
+    import readout_cases as R
+    kw, ref_of = READOUT_MODELS[name]
+    m = F.live(name)
+    ref = ref_of(m)
+    us = np.asarray(R.unaries(m), np.int32)
+    L = int(m.f_dim0[us].max())
+    with Far(bufs, m, ANISO, oracle_of=lambda s: F.oracle_model(ref_of(s)), **kw) as x:
+        e = x.e
+        x.classes(F.LIVE[name][1])
+        e.compute_pass(1); x.o.ComputePass(1)
+        d = x.duals()
+        stride = L + 3
+        want = {"vectors": (R.vectors_np(m, d, us), R.vectors_np(m, d, us, stride=stride)),
+                "beliefs": (R.beliefs_np(ref, d, us), R.beliefs_np(ref, d, us, stride=stride))}
+        assert not np.array_equal(want["vectors"][0], want["beliefs"][0], equal_nan=True)
+        primal = e.download_primal()
+        assert np.array_equal(primal[us + x.n_pad, 0], m.f_dim0[us])                   # no label set: the label count
+        for factors in (us + x.n_pad, None):        # None: every VECTOR factor — dense padding has none, so exactly the live unaries
+            r = e.readout(factors)
+            assert r.n == len(us) and r.max_labels == L
+            for what, (host, dev) in want.items():
+                call = getattr(r, what)
+                assert np.array_equal(call(), host, equal_nan=True), (name, what)
+                _check_rows(_device_rows(x, lambda p, s: call(p, s), r.n, stride), dev, (name, what))
+            _check_labels(x, r, primal[us + x.n_pad, 0], name)
+            r.close()
+        e.synchronize()
+        assert np.array_equal(bufs.dual_tail(), d)                  # a read-out reads only
+        x.padding_untouched()
+    _note(family, "readout_vectors_kernel<%d>" % (8 if L <= 8 else 16 if L <= 16 else 32 if L <= 32 else 64),
+          "readout_beliefs_kernel<%d, 1>" % (4 if L <= 4 else 8 if L <= 8 else 16 if L <= 16 else 32 if L <= 32 else 64), "readout_labels_kernel")
+
+
+@pytest.mark.parametrize("name", list(READOUT_MODELS))
+def test_readouts(p31, name):
+    _readouts(p31, name, "read-outs")
+
+
+def test_readout_of_rounded_labels(p31):
+    import readout_cases as R
+    m = F.live("primal_dense8")
+    us = np.asarray(R.unaries(m), np.int32)
+    with Far(p31, m, ANISO) as x:
+        r = x.e.readout(us + x.n_pad)
+        x.e.compute_pass_and_primal(0); x.o.ComputePassAndPrimal(0)
+        want = x.o.primal()[us, 0]
+        assert np.all(want < m.f_dim0[us]) and np.array_equal(x.e.download_primal()[us + x.n_pad, 0], want)
+        _check_labels(x, r, want, "after compute_pass_and_primal")
+        r.close()
+        x.duals()
+        x.padding_untouched()
+
+
+# ---- moving label windows ---------------------------------------------------------------------------------------------------
+def _moved_shifts(m, us, delta):
+    """the const array of ``m`` with every shift := shift + delta_left - delta_right (the unaries of a DIFF_SHIFT factor's two sides)"""
+    row = {int(u): i for i, u in enumerate(us)}
+    side = {(int(m.m_right[k]), int(m.mtypes[int(m.m_type[k])].param)): int(m.m_left[k]) for k in range(m.n_messages)}
+    coff = m.const_offsets()
+    const = np.array(m.const_data, np.float64, copy=True)
+    for p in np.flatnonzero(m.f_kind == M.F_PAIRWISE_DIFF_SHIFT):
+        dl, dr = (int(delta[row[side[(int(p), s)]]]) if side.get((int(p), s)) in row else 0 for s in (0, 1))
+        const[coff[p] + 1] = float(min(max(M.diff_shift_int(const[coff[p] + 1]) + dl - dr, -(1 << 30)), 1 << 30))
+    return const
+
+
+def _moves(bufs, name, family):
+    """four moves on one engine, two passes against the oracle on the moved model after each: deltas from the host, the way back from
+    device memory, then with the unary costs of the old and the new window from the host and from device memory"""
+    import torch
+    import move_windows_cases as MW
+    m = F.live(name)
+    us = MW.unaries(m)
+    L = int(m.f_dim0[us].max())
+    delta = MW.deltas(m.f_dim0[us], L)
+    assert {0, 1, -1, 63, -64, L - 1, -L, L + 7} <= set(delta.tolist())
+    assert MW.has_hazard(m.f_dim0[us], delta) or L < 130
+    stride = L + 6
+    with Far(bufs, m, ANISO) as x:
+        e = x.e
+        x.classes({"diff"})
+        ws = e.window_set(us + x.n_pad)
+        assert ws.n == len(us) and ws.max_labels == L and ws.n_pairwise == int((m.f_kind == M.F_PAIRWISE_DIFF_SHIFT).sum())
+        for n in (1, 2):
+            e.compute_pass(n); x.o.ComputePass(n)
+        d = x.duals("before the first move")
+        built = e.schedules_built()
+        for k, (dl, costs, dev) in enumerate(((delta, False, False), (-delta, False, True), (delta[::-1].copy(), True, False), (-delta[::-1], True, True))):
+            co, cn = MW.cost_pair(x.m, us, dl, 12 + k, stride=stride) if costs else (None, None)
+            keep = []
+            if dev:
+                keep = [torch.from_numpy(np.concatenate([dl, [1 << 30]]).astype(np.int32)).cuda()]
+                if costs:
+                    keep += [torch.from_numpy(co).cuda(), torch.from_numpy(cn).cuda()]
+                torch.cuda.synchronize()
+                ws.move(delta_dev=keep[0].data_ptr(), cost_dev=(keep[1].data_ptr(), keep[2].data_ptr()) if costs else None, stride=stride if costs else None)
+                e.synchronize()
+                assert np.array_equal(keep[0].cpu().numpy()[:-1], dl)
+            else:
+                ws.move(dl, cost_old=co, cost_new=cn)
+            m2, d2 = M.move_windows(x.m, d, us, dl, co, cn)
+            e.synchronize()
+            got = bufs.dual_tail()
+            assert not np.any(np.isnan(got)) and np.array_equal(got, d2), (name, k, int(np.sum(got != d2)))
+            assert np.array_equal(m2.const_data, _moved_shifts(x.m, us, dl)) and not np.array_equal(m2.const_data, x.m.const_data), (name, k)
+            assert np.array_equal(bufs.const_tail(), m2.const_data), (name, k)           # the shifts: a write into the borrowed const buffer
+            assert bufs.const_padding_nonzero() == 0 and bufs.dual_padding_nonzero() == 0, (name, k)
+            _restart_oracle(x, m2, d2)
+            x.bound((name, k))
+            e.compute_pass(2); x.o.ComputePass(2)
+            d = x.duals((name, k))
+            x.bound((name, k))
+            assert e.schedules_built() == built                     # a move plans and builds nothing
+        x.factor_bounds()
+        ws.close()
+        x.padding_untouched(const_tail=False)
+        assert np.array_equal(bufs.const_tail(), x.m.const_data)
+    _note(family, "move_windows_kernel (%d labels: %d of its 8 predicated blocks)" % (L, (L + 63) // 64), "move_shifts_kernel")
+
+
+@pytest.mark.parametrize("name", ["diff_shift40", "diff_shift130"])
+def test_moving_windows(p31, name):
+    _moves(p31, name, "moving windows")
+
+
+def test_a_window_set_next_to_a_dense_factor_is_refused(p31):
+    m = F.live("diff_shift_mixed")
+    dense = set(np.flatnonzero(m.f_kind == M.F_PAIRWISE_DENSE).tolist())
+    u = next(int(m.m_left[k]) for k in range(m.n_messages) if int(m.m_right[k]) in dense)
+    assert m.f_kind[u] == M.F_VECTOR
+    with pytest.raises(M.WindowsUnsupported):
+        M.window_links(m, [u])
+    with Far(p31, m, ANISO) as x:
+        x.e.compute_pass(2); x.o.ComputePass(2)
+        d = x.duals()
+        with pytest.raises(E.EngineError) as ei:
+            x.e.window_set(np.array([u + x.n_pad], np.int32))
+        assert ei.value.code == UNSUPPORTED and "factor %d " % (u + x.n_pad) in str(ei.value), str(ei.value)
+        x.e.synchronize()
+        assert p31.dual_tail().tobytes() == d.tobytes()
+        x.padding_untouched()                                       # constants and both paddings bitwise as before
+
+
+# ---- labeling lists whose left factor has several labelings ------------------------------------------------------------------
+@pytest.mark.parametrize("engine", ["level loop", "chain tickets"])
+@pytest.mark.parametrize("name", list(F.LABELING_NL))
+def test_labeling_lists_with_several_left_labelings(p31, name, engine, monkeypatch):
+    import labeling_cases as LC
+    c = LC.CASES[F.LABELING_NL[name]]
+    assert c.fam.nl > 1
+    monkeypatch.delenv("LPMP_NO_CHAIN", raising=False)
+    for k in ("LPMP_NO_LEVEL_LOOP", "LPMP_CHAIN_ALL", "LPMP_CHAIN_MIN"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in dict(LC.ENGINES)[engine].items():
+        monkeypatch.setenv(k, v)
+    m = F.live(name)
+    for mode in MODES:
+        with Far(p31, m, mode) as x:
+            LC.assert_path(x.e.plan, c, engine)                     # on the FAR plan, before anything runs
+            if engine == "level loop" and c.fam.cls == "small":
+                reached = {b for d in (M.FORWARD, M.BACKWARD, -1) for md in MODES for b, n in LC.bodies(x.e.plan, d, md).items() if n > 0}
+                assert {"paired staged", "staged"} <= reached, reached
+                _note("labeling lists, nl > 1", "level loop of class small, bodies %s (nl = %d)" % (sorted(reached), c.fam.nl))
+            else:
+                _note("labeling lists, nl > 1", "%s of class %s (nl = %d)" % (engine, c.fam.cls, c.fam.nl))
+            x.bound("upload")
+            for what, n in LC.CALLS:
+                LC.call(x.e, what, n); LC.call(x.o, what, n)
+                x.duals((what, n))
+                x.bound((what, n))
+            x.factor_bounds()
+            x.padding_untouched()
+
+
 # ---- placement P32: an unsigned 32-bit truncation shows here, not at P31 ----------------------------------------------------
 class TestP32:
     @pytest.mark.parametrize("name", F.P32_MODELS)
@@ -542,3 +1042,19 @@ class TestP32:
         assert p32.pad_c >= 2**32 and p32.pad_d >= 2**32
         kernel = {**PACKED_DENSE, **PACKED_POTTS, **STREAMING}[name]
         _run(p32, name, "P32 " + name, kernel=kernel)
+
+    def test_diff_shift_sweep(self, p32):
+        assert p32.pad_c >= 2**32 and p32.pad_d >= 2**32
+        _diff_shift_sweep(p32, "diff_shift40", "P32 diff shift")
+
+    @pytest.mark.parametrize("engine", ["default", "no_peer_minima"])
+    def test_joined_passes_with_and_without_peer_minima(self, p32, engine, monkeypatch):
+        _joined_passes(p32, "joined_dense32", engine, monkeypatch)
+
+    @pytest.mark.parametrize("name", list(READOUT_MODELS))
+    def test_readouts(self, p32, name):
+        _readouts(p32, name, "P32 read-outs")
+
+    @pytest.mark.parametrize("name", ["diff_shift40", "diff_shift130"])
+    def test_moving_windows(self, p32, name):
+        _moves(p32, name, "P32 moving windows")

@@ -2,7 +2,8 @@
 a small model, tests/far_offset_cases.py — is the schedule of ``m`` field for field, with every dual / const offset moved by
 exactly the padding, as Python ints past 2^31 (P31) and 2^32 (P32).  Read through tests/cpp/schedule_probe.cpp: records, ops and
 the packet copies of both.  If a GPU test of tests/test_far_offsets_gpu.py fails, this module tells whether the planner or the
-kernel is wrong."""
+kernel is wrong.  The plans of the calls around the sweeps are pinned here as well: which form the joined passes take, the bodies of
+the level loop, and the decode plan, which exists behind VECTOR padding only."""
 import os
 import sys
 
@@ -159,3 +160,82 @@ def test_far_schedule_is_the_small_schedule_moved_by_the_padding(probe_lib, name
             assert B["chain_level_loop"].tolist() == [1], sname
     if F.LIVE[name][1] and not F.LIVE[name][1] & {"dense_big", "diff"}:
         assert packets > 0, "a packed class without packets: the probe did not reach them"
+
+
+# ---- the models added for the kernels that came after the first far-offset tests ---------------------------------------------
+NEW_MODELS = F.DIFF_SHIFT_MODELS + ("pq_mixed_sides",) + tuple(F.LABELING_NL)
+DECODE_MODELS = ("dense8", "dense_v21", "big130", "shared32", "diff_shift40")
+ERR_UNSUPPORTED = -2
+
+
+def test_new_models_are_what_the_gpu_tests_take_them_for():
+    """kinds, label counts and sizes (at most 270 k constants and 66 k duals: TAIL stays), the peer-minima form, and the bodies of
+    the level loop the two labeling models reach — on the SMALL plans; the far plans equal them in the test below"""
+    import labeling_cases as LC
+    ANISO = M.REPAM_ANISOTROPIC
+    for name in NEW_MODELS:
+        m = F.live(name)
+        assert int(m.const_sizes().sum()) <= 270_000 and m.dual_data.shape[0] <= 66_000, name
+    for name, L in (("diff_shift40", 40), ("diff_shift130", 130)):
+        m = F.live(name)
+        assert set(m.f_kind.tolist()) == {M.F_VECTOR, M.F_PAIRWISE_DIFF_SHIFT} and set(m.f_dim0[m.f_kind == M.F_VECTOR].tolist()) == {L}
+    mixed = F.live("diff_shift_mixed")
+    assert {M.F_PAIRWISE_DIFF_SHIFT, M.F_PAIRWISE_DIFF, M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DENSE, M.F_PAIRWISE_POTTS} <= set(mixed.f_kind.tolist())
+    p = E.Plan(F.live("pq_mixed_sides"))
+    assert p.pass_rotates(ANISO) and p.peer_minima(ANISO) == (True, "")
+    assert E.Plan(F.live("joined_dense32")).peer_minima(ANISO) == (True, "")
+    for name, cls in (("labeling_nl_small", "small"), ("labeling_nl_generic", "generic")):
+        c = LC.CASES[F.LABELING_NL[name]]
+        assert c.fam.cls == cls and c.fam.nl > 1 and c.chain_min == 0, name
+        p = E.Plan(F.live(name))
+        for mode in MODES:
+            for d in (0, 1):
+                assert set(p.schedule_classes(d, mode)) == {cls}, (name, mode, d)
+    assert LC.CASES[F.LABELING_NL["labeling_nl_generic"]].fam.nl >= 9
+    p = E.Plan(F.live("labeling_nl_small"))
+    reached = {b for d in (0, 1, -1) for mode in MODES for b, n in LC.bodies(p, d, mode).items() if n > 0}
+    assert {"paired staged", "staged"} <= reached, reached
+
+
+@pytest.mark.parametrize("placement", PLACEMENTS)
+@pytest.mark.parametrize("name", NEW_MODELS)
+def test_new_models_plan_alike_behind_the_padding(name, placement):
+    """class sets, whether passes join, the peer-minima form, the shifted launches of class diff and the bodies of the level loop:
+    the far plan's equal the small plan's"""
+    import labeling_cases as LC
+    m = F.live(name)
+    a, b = E.Plan(m), E.Plan(F.pad_front(m, F.N_PAD[placement], "dense"))
+    for mode in MODES:
+        for d in (0, 1):
+            assert a.schedule_classes(d, mode) == b.schedule_classes(d, mode), (mode, d)
+            assert a.diff_band_info(d, mode) == b.diff_band_info(d, mode), (mode, d)
+        assert a.pass_rotates(mode) == b.pass_rotates(mode), mode
+        assert a.peer_minima(mode) == b.peer_minima(mode), mode
+        assert a.pass_schedule_info(mode) == b.pass_schedule_info(mode), mode
+        for d in (0, 1, -1):
+            assert a.chain_info(d, mode) == b.chain_info(d, mode), (mode, d)
+            assert a.level_loop_info(d, mode) == b.level_loop_info(d, mode), (mode, d)
+            if name in F.LABELING_NL:
+                assert LC.bodies(a, d, mode) == LC.bodies(b, d, mode), (mode, d)
+
+
+@pytest.mark.parametrize("placement", PLACEMENTS)
+@pytest.mark.parametrize("name", DECODE_MODELS)
+def test_decode_plan_behind_vector_padding(name, placement):
+    """the decode planner takes isolated VECTOR factors (each a unary of level 1 without links) and refuses isolated pairwise ones, so
+    the far decode runs behind vector padding: far duals, near constants.  Its plan is the small plan's with the padding unaries
+    added: as many levels and links, and the live unaries in the same order at the same levels"""
+    m = F.live(name)
+    n_pad = F.N_PAD[placement]
+    a, b = E.Plan(m), E.Plan(F.pad_front(m, n_pad, "vector"))
+    for d in (0, 1):
+        ia, ib = a.decode_info(d), b.decode_info(d)
+        assert ib == dict(n_unaries=ia["n_unaries"] + n_pad, n_levels=ia["n_levels"], n_links=ia["n_links"]), (d, ia, ib)
+        assert ia["n_unaries"] == int((m.f_kind == M.F_VECTOR).sum()) and ia["n_levels"] > 1
+        (fa, la), (fb, lb) = a.decode_levels(d), b.decode_levels(d)
+        live = fb >= n_pad
+        assert np.array_equal(fb[live], fa + n_pad) and np.array_equal(lb[live], la), d
+        assert sorted(fb[~live].tolist()) == list(range(n_pad)) and np.all(lb[~live] == 1), d
+    with pytest.raises(E.EngineError) as ei:
+        E.Plan(F.pad_front(m, n_pad, "dense")).decode_info(0)
+    assert ei.value.code == ERR_UNSUPPORTED and "factor 0 " in str(ei.value) and "no unary" in str(ei.value), str(ei.value)
