@@ -820,7 +820,11 @@ void classify(const Plan& p, Updates& U, const OpVec& ops) {
     if (p.f_kind[uf[u]] != LPMP_F_VECTOR) {                // updated pairwise factors
       if (small_ok[u]) return KC_SMALL;
       const int w = std::max(p.f_dim0[uf[u]], p.f_dim1[uf[u]]);
-      if (U.pw_right[u] && w <= 32 && n_recv_of[u] + n_send_of[u] <= PW_MAX_OPS)
+      // (pw_right is cleared op by op: a record WITHOUT any op — a COMPUTE_PRIMAL pairwise type whose messages are all inactive in
+      // this sweep — keeps it whatever its kind, and the packed kernel would read d0 x d1 table entries where a SHARED / DIFF /
+      // DIFF_SHIFT factor holds two or four words.  The kind is asked here as well.)
+      const int fk = p.f_kind[uf[u]];
+      if (U.pw_right[u] && (fk == LPMP_F_PAIRWISE_DENSE || fk == LPMP_F_PAIRWISE_POTTS) && w <= 32 && n_recv_of[u] + n_send_of[u] <= PW_MAX_OPS)
         return KC_PW_4 + (w <= 4 ? 0 : w <= 8 ? 1 : w <= 16 ? 2 : 3);
       return KC_GENERIC;
     }

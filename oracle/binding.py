@@ -56,6 +56,7 @@ def lib():
         L.orc_evaluate_primal.argtypes = [C.c_void_p]
         L.orc_get_primal.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_get_primal_access.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_set_primal.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.orc_get_duals.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_set_duals.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_get_order.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -150,6 +151,13 @@ class Oracle:
         out = np.empty(self.L.orc_n_factors(self.h), np.uint64)
         self.L.orc_get_primal_access(self.h, out.ctypes.data)
         return out
+
+    def set_primal(self, primal: np.ndarray, access: int):
+        """the twin of Engine.upload_primal: the [n_factors, 2] primal_ members as given, every primal_access_ = ``access`` (the
+        time stamp 2 * iteration + 1 / + 2 of the pass the labels are to count as rounded in)"""
+        p = np.ascontiguousarray(primal, np.int32)
+        assert p.shape == (self.L.orc_n_factors(self.h), 2)
+        self.L.orc_set_primal(self.h, p.ctypes.data, C.c_uint64(int(access)))
 
     def factor_lower_bound(self, f: int) -> float:
         return float(self.L.orc_factor_lower_bound(self.h, int(f)))

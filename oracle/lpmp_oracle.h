@@ -44,6 +44,7 @@ int orc_check_primal_consistency(orc_t* o);                      /* LP::CheckPri
 double orc_evaluate_primal(orc_t* o);                            /* LP::EvaluatePrimal, LP_MP.h:1521-1536 */
 void orc_get_primal(orc_t* o, int32_t* out /*[2*n_factors]*/);   /* the factors' primal_ members (unset = dim) */
 void orc_get_primal_access(orc_t* o, uint64_t* out /*[n_factors]*/);
+void orc_set_primal(orc_t* o, const int32_t* in /*[2*n_factors]*/, uint64_t access);   /* preset labels, as lpmp_upload_primal */
 
 int64_t orc_n_factors(orc_t* o);
 int64_t orc_dual_size(orc_t* o);

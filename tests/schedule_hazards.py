@@ -118,7 +118,7 @@ class ModelInfo:
 
     def __init__(self, model):
         self.model = model
-        self.oracle_model = model.expand_shared() if model.has_shared else model
+        self.oracle_model = model.expand_diff().expand_shared() if (model.has_shared or model.has_diff) else model
         o = Oracle(self.oracle_model)
         off, ent = o.msg_lists()
         self.fm_off = off.tolist()
