@@ -258,7 +258,8 @@ struct RotChain {
   int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
 };
 // the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
-struct RotOrder { bool have_geo = false; RotGeometry geo; TileSet tiles; };
+// (tile_sets: one per tile size asked for — short and long calls of one model may take different sizes, and both stay)
+struct RotOrder { bool have_geo = false; RotGeometry geo; std::map<int, TileSet> tile_sets; bool have_pq_geo = false; PqGeometry pq_geo; };
 // conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
 // their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
 struct DevDecode {
@@ -429,6 +430,10 @@ struct lpmp_engine {
   bool pq_scatter = true;         // LPMP_PQ_SCATTER: the three-table form publishes a table's row minima with a reduce-scatter (0: eight row all-reduces)
   int pq_hold = 3;                // LPMP_PQ_HOLD: tables such a record holds in registers, 3 or 2 (pq_lds 0: always 2, none parked)
   bool pq_wide = true;            // LPMP_PQ_WIDE=0: the consuming records one per wave, four per ticket, on the plan's own block relations
+  // the ticket order of the peer-minima launches (rotation_chain): LPMP_PQ_TILES=0 the order every other launch takes (band order, or
+  // tiles by the old rule), =T tiles of T blocks; LPMP_PQ_SUB / _SUBLAG / _SUBGAP: sub-bands per tile, their lag, the gap behind a predecessor (unset: the engine's own)
+  int pq_tiles = -1, pq_sub = 0, pq_sublag = 0, pq_subgap = -1;
+  int pq_min_passes = 12;         // LPMP_PQ_MIN_PASSES: calls of fewer passes keep the old order (rotation_chain)
   bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
   RotSettings rot_opts;      // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
   // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
@@ -949,17 +954,49 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   // Depth of the tiled order (TileSet::depth): the flat tiles of a 2-D grid lose about 4 % per step: depth 8; the balls of a 3-D grid
   // 16 %: depth 4 — measured there: depth 2 / 4 / 6 / 8 = 7.9 / 7.27 / 7.28 / 7.6 ms per pass at 96^3 x 32 labels, 5.92 / 5.72 / - /
   // 7.24 at 128^3 x 16).
+  // Peer-minima launches (EXPERIMENTS.md T): K / T read no table, so the only second reader of a table is the W step of the next
+  // pass, and the band order can serve at most every second of those reads on-die, at a distance the reach of a grid row keeps at
+  // the edge of the cache.  They take a geometry of their own for calls of at least 12 passes where a W step's tables exceed the
+  // Infinity Cache: large tiles (few delayed blocks), groups of 8 steps, and the skew of the band order over the sub-bands of the
+  // tiles (order.cpp skewed_tile_order), whose lag has to cover a row of a tile only.  LPMP_PQ_TILES=0 returns them to the rule of
+  // every other launch; LPMP_PQ_TILES=T / LPMP_PQ_SUB / LPMP_PQ_SUBLAG / LPMP_PQ_SUBGAP force tile blocks, sub-bands per tile, their
+  // lag and the gap behind a predecessor.  Tiles forced with LPMP_ROT_TILES take the sub-bands their size gives (none when small).
   JoinedOrder ord{geo.bands, geo.lag, geo.depth, nullptr};
+  PqGeometry pqg;
+  TileSet* tiles = nullptr;
   {
     const bool worthwhile = ri.valid && kc_is_dense(ri.kclass) && !kc_is_var(ri.kclass) &&
                             (rot_bands > 0 || (e->model.model_big && ri.t[1].bytes >= ((int64_t)64 << 20)));
-    const int want = !worthwhile || ri.t[0].nb != ri.t[2].nb || ri.t[3].nb != ri.t[2].nb ? 0
+    const bool tileable = worthwhile && ri.t[0].nb == ri.t[2].nb && ri.t[3].nb == ri.t[2].nb;
+    // (with LPMP_PQ_TILES=T the rule also runs under a forced band count: that is how a model of test size reaches it)
+    // Calls of fewer than PQ_MIN_PASSES passes keep the old order: a 5-pass call was 3 % slower in the new one (20.41 against 19.74 ms
+    // in the kernel trace; its T tickets wait 22 instead of 12 us) — 11 steps are one group of 8 and a rest; from 12 passes on every
+    // call is a periodic template.  6 to 11 passes were not measured.  LPMP_PQ_MIN_PASSES moves the threshold (tests, probes).
+    bool pq_own = tileable && !pq_why && e->pq_tiles != 0 && !e->rot_tiles_set && (rot_bands <= 0 || e->pq_tiles > 0) && n_call >= e->pq_min_passes;
+    if (pq_own) {
+      if (!ro.have_pq_geo) { ro.pq_geo = peer_minima_geometry(ri, e->pq_tiles > 0 ? e->pq_tiles : 0); ro.have_pq_geo = true; }
+      pq_own = ro.pq_geo.use || e->pq_tiles > 0;
+    }
+    // (the buffer of the minima first: without it the launch is not a peer-minima launch and keeps its old order)
+    if (pq_own && !e->model.d_peerq.get() && !e->model.d_peerq.try_alloc((size_t)e->model.plan->p.nf * 32)) pq_own = false;
+    const int want = !tileable ? 0
+                   : pq_own ? ro.pq_geo.tile_blocks
                    : e->rot_tiles_set ? e->rot_tiles
                    : (rot_bands <= 0 && (geo.depth != 4 || !geo.fits) && n_call >= 4 ? 1024 : 0);
     if (want > 0) {
-      if (ro.tiles.T != want) ro.tiles = make_tiles(ri, want);
-      ord.tiles = &ro.tiles;
-      if (!e->rot_opts.depth_set) ord.depth = ro.tiles.depth;
+      TileSet& ts = ro.tile_sets[want];
+      if (ts.T != want) ts = make_tiles(ri, want);
+      ord.tiles = tiles = &ts;
+      if (!e->rot_opts.depth_set) ord.depth = ts.depth;
+      // the skew over the tiles: the rule's own tiles, and tiles forced with LPMP_ROT_TILES on a peer-minima launch where they are large
+      // enough for two sub-bands (tiles the old rule chose stay plain)
+      if (!pq_why && e->pq_tiles != 0 && (pq_own || e->rot_tiles_set)) {
+        pqg = pq_own ? ro.pq_geo : peer_minima_geometry(ri, want);
+        if (e->pq_sub > 0) pqg.sub = e->pq_sub;
+        if (e->pq_sublag > 0) pqg.sub_lag = e->pq_sublag;
+        if (e->pq_subgap >= 0) pqg.sub_gap = e->pq_subgap;
+        ord.sub = pqg.sub; ord.sub_lag = pqg.sub_lag; ord.sub_gap = pqg.sub_gap;
+      }
     }
   }
   const int depth = ord.depth;
@@ -968,7 +1005,8 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const int n_template = (3 * depth + tail - 1) / 2;
   const bool periodic = depth % 2 == 0 && n_call > ROT_EXPLICIT_MAX && n_call >= n_template && !std::getenv("LPMP_ROT_EXPLICIT");
   const int n = periodic ? n_template : n_call;
-  const int key = periodic ? -tail : n_call;
+  // (a periodic template serves every call of its tail, depth and order: short and long calls of one model may differ in the last two)
+  const int key = periodic ? -(tail + 32 * depth + (ord.tiles ? 1024 : 0) + (ord.sub > 1 ? 2048 : 0)) : n_call;
   auto it = e->model.rot_chain[mode].find(key);
   if (it != e->model.rot_chain[mode].end()) { it->second.last_use = ++e->rot_clock; return it->second.n_steps > 0 ? &it->second : nullptr; }
   RotChain& rc = e->model.rot_chain[mode][key];           // n_steps == 0: tried, not possible
@@ -993,8 +1031,15 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   // reuse (1024:3:5 5.67, 1024:3:6 6.37), lag 2 leaves the waiting workgroups less slack (1024:2:4 5.24)
   // (round 6: lag and depth follow the reach of the dependencies — order.cpp rot_geometry; C3 keeps 3 and 4)
   if (!geo.fits && !ord.tiles) return no("a step's dependencies reach further than the Infinity Cache window can cover");
-  if (ord.tiles && verbose) std::fprintf(stderr, "lpmp:   %d tiles of about %d blocks per step, radius %.1f hops, delayed after 1 / 3 / 5 / 7 steps: %.2f / %.2f / %.2f / %.2f\n", ro.tiles.n, ro.tiles.T,
-                                         ro.tiles.radius, ro.tiles.delayed[1], ro.tiles.delayed[3], ro.tiles.delayed[5], ro.tiles.delayed[7]);
+  if (ord.tiles && verbose) std::fprintf(stderr, "lpmp:   %d tiles of about %d blocks per step, radius %.1f hops, delayed after 1 / 3 / 5 / 7 steps: %.2f / %.2f / %.2f / %.2f\n", tiles->n, tiles->T,
+                                         tiles->radius, tiles->delayed[1], tiles->delayed[3], tiles->delayed[5], tiles->delayed[7]);
+  if (ord.tiles && ord.sub > 1 && verbose) {
+    extend_tile_delays(ri, *tiles);          // (steps 8 to 15: only this line shows them)
+    std::fprintf(stderr, "lpmp:   peer-minima geometry: tiles of %.0f MiB of a W step (%.0f W blocks; steps move %.2f / %.2f / %.2f / %.2f GB), depth %d, %d sub-bands per tile at lag %d, gap %d, "
+                 "delayed after 7 / 11 / 15 steps: %.2f / %.2f / %.2f; predicted HBM share of the table reads %.2f\n", pqg.tile_bytes / 1048576.0, pqg.w_blocks_per_tile,
+                 pqg.step_bytes[0] / 1e9, pqg.step_bytes[1] / 1e9, pqg.step_bytes[2] / 1e9, pqg.step_bytes[3] / 1e9, ord.depth, ord.sub, ord.sub_lag, ord.sub_gap,
+                 tiles->delayed[7], tiles->delayed[11], tiles->delayed[15], peer_minima_hbm_share(*tiles, ord.depth));
+  }
   if (!pq_why && !e->model.d_peerq.get() && !e->model.d_peerq.try_alloc((size_t)e->model.plan->p.nf * 32)) {
     if (wide) {   // the old form then, planned from its own relations: this entry goes, the wide relations with it
       e->model.rot_chain[mode].erase(key);
@@ -1002,6 +1047,7 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
       return rotation_chain(e, mode, n_call);
     }
     pq_why = "no device memory for the published minima";
+    ord.sub = 1;
   }
   JoinedTables jt;
   const std::string why = joined_pass_tables(ri, ord, n, periodic, jt, verbose ? stderr : nullptr);
@@ -1062,7 +1108,8 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   }
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
-                 periodic ? (ord.tiles ? " (periodic template, tiled order)" : " (periodic template)") : ord.tiles ? " (tiled order)" : "", (long long)N, ord.bands, jt.lag, depth,
+                 periodic ? (ord.tiles ? (jt.sub > 1 ? " (periodic template, skewed tiled order)" : " (periodic template, tiled order)") : " (periodic template)")
+                          : ord.tiles ? (jt.sub > 1 ? " (skewed tiled order)" : " (tiled order)") : "", (long long)N, ord.bands, jt.lag, depth,
                  geo.reach_bytes / 1e6, (double)ri.t[1].bytes / ord.bands / 1e6, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
   return &rc;
 }
@@ -1523,6 +1570,11 @@ int lpmp_create(int device, lpmp_engine** out) {
     if (const char* v = std::getenv("LPMP_PQ_HOLD")) e->pq_hold = v[0] == '2' ? 2 : 3;
     if (const char* v = std::getenv("LPMP_PQ_SCATTER")) e->pq_scatter = v[0] != '0';
     if (const char* v = std::getenv("LPMP_PQ_WIDE")) e->pq_wide = v[0] != '0';
+    if (const char* v = std::getenv("LPMP_PQ_TILES")) e->pq_tiles = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("LPMP_PQ_SUB")) e->pq_sub = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("LPMP_PQ_SUBLAG")) e->pq_sublag = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("LPMP_PQ_SUBGAP")) e->pq_subgap = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("LPMP_PQ_MIN_PASSES")) e->pq_min_passes = std::max(1, std::atoi(v));
     if (const char* v = std::getenv("LPMP_ROT_BANDS")) e->rot_opts.bands = std::atoi(v);
     if (const char* v = std::getenv("LPMP_ROT_LAG")) { e->rot_opts.lag = std::max(1, std::atoi(v)); e->rot_opts.lag_set = true; }
     if (const char* v = std::getenv("LPMP_ROT_DEPTH")) { e->rot_opts.depth = std::max(1, std::atoi(v)); e->rot_opts.depth_set = true; }

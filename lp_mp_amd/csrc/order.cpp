@@ -228,10 +228,10 @@ int32_t grow_tiles(const RotationInfo& ri, int64_t T, std::vector<int32_t>& tile
   return n_tiles;
 }
 
-// how much of a tile is left after sd steps: phases of a steady-state group (K, W, K, W, ...) of 8 steps, share of delayed blocks per step
-void tile_delays(const RotationInfo& ri, const std::vector<int32_t>& tile_w, const std::vector<int32_t>& tile_k, double (&delayed)[8]) {
+// how much of a tile is left after sd steps: phases of a steady-state group (K, W, K, W, ...) of n_steps steps, share of delayed blocks per step
+void tile_delays(const RotationInfo& ri, const std::vector<int32_t>& tile_w, const std::vector<int32_t>& tile_k, double (&delayed)[TILE_STEPS_MAX], int n_steps) {
   std::vector<int32_t> ph[3];
-  for (int sd = 0; sd < 8; ++sd) {
+  for (int sd = 0; sd < n_steps; ++sd) {
     const int kd = sd % 2 == 0 ? 3 : 2;
     const std::vector<int32_t>& tl = sd % 2 == 0 ? tile_k : tile_w;
     const int64_t nb = (int64_t)tl.size();
@@ -268,12 +268,56 @@ TileSet make_tiles(const RotationInfo& ri, int T) {
   TileSet ts;
   ts.T = T;
   ts.n = grow_tiles(ri, T, ts.w, ts.k, ts.radius);
-  tile_delays(ri, ts.w, ts.k, ts.delayed);
+  tile_delays(ri, ts.w, ts.k, ts.delayed, 8);
   // a block whose predecessor ran in a later tile is delayed to that tile's phase — one more shell of every tile per step: the
   // deepest even depth (up to 8) whose LAST step still runs at least half of its blocks in their own tile's phase
   ts.depth = 2;
   for (int d = 4; d <= 8; d += 2) if (ts.delayed[d - 1] <= 0.5) ts.depth = d;
   return ts;
+}
+
+void extend_tile_delays(const RotationInfo& ri, TileSet& ts) {
+  if (ts.delays_extended || ts.T <= 0) return;
+  tile_delays(ri, ts.w, ts.k, ts.delayed, TILE_STEPS_MAX);
+  ts.delays_extended = true;
+}
+
+// Measured on 1024^2 x 32 labels (EXPERIMENTS.md T).  PQ_TILE_BYTES of a W step per tile is what 8192 blocks per tile are on that grid:
+// such a tile is NOT inside the Infinity Cache, and is not meant to be — tiles only make the reach of the dependencies a row of a
+// tile, large ones have few blocks on a rim, and the distance between two reads of a table comes from the lag alone (2 x PQ_SUB_LAG
+// times of depth / 2 W sub-bands each, about 150 MB of tables).  4096 blocks were 1 % slower, 2048 3 %, 32768 5 %; nothing else between
+// 4096 and 32768 was tried.  PQ_SUB_TICKETS W tickets per sub-band, PQ_SUB_LAG times between consecutive steps, PQ_SUB_GAP times at least
+// behind every predecessor, groups of at most PQ_DEPTH steps (12 and 16 were slower).
+namespace {
+constexpr double PQ_TILE_BYTES = 1662.0 * 1048576.0;
+constexpr int PQ_SUB_TICKETS = 64, PQ_SUB_LAG = 3, PQ_SUB_GAP = 2, PQ_DEPTH = 8;
+constexpr int64_t PQ_TABLE_BYTES = 32 * 32 * 8, PQ_MINIMA_BYTES = 32 * 8, INFINITY_CACHE_BYTES = (int64_t)256 << 20;
+}  // namespace
+
+PqGeometry peer_minima_geometry(const RotationInfo& ri, int tile_blocks) {
+  PqGeometry g;
+  // (PQ_TABLE_BYTES / PQ_MINIMA_BYTES are the exact 32-label f64 class's, the only one peer_minima_obstacle admits)
+  if (!ri.valid || !ri.peer_minima || ri.kclass != KC_DENSE_32 || ri.t[1].nb <= 0 || ri.t[2].nb <= 0) return g;
+  for (int i = 0; i < 4; ++i)
+    g.step_bytes[i] = i == 1 ? ri.t[i].bytes + ri.t[i].recv * PQ_MINIMA_BYTES : std::max<int64_t>(0, ri.t[i].bytes - ri.t[i].recv * (PQ_TABLE_BYTES - PQ_MINIMA_BYTES));
+  g.use = ri.t[1].recv * PQ_TABLE_BYTES > INFINITY_CACHE_BYTES;
+  const double nw = (double)ri.t[1].nb, nk = (double)ri.t[2].nb, w_block_bytes = (double)g.step_bytes[1] / nw;
+  // a tile of T blocks holds about 2 T blocks of the W and K steps together (order.cpp grow_tiles), W and K in the ratio of their counts
+  const double w_share = 2.0 * nw / (nw + nk);
+  g.tile_blocks = tile_blocks > 0 ? tile_blocks : (int)std::max(1.0, std::min(nw, std::floor(PQ_TILE_BYTES / w_block_bytes / w_share + 0.5)));
+  g.w_blocks_per_tile = std::min(nw, g.tile_blocks * w_share);
+  g.tile_bytes = g.w_blocks_per_tile * w_block_bytes;
+  g.sub = (int)std::max(1.0, std::floor(g.w_blocks_per_tile / PQ_SUB_TICKETS));
+  g.sub_lag = PQ_SUB_LAG; g.sub_gap = PQ_SUB_GAP;
+  g.depth = PQ_DEPTH;                      // (what make_tiles allows at most: the rule takes TileSet::depth)
+  return g;
+}
+
+double peer_minima_hbm_share(const TileSet& ts, int depth) {
+  if (depth < 2) return 1.0;
+  double late = 0;
+  for (int sd = 3; sd < std::min(depth, TILE_STEPS_MAX); sd += 2) late += ts.delayed[sd];
+  return std::min(1.0, (1.0 + late) / (depth / 2));
 }
 
 void band_order(const std::vector<int64_t>& nb, int bands, int lag, int depth, TicketOrder& o) {
@@ -351,6 +395,77 @@ void tiled_order(const RotationInfo& ri, int n, const TileSet& ts, int depth, Ti
   o.group_begin.push_back(at);
 }
 
+// Skewed tiled order (peer-minima launches; chosen in engine.cpp rotation_chain).  In the tiled order the steps of a phase run back to
+// back, so the first tickets of every step are drawn while their predecessors still run, and a table is read again a whole tile
+// later.  Here the blocks of a tile are cut, in block order, into `sub` sub-bands, the sub-bands of all tiles form one list in tile
+// order, and sub-band b of the group's sd-th step comes at time b + lag * sd — the band order's skew over a list in which a block's
+// predecessors lie a row of its TILE away, not a row of the grid.  Where they lie further (the rim of a tile next to a later one)
+// the block waits for them: a block never comes before time(predecessor) + gap.  Valid by construction, whatever sub, lag and gap
+// are.  Tickets by (time, step, block); sub <= 1 is tiled_order's order.
+void skewed_tile_order(const RotationInfo& ri, int n, const TileSet& ts, int depth, int sub, int lag, int gap, TicketOrder& o) {
+  if (sub <= 1) { tiled_order(ri, n, ts, depth, o); return; }
+  std::vector<int> tmpl, kind;
+  joined_steps(n, tmpl, kind);
+  const int n_steps = (int)tmpl.size();
+  std::vector<int64_t> base((size_t)n_steps + 1, 0);
+  for (int s = 0; s < n_steps; ++s) base[s + 1] = base[s] + ri.t[tmpl[s]].nb;
+  const int64_t N = base[n_steps];
+  o.tk_step.resize((size_t)N); o.tk_block.resize((size_t)N); o.new_of.resize((size_t)N); o.group_begin.clear();
+  lag = std::max(1, lag); gap = std::max(0, gap);
+  if ((int64_t)ts.n * sub + (int64_t)(lag + gap) * depth >= INT32_MAX / (2 * depth)) throw std::runtime_error("rotation chain: too many sub-bands");
+  // the sub-band of every W block and of every block of the other templates, counted through the tiles
+  std::vector<int32_t> band[2];
+  for (int which = 0; which < 2; ++which) {
+    const std::vector<int32_t>& tl = which == 0 ? ts.w : ts.k;
+    std::vector<int64_t> members((size_t)ts.n, 0), seen((size_t)ts.n, 0);
+    for (int32_t t : tl) ++members[t];
+    band[which].resize(tl.size());
+    for (size_t j = 0; j < tl.size(); ++j) band[which][j] = (int32_t)((int64_t)tl[j] * sub + seen[tl[j]]++ * sub / members[tl[j]]);
+  }
+  std::vector<int32_t> tm[3];
+  std::vector<int64_t> bucket;
+  std::vector<std::vector<int32_t>> key_of((size_t)depth);
+  int64_t at = 0;
+  for (int s0 = 0; s0 < n_steps; s0 += depth) {
+    o.group_begin.push_back(at);
+    const int d = std::min(depth, n_steps - s0);
+    int32_t t_max = 0;
+    for (int sd = 0; sd < d; ++sd) {
+      const int s = s0 + sd;
+      const int64_t nb = ri.t[tmpl[s]].nb;
+      const std::vector<int32_t>& bd = band[tmpl[s] == 1 ? 0 : 1];
+      std::vector<int32_t>& cur = tm[sd % 3];
+      cur.resize((size_t)nb);
+      key_of[sd].resize((size_t)nb);
+      const int kd = kind[s];
+      for (int64_t j = 0; j < nb; ++j) {
+        int32_t t = bd[j] + lag * sd;
+        if (kd >= 0)
+          for (int64_t q = ri.off[kd][j]; q < ri.off[kd][j + 1]; ++q) {
+            const int dl = ri.delta[kd][q];
+            if (dl <= sd) t = std::max(t, tm[(sd - dl) % 3][ri.block[kd][q]] + gap);
+          }
+        cur[j] = t;
+        t_max = std::max(t_max, t);
+        key_of[sd][j] = t * d + sd;
+      }
+    }
+    bucket.assign((size_t)(t_max + 1) * d + 1, 0);
+    for (int sd = 0; sd < d; ++sd) for (int32_t k : key_of[sd]) ++bucket[(size_t)k + 1];
+    for (size_t k = 0; k + 1 < bucket.size(); ++k) bucket[k + 1] += bucket[k];
+    for (int sd = 0; sd < d; ++sd) {
+      const int s = s0 + sd;
+      const int64_t nb = ri.t[tmpl[s]].nb;
+      for (int64_t j = 0; j < nb; ++j) {
+        const int64_t t = at + bucket[key_of[sd][j]]++;
+        o.new_of[base[s] + j] = (int32_t)t; o.tk_step[t] = s; o.tk_block[t] = (int32_t)j;
+      }
+    }
+    for (int sd = 0; sd < d; ++sd) at += ri.t[tmpl[s0 + sd]].nb;
+  }
+  o.group_begin.push_back(at);
+}
+
 std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, int n, bool periodic, JoinedTables& out, FILE* log) {
   const auto t_begin = std::chrono::steady_clock::now();
   auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -365,8 +480,10 @@ std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, i
   TicketOrder o;
   // the band order searches its lag from ord.lag on; the tiled order does not depend on it
   const int lag_end = ord.tiles ? ord.lag : std::max(16, 2 * ord.lag);
+  int sub = ord.tiles ? ord.sub : 1;                 // (a skewed tiled order that is refused is tried again as the plain tiled order)
   for (int lag = ord.lag; lag <= lag_end; ++lag) {
-    if (ord.tiles) tiled_order(ri, n, *ord.tiles, depth, o);
+    if (ord.tiles && sub > 1) skewed_tile_order(ri, n, *ord.tiles, depth, sub, ord.sub_lag, ord.sub_gap, o);
+    else if (ord.tiles) tiled_order(ri, n, *ord.tiles, depth, o);
     else band_order(nb, ord.bands, lag, depth, o);
     if (o.group_begin.back() != N) throw std::runtime_error("rotation chain: ticket count");
     if (log) std::fprintf(log, "lpmp:   %d passes, lag %d: order after %.0f ms\n", n, lag, since());
@@ -384,6 +501,7 @@ std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, i
           }
     }
     if (log) std::fprintf(log, "lpmp:   checked after %.0f ms (%s)\n", since(), ok ? "valid" : "a dependency points forward");
+    if (!ok && ord.tiles && sub > 1) { sub = 1; --lag; continue; }
     if (!ok && ord.tiles) return "internal: the tiled order broke a dependency";   // (valid by construction)
     if (!ok) continue;
     // dependencies in ticket order
@@ -442,7 +560,7 @@ std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, i
       if (tmpl[s] == 1 && ((s - 1) / 2 < n - 1 || periodic)) out.step_row[s] = (s - 1) / 2;
       if (tmpl[s] == 2) out.step_row[s] = (s - 2) / 2;
     }
-    out.lag = lag;
+    out.lag = lag; out.sub = sub;
     return "";
   }
   return "no band order keeps the dependencies backwards";

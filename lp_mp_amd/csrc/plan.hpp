@@ -461,20 +461,40 @@ RotGeometry rot_geometry(const RotSettings& rs, const RotationInfo& ri);
 
 // tiles of about T blocks of the W and K steps (w, k: tile of every block; n tiles); delayed[sd]: share of a steady-state step's
 // blocks that run later than their own tile's phase, sd steps into a group; depth: the group depth that follows from it
-struct TileSet { int T = 0; std::vector<int32_t> w, k; int32_t n = 0; double radius = 0; double delayed[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int depth = 2; };
+// (make_tiles fills delayed[0 .. 7], which is what the depth follows from; extend_tile_delays fills the rest, so that groups of 12 and
+// 16 steps can be judged by the same figures: both were slower than 8 on the headline grid, EXPERIMENTS.md T, and no rule picks them)
+constexpr int TILE_STEPS_MAX = 16;
+struct TileSet { int T = 0; std::vector<int32_t> w, k; int32_t n = 0; double radius = 0; double delayed[TILE_STEPS_MAX] = {}; int depth = 2; bool delays_extended = false; };
 TileSet make_tiles(const RotationInfo& ri, int T);
+void extend_tile_delays(const RotationInfo& ri, TileSet& ts);
+
+// The geometry of a peer-minima launch (engine.cpp rotation_chain; EXPERIMENTS.md T).  step_bytes: what a step of that form moves —
+// W: tables + vectors + the minima it writes, H / K / T: vectors + the minima they read (RotationInfo::t[].bytes still counts a table
+// per K / T receive).  use: the tables of a W step exceed the Infinity Cache.  tile_blocks (the T of make_tiles) follows from
+// tile_bytes of a W step, sub from the W tickets a sub-band should hold.  peer_minima_geometry(ri, T > 0): for tiles of T blocks.
+struct PqGeometry { bool use = false; int tile_blocks = 0, depth = 8, sub = 1, sub_lag = 1, sub_gap = 0; int64_t step_bytes[4] = {0, 0, 0, 0}; double tile_bytes = 0, w_blocks_per_tile = 0; };
+PqGeometry peer_minima_geometry(const RotationInfo& ri, int tile_blocks = 0);
+// share of a W step's table reads that is expected to come from HBM: the first W step of a group of `depth` steps, and the delayed
+// blocks of the others (their tile's phase is long over)
+double peer_minima_hbm_share(const TileSet& ts, int depth);
 // tiled order of n joined passes: in a group of `depth` steps a block runs in the phase of its own tile or the latest phase of its
 // predecessors in the group; tickets sorted by (phase, step, block)
 void tiled_order(const RotationInfo& ri, int n, const TileSet& ts, int depth, TicketOrder& o);
+// the same with the band order's skew over the tiles: every tile cut into `sub` sub-bands in block order, all sub-bands one list in
+// tile order, sub-band b of the group's sd-th step at time b + lag * sd, a block never before time(predecessor) + gap; tickets by
+// (time, step, block); sub <= 1: tiled_order
+void skewed_tile_order(const RotationInfo& ri, int n, const TileSet& ts, int depth, int sub, int lag, int gap, TicketOrder& o);
 
 // the order of a joined-pass launch: band order (bands, lags from `lag` to max(16, 2 lag), depth) or, with tiles, the tiled order
-struct JoinedOrder { int bands = 1, lag = 3, depth = 4; const TileSet* tiles = nullptr; };
+// sub > 1 (tiles only): the skewed tiled order, sub sub-bands per tile at a lag of sub_lag times between consecutive steps
+struct JoinedOrder { int bands = 1, lag = 3, depth = 4; const TileSet* tiles = nullptr; int sub = 1, sub_lag = 1, sub_gap = 0; };
 struct JoinedTables {
   std::vector<int32_t> tk_launch, tk_block, dep_off, dep;   // ticket -> step, block; dependencies (CSR over tickets)
   std::vector<int> step_tmpl;                               // per step: its template (0 H, 1 W, 2 K, 3 T)
   std::vector<int32_t> step_row;                            // per step: the per-pass bound row its launch writes (-1: none)
   int32_t per_begin = 0, per_len = 0, ring = 0;             // periodic template: the period's tickets, slots of the flag ring
   int lag = 0;                                              // the lag the band order was built with
+  int sub = 1;                                              // the sub-bands the tiled order was built with (1: the plain tiled order)
 };
 // the tables of n joined passes (periodic: the template of n passes whose group 2 is the period; the depth must be even) — ""
 // or why the passes stay one launch per step; log (or nullptr): progress lines.  ri must be valid.
