@@ -92,11 +92,22 @@ int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t*
  * references a banded vector; none when LPMP_NO_DIFF_BAND was set as the plan was made), and the receives of both */
 int lpmp_plan_diff_band_info(lpmp_plan* p, int direction, int mode, int64_t* diff_launches, int64_t* band_launches,
                              int64_t* diff_receives, int64_t* band_receives);
+/* The same for DIFF_SHIFT factors.  The band [lo, hi] of pool entry `table` as DIFF_SHIFT factors see it: that of D
+ * itself, as above, whatever the shifts; referenced: 1 when a DIFF_SHIFT factor references the entry, else 0 (and lo 0, hi -1).  A
+ * receive of a d0 x d1 factor is banded when (hi - lo + 1) * 4 <= d0 + d1 - 1: the shift moves the band inside the receive's
+ * d0 + d1 - 1 differences (or out of them) and never widens it, so pool values and structure decide, never a shift. */
+int lpmp_plan_get_diff_shift_band(const lpmp_plan* p, int table, int32_t* lo, int32_t* hi, int* referenced);
+/* launches of class diff with a DIFF_SHIFT factor in that sweep, how many of them run the shifted banded kernel (every receive of
+ * every record of the launch is banded, a plain DIFF peer by its own rule; none when LPMP_NO_DIFF_BAND was set as the plan was
+ * made), and the receives of both.  lpmp_plan_diff_band_info counts none of them as band launches. */
+int lpmp_plan_diff_shift_band_info(lpmp_plan* p, int direction, int mode, int64_t* shift_launches, int64_t* shift_band_launches,
+                                   int64_t* shift_receives, int64_t* shift_band_receives);
 /* host only: new VALUES for the pool of a plan, packed as lpmp_model.sh_data (same n_shared_tables, sh_off, dims).  A NaN entry is
  * refused (LPMP_ERR_INVALID naming the table, the plan untouched), as are a NULL pointer and a plan without a pool.  The band of
- * every entry a DIFF factor references is detected again (LPMP_NO_DIFF_BAND stays what it was when the plan was made), and in every
+ * every entry a DIFF or DIFF_SHIFT factor references is detected again (LPMP_NO_DIFF_BAND stays what it was when the plan was made), and in every
  * schedule the plan has cached each launch of class diff gets its kernel choice again by the rule above: nothing else of a schedule
- * moves and none is built.  lpmp_plan_get_diff_band / lpmp_plan_diff_band_info report the new state. */
+ * moves and none is built.  lpmp_plan_get_diff_band / lpmp_plan_diff_band_info and their
+ * DIFF_SHIFT counterparts report the new state. */
 int lpmp_plan_set_shared_pool(lpmp_plan* p, const double* sh_data);
 
 /* the same summary for an iterator-range pass (LP_MP.h:981-1005) given as factor list + weight rows + receive-mask
@@ -594,8 +605,11 @@ int lpmp_reset_kernel_timing(lpmp_engine* e);
 int lpmp_get_chain_launches(lpmp_engine* e, int n_classes, int64_t* chain_launches /*[n]*/);
 /* of the launches reported for class diff: how many ran the banded kernel (sweep_diff_band_kernel) */
 int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches);
-/* ... and how many ran the shifted kernel (sweep_diff_shift_kernel: launches with a LPMP_F_PAIRWISE_DIFF_SHIFT factor; never banded) */
+/* ... and how many had a LPMP_F_PAIRWISE_DIFF_SHIFT factor (sweep_diff_shift_kernel or sweep_diff_shift_band_kernel; never
+ * sweep_diff_band_kernel) */
 int lpmp_get_diff_shift_launches(lpmp_engine* e, int64_t* shift_launches);
+/* ... and of those, how many ran the shifted banded kernel (sweep_diff_shift_band_kernel) */
+int lpmp_get_diff_shift_band_launches(lpmp_engine* e, int64_t* shift_band_launches);
 /* joined-pass launches in the peer-minima form since the last lpmp_reset_kernel_timing; counted with timing off,
  * too (passes that run ahead of the caller are never timed): with timing on since the reset, a part of dense32's chain launches */
 int lpmp_get_peer_minima_launches(lpmp_engine* e, int64_t* launches);

@@ -101,7 +101,7 @@ struct LaunchView { const UpdRec* recs; const Op* ops; const Op* packets; const 
 struct DevSchedule {
   DevBuf<UpdRec> recs; DevBuf<Op> ops, packets;   // (a scratch schedule is refilled in place: DevBuf::grow)
   std::vector<LevelRange> launches;
-  std::vector<int32_t> diff_tab_off, diff_tab;   // Schedule::diff_tab_off / diff_tab: what new pool values ask again (refresh_diff_band)
+  std::vector<int32_t> diff_tab_off, diff_tab, diff_tab_ne;   // Schedule::diff_tab_off / diff_tab / diff_tab_ne: what new pool values ask again (refresh_diff_band)
   int64_t n_levels = 0, n_recv = 0, n_send = 0, alg_bytes = 0;
   GraphExec graph, graph_primal;           // graph_primal: the same launches with the SWEEP_PRIMAL flag
   bool adaptive_built = false;             // built with every update on the generic kernels (adaptive send rule)
@@ -115,11 +115,11 @@ struct DevSchedule {
     graph.reset(); graph_primal.reset();
     recs.reset(); ops.reset(); packets.reset();
     release_chain();
-    launches.clear(); diff_tab_off.clear(); diff_tab.clear();
+    launches.clear(); diff_tab_off.clear(); diff_tab.clear(); diff_tab_ne.clear();
   }
-  // new pool values: diff_band of the KC_DIFF launches again; a graph captured with the other kernel choice is never replayed
+  // new pool values: diff_band / diff_shift_band of the KC_DIFF launches again; a graph captured with the other kernel choice is never replayed
   void refresh_diff_band(const Plan& p) {
-    const bool a = p.refresh_diff_band(launches, diff_tab_off, diff_tab), b = p.refresh_diff_band(plain, diff_tab_off, diff_tab);
+    const bool a = p.refresh_diff_band(launches, diff_tab_off, diff_tab, diff_tab_ne), b = p.refresh_diff_band(plain, diff_tab_off, diff_tab, diff_tab_ne);
     bool diff = false;
     for (const auto& lr : launches) diff = diff || lr.kclass == KC_DIFF;
     if (a || b || diff) { graph.reset(); graph_primal.reset(); }
@@ -131,7 +131,7 @@ static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 
   return v;
 }
 
-struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, shift_launches = 0, peer_minima_launches = 0; };
+struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, shift_launches = 0, shift_band_launches = 0, peer_minima_launches = 0; };
 
 }  // namespace
 
@@ -147,10 +147,10 @@ struct lpmp_plan {
     if (!have_decode[d]) { decode_cache[d] = p.decode_plan(d); have_decode[d] = true; }
     return decode_cache[d];
   }
-  // new VALUES for the pool (Plan::set_shared_pool): of the cached schedules only diff_band of their KC_DIFF launches moves
+  // new VALUES for the pool (Plan::set_shared_pool): of the cached schedules only diff_band / diff_shift_band of their KC_DIFF launches move
   void set_shared_pool(const double* values) {
     p.set_shared_pool(values);
-    auto again = [&](Schedule& s) { p.refresh_diff_band(s.launches, s.diff_tab_off, s.diff_tab); };
+    auto again = [&](Schedule& s) { p.refresh_diff_band(s.launches, s.diff_tab_off, s.diff_tab, s.diff_tab_ne); };
     for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
       for (int d = 0; d < 2; ++d) again(sched_cache[d][m]);
       again(pass_cache[m]); again(bf_cache[m]);
@@ -441,7 +441,7 @@ struct lpmp_engine {
   int rot_tiles = 0; bool rot_tiles_set = false;
   bool timing = false;
   ClassTiming ct[KC_COUNT];
-  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false; };   // band: sweep_diff_band_kernel; shift: sweep_diff_shift_kernel
+  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false, shift_band = false; };   // band: sweep_diff_band_kernel; shift: a launch with a DIFF_SHIFT factor; shift_band: of those, sweep_diff_shift_band_kernel
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
   hipEvent_t get_event() {
@@ -453,7 +453,7 @@ struct lpmp_engine {
       HIP_CHECK(hipEventSynchronize(p.b));
       float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
       ClassTiming& c = ct[p.cls];
-      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.shift_launches += p.shift ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
+      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.shift_launches += p.shift ? 1 : 0; c.shift_band_launches += p.shift_band ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
       event_pool.push_back(p.a); event_pool.push_back(p.b);
     }
     pending.clear();
@@ -598,7 +598,7 @@ DevChain upload_chain(const std::vector<ChainLaunch>& lds, const std::vector<int
 void upload_schedule(const Schedule& s, DevSchedule& d, hipStream_t stream, bool keep = false, bool adaptive_built = false) {
   if (keep) { d.graph.reset(); d.graph_primal.reset(); }
   else d.release();
-  d.launches = s.launches; d.diff_tab_off = s.diff_tab_off; d.diff_tab = s.diff_tab; d.n_levels = s.n_levels; d.n_recv = s.n_recv; d.n_send = s.n_send; d.alg_bytes = s.alg_bytes;
+  d.launches = s.launches; d.diff_tab_off = s.diff_tab_off; d.diff_tab = s.diff_tab; d.diff_tab_ne = s.diff_tab_ne; d.n_levels = s.n_levels; d.n_recv = s.n_recv; d.n_send = s.n_send; d.alg_bytes = s.alg_bytes;
   d.adaptive_built = adaptive_built;
   fill_device(d.recs, s.recs, stream);
   fill_device(d.ops, s.ops, stream);
@@ -758,7 +758,7 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
         throw DeviceError("sweep: launch of shared class " + std::to_string(lr.kclass) + " without packets or tables");
     }
     else if (lr.kclass == KC_DIFF)     // (LDS by the launch's label counts, as the streaming class)
-      launch_sweep_diff(lr.diff_band, lr.diff_shift, s.recs, s.ops, e->model.d_dual, e->model.d_const, e->model.d_lb, e->model.d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
+      launch_sweep_diff(lr.diff_band || lr.diff_shift_band, lr.diff_shift, s.recs, s.ops, e->model.d_dual, e->model.d_const, e->model.d_lb, e->model.d_primal, lr.begin, lr.end - lr.begin, flags | sweep_bigdim_flags(lr.max_dim), stream);
     else if (!(lr.stride != 0 &&
           launch_sweep_packed(lr.kclass, lr.stride > 0 ? s.packets + lr.pk_begin : nullptr, s.recs + lr.begin, s.ops, lr.stride, e->model.d_dual,
                               e->model.d_const, e->model.d_lb, e->model.d_primal, lr.end - lr.begin, flags, stream))) {
@@ -769,7 +769,8 @@ void issue_launches(lpmp_engine* e, const LaunchView& s, bool timed, hipStream_t
     }
     if (timed) {
       HIP_CHECK(hipEventRecord(b, stream));
-      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes, lr.kclass == KC_DIFF && lr.diff_band, lr.kclass == KC_DIFF && lr.diff_shift});
+      e->pending.push_back({a, b, lr.kclass, lr.end - lr.begin, lr.n_recv, lr.bytes, lr.kclass == KC_DIFF && lr.diff_band, lr.kclass == KC_DIFF && lr.diff_shift,
+                            lr.kclass == KC_DIFF && lr.diff_shift && lr.diff_shift_band});
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -1331,6 +1332,15 @@ int lpmp_plan_get_diff_band(const lpmp_plan* p, int table, int32_t* lo, int32_t*
     if (banded) *banded = p->p.sh_banded[(size_t)table];
   });
 }
+int lpmp_plan_get_diff_shift_band(const lpmp_plan* p, int table, int32_t* lo, int32_t* hi, int* referenced) {
+  return guarded([&] {
+    if (!p || table < 0 || table >= p->p.n_shared) throw std::runtime_error("bad argument");
+    const bool ref = p->p.sh_shift_ref[(size_t)table] != 0;
+    if (lo) *lo = ref ? p->p.sh_lo[(size_t)table] : 0;
+    if (hi) *hi = ref ? p->p.sh_hi[(size_t)table] : -1;
+    if (referenced) *referenced = ref ? 1 : 0;
+  });
+}
 int lpmp_plan_set_shared_pool(lpmp_plan* p, const double* sh_data) {
   return guarded([&] {
     if (!p || !sh_data) throw std::runtime_error("lpmp_plan_set_shared_pool: null argument");
@@ -1349,6 +1359,21 @@ int lpmp_plan_diff_band_info(lpmp_plan* p, int d, int mode, int64_t* diff_launch
     if (band_launches) *band_launches = v[1];
     if (diff_receives) *diff_receives = v[2];
     if (band_receives) *band_receives = v[3];
+  });
+}
+
+int lpmp_plan_diff_shift_band_info(lpmp_plan* p, int d, int mode, int64_t* shift_launches, int64_t* shift_band_launches, int64_t* shift_receives,
+                                   int64_t* shift_band_receives) {
+  return guarded([&] {
+    if (!p || d < 0 || d > 1 || mode < 0 || mode >= LPMP_REPAM_COUNT) throw std::runtime_error("bad argument");
+    plan_schedule(p, d, mode);
+    int64_t v[4] = {0, 0, 0, 0};
+    for (const auto& lr : p->sched_cache[d][mode].launches)
+      if (lr.kclass == KC_DIFF && lr.diff_shift) { ++v[0]; v[2] += lr.n_recv; if (lr.diff_shift_band) { ++v[1]; v[3] += lr.n_recv; } }
+    if (shift_launches) *shift_launches = v[0];
+    if (shift_band_launches) *shift_band_launches = v[1];
+    if (shift_receives) *shift_receives = v[2];
+    if (shift_band_receives) *shift_band_receives = v[3];
   });
 }
 
@@ -1730,8 +1755,9 @@ static void gather_shared_cells(ModelState& m, hipStream_t stream) {
   HIP_CHECK(hipGetLastError());
 }
 // ... the pool block of d_shared, behind the n_sf cells (two words each): every entry t of the plan's pool with one 8-byte band word
-// {int32 lo, int32 hi} in front of it — sweep_diff_band_kernel learns the band of a DIFF vector from the word before the offset in
-// the factor's cell (entries no DIFF factor references: an empty band, never read).  Entry t starts at shared_pool_at(p, t).
+// {int32 lo, int32 hi} in front of it — sweep_diff_band_kernel and sweep_diff_shift_band_kernel learn the band of a DIFF / DIFF_SHIFT
+// vector from the word before the offset in the factor's cell (entries neither kind references: an empty band, never read; the plan
+// keeps sh_lo / sh_hi for both kinds, so new pool values rewrite the word of a shift-only entry too).  Entry t starts at shared_pool_at(p, t).
 static int64_t shared_pool_at(const Plan& p, int32_t t) { return p.sh_off[(size_t)t] + t + 1; }
 static void write_shared_pool(ModelState& m, hipStream_t stream, int64_t n_sf) {
   const Plan& p = m.plan->p;
@@ -3350,13 +3376,22 @@ int lpmp_get_diff_band_launches(lpmp_engine* e, int64_t* band_launches) {
     *band_launches = e->ct[KC_DIFF].band_launches;
   });
 }
-// ... and how many ran sweep_diff_shift_kernel
+// ... and how many had a DIFF_SHIFT factor (sweep_diff_shift_kernel or sweep_diff_shift_band_kernel)
 int lpmp_get_diff_shift_launches(lpmp_engine* e, int64_t* shift_launches) {
   return guarded([&] {
     if (!e || !shift_launches) throw std::runtime_error("null argument");
     HIP_CHECK(hipStreamSynchronize(e->stream));
     e->drain_timing();
     *shift_launches = e->ct[KC_DIFF].shift_launches;
+  });
+}
+// ... and of those, how many ran sweep_diff_shift_band_kernel
+int lpmp_get_diff_shift_band_launches(lpmp_engine* e, int64_t* shift_band_launches) {
+  return guarded([&] {
+    if (!e || !shift_band_launches) throw std::runtime_error("null argument");
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->drain_timing();
+    *shift_band_launches = e->ct[KC_DIFF].shift_band_launches;
   });
 }
 int lpmp_reset_kernel_timing(lpmp_engine* e) {

@@ -3229,6 +3229,138 @@ sweep_diff_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ o
   ob = wave_min(ob);
   if (lane == 0) st_lb<A>(lb + rec.factor, ob);
 }
+// The shifted banded kernel (launches with a DIFF_SHIFT peer whose receives all pass the shifted rule: LevelRange::diff_shift_band):
+// the text of sweep_diff_band_kernel with the band of a receive computed from the band word of D and the window {s, n} of the
+// shifted fill.  The expansion of a receive over i = a - b + C - 1 is D[clamp(i - off, 0, n - 1)], off = C - 1 - s: entries below
+// le = clamp(lo + off, 0, R + C - 1) are D[0], entries above he = clamp(hi + off, -1, R + C - 2) are D[n - 1], the ones between
+// are D[i - off] — the band moved, clipped to the receive, the clamp continuing both tails — and diff_band_minplus is exact on
+// {le, he, scale * D[0], scale * D[n - 1]} as it stands.  A plain DIFF peer has s = C - 1, n = R + C - 1: off = 0.
+// Registers: the window's two words beside the band word take the body past the 80 VGPRs of six waves per SIMD, which the banded
+// kernel fills to the last one — every six-wave form tried kept 8 to 28 bytes of scratch per lane —, so this kernel
+// is built for five (96 VGPRs allowed, 0 scratch).  Up to 128 labels that is one wave per SIMD fewer than the banded kernel; above,
+// the LDS of the banded layout sets the occupancy of both.
+constexpr int DIFF_SHIFT_BAND_WAVES_PER_SIMD = 5;
+__global__ void __launch_bounds__(64 * BIG_WAVES, DIFF_SHIFT_BAND_WAVES_PER_SIMD)
+sweep_diff_shift_band_kernel(const UpdRec* __restrict__ recs, const Op* __restrict__ ops, double* __restrict__ dual,
+                             const double* __restrict__ cdata, double* __restrict__ lb, int32_t* __restrict__ primal,
+                             int64_t first, int64_t count, int flags) {
+  constexpr int A = ACC_PLAIN;
+  extern __shared__ double big_lds_pool[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t idx = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  if (idx >= count) return;
+  const int ldim = big_ldim(flags);
+  double* const slab = big_lds_pool + (size_t)wave * DIFF_BAND_SLABS * ldim;
+  BigLds S{slab, slab + ldim, slab + 2 * ldim};
+  double* const pre = slab + 3 * ldim; double* const suf = slab + 4 * ldim; double* const sB = slab + 5 * ldim;
+  UpdRec rec = recs[first + idx];
+  rec.dual_off = uni64<64>(rec.dual_off); rec.d0 = uni<64>(rec.d0); rec.op_begin = uni<64>(rec.op_begin);
+  rec.n_recv = (int16_t)uni<64>((int)rec.n_recv); rec.n_send = (int16_t)uni<64>((int)rec.n_send);
+  rec.factor = uni<64>(rec.factor); rec.kind_flags = uni<64>(rec.kind_flags);
+  const int Lr = rec.d0;
+  double* own_g = dual + rec.dual_off;
+  for (int i = lane; i < Lr; i += 64) S.theta[i] = ld_dual<A>(own_g + i);
+  Op nxt{};
+  double nscale = 0.0; int64_t noff = 0;               // the next receive's two constant words {scale, offset of D}
+  int2 nband = make_int2(0, -1);                       // ... the band word of its D ...
+  DiffWin nwin{0, 1};                                  // ... and its window {s, n}
+  if (rec.n_recv > 0) {
+    nxt = ops[rec.op_begin];
+    const int64_t pc = uni64<64>(nxt.peer_const);
+    nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+    nband = diff_band_word(cdata, uni64<64>(noff));
+    nwin = diff_next_win(nxt, cdata, pc);
+  }
+  for (int k = 0; k < rec.n_recv; ++k) {
+    const Op op = uni_op(nxt);
+    const double scale = uni_f64(nscale);
+    const double* D = cdata + uni64<64>(noff);
+    const int ws = uni<64>(nwin.s), wn = uni<64>(nwin.n);
+    const int blo = uni<64>(nband.x), bhi = uni<64>(nband.y);
+    if (k + 1 < rec.n_recv) nxt = ops[rec.op_begin + k + 1];   // requested before this receive's reduction starts
+    const int side = (op.info >> 5) & 1;
+    const int R = op.pd0, C = op.pd1;
+    double* ms = dual + op.peer_dual + (side == 0 ? 0 : R);
+    const double* mo = dual + op.peer_dual + (side == 0 ? R : 0);
+    const int Lo = side == 0 ? C : R;
+    double ms_pre[2];                                  // the own side m_s is requested together with m_o and D
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ms_pre[j] = lane + 64 * j < Lr ? ld_dual<A>(ms + lane + 64 * j) : 0.0;
+    for (int i = lane; i < Lo; i += 64) S.mo[i] = ld_dual<A>(mo + i);
+    // the band of D in the receive's R + C - 1 entries: moved by off = C - 1 - s, clipped to them (wave-uniform).  |off| <= 2^30 +
+    // 2^16 fits an int, the band word (below 2^31) plus off need not: those two sums in 64 bits.  hi >= lo - 1, so he >= le - 1:
+    // an empty window is le = he + 1, all tails
+    const int off = C - 1 - ws;
+    const int lo = (int)min(max((long long)blo + off, 0ll), (long long)(R + C - 1));
+    const int hi = (int)min(max((long long)bhi + off, -1ll), (long long)(R + C - 2));
+    // the ONE multiply per entry, for the window only (k - off is inside the band of D: no clamp; at most (R + C - 1) / DIFF_BAND_DIV
+    // entries by the planner's rule: inside the sB slab); the two tail constants are the products of the end entries of D
+    for (int i = lo + lane; i <= hi; i += 64) sB[i - lo] = scale * D[i - off];
+    const double cL = scale * D[0], cR = scale * D[wn - 1];
+    wave_sync();
+    if (k + 1 < rec.n_recv) {                          // the next op has arrived with m_o: its constants and window travel during the reduction ...
+      const int64_t pc = uni64<64>(nxt.peer_const);
+      nscale = cdata[pc]; noff = shared_table_off(cdata, pc);
+      nwin = diff_next_win(nxt, cdata, pc);
+    }
+    diff_band_scans(S.mo, pre, suf, Lo, lane);
+    wave_sync();
+    if (side == 0) diff_band_minplus_all<false>(sB, S.mo, pre, suf, S.q, Lr, Lo, C, lo, hi, cL, cR, lane);
+    else diff_band_minplus_all<true>(sB, S.mo, pre, suf, S.q, Lr, Lo, C, lo, hi, cL, cR, lane);
+    if (k + 1 < rec.n_recv) nband = diff_band_word(cdata, uni64<64>(noff));   // ... and the band word of its D during the update below
+    wave_sync();
+    double pb = LPMP_INF;                              // peer's bound after this receive
+    for (int i = lane, j = 0; i < Lr; i += 64, ++j) {
+      const double msv = j == 0 ? ms_pre[0] : j == 1 ? ms_pre[1] : ld_dual<A>(ms + i), qv = S.q[i];
+      const double delta = msv + qv;                   // omega = 1: delta = min-marginal
+      S.theta[i] += delta;
+      const double mn = msv - delta;
+      st_dual<A>(ms + i, mn);
+      pb = fmin(pb, mn + qv);
+    }
+    pb = wave_min(pb);
+    if (lane == 0) st_lb<A>(lb + op.peer, pb);
+    wave_sync();
+  }
+  if ((flags & SWEEP_PRIMAL) && (rec.kind_flags & UPD_PRIMAL)) {   // first minimiser of theta after the receives
+    double bv = LPMP_INF; int bi = 0x7fffffff;
+    for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; if (bi == 0x7fffffff || x < bv) { bv = x; bi = i; } }
+    const double mn = wave_min(bv);
+    int cand = (bi != 0x7fffffff && bv == mn) ? bi : 0x7fffffff;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
+    if (lane == 0) store_label(primal, rec.factor, Lr, cand);
+  }
+  // sends from the state after the receives (kept in q); a lane always owns the same elements: no barrier needed
+  for (int i = lane; i < Lr; i += 64) S.q[i] = S.theta[i];
+  for (int k = 0; k < rec.n_send; ++k) {
+    const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+    double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+    for (int i = lane; i < Lr; i += 64) {
+      const double delta = op.omega * S.q[i];
+      st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+      S.theta[i] -= delta;
+    }
+    if (lane == 0) st_lb<A>(lb + op.peer, LPMP_NAN);
+  }
+  if (flags & SWEEP_RESIDUAL) {
+    double residual = 0.0;
+    for (int k = 0; k < rec.n_send; ++k) {
+      const Op op = uni_op(ops[rec.op_begin + rec.n_recv + k]);
+      double* ms = dual + op.peer_dual + (((op.info >> 5) & 1) ? op.pd0 : 0);
+      residual += op.omega;
+      for (int i = lane; i < Lr; i += 64) {
+        const double delta = residual * S.theta[i];
+        st_dual<A>(ms + i, ld_dual<A>(ms + i) + delta);
+        S.theta[i] -= delta;
+      }
+    }
+  }
+  double ob = LPMP_INF;
+  for (int i = lane; i < Lr; i += 64) { const double x = S.theta[i]; st_dual<A>(own_g + i, x); ob = fmin(ob, x); }
+  ob = wave_min(ob);
+  if (lane == 0) st_lb<A>(lb + rec.factor, ob);
+}
 // -------------------------------------------------------------------------------------------------
 // Updated pairwise factors (dense or Potts), packed form (classes KC_PW_4..32; `right` / `full` schedules, e.g. MPLP-style
 // FMCs): the factor is on the right of all its (unary-pairwise) messages.  A receive pulls the whole unary in
@@ -3700,6 +3832,12 @@ void launch_sweep(int kclass, const UpdRec* recs, const Op* ops, double* dual, c
 void launch_sweep_diff(bool band, bool shift, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s) {
   if (count <= 0) return;
+  if (band && shift) {                                 // a DIFF_SHIFT peer, every receive banded (LevelRange::diff_shift_band): LDS and waves of the banded kernel
+    const int waves = big_waves(flags, DIFF_BAND_SLABS);
+    hipLaunchKernelGGL(sweep_diff_shift_band_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_BAND_SLABS), s,
+                       recs, ops, dual, cdata, lb, primal, first, count, flags);
+    return;
+  }
   if (band) {                                          // every receive of the launch has a banded D (LevelRange::diff_band)
     const int waves = big_waves(flags, DIFF_BAND_SLABS);
     hipLaunchKernelGGL(sweep_diff_band_kernel, dim3((unsigned)((count + waves - 1) / waves)), dim3(64 * waves), big_lds_bytes(flags, DIFF_BAND_SLABS), s,

@@ -121,8 +121,9 @@ bool launch_sweep_packed(int kclass, const Op* packets, const UpdRec* recs, cons
                          double* lb, int32_t* primal, int64_t count, int flags, hipStream_t s);
 bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, const Op* ops, int stride, double* dual, const double* cdata,
                          double* lb, int32_t* primal, int64_t count, int flags, const ShTableDesc* desc, const int32_t* tabs, int n_tabs, hipStream_t s);
-// band: the launch's LevelRange::diff_band (sweep_diff_band_kernel; cdata then holds a band word in front of every D)
-// shift: the launch's LevelRange::diff_shift (sweep_diff_shift_kernel: DIFF_SHIFT peers, plain DIFF ones beside them; never with band)
+// band: the launch's LevelRange::diff_band or diff_shift_band (cdata then holds a band word in front of every D)
+// shift: the launch's LevelRange::diff_shift (DIFF_SHIFT peers, plain DIFF ones beside them)
+// neither: sweep_diff_kernel; band: sweep_diff_band_kernel; shift: sweep_diff_shift_kernel; both: sweep_diff_shift_band_kernel
 void launch_sweep_diff(bool band, bool shift, const UpdRec* recs, const Op* ops, double* dual, const double* cdata, double* lb, int32_t* primal, int64_t first, int64_t count,
                        int flags, hipStream_t s);
 // peerq != nullptr: the launches carry CHAIN_LAUNCH_PQ_* roles (joined passes with peer minima; KC_DENSE_32 on f64 tables only)

@@ -114,14 +114,22 @@ bool Plan::diff_launch_banded(const int32_t* tabs, int64_t n) const {
   return true;
 }
 
-bool Plan::refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs) const {
+bool Plan::diff_launch_shift_banded(const int32_t* tabs, const int32_t* ne, int64_t n) const {
+  if (no_diff_band) return false;
+  for (int64_t j = 0; j < n; ++j) if (!diff_band_rule(sh_lo[(size_t)tabs[j]], sh_hi[(size_t)tabs[j]], ne[j])) return false;
+  return true;
+}
+
+bool Plan::refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs,
+                             const std::vector<int32_t>& tabs_ne) const {
   bool changed = false;
   for (LevelRange& lr : launches) {
     if (lr.kclass != KC_DIFF || lr.diff_row < 0 || (size_t)lr.diff_row + 1 >= tabs_off.size()) continue;
     const int32_t t0 = tabs_off[(size_t)lr.diff_row], t1 = tabs_off[(size_t)lr.diff_row + 1];
     const bool band = !lr.diff_shift && diff_launch_banded(tabs.data() + t0, t1 - t0);
-    changed = changed || band != lr.diff_band;
-    lr.diff_band = band;
+    const bool shift_band = lr.diff_shift && tabs_ne.size() == tabs.size() && diff_launch_shift_banded(tabs.data() + t0, tabs_ne.data() + t0, t1 - t0);
+    changed = changed || band != lr.diff_band || shift_band != lr.diff_shift_band;
+    lr.diff_band = band; lr.diff_shift_band = shift_band;
   }
   return changed;
 }
@@ -134,9 +142,9 @@ void Plan::set_shared_pool(const double* values) {
       if (values[i] != values[i]) fail("shared table " + std::to_string(t) + ": NaN entry");
   sh_data.assign(values, values + sh_off[(size_t)n_shared]);
   for (int t = 0; t < n_shared; ++t) {
-    if (sh_banded[(size_t)t] < 0) continue;                 // no DIFF factor references the entry
+    if (sh_banded[(size_t)t] < 0 && !sh_shift_ref[(size_t)t]) continue;   // neither a DIFF nor a DIFF_SHIFT factor references the entry
     diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
-    sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
+    if (sh_banded[(size_t)t] >= 0) sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
   }
 }
 
@@ -193,7 +201,7 @@ void Plan::build(const lpmp_model& m) {
       for (int64_t i = sh_off[t]; i < sh_off[t + 1]; ++i)
         if (sh_data[(size_t)i] != sh_data[(size_t)i]) fail("shared table " + std::to_string(t) + ": NaN entry");
   }
-  sh_lo.assign((size_t)n_shared, 0); sh_hi.assign((size_t)n_shared, -1); sh_banded.assign((size_t)n_shared, -1);
+  sh_lo.assign((size_t)n_shared, 0); sh_hi.assign((size_t)n_shared, -1); sh_banded.assign((size_t)n_shared, -1); sh_shift_ref.assign((size_t)n_shared, 0);
   no_diff_band = std::getenv("LPMP_NO_DIFF_BAND") != nullptr;
   max_dual = 1;
   for (int64_t f = 0; f < nf; ++f) {
@@ -219,7 +227,7 @@ void Plan::build(const lpmp_model& m) {
              std::to_string((int64_t)f_dim0[f] + f_dim1[f] - 1) + ", shared table " + std::to_string(t) + " is " + std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]));
       f_table[f] = t;
       if (sh_banded[(size_t)t] < 0) {
-        diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
+        if (!sh_shift_ref[(size_t)t]) diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
         sh_banded[(size_t)t] = diff_band_rule(sh_lo[(size_t)t], sh_hi[(size_t)t], sh_dim1[(size_t)t]) ? 1 : 0;
       }
     }
@@ -232,7 +240,10 @@ void Plan::build(const lpmp_model& m) {
       if (sh_dim0[t] != 1)
         fail("factor " + std::to_string(f) + ": a shifted difference-indexed factor needs a vector (1 x n), shared table " + std::to_string(t) + " is " +
              std::to_string(sh_dim0[t]) + " x " + std::to_string(sh_dim1[t]));
-      f_table[f] = t;                                   // (sh_banded stays as it is: the band serves the banded kernel, which no shifted launch runs)
+      f_table[f] = t;
+      // the band of D for the shifted banded kernel (sh_banded stays as it is: the plain rule is about DIFF factors only)
+      if (sh_banded[(size_t)t] < 0 && !sh_shift_ref[(size_t)t]) diff_band(sh_data.data() + sh_off[(size_t)t], sh_dim1[(size_t)t], &sh_lo[(size_t)t], &sh_hi[(size_t)t]);
+      sh_shift_ref[(size_t)t] = 1;
     }
     if (f_type[f] < 0 || f_type[f] >= n_ftypes) fail("factor " + std::to_string(f) + ": type out of range");
     if (f_dim0[f] <= 0 || (f_kind[f] == LPMP_F_PAIRWISE_DENSE && f_dim1[f] <= 0)) fail("factor " + std::to_string(f) + ": bad dimension");
@@ -945,8 +956,8 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
       out.recs[cur[key(u)]++] = r;
     }
   }
-  out.diff_tab_off.assign(1, 0); out.diff_tab.clear();
-  std::vector<uint8_t> diff_seen((size_t)p.n_shared, 0);
+  out.diff_tab_off.assign(1, 0); out.diff_tab.clear(); out.diff_tab_ne.clear();
+  std::vector<int32_t> diff_seen((size_t)p.n_shared, 0);   // 0, or the smallest d0 + d1 - 1 among the launch's references so far
   for (int64_t k = 0; k < n_keys; ++k) {
     LevelRange lr;
     lr.kclass = key_class[k]; lr.begin = key_count[k]; lr.end = key_count[k + 1];
@@ -961,19 +972,22 @@ void bucket(const Plan& p, Updates& U, const OpVec& ops, Schedule& out) {
         const UpdRec& r = out.recs[(size_t)i];
         const Op* o = ops.data() + r.op_begin;
         const int n_ops = lr.n_recv > 0 ? r.n_recv : r.n_send;
-        // a DIFF_SHIFT peer anywhere in the launch (receive or send): the shifted kernel, which is never banded
+        // a DIFF_SHIFT peer anywhere in the launch (receive or send): a shifted kernel (banded by the rule of its own, below)
         for (int q = 0; q < r.n_recv + r.n_send && !lr.diff_shift; ++q) lr.diff_shift = p.f_kind[(size_t)o[q].peer] == LPMP_F_PAIRWISE_DIFF_SHIFT;
         for (int q = 0; q < n_ops; ++q) {
           const int32_t t = p.f_table[(size_t)o[q].peer];
-          if (!diff_seen[(size_t)t]) { diff_seen[(size_t)t] = 1; out.diff_tab.push_back(t); }
+          const int32_t ne = p.f_dim0[(size_t)o[q].peer] + p.f_dim1[(size_t)o[q].peer] - 1;
+          if (!diff_seen[(size_t)t]) { diff_seen[(size_t)t] = ne; out.diff_tab.push_back(t); }
+          else diff_seen[(size_t)t] = std::min(diff_seen[(size_t)t], ne);
         }
       }
       const int32_t t0 = out.diff_tab_off.back();
-      for (size_t j = (size_t)t0; j < out.diff_tab.size(); ++j) diff_seen[(size_t)out.diff_tab[j]] = 0;
       std::sort(out.diff_tab.begin() + t0, out.diff_tab.end());
+      for (size_t j = (size_t)t0; j < out.diff_tab.size(); ++j) { out.diff_tab_ne.push_back(diff_seen[(size_t)out.diff_tab[j]]); diff_seen[(size_t)out.diff_tab[j]] = 0; }
       lr.diff_row = (int32_t)out.diff_tab_off.size() - 1;
       out.diff_tab_off.push_back((int32_t)out.diff_tab.size());
       lr.diff_band = !lr.diff_shift && p.diff_launch_banded(out.diff_tab.data() + t0, (int64_t)out.diff_tab.size() - t0);
+      lr.diff_shift_band = lr.diff_shift && p.diff_launch_shift_banded(out.diff_tab.data() + t0, out.diff_tab_ne.data() + t0, (int64_t)out.diff_tab.size() - t0);
     }
     if (!kc_is_shared(lr.kclass)) { out.launches.push_back(lr); continue; }
     // a shared class: one launch per table-set group of the records (classify), each with the list of its distinct tables

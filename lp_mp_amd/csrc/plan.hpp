@@ -105,6 +105,11 @@ constexpr int BIG_MAX_LABELS = 512;
 // whose receives all reference banded vectors runs sweep_diff_band_kernel: the window and two tail terms instead of all pairs.
 constexpr int DIFF_BAND_DIV = 4;
 constexpr bool diff_band_rule(int64_t lo, int64_t hi, int64_t n) { return (hi - lo + 1) * DIFF_BAND_DIV <= n; }
+// A DIFF_SHIFT receive (dims d0 x d1, pool vector D of any n entries, shift s) expands D over i = a - b + d1 - 1 in [0, ne),
+// ne = d0 + d1 - 1, as D[clamp(i - off, 0, n - 1)], off = d1 - 1 - s: the band of D moved by off and clipped to [0, ne), the clamp
+// continuing the two tails.  The shift moves the band and never widens it, so the rule reads the width of D's OWN band against ne
+// and stays a function of structure and pool values: diff_band_rule(lo, hi, ne).  A launch with a DIFF_SHIFT peer whose receives
+// all pass it runs sweep_diff_shift_band_kernel (a plain DIFF peer beside them is the case n = ne, off = 0: its own rule).
 constexpr int SMALL_MAXD = 8;
 constexpr int PW_MAX_OPS = 6;
 constexpr bool kc_is_pw(int kclass) { return kclass >= KC_PW_4 && kclass <= KC_PW_32; }
@@ -139,9 +144,13 @@ struct LevelRange {            // one kernel launch: a range of UpdRec indices o
   int32_t n_sh = 0; int32_t sh_tab[SHARED_MAX_TABLES] = {};
   // class diff: every receive of every record references a banded vector (cleared by LPMP_NO_DIFF_BAND): the banded kernel
   bool diff_band = false;
-  // class diff: a record of the launch has a DIFF_SHIFT peer (LPMP_F_PAIRWISE_DIFF_SHIFT): sweep_diff_shift_kernel, never banded —
-  // structure, so new pool values (Plan::refresh_diff_band) leave it alone
+  // class diff: a record of the launch has a DIFF_SHIFT peer (LPMP_F_PAIRWISE_DIFF_SHIFT): one of the two shifted kernels, never
+  // sweep_diff_band_kernel — structure, so new pool values (Plan::refresh_diff_band) leave it alone
   bool diff_shift = false;
+  // class diff, diff_shift: every receive of every record passes the shifted rule (diff_band_rule above against the receive's
+  // d0 + d1 - 1; cleared by LPMP_NO_DIFF_BAND): sweep_diff_shift_band_kernel, otherwise sweep_diff_shift_kernel.  Pool values
+  // and structure decide it, never a shift
+  bool diff_shift_band = false;
   // class diff: the launch's row of Schedule::diff_tab_off — the pool entries diff_band was decided from (-1: another class)
   int32_t diff_row = -1;
 };
@@ -267,8 +276,10 @@ struct Schedule {             // executable form of one (factor list, omega, mas
   std::vector<int32_t> plain_launches;
   // per KC_DIFF launch (LevelRange::diff_row, CSR): the distinct pool entries that decide its kernel — those of its receives, of its
   // sends where it has no receive.  All a schedule keeps of the pool's VALUES is diff_band of those launches, and with this list
-  // Plan::refresh_diff_band sets it again from new values without the records and ops (which the engine does not keep on the host)
-  std::vector<int32_t> diff_tab_off, diff_tab;
+  // Plan::refresh_diff_band sets it again from new values without the records and ops (which the engine does not keep on the host).
+  // diff_tab_ne, beside every entry of diff_tab: the smallest d0 + d1 - 1 among those receives (sends) of the launch that reference
+  // the pool entry — what the shifted rule holds the width of the entry's band against (LevelRange::diff_shift_band)
+  std::vector<int32_t> diff_tab_off, diff_tab, diff_tab_ne;
 };
 
 // Conditional rounding from the duals (lpmp_decode_primal): the structure of a decode in one direction.  Every vector
@@ -302,9 +313,10 @@ struct Plan {
   int32_t n_shared = 0;
   std::vector<int64_t> sh_off; std::vector<int32_t> sh_dim0, sh_dim1; std::vector<double> sh_data;
   std::vector<int32_t> f_table;
-  // per pool entry a DIFF factor references: the band [sh_lo, sh_hi] of its vector (diff_band below) and whether the rule holds
-  // (sh_banded: 0 / 1; -1: no DIFF factor references the entry)
-  std::vector<int32_t> sh_lo, sh_hi; std::vector<int8_t> sh_banded;
+  // per pool entry a DIFF or DIFF_SHIFT factor references: the band [sh_lo, sh_hi] of its vector (diff_band below).  sh_banded:
+  // whether the plain rule holds (0 / 1; -1: no DIFF factor references the entry — a DIFF_SHIFT factor does not count, its rule
+  // depends on the receive: diff_launch_shift_banded).  sh_shift_ref: a DIFF_SHIFT factor references the entry
+  std::vector<int32_t> sh_lo, sh_hi; std::vector<int8_t> sh_banded; std::vector<uint8_t> sh_shift_ref;
   bool no_diff_band = false;     // LPMP_NO_DIFF_BAND set when the plan was built: no launch gets LevelRange::diff_band
   std::vector<int32_t> m_type, m_left, m_right;
   double constant = 0;
@@ -344,13 +356,21 @@ struct Plan {
   // throws std::runtime_error on invalid input (the reference throws too, LP_MP.h:458)
   void build(const lpmp_model& m);
   // New VALUES for the pool (same entries, offsets and dims; packed as lpmp_model.sh_data).  A NaN entry is refused with nothing
-  // changed.  Of the plan, only sh_data and the band of every entry a DIFF factor references (sh_lo / sh_hi / sh_banded) read a
-  // pool value; of a schedule, only diff_band of its KC_DIFF launches: refresh_diff_band sets those again, for the launches of a
-  // schedule or of any copy of them (tabs_off / tabs: the schedule's diff_tab_off / diff_tab).  Returns whether a launch changed.
+  // changed.  Of the plan, only sh_data and the band of every entry a DIFF or DIFF_SHIFT factor references (sh_lo / sh_hi /
+  // sh_banded) read a pool value; of a schedule, only diff_band and diff_shift_band of its KC_DIFF launches: refresh_diff_band sets
+  // those again, for the launches of a schedule or of any copy of them (tabs_off / tabs / tabs_ne: the schedule's diff_tab_off /
+  // diff_tab / diff_tab_ne).  Returns whether a launch changed.
   void set_shared_pool(const double* values);
   // the banded kernel for a KC_DIFF launch: only if every one of these pool entries (Schedule::diff_tab) holds a banded vector
   bool diff_launch_banded(const int32_t* tabs, int64_t n) const;
-  bool refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs) const;
+  // ... and for one with a DIFF_SHIFT peer: only if the band of every entry passes the rule against its ne (Schedule::diff_tab_ne)
+  bool diff_launch_shift_banded(const int32_t* tabs, const int32_t* ne, int64_t n) const;
+  bool refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs,
+                         const std::vector<int32_t>& tabs_ne) const;
+  // (without the ne row a launch with a DIFF_SHIFT factor goes to the full shifted kernel, which is correct for every vector)
+  bool refresh_diff_band(std::vector<LevelRange>& launches, const std::vector<int32_t>& tabs_off, const std::vector<int32_t>& tabs) const {
+    return refresh_diff_band(launches, tabs_off, tabs, std::vector<int32_t>());
+  }
   void ensure_weights(int mode);
   void anisotropic_weights(const int32_t* list, int64_t n, Csr<double>& om, Csr<uint8_t>& mk) const;
   // one sweep: a factor list with one omega row and one receive-mask row per listed factor

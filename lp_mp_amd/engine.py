@@ -73,6 +73,7 @@ EXPORTS = [
     "lpmp_plan_suggest_order", "lpmp_graph_colour_major_order", "lpmp_graph_refine_partition",
     "lpmp_set_table_precision", "lpmp_table_precision", "lpmp_plan_set_table_precision",
     "lpmp_plan_n_shared_tables", "lpmp_plan_get_diff_band", "lpmp_plan_diff_band_info", "lpmp_get_diff_band_launches", "lpmp_get_diff_shift_launches",
+    "lpmp_plan_get_diff_shift_band", "lpmp_plan_diff_shift_band_info", "lpmp_get_diff_shift_band_launches",
     "lpmp_upload_costs", "lpmp_set_vectors", "lpmp_zero_pairwise_duals", "lpmp_schedules_built",
     "lpmp_plan_set_shared_pool", "lpmp_upload_shared_pool", "lpmp_set_constants",
     "lpmp_plan_peer_minima", "lpmp_get_peer_minima_launches",
@@ -194,6 +195,10 @@ def lib():
             L.lpmp_get_diff_band_launches.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "lpmp_get_diff_shift_launches"):   # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
             L.lpmp_get_diff_shift_launches.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "lpmp_plan_get_diff_shift_band"):   # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_plan_get_diff_shift_band.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+            L.lpmp_plan_diff_shift_band_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+            L.lpmp_get_diff_shift_band_launches.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "lpmp_plan_peer_minima"):      # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
             L.lpmp_plan_peer_minima.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
             L.lpmp_get_peer_minima_launches.argtypes = [C.c_void_p, C.c_void_p]
@@ -394,6 +399,25 @@ def _diff_band_info(self, d: int, mode: int) -> dict:
     return dict(zip(("diff_launches", "band_launches", "diff_receives", "band_receives"), [x.value for x in v]))
 
 
+def _diff_shift_bands(self) -> dict:
+    """{pool entry: (lo, hi)} for every entry a DIFF_SHIFT factor references: the band of the vector itself, as ``model.diff_band``
+    states it.  Whether a receive is banded depends on its dims too (``model.diff_shift_is_banded``), never on its shift"""
+    out = {}
+    for t in range(self.L.lpmp_plan_n_shared_tables(self.h)):
+        lo, hi, ref = C.c_int32(), C.c_int32(), C.c_int()
+        _chk(self.L.lpmp_plan_get_diff_shift_band(self.h, t, C.addressof(lo), C.addressof(hi), C.addressof(ref)))
+        if ref.value:
+            out[t] = (lo.value, hi.value)
+    return out
+
+
+def _diff_shift_band_info(self, d: int, mode: int) -> dict:
+    """launches / receives of class diff with a DIFF_SHIFT factor in the sweep, and how many of them run the shifted banded kernel"""
+    v = [C.c_int64() for _ in range(4)]
+    _chk(self.L.lpmp_plan_diff_shift_band_info(self.h, d, mode, *[C.addressof(x) for x in v]))
+    return dict(zip(("shift_launches", "shift_band_launches", "shift_receives", "shift_band_receives"), [x.value for x in v]))
+
+
 def _set_shared_pool(self, sh_data):
     """new VALUES for the pool of this plan (lpmp_plan_set_shared_pool): ``sh_data`` packed as ``FlatModel.sh_data``.  The bands of
     the DIFF vectors and the kernel choice of every cached launch of class diff follow; nothing else of a schedule moves.  None is
@@ -409,6 +433,8 @@ def _set_shared_pool(self, sh_data):
 Plan.set_shared_pool = _set_shared_pool
 Plan.diff_bands = _diff_bands
 Plan.diff_band_info = _diff_band_info
+Plan.diff_shift_bands = _diff_shift_bands
+Plan.diff_shift_band_info = _diff_shift_band_info
 
 
 def _pass_info(self, mode: int) -> dict:
@@ -982,12 +1008,17 @@ class Engine:
                     if nb.value == arrs[0][c]:
                         out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_band_kernel"
                     if hasattr(self.L, "lpmp_get_diff_shift_launches"):
-                        # launches that touch a DIFF_SHIFT factor run the shifted kernel (never banded); the name as above
+                        # launches that touch a DIFF_SHIFT factor run one of the two shifted kernels; the name as above, whichever
+                        # of them ran: shift_band_launches tells sweep_diff_shift_band_kernel from sweep_diff_shift_kernel
                         ns = C.c_int64()
                         _chk(self.L.lpmp_get_diff_shift_launches(self.h, C.addressof(ns)))
                         out[KCLASS_NAMES[c]]["shift_launches"] = ns.value
                         if ns.value == arrs[0][c]:
                             out[KCLASS_NAMES[c]]["kernel"] = "sweep_diff_shift_kernel"
+                        if hasattr(self.L, "lpmp_get_diff_shift_band_launches"):
+                            nsb = C.c_int64()
+                            _chk(self.L.lpmp_get_diff_shift_band_launches(self.h, C.addressof(nsb)))
+                            out[KCLASS_NAMES[c]]["shift_band_launches"] = nsb.value
         return out
 
 

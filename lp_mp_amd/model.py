@@ -549,6 +549,25 @@ def diff_band_is_banded(D) -> bool:
     return (hi - lo + 1) * DIFF_BAND_DIV <= np.asarray(D).size
 
 
+def diff_shift_band(D, d0: int, d1: int, shift) -> tuple:
+    """the band (le, he) of a DIFF_SHIFT receive: of the expansion D[clip(i - off, 0, n - 1)], i = a - b + d1 - 1 in [0, d0 + d1 - 1),
+    off = d1 - 1 - diff_shift_int(shift).  The band (lo, hi) of D moved by off and clipped to the expansion: every entry below le is
+    D[0], every entry above he is D[n - 1], entry i in [le, he] is D[i - off]; he >= le - 1.  (kernels.hip, sweep_diff_shift_band_kernel.)
+    Where an end of the expansion falls inside the band, le / he is that end and not the first / last entry that differs from it:
+    a bound of the band, which is all the reduction needs"""
+    lo, hi = diff_band(D)
+    ne = d0 + d1 - 1
+    off = d1 - 1 - diff_shift_int(shift)
+    return min(max(lo + off, 0), ne), min(max(hi + off, -1), ne - 1)
+
+
+def diff_shift_is_banded(D, d0: int, d1: int) -> bool:
+    """the rule of the shifted banded kernel for a d0 x d1 receive: the band of D itself has at most (d0 + d1 - 1) / DIFF_BAND_DIV
+    entries.  The shift moves the band and never widens it: it is not an argument"""
+    lo, hi = diff_band(D)
+    return (hi - lo + 1) * DIFF_BAND_DIV <= d0 + d1 - 1
+
+
 class ModelBuilder:
     """Collects factors / messages / relations in insertion order (bulk or one at a time)."""
 

@@ -4,6 +4,7 @@ device is an error.
 
     python tools/diff_shift_probe.py --compare --grid 512 --labels 128 --warmup 5 --steps 20 --repeat 5
     python tools/diff_shift_probe.py --two-level --grid 256 --full-labels 256 --window 32 --passes 30 [--full]
+    python tools/diff_shift_probe.py --windows --grid 512 --labels 128 --trunc-labels 2 --warmup 5 --steps 20 --repeat 1
 
 --compare: a grid of DIFF_SHIFT factors with a random shift per edge against the plain DIFF grid of the same size, labels, vectors
 (random ones: the plain grid runs the full kernel, not the banded one) and scales, two engines side by side, repetitions
@@ -13,6 +14,12 @@ grid's after the same passes (duals_equal_degenerate).
 -> a window of WINDOW labels per variable around its coarse estimate -> the DIFF_SHIFT model on the compact truncated-linear
 vector -> decode_primal.  Reports the times and the energy of the final labelling evaluated on the full-range model (numpy, on
 the host); --full also solves the full-range DIFF model for the same number of passes.
+--windows: one level of a coarse-to-fine run on its own: a grid of DIFF_SHIFT factors over windows of LABELS labels around random
+centres, on the compact truncated-linear vector of 2 TRUNC_LABELS + 1 entries (--trunc-labels K; or, with --band-width W, on a
+vector whose band has W random entries between two unequal tails).  Such windows run sweep_diff_shift_band_kernel where the rule
+admits the band ((W or 2 K - 1) * 4 <= 2 LABELS - 1) and sweep_diff_shift_kernel under LPMP_NO_DIFF_BAND=1 or with a library from
+before the banded form (LPMP_ENGINE_SO): one process per run for an A/B.  Reports ms per pass, the kernels that ran and a digest
+of the duals (two runs of one model: equal digests = equal bits).
 Prints one JSON line."""
 from __future__ import annotations
 
@@ -86,6 +93,44 @@ def compare(a, out) -> int:
     out["duals_equal_degenerate"] = bool(np.array_equal(d[0], d[1]))
     eng["diff"].close()
     return 0 if out["duals_equal_degenerate"] else 1
+
+
+def windows(a, out) -> int:
+    from lp_mp_amd import build as B, model as M, synthetic as S
+    from lp_mp_amd.engine import Engine
+    mode = M.REPAM_NAMES[a.mode]
+    G, L = a.grid, a.labels
+    n = G * G
+    var = S.grid_variable_order(G, G, a.order).reshape(-1)
+    ga, gb = S.grid_edges(G, G)
+    ei, ej = np.minimum(var[ga], var[gb]), np.maximum(var[ga], var[gb])
+    E = ei.shape[0]
+    rng = np.random.default_rng(a.seed)
+    if a.band_width is None:
+        Dv, zero = M.truncated_linear_compact(a.slope, a.slope * a.trunc_labels)
+    else:
+        W = a.band_width
+        Dv = np.concatenate([np.full(3, 2.0), rng.uniform(0.05, 1.0, W), np.full(3, 1.5)])
+        zero = 3 + W // 2
+    centres = rng.integers(0, max(1, a.centre_spread) + 1, n)      # neighbouring windows overlap: most bands lie inside the receive
+    shifts = M.window_shift(centres[ei], centres[ej], zero)
+    m = S.grid_model(G, G, L, pairwise="diff_shift", order=a.order, seed=a.seed, diff_tables=[Dv], shifts=shifts)
+    lo, hi = M.diff_band(Dv)
+    e = Engine(0)
+    e.upload(m); e.set_reparametrization(mode); e.prepare_passes(a.steps)
+    info = e.plan.pass_schedule_info(mode)
+    out.update(labels=L, vector_entries=int(Dv.shape[0]), band=[lo, hi], band_width=hi - lo + 1, rule_admits=bool((hi - lo + 1) * M.DIFF_BAND_DIV <= 2 * L - 1),
+               no_diff_band=os.environ.get("LPMP_NO_DIFF_BAND") is not None, library=os.environ.get("LPMP_ENGINE_SO", "tree"),
+               library_source_hash=B.source_hash(), classes_forward=e.plan.schedule_classes(0, mode), n_launches_per_pass=int(info["n_launches"]),
+               algorithmic_bytes_per_pass=int(info["algorithmic_bytes"]))
+    if hasattr(e.L, "lpmp_plan_diff_shift_band_info"):      # (absent in a library from before the banded form)
+        out["diff_shift_band_info"] = e.plan.diff_shift_band_info(0, mode)
+    out["ms_per_pass"] = [timed(e, a.warmup, a.steps) for _ in range(a.repeat)]
+    out["lower_bound"] = e.lower_bound()
+    out["duals_sha256"] = hashlib.sha256(e.download_duals().tobytes()).hexdigest()
+    out["kernel_timing"] = kernel_times(e, a.steps)
+    e.close()
+    return 0
 
 
 def energy(un, ei, ej, scales, labels, slope, trunc) -> float:
@@ -165,6 +210,9 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--compare", action="store_true")
     ap.add_argument("--two-level", action="store_true")
+    ap.add_argument("--windows", action="store_true")
+    ap.add_argument("--band-width", type=int, default=None, help="windows: a vector with a band of that many random entries instead of the truncated-linear one")
+    ap.add_argument("--centre-spread", type=int, default=8, help="windows: the window centres are uniform in [0, SPREAD]")
     ap.add_argument("--grid", type=int, default=512, help="the grid is GRID x GRID")
     ap.add_argument("--labels", type=int, default=128)
     ap.add_argument("--tables", type=int, default=2)
@@ -176,7 +224,7 @@ def main() -> int:
     ap.add_argument("--stride", type=int, default=8, help="fine labels per coarse label")
     ap.add_argument("--passes", type=int, default=30)
     ap.add_argument("--slope", type=float, default=0.05)
-    ap.add_argument("--trunc-labels", type=int, default=12)
+    ap.add_argument("--trunc-labels", type=int, default=12, help="the truncated-linear potential is cut at that many labels (two-level, windows)")
     ap.add_argument("--full", action="store_true", help="two-level: also solve the full-range DIFF model")
     ap.add_argument("--order", default="colour_major", choices=["colour_major", "row_major"])
     ap.add_argument("--mode", default="anisotropic", choices=["anisotropic", "anisotropic2", "uniform", "damped_uniform"])
@@ -186,10 +234,11 @@ def main() -> int:
     if not torch.cuda.is_available():
         print("diff_shift_probe: no GPU", file=sys.stderr)
         return 2
-    if a.compare == a.two_level:
-        ap.error("one of --compare / --two-level")
-    out = dict(mode_of_run="compare" if a.compare else "two-level", grid=a.grid, order=a.order, mode=a.mode, device=torch.cuda.get_device_name(0))
-    rc = compare(a, out) if a.compare else two_level(a, out)
+    if a.compare + a.two_level + a.windows != 1:
+        ap.error("one of --compare / --two-level / --windows")
+    out = dict(mode_of_run="compare" if a.compare else "two-level" if a.two_level else "windows", grid=a.grid, order=a.order, mode=a.mode,
+               device=torch.cuda.get_device_name(0))
+    rc = compare(a, out) if a.compare else two_level(a, out) if a.two_level else windows(a, out)
     print(json.dumps(out))
     return rc
 
