@@ -417,6 +417,78 @@ int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_m
 int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
 int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
 
+/* ---- path moves: exact relabelling of whole paths given all other labels ------------------------------------------
+ * Block coordinate descent on the labels: take a path of the graph (a row or a column of a grid), keep every other label, and give
+ * the path the labels that minimise the energy over it, by dynamic programming.  Reads the duals, the constants and the primal
+ * array, writes only the primal array that lpmp_download_primal / lpmp_evaluate_primal / lpmp_readout_labels read.  No counterpart
+ * in the reference.
+ *
+ * A path set is a prepared object like an lpmp_readout or an lpmp_window_set.  It holds n_groups groups; group g is the paths
+ * [group_off[g], group_off[g+1]); path j is the entries [path_off[j], path_off[j+1]) of `unaries`: k >= 1 distinct VECTOR factors
+ * u_0 ... u_{k-1} of the uploaded model.  Consecutive members are joined by exactly one pairwise factor e_i between u_i and
+ * u_{i+1}, the path edge; the engine finds it.  A unary may appear in several groups (rows and columns), never twice in one.
+ *
+ * lpmp_path_moves runs the groups in the given order, `rounds` times.  The paths of a group are independent (no pairwise factor
+ * joins two of them) and run concurrently.  For one path, with x_v the label unary v holds in the primal array:
+ *   node cost   n_i[x] = theta_{u_i}[x]                                  (the current dual)
+ *               for every message of u_i, in ascending MESSAGE INDEX as in lpmp_decode_primal; p its pairwise factor, s the side
+ *               of u_i in p, v the unary on the other side:
+ *                   p is e_{i-1} or e_i:   n_i[x] = n_i[x] + m_s[x]
+ *                   otherwise:             n_i[x] = n_i[x] + (t[x] + m_s[x]),  t[x] = cost_p(x, x_v) if s == 0 else cost_p(x_v, x)
+ *               (m_s: p's dual vector of side s; the inner sum first).  x_v is clamped into [0, d_v - 1] where it is read, as the
+ *               decode kernel does: a neighbour without a label is outside the energy guarantee, but no bit pattern reads
+ *               outside a table.
+ *   forward     f_0 = n_0;  for i >= 1:  g_i[y] = min_x (f_{i-1}[x] + c_i(x, y)),  back_i[y] = the smallest minimising x,
+ *               f_i[y] = g_i[y] + n_i[y],  with c_i(x, y) = cost_{e_{i-1}}(x, y) when u_{i-1} is on side 0 of the edge and
+ *               cost_{e_{i-1}}(y, x) otherwise
+ *   backwards   x_{k-1} = the smallest minimiser of f_{k-1};  x_{i-1} = back_i[x_i].  The new labels go to the primal array.
+ * cost_p is the pairwise cost of lpmp_model.h as in lpmp_decode_primal (ONE multiply for SHARED / DIFF / DIFF_SHIFT, floats widened
+ * under the f32 table modes).  All arithmetic is IEEE double in this order, no contraction.  +inf entries are allowed (an all +inf
+ * column: back-pointer 0; an all +inf f_{k-1}: label 0); NaN is outside the contract.  After the last group of the last round both
+ * slots of every pairwise factor take the labels of its unaries, as after a decode.
+ * The sum of n_i[x_i] over the path plus the sum of c_{i+1}(x_i, x_{i+1}) is every term of the energy that depends on the path's
+ * labels, written with theta_u + sum m_s as the unaries (the original unaries up to rounding): on a complete labelling
+ * the primal cost never rises over a path, a group or a round.  A path of one member is one step of the decode's refinement sweep;
+ * a path that is the whole of a chain model gives the optimum whatever the duals are.
+ *
+ * lpmp_path_set_create: LPMP_ERR_STATE before lpmp_upload_model.  Checked in this order, the first failure reported:
+ *   LPMP_ERR_INVALID, naming the entry: offsets that are not monotone (group_off[0] and path_off[0] are 0; a path has at least one
+ *     member); an index out of range or a non-VECTOR factor; a unary that appears twice in one group, in one path or in two;
+ *   LPMP_ERR_UNSUPPORTED, naming the lowest offending listed unary u: a message of u that is not LPMP_M_UNARY_PAIRWISE with u as
+ *     its left factor; an adjacent pairwise factor that does not have exactly one unary on each side, from two different unaries;
+ *     more than 512 labels;
+ *   LPMP_ERR_INVALID, naming the entries: consecutive members joined by no pairwise factor, or by more than one; a pairwise factor
+ *     that joins two non-consecutive members of one path (a closed ring included), or members of two paths of one group.
+ * Unlisted parts of the model may be anything.  On a model the rounding code refuses (a message of another kind off the paths) the
+ * primal array is the array of unset labels lpmp_readout_labels makes: the paths' unaries get labels, no pairwise slot is written.
+ * At create the record / link / edge tables and the back-pointer scratch are built and uploaded — the scratch holds the
+ * back-pointers of the largest group, one byte per entry where the previous member has at most 256 labels, two above
+ * (lpmp_path_set_scratch_bytes) — and lpmp_schedules_built counts the create ONCE; a move plans and uploads nothing.  n_groups == 0
+ * or groups without paths: a set whose moves are no-ops after their checks.
+ * The set is structure: it stays valid across lpmp_upload_costs, lpmp_set_vectors, lpmp_upload_shared_pool, lpmp_set_constants,
+ * lpmp_move_windows, lpmp_zero_pairwise_duals, passes and decodes; after the next lpmp_upload_model every move on it returns
+ * LPMP_ERR_STATE (destroying it stays legal); lpmp_destroy does not free it.
+ *
+ * lpmp_path_moves settles passes that ran ahead first, needs specified constants (LPMP_ERR_STATE while they are not, as the
+ * decode), allocates the primal array on first use, and is asynchronous on the engine's stream: one plain launch per group, form
+ * (a wave per path while no member has more than 64 labels, a workgroup per path above) and round.  Duals, tracked bounds,
+ * weights, schedules, kernel timing and speculation depth do not move.  rounds < 0: LPMP_ERR_INVALID; rounds == 0: a no-op after
+ * the checks.  Works under the rows layout and both f32 table modes. */
+typedef struct lpmp_path_set lpmp_path_set;
+int lpmp_path_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off /* [n_groups + 1], in paths */,
+                         const int64_t* path_off /* [n_paths + 1], in entries */, const int32_t* unaries, lpmp_path_set** out);
+void lpmp_path_set_destroy(lpmp_path_set* ps);
+int64_t lpmp_path_set_n_groups(const lpmp_path_set* ps);
+int64_t lpmp_path_set_n_paths(const lpmp_path_set* ps);
+int64_t lpmp_path_set_longest(const lpmp_path_set* ps);        /* members of the longest path */
+int64_t lpmp_path_set_scratch_bytes(const lpmp_path_set* ps);
+int lpmp_path_moves(lpmp_engine* e, lpmp_path_set* ps, int rounds);
+/* host only: the checks of lpmp_path_set_create on a plan, and the counts: paths, path edges (sum of k - 1), links of listed unaries
+ * that are no path edge (one cost line each per move; a unary listed in two groups counts in both).  Any pointer may be NULL; on
+ * failure `why` (why_n bytes) receives the message of lpmp_last_error. */
+int lpmp_plan_path_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries,
+                        int64_t* n_paths, int64_t* n_path_edges, int64_t* n_off_path_links, char* why, int why_n);
+
 int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);

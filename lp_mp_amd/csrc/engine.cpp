@@ -2468,6 +2468,136 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
   });
 }
 
+// ---- path moves: exact relabelling of whole paths given all other labels (include/lpmp_engine.h) ----------------------
+// A prepared object like lpmp_readout: the planner's checks and path edges (plan.cpp, path_plan), then the device records with the
+// offsets of the uploaded model (rows layout, float tables and SHARED / DIFF cells are all behind Plan::doff / coff, as in
+// ensure_decode) and the back-pointer scratch, all uploaded at create.  A move plans and uploads nothing.
+struct lpmp_path_set {
+  int device = 0;
+  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
+  int64_t n_groups = 0, n_paths = 0, longest = 0, scratch_bytes = 0;
+  DevBuf<PathRec> paths; DevBuf<PathNode> nodes; DevBuf<PathLink> links;
+  DevBuf<unsigned char> back;           // back-pointers of one group at a time (launches on one stream follow each other)
+  struct Launch { int64_t first, count; int32_t wide, group; };   // per group: its paths of the wave form, then those of the workgroup form
+  std::vector<Launch> launches;
+};
+
+static PathPlan path_plan_or_refuse(const Plan& p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, const std::string& who) {
+  PathPlan pp = p.path_plan(n_groups, group_off, path_off, unaries, who);
+  if (!pp.why.empty()) throw UnsupportedError(pp.why);
+  return pp;
+}
+
+int lpmp_plan_path_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries,
+                        int64_t* n_paths, int64_t* n_path_edges, int64_t* n_off_path_links, char* why, int why_n) {
+  if (why && why_n > 0) why[0] = 0;
+  const int rc = guarded([&] {
+    if (!p) throw std::runtime_error("lpmp_plan_path_info: bad argument");
+    const PathPlan pp = path_plan_or_refuse(p->p, n_groups, group_off, path_off, unaries, "lpmp_plan_path_info");
+    if (n_paths) *n_paths = (int64_t)pp.path_off.size() - 1;
+    if (n_path_edges) *n_path_edges = pp.n_path_edges;
+    if (n_off_path_links) *n_off_path_links = pp.n_off_path_links;
+  });
+  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
+  return rc;
+}
+
+int lpmp_path_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, lpmp_path_set** out) {
+  return guarded([&] {
+    if (!e || !e->model.plan) throw StateError("lpmp_path_set_create: no model uploaded (a path set lists factors of the uploaded model)");
+    if (!out) throw std::runtime_error("lpmp_path_set_create: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    ModelState& m = e->model;
+    const Plan& p = m.plan->p;
+    const PathPlan pp = path_plan_or_refuse(p, n_groups, group_off, path_off, unaries, "lpmp_path_set_create");
+    auto ps = std::make_unique<lpmp_path_set>();
+    ps->device = e->device; ps->gen = m.model_gen;
+    ps->n_groups = n_groups; ps->n_paths = (int64_t)pp.path_off.size() - 1; ps->longest = pp.longest;
+    const size_t ne = pp.unaries.size();
+    std::vector<PathRec> paths; paths.reserve((size_t)ps->n_paths);
+    std::vector<PathNode> nodes(ne);
+    std::vector<PathLink> links(pp.links.size());
+    for (size_t k = 0; k < links.size(); ++k) {
+      const PathLinkPlan& l = pp.links[k];
+      links[k] = {p.doff(l.p) + (l.side ? p.f_dim0[l.p] : 0), p.coff(l.p), p.f_kind[l.p], p.f_dim1[l.p], l.side, l.other, p.f_dim0[l.other], l.on_path};
+    }
+    for (int64_t g = 0; g < n_groups; ++g) {
+      int64_t bytes = 0;                // of this group's back-pointers: d0 entries per node behind the first of its path
+      std::vector<int64_t> form[2];     // the group's paths by form
+      for (int64_t j = pp.group_off[(size_t)g]; j < pp.group_off[(size_t)g + 1]; ++j) {
+        int32_t widest = 0;
+        for (int64_t en = pp.path_off[(size_t)j]; en < pp.path_off[(size_t)j + 1]; ++en) {
+          const int32_t u = pp.unaries[(size_t)en], d = p.f_dim0[u], pw = pp.edge[(size_t)en];
+          if (d < 1) throw std::runtime_error("lpmp_path_set_create: factor " + std::to_string(u) + " (entry " + std::to_string(en) + ") has no label");
+          widest = std::max(widest, d);
+          PathNode nd{p.doff(u), 0, 0, d, u, (int32_t)pp.link_off[(size_t)en], (int32_t)(pp.link_off[(size_t)en + 1] - pp.link_off[(size_t)en]), -1, 0, 0, 0};
+          if (pw >= 0) {
+            const int32_t dprev = p.f_dim0[pp.unaries[(size_t)en - 1]];
+            nd.edge_const = p.coff(pw); nd.edge_kind = p.f_kind[pw]; nd.edge_d1 = p.f_dim1[pw]; nd.edge_prev_side = pp.edge_prev_side[(size_t)en];
+            nd.back_wide = dprev > 256 ? 1 : 0;
+            bytes = (bytes + nd.back_wide) & ~(int64_t)nd.back_wide;      // (two-byte entries start at an even byte)
+            nd.back_off = bytes;
+            bytes += (int64_t)d * (nd.back_wide ? 2 : 1);
+          }
+          nodes[(size_t)en] = nd;
+        }
+        form[widest > PATH_WAVE_MAX ? 1 : 0].push_back(j);
+      }
+      ps->scratch_bytes = std::max(ps->scratch_bytes, bytes);
+      for (int w = 0; w < 2; ++w) {
+        if (form[w].empty()) continue;
+        ps->launches.push_back({(int64_t)paths.size(), (int64_t)form[w].size(), w, (int32_t)g});
+        for (int64_t j : form[w]) paths.push_back({pp.path_off[(size_t)j], (int32_t)(pp.path_off[(size_t)j + 1] - pp.path_off[(size_t)j]), 0});
+      }
+    }
+    if (!paths.empty()) { ps->paths.alloc(paths.size()); h2d(ps->paths, paths.data(), paths.size() * sizeof(PathRec), e->stream); }
+    if (!nodes.empty()) { ps->nodes.alloc(nodes.size()); h2d(ps->nodes, nodes.data(), nodes.size() * sizeof(PathNode), e->stream); }
+    if (!links.empty()) { ps->links.alloc(links.size()); h2d(ps->links, links.data(), links.size() * sizeof(PathLink), e->stream); }
+    if (ps->scratch_bytes > 0) ps->back.alloc((size_t)ps->scratch_bytes);
+    ++m.schedules_built;   // the record tables: structure, like a schedule, counted once
+    *out = ps.release();
+  });
+}
+void lpmp_path_set_destroy(lpmp_path_set* ps) {
+  if (!ps) return;
+  (void)hipSetDevice(ps->device);
+  delete ps;
+}
+int64_t lpmp_path_set_n_groups(const lpmp_path_set* ps) { return ps ? ps->n_groups : 0; }
+int64_t lpmp_path_set_n_paths(const lpmp_path_set* ps) { return ps ? ps->n_paths : 0; }
+int64_t lpmp_path_set_longest(const lpmp_path_set* ps) { return ps ? ps->longest : 0; }
+int64_t lpmp_path_set_scratch_bytes(const lpmp_path_set* ps) { return ps ? ps->scratch_bytes : 0; }
+
+int lpmp_path_moves(lpmp_engine* e, lpmp_path_set* ps, int rounds) {
+  return guarded([&] {
+    const std::string who = "lpmp_path_moves";
+    if (!e || !ps) throw std::runtime_error(who + ": null argument");
+    if (!e->model.plan || ps->gen != e->model.model_gen) throw StateError(who + ": the path set was made for another model (lpmp_upload_model since lpmp_path_set_create)");
+    if (rounds < 0) throw std::runtime_error(who + ": negative number of rounds");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);                 // passes that ran ahead: the duals read are those of the pass the caller is at
+    require_consts(e);
+    ModelState& m = e->model;
+    if (!m.have_primal && !m.primal_unset_only) {
+      try { ensure_primal(e); }
+      catch (const UnsupportedError&) {
+        // a model the rounding code does not take (a message of another kind somewhere off the paths): the array of unset labels
+        // of lpmp_readout_labels; the listed unaries get labels, no pairwise slot is written
+        m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
+        upload_unset_primal(e);
+        m.primal_unset_only = true;
+      }
+    }
+    if (rounds == 0 || ps->launches.empty()) return;
+    rows_refresh(e);           // (reads the rows; writes no dual)
+    for (int r = 0; r < rounds; ++r)
+      for (const auto& l : ps->launches)
+        launch_path_moves(ps->paths, ps->nodes, ps->links, m.d_dual, m.d_const, m.d_primal, ps->back, l.first, l.count, l.wide, m.tab_flag, e->stream);
+    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
 // ---- prepared read-outs: labels, unaries and beliefs of listed VECTOR factors into the caller's array (include/lpmp_engine.h) -------
 // The output twin of lpmp_set_vectors, prepared like a schedule: the record list is uploaded at create, a call uploads nothing.
 struct lpmp_readout {

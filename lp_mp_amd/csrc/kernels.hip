@@ -3730,6 +3730,139 @@ decode_kernel(const DecodeRec* __restrict__ recs, const DecodeLink* __restrict__
   if (live && g == 0 && label != NONE) primal[2 * (int64_t)r.factor] = label;
 }
 
+// ---- path moves: exact relabelling of whole paths (lpmp_path_moves) ----------------------------------------------
+// One launch is the paths of one group that share a form; they are independent by construction (no pairwise factor joins two of
+// them), so no workgroup waits for another.  T threads per path — a wave (four paths per workgroup) while no node has more than
+// PATH_WAVE_MAX labels, the workgroup above — with thread y holding label y (and y + T).  Per node i, in path order:
+//   n_i[y] = theta[y] + its links in ascending message index: m_s[y] for a path edge, (cost line at the other unary's label + m_s[y])
+//            otherwise (the decode's sum)
+//   f_i[y] = min_x (f_{i-1}[x] + c_i(x, y)) + n_i[y], strict < in ascending x (the first minimiser is the back-pointer)
+// f lives in LDS, double buffered (one barrier per node); c_i goes through pw_cost entry by entry, the exact O(L^2) form for every
+// kind.  n_{i+1} does not depend on f: its record, labels, lines and vectors are requested before the min-plus of node i.  The
+// back-pointers go to the scratch buffer (a byte each while the previous node has at most 256 labels, two above) and thread 0
+// walks them backwards at the end; nothing but the labels of the path's nodes is written to primal.
+template <int T>
+__device__ __forceinline__ void path_sync() { if (T == 64) wave_sync(); else __syncthreads(); }
+__device__ __forceinline__ double path_node_cost(const PathNode& nd, const PathLink* __restrict__ links, const double* __restrict__ dual,
+                                                 const double* __restrict__ cdata, const int32_t* primal, int y, int tab32) {
+  double n = dual[nd.dual_off + y];
+  const PathLink* lks = links + nd.link_begin;
+  for (int k = 0; k < nd.n_links; ++k) {
+    const PathLink lk = lks[k];
+    const double ms = dual[lk.vec_off + y];
+    if (lk.on_path) { n = n + ms; continue; }
+    const int xv = min(max(primal[2 * (int64_t)lk.other], 0), lk.od - 1);   // (an unset or stray label: the clamp keeps the read inside the table)
+    const double t = lk.side == 0 ? pw_cost(cdata, lk.peer_const, lk.kind, lk.pd1, y, xv, tab32) : pw_cost(cdata, lk.peer_const, lk.kind, lk.pd1, xv, y, tab32);
+    n = n + (t + ms);
+  }
+  return n;
+}
+// g = min_x (fp[x] + c(x, y)) and b = the smallest minimising x (g = +inf, b = 0 on entry), c(x, y) = cost(x, y) with the previous
+// node on side 0 of the edge and cost(y, x) otherwise.  Ascending x, strict <; the costs of PATH_CHUNK consecutive x are requested
+// before the first of them is added (an x beyond dp - 1 requests entry dp - 1 again and is not counted)
+constexpr int PATH_CHUNK = 16;
+template <int KIND, int T32>
+__device__ __forceinline__ void path_min_plus(const double* __restrict__ cdata, int64_t coff, int d1, int prev_side, const double* fp, int dp, int y,
+                                              double& g, int& b) {
+  for (int x0 = 0; x0 < dp; x0 += PATH_CHUNK) {
+    double c[PATH_CHUNK];
+    if (prev_side == 0) {
+#pragma unroll
+      for (int j = 0; j < PATH_CHUNK; ++j) c[j] = pw_cost(cdata, coff, KIND, d1, min(x0 + j, dp - 1), y, T32);
+    } else {
+#pragma unroll
+      for (int j = 0; j < PATH_CHUNK; ++j) c[j] = pw_cost(cdata, coff, KIND, d1, y, min(x0 + j, dp - 1), T32);
+    }
+#pragma unroll
+    for (int j = 0; j < PATH_CHUNK; ++j) {
+      const int x = x0 + j;
+      const double v = fp[min(x, dp - 1)] + c[j];
+      if (x < dp && v < g) { g = v; b = x; }
+    }
+  }
+}
+template <int T>
+__global__ void __launch_bounds__(256)
+path_moves_kernel(const PathRec* __restrict__ paths, const PathNode* __restrict__ nodes, const PathLink* __restrict__ links,
+                  const double* __restrict__ dual, const double* __restrict__ cdata, int32_t* primal, unsigned char* back,
+                  int64_t first, int64_t count, int tab32) {
+  constexpr int PPB = 256 / T, W = T == 64 ? PATH_WAVE_MAX : PATH_MAX_LABELS, NY = W / T, NONE = 0x7fffffff;
+  __shared__ double f[PPB][2][W];
+  __shared__ double red_v[4];
+  __shared__ int red_i[4];
+  const int team = threadIdx.x / T, t = threadIdx.x % T;
+  const int64_t idx = (int64_t)blockIdx.x * PPB + team;
+  if (idx >= count) return;          // (T == 64: a whole wave, and the wave form has no workgroup barrier; T == 256: never)
+  const PathRec pr = paths[first + idx];
+  const PathNode* nds = nodes + pr.node_begin;
+  const int k = pr.n_nodes;
+  PathNode nd = nds[0], nx = nd;
+  double nc[NY], nn[NY];
+#pragma unroll
+  for (int j = 0; j < NY; ++j) { const int y = t + j * T; nc[j] = y < nd.d0 ? path_node_cost(nd, links, dual, cdata, primal, y, tab32) : 0.0; nn[j] = 0.0; }
+  int dp = 0;
+  for (int i = 0; i < k; ++i) {
+    double* fc = f[team][i & 1];
+    const double* fp = f[team][(i & 1) ^ 1];
+    const bool more = i + 1 < k;
+    if (more) {
+      nx = nds[i + 1];
+#pragma unroll
+      for (int j = 0; j < NY; ++j) { const int y = t + j * T; nn[j] = y < nx.d0 ? path_node_cost(nx, links, dual, cdata, primal, y, tab32) : 0.0; }
+    }
+#pragma unroll
+    for (int j = 0; j < NY; ++j) {
+      const int y = t + j * T;
+      if (y >= nd.d0) continue;
+      if (i == 0) { fc[y] = nc[j]; continue; }
+      double g = LPMP_INF; int b = 0;
+      switch (nd.edge_kind) {      // (wave-uniform: pw_cost with the kind known, so that the loads of a chunk are issued together)
+        case LPMP_F_PAIRWISE_DENSE:
+          if (tab32) path_min_plus<LPMP_F_PAIRWISE_DENSE, 1>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b);
+          else path_min_plus<LPMP_F_PAIRWISE_DENSE, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b);
+          break;
+        case LPMP_F_PAIRWISE_SHARED: path_min_plus<LPMP_F_PAIRWISE_SHARED, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b); break;
+        case LPMP_F_PAIRWISE_DIFF: path_min_plus<LPMP_F_PAIRWISE_DIFF, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b); break;
+        case LPMP_F_PAIRWISE_DIFF_SHIFT: path_min_plus<LPMP_F_PAIRWISE_DIFF_SHIFT, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b); break;
+        default: path_min_plus<LPMP_F_PAIRWISE_POTTS, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_prev_side, fp, dp, y, g, b); break;
+      }
+      if (nd.back_wide) reinterpret_cast<unsigned short*>(back + nd.back_off)[y] = (unsigned short)b;
+      else back[nd.back_off + y] = (unsigned char)b;
+      fc[y] = g + nc[j];
+    }
+    path_sync<T>();
+    dp = nd.d0;
+    if (more) {
+      nd = nx;
+#pragma unroll
+      for (int j = 0; j < NY; ++j) nc[j] = nn[j];
+    }
+  }
+  // the first minimiser of the last f: per thread in ascending y, then value / index butterflies over the wave (and the waves)
+  const double* fl = f[team][(k - 1) & 1];
+  double bv = LPMP_INF; int bi = NONE;
+#pragma unroll
+  for (int j = 0; j < NY; ++j) { const int y = t + j * T; if (y < nd.d0 && (bi == NONE || fl[y] < bv)) { bv = fl[y]; bi = y; } }
+  double mn = decode_min<64>(bv);
+  int label = decode_min<64>((bi != NONE && bv == mn) ? bi : NONE);
+  if (T > 64) {
+    if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = mn; red_i[threadIdx.x >> 6] = label; }
+    __syncthreads();
+    mn = LPMP_INF; label = NONE;
+    for (int w = 0; w < T / 64; ++w)
+      if (red_i[w] != NONE && (label == NONE || red_v[w] < mn || (red_v[w] == mn && red_i[w] < label))) { mn = red_v[w]; label = red_i[w]; }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the back-pointers the other threads stored
+  if (t != 0) return;
+  int x = label;
+  for (int i = k - 1; i >= 1; --i) {
+    const PathNode b = nds[i];
+    primal[2 * (int64_t)b.factor] = x;
+    x = b.back_wide ? (int)reinterpret_cast<const unsigned short*>(back + b.back_off)[x] : (int)back[b.back_off + x];
+  }
+  primal[2 * (int64_t)nds[0].factor] = x;
+}
+
 // LP::CheckPrimalConsistency (reference LP_MP.h:1067-1082): every message's two sides agree
 __global__ void __launch_bounds__(256)
 primal_check_kernel(const PrimalLink* __restrict__ links, int64_t n, const int32_t* __restrict__ primal, int* __restrict__ bad) {
@@ -4079,6 +4212,12 @@ static void launch_decode_as(const DecodeRec* recs, const DecodeLink* links, con
   constexpr int GPB = 256 / G;
   hipLaunchKernelGGL((decode_kernel<G, CH>), dim3((unsigned)((count + GPB - 1) / GPB)), dim3(256), 0, s, recs, links, dual, cdata, primal, first, count,
                      level, flags, tab32);
+}
+void launch_path_moves(const PathRec* paths, const PathNode* nodes, const PathLink* links, const double* dual, const double* cdata,
+                       int32_t* primal, unsigned char* back, int64_t first, int64_t count, int wide, int tab32, hipStream_t s) {
+  if (count <= 0) return;
+  if (wide) hipLaunchKernelGGL((path_moves_kernel<256>), dim3((unsigned)count), dim3(256), 0, s, paths, nodes, links, dual, cdata, primal, back, first, count, tab32);
+  else hipLaunchKernelGGL((path_moves_kernel<64>), dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, paths, nodes, links, dual, cdata, primal, back, first, count, tab32);
 }
 void launch_decode(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
                    int64_t first, int64_t count, int width, int level, int flags, int tab32, hipStream_t s) {

@@ -100,6 +100,19 @@ struct ReadoutRec { int64_t dual_off, row; int32_t d0, factor, link_begin, n_lin
 static_assert(sizeof(ReadoutRec) == 32, "read-out record layout");
 constexpr int READOUT_GROUP_MAX = DECODE_GROUP_MAX;   // beliefs: a lane group per unary up to this many labels, a wave above (the decode's split)
 constexpr int READOUT_CHUNK = DECODE_CHUNK;           // ... and the labels a wave holds in registers at a time
+// path moves (lpmp_path_moves; DESIGN.md 8, path_moves_kernel): a path is a run of nodes.  A node: its place in the packed duals
+// (vector factors live there under every layout), its label count, its links in ascending message index, and the path edge to the
+// PREVIOUS node — constants, kind and second dimension of that pairwise factor and the side the previous node has in it
+// (edge_kind < 0: the first node) — and where its back-pointers go in the scratch buffer: d0 entries at byte back_off, one byte
+// each when the previous node has at most 256 labels (back_wide == 0), two otherwise.  A link: the message vector of the node's
+// side (device dual offset), the pairwise factor's constants, kind and second dimension, the node's side, the unary on the other
+// side with its label count, and on_path for a path edge (only the message vector is added then)
+struct PathRec { int64_t node_begin; int32_t n_nodes, pad; };
+struct PathNode { int64_t dual_off, edge_const, back_off; int32_t d0, factor, link_begin, n_links, edge_kind, edge_d1, edge_prev_side, back_wide; };
+struct PathLink { int64_t vec_off, peer_const; int32_t kind, pd1, side, other, od, on_path; };
+static_assert(sizeof(PathRec) == 16 && sizeof(PathNode) == 56 && sizeof(PathLink) == 40, "path record layout");
+constexpr int PATH_WAVE_MAX = 64;        // a wave per path while no node of it has more labels (four paths per workgroup), a workgroup above
+static_assert(PATH_MAX_LABELS <= GEN_MAXD, "path moves hold a vector of f in LDS");
 // moving label windows (lpmp_move_windows): one listed unary — its place in the packed duals, its label count (at most
 // MOVE_MAX_LABELS: a wave holds a whole vector in registers), its row of delta / cost_old / cost_new, and its links in message-list
 // order: the message vector of its side in the pairwise factor (device dual offset) ...
@@ -155,6 +168,11 @@ void launch_readout_labels(const ReadoutRec* recs, int64_t n, const int32_t* pri
 void launch_readout_vectors(const ReadoutRec* recs, int64_t n, int width, const double* dual, double* dst, int64_t dst_stride, hipStream_t s);
 void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, const double* dual, const double* cdata, double* dst,
                             int64_t dst_stride, int64_t first, int64_t count, int width, int tab32, hipStream_t s);
+// path moves: paths [first, first + count) of one group, all of one form — wide == 0: no node has more than PATH_WAVE_MAX labels
+// (a wave per path), wide != 0: a workgroup per path.  Exact dynamic programming over each path given the labels of all other
+// unaries; writes the back-pointers into `back` and the new labels of the paths' nodes into primal
+void launch_path_moves(const PathRec* paths, const PathNode* nodes, const PathLink* links, const double* dual, const double* cdata,
+                       int32_t* primal, unsigned char* back, int64_t first, int64_t count, int wide, int tab32, hipStream_t s);
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
 void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s);
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);

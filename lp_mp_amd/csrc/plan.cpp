@@ -1328,6 +1328,115 @@ DecodePlan Plan::decode_plan(int direction) const {
   return dp;
 }
 
+// ---- path moves (plan.hpp, PathPlan) ----------------------------------------------------------------------------------------
+PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* un, const std::string& who) const {
+  PathPlan pp;
+  auto S = [](int64_t v) { return std::to_string(v); };
+  if (n_groups < 0 || !group_off || !path_off) fail(who + ": bad argument");
+  if (group_off[0] != 0) fail(who + ": group_off[0] is " + S(group_off[0]) + ", not 0");
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (group_off[g + 1] < group_off[g]) fail(who + ": group_off is not monotone at group " + S(g));
+  const int64_t n_paths = group_off[n_groups];
+  if (path_off[0] != 0) fail(who + ": path_off[0] is " + S(path_off[0]) + ", not 0");
+  for (int64_t j = 0; j < n_paths; ++j)
+    if (path_off[j + 1] <= path_off[j]) fail(who + ": path_off is not increasing at path " + S(j) + " (a path has at least one member)");
+  const int64_t ne = path_off[n_paths];
+  if (ne > (int64_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 entries");
+  if (ne > 0 && !un) fail(who + ": null list of unaries");
+  for (int64_t e = 0; e < ne; ++e) {
+    const int32_t f = un[e];
+    if (f < 0 || f >= nf) fail(who + ": factor index " + S(f) + " (entry " + S(e) + ") is out of range");
+    if (f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + S(f) + " (entry " + S(e) + ") is not a VECTOR factor");
+  }
+  // where a unary sits in the group at hand: group stamp, path, index in the path, entry
+  std::vector<int64_t> grp_of((size_t)nf, -1), path_of((size_t)nf, 0), ent_of((size_t)nf, 0);
+  for (int64_t g = 0; g < n_groups; ++g)
+    for (int64_t e = path_off[group_off[g]]; e < path_off[group_off[g + 1]]; ++e) {
+      const size_t f = (size_t)un[e];
+      if (grp_of[f] == g) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") appears twice in group " + S(g) + " (first: entry " + S(ent_of[f]) + ")");
+      grp_of[f] = g; ent_of[f] = e;
+    }
+  pp.group_off.assign(group_off, group_off + n_groups + 1);
+  pp.path_off.assign(path_off, path_off + n_paths + 1);
+  pp.unaries.assign(un, un + ne);
+  // the unary on each side of every pairwise factor, from all unary-pairwise messages (as in decode_plan)
+  std::vector<int32_t> side_unary(2 * (size_t)nf, -1);
+  std::vector<uint8_t> side_count(2 * (size_t)nf, 0);
+  auto unary_pairwise = [&](int64_t m) {
+    const lpmp_msg_type& mt = mtypes[(size_t)m_type[(size_t)m]];
+    return mt.kind == LPMP_M_UNARY_PAIRWISE && (mt.param == 0 || mt.param == 1) && f_kind[m_left[(size_t)m]] == LPMP_F_VECTOR && f_kind[m_right[(size_t)m]] != LPMP_F_VECTOR;
+  };
+  for (int64_t m = 0; m < nm; ++m) {
+    if (!unary_pairwise(m)) continue;
+    const size_t slot = 2 * (size_t)m_right[(size_t)m] + (size_t)mtypes[(size_t)m_type[(size_t)m]].param;
+    if (side_count[slot] < 2) ++side_count[slot];
+    side_unary[slot] = m_left[(size_t)m];
+  }
+  // the unsupported shapes: the lowest listed unary that has one
+  int32_t bad = -1; std::string what;
+  auto offend = [&](int32_t u, const std::string& w) { if (bad < 0 || u < bad) { bad = u; what = w; } };
+  for (int64_t e = 0; e < ne; ++e) {
+    const int32_t u = un[e];
+    if (bad >= 0 && u >= bad) continue;
+    if (f_dim0[u] > PATH_MAX_LABELS) offend(u, "has " + S(f_dim0[u]) + " labels (a path move takes at most " + S(PATH_MAX_LABELS) + ")");
+    for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) {
+      const MsgEntry& me = fm[(size_t)k];
+      if (me.role != 0 || !unary_pairwise(me.msg)) { offend(u, "has a message that is not a unary-pairwise message with the factor as its unary"); continue; }
+      const size_t s = 2 * (size_t)m_right[(size_t)me.msg];
+      if (side_count[s] != 1 || side_count[s + 1] != 1 || side_unary[s] == side_unary[s + 1])
+        offend(u, "is next to pairwise factor " + S(m_right[(size_t)me.msg]) + ", which does not have exactly one unary on each side from two different unaries");
+    }
+  }
+  if (bad >= 0) {
+    pp.bad_factor = bad;
+    pp.why = who + ": factor " + S(bad) + " " + what + " (DESIGN.md 8, path moves)";
+    return pp;
+  }
+  // links in ascending message index, and the path edges
+  pp.edge.assign((size_t)ne, -1); pp.edge_prev_side.assign((size_t)ne, 0);
+  pp.link_off.assign(1, 0);
+  std::fill(grp_of.begin(), grp_of.end(), -1);
+  std::vector<int32_t> msgs;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    for (int64_t j = group_off[g]; j < group_off[g + 1]; ++j)
+      for (int64_t e = path_off[j]; e < path_off[j + 1]; ++e) { const size_t f = (size_t)un[e]; grp_of[f] = g; path_of[f] = j; ent_of[f] = e; }
+    for (int64_t j = group_off[g]; j < group_off[g + 1]; ++j) {
+      pp.longest = std::max(pp.longest, path_off[j + 1] - path_off[j]);
+      for (int64_t e = path_off[j]; e < path_off[j + 1]; ++e) {
+        const int32_t u = un[e];
+        pp.max_labels = std::max(pp.max_labels, f_dim0[u]);
+        msgs.clear();
+        for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) msgs.push_back(fm[(size_t)k].msg);
+        std::sort(msgs.begin(), msgs.end());
+        for (int32_t m : msgs) {
+          const int32_t p = m_right[(size_t)m], side = mtypes[(size_t)m_type[(size_t)m]].param, v = side_unary[2 * (size_t)p + (size_t)(1 - side)];
+          int32_t on_path = 0;
+          if (grp_of[(size_t)v] == g) {
+            const std::string pair = "pairwise factor " + S(p) + " joins factor " + S(u) + " (entry " + S(e) + ") and factor " + S(v) + " (entry " + S(ent_of[(size_t)v]) + ")";
+            if (path_of[(size_t)v] != j) fail(who + ": " + pair + ", members of two paths of group " + S(g));
+            const int64_t di = ent_of[(size_t)v] - e;
+            if (di != 1 && di != -1) fail(who + ": " + pair + ", two non-consecutive members of path " + S(j) + " (a closed ring included)");
+            if (di == -1) {
+              if (pp.edge[(size_t)e] >= 0)
+                fail(who + ": more than one pairwise factor (" + S(pp.edge[(size_t)e]) + " and " + S(p) + ") joins factor " + S(v) + " (entry " + S(e - 1) + ") and factor " + S(u) + " (entry " + S(e) + ")");
+              pp.edge[(size_t)e] = p; pp.edge_prev_side[(size_t)e] = 1 - side;
+            }
+            on_path = 1;
+          }
+          pp.links.push_back({p, side, v, on_path});
+          if (!on_path) ++pp.n_off_path_links;
+        }
+        pp.link_off.push_back((int64_t)pp.links.size());
+        if (e > path_off[j] && pp.edge[(size_t)e] < 0)
+          fail(who + ": no pairwise factor joins factor " + S(un[e - 1]) + " (entry " + S(e - 1) + ") and factor " + S(u) + " (entry " + S(e) + ")");
+      }
+      pp.n_path_edges += path_off[j + 1] - path_off[j] - 1;
+    }
+  }
+  if (pp.links.size() > (size_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 links");
+  return pp;
+}
+
 // ---- partition sweeps (reference LP_MP.h:1717-1843).  union_find.hxx:5-93: union by size, the first argument's root
 // wins ties, contiguous ids in increasing root index; partitions without updated factors are dropped (:1736-1745).
 // Intra-partition order: the reference sorts by position in forwardOrdering_ with a comparator that is false for every

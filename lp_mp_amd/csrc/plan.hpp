@@ -297,6 +297,24 @@ struct DecodePlan {
   int32_t n_levels = 0;
 };
 
+// Path moves (lpmp_path_moves): the structure of a path set.  Groups of paths of VECTOR factors; consecutive members
+// of a path are joined by exactly one pairwise factor (the path edge), found here.  Per entry (a member of a path, in the caller's
+// order): the edge to the PREVIOUS member with the side the previous member has in it, and the member's links in ascending
+// message index — on_path marks the one or two that are path edges, whose table the recursion reads instead of a line of it.
+constexpr int32_t PATH_MAX_LABELS = 512;
+struct PathLinkPlan { int32_t p, side, other, on_path; };   // pairwise factor, the member's side in it, the unary on the other side
+struct PathPlan {
+  std::string why;                       // "" or why the set is refused as unsupported (names the lowest offending listed unary)
+  int32_t bad_factor = -1;
+  std::vector<int64_t> group_off, path_off;
+  std::vector<int32_t> unaries;
+  std::vector<int32_t> edge, edge_prev_side;   // per entry; -1 / 0 for the first member of a path
+  std::vector<int64_t> link_off;         // CSR over the entries
+  std::vector<PathLinkPlan> links;
+  int64_t n_path_edges = 0, n_off_path_links = 0, longest = 0;
+  int32_t max_labels = 0;
+};
+
 struct Plan {
   // copied structure (no cost data)
   int32_t n_ftypes = 0, n_mtypes = 0, n_tables = 0;
@@ -401,6 +419,11 @@ struct Plan {
   // lowest offending factor is (a factor of a message of another kind; a pairwise factor with a side that has no unary or two,
   // or with one unary on both sides)
   DecodePlan decode_plan(int direction) const;
+  // Structure of a path set (include/lpmp_engine.h, lpmp_path_set_create): group_off [n_groups + 1] in paths, path_off [n_paths + 1]
+  // in entries, unaries [entries].  Throws std::runtime_error (LPMP_ERR_INVALID) naming the entry, with `who` in front; a set the
+  // move does not take comes back with PathPlan::why set.  Order of the checks: offsets, indices and kinds, duplicates inside a
+  // group; then the unsupported shapes; then the path edges (they are read off the supported shape)
+  PathPlan path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, const std::string& who) const;
 };
 
 // The band of a difference vector D of n entries, by the BITS of the doubles (-0.0 and +0.0 differ): lo = the first index whose

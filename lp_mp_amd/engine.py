@@ -82,6 +82,8 @@ EXPORTS = [
     "lpmp_readout_labels", "lpmp_readout_vectors", "lpmp_readout_beliefs",
     "lpmp_window_set_create", "lpmp_window_set_destroy", "lpmp_window_set_n", "lpmp_window_set_max_labels", "lpmp_window_set_n_pairwise",
     "lpmp_move_windows", "lpmp_plan_window_info",
+    "lpmp_path_set_create", "lpmp_path_set_destroy", "lpmp_path_set_n_groups", "lpmp_path_set_n_paths", "lpmp_path_set_longest",
+    "lpmp_path_set_scratch_bytes", "lpmp_path_moves", "lpmp_plan_path_info",
 ]
 
 
@@ -238,6 +240,15 @@ def lib():
             L.lpmp_window_set_max_labels.argtypes = [C.c_void_p]
             L.lpmp_move_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
             L.lpmp_plan_window_info.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+        if hasattr(L, "lpmp_path_set_create"):       # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_path_set_create.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+            L.lpmp_path_set_destroy.restype = None
+            L.lpmp_path_set_destroy.argtypes = [C.c_void_p]
+            for n in ("lpmp_path_set_n_groups", "lpmp_path_set_n_paths", "lpmp_path_set_longest", "lpmp_path_set_scratch_bytes"):
+                getattr(L, n).restype = C.c_int64
+                getattr(L, n).argtypes = [C.c_void_p]
+            L.lpmp_path_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.lpmp_plan_path_info.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -562,6 +573,36 @@ def _window_info(self, factors=None) -> dict:
 Plan.window_info = _window_info
 
 
+def flatten_path_groups(groups):
+    """(group_off [n_groups + 1] int64 in paths, path_off [n_paths + 1] int64 in entries, unaries int32) of ``groups``: a sequence of
+    groups, each a sequence of paths, each a sequence of factor indices — the arrays of lpmp_path_set_create"""
+    group_off, path_off, un = [0], [0], []
+    for g in groups:
+        for path in g:
+            un.extend(int(f) for f in path)
+            path_off.append(len(un))
+        group_off.append(len(path_off) - 1)
+    if un and (min(un) < -(1 << 31) or max(un) >= (1 << 31)):
+        raise ValueError("path groups: a factor index does not fit an int32")
+    return np.asarray(group_off, np.int64), np.asarray(path_off, np.int64), np.asarray(un if un else [0], np.int32)[:len(un)]
+
+
+def _path_info(self, groups) -> dict:
+    """structure of ``Engine.path_set(groups)`` (lpmp_plan_path_info): ``n_paths``, ``n_path_edges`` (pairwise factors the recursion
+    reads as tables) and ``n_off_path_links`` (cost lines a move reads).  EngineError with the refusals of lpmp_path_set_create:
+    LPMP_ERR_INVALID naming the entry, LPMP_ERR_UNSUPPORTED naming the lowest listed factor a move does not take."""
+    go, po, un = flatten_path_groups(groups)
+    keep = un if un.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
+    v = [C.c_int64() for _ in range(3)]
+    buf = C.create_string_buffer(512)
+    _chk(self.L.lpmp_plan_path_info(self.h, int(go.shape[0]) - 1, go.ctypes.data, po.ctypes.data, keep.ctypes.data,
+                                    *[C.addressof(x) for x in v], buf, 512))
+    return dict(zip(("n_paths", "n_path_edges", "n_off_path_links"), [x.value for x in v]))
+
+
+Plan.path_info = _path_info
+
+
 def graph_colour_major_order(n: int, edge_i, edge_j, seed: int = 0):
     """(rank[n] int64, number of colours): colour-major variable order of a pairwise graph on the planner's threads
     (lpmp_graph_colour_major_order; the numpy statement of the same algorithm is ordering.colour_major_order_numpy)"""
@@ -869,6 +910,12 @@ class Engine:
         ``WindowSet.move`` carries their unaries, their messages and the shifts of the adjacent DIFF_SHIFT factors along"""
         return WindowSet(self, factors)
 
+    def path_set(self, groups) -> "PathSet":
+        """a prepared set of paths of VECTOR factors (lpmp_path_set_create): ``groups`` is a sequence of groups, each a sequence of
+        paths, each a sequence of factor indices whose consecutive members share exactly one pairwise factor.  ``PathSet.move``
+        relabels every path exactly, given all other labels"""
+        return PathSet(self, groups)
+
     def check_primal_consistency(self) -> bool:
         out = C.c_int()
         _chk(self.L.lpmp_check_primal_consistency(self.h, C.addressof(out)))
@@ -1150,6 +1197,38 @@ class WindowSet:
                 raise ValueError("move: stride beyond the rows of the cost arrays")
             co, cn = [None if a is None else C.c_void_p(a.ctypes.data) for a in arrs]
         _chk(self.L.lpmp_move_windows(self.e.h, self.h, dp, dm, co, cn, cs, cm))
+
+
+class PathSet:
+    """Prepared groups of paths of the engine's uploaded model (include/lpmp_engine.h, lpmp_path_set_* / lpmp_path_moves).  Structure,
+    like a ``Readout``: it stays valid across new costs, passes, decodes and window moves; after the engine's next ``upload`` every
+    move raises (LPMP_ERR_STATE) and ``close`` still works."""
+
+    def __init__(self, engine: Engine, groups):
+        self.e = engine
+        self.L = engine.L
+        go, po, un = flatten_path_groups(groups)
+        keep = un if un.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
+        h = C.c_void_p()
+        _chk(self.L.lpmp_path_set_create(engine.h, int(go.shape[0]) - 1, go.ctypes.data, po.ctypes.data, keep.ctypes.data, C.addressof(h)))
+        self.h = h.value
+        self.n_groups = int(self.L.lpmp_path_set_n_groups(self.h))
+        self.n_paths = int(self.L.lpmp_path_set_n_paths(self.h))
+        self.longest = int(self.L.lpmp_path_set_longest(self.h))
+        self.scratch_bytes = int(self.L.lpmp_path_set_scratch_bytes(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lpmp_path_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def move(self, rounds: int = 1):
+        """``rounds`` times over the groups in their order: every path takes the labels that minimise the energy over it given all
+        other labels (lpmp_path_moves).  Asynchronous on the engine's stream; reads duals, constants and labels, writes labels."""
+        _chk(self.L.lpmp_path_moves(self.e.h, self.h, int(rounds)))
 
 
 def device_identity(device: int = 0) -> str:

@@ -649,6 +649,20 @@ class LP:
         e.decode_primal(direction, refine)
         return e.evaluate_primal()
 
+    def path_moves(self, groups, rounds: int = 1) -> float:
+        """exact relabelling of whole paths given all other labels (Engine.path_set / PathSet.move; no reference
+        counterpart): ``groups`` is a sequence of groups, each a sequence of paths, each a sequence of vector-factor handles (what
+        ``add_factor`` returned) whose consecutive members share exactly one pairwise factor.  Runs the groups in order ``rounds``
+        times on the labels the primal array holds (after ``decode_primal``, say) and returns EvaluatePrimal(); on a complete
+        labelling that cost never rises.  The prepared set is made and closed here: keep ``Engine.path_set`` for repeated moves."""
+        e = self._ready()
+        ps = e.path_set(groups)
+        try:
+            ps.move(rounds)
+            return e.evaluate_primal()
+        finally:
+            ps.close()
+
     def readout(self, factor_handles=None):
         """a prepared read-out (Engine.readout; no reference counterpart) of the listed vector factors — what
         ``add_factor`` returned for them, None: all of them — with ``labels()``, ``vectors()`` and ``beliefs()`` into host or device

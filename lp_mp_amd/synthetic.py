@@ -236,6 +236,16 @@ def grid_model(H: int, W: int, L: int, pairwise: str = "dense", order: str = "ro
     raise ValueError(pairwise)
 
 
+def grid_paths(H: int, W: int, order: str = "row_major"):
+    """The four path groups of an H x W grid for ``Engine.path_set`` / ``LP.path_moves``: even rows, odd rows, even columns, odd
+    columns, each path a whole row (left to right) or column (top to bottom) as the unary factor indices of
+    ``grid_model(H, W, ..., order=order)`` (the unaries are that model's first H * W factors, in variable order).  Two rows of one
+    parity are never adjacent, so the paths of a group share no pairwise factor; a group without paths (H or W of 1) is kept, empty."""
+    var = grid_variable_order(H, W, order)
+    return [[[int(f) for f in var[r, :]] for r in range(0, H, 2)], [[int(f) for f in var[r, :]] for r in range(1, H, 2)],
+            [[int(f) for f in var[:, c]] for c in range(0, W, 2)], [[int(f) for f in var[:, c]] for c in range(1, W, 2)]]
+
+
 def _diff_costs(E: int, L: int, first: int, seed: int, n_tables: int, vecs=None, scales=None):
     """(vectors [T,2L-1], vector of every edge [E], scale of every edge [E]) of the ``pairwise="diff"`` generators"""
     if vecs is None:
