@@ -489,6 +489,88 @@ int lpmp_path_moves(lpmp_engine* e, lpmp_path_set* ps, int rounds);
 int lpmp_plan_path_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries,
                         int64_t* n_paths, int64_t* n_path_edges, int64_t* n_off_path_links, char* why, int why_n);
 
+/* ---- forest moves: exact relabelling of induced forests given all other labels ------------------------------------
+ * The path move for any graph: a path is a tree, and the dynamic programme that is exact on a path is exact on any set of unaries
+ * whose induced subgraph is a forest — leaf-to-root min-plus, then root-to-leaf back-tracking.  Reads the duals, the constants and
+ * the primal array, writes only the primal array.  No counterpart in the reference.
+ *
+ * A forest set is a prepared object like an lpmp_path_set.  It holds n_groups groups; group g is the entries
+ * [group_off[g], group_off[g+1]) of two parallel arrays: unaries[i] is a VECTOR factor of the uploaded model, parent[i] the FACTOR
+ * INDEX of the parent of unaries[i], or -1 for a root.  The parent is listed in the same group.  A unary may be in several groups,
+ * never twice in one.  A child and its parent are joined by exactly one pairwise factor, the tree edge; the engine finds it.
+ *
+ * lpmp_forest_moves runs the groups in the given order, `rounds` times.  The trees of a group are independent and run concurrently.
+ * For one group, with x_v the label unary v holds in the primal array when the group starts:
+ *   children    of v: the members whose parent is v, in ascending MESSAGE INDEX of v's message into the tree edge
+ *   node cost   exactly as in lpmp_path_moves:  n_v[x] = theta_v[x];  then every message of v in ascending message index, p its
+ *               pairwise factor, s the side of v, w the other unary:
+ *                   p is a tree edge (to the parent or to a child):   n_v[x] = n_v[x] + m_s[x]
+ *                   otherwise:             n_v[x] = n_v[x] + (t[x] + m_s[x]),  t[x] = cost_p(x, x_w) if s == 0 else cost_p(x_w, x)
+ *               x_w is clamped into [0, d_w - 1] where it is read
+ *   up          children before parents:  f_v[x] = n_v[x];  then for every child c in the order above  f_v[x] = f_v[x] + g_c[x].
+ *               A non-root v with parent q and tree edge e:  g_v[y] = min_x (f_v[x] + c_v(x, y)),  back_v[y] = the smallest
+ *               minimising x (ascending x, strict <),  c_v(x, y) = cost_e(x, y) when v is on side 0 of e and cost_e(y, x) otherwise
+ *   down        x_r = the smallest minimiser of f_r for a root;  x_v = back_v[x_q] otherwise.  The new labels go to the primal array.
+ * cost_p, the arithmetic (IEEE double in this order, no contraction), +inf (an all +inf column: back-pointer 0; an all +inf f_r:
+ * label 0), NaN (outside the contract) and the propagation into the pairwise slots after the last group of the last round are those
+ * of lpmp_path_moves, and so is the treatment of a model the rounding code refuses.  Consequences:
+ *   paths        IEEE addition is commutative (n + g has the bits of g + n): a group whose trees are the paths u_0 ... u_{k-1} with
+ *                parent[u_i] = u_{i+1} gives bit for bit the labels of lpmp_path_moves on those paths
+ *   single nodes a tree of one node is one step of the decode's refinement sweep
+ *   energy       sum_v n_v[x_v] + sum over the tree edges c_v(x_v, x_q) is every term of the energy that depends on the group's
+ *                labels (no pairwise factor joins two trees): on a complete labelling the primal cost never rises over a group
+ *   tree models  a group that is the whole of a tree-structured model gives the optimum whatever the duals are
+ *
+ * lpmp_forest_set_create: LPMP_ERR_STATE before lpmp_upload_model.  Checked in this order, the first failure reported:
+ *   LPMP_ERR_INVALID, naming the entry: offsets that are not monotone, or group_off[0] != 0; an index out of range or a non-VECTOR
+ *     factor; a unary twice in one group; a parent that is neither -1 nor a member of the same group, or is the entry itself;
+ *     parent pointers that close a cycle (the lowest entry on one is named);
+ *   LPMP_ERR_UNSUPPORTED, naming the lowest offending listed unary: the refusals of lpmp_path_set_create (a message that is not
+ *     LPMP_M_UNARY_PAIRWISE with the unary on the left; an adjacent pairwise factor without exactly one unary on each side from two
+ *     different unaries; more than 512 labels);
+ *   LPMP_ERR_INVALID, naming the entries: a child and its parent joined by no pairwise factor, or by more than one; a pairwise
+ *     factor that joins two members of one group that are not child and parent (a chord, an edge between two trees): the members
+ *     of a group must induce a forest.
+ * At create the node / link / child tables, the launch lists (per group: its nodes by height and form, then by depth) and the
+ * scratch are built and uploaded; lpmp_schedules_built counts the create ONCE; a move plans and uploads nothing.  The scratch holds,
+ * per non-root node of the largest group, d_parent doubles (g_v) and d_parent back-pointers, one byte each while d_v <= 256, two
+ * above (lpmp_forest_set_scratch_bytes).  n_groups == 0 or empty groups: a set whose moves are no-ops after their checks.
+ * The set is structure: it stays valid across lpmp_upload_costs, lpmp_set_vectors, lpmp_upload_shared_pool, lpmp_set_constants,
+ * lpmp_move_windows, lpmp_zero_pairwise_duals, passes and decodes; after the next lpmp_upload_model every move on it returns
+ * LPMP_ERR_STATE (destroying it stays legal); lpmp_destroy does not free it.
+ *
+ * lpmp_forest_moves settles passes that ran ahead first, needs specified constants (LPMP_ERR_STATE while they are not, as the
+ * decode), allocates the primal array on first use, and is asynchronous on the engine's stream: per group and round one plain
+ * launch per height level and form (a wave per node while neither the node nor its parent has more than 64 labels, a workgroup
+ * per node above) and one per depth level >= 1.  Duals, tracked bounds, weights, schedules, kernel timing and speculation depth do
+ * not move.  rounds < 0: LPMP_ERR_INVALID; rounds == 0: a no-op after the checks.  Works under the rows layout and both f32 table
+ * modes. */
+typedef struct lpmp_forest_set lpmp_forest_set;
+int lpmp_forest_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off /* [n_groups + 1], in entries */,
+                           const int32_t* unaries, const int32_t* parent, lpmp_forest_set** out);
+void lpmp_forest_set_destroy(lpmp_forest_set* fs);
+int64_t lpmp_forest_set_n_groups(const lpmp_forest_set* fs);
+int64_t lpmp_forest_set_n_trees(const lpmp_forest_set* fs);
+int64_t lpmp_forest_set_max_height(const lpmp_forest_set* fs);   /* edges on the longest leaf-to-root walk: dependent up launches - 1 */
+int64_t lpmp_forest_set_scratch_bytes(const lpmp_forest_set* fs);
+int lpmp_forest_moves(lpmp_engine* e, lpmp_forest_set* fs, int rounds);
+/* host only: the checks of lpmp_forest_set_create on a plan, and the counts: trees (roots), tree edges (non-roots), links of listed
+ * unaries that are no tree edge (one cost line each per move; a unary listed in two groups counts in both), the highest height (0
+ * for sets of single nodes and for empty sets).  Any pointer may be NULL; on failure `why` receives the message of lpmp_last_error. */
+int lpmp_plan_forest_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent,
+                          int64_t* n_trees, int64_t* n_tree_edges, int64_t* n_off_tree_links, int64_t* max_height, char* why, int why_n);
+/* host only: a cover of any model by forest groups, in the arrays of lpmp_forest_set_create.  Call once with NULL arrays for
+ * *n_groups and *n_entries, then with group_off [n_groups + 1], unaries and parent [n_entries].  Deterministic.
+ * Eligible are the VECTOR factors without any of the LPMP_ERR_UNSUPPORTED shapes above; the others are left out and counted in
+ * *n_left_out.  One group: the eligible unaries that no earlier group holds are visited in ascending index, then the others in
+ * ascending index; a union-find runs over the group's members, and a unary joins unless two of its links, parallel factors
+ * included, lead into the same component of the group.  Groups are added until every eligible unary is in one, or until max_groups
+ * (0: no limit).  Every tree is rooted at a centre (the lower factor index where there are two): its height is
+ * ceil(diameter / 2).  At most floor(D / 2) + 1 groups are needed, D the largest number of links of an eligible unary: a unary
+ * that is still uncovered and is refused by a group sees at least two of its links become covered in that group. */
+int lpmp_plan_suggest_forests(lpmp_plan* p, int64_t max_groups, int64_t* n_groups, int64_t* n_entries, int64_t* group_off, int32_t* unaries,
+                              int32_t* parent, int64_t* n_left_out);
+
 int64_t lpmp_dual_size(const lpmp_engine* e);
 /* serialize_dual + save_archive / load_archive (include/serialization.hxx:228-424): packed duals */
 int lpmp_download_duals(lpmp_engine* e, double* host_out);

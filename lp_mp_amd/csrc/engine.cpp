@@ -2598,6 +2598,171 @@ int lpmp_path_moves(lpmp_engine* e, lpmp_path_set* ps, int rounds) {
   });
 }
 
+// ---- forest moves: exact relabelling of induced forests given all other labels (include/lpmp_engine.h) -----------------
+// The path set's twin for trees: the planner's checks, tree edges, children, heights and depths (plan.cpp, forest_plan), then the
+// device records, the launch lists (per group: the nodes by height and form for the up sweep, by depth for the down sweep) and the
+// scratch of rows and back-pointers of the largest group, all uploaded at create.  A move plans and uploads nothing.
+struct lpmp_forest_set {
+  int device = 0;
+  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
+  int64_t n_groups = 0, n_trees = 0, max_height = 0, scratch_bytes = 0;
+  DevBuf<ForestNode> nodes; DevBuf<PathLink> links; DevBuf<int64_t> child_g; DevBuf<int32_t> list;
+  DevBuf<double> rows; DevBuf<unsigned char> back;      // of one group at a time (launches on one stream follow each other)
+  struct Launch { int64_t first, count; int32_t wide; };            // wide < 0: a level of the down sweep
+  std::vector<Launch> launches;
+};
+
+static ForestPlan forest_plan_or_refuse(const Plan& p, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, const std::string& who) {
+  ForestPlan fp = p.forest_plan(n_groups, group_off, unaries, parent, who);
+  if (!fp.why.empty()) throw UnsupportedError(fp.why);
+  return fp;
+}
+
+int lpmp_plan_forest_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent,
+                          int64_t* n_trees, int64_t* n_tree_edges, int64_t* n_off_tree_links, int64_t* max_height, char* why, int why_n) {
+  if (why && why_n > 0) why[0] = 0;
+  const int rc = guarded([&] {
+    if (!p) throw std::runtime_error("lpmp_plan_forest_info: bad argument");
+    const ForestPlan fp = forest_plan_or_refuse(p->p, n_groups, group_off, unaries, parent, "lpmp_plan_forest_info");
+    if (n_trees) *n_trees = fp.n_trees;
+    if (n_tree_edges) *n_tree_edges = fp.n_tree_edges;
+    if (n_off_tree_links) *n_off_tree_links = fp.n_off_tree_links;
+    if (max_height) *max_height = fp.max_height;
+  });
+  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
+  return rc;
+}
+
+int lpmp_plan_suggest_forests(lpmp_plan* p, int64_t max_groups, int64_t* n_groups, int64_t* n_entries, int64_t* group_off, int32_t* unaries,
+                              int32_t* parent, int64_t* n_left_out) {
+  return guarded([&] {
+    if (!p || max_groups < 0) throw std::runtime_error("lpmp_plan_suggest_forests: bad argument");
+    const ForestCover fc = suggest_forests(p->p, max_groups);
+    if (n_groups) *n_groups = (int64_t)fc.group_off.size() - 1;
+    if (n_entries) *n_entries = (int64_t)fc.unaries.size();
+    if (n_left_out) *n_left_out = fc.n_left_out;
+    if (group_off) std::copy(fc.group_off.begin(), fc.group_off.end(), group_off);
+    if (unaries) std::copy(fc.unaries.begin(), fc.unaries.end(), unaries);
+    if (parent) std::copy(fc.parent.begin(), fc.parent.end(), parent);
+  });
+}
+
+int lpmp_forest_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, lpmp_forest_set** out) {
+  return guarded([&] {
+    if (!e || !e->model.plan) throw StateError("lpmp_forest_set_create: no model uploaded (a forest set lists factors of the uploaded model)");
+    if (!out) throw std::runtime_error("lpmp_forest_set_create: bad argument");
+    HIP_CHECK(hipSetDevice(e->device));
+    ModelState& m = e->model;
+    const Plan& p = m.plan->p;
+    const ForestPlan fp = forest_plan_or_refuse(p, n_groups, group_off, unaries, parent, "lpmp_forest_set_create");
+    auto fs = std::make_unique<lpmp_forest_set>();
+    fs->device = e->device; fs->gen = m.model_gen;
+    fs->n_groups = n_groups; fs->n_trees = fp.n_trees; fs->max_height = fp.max_height;
+    const size_t ne = fp.unaries.size();
+    std::vector<ForestNode> nodes(ne);
+    std::vector<PathLink> links(fp.links.size());
+    std::vector<int64_t> child_g(fp.children.size());
+    std::vector<int32_t> list; list.reserve(2 * ne);
+    for (size_t k = 0; k < links.size(); ++k) {
+      const ForestLinkPlan& l = fp.links[k];
+      links[k] = {p.doff(l.p) + (l.side ? p.f_dim0[l.p] : 0), p.coff(l.p), p.f_kind[l.p], p.f_dim1[l.p], l.side, l.other, p.f_dim0[l.other], l.tree ? 1 : 0};
+    }
+    int64_t max_rows = 0, max_back = 0;
+    std::vector<std::vector<int32_t>> up[2], down;     // the group's entries by height and form, and by depth
+    for (int64_t g = 0; g < n_groups; ++g) {
+      const int64_t gb = fp.group_off[(size_t)g], ge = fp.group_off[(size_t)g + 1];
+      if (gb == ge) continue;
+      const size_t levels = (size_t)fp.group_height[(size_t)g] + 1;
+      for (int w = 0; w < 2; ++w) up[w].assign(levels, {});
+      down.assign(levels, {});
+      int64_t n_rows = 0, bytes = 0;    // of this group's rows (doubles) and back-pointers
+      for (int64_t en = gb; en < ge; ++en) {
+        const int32_t u = fp.unaries[(size_t)en], d = p.f_dim0[u], q = fp.parent_entry[(size_t)en], pw = fp.edge[(size_t)en];
+        if (d < 1) throw std::runtime_error("lpmp_forest_set_create: factor " + std::to_string(u) + " (entry " + std::to_string(en) + ") has no label");
+        ForestNode nd{p.doff(u), 0, 0, 0, d, u, (int32_t)fp.link_off[(size_t)en], (int32_t)(fp.link_off[(size_t)en + 1] - fp.link_off[(size_t)en]), -1, 0, 0, 0, 0, -1,
+                      (int32_t)fp.child_off[(size_t)en], (int32_t)(fp.child_off[(size_t)en + 1] - fp.child_off[(size_t)en])};
+        int32_t widest = d;
+        if (q >= 0) {
+          const int32_t dq = p.f_dim0[fp.unaries[(size_t)q]];
+          widest = std::max(widest, dq);
+          nd.edge_const = p.coff(pw); nd.edge_kind = p.f_kind[pw]; nd.edge_d1 = p.f_dim1[pw]; nd.edge_side = fp.edge_side[(size_t)en];
+          nd.dq = dq; nd.parent = fp.unaries[(size_t)q];
+          nd.g_off = n_rows; n_rows += dq;
+          nd.back_wide = d > 256 ? 1 : 0;
+          bytes = (bytes + nd.back_wide) & ~(int64_t)nd.back_wide;      // (two-byte entries start at an even byte)
+          nd.back_off = bytes;
+          bytes += (int64_t)dq * (nd.back_wide ? 2 : 1);
+          down[(size_t)fp.depth[(size_t)en]].push_back((int32_t)en);
+        }
+        nodes[(size_t)en] = nd;
+        up[widest > PATH_WAVE_MAX ? 1 : 0][(size_t)fp.height[(size_t)en]].push_back((int32_t)en);
+      }
+      max_rows = std::max(max_rows, n_rows); max_back = std::max(max_back, bytes);
+      for (size_t h = 0; h < levels; ++h)
+        for (int w = 0; w < 2; ++w) {
+          if (up[w][h].empty()) continue;
+          fs->launches.push_back({(int64_t)list.size(), (int64_t)up[w][h].size(), w});
+          list.insert(list.end(), up[w][h].begin(), up[w][h].end());
+        }
+      for (size_t dp = 1; dp < levels; ++dp) {
+        if (down[dp].empty()) continue;
+        fs->launches.push_back({(int64_t)list.size(), (int64_t)down[dp].size(), -1});
+        list.insert(list.end(), down[dp].begin(), down[dp].end());
+      }
+    }
+    for (size_t k = 0; k < child_g.size(); ++k) child_g[k] = nodes[(size_t)fp.children[k]].g_off;
+    fs->scratch_bytes = 8 * max_rows + max_back;
+    if (!nodes.empty()) { fs->nodes.alloc(nodes.size()); h2d(fs->nodes, nodes.data(), nodes.size() * sizeof(ForestNode), e->stream); }
+    if (!links.empty()) { fs->links.alloc(links.size()); h2d(fs->links, links.data(), links.size() * sizeof(PathLink), e->stream); }
+    if (!child_g.empty()) { fs->child_g.alloc(child_g.size()); h2d(fs->child_g, child_g.data(), child_g.size() * sizeof(int64_t), e->stream); }
+    if (!list.empty()) { fs->list.alloc(list.size()); h2d(fs->list, list.data(), list.size() * sizeof(int32_t), e->stream); }
+    if (max_rows > 0) fs->rows.alloc((size_t)max_rows);
+    if (max_back > 0) fs->back.alloc((size_t)max_back);
+    ++m.schedules_built;   // the record tables: structure, like a schedule, counted once
+    *out = fs.release();
+  });
+}
+void lpmp_forest_set_destroy(lpmp_forest_set* fs) {
+  if (!fs) return;
+  (void)hipSetDevice(fs->device);
+  delete fs;
+}
+int64_t lpmp_forest_set_n_groups(const lpmp_forest_set* fs) { return fs ? fs->n_groups : 0; }
+int64_t lpmp_forest_set_n_trees(const lpmp_forest_set* fs) { return fs ? fs->n_trees : 0; }
+int64_t lpmp_forest_set_max_height(const lpmp_forest_set* fs) { return fs ? fs->max_height : 0; }
+int64_t lpmp_forest_set_scratch_bytes(const lpmp_forest_set* fs) { return fs ? fs->scratch_bytes : 0; }
+
+int lpmp_forest_moves(lpmp_engine* e, lpmp_forest_set* fs, int rounds) {
+  return guarded([&] {
+    const std::string who = "lpmp_forest_moves";
+    if (!e || !fs) throw std::runtime_error(who + ": null argument");
+    if (!e->model.plan || fs->gen != e->model.model_gen) throw StateError(who + ": the forest set was made for another model (lpmp_upload_model since lpmp_forest_set_create)");
+    if (rounds < 0) throw std::runtime_error(who + ": negative number of rounds");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);                 // passes that ran ahead: the duals read are those of the pass the caller is at
+    require_consts(e);
+    ModelState& m = e->model;
+    if (!m.have_primal && !m.primal_unset_only) {
+      try { ensure_primal(e); }
+      catch (const UnsupportedError&) {
+        // as lpmp_path_moves: a model the rounding code does not take gets the array of unset labels; no pairwise slot is written
+        m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
+        upload_unset_primal(e);
+        m.primal_unset_only = true;
+      }
+    }
+    if (rounds == 0 || fs->launches.empty()) return;
+    rows_refresh(e);           // (reads the rows; writes no dual)
+    for (int r = 0; r < rounds; ++r)
+      for (const auto& l : fs->launches) {
+        if (l.wide < 0) launch_forest_down(fs->list, fs->nodes, m.d_primal, fs->back, l.first, l.count, e->stream);
+        else launch_forest_up(fs->list, fs->nodes, fs->child_g, fs->links, m.d_dual, m.d_const, m.d_primal, fs->rows, fs->back, l.first, l.count, l.wide, m.tab_flag, e->stream);
+      }
+    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
 // ---- prepared read-outs: labels, unaries and beliefs of listed VECTOR factors into the caller's array (include/lpmp_engine.h) -------
 // The output twin of lpmp_set_vectors, prepared like a schedule: the record list is uploaded at create, a call uploads nothing.
 struct lpmp_readout {

@@ -271,6 +271,92 @@ int32_t suggest_order(const Plan& p, uint64_t seed, int32_t* rank) {
   return n_col;
 }
 
+// A cover of the unaries a forest move takes by groups that each induce a forest (include/lpmp_engine.h, lpmp_plan_suggest_forests).
+// One group: the eligible unaries no earlier group holds in ascending index, then the others in ascending index; a union-find
+// runs over the members, and a unary joins unless two of its links (parallel factors included) lead into one component — so the
+// members induce a forest, and a refused unary has at least two links into the group.  Every tree is then rooted at a centre (the
+// middle of a longest path, found by two breadth-first searches; the lower factor index where there are two): height
+// ceil(diameter / 2).  Sequential and without any random number: the same plan gives the same cover.
+ForestCover suggest_forests(const Plan& p, int64_t max_groups) {
+  ForestCover fc;
+  fc.group_off.assign(1, 0);
+  const int64_t nf = p.nf;
+  const PairSides sides = p.pair_sides();
+  std::vector<int32_t> el;
+  std::vector<int64_t> noff((size_t)nf + 1, 0);
+  std::vector<int32_t> nb;
+  for (int64_t f = 0; f < nf; ++f) {
+    if (p.f_kind[(size_t)f] == LPMP_F_VECTOR) {
+      if (p.move_obstacle((int32_t)f, sides, "forest").empty()) {
+        el.push_back((int32_t)f);
+        for (int64_t k = p.fm_off[(size_t)f]; k < p.fm_off[(size_t)f + 1]; ++k) {
+          const int32_t m = p.fm[(size_t)k].msg, pw = p.m_right[(size_t)m], side = p.mtypes[(size_t)p.m_type[(size_t)m]].param;
+          nb.push_back(sides.side_unary[2 * (size_t)pw + (size_t)(1 - side)]);
+        }
+      } else ++fc.n_left_out;
+    }
+    noff[(size_t)f + 1] = (int64_t)nb.size();
+  }
+  std::vector<uint8_t> covered((size_t)nf, 0);
+  std::vector<int64_t> in_group((size_t)nf, -1), root_mark((size_t)nf, -1);
+  std::vector<int32_t> uf((size_t)nf), prev((size_t)nf), dist((size_t)nf), members, order;
+  auto find = [&](int32_t v) { while (uf[(size_t)v] != v) { uf[(size_t)v] = uf[(size_t)uf[(size_t)v]]; v = uf[(size_t)v]; } return v; };
+  int64_t left = (int64_t)el.size(), visit = 0;
+  for (int64_t g = 0; left > 0 && (max_groups <= 0 || g < max_groups); ++g) {
+    members.clear();
+    for (int pass = 0; pass < 2; ++pass)
+      for (int32_t u : el) {
+        if ((covered[(size_t)u] != 0) != (pass == 1)) continue;
+        ++visit;
+        bool joins = true;
+        for (int64_t k = noff[(size_t)u]; k < noff[(size_t)u + 1] && joins; ++k) {
+          const int32_t v = nb[(size_t)k];
+          if (in_group[(size_t)v] != g) continue;
+          const int32_t r = find(v);
+          if (root_mark[(size_t)r] == visit) joins = false;
+          root_mark[(size_t)r] = visit;
+        }
+        if (!joins) continue;
+        in_group[(size_t)u] = g; uf[(size_t)u] = u;
+        for (int64_t k = noff[(size_t)u]; k < noff[(size_t)u + 1]; ++k)
+          if (in_group[(size_t)nb[(size_t)k]] == g && nb[(size_t)k] != u) uf[(size_t)find(nb[(size_t)k])] = u;
+        members.push_back(u);
+      }
+    // breadth-first search over the group's tree of s: `order` by distance, prev = the vertex it was reached from
+    auto bfs = [&](int32_t s) {
+      order.clear(); order.push_back(s);
+      dist[(size_t)s] = 0; prev[(size_t)s] = -1;
+      for (size_t h = 0; h < order.size(); ++h) {
+        const int32_t v = order[h];
+        for (int64_t k = noff[(size_t)v]; k < noff[(size_t)v + 1]; ++k) {
+          const int32_t w = nb[(size_t)k];
+          if (in_group[(size_t)w] != g || w == prev[(size_t)v]) continue;
+          dist[(size_t)w] = dist[(size_t)v] + 1; prev[(size_t)w] = v; order.push_back(w);
+        }
+      }
+    };
+    const size_t base = fc.unaries.size();
+    fc.unaries.insert(fc.unaries.end(), members.begin(), members.end());
+    fc.parent.resize(fc.unaries.size(), -1);
+    for (int32_t u : members) root_mark[(size_t)u] = -1;       // (reused: -2 = rooted)
+    for (int32_t a : members) {
+      if (root_mark[(size_t)a] == -2) continue;
+      bfs(a);
+      bfs(order.back());
+      int32_t c = order.back();
+      const int32_t D = dist[(size_t)c];
+      for (int32_t s = 0; s < D - (D + 1) / 2; ++s) c = prev[(size_t)c];      // at distance ceil(D / 2) from the other end
+      if ((D & 1) && prev[(size_t)c] < c) c = prev[(size_t)c];
+      bfs(c);
+      for (int32_t v : order) root_mark[(size_t)v] = -2;
+    }
+    for (size_t i = 0; i < members.size(); ++i) fc.parent[base + i] = prev[(size_t)members[i]];
+    for (int32_t u : members) { if (!covered[(size_t)u]) { covered[(size_t)u] = 1; --left; } root_mark[(size_t)u] = -1; }
+    fc.group_off.push_back((int64_t)fc.unaries.size());
+  }
+  return fc;
+}
+
 }  // namespace lpmp
 
 using namespace lpmp;

@@ -3863,6 +3863,90 @@ path_moves_kernel(const PathRec* __restrict__ paths, const PathNode* __restrict_
   primal[2 * (int64_t)nds[0].factor] = x;
 }
 
+// ---- forest moves: exact relabelling of induced forests (lpmp_forest_moves) ---------------------------------------
+// One launch of the up kernel is the nodes of one group, one height and one form; their children are lower and were done by
+// earlier launches on the stream, so no workgroup waits for another.  T threads per node (a wave — four nodes per workgroup —
+// while neither the node nor its parent has more than PATH_WAVE_MAX labels, the workgroup above):
+//   thread x:  f[x] = n[x] (path_node_cost: the tree edges count with their message vector only), then + the row g_c[x] of every
+//              child in child order; f goes to LDS, one barrier
+//   a non-root node, thread y over the PARENT's labels:  g[y] = min_x (f[x] + c(x, y)), strict < in ascending x (path_min_plus),
+//              stored with the back-pointer to the scratch
+//   a root:    the first minimiser of f (the value / index reduction of path_moves_kernel) is its label
+// The down kernel takes one depth level >= 1 per launch, a thread per node: its label is its back-pointer at the parent's label.
+// Off-tree neighbours are never members of the group (the planner refuses such a set), so the labels read by the node costs are
+// those the group started on whatever the launches have written.
+template <int T>
+__global__ void __launch_bounds__(256)
+forest_up_kernel(const int32_t* __restrict__ list, const ForestNode* __restrict__ nodes, const int64_t* __restrict__ child_g,
+                 const PathLink* __restrict__ links, const double* __restrict__ dual, const double* __restrict__ cdata, int32_t* primal,
+                 double* rows, unsigned char* back, int64_t first, int64_t count, int tab32) {
+  constexpr int PPB = 256 / T, W = T == 64 ? PATH_WAVE_MAX : PATH_MAX_LABELS, NY = W / T, NONE = 0x7fffffff;
+  __shared__ double f[PPB][W];
+  __shared__ double red_v[4];
+  __shared__ int red_i[4];
+  const int team = threadIdx.x / T, t = threadIdx.x % T;
+  const int64_t idx = (int64_t)blockIdx.x * PPB + team;
+  if (idx >= count) return;          // (T == 64: a whole wave, and the wave form has no workgroup barrier; T == 256: never)
+  const ForestNode nd = nodes[list[first + idx]];
+  const PathNode pn{nd.dual_off, 0, 0, nd.d0, nd.factor, nd.link_begin, nd.n_links, -1, 0, 0, 0};
+  const int64_t* ch = child_g + nd.child_begin;
+  double* fv = f[team];
+#pragma unroll
+  for (int j = 0; j < NY; ++j) {
+    const int x = t + j * T;
+    if (x >= nd.d0) continue;
+    double v = path_node_cost(pn, links, dual, cdata, primal, x, tab32);
+    for (int c = 0; c < nd.n_children; ++c) v = v + rows[ch[c] + x];
+    fv[x] = v;
+  }
+  path_sync<T>();
+  if (nd.parent < 0) {
+    // the first minimiser of f: per thread in ascending x, then value / index butterflies over the wave (and the waves)
+    double bv = LPMP_INF; int bi = NONE;
+#pragma unroll
+    for (int j = 0; j < NY; ++j) { const int x = t + j * T; if (x < nd.d0 && (bi == NONE || fv[x] < bv)) { bv = fv[x]; bi = x; } }
+    double mn = decode_min<64>(bv);
+    int label = decode_min<64>((bi != NONE && bv == mn) ? bi : NONE);
+    if (T > 64) {
+      if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = mn; red_i[threadIdx.x >> 6] = label; }
+      __syncthreads();
+      mn = LPMP_INF; label = NONE;
+      for (int w = 0; w < T / 64; ++w)
+        if (red_i[w] != NONE && (label == NONE || red_v[w] < mn || (red_v[w] == mn && red_i[w] < label))) { mn = red_v[w]; label = red_i[w]; }
+    }
+    if (t == 0) primal[2 * (int64_t)nd.factor] = label;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < NY; ++j) {
+    const int y = t + j * T;
+    if (y >= nd.dq) continue;
+    double g = LPMP_INF; int b = 0;
+    switch (nd.edge_kind) {      // (uniform over the node's threads, as in path_moves_kernel)
+      case LPMP_F_PAIRWISE_DENSE:
+        if (tab32) path_min_plus<LPMP_F_PAIRWISE_DENSE, 1>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b);
+        else path_min_plus<LPMP_F_PAIRWISE_DENSE, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b);
+        break;
+      case LPMP_F_PAIRWISE_SHARED: path_min_plus<LPMP_F_PAIRWISE_SHARED, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b); break;
+      case LPMP_F_PAIRWISE_DIFF: path_min_plus<LPMP_F_PAIRWISE_DIFF, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b); break;
+      case LPMP_F_PAIRWISE_DIFF_SHIFT: path_min_plus<LPMP_F_PAIRWISE_DIFF_SHIFT, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b); break;
+      default: path_min_plus<LPMP_F_PAIRWISE_POTTS, 0>(cdata, nd.edge_const, nd.edge_d1, nd.edge_side, fv, nd.d0, y, g, b); break;
+    }
+    rows[nd.g_off + y] = g;
+    if (nd.back_wide) reinterpret_cast<unsigned short*>(back + nd.back_off)[y] = (unsigned short)b;
+    else back[nd.back_off + y] = (unsigned char)b;
+  }
+}
+__global__ void __launch_bounds__(256)
+forest_down_kernel(const int32_t* __restrict__ list, const ForestNode* __restrict__ nodes, int32_t* primal, const unsigned char* __restrict__ back,
+                   int64_t first, int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const ForestNode nd = nodes[list[first + i]];
+  const int xq = primal[2 * (int64_t)nd.parent];     // (written by this group's up sweep or by the level above: inside [0, dq))
+  primal[2 * (int64_t)nd.factor] = nd.back_wide ? (int)reinterpret_cast<const unsigned short*>(back + nd.back_off)[xq] : (int)back[nd.back_off + xq];
+}
+
 // LP::CheckPrimalConsistency (reference LP_MP.h:1067-1082): every message's two sides agree
 __global__ void __launch_bounds__(256)
 primal_check_kernel(const PrimalLink* __restrict__ links, int64_t n, const int32_t* __restrict__ primal, int* __restrict__ bad) {
@@ -4218,6 +4302,16 @@ void launch_path_moves(const PathRec* paths, const PathNode* nodes, const PathLi
   if (count <= 0) return;
   if (wide) hipLaunchKernelGGL((path_moves_kernel<256>), dim3((unsigned)count), dim3(256), 0, s, paths, nodes, links, dual, cdata, primal, back, first, count, tab32);
   else hipLaunchKernelGGL((path_moves_kernel<64>), dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, paths, nodes, links, dual, cdata, primal, back, first, count, tab32);
+}
+void launch_forest_up(const int32_t* list, const ForestNode* nodes, const int64_t* child_g, const PathLink* links, const double* dual, const double* cdata,
+                      int32_t* primal, double* rows, unsigned char* back, int64_t first, int64_t count, int wide, int tab32, hipStream_t s) {
+  if (count <= 0) return;
+  if (wide) hipLaunchKernelGGL((forest_up_kernel<256>), dim3((unsigned)count), dim3(256), 0, s, list, nodes, child_g, links, dual, cdata, primal, rows, back, first, count, tab32);
+  else hipLaunchKernelGGL((forest_up_kernel<64>), dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, list, nodes, child_g, links, dual, cdata, primal, rows, back, first, count, tab32);
+}
+void launch_forest_down(const int32_t* list, const ForestNode* nodes, int32_t* primal, const unsigned char* back, int64_t first, int64_t count, hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(forest_down_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, list, nodes, primal, back, first, count);
 }
 void launch_decode(const DecodeRec* recs, const DecodeLink* links, const double* dual, const double* cdata, int32_t* primal,
                    int64_t first, int64_t count, int width, int level, int flags, int tab32, hipStream_t s) {

@@ -113,6 +113,15 @@ struct PathLink { int64_t vec_off, peer_const; int32_t kind, pd1, side, other, o
 static_assert(sizeof(PathRec) == 16 && sizeof(PathNode) == 56 && sizeof(PathLink) == 40, "path record layout");
 constexpr int PATH_WAVE_MAX = 64;        // a wave per path while no node of it has more labels (four paths per workgroup), a workgroup above
 static_assert(PATH_MAX_LABELS <= GEN_MAXD, "path moves hold a vector of f in LDS");
+// forest moves (lpmp_forest_moves; DESIGN.md 8, forest_up_kernel / forest_down_kernel): a node of a tree.  As a PathNode: its place
+// in the packed duals, its label count, its links (PathLink records in ascending message index; on_path marks the tree edges, to
+// the parent and to the children alike).  The tree edge to the PARENT: constants, kind and second dimension of that pairwise factor,
+// the side THIS node has in it, the parent's factor and label count dq (parent < 0: a root).  Its row g of dq doubles starts at
+// element g_off of the scratch of rows, its dq back-pointers at byte back_off of the scratch of back-pointers: one byte each while
+// this node has at most 256 labels (back_wide == 0), two otherwise.  Its children: n_children entries from child_begin of the
+// child table, each the g_off of a child's row (of d0 doubles), in ascending message index of this node's message into the edge
+struct ForestNode { int64_t dual_off, edge_const, g_off, back_off; int32_t d0, factor, link_begin, n_links, edge_kind, edge_d1, edge_side, back_wide, dq, parent, child_begin, n_children; };
+static_assert(sizeof(ForestNode) == 80, "forest record layout");
 // moving label windows (lpmp_move_windows): one listed unary — its place in the packed duals, its label count (at most
 // MOVE_MAX_LABELS: a wave holds a whole vector in registers), its row of delta / cost_old / cost_new, and its links in message-list
 // order: the message vector of its side in the pairwise factor (device dual offset) ...
@@ -173,6 +182,13 @@ void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, con
 // unaries; writes the back-pointers into `back` and the new labels of the paths' nodes into primal
 void launch_path_moves(const PathRec* paths, const PathNode* nodes, const PathLink* links, const double* dual, const double* cdata,
                        int32_t* primal, unsigned char* back, int64_t first, int64_t count, int wide, int tab32, hipStream_t s);
+// forest moves, one height level of one group: the nodes list[first, first + count) all of one form — wide == 0: neither the node
+// nor its parent has more than PATH_WAVE_MAX labels (a wave per node), wide != 0: a workgroup per node.  f = node cost + the
+// children's rows; a non-root node stores its row and back-pointers, a root writes its label into primal
+void launch_forest_up(const int32_t* list, const ForestNode* nodes, const int64_t* child_g, const PathLink* links, const double* dual, const double* cdata,
+                      int32_t* primal, double* rows, unsigned char* back, int64_t first, int64_t count, int wide, int tab32, hipStream_t s);
+// ... and one depth level >= 1: primal[node] = back_node[primal[parent]]
+void launch_forest_down(const int32_t* list, const ForestNode* nodes, int32_t* primal, const unsigned char* back, int64_t first, int64_t count, hipStream_t s);
 void launch_primal_check(const PrimalLink* links, int64_t n, const int32_t* primal, int* bad, hipStream_t s);
 void launch_primal_cost(const LbRec* recs, const double* dual, const double* cdata, const int32_t* primal, double* out, int64_t count, int tab32, hipStream_t s);
 void launch_lb_collect_stale(const double* lb, int64_t n, int32_t* list, unsigned long long* counter, hipStream_t s);

@@ -1328,6 +1328,37 @@ DecodePlan Plan::decode_plan(int direction) const {
   return dp;
 }
 
+// ---- what path moves and forest moves take (plan.hpp, PairSides) ----------------------------------------------------------------
+static bool is_unary_pairwise(const Plan& p, int64_t m) {
+  const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)m]];
+  return mt.kind == LPMP_M_UNARY_PAIRWISE && (mt.param == 0 || mt.param == 1) && p.f_kind[p.m_left[(size_t)m]] == LPMP_F_VECTOR &&
+         p.f_kind[p.m_right[(size_t)m]] != LPMP_F_VECTOR;
+}
+PairSides Plan::pair_sides() const {
+  PairSides ps;
+  ps.side_unary.assign(2 * (size_t)nf, -1);
+  ps.side_count.assign(2 * (size_t)nf, 0);
+  for (int64_t m = 0; m < nm; ++m) {
+    if (!is_unary_pairwise(*this, m)) continue;
+    const size_t slot = 2 * (size_t)m_right[(size_t)m] + (size_t)mtypes[(size_t)m_type[(size_t)m]].param;
+    if (ps.side_count[slot] < 2) ++ps.side_count[slot];
+    ps.side_unary[slot] = m_left[(size_t)m];
+  }
+  return ps;
+}
+std::string Plan::move_obstacle(int32_t u, const PairSides& ps, const char* move) const {
+  auto S = [](int64_t v) { return std::to_string(v); };
+  if (f_dim0[u] > PATH_MAX_LABELS) return "has " + S(f_dim0[u]) + " labels (a " + move + " move takes at most " + S(PATH_MAX_LABELS) + ")";
+  for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) {
+    const MsgEntry& me = fm[(size_t)k];
+    if (me.role != 0 || !is_unary_pairwise(*this, me.msg)) return "has a message that is not a unary-pairwise message with the factor as its unary";
+    const size_t s = 2 * (size_t)m_right[(size_t)me.msg];
+    if (ps.side_count[s] != 1 || ps.side_count[s + 1] != 1 || ps.side_unary[s] == ps.side_unary[s + 1])
+      return "is next to pairwise factor " + S(m_right[(size_t)me.msg]) + ", which does not have exactly one unary on each side from two different unaries";
+  }
+  return "";
+}
+
 // ---- path moves (plan.hpp, PathPlan) ----------------------------------------------------------------------------------------
 PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* un, const std::string& who) const {
   PathPlan pp;
@@ -1360,32 +1391,15 @@ PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64
   pp.path_off.assign(path_off, path_off + n_paths + 1);
   pp.unaries.assign(un, un + ne);
   // the unary on each side of every pairwise factor, from all unary-pairwise messages (as in decode_plan)
-  std::vector<int32_t> side_unary(2 * (size_t)nf, -1);
-  std::vector<uint8_t> side_count(2 * (size_t)nf, 0);
-  auto unary_pairwise = [&](int64_t m) {
-    const lpmp_msg_type& mt = mtypes[(size_t)m_type[(size_t)m]];
-    return mt.kind == LPMP_M_UNARY_PAIRWISE && (mt.param == 0 || mt.param == 1) && f_kind[m_left[(size_t)m]] == LPMP_F_VECTOR && f_kind[m_right[(size_t)m]] != LPMP_F_VECTOR;
-  };
-  for (int64_t m = 0; m < nm; ++m) {
-    if (!unary_pairwise(m)) continue;
-    const size_t slot = 2 * (size_t)m_right[(size_t)m] + (size_t)mtypes[(size_t)m_type[(size_t)m]].param;
-    if (side_count[slot] < 2) ++side_count[slot];
-    side_unary[slot] = m_left[(size_t)m];
-  }
+  const PairSides sides = pair_sides();
+  const std::vector<int32_t>& side_unary = sides.side_unary;
   // the unsupported shapes: the lowest listed unary that has one
   int32_t bad = -1; std::string what;
-  auto offend = [&](int32_t u, const std::string& w) { if (bad < 0 || u < bad) { bad = u; what = w; } };
   for (int64_t e = 0; e < ne; ++e) {
     const int32_t u = un[e];
     if (bad >= 0 && u >= bad) continue;
-    if (f_dim0[u] > PATH_MAX_LABELS) offend(u, "has " + S(f_dim0[u]) + " labels (a path move takes at most " + S(PATH_MAX_LABELS) + ")");
-    for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) {
-      const MsgEntry& me = fm[(size_t)k];
-      if (me.role != 0 || !unary_pairwise(me.msg)) { offend(u, "has a message that is not a unary-pairwise message with the factor as its unary"); continue; }
-      const size_t s = 2 * (size_t)m_right[(size_t)me.msg];
-      if (side_count[s] != 1 || side_count[s + 1] != 1 || side_unary[s] == side_unary[s + 1])
-        offend(u, "is next to pairwise factor " + S(m_right[(size_t)me.msg]) + ", which does not have exactly one unary on each side from two different unaries");
-    }
+    const std::string w = move_obstacle(u, sides, "path");
+    if (!w.empty()) { bad = u; what = w; }
   }
   if (bad >= 0) {
     pp.bad_factor = bad;
@@ -1435,6 +1449,141 @@ PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64
   }
   if (pp.links.size() > (size_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 links");
   return pp;
+}
+
+// ---- forest moves (plan.hpp, ForestPlan) --------------------------------------------------------------------------------------
+ForestPlan Plan::forest_plan(int64_t n_groups, const int64_t* group_off, const int32_t* un, const int32_t* par, const std::string& who) const {
+  ForestPlan fp;
+  auto S = [](int64_t v) { return std::to_string(v); };
+  if (n_groups < 0 || !group_off) fail(who + ": bad argument");
+  if (group_off[0] != 0) fail(who + ": group_off[0] is " + S(group_off[0]) + ", not 0");
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (group_off[g + 1] < group_off[g]) fail(who + ": group_off is not monotone at group " + S(g));
+  const int64_t ne = group_off[n_groups];
+  if (ne > (int64_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 entries");
+  if (ne > 0 && (!un || !par)) fail(who + ": null list of unaries or parents");
+  for (int64_t e = 0; e < ne; ++e) {
+    const int32_t f = un[e];
+    if (f < 0 || f >= nf) fail(who + ": factor index " + S(f) + " (entry " + S(e) + ") is out of range");
+    if (f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + S(f) + " (entry " + S(e) + ") is not a VECTOR factor");
+  }
+  // where a unary sits in the group at hand: group stamp and entry
+  std::vector<int64_t> grp_of((size_t)nf, -1), ent_of((size_t)nf, 0);
+  for (int64_t g = 0; g < n_groups; ++g)
+    for (int64_t e = group_off[g]; e < group_off[g + 1]; ++e) {
+      const size_t f = (size_t)un[e];
+      if (grp_of[f] == g) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") appears twice in group " + S(g) + " (first: entry " + S(ent_of[f]) + ")");
+      grp_of[f] = g; ent_of[f] = e;
+    }
+  fp.group_off.assign(group_off, group_off + n_groups + 1);
+  fp.unaries.assign(un, un + ne);
+  fp.parent.assign(par, par + ne);
+  fp.parent_entry.assign((size_t)ne, -1);
+  std::fill(grp_of.begin(), grp_of.end(), -1);
+  for (int64_t g = 0; g < n_groups; ++g) {
+    for (int64_t e = group_off[g]; e < group_off[g + 1]; ++e) { grp_of[(size_t)un[e]] = g; ent_of[(size_t)un[e]] = e; }
+    for (int64_t e = group_off[g]; e < group_off[g + 1]; ++e) {
+      const int32_t q = par[e];
+      if (q == -1) continue;
+      if (q == un[e]) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") is its own parent");
+      if (q < 0 || q >= nf || grp_of[(size_t)q] != g)
+        fail(who + ": the parent " + S(q) + " of factor " + S(un[e]) + " (entry " + S(e) + ") is neither -1 nor a member of group " + S(g));
+      fp.parent_entry[(size_t)e] = (int32_t)ent_of[(size_t)q];
+    }
+  }
+  // cycles of parent pointers: walk up from every entry; a walk that meets itself has found one.  The lowest entry on any
+  { std::vector<int64_t> seen((size_t)ne, -1);      // the walk that reached the entry
+    int64_t lowest = -1;
+    for (int64_t e0 = 0; e0 < ne; ++e0) {
+      int64_t e = e0;
+      while (e >= 0 && seen[(size_t)e] < 0) { seen[(size_t)e] = e0; e = fp.parent_entry[(size_t)e]; }
+      if (e < 0 || seen[(size_t)e] != e0) continue;
+      int64_t lo = e;
+      for (int64_t c = fp.parent_entry[(size_t)e]; c != e; c = fp.parent_entry[(size_t)c]) lo = std::min(lo, c);
+      if (lowest < 0 || lo < lowest) lowest = lo;
+    }
+    if (lowest >= 0) fail(who + ": the parent pointers close a cycle through factor " + S(un[lowest]) + " (entry " + S(lowest) + ")");
+  }
+  // the unsupported shapes: the lowest listed unary that has one
+  const PairSides sides = pair_sides();
+  { int32_t bad = -1; std::string what;
+    for (int64_t e = 0; e < ne; ++e) {
+      const int32_t u = un[e];
+      if (bad >= 0 && u >= bad) continue;
+      const std::string w = move_obstacle(u, sides, "forest");
+      if (!w.empty()) { bad = u; what = w; }
+    }
+    if (bad >= 0) {
+      fp.bad_factor = bad;
+      fp.why = who + ": factor " + S(bad) + " " + what + " (DESIGN.md 8, forest moves)";
+      return fp;
+    }
+  }
+  // links in ascending message index, the tree edges and the children
+  fp.edge.assign((size_t)ne, -1); fp.edge_side.assign((size_t)ne, 0);
+  fp.link_off.assign(1, 0); fp.child_off.assign(1, 0);
+  fp.height.assign((size_t)ne, 0); fp.depth.assign((size_t)ne, -1);
+  fp.group_height.assign((size_t)n_groups, -1);
+  std::fill(grp_of.begin(), grp_of.end(), -1);
+  std::vector<int32_t> msgs, by_depth;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    const int64_t b = group_off[g], en = group_off[g + 1];
+    for (int64_t e = b; e < en; ++e) { grp_of[(size_t)un[e]] = g; ent_of[(size_t)un[e]] = e; }
+    for (int64_t e = b; e < en; ++e) {
+      const int32_t u = un[e];
+      fp.max_labels = std::max(fp.max_labels, f_dim0[u]);
+      msgs.clear();
+      for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) msgs.push_back(fm[(size_t)k].msg);
+      std::sort(msgs.begin(), msgs.end());
+      for (int32_t m : msgs) {
+        const int32_t p = m_right[(size_t)m], side = mtypes[(size_t)m_type[(size_t)m]].param, v = sides.side_unary[2 * (size_t)p + (size_t)(1 - side)];
+        int32_t tree = 0;
+        if (grp_of[(size_t)v] == g) {
+          const int64_t ev = ent_of[(size_t)v];
+          if (fp.parent_entry[(size_t)e] == ev) {
+            if (fp.edge[(size_t)e] >= 0)
+              fail(who + ": more than one pairwise factor (" + S(fp.edge[(size_t)e]) + " and " + S(p) + ") joins factor " + S(u) + " (entry " + S(e) + ") and its parent, factor " + S(v) + " (entry " + S(ev) + ")");
+            fp.edge[(size_t)e] = p; fp.edge_side[(size_t)e] = side;
+            tree = 1;
+          } else if (fp.parent_entry[(size_t)ev] == e) {
+            fp.children.push_back((int32_t)ev);     // (a second factor to the same child: refused at the child)
+            tree = 2;
+          } else {
+            fail(who + ": pairwise factor " + S(p) + " joins factor " + S(u) + " (entry " + S(e) + ") and factor " + S(v) + " (entry " + S(ev) + "), members of group " + S(g) +
+                 " that are not child and parent (the members of a group must induce a forest)");
+          }
+        }
+        fp.links.push_back({p, side, v, tree});
+        if (!tree) ++fp.n_off_tree_links;
+      }
+      fp.link_off.push_back((int64_t)fp.links.size());
+      fp.child_off.push_back((int64_t)fp.children.size());
+      if (fp.parent_entry[(size_t)e] >= 0) {
+        if (fp.edge[(size_t)e] < 0)
+          fail(who + ": no pairwise factor joins factor " + S(u) + " (entry " + S(e) + ") and its parent, factor " + S(par[e]) + " (entry " + S(fp.parent_entry[(size_t)e]) + ")");
+        ++fp.n_tree_edges;
+      } else ++fp.n_trees;
+    }
+    // depths (walk up to the first entry that has one), then heights from the deepest entries upwards
+    for (int64_t e0 = b; e0 < en; ++e0) {
+      int32_t steps = 0;
+      int64_t e = e0;
+      while (fp.depth[(size_t)e] < 0 && fp.parent_entry[(size_t)e] >= 0) { e = fp.parent_entry[(size_t)e]; ++steps; }
+      int32_t d = (fp.depth[(size_t)e] < 0 ? 0 : fp.depth[(size_t)e]) + steps;
+      for (e = e0; fp.depth[(size_t)e] < 0; e = fp.parent_entry[(size_t)e]) { fp.depth[(size_t)e] = d--; if (fp.parent_entry[(size_t)e] < 0) break; }
+    }
+    by_depth.clear();
+    for (int64_t e = b; e < en; ++e) by_depth.push_back((int32_t)e);
+    std::stable_sort(by_depth.begin(), by_depth.end(), [&](int32_t x, int32_t y) { return fp.depth[(size_t)x] > fp.depth[(size_t)y]; });
+    for (int32_t e : by_depth) {
+      const int32_t q = fp.parent_entry[(size_t)e];
+      if (q >= 0) fp.height[(size_t)q] = std::max(fp.height[(size_t)q], fp.height[(size_t)e] + 1);
+      fp.group_height[(size_t)g] = std::max(fp.group_height[(size_t)g], fp.height[(size_t)e]);
+    }
+    fp.max_height = std::max(fp.max_height, fp.group_height[(size_t)g]);
+  }
+  if (fp.links.size() > (size_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 links");
+  return fp;
 }
 
 // ---- partition sweeps (reference LP_MP.h:1717-1843).  union_find.hxx:5-93: union by size, the first argument's root

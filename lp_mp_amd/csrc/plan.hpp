@@ -315,6 +315,32 @@ struct PathPlan {
   int32_t max_labels = 0;
 };
 
+// Forest moves (lpmp_forest_moves): the structure of a forest set.  Groups of VECTOR factors with a parent each (a factor
+// index, -1 for a root); a child and its parent are joined by exactly one pairwise factor (the tree edge), found here, and no other
+// pairwise factor joins two members of a group.  Per entry, in the caller's order: the parent's entry, the tree edge with the side
+// the ENTRY has in it, the links in ascending message index (tree: 0 = a cost line, 1 = the edge to the parent, 2 = to a child),
+// the children (entries) in ascending message index of the entry's message into the tree edge, the height (0 for a leaf) and the
+// depth (0 for a root).
+struct ForestLinkPlan { int32_t p, side, other, tree; };
+struct ForestPlan {
+  std::string why;                       // "" or why the set is refused as unsupported (names the lowest offending listed unary)
+  int32_t bad_factor = -1;
+  std::vector<int64_t> group_off;
+  std::vector<int32_t> unaries, parent, parent_entry;
+  std::vector<int32_t> edge, edge_side;  // per entry; -1 / 0 for a root
+  std::vector<int64_t> link_off;         // CSR over the entries
+  std::vector<ForestLinkPlan> links;
+  std::vector<int64_t> child_off;        // CSR over the entries
+  std::vector<int32_t> children;
+  std::vector<int32_t> height, depth;
+  std::vector<int32_t> group_height;     // per group: the highest height (-1: an empty group)
+  int64_t n_trees = 0, n_tree_edges = 0, n_off_tree_links = 0;
+  int32_t max_height = 0, max_labels = 0;
+};
+// The unary on each side of every pairwise factor, from all unary-pairwise messages: side_unary[2 p + s], and how many messages
+// name that side (saturating at 2).  What path sets, forest sets and the forest cover judge a unary by (Plan::move_obstacle)
+struct PairSides { std::vector<int32_t> side_unary; std::vector<uint8_t> side_count; };
+
 struct Plan {
   // copied structure (no cost data)
   int32_t n_ftypes = 0, n_mtypes = 0, n_tables = 0;
@@ -424,6 +450,17 @@ struct Plan {
   // move does not take comes back with PathPlan::why set.  Order of the checks: offsets, indices and kinds, duplicates inside a
   // group; then the unsupported shapes; then the path edges (they are read off the supported shape)
   PathPlan path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, const std::string& who) const;
+  // Structure of a forest set (include/lpmp_engine.h, lpmp_forest_set_create): group_off [n_groups + 1] in entries, unaries and
+  // parent [entries].  Throws std::runtime_error (LPMP_ERR_INVALID) naming the entry, with `who` in front; a set the move does
+  // not take comes back with ForestPlan::why set.  Order of the checks: offsets, indices and kinds, duplicates inside a group,
+  // parents, cycles; then the unsupported shapes (those of path_plan); then the tree edges and the pairwise factors that would
+  // close a cycle or join two trees
+  ForestPlan forest_plan(int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, const std::string& who) const;
+  // what the unsupported-shape check of path_plan / forest_plan reads, and the check itself on VECTOR factor u: "" or what is
+  // wrong with it (a message that is not unary-pairwise with u on the left; an adjacent pairwise factor without exactly one
+  // unary on each side from two different unaries; more than PATH_MAX_LABELS labels — `move` is the word the message uses)
+  PairSides pair_sides() const;
+  std::string move_obstacle(int32_t u, const PairSides& ps, const char* move) const;
 };
 
 // The band of a difference vector D of n entries, by the BITS of the doubles (-0.0 and +0.0 differ): lo = the first index whose
@@ -434,6 +471,11 @@ void diff_band(const double* D, int64_t n, int32_t* lo, int32_t* hi);
 
 // graph.cpp: an order of all factors with the updated ones colour by colour (rank[f] = position; returns the number of colours)
 int32_t suggest_order(const Plan& p, uint64_t seed, int32_t* rank);
+// graph.cpp: a cover of the unaries a forest move takes (Plan::move_obstacle finds none) by groups that each induce a forest,
+// every tree rooted at a centre (include/lpmp_engine.h, lpmp_plan_suggest_forests).  group_off in entries; returns the number of
+// VECTOR factors left out
+struct ForestCover { std::vector<int64_t> group_off; std::vector<int32_t> unaries, parent; int64_t n_left_out = 0; };
+ForestCover suggest_forests(const Plan& p, int64_t max_groups);
 
 // ---- order.cpp: ticket orders of the Infinity-Cache chain launches ------------------------------------------------------------
 // A skewed order of the blocks of consecutive steps: new_of[base[s] + j] = ticket of block j of step s (base: the steps' blocks in

@@ -84,6 +84,8 @@ EXPORTS = [
     "lpmp_move_windows", "lpmp_plan_window_info",
     "lpmp_path_set_create", "lpmp_path_set_destroy", "lpmp_path_set_n_groups", "lpmp_path_set_n_paths", "lpmp_path_set_longest",
     "lpmp_path_set_scratch_bytes", "lpmp_path_moves", "lpmp_plan_path_info",
+    "lpmp_forest_set_create", "lpmp_forest_set_destroy", "lpmp_forest_set_n_groups", "lpmp_forest_set_n_trees", "lpmp_forest_set_max_height",
+    "lpmp_forest_set_scratch_bytes", "lpmp_forest_moves", "lpmp_plan_forest_info", "lpmp_plan_suggest_forests",
 ]
 
 
@@ -249,6 +251,16 @@ def lib():
                 getattr(L, n).argtypes = [C.c_void_p]
             L.lpmp_path_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             L.lpmp_plan_path_info.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_char_p, C.c_int]
+        if hasattr(L, "lpmp_forest_set_create"):     # (absent only in an older build loaded through LPMP_ENGINE_SO for an A/B)
+            L.lpmp_forest_set_create.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+            L.lpmp_forest_set_destroy.restype = None
+            L.lpmp_forest_set_destroy.argtypes = [C.c_void_p]
+            for n in ("lpmp_forest_set_n_groups", "lpmp_forest_set_n_trees", "lpmp_forest_set_max_height", "lpmp_forest_set_scratch_bytes"):
+                getattr(L, n).restype = C.c_int64
+                getattr(L, n).argtypes = [C.c_void_p]
+            L.lpmp_forest_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.lpmp_plan_forest_info.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_int]
+            L.lpmp_plan_suggest_forests.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -603,6 +615,60 @@ def _path_info(self, groups) -> dict:
 Plan.path_info = _path_info
 
 
+def flatten_forest_groups(groups):
+    """(group_off [n_groups + 1] int64 in entries, unaries int32, parent int32) of ``groups``: a sequence of (unaries, parent) pairs
+    of equally long sequences — parent[i] the factor index of the parent of unaries[i], -1 for a root — the arrays of
+    lpmp_forest_set_create"""
+    group_off, un, par = [0], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for u, q in groups:
+        u, q = np.asarray(u, np.int64).reshape(-1), np.asarray(q, np.int64).reshape(-1)
+        if u.shape[0] != q.shape[0]:
+            raise ValueError("forest groups: %d unaries with %d parents" % (u.shape[0], q.shape[0]))
+        un.append(u); par.append(q)
+        group_off.append(group_off[-1] + u.shape[0])
+    un, par = np.concatenate(un), np.concatenate(par)
+    for x in (un, par):
+        if x.shape[0] and (x.min() < -(1 << 31) or x.max() >= (1 << 31)):
+            raise ValueError("forest groups: a factor index does not fit an int32")
+    return np.asarray(group_off, np.int64), un.astype(np.int32), par.astype(np.int32)
+
+
+def _valid_ptr(a):
+    return a if a.shape[0] else np.zeros(1, a.dtype)      # (an empty list: still a valid pointer)
+
+
+def _forest_info(self, groups) -> dict:
+    """structure of ``Engine.forest_set(groups)`` (lpmp_plan_forest_info): ``n_trees``, ``n_tree_edges`` (pairwise factors the up
+    sweep reads as tables), ``n_off_tree_links`` (cost lines a move reads) and ``max_height``.  EngineError with the refusals of
+    lpmp_forest_set_create: LPMP_ERR_INVALID naming the entry, LPMP_ERR_UNSUPPORTED naming the lowest listed factor a move does
+    not take."""
+    go, un, par = flatten_forest_groups(groups)
+    un, par = _valid_ptr(un), _valid_ptr(par)
+    v = [C.c_int64() for _ in range(4)]
+    buf = C.create_string_buffer(512)
+    _chk(self.L.lpmp_plan_forest_info(self.h, int(go.shape[0]) - 1, go.ctypes.data, un.ctypes.data, par.ctypes.data,
+                                      *[C.addressof(x) for x in v], buf, 512))
+    return dict(zip(("n_trees", "n_tree_edges", "n_off_tree_links", "max_height"), [x.value for x in v]))
+
+
+def _suggest_forests(self, max_groups: int = 0, left_out=None):
+    """a cover of the model by forest groups for ``Engine.forest_set`` / ``LP.forest_moves`` (lpmp_plan_suggest_forests): a list
+    of (unaries, parent) int32 array pairs, every tree rooted at a centre; deterministic.  ``max_groups`` > 0 stops after that
+    many groups.  ``left_out`` (a list) receives the number of VECTOR factors a forest move does not take."""
+    ng, ne, lo = C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(self.L.lpmp_plan_suggest_forests(self.h, int(max_groups), C.addressof(ng), C.addressof(ne), None, None, None, C.addressof(lo)))
+    go = np.zeros(ng.value + 1, np.int64)
+    un, par = np.zeros(max(ne.value, 1), np.int32), np.zeros(max(ne.value, 1), np.int32)
+    _chk(self.L.lpmp_plan_suggest_forests(self.h, int(max_groups), None, None, go.ctypes.data, un.ctypes.data, par.ctypes.data, None))
+    if left_out is not None:
+        left_out.append(int(lo.value))
+    return [(un[go[g]:go[g + 1]].copy(), par[go[g]:go[g + 1]].copy()) for g in range(ng.value)]
+
+
+Plan.forest_info = _forest_info
+Plan.suggest_forests = _suggest_forests
+
+
 def graph_colour_major_order(n: int, edge_i, edge_j, seed: int = 0):
     """(rank[n] int64, number of colours): colour-major variable order of a pairwise graph on the planner's threads
     (lpmp_graph_colour_major_order; the numpy statement of the same algorithm is ordering.colour_major_order_numpy)"""
@@ -915,6 +981,13 @@ class Engine:
         paths, each a sequence of factor indices whose consecutive members share exactly one pairwise factor.  ``PathSet.move``
         relabels every path exactly, given all other labels"""
         return PathSet(self, groups)
+
+    def forest_set(self, groups) -> "ForestSet":
+        """a prepared set of forests of VECTOR factors (lpmp_forest_set_create): ``groups`` is a sequence of (unaries, parent) pairs
+        — parent[i] the factor index of the parent of unaries[i], -1 for a root — whose members induce a forest;
+        ``Plan.suggest_forests`` covers any model with such groups, ``model.forests_from_paths`` turns path groups into them.
+        ``ForestSet.move`` relabels every tree exactly, given all other labels"""
+        return ForestSet(self, groups)
 
     def check_primal_consistency(self) -> bool:
         out = C.c_int()
@@ -1229,6 +1302,38 @@ class PathSet:
         """``rounds`` times over the groups in their order: every path takes the labels that minimise the energy over it given all
         other labels (lpmp_path_moves).  Asynchronous on the engine's stream; reads duals, constants and labels, writes labels."""
         _chk(self.L.lpmp_path_moves(self.e.h, self.h, int(rounds)))
+
+
+class ForestSet:
+    """Prepared groups of forests of the engine's uploaded model (include/lpmp_engine.h, lpmp_forest_set_* / lpmp_forest_moves).
+    Structure, like a ``PathSet``: it stays valid across new costs, passes, decodes and window moves; after the engine's next
+    ``upload`` every move raises (LPMP_ERR_STATE) and ``close`` still works."""
+
+    def __init__(self, engine: Engine, groups):
+        self.e = engine
+        self.L = engine.L
+        go, un, par = flatten_forest_groups(groups)
+        un, par = _valid_ptr(un), _valid_ptr(par)
+        h = C.c_void_p()
+        _chk(self.L.lpmp_forest_set_create(engine.h, int(go.shape[0]) - 1, go.ctypes.data, un.ctypes.data, par.ctypes.data, C.addressof(h)))
+        self.h = h.value
+        self.n_groups = int(self.L.lpmp_forest_set_n_groups(self.h))
+        self.n_trees = int(self.L.lpmp_forest_set_n_trees(self.h))
+        self.max_height = int(self.L.lpmp_forest_set_max_height(self.h))
+        self.scratch_bytes = int(self.L.lpmp_forest_set_scratch_bytes(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lpmp_forest_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def move(self, rounds: int = 1):
+        """``rounds`` times over the groups in their order: every tree takes the labels that minimise the energy over it given all
+        other labels (lpmp_forest_moves).  Asynchronous on the engine's stream; reads duals, constants and labels, writes labels."""
+        _chk(self.L.lpmp_forest_moves(self.e.h, self.h, int(rounds)))
 
 
 def device_identity(device: int = 0) -> str:

@@ -663,6 +663,23 @@ class LP:
         finally:
             ps.close()
 
+    def forest_moves(self, groups=None, rounds: int = 1) -> float:
+        """exact relabelling of induced forests given all other labels (Engine.forest_set / ForestSet.move; no
+        reference counterpart): ``groups`` is a sequence of (unaries, parent) pairs of vector-factor handles, parent[i] the handle
+        of the parent of unaries[i] or -1 for a root; None takes the cover the engine suggests for this LP
+        (``Plan.suggest_forests``), which any graph has.  Runs the groups in order ``rounds`` times on the labels the primal array
+        holds and returns EvaluatePrimal(); on a complete labelling that cost never rises.  The prepared set is made and closed
+        here: keep ``Engine.forest_set`` for repeated moves."""
+        e = self._ready()
+        if groups is None:
+            groups = e.plan.suggest_forests()
+        fs = e.forest_set(groups)
+        try:
+            fs.move(rounds)
+            return e.evaluate_primal()
+        finally:
+            fs.close()
+
     def readout(self, factor_handles=None):
         """a prepared read-out (Engine.readout; no reference counterpart) of the listed vector factors — what
         ``add_factor`` returned for them, None: all of them — with ``labels()``, ``vectors()`` and ``beliefs()`` into host or device

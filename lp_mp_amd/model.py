@@ -568,6 +568,18 @@ def diff_shift_is_banded(D, d0: int, d1: int) -> bool:
     return (hi - lo + 1) * DIFF_BAND_DIV <= d0 + d1 - 1
 
 
+def forests_from_paths(path_groups):
+    """the groups of ``Engine.path_set`` (a sequence of groups, each a sequence of paths of factor indices) as the forest groups of
+    ``Engine.forest_set``: one (unaries, parent) int32 array pair per group, the parent of a member the NEXT member of its path
+    and the last member the root — the rooting under which a forest move gives the labels of the path move bit for bit"""
+    out = []
+    for g in path_groups:
+        un = [int(f) for path in g for f in path]
+        par = [int(q) for path in g for q in list(path[1:]) + [-1]]
+        out.append((np.asarray(un, np.int32).reshape(-1), np.asarray(par, np.int32).reshape(-1)))
+    return out
+
+
 class ModelBuilder:
     """Collects factors / messages / relations in insertion order (bulk or one at a time)."""
 
