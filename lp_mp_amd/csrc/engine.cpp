@@ -2249,7 +2249,8 @@ static void upload_unset_primal(lpmp_engine* e) {
 }
 static void ensure_primal(lpmp_engine* e) {
   if (e->model.have_primal) return;
-  e->model.release_primal();   // a previous attempt may have stopped half way
+  // (every refusal below comes before anything is released or allocated: on a model this code refuses, the array of unset labels
+  // that lpmp_path_moves / lpmp_forest_moves / lpmp_readout_labels keep — primal_unset_only — survives the refused call)
   const Plan& p = e->model.plan->p;
   for (const auto& mt : p.mtypes)
     if (mt.kind != LPMP_M_UNARY_PAIRWISE)
@@ -2283,6 +2284,7 @@ static void ensure_primal(lpmp_engine* e) {
       touched[r] = 1;
     } else rest.push_back(k);
   }
+  e->model.release_primal();   // a previous attempt may have stopped half way
   if (pw_computes) {
     // conditionally_init_primal reaches one step further: a pairwise factor whose slot changes initialises all its unaries
     for (int64_t m = 0; m < p.nm; ++m) if (touched[p.m_right[m]]) touched[p.m_left[m]] = 2;
@@ -2906,8 +2908,8 @@ int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_m
     if (!e->model.have_primal && !e->model.primal_unset_only) {
       try { ensure_primal(e); }
       catch (const UnsupportedError&) {
-        // a model the rounding code does not take (messages other than unary-pairwise): no call can set a label, every slot is
-        // unset.  The array is made once and remembered until release_primal (the model goes, or another call tries the rounding tables)
+        // a model the rounding code does not take (messages other than unary-pairwise): only a path or forest move sets a label, every
+        // other slot is unset.  The array is made once and remembered until release_primal (the model goes); a refused call leaves it (ensure_primal)
         e->model.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)e->model.plan->p.nf));
         upload_unset_primal(e);
         e->model.primal_unset_only = true;
@@ -3133,7 +3135,7 @@ int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta,
     launch_move_shifts(ws->pairs, ws->n_pairwise, d_delta, m.d_const, m.d_lb, e->stream);
     launch_move_windows(ws->recs, ws->links, ws->n, d_delta, m.d_dual, m.d_lb, d_cost[0], d_cost[1], cost_stride, e->stream);
     HIP_CHECK(hipGetLastError());
-    if (m.have_primal) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
+    if (m.have_primal || m.primal_unset_only) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
     if (host_delta || host_costs) HIP_CHECK(hipStreamSynchronize(e->stream));   // the caller's arrays are the caller's again
   });
 }
@@ -3367,7 +3369,8 @@ int lpmp_invalidate_lower_bounds(lpmp_engine* e) {
 static void costs_changed(lpmp_engine* e) {
   HIP_CHECK(hipMemsetAsync(e->model.d_lb, 0xFF, (size_t)e->model.plan->p.nf * sizeof(double), e->stream));   // all NaN, as after the upload
   e->model.lb_all_stale = true;
-  if (e->model.have_primal) { upload_unset_primal(e); e->model.primal_t = 0; }
+  // (primal_unset_only: labels that a path or forest move wrote into the array of unset labels of a model the rounding code refuses)
+  if (e->model.have_primal || e->model.primal_unset_only) { upload_unset_primal(e); e->model.primal_t = 0; }
 }
 int lpmp_upload_costs(lpmp_engine* e, const double* const_data, int const_mem, const double* dual_data, int dual_mem) {
   return guarded([&] {
@@ -3496,7 +3499,7 @@ int lpmp_set_constants(lpmp_engine* e, int64_t n, const int32_t* factors, const 
     }
     launch_set_constants(m.d_setcrecs, n, s.src, s.stride, m.d_const, m.d_lb, e->stream);
     HIP_CHECK(hipGetLastError());
-    if (m.have_primal) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_upload_costs: the labels belong to the old costs
+    if (m.have_primal || m.primal_unset_only) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_upload_costs: the labels belong to the old costs
     HIP_CHECK(hipStreamSynchronize(e->stream));   // the record buffer is refilled by the next call; the caller's source is the caller's again
   });
 }

@@ -49,6 +49,25 @@ The contract, call by call (op -> paragraph of include/lpmp_engine.h -> statemen
                                                                         (decode_cases.cost_line, readout_cases.cost_table); new costs
                                                                         and listed rows give {scale, integer shift}
                                                                         (recost_cases.recost_shift, repool_cases.rows_for_shift)
+  path_set_create / _destroy  lpmp_path_set_create ("counted ONCE by    the groups are kept by slot (path_list); create counts once in
+                              lpmp_schedules_built")                    schedules_built; after an upload a move on the set is
+                                                                        LPMP_ERR_STATE and destroying it stays legal
+  forest_set_create/_destroy  lpmp_forest_set_create                    as above (forest_list; None: the cover of Plan.suggest_forests())
+  path_moves(slot, rounds)    lpmp_path_moves / lpmp_forest_moves       labels = path_moves_cases.path_moves_reference /
+  forest_moves(slot, rounds)  ("reads the duals, the constants and the  forest_moves_cases.forest_moves_reference(eff model, shadow
+                              primal array, writes only the primal      duals, labels, groups, rounds), rounds in 0 .. 3.  Duals,
+                              array")                                   bounds, weight mode, schedules, schedules_built, read-outs and
+                                                                        window sets do not move
+  upload_primal(seed, form)   lpmp_upload_primal                        the labels given (primal_for): random; partly_unset (some
+                                                                        unaries hold their dimension); stray (negative entries).  A move
+                                                                        counts an off-path neighbour's unset label as its last label and
+                                                                        a negative one as 0 (the two ..._unset_neighbour_is_clamped tests)
+  (a model the rounding code  the "array of unset labels" sentences of  the moves are stated on the grid that is the first factors of the
+  refuses: rlists)            lpmp_path_moves / lpmp_forest_moves /     model, with the prefix of the duals and constants (move_model);
+                              lpmp_readout_labels                       they write the unary slots only and no pairwise slot; ro_labels
+                                                                        sees them; every cost change unsets them; a refused call
+                                                                        (download_primal, evaluate_primal, check_primal_consistency,
+                                                                        upload_primal, ..._pass_and_primal, decode_primal) leaves them
   lower_bound                 lpmp_lower_bound                          Oracle.LowerBound
   factor_lower_bounds         lpmp_factor_lower_bounds                  Oracle.factor_lower_bound per factor
   download_duals              lpmp_download_duals                       Oracle.duals
@@ -74,8 +93,10 @@ from oracle.binding import Oracle
 
 import decode_cases as DC
 import diff_shift_cases as DS
+import forest_moves_cases as FM
 import mixed_precision_cases as MP
 import move_windows_cases as MW
+import path_moves_cases as PM
 import readout_cases as RO
 import recost_cases as RC
 import repool_cases as RP
@@ -92,7 +113,7 @@ PAIR_TOL = 1e-12          # tests/test_speculation_gpu.py lines 115-121: bounds 
 
 OBSERVING = ("lb", "flb", "dl", "labels", "ro_labels", "ro_vectors", "ro_beliefs")
 COST = ("cold", "warm", "vectors", "zero", "consts", "pool", "duals", "move")
-STATE = ("pass", "dir", "custom", "primal_pass", "decode", "mode", "rtype", "knob") + COST + ("reupload", "refused")
+STATE = ("pass", "dir", "custom", "primal_pass", "decode", "mode", "rtype", "knob") + COST + ("reupload", "refused", "relabel", "sets")
 OP_CLASS = {
     "compute_pass": "pass", "forward_pass": "dir", "backward_pass": "dir",
     "compute_pass_custom": "custom", "schedule_create": "custom", "schedule_run": "custom", "schedule_destroy": "custom",
@@ -105,6 +126,8 @@ OP_CLASS = {
     "lower_bound": "lb", "factor_lower_bounds": "flb", "download_duals": "dl", "labels": "labels",
     "ro_labels": "ro_labels", "ro_vectors": "ro_vectors", "ro_beliefs": "ro_beliefs",
     "window_set_create": "move", "window_set_destroy": "move", "move_windows": "move",
+    "path_moves": "relabel", "forest_moves": "relabel", "upload_primal": "relabel",
+    "path_set_create": "sets", "forest_set_create": "sets", "path_set_destroy": "sets", "forest_set_destroy": "sets",
 }
 CLASS_OPS = {c: tuple(o for o, k in OP_CLASS.items() if k == c) for c in STATE + OBSERVING}
 NEEDS_MODE = {"compute_pass", "forward_pass", "backward_pass", "forward_pass_and_primal", "backward_pass_and_primal",
@@ -112,6 +135,11 @@ NEEDS_MODE = {"compute_pass", "forward_pass", "backward_pass", "forward_pass_and
 
 
 # ---- models ------------------------------------------------------------------------------------------------------------------
+# the keys whose models admit path / forest sets, their moves and upload_primal, with the (H, W) of the colour-major grid that the
+# unaries of the lists are taken from (None: lists from the suggested forest cover)
+RELABEL_GRIDS = {"rgrid8": (9, 7), "rmixed4": None, "rrows": None, "rlists": (5, 4), "rshift24": (7, 6), "rshift72": (7, 6)}
+
+
 @functools.lru_cache(maxsize=None)
 def base_model(key):
     """the models of the cells, built once per process and never modified"""
@@ -129,6 +157,16 @@ def base_model(key):
         return RP.diff_grid(40)
     if key == "shared32":
         return RP.shared_grid_small(32)
+    if key == "rgrid8":            # the lane-group form of the move kernels; dense tables (float tables under the f32 modes)
+        return S.grid_model(9, 7, 8, order="colour_major", compute_primal=True)
+    if key == "rmixed4":           # SHARED, DIFF and Potts links in one model: the float-table path of the move kernels (tab_flag)
+        return MP.m1()
+    if key == "rrows":             # the rows layout: a move's rows_refresh is real work
+        return RC.rows_graph()
+    if key == "rlists":            # a Potts grid (its first factors: move_base) beside labeling-list factors: the rounding code refuses it
+        return S.c5_model(5, 4, 4, 12, 6, 3, seed=2, window=12)
+    if key in ("rshift24", "rshift72"):      # the models of shift24 / shift72 under keys that admit the relabelling ops
+        return base_model(key[1:])
     if key in ("shift24", "shift72"):      # one register per lane and the <= 32 read-out groups | two registers, the > 64 sweep class
         L = int(key[5:])
         return DS.shift_grid(7, 6, L, order="colour_major", compute_primal=True, lengths=(5, L, 2 * L - 1))
@@ -143,7 +181,7 @@ def props(key):
     pw = m.f_kind[m.f_kind != M.F_VECTOR]
     # shift: some factor is DIFF_SHIFT; windows: every pairwise factor is (every unary may be listed in a window set)
     return dict(mrf=mrf, rounds=mrf and bool(np.all(np.asarray(m.ftype_computes_primal)[vec_types] != 0)), pool=m.sh_data is not None,
-                diff=m.has_diff, dense=bool(np.any(m.f_kind == M.F_PAIRWISE_DENSE)), rows_layout=key == "rows",
+                diff=m.has_diff, dense=bool(np.any(m.f_kind == M.F_PAIRWISE_DENSE)), rows_layout=key in ("rows", "rrows"), relabel=key in RELABEL_GRIDS,
                 shift=bool(np.any(pw == M.F_PAIRWISE_DIFF_SHIFT)), windows=mrf and len(pw) > 0 and bool(np.all(pw == M.F_PAIRWISE_DIFF_SHIFT)))
 
 
@@ -158,7 +196,12 @@ def model_with_costs(key, seed, strict):
     m = base_model(key)
     if seed is None:
         return MP.float_valued(m) if strict else m
-    return RC.recost_shift(m, seed, float_valued=strict)
+    new = RC.recost_shift(m, seed, float_valued=strict)
+    if key == "rgrid8":
+        # new costs of this model are multiples of 1/4: sums are exact and minimisers tie, so that "the smallest minimiser" is asked for
+        q = lambda x: np.round(np.asarray(x, np.float64) * 4.0) / 4.0
+        new = dataclasses.replace(new, const_data=q(new.const_data), dual_data=q(new.dual_data), _keep=[])
+    return new
 
 
 def vectors_of(m):
@@ -299,6 +342,174 @@ def unset_labels(m):
     return out
 
 
+# ---- path and forest moves: the lists of a session and the model a move is stated on ---------------------------------------------
+@functools.lru_cache(maxsize=None)
+def move_base(key):
+    """the unary / pairwise model the moves on ``key`` are stated on: the model itself or, for rlists, the Potts grid that is its
+    first factors, factor for factor (tests/test_path_moves_gpu.py test_unlisted_parts_and_a_labeling_list_factor_elsewhere)"""
+    m = base_model(key)
+    if key != "rlists":
+        return m
+    H, W = RELABEL_GRIDS[key]
+    mg = S.grid_model(H, W, 4, pairwise="potts", order="colour_major", seed=2)
+    n = mg.n_factors
+    assert np.array_equal(m.f_kind[:n], mg.f_kind) and np.array_equal(m.f_dim0[:n], mg.f_dim0)
+    assert np.array_equal(m.const_data[:mg.const_data.shape[0]], mg.const_data) and np.array_equal(m.dual_data[:mg.dual_data.shape[0]], mg.dual_data)
+    assert np.array_equal(m.const_offsets()[:n + 1], mg.const_offsets()) and np.array_equal(m.dual_offsets()[:n + 1], mg.dual_offsets())
+    return mg
+
+
+def _signature(m):
+    return (m.n_factors, m.n_messages, zlib.crc32(np.ascontiguousarray(m.f_dim0).tobytes()), zlib.crc32(np.ascontiguousarray(m.m_left).tobytes()))
+
+
+@functools.lru_cache(maxsize=None)
+def _relabel_signatures():
+    return {_signature(base_model(k)): k for k in RELABEL_GRIDS}
+
+
+def move_model(key, eff, duals):
+    """(model, duals) a move is stated on: ``eff`` (the model the engine computes on) and the duals, or the prefix of both"""
+    mg = move_base(key)
+    if mg.n_factors == eff.n_factors:
+        return eff, duals
+    nc, nd = mg.const_data.shape[0], mg.dual_data.shape[0]
+    return dataclasses.replace(mg, const_data=np.array(eff.const_data[:nc], np.float64), dual_data=np.array(duals[:nd], np.float64), _keep=[]), np.array(duals[:nd], np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def structure_plan(key):
+    """the host planner on the structure of ``key`` (no cost enters a check of a path or forest list)"""
+    return E.Plan(base_model(key))
+
+
+@functools.lru_cache(maxsize=None)
+def suggested_cover(key):
+    return E.Plan(move_base(key)).suggest_forests()
+
+
+def cover_chains(cover):
+    """path groups from forest groups: per tree ONE chain, from a deepest member (the lowest index among them) up to the root.  The
+    trees of a group are induced and not adjacent, so the chains of a group are legal paths of one group"""
+    out = []
+    for un, par in cover:
+        parent = dict(zip([int(u) for u in un], [int(q) for q in par]))
+        best = {}
+        for u in sorted(parent):
+            walk = [u]
+            while parent[walk[-1]] != -1:
+                walk.append(parent[walk[-1]])
+            if len(walk) > len(best.get(walk[-1], ())):
+                best[walk[-1]] = walk
+        out.append([best[r] for r in sorted(best)])
+    return out
+
+
+@functools.lru_cache(maxsize=256)
+def path_list(key, seed):
+    """the groups of a path set, by seed: whole groups (seed % 4 == 0), a seeded subset of the paths (1), partial paths (2), paths of one
+    unary (3: the two colours of a grid, the first unary of every chain elsewhere).  Grids: synthetic.grid_paths — rows and columns —;
+    other models: cover_chains(suggested_cover)"""
+    rng = np.random.default_rng([int(seed), 23])
+    hw, form = RELABEL_GRIDS[key], int(seed) % 4
+    groups = S.grid_paths(hw[0], hw[1], "colour_major") if hw else cover_chains(suggested_cover(key))
+    groups = [[list(p) for p in g] for g in groups]
+    if form == 1:
+        keep = [[p for p in g if rng.random() < 0.6] for g in groups]
+        groups = keep if any(keep) else groups[:1]
+    elif form == 2:
+        cut = []
+        for g in groups:
+            cut.append([])
+            for p in g:
+                a = int(rng.integers(0, len(p)))
+                cut[-1].append(p[a:int(rng.integers(a + 1, len(p) + 1))])
+        groups = cut
+    elif form == 3 and hw:
+        var = S.grid_variable_order(hw[0], hw[1], "colour_major")
+        groups = [[[int(var[r, c])] for r in range(hw[0]) for c in range(hw[1]) if (r + c) % 2 == k] for k in (0, 1)]
+    elif form == 3:
+        groups = [[p[:1] for p in g] for g in groups]
+    return groups
+
+
+@functools.lru_cache(maxsize=256)
+def forest_list(key, seed):
+    """the groups of a forest set: None — the cover of Plan.suggest_forests(); grids: model.forests_from_paths(path_list(key, seed));
+    other models: a seeded subset of the cover's groups in shuffled order"""
+    if seed is None:
+        return suggested_cover(key)
+    if RELABEL_GRIDS[key]:
+        return M.forests_from_paths(path_list(key, seed))
+    cover = suggested_cover(key)
+    rng = np.random.default_rng([int(seed), 27])
+    order = rng.permutation(len(cover))[:max(1, int(rng.integers(1, len(cover) + 1)))]
+    return [cover[int(g)] for g in order]
+
+
+def primal_for(m, seed, form):
+    """the array of an upload_primal step on the unary / pairwise model ``m``: a random label for every unary; ``partly_unset``: about a
+    third of the unaries hold their dimension; ``stray``: about a third hold a negative number.  The pairwise slots take the labels of
+    the unaries that hold one (path_moves_cases.propagate: whatever is below the dimension)"""
+    unaries, links = PM.structure(m)
+    r = np.random.default_rng([int(seed), 29])
+    pr = unset_labels(m)
+    for u in unaries:
+        d, x = int(m.f_dim0[u]), r.random()
+        pr[u, 0] = int(r.integers(0, d))
+        if form == "partly_unset" and x < 1 / 3:
+            pr[u, 0] = d
+        if form == "stray" and x < 1 / 3:
+            pr[u, 0] = -int(r.integers(1, 9))
+    return PM.propagate(m, pr, links)
+
+
+PRIMAL_FORMS = ("random", "partly_unset", "stray")
+
+
+def refusal_list(key, kind):
+    """a list lpmp_path_set_create / lpmp_forest_set_create refuses, from the structure of the model: ``path_set_ring`` — a shortest
+    cycle of the unaries as one path; ``path_set_neighbours_in_group`` — two joined unaries as two paths of one group;
+    ``forest_set_not_induced`` — the cycle as a chain of parents (its ends are joined: a chord); ``forest_set_no_edge`` — a child
+    and a parent that no pairwise factor joins"""
+    _, links = PM.structure(move_base(key))
+    count = {u: collections.Counter(v for _, _, v in lk) for u, lk in links.items()}
+    adj = {u: sorted(v for v, c in count[u].items() if c == 1 and count[v][u] == 1) for u in links}
+    if kind == "path_set_neighbours_in_group":
+        u = min(u for u in adj if adj[u])
+        return [[[u], [adj[u][0]]]]
+    if kind == "forest_set_no_edge":
+        u = min(adj)
+        w = min(v for v in adj if v != u and u not in count[v] and v not in count[u])
+        return [(np.array([u, w], np.int32), np.array([-1, u], np.int32))]
+    cycle = None
+    for root in sorted(adj):                       # a shortest cycle through the lowest unary that lies on one (breadth first)
+        prev, queue = {root: None}, [root]
+        for u in queue:
+            for v in adj[u]:
+                if v not in prev:
+                    prev[v] = u
+                    queue.append(v)
+                elif v != prev[u] and cycle is None:
+                    a, b = [u], [v]
+                    while prev[a[-1]] is not None:
+                        a.append(prev[a[-1]])
+                    while prev[b[-1]] is not None:
+                        b.append(prev[b[-1]])
+                    while len(a) > 1 and len(b) > 1 and a[-2] == b[-2]:
+                        a.pop(); b.pop()
+                    cycle = a[::-1] + b[:-1]
+            if cycle:
+                break
+        if cycle:
+            break
+    assert cycle and len(cycle) >= 3 and len(set(cycle)) == len(cycle), cycle
+    if kind == "path_set_ring":
+        return [[cycle]]
+    assert kind == "forest_set_not_induced", kind
+    return [(np.array(cycle, np.int32), np.array(cycle[1:] + [-1], np.int32))]
+
+
 # ---- the shadow ----------------------------------------------------------------------------------------------------------------
 def refuse(code, what):
     return E.EngineError(code, "shadow: " + what)
@@ -368,6 +579,32 @@ class ShadowWindowSet:
         if np.any(np.abs(delta.astype(np.int64)) > M.MOVE_DELTA_MAX):
             raise refuse(ERR_INVALID, "a delta beyond +-2^20")
         self.sh._move(self, delta.astype(np.int64), cost_old, cost_new)
+
+    def close(self):
+        pass
+
+
+class ShadowMoveSet:
+    """Engine.path_set / Engine.forest_set stated on the shadow: the groups are checked at create by the host planner on the
+    structure of the session's model (what it refuses and how is stated by ``_refused`` from the header and by
+    tests/test_session_host.py from the planner's text); a move is the numpy reference of its kind"""
+
+    def __init__(self, sh, kind, groups):
+        self.sh, self.gen, self.kind, self.groups = sh, sh.gen, kind, groups
+        plan = structure_plan(sh.move_key())
+        try:
+            (plan.path_info if kind == "path" else plan.forest_info)(groups)
+        except E.EngineError as ex:
+            raise refuse(ex.code, str(ex))
+        flat = E.flatten_path_groups(groups) if kind == "path" else E.flatten_forest_groups(groups)
+        self.ident = (kind,) + tuple(zlib.crc32(np.ascontiguousarray(x).tobytes()) for x in flat)
+
+    def move(self, rounds=1):
+        if not self.sh._move_set_alive(self):
+            raise refuse(ERR_STATE, "the %s set was made for another model" % self.kind)
+        if rounds < 0:
+            raise refuse(ERR_INVALID, "negative number of rounds")
+        self.sh._relabel(self, int(rounds))
 
     def close(self):
         pass
@@ -498,6 +735,37 @@ class Shadow:
         self.labels = unset_labels(self.raw)
         self._rebuild(d)
 
+    # ---- path and forest moves ----
+    def move_key(self):
+        """the key among RELABEL_GRIDS whose model has the structure of the uploaded one"""
+        return _relabel_signatures()[_signature(self.raw)]
+
+    def path_set(self, groups):
+        self._model()
+        return ShadowMoveSet(self, "path", groups)
+
+    def forest_set(self, groups):
+        self._model()
+        return ShadowMoveSet(self, "forest", groups)
+
+    def _move_set_alive(self, ms):
+        return self.raw is not None and ms.gen == self.gen
+
+    def _reference(self, m, d, lab, ms, rounds):
+        """the labels after the move, from the array ``lab`` of the model ``m`` the move is stated on"""
+        ref = PM.path_moves_reference if ms.kind == "path" else FM.forest_moves_reference
+        return _memo("moves", m, d, (ms.ident, rounds, zlib.crc32(np.ascontiguousarray(lab).tobytes())), lambda: ref(m, d, lab, ms.groups, rounds)).copy()
+
+    def _relabel(self, ms, rounds):
+        m, d = move_model(self.move_key(), self.eff(), self.duals())
+        new = self._reference(m, d, self.labels[:m.n_factors].copy(), ms, rounds)
+        if self._mrf():
+            self.labels = new
+        else:               # the array of unset labels: the unaries of the lists get labels, no pairwise slot is written
+            un = np.flatnonzero(m.f_kind == M.F_VECTOR)
+            self.labels = self.labels.copy()
+            self.labels[un, 0] = new[un, 0]
+
     # ---- passes ----
     def set_reparametrization(self, mode):
         self._model()
@@ -592,15 +860,22 @@ class Shadow:
         self._model()
         return self.duals()
 
-    def download_primal(self):
+    def _rounding_tables(self):
+        """lpmp_download_primal, lpmp_upload_primal, lpmp_check_primal_consistency, lpmp_evaluate_primal need the rounding code's tables"""
         self._model()
+        if not self._mrf():
+            raise refuse(ERR_UNSUPPORTED, "primal rounding is built for unary / pairwise models")
+
+    def download_primal(self):
+        self._rounding_tables()
         return self.labels.copy()
 
     def upload_primal(self, primal):
-        self._model()
+        self._rounding_tables()
         self.labels = np.array(primal, np.int32, copy=True)
 
     def check_primal_consistency(self):
+        self._rounding_tables()
         m, lab = self.raw, self.labels
         side = np.array([int(m.mtypes[int(t)].param) for t in m.m_type], np.int64)
         return bool(np.all(lab[m.m_left, 0] == lab[m.m_right, side]))
@@ -623,6 +898,7 @@ class Shadow:
 
 # ---- cells -----------------------------------------------------------------------------------------------------------------------
 PRECISIONS = ("f64", "f32", "f32_round")
+RELABEL_N = {"relabel": 160, "relabel_lists": 100, "relabel_windows": 188}       # (session lengths: covering_length plus the margin of the other cells)
 # models: what the cell's uploads move through; n: session length; seeds: committed seeds; prologue: fixed first steps
 CELLS = {
     "joined32": dict(models=("joined32",), n=116, seeds=(0, 1, 2, 3)),
@@ -632,10 +908,18 @@ CELLS = {
     "lists": dict(models=("lists",), n=72, seeds=(0, 1, 2, 3)),
     "diffpool": dict(models=("diff40", "shared32"), n=96, seeds=(0, 1, 2, 3), weight={"pool": 3, "consts": 3}),
     "windows": dict(models=("shift24", "shift72"), n=144, seeds=(0, 1, 2, 3), weight={"move": 3, "consts": 3}),
+    # path and forest moves, their sets and upload_primal among all other calls.  relabel: the unary / pairwise models (union: a
+    # class that only some of its models admit is drawn, too, and a covering block goes to a model that admits all of it);
+    # relabel_lists: a model the rounding code refuses; relabel_windows: the window ops and the new ops on 24 and 72 labels
+    "relabel": dict(models=("rgrid8", "rmixed4", "rrows"), n=RELABEL_N["relabel"], seeds=(0, 1, 2, 3), union=True, weight={"relabel": 4, "sets": 2}),
+    "relabel_lists": dict(models=("rlists",), n=RELABEL_N["relabel_lists"], seeds=(0, 1, 2, 3), weight={"relabel": 4, "sets": 2}),
+    "relabel_windows": dict(models=("rshift24", "rshift72"), n=RELABEL_N["relabel_windows"], seeds=(0, 1, 2, 3), weight={"relabel": 4, "sets": 2, "move": 3, "consts": 2}),
 }
 # (route 3: a window set goes stale on a hop into a model of another kind, and the engine comes back to a DIFF_SHIFT model)
 HOP_ROUTES = {0: ("shared32", "joined32", "lists", "diff40"), 1: ("mixed4", "deep", "rows", "shared32"), 2: ("lists", "joined32", "diff40", "rows"),
-              3: ("shift24", "deep", "diff40", "shift72")}
+              3: ("shift24", "deep", "diff40", "shift72"),
+              # (route 4: a path set and a forest set go stale on a hop into a model of another kind, and the engine comes back)
+              4: ("rshift24", "deep", "rgrid8", "rshift72")}
 HOP_SEEDS = tuple(HOP_ROUTES)
 
 
@@ -652,6 +936,10 @@ def variant(cell, seed):
         v["prec"], v["borrowed"] = PRECISIONS[seed % 3], seed >= 3
     elif cell == "windows":
         v["borrowed"] = seed == 3          # the packed constants a move writes its shifts to are the caller's buffer
+    elif cell == "relabel":
+        v["prec"] = PRECISIONS[seed % 3]   # (as in mixed4; the rows layout runs on doubles whatever the session asks for)
+    elif cell == "relabel_windows":
+        v["borrowed"] = seed == 3
     elif cell == "hop":
         v["env"] = {"LPMP_ROT_BANDS": "6"}
         v["prec"] = "f32_round" if seed == 1 else "f64"
@@ -674,6 +962,9 @@ def admissible_ops(key, prec):
         ops.add("upload_shared_pool")
     if p["windows"]:
         ops |= {"window_set_create", "window_set_destroy", "move_windows"}
+    if p["relabel"]:
+        ops |= {"path_set_create", "path_set_destroy", "forest_set_create", "forest_set_destroy", "path_moves", "forest_moves"}
+        ops |= {"upload_primal"} if p["mrf"] else set()
     return ops
 
 
@@ -687,12 +978,15 @@ def refusal_kinds(key, prec):
         kinds.append("consts_f32")
     if p["windows"]:
         kinds += ["move_delta_range", "move_one_cost", "move_stride", "window_set_twice", "window_set_pairwise"]
+    if p["relabel"]:
+        kinds += ["moves_negative_rounds", "path_set_ring", "path_set_neighbours_in_group", "forest_set_not_induced", "forest_set_no_edge"]
+        kinds += [] if p["mrf"] else ["labels_lists", "upload_primal_lists", "primal_pass_lists"]
     return kinds
 
 
 def admissible_classes(cell):
     keys = CELLS[cell]["models"]
-    ops = set.intersection(*[admissible_ops(k, "f64") for k in keys])
+    ops = (set.union if CELLS[cell].get("union") else set.intersection)(*[admissible_ops(k, "f64") for k in keys])
     return [c for c in STATE if any(o in ops for o in CLASS_OPS[c])], [c for c in OBSERVING if any(o in ops for o in CLASS_OPS[c])], ops
 
 
@@ -723,7 +1017,7 @@ def _covering_blocks(cell):
     blocks += [tuple(chain[i:i + 7]) for i in range(0, len(chain) - 1, 6)]       # pieces overlap by one class: no pair is lost
     blocks += [("mode", "pass")] * len(CELLS[cell]["seeds"])                      # other weights for the very next pass
     kinds = sorted(set().union(*[refusal_kinds(k, "f64") for k in CELLS[cell]["models"]]) | {"destroyed_schedule", "stale_readout"}
-                   | ({"stale_window_set"} if "move" in st else set()))
+                   | ({"stale_window_set"} if "move" in st else set()) | ({"stale_path_set", "stale_forest_set"} if "relabel" in st else set()))
     names = {c: ([o for o in CLASS_OPS[c] if o in ops] if c != "refused" else kinds) for c in st + ob}
     if "move" in st:
         # class move stands for the move itself wherever a pair or the chain names it; the handles get blocks of their own below
@@ -759,21 +1053,60 @@ def _covering_blocks(cell):
                   (mv, ("primal_pass", "compute_pass_and_primal"), ("labels", "labels"), mv, ("ro_labels", "ro_labels")),
                   (("lb", "lower_bound"), mv, ("dir", "forward_pass"), ("lb", "lower_bound"), mv, ("dir", "backward_pass"), ("flb", "factor_lower_bounds")),
                   (("knob", "invalidate_lower_bounds"), mv, ("lb", "lower_bound"), mv, ("knob", "invalidate_lower_bounds"), ("lb", "lower_bound"))]
+    if "relabel" in st:
+        named += _relabel_blocks(st, ob, cost)
     rng = np.random.default_rng(zlib.crc32(cell.encode()))
     order = rng.permutation(len(named))
     seeds = CELLS[cell]["seeds"]
     return {s: [named[i] for i in order[k::len(seeds)]] for k, s in enumerate(seeds)}
 
 
+def _relabel_blocks(st, ob, cost):
+    """the fixed blocks of the cells with path and forest moves.  ``mv``: a path move and a forest move in turn, of one round at least;
+    ``move_last``: a move on the set that was created or moved last; ``flush``: what a refusal would try first (stale handles, a
+    weight mode) comes before the block, so that its steps stand next to each other"""
+    turn = [0]
+
+    def mv():
+        turn[0] += 1
+        return ("relabel", ("path_moves", "forest_moves")[turn[0] % 2])
+
+    flush, last, lab = ("flush", None), ("relabel", "move_last"), ("labels", "labels")
+    seen = lab if "labels" in ob else ("ro_labels", "ro_labels")
+    out = []
+    # every cost-changing class right behind a move, the labels right behind it: they are unset, whatever array they live in
+    out += [(flush, mv(), (c, "move_windows" if c == "move" else None), seen) for c in cost]
+    if "decode" in st:
+        out.append((flush, ("decode", "decode_primal"), mv(), lab))
+    if "primal_pass" in st:
+        # a rounding sweep after a move does not depend on the moved labels (test_a_rounding_sweep_does_not_depend_on_earlier_labels)
+        cpp = ("primal_pass", "compute_pass_and_primal")
+        out.append((flush, cpp, mv(), lab, cpp, lab))
+    # the duals of the moment: a move, a pass, a move on the same set; tracked bounds are not stale after a move
+    out += [(flush, mv(), ("pass", "compute_pass"), last, seen), (flush, mv(), ("pass", "compute_pass"), last, seen)]
+    out.append((flush, ("lb", "lower_bound"), mv(), ("dir", "forward_pass"), ("lb", "lower_bound")))
+    # an uploaded labelling (every form in turn) is what the next move starts on
+    if "labels" in ob:
+        out += [(flush, ("relabel", "upload_primal"), mv(), lab)] * len(PRIMAL_FORMS)
+    if "move" in st:
+        # a set made before a window move moves on the shifts and duals after it: the labels are unset by the window move and clamped
+        out += [(flush, ("sets", kind), ("move", "move_windows"), last, lab) for kind in ("path_set_create", "forest_set_create")]
+    if "labels" not in ob:
+        # a model the rounding code refuses: every refused label call right behind a move leaves the moved labels
+        out += [(flush, mv(), ("refused", kind), ("ro_labels", "ro_labels"))
+                for kind in ("labels_lists", "labels_lists", "labels_lists", "upload_primal_lists", "primal_pass_lists", "decode_lists")]
+    return out
+
+
 def observe_plan(cell, seed, session):
     """per step: are the duals downloaded and compared after it?  About one state-changing step in four (a knob: one in two), always
-    after a refusal and after a move_windows (all delta 0: no byte changes), never after compute_pass(1) — a download settles a speculative batch, and a batch has to live across the call
+    after a refusal, after a move_windows (all delta 0: no byte changes) and after a path or forest move (never a byte changes), never after compute_pass(1) — a download settles a speculative batch, and a batch has to live across the call
     that follows it.  One draw per step index, so a prefix of a session has the prefix of the plan."""
     u = np.random.default_rng([zlib.crc32(cell.encode()), int(seed), 7]).random(len(session))
     out = []
     for (op, a), x in zip(session, u):
         c = OP_CLASS[op]
-        out.append(c not in OBSERVING and (c == "refused" or op == "move_windows" or (op != "compute_pass" or a[0] != 1) and x < (0.5 if c == "knob" else 0.25)))
+        out.append(c not in OBSERVING and (c == "refused" or op in ("move_windows", "path_moves", "forest_moves") or (op != "compute_pass" or a[0] != 1) and x < (0.5 if c == "knob" else 0.25)))
     return out
 
 
@@ -883,6 +1216,28 @@ class _Gen:
         self.warm_diff = False       # the difference new - old of the last warm start is still to come
         self.warms = 0
         self.wlive, self.w_slots, self.w_old = {}, 0, 0      # live window sets {slot: lists every unary}; sets of the previous model not yet tried
+        self.plive, self.p_slots, self.p_old = {}, 0, []     # live path / forest sets {slot: kind}; kinds of those of the previous model not yet tried
+        self.last_set = None                                 # (kind, slot) of the set created or moved last
+
+    def set_create(self, kind, list_seed):
+        self.push(kind + "_set_create", self.p_slots, list_seed)
+        self.plive[self.p_slots] = kind
+        self.last_set = (kind, self.p_slots)
+        self.p_slots += 1
+        return self.p_slots - 1
+
+    def set_of(self, kind):
+        """a live set of the kind (one is made when there is none)"""
+        slots = sorted(s for s, k in self.plive.items() if k == kind)
+        if not slots:
+            return self.set_create(kind, self._seed())
+        return int(slots[int(self.rng.integers(0, len(slots)))])
+
+    def flush(self):
+        """what a refusal would try first comes now: the stale handles of the model before, a weight mode for the sweeps"""
+        if self.stale or self.w_old or self.p_old:
+            self.emit_class("refused", "vectors_twice")
+        self.need_mode()
 
     def window_set_create(self, every):
         self.push("window_set_create", self.w_slots, None if every else self._seed())
@@ -917,7 +1272,7 @@ class _Gen:
     def _check(self, i):
         op, a = self.steps[i]
         c = OP_CLASS[op]
-        return c not in OBSERVING and (c == "refused" or op == "move_windows" or (op != "compute_pass" or a[0] != 1) and self.u[i] < (0.5 if c == "knob" else 0.25))
+        return c not in OBSERVING and (c == "refused" or op in ("move_windows", "path_moves", "forest_moves") or (op != "compute_pass" or a[0] != 1) and self.u[i] < (0.5 if c == "knob" else 0.25))
 
     def spec_block(self, c, want=None):
         """speculation usable, single passes until the caller stands inside a batch, then a call of class ``c`` and a download"""
@@ -978,6 +1333,7 @@ class _Gen:
         self.live, self.dead = [], []
         self.warm_diff = False
         self.w_old, self.wlive = len(self.wlive), {}
+        self.p_old, self.plive, self.last_set = [self.plive[s] for s in sorted(self.plive)], {}, None
 
     def need_mode(self):
         if not self.mode_set:
@@ -985,7 +1341,39 @@ class _Gen:
 
     def emit_class(self, c, want=None):
         """one step of class ``c`` (``want``: this op / refusal kind where it can be drawn now), after whatever it needs first"""
+        if c == "flush":
+            return self.flush()
         ops = [o for o in CLASS_OPS[c] if o in admissible_ops(self.key, self.prec)]
+        if c == "sets":
+            op = want if want in ops else self._next(c, ("path_set_create", "forest_set_create", "path_set_destroy", "forest_set_create", "forest_set_destroy", "path_set_create"))
+            kind = op.split("_")[0]
+            if op.endswith("_create"):
+                # (a forest set: the suggested cover every other time)
+                self.set_create(kind, None if kind == "forest" and self._next("cover", (True, False)) else self._seed())
+            else:
+                if len([s for s, k in self.plive.items() if k == kind]) < 2:      # (one set of a kind stays: a move never waits for one)
+                    self.set_create(kind, self._seed())
+                slots = sorted(s for s, k in self.plive.items() if k == kind)
+                slot = slots[int(self.rng.integers(0, len(slots)))]
+                del self.plive[slot]
+                self.last_set = None if self.last_set == (kind, slot) else self.last_set
+                self.push(op, int(slot))
+            return
+        if c == "relabel":
+            if want == "move_last" and self.last_set is not None:
+                kind, slot = self.last_set
+                self.push(kind + "_moves", int(slot), int(self._next("rounds_w", (1, 2, 1, 3))))
+                return
+            op = want if want in ops else self._next(c, [o for o in ("path_moves", "forest_moves", "upload_primal", "forest_moves", "path_moves") if o in ops])
+            if op == "upload_primal":
+                self.push(op, self._seed(), self._next("primal_form", PRIMAL_FORMS))
+                return
+            kind = op.split("_")[0]
+            slot = self.set_of(kind)
+            # (a move a block asks for does at least one round)
+            self.push(op, slot, int(self._next("rounds_w", (1, 2, 1, 3)) if want else self._next("rounds", (1, 2, 0, 1, 3, 1))))
+            self.last_set = (kind, slot)
+            return
         if c == "custom":
             op = want if want in ops else self._next(c, ops)
             if op in ("schedule_run", "schedule_destroy") and not self.live:
@@ -1007,7 +1395,7 @@ class _Gen:
             keys = CELLS[self.cell]["models"] if self.cell in CELLS else (self.key,)
             precs = (self.prec0, "f64") if self.prec0 != "f64" else ("f64",)
             # (the windows cell goes to its other model every time: both are reached with two uploads)
-            key = [k for k in keys if k != self.key][0] if self.cell == "windows" else self._next("key", keys)
+            key = [k for k in keys if k != self.key][0] if self.cell in ("windows", "relabel_windows") else self._next("key", keys)
             self.upload(key, prec=self._next("prec", precs))
             return
         if c == "move":
@@ -1027,7 +1415,13 @@ class _Gen:
         if c == "refused":
             kinds = refusal_kinds(self.key, self.prec) + ["destroyed_schedule"] + (["stale_readout"] if self.uploads >= 2 else [])
             kinds += ["stale_window_set"] if self.w_old else []
+            kinds += sorted({"stale_%s_set" % k for k in self.p_old})
             kind = want if want in kinds else self._next(c, kinds)
+            if kind in ("stale_path_set", "stale_forest_set"):
+                self.p_old.remove(kind.split("_")[1])                         # (the one the step itself tries)
+            for k in self.p_old:                                               # the sets of the previous model are tried once after every upload
+                self.push("refused", "stale_%s_set" % k, 0)
+            self.p_old = []
             if self.w_old and kind != "stale_window_set":          # a set of the previous model is tried once after every upload
                 self.push("refused", "stale_window_set", 0)
                 self.w_old -= 1
@@ -1035,6 +1429,18 @@ class _Gen:
                 self.w_old -= 1
             if kind.startswith("move_"):
                 self.push("refused", kind, int(sorted(self.wlive)[int(self.rng.integers(0, len(self.wlive)))]))
+                return
+            if kind in ("stale_path_set", "stale_forest_set"):
+                self.push("refused", kind, 0)
+                return
+            if kind == "moves_negative_rounds":
+                k = self._next("neg_kind", ("path", "forest"))
+                self.push("refused", kind, self.set_of(k))
+                return
+            if kind == "primal_pass_lists":
+                self.need_mode()
+            if kind == "labels_lists":                                 # download_primal, evaluate_primal, check_primal_consistency in turn
+                self.push("refused", kind, int(self._next("labels_lists", (0, 1, 2))))
                 return
             if self.stale and kind != "stale_readout":              # handles of the previous model are tried once after every move
                 self.push("refused", "stale_readout", self._seed())
@@ -1085,10 +1491,11 @@ class _Gen:
             self.push(op)
 
     def random_class(self):
-        st, ob, _ = admissible_classes(self.cell) if self.cell in CELLS else (None, None, None)
+        union = self.cell in CELLS and CELLS[self.cell].get("union")      # (what the model of the moment admits, and a re-upload)
+        st, ob, _ = admissible_classes(self.cell) if self.cell in CELLS and not union else (None, None, None)
         if st is None:
             ops = admissible_ops(self.key, self.prec)
-            st = [c for c in STATE if c != "reupload" and any(o in ops for o in CLASS_OPS[c])]
+            st = [c for c in STATE if (union or c != "reupload") and any(o in ops for o in CLASS_OPS[c])]
             ob = [c for c in OBSERVING if any(o in ops for o in CLASS_OPS[c])]
         w = CELLS.get(self.cell, {}).get("weight", {})
         cls = st + ob + ["pass"] * 3
@@ -1096,7 +1503,29 @@ class _Gen:
         return cls[int(self.rng.choice(len(cls), p=p / p.sum()))]
 
 
+def _block_key(g, block):
+    """a cell whose models admit different classes (union): the key of a model that admits every step of the block — the model of the
+    moment where it does"""
+    def admits(key):
+        ops, kinds = admissible_ops(key, "f64"), refusal_kinds(key, "f64")
+        for c, want in block:
+            if c in ("flush", "spec"):
+                continue
+            if c == "refused":
+                if want in set().union(*[refusal_kinds(k, "f64") for k in CELLS[g.cell]["models"]]) and want not in kinds:
+                    return False
+            elif not any(o in ops for o in CLASS_OPS[c]) or (want in OP_CLASS and want not in ops):
+                return False
+        return True
+    keys = [k for k in CELLS[g.cell]["models"] if admits(k)]
+    return g.key if g.key in keys else g._next("block_key", keys)
+
+
 def _after_block(g, state):
+    if g.key is not None and props(g.key)["relabel"] and not g.plive:
+        # a path set and a forest set behind the block of an upload — a move never waits for one —: made before the first window move
+        g.set_create("path", g._seed())
+        g.set_create("forest", None)
     if g.key is not None and props(g.key)["windows"] and not g.wlive:
         # a set of every unary behind the block of an upload — a move never waits for one —, and one move of the new model's windows
         # between two passes before anything else happens to it
@@ -1118,7 +1547,7 @@ def _after_block(g, state):
 def _cell_steps(cell, seed, n):
     g = _Gen(cell, seed, variant(cell, seed)["prec"])
     # (the windows cell starts on its 24-label model with even seeds and on its 72-label model with odd ones)
-    g.upload(CELLS[cell]["models"][seed % 2 if cell == "windows" else 0], recost=False)
+    g.upload(CELLS[cell]["models"][seed % 2 if cell in ("windows", "relabel_windows") else seed % 3 if cell == "relabel" else 0], recost=False)
     if cell in ("joined32", "deep"):
         g.push("set_reparametrization", ANISO)
     g.need_mode()
@@ -1142,6 +1571,10 @@ def _cell_steps(cell, seed, n):
         g.push("enable_kernel_timing", True)
         _after_block(g, {})
         g.push("lower_bound")
+    if cell.startswith("relabel"):
+        # the sets of the upload, and one move of each kind on labels that are unset before anything else happened
+        _after_block(g, {})
+        g.emit_class("relabel", "path_moves"); g.emit_class("ro_labels"); g.emit_class("relabel", "forest_moves"); g.emit_class("ro_labels")
     blocks = list(_covering_blocks(cell)[seed])
     state = {}
     while blocks if n is None else len(g.steps) < n:
@@ -1150,6 +1583,10 @@ def _cell_steps(cell, seed, n):
             if g.key == "joined32":
                 g.spec_block(block[0][1])
         else:
+            key = _block_key(g, block) if CELLS[cell].get("union") else g.key
+            if key != g.key:
+                g.upload(key)
+                _after_block(g, state)
             for c, want in block:
                 g.emit_class(c, want)
         _after_block(g, state)
@@ -1167,8 +1604,10 @@ def _hop_steps(seed, n):
             if had_slot:
                 g.push("refused", "stale_schedule", 0)
         g.need_mode()
-        if props(key)["windows"]:                                    # the set of the upload moves once at least before the next hop
+        if props(key)["windows"] or props(key)["relabel"]:          # the set of the upload moves once at least before the next hop
             _after_block(g, state)
+        if props(key)["relabel"]:
+            g.emit_class("relabel", "path_moves"); g.emit_class("relabel", "forest_moves"); g.emit_class("ro_labels")
         g.push("schedule_create", g.n_slots, g._seed(), False)       # a handle for the next move to try
         g.live.append(g.n_slots); g.n_slots += 1
         spec = [g._next("hop_spec", ("cold", "vectors", "consts", "decode", "custom", "warm", "zero", "duals", "knob", "refused"))
@@ -1216,8 +1655,12 @@ class _Side:
         self.stale_id = None
         self.keep = None
         self.wsets, self.old_wsets = {}, []          # window sets by slot; those of the model before, not yet tried
+        self.psets, self.old_psets = {}, []          # (kind, path or forest set) by slot; those of the model before, not yet tried
 
     def close(self):
+        for _, w in list(self.psets.values()) + self.old_psets:
+            w.close()
+        self.psets, self.old_psets = {}, []
         for r in (self.readouts or ()) + (self.old_readouts or ()):
             r.close()
         self.readouts = self.old_readouts = None
@@ -1242,6 +1685,9 @@ class Reach:
         self.shift_launches = 0               # timed launches of sweep_diff_shift_kernel
         self.models = set()                   # keys uploaded
         self.lb_rel_max = 0.0                 # largest |lower_bound - oracle's| / max(1, |oracle's|) seen (the limit is LB_RTOL)
+        # path_moves / forest_moves steps done, path and forest sets created (run() checks schedules_built around each), moves done while
+        # every label was unset, moves on a set that was made before the last move_windows of its model
+        self.path_moves = self.forest_moves = self.move_sets = self.moves_on_unset = self.moves_behind_windows = 0
 
     def before_reset(self, e):
         st = e.speculation_stats()
@@ -1343,6 +1789,22 @@ def _refused(side, sh, kind, arg):
     if kind == "stale_window_set":
         ws = side.old_wsets[0]
         return ERR_STATE, lambda: ws.move(np.ones(ws.n, np.int32))
+    if kind in ("stale_path_set", "stale_forest_set"):
+        ms = [w for k, w in side.old_psets if k == kind.split("_")[1]][0]
+        return ERR_STATE, lambda: ms.move(1)
+    if kind == "moves_negative_rounds":
+        return ERR_INVALID, lambda: side.psets[arg][1].move(-1)
+    # lpmp_path_set_create / lpmp_forest_set_create, the last group of their refusals: "LPMP_ERR_INVALID, naming the entries"
+    if kind in ("path_set_ring", "path_set_neighbours_in_group"):
+        return ERR_INVALID, lambda: t.path_set(refusal_list(sh.key, kind))
+    if kind in ("forest_set_not_induced", "forest_set_no_edge"):
+        return ERR_INVALID, lambda: t.forest_set(refusal_list(sh.key, kind))
+    if kind == "labels_lists":
+        return ERR_UNSUPPORTED, (t.download_primal, t.evaluate_primal, t.check_primal_consistency)[arg % 3]
+    if kind == "upload_primal_lists":
+        return ERR_UNSUPPORTED, lambda: t.upload_primal(unset_labels(m))
+    if kind == "primal_pass_lists":
+        return ERR_UNSUPPORTED, lambda: (t.forward_pass_and_primal, t.backward_pass_and_primal, t.compute_pass_and_primal)[arg % 3](arg)
     if kind == "window_set_twice":
         return ERR_INVALID, lambda: t.window_set([vec[0], vec[-1], vec[0]])
     if kind == "window_set_pairwise":
@@ -1387,6 +1849,9 @@ def apply(side, sh, step):
         for w in side.old_wsets:
             w.close()
         side.old_wsets, side.wsets = [side.wsets[k] for k in sorted(side.wsets)], {}
+        for _, w in side.old_psets:
+            w.close()
+        side.old_psets, side.psets = [side.psets[k] for k in sorted(side.psets)], {}
     elif op == "window_set_create":
         side.wsets[a[0]] = t.window_set(window_list(sh.raw, a[1]))
     elif op == "window_set_destroy":
@@ -1406,6 +1871,15 @@ def apply(side, sh, step):
             t.synchronize()                           # (the call is asynchronous: the arrays live until it has run)
         else:
             ws.move(delta, cost_old=co, cost_new=cn)
+    elif op in ("path_set_create", "forest_set_create"):
+        kind, groups = sh.set_lists[a[0]]
+        side.psets[a[0]] = (kind, t.path_set(groups) if kind == "path" else t.forest_set(groups))
+    elif op in ("path_set_destroy", "forest_set_destroy"):
+        side.psets.pop(a[0])[1].close()
+    elif op in ("path_moves", "forest_moves"):
+        side.psets[a[0]][1].move(a[1])
+    elif op == "upload_primal":
+        t.upload_primal(primal_for(sh.raw, a[0], a[1]))
     elif op == "compute_pass_custom":
         t.compute_pass_custom(*custom_rows(_key_of(sh), a[0]))
     elif op == "schedule_create":
@@ -1442,13 +1916,22 @@ def apply(side, sh, step):
             return None                                   # (an engine that took over in the middle of a replay has no older handles)
         if a[0] == "stale_window_set" and not side.old_wsets:
             return None
+        if a[0] in ("stale_path_set", "stale_forest_set") and not [1 for k, _ in side.old_psets if k == a[0].split("_")[1]]:
+            return None
         code, call = _refused(side, sh, a[0], a[1])
         ok, got = _expect(code, call)
         if not ok:
             raise Mismatch("refusal %s: expected %s, got %s" % (a[0], code, got))
         if a[0] == "stale_window_set":
             side.old_wsets.pop(0).close()                 # destroying it stays legal
+        if a[0] in ("stale_path_set", "stale_forest_set"):
+            k = [k for k, _ in side.old_psets].index(a[0].split("_")[1])
+            side.old_psets.pop(k)[1].close()              # destroying it stays legal
     elif op == "labels":
+        if sh.labels is not None and sh.labels.min() < 0:
+            # a stray negative label (upload_primal, form stray) that no move has replaced yet: the array is compared; its cost and its
+            # consistency are outside the contract of lpmp_evaluate_primal and are not asked for
+            return (None, None, t.download_primal())
         return (t.evaluate_primal(), t.check_primal_consistency(), t.download_primal())
     elif op in ("ro_labels", "ro_vectors", "ro_beliefs"):
         return tuple(getattr(r, op[3:])() for r in side.readouts)
@@ -1497,6 +1980,8 @@ def compare(op, got, want, pair=False):
             return "labels: " + _first_diff(lab, labw)
         if ok != okw:
             return "check_primal_consistency %r / %r" % (ok, okw)
+        if c is None and cw is None:
+            return None
         if pair or np.isinf(cw) or np.isinf(c):
             return None if c == cw else "evaluate_primal %r / %r" % (c, cw)
         # tests/test_decode_gpu.py test_decoded_labels_are_consistent_and_cost_the_original_energy: abs(cost - want) <= 1e-9 * max(1, abs(want))
@@ -1564,6 +2049,7 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                     s.readouts = tuple(s.t.readout(None if r is None else r) for r in shadow.ro_lists)
                     s.ids = {slot: s.t.schedule_create(*rows) for slot, rows in shadow.slot_rows.items()}
                     s.wsets = {slot: s.t.window_set(lst) for slot, lst in shadow.window_lists.items()}
+                    s.psets = {slot: (k, s.t.path_set(g) if k == "path" else s.t.forest_set(g)) for slot, (k, g) in shadow.set_lists.items()}
                     if props(shadow.key)["mrf"]:                    # the labels, too: a later labels / read-out step compares them
                         s.t.upload_primal(shadow.download_primal())
                 engines[:] = [s.t for s in sides]
@@ -1572,7 +2058,14 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                 continue
             if op == "upload":
                 shadow.key, shadow.slot_rows, shadow.window_lists, shadow.warm_new = a[0], {}, {}, None
+                shadow.set_lists, shadow.sets_at_window_move = {}, set()
                 shadow.ro_lists = (vector_subset(base_model(a[0]), a[3])[0], None)
+            if op in ("path_set_create", "forest_set_create"):
+                shadow.set_lists[a[0]] = ("path", path_list(shadow.key, a[1])) if op[0] == "p" else ("forest", forest_list(shadow.key, a[1]))
+            if op in ("path_set_destroy", "forest_set_destroy"):
+                shadow.set_lists.pop(a[0], None)
+            if op == "move_windows":
+                shadow.sets_at_window_move = set(shadow.set_lists)
             if op == "window_set_create":
                 shadow.window_lists[a[0]] = window_list(shadow.raw, a[1])
             if op == "window_set_destroy":
@@ -1591,9 +2084,22 @@ def run(engines, shadow, session, observe=None, cell="?", seed="?", borrowed=Fal
                         continue
                     if op == "reset_kernel_timing" and isinstance(s.t, E.Engine):
                         reach.before_reset(s.t)
-                    built = s.t.schedules_built() if op in ("move_windows", "window_set_create") and isinstance(s.t, E.Engine) else None
+                    counted = ("move_windows", "window_set_create", "path_moves", "forest_moves", "path_set_create", "forest_set_create")
+                    built = s.t.schedules_built() if op in counted and isinstance(s.t, E.Engine) else None
                     apply(s, shadow, (op, a))
-                    if built is not None:
+                    if built is not None and OP_CLASS[op] in ("relabel", "sets"):
+                        # lpmp_path_set_create / lpmp_forest_set_create: "lpmp_schedules_built counts the create ONCE; a move plans and
+                        # uploads nothing"
+                        reach.path_moves += op == "path_moves"
+                        reach.forest_moves += op == "forest_moves"
+                        reach.move_sets += op.endswith("_create")
+                        if op.endswith("_moves"):
+                            un = shadow.raw.f_kind == M.F_VECTOR
+                            reach.moves_on_unset += bool(np.all(shadow.labels[un, 0] >= shadow.raw.f_dim0[un]))
+                            reach.moves_behind_windows += a[0] in shadow.sets_at_window_move
+                        if s.t.schedules_built() != built + op.endswith("_create"):
+                            raise Mismatch("schedules_built went from %d to %d" % (built, s.t.schedules_built()))
+                    elif built is not None:
                         # lpmp_window_set_create: "counted ONCE by lpmp_schedules_built"; lpmp_move_windows: "plans nothing"
                         reach.moves += op == "move_windows"
                         reach.window_sets += op == "window_set_create"

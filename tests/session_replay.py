@@ -3,9 +3,9 @@ python tests/session_replay.py CELL SEED [--upto K] [--observe-all] [--fresh-at 
   --upto K       only the first K steps (a prefix of a session is the session of that length)
   --observe-all  download and compare the duals after every step: settles every speculative batch, so it narrows down and does not
                  reproduce
-  --fresh-at K   at step K a new engine takes over with the shadow's model and duals (schedules, read-outs and the live window sets
-                 are made again from the shadow's lists): a divergence that goes away was stale state in the old engine, one that
-                 stays is a wrong kernel
+  --fresh-at K   at step K a new engine takes over with the shadow's model and duals (schedules, read-outs and the live window, path
+                 and forest sets are made again from the shadow's lists; the labels are uploaded where the model takes
+                 lpmp_upload_primal): a divergence that goes away was stale state in the old engine, one that stays is a wrong kernel
 One engine, one process; ends at the first mismatch.  For a finding of the tests, not for running something again and again."""
 import argparse
 import os

@@ -21,7 +21,7 @@ def _run(cell, seed, monkeypatch, pair=False):
     engines, skip = [], {}
     reach = SC.Reach()
     try:
-        if pair and cell == "windows":    # the first engine: plain launches throughout, the second one follows the session (chain launches)
+        if pair and cell in ("windows", "relabel_windows"):    # the first engine: plain launches throughout, the second one follows the session (chain launches)
             engines.append(E.Engine(0))
             engines[0].set_persistent_launches(False)
             skip = {0: {"set_persistent_launches"}}
@@ -73,6 +73,17 @@ def test_session(cell, seed, monkeypatch):
         # windows moved, timed launches of the shifted kernel, both label counts (SC.run checked schedules_built around every
         # window_set_create — one more — and every move_windows — unmoved)
         assert reach.moves > 0 and reach.window_sets > 0 and reach.shift_launches > 0 and reach.models == {"shift24", "shift72"}, vars(reach)
+    if cell.startswith("relabel"):
+        # path and forest moves done, sets created (SC.run checked schedules_built around every create — one more — and every move —
+        # unmoved —, and the duals behind every move: no byte changes), moves on labels that were all unset
+        assert reach.path_moves > 0 and reach.forest_moves > 0 and reach.move_sets > 0 and reach.moves_on_unset > 0, vars(reach)
+        assert reach.models == set(SC.CELLS[cell]["models"]), vars(reach)
+    if cell == "relabel":
+        assert v["prec"] in reach.precisions and reach.rows, vars(reach)
+    elif cell == "relabel_windows":
+        # both label counts (the wave form and the workgroup form of the move kernels), a path or forest move on a set that was made
+        # before a move_windows
+        assert reach.moves > 0 and reach.moves_behind_windows > 0, vars(reach)
 
 
 @pytest.mark.parametrize("seed", SC.HOP_SEEDS)
@@ -81,13 +92,15 @@ def test_one_engine_moves_through_four_models(seed, monkeypatch):
     print("hop", seed, vars(reach))
 
 
-@pytest.mark.parametrize("cell,seed", [("joined32", 0), ("mixed4", 2), ("windows", 1)])
+@pytest.mark.parametrize("cell,seed", [("joined32", 0), ("mixed4", 2), ("windows", 1), ("relabel", 2), ("relabel_windows", 1)])
 def test_two_engines_run_the_same_session(cell, seed, monkeypatch):
     """one engine without passes ahead and with LPMP_PQ_LDS=0, one with the defaults (windows: one engine with plain launches
     throughout, one that follows the session's set_persistent_launches): both equal the shadow, and each other bit for bit (bounds
-    as tests/test_speculation_gpu.py lines 115-121 allow)"""
+    as tests/test_speculation_gpu.py lines 115-121 allow).  relabel: as joined32 and mixed4; relabel_windows: as windows"""
     reach, _ = _run(cell, seed, monkeypatch, pair=True)
     if cell == "joined32":
         assert reach.peer_minima > 0 and reach.batches > 0, vars(reach)
     if cell == "windows":
         assert reach.moves > 0 and reach.models == {"shift24", "shift72"}, vars(reach)
+    if cell.startswith("relabel"):
+        assert reach.path_moves > 0 and reach.forest_moves > 0 and reach.models == set(SC.CELLS[cell]["models"]), vars(reach)

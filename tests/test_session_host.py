@@ -39,8 +39,8 @@ def test_steps_are_a_pure_function_and_prefixes_replay(cell, seed):
         assert op in SC.OP_CLASS and all(isinstance(x, (int, str, bool, type(None))) for x in args), (op, args)
 
 
-# crc32 of repr(steps(cell, seed)) of every session that was committed before the windows cell and hop route 3 came (computed on the
-# commit before them): a new op, class or cell must leave the sessions that exist as they are
+# crc32 of repr(steps(cell, seed)) of every session that was committed before the cells of the path and forest moves and hop route 4
+# came (computed on the commits before them): a new op, class or cell must leave the sessions that exist as they are
 STEP_DIGESTS = {
     "joined32": {0: 0x701a6554, 1: 0xb27b3ebc, 2: 0xd577a5f8, 3: 0x66ba7427},
     "mixed4": {0: 0x7da306fd, 1: 0x8c2d485a, 2: 0xc3af258a, 3: 0x85e85698, 4: 0x26e2e77c, 5: 0x845003a3},
@@ -48,7 +48,8 @@ STEP_DIGESTS = {
     "deep": {0: 0x2dc5e04f, 1: 0xc366597f, 2: 0x1115e9cd, 3: 0x01f3443e},
     "lists": {0: 0x3a7d8a6f, 1: 0x399a6905, 2: 0x32a27a3a, 3: 0x04451d75},
     "diffpool": {0: 0x010f493c, 1: 0xe5fda1cb, 2: 0xa274ea55, 3: 0x7f75df4f},
-    "hop": {0: 0x904bf48f, 1: 0xe05d07c5, 2: 0x03a8f414},
+    "windows": {0: 0xf67cdf6c, 1: 0xbae1e167, 2: 0x02fbd3dd, 3: 0xdac8bae1},
+    "hop": {0: 0x904bf48f, 1: 0xe05d07c5, 2: 0x03a8f414, 3: 0x17d52bda},
 }
 
 
@@ -57,7 +58,7 @@ def test_the_sessions_from_before_the_windows_cell_are_unchanged():
         assert set(seeds) <= set(SC.HOP_SEEDS if cell == "hop" else SC.CELLS[cell]["seeds"]), cell
         for seed, want in seeds.items():
             assert zlib.crc32(repr(SC.steps(cell, seed)).encode()) == want, (cell, seed)
-    assert {c for c, _ in ALL} - set(STEP_DIGESTS) == {"windows"} and set(SC.HOP_SEEDS) - set(STEP_DIGESTS["hop"]) == {3}
+    assert {c for c, _ in ALL} - set(STEP_DIGESTS) == {"relabel", "relabel_lists", "relabel_windows"} and set(SC.HOP_SEEDS) - set(STEP_DIGESTS["hop"]) == {4}
 
 
 # ---- coverage: a condition on the generator ------------------------------------------------------------------------------------
@@ -90,6 +91,7 @@ def test_committed_sessions_cover_ops_pairs_and_cost_pairs(cell):
         precs = {SC.variant(cell, s)["prec"] for s in seeds}
         want = set().union(*[SC.refusal_kinds(key, p) for p in precs]) | {"destroyed_schedule", "stale_readout"}
         want |= {"stale_window_set"} if SC.props(key)["windows"] else set()
+        want |= {"stale_path_set", "stale_forest_set"} if SC.props(key)["relabel"] else set()
         assert want <= set(kinds), want - set(kinds)
 
 
@@ -141,16 +143,21 @@ def test_cells_reach_the_state_they_are_about():
     for seed in SC.HOP_SEEDS:
         s = SC.steps("hop", seed)
         ups = [i for i, x in enumerate(s) if x[0] == "upload"]
-        assert len(ups) == 4 and all(15 <= b - a - 4 <= 36 for a, b in zip(ups, ups[1:]))
+        assert len(ups) == 4 and all(15 <= b - a - 4 <= (36 if seed < 4 else 48) for a, b in zip(ups, ups[1:]))       # (route 4: its sets and first moves)
         rtype = 0
         for i, (op, a) in enumerate(s):                 # the send rule stays across uploads: SHARED when a model comes that draws no other
             rtype = a[0] if op == "set_reparametrization_type" else rtype
             assert not (op == "upload" and not SC.props(a[0])["mrf"] and rtype != 0), (seed, i)
         for i in ups[1:]:
             # (the window set that comes with a DIFF_SHIFT model and the try of the one before stand first)
-            r = [x for x in s[i + 1:i + 6] if x[0] != "window_set_create" and x[:1] + x[1][:1] != ("refused", "stale_window_set")]
+            # (... and so do the path and forest sets of a model that admits them, and the tries of those of the model before)
+            mine = ("window_set_create", "path_set_create", "forest_set_create")
+            stale = ("stale_window_set", "stale_path_set", "stale_forest_set")
+            r = [x for x in s[i + 1:i + 9] if x[0] not in mine and not (x[0] == "refused" and x[1][0] in stale)]
             assert r[0] == ("refused", ("stale_readout", r[0][1][1])) and r[1][:1] == ("refused",) and r[1][1][0] == "stale_schedule"
-            assert (("refused", ("stale_window_set", 0)) in s[i + 1:i + 4]) == SC.props(s[[u for u in ups if u < i][-1]][1][0])["windows"]
+            assert (("refused", ("stale_window_set", 0)) in s[i + 1:i + 6]) == SC.props(s[[u for u in ups if u < i][-1]][1][0])["windows"]
+            for kind in ("stale_path_set", "stale_forest_set"):
+                assert (("refused", (kind, 0)) in s[i + 1:i + 6]) == SC.props(s[[u for u in ups if u < i][-1]][1][0])["relabel"]
 
 
 # ---- the windows cell: what its committed steps hold ---------------------------------------------------------------------------
@@ -201,7 +208,7 @@ def test_window_deltas_and_costs_are_what_the_cell_says():
 def test_windows_sessions_hold_what_the_cell_is_about():
     seeds = SC.CELLS["windows"]["seeds"]
     assert all(SC.props(k)["windows"] and SC.props(k)["shift"] and SC.props(k)["rounds"] and SC.props(k)["pool"] for k in ("shift24", "shift72"))
-    assert not any(SC.props(k)["windows"] or SC.props(k)["shift"] for c in STEP_DIGESTS if c != "hop" for k in SC.CELLS[c]["models"])
+    assert not any(SC.props(k)["windows"] or SC.props(k)["shift"] for c in STEP_DIGESTS if c not in ("hop", "windows") for k in SC.CELLS[c]["models"])
     forms, infs, next_to = collections.Counter(), 0, collections.Counter()
     run_after, decode_after = 0, 0
     cost_ops = ("set_constants", "upload_costs_warm", "upload_costs_cold", "upload_duals", "zero_pairwise_duals", "upload_shared_pool")
@@ -716,15 +723,19 @@ def test_a_seeded_defect_fails_the_session_where_it_is(defect, cell):
         assert not [k for k in range(before[-1] + 1, i) if session[k][0] in shows], (before[-1], i)
 
 
-@pytest.mark.parametrize("cell", ["diffpool", "mixed4", "deep", "hop", "windows"])
+@pytest.mark.parametrize("cell", ["diffpool", "mixed4", "deep", "hop", "windows", "relabel", "relabel_windows"])
 def test_replay_with_a_fresh_engine_in_the_middle(cell):
     """tests/session_replay.py --fresh-at K: a new engine takes over with the shadow's model, duals, mode, read-outs, schedules and
-    labels — K right behind a step that sets labels which a later step still observes (no cost change in between unsets them)"""
+    labels — K right behind a step that sets labels which a later step still observes (no cost change in between unsets them).  The
+    cells of the path and forest moves: K right behind a move, and the engine that takes over moves on a set it made again from the
+    shadow's lists"""
     unsets = ("upload", "upload_costs_cold", "upload_costs_warm", "set_constants", "upload_shared_pool", "move_windows")
+    moves = ("path_moves", "forest_moves")
+    relabel = cell.startswith("relabel")
     k = None
     for seed in (SC.HOP_SEEDS if cell == "hop" else SC.CELLS[cell]["seeds"]):
         s = SC.steps(cell, seed)
-        for i in [i for i, (op, a) in enumerate(s) if op == "decode_primal" or op.endswith("_and_primal")]:
+        for i in [i for i, (op, a) in enumerate(s) if (op in moves if relabel else op == "decode_primal" or op.endswith("_and_primal"))]:
             j = next((j for j in range(i + 1, len(s)) if s[j][0] in ("labels", "ro_labels") or s[j][0] in unsets), None)
             if j is not None and s[j][0] not in unsets:
                 k = i + 1
@@ -732,4 +743,309 @@ def test_replay_with_a_fresh_engine_in_the_middle(cell):
         if k is not None:
             break
     assert k is not None
+    if relabel:
+        made = {a[0] for op, a in s[:k] if op.endswith("_set_create")}
+        upto = next((j for j in range(k, len(s)) if s[j][0] == "upload"), len(s))
+        assert [j for j in range(k, upto) if s[j][0] in moves and s[j][1][0] in made], (cell, seed, k)
     SC.run([SC.Shadow()], SC.Shadow(), s, observe=None, cell=cell, seed=seed, fresh_at=k, fresh=SC.Shadow)
+
+
+# ---- the cells of the path and forest moves: what their committed steps hold ------------------------------------------------------
+RELABEL_CELLS = ("relabel", "relabel_lists", "relabel_windows")
+_LIST_TEXT = {"path_set_ring": "non-consecutive members of path 0", "path_set_neighbours_in_group": "two paths of group 0",
+              "forest_set_not_induced": "induce a forest", "forest_set_no_edge": "no pairwise factor joins"}
+
+
+def _relabel_sessions():
+    return [(c, s) for c in RELABEL_CELLS for s in SC.CELLS[c]["seeds"]] + [("hop", 4)]
+
+
+def test_committed_path_and_forest_lists_are_legal_and_the_refusal_lists_are_refused():
+    """every list of a committed path_set_create / forest_set_create step is accepted by Plan.path_info / Plan.forest_info on the
+    model of the step; every refusal list is refused by them with the code of the header and the text the kind is about.  The
+    chains of rrows — one per tree of each suggested forest group — are legal path groups"""
+    forms, n_lists = collections.Counter(), 0
+    for cell, seed in _relabel_sessions():
+        key = None
+        for op, a in SC.steps(cell, seed):
+            key = a[0] if op == "upload" else key
+            if op == "path_set_create":
+                info = SC.structure_plan(key).path_info(SC.path_list(key, a[1]))
+                assert info["n_paths"] >= 1, (cell, seed, op, a)
+                forms[(key, a[1] % 4)] += 1
+                n_lists += 1
+            elif op == "forest_set_create":
+                info = SC.structure_plan(key).forest_info(SC.forest_list(key, a[1]))
+                assert info["n_trees"] >= 1, (cell, seed, op, a)
+                forms[(key, "cover" if a[1] is None else "seeded")] += 1
+                n_lists += 1
+    print("lists", n_lists, dict(forms))
+    assert {f for _, f in forms} == {0, 1, 2, 3, "cover", "seeded"}
+    for key in SC.RELABEL_GRIDS:
+        have = {f for k, f in forms if k == key}
+        assert have & {0, 1, 2, 3} and have & {"cover", "seeded"}, (key, have)
+        for kind, text in _LIST_TEXT.items():
+            lst = SC.refusal_list(key, kind)
+            with pytest.raises(E.EngineError) as ei:
+                (SC.structure_plan(key).path_info if kind.startswith("path") else SC.structure_plan(key).forest_info)(lst)
+            assert ei.value.code == SC.ERR_INVALID and text in str(ei.value), (key, kind, str(ei.value))
+    chains = SC.cover_chains(SC.suggested_cover("rrows"))
+    info = SC.structure_plan("rrows").path_info(chains)
+    assert info["n_paths"] == sum(int(np.sum(par == -1)) for _, par in SC.suggested_cover("rrows")) and info["n_path_edges"] > info["n_paths"]
+    # the grid of rlists is the first factors of the model, and nothing else of it is eligible for a move
+    assert max(int(u.max()) for u, _ in SC.suggested_cover("rlists")) < 20 and not SC.props("rlists")["mrf"]
+    # 8, 24 and 72 labels: the lane-group, wave and workgroup forms; rmixed4 holds SHARED, DIFF and Potts links
+    assert [int(SC.base_model(k).f_dim0.max()) for k in ("rgrid8", "rshift24", "rshift72")] == [8, 24, 72]
+    kinds = set(SC.base_model("rmixed4").f_kind.tolist())
+    assert {M.F_PAIRWISE_SHARED, M.F_PAIRWISE_DIFF, M.F_PAIRWISE_POTTS, M.F_PAIRWISE_DENSE} <= kinds
+
+
+def _count(cell, pattern):
+    """how often the committed sessions of the cell hold these ops as neighbours ("mv": a path or forest move of one round at least;
+    "same": such a move on the set of the "mv" / the create before it)"""
+    n = 0
+    for seed in SC.CELLS[cell]["seeds"]:
+        s = SC.steps(cell, seed)
+        for i in range(len(s) - len(pattern) + 1):
+            slot, ok = None, True
+            for (op, a), want in zip(s[i:], pattern):
+                if want in ("mv", "same"):
+                    ok = op in ("path_moves", "forest_moves") and a[1] > 0 and (want == "mv" or a[0] == slot)
+                else:
+                    ok = op == want
+                if not ok:
+                    break
+                slot = a[0] if want == "mv" or want.endswith("_set_create") else slot
+            n += ok
+    return n
+
+
+def test_relabel_sessions_hold_what_their_cells_are_about():
+    cost_ops = ("upload_costs_cold", "upload_costs_warm", "set_constants", "upload_shared_pool", "move_windows")
+    moves = ("path_moves", "forest_moves")
+    for cell in RELABEL_CELLS:
+        behind, rounds, forms, precs, keys = collections.Counter(), collections.Counter(), collections.Counter(), set(), set()
+        for seed in SC.CELLS[cell]["seeds"]:
+            s = SC.steps(cell, seed)
+            plan = SC.observe_plan(cell, seed, s)
+            precs.add(SC.variant(cell, seed)["prec"])
+            made_before_window_move = 0
+            sets_then = set()
+            live = set()
+            for i, (op, a) in enumerate(s):
+                if op == "upload":
+                    keys.add(a[0]); live, sets_then = set(), set()
+                if op.endswith("_set_create"):
+                    live.add(a[0])
+                if op == "move_windows":
+                    sets_then = set(live)
+                if op in moves:
+                    assert plan[i], (cell, seed, i)           # the duals are compared behind every move
+                    rounds[a[1]] += 1
+                    made_before_window_move += a[0] in sets_then
+                    nxt = s[i + 1:i + 3]
+                    if len(nxt) == 2 and nxt[1][0] in ("labels", "ro_labels"):
+                        behind[nxt[0][0] if nxt[0][0] != "refused" else nxt[0][1][0]] += 1
+                if op == "upload_primal":
+                    forms[a[1]] += 1
+            if cell == "relabel_windows":
+                assert made_before_window_move >= 1, (cell, seed)
+        print(cell, "| behind a move, labels next:", dict(behind), "| rounds", dict(rounds), "| forms", dict(forms), "| keys", sorted(keys))
+        assert keys == set(SC.CELLS[cell]["models"]) and set(rounds) == {0, 1, 2, 3}
+        st, _, _ = SC.admissible_classes(cell)
+        for c in [c for c in SC.COST if c in st]:
+            assert any(behind[o] for o in SC.CLASS_OPS[c] if o in cost_ops + ("set_vectors", "set_vectors_diff", "zero_pairwise_duals", "upload_duals")), (cell, c)
+        if cell == "relabel_lists":
+            # a cost change and each new refusal kind directly behind a move, ro_labels behind it
+            assert any(behind[o] for o in cost_ops) and all(behind[k] >= 1 for k in ("labels_lists", "upload_primal_lists", "primal_pass_lists", "decode_lists")), dict(behind)
+            assert behind["labels_lists"] >= 3
+        else:
+            assert set(forms) == set(SC.PRIMAL_FORMS)
+            # the fixed blocks: a decode, a move, the labels; a rounding sweep, a move, the labels, a rounding sweep, the labels; a move,
+            # a pass, a move on the same set, the labels; a bound, a move, a directional sweep, a bound
+            assert _count(cell, ("decode_primal", "mv", "labels")) >= 1
+            assert _count(cell, ("compute_pass_and_primal", "mv", "labels", "compute_pass_and_primal", "labels")) >= 1
+            assert _count(cell, ("lower_bound", "mv", "forward_pass", "lower_bound")) >= 1
+            assert _count(cell, ("upload_primal", "mv", "labels")) >= 3
+        assert _count(cell, ("mv", "compute_pass", "same", "labels" if cell != "relabel_lists" else "ro_labels")) >= 1
+        if cell == "relabel_windows":
+            assert _count(cell, ("path_set_create", "move_windows", "same", "labels")) >= 1 and _count(cell, ("forest_set_create", "move_windows", "same", "labels")) >= 1
+        if cell == "relabel":
+            assert precs == set(SC.PRECISIONS) and SC.props("rrows")["rows_layout"]
+    # the primal arrays: about a third of the unaries unset / stray, the pairwise slots copies of what is below the dimension
+    m = SC.base_model("rgrid8")
+    un = m.f_kind == M.F_VECTOR
+    for form in SC.PRIMAL_FORMS:
+        pr = SC.primal_for(m, 5, form)
+        unset, stray = pr[un, 0] >= m.f_dim0[un], pr[un, 0] < 0
+        assert (0.15 < unset.mean() < 0.5) == (form == "partly_unset") and (0.15 < stray.mean() < 0.5) == (form == "stray")
+        assert unset.any() == (form == "partly_unset") and stray.any() == (form == "stray")
+    # new costs of rgrid8 tie: a quarter grid
+    c = SC.model_with_costs("rgrid8", 7, False)
+    assert np.array_equal(c.const_data * 4, np.round(c.const_data * 4)) and np.array_equal(c.dual_data * 4, np.round(c.dual_data * 4))
+    assert len(np.unique(c.const_data)) <= 5
+
+
+# ---- defects of the path and forest moves and of the labels they leave -------------------------------------------------------------
+class CostChangeLeavesMovedLabelsOnLists(SC.Shadow):
+    """(a) on a model the rounding code refuses a change of costs leaves the labels a move wrote"""
+
+    def _keeping(self, call, *a):
+        lab = self.labels
+        call(*a)
+        if not self._mrf():
+            self.labels = lab
+
+    def upload_costs(self, const=None, duals=None):
+        self._keeping(super().upload_costs, const, duals)
+
+    def set_constants(self, factors, src):
+        self._keeping(super().set_constants, factors, src)
+
+    def upload_shared_pool(self, sh_data=None):
+        self._keeping(super().upload_shared_pool, sh_data)
+
+
+class RefusedLabelCallUnsetsLists(SC.Shadow):
+    """(b) on such a model a refused call that asks for the rounding tables frees the array the move wrote into"""
+
+    def _rounding_tables(self):
+        try:
+            super()._rounding_tables()
+        except E.EngineError:
+            if self.raw is not None:
+                self.labels = SC.unset_labels(self.raw)
+            raise
+
+    def _primal(self, call, it):
+        self._mode()
+        self._rounding_tables()
+        super()._primal(call, it)
+
+
+class MoveTakesTheLastMinimiser(SC.Shadow):
+    """(c)"""
+
+    def _reference(self, m, d, lab, ms, rounds):
+        groups = ms.groups if ms.kind == "forest" else M.forests_from_paths(ms.groups)
+        return SC.FM.forest_moves_reference(m, d, lab, groups, rounds, variant="last")
+
+
+def _members(ms):
+    return sorted({int(u) for g in ms.groups for p in g for u in p} if ms.kind == "path" else {int(u) for un, _ in ms.groups for u in un})
+
+
+def _with_other_labels(sh, m, d, lab, ms, rounds, change):
+    """the move on an array in which ``change`` rewrote the unary labels; unaries that are in no group keep what they held"""
+    if rounds == 0 or not _members(ms):
+        return lab.copy()
+    lab2 = lab.copy()
+    change(lab2)
+    new = SC.Shadow._reference(sh, m, d, lab2, ms, rounds)
+    off = np.setdiff1d(np.flatnonzero(m.f_kind == M.F_VECTOR), _members(ms))
+    new[off, 0] = lab[off, 0]
+    return SC.PM.propagate(m, new, SC.PM.structure(m)[1])
+
+
+class MoveIgnoresOffListNeighbours(SC.Shadow):
+    """(d) a unary that is in no group of the set counts with label 0"""
+
+    def _reference(self, m, d, lab, ms, rounds):
+        def change(x):
+            x[np.setdiff1d(np.flatnonzero(m.f_kind == M.F_VECTOR), _members(ms)), 0] = 0
+        return _with_other_labels(self, m, d, lab, ms, rounds, change)
+
+
+class MoveReadsTheDualsBeforeTheLastPass(SC.Shadow):
+    """(e) a move reads the message vectors of the pairwise factors as they were before the most recent pass (rows that were not
+    refreshed) next to the unaries of the moment.  (With ALL duals from before the pass a move would see the same energy, up to
+    rounding: theta_u + sum m_s is the original unary under every reparametrisation)"""
+    _old = None
+
+    def _rebuild(self, duals):
+        self._old = None
+        super()._rebuild(duals)
+
+    def compute_pass(self, n=1):
+        old = self.duals()
+        super().compute_pass(n)
+        self._old = old
+
+    def _reference(self, m, d, lab, ms, rounds):
+        if self._old is not None:
+            pw = ~RC.vector_mask(m)
+            d = np.array(d, np.float64, copy=True)
+            d[pw] = self._old[:len(d)][pw]
+        return super()._reference(m, d, lab, ms, rounds)
+
+
+class MoveSkipsThePairwiseSlots(SC.Shadow):
+    """(f)"""
+
+    def _relabel(self, ms, rounds):
+        before = self.labels.copy()
+        super()._relabel(ms, rounds)
+        pw = self.raw.f_kind != M.F_VECTOR
+        self.labels[pw] = before[pw]
+
+
+class StaleMoveSetStillMoves(SC.Shadow):
+    """(g) a set survives an upload"""
+
+    def _move_set_alive(self, ms):
+        return self.raw is not None
+
+    def _relabel(self, ms, rounds):
+        if ms.gen == self.gen:
+            super()._relabel(ms, rounds)
+
+
+class UnsetNeighbourCountsAsLabelZero(SC.Shadow):
+    """(h) a unary without a label counts with label 0, not with its last label"""
+
+    def _reference(self, m, d, lab, ms, rounds):
+        def change(x):
+            un = np.flatnonzero(m.f_kind == M.F_VECTOR)
+            x[un, 0] = np.where(x[un, 0] >= m.f_dim0[un], 0, x[un, 0])
+        return _with_other_labels(self, m, d, lab, ms, rounds, change)
+
+
+_MOVES = ("path_moves", "forest_moves")
+_LIST_REFUSALS = ("labels_lists", "upload_primal_lists", "primal_pass_lists")
+# defect -> (cell, acts(step): the defect may act at this step, ops that may be the first to show it)
+RELABEL_DEFECTS = {
+    CostChangeLeavesMovedLabelsOnLists: ("relabel_lists", lambda x: x[0] in ("upload_costs_cold", "upload_costs_warm", "set_constants"), ("ro_labels",)),
+    RefusedLabelCallUnsetsLists: ("relabel_lists", lambda x: x[0] == "refused" and x[1][0] in _LIST_REFUSALS, ("ro_labels",)),
+    MoveTakesTheLastMinimiser: ("relabel", lambda x: x[0] in _MOVES and x[1][1] > 0, ("labels", "ro_labels")),
+    MoveIgnoresOffListNeighbours: ("relabel", lambda x: x[0] in _MOVES and x[1][1] > 0, ("labels", "ro_labels")),
+    MoveReadsTheDualsBeforeTheLastPass: ("relabel", lambda x: x[0] in _MOVES and x[1][1] > 0, ("labels", "ro_labels")),
+    MoveSkipsThePairwiseSlots: ("relabel", lambda x: x[0] in _MOVES and x[1][1] > 0, ("labels",)),
+    StaleMoveSetStillMoves: ("relabel", lambda x: x[0] == "refused" and x[1][0] in ("stale_path_set", "stale_forest_set"), ()),
+    UnsetNeighbourCountsAsLabelZero: ("relabel_windows", lambda x: x[0] in _MOVES and x[1][1] > 0, ("labels", "ro_labels")),
+}
+
+
+@pytest.mark.parametrize("defect", list(RELABEL_DEFECTS), ids=lambda d: d.__name__)
+def test_a_seeded_defect_of_the_relabelling_calls_fails_a_session_where_it_acts(defect):
+    """a committed session of the defect's cell fails: at a step where the defect acts, or at the first observation of the labels
+    behind such a step — and never before the first step at which it can act"""
+    cell, acts, shows = RELABEL_DEFECTS[defect]
+    for seed in SC.CELLS[cell]["seeds"]:
+        session = SC.steps(cell, seed)
+        try:
+            SC.run(defect(), SC.Shadow(), session, observe=None, cell=cell, seed=seed)
+        except SC.Mismatch as ex:
+            i, msg = ex.index, str(ex)
+            break
+    else:
+        pytest.fail("no committed session of %s notices %s" % (cell, defect.__name__))
+    print(defect.__name__, cell, "seed", seed, "noticed at step", i, session[i])
+    assert ("session %s seed %d, step %d %s" % (cell, seed, i, session[i][0])) in msg and "the last steps:" in msg
+    acting = [k for k in range(i + 1) if acts(session[k])]
+    assert acting, (i, session[i])
+    if acts(session[i]):
+        return
+    assert session[i][0] in shows or i == len(session) - 1, (i, session[i])
+    if defect in (CostChangeLeavesMovedLabelsOnLists, RefusedLabelCallUnsetsLists):
+        # labels that are unset when the step acts show nothing: a move of one round at least came before it
+        assert [k for k in range(acting[-1]) if session[k][0] in _MOVES and session[k][1][1] > 0], (acting, i)
