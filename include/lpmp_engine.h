@@ -288,6 +288,23 @@ int lpmp_schedule_info(lpmp_engine* e, int id, int64_t* n_levels, int64_t* n_lau
 int lpmp_schedule_destroy(lpmp_engine* e, int id);
 int lpmp_lower_bound(lpmp_engine* e, double* out);          /* LP::LowerBound, LP_MP.h:1507-1518 */
 int lpmp_factor_lower_bounds(lpmp_engine* e, double* out /*[n_factors], host*/); /* FactorTypeAdapter::LowerBound */
+/* The two scalars into the caller's DEVICE memory: exactly one double is written, asynchronously on the engine's stream.  There is no
+ * stream synchronisation and no device-to-host copy on either path, so a stopping rule, a loss or a log that lives in device code
+ * never stalls the stream; an aborted persistent launch is reported by the next call that synchronises, as for device read-outs.
+ * The value is bit for bit what the host call returns on the same state: the model constant plus the partial sums of the two-stage
+ * sum, added in ascending order by one thread, no contraction.
+ *   lpmp_lower_bound_dev      the stale count never reaches the host: when the engine knows that every tracked bound is stale (an
+ *     upload, lpmp_upload_costs, lpmp_invalidate_lower_bounds, ...) every factor is recomputed; otherwise the stale entries are
+ *     collected and recomputed by a launch of fixed size that reads their number on the device — however many there are (the host
+ *     call recomputes everything above an eighth; the per-factor values are the same).  Inside an open batch of passes that ran
+ *     ahead it reads the row of the pass the caller is at, like lpmp_lower_bound, and does not settle.
+ *     lpmp_lower_bound_recomputed keeps the value of the last HOST call.  LPMP_ERR_STATE while the constants are unspecified.
+ *   lpmp_evaluate_primal_dev  settles first, as the host call; +inf when a side disagrees or a slot is unset (the last kernel reads
+ *     the consistency flag on the device).  LPMP_ERR_UNSUPPORTED on a model the rounding code refuses, as the host call;
+ *     LPMP_ERR_STATE before an upload and while the constants are unspecified.
+ * LPMP_ERR_INVALID for a null pointer.  Rows layout and both f32 table modes work unchanged. */
+int lpmp_lower_bound_dev(lpmp_engine* e, double* dst_dev);
+int lpmp_evaluate_primal_dev(lpmp_engine* e, double* dst_dev);
 /* The sweep kernels keep a per-factor lower bound current as a by-product, so lpmp_lower_bound after
  * a pass is a sum over an array.  Call this after changing duals behind the engine's back (writes through
  * lpmp_device_duals or a borrowed dual buffer): the next lpmp_lower_bound recomputes every factor.
@@ -414,6 +431,24 @@ void lpmp_readout_destroy(lpmp_readout* r);
 int64_t lpmp_readout_n(const lpmp_readout* r);          /* rows */
 int32_t lpmp_readout_max_labels(const lpmp_readout* r); /* longest listed vector */
 int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_mem);
+/* The input twin of lpmp_readout_labels: src[i] (int32, host or device: src_mem) becomes the label of factors[i].  0 ... d0 - 1 is a
+ * label, d0 (the dimension) means unset, exactly what lpmp_readout_labels reports: what one call wrote the other reads back.
+ *   host source    a value outside [0, d0] is LPMP_ERR_INVALID naming the entry, with nothing written; the call returns after its copy
+ *   device source  a value outside [0, d0 - 1] is stored as unset where it is read (the saturated device delta of lpmp_move_windows is
+ *                  the precedent): no bit pattern is copied into the primal array unchecked.  Asynchronous on the engine's stream, no
+ *                  host synchronisation
+ * A read-out that lists a factor twice is refused by THIS call (LPMP_ERR_INVALID naming the factor; decided at lpmp_readout_create and
+ * stored): two rows would write one slot.  labels / vectors / beliefs stay usable on it.
+ * The primal array is made on first use exactly as lpmp_readout_labels makes it, the array of unset labels of a model the rounding
+ * code refuses included: there only the unaries' labels are written, as path moves do.  Otherwise both slots of every pairwise
+ * factor take the labels of its unaries, as after a decode: a label that is SET is copied, so a unary given as unset leaves its
+ * pairwise slots as they were (lpmp_evaluate_primal is +inf either way).  Labels of unlisted unaries stay.  A later
+ * ..._pass_and_primal behaves as after lpmp_upload_primal.  Settles passes that ran ahead; moves no dual, bound, weight, schedule or
+ * timing state; lpmp_schedules_built does not move.  This is how lpmp_path_moves / lpmp_forest_moves — block coordinate descent FROM
+ * the labels the primal array holds — start from a labelling that lives on the device (the previous frame, the coarse level, a
+ * network's arg-max).  LPMP_ERR_STATE for a read-out of a model replaced since; LPMP_ERR_INVALID for a null source (n > 0) or a bad
+ * src_mem; n == 0 is a no-op after the checks. */
+int lpmp_readout_set_labels(lpmp_engine* e, lpmp_readout* r, const int32_t* src, int src_mem);
 int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
 int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem);
 
@@ -694,6 +729,18 @@ int32_t lpmp_window_set_max_labels(const lpmp_window_set* ws);   /* longest list
 int64_t lpmp_window_set_n_pairwise(const lpmp_window_set* ws);   /* DIFF_SHIFT factors whose shift a move may write */
 int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old,
                       const double* cost_new, int64_t cost_stride, int cost_mem);
+/* lpmp_move_windows that CARRIES the labels instead of unsetting them.  Same arguments, same checks; everything lpmp_move_windows does
+ * to duals, shifts, tracked bounds and the caller's arrays, bit for bit.  The labelling is the one piece of state whose meaning is
+ * exactly an absolute label:
+ *   a listed unary i with a label x < d gets x' = min(max(x - delta_i, 0), d - 1), delta_i saturated as in the move; x == d (unset)
+ *   stays unset; unlisted unaries keep their labels.  Afterwards the pairwise slots follow their unaries as after a decode (on a
+ *   model the rounding code refuses: unaries only).  When no primal array exists, none is created.
+ * Consequence: a labelling whose absolute labels all lie in the old and the new windows keeps its primal cost (lpmp_evaluate_primal)
+ * bit for bit, for a move without costs or with cost_old / cost_new that agree on the shared absolute labels — the reparametrised
+ * energy is kept term by term, as said above.  A label that left the window names the nearest absolute label that stayed.  The time
+ * stamp of the rounding passes stays, as after lpmp_upload_primal.  lpmp_move_windows itself keeps unsetting the labels. */
+int lpmp_move_windows_carry(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old,
+                            const double* cost_new, int64_t cost_stride, int cost_mem);
 /* host only: the same support check on a plan.  n_links: unary-pairwise links of the listed factors, n_pairwise as above (either may be
  * NULL); why (why_n bytes; may be NULL): "" or the refusal, which lpmp_last_error reports as well */
 int lpmp_plan_window_info(lpmp_plan* p, int64_t n, const int32_t* factors, int64_t* n_links, int64_t* n_pairwise, char* why, int why_n);

@@ -2389,6 +2389,28 @@ int lpmp_evaluate_primal(lpmp_engine* e, double* cost) {
     *cost = c;
   });
 }
+// the same value into the caller's device memory: no host synchronisation, no device-to-host copy.  The last kernel reads the
+// consistency flag and adds the partial sums as the host does above
+int lpmp_evaluate_primal_dev(lpmp_engine* e, double* dst_dev) {
+  return guarded([&] {
+    require_model(e);
+    if (!dst_dev) throw std::runtime_error("lpmp_evaluate_primal_dev: null destination");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);
+    require_consts(e);
+    ensure_primal(e);
+    ModelState& m = e->model;
+    const int64_t nf = m.plan->p.nf;
+    HIP_CHECK(hipMemsetAsync(m.d_pbad, 0, sizeof(int), e->stream));
+    launch_primal_check(m.d_plinks, m.n_plinks, m.d_primal, m.d_pbad, e->stream);
+    rows_refresh(e);
+    launch_primal_cost(m.d_lbrecs, m.d_dual, m.d_const, m.d_primal, m.d_pcost, nf, m.tab_flag, e->stream);
+    int64_t nb, per; lb_sum_blocks(nf, nb, per);
+    launch_sum_stage(m.d_pcost, m.d_part, nf, per, nb, e->stream);
+    launch_sum_final(m.d_part, nb, m.plan->p.constant, m.d_pbad, dst_dev, e->stream);
+    HIP_CHECK(hipGetLastError());
+  });
+}
 int lpmp_download_primal(lpmp_engine* e, int32_t* out) {
   return guarded([&] {
     require_model(e);
@@ -2776,6 +2798,7 @@ struct lpmp_readout {
   DevBuf<ReadoutRec> recs;              // in the caller's order: row i = record i
   int32_t unsupported = -1;             // lowest listed factor with a message the beliefs do not take (-1: none)
   std::string why;
+  int32_t duplicate = -1;               // lowest factor listed twice (-1: none): lpmp_readout_set_labels refuses the read-out
   // beliefs: the records again, sorted by label-count class, with their links in message-list order; built on the first call
   struct Launch { int64_t first, count; int32_t width; };
   bool have_links = false;
@@ -2838,6 +2861,13 @@ int lpmp_readout_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_
       }
     }
     r->n = (int64_t)r->factors.size();
+    if (factors) {   // (reads are idempotent; a write of two rows into one slot is not: decided here, refused in lpmp_readout_set_labels)
+      std::vector<uint8_t> seen((size_t)p.nf, 0);
+      for (const int32_t f : r->factors) {
+        if (seen[(size_t)f] && (r->duplicate < 0 || f < r->duplicate)) r->duplicate = f;
+        seen[(size_t)f] = 1;
+      }
+    }
     std::vector<ReadoutRec> recs((size_t)r->n);
     r->d0.resize((size_t)r->n);
     for (int64_t i = 0; i < r->n; ++i) {
@@ -2901,26 +2931,64 @@ static void readout_rows(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t d
   }
 }
 
+// the primal array of a call that reads or writes labels on any model: the one ensure_primal makes, or, on a model the rounding code
+// does not take (messages other than unary-pairwise), the array of unset labels in which only unaries ever get a label.  That array
+// is made once and remembered until release_primal (the model goes); a refused call leaves it (ensure_primal)
+static void ensure_label_array(lpmp_engine* e) {
+  ModelState& m = e->model;
+  if (m.have_primal || m.primal_unset_only) return;
+  try { ensure_primal(e); }
+  catch (const UnsupportedError&) {
+    m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
+    upload_unset_primal(e);
+    m.primal_unset_only = true;
+  }
+}
 int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_mem) {
   return guarded([&] {
     readout_enter(e, r, dst, dst_mem, nullptr, "lpmp_readout_labels");
     if (r->n == 0) return;
-    if (!e->model.have_primal && !e->model.primal_unset_only) {
-      try { ensure_primal(e); }
-      catch (const UnsupportedError&) {
-        // a model the rounding code does not take (messages other than unary-pairwise): only a path or forest move sets a label, every
-        // other slot is unset.  The array is made once and remembered until release_primal (the model goes); a refused call leaves it (ensure_primal)
-        e->model.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)e->model.plan->p.nf));
-        upload_unset_primal(e);
-        e->model.primal_unset_only = true;
-      }
-    }
+    ensure_label_array(e);
     if (dst_mem == LPMP_MEM_DEVICE) { launch_readout_labels(r->recs, r->n, e->model.d_primal, dst, e->stream); HIP_CHECK(hipGetLastError()); return; }
     e->model.d_readout.grow(((size_t)r->n + 1) / 2);
     int32_t* stage = reinterpret_cast<int32_t*>(e->model.d_readout.get());
     launch_readout_labels(r->recs, r->n, e->model.d_primal, stage, e->stream);
     HIP_CHECK(hipGetLastError());
     d2h(dst, stage, (size_t)r->n * sizeof(int32_t), e->stream);
+  });
+}
+// the input twin of lpmp_readout_labels (include/lpmp_engine.h)
+int lpmp_readout_set_labels(lpmp_engine* e, lpmp_readout* r, const int32_t* src, int src_mem) {
+  return guarded([&] {
+    const std::string who = "lpmp_readout_set_labels";
+    if (!e || !r) throw std::runtime_error(who + ": null argument");
+    if (!e->model.plan || r->gen != e->model.model_gen) throw StateError(who + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
+    if (src_mem != LPMP_MEM_HOST && src_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": src_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
+    if (r->n > 0 && !src) throw std::runtime_error(who + ": null source");
+    if (r->duplicate >= 0) throw std::runtime_error(who + ": factor " + std::to_string(r->duplicate) + " is listed twice in the read-out (two rows would write one label)");
+    const bool host = src_mem == LPMP_MEM_HOST;
+    if (host)
+      for (int64_t i = 0; i < r->n; ++i)
+        if (src[i] < 0 || src[i] > r->d0[(size_t)i])
+          throw std::runtime_error(who + ": label " + std::to_string(src[i]) + " (entry " + std::to_string(i) + ", factor " + std::to_string(r->factors[(size_t)i]) + ") is outside [0, " +
+                                   std::to_string(r->d0[(size_t)i]) + "] (the dimension means unset); nothing was written");
+    HIP_CHECK(hipSetDevice(e->device));
+    settle(e);
+    // (a device source never waits for the stream, as a read-out into device memory does not; a host source ends in a synchronising copy)
+    if (host) check_chain(e);
+    if (r->n == 0) return;
+    ensure_label_array(e);
+    ModelState& m = e->model;
+    const int32_t* d_src = src;
+    if (host) {
+      m.d_readout.grow(((size_t)r->n + 1) / 2);
+      int32_t* stage = reinterpret_cast<int32_t*>(m.d_readout.get());
+      h2d(stage, src, (size_t)r->n * sizeof(int32_t), e->stream);
+      d_src = stage;
+    }
+    launch_set_labels(r->recs, r->n, d_src, m.d_primal, e->stream);
+    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
+    HIP_CHECK(hipGetLastError());
   });
 }
 int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem) {
@@ -3098,10 +3166,11 @@ int64_t lpmp_window_set_n(const lpmp_window_set* ws) { return ws ? ws->n : 0; }
 int32_t lpmp_window_set_max_labels(const lpmp_window_set* ws) { return ws ? ws->max_labels : 0; }
 int64_t lpmp_window_set_n_pairwise(const lpmp_window_set* ws) { return ws ? ws->n_pairwise : 0; }
 
-int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
-                      int64_t cost_stride, int cost_mem) {
+// lpmp_move_windows and lpmp_move_windows_carry: one path up to what becomes of the labels
+static int move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
+                        int64_t cost_stride, int cost_mem, bool carry) {
   return guarded([&] {
-    const std::string who = "lpmp_move_windows";
+    const std::string who = carry ? "lpmp_move_windows_carry" : "lpmp_move_windows";
     if (!e || !ws) throw std::runtime_error(who + ": null argument");
     if (!e->model.plan || ws->gen != e->model.model_gen) throw StateError(who + ": the window set was made for another model (lpmp_upload_model since lpmp_window_set_create)");
     require_consts(e);
@@ -3135,9 +3204,23 @@ int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta,
     launch_move_shifts(ws->pairs, ws->n_pairwise, d_delta, m.d_const, m.d_lb, e->stream);
     launch_move_windows(ws->recs, ws->links, ws->n, d_delta, m.d_dual, m.d_lb, d_cost[0], d_cost[1], cost_stride, e->stream);
     HIP_CHECK(hipGetLastError());
-    if (m.have_primal || m.primal_unset_only) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
+    if (carry) {
+      // the labelling is the one piece of state whose meaning is exactly an absolute label: x names x - delta in the new window.  No
+      // primal array: none is made.  The pairwise slots follow their unaries as after a decode (primal_unset_only: unaries only)
+      if (m.have_primal || m.primal_unset_only) launch_carry_labels(ws->recs, ws->n, d_delta, m.d_primal, e->stream);
+      if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);
+      HIP_CHECK(hipGetLastError());
+    } else if (m.have_primal || m.primal_unset_only) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
     if (host_delta || host_costs) HIP_CHECK(hipStreamSynchronize(e->stream));   // the caller's arrays are the caller's again
   });
+}
+int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
+                      int64_t cost_stride, int cost_mem) {
+  return move_windows(e, ws, delta, delta_mem, cost_old, cost_new, cost_stride, cost_mem, false);
+}
+int lpmp_move_windows_carry(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
+                            int64_t cost_stride, int cost_mem) {
+  return move_windows(e, ws, delta, delta_mem, cost_old, cost_new, cost_stride, cost_mem, true);
 }
 
 int lpmp_compute_pass_custom(lpmp_engine* e, int64_t n, const int32_t* factors, const int64_t* om_off, const double* om,
@@ -3288,6 +3371,42 @@ int lpmp_lower_bound(lpmp_engine* e, double* out) {
     double lb = e->model.plan->p.constant;
     for (int64_t i = 0; i < nb; ++i) lb += e->h_part[i];
     *out = lb;
+  });
+}
+
+// the same value into the caller's device memory: no host synchronisation, no device-to-host copy, so the count of stale entries
+// stays on the device (the list kernel reads it there) and an aborted chain run is reported by the next call that synchronises.
+// lpmp_lower_bound_recomputed keeps the value of the last host call
+int lpmp_lower_bound_dev(lpmp_engine* e, double* dst_dev) {
+  return guarded([&] {
+    require_model(e);
+    if (!dst_dev) throw std::runtime_error("lpmp_lower_bound_dev: null destination");
+    HIP_CHECK(hipSetDevice(e->device));
+    ModelState& m = e->model;
+    const int64_t nf = m.plan->p.nf;
+    int64_t nb, per; lb_sum_blocks(nf, nb, per);
+    const auto& sp = m.batch;
+    if (sp.n > 0 && sp.pos >= 1 && sp.pos < sp.n) {   // inside a batch of passes that ran ahead: that pass's own row, as the host call
+      launch_sum_final(sp.d_hpart + (size_t)(sp.pos - 1) * 1024, nb, m.plan->p.constant, nullptr, dst_dev, e->stream);
+      HIP_CHECK(hipGetLastError());
+      return;
+    }
+    require_consts(e);
+    rows_refresh(e);
+    if (e->use_lb_tracking && !m.lb_all_stale) {
+      HIP_CHECK(hipMemsetAsync(m.d_stale_n, 0, sizeof(unsigned long long), e->stream));
+      launch_lb_collect_stale(m.d_lb, nf, m.d_stale, m.d_stale_n, e->stream);
+      launch_factor_lb_list_dev(m.d_lbrecs, m.d_dual, m.d_const, m.d_lb, m.d_stale, m.d_stale_n, nf, m.tab_flag, e->stream);
+    } else {
+      for (const auto& r : m.lb_runs) {
+        if (r.cls == 0 || !launch_dense_lb(r.cls, m.d_lbrecs, m.d_dual, m.d_const, m.d_lb, r.first, r.count, m.tab_flag, e->stream))
+          launch_factor_lb(m.d_lbrecs + r.first, m.d_dual, m.d_const, m.d_lb + r.first, r.count, m.tab_flag, e->stream);
+      }
+      m.lb_all_stale = false;
+    }
+    launch_sum_stage(m.d_lb, m.d_part, nf, per, nb, e->stream);
+    launch_sum_final(m.d_part, nb, m.plan->p.constant, nullptr, dst_dev, e->stream);
+    HIP_CHECK(hipGetLastError());
   });
 }
 

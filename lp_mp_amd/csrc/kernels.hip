@@ -4689,4 +4689,70 @@ void launch_move_shifts(const MoveShiftRec* recs, int64_t n, const int32_t* delt
   if (n > 0) hipLaunchKernelGGL(move_shifts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, delta, cdata, lb);
 }
 
+// ---- primal state on the device (engine.cpp: lpmp_readout_set_labels, lpmp_move_windows_carry, lpmp_lower_bound_dev,
+// lpmp_evaluate_primal_dev) ------------------------------------------------------------------------------------
+// Plain launches on the engine's stream: no LDS, no atomics, plain vector stores, 64-bit indexing of primal[2 * f].
+// labels in: the input twin of readout_labels_kernel.  One thread per listed factor; src[row] is its label, the dimension (or any
+// value outside [0, d0 - 1]: no bit pattern reaches the primal array unchecked) means unset.  A read-out with a factor listed
+// twice never gets here (engine.cpp), so every slot has one writer
+__global__ void __launch_bounds__(256)
+set_labels_kernel(const ReadoutRec* __restrict__ recs, int64_t n, const int32_t* __restrict__ src, int32_t* __restrict__ primal) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const ReadoutRec r = recs[i];
+  const int32_t x = src[r.row];
+  primal[2 * (int64_t)r.factor] = (x >= 0 && x < r.d0) ? x : r.d0;
+}
+// labels carried through a window move: new label x is old label x + delta, so the label that named old x names x - delta now,
+// clamped into the window (the nearest absolute label that stayed).  One thread per listed unary; the delta is saturated as
+// move_windows_kernel saturates it; an unset slot (the dimension, or whatever else is no label) is left as it is
+__global__ void __launch_bounds__(256)
+carry_labels_kernel(const MoveRec* __restrict__ recs, int64_t n, const int32_t* __restrict__ delta, int32_t* __restrict__ primal) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const MoveRec r = recs[i];
+  const int32_t x = primal[2 * (int64_t)r.factor];
+  if (x < 0 || x >= r.d0) return;
+  primal[2 * (int64_t)r.factor] = min(max(x - move_delta(delta, r.row), 0), r.d0 - 1);
+}
+// factor_lb_list_kernel with the length of the list read from the device counter lb_collect_stale_kernel left: a fixed grid, a
+// wave per entry, grid-stride (the host never learns the count)
+__global__ void __launch_bounds__(256)
+factor_lb_list_dev_kernel(const LbRec* __restrict__ recs, const double* __restrict__ dual, const double* __restrict__ cdata,
+                          double* __restrict__ out, const int32_t* __restrict__ list, const unsigned long long* __restrict__ counter, int tab32) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t count = (int64_t)*counter, stride = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < count; i += stride) {
+    const int32_t f = list[i];
+    const double lb = factor_lb(recs[f], dual, cdata, tab32, lane);
+    if (lane == 0) out[f] = lb;
+  }
+}
+// the second stage of the two-stage sum, as the host adds it: the model constant plus the partial sums of sum_stage_kernel in
+// ascending order, one thread, one IEEE add each.  bad != nullptr: the consistency flag of primal_check_kernel; set: +inf
+__global__ void __launch_bounds__(64)
+sum_final_kernel(const double* __restrict__ part, int64_t n_part, double constant, const int* __restrict__ bad, double* __restrict__ dst) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double s = constant;
+  for (int64_t i = 0; i < n_part; ++i) s += part[i];
+  if (bad && *bad != 0) s = LPMP_INF;
+  *dst = s;
+}
+void launch_set_labels(const ReadoutRec* recs, int64_t n, const int32_t* src, int32_t* primal, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(set_labels_kernel, blocks256(n), dim3(256), 0, s, recs, n, src, primal);
+}
+void launch_carry_labels(const MoveRec* recs, int64_t n, const int32_t* delta, int32_t* primal, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(carry_labels_kernel, blocks256(n), dim3(256), 0, s, recs, n, delta, primal);
+}
+void launch_factor_lb_list_dev(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list,
+                               const unsigned long long* counter, int64_t max_count, int tab32, hipStream_t s) {
+  if (max_count <= 0) return;
+  int64_t blocks = (max_count + 3) / 4;
+  if (blocks > LB_LIST_DEV_BLOCKS) blocks = LB_LIST_DEV_BLOCKS;
+  hipLaunchKernelGGL(factor_lb_list_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, s, recs, dual, cdata, out, list, counter, tab32);
+}
+void launch_sum_final(const double* part, int64_t n_part, double constant, const int* bad, double* dst, hipStream_t s) {
+  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(64), 0, s, part, n_part, constant, bad, dst);
+}
+
 }  // namespace lpmp

@@ -219,5 +219,16 @@ void launch_set_constants(const SetConstRec* recs, int64_t n, const double* src,
 void launch_move_windows(const MoveRec* recs, const MoveLink* links, int64_t n, const int32_t* delta, double* dual, double* lb,
                          const double* cost_old, const double* cost_new, int64_t cost_stride, hipStream_t s);
 void launch_move_shifts(const MoveShiftRec* recs, int64_t n, const int32_t* delta, double* cdata, double* lb, hipStream_t s);
+// primal state on the device.  set_labels: label slot of record i's factor := src[row] (device array), unset (the dimension) for a
+// value outside [0, d0 - 1].  carry_labels: the label slot x < d0 of record i's factor := clamp(x - delta[row], 0, d0 - 1), the delta
+// saturated as in launch_move_windows; unset slots stay.  factor_lb_list_dev: launch_factor_lb_list with the count read from
+// *counter on the device (max_count: the most it can be, sizes the fixed grid of at most LB_LIST_DEV_BLOCKS workgroups).  sum_final:
+// *dst = constant + part[0] + ... + part[n_part - 1] added in that order by one thread, or +inf when bad != nullptr and *bad != 0
+constexpr int64_t LB_LIST_DEV_BLOCKS = 2048;
+void launch_set_labels(const ReadoutRec* recs, int64_t n, const int32_t* src, int32_t* primal, hipStream_t s);
+void launch_carry_labels(const MoveRec* recs, int64_t n, const int32_t* delta, int32_t* primal, hipStream_t s);
+void launch_factor_lb_list_dev(const LbRec* recs, const double* dual, const double* cdata, double* out, const int32_t* list,
+                               const unsigned long long* counter, int64_t max_count, int tab32, hipStream_t s);
+void launch_sum_final(const double* part, int64_t n_part, double constant, const int* bad, double* dst, hipStream_t s);
 
 }  // namespace lpmp

@@ -86,6 +86,7 @@ EXPORTS = [
     "lpmp_path_set_scratch_bytes", "lpmp_path_moves", "lpmp_plan_path_info",
     "lpmp_forest_set_create", "lpmp_forest_set_destroy", "lpmp_forest_set_n_groups", "lpmp_forest_set_n_trees", "lpmp_forest_set_max_height",
     "lpmp_forest_set_scratch_bytes", "lpmp_forest_moves", "lpmp_plan_forest_info", "lpmp_plan_suggest_forests",
+    "lpmp_readout_set_labels", "lpmp_move_windows_carry", "lpmp_lower_bound_dev", "lpmp_evaluate_primal_dev",
 ]
 
 
@@ -261,6 +262,11 @@ def lib():
             L.lpmp_forest_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             L.lpmp_plan_forest_info.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_int]
             L.lpmp_plan_suggest_forests.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+        if hasattr(L, "lpmp_readout_set_labels"):    # primal state on the device (absent only in an older build loaded for an A/B)
+            L.lpmp_readout_set_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.lpmp_move_windows_carry.argtypes = L.lpmp_move_windows.argtypes
+            L.lpmp_lower_bound_dev.argtypes = [C.c_void_p, C.c_void_p]
+            L.lpmp_evaluate_primal_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.lpmp_plan_suggest_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_colour_major_order.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lpmp_graph_refine_partition.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]
@@ -943,7 +949,12 @@ class Engine:
     def schedule_destroy(self, sid: int):
         _chk(self.L.lpmp_schedule_destroy(self.h, int(sid)))
 
-    def lower_bound(self) -> float:
+    def lower_bound(self, dst_dev: Optional[int] = None):
+        """LP::LowerBound.  ``dst_dev``: a raw device pointer to one double — the value is written there asynchronously on the
+        engine's stream, without any host synchronisation (lpmp_lower_bound_dev), and the call returns None"""
+        if dst_dev is not None:
+            _chk(self.L.lpmp_lower_bound_dev(self.h, C.c_void_p(dst_dev)))
+            return None
         out = C.c_double()
         _chk(self.L.lpmp_lower_bound(self.h, C.addressof(out)))
         return out.value
@@ -994,7 +1005,12 @@ class Engine:
         _chk(self.L.lpmp_check_primal_consistency(self.h, C.addressof(out)))
         return bool(out.value)
 
-    def evaluate_primal(self) -> float:
+    def evaluate_primal(self, dst_dev: Optional[int] = None):
+        """LP::EvaluatePrimal (+inf when inconsistent / unset).  ``dst_dev``: a raw device pointer to one double — written
+        asynchronously on the engine's stream without any host synchronisation (lpmp_evaluate_primal_dev); returns None"""
+        if dst_dev is not None:
+            _chk(self.L.lpmp_evaluate_primal_dev(self.h, C.c_void_p(dst_dev)))
+            return None
         out = C.c_double()
         _chk(self.L.lpmp_evaluate_primal(self.h, C.addressof(out)))
         return out.value
@@ -1178,6 +1194,23 @@ class Readout:
         _chk(self.L.lpmp_readout_labels(self.e.h, self.h, out.ctypes.data, MEM_HOST))
         return out[:self.n]
 
+    def set_labels(self, src=None, src_dev: Optional[int] = None):
+        """the input twin of ``labels`` (lpmp_readout_set_labels): ``src`` an integer array of ``n`` entries, entry i the label of
+        listed factor i, its label count meaning unset; or ``src_dev`` a raw device pointer to int32 values (asynchronous on the
+        engine's stream; values that are no label are stored as unset).  A read-out that lists a factor twice is refused."""
+        if src_dev is not None:
+            _chk(self.L.lpmp_readout_set_labels(self.e.h, self.h, C.c_void_p(src_dev), MEM_DEVICE))
+            return
+        s = np.asarray([] if src is None else src).reshape(-1)
+        if s.shape[0] != self.n:
+            raise ValueError(f"set_labels: {self.n} labels expected, got {s.shape[0]}")
+        if self.n and not np.issubdtype(s.dtype, np.integer):
+            raise ValueError("set_labels: integer labels are expected")
+        if self.n and (s.min() < -(1 << 31) or s.max() >= (1 << 31)):
+            raise ValueError("set_labels: a label does not fit an int32")
+        s = np.ascontiguousarray(s, np.int32) if self.n else np.zeros(1, np.int32)
+        _chk(self.L.lpmp_readout_set_labels(self.e.h, self.h, C.c_void_p(s.ctypes.data), MEM_HOST))
+
     def _rows(self, fn, dst_dev, stride):
         stride = self.max_labels if stride is None else int(stride)
         if dst_dev is not None:
@@ -1226,13 +1259,16 @@ class WindowSet:
     def __del__(self):
         self.close()
 
-    def move(self, delta=None, delta_dev: Optional[int] = None, cost_old=None, cost_new=None, cost_dev=None, stride: Optional[int] = None):
+    def move(self, delta=None, delta_dev: Optional[int] = None, cost_old=None, cost_new=None, cost_dev=None, stride: Optional[int] = None,
+             carry_labels: bool = False):
         """move the window of listed factor i by ``delta[i]`` labels (lpmp_move_windows): ``delta`` an integer array of ``n`` entries
         with |delta| <= 2^20, or ``delta_dev`` a raw device pointer to int32 values.  ``cost_old`` / ``cost_new``: the original unary
         costs in the old and in the new window as [n, >= max_labels] arrays (both or neither), or ``cost_dev=(old_ptr, new_ptr)`` raw
         device pointers with ``stride``; a pointer of the pair may be None to hand the library one array alone (refused).  With
         device inputs only the call is asynchronous on the engine's stream.  ``Engine.model`` keeps the constants of the upload
-        (``model.move_windows`` gives the moved model; ``LP.move_windows`` keeps the mirror's books)."""
+        (``model.move_windows`` gives the moved model; ``LP.move_windows`` keeps the mirror's books).
+        ``carry_labels``: the labels move with their windows instead of becoming unset (lpmp_move_windows_carry;
+        ``model.move_labels`` is the numpy statement)."""
         if delta_dev is not None:
             dp, dm = C.c_void_p(delta_dev), MEM_DEVICE
         else:
@@ -1269,7 +1305,8 @@ class WindowSet:
             if cs > have[0].shape[1]:
                 raise ValueError("move: stride beyond the rows of the cost arrays")
             co, cn = [None if a is None else C.c_void_p(a.ctypes.data) for a in arrs]
-        _chk(self.L.lpmp_move_windows(self.e.h, self.h, dp, dm, co, cn, cs, cm))
+        fn = self.L.lpmp_move_windows_carry if carry_labels else self.L.lpmp_move_windows
+        _chk(fn(self.e.h, self.h, dp, dm, co, cn, cs, cm))
 
 
 class PathSet:

@@ -518,7 +518,7 @@ class LP:
         self._cost_dual = new.dual_data
         e.model = new
 
-    def move_windows(self, handles, delta, new_costs=None):
+    def move_windows(self, handles, delta, new_costs=None, carry_labels=False):
         """move the label windows of the unaries ``handles`` (add_factor's return values, each once) by ``delta[i]`` labels ON THE
         DEVICE (Engine.window_set / WindowSet.move): new label x of unary i is its old label x + delta[i], theta and the messages of
         the adjacent ``diff_shift_pairwise_factor``s are carried along their label axis, and the shift of every such factor becomes
@@ -526,7 +526,8 @@ class LP:
         its new window (same length); None: labels that stay keep their cost and labels that enter the window copy the nearest end.
         The stored ops follow (``shift`` of the adjacent factors, the unaries' ``cost``), so a following ``upload_costs(warm=True)``
         finds nothing to send.  NOT a structural call: every schedule stays.  Every message of a listed unary must lead to a
-        diff_shift_pairwise_factor (Engine.window_set raises otherwise, naming the factor)."""
+        diff_shift_pairwise_factor (Engine.window_set raises otherwise, naming the factor).  ``carry_labels``: the labels move with
+        their windows (label x becomes x - delta[i], clamped into the window) instead of becoming unset."""
         import dataclasses
         e = self._ready()
         handles = [int(h) for h in handles]
@@ -547,14 +548,15 @@ class LP:
             if n.shape != c.shape:
                 raise RuntimeError("move_windows: the cost of factor %d would change its length (a structural change)" % h)
             old.append(c); new.append(np.array(n, copy=True))
+        kw = {"carry_labels": True} if carry_labels else {}
         if new_costs is None:
-            ws.move(delta)
+            ws.move(delta, **kw)
         else:
             L = max(ws.max_labels, 1)
             co, cn = np.zeros((len(handles), L)), np.zeros((len(handles), L))
             for i in range(len(handles)):
                 co[i, :old[i].shape[0]] = old[i]; cn[i, :new[i].shape[0]] = new[i]
-            ws.move(delta, cost_old=co, cost_new=cn)
+            ws.move(delta, cost_old=co, cost_new=cn, **kw)
         # the host's books: ops, the uploaded constants and the costs the next warm upload takes differences to
         const = np.array(self._model.const_data, np.float64, copy=True)
         coff, doff = self._model.const_offsets(), self._model.dual_offsets()
@@ -621,8 +623,10 @@ class LP:
     def ComputeBackwardPass(self):
         e = self._ready(); e.set_reparametrization(self._mode()); e.backward_pass()
 
-    def LowerBound(self) -> float:
-        return self._ready().lower_bound()
+    def LowerBound(self, dst_dev=None):
+        """``dst_dev``: a raw device pointer to one double — written asynchronously on the engine's stream without any host
+        synchronisation (Engine.lower_bound); returns None then"""
+        return self._ready().lower_bound(dst_dev)
 
     # -- primal rounding inside the sweep (reference LP_MP.h:914-940, 1067-1082, 1521-1536) ------------------
     def ComputeForwardPassAndPrimal(self, iteration: int):
@@ -638,8 +642,9 @@ class LP:
     def CheckPrimalConsistency(self) -> bool:
         return self._ready().check_primal_consistency()
 
-    def EvaluatePrimal(self) -> float:
-        return self._ready().evaluate_primal()
+    def EvaluatePrimal(self, dst_dev=None):
+        """``dst_dev``: as in ``LowerBound``"""
+        return self._ready().evaluate_primal(dst_dev)
 
     def decode_primal(self, direction: int = 0, refine: int = 0) -> float:
         """labels from the current duals by conditional rounding (Engine.decode_primal; no reference counterpart):
@@ -683,7 +688,7 @@ class LP:
     def readout(self, factor_handles=None):
         """a prepared read-out (Engine.readout; no reference counterpart) of the listed vector factors — what
         ``add_factor`` returned for them, None: all of them — with ``labels()``, ``vectors()`` and ``beliefs()`` into host or device
-        arrays.  It belongs to the uploaded model: a structural change of the LP (the next upload) ends it."""
+        arrays, and ``set_labels()`` from one (the start labelling of ``path_moves`` / ``forest_moves``).  It belongs to the uploaded model: a structural change of the LP (the next upload) ends it."""
         return self._ready().readout(factor_handles)
 
     def primal(self) -> np.ndarray:

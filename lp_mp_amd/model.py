@@ -521,6 +521,37 @@ def move_windows(model: "FlatModel", duals, factors, delta, cost_old=None, cost_
     return dataclasses.replace(model, const_data=const, _keep=[]), out
 
 
+def move_labels(primal, model: "FlatModel", factors, delta):
+    """The numpy statement of what lpmp_move_windows_carry does to the labels (include/lpmp_engine.h has the rule).  ``primal`` is the
+    [n_factors, 2] array of ``Engine.download_primal``; the windows of the listed VECTOR ``factors`` (None: all of them) move by
+    ``delta[i]`` labels, a delta beyond +-2^20 saturated as the device saturates it.  Returns a new array: a listed unary with a label
+    x < d gets min(max(x - delta_i, 0), d - 1) — new label x is old label x + delta, so what named old x names x - delta —, an unset
+    entry (the dimension) stays unset, unlisted unaries keep their labels, and then side s of every pairwise factor takes the label
+    of its unary over every unary-pairwise message whose unary holds one, as after a decode.  On a model the rounding code refuses
+    (a message type that is not unary-pairwise) no pairwise slot is written."""
+    out = np.array(primal, np.int32, copy=True)
+    if out.shape != (model.n_factors, 2):
+        raise ValueError("move_labels: a [n_factors, 2] primal array is expected")
+    if factors is None:
+        factors = np.flatnonzero(model.f_kind == F_VECTOR)
+    factors = np.asarray(factors, np.int64).reshape(-1)
+    delta = np.asarray(delta).reshape(-1)
+    if delta.shape[0] != factors.shape[0] or (factors.shape[0] and not np.issubdtype(delta.dtype, np.integer)):
+        raise ValueError("move_labels: one integer delta per listed factor")
+    delta = np.clip(delta.astype(np.int64), -MOVE_DELTA_MAX, MOVE_DELTA_MAX)
+    for i, u in enumerate(factors):
+        u = int(u)
+        d, x = int(model.f_dim0[u]), int(out[u, 0])
+        if 0 <= x < d:
+            out[u, 0] = min(max(x - int(delta[i]), 0), d - 1)
+    if all(t.kind == M_UNARY_PAIRWISE for t in model.mtypes):
+        for k in range(model.n_messages):
+            u, p = int(model.m_left[k]), int(model.m_right[k])
+            if out[u, 0] < model.f_dim0[u]:
+                out[p, int(model.mtypes[int(model.m_type[k])].param)] = out[u, 0]
+    return out
+
+
 def truncated_quadratic(d0: int, d1: int, slope: float, trunc: float) -> np.ndarray:
     """D[k] = min(slope * (k - (d1 - 1))^2, trunc): the square is exact in double, then one multiply"""
     k = np.arange(d0 + d1 - 1, dtype=np.float64) - (d1 - 1)
