@@ -1,5 +1,6 @@
 // engine.cpp — the C ABI of include/lpmp_engine.h: device memory, schedules, launches.
-// Host code only; the kernels are in kernels.hip.  There is NO CPU execution path: every compute
+// Host code only; the kernels are in kernels.hip, the prepared sets (read-outs, window, path and forest sets) in prepared.cpp, and
+// what the two host files share in engine_state.hpp.  There is NO CPU execution path: every compute
 // entry point needs a HIP device and fails with LPMP_ERR_DEVICE otherwise.
 #include <hip/hip_runtime.h>
 
@@ -19,10 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "engine_internal.h"
-#include "kernels.hpp"
-
-using namespace lpmp;
+#include "engine_state.hpp"
 
 static thread_local std::string g_error;
 const char* lpmp_last_error(void) { return g_error.c_str(); }
@@ -30,139 +28,10 @@ int lpmp_set_last_error(const char* msg) { g_error = msg ? msg : ""; return 0; }
 const char* lpmp_version(void) { return "lp_mp_amd 0.1 (gfx950)"; }
 int lpmp_experiment_build(void) { return 0; }   // kept for the ABI: the library has no experimental build
 
-namespace {
-
-struct DeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct StateError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct UnsupportedError : std::runtime_error { using std::runtime_error::runtime_error; };
-
-#define HIP_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw DeviceError(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <class F>
-int guarded(F&& f) {
-  try { f(); return LPMP_OK; }
-  catch (const DeviceError& e) { g_error = e.what(); return LPMP_ERR_DEVICE; }
-  catch (const StateError& e) { g_error = e.what(); return LPMP_ERR_STATE; }
-  catch (const UnsupportedError& e) { g_error = e.what(); return LPMP_ERR_UNSUPPORTED; }
-  catch (const lpmp::UnsupportedModel& e) { g_error = e.what(); return LPMP_ERR_UNSUPPORTED; }   // (the planner's size limits)
-  catch (const std::bad_alloc&) { g_error = "out of host memory"; return LPMP_ERR_INVALID; }
-  catch (const std::exception& e) { g_error = e.what(); return LPMP_ERR_INVALID; }
-}
-
-// A device allocation that frees itself: move-only, empty or `capacity()` elements.  The only place of this file that calls
-// hipMalloc / hipFree.  Freeing (reset, destructor, move assignment) never throws; hipFree waits for the device.
-template <class T>
-class DevBuf {
-  T* p_ = nullptr; size_t cap_ = 0;
- public:
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; } return *this; }
-  ~DevBuf() { reset(); }
-  T* get() const { return p_; }
-  operator T*() const { return p_; }
-  size_t capacity() const { return cap_; }
-  void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
-  // a fresh allocation of n elements (what the buffer held is freed first); try_alloc reports a failure instead of throwing
-  bool try_alloc(size_t n) {
-    reset();
-    if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return false; }
-    cap_ = n;
-    return true;
-  }
-  void alloc(size_t n) { reset(); HIP_CHECK(hipMalloc((void**)&p_, n * sizeof(T))); cap_ = n; }
-  // a buffer that is refilled in place: a new allocation only when n exceeds the capacity, then with a quarter to spare
-  void grow(size_t n) { if (n > cap_) alloc(n + n / 4 + 16); }
-};
-struct GraphExec {   // an instantiated graph, destroyed with its owner; move-only
-  hipGraphExec_t g = nullptr;
-  GraphExec() = default;
-  GraphExec(const GraphExec&) = delete;
-  GraphExec& operator=(const GraphExec&) = delete;
-  GraphExec(GraphExec&& o) noexcept : g(o.g) { o.g = nullptr; }
-  GraphExec& operator=(GraphExec&& o) noexcept { if (this != &o) { reset(); g = o.g; o.g = nullptr; } return *this; }
-  ~GraphExec() { reset(); }
-  void reset() { if (g) { (void)hipGraphExecDestroy(g); g = nullptr; } }
-};
-
-// chain executor (deep schedules): the device copy of a ChainPlan, or of the ticket lists of n joined passes
-struct DevChain {
-  int32_t kclass = 0, tickets = 0, epoch = 0;
-  bool banded = false;                     // Infinity-Cache ticket order: plain table loads, not the streaming policy
-  bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
-  DevBuf<ChainLaunch> launches; DevBuf<int32_t> tk_launch, tk_block, dep_off, dep, done, next;
-  DevBuf<unsigned long long> mailbox;      // tagged granules of the message vectors that travel between dependent records (chain_plan.cpp)
-};
-// what issue_launches reads of a schedule: its device arrays and a list of its launches
-struct LaunchView { const UpdRec* recs; const Op* ops; const Op* packets; const std::vector<LevelRange>& launches; };
-
-struct DevSchedule {
-  DevBuf<UpdRec> recs; DevBuf<Op> ops, packets;   // (a scratch schedule is refilled in place: DevBuf::grow)
-  std::vector<LevelRange> launches;
-  std::vector<int32_t> diff_tab_off, diff_tab, diff_tab_ne;   // Schedule::diff_tab_off / diff_tab / diff_tab_ne: what new pool values ask again (refresh_diff_band)
-  int64_t n_levels = 0, n_recv = 0, n_send = 0, alg_bytes = 0;
-  GraphExec graph, graph_primal;           // graph_primal: the same launches with the SWEEP_PRIMAL flag
-  bool adaptive_built = false;             // built with every update on the generic kernels (adaptive send rule)
-  std::vector<DevChain> chains;            // one per kernel class; the other launches stay plain
-  std::vector<LevelRange> plain;           // launches that do not belong to a chain
-  bool chain = false;
-  LaunchView view() const { return {recs, ops, packets, launches}; }
-  LaunchView plain_view() const { return {recs, ops, packets, plain}; }
-  void release_chain() { chains.clear(); plain.clear(); chain = false; }
-  void release() {
-    graph.reset(); graph_primal.reset();
-    recs.reset(); ops.reset(); packets.reset();
-    release_chain();
-    launches.clear(); diff_tab_off.clear(); diff_tab.clear(); diff_tab_ne.clear();
-  }
-  // new pool values: diff_band / diff_shift_band of the KC_DIFF launches again; a graph captured with the other kernel choice is never replayed
-  void refresh_diff_band(const Plan& p) {
-    const bool a = p.refresh_diff_band(launches, diff_tab_off, diff_tab, diff_tab_ne), b = p.refresh_diff_band(plain, diff_tab_off, diff_tab, diff_tab_ne);
-    bool diff = false;
-    for (const auto& lr : launches) diff = diff || lr.kclass == KC_DIFF;
-    if (a || b || diff) { graph.reset(); graph_primal.reset(); }
-  }
-};
-
 static long long chain_timeout_ticks() {    // LPMP_CHAIN_TIMEOUT_S (default 20 s)
   static const long long v = [] { const char* e = std::getenv("LPMP_CHAIN_TIMEOUT_S"); const double s = e ? std::atof(e) : 20.0; return (long long)(std::max(0.001, s) * 1e8); }();
   return v;
 }
-
-struct ClassTiming { double ms = 0; int64_t launches = 0, factors = 0, receives = 0, bytes = 0, chain_launches = 0, band_launches = 0, shift_launches = 0, shift_band_launches = 0, peer_minima_launches = 0; };
-
-}  // namespace
-
-struct lpmp_plan {
-  Plan p;
-  RotationInfo rot[LPMP_REPAM_COUNT];
-  Schedule sched_cache[2][LPMP_REPAM_COUNT]; bool have_sched[2][LPMP_REPAM_COUNT] = {{false}};
-  Schedule pass_cache[LPMP_REPAM_COUNT]; bool have_pass[LPMP_REPAM_COUNT] = {false};   // forward+backward as one fused sequence
-  Schedule bf_cache[LPMP_REPAM_COUNT]; bool have_bf[LPMP_REPAM_COUNT] = {false};       // backward+forward (the seam between two passes)
-  bool rotation_ok[LPMP_REPAM_COUNT] = {false};
-  DecodePlan decode_cache[2]; bool have_decode[2] = {false, false};   // conditional rounding (structure only: no weights, no mode)
-  const DecodePlan& decode(int d) {
-    if (!have_decode[d]) { decode_cache[d] = p.decode_plan(d); have_decode[d] = true; }
-    return decode_cache[d];
-  }
-  // new VALUES for the pool (Plan::set_shared_pool): of the cached schedules only diff_band / diff_shift_band of their KC_DIFF launches move
-  void set_shared_pool(const double* values) {
-    p.set_shared_pool(values);
-    auto again = [&](Schedule& s) { p.refresh_diff_band(s.launches, s.diff_tab_off, s.diff_tab, s.diff_tab_ne); };
-    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
-      for (int d = 0; d < 2; ++d) again(sched_cache[d][m]);
-      again(pass_cache[m]); again(bf_cache[m]);
-    }
-  }
-  void drop_caches() {   // the kernel classes of every schedule change with Plan::force_generic
-    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
-      for (int d = 0; d < 2; ++d) { sched_cache[d][m] = Schedule(); have_sched[d][m] = false; }
-      pass_cache[m] = Schedule(); have_pass[m] = false; bf_cache[m] = Schedule(); have_bf[m] = false; rotation_ok[m] = false;
-    }
-  }
-};
 
 static void plan_pass_schedule(lpmp_plan* pl, int mode, bool chains = true) {
   if (pl->have_pass[mode]) return;
@@ -242,223 +111,6 @@ static void plan_rotation(lpmp_plan* pl, int mode) {
   pl->rotation_ok[mode] = ok;
   if (!ok) bf = Schedule();
 }
-
-// the uploaded model and its parts: internal to the engine's host code
-namespace lpmp {
-namespace host {
-
-// joined passes as one persistent launch: expansions of RotationInfo, by mode and pass count
-struct RotChain {
-  DevChain dc; int n_steps = 0; int64_t factors = 0, recv = 0, bytes = 0; uint64_t last_use = 0; size_t dev_bytes = 0;
-  // periodic form (rotation_chain): dc holds the TEMPLATE of n_tmpl passes whose tickets [per_begin, per_begin + per_len) are
-  // one group of `depth` steps that an n-pass launch executes 1 + (n - n_tmpl) / (depth / 2) times; per_* sums: one period
-  bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
-  bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
-  bool pq_wide = false;           // ... and the H / K / T blocks hold PQ_WIDE_RECORDS records (ModelState::rot_wide): the wide consume form
-  int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
-};
-// the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
-// (tile_sets: one per tile size asked for — short and long calls of one model may take different sizes, and both stay)
-struct RotOrder { bool have_geo = false; RotGeometry geo; std::map<int, TileSet> tile_sets; bool have_pq_geo = false; PqGeometry pq_geo; };
-// conditional rounding from the duals (lpmp_decode_primal): per direction the records sorted by (level, lane-group / wave class),
-// their links, and one launch per level and class.  Structure only: built on first use, kept until the next lpmp_upload_model
-struct DevDecode {
-  struct Launch { int64_t first, count; int32_t width, level; };
-  bool have = false;
-  DevBuf<DecodeRec> recs; DevBuf<DecodeLink> links;
-  std::vector<Launch> launches;
-  void release() { have = false; recs.reset(); links.reset(); launches.clear(); }
-};
-struct LbRun { int cls; int64_t first, count; };
-// speculative passes: the open batch and what the engine has learnt of the caller on this model; a fresh value
-// is "no batch, nothing learnt, no buffers"
-struct SpecBatch {
-  int n = 0, pos = 0, mode = -1;     // the open batch: n passes were launched as one chain, the caller has asked for pos of them
-  int run_len = 0, learned = 0, last_batch = 0;   // plain single passes since the last other call; length of the previous such run
-  bool lb_ready = false; std::vector<double> lb;   // bounds after passes 1 ... n - 1 of the batch
-  DevBuf<double> d_snap;             // duals (+ tracked bounds) at the start of the batch
-  DevBuf<double> d_hist;             // (n - 1) rows of per-factor bounds
-  DevBuf<double> d_hpart;            // partial sums of those rows
-  bool snap_lb_stale = false;
-};
-
-// Everything that belongs to the uploaded model.  A default-constructed value is "no model" (plan empty); lpmp_upload_model builds
-// one as a local and commits it by move, so a refused upload leaves nothing behind, and a member added here needs no line anywhere
-// else to be dropped with its model.
-struct ModelState {
-  std::unique_ptr<lpmp_plan> plan;
-  // the base pointers the kernels use, and beside each the engine's own allocation: empty when the caller's memory is borrowed (LPMP_MEM_DEVICE)
-  double* d_dual = nullptr; DevBuf<double> dual_buf; bool own_dual() const { return dual_buf.get() != nullptr; }
-  double* d_const = nullptr; DevBuf<double> const_buf;
-  DevBuf<int32_t> d_tabs;
-  DevBuf<LbRec> d_lbrecs;
-  DevBuf<double> d_lb, d_part;
-  // tracked per-factor lower bounds (kernels.hip): d_lb[f] is valid or NaN; lb_all_stale: recompute everything
-  DevBuf<int32_t> d_stale; DevBuf<unsigned long long> d_stale_n;
-  bool lb_all_stale = true;
-  // primal rounding: the factors' primal_ members, the lazily initialised set, the message links
-  DevBuf<int32_t> d_primal;
-  DevBuf<PrimalInit> d_pinit; int64_t n_pinit = 0;
-  DevBuf<PrimalLink> d_plinks; int64_t n_plinks = 0, n_pprop = 0;   // all messages; the first n_pprop propagate labels
-  DevBuf<int32_t> d_pw_unary;     // [2 nf] the unary on each side of a pairwise factor; only with pairwise types that round themselves
-  DevBuf<double> d_pcost; DevBuf<int> d_pbad;
-  uint64_t primal_t = 0;          // primal_access_ of every factor a primal pass touches (they move together)
-  bool have_primal = false;
-  bool primal_unset_only = false; // d_primal holds only the unset labels of a model the rounding code refuses (lpmp_readout_labels)
-  DevDecode decode[2];
-  // rows layout (kernels.hip, rows_copy_kernel): dense pairwise factors live as [table | m1 | m2] rows of d_rows; the packed
-  // dual array keeps the vector factors and is the format of every call that hands duals over.  packed_stale: the rows hold
-  // newer message vectors than the packed array; rows_stale: the packed array was (or may have been) written by the caller
-  bool rows = false, packed_stale = false, rows_stale = false;
-  DevBuf<double> d_rows; DevBuf<RowRec> d_rowrecs; int64_t n_rowrecs = 0;
-  // shared pairwise tables: [two words {scale, table offset} per SHARED factor | the pool], an allocation of the engine's own
-  // that the SHARED factors' device const offsets point into (Plan::dev_coff), and the pool's tables as the shared classes' kernel sees them
-  DevBuf<double> d_shared; DevBuf<ShTableDesc> d_sh_desc;
-  int nt_flag = 0;                // SWEEP_NT when tables + duals are far larger than L2 + Infinity Cache
-  // table precision (lpmp_set_table_precision): the engine's want_tab applies to the next upload, tab_prec is the uploaded model's; with
-  // an f32 mode the dense tables live as floats in d_tab32 (every table 16-byte aligned), the DENSE factors' device const offsets point
-  // there (Plan::dev_coff, still in 8-byte units relative to d_const) and every launch carries tab_flag = SWEEP_TAB32
-  int tab_prec = LPMP_TABLES_F64, tab_flag = 0;
-  DevBuf<float> d_tab32;
-  bool model_big = false;         // tables + duals > 1 GiB: only then is an Infinity-Cache ticket order worth a chain launch
-  // new costs on the planned model (lpmp_upload_costs, lpmp_set_vectors, lpmp_zero_pairwise_duals): everything below is a function
-  // of the structure, kept so that the engine-private copies of the constants can be derived again without planning anything
-  int64_t schedules_built = 0;    // schedules, chain plans and joined-pass templates planned and uploaded for this model
-  bool const_bad = false;         // a refused lpmp_upload_costs left the constants unspecified: nothing may read them
-  bool tab_compact = false;       // f32 tables from host memory: const_buf holds only the cells of the non-DENSE factors
-  std::vector<int64_t> sh_cells;  // the SHARED / DIFF cells as launch_shared_cells receives them: {const offset, table offset}; a DIFF_SHIFT factor has two in a row, the second {const offset of its shift, length of D}
-  DevBuf<SetVecRec> d_setrecs; DevBuf<double> d_setsrc;   // records and (host sources) rows of lpmp_set_vectors, refilled in place
-  DevBuf<SetConstRec> d_setcrecs;                         // records of lpmp_set_constants (its host rows share d_setsrc)
-  DevBuf<ZeroRec> d_zero; int64_t n_zero = -1;            // pieces of the pairwise message vectors; -1: not built yet
-  // prepared read-outs (lpmp_readout_*): model_gen names the uploaded model (unique over all engines of the process; a read-out
-  // remembers the one it was made for), d_readout is where a call with a HOST destination lets the kernel write before the copy
-  uint64_t model_gen = 0;
-  DevBuf<double> d_readout;
-  std::vector<LbRun> lb_runs;
-  DevSchedule sched[2][LPMP_REPAM_COUNT];
-  bool have_sched[LPMP_REPAM_COUNT] = {false, false, false, false};
-  DevSchedule sched_pass[LPMP_REPAM_COUNT];            // fused forward+backward (ComputePass)
-  DevSchedule sched_bf[LPMP_REPAM_COUNT];              // fused backward+forward: its middle step joins two passes
-  DevSchedule sched_part[2]; bool have_part[2] = {false, false};   // compute_partition_pass / compute_overlapping_partition_pass as ONE sequence
-  bool rotation_ok[LPMP_REPAM_COUNT] = {false, false, false, false};
-  bool have_pass[LPMP_REPAM_COUNT] = {false, false, false, false};
-  bool pass_chain_tried[LPMP_REPAM_COUNT] = {};   // ensure_pass_chain_plan ran for that mode
-  std::vector<std::unique_ptr<DevSchedule>> custom;   // prepared iterator-range passes
-  DevSchedule scratch;                                 // the one-off schedule of lpmp_compute_pass_custom
-  int mode = -1;
-  // the ticket lists of a pass count are device memory (C3, 32 passes: ~350 MB): the cache of built chains is bounded in BYTES
-  // over all modes (the engine's rot_cache_limit; least recently used first), lpmp_chain_cache_bytes reports it
-  size_t rot_cache_bytes = 0;
-  std::map<int, RotChain> rot_chain[LPMP_REPAM_COUNT];
-  // (per form as well as per mode: the window and a TileSet are sized by block counts — [1]: the wide consume form, rot_wide)
-  RotOrder rot_order[LPMP_REPAM_COUNT][2];
-  // the block relations of a mode's joined passes with consume blocks (H, K, T) of PQ_WIDE_RECORDS records, beside the plan's own
-  // (lpmp_plan::rot, every block the class's four): what a peer-minima launch in the wide consume form is planned from.  Built
-  // with the plan's, while the host schedules still exist, and only where such a launch can come; not valid otherwise
-  RotationInfo rot_wide[LPMP_REPAM_COUNT];
-  // peer minima (kernels.hip, dense_pq_*_body): 32 doubles per factor, written by the W steps of a joined launch and read by its K / T
-  // steps — never across calls (every call starts with H and W), so no upload invalidates it.  Allocated with the first eligible
-  // joined launch, freed with the model; not part of the chain cache
-  DevBuf<double> d_peerq;
-  SpecBatch batch;
-
-  // drop the joined-pass launches of a mode (or of all modes) and their order
-  void release_rot_chains(int only_mode = -1) {
-    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) {
-      if (only_mode >= 0 && m != only_mode) continue;
-      for (auto& kv : rot_chain[m]) rot_cache_bytes -= std::min(rot_cache_bytes, kv.second.dev_bytes);
-      rot_chain[m].clear();
-      rot_order[m][0] = rot_order[m][1] = RotOrder();
-    }
-  }
-  // every device schedule of the engine (built-in, partition, prepared iterator-range passes, the scratch one)
-  template <class F>
-  void for_each_schedule(F&& f) {
-    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) { for (int d = 0; d < 2; ++d) f(sched[d][m]); f(sched_pass[m]); f(sched_bf[m]); }
-    for (int k = 0; k < 2; ++k) f(sched_part[k]);
-    for (auto& c : custom) if (c) f(*c);
-    f(scratch);
-  }
-  void release_primal() {
-    d_primal.reset(); d_pinit.reset(); d_plinks.reset(); d_pw_unary.reset(); d_pcost.reset(); d_pbad.reset();
-    have_primal = false; primal_unset_only = false; primal_t = 0; n_pinit = n_plinks = n_pprop = 0;
-  }
-  // the built-in schedules (everything but the caller's prepared iterator-range passes)
-  void release_schedules() {
-    for (int d = 0; d < 2; ++d) for (int m = 0; m < LPMP_REPAM_COUNT; ++m) sched[d][m].release();
-    for (int m = 0; m < LPMP_REPAM_COUNT; ++m) { have_sched[m] = false; sched_pass[m].release(); sched_bf[m].release(); have_pass[m] = false; rotation_ok[m] = false; pass_chain_tried[m] = false; }
-    for (int k = 0; k < 2; ++k) { sched_part[k].release(); have_part[k] = false; }
-    release_rot_chains();
-  }
-};
-
-}  // namespace host
-}  // namespace lpmp
-using namespace lpmp::host;
-
-struct lpmp_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipStream_t capture_stream = nullptr;   // graphs are captured here (the caller's stream may be the legacy default stream, which cannot capture) and replayed on `stream`
-  ModelState model;
-  void release_model() { model = ModelState(); deep_note_given = false; }
-  // this engine's block of device-written host words (from the pool, taken with the first upload) and the words in it
-  char* pinned = nullptr; double* h_part = nullptr; unsigned long long* h_stale_n = nullptr; int* h_pbad = nullptr;
-  bool use_lb_tracking = true;
-  int64_t last_lb_recomputed = -1;   // factor bounds the last evaluation had to recompute (-1: none evaluated yet)
-  bool primal_pass = false;       // the launches being issued belong to an ...AndPrimal pass
-  bool want_rows = false;         // rows layout for the next upload (lpmp_set_rows_layout)
-  int want_tab = LPMP_TABLES_F64; // table precision for the next upload (lpmp_set_table_precision)
-  int inner_iterations = 5;                            // --innerIteration (reference LP_MP.h:590)
-  bool use_fused = true;
-  bool use_rotation = true;
-  int rtype = 0;   // enum lpmp_reparametrization_type
-  bool use_graph = true;
-  bool use_chain = true;          // deep single-class schedules as one persistent launch (LPMP_NO_CHAIN=1: graph replay)
-  DevBuf<int32_t> d_chain_abort; bool chain_ran = false;
-  uint64_t rot_clock = 0;
-  size_t rot_cache_limit = (size_t)2 << 30;   // bound of ModelState::rot_cache_bytes (default 2 GiB, LPMP_CHAIN_CACHE_MB)
-  // ---- speculative passes (lpmp_set_speculation, include/lpmp_engine.h): the setting and the lifetime counters ----
-  struct Spec {
-    int max_depth = 0;                 // 0: off
-    int64_t batches = 0, passes_launched = 0, passes_used = 0, rollbacks = 0, alloc_failures = 0;
-  } spec;
-  bool use_blocked_passes = true;     // LPMP_NO_BLOCKED_PASSES=1: the joined passes as one launch per step
-  bool use_peer_minima = true;        // LPMP_NO_PEER_MINIMA=1: every joined launch in the old form (ModelState::d_peerq)
-  int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
-  bool pq_scatter = true;         // LPMP_PQ_SCATTER: the three-table form publishes a table's row minima with a reduce-scatter (0: eight row all-reduces)
-  int pq_hold = 3;                // LPMP_PQ_HOLD: tables such a record holds in registers, 3 or 2 (pq_lds 0: always 2, none parked)
-  bool pq_wide = true;            // LPMP_PQ_WIDE=0: the consuming records one per wave, four per ticket, on the plan's own block relations
-  // the ticket order of the peer-minima launches (rotation_chain): LPMP_PQ_TILES=0 the order every other launch takes (band order, or
-  // tiles by the old rule), =T tiles of T blocks; LPMP_PQ_SUB / _SUBLAG / _SUBGAP: sub-bands per tile, their lag, the gap behind a predecessor (unset: the engine's own)
-  int pq_tiles = -1, pq_sub = 0, pq_sublag = 0, pq_subgap = -1;
-  int pq_min_passes = 12;         // LPMP_PQ_MIN_PASSES: calls of fewer passes keep the old order (rotation_chain)
-  bool deep_note_given = false;                   // the one-line note about a schedule of many levels was printed
-  RotSettings rot_opts;      // skewed ticket order (0 bands: from the table bytes per step); DESIGN.md 6 has the sweep
-  // tiled ticket order of the joined passes (rotation_chain): LPMP_ROT_TILES=T forces tiles of T blocks per step, =0 forbids them;
-  // unset: the engine's own choice (tiles of 1024 blocks where the band order is down to depth 2 or does not fit at all)
-  int rot_tiles = 0; bool rot_tiles_set = false;
-  bool timing = false;
-  ClassTiming ct[KC_COUNT];
-  struct Pending { hipEvent_t a, b; int cls; int64_t factors, receives, bytes; bool band = false, shift = false, shift_band = false; };   // band: sweep_diff_band_kernel; shift: a launch with a DIFF_SHIFT factor; shift_band: of those, sweep_diff_shift_band_kernel
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> event_pool;
-  hipEvent_t get_event() {
-    if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
-    hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); return e;
-  }
-  void drain_timing() {
-    for (auto& p : pending) {
-      HIP_CHECK(hipEventSynchronize(p.b));
-      float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
-      ClassTiming& c = ct[p.cls];
-      c.ms += ms; c.launches++; c.band_launches += p.band ? 1 : 0; c.shift_launches += p.shift ? 1 : 0; c.shift_band_launches += p.shift_band ? 1 : 0; c.factors += p.factors; c.receives += p.receives; c.bytes += p.bytes;
-      event_pool.push_back(p.a); event_pool.push_back(p.b);
-    }
-    pending.clear();
-  }
-};
 
 namespace {
 
@@ -541,12 +193,14 @@ struct StreamPool {
   }
 };
 StreamPool& stream_pool() { static thread_local StreamPool p; return p; }
-constexpr size_t STAGE_CHUNK = (size_t)32 << 20;
 Staging& staging() { static thread_local Staging s; return s; }
 
 // LPMP_DIRECT_COPIES=1: asynchronous copies straight to / from the caller's (pageable) memory followed by a stream
 // synchronise — the round-1 original, kept as an A/B switch of the host-heap corruption hunt
 bool direct_copies() { static const bool v = [] { const char* e = std::getenv("LPMP_DIRECT_COPIES"); return e && e[0] == '1'; }(); return v; }
+}  // namespace
+
+// (declared in engine_state.hpp)
 void h2d(void* dst, const void* src, size_t bytes, hipStream_t stream) {
   if (direct_copies()) { HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream)); HIP_CHECK(hipStreamSynchronize(stream)); return; }
   for (size_t off = 0; off < bytes; off += STAGE_CHUNK) {
@@ -570,11 +224,7 @@ void d2h(void* dst, const void* src, size_t bytes, hipStream_t stream) {
   }
 }
 
-template <class T, class V>
-void fill_device(DevBuf<T>& dst, const V& src, hipStream_t stream) {
-  dst.grow(src.size());
-  h2d(dst, src.data(), src.size() * sizeof(T), stream);
-}
+namespace {
 
 // a chain's tables on the device: its launches, ticket lists and dependency lists, n_done zeroed completion flags and the ticket
 // counter.  Nothing half-built stays behind: on failure the buffers go with the local.
@@ -1159,9 +809,9 @@ void require_mode(const lpmp_engine* e) {
 
 }  // namespace
 
-static void settle(lpmp_engine* e);          // speculative passes: make the device state the caller's state (below)
+// (settle, check_chain: defined below, declared in engine_state.hpp like rows_refresh and require_consts)
 // rows layout: bring the side that is about to be read up to date (stream-ordered copies of the message vectors)
-static void rows_refresh(lpmp_engine* e) {   // packed duals -> rows, before anything computes on the rows
+void rows_refresh(lpmp_engine* e) {   // packed duals -> rows, before anything computes on the rows
   // (every hand-over first writes the rows out — rows_flush — and only then lets the caller write: both copies newer than the
   // other would mean one of the two gets lost)
   if (e->model.rows && e->model.rows_stale && e->model.packed_stale) throw StateError("rows layout: packed duals and rows both hold newer vectors");
@@ -1172,12 +822,11 @@ static void rows_flush(lpmp_engine* e) {     // rows -> packed duals, before the
 }
 // the constants are unspecified after a refused lpmp_upload_costs: whatever would read them says so — passes, bounds, the primal
 // cost.  The lpmp_boundary_* / lpmp_halo_* kernels (boundary.hip) touch duals only and are not checked.
-static void require_consts(const lpmp_engine* e) {
+void require_consts(const lpmp_engine* e) {
   if (e->model.const_bad) throw StateError("the constants are unspecified since lpmp_upload_costs refused them: upload costs the table precision accepts, or the model");
 }
 static void begin_compute(lpmp_engine* e) { require_consts(e); rows_refresh(e); if (e->model.rows) e->model.packed_stale = true; }
 
-static void check_chain(lpmp_engine* e);
 namespace {
 // The listed rows of lpmp_set_vectors / lpmp_set_constants.  Validates the list (range, kind: `vectors` says which kind the call
 // takes and wrong_kind how it refuses the other, no factor twice), lets `fill(i, f, src_row)` make record i, checks the stride
@@ -1220,8 +869,7 @@ ListedSrc listed_rows(lpmp_engine* e, const std::string& who, int64_t n, const i
 }
 }  // namespace
 
-extern "C" {
-
+// (the lpmp_* functions below have C linkage from their declarations in include/lpmp_engine.h and engine_internal.h)
 // ---- plan -----------------------------------------------------------------------------------------
 int lpmp_plan_create(const lpmp_model* m, lpmp_plan** out) {
   return guarded([&] {
@@ -2095,7 +1743,7 @@ static void spec_interrupt(lpmp_engine* e) {
   if (sp.run_len > 0) sp.learned = sp.run_len;
   sp.run_len = 0; sp.last_batch = 0;
 }
-static void settle(lpmp_engine* e) {
+void settle(lpmp_engine* e) {
   if (!e) return;
   auto& sp = e->model.batch;
   if (sp.n > 0) {
@@ -2240,14 +1888,14 @@ int lpmp_compute_pass(lpmp_engine* e, int n) {   // LP::ComputePass, LP_MP.h:869
 // nothing reads it before EvaluatePrimal: with a `left` schedule the recursion of propagate_primal_through_messages
 // stops at the pairwise factor (its other side is unset or already equal).
 // init_primal of every factor: an unset entry holds the dimension (what PrimalInit records say for the touched ones)
-static void upload_unset_primal(lpmp_engine* e) {
+void upload_unset_primal(lpmp_engine* e) {
   const Plan& p = e->model.plan->p;
   if (p.nf <= 0) return;
   std::vector<int32_t> h(2 * (size_t)p.nf);
   for (int64_t f = 0; f < p.nf; ++f) { h[2 * f] = p.f_dim0[f]; h[2 * f + 1] = p.f_kind[f] == LPMP_F_VECTOR ? 0 : p.f_dim1[f]; }
   h2d(e->model.d_primal, h.data(), h.size() * sizeof(int32_t), e->stream);
 }
-static void ensure_primal(lpmp_engine* e) {
+void ensure_primal(lpmp_engine* e) {
   if (e->model.have_primal) return;
   // (every refusal below comes before anything is released or allocated: on a model this code refuses, the array of unset labels
   // that lpmp_path_moves / lpmp_forest_moves / lpmp_readout_labels keep — primal_unset_only — survives the refused call)
@@ -2316,6 +1964,19 @@ static void ensure_primal(lpmp_engine* e) {
   }
   e->model.primal_t = 0;
   e->model.have_primal = true;
+}
+// the primal array of a call that reads or writes labels on any model: the one ensure_primal makes, or, on a model the rounding code
+// does not take (messages other than unary-pairwise), the array of unset labels in which only unaries ever get a label.  That array
+// is made once and remembered until release_primal (the model goes); a refused call leaves it (ensure_primal)
+void ensure_label_array(lpmp_engine* e) {
+  ModelState& m = e->model;
+  if (m.have_primal || m.primal_unset_only) return;
+  try { ensure_primal(e); }
+  catch (const UnsupportedError&) {
+    m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
+    upload_unset_primal(e);
+    m.primal_unset_only = true;
+  }
 }
 
 static void run_primal_sweep(lpmp_engine* e, int d, uint64_t t) {
@@ -2492,737 +2153,6 @@ int lpmp_decode_primal(lpmp_engine* e, int direction, int refine_sweeps) {
   });
 }
 
-// ---- path moves: exact relabelling of whole paths given all other labels (include/lpmp_engine.h) ----------------------
-// A prepared object like lpmp_readout: the planner's checks and path edges (plan.cpp, path_plan), then the device records with the
-// offsets of the uploaded model (rows layout, float tables and SHARED / DIFF cells are all behind Plan::doff / coff, as in
-// ensure_decode) and the back-pointer scratch, all uploaded at create.  A move plans and uploads nothing.
-struct lpmp_path_set {
-  int device = 0;
-  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
-  int64_t n_groups = 0, n_paths = 0, longest = 0, scratch_bytes = 0;
-  DevBuf<PathRec> paths; DevBuf<PathNode> nodes; DevBuf<PathLink> links;
-  DevBuf<unsigned char> back;           // back-pointers of one group at a time (launches on one stream follow each other)
-  struct Launch { int64_t first, count; int32_t wide, group; };   // per group: its paths of the wave form, then those of the workgroup form
-  std::vector<Launch> launches;
-};
-
-static PathPlan path_plan_or_refuse(const Plan& p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, const std::string& who) {
-  PathPlan pp = p.path_plan(n_groups, group_off, path_off, unaries, who);
-  if (!pp.why.empty()) throw UnsupportedError(pp.why);
-  return pp;
-}
-
-int lpmp_plan_path_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries,
-                        int64_t* n_paths, int64_t* n_path_edges, int64_t* n_off_path_links, char* why, int why_n) {
-  if (why && why_n > 0) why[0] = 0;
-  const int rc = guarded([&] {
-    if (!p) throw std::runtime_error("lpmp_plan_path_info: bad argument");
-    const PathPlan pp = path_plan_or_refuse(p->p, n_groups, group_off, path_off, unaries, "lpmp_plan_path_info");
-    if (n_paths) *n_paths = (int64_t)pp.path_off.size() - 1;
-    if (n_path_edges) *n_path_edges = pp.n_path_edges;
-    if (n_off_path_links) *n_off_path_links = pp.n_off_path_links;
-  });
-  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
-  return rc;
-}
-
-int lpmp_path_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* unaries, lpmp_path_set** out) {
-  return guarded([&] {
-    if (!e || !e->model.plan) throw StateError("lpmp_path_set_create: no model uploaded (a path set lists factors of the uploaded model)");
-    if (!out) throw std::runtime_error("lpmp_path_set_create: bad argument");
-    HIP_CHECK(hipSetDevice(e->device));
-    ModelState& m = e->model;
-    const Plan& p = m.plan->p;
-    const PathPlan pp = path_plan_or_refuse(p, n_groups, group_off, path_off, unaries, "lpmp_path_set_create");
-    auto ps = std::make_unique<lpmp_path_set>();
-    ps->device = e->device; ps->gen = m.model_gen;
-    ps->n_groups = n_groups; ps->n_paths = (int64_t)pp.path_off.size() - 1; ps->longest = pp.longest;
-    const size_t ne = pp.unaries.size();
-    std::vector<PathRec> paths; paths.reserve((size_t)ps->n_paths);
-    std::vector<PathNode> nodes(ne);
-    std::vector<PathLink> links(pp.links.size());
-    for (size_t k = 0; k < links.size(); ++k) {
-      const PathLinkPlan& l = pp.links[k];
-      links[k] = {p.doff(l.p) + (l.side ? p.f_dim0[l.p] : 0), p.coff(l.p), p.f_kind[l.p], p.f_dim1[l.p], l.side, l.other, p.f_dim0[l.other], l.on_path};
-    }
-    for (int64_t g = 0; g < n_groups; ++g) {
-      int64_t bytes = 0;                // of this group's back-pointers: d0 entries per node behind the first of its path
-      std::vector<int64_t> form[2];     // the group's paths by form
-      for (int64_t j = pp.group_off[(size_t)g]; j < pp.group_off[(size_t)g + 1]; ++j) {
-        int32_t widest = 0;
-        for (int64_t en = pp.path_off[(size_t)j]; en < pp.path_off[(size_t)j + 1]; ++en) {
-          const int32_t u = pp.unaries[(size_t)en], d = p.f_dim0[u], pw = pp.edge[(size_t)en];
-          if (d < 1) throw std::runtime_error("lpmp_path_set_create: factor " + std::to_string(u) + " (entry " + std::to_string(en) + ") has no label");
-          widest = std::max(widest, d);
-          PathNode nd{p.doff(u), 0, 0, d, u, (int32_t)pp.link_off[(size_t)en], (int32_t)(pp.link_off[(size_t)en + 1] - pp.link_off[(size_t)en]), -1, 0, 0, 0};
-          if (pw >= 0) {
-            const int32_t dprev = p.f_dim0[pp.unaries[(size_t)en - 1]];
-            nd.edge_const = p.coff(pw); nd.edge_kind = p.f_kind[pw]; nd.edge_d1 = p.f_dim1[pw]; nd.edge_prev_side = pp.edge_prev_side[(size_t)en];
-            nd.back_wide = dprev > 256 ? 1 : 0;
-            bytes = (bytes + nd.back_wide) & ~(int64_t)nd.back_wide;      // (two-byte entries start at an even byte)
-            nd.back_off = bytes;
-            bytes += (int64_t)d * (nd.back_wide ? 2 : 1);
-          }
-          nodes[(size_t)en] = nd;
-        }
-        form[widest > PATH_WAVE_MAX ? 1 : 0].push_back(j);
-      }
-      ps->scratch_bytes = std::max(ps->scratch_bytes, bytes);
-      for (int w = 0; w < 2; ++w) {
-        if (form[w].empty()) continue;
-        ps->launches.push_back({(int64_t)paths.size(), (int64_t)form[w].size(), w, (int32_t)g});
-        for (int64_t j : form[w]) paths.push_back({pp.path_off[(size_t)j], (int32_t)(pp.path_off[(size_t)j + 1] - pp.path_off[(size_t)j]), 0});
-      }
-    }
-    if (!paths.empty()) { ps->paths.alloc(paths.size()); h2d(ps->paths, paths.data(), paths.size() * sizeof(PathRec), e->stream); }
-    if (!nodes.empty()) { ps->nodes.alloc(nodes.size()); h2d(ps->nodes, nodes.data(), nodes.size() * sizeof(PathNode), e->stream); }
-    if (!links.empty()) { ps->links.alloc(links.size()); h2d(ps->links, links.data(), links.size() * sizeof(PathLink), e->stream); }
-    if (ps->scratch_bytes > 0) ps->back.alloc((size_t)ps->scratch_bytes);
-    ++m.schedules_built;   // the record tables: structure, like a schedule, counted once
-    *out = ps.release();
-  });
-}
-void lpmp_path_set_destroy(lpmp_path_set* ps) {
-  if (!ps) return;
-  (void)hipSetDevice(ps->device);
-  delete ps;
-}
-int64_t lpmp_path_set_n_groups(const lpmp_path_set* ps) { return ps ? ps->n_groups : 0; }
-int64_t lpmp_path_set_n_paths(const lpmp_path_set* ps) { return ps ? ps->n_paths : 0; }
-int64_t lpmp_path_set_longest(const lpmp_path_set* ps) { return ps ? ps->longest : 0; }
-int64_t lpmp_path_set_scratch_bytes(const lpmp_path_set* ps) { return ps ? ps->scratch_bytes : 0; }
-
-int lpmp_path_moves(lpmp_engine* e, lpmp_path_set* ps, int rounds) {
-  return guarded([&] {
-    const std::string who = "lpmp_path_moves";
-    if (!e || !ps) throw std::runtime_error(who + ": null argument");
-    if (!e->model.plan || ps->gen != e->model.model_gen) throw StateError(who + ": the path set was made for another model (lpmp_upload_model since lpmp_path_set_create)");
-    if (rounds < 0) throw std::runtime_error(who + ": negative number of rounds");
-    HIP_CHECK(hipSetDevice(e->device));
-    settle(e);                 // passes that ran ahead: the duals read are those of the pass the caller is at
-    require_consts(e);
-    ModelState& m = e->model;
-    if (!m.have_primal && !m.primal_unset_only) {
-      try { ensure_primal(e); }
-      catch (const UnsupportedError&) {
-        // a model the rounding code does not take (a message of another kind somewhere off the paths): the array of unset labels
-        // of lpmp_readout_labels; the listed unaries get labels, no pairwise slot is written
-        m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
-        upload_unset_primal(e);
-        m.primal_unset_only = true;
-      }
-    }
-    if (rounds == 0 || ps->launches.empty()) return;
-    rows_refresh(e);           // (reads the rows; writes no dual)
-    for (int r = 0; r < rounds; ++r)
-      for (const auto& l : ps->launches)
-        launch_path_moves(ps->paths, ps->nodes, ps->links, m.d_dual, m.d_const, m.d_primal, ps->back, l.first, l.count, l.wide, m.tab_flag, e->stream);
-    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
-    HIP_CHECK(hipGetLastError());
-  });
-}
-
-// ---- forest moves: exact relabelling of induced forests given all other labels (include/lpmp_engine.h) -----------------
-// The path set's twin for trees: the planner's checks, tree edges, children, heights and depths (plan.cpp, forest_plan), then the
-// device records, the launch lists (per group: the nodes by height and form for the up sweep, by depth for the down sweep) and the
-// scratch of rows and back-pointers of the largest group, all uploaded at create.  A move plans and uploads nothing.
-struct lpmp_forest_set {
-  int device = 0;
-  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
-  int64_t n_groups = 0, n_trees = 0, max_height = 0, scratch_bytes = 0;
-  DevBuf<ForestNode> nodes; DevBuf<PathLink> links; DevBuf<int64_t> child_g; DevBuf<int32_t> list;
-  DevBuf<double> rows; DevBuf<unsigned char> back;      // of one group at a time (launches on one stream follow each other)
-  struct Launch { int64_t first, count; int32_t wide; };            // wide < 0: a level of the down sweep
-  std::vector<Launch> launches;
-};
-
-static ForestPlan forest_plan_or_refuse(const Plan& p, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, const std::string& who) {
-  ForestPlan fp = p.forest_plan(n_groups, group_off, unaries, parent, who);
-  if (!fp.why.empty()) throw UnsupportedError(fp.why);
-  return fp;
-}
-
-int lpmp_plan_forest_info(lpmp_plan* p, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent,
-                          int64_t* n_trees, int64_t* n_tree_edges, int64_t* n_off_tree_links, int64_t* max_height, char* why, int why_n) {
-  if (why && why_n > 0) why[0] = 0;
-  const int rc = guarded([&] {
-    if (!p) throw std::runtime_error("lpmp_plan_forest_info: bad argument");
-    const ForestPlan fp = forest_plan_or_refuse(p->p, n_groups, group_off, unaries, parent, "lpmp_plan_forest_info");
-    if (n_trees) *n_trees = fp.n_trees;
-    if (n_tree_edges) *n_tree_edges = fp.n_tree_edges;
-    if (n_off_tree_links) *n_off_tree_links = fp.n_off_tree_links;
-    if (max_height) *max_height = fp.max_height;
-  });
-  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
-  return rc;
-}
-
-int lpmp_plan_suggest_forests(lpmp_plan* p, int64_t max_groups, int64_t* n_groups, int64_t* n_entries, int64_t* group_off, int32_t* unaries,
-                              int32_t* parent, int64_t* n_left_out) {
-  return guarded([&] {
-    if (!p || max_groups < 0) throw std::runtime_error("lpmp_plan_suggest_forests: bad argument");
-    const ForestCover fc = suggest_forests(p->p, max_groups);
-    if (n_groups) *n_groups = (int64_t)fc.group_off.size() - 1;
-    if (n_entries) *n_entries = (int64_t)fc.unaries.size();
-    if (n_left_out) *n_left_out = fc.n_left_out;
-    if (group_off) std::copy(fc.group_off.begin(), fc.group_off.end(), group_off);
-    if (unaries) std::copy(fc.unaries.begin(), fc.unaries.end(), unaries);
-    if (parent) std::copy(fc.parent.begin(), fc.parent.end(), parent);
-  });
-}
-
-int lpmp_forest_set_create(lpmp_engine* e, int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, lpmp_forest_set** out) {
-  return guarded([&] {
-    if (!e || !e->model.plan) throw StateError("lpmp_forest_set_create: no model uploaded (a forest set lists factors of the uploaded model)");
-    if (!out) throw std::runtime_error("lpmp_forest_set_create: bad argument");
-    HIP_CHECK(hipSetDevice(e->device));
-    ModelState& m = e->model;
-    const Plan& p = m.plan->p;
-    const ForestPlan fp = forest_plan_or_refuse(p, n_groups, group_off, unaries, parent, "lpmp_forest_set_create");
-    auto fs = std::make_unique<lpmp_forest_set>();
-    fs->device = e->device; fs->gen = m.model_gen;
-    fs->n_groups = n_groups; fs->n_trees = fp.n_trees; fs->max_height = fp.max_height;
-    const size_t ne = fp.unaries.size();
-    std::vector<ForestNode> nodes(ne);
-    std::vector<PathLink> links(fp.links.size());
-    std::vector<int64_t> child_g(fp.children.size());
-    std::vector<int32_t> list; list.reserve(2 * ne);
-    for (size_t k = 0; k < links.size(); ++k) {
-      const ForestLinkPlan& l = fp.links[k];
-      links[k] = {p.doff(l.p) + (l.side ? p.f_dim0[l.p] : 0), p.coff(l.p), p.f_kind[l.p], p.f_dim1[l.p], l.side, l.other, p.f_dim0[l.other], l.tree ? 1 : 0};
-    }
-    int64_t max_rows = 0, max_back = 0;
-    std::vector<std::vector<int32_t>> up[2], down;     // the group's entries by height and form, and by depth
-    for (int64_t g = 0; g < n_groups; ++g) {
-      const int64_t gb = fp.group_off[(size_t)g], ge = fp.group_off[(size_t)g + 1];
-      if (gb == ge) continue;
-      const size_t levels = (size_t)fp.group_height[(size_t)g] + 1;
-      for (int w = 0; w < 2; ++w) up[w].assign(levels, {});
-      down.assign(levels, {});
-      int64_t n_rows = 0, bytes = 0;    // of this group's rows (doubles) and back-pointers
-      for (int64_t en = gb; en < ge; ++en) {
-        const int32_t u = fp.unaries[(size_t)en], d = p.f_dim0[u], q = fp.parent_entry[(size_t)en], pw = fp.edge[(size_t)en];
-        if (d < 1) throw std::runtime_error("lpmp_forest_set_create: factor " + std::to_string(u) + " (entry " + std::to_string(en) + ") has no label");
-        ForestNode nd{p.doff(u), 0, 0, 0, d, u, (int32_t)fp.link_off[(size_t)en], (int32_t)(fp.link_off[(size_t)en + 1] - fp.link_off[(size_t)en]), -1, 0, 0, 0, 0, -1,
-                      (int32_t)fp.child_off[(size_t)en], (int32_t)(fp.child_off[(size_t)en + 1] - fp.child_off[(size_t)en])};
-        int32_t widest = d;
-        if (q >= 0) {
-          const int32_t dq = p.f_dim0[fp.unaries[(size_t)q]];
-          widest = std::max(widest, dq);
-          nd.edge_const = p.coff(pw); nd.edge_kind = p.f_kind[pw]; nd.edge_d1 = p.f_dim1[pw]; nd.edge_side = fp.edge_side[(size_t)en];
-          nd.dq = dq; nd.parent = fp.unaries[(size_t)q];
-          nd.g_off = n_rows; n_rows += dq;
-          nd.back_wide = d > 256 ? 1 : 0;
-          bytes = (bytes + nd.back_wide) & ~(int64_t)nd.back_wide;      // (two-byte entries start at an even byte)
-          nd.back_off = bytes;
-          bytes += (int64_t)dq * (nd.back_wide ? 2 : 1);
-          down[(size_t)fp.depth[(size_t)en]].push_back((int32_t)en);
-        }
-        nodes[(size_t)en] = nd;
-        up[widest > PATH_WAVE_MAX ? 1 : 0][(size_t)fp.height[(size_t)en]].push_back((int32_t)en);
-      }
-      max_rows = std::max(max_rows, n_rows); max_back = std::max(max_back, bytes);
-      for (size_t h = 0; h < levels; ++h)
-        for (int w = 0; w < 2; ++w) {
-          if (up[w][h].empty()) continue;
-          fs->launches.push_back({(int64_t)list.size(), (int64_t)up[w][h].size(), w});
-          list.insert(list.end(), up[w][h].begin(), up[w][h].end());
-        }
-      for (size_t dp = 1; dp < levels; ++dp) {
-        if (down[dp].empty()) continue;
-        fs->launches.push_back({(int64_t)list.size(), (int64_t)down[dp].size(), -1});
-        list.insert(list.end(), down[dp].begin(), down[dp].end());
-      }
-    }
-    for (size_t k = 0; k < child_g.size(); ++k) child_g[k] = nodes[(size_t)fp.children[k]].g_off;
-    fs->scratch_bytes = 8 * max_rows + max_back;
-    if (!nodes.empty()) { fs->nodes.alloc(nodes.size()); h2d(fs->nodes, nodes.data(), nodes.size() * sizeof(ForestNode), e->stream); }
-    if (!links.empty()) { fs->links.alloc(links.size()); h2d(fs->links, links.data(), links.size() * sizeof(PathLink), e->stream); }
-    if (!child_g.empty()) { fs->child_g.alloc(child_g.size()); h2d(fs->child_g, child_g.data(), child_g.size() * sizeof(int64_t), e->stream); }
-    if (!list.empty()) { fs->list.alloc(list.size()); h2d(fs->list, list.data(), list.size() * sizeof(int32_t), e->stream); }
-    if (max_rows > 0) fs->rows.alloc((size_t)max_rows);
-    if (max_back > 0) fs->back.alloc((size_t)max_back);
-    ++m.schedules_built;   // the record tables: structure, like a schedule, counted once
-    *out = fs.release();
-  });
-}
-void lpmp_forest_set_destroy(lpmp_forest_set* fs) {
-  if (!fs) return;
-  (void)hipSetDevice(fs->device);
-  delete fs;
-}
-int64_t lpmp_forest_set_n_groups(const lpmp_forest_set* fs) { return fs ? fs->n_groups : 0; }
-int64_t lpmp_forest_set_n_trees(const lpmp_forest_set* fs) { return fs ? fs->n_trees : 0; }
-int64_t lpmp_forest_set_max_height(const lpmp_forest_set* fs) { return fs ? fs->max_height : 0; }
-int64_t lpmp_forest_set_scratch_bytes(const lpmp_forest_set* fs) { return fs ? fs->scratch_bytes : 0; }
-
-int lpmp_forest_moves(lpmp_engine* e, lpmp_forest_set* fs, int rounds) {
-  return guarded([&] {
-    const std::string who = "lpmp_forest_moves";
-    if (!e || !fs) throw std::runtime_error(who + ": null argument");
-    if (!e->model.plan || fs->gen != e->model.model_gen) throw StateError(who + ": the forest set was made for another model (lpmp_upload_model since lpmp_forest_set_create)");
-    if (rounds < 0) throw std::runtime_error(who + ": negative number of rounds");
-    HIP_CHECK(hipSetDevice(e->device));
-    settle(e);                 // passes that ran ahead: the duals read are those of the pass the caller is at
-    require_consts(e);
-    ModelState& m = e->model;
-    if (!m.have_primal && !m.primal_unset_only) {
-      try { ensure_primal(e); }
-      catch (const UnsupportedError&) {
-        // as lpmp_path_moves: a model the rounding code does not take gets the array of unset labels; no pairwise slot is written
-        m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
-        upload_unset_primal(e);
-        m.primal_unset_only = true;
-      }
-    }
-    if (rounds == 0 || fs->launches.empty()) return;
-    rows_refresh(e);           // (reads the rows; writes no dual)
-    for (int r = 0; r < rounds; ++r)
-      for (const auto& l : fs->launches) {
-        if (l.wide < 0) launch_forest_down(fs->list, fs->nodes, m.d_primal, fs->back, l.first, l.count, e->stream);
-        else launch_forest_up(fs->list, fs->nodes, fs->child_g, fs->links, m.d_dual, m.d_const, m.d_primal, fs->rows, fs->back, l.first, l.count, l.wide, m.tab_flag, e->stream);
-      }
-    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
-    HIP_CHECK(hipGetLastError());
-  });
-}
-
-// ---- prepared read-outs: labels, unaries and beliefs of listed VECTOR factors into the caller's array (include/lpmp_engine.h) -------
-// The output twin of lpmp_set_vectors, prepared like a schedule: the record list is uploaded at create, a call uploads nothing.
-struct lpmp_readout {
-  int device = 0;
-  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
-  int64_t n = 0;
-  int32_t max_labels = 0;
-  std::vector<int32_t> factors, d0;     // the list, and every row's label count (a host destination is filled row by row)
-  DevBuf<ReadoutRec> recs;              // in the caller's order: row i = record i
-  int32_t unsupported = -1;             // lowest listed factor with a message the beliefs do not take (-1: none)
-  std::string why;
-  int32_t duplicate = -1;               // lowest factor listed twice (-1: none): lpmp_readout_set_labels refuses the read-out
-  // beliefs: the records again, sorted by label-count class, with their links in message-list order; built on the first call
-  struct Launch { int64_t first, count; int32_t width; };
-  bool have_links = false;
-  DevBuf<ReadoutRec> brecs; DevBuf<DecodeLink> links;
-  std::vector<Launch> launches;
-};
-
-static int readout_class(int32_t d0) { return d0 <= 4 ? 0 : d0 <= 8 ? 1 : d0 <= 16 ? 2 : d0 <= READOUT_GROUP_MAX ? 3 : d0 <= 64 ? 4 : 5; }
-static const int32_t READOUT_CLASS_WIDTH[6] = {4, 8, 16, READOUT_GROUP_MAX, 64, GEN_MAXD};
-
-// the link tables of the beliefs: a function of the structure, like a schedule, and counted as one
-static void ensure_readout_links(lpmp_engine* e, lpmp_readout* r) {
-  if (r->have_links) return;
-  r->brecs.reset(); r->links.reset(); r->launches.clear();
-  const Plan& p = e->model.plan->p;
-  int64_t start[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int64_t i = 0; i < r->n; ++i) ++start[readout_class(r->d0[(size_t)i]) + 1];
-  for (int c = 0; c < 6; ++c) start[c + 1] += start[c];
-  std::vector<ReadoutRec> recs((size_t)r->n);
-  std::vector<DecodeLink> links;
-  std::vector<int64_t> begin_of((size_t)p.nf, -1);   // a factor listed twice shares its links
-  int64_t cur[6];
-  for (int c = 0; c < 6; ++c) cur[c] = start[c];
-  for (int64_t i = 0; i < r->n; ++i) {
-    const int32_t u = r->factors[(size_t)i];
-    const int64_t a = p.fm_off[(size_t)u], b = p.fm_off[(size_t)u + 1];
-    if (begin_of[(size_t)u] < 0) {
-      begin_of[(size_t)u] = (int64_t)links.size();
-      for (int64_t k = a; k < b; ++k) {   // the order of the message list: the order in which a sweep receives
-        const int32_t msg = p.fm[(size_t)k].msg, pw = p.m_right[(size_t)msg];
-        links.push_back({p.doff(pw), p.coff(pw), p.f_kind[pw], p.f_dim0[pw], p.f_dim1[pw], p.mtypes[(size_t)p.m_type[(size_t)msg]].param, 0, 0});
-      }
-      if (links.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error("lpmp_readout_beliefs: more than 2^31 links");
-    }
-    recs[(size_t)cur[readout_class(r->d0[(size_t)i])]++] = {p.f_doff[(size_t)u], i, r->d0[(size_t)i], u, (int32_t)begin_of[(size_t)u], (int32_t)(b - a)};
-  }
-  for (int c = 0; c < 6; ++c) if (start[c + 1] > start[c]) r->launches.push_back({start[c], start[c + 1] - start[c], READOUT_CLASS_WIDTH[c]});
-  if (r->n) { r->brecs.alloc((size_t)r->n); h2d(r->brecs, recs.data(), recs.size() * sizeof(ReadoutRec), e->stream); }
-  if (!links.empty()) { r->links.alloc(links.size()); h2d(r->links, links.data(), links.size() * sizeof(DecodeLink), e->stream); }
-  r->have_links = true;
-  ++e->model.schedules_built;
-}
-
-int lpmp_readout_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_readout** out) {
-  return guarded([&] {
-    if (!e || !e->model.plan) throw StateError("lpmp_readout_create: no model uploaded (a read-out lists factors of the uploaded model)");
-    if (!out || (factors && n < 0)) throw std::runtime_error("lpmp_readout_create: bad argument");
-    HIP_CHECK(hipSetDevice(e->device));
-    const Plan& p = e->model.plan->p;
-    auto r = std::make_unique<lpmp_readout>();
-    r->device = e->device; r->gen = e->model.model_gen;
-    if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) r->factors.push_back((int32_t)f); }
-    else {
-      r->factors.reserve((size_t)n);
-      for (int64_t i = 0; i < n; ++i) {
-        const int32_t f = factors[i];
-        if (f < 0 || f >= p.nf) throw std::runtime_error("lpmp_readout_create: factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
-        if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error("lpmp_readout_create: factor " + std::to_string(f) + " is not a VECTOR factor");
-        r->factors.push_back(f);
-      }
-    }
-    r->n = (int64_t)r->factors.size();
-    if (factors) {   // (reads are idempotent; a write of two rows into one slot is not: decided here, refused in lpmp_readout_set_labels)
-      std::vector<uint8_t> seen((size_t)p.nf, 0);
-      for (const int32_t f : r->factors) {
-        if (seen[(size_t)f] && (r->duplicate < 0 || f < r->duplicate)) r->duplicate = f;
-        seen[(size_t)f] = 1;
-      }
-    }
-    std::vector<ReadoutRec> recs((size_t)r->n);
-    r->d0.resize((size_t)r->n);
-    for (int64_t i = 0; i < r->n; ++i) {
-      const int32_t f = r->factors[(size_t)i], len = p.f_dim0[f];
-      r->d0[(size_t)i] = len;
-      r->max_labels = std::max(r->max_labels, len);
-      recs[(size_t)i] = {p.f_doff[f], i, len, f, 0, 0};
-      // beliefs: every message of the factor is a unary-pairwise one with the factor on its left (the unary) and a pairwise factor on its right
-      for (int64_t k = p.fm_off[(size_t)f]; k < p.fm_off[(size_t)f + 1]; ++k) {
-        const MsgEntry& me = p.fm[(size_t)k];
-        const bool ok = p.mtypes[(size_t)p.m_type[(size_t)me.msg]].kind == LPMP_M_UNARY_PAIRWISE && me.role == 0 && p.f_kind[p.m_right[(size_t)me.msg]] != LPMP_F_VECTOR;
-        if (!ok && (r->unsupported < 0 || f < r->unsupported)) r->unsupported = f;
-      }
-    }
-    if (r->unsupported >= 0)
-      r->why = "lpmp_readout_beliefs: factor " + std::to_string(r->unsupported) + " has a message that is not a unary-pairwise message with the factor as its unary (DESIGN.md 8)";
-    if (r->n) { r->recs.alloc((size_t)r->n); h2d(r->recs, recs.data(), recs.size() * sizeof(ReadoutRec), e->stream); }
-    *out = r.release();
-  });
-}
-void lpmp_readout_destroy(lpmp_readout* r) {
-  if (!r) return;
-  (void)hipSetDevice(r->device);
-  delete r;
-}
-int64_t lpmp_readout_n(const lpmp_readout* r) { return r ? r->n : 0; }
-int32_t lpmp_readout_max_labels(const lpmp_readout* r) { return r ? r->max_labels : 0; }
-
-// common entry of the three calls: the read-out belongs to the uploaded model, the arguments are usable, passes that ran ahead
-// are settled (the state read is that of the pass the caller is at)
-static void readout_enter(lpmp_engine* e, lpmp_readout* r, const void* dst, int dst_mem, const int64_t* dst_stride, const char* who) {
-  if (!e || !r) throw std::runtime_error(std::string(who) + ": null argument");
-  if (!e->model.plan || r->gen != e->model.model_gen) throw StateError(std::string(who) + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
-  if (dst_mem != LPMP_MEM_HOST && dst_mem != LPMP_MEM_DEVICE) throw std::runtime_error(std::string(who) + ": dst_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
-  if (r->n > 0 && !dst) throw std::runtime_error(std::string(who) + ": null destination");
-  if (dst_stride && *dst_stride < r->max_labels)
-    throw std::runtime_error(std::string(who) + ": dst_stride " + std::to_string(*dst_stride) + " is smaller than the " + std::to_string(r->max_labels) + " entries of the longest listed vector");
-  HIP_CHECK(hipSetDevice(e->device));
-  settle(e);
-  // a DEVICE destination never waits for the stream, as lpmp_decode_primal does not: an aborted chain run is reported by the next
-  // call that synchronises anyway.  A HOST destination ends in a synchronising copy and reports it here
-  if (dst_mem == LPMP_MEM_HOST) check_chain(e);
-}
-// rows of doubles: straight into a device destination, or into the engine's buffer (rows max_labels apart) and from there, row by
-// row, into the entries of the host destination that belong to a factor
-static void readout_rows(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem, const std::function<void(double*, int64_t)>& launch) {
-  if (dst_mem == LPMP_MEM_DEVICE) { launch(dst, dst_stride); HIP_CHECK(hipGetLastError()); return; }
-  const size_t total = (size_t)r->n * (size_t)r->max_labels;
-  if (total == 0) return;
-  e->model.d_readout.grow(total);
-  launch(e->model.d_readout.get(), (int64_t)r->max_labels);
-  HIP_CHECK(hipGetLastError());
-  // (whole rows, one staging chunk at a time: no second buffer of the size of the read-out on the host)
-  const int64_t L = r->max_labels, per = std::max<int64_t>(1, (int64_t)(STAGE_CHUNK / sizeof(double)) / L);
-  std::vector<double> rows((size_t)(std::min(per, r->n) * L));
-  for (int64_t first = 0; first < r->n; first += per) {
-    const int64_t cnt = std::min(per, r->n - first);
-    d2h(rows.data(), e->model.d_readout.get() + first * L, (size_t)(cnt * L) * sizeof(double), e->stream);
-    for (int64_t i = 0; i < cnt; ++i)
-      std::copy(rows.begin() + i * L, rows.begin() + i * L + r->d0[(size_t)(first + i)], dst + (first + i) * dst_stride);
-  }
-}
-
-// the primal array of a call that reads or writes labels on any model: the one ensure_primal makes, or, on a model the rounding code
-// does not take (messages other than unary-pairwise), the array of unset labels in which only unaries ever get a label.  That array
-// is made once and remembered until release_primal (the model goes); a refused call leaves it (ensure_primal)
-static void ensure_label_array(lpmp_engine* e) {
-  ModelState& m = e->model;
-  if (m.have_primal || m.primal_unset_only) return;
-  try { ensure_primal(e); }
-  catch (const UnsupportedError&) {
-    m.d_primal.alloc(std::max<size_t>(1, 2 * (size_t)m.plan->p.nf));
-    upload_unset_primal(e);
-    m.primal_unset_only = true;
-  }
-}
-int lpmp_readout_labels(lpmp_engine* e, lpmp_readout* r, int32_t* dst, int dst_mem) {
-  return guarded([&] {
-    readout_enter(e, r, dst, dst_mem, nullptr, "lpmp_readout_labels");
-    if (r->n == 0) return;
-    ensure_label_array(e);
-    if (dst_mem == LPMP_MEM_DEVICE) { launch_readout_labels(r->recs, r->n, e->model.d_primal, dst, e->stream); HIP_CHECK(hipGetLastError()); return; }
-    e->model.d_readout.grow(((size_t)r->n + 1) / 2);
-    int32_t* stage = reinterpret_cast<int32_t*>(e->model.d_readout.get());
-    launch_readout_labels(r->recs, r->n, e->model.d_primal, stage, e->stream);
-    HIP_CHECK(hipGetLastError());
-    d2h(dst, stage, (size_t)r->n * sizeof(int32_t), e->stream);
-  });
-}
-// the input twin of lpmp_readout_labels (include/lpmp_engine.h)
-int lpmp_readout_set_labels(lpmp_engine* e, lpmp_readout* r, const int32_t* src, int src_mem) {
-  return guarded([&] {
-    const std::string who = "lpmp_readout_set_labels";
-    if (!e || !r) throw std::runtime_error(who + ": null argument");
-    if (!e->model.plan || r->gen != e->model.model_gen) throw StateError(who + ": the read-out was made for another model (lpmp_upload_model since lpmp_readout_create)");
-    if (src_mem != LPMP_MEM_HOST && src_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": src_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
-    if (r->n > 0 && !src) throw std::runtime_error(who + ": null source");
-    if (r->duplicate >= 0) throw std::runtime_error(who + ": factor " + std::to_string(r->duplicate) + " is listed twice in the read-out (two rows would write one label)");
-    const bool host = src_mem == LPMP_MEM_HOST;
-    if (host)
-      for (int64_t i = 0; i < r->n; ++i)
-        if (src[i] < 0 || src[i] > r->d0[(size_t)i])
-          throw std::runtime_error(who + ": label " + std::to_string(src[i]) + " (entry " + std::to_string(i) + ", factor " + std::to_string(r->factors[(size_t)i]) + ") is outside [0, " +
-                                   std::to_string(r->d0[(size_t)i]) + "] (the dimension means unset); nothing was written");
-    HIP_CHECK(hipSetDevice(e->device));
-    settle(e);
-    // (a device source never waits for the stream, as a read-out into device memory does not; a host source ends in a synchronising copy)
-    if (host) check_chain(e);
-    if (r->n == 0) return;
-    ensure_label_array(e);
-    ModelState& m = e->model;
-    const int32_t* d_src = src;
-    if (host) {
-      m.d_readout.grow(((size_t)r->n + 1) / 2);
-      int32_t* stage = reinterpret_cast<int32_t*>(m.d_readout.get());
-      h2d(stage, src, (size_t)r->n * sizeof(int32_t), e->stream);
-      d_src = stage;
-    }
-    launch_set_labels(r->recs, r->n, d_src, m.d_primal, e->stream);
-    if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);   // every message's pairwise slot := its unary's label
-    HIP_CHECK(hipGetLastError());
-  });
-}
-int lpmp_readout_vectors(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem) {
-  return guarded([&] {
-    readout_enter(e, r, dst, dst_mem, &dst_stride, "lpmp_readout_vectors");
-    if (r->n == 0) return;
-    // (vector factors live in the packed array under every layout: nothing of the rows is read)
-    readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
-      launch_readout_vectors(r->recs, r->n, r->max_labels, e->model.d_dual, d, stride, e->stream);
-    });
-  });
-}
-int lpmp_readout_beliefs(lpmp_engine* e, lpmp_readout* r, double* dst, int64_t dst_stride, int dst_mem) {
-  return guarded([&] {
-    readout_enter(e, r, dst, dst_mem, &dst_stride, "lpmp_readout_beliefs");
-    if (r->unsupported >= 0) throw UnsupportedError(r->why);
-    if (r->n == 0) return;
-    require_consts(e);
-    ensure_readout_links(e, r);
-    rows_refresh(e);           // (reads the rows; writes no dual)
-    readout_rows(e, r, dst, dst_stride, dst_mem, [&](double* d, int64_t stride) {
-      for (const auto& l : r->launches)
-        launch_readout_beliefs(r->brecs, r->links, e->model.d_dual, e->model.d_const, d, stride, l.first, l.count, l.width, e->model.tab_flag, e->stream);
-    });
-  });
-}
-
-// ---- moving label windows: duals and shifts carried along on the device (include/lpmp_engine.h) ---------------------------------
-// What a window set is made of, from the structure alone (lpmp_plan_window_info asks a stand-alone plan): the listed unaries, the
-// links of each in message-list order, and the DIFF_SHIFT factors next to them with the row of the unary on either side.
-namespace {
-struct WindowLink { int32_t p, side; };
-struct WindowPair { int32_t p, left_row, right_row; };
-struct WindowPlan {
-  std::vector<int32_t> factors;
-  std::vector<int64_t> link_off;        // CSR over `factors`
-  std::vector<WindowLink> links;
-  std::vector<WindowPair> pairs;        // in the order the listed unaries meet them
-  int32_t max_labels = 0;
-};
-// LPMP_ERR_INVALID (std::runtime_error) naming the entry: out of range, not a VECTOR factor, listed twice.  LPMP_ERR_UNSUPPORTED
-// naming the lowest listed factor the move does not take.  factors == nullptr: every VECTOR factor
-void window_plan(const Plan& p, int64_t n, const int32_t* factors, const std::string& who, WindowPlan& w) {
-  std::vector<int32_t> row_of((size_t)p.nf, -1);
-  if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) { row_of[(size_t)f] = (int32_t)w.factors.size(); w.factors.push_back((int32_t)f); } }
-  else {
-    if (n > (int64_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error(who + ": more than 2^31 factors listed");
-    w.factors.reserve((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t f = factors[i];
-      if (f < 0 || f >= p.nf) throw std::runtime_error(who + ": factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
-      if (p.f_kind[f] != LPMP_F_VECTOR) throw std::runtime_error(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is not a VECTOR factor");
-      if (row_of[(size_t)f] >= 0) throw std::runtime_error(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is listed twice");
-      row_of[(size_t)f] = (int32_t)i;
-      w.factors.push_back(f);
-    }
-  }
-  int32_t bad = -1; std::string why;
-  auto refuse = [&](int32_t u, const std::string& what) { if (bad < 0 || u < bad) { bad = u; why = what; } };
-  // the unary on each side of a DIFF_SHIFT factor, from ALL its unary-pairwise messages (-1: none, -2: two different ones)
-  auto side_unaries = [&](int32_t pw, int32_t out[2]) {
-    out[0] = out[1] = -1;
-    for (int64_t k = p.fm_off[(size_t)pw]; k < p.fm_off[(size_t)pw + 1]; ++k) {
-      const MsgEntry& me = p.fm[(size_t)k];
-      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
-      if (me.role != 1 || mt.kind != LPMP_M_UNARY_PAIRWISE || (mt.param != 0 && mt.param != 1)) continue;
-      const int32_t u = p.m_left[(size_t)me.msg];
-      int32_t& slot = out[mt.param];
-      slot = slot == -1 || slot == u ? u : -2;
-    }
-  };
-  std::vector<int32_t> pair_of((size_t)p.nf, -1);
-  w.link_off.assign(1, 0);
-  for (size_t i = 0; i < w.factors.size(); ++i) {
-    const int32_t u = w.factors[i], d = p.f_dim0[u];
-    w.max_labels = std::max(w.max_labels, d);
-    if (d > MOVE_MAX_LABELS) refuse(u, "has " + std::to_string(d) + " labels (a wave holds a vector of at most " + std::to_string(MOVE_MAX_LABELS) + ")");
-    const size_t first = w.links.size();
-    for (int64_t k = p.fm_off[(size_t)u]; k < p.fm_off[(size_t)u + 1]; ++k) {
-      const MsgEntry& me = p.fm[(size_t)k];
-      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
-      const int32_t pw = me.role == 0 ? p.m_right[(size_t)me.msg] : -1;
-      if (mt.kind != LPMP_M_UNARY_PAIRWISE || pw < 0 || p.f_kind[pw] != LPMP_F_PAIRWISE_DIFF_SHIFT || (mt.param != 0 && mt.param != 1)) {
-        refuse(u, "has a message that is not a unary-pairwise message with the factor as its unary and a DIFF_SHIFT factor on the right");
-        continue;
-      }
-      const int32_t side = mt.param;
-      if ((side ? p.f_dim1[pw] : p.f_dim0[pw]) != d) { refuse(u, "and side " + std::to_string(side) + " of factor " + std::to_string(pw) + " differ in their label counts"); continue; }
-      bool twice = false;
-      for (size_t q = first; q < w.links.size(); ++q) twice = twice || (w.links[q].p == pw && w.links[q].side == side);
-      if (twice) { refuse(u, "has two messages into one vector of factor " + std::to_string(pw)); continue; }
-      w.links.push_back({pw, side});
-      if (pair_of[(size_t)pw] < 0) {
-        int32_t su[2];
-        side_unaries(pw, su);
-        if (su[0] == -2 || su[1] == -2) { refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side"); pair_of[(size_t)pw] = -2; continue; }
-        pair_of[(size_t)pw] = (int32_t)w.pairs.size();
-        w.pairs.push_back({pw, su[0] >= 0 ? row_of[(size_t)su[0]] : -1, su[1] >= 0 ? row_of[(size_t)su[1]] : -1});
-      } else if (pair_of[(size_t)pw] == -2) refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side");
-    }
-    w.link_off.push_back((int64_t)w.links.size());
-  }
-  if (w.links.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error(who + ": more than 2^31 links");
-  if (bad >= 0) throw UnsupportedError(who + ": factor " + std::to_string(bad) + " " + why + " (DESIGN.md 4, moving label windows)");
-}
-}  // namespace
-
-int lpmp_plan_window_info(lpmp_plan* p, int64_t n, const int32_t* factors, int64_t* n_links, int64_t* n_pairwise, char* why, int why_n) {
-  if (why && why_n > 0) why[0] = 0;
-  const int rc = guarded([&] {
-    if (!p || (factors && n < 0)) throw std::runtime_error("lpmp_plan_window_info: bad argument");
-    WindowPlan w;
-    window_plan(p->p, n, factors, "lpmp_plan_window_info", w);
-    if (n_links) *n_links = (int64_t)w.links.size();
-    if (n_pairwise) *n_pairwise = (int64_t)w.pairs.size();
-  });
-  if (rc != LPMP_OK && why && why_n > 0) { std::strncpy(why, lpmp_last_error(), (size_t)why_n - 1); why[why_n - 1] = 0; }
-  return rc;
-}
-
-// A prepared list of unaries whose windows move together, modelled on lpmp_readout: records and links are uploaded at create, a
-// move plans and uploads nothing but its inputs
-struct lpmp_window_set {
-  int device = 0;
-  uint64_t gen = 0;                     // ModelState::model_gen of the model it was made for
-  int64_t n = 0, n_pairwise = 0;
-  int32_t max_labels = 0;
-  DevBuf<MoveRec> recs; DevBuf<MoveLink> links; DevBuf<MoveShiftRec> pairs;
-  DevBuf<int32_t> d_delta;              // a host delta, and host costs, pass through buffers of the set
-  DevBuf<double> d_cost[2];
-};
-
-int lpmp_window_set_create(lpmp_engine* e, int64_t n, const int32_t* factors, lpmp_window_set** out) {
-  return guarded([&] {
-    if (!e || !e->model.plan) throw StateError("lpmp_window_set_create: no model uploaded (a window set lists factors of the uploaded model)");
-    if (!out || (factors && n < 0)) throw std::runtime_error("lpmp_window_set_create: bad argument");
-    HIP_CHECK(hipSetDevice(e->device));
-    ModelState& m = e->model;
-    const Plan& p = m.plan->p;
-    WindowPlan w;
-    window_plan(p, n, factors, "lpmp_window_set_create", w);
-    auto ws = std::make_unique<lpmp_window_set>();
-    ws->device = e->device; ws->gen = m.model_gen;
-    ws->n = (int64_t)w.factors.size(); ws->n_pairwise = (int64_t)w.pairs.size(); ws->max_labels = w.max_labels;
-    std::vector<MoveRec> recs((size_t)ws->n);
-    for (int64_t i = 0; i < ws->n; ++i) {
-      const int32_t u = w.factors[(size_t)i];
-      // (vector factors live in the packed array under every layout)
-      recs[(size_t)i] = {p.f_doff[(size_t)u], p.f_dim0[u], u, (int32_t)w.link_off[(size_t)i], (int32_t)(w.link_off[(size_t)i + 1] - w.link_off[(size_t)i]), (int32_t)i, 0};
-    }
-    std::vector<MoveLink> links(w.links.size());
-    for (size_t k = 0; k < links.size(); ++k) links[k] = {p.doff(w.links[k].p) + (w.links[k].side ? p.f_dim0[w.links[k].p] : 0)};
-    // the places of a shift: those lpmp_set_constants writes for the second entry of a DIFF_SHIFT row
-    const int64_t sh_base = m.d_shared ? (int64_t)(((intptr_t)m.d_shared.get() - (intptr_t)m.d_const) / 8) : 0;
-    std::vector<MoveShiftRec> pairs(w.pairs.size());
-    for (size_t k = 0; k < pairs.size(); ++k) {
-      const int32_t f = w.pairs[k].p;
-      const int64_t cell = p.coff(f), c = (cell - sh_base) / 2;
-      if (c < 0 || 2 * c + 3 >= (int64_t)m.sh_cells.size() || sh_base + 2 * c != cell) throw std::runtime_error("lpmp_window_set_create: internal: factor " + std::to_string(f) + " has no cell");
-      pairs[k] = {cell + 2, m.sh_cells[(size_t)(2 * c + 2)], w.pairs[k].left_row, w.pairs[k].right_row, f, 0};
-    }
-    if (!recs.empty()) { ws->recs.alloc(recs.size()); h2d(ws->recs, recs.data(), recs.size() * sizeof(MoveRec), e->stream); }
-    if (!links.empty()) { ws->links.alloc(links.size()); h2d(ws->links, links.data(), links.size() * sizeof(MoveLink), e->stream); }
-    if (!pairs.empty()) { ws->pairs.alloc(pairs.size()); h2d(ws->pairs, pairs.data(), pairs.size() * sizeof(MoveShiftRec), e->stream); }
-    ++m.schedules_built;   // the link tables: structure, like a schedule, counted once
-    *out = ws.release();
-  });
-}
-void lpmp_window_set_destroy(lpmp_window_set* ws) {
-  if (!ws) return;
-  (void)hipSetDevice(ws->device);
-  delete ws;
-}
-int64_t lpmp_window_set_n(const lpmp_window_set* ws) { return ws ? ws->n : 0; }
-int32_t lpmp_window_set_max_labels(const lpmp_window_set* ws) { return ws ? ws->max_labels : 0; }
-int64_t lpmp_window_set_n_pairwise(const lpmp_window_set* ws) { return ws ? ws->n_pairwise : 0; }
-
-// lpmp_move_windows and lpmp_move_windows_carry: one path up to what becomes of the labels
-static int move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
-                        int64_t cost_stride, int cost_mem, bool carry) {
-  return guarded([&] {
-    const std::string who = carry ? "lpmp_move_windows_carry" : "lpmp_move_windows";
-    if (!e || !ws) throw std::runtime_error(who + ": null argument");
-    if (!e->model.plan || ws->gen != e->model.model_gen) throw StateError(who + ": the window set was made for another model (lpmp_upload_model since lpmp_window_set_create)");
-    require_consts(e);
-    const bool costs = cost_old || cost_new;
-    if (delta_mem != LPMP_MEM_HOST && delta_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": delta_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
-    if (costs && cost_mem != LPMP_MEM_HOST && cost_mem != LPMP_MEM_DEVICE) throw std::runtime_error(who + ": cost_mem must be LPMP_MEM_HOST or LPMP_MEM_DEVICE");
-    if (!cost_old != !cost_new) throw std::runtime_error(who + ": cost_old and cost_new come together (the unary costs in the old and in the new window), or not at all");
-    if (ws->n > 0 && !delta) throw std::runtime_error(who + ": null delta");
-    if (costs && cost_stride < ws->max_labels)
-      throw std::runtime_error(who + ": cost_stride " + std::to_string(cost_stride) + " is smaller than the " + std::to_string(ws->max_labels) + " entries of the longest listed vector");
-    const bool host_delta = delta_mem == LPMP_MEM_HOST, host_costs = costs && cost_mem == LPMP_MEM_HOST;
-    if (host_delta)
-      for (int64_t i = 0; i < ws->n; ++i)
-        if (delta[i] < -MOVE_DELTA_MAX || delta[i] > MOVE_DELTA_MAX)
-          throw std::runtime_error(who + ": delta " + std::to_string(delta[i]) + " (entry " + std::to_string(i) + ") is beyond +-2^20; nothing was written");
-    HIP_CHECK(hipSetDevice(e->device));
-    settle(e);                 // passes that ran ahead: the duals moved are those of the pass the caller is at
-    // (device inputs never wait for the stream, as a read-out into device memory does not; host inputs end in a synchronisation)
-    if (host_delta || host_costs) check_chain(e);
-    if (ws->n == 0) return;
-    ModelState& m = e->model;
-    const int32_t* d_delta = delta;
-    if (host_delta) { ws->d_delta.grow((size_t)ws->n); h2d(ws->d_delta, delta, (size_t)ws->n * sizeof(int32_t), e->stream); d_delta = ws->d_delta.get(); }
-    const double* d_cost[2] = {cost_old, cost_new};
-    if (host_costs) {
-      const size_t total = (size_t)(ws->n - 1) * (size_t)cost_stride + (size_t)ws->max_labels;   // (the last row need not be a whole stride)
-      for (int k = 0; k < 2; ++k) { ws->d_cost[k].grow(total); h2d(ws->d_cost[k], d_cost[k], total * sizeof(double), e->stream); d_cost[k] = ws->d_cost[k].get(); }
-    }
-    // (the message vectors of DIFF_SHIFT factors and all vector factors live in the packed array under every layout, and both
-    // kernels are plain launches on the engine's stream: never part of a captured graph or a persistent launch)
-    launch_move_shifts(ws->pairs, ws->n_pairwise, d_delta, m.d_const, m.d_lb, e->stream);
-    launch_move_windows(ws->recs, ws->links, ws->n, d_delta, m.d_dual, m.d_lb, d_cost[0], d_cost[1], cost_stride, e->stream);
-    HIP_CHECK(hipGetLastError());
-    if (carry) {
-      // the labelling is the one piece of state whose meaning is exactly an absolute label: x names x - delta in the new window.  No
-      // primal array: none is made.  The pairwise slots follow their unaries as after a decode (primal_unset_only: unaries only)
-      if (m.have_primal || m.primal_unset_only) launch_carry_labels(ws->recs, ws->n, d_delta, m.d_primal, e->stream);
-      if (m.have_primal) launch_primal_propagate(m.d_plinks, m.n_plinks, m.d_primal, e->stream);
-      HIP_CHECK(hipGetLastError());
-    } else if (m.have_primal || m.primal_unset_only) { upload_unset_primal(e); m.primal_t = 0; }   // as after lpmp_set_constants: the labels belong to the old windows
-    if (host_delta || host_costs) HIP_CHECK(hipStreamSynchronize(e->stream));   // the caller's arrays are the caller's again
-  });
-}
-int lpmp_move_windows(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
-                      int64_t cost_stride, int cost_mem) {
-  return move_windows(e, ws, delta, delta_mem, cost_old, cost_new, cost_stride, cost_mem, false);
-}
-int lpmp_move_windows_carry(lpmp_engine* e, lpmp_window_set* ws, const int32_t* delta, int delta_mem, const double* cost_old, const double* cost_new,
-                            int64_t cost_stride, int cost_mem) {
-  return move_windows(e, ws, delta, delta_mem, cost_old, cost_new, cost_stride, cost_mem, true);
-}
-
 int lpmp_compute_pass_custom(lpmp_engine* e, int64_t n, const int32_t* factors, const int64_t* om_off, const double* om,
                              const int64_t* mk_off, const uint8_t* mk) {
   return guarded([&] {
@@ -3306,7 +2236,7 @@ int lpmp_schedule_destroy(lpmp_engine* e, int id) {
 }
 
 // the chain executor bounds every wait; a run that gave up leaves the duals half updated and must not pass silently
-static void check_chain(lpmp_engine* e) {
+void check_chain(lpmp_engine* e) {
   if (!e->chain_ran || !e->d_chain_abort) return;
   int32_t* h = (int32_t*)(e->pinned + 8 * 1024 + 128);
   static_assert(8 * 1024 + 128 + CHAIN_ABORT_WORDS * 4 <= PINNED_WORDS_BYTES, "pinned block");
@@ -3827,5 +2757,3 @@ int lpmp_synth_fill(void* p, int64_t n, uint64_t seed, uint64_t first, void* str
     HIP_CHECK(hipGetLastError());
   });
 }
-
-}  // extern "C"

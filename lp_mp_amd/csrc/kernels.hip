@@ -4469,7 +4469,7 @@ void launch_zero_pairwise(const ZeroRec* recs, int64_t n, double* dual, hipStrea
   if (n > 0) hipLaunchKernelGGL(zero_pairwise_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, recs, n, dual);
 }
 
-// ---- prepared read-outs (engine.cpp, lpmp_readout_*) ----------------------------------------------------------
+// ---- prepared read-outs (prepared.cpp, lpmp_readout_*) ----------------------------------------------------------
 // Gathers over a device record list into the caller's array: no LDS, no atomics, plain vector stores, 64-bit offsets.  Nothing but
 // dst is written, and of a row only the entries below the factor's label count.
 // labels: one thread per listed factor; dst[i] = its label slot of the primal array
@@ -4610,7 +4610,7 @@ void launch_readout_beliefs(const ReadoutRec* recs, const DecodeLink* links, con
   else launch_readout_beliefs_as<64, READOUT_CHUNK / 64>(recs, links, dual, cdata, dst, dst_stride, first, count, tab32, s);
 }
 
-// ---- moving label windows (engine.cpp, lpmp_move_windows) ---------------------------------------------------------
+// ---- moving label windows (prepared.cpp, lpmp_move_windows) ---------------------------------------------------------
 // The window of a listed unary moves by delta labels: new label x is old label x + delta, labels that enter the window copy the
 // nearest old end value — v'[x] = v[g(x)], g(x) = clamp(x + delta, 0, d0 - 1) — for theta and for the unary's message vector in every
 // adjacent pairwise factor.  One wave per listed unary; a vector of up to MOVE_MAX_LABELS labels is held in registers, lane l the
@@ -4689,12 +4689,12 @@ void launch_move_shifts(const MoveShiftRec* recs, int64_t n, const int32_t* delt
   if (n > 0) hipLaunchKernelGGL(move_shifts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, delta, cdata, lb);
 }
 
-// ---- primal state on the device (engine.cpp: lpmp_readout_set_labels, lpmp_move_windows_carry, lpmp_lower_bound_dev,
+// ---- primal state on the device (prepared.cpp: lpmp_readout_set_labels, lpmp_move_windows_carry; engine.cpp: lpmp_lower_bound_dev,
 // lpmp_evaluate_primal_dev) ------------------------------------------------------------------------------------
 // Plain launches on the engine's stream: no LDS, no atomics, plain vector stores, 64-bit indexing of primal[2 * f].
 // labels in: the input twin of readout_labels_kernel.  One thread per listed factor; src[row] is its label, the dimension (or any
 // value outside [0, d0 - 1]: no bit pattern reaches the primal array unchecked) means unset.  A read-out with a factor listed
-// twice never gets here (engine.cpp), so every slot has one writer
+// twice never gets here (prepared.cpp), so every slot has one writer
 __global__ void __launch_bounds__(256)
 set_labels_kernel(const ReadoutRec* __restrict__ recs, int64_t n, const int32_t* __restrict__ src, int32_t* __restrict__ primal) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

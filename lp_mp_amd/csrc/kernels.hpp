@@ -1,6 +1,6 @@
-// kernels.hpp — the interface between engine.cpp (host) and kernels.hip (device code and its launch wrappers): the one
-// definition of every struct, constant and prototype that crosses the launch boundary.  Included by those two files only;
-// the planner (plan.hpp and its sources) stays free of HIP.
+// kernels.hpp — the interface between the engine's host code (engine.cpp, prepared.cpp) and kernels.hip (device code and its launch
+// wrappers): the one definition of every struct, constant and prototype that crosses the launch boundary.  Included by those files
+// only (the host code through engine_state.hpp); the planner (plan.hpp and its sources) stays free of HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -132,7 +132,7 @@ struct MoveLink { int64_t vec_off; };
 // and the rows of the unaries on its two sides (-1: no unary there, or one that is not listed: delta 0)
 struct MoveShiftRec { int64_t cell, packed; int32_t left_row, right_row, factor, pad; };
 static_assert(sizeof(MoveRec) == 32 && sizeof(MoveShiftRec) == 32, "window record layout");
-constexpr int MOVE_MAX_LABELS = GEN_MAXD;
+static_assert(MOVE_MAX_LABELS == GEN_MAXD, "window moves hold a vector in the registers of one wave (plan.hpp)");
 constexpr int MOVE_DELTA_MAX = 1 << 20;               // |delta| of a move: a host value beyond it is refused, a device value saturated
 
 // ---- launch wrappers (kernels.hip) -------------------------------------------------------------------------------------

@@ -1359,14 +1359,57 @@ std::string Plan::move_obstacle(int32_t u, const PairSides& ps, const char* move
   return "";
 }
 
-// ---- path moves (plan.hpp, PathPlan) ----------------------------------------------------------------------------------------
-PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* un, const std::string& who) const {
-  PathPlan pp;
-  auto S = [](int64_t v) { return std::to_string(v); };
-  if (n_groups < 0 || !group_off || !path_off) fail(who + ": bad argument");
+// ---- the stages path_plan and forest_plan share ---------------------------------------------------------------------------------
+namespace {
+std::string S(int64_t v) { return std::to_string(v); }
+// group_off [n_groups + 1] starts at 0 and never decreases
+void check_group_off(int64_t n_groups, const int64_t* group_off, const std::string& who) {
   if (group_off[0] != 0) fail(who + ": group_off[0] is " + S(group_off[0]) + ", not 0");
   for (int64_t g = 0; g < n_groups; ++g)
     if (group_off[g + 1] < group_off[g]) fail(who + ": group_off is not monotone at group " + S(g));
+}
+// the ne listed members, group g holding the entries [first(g), first(g + 1)): every one a VECTOR factor of the plan, none twice
+// in its group.  grp_of / ent_of [nf] are the scan's stamps (the group a factor was last seen in, and its entry there)
+template <class First>
+void check_members(const Plan& p, int64_t ne, const int32_t* un, int64_t n_groups, First first, const std::string& who,
+                   std::vector<int64_t>& grp_of, std::vector<int64_t>& ent_of) {
+  for (int64_t e = 0; e < ne; ++e) {
+    const int32_t f = un[e];
+    if (f < 0 || f >= p.nf) fail(who + ": factor index " + S(f) + " (entry " + S(e) + ") is out of range");
+    if (p.f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + S(f) + " (entry " + S(e) + ") is not a VECTOR factor");
+  }
+  grp_of.assign((size_t)p.nf, -1); ent_of.assign((size_t)p.nf, 0);
+  for (int64_t g = 0; g < n_groups; ++g)
+    for (int64_t e = first(g); e < first(g + 1); ++e) {
+      const size_t f = (size_t)un[e];
+      if (grp_of[f] == g) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") appears twice in group " + S(g) + " (first: entry " + S(ent_of[f]) + ")");
+      grp_of[f] = g; ent_of[f] = e;
+    }
+}
+// the unsupported shapes: the lowest listed unary that has one goes into `bad`, and the text of `why` comes back ("": none has)
+std::string lowest_obstacle(const Plan& p, int64_t ne, const int32_t* un, const PairSides& sides, const char* move, const std::string& who, int32_t& bad) {
+  std::string what;
+  for (int64_t e = 0; e < ne; ++e) {
+    const int32_t u = un[e];
+    if (bad >= 0 && u >= bad) continue;
+    const std::string w = p.move_obstacle(u, sides, move);
+    if (!w.empty()) { bad = u; what = w; }
+  }
+  return bad < 0 ? "" : who + ": factor " + S(bad) + " " + what + " (DESIGN.md 8, " + move + " moves)";
+}
+// the messages of unary u in ascending message index: the order of its links
+void sorted_messages(const Plan& p, int32_t u, std::vector<int32_t>& msgs) {
+  msgs.clear();
+  for (int64_t k = p.fm_off[(size_t)u]; k < p.fm_off[(size_t)u + 1]; ++k) msgs.push_back(p.fm[(size_t)k].msg);
+  std::sort(msgs.begin(), msgs.end());
+}
+}  // namespace
+
+// ---- path moves (plan.hpp, PathPlan) ----------------------------------------------------------------------------------------
+PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64_t* path_off, const int32_t* un, const std::string& who) const {
+  PathPlan pp;
+  if (n_groups < 0 || !group_off || !path_off) fail(who + ": bad argument");
+  check_group_off(n_groups, group_off, who);
   const int64_t n_paths = group_off[n_groups];
   if (path_off[0] != 0) fail(who + ": path_off[0] is " + S(path_off[0]) + ", not 0");
   for (int64_t j = 0; j < n_paths; ++j)
@@ -1374,38 +1417,17 @@ PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64
   const int64_t ne = path_off[n_paths];
   if (ne > (int64_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 entries");
   if (ne > 0 && !un) fail(who + ": null list of unaries");
-  for (int64_t e = 0; e < ne; ++e) {
-    const int32_t f = un[e];
-    if (f < 0 || f >= nf) fail(who + ": factor index " + S(f) + " (entry " + S(e) + ") is out of range");
-    if (f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + S(f) + " (entry " + S(e) + ") is not a VECTOR factor");
-  }
   // where a unary sits in the group at hand: group stamp, path, index in the path, entry
-  std::vector<int64_t> grp_of((size_t)nf, -1), path_of((size_t)nf, 0), ent_of((size_t)nf, 0);
-  for (int64_t g = 0; g < n_groups; ++g)
-    for (int64_t e = path_off[group_off[g]]; e < path_off[group_off[g + 1]]; ++e) {
-      const size_t f = (size_t)un[e];
-      if (grp_of[f] == g) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") appears twice in group " + S(g) + " (first: entry " + S(ent_of[f]) + ")");
-      grp_of[f] = g; ent_of[f] = e;
-    }
+  std::vector<int64_t> grp_of, path_of((size_t)nf, 0), ent_of;
+  check_members(*this, ne, un, n_groups, [&](int64_t g) { return path_off[group_off[g]]; }, who, grp_of, ent_of);
   pp.group_off.assign(group_off, group_off + n_groups + 1);
   pp.path_off.assign(path_off, path_off + n_paths + 1);
   pp.unaries.assign(un, un + ne);
   // the unary on each side of every pairwise factor, from all unary-pairwise messages (as in decode_plan)
   const PairSides sides = pair_sides();
   const std::vector<int32_t>& side_unary = sides.side_unary;
-  // the unsupported shapes: the lowest listed unary that has one
-  int32_t bad = -1; std::string what;
-  for (int64_t e = 0; e < ne; ++e) {
-    const int32_t u = un[e];
-    if (bad >= 0 && u >= bad) continue;
-    const std::string w = move_obstacle(u, sides, "path");
-    if (!w.empty()) { bad = u; what = w; }
-  }
-  if (bad >= 0) {
-    pp.bad_factor = bad;
-    pp.why = who + ": factor " + S(bad) + " " + what + " (DESIGN.md 8, path moves)";
-    return pp;
-  }
+  pp.why = lowest_obstacle(*this, ne, un, sides, "path", who, pp.bad_factor);
+  if (!pp.why.empty()) return pp;
   // links in ascending message index, and the path edges
   pp.edge.assign((size_t)ne, -1); pp.edge_prev_side.assign((size_t)ne, 0);
   pp.link_off.assign(1, 0);
@@ -1419,9 +1441,7 @@ PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64
       for (int64_t e = path_off[j]; e < path_off[j + 1]; ++e) {
         const int32_t u = un[e];
         pp.max_labels = std::max(pp.max_labels, f_dim0[u]);
-        msgs.clear();
-        for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) msgs.push_back(fm[(size_t)k].msg);
-        std::sort(msgs.begin(), msgs.end());
+        sorted_messages(*this, u, msgs);
         for (int32_t m : msgs) {
           const int32_t p = m_right[(size_t)m], side = mtypes[(size_t)m_type[(size_t)m]].param, v = side_unary[2 * (size_t)p + (size_t)(1 - side)];
           int32_t on_path = 0;
@@ -1454,27 +1474,14 @@ PathPlan Plan::path_plan(int64_t n_groups, const int64_t* group_off, const int64
 // ---- forest moves (plan.hpp, ForestPlan) --------------------------------------------------------------------------------------
 ForestPlan Plan::forest_plan(int64_t n_groups, const int64_t* group_off, const int32_t* un, const int32_t* par, const std::string& who) const {
   ForestPlan fp;
-  auto S = [](int64_t v) { return std::to_string(v); };
   if (n_groups < 0 || !group_off) fail(who + ": bad argument");
-  if (group_off[0] != 0) fail(who + ": group_off[0] is " + S(group_off[0]) + ", not 0");
-  for (int64_t g = 0; g < n_groups; ++g)
-    if (group_off[g + 1] < group_off[g]) fail(who + ": group_off is not monotone at group " + S(g));
+  check_group_off(n_groups, group_off, who);
   const int64_t ne = group_off[n_groups];
   if (ne > (int64_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 entries");
   if (ne > 0 && (!un || !par)) fail(who + ": null list of unaries or parents");
-  for (int64_t e = 0; e < ne; ++e) {
-    const int32_t f = un[e];
-    if (f < 0 || f >= nf) fail(who + ": factor index " + S(f) + " (entry " + S(e) + ") is out of range");
-    if (f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + S(f) + " (entry " + S(e) + ") is not a VECTOR factor");
-  }
   // where a unary sits in the group at hand: group stamp and entry
-  std::vector<int64_t> grp_of((size_t)nf, -1), ent_of((size_t)nf, 0);
-  for (int64_t g = 0; g < n_groups; ++g)
-    for (int64_t e = group_off[g]; e < group_off[g + 1]; ++e) {
-      const size_t f = (size_t)un[e];
-      if (grp_of[f] == g) fail(who + ": factor " + S(un[e]) + " (entry " + S(e) + ") appears twice in group " + S(g) + " (first: entry " + S(ent_of[f]) + ")");
-      grp_of[f] = g; ent_of[f] = e;
-    }
+  std::vector<int64_t> grp_of, ent_of;
+  check_members(*this, ne, un, n_groups, [&](int64_t g) { return group_off[g]; }, who, grp_of, ent_of);
   fp.group_off.assign(group_off, group_off + n_groups + 1);
   fp.unaries.assign(un, un + ne);
   fp.parent.assign(par, par + ne);
@@ -1504,21 +1511,9 @@ ForestPlan Plan::forest_plan(int64_t n_groups, const int64_t* group_off, const i
     }
     if (lowest >= 0) fail(who + ": the parent pointers close a cycle through factor " + S(un[lowest]) + " (entry " + S(lowest) + ")");
   }
-  // the unsupported shapes: the lowest listed unary that has one
   const PairSides sides = pair_sides();
-  { int32_t bad = -1; std::string what;
-    for (int64_t e = 0; e < ne; ++e) {
-      const int32_t u = un[e];
-      if (bad >= 0 && u >= bad) continue;
-      const std::string w = move_obstacle(u, sides, "forest");
-      if (!w.empty()) { bad = u; what = w; }
-    }
-    if (bad >= 0) {
-      fp.bad_factor = bad;
-      fp.why = who + ": factor " + S(bad) + " " + what + " (DESIGN.md 8, forest moves)";
-      return fp;
-    }
-  }
+  fp.why = lowest_obstacle(*this, ne, un, sides, "forest", who, fp.bad_factor);
+  if (!fp.why.empty()) return fp;
   // links in ascending message index, the tree edges and the children
   fp.edge.assign((size_t)ne, -1); fp.edge_side.assign((size_t)ne, 0);
   fp.link_off.assign(1, 0); fp.child_off.assign(1, 0);
@@ -1532,9 +1527,7 @@ ForestPlan Plan::forest_plan(int64_t n_groups, const int64_t* group_off, const i
     for (int64_t e = b; e < en; ++e) {
       const int32_t u = un[e];
       fp.max_labels = std::max(fp.max_labels, f_dim0[u]);
-      msgs.clear();
-      for (int64_t k = fm_off[(size_t)u]; k < fm_off[(size_t)u + 1]; ++k) msgs.push_back(fm[(size_t)k].msg);
-      std::sort(msgs.begin(), msgs.end());
+      sorted_messages(*this, u, msgs);
       for (int32_t m : msgs) {
         const int32_t p = m_right[(size_t)m], side = mtypes[(size_t)m_type[(size_t)m]].param, v = sides.side_unary[2 * (size_t)p + (size_t)(1 - side)];
         int32_t tree = 0;
@@ -1584,6 +1577,77 @@ ForestPlan Plan::forest_plan(int64_t n_groups, const int64_t* group_off, const i
   }
   if (fp.links.size() > (size_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 links");
   return fp;
+}
+
+// ---- moving label windows (plan.hpp, WindowPlan) ----------------------------------------------------------------------------------
+WindowPlan Plan::window_plan(int64_t n, const int32_t* factors, const std::string& who) const {
+  WindowPlan w;
+  const Plan& p = *this;
+  std::vector<int32_t> row_of((size_t)p.nf, -1);
+  if (!factors) { for (int64_t f = 0; f < p.nf; ++f) if (p.f_kind[f] == LPMP_F_VECTOR) { row_of[(size_t)f] = (int32_t)w.factors.size(); w.factors.push_back((int32_t)f); } }
+  else {
+    if (n > (int64_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 factors listed");
+    w.factors.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t f = factors[i];
+      if (f < 0 || f >= p.nf) fail(who + ": factor index " + std::to_string(f) + " (entry " + std::to_string(i) + ") is out of range");
+      if (p.f_kind[f] != LPMP_F_VECTOR) fail(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is not a VECTOR factor");
+      if (row_of[(size_t)f] >= 0) fail(who + ": factor " + std::to_string(f) + " (entry " + std::to_string(i) + ") is listed twice");
+      row_of[(size_t)f] = (int32_t)i;
+      w.factors.push_back(f);
+    }
+  }
+  int32_t bad = -1; std::string why;
+  auto refuse = [&](int32_t u, const std::string& what) { if (bad < 0 || u < bad) { bad = u; why = what; } };
+  // the unary on each side of a DIFF_SHIFT factor, from ALL its unary-pairwise messages (-1: none, -2: two different ones)
+  auto side_unaries = [&](int32_t pw, int32_t out[2]) {
+    out[0] = out[1] = -1;
+    for (int64_t k = p.fm_off[(size_t)pw]; k < p.fm_off[(size_t)pw + 1]; ++k) {
+      const MsgEntry& me = p.fm[(size_t)k];
+      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
+      if (me.role != 1 || mt.kind != LPMP_M_UNARY_PAIRWISE || (mt.param != 0 && mt.param != 1)) continue;
+      const int32_t u = p.m_left[(size_t)me.msg];
+      int32_t& slot = out[mt.param];
+      slot = slot == -1 || slot == u ? u : -2;
+    }
+  };
+  std::vector<int32_t> pair_of((size_t)p.nf, -1);
+  w.link_off.assign(1, 0);
+  for (size_t i = 0; i < w.factors.size(); ++i) {
+    const int32_t u = w.factors[i], d = p.f_dim0[u];
+    w.max_labels = std::max(w.max_labels, d);
+    if (d > MOVE_MAX_LABELS) refuse(u, "has " + std::to_string(d) + " labels (a wave holds a vector of at most " + std::to_string(MOVE_MAX_LABELS) + ")");
+    const size_t first = w.links.size();
+    for (int64_t k = p.fm_off[(size_t)u]; k < p.fm_off[(size_t)u + 1]; ++k) {
+      const MsgEntry& me = p.fm[(size_t)k];
+      const lpmp_msg_type& mt = p.mtypes[(size_t)p.m_type[(size_t)me.msg]];
+      const int32_t pw = me.role == 0 ? p.m_right[(size_t)me.msg] : -1;
+      if (mt.kind != LPMP_M_UNARY_PAIRWISE || pw < 0 || p.f_kind[pw] != LPMP_F_PAIRWISE_DIFF_SHIFT || (mt.param != 0 && mt.param != 1)) {
+        refuse(u, "has a message that is not a unary-pairwise message with the factor as its unary and a DIFF_SHIFT factor on the right");
+        continue;
+      }
+      const int32_t side = mt.param;
+      if ((side ? p.f_dim1[pw] : p.f_dim0[pw]) != d) { refuse(u, "and side " + std::to_string(side) + " of factor " + std::to_string(pw) + " differ in their label counts"); continue; }
+      bool twice = false;
+      for (size_t q = first; q < w.links.size(); ++q) twice = twice || (w.links[q].p == pw && w.links[q].side == side);
+      if (twice) { refuse(u, "has two messages into one vector of factor " + std::to_string(pw)); continue; }
+      w.links.push_back({pw, side});
+      if (pair_of[(size_t)pw] < 0) {
+        int32_t su[2];
+        side_unaries(pw, su);
+        if (su[0] == -2 || su[1] == -2) { refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side"); pair_of[(size_t)pw] = -2; continue; }
+        pair_of[(size_t)pw] = (int32_t)w.pairs.size();
+        w.pairs.push_back({pw, su[0] >= 0 ? row_of[(size_t)su[0]] : -1, su[1] >= 0 ? row_of[(size_t)su[1]] : -1});
+      } else if (pair_of[(size_t)pw] == -2) refuse(u, "is next to DIFF_SHIFT factor " + std::to_string(pw) + ", which has two different unaries on one side");
+    }
+    w.link_off.push_back((int64_t)w.links.size());
+  }
+  if (w.links.size() > (size_t)std::numeric_limits<int32_t>::max()) fail(who + ": more than 2^31 links");
+  if (bad >= 0) {
+    w.bad_factor = bad;
+    w.why = who + ": factor " + std::to_string(bad) + " " + why + " (DESIGN.md 4, moving label windows)";
+  }
+  return w;
 }
 
 // ---- partition sweeps (reference LP_MP.h:1717-1843).  union_find.hxx:5-93: union by size, the first argument's root

@@ -337,6 +337,21 @@ struct ForestPlan {
   int64_t n_trees = 0, n_tree_edges = 0, n_off_tree_links = 0;
   int32_t max_height = 0, max_labels = 0;
 };
+// Moving label windows (lpmp_move_windows): the structure of a window set, from the structure alone.  The listed unaries
+// (every VECTOR factor without a list), the links of each in message-list order, and the DIFF_SHIFT factors next to them with the
+// row of the unary on either side (-1: not listed).
+constexpr int MOVE_MAX_LABELS = 512;       // a listed unary's label count: a wave holds a whole vector in registers (kernels.hpp)
+struct WindowLink { int32_t p, side; };
+struct WindowPair { int32_t p, left_row, right_row; };
+struct WindowPlan {
+  std::string why;                       // "" or why the set is refused as unsupported (names the lowest offending listed unary)
+  int32_t bad_factor = -1;
+  std::vector<int32_t> factors;
+  std::vector<int64_t> link_off;        // CSR over `factors`
+  std::vector<WindowLink> links;
+  std::vector<WindowPair> pairs;        // in the order the listed unaries meet them
+  int32_t max_labels = 0;
+};
 // The unary on each side of every pairwise factor, from all unary-pairwise messages: side_unary[2 p + s], and how many messages
 // name that side (saturating at 2).  What path sets, forest sets and the forest cover judge a unary by (Plan::move_obstacle)
 struct PairSides { std::vector<int32_t> side_unary; std::vector<uint8_t> side_count; };
@@ -456,6 +471,10 @@ struct Plan {
   // parents, cycles; then the unsupported shapes (those of path_plan); then the tree edges and the pairwise factors that would
   // close a cycle or join two trees
   ForestPlan forest_plan(int64_t n_groups, const int64_t* group_off, const int32_t* unaries, const int32_t* parent, const std::string& who) const;
+  // Structure of a window set (include/lpmp_engine.h, lpmp_window_set_create): n listed factors, or factors == nullptr for every VECTOR
+  // factor.  Throws std::runtime_error (LPMP_ERR_INVALID) naming the entry: out of range, not a VECTOR factor, listed twice; a set
+  // the move does not take comes back with WindowPlan::why set, naming the lowest listed factor with an obstacle
+  WindowPlan window_plan(int64_t n, const int32_t* factors, const std::string& who) const;
   // what the unsupported-shape check of path_plan / forest_plan reads, and the check itself on VECTOR factor u: "" or what is
   // wrong with it (a message that is not unary-pairwise with u on the left; an adjacent pairwise factor without exactly one
   // unary on each side from two different unaries; more than PATH_MAX_LABELS labels — `move` is the word the message uses)

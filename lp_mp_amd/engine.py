@@ -1158,32 +1158,57 @@ class Engine:
         return out
 
 
-class Readout:
-    """A prepared list of VECTOR factors of the engine's uploaded model (include/lpmp_engine.h, lpmp_readout_*).  Structure: it stays
-    valid across new costs, passes and decodes; after the engine's next ``upload`` every call raises (LPMP_ERR_STATE) and ``close``
-    still works.  ``dst_dev``: a raw device pointer — the call is asynchronous on the engine's stream and returns None."""
+class _PreparedSet:
+    """What the four prepared sets share: the engine and library handles, the handle the library's create call returns, and
+    ``close`` / ``__del__`` through the library call that ``_destroy`` names."""
+    _destroy = None
 
-    def __init__(self, engine: Engine, factors=None):
+    def _create(self, engine: Engine, create: str, *args):
         self.e = engine
         self.L = engine.L
         h = C.c_void_p()
+        _chk(getattr(self.L, create)(engine.h, *args, C.addressof(h)))
+        self.h = h.value
+
+    def _create_listed(self, engine: Engine, create: str, factors):
+        """a set made from a list of factors, or from None: every VECTOR factor"""
         if factors is None:
-            _chk(self.L.lpmp_readout_create(engine.h, 0, None, C.addressof(h)))
+            self._create(engine, create, 0, None)
         else:
             factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
-            keep = factors if factors.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
-            _chk(self.L.lpmp_readout_create(engine.h, int(factors.shape[0]), keep.ctypes.data, C.addressof(h)))
-        self.h = h.value
-        self.n = int(self.L.lpmp_readout_n(self.h))
-        self.max_labels = int(self.L.lpmp_readout_max_labels(self.h))
+            self._create(engine, create, int(factors.shape[0]), _valid_ptr(factors).ctypes.data)
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.lpmp_readout_destroy(self.h)
+            getattr(self.L, self._destroy)(self.h)
             self.h = None
 
     def __del__(self):
         self.close()
+
+
+def _int32_list(values, n: int, who: str, noun: str):
+    """``values`` (None: an empty list) as ``n`` contiguous int32 entries, never an empty array (still a valid pointer)"""
+    v = np.asarray([] if values is None else values).reshape(-1)
+    if v.shape[0] != n:
+        raise ValueError(f"{who}: {n} {noun}s expected, got {v.shape[0]}")
+    if n and not np.issubdtype(v.dtype, np.integer):
+        raise ValueError(f"{who}: integer {noun}s are expected")
+    if n and (v.min() < -(1 << 31) or v.max() >= (1 << 31)):
+        raise ValueError(f"{who}: a {noun} does not fit an int32")
+    return np.ascontiguousarray(v, np.int32) if n else np.zeros(1, np.int32)
+
+
+class Readout(_PreparedSet):
+    """A prepared list of VECTOR factors of the engine's uploaded model (include/lpmp_engine.h, lpmp_readout_*).  Structure: it stays
+    valid across new costs, passes and decodes; after the engine's next ``upload`` every call raises (LPMP_ERR_STATE) and ``close``
+    still works.  ``dst_dev``: a raw device pointer — the call is asynchronous on the engine's stream and returns None."""
+    _destroy = "lpmp_readout_destroy"
+
+    def __init__(self, engine: Engine, factors=None):
+        self._create_listed(engine, "lpmp_readout_create", factors)
+        self.n = int(self.L.lpmp_readout_n(self.h))
+        self.max_labels = int(self.L.lpmp_readout_max_labels(self.h))
 
     def labels(self, dst_dev: Optional[int] = None):
         """[n] int32: the label slot of every listed factor as ``Engine.download_primal`` reports it (unset: the label count)"""
@@ -1201,14 +1226,7 @@ class Readout:
         if src_dev is not None:
             _chk(self.L.lpmp_readout_set_labels(self.e.h, self.h, C.c_void_p(src_dev), MEM_DEVICE))
             return
-        s = np.asarray([] if src is None else src).reshape(-1)
-        if s.shape[0] != self.n:
-            raise ValueError(f"set_labels: {self.n} labels expected, got {s.shape[0]}")
-        if self.n and not np.issubdtype(s.dtype, np.integer):
-            raise ValueError("set_labels: integer labels are expected")
-        if self.n and (s.min() < -(1 << 31) or s.max() >= (1 << 31)):
-            raise ValueError("set_labels: a label does not fit an int32")
-        s = np.ascontiguousarray(s, np.int32) if self.n else np.zeros(1, np.int32)
+        s = _int32_list(src, self.n, "set_labels", "label")
         _chk(self.L.lpmp_readout_set_labels(self.e.h, self.h, C.c_void_p(s.ctypes.data), MEM_HOST))
 
     def _rows(self, fn, dst_dev, stride):
@@ -1231,33 +1249,17 @@ class Readout:
         return self._rows(self.L.lpmp_readout_beliefs, dst_dev, stride)
 
 
-class WindowSet:
+class WindowSet(_PreparedSet):
     """A prepared list of distinct VECTOR factors of the engine's uploaded model whose label windows move together
     (include/lpmp_engine.h, lpmp_window_set_* / lpmp_move_windows).  Structure, like a ``Readout``: it stays valid across new costs,
     passes and moves; after the engine's next ``upload`` every move raises (LPMP_ERR_STATE) and ``close`` still works."""
+    _destroy = "lpmp_window_set_destroy"
 
     def __init__(self, engine: Engine, factors=None):
-        self.e = engine
-        self.L = engine.L
-        h = C.c_void_p()
-        if factors is None:
-            _chk(self.L.lpmp_window_set_create(engine.h, 0, None, C.addressof(h)))
-        else:
-            factors = np.ascontiguousarray(factors, np.int32).reshape(-1)
-            keep = factors if factors.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
-            _chk(self.L.lpmp_window_set_create(engine.h, int(factors.shape[0]), keep.ctypes.data, C.addressof(h)))
-        self.h = h.value
+        self._create_listed(engine, "lpmp_window_set_create", factors)
         self.n = int(self.L.lpmp_window_set_n(self.h))
         self.n_pairwise = int(self.L.lpmp_window_set_n_pairwise(self.h))
         self.max_labels = int(self.L.lpmp_window_set_max_labels(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lpmp_window_set_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def move(self, delta=None, delta_dev: Optional[int] = None, cost_old=None, cost_new=None, cost_dev=None, stride: Optional[int] = None,
              carry_labels: bool = False):
@@ -1272,14 +1274,7 @@ class WindowSet:
         if delta_dev is not None:
             dp, dm = C.c_void_p(delta_dev), MEM_DEVICE
         else:
-            d = np.asarray([] if delta is None else delta).reshape(-1)
-            if d.shape[0] != self.n:
-                raise ValueError(f"move: {self.n} deltas expected, got {d.shape[0]}")
-            if self.n and not np.issubdtype(d.dtype, np.integer):
-                raise ValueError("move: integer deltas are expected")
-            if self.n and (d.min() < -(1 << 31) or d.max() >= (1 << 31)):
-                raise ValueError("move: a delta does not fit an int32")
-            d = np.ascontiguousarray(d, np.int32) if self.n else np.zeros(1, np.int32)
+            d = _int32_list(delta, self.n, "move", "delta")
             dp, dm = C.c_void_p(d.ctypes.data), MEM_HOST
         co = cn = None
         cm, cs = MEM_HOST, 0
@@ -1309,31 +1304,19 @@ class WindowSet:
         _chk(fn(self.e.h, self.h, dp, dm, co, cn, cs, cm))
 
 
-class PathSet:
+class PathSet(_PreparedSet):
     """Prepared groups of paths of the engine's uploaded model (include/lpmp_engine.h, lpmp_path_set_* / lpmp_path_moves).  Structure,
     like a ``Readout``: it stays valid across new costs, passes, decodes and window moves; after the engine's next ``upload`` every
     move raises (LPMP_ERR_STATE) and ``close`` still works."""
+    _destroy = "lpmp_path_set_destroy"
 
     def __init__(self, engine: Engine, groups):
-        self.e = engine
-        self.L = engine.L
         go, po, un = flatten_path_groups(groups)
-        keep = un if un.shape[0] else np.zeros(1, np.int32)      # (an empty list: still a valid pointer)
-        h = C.c_void_p()
-        _chk(self.L.lpmp_path_set_create(engine.h, int(go.shape[0]) - 1, go.ctypes.data, po.ctypes.data, keep.ctypes.data, C.addressof(h)))
-        self.h = h.value
+        self._create(engine, "lpmp_path_set_create", int(go.shape[0]) - 1, go.ctypes.data, po.ctypes.data, _valid_ptr(un).ctypes.data)
         self.n_groups = int(self.L.lpmp_path_set_n_groups(self.h))
         self.n_paths = int(self.L.lpmp_path_set_n_paths(self.h))
         self.longest = int(self.L.lpmp_path_set_longest(self.h))
         self.scratch_bytes = int(self.L.lpmp_path_set_scratch_bytes(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lpmp_path_set_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def move(self, rounds: int = 1):
         """``rounds`` times over the groups in their order: every path takes the labels that minimise the energy over it given all
@@ -1341,31 +1324,19 @@ class PathSet:
         _chk(self.L.lpmp_path_moves(self.e.h, self.h, int(rounds)))
 
 
-class ForestSet:
+class ForestSet(_PreparedSet):
     """Prepared groups of forests of the engine's uploaded model (include/lpmp_engine.h, lpmp_forest_set_* / lpmp_forest_moves).
     Structure, like a ``PathSet``: it stays valid across new costs, passes, decodes and window moves; after the engine's next
     ``upload`` every move raises (LPMP_ERR_STATE) and ``close`` still works."""
+    _destroy = "lpmp_forest_set_destroy"
 
     def __init__(self, engine: Engine, groups):
-        self.e = engine
-        self.L = engine.L
         go, un, par = flatten_forest_groups(groups)
-        un, par = _valid_ptr(un), _valid_ptr(par)
-        h = C.c_void_p()
-        _chk(self.L.lpmp_forest_set_create(engine.h, int(go.shape[0]) - 1, go.ctypes.data, un.ctypes.data, par.ctypes.data, C.addressof(h)))
-        self.h = h.value
+        self._create(engine, "lpmp_forest_set_create", int(go.shape[0]) - 1, go.ctypes.data, _valid_ptr(un).ctypes.data, _valid_ptr(par).ctypes.data)
         self.n_groups = int(self.L.lpmp_forest_set_n_groups(self.h))
         self.n_trees = int(self.L.lpmp_forest_set_n_trees(self.h))
         self.max_height = int(self.L.lpmp_forest_set_max_height(self.h))
         self.scratch_bytes = int(self.L.lpmp_forest_set_scratch_bytes(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lpmp_forest_set_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def move(self, rounds: int = 1):
         """``rounds`` times over the groups in their order: every tree takes the labels that minimise the energy over it given all

@@ -576,3 +576,45 @@ def test_planner_is_plain_cpp17_without_hip(tmp_path):
                           "-o", str(tmp_path / "libplanner.so")] + [os.path.join(csrc, f) for f in ("plan.cpp", "chain_plan.cpp", "order.cpp")]
                          + ["-lpthread"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+
+
+def _info_calls(p):
+    """the plan-side info calls of the prepared sets as ``call(why, why_n) -> rc``, each once with arguments it refuses as invalid
+    (LPMP_ERR_INVALID, -1) and once with a set the move does not take (LPMP_ERR_UNSUPPORTED, -2: the toy model's messages are not
+    unary-pairwise ones)"""
+    i64 = lambda v: np.asarray(v, np.int64)
+    i32 = lambda v: np.asarray(v, np.int32)
+    bad_off, off, po, un, par, far = i64([1, 1]), i64([0, 1]), i64([0, 1]), i32([0]), i32([-1]), i32([1 << 20])
+    L, h = p.L, p.h
+    return {
+        ("path", -1): lambda why, n: L.lpmp_plan_path_info(h, 1, bad_off.ctypes.data, po.ctypes.data, un.ctypes.data, None, None, None, why, n),
+        ("path", -2): lambda why, n: L.lpmp_plan_path_info(h, 1, off.ctypes.data, po.ctypes.data, un.ctypes.data, None, None, None, why, n),
+        ("forest", -1): lambda why, n: L.lpmp_plan_forest_info(h, 1, bad_off.ctypes.data, un.ctypes.data, par.ctypes.data, None, None, None, None, why, n),
+        ("forest", -2): lambda why, n: L.lpmp_plan_forest_info(h, 1, off.ctypes.data, un.ctypes.data, par.ctypes.data, None, None, None, None, why, n),
+        ("window", -1): lambda why, n: L.lpmp_plan_window_info(h, 1, far.ctypes.data, None, None, why, n),
+        ("window", -2): lambda why, n: L.lpmp_plan_window_info(h, 1, un.ctypes.data, None, None, why, n),
+    }
+
+
+def test_info_calls_return_the_last_error_in_why():
+    """lpmp_plan_path_info, lpmp_plan_forest_info and lpmp_plan_window_info hand their refusal over twice: as lpmp_last_error and in
+    ``why``, cut to ``why_n`` bytes with the terminator; ``why_n`` = 0 or a null ``why`` is tolerated and writes nothing.
+    lpmp_plan_peer_minima, the fourth call with a ``why``, fills it with the obstacle on SUCCESS and is held to the same bounds."""
+    p = E.Plan(_toy())
+    for (name, code), call in _info_calls(p).items():
+        buf = C.create_string_buffer(b"?" * 511, 512)
+        assert call(buf, 512) == code, (name, code)
+        text = p.L.lpmp_last_error()
+        assert text and buf.value == text and name.encode() in text, (name, code, buf.value, text)
+        short = C.create_string_buffer(b"?" * 15, 16)
+        assert call(short, 8) == code and short.raw == text[:7] + b"\0" + b"?" * 7 + b"\0", (name, code, short.raw)
+        none = C.create_string_buffer(b"?" * 15, 16)
+        assert call(none, 0) == code and none.raw == b"?" * 15 + b"\0", (name, code, none.raw)
+        assert call(None, 512) == code and p.L.lpmp_last_error() == text, (name, code)
+    full = C.create_string_buffer(b"?" * 255, 256)
+    assert p.L.lpmp_plan_peer_minima(p.h, M.REPAM_ANISOTROPIC, full, 256) == 0 and full.value and full.value != b"?" * 255
+    short = C.create_string_buffer(b"?" * 15, 16)
+    assert p.L.lpmp_plan_peer_minima(p.h, M.REPAM_ANISOTROPIC, short, 8) == 0 and short.raw == full.value[:7] + b"\0" + b"?" * 7 + b"\0"
+    none = C.create_string_buffer(b"?" * 15, 16)
+    assert p.L.lpmp_plan_peer_minima(p.h, M.REPAM_ANISOTROPIC, none, 0) == 0 and none.raw == b"?" * 15 + b"\0"
+    assert p.L.lpmp_plan_peer_minima(p.h, M.REPAM_ANISOTROPIC, None, 256) == 0

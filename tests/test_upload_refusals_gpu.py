@@ -1,4 +1,4 @@
-"""lpmp_upload_model builds the new model as a value and commits it at the end (csrc/engine.cpp, ModelState): a refused upload leaves
+"""lpmp_upload_model builds the new model as a value and commits it at the end (csrc/engine.cpp; ModelState, csrc/engine_state.hpp): a refused upload leaves
 NO model at whatever point it is refused, the engine's settings survive it, and nothing of an earlier model survives the next one.
 Every case compares the engine that went through the refusal (or through a larger model) with a freshly created engine given the
 same calls: duals, bound and labels bit for bit.  Model: a 4 x 4 grid with 3 labels and dense pairwise tables."""

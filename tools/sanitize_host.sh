@@ -8,7 +8,7 @@
 cd "$(dirname "$0")/.." || exit 1
 OUT=${1:-profiles/r05_sanitizers_host.txt}
 mkdir -p build/exp
-SRC="kernels.hip engine.cpp plan.cpp chain_plan.cpp order.cpp boundary.hip graph.cpp"
+SRC="kernels.hip engine.cpp prepared.cpp plan.cpp chain_plan.cpp order.cpp boundary.hip graph.cpp"
 FLAGS="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -shared -ffp-contract=off -fno-strict-aliasing -fno-omit-frame-pointer -Wno-unused-function"
 RT=$(dirname "$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)")
 FILES="tests/test_plan_host.py tests/test_graph_host.py tests/test_partitioners.py tests/test_lockstep.py tests/test_overlap.py tests/test_multi_gpu.py tests/test_lp_mirror.py tests/test_bench_contract.py tests/test_oracle_ref.py"
