@@ -531,7 +531,8 @@ void run_schedule(lpmp_engine* e, DevSchedule& s) {
       ChainTrace tr;
       ChainArgs ca = chain_args(e, c, c.tickets, tr.begin(c.tickets, e->stream));
       ca.mailbox = c.mailbox;
-      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->model.nt_flag) | e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->model.d_primal, e->stream))
+      if (!launch_chain(c.kclass, rule | (c.banded ? 0 : e->model.nt_flag) | e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, e->model.d_primal, e->stream,
+                        nullptr, 1, false, 2, false, ChainAhead(), e->chain_max_wgs))
         throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
       tr.end(c, e->stream, e->d_chain_abort);
     }
@@ -724,6 +725,13 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   const int64_t N = (int64_t)jt.tk_launch.size();
   const size_t n_done = periodic ? (size_t)jt.ring : (size_t)N;
   rc.dev_bytes = lds.size() * sizeof(ChainLaunch) + (jt.tk_launch.size() + jt.tk_block.size() + jt.dep_off.size() + jt.dep.size() + n_done + 1) * sizeof(int32_t);
+  // tickets ahead: the shipped peer-minima form only, and only while the launch table fits the kernel's LDS copy.  The descriptors
+  // are device bytes of the cached chain like its other arrays, counted before the cache makes room; a chain that fits the cache's
+  // bound only without them is built plain
+  int ahead = pq && e->pq_ahead != 0 && pq_ahead_applies(e->pq_lds, e->pq_hold, wide, e->pq_scatter, (int)lds.size()) ? e->pq_ahead : 0;
+  const size_t desc_bytes = (size_t)N * TICKET_DESC_WORDS * sizeof(int32_t);
+  if (ahead && rc.dev_bytes <= e->rot_cache_limit && rc.dev_bytes + desc_bytes > e->rot_cache_limit) ahead = 0;
+  if (ahead) rc.dev_bytes += desc_bytes;
   // bound the cache in bytes: drop the least recently used built chains (of any mode) until the new one fits; the stream is drained first
   for (bool drained = false; e->model.rot_cache_bytes + rc.dev_bytes > e->rot_cache_limit;) {
     std::map<int, RotChain>* vm = nullptr; std::map<int, RotChain>::iterator victim;
@@ -735,8 +743,16 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
     e->model.rot_cache_bytes -= std::min(e->model.rot_cache_bytes, victim->second.dev_bytes);
     vm->erase(victim);
   }
+  std::vector<int32_t> desc;
+  if (ahead) desc = ticket_descriptors(jt.tk_launch, jt.tk_block, jt.dep_off, jt.dep, e->pq_desc_inline);
   try {
     rc.dc = upload_chain(lds, jt.tk_launch, jt.tk_block, jt.dep_off, jt.dep, n_done, e->stream);
+    if (ahead) {
+      rc.dc.desc.alloc(std::max<size_t>(1, desc.size()));
+      if (!desc.empty()) h2d(rc.dc.desc, desc.data(), desc.size() * sizeof(int32_t), e->stream);
+      rc.dc.desc_inline = e->pq_desc_inline;
+    }
+    rc.dc.n_launches = (int32_t)lds.size();
     HIP_CHECK(hipStreamSynchronize(e->stream));
   } catch (...) {
     // nothing half-built stays behind: the entry goes (a later call tries again), the bytes were never counted
@@ -746,16 +762,24 @@ RotChain* rotation_chain(lpmp_engine* e, int mode, int n_call) {
   rc.dc.kclass = ri.kclass;
   e->model.rot_cache_bytes += rc.dev_bytes;
   ++e->model.schedules_built;
-  rc.peer_minima = pq; rc.pq_wide = pq && wide;
+  rc.peer_minima = pq; rc.pq_wide = pq && wide; rc.pq_ahead = ahead;
   rc.n_steps = n_steps; rc.periodic = periodic; rc.n_tmpl = n; rc.depth = depth; rc.ring = jt.ring; rc.per_begin = jt.per_begin; rc.per_len = jt.per_len;
   if (verbose && pq) {
     int per_cu = 0;
     int num_regs = 0, scratch = 0;
     const bool three = e->pq_lds != 0 && e->pq_hold == 3;
-    const unsigned grid = chain_pq_grid(e->pq_lds, e->pq_hold, rc.pq_wide, e->pq_scatter, (int)std::min<int64_t>(N, INT32_MAX), &per_cu, &num_regs, &scratch);
+    const unsigned grid = chain_pq_grid(e->pq_lds, e->pq_hold, rc.pq_wide, e->pq_scatter, (int)std::min<int64_t>(N, INT32_MAX), &per_cu, &num_regs, &scratch, ahead, e->chain_max_wgs);
     std::fprintf(stderr, "lpmp:   peer minima launch (LPMP_PQ_LDS=%d, LPMP_PQ_WIDE=%d: %d records per consume ticket, %lld tickets): %d resident workgroups per CU, grid %u; "
                  "%d tables in registers, %d registers, %d bytes of scratch; publish: %s\n",
                  e->pq_lds, rc.pq_wide ? 1 : 0, ri.consume_gpb, (long long)N, per_cu, grid, three ? 3 : 2, num_regs, scratch, three && e->pq_scatter ? "reduce-scatter" : "all-reduce");
+    // (a line of its own: the line above is matched to its end by tests that were written before this form existed)
+    std::fprintf(stderr, "lpmp:   peer minima launch; tickets: %s\n", ahead ? "ahead (a descriptor per ticket, the launch table in LDS)" : "plain");
+    // dependencies per ticket, and what the descriptors' inline part covers
+    const std::vector<int64_t> h = ticket_dep_histogram(jt.dep_off, TICKET_DESC_INLINE + 1);
+    std::string hs; int64_t in = 0;
+    for (size_t c = 0; c < h.size(); ++c) { hs += (c ? " " : "") + std::to_string(h[c]); if ((int)c <= e->pq_desc_inline) in += h[c]; }
+    std::fprintf(stderr, "lpmp:   dependencies per ticket (0 ... %d, more): %s; %.4f of the tickets within an inline cap of %d\n", TICKET_DESC_INLINE, hs.c_str(),
+                 N > 0 ? (double)in / (double)N : 1.0, e->pq_desc_inline);
   }
   if (verbose)
     std::fprintf(stderr, "lpmp: %d passes as one launch%s: %lld tickets, %d bands, lag %d, depth %d (reach %.1f MB of %.1f MB per band); built and uploaded in %.0f ms\n", n,
@@ -783,12 +807,14 @@ bool run_rotation_chain(lpmp_engine* e, int mode, int n, double* lb_hist = nullp
   const int32_t n_tickets = c.tickets + extra * rc->per_len;
   ChainArgs ca = chain_args(e, c, n_tickets, rc->periodic ? nullptr : tr.begin(c.tickets, e->stream));
   if (lb_hist) { ca.lb_hist = lb_hist; ca.hist_stride = e->model.plan->p.nf; ca.hist_rows = n - 1; }
+  ChainAhead ahead;
+  if (rc->pq_ahead) { ahead.desc = c.desc; ahead.desc_inline = c.desc_inline; ahead.n_launches = c.n_launches; ahead.form = rc->pq_ahead; }
   if (rc->periodic) { ca.per_begin = rc->per_begin; ca.per_len = rc->per_len; ca.per_count = 1 + extra; ca.per_row_shift = rc->depth / 2; ca.ring = rc->ring; }
   hipEvent_t a = nullptr, b = nullptr;
   if (e->timing) { a = e->get_event(); b = e->get_event(); HIP_CHECK(hipEventRecord(a, e->stream)); }
   // (plain table loads, not the streaming policy: the second reader of a table is meant to find it in the Infinity Cache)
   if (rc->peer_minima && !e->model.d_peerq.get()) throw std::runtime_error("rotation chain: the buffer of the published minima is gone");
-  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds, rc->pq_wide, e->pq_hold, e->pq_scatter)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
+  if (!launch_chain(c.kclass, e->model.tab_flag, ca, c.launches, e->model.d_dual, e->model.d_const, e->model.d_tabs, e->model.d_lb, nullptr, e->stream, rc->peer_minima ? e->model.d_peerq.get() : nullptr, e->pq_lds, rc->pq_wide, e->pq_hold, e->pq_scatter, ahead, e->chain_max_wgs)) throw DeviceError("chain executor: no kernel for class " + std::to_string(c.kclass));
   if (!rc->periodic) tr.end(c, e->stream, e->d_chain_abort);
   if (e->timing) {
     HIP_CHECK(hipEventRecord(b, e->stream));
@@ -1243,6 +1269,9 @@ int lpmp_create(int device, lpmp_engine** out) {
     if (const char* v = std::getenv("LPMP_PQ_HOLD")) e->pq_hold = v[0] == '2' ? 2 : 3;
     if (const char* v = std::getenv("LPMP_PQ_SCATTER")) e->pq_scatter = v[0] != '0';
     if (const char* v = std::getenv("LPMP_PQ_WIDE")) e->pq_wide = v[0] != '0';
+    if (const char* v = std::getenv("LPMP_PQ_AHEAD")) e->pq_ahead = v[0] == '0' ? 0 : v[0] == '2' ? 2 : 1;
+    if (const char* v = std::getenv("LPMP_PQ_DESC_INLINE")) e->pq_desc_inline = std::min(std::max(0, std::atoi(v)), TICKET_DESC_INLINE);
+    if (const char* v = std::getenv("LPMP_CHAIN_MAX_WGS")) e->chain_max_wgs = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("LPMP_PQ_TILES")) e->pq_tiles = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("LPMP_PQ_SUB")) e->pq_sub = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("LPMP_PQ_SUBLAG")) e->pq_sublag = std::max(0, std::atoi(v));

@@ -78,8 +78,12 @@ struct GraphExec {   // an instantiated graph, destroyed with its owner; move-on
 struct DevChain {
   int32_t kclass = 0, tickets = 0, epoch = 0;
   bool banded = false;                     // Infinity-Cache ticket order: plain table loads, not the streaming policy
-  bool level_loop = false; int32_t n_launches = 0;   // one workgroup walks the launches (tiny levels of a generic class)
+  bool level_loop = false;                 // one workgroup walks the launches (tiny levels of a generic class)
+  // entries of `launches`: what the level loop walks, and, set for every chain of joined passes (rotation_chain), what the kernel with
+  // tickets ahead copies to LDS (at most PQ_AHEAD_MAX_LAUNCHES)
+  int32_t n_launches = 0;
   DevBuf<ChainLaunch> launches; DevBuf<int32_t> tk_launch, tk_block, dep_off, dep, done, next;
+  DevBuf<int32_t> desc; int32_t desc_inline = 0;   // one descriptor per ticket (plan.hpp ticket_descriptors): the joined passes whose kernel takes tickets ahead
   DevBuf<unsigned long long> mailbox;      // tagged granules of the message vectors that travel between dependent records (chain_plan.cpp)
 };
 // what issue_launches reads of a schedule: its device arrays and a list of its launches
@@ -161,6 +165,7 @@ struct RotChain {
   bool periodic = false; int n_tmpl = 0, depth = 0; int32_t per_begin = 0, per_len = 0, ring = 0;
   bool peer_minima = false;       // the steps carry CHAIN_LAUNCH_PQ_* roles: launched with the engine's peerq buffer
   bool pq_wide = false;           // ... and the H / K / T blocks hold PQ_WIDE_RECORDS records (ModelState::rot_wide): the wide consume form
+  int pq_ahead = 0;               // ... and dc carries ticket descriptors: launched as chain_dense_pq_ahead_kernel (the engine's pq_ahead value)
   int64_t per_factors = 0, per_recv = 0, per_bytes = 0;
 };
 // the order of a mode's joined passes (order.cpp): its window, computed once, and its tiles, grown the first time a call wants them
@@ -254,6 +259,10 @@ struct ModelState {
   int mode = -1;
   // the ticket lists of a pass count are device memory (C3, 32 passes: ~350 MB): the cache of built chains is bounded in BYTES
   // over all modes (the engine's rot_cache_limit; least recently used first), lpmp_chain_cache_bytes reports it
+  // A chain whose kernel takes tickets ahead also holds one 64-byte descriptor per template ticket (DevChain::desc), two to three
+  // times its other ticket arrays together: the headline's 20-pass template has 2.42 M tickets with 13.2 M dependencies, 155 MB of
+  // descriptors beside 82 MB of ticket lists.  They are counted here before the cache makes room; a chain that fits the limit only without them
+  // is built plain (rotation_chain)
   size_t rot_cache_bytes = 0;
   std::map<int, RotChain> rot_chain[LPMP_REPAM_COUNT];
   // (per form as well as per mode: the window and a TileSet are sized by block counts — [1]: the wide consume form, rot_wide)
@@ -333,6 +342,11 @@ struct lpmp_engine {
   bool use_peer_minima = true;        // LPMP_NO_PEER_MINIMA=1: every joined launch in the old form (ModelState::d_peerq)
   int pq_lds = 1;                 // LPMP_PQ_LDS: the publishing records' form (kernels.hpp launch_chain)
   bool pq_scatter = true;         // LPMP_PQ_SCATTER: the three-table form publishes a table's row minima with a reduce-scatter (0: eight row all-reduces)
+  // LPMP_PQ_AHEAD: 1 = a ticket of the shipped peer-minima form starts from a descriptor fetched during the ticket before
+  // (kernels.hpp launch_chain), 0 = the kernels and tables without it, 2 = 1 with the consume records' old preload (measurements);
+  // LPMP_PQ_DESC_INLINE: cap of the dependencies a descriptor holds inline (tests: 0 and 1 reach the path through dep[])
+  int pq_ahead = 1, pq_desc_inline = TICKET_DESC_INLINE;
+  int chain_max_wgs = 0;          // LPMP_CHAIN_MAX_WGS: cap of a chain launch's grid (tests, tracing); 0: what is resident at once
   int pq_hold = 3;                // LPMP_PQ_HOLD: tables such a record holds in registers, 3 or 2 (pq_lds 0: always 2, none parked)
   bool pq_wide = true;            // LPMP_PQ_WIDE=0: the consuming records one per wave, four per ticket, on the plan's own block relations
   // the ticket order of the peer-minima launches (rotation_chain): LPMP_PQ_TILES=0 the order every other launch takes (band order, or

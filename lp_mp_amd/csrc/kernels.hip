@@ -188,6 +188,84 @@ __device__ __forceinline__ void chain_publish(const ChainArgs& ca, int ticket) {
   chain_stamp(ca, ticket, 3);                      // published
 }
 
+// ---- tickets ahead (chain_loop_roles_ahead, chain_dense_pq_ahead_kernel) -----------------------------------------------------------
+// What chain_wait collects in dependent round trips — dep_off[idx], then dep[i], then the flag — a ticket of that loop has in LDS
+// when it begins: its descriptor (ChainAhead::desc, plan.hpp ticket_descriptors), fetched by wave 0 during the ticket before.  The
+// wait is therefore split: chain_poll_issue requests the FIRST poll of every predecessor's flag right behind the packet request,
+// chain_wait_polled looks at the answers after the tables have been requested and keeps polling only where a flag was not yet set.
+// The same bounds and abort words as chain_wait; the invariant above chain_publish holds as it stands: descriptors and packets are
+// constants written before the launch (plain loads), flags take agent-scope loads, duals are requested after the flags were seen.
+struct PqAhead {
+  const ChainAhead* aa;     // the launch's descriptors
+  const int* desc;          // LDS: this ticket's descriptor
+  int copy;                 // its copy of the period (chain_ticket_ref)
+  int next;                 // thread 0: the number drawn for the next ticket — the atomic's result, awaited in chain_wait_polled
+  int word;                 // lanes 0-15 of wave 0: their word of the next ticket's descriptor, awaited behind the body
+  int* s_next;              // LDS: where the next ticket's number goes
+  int* s_bad;               // LDS: set by a wait that gave up (the loop clears it behind the publish)
+  int d, v;                 // this thread's first predecessor and the flag word of its first poll (d < 0: none)
+};
+__device__ __forceinline__ int chain_flag_word(const ChainArgs& ca, int dep_ticket) {
+  return __hip_atomic_load(ca.done + (ca.ring ? dep_ticket % ca.ring : dep_ticket), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool chain_flag_word_set(const ChainArgs& ca, int dep_ticket, int v) {   // chain_flag_set on a word already read
+  if (ca.ring == 0) return v == ca.epoch;
+  return (v >> CHAIN_GEN_BITS) == ca.epoch && (v & ((1 << CHAIN_GEN_BITS) - 1)) >= dep_ticket / ca.ring;
+}
+// predecessor i of the ticket: inline, from dep[] behind the inline ones, or (i == n) the ring predecessor
+__device__ __forceinline__ int chain_desc_dep(const ChainArgs& ca, const PqAhead& ah, int ticket, int i, int n, int n_inline) {
+  if (i >= n) return ticket - ca.ring;
+  const int d = i < n_inline ? ah.desc[TD_DEPS + i] : ca.dep[ah.desc[TD_REST] + (i - n_inline)];
+  return d + ah.copy * ca.per_len;
+}
+// all threads: thread i requests the flag of predecessor i.  A ticket with more dependencies than the descriptor holds inline takes
+// the round trip through dep[] here, behind a branch the whole workgroup agrees on, so that the others wait for nothing
+__device__ __forceinline__ void chain_poll_issue(const ChainArgs& ca, int ticket, PqAhead& ah) {
+  const int n = __builtin_amdgcn_readfirstlane(ah.desc[TD_NDEPS]);
+  const int n_inline = min(n, ah.aa->desc_inline);
+  const int total = n + ((ca.ring > 0 && ticket >= ca.ring) ? 1 : 0);
+  const int i = (int)threadIdx.x;
+  ah.d = -1; ah.v = 0;
+  if (i < n_inline) ah.d = ah.desc[TD_DEPS + i] + ah.copy * ca.per_len;
+  else if (i >= n && i < total) ah.d = ticket - ca.ring;
+  if (n > n_inline) { if (i >= n_inline && i < n) ah.d = ca.dep[ah.desc[TD_REST] + (i - n_inline)] + ah.copy * ca.per_len; }
+  if (ah.d >= 0) ah.v = chain_flag_word(ca, ah.d);
+}
+// all threads; returns false when the run was aborted.  Behind the barrier wave 0 takes the next ticket's number, which the atomic
+// has had the whole wait to return, puts it down for the next iteration and requests that ticket's descriptor, a word per lane
+__device__ __forceinline__ bool chain_wait_polled(const ChainArgs& ca, int ticket, PqAhead& ah) {
+  const int n = __builtin_amdgcn_readfirstlane(ah.desc[TD_NDEPS]);
+  const int n_inline = min(n, ah.aa->desc_inline);
+  const int total = n + ((ca.ring > 0 && ticket >= ca.ring) ? 1 : 0);
+  bool first = true;
+  // (a second trip of this loop, through chain_desc_dep, needs a ticket with more predecessors than the workgroup has threads: no
+  // template the planner builds has one — the headline's tickets have at most 8 and the ring's — and no test reaches it.  It is
+  // kept, with chain_wait's striding, so that the descriptor format sets no cap of its own on a ticket's dependency count)
+  for (int i = (int)threadIdx.x; i < total; i += (int)blockDim.x) {
+    const int d = first ? ah.d : chain_desc_dep(ca, ah, ticket, i, n, n_inline);
+    bool set = first ? chain_flag_word_set(ca, d, ah.v) : chain_flag_set(ca, d);
+    first = false;
+    int spins = 0; long long t0 = 0; bool own;
+    while (!set) {
+      chain_poll_pause(spins);
+      if (chain_wait_expired(ca, ++spins, t0, own)) {
+        chain_abort(ca, own, ticket, d, chain_flag_word(ca, d), t0);
+        *ah.s_bad = 1;
+        break;
+      }
+      set = chain_flag_set(ca, d);
+    }
+  }
+  __syncthreads();
+  chain_stamp(ca, ticket, 1);                      // predecessors seen
+  if (threadIdx.x < 64) {
+    const int nt = __builtin_amdgcn_readfirstlane(ah.next);
+    if (threadIdx.x == 0) *ah.s_next = nt;
+    if (nt < ca.n_tickets && threadIdx.x < TICKET_DESC_WORDS) ah.word = ah.aa->desc[(int64_t)chain_ticket_ref(ca, nt).idx * TICKET_DESC_WORDS + threadIdx.x];
+  }
+  return *ah.s_bad == 0;
+}
+
 
 // Mailbox of a dense chain (chain_plan.cpp decides which vectors travel this way): the value a send has just computed, as two
 // self-validating 8-byte granules {half of the double, epoch of the running launch}.  An aligned 8-byte access is atomic,
@@ -771,6 +849,20 @@ __device__ __forceinline__ void load_packet(double2_t* slab, const Op* __restric
   }
 }
 
+// load_packet in packet mode (stride > 0) with `between` issued while the packet is in flight: loads return in the order they were
+// requested, so taking the packet does not wait for what `between` asked for
+template <int G, class F>
+__device__ __forceinline__ void load_packet_then(double2_t* slab, const Op* __restrict__ packets, int64_t idx, int stride, bool live, int g, F between) {
+  const bool has = live && g < 3 * stride;
+  const double2_t* src = reinterpret_cast<const double2_t*>(packets + (live ? idx * stride : 0));
+  double2_t first = double2_t{0.0, 0.0};
+  if (has) first = src[g];
+  between();
+  if (has) slab[g] = first;
+  if (live) for (int p = g + G; p < 3 * stride; p += G) slab[p] = src[p];
+  wave_sync();
+}
+
 // VAR: L is the padded width; the label count of the factor (<= L) and the dims of each peer table (d0 x d1, both
 // <= L, the own side's equal to the label count) are read at run time, lanes beyond them carry +inf / 0
 // NT: streaming policy of the table loads.  A: access policy of the duals.  CHAIN: called from the chain executor with a
@@ -1326,7 +1418,8 @@ __device__ __forceinline__ void chain_loop(const ChainArgs& ca, const ChainLaunc
 // ticket (tools/chain_trace.py: t1 - t0), more than a level.  Here the first thread draws ticket numbers TWO iterations
 // ahead and fetches the fields of the next ticket while the current one is processed: all of it returns during the body and
 // is put down in LDS after it.  (A workgroup runs its tickets in increasing order, so the lowest unfinished ticket of the
-// launch is always one that is running: drawing ahead cannot deadlock.)  Costs registers: not for the joined passes.
+// launch is always one that is running: drawing ahead cannot deadlock.)  Costs registers: the joined passes of the shared dense body
+// (167-171 VGPRs) have none to spare; the peer-minima form has, and takes a loop of its own (chain_loop_roles_ahead).
 template <class Body>
 __device__ __forceinline__ void chain_loop_ahead(const ChainArgs& ca, const ChainLaunch* __restrict__ launches, Body body) {
   __shared__ int s_tk[3][4];                       // ticket, launch, block, number of dependencies
@@ -1436,11 +1529,13 @@ struct PqRec {
 };
 // G: lanes per record.  64: a wave per record, the fields are wave-uniform scalars.  32 (consume records only, PQ_CG): two records
 // per wave, every field a per-lane value read from the half-wave's own slab
-template <int L, int G = 64>
+// AH (tickets ahead): the first polls of the ticket's predecessors go out while the packet is in flight
+template <int L, int G = 64, bool AH = false>
 __device__ __forceinline__ void pq_load_rec(PqRec& r, double2_t* slab, const Op* __restrict__ packets, double* __restrict__ dual, int64_t idx, int64_t count,
-                                            int stride, int g) {
+                                            int stride, int g, const ChainArgs* ca = nullptr, int ticket = 0, PqAhead* ah = nullptr) {
   r.live = idx < count;
-  load_packet<G>(slab, packets, nullptr, nullptr, idx, stride, r.live, g);
+  if constexpr (AH) load_packet_then<G>(slab, packets, idx, stride, r.live, g, [&] { chain_poll_issue(*ca, ticket, *ah); });
+  else load_packet<G>(slab, packets, nullptr, nullptr, idx, stride, r.live, g);
   r.hdr = reinterpret_cast<const UpdRec*>(&slab[0]);
   r.lop = reinterpret_cast<const Op*>(&slab[3]);
   r.n_recv = r.live ? min(uni<G>((int)r.hdr->n_recv), PQ_OPS) : 0;
@@ -1474,10 +1569,13 @@ __device__ __forceinline__ void pq_load_rec(PqRec& r, double2_t* slab, const Op*
 // preload_ok — so nothing that moves data across lanes (vec_min: DPP, shuffles) sits in a branch only one half takes: the
 // reductions run for all four receives on every lane (+inf where there is none) and only the loads and stores are guarded.
 // Per lane the arithmetic and the order of its statements are those of the 64-lane form.
-template <int L, int G>
+// AH: a ticket of chain_loop_roles_ahead (its wait is chain_poll_issue / chain_wait_polled).  LIVE_SM (that loop's instantiation
+// only): a send's own vector is preloaded only where the send uses it (s_fw == 0) — one that forwards a receive takes mnew instead,
+// and every K / H / T send of a grid does.  Per lane the statements and the bits are unchanged.
+template <int L, int G, bool AH = false, bool LIVE_SM = false>
 __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ packets, double* __restrict__ dual, double* __restrict__ lb,
                                                       const double* __restrict__ peerq, int64_t count, int stride, int64_t block,
-                                                      const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
+                                                      const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode, PqAhead* ah = nullptr) {
   static_assert(G == 64 || (G == 32 && L == 32), "a wave or half a wave per record");
   constexpr int GPB = 256 / G, A = ACC_COH;
   __shared__ double2_t lds_pk[GPB][3 * (1 + PK_MAX_OPS)];
@@ -1487,12 +1585,14 @@ __device__ __forceinline__ void dense_pq_consume_body(const Op* __restrict__ pac
   if constexpr (G == 32) asm volatile("" : "+v"(tid));
   const int grp = tid / G, g = tid % G;
   PqRec r;
-  pq_load_rec<L, G>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g);
-  const bool aborted = !chain_wait(*ca, ticket);
+  pq_load_rec<L, G, AH>(r, lds_pk[grp], packets, dual, block * GPB + grp, count, stride, g, ca, ticket, ah);
+  bool aborted;
+  if constexpr (AH) aborted = !chain_wait_polled(*ca, ticket, *ah);
+  else aborted = !chain_wait(*ca, ticket);
   double theta = r.vl ? ld_dual<A>(r.own_g + g) : 0.0;
   double sm[PQ_OPS], msv[PQ_OPS], qv[PQ_OPS], mnew[PQ_OPS];
 #pragma unroll
-  for (int k = 0; k < PQ_OPS; ++k) { sm[k] = 0.0; if (r.preload_ok && k < r.n_send && g < L) sm[k] = ld_dual<A>(r.s_ms[k] + g); }
+  for (int k = 0; k < PQ_OPS; ++k) { sm[k] = 0.0; if (r.preload_ok && k < r.n_send && g < L && (!LIVE_SM || r.s_fw[k] == 0)) sm[k] = ld_dual<A>(r.s_ms[k] + g); }
 #pragma unroll
   for (int j = 0; j < PQ_OPS; ++j) {
     msv[j] = 0.0; qv[j] = 0.0; mnew[j] = 0.0;
@@ -1746,10 +1846,11 @@ __device__ __forceinline__ void dense_pq_publish_body(const Op* __restrict__ pac
 // in > 40 SGPRs, and the kernel is at the SGPR cap), and the vectors m_o, then m_new, then m' of receive j share row j of lds_mv —
 // the reductions read the row directly, the send picks its row by the run-time forward index instead of a select chain that keeps
 // four vectors live.  Per lane the floating-point statements and their order are those of dense_pq_publish_body.
-template <int L, bool SC = false>
+// AH: a ticket of chain_loop_roles_ahead — packet requested, first flag polls issued, packet taken, tables requested, polls looked at
+template <int L, bool SC = false, bool AH = false>
 __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ packets, double* __restrict__ dual, const double* __restrict__ cdata,
                                                        double* __restrict__ lb, double* __restrict__ peerq, int64_t count, int stride, int64_t block,
-                                                       const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode) {
+                                                       const ChainArgs* ca, int ticket, double* __restrict__ lbh, int hmode, PqAhead* ah = nullptr) {
   static_assert(L == 32, "the exact 32-label class");
   constexpr int G = 64, GPB = 256 / G, A = ACC_COH, KM = 3;
   constexpr int CL = L / 2, RPL = 2 * G / L, NL = L / RPL;
@@ -1760,7 +1861,8 @@ __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ pa
   const int c2 = g % CL, rl = g / CL;
   const int64_t idx = block * GPB + grp;
   const bool live = idx < count;
-  load_packet<G>(lds_pk[grp], packets, nullptr, nullptr, idx, stride, live, g);
+  if constexpr (AH) load_packet_then<G>(lds_pk[grp], packets, idx, stride, live, g, [&] { chain_poll_issue(*ca, ticket, *ah); });
+  else load_packet<G>(lds_pk[grp], packets, nullptr, nullptr, idx, stride, live, g);
   const UpdRec* const hdr = reinterpret_cast<const UpdRec*>(&lds_pk[grp][0]);
   const Op* const lop = reinterpret_cast<const Op*>(&lds_pk[grp][3]);
   const int n_recv = live ? min(uni<G>((int)hdr->n_recv), PQ_OPS) : 0;
@@ -1831,7 +1933,9 @@ __device__ __forceinline__ void dense_pq_publish3_body(const Op* __restrict__ pa
       for (int i = 0; i < NL; ++i) t[j][i] = double2_t{0.0, 0.0};
     }
   }
-  const bool aborted = !chain_wait(*ca, ticket);
+  bool aborted;
+  if constexpr (AH) aborted = !chain_wait_polled(*ca, ticket, *ah);
+  else aborted = !chain_wait(*ca, ticket);
   double* const own_g = dual + (live ? uni64<G>(hdr->dual_off) : 0);
   double theta = vl ? ld_dual<A>(own_g + g) : 0.0;
   double msv[PQ_OPS], mov[PQ_OPS];
@@ -1972,6 +2076,68 @@ chain_dense_pq_scatter_kernel(ChainArgs ca, const ChainLaunch* __restrict__ laun
     double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
     if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish3_body<L, true>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
     else dense_pq_consume_body<L, CG>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode);
+  });
+}
+
+// chain_loop_roles with the next ticket's descriptor fetched during the current body (the joined passes had no register for it at
+// 167-171 VGPRs; the three-table form has: it costs the one VGPR of the descriptor word and the drawn number).  Ticket numbers are
+// drawn exactly where chain_loop_roles draws them, one ahead, but the atomic's result stays in a register of thread 0 until the
+// wait's barrier (chain_wait_polled), where wave 0 puts it down and requests that ticket's descriptor, one word per lane; the word
+// lands in s_desc behind the body.  The call's launch table (ChainAhead::n_launches <= PQ_AHEAD_MAX_LAUNCHES entries) is copied to
+// LDS once per workgroup, so a ticket's ChainLaunch costs no round trip either.  A ticket thus begins with everything but its
+// packet in LDS.  s_desc / s_ticket [(it + 1) & 1] were last read in iteration it - 1, two barriers ago.
+template <class Body>
+__device__ __forceinline__ void chain_loop_roles_ahead(const ChainArgs& ca, const ChainAhead& aa, const ChainLaunch* __restrict__ launches, Body body) {
+  __shared__ int s_ticket[2];
+  __shared__ int s_desc[2][TICKET_DESC_WORDS];
+  __shared__ int s_bad;
+  __shared__ long long s_ln[PQ_AHEAD_MAX_LAUNCHES * (sizeof(ChainLaunch) / 8)];
+  constexpr int LW = (int)(sizeof(ChainLaunch) / 8);
+  for (int i = (int)threadIdx.x; i < aa.n_launches * LW; i += (int)blockDim.x) s_ln[i] = reinterpret_cast<const long long*>(launches)[i];
+  if (threadIdx.x == 0) { s_ticket[0] = atomicAdd(ca.next, 1); s_bad = 0; }
+  __syncthreads();
+  {
+    const int t = s_ticket[0];
+    if (t < ca.n_tickets && threadIdx.x < TICKET_DESC_WORDS) s_desc[0][threadIdx.x] = aa.desc[(int64_t)chain_ticket_ref(ca, t).idx * TICKET_DESC_WORDS + threadIdx.x];
+  }
+  __syncthreads();
+  for (int it = 0;; ++it) {
+    const int ticket = s_ticket[it & 1];
+    if (ticket >= ca.n_tickets) break;
+    PqAhead ah;
+    ah.aa = &aa; ah.next = 0; ah.word = 0;
+    if (threadIdx.x == 0) ah.next = atomicAdd(ca.next, 1);
+    chain_stamp(ca, ticket, 0);
+    ah.desc = s_desc[it & 1]; ah.copy = chain_ticket_ref(ca, ticket).copy;
+    ah.s_next = &s_ticket[(it + 1) & 1]; ah.s_bad = &s_bad;
+    const long long* lw = s_ln + (ah.desc[TD_LAUNCH] + ah.copy * ca.per_launch_shift) * LW;
+    ChainLaunch ln;
+    ln.packets = reinterpret_cast<const Op*>(lw[0]); ln.recs = reinterpret_cast<const UpdRec*>(lw[1]); ln.ops = reinterpret_cast<const Op*>(lw[2]);
+    ln.count = lw[3]; ln.stride = (int32_t)(lw[4] & 0xffffffffLL); ln.pad = (int32_t)(lw[4] >> 32);
+    const int role = ln.pad & CHAIN_LAUNCH_PQ_MASK;
+    ln.pad &= ~CHAIN_LAUNCH_PQ_MASK;
+    if (ln.pad & 3) {
+      ln.pad += (ah.copy * ca.per_row_shift) << 2;
+      if ((ln.pad >> 2) >= ca.hist_rows) ln.pad = 0;
+    }
+    body(ln, (int64_t)ah.desc[TD_BLOCK], ticket, role, ah);
+    if (threadIdx.x < TICKET_DESC_WORDS) s_desc[(it + 1) & 1][threadIdx.x] = ah.word;
+    chain_publish(ca, ticket);
+    if (threadIdx.x == 0) s_bad = 0;               // (every thread has read it: the publish has a barrier)
+    __syncthreads();
+  }
+}
+static_assert(sizeof(ChainLaunch) == 40 && offsetof(ChainLaunch, count) == 24 && offsetof(ChainLaunch, stride) == 32 && offsetof(ChainLaunch, pad) == 36, "chain_loop_roles_ahead reads a ChainLaunch as five 8-byte words");
+// chain_dense_pq_scatter_kernel<L, 32> on that loop; LIVE_SM: dense_pq_consume_body (false: measurements, LPMP_PQ_AHEAD=2)
+template <int L, int CG, bool LIVE_SM>
+__global__ void __launch_bounds__(256, 3)
+chain_dense_pq_ahead_kernel(ChainArgs ca, ChainAhead aa, const ChainLaunch* __restrict__ launches, double* __restrict__ dual, const double* __restrict__ cdata,
+                            double* __restrict__ lb, double* __restrict__ peerq) {
+  chain_loop_roles_ahead(ca, aa, launches, [&](const ChainLaunch& ln, int64_t block, int ticket, int role, PqAhead& ah) {
+    const int hmode = ca.lb_hist ? (ln.pad & 3) : 0;
+    double* lbh = hmode ? ca.lb_hist + (int64_t)(ln.pad >> 2) * ca.hist_stride : nullptr;
+    if (role == CHAIN_LAUNCH_PQ_PUBLISH) dense_pq_publish3_body<L, true, true>(ln.packets, dual, cdata, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode, &ah);
+    else dense_pq_consume_body<L, CG, true, LIVE_SM>(ln.packets, dual, lb, peerq, ln.count, ln.stride, block, &ca, ticket, lbh, hmode, &ah);
   });
 }
 
@@ -4188,13 +4354,14 @@ bool launch_sweep_shared(int kclass, const Op* packets, const UpdRec* recs, cons
 // chain executor: one persistent launch for a deep single-class schedule; grid = what is resident at once (more
 // workgroups would only queue behind the running ones).  Returns false for a class without a chain kernel.
 template <class K>
-static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_cu_out = nullptr) {
+static unsigned chain_grid(K kernel, int n_tickets, int threads = 256, int* per_cu_out = nullptr, int max_wgs = 0) {
   int di = 0;
   const int n_cu = device_cu_count(di);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
   if (per_cu_out) *per_cu_out = per_cu;
-  const long cap = (long)n_cu * per_cu;
+  long cap = (long)n_cu * per_cu;
+  if (max_wgs > 0 && max_wgs < cap) cap = max_wgs;
   return (unsigned)(n_tickets < cap ? n_tickets : cap);
 }
 // what launch_chain will launch for a peer-minima chain of n_tickets (LPMP_ROT_VERBOSE, engine.cpp)
@@ -4205,14 +4372,16 @@ static auto with_pq_kernel(int pq_lds, int pq_hold, bool wide, bool scatter, F f
   if (wide) return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM, 0, 32>) : f(chain_dense_pq_kernel<32, PQ_KM, 1, 32>);
   return pq_lds == 0 ? f(chain_dense_pq_kernel<32, PQ_KM>) : f(chain_dense_pq_kernel<32, PQ_KM, 1>);
 }
-unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs, int* scratch_bytes) {
-  return with_pq_kernel(pq_lds, pq_hold, pq_wide, pq_scatter, [&](auto k) {
+unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs, int* scratch_bytes, int pq_ahead, int max_wgs) {
+  auto report = [&](auto k) {
     hipFuncAttributes fa{};
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k)) != hipSuccess) { (void)hipGetLastError(); fa.numRegs = -1; fa.localSizeBytes = (size_t)-1; }
     if (num_regs) *num_regs = fa.numRegs;
     if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
-    return chain_grid(k, n_tickets, 256, per_cu);
-  });
+    return chain_grid(k, n_tickets, 256, per_cu, max_wgs);
+  };
+  if (pq_ahead != 0 && pq_ahead_applies(pq_lds, pq_hold, pq_wide, pq_scatter, 0)) return pq_ahead == 2 ? report(chain_dense_pq_ahead_kernel<32, 32, false>) : report(chain_dense_pq_ahead_kernel<32, 32, true>);
+  return with_pq_kernel(pq_lds, pq_hold, pq_wide, pq_scatter, report);
 }
 void debug_set_level_trace(long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_level_trace), &p, sizeof(p)); }
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launches, double* dual, const double* cdata,
@@ -4223,15 +4392,22 @@ bool launch_level_loop(int kclass, int flags, const ChainLaunch* ln, int n_launc
   return true;
 }
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* ln, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide, int pq_hold, bool pq_scatter) {
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq, int pq_lds, bool pq_wide, int pq_hold, bool pq_scatter,
+                  const ChainAhead& ahead, int max_wgs) {
   const bool nt = (flags & SWEEP_NT) != 0, mailbox = ca.mailbox != nullptr, t32 = (flags & SWEEP_TAB32) != 0;
   if (peerq) {   // joined passes with peer minima: no other class, table format or send rule has the form
     if (kclass != KC_DENSE_32 || flags != 0 || mailbox) return false;
-    auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
+    if (ahead.form != 0) {   // (the engine asks for it only where it applies)
+      if (!ahead.desc || !pq_ahead_applies(pq_lds, pq_hold, pq_wide, pq_scatter, ahead.n_launches)) return false;
+      auto k = ahead.form == 2 ? chain_dense_pq_ahead_kernel<32, 32, false> : chain_dense_pq_ahead_kernel<32, 32, true>;
+      hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, 256, nullptr, max_wgs)), dim3(256), 0, s, ca, ahead, ln, dual, cdata, lb, peerq);
+      return true;
+    }
+    auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, 256, nullptr, max_wgs)), dim3(256), 0, s, ca, ln, dual, cdata, lb, peerq); return true; };
     return with_pq_kernel(pq_lds, pq_hold, pq_wide, pq_scatter, go);
   }
-  auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
-  auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
+  auto packed = [&](auto k) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, 256, nullptr, max_wgs)), dim3(256), 0, s, ca, ln, dual, cdata, lb, primal, flags); return true; };
+  auto generic = [&](auto k, int threads) { hipLaunchKernelGGL(k, dim3(chain_grid(k, ca.n_tickets, threads, nullptr, max_wgs)), dim3(threads), 0, s, ca, ln, dual, cdata, tabs, lb, flags); return true; };
   if (kclass == KC_GENERIC) return generic(chain_generic_kernel<64>, GenCtx<64>::THREADS);
   if (kclass == KC_SMALL) return generic(chain_generic_kernel<1>, GenCtx<1>::THREADS);
   return with_class(kclass, [&](auto fam, auto width, auto var) {

@@ -48,6 +48,13 @@ struct ChainArgs {
   // published there (one more dependency of t), and a waiter accepts any generation >= the one it needs
   int32_t ring;
 };
+// tickets ahead (chain_dense_pq_ahead_kernel): one descriptor of TICKET_DESC_WORDS words per TEMPLATE ticket (plan.hpp
+// ticket_descriptors) built with an inline cap of desc_inline, and the number of entries of the launch table, which that kernel
+// keeps in LDS (at most PQ_AHEAD_MAX_LAUNCHES).  A kernel argument of its own and not a part of ChainArgs: every other chain kernel
+// keeps its argument layout and with it its code.  form: 0 = not asked for (launch_chain: the other kernels); 1 = that kernel;
+// 2 = that kernel with the consume records' send vectors preloaded as in the other kernels (LPMP_PQ_AHEAD=2: measurements)
+struct ChainAhead { const int32_t* desc = nullptr; int32_t desc_inline = 0, n_launches = 0, form = 0; };
+constexpr int PQ_AHEAD_MAX_LAUNCHES = 128;   // 5 KiB of LDS: calls of up to 63 passes as explicit lists, every periodic template
 constexpr int CHAIN_GEN_BITS = 8;            // low bits of a ring slot: generation t / ring (< 256); the rest: the epoch
 constexpr int CHAIN_ABORT_WORDS = 16;        // abort word + what the first wait that gave up was waiting for (kernels.hip, chain_abort)
 // debugging (LPMP_LEVEL_TRACE, engine.cpp): time stamps of the first LEVEL_TRACE_MAX levels of a level-loop launch, 8 slots per level
@@ -156,11 +163,20 @@ void launch_sweep_diff(bool band, bool shift, const UpdRec* recs, const Op* ops,
 // 16-lane row (chain_dense_pq_scatter_kernel), false = eight row all-reduces (chain_dense_pq_kernel<32, 3, 1, *>); the two-table forms ignore it
 // pq_wide: the consuming records' form (LPMP_PQ_WIDE): true = two records per wave, PQ_WIDE_RECORDS per ticket — the launches'
 // H / K / T blocks must have been planned with that many records (order.cpp plan_rotation_chain, consume_gpb)
+// ahead (LPMP_PQ_AHEAD; form != 0): chain_dense_pq_ahead_kernel, the scatter form with wide consume records whose tickets start from
+// a descriptor fetched during the ticket before (pq_ahead_applies says which forms have it; false for the others)
+// max_wgs > 0 (LPMP_CHAIN_MAX_WGS): no chain launch has more workgroups.  Safe for any value >= 1: a ticket waits for lower tickets
+// only, and those are held by workgroups that are running
 bool launch_chain(int kclass, int flags, const ChainArgs& ca, const ChainLaunch* launches, double* dual, const double* cdata,
-                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr, int pq_lds = 1, bool pq_wide = false, int pq_hold = 2, bool pq_scatter = false);
+                  const int32_t* tabs, double* lb, int32_t* primal, hipStream_t s, double* peerq = nullptr, int pq_lds = 1, bool pq_wide = false, int pq_hold = 2, bool pq_scatter = false,
+                  const ChainAhead& ahead = ChainAhead(), int max_wgs = 0);
+inline bool pq_ahead_applies(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_launches) {
+  return pq_lds != 0 && pq_hold == 3 && pq_wide && pq_scatter && n_launches <= PQ_AHEAD_MAX_LAUNCHES;
+}
 // grid and resident workgroups per CU of that launch; num_regs / scratch_bytes: what hipFuncGetAttributes reports for its kernel
 // (numRegs, localSizeBytes; -1 when the query fails)
-unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs = nullptr, int* scratch_bytes = nullptr);
+unsigned chain_pq_grid(int pq_lds, int pq_hold, bool pq_wide, bool pq_scatter, int n_tickets, int* per_cu, int* num_regs = nullptr, int* scratch_bytes = nullptr,
+                       int pq_ahead = 0, int max_wgs = 0);   // pq_ahead: ChainAhead::form
 bool launch_level_loop(int kclass, int flags, const ChainLaunch* launches, int n_launches, double* dual, const double* cdata,
                        const int32_t* tabs, double* lb, hipStream_t s);
 void debug_set_level_trace(long long* p);

@@ -566,4 +566,25 @@ std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, i
   return "no band order keeps the dependencies backwards";
 }
 
+std::vector<int32_t> ticket_descriptors(const std::vector<int32_t>& tk_launch, const std::vector<int32_t>& tk_block, const std::vector<int32_t>& dep_off,
+                                        const std::vector<int32_t>& dep, int cap) {
+  const size_t N = tk_launch.size();
+  if (tk_block.size() != N || dep_off.size() != N + 1 || (N > 0 && (size_t)dep_off[N] != dep.size())) throw std::runtime_error("ticket descriptors: inconsistent ticket tables");
+  cap = std::min(std::max(cap, 0), TICKET_DESC_INLINE);
+  std::vector<int32_t> d(N * TICKET_DESC_WORDS, -1);
+  for (size_t t = 0; t < N; ++t) {
+    int32_t* w = d.data() + t * TICKET_DESC_WORDS;
+    const int32_t n = dep_off[t + 1] - dep_off[t], ni = std::min<int32_t>(n, cap);
+    w[TD_LAUNCH] = tk_launch[t]; w[TD_BLOCK] = tk_block[t]; w[TD_NDEPS] = n; w[TD_REST] = dep_off[t] + ni;
+    for (int32_t i = 0; i < ni; ++i) w[TD_DEPS + i] = dep[(size_t)dep_off[t] + i];
+  }
+  return d;
+}
+
+std::vector<int64_t> ticket_dep_histogram(const std::vector<int32_t>& dep_off, int max_count) {
+  std::vector<int64_t> h((size_t)std::max(max_count, 0) + 1, 0);
+  for (size_t t = 0; t + 1 < dep_off.size(); ++t) ++h[(size_t)std::min<int32_t>(dep_off[t + 1] - dep_off[t], (int32_t)h.size() - 1)];
+  return h;
+}
+
 }  // namespace lpmp

@@ -603,5 +603,17 @@ struct JoinedTables {
 // the tables of n joined passes (periodic: the template of n passes whose group 2 is the period; the depth must be even) — ""
 // or why the passes stay one launch per step; log (or nullptr): progress lines.  ri must be valid.
 std::string joined_pass_tables(const RotationInfo& ri, const JoinedOrder& ord, int n, bool periodic, JoinedTables& out, FILE* log);
+// One fixed-size descriptor per TEMPLATE ticket (the peer-minima kernel with tickets ahead, kernels.hip chain_loop_roles_ahead): what
+// a ticket otherwise collects from tk_launch, tk_block, dep_off and dep in dependent round trips, as one 64-byte record that 16 lanes
+// fetch with one word each.  Word TD_LAUNCH: the template launch; TD_BLOCK: the block; TD_NDEPS: the dependency count; TD_REST:
+// the position in dep[] where the dependencies that are not inline continue, dep_off[t] + min(count, cap); TD_DEPS ...: the first
+// min(count, cap) predecessor tickets, -1 behind them.  cap is clamped to [0, TICKET_DESC_INLINE].  The periodic arithmetic (copy,
+// shifts, ring predecessor) stays in the kernel: a descriptor describes a template ticket.
+constexpr int TICKET_DESC_WORDS = 16, TD_LAUNCH = 0, TD_BLOCK = 1, TD_NDEPS = 2, TD_REST = 3, TD_DEPS = 4;
+constexpr int TICKET_DESC_INLINE = TICKET_DESC_WORDS - TD_DEPS;
+std::vector<int32_t> ticket_descriptors(const std::vector<int32_t>& tk_launch, const std::vector<int32_t>& tk_block, const std::vector<int32_t>& dep_off,
+                                        const std::vector<int32_t>& dep, int cap = TICKET_DESC_INLINE);
+// hist[c] = tickets with c dependencies (the last entry: that many or more)
+std::vector<int64_t> ticket_dep_histogram(const std::vector<int32_t>& dep_off, int max_count);
 
 }  // namespace lpmp
