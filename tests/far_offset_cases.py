@@ -171,6 +171,11 @@ def _diff_shift_mixed():
     return DS.mixed_graph(np.random.default_rng(311))       # DIFF_SHIFT beside DIFF, SHARED, DENSE and POTTS peers
 
 
+def _diff_shift_band(L):
+    import diff_shift_band_cases as DB
+    return DB.label_grid(L, "colour_major")     # every vector with constant tails inside the rule: every shifted launch is banded
+
+
 def _pq_mixed_sides():
     import peer_minima_cases as PQ
     return PQ.case(PQ_MIXED_SIDES).model()
@@ -224,18 +229,175 @@ LIVE = {
     # tests/test_far_offsets_host.py: these classes have no packets, which a class set named here would make the probe test ask for)
     "labeling_nl_small": (lambda: _labeling(LABELING_NL["labeling_nl_small"]), None),
     "labeling_nl_generic": (lambda: _labeling(LABELING_NL["labeling_nl_generic"]), None),
+    "diff_shift_band40": (lambda: _diff_shift_band(40), {"diff"}),
+    "diff_shift_band130": (lambda: _diff_shift_band(130), {"diff"}),        # more than 128 labels: the LDS-bound occupancy branch
+    # the smallest grid of the skewed tiled order's near tests (tests/test_pq_ahead_gpu.py "24x24", tests/test_pq_tiles_gpu.py)
+    "skew_dense32": (lambda: S.grid_model(24, 24, 32, order="colour_major", seed=9100 + 24 * 24), {"dense32"}),
 }
+DIFF_SHIFT_BAND_MODELS = ("diff_shift_band40", "diff_shift_band130")
 DIFF_SHIFT_MODELS = ("diff_shift40", "diff_shift130", "diff_shift_mixed")
 # the first three families of the issue's table: placement P32 as well
 P32_MODELS = ("dense32", "dense8", "dense4", "dense_v21", "dense_v5", "potts16", "potts_v5", "big48", "big130")
 
 
+def _shift24():
+    import primal_state_cases as PS
+    return PS.shift_model(PS.SHIFT_KEYS[0])
+
+
+# live models that no sweep test runs (they are in none of the host module's lists over LIVE): the DIFF_SHIFT model of the label write-in
+EXTRA = {"primal_shift24": _shift24}
+
+
 @functools.lru_cache(maxsize=None)
 def live(name):
     """built once per process and never modified"""
-    return LIVE[name][0]()
+    return (LIVE[name][0] if name in LIVE else EXTRA[name])()
 
 
 def oracle_model(m):
     """what the unchanged CPU oracle runs: DIFF and SHARED factors expanded to private tables"""
     return m.expand_diff().expand_shared()
+
+
+# ---- path and forest moves: live models that come with their groups -----------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Relabel:
+    """``make()`` -> (model, groups); upload keywords; passes before the move (0: random duals of seed ``duals``, written into the
+    borrowed tail); the seed of the starting labelling"""
+    make: object
+    kw: tuple = ()
+    passes: int = 2
+    duals: int = 0
+    start: int = 7
+
+
+def _paths(name, *a, **kw):
+    import path_moves_cases as PM
+    return lambda: getattr(PM, name)(*a, **kw)
+
+
+def _forest(name, *a, **kw):
+    import forest_moves_cases as FM
+    return lambda: getattr(FM, name)(*a, **kw)
+
+
+def _thinned():
+    import forest_moves_cases as FM
+    from lp_mp_amd import engine as E
+    m = FM.thinned_grid()
+    return m, E.Plan(m).suggest_forests()
+
+
+F32 = (("table_precision", "f32"),)
+T7 = (-1, 0, 0, 1, 1, 1, 2)                     # forest_moves_cases.TREE7
+PATH_CASES = {
+    "dense13": Relabel(_paths("ladder", (13, 13, 13, 13), "dense", seed=3)),                  # f64 tables, both sides of an edge, the wave form
+    "dense_f32": Relabel(_paths("ladder", (13, 9, 13, 9), "dense_f32", seed=4), kw=F32),     # pw_cost's float branch
+    "mixed": Relabel(_paths("mixed_path_case")),          # dense, Potts, SHARED, DIFF, banded DIFF as path edges and as off-path lines
+    "diff_shift": Relabel(_paths("diff_shift_case")),     # the four-word cell
+    "rect_both_forms": Relabel(_paths("rect_case"), passes=0, duals=1015),                   # both forms, both back-pointer widths
+    "length300": Relabel(_paths("long_case")),            # PathRec::node_begin and the back-pointer walk over 300 far nodes
+}
+FOREST_CASES = {
+    "tree": Relabel(_forest("tree_model")),               # TREE7, dense, mixed sides
+    "rect": Relabel(_forest("rect_case"), passes=0, duals=1026),
+    "fan40": Relabel(_forest("fan_case", 40)),            # the largest fan of tests/test_forest_moves_gpu.py
+    "diff_shift": Relabel(_forest("diff_shift_tree")),
+    "thinned_grid": Relabel(_thinned),                    # the suggested cover of a grid with parallel edges and isolated unaries
+    "potts": Relabel(_forest("tree_model", T7, (13,) * 7, "potts", seed=6)),
+    "shared": Relabel(_forest("tree_model", T7, (13, 7, 13, 7, 13, 7, 13), "shared", seed=7)),
+    "diff": Relabel(_forest("tree_model", T7, (40, 33, 40, 33, 40, 33, 40), "diff", seed=8)),
+    "dense_f32": Relabel(_forest("tree_model", T7, (13, 9, 13, 9, 13, 9, 5), "dense_f32", seed=4), kw=F32),
+}
+RELABEL = {"path": PATH_CASES, "forest": FOREST_CASES}
+RELABEL_ROUNDS = 2
+P32_RELABEL = {"path": ("dense13", "mixed"), "forest": ("tree", "diff_shift")}
+
+
+@functools.lru_cache(maxsize=None)
+def relabel_case(kind, name):
+    """(model, groups, the model the device computes on: float tables rounded); built once per process and never modified"""
+    c = RELABEL[kind][name]
+    m, groups = c.make()
+    return m, groups, (m.with_f32_tables() if c.kw else m)
+
+
+def relabel_start(kind, name):
+    import path_moves_cases as PM
+    return PM.random_primal(relabel_case(kind, name)[0], RELABEL[kind][name].start)
+
+
+def relabel_random_duals(kind, name):
+    c = RELABEL[kind][name]
+    return None if c.passes else np.random.default_rng(c.duals).random(relabel_case(kind, name)[0].dual_data.shape[0])
+
+
+def relabel_reference(kind, name, duals, start, trace=None):
+    import forest_moves_cases as FM
+    import path_moves_cases as PM
+    _, groups, ref = relabel_case(kind, name)
+    fn = PM.path_moves_reference if kind == "path" else FM.forest_moves_reference
+    return fn(ref, duals, start, groups, rounds=RELABEL_ROUNDS, trace=trace)
+
+
+def relabel_members(kind, groups):
+    if kind == "path":
+        return sorted({int(u) for g in groups for p in g for u in p})
+    return sorted({int(u) for un, _ in groups for u in un})
+
+
+def far_groups(kind, groups, n_pad):
+    """the groups of the small model with n_pad added to every member (a root's parent stays -1)"""
+    if kind == "path":
+        return [[[int(u) + n_pad for u in p] for p in g] for g in groups]
+    return [(np.asarray(un, np.int32) + np.int32(n_pad), np.where(np.asarray(par) == -1, -1, np.asarray(par) + n_pad).astype(np.int32)) for un, par in groups]
+
+
+# ---- carried labels: the four moves of the far window tests, each with the labelling it starts from ---------------------------
+CARRY_MODELS = ("diff_shift40", "diff_shift130")
+
+
+def window_moves(name):
+    """(unaries, longest window, [(deltas, with costs, from device memory, labels)]): the moves of the far window test of
+    tests/test_far_offsets_gpu.py — deltas with 0, +-1, 63, -64, L - 1, -L and L + 7 —, and per move a random labelling of the
+    small model with every sixth unary unset"""
+    import move_windows_cases as MW
+    import primal_state_cases as PS
+    m = live(name)
+    us = MW.unaries(m)
+    L = int(m.f_dim0[us].max())
+    delta = MW.deltas(m.f_dim0[us], L)
+    moves = ((delta, False, False), (-delta, False, True), (delta[::-1].copy(), True, False), (-delta[::-1], True, True))
+    return us, L, [(dl, costs, dev, PS.random_primal(m, 40 + k, unset_every=6)) for k, (dl, costs, dev) in enumerate(moves)]
+
+
+def checkerboard_moves(name):
+    """two more moves, there (host) and back (device memory), that keep a model with a +inf-tailed vector feasible: one colour of
+    the graph's two-colouring moves by one label, so that the shift of EVERY DIFF_SHIFT cell changes by +-1 — inside the band that
+    diff_shift_band_cases.feasible_shift keeps on the diagonal"""
+    import move_windows_cases as MW
+    m = live(name)
+    us = MW.unaries(m)
+    ends = {}
+    for k in range(m.n_messages):
+        ends.setdefault(int(m.m_right[k]), []).append(int(m.m_left[k]))
+    adj = {int(u): [] for u in us}
+    for a, b in ends.values():
+        adj[a].append(b); adj[b].append(a)
+    colour, stack = {int(us[0]): 0}, [int(us[0])]
+    while stack:
+        v = stack.pop()
+        for w in adj[v]:
+            if w not in colour:
+                colour[w] = 1 - colour[v]
+                stack.append(w)
+            assert colour[w] != colour[v], "not two-colourable"
+    assert len(colour) == len(us), "not connected"
+    delta = np.asarray([colour[int(u)] for u in us], np.int64)
+    return [(delta, False, False, None), (-delta, False, True, None)]
+
+
+# ---- the scalars in device memory: the models of the list-bound procedure -----------------------------------------------------
+SCALAR_MODELS = ("dense8", "diff40", "mixed_graph")
+SET_LABEL_MODELS = ("primal_dense8", "primal_shift24")

@@ -14,6 +14,7 @@ Tolerances are those of tests/test_diff_tables_gpu.py.  The kernel class is asse
 hands out the right offsets is tests/test_far_offsets_host.py; this module is about the kernels' index arithmetic."""
 import dataclasses
 import json
+import re
 
 import numpy as np
 import pytest
@@ -25,38 +26,13 @@ from oracle.binding import Oracle
 
 import far_offset_cases as F
 import recost_cases as RC
+from far_offset_gpu import (FLB_ATOL, LB_RTOL, SENTINEL_I32, Far, _buffers, _check_labels, _mem, _note, _release, _restart_oracle,  # noqa: F401
+                            _sample_memory, _timed)
 
 pytestmark = pytest.mark.gpu
 
-LB_RTOL = 1e-5
-FLB_ATOL = 1e-12
 ANISO, UNIFORM = M.REPAM_ANISOTROPIC, M.REPAM_UNIFORM
 MODES = (ANISO, UNIFORM)
-SLACK = 8 * F.GIB
-_mem = {"free0": None, "min_free": None, "ran": set(), "kernels": {}}
-
-
-def _sample_memory():
-    import torch
-    free = torch.cuda.mem_get_info()[0]
-    if _mem["free0"] is None:
-        _mem["free0"] = free
-    _mem["min_free"] = free if _mem["min_free"] is None else min(_mem["min_free"], free)
-
-
-def _buffers(placement, kind="dense"):
-    import torch
-    _sample_memory()
-    need, free = F.FarBuffers.bytes_needed(placement, kind), torch.cuda.mem_get_info()[0]
-    if free < need + SLACK:
-        pytest.skip("placement %s (%s padding) needs %.1f GiB + 8 GiB, the device reports %.1f GiB free" % (placement, kind, need / F.GIB, free / F.GIB))
-    return F.FarBuffers(placement, kind)
-
-
-def _release(b):
-    import torch
-    b.const = b.dual = None
-    torch.cuda.empty_cache()
 
 
 @pytest.fixture(scope="module")
@@ -87,98 +63,6 @@ def p31_vector():
 def _memory_after_every_test():
     yield
     _sample_memory()
-
-
-class Far:
-    """an engine on pad_front(m) over the borrowed buffers, and the oracle on the small model"""
-
-    def __init__(self, bufs, m, mode, oracle_of=F.oracle_model, const=None, dual=None, **upload_kw):
-        self.bufs, self.m, self.n_pad = bufs, m, bufs.n_pad
-        self.far = F.pad_front(m, bufs.n_pad, bufs.kind)
-        assert int(self.far.const_offsets()[self.n_pad]) == bufs.pad_c and int(self.far.dual_offsets()[self.n_pad]) == bufs.pad_d
-        assert bufs.pad_d >= 2**31 and (bufs.kind == "vector" or bufs.pad_c >= 2**31)
-        cp, dp = bufs.load(m, const, dual)
-        assert bufs.dual_padding_nonzero() == 0
-        self.o = None                        # (oracle_of=None: the caller compares with a trajectory computed once)
-        if oracle_of is not None:
-            self.o = Oracle(oracle_of(m)); self.o.set_reparametrization(mode)
-        self.e = E.Engine(0)
-        try:
-            self.e.upload(self.far, const_dev=cp, dual_dev=dp, keep=(bufs.const, bufs.dual), **upload_kw)
-            self.e.set_reparametrization(mode)
-        except BaseException:
-            self.e.close()
-            raise
-        self.mode = mode
-        _mem["ran"].add(bufs.placement + " " + bufs.kind)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        _sample_memory()
-        self.e.close()
-        self.bufs.reset()                    # the used tails go back to zero after every engine
-
-    def classes(self, only=None, some=None):
-        """asserted BEFORE anything runs, so that a fallback cannot stand in"""
-        for d in (0, 1):
-            c = self.e.plan.schedule_classes(d, self.mode)
-            if only is not None:
-                assert set(c) == set(only), (c, only)
-            if some is not None and d == 1:
-                assert set(c) & set(some), (c, some)
-
-    def bound(self, what=""):
-        lb, lbo = self.e.lower_bound(), self.o.LowerBound()
-        assert np.isfinite(lb) and abs(lb - lbo) <= LB_RTOL * max(1.0, abs(lbo)), (what, lb, lbo)
-
-    def duals(self, what=""):
-        """the tail of the borrowed buffer against the oracle; never download_duals()"""
-        self.e.synchronize()
-        d, do = self.bufs.dual_tail(), self.o.duals()
-        assert not np.any(np.isnan(d)), what
-        assert np.array_equal(d, do), (what, float(np.max(np.abs(d - do))))
-        return d
-
-    def factor_bounds(self, what=""):
-        flb = self.e.factor_lower_bounds()
-        assert flb.shape[0] == self.far.n_factors
-        assert np.all(flb[:self.n_pad] == 0.0), what
-        ref = np.array([self.o.factor_lower_bound(f) for f in range(self.m.n_factors)])
-        assert np.max(np.abs(flb[self.n_pad:] - ref)) <= FLB_ATOL, (what, float(np.max(np.abs(flb[self.n_pad:] - ref))))
-
-    def padding_untouched(self, const_tail=True):
-        self.e.synchronize()
-        assert self.bufs.dual_padding_nonzero() == 0
-        assert self.bufs.const_padding_nonzero() == 0
-        if const_tail:
-            assert np.array_equal(self.bufs.const_tail(), self.m.const_data)     # the constants are read-only
-
-    def timed_passes(self, n, family):
-        self.e.enable_kernel_timing(True); self.e.reset_kernel_timing()
-        self.e.compute_pass(n); self.o.ComputePass(n)
-        kt = self.e.kernel_timing()
-        self.e.enable_kernel_timing(False)
-        names = sorted(v["kernel"] for v in kt.values())
-        _mem["kernels"].setdefault(family, [])
-        for k in names:
-            if k not in _mem["kernels"][family]:
-                _mem["kernels"][family].append(k)
-        return kt
-
-    def standard(self, family):
-        """3 single passes with the bound after each, then compute_pass(2) (timed: the kernel that ran), duals, per-factor bounds"""
-        self.bound("upload")
-        for k in range(3):
-            self.e.compute_pass(1); self.o.ComputePass(1)
-            self.bound(k)
-        kt = self.timed_passes(2, family)
-        self.bound("after 2 more")
-        self.duals()
-        self.factor_bounds()
-        self.padding_untouched()
-        return kt
 
 
 def _run(bufs, name, family, only=None, some=None, modes=MODES, kernel=None, **kw):
@@ -590,33 +474,10 @@ def test_halo_and_boundary_kernels(p31, name):
 # Each family is a function over the buffers of a placement: the P31 tests below and the methods of TestP32 call the same one.
 UNSUPPORTED = -2
 SENTINEL = np.array([0x7FF8DEAD0000BEEF], np.uint64).view(np.float64)[0]      # a NaN with a payload (tests/test_readout_gpu.py)
-SENTINEL_I32 = np.int32(-0x5EADBEF)
-
-
-def _note(family, *kernels):
-    """kernels that kernel_timing does not name, for the closing printout"""
-    have = _mem["kernels"].setdefault(family, [])
-    have += [k for k in kernels if k not in have]
 
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def _timed(x, call, family):
-    x.e.enable_kernel_timing(True); x.e.reset_kernel_timing()
-    call()
-    kt = x.e.kernel_timing()
-    x.e.enable_kernel_timing(False)
-    _note(family, *sorted(v["kernel"] for v in kt.values()))
-    return kt
-
-
-def _restart_oracle(x, m, duals):
-    """the oracle again, on model ``m`` (same structure) with the packed ``duals``: after a call that changed constants or moved duals"""
-    x.m = m
-    x.o = Oracle(dataclasses.replace(F.oracle_model(m), dual_data=np.array(duals, np.float64, copy=True), _keep=[]))
-    x.o.set_reparametrization(x.mode)
 
 
 # ---- shifted difference-indexed factors -------------------------------------------------------------------------------------
@@ -646,13 +507,25 @@ def test_diff_shift_sweep(p31, name):
 
 
 # ---- joined passes in every form --------------------------------------------------------------------------------------------
-PQ_KEYS = ("LPMP_PQ_WIDE", "LPMP_PQ_LDS", "LPMP_PQ_HOLD", "LPMP_PQ_SCATTER", "LPMP_NO_PEER_MINIMA")
+PQ_KEYS = ("LPMP_PQ_WIDE", "LPMP_PQ_LDS", "LPMP_PQ_HOLD", "LPMP_PQ_SCATTER", "LPMP_NO_PEER_MINIMA", "LPMP_PQ_AHEAD", "LPMP_PQ_DESC_INLINE")
 # name -> (environment of the engine, whether its joined passes run in the peer-minima form)
 PQ_ENGINES = {"default": ({}, True), "wide0": ({"LPMP_PQ_WIDE": "0"}, True), "lds0": ({"LPMP_PQ_LDS": "0"}, True), "hold2": ({"LPMP_PQ_HOLD": "2"}, True),
-              "scatter0": ({"LPMP_PQ_SCATTER": "0"}, True), "no_peer_minima": ({"LPMP_NO_PEER_MINIMA": "1"}, False)}
+              "scatter0": ({"LPMP_PQ_SCATTER": "0"}, True), "no_peer_minima": ({"LPMP_NO_PEER_MINIMA": "1"}, False),
+              "ahead0": ({"LPMP_PQ_AHEAD": "0"}, True), "inline0": ({"LPMP_PQ_DESC_INLINE": "0"}, True)}
+# the ticket form the verbose line of a peer-minima launch must name: tickets ahead (chain_dense_pq_ahead_kernel) is the default form
+# and has no other switch turned; every other peer-minima form keeps the plain loop (kernels.hpp, pq_ahead_applies)
+PQ_TICKETS = {"default": "ahead", "inline0": "ahead", "ahead0": "plain", "wide0": "plain", "hold2": "plain", "lds0": "plain", "scatter0": "plain"}
+PQ_TICKET_LINE = re.compile(r"lpmp:   peer minima launch; tickets: (ahead|plain)")
+PQ_LAUNCH_LINE = re.compile(r"lpmp: \d+ passes as one launch( \([a-z ,]+\))?: \d+ tickets")
 PQ_PASSES = (1, 2, 9, 33)                    # explicit lists, the periodic template, a slice of 32 + 1
 JOINED_WINDOW = (8, 2, 4)                    # bands : lag : depth, as tests/test_peer_minima_shapes_gpu.py runs both models
 JOINED_KERNEL = "chain_dense_pk_kernel<32, 2, false, false>"          # the class's name in the timing, whichever form ran
+# the skewed tiled order at test size (tests/test_pq_ahead_gpu.py SKEW, on its 24 x 24 grid of 32 labels)
+SKEW = {"LPMP_ROT_BANDS": "8", "LPMP_ROT_LAG": "2", "LPMP_PQ_TILES": "4", "LPMP_PQ_SUB": "3", "LPMP_PQ_SUBLAG": "2", "LPMP_PQ_SUBGAP": "2"}
+SKEW_KEYS = ("LPMP_ROT_BANDS", "LPMP_ROT_LAG", "LPMP_ROT_DEPTH", "LPMP_ROT_TILES", "LPMP_PQ_TILES", "LPMP_PQ_SUB", "LPMP_PQ_SUBLAG", "LPMP_PQ_SUBGAP",
+             "LPMP_PQ_MIN_PASSES", "LPMP_CHAIN_MAX_WGS")
+SKEW_CALLS = (20, 8)
+SKEW_MIN_PASSES = 12                         # the shipped threshold (tests/test_pq_tiles_gpu.py)
 _TRAJECTORY = {}
 
 
@@ -664,53 +537,101 @@ def _pq_env(monkeypatch, env):
         monkeypatch.setenv(k, v)
 
 
-def _joined_trajectory(name):
-    """the oracle on the small model over PQ_PASSES, computed once and left unchanged: (duals, bound) after every call, the factors'
+def _joined_trajectory(name, calls=PQ_PASSES):
+    """the oracle on the small model over ``calls``, computed once and left unchanged: (duals, bound) after every call, the factors'
     bounds at the end (the form of a launch changes nothing in what it computes)"""
-    if name not in _TRAJECTORY:
+    if (name, calls) not in _TRAJECTORY:
         m = F.live(name)
         o = Oracle(m); o.set_reparametrization(ANISO)
         steps = []
-        for n in PQ_PASSES:
+        for n in calls:
             o.ComputePass(n)
             d = o.duals().copy(); d.setflags(write=False)
             steps.append((d, o.LowerBound()))
         flb = np.array([o.factor_lower_bound(f) for f in range(m.n_factors)]); flb.setflags(write=False)
-        _TRAJECTORY[name] = (steps, flb)
-    return _TRAJECTORY[name]
+        _TRAJECTORY[(name, calls)] = (steps, flb)
+    return _TRAJECTORY[(name, calls)]
 
 
-def _joined_passes(bufs, name, engine, monkeypatch):
+def _joined_calls(x, bufs, engine, pq, calls, steps, flb, capfd, order=None):
+    """the calls on one far engine against the trajectory; returns the duals after every call.  The verbose lines of the launches
+    built on the way name the ticket form (and the order, where ``order`` is asked for): a fallback cannot stand in"""
+    forms, orders, out = [], [], []
+    for n, (duals, bound) in zip(calls, steps):
+        capfd.readouterr()
+        kt = _timed(x, lambda: x.e.compute_pass(n), "joined passes, " + engine)
+        err = capfd.readouterr().err
+        forms += PQ_TICKET_LINE.findall(err)
+        orders.append((n, PQ_LAUNCH_LINE.findall(err)))
+        (v,) = kt.values()
+        assert v["kernel"] == JOINED_KERNEL and v["chain_launches"] == (n + 31) // 32, (engine, n, kt)
+        assert v["peer_minima_launches"] == (v["chain_launches"] if pq else 0), (engine, n, kt)
+        _note("joined passes, " + engine, "peer-minima launches: %s" % ("all" if pq else "none"))
+        x.e.synchronize()
+        d = bufs.dual_tail()
+        assert np.array_equal(d, duals), (engine, n, float(np.max(np.abs(d - duals))))
+        lb = x.e.lower_bound()
+        assert np.isfinite(lb) and abs(lb - bound) <= LB_RTOL * max(1.0, abs(bound)), (engine, n, lb, bound)
+        out.append((d, lb))
+    got = x.e.factor_lower_bounds()
+    assert np.all(got[:x.n_pad] == 0.0) and np.max(np.abs(got[x.n_pad:] - flb)) <= FLB_ATOL, engine
+    x.padding_untouched()
+    want = PQ_TICKETS.get(engine)
+    print("joined passes, %s: ticket forms of the launches built: %s%s" % (engine, forms, orders if order else ""))
+    if pq:
+        assert forms and set(forms) == {want}, (engine, forms, want)
+        _note("joined passes, " + engine, "tickets: %s (%s)" % (want, "chain_dense_pq_ahead_kernel" if want == "ahead" else "the plain ticket loop"))
+    else:
+        assert not forms, (engine, forms)
+    if order:      # calls of at least SKEW_MIN_PASSES passes take the order; a shorter call builds its template in the band order
+        long = [o for n, built in orders if n >= SKEW_MIN_PASSES for o in built]
+        assert long and all(order in o and "periodic template" in o for o in long), (engine, orders)
+        _note("joined passes, " + engine, "periodic template, " + order)
+    return out
+
+
+def _joined_passes(bufs, name, engine, monkeypatch, capfd):
     env, pq = PQ_ENGINES[engine]
     _pq_env(monkeypatch, env)
     for k, v in zip(("LPMP_ROT_BANDS", "LPMP_ROT_LAG", "LPMP_ROT_DEPTH"), JOINED_WINDOW):
         monkeypatch.setenv(k, str(v))
+    monkeypatch.setenv("LPMP_ROT_VERBOSE", "1")
     steps, flb = _joined_trajectory(name)
     with Far(bufs, F.live(name), ANISO, oracle_of=None) as x:
         x.classes({"dense32"})
         assert x.e.plan.pass_rotates(ANISO) and x.e.plan.peer_minima(ANISO) == (True, "")
-        for n, (duals, bound) in zip(PQ_PASSES, steps):
-            kt = _timed(x, lambda: x.e.compute_pass(n), "joined passes, " + engine)
-            (v,) = kt.values()
-            assert v["kernel"] == JOINED_KERNEL and v["chain_launches"] == (n + 31) // 32, (engine, n, kt)
-            assert v["peer_minima_launches"] == (v["chain_launches"] if pq else 0), (engine, n, kt)
-            _note("joined passes, " + engine, "peer-minima launches: %s" % ("all" if pq else "none"))
-            x.e.synchronize()
-            d = bufs.dual_tail()
-            assert np.array_equal(d, duals), (engine, n, float(np.max(np.abs(d - duals))))
-            lb = x.e.lower_bound()
-            assert np.isfinite(lb) and abs(lb - bound) <= LB_RTOL * max(1.0, abs(bound)), (engine, n, lb, bound)
-        got = x.e.factor_lower_bounds()
-        assert np.all(got[:x.n_pad] == 0.0) and np.max(np.abs(got[x.n_pad:] - flb)) <= FLB_ATOL, engine
-        x.padding_untouched()
+        _joined_calls(x, bufs, engine, pq, PQ_PASSES, steps, flb, capfd)
 
 
 @pytest.mark.parametrize("engine", list(PQ_ENGINES))
 @pytest.mark.parametrize("name", ["joined_dense32", "pq_mixed_sides"])
-def test_joined_passes_in_every_form(p31, name, engine, monkeypatch):
-    """peer minima as it is by default, with each of its four switches turned, and the joined form it replaced (what float tables, the
-    rows layout and LPMP_NO_PEER_MINIMA run): which form ran is read from the engine's counter"""
-    _joined_passes(p31, name, engine, monkeypatch)
+def test_joined_passes_in_every_form(p31, name, engine, monkeypatch, capfd):
+    """peer minima as it is by default (tickets ahead), with each of its switches turned — the plain ticket loop, every dependency
+    through dep[] — and the joined form it replaced (what float tables, the rows layout and LPMP_NO_PEER_MINIMA run): which form ran
+    is read from the engine's counter, which tickets from the verbose line of every launch built"""
+    _joined_passes(p31, name, engine, monkeypatch, capfd)
+
+
+def test_joined_passes_in_the_skewed_tiled_order(p31, monkeypatch, capfd):
+    """the skewed tiled order with its periodic template and flag ring, tickets ahead and LPMP_PQ_AHEAD=0 side by side on calls of 20
+    and 8 passes: duals bit-equal to the oracle's trajectory and between the two engines, bounds as in every joined test"""
+    name = "skew_dense32"
+    steps, flb = _joined_trajectory(name, SKEW_CALLS)
+    got = {}
+    for engine in ("default", "ahead0"):
+        env, pq = PQ_ENGINES[engine]
+        _pq_env(monkeypatch, env)
+        for k in SKEW_KEYS:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in SKEW.items():
+            monkeypatch.setenv(k, v)
+        monkeypatch.setenv("LPMP_ROT_VERBOSE", "1")
+        with Far(p31, F.live(name), ANISO, oracle_of=None) as x:
+            x.classes({"dense32"})
+            assert x.e.plan.pass_rotates(ANISO) and x.e.plan.peer_minima(ANISO) == (True, "")
+            got[engine] = _joined_calls(x, p31, engine, pq, SKEW_CALLS, steps, flb, capfd, order="skewed tiled order")
+    for (da, la), (db, lb) in zip(got["default"], got["ahead0"]):
+        assert np.array_equal(da, db) and la == lb, (la, lb)
 
 
 # ---- listed constants and the pool ------------------------------------------------------------------------------------------
@@ -847,17 +768,6 @@ def _check_rows(got_dev, want, what):
     assert np.array_equal(got_dev[:n][written], want[written]), what
     assert np.all(_bits(got_dev[:n][~written]) == _bits(SENTINEL)), what
     assert np.all(_bits(got_dev[n]) == _bits(SENTINEL)), what
-
-
-def _check_labels(x, r, want, what):
-    import torch
-    assert np.array_equal(r.labels(), want), what
-    t = torch.from_numpy(np.full(r.n + 1, SENTINEL_I32, np.int32)).cuda()
-    torch.cuda.synchronize()
-    assert r.labels(t.data_ptr()) is None
-    x.e.synchronize()
-    got = t.cpu().numpy()
-    assert np.array_equal(got[:r.n], want) and got[r.n] == SENTINEL_I32, what
 
 
 def _readouts(bufs, name, family):
@@ -1047,9 +957,9 @@ class TestP32:
         assert p32.pad_c >= 2**32 and p32.pad_d >= 2**32
         _diff_shift_sweep(p32, "diff_shift40", "P32 diff shift")
 
-    @pytest.mark.parametrize("engine", ["default", "no_peer_minima"])
-    def test_joined_passes_with_and_without_peer_minima(self, p32, engine, monkeypatch):
-        _joined_passes(p32, "joined_dense32", engine, monkeypatch)
+    @pytest.mark.parametrize("engine", ["default", "no_peer_minima", "ahead0"])
+    def test_joined_passes_with_and_without_peer_minima(self, p32, engine, monkeypatch, capfd):
+        _joined_passes(p32, "joined_dense32", engine, monkeypatch, capfd)
 
     @pytest.mark.parametrize("name", list(READOUT_MODELS))
     def test_readouts(self, p32, name):

@@ -163,7 +163,8 @@ def test_far_schedule_is_the_small_schedule_moved_by_the_padding(probe_lib, name
 
 
 # ---- the models added for the kernels that came after the first far-offset tests ---------------------------------------------
-NEW_MODELS = F.DIFF_SHIFT_MODELS + ("pq_mixed_sides",) + tuple(F.LABELING_NL)
+SMALL_NEW_MODELS = F.DIFF_SHIFT_MODELS + ("pq_mixed_sides",) + tuple(F.LABELING_NL)
+NEW_MODELS = SMALL_NEW_MODELS + F.DIFF_SHIFT_BAND_MODELS + ("skew_dense32",)
 DECODE_MODELS = ("dense8", "dense_v21", "big130", "shared32", "diff_shift40")
 ERR_UNSUPPORTED = -2
 
@@ -173,9 +174,26 @@ def test_new_models_are_what_the_gpu_tests_take_them_for():
     the level loop the two labeling models reach — on the SMALL plans; the far plans equal them in the test below"""
     import labeling_cases as LC
     ANISO = M.REPAM_ANISOTROPIC
-    for name in NEW_MODELS:
+    for name in SMALL_NEW_MODELS:
         m = F.live(name)
         assert int(m.const_sizes().sum()) <= 270_000 and m.dual_data.shape[0] <= 66_000, name
+    # the banded DIFF_SHIFT grids: every vector inside the rule (the numpy statement), every shifted launch of the plan banded, and
+    # the second with more than 128 labels (the LDS-bound occupancy branch of the banded kernel)
+    import diff_shift_band_cases as DB
+    for name, L in (("diff_shift_band40", 40), ("diff_shift_band130", 130)):
+        m = F.live(name)
+        assert set(m.f_kind.tolist()) == {M.F_VECTOR, M.F_PAIRWISE_DIFF_SHIFT} and set(m.f_dim0[m.f_kind == M.F_VECTOR].tolist()) == {L}
+        assert DB.banded(m), name
+        p = E.Plan(m)
+        for mode in (M.REPAM_ANISOTROPIC, M.REPAM_UNIFORM):
+            for d in (0, 1):
+                i = p.diff_shift_band_info(d, mode)
+                assert i["shift_band_launches"] == i["shift_launches"] > 0, (name, mode, d, i)
+    # the grid of the skewed tiled order: 24 x 24 of 32 labels, joined passes in the peer-minima form
+    m = F.live("skew_dense32")
+    assert int((m.f_kind == M.F_VECTOR).sum()) == 24 * 24 and set(m.f_dim0.tolist()) == {32} and set(m.f_dim1[m.f_kind != M.F_VECTOR].tolist()) == {32}
+    p = E.Plan(m)
+    assert p.pass_rotates(ANISO) and p.peer_minima(ANISO) == (True, "")
     for name, L in (("diff_shift40", 40), ("diff_shift130", 130)):
         m = F.live(name)
         assert set(m.f_kind.tolist()) == {M.F_VECTOR, M.F_PAIRWISE_DIFF_SHIFT} and set(m.f_dim0[m.f_kind == M.F_VECTOR].tolist()) == {L}
@@ -209,6 +227,7 @@ def test_new_models_plan_alike_behind_the_padding(name, placement):
         for d in (0, 1):
             assert a.schedule_classes(d, mode) == b.schedule_classes(d, mode), (mode, d)
             assert a.diff_band_info(d, mode) == b.diff_band_info(d, mode), (mode, d)
+            assert a.diff_shift_band_info(d, mode) == b.diff_shift_band_info(d, mode), (mode, d)
         assert a.pass_rotates(mode) == b.pass_rotates(mode), mode
         assert a.peer_minima(mode) == b.peer_minima(mode), mode
         assert a.pass_schedule_info(mode) == b.pass_schedule_info(mode), mode
@@ -239,3 +258,140 @@ def test_decode_plan_behind_vector_padding(name, placement):
     with pytest.raises(E.EngineError) as ei:
         E.Plan(F.pad_front(m, n_pad, "dense")).decode_info(0)
     assert ei.value.code == ERR_UNSUPPORTED and "factor 0 " in str(ei.value) and "no unary" in str(ei.value), str(ei.value)
+
+
+# ---- path and forest moves, the primal state: the plans behind the padding, and conditions on the inputs -------------------------
+RELABEL_CASES = [(kind, name) for kind in F.RELABEL for name in F.RELABEL[kind]]
+ANISO = M.REPAM_ANISOTROPIC
+
+
+@pytest.mark.parametrize("placement", PLACEMENTS)
+@pytest.mark.parametrize("kind,name", RELABEL_CASES)
+def test_relabel_plans_alike_behind_the_padding(kind, name, placement):
+    """lpmp_plan_path_info / lpmp_plan_forest_info: the far plan accepts the groups shifted by the padding and counts what the small
+    plan counts — paths, path edges and off-path links; trees, tree edges, off-tree links and the greatest height"""
+    m, groups, _ = F.relabel_case(kind, name)
+    n_pad = F.N_PAD[placement]
+    kw = dict(F.RELABEL[kind][name].kw)
+    a, b = E.Plan(m, **kw), E.Plan(F.pad_front(m, n_pad, "dense"), **kw)
+    far = F.far_groups(kind, groups, n_pad)
+    assert F.relabel_members(kind, far) == [u + n_pad for u in F.relabel_members(kind, groups)] and min(F.relabel_members(kind, far)) >= n_pad
+    if kind == "path":
+        ia, ib = a.path_info(groups), b.path_info(far)
+        assert ia == ib and ia["n_paths"] == sum(len(g) for g in groups) > 0 and ia["n_path_edges"] == sum(len(p) - 1 for g in groups for p in g), (ia, ib)
+        assert ia["n_off_path_links"] > 0, ia
+    else:
+        ia, ib = a.forest_info(groups), b.forest_info(far)
+        assert ia == ib and ia["n_trees"] == sum(int((np.asarray(par) == -1).sum()) for _, par in groups) > 0, (ia, ib)
+        assert ia["n_tree_edges"] == sum(int((np.asarray(par) != -1).sum()) for _, par in groups) > 0 and ia["max_height"] > 0, ia
+        assert ia["n_off_tree_links"] > 0 or name == "thinned_grid", ia          # (the suggested cover of a graph: its groups decide)
+    with pytest.raises(E.EngineError):     # the groups as they are name padding factors in the far model: no unaries
+        (b.path_info if kind == "path" else b.forest_info)(groups)
+    if kind == "forest" and name in ("tree", "diff_shift"):
+        for (un, par), (fu, fp) in zip(groups, far):
+            assert np.array_equal(fu - n_pad, un) and np.array_equal(fp == -1, np.asarray(par) == -1)
+
+
+def _host_duals(kind, name):
+    """the duals a far GPU test of the case moves on: random ones, or those of the oracle's passes (the engine's, bit for bit: every
+    sweep test of the suite asserts it)"""
+    c = F.RELABEL[kind][name]
+    if not c.passes:
+        return F.relabel_random_duals(kind, name)
+    o = Oracle(F.oracle_model(F.relabel_case(kind, name)[2])); o.set_reparametrization(ANISO)
+    o.ComputePass(c.passes)
+    return o.duals().copy()
+
+
+@pytest.mark.parametrize("kind,name", RELABEL_CASES)
+def test_every_relabel_case_moves_a_label_in_its_first_round(kind, name):
+    """no far path or forest test can pass vacuously: from the starting labelling the reference changes the label of at least one
+    member within the first round (and the labelling it ends on differs from the start)"""
+    m, groups, _ = F.relabel_case(kind, name)
+    start = F.relabel_start(kind, name)
+    trace = []
+    want = F.relabel_reference(kind, name, _host_duals(kind, name), start, trace=trace)
+    assert len(trace) == F.RELABEL_ROUNDS * len(groups)
+    members = F.relabel_members(kind, groups)
+    first = trace[len(groups) - 1]
+    changed = int(np.sum(first[members, 0] != start[members, 0]))
+    print(kind, name, "labels changed in the first round:", changed, "of", len(members))
+    assert changed > 0 and not np.array_equal(want, start)
+
+
+@pytest.mark.parametrize("name", F.CARRY_MODELS)
+def test_carried_labels_clamp_somewhere_and_not_everywhere(name):
+    """every move of the far carry test: at least one set label leaves its window (it clamps), at least one stays inside, and at
+    least one listed unary is unset"""
+    m = F.live(name)
+    us, L, moves = F.window_moves(name)
+    d = m.f_dim0[us].astype(np.int64)
+    assert {0, 1, -1, 63, -64, L - 1, -L, L + 7} <= set(moves[0][0].tolist())
+    for k, (dl, _, _, labels) in enumerate(moves):
+        x = labels[us, 0].astype(np.int64)
+        is_set = x < d
+        moved = x - dl
+        clamped = is_set & ((moved < 0) | (moved > d - 1))
+        assert clamped.any() and (is_set & ~clamped).any() and (~is_set).any(), (name, k)
+        want = M.move_labels(labels, m, us, dl)
+        assert np.array_equal(want[us, 0][clamped], np.where(moved < 0, 0, d - 1)[clamped]) and np.array_equal(want[us, 0][~is_set], d[~is_set]), (name, k)
+
+
+def test_moves_on_the_banded_model_and_where_it_stays_feasible():
+    """diff_shift_band40 has a vector with +inf tails whose band sits on the diagonal.  The four moves of the far window test push it
+    off — no finite labelling is left until the windows are back —, so the GPU test compares the bound there and runs no pass; the
+    two checkerboard moves behind them change every shift word by one and keep the model feasible, duals finite after the passes.
+    The oracle alone, on ``model.move_windows``' models, without passes on an infeasible state — as the GPU test proceeds"""
+    import dataclasses
+    import move_windows_cases as MW
+    name = "diff_shift_band40"
+    m = F.live(name)
+    us, L, moves = F.window_moves(name)
+    more = F.checkerboard_moves(name)
+    cells = np.flatnonzero(m.f_kind == M.F_PAIRWISE_DIFF_SHIFT)
+    shifts = m.const_data[m.const_offsets()[cells] + 1]
+    inner = int((np.abs(shifts) < 2.0 ** 30).sum())                # (a shift at +-2^30 is clipped there: the "huge" placements)
+    assert 2 * inner > len(cells)
+    o = Oracle(F.oracle_model(m)); o.set_reparametrization(ANISO)
+    o.ComputePass(1); o.ComputePass(2)
+    d, cur, finite = o.duals().copy(), m, []
+    for k, (dl, costs, _, _) in enumerate(moves + more):
+        co, cn = MW.cost_pair(cur, us, dl, 12 + k, stride=L + 6) if costs else (None, None)
+        m2, d2 = M.move_windows(cur, d, us, dl, co, cn)
+        assert np.isfinite(d2).all(), k
+        changed = int((m2.const_data != cur.const_data).sum())
+        o = Oracle(dataclasses.replace(F.oracle_model(m2), dual_data=np.array(d2, np.float64, copy=True), _keep=[])); o.set_reparametrization(ANISO)
+        cur, d = m2, d2
+        finite.append(bool(np.isfinite(o.LowerBound())))
+        if finite[-1]:
+            o.ComputePass(2)
+            d = o.duals().copy()
+            assert np.isfinite(d).all() and np.isfinite(o.LowerBound()), k
+        if k >= len(moves):
+            assert finite[-1] and changed >= inner, (k, changed, inner)            # the shift word of every cell inside the clip is rewritten
+    print("moves after which the model has a finite labelling:", finite)
+    assert finite == [False, True, False, True, True, True]
+
+
+@pytest.mark.parametrize("name", F.SCALAR_MODELS)
+def test_the_send_only_pass_leaves_some_bounds_stale_and_not_all(name):
+    """the custom pass of the device-scalar tests: a send marks the tracked bound of its peer stale, so with at least one send-only
+    update at least one bound is stale, and the stale bounds lie among the neighbours of the updates kept — fewer than all factors
+    (how many exactly the GPU test reads from the engine's counter)"""
+    from test_far_offsets_gpu import send_only_updates
+    m = F.live(name)
+    o = Oracle(F.oracle_model(m)); o.set_reparametrization(ANISO)
+    factors = send_only_updates(o, ANISO)[0]
+    assert len(factors) > 0
+    kept = set(factors.tolist())
+    peers = {int(m.m_right[k]) for k in range(m.n_messages) if int(m.m_left[k]) in kept} | {int(m.m_left[k]) for k in range(m.n_messages) if int(m.m_right[k]) in kept}
+    assert 0 < len(peers) < m.n_factors, (name, len(peers), m.n_factors)
+
+
+def test_every_live_model_of_the_relabel_module_fits_the_tail():
+    models = [F.live(n) for n in F.DIFF_SHIFT_BAND_MODELS + ("skew_dense32",) + F.SET_LABEL_MODELS + F.CARRY_MODELS + F.SCALAR_MODELS]
+    models += [F.relabel_case(kind, name)[0] for kind, name in RELABEL_CASES]
+    largest = max(max(int(m.const_data.shape[0]), int(m.dual_data.shape[0])) for m in models)
+    print("largest live model: %d doubles of %d" % (largest, F.TAIL))
+    assert largest <= F.TAIL
+    assert set(F.SET_LABEL_MODELS) <= set(F.LIVE) | set(F.EXTRA) and F.live("primal_shift24").f_kind.tolist().count(M.F_PAIRWISE_DIFF_SHIFT) > 0
